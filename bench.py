@@ -16,8 +16,13 @@ the path has.  `python bench.py --gpus N` starts its own N rank
 this process touches the GPU); under torch.distributed.run it runs as a rank.  --in-library: ONE process, ONE handle with
 N replicas, host buffers through rbq_search_batch (the reference's batch_search binding).
 
-The timed region of exactly K steps (barrier + synchronize on both sides, max over ranks) is repeated until
---min-seconds (0.5 s) have been measured; `value` is the median region (`timed_regions`, `region_ms`).
+The timed region is exactly K = --steps steps (barrier + synchronize on both sides, max over ranks); `ms_per_step` is its
+duration / K.  With --min-seconds S > 0 the region is repeated until S seconds have been measured and `value` is the median
+region (`timed_regions`, `region_ms`).
+
+--dump-outputs DIR writes what the timed path returned in its last timed step (ids, scores, counts of that batch, as float64 /
+float32 .npy files) and the batch's queries.  Inputs are seeded and the harness k-means is deterministic, so two runs with the
+same arguments search the same index with the same queries and their dumps can be compared file by file.
 
 Prints one JSON line (rank 0).  What the objects mean:
   value / ms_per_step   whole path, queries and results resident in HBM, batches pipelined over --streams HIP streams
@@ -53,10 +58,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# The HIP runtime multiplexes a process's streams over 4 hardware queues by default; two of the batch streams on one
-# queue serialise their kernels.  Sixteen queues let every batch stream have its own (set before HIP starts; round 3,
-# headline: 8 queues / 6 streams 7.05 M, 16 / 12 7.5 M queries/s at --steps 96; 32 queues hung a box once — not used).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# The HIP runtime multiplexes a process's streams over its default number of hardware queues; the benchmark leaves that
+# count alone (raising it is a machine-wide setting on shared machines, and more queues than the card's slots has hung one).
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8 TB/s
 # HBM bytes per bound-off k_scan launch of the HEADLINE configuration from the committed PMC pass of this build (FETCH_SIZE x 2 on
@@ -112,9 +115,11 @@ def parse():
     ap.add_argument("--streams", type=int, default=12, help="HIP streams the batches are issued on, round-robin (tools/streams_sweep.py)")
     ap.add_argument("--config", default=None, choices=sorted(PRESETS),
                     help="a BASELINE.json configuration by name (sets n/dim/nlist/nprobe/bits/metric/batch/top-k; explicit flags win)")
-    ap.add_argument("--min-seconds", type=float, default=0.5,
+    ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="the K-step timed region is repeated (each repeat bracketed by barrier + synchronize) until this much "
-                         "time has been measured; value = median region (0 = one region)")
+                         "time has been measured; value = median region (default 0: one region, exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step (what a caller of the timed path receives) as DIR/<name>.npy")
     ap.add_argument("--in-library", action="store_true",
                     help="ONE process, ONE handle with --gpus replicas, host buffers through rbq_search_batch (the reference's "
                          "batch_search binding, src/ivf.rs:1743-1752) instead of one process per GPU")
@@ -182,7 +187,9 @@ def kmeans_gpu(torch, x, k, iters, seed):
         assign = assign_gpu(torch, x, cent, assign)
         if it == iters:
             break
-        sums = torch.zeros_like(cent).index_add_(0, assign, x)
+        # index_put_ with accumulate sorts the indices and adds in a fixed order (index_add_ uses atomics: the centroids, and
+        # with them a few list assignments, would change from run to run)
+        sums = torch.zeros_like(cent).index_put_((assign,), x, accumulate=True)
         cnt = torch.bincount(assign, minlength=k).clamp(min=1).unsqueeze(1)
         newc = sums / cnt
         empty = (torch.bincount(assign, minlength=k) == 0)
@@ -228,6 +235,27 @@ def exact_topk(torch, x, q, k, metric):
     best = [torch.full((q.shape[0], k), fill, device=q.device), torch.full((q.shape[0], k), -1, dtype=torch.int64, device=q.device)]
     exact_topk_update(torch, best, x, 0, q, k, metric)
     return best[1]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, ids, scores, counts, queries):
+    """The last timed step's results, as a caller of the timed path receives them: ids [nq][top_k] (uint64, written as float64:
+    exact below 2^53, the empty-slot sentinel 2^64 - 1 rounds to 2^64), scores [nq][top_k] float32, counts [nq] (float64) and
+    the queries of that step [nq][dim] float32.  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the queries' rows is written
+    (`rows` holds their indices)."""
+    nq = ids.shape[0]
+    row_bytes = ids.shape[1] * 12 + 16 + queries.shape[1] * 4  # ids f64 + scores f32, counts f64, rows f64, queries f32
+    budget = DUMP_LIMIT_BYTES - 4096  # (.npy headers)
+    rows = np.arange(nq)
+    if nq * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(20260106).choice(nq, budget // row_bytes, replace=False))
+    os.makedirs(d, exist_ok=True)
+    arrays = {"ids": ids[rows].astype(np.float64), "scores": scores[rows].astype(np.float32), "counts": counts[rows].astype(np.float64),
+              "queries": queries[rows].astype(np.float32), "rows": rows.astype(np.float64)}
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(v))
 
 
 def recall_of(ids, gt, k):
@@ -614,6 +642,8 @@ def main():
             dts.append(dt)
             if sum(dts) >= min_seconds or len(dts) >= 64:
                 break
+        last = counter[0] - 1  # the last timed step: its batch and the result slot it wrote (synchronized by fence())
+        last_out = {"ids": d_ids[last % nslots], "scores": d_sc[last % nslots], "counts": d_cnt[last % nslots], "batch": last % nbq}
         index.profile_end()
         index.set_option("profile_counters", 1)
         nreg = len(dts)
@@ -621,7 +651,7 @@ def main():
         prof = {"issue_s": t_issue / nreg, "scan_ms": ms, "scan_launches": launches, "scan_samples_ms": [round(float(v), 4) for v in index.profile_stage_samples("scan")][:64],
                 "counters": index.profile_counters(), "steps_total": steps * nreg, "counter_steps": steps * nreg,
                 "algorithmic_bytes": index.profile_scan_bytes(),
-                "stage_ms": {st_: index.profile_stage(st_)[0] for st_ in stages}}
+                "stage_ms": {st_: index.profile_stage(st_)[0] for st_ in stages}, "last_out": last_out}
         for st in streams:
             index.release_stream(st.cuda_stream)
         return dts, own, prof
@@ -780,6 +810,11 @@ def main():
                 break
         dt = statistics.median(dts)
         value = per_call * a.steps / dt
+        if a.dump_outputs:  # the last call of caller thread 0 in the last region (worker 0 makes share[0] calls, query set r % nsets)
+            pp = pin[0][(a.steps // nthr + (1 if a.steps % nthr else 0) - 1) % nsets]
+            host = lambda p_, ct, shape: np.ctypeslib.as_array(C.cast(p_, C.POINTER(ct)), shape=shape).copy()  # noqa: E731
+            dump_outputs(a.dump_outputs, host(pp[1], C.c_uint64, (per_call, a.top_k)), host(pp[2], C.c_float, (per_call, a.top_k)),
+                         host(pp[3], C.c_uint32, (per_call,)), host(pp[0], C.c_float, (per_call, a.dim)))
         # results of the first query set against the exact ground truth, and against ONE replica serving the same queries
         ids0 = np.ctypeslib.as_array(C.cast(pin[0][0][1], C.POINTER(C.c_uint64)), shape=(per_call, a.top_k)).copy()
         gtn = gt.cpu().numpy()[:per_call]
@@ -819,6 +854,10 @@ def main():
     mark("timed regions + counter pass")
     ns = max(1, a.streams)
     dts, own_dts, prof = run_measured(idx, q_all, a.nprobe, a.steps, a.warmup, ns, gather=True, min_seconds=a.min_seconds)
+    last = prof.pop("last_out")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last["ids"].cpu().numpy().view(np.uint64), last["scores"].cpu().numpy(),
+                     last["counts"].cpu().numpy().view(np.uint32), q_all[last["batch"]].cpu().numpy())
     dt = statistics.median(dts)  # the median K-step region (each one bracketed by barrier + synchronize, max over ranks)
     value = a.batch * world * a.steps / dt
     per_rank = [a.batch * a.steps / statistics.median(own_dts)]

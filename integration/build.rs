@@ -30,7 +30,5 @@ fn main() {
     // run-time lookup without LD_LIBRARY_PATH
     println!("cargo:rustc-link-arg=-Wl,-rpath,{}", dir.display());
     println!("cargo:rustc-link-arg=-Wl,-rpath,{}/lib", rocm);
-    // A host that issues batches from several threads or opens replicas on one device wants more than the default
-    // four hardware queues: set GPU_MAX_HW_QUEUES=16 in the process environment before the first HIP call
-    // (INTEGRATION.md G).
+    // The HIP hardware-queue count is the host's choice; the library does not change it.
 }

@@ -34,13 +34,11 @@ using rbq_host::ListSrc;
 using rbq_host::OutPack;
 using rbq_host::align_up;
 
-// The HIP runtime multiplexes a process's streams over FOUR hardware queues unless GPU_MAX_HW_QUEUES says otherwise, and two of this
-// library's lanes (or two caller streams) on one queue serialise their kernels: 16 queues are worth 5-15 % of the pipelined rate
-// (DESIGN 5).  The variable is read when the runtime initialises.  The library does NOT touch the environment on its own (round 4 did,
-// from a load-time constructor: a silent change for every other HIP user of the process, and setenv under dlopen races with getenv in
-// a threaded host); rbq_process_defaults() is the explicit opt-in, for a host that wants the library's recommendation applied.
+// The HIP runtime multiplexes a process's streams over its hardware queues; the queue count is a process-wide setting of the host
+// (GPU_MAX_HW_QUEUES, read when the runtime initialises) and the library leaves it alone.  rbq_process_defaults() used to raise it;
+// more queues than a card's slots is a state that has hung shared machines, so it now changes nothing and is kept for the ABI.
 extern "C" int rbq_process_defaults(void) {
-    return setenv("GPU_MAX_HW_QUEUES", "16", /*overwrite=*/0) == 0 ? RBQ_OK : RBQ_IO;
+    return RBQ_OK;
 }
 
 namespace {

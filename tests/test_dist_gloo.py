@@ -41,7 +41,7 @@ def _worker(rank, world, port, out_dir):
             ex.scores[slot].copy_(torch.from_numpy(sc.copy()))
             if bucket == 1 or slot == 1:
                 ex.gather(dist, slot // bucket)                                          # the path's only collective
-        dist.barrier()
+        dist.all_reduce(torch.zeros(1))  # a barrier on a CPU tensor (dist.barrier() asks the GPU runtime for its devices: every rank would open the GPU)
         if rank == 0:
             for slot, seed in ((0, 123), (1, 124)):
                 q_all = make_dataset(batch * world, 64, 3, seed)

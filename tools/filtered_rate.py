@@ -3,7 +3,6 @@ beside the unfiltered rate, same streams / batches protocol as bench.py's timed 
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np, torch
 import bench
 import rabitq_rs_amd as rq
