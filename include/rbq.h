@@ -224,6 +224,23 @@ void rbq_host_free(void* p);
  * Toggle with rbq_debug_set_option(idx, "rerank", 0/1) once vectors are attached (attaching switches it on). */
 int rbq_index_set_rerank_vectors(rbq_index* idx, const float* vectors, uint64_t n);
 
+/* Numeric variant: which build of the reference the kernels reproduce bit for bit.  The reference picks its arithmetic at
+ * compile time (cfg(target_feature) in src/simd.rs), so two builds of it return different last bits of the scores:
+ *   RBQ_NUMERIC_NATIVE_AVX512 (default)  the crate built in its own checkout (.cargo/config.toml: target-cpu=native) on an
+ *                                        AVX-512 host
+ *   RBQ_NUMERIC_NATIVE_AVX2              the same on an AVX2-only host (the AVX2 body of the ex-code dot product)
+ *   RBQ_NUMERIC_PORTABLE                 RUSTFLAGS="" builds: a crates.io dependency, the PyPI wheel, on x86-64 hosts with AVX2
+ *                                        (the scalar bodies of the ex-code dot product and of the estimator's first operation)
+ * Out of scope: x86-64 hosts without AVX2 (math.rs then takes its SSE2 bodies), non-x86 hosts, and builds with
+ * -C llvm-args=--ffast-math.  INTEGRATION.md, "Which arithmetic to pick".  The setting applies to every replica; like every other
+ * option it is not synchronised with calls already in flight.  Any other value: RBQ_INVALID_CONFIG (detail set). */
+#define RBQ_NUMERIC_NATIVE_AVX512 0
+#define RBQ_NUMERIC_NATIVE_AVX2   1
+#define RBQ_NUMERIC_PORTABLE      2
+int rbq_index_set_numeric_variant(rbq_index* idx, int variant);
+/* The handle's numeric variant (RBQ_NUMERIC_*), or -1 for a null handle. */
+int rbq_index_numeric_variant(const rbq_index* idx);
+
 /* Timing taps for bench.py: average duration (ms) of each stage kernel between
  * rbq_profile_begin/end, measured with hipEvents on the stream the kernels run
  * on. stage names: "prep", "rank", "select", "scan". Returns <0 for an unknown stage. */
@@ -295,8 +312,9 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *   "scan_wave" 0/1/2    which scan kernel serves a call
  *   "rank_ksplit" 0      never split the K loop of the ranking GEMM (default 1: calls of up to 256 queries split it 2-4 ways over
  *                        grid.z, the parts added atomically to a cleared row; n > 1 forces n parts)
- * and two that are not result-neutral:
+ * and three that are not result-neutral:
  *   "rerank" 0/1         the optional full-precision rerank (needs rbq_index_set_rerank_vectors)
+ *   "numeric_variant" v  rbq_index_set_numeric_variant(idx, v): which build of the reference the scores reproduce
  *   "debug_replica" r    which replica rbq_debug_copy_index / rbq_debug_copy_workspace read */
 int rbq_debug_set_option(rbq_index* idx, const char* name, int value);
 

@@ -19,6 +19,18 @@ use crate::RabitqError;
 
 // ---- include/rbq.h -------------------------------------------------------------------------------------------------
 
+/// RBQ_NUMERIC_*: which build of this crate the GPU scores reproduce bit for bit.
+#[repr(i32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum NumericVariant {
+    /// built in the crate's own checkout (target-cpu=native) on an AVX-512 host (the default)
+    NativeAvx512 = 0,
+    /// built in the crate's own checkout on an AVX2-only host
+    NativeAvx2 = 1,
+    /// RUSTFLAGS="" builds: a crates.io dependency, the PyPI wheel (x86-64 with AVX2)
+    Portable = 2,
+}
+
 #[repr(C)]
 pub struct RbqIndex {
     _p: [u8; 0],
@@ -106,6 +118,8 @@ extern "C" {
     fn rbq_host_free(p: *mut c_void);
     fn rbq_index_set_rerank_vectors(idx: *mut RbqIndex, vectors: *const f32, n: u64) -> c_int;
     fn rbq_debug_set_option(idx: *mut RbqIndex, name: *const c_char, value: c_int) -> c_int;
+    fn rbq_index_set_numeric_variant(idx: *mut RbqIndex, variant: c_int) -> c_int;
+    fn rbq_index_numeric_variant(idx: *const RbqIndex) -> c_int;
     fn rbq_strerror(code: c_int) -> *const c_char;
     fn rbq_last_error_detail(buf: *mut c_char, n: usize) -> c_int;
     fn rbq_abi_version() -> u32;
@@ -355,6 +369,21 @@ impl GpuIvf {
         out.into_iter().map(|r| r.unwrap()).collect()
     }
 
+    /// Which build of this crate the GPU scores reproduce bit for bit (`rbq_index_set_numeric_variant`; INTEGRATION.md,
+    /// "Which arithmetic to pick").  Applies to every replica; not synchronised with searches already in flight.
+    pub fn set_numeric_variant(&self, v: NumericVariant) -> Result<(), RabitqError> {
+        map_err(unsafe { rbq_index_set_numeric_variant(self.h, v as i32 as c_int) }, 0, 0)
+    }
+
+    /// The numeric variant the handle uses.
+    pub fn numeric_variant(&self) -> NumericVariant {
+        match unsafe { rbq_index_numeric_variant(self.h) } {
+            1 => NumericVariant::NativeAvx2,
+            2 => NumericVariant::Portable,
+            _ => NumericVariant::NativeAvx512,
+        }
+    }
+
     /// Diagnostic switches of the library (`rbq_debug_set_option`), e.g. ("lazy_select", 0).
     pub fn set_option(&self, name: &str, value: i32) -> Result<(), RabitqError> {
         let c = std::ffi::CString::new(name).map_err(|_| RabitqError::InvalidConfig("option name contains NUL"))?;
@@ -465,6 +494,8 @@ fn _boundary_is_complete() {
         rbq_search_batch_device as usize,
         rbq_release_stream as usize,
         rbq_index_set_rerank_vectors as usize,
+        rbq_index_set_numeric_variant as usize,
+        rbq_index_numeric_variant as usize,
         rbq_strerror as usize,
     );
 }

@@ -5,6 +5,9 @@ RBQ_OK, RBQ_DIMENSION_MISMATCH, RBQ_INVALID_CONFIG, RBQ_EMPTY_INDEX, RBQ_IO, \
     RBQ_INVALID_PERSISTENCE, RBQ_DEVICE = range(7)
 METRIC_L2, METRIC_IP = 0, 1
 ROTATOR_MATRIX, ROTATOR_FHT_KAC = 0, 1
+# numeric variants (RBQ_NUMERIC_*): which build of the reference the scores reproduce bit for bit
+NUMERIC_NATIVE_AVX512, NUMERIC_NATIVE_AVX2, NUMERIC_PORTABLE = 0, 1, 2
+NUMERIC_VARIANTS = {"native_avx512": NUMERIC_NATIVE_AVX512, "native_avx2": NUMERIC_NATIVE_AVX2, "portable": NUMERIC_PORTABLE}
 BATCH = 32
 
 

@@ -109,25 +109,36 @@ hipError_t launch_select_exact(const SelectParams& p, int device, hipStream_t s,
     const uint32_t np2 = next_pow2(p.nprobe);
     // key_window != null: [nq][np2] u64 in global memory (nprobe > kNprobeMax)
     const size_t lds = (key_window ? 0 : (size_t)np2 * 8) + (size_t)p.D * 4 + kThreads * 4;
-    static LdsAttrCache attr; // nprobe > 4096: more than the default 64 KB of dynamic LDS
-    if (probe_stage(2, reinterpret_cast<const void*>(&k_select), dim3(p.nq), kThreads, lds)) return hipSuccess;
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_select), lds, device);
+    static LdsAttrCache attr, attr_unf; // nprobe > 4096: more than the default 64 KB of dynamic LDS
+    const bool unf = p.numeric_variant == (uint32_t)kVarPortable;
+    const void* fn = unf ? reinterpret_cast<const void*>(&k_select<true>) : reinterpret_cast<const void*>(&k_select<false>);
+    if (probe_stage(2, fn, dim3(p.nq), kThreads, lds)) return hipSuccess;
+    hipError_t e = (unf ? attr_unf : attr).ensure(fn, lds, device);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_select, dim3(p.nq), dim3(kThreads), lds, s, (const float*)p.scores, p.nlist, p.nprobe, np2, p.metric, p.rot,
+    if (unf) hipLaunchKernelGGL(k_select<true>, dim3(p.nq), dim3(kThreads), lds, s, (const float*)p.scores, p.nlist, p.nprobe, np2, p.metric, p.rot,
+                                p.cent, p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream, p.nvec, p.prof_total, p.consts,
+                                p.bsum, key_window);
+    else hipLaunchKernelGGL(k_select<false>, dim3(p.nq), dim3(kThreads), lds, s, (const float*)p.scores, p.nlist, p.nprobe, np2, p.metric, p.rot,
                        p.cent, p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream, p.nvec, p.prof_total, p.consts,
                        p.bsum, key_window);
     return hipGetLastError();
 }
 
 namespace {
+template <int RM, int V>
+hipError_t launch_select_rmv(const SelectParams& p, const SelectGeom& g, size_t lds, int device, hipStream_t s) {
+    static LdsAttrCache attr;
+    if (probe_stage(2, reinterpret_cast<const void*>(&k_select_mfma<RM, V>), dim3(p.nq), kThreads, lds)) return hipSuccess;
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_select_mfma<RM, V>), lds, device);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_select_mfma<RM, V>), dim3(p.nq), dim3(kThreads), lds, s, p, g);
+    return hipGetLastError();
+}
 template <int RM>
 hipError_t launch_select_rm(const SelectParams& p, const SelectGeom& g, size_t lds, int device, hipStream_t s) {
-    static LdsAttrCache attr;
-    if (probe_stage(2, reinterpret_cast<const void*>(&k_select_mfma<RM>), dim3(p.nq), kThreads, lds)) return hipSuccess;
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_select_mfma<RM>), lds, device);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_select_mfma<RM>, dim3(p.nq), dim3(kThreads), lds, s, p, g);
-    return hipGetLastError();
+    if (p.numeric_variant == (uint32_t)kVarAvx2) return launch_select_rmv<RM, kVarAvx2>(p, g, lds, device, s);
+    if (p.numeric_variant == (uint32_t)kVarPortable) return launch_select_rmv<RM, kVarPortable>(p, g, lds, device, s);
+    return launch_select_rmv<RM, kVarAvx512>(p, g, lds, device, s);
 }
 } // namespace
 
@@ -185,9 +196,13 @@ hipError_t launch_select_mfma(const SelectParams& p, int device, hipStream_t s) 
 }
 
 hipError_t launch_probes_given(const ProbesGivenParams& p, hipStream_t s) {
-    hipLaunchKernelGGL(k_probes_given, dim3(p.nq), dim3(kThreads), (size_t)p.D * 4 + kThreads * 4, s, p.list_ids, p.list_counts,
-                       p.max_lists, p.nlist, p.metric, p.rot, p.cent, p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream,
-                       p.consts, p.bsum);
+    if (p.numeric_variant == (uint32_t)kVarPortable)
+        hipLaunchKernelGGL(k_probes_given<true>, dim3(p.nq), dim3(kThreads), (size_t)p.D * 4 + kThreads * 4, s, p.list_ids, p.list_counts,
+                           p.max_lists, p.nlist, p.metric, p.rot, p.cent, p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream,
+                           p.consts, p.bsum);
+    else hipLaunchKernelGGL(k_probes_given<false>, dim3(p.nq), dim3(kThreads), (size_t)p.D * 4 + kThreads * 4, s, p.list_ids, p.list_counts,
+                            p.max_lists, p.nlist, p.metric, p.rot, p.cent, p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream,
+                            p.consts, p.bsum);
     return hipGetLastError();
 }
 

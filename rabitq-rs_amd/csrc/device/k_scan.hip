@@ -27,23 +27,23 @@ hipError_t LdsAttrCache::ensure(const void* fn, size_t lds, int device) {
 
 namespace {
 
-template <int DT, int EX, int TR>
+template <int DT, int EX, int TR, int V = kVarAvx512>
 hipError_t launch_scan_r(const ScanParams& P, uint32_t nq, size_t lds, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     static LdsAttrCache attr;
-    if (probe_stage(3, reinterpret_cast<const void*>(&k_scan<DT, EX, TR>), dim3(nq), kScanThreads, lds)) return hipSuccess;
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_scan<DT, EX, TR>), lds, device);
+    if (probe_stage(3, reinterpret_cast<const void*>(&k_scan<DT, EX, TR, V>), dim3(nq), kScanThreads, lds)) return hipSuccess;
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_scan<DT, EX, TR, V>), lds, device);
     if (e != hipSuccess) return e;
-    if (ev0) hipExtLaunchKernelGGL((k_scan<DT, EX, TR>), dim3(nq), dim3(kScanThreads), lds, s, ev0, ev1, 0, P);
-    else hipLaunchKernelGGL((k_scan<DT, EX, TR>), dim3(nq), dim3(kScanThreads), lds, s, P);
+    if (ev0) hipExtLaunchKernelGGL((k_scan<DT, EX, TR, V>), dim3(nq), dim3(kScanThreads), lds, s, ev0, ev1, 0, P);
+    else hipLaunchKernelGGL((k_scan<DT, EX, TR, V>), dim3(nq), dim3(kScanThreads), lds, s, P);
     return hipGetLastError();
 }
 // top_k <= 63: one register per lane of the replay wave holds the top-k (bag, or the exact heap after a distance tie);
 // 64..128: two registers (the reference benchmarks top_k = 100); ..kTopKRegMax = 256: four; above that the exact heap in LDS
-template <int DT, int EX>
+template <int DT, int EX, int V = kVarAvx512>
 hipError_t launch_scan_t(const ScanParams& P, uint32_t nq, size_t lds, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    if (P.top_k >= 64u && P.top_k <= 128u) return launch_scan_r<DT, EX, 2>(P, nq, lds, device, s, ev0, ev1);
-    if (P.top_k > 128u && P.top_k <= kTopKRegMax) return launch_scan_r<DT, EX, 4>(P, nq, lds, device, s, ev0, ev1);
-    return launch_scan_r<DT, EX, 1>(P, nq, lds, device, s, ev0, ev1);
+    if (P.top_k >= 64u && P.top_k <= 128u) return launch_scan_r<DT, EX, 2, V>(P, nq, lds, device, s, ev0, ev1);
+    if (P.top_k > 128u && P.top_k <= kTopKRegMax) return launch_scan_r<DT, EX, 4, V>(P, nq, lds, device, s, ev0, ev1);
+    return launch_scan_r<DT, EX, 1, V>(P, nq, lds, device, s, ev0, ev1);
 }
 template <int DT>
 hipError_t launch_scan_d(const ScanParams& P, uint32_t nq, size_t lds, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
@@ -70,6 +70,12 @@ hipError_t launch_scan(const ScanParams& P, uint32_t nq, int device, hipStream_t
         if (e != hipErrorNotSupported) return e; // (not supported: that instantiation spills registers — k_scan serves the call)
     }
     const uint32_t D = P.D, Dc = P.Dc;
+    if (P.numeric_variant != (uint32_t)kVarAvx512) { // the other numeric variants: runtime-dimension instantiations only
+        const size_t lds = scan_lds_bytes(Dc, D, P.ex_bits, P.top_k, P.heap_ws == nullptr, scan_nb(0u));
+        if (P.numeric_variant == (uint32_t)kVarAvx2) return launch_scan_t<0, 0, kVarAvx2>(P, nq, lds, device, s, ev0, ev1);
+        if (P.numeric_variant == (uint32_t)kVarPortable) return launch_scan_t<0, 0, kVarPortable>(P, nq, lds, device, s, ev0, ev1);
+        return hipErrorInvalidValue;
+    }
     const int nb = D == Dc ? scan_nb(D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 960 || D == 1024 || D == 1536 ? D : 0u) : 1;
     // (RBQ_SCAN_LDS_PAD: diagnostic — extra dynamic LDS per workgroup, occupancy experiments)
     static const size_t pad = [] { const char* e = std::getenv("RBQ_SCAN_LDS_PAD"); return e ? (size_t)std::atol(e) : (size_t)0; }();

@@ -11,7 +11,7 @@ namespace {
 
 constexpr int kScanwMaxScratch = 16; // bytes per lane
 
-template <int DT, int EX, int TR>
+template <int DT, int EX, int TR, int V = kVarAvx512>
 hipError_t launch_scanw_r(const ScanParams& P, uint32_t nq, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     const size_t lds = scanw_lds_bytes(P.Dc, P.D, P.ex_bits, TR); // (always below the default 48 KB dynamic limit: D <= 2048)
     (void)device;
@@ -20,22 +20,22 @@ hipError_t launch_scanw_r(const ScanParams& P, uint32_t nq, int device, hipStrea
     // code object says how much it got; k_scan serves the call instead (identical results).
     static const int spills = [] {
         hipFuncAttributes fa;
-        if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_scanw<DT, EX, TR>)) != hipSuccess) { (void)hipGetLastError(); return 1; }
+        if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_scanw<DT, EX, TR, V>)) != hipSuccess) { (void)hipGetLastError(); return 1; }
         return fa.localSizeBytes > (size_t)kScanwMaxScratch ? 1 : 0;
     }();
     if (spills) return hipErrorNotSupported;
-    if (probe_stage(3, reinterpret_cast<const void*>(&k_scanw<DT, EX, TR>), dim3(nq), 64, lds)) return hipSuccess;
-    if (ev0) hipExtLaunchKernelGGL((k_scanw<DT, EX, TR>), dim3(nq), dim3(64), lds, s, ev0, ev1, 0, P);
-    else hipLaunchKernelGGL((k_scanw<DT, EX, TR>), dim3(nq), dim3(64), lds, s, P);
+    if (probe_stage(3, reinterpret_cast<const void*>(&k_scanw<DT, EX, TR, V>), dim3(nq), 64, lds)) return hipSuccess;
+    if (ev0) hipExtLaunchKernelGGL((k_scanw<DT, EX, TR, V>), dim3(nq), dim3(64), lds, s, ev0, ev1, 0, P);
+    else hipLaunchKernelGGL((k_scanw<DT, EX, TR, V>), dim3(nq), dim3(64), lds, s, P);
     return hipGetLastError();
 }
 // top_k <= 63: one register per lane holds the top-k (sorted run, or the exact heap after a distance tie); 64..127: two
 // registers (RankRun; the reference benchmarks top_k = 100); ..255: four
-template <int DT, int EX>
+template <int DT, int EX, int V = kVarAvx512>
 hipError_t launch_scanw_t(const ScanParams& P, uint32_t nq, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    if (P.top_k < 64u) return launch_scanw_r<DT, EX, 1>(P, nq, device, s, ev0, ev1);
-    if (P.top_k < 128u) return launch_scanw_r<DT, EX, 2>(P, nq, device, s, ev0, ev1);
-    return launch_scanw_r<DT, EX, 4>(P, nq, device, s, ev0, ev1);
+    if (P.top_k < 64u) return launch_scanw_r<DT, EX, 1, V>(P, nq, device, s, ev0, ev1);
+    if (P.top_k < 128u) return launch_scanw_r<DT, EX, 2, V>(P, nq, device, s, ev0, ev1);
+    return launch_scanw_r<DT, EX, 4, V>(P, nq, device, s, ev0, ev1);
 }
 template <int DT>
 hipError_t launch_scanw_d(const ScanParams& P, uint32_t nq, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
@@ -61,6 +61,10 @@ bool scanw_serves(const ScanParams& P) {
 }
 hipError_t launch_scanw(const ScanParams& P, uint32_t nq, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     const uint32_t D = P.D, Dc = P.Dc;
+    // the other numeric variants: runtime-dimension instantiations only (not supported: k_scan serves the call)
+    if (P.numeric_variant == (uint32_t)kVarAvx2) return launch_scanw_t<0, 0, kVarAvx2>(P, nq, device, s, ev0, ev1);
+    if (P.numeric_variant == (uint32_t)kVarPortable) return launch_scanw_t<0, 0, kVarPortable>(P, nq, device, s, ev0, ev1);
+    if (P.numeric_variant != (uint32_t)kVarAvx512) return hipErrorNotSupported;
     if (D == Dc && D == 960) return launch_scanw_d<960>(P, nq, device, s, ev0, ev1);
     if (D == Dc && D == 768) return launch_scanw_d<768>(P, nq, device, s, ev0, ev1);
     if (D == Dc) {

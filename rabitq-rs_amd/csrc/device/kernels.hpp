@@ -20,12 +20,35 @@
 
 namespace rbq {
 
+// ---- numeric variants (rbq_index_set_numeric_variant): which build of the reference the kernels reproduce bit for bit ----
+//   kVarAvx512   (0, default)  target-cpu=native on an AVX-512 host: AVX2 epilogue `fmaf(delta, accu, sum_vl)`, ex-code dot
+//                              ip_packed_ex{2,6}_f32 AVX-512 bodies (16-lane FMA chains + _mm512_reduce_add_ps tree)
+//   kVarAvx2     (1)           target-cpu=native on an AVX2-only host: same epilogue, ex-code dot of ip_packed_ex{2,6}_f32_avx2
+//                              (src/simd.rs:1722-1825: ONE 8-lane FMA accumulator, dims 16t+l then 16t+8+l, hsum lo+hi / movehl / 0x55)
+//   kVarPortable (2)           RUSTFLAGS="" / crates.io / the PyPI wheel: compute_batch_distances_u16_scalar (:2039-2061,
+//                              `delta * accu + sum_vl` NOT fused) and ip_packed_ex{2,6}_f32_scalar (:1615-1713, one running sum,
+//                              `sum += c * q` unfused, in the scalar bodies' dimension order)
+// The default kernels are the V = 0 instantiations, whose code the variant switches leave untouched (`if constexpr`).
+// (kVarAvx512 / kVarAvx2 / kVarPortable: types.hpp, shared with the host side)
+
+// First operation of the epilogue: ip = delta * accu + sum_vl, fused (AVX2 body) or not (scalar body).
+__device__ __forceinline__ float epi_ip(float delta, float accu, float sum_vl, bool unfused) {
+    if (unfused) {
+        const float pm = delta * accu;
+        return pm + sum_vl;
+    }
+    return fmaf(delta, accu, sum_vl);
+}
+
 // Block-level bound: accu of any code lies in [amin, amax] and lb is monotone in accu (direction = sign of
 // f_rescale), so the epilogue's own operation sequence (compute_batch_distances_u16, AVX2 body: only the first
 // op is fused) evaluated on the extremes of every operand is <= lb of every real vector of the block.
-__device__ __forceinline__ float block_lbmin(const BlockSummary& bs, float g_add, float g_err, const QueryConsts& qc) {
-    const float tA = fmaf(qc.delta, qc.amin, qc.sum_vl) + qc.k1x;
-    const float tB = fmaf(qc.delta, qc.amax, qc.sum_vl) + qc.k1x;
+// `unfused` (kVarPortable): the scan's epilogue is the scalar body's `delta * accu + sum_vl` unfused, and the bound runs the
+// same two roundings — a fused bound could sit one ulp off the scan's value and skip a block wrongly.  The unfused sequence is
+// monotone in accu as well: delta > 0, so delta * accu is (rounding is monotone) and so is its sum with a constant.
+__device__ __forceinline__ float block_lbmin(const BlockSummary& bs, float g_add, float g_err, const QueryConsts& qc, bool unfused = false) {
+    const float tA = epi_ip(qc.delta, qc.amin, qc.sum_vl, unfused) + qc.k1x;
+    const float tB = epi_ip(qc.delta, qc.amax, qc.sum_vl, unfused) + qc.k1x;
     const float r0 = bs.fres_min * tA, r1 = bs.fres_min * tB, r2 = bs.fres_max * tA, r3 = bs.fres_max * tB;
     const float rmin = fminf(fminf(r0, r1), fminf(r2, r3)), rmax = fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
     float elo = bs.fadd_min + g_add;
@@ -48,13 +71,18 @@ __device__ __forceinline__ float block_lbmin(const BlockSummary& bs, float g_add
 //   * the u8 quantisation of the LUT (src/ivf.rs:798-845): every codebook entry within delta/2 (+ rounding) of its f32
 //     value, D/4 codebooks:  |ip - <q, bit>| <= E_ip = (D/8) delta 1.01 + 1e-4 |q|_1   (the second term also covers the
 //     sequential f32 sums behind k1x / kbx and sum_vl),
-//   * the f32 summation of the ex-code dot (16-lane FMA chains + tree): <= 1e-3 (2^ex - 1) |q|_1  (actual: < 1.3e-4),
+//   * the f32 summation of the ex-code dot (16-lane FMA chains + tree): <= 1e-3 (2^ex - 1) |q|_1  (actual: < 1.3e-4);
+//     the other variants' orders stay inside the same term: the AVX2 order (8 FMA chains + a 3-level tree) has fewer
+//     levels than D, and the portable one (D unfused products, one serial chain) rounds each product once and each partial
+//     sum once, at most (D + 1) 2^-24 of the sum of |terms| <= (2^ex - 1) |q|_1: 1.2e-4 of it at D = 2048, below 1e-3,
+//   * (the epilogue's first operation is fused or not per variant (`unfused`): ipA / ipB follow the scan's own sequence)
 //   * the roundings of the handful of f32 operations of the two formulas: 1e-5 of the sum of the magnitudes involved
 //     (each operation contributes at most 6e-8 of its operands), magnitudes bounded through the all-codes ranges.
 // +inf when anything is not finite (such a block proves nothing).
 __device__ __forceinline__ float block_ub(const BlockSummary& bs, const BlockSummaryEx& bx, float g_add, float g_err,
-                                          const QueryConsts& qc, uint32_t D, uint32_t ex_bits, const SlackMul sm = SlackMul()) {
-    const float ipA = fmaf(qc.delta, qc.amin, qc.sum_vl), ipB = fmaf(qc.delta, qc.amax, qc.sum_vl);
+                                          const QueryConsts& qc, uint32_t D, uint32_t ex_bits, const SlackMul sm = SlackMul(),
+                                          bool unfused = false) {
+    const float ipA = epi_ip(qc.delta, qc.amin, qc.sum_vl, unfused), ipB = epi_ip(qc.delta, qc.amax, qc.sum_vl, unfused);
     const float tmax = fmaxf(fabsf(ipA + qc.k1x), fabsf(ipB + qc.k1x));
     const float ge = g_err * (1.0f + sm.ge * 1e-4f);
     const float E_ip = sm.eip * ((float)D * 0.125f * qc.delta * 1.01f + 1e-4f * qc.q1norm + 1e-6f * (fabsf(qc.sum_vl) + qc.delta * qc.amax));
@@ -82,9 +110,9 @@ __device__ __forceinline__ float block_ub(const BlockSummary& bs, const BlockSum
 // Whole-list bound: `ls` = the factor ranges over ALL blocks of a list, g_add in [ga_lo, ga_hi], g_err in [ge_lo, ge_hi]
 // (0 <= ge_lo).  True iff every vector of the list has a finite lower bound >= T for every admissible (g_add, g_err).
 __device__ __forceinline__ bool list_bound_reaches(const BlockSummary& ls, float ga_lo, float ga_hi, float ge_lo, float ge_hi,
-                                                   const QueryConsts& qc, float T) {
-    const float tA = fmaf(qc.delta, qc.amin, qc.sum_vl) + qc.k1x;
-    const float tB = fmaf(qc.delta, qc.amax, qc.sum_vl) + qc.k1x;
+                                                   const QueryConsts& qc, float T, bool unfused = false) {
+    const float tA = epi_ip(qc.delta, qc.amin, qc.sum_vl, unfused) + qc.k1x; // (`unfused`: as block_lbmin)
+    const float tB = epi_ip(qc.delta, qc.amax, qc.sum_vl, unfused) + qc.k1x;
     const float r0 = ls.fres_min * tA, r1 = ls.fres_min * tB, r2 = ls.fres_max * tA, r3 = ls.fres_max * tB;
     const float rmin = fminf(fminf(r0, r1), fminf(r2, r3)), rmax = fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
     const float e0 = ls.ferr_min * ge_lo, e1 = ls.ferr_min * ge_hi, e2 = ls.ferr_max * ge_lo, e3 = ls.ferr_max * ge_hi;
@@ -164,6 +192,77 @@ __device__ __forceinline__ float group16_reduce(float sacc) { // _mm512_reduce_a
     sacc = sacc + __shfl_xor(sacc, 2, 16);
     sacc = sacc + __shfl_xor(sacc, 1, 16);
     return sacc;
+}
+
+// ---- ex-code dot of the other numeric variants, for one 16-lane group (every lane returns the group's sum) -----------------
+// Same layout as ex_dot_units: unit j of lane l holds the codes of dims 16 (j CPU + k) + l; `sq` as there; `ntiles` = D / 16
+// (tiles beyond it are never read).  The codes are read from memory here: these kernels are the V != 0 instantiations only.
+//   kVarAvx2: lane l (and lane l + 8, which computes the same value) runs ONE chain over dims 16t + (l & 7) and 16t + 8 + (l & 7),
+//     fmaf both, t ascending — the 8 lanes of the reference's single __m256 accumulator.  Its horizontal sum
+//     (b[i] = s[i] + s[i+4]; b0 + b2, b1 + b3; their sum) is the xor-4 / 2 / 1 halving tree over those 8 lanes (f32 addition is
+//     commutative, so the operand order of each pair does not matter).
+//   kVarPortable: one running sum, `p = c * q; sum = sum + p`, t ascending and inside a tile in the scalar bodies' order (ex6: dims
+//     0..15; ex2: i, i+4, i+8, i+12 for i = 0..3).  No parallel form gives the same bits, so every lane computes its own product
+//     and the 16 products of a tile feed one serial add chain through lane broadcasts (every lane of the group runs the chain).
+template <int EX, int V>
+__device__ __forceinline__ float ex_dot_var(const uint8_t* __restrict__ ex, const float* sq, uint32_t gl, uint32_t nunits, uint32_t ntiles) {
+    static_assert(V == kVarAvx2 || V == kVarPortable, "the default variant uses ex_dot_units / ex_dot_all + group16_reduce");
+    constexpr int CPU = 128 / EX;
+    constexpr uint32_t mask = (1u << EX) - 1u;
+    auto code_of = [](const uint32_t (&w)[5], int k) -> uint32_t {
+        const int bit = k * EX, idx = bit >> 5, sh = bit & 31;
+        if (sh + EX <= 32) return (w[idx] >> sh) & mask;
+        return ((w[idx] >> sh) | (w[idx + 1] << (32 - sh))) & mask;
+    };
+    if constexpr (V == kVarAvx2) {
+        const uint32_t lo = gl & 7u;
+        const uint4* pa = reinterpret_cast<const uint4*>(ex) + lo;
+        float s = 0.0f;
+#pragma unroll 1
+        for (uint32_t j = 0; j < nunits; ++j) {
+            const uint4 ua = pa[j * 16], ub = pa[j * 16 + 8];
+            const uint32_t wa[5] = {ua.x, ua.y, ua.z, ua.w, 0u}, wb[5] = {ub.x, ub.y, ub.z, ub.w, 0u};
+            const float* qj = sq + (size_t)j * CPU * 16 + lo;
+#pragma unroll
+            for (int k = 0; k < CPU; ++k) {
+                if (j * CPU + (uint32_t)k < ntiles) { // wave-uniform
+                    s = fmaf((float)code_of(wa, k), qj[16 * k], s);
+                    s = fmaf((float)code_of(wb, k), qj[16 * k + 8], s);
+                }
+            }
+        }
+        s = s + __shfl_xor(s, 4, 16);
+        s = s + __shfl_xor(s, 2, 16);
+        s = s + __shfl_xor(s, 1, 16);
+        return s;
+    } else {
+        const uint4* p = reinterpret_cast<const uint4*>(ex) + gl;
+        float sum = 0.0f;
+#pragma unroll 1
+        for (uint32_t j = 0; j < nunits; ++j) {
+            const uint4 u = p[j * 16];
+            const uint32_t w[5] = {u.x, u.y, u.z, u.w, 0u};
+            const float* qj = sq + (size_t)j * CPU * 16 + gl;
+#pragma unroll
+            for (int k = 0; k < CPU; ++k) {
+                if (j * CPU + (uint32_t)k < ntiles) { // wave-uniform
+                    const float pr = (float)code_of(w, k) * qj[16 * k];
+#pragma unroll
+                    for (int n = 0; n < 16; ++n) {
+                        const int src = EX == 2 ? (n >> 2) + 4 * (n & 3) : n; // position n of the tile's order -> lane
+                        sum = sum + __shfl(pr, src, 16);
+                    }
+                }
+            }
+        }
+        return sum;
+    }
+}
+// runtime ex_bits (2 / 6)
+template <int V>
+__device__ __forceinline__ float ex_dot_var_rt(const uint8_t* __restrict__ ex, const float* sq, uint32_t gl, uint32_t nunits, uint32_t ntiles,
+                                               uint32_t ex_bits) {
+    return ex_bits == 6 ? ex_dot_var<6, V>(ex, sq, gl, nunits, ntiles) : ex_dot_var<2, V>(ex, sq, gl, nunits, ntiles);
 }
 
 __device__ __forceinline__ int32_t total_key(float x) { // f32::total_cmp ordering key

@@ -112,6 +112,7 @@ struct SelectParams {
     uint32_t* audit_dead;         // null, or (option lazy_audit) [nq][kAuditCap + 1] u32: the number of lists this query's selection dropped as
                                   // a whole, then their ids — exported WITHOUT changing any decision, with or without diagnostics or a
                                   // filter, so that a test can ask the oracle what the reference did with exactly those lists
+    uint32_t numeric_variant;     // kVarAvx512 / kVarAvx2 / kVarPortable (kernels.hpp): picks the instantiation (host side only)
     int fault_dead_all;           // TEST ONLY (debug option lazy_fault_inject, default 0): T_ub := -inf — every list behind the head is
                                   // declared dead whatever its bounds say: a deliberately WRONG selection, so that the
                                   // bound_violations audit can be shown to catch one
@@ -136,6 +137,7 @@ struct ProbesGivenParams {
     uint32_t* nstream;
     const QueryConsts* consts;
     const BlockSummary* bsum;
+    uint32_t numeric_variant;     // kVarPortable: block_lbmin's epilogue is not fused
 };
 hipError_t launch_probes_given(const ProbesGivenParams& p, hipStream_t s);
 

@@ -8,7 +8,10 @@ namespace rbq {
 
 // Range of sum_i code_i * q_i over ALL ex codes (code_i in [0, 2^ex - 1]) from the sums of the positive and of the negative
 // query elements, widened by 1e-3 of the largest possible magnitude: that covers the rounding of these two sums and of the
-// scan kernel's own 16-lane FMA summation (each below D * 2^-24 <= 1.3e-4 relative for D <= 2048).
+// scan kernel's own 16-lane FMA summation (each below D * 2^-24 <= 1.3e-4 relative for D <= 2048).  The other numeric
+// variants' orders are covered by the same slack: the AVX2 order is 8 FMA chains of D / 8 steps and a 3-level tree (below
+// D * 2^-24 as well); the portable order (kernels.hpp, ex_dot_var) rounds each of the D products once and then adds them in
+// one serial chain, which is at most (D + 1) * 2^-24 of the sum of |terms| — 1.2e-4 at D = 2048, still below 1e-3.
 __device__ __forceinline__ void ex_dot_range(float sum_pos, float sum_neg, uint32_t ex_bits, float& lo, float& hi) {
     const float cmax = (float)((1u << ex_bits) - 1u);
     const float slack = cmax * (sum_pos - sum_neg) * 1e-3f;
@@ -615,6 +618,8 @@ __global__ __launch_bounds__(kThreads) void k_rank_scores(const float* __restric
 }
 
 
+// UNF: the epilogue's first operation is not fused (kVarPortable: block_lbmin)
+template <bool UNF = false>
 __global__ __launch_bounds__(kThreads) void k_select(const float* __restrict__ scores, uint32_t nlist, uint32_t nprobe,
                                                      uint32_t np2, int metric, const float* __restrict__ rot,
                                                      const float* __restrict__ cent, uint32_t D,
@@ -743,7 +748,7 @@ __global__ __launch_bounds__(kThreads) void k_select(const float* __restrict__ s
             StreamItem wi;
             wi.gblock = gb + b;
             wi.rank_nvalid = (r << 6) | nv;
-            wi.lbmin = block_lbmin(bsum[gb + b], pi.g_add, pi.g_err, qc);
+            wi.lbmin = block_lbmin(bsum[gb + b], pi.g_add, pi.g_err, qc, UNF);
             wi.pad = 0;
             wl[pos++] = wi;
         }

@@ -672,7 +672,8 @@ __device__ __forceinline__ uint32_t hx_look8(uint32_t x, const uint8_t* p) { // 
 __device__ __forceinline__ bool hx_tame(float x) { return fabsf(x) < 1e30f; } // far from overflow: the exact value next to it is finite too
 // Returns T' (see the kernel), +inf when the list is too short or too few of its vectors have finite bounds.  Every thread of the
 // workgroup calls it and gets the same value.  scratch: the LDS region above; part / hist: 256 words of LDS scratch each.
-template <class CostOf>
+// V: numeric variant (kernels.hpp) — the head vectors are evaluated with the scan's own arithmetic under every variant
+template <int V, class CostOf>
 __device__ __forceinline__ float head_exact_bound(const SelectParams& P, const SelectGeom& G, const QueryConsts& qc, const uint64_t* keys,
                                                   const uint32_t* s_head, const uint32_t* s_hgb, const uint32_t* s_hn, const float* s_hcn,
                                                   uint32_t h, float eps, unsigned char* scratch, const float* qrot, uint32_t* part, uint32_t* hist,
@@ -741,7 +742,7 @@ __device__ __forceinline__ float head_exact_bound(const SelectParams& P, const S
             }
         }
         if (Dc & 64u) acc += hx_look8(ytail.x, lutL + G16 * 512) + hx_look8(ytail.y, lutL + G16 * 512 + 128);
-        const float ip = fmaf(qc.delta, (float)(acc & 0xffffu), qc.sum_vl);
+        const float ip = epi_ip(qc.delta, (float)(acc & 0xffffu), qc.sum_vl, V == kVarPortable);
         const float tt = ip + qc.k1x;
         const float rs = f_rescale * tt;
         float est = f_add + g_add;
@@ -797,12 +798,13 @@ __device__ __forceinline__ float head_exact_bound(const SelectParams& P, const S
             const uint8_t* ex = P.ex_codes + (size_t)slot * exb;
             const float fa = P.f_add_ex[slot], fr = P.f_rescale_ex[slot]; // (requested with the code units)
             float sacc;
-            if (RBQ_HX_EX_ALL && nunits <= (uint32_t)kExRegUnits) { // every unit in flight before the first is decoded (same arithmetic: ex_dot_all)
+            if constexpr (V != kVarAvx512) sacc = ex_dot_var_rt<V>(ex, sq, gl, nunits, D / 16, ex_bits); // (already the group's sum)
+            else if (RBQ_HX_EX_ALL && nunits <= (uint32_t)kExRegUnits) { // every unit in flight before the first is decoded (same arithmetic: ex_dot_all)
                 uint4 uu[kExRegUnits];
                 ex_load_all(uu, ex, gl, nunits);
                 sacc = ex_bits == 6 ? ex_dot_all<6>(uu, sq, gl, nunits) : ex_dot_all<2>(uu, sq, gl, nunits);
             } else sacc = ex_bits == 6 ? ex_dot_units<6>(ex, sq, gl, nunits) : ex_dot_units<2>(ex, sq, gl, nunits);
-            sacc = group16_reduce(sacc);
+            if constexpr (V == kVarAvx512) sacc = group16_reduce(sacc);
             if (gl == 0) {
                 float tt2 = qc.scale * vIp[v];
                 const float t0 = tt2;
@@ -868,7 +870,8 @@ constexpr uint32_t kSelZoneMax = 1024; // boundary-zone lists whose membership t
 // Off (eager = every shortlisted list scored, every member streamed, the round-2 behaviour) when P.lazy == 0, with a
 // filter (filtered vectors are not pushed: no T_ub), when accu may wrap, and per query when T_ub is infinite or the
 // exceptional sizes above are exceeded.
-template <int RM>
+// V: numeric variant (kernels.hpp): the head evaluation and every bound follow the scan's arithmetic
+template <int RM, int V = kVarAvx512>
 __global__ RBQ_SEL_BOUNDS void k_select_mfma(const SelectParams P, const SelectGeom G) {
     extern __shared__ __align__(16) unsigned char smraw[];
     const uint32_t nlist = P.nlist, nprobe = P.nprobe, cap2 = G.cap2, D = P.D;
@@ -1282,7 +1285,7 @@ __global__ RBQ_SEL_BOUNDS void k_select_mfma(const SelectParams P, const SelectG
                 head_info(r, g_add, g_err, gb, nvec);
                 const BlockSummary bs = P.bsum[gb + b];
                 const BlockSummaryEx bx = P.bsumx[gb + b];
-                myU = block_ub(bs, bx, g_add, g_err, qc, D, P.ex_bits, P.slack) + 1e-4f * eps; // (+: |g_add| in the rounding slack is taken at the upper end)
+                myU = block_ub(bs, bx, g_add, g_err, qc, D, P.ex_bits, P.slack, V == kVarPortable) + 1e-4f * eps; // (+: |g_add| in the rounding slack is taken at the upper end)
                 myN = (b + 1 == ((nvec + 31u) >> 5)) ? nvec - b * 32u : 32u;
             }
             float* candU = reinterpret_cast<float*>(part);
@@ -1306,7 +1309,7 @@ __global__ RBQ_SEL_BOUNDS void k_select_mfma(const SelectParams P, const SelectG
             const float cost_maxh = key_to_float((int32_t)s_maxh);
             bool hx_done = false;
             if (P.filter) { // (uniform)
-                T_ub = (G.hx_nv && P.head_exact) ? head_exact_bound(P, G, qc, keys, s_head, s_hgb, s_hn, s_hcn, h, eps, reinterpret_cast<unsigned char*>(rows), qrot, part, hist, q, tid, cost_of) : INFINITY;
+                T_ub = (G.hx_nv && P.head_exact) ? head_exact_bound<V>(P, G, qc, keys, s_head, s_hgb, s_hn, s_hcn, h, eps, reinterpret_cast<unsigned char*>(rows), qrot, part, hist, q, tid, cost_of) : INFINITY;
                 hx_done = true;
                 if (P.fault_dead_all) T_ub = -INFINITY; // (the test-only fault injection also under a filter: ADVICE r4)
             }
@@ -1331,7 +1334,7 @@ __global__ RBQ_SEL_BOUNDS void k_select_mfma(const SelectParams P, const SelectG
                             ge_lo = sqrtf(fmaxf(da - 4.0f * eps, 0.0f)); ge_hi = sqrtf(fmaxf(da + 4.0f * eps, 0.0f));
                         }
                         const BlockSummary ls = u == 0 ? ls_own : P.lsum[cid];
-                        const bool dead = clo > cost_maxh && list_bound_reaches(ls, clo, chi, ge_lo, ge_hi, qc, T);
+                        const bool dead = clo > cost_maxh && list_bound_reaches(ls, clo, chi, ge_lo, ge_hi, qc, T, V == kVarPortable);
                         if (dead) m_dead |= 1ull << u;
                         else {
                             if (!((m_certain >> u) & 1ull)) s_flag = 1u; // a zone list is alive
@@ -1357,7 +1360,7 @@ __global__ RBQ_SEL_BOUNDS void k_select_mfma(const SelectParams P, const SelectG
                 const uint32_t need1 = s_need;
                 __syncthreads();
                 if (G.hx_nv && P.head_exact && !hx_done && need1 - h > kHxTrigger) { // (uniform)
-                    const float T2 = head_exact_bound(P, G, qc, keys, s_head, s_hgb, s_hn, s_hcn, h, eps, reinterpret_cast<unsigned char*>(rows), qrot, part, hist, q, tid, cost_of);
+                    const float T2 = head_exact_bound<V>(P, G, qc, keys, s_head, s_hgb, s_hn, s_hcn, h, eps, reinterpret_cast<unsigned char*>(rows), qrot, part, hist, q, tid, cost_of);
                     if (T2 < T_ub) {
                         m_dead = 0ull;
                         if (tid == 0) { s_need = h; s_flag = 0u; }
@@ -1677,7 +1680,7 @@ __global__ RBQ_SEL_BOUNDS void k_select_mfma(const SelectParams P, const SelectG
                 StreamItem wi;
                 wi.gblock = gbb[u];
                 wi.rank_nvalid = (rr[u] << 6) | nvv[u];
-                wi.lbmin = block_lbmin(bs[u], g_add, g_err, qc);
+                wi.lbmin = block_lbmin(bs[u], g_add, g_err, qc, V == kVarPortable);
                 wi.pad = 0;
                 out[i] = wi;
             }
@@ -1707,6 +1710,8 @@ __global__ RBQ_SEL_BOUNDS void k_select_mfma(const SelectParams P, const SelectG
 // per-list constants of search_posting_list_fastscan (g_add = l2_distance_sqr(query, centroid) or -dot in
 // canonical order, g_error = 0; src/mstg/index.rs:227-231) and the block work list, in the given order.
 // dynamic LDS: qrot[D] f32 | part[256] u32
+// UNF: the epilogue's first operation is not fused (kVarPortable: block_lbmin)
+template <bool UNF = false>
 __global__ __launch_bounds__(kThreads) void k_probes_given(const uint32_t* __restrict__ list_ids,
                                                            const uint32_t* __restrict__ list_counts, uint32_t max_lists,
                                                            uint32_t nlist, int metric, const float* __restrict__ rot,
@@ -1771,7 +1776,7 @@ __global__ __launch_bounds__(kThreads) void k_probes_given(const uint32_t* __res
             StreamItem wi;
             wi.gblock = gb + b;
             wi.rank_nvalid = (r << 6) | nv;
-            wi.lbmin = block_lbmin(bsum[gb + b], pi.g_add, pi.g_err, qcs);
+            wi.lbmin = block_lbmin(bsum[gb + b], pi.g_add, pi.g_err, qcs, UNF);
             wi.pad = 0;
             wl[pos++] = wi;
         }

@@ -250,6 +250,7 @@ struct Replica {
     uint64_t n_raw = 0;      // raw vectors attached for the optional rerank
     bool raw_borrowed = false;
     bool rerank = false;
+    uint32_t numeric_variant = 0; // RBQ_NUMERIC_*: which build of the reference the kernels reproduce (kernels.hpp, kVar*)
     uint32_t host_lanes = 0, host_subbatch = 0, host_trace = 0; // rbq_debug_set_option: pipeline shape of rbq_search_batch (0 = default)
     int rank_ksplit = 1;              // option rank_ksplit: 0 = never split the ranking GEMM's K loop, 1 = by batch size, n > 1 = forced
     int host_taper = 0;               // option host_taper: weights of a call's sub-batches (rbq_host_logic.hpp; A/B runs)
@@ -1116,6 +1117,7 @@ int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, ui
     P.mstg = mstg ? 1u : 0u;
     P.prof = (ix->profiling && ix->profile_counters) ? (unsigned long long*)ix->prof.p : nullptr;
     P.dead_skipped = d_dead_skipped;
+    P.numeric_variant = ix->numeric_variant;
     // scan_wave = 2 (default): the wave-per-query kernel serves the pruned regime of batches large enough to fill the chip with
     // waves; with the block bound off (every probed block streamed: the roofline configuration) the four-wave kernel streams
     // at twice its rate and serves the call.  Results are identical either way.
@@ -1244,6 +1246,7 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
     sp.cnorm2 = (const float*)ix->cnorm2.p; sp.lsum = (const BlockSummary*)ix->lsum.p; sp.bsumx = (const BlockSummaryEx*)ix->bsumx.p;
     sp.dead_skipped = (uint32_t*)w->dead_skipped.p; sp.top_k = top_k; sp.ex_bits = ix->ex_bits;
     sp.slack = ix->slack;
+    sp.numeric_variant = ix->numeric_variant;
     sp.audit_dead = nullptr;
     if (ix->lazy_audit) { // diagnostic: the lists the selection drops as a whole are exported (rbq_debug_copy_workspace "audit_dead")
         if ((rc = w->audit_dead.ensure(nq * (size_t)(kAuditCap + 1) * 4))) return rc;
@@ -1513,7 +1516,8 @@ Replica* replica_of_pointer(rbq_index* h, const void* dptr) {
 
 extern "C" {
 
-uint32_t rbq_abi_version(void) { return (2u << 16) | 1u; } // (minor 1: rbq_debug_tie_log_stats; options latency_path, tie_log)
+// (minor 1: rbq_debug_tie_log_stats; options latency_path, tie_log.  minor 2: rbq_index_set_numeric_variant / rbq_index_numeric_variant)
+uint32_t rbq_abi_version(void) { return (2u << 16) | 2u; }
 
 const char* rbq_strerror(int code) {
     switch (code) {
@@ -1822,6 +1826,7 @@ int rbq_posting_scan_batch(const rbq_index* ch, const float* queries, uint64_t n
                 p.list_n = (const uint32_t*)ix->list_n.p; p.probe = (ProbeInfo*)w->probe.p; p.wl = (StreamItem*)w->wl.p;
                 p.wl_stride = wl_stride; p.nstream = (uint32_t*)w->nstream.p; p.consts = (const QueryConsts*)w->consts.p;
                 p.bsum = (const BlockSummary*)ix->bsum.p;
+                p.numeric_variant = ix->numeric_variant;
                 HIP_TRY(launch_probes_given(p, st));
             }
             if ((r2 = scan_stage(ix, w, n, max_lists, top_k, wl_stride, nullptr, 0, (uint64_t*)(dp + op.o_ids), (float*)(dp + op.o_scores),
@@ -1976,8 +1981,25 @@ int rbq_profile_counters(const rbq_index* h, uint64_t* out, uint32_t n) {
 void rbq_profile_select_stages(rbq_index* h, uint32_t mask) { if (h) for (Replica* ix : h->reps) ix->prof_mask = mask & 0xfu; }
 void rbq_profile_set_sampling(rbq_index* h, uint32_t every) { if (h) for (Replica* ix : h->reps) ix->prof_every = every ? every : 1u; }
 
+int rbq_index_set_numeric_variant(rbq_index* h, int variant) {
+    g_err.clear();
+    if (!h || h->reps.empty()) return fail(RBQ_INVALID_CONFIG, "null index");
+    if (variant != RBQ_NUMERIC_NATIVE_AVX512 && variant != RBQ_NUMERIC_NATIVE_AVX2 && variant != RBQ_NUMERIC_PORTABLE)
+        return fail(RBQ_INVALID_CONFIG, "numeric variant " + std::to_string(variant) +
+                                            " is not one of 0 (native_avx512), 1 (native_avx2), 2 (portable)");
+    static_assert(RBQ_NUMERIC_NATIVE_AVX512 == kVarAvx512 && RBQ_NUMERIC_NATIVE_AVX2 == kVarAvx2 && RBQ_NUMERIC_PORTABLE == kVarPortable,
+                  "the ABI values are the kernels' variant numbers");
+    for (Replica* ix : h->reps) ix->numeric_variant = (uint32_t)variant;
+    return RBQ_OK;
+}
+int rbq_index_numeric_variant(const rbq_index* h) {
+    if (!h || h->reps.empty()) return -1;
+    return (int)h->reps[0]->numeric_variant;
+}
+
 int rbq_debug_set_option(rbq_index* h, const char* name, int value) {
     if (!h || h->reps.empty() || !name) return RBQ_INVALID_CONFIG;
+    if (!std::strcmp(name, "numeric_variant")) return rbq_index_set_numeric_variant(h, value);
     if (!std::strcmp(name, "debug_replica")) {
         if (value < 0 || (size_t)value >= h->reps.size()) return fail(RBQ_INVALID_CONFIG, "no such replica");
         h->debug_replica = value;

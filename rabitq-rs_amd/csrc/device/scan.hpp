@@ -1000,7 +1000,9 @@ __device__ __attribute__((noinline)) RegHeap<TR> tie_log_replay(float* heap_d, u
 // EX: compile-time ex_bits (0/2/6) when DT != 0; ignored (runtime P.ex_bits) when DT == 0.
 // TR: registers per lane of the replay wave's top-k (1: top_k <= 63; 2: <= 128; 4: <= 256 — with more than one,
 // four waves per SIMD instead of five).
-template <int DT, int EX, int TR>
+// V: numeric variant (kernels.hpp, kVarAvx512 / kVarAvx2 / kVarPortable).  The variants other than the default are instantiated
+// for the runtime-dimension kernel only (DT = 0), so the default instantiations keep their code and the build its size.
+template <int DT, int EX, int TR, int V = kVarAvx512>
 __global__ __launch_bounds__(kScanThreads, ((TR == 1 && scan_nb((uint32_t)DT) == 1) ? RBQ_SCAN_WAVES : 4)) void k_scan(ScanParams P) {
     extern __shared__ __align__(16) unsigned char smraw[];
     // blocks per scanner half-wave and tile: 1; a build option gives 2 at small dimensions (types.hpp: measured, not faster)
@@ -1094,7 +1096,10 @@ __global__ __launch_bounds__(kScanThreads, ((TR == 1 && scan_nb((uint32_t)DT) ==
             const uint8_t* ex = P.ex_codes + (size_t)sl * exb;
             float sacc;
             float fa, fr;
-            if (nunits <= (uint32_t)kExRegUnits) {
+            if constexpr (V != kVarAvx512) {
+                fa = P.f_add_ex[sl]; fr = P.f_rescale_ex[sl];
+                sacc = ex_dot_var_rt<V>(ex, s_q, gl, nunits, D / 16, ex_bits); // (already the group's sum)
+            } else if (nunits <= (uint32_t)kExRegUnits) {
                 uint4 u[kExRegUnits];
                 ex_load_all(u, ex, gl, nunits);
                 fa = P.f_add_ex[sl]; fr = P.f_rescale_ex[sl];
@@ -1105,7 +1110,7 @@ __global__ __launch_bounds__(kScanThreads, ((TR == 1 && scan_nb((uint32_t)DT) ==
                 asm volatile("" : "+v"(fa), "+v"(fr));
                 sacc = ex_bits == 6 ? ex_dot_units<6>(ex, s_q, gl, nunits) : ex_dot_units<2>(ex, s_q, gl, nunits);
             }
-            sacc = group16_reduce(sacc);
+            if constexpr (V == kVarAvx512) sacc = group16_reduce(sacc);
             if (gl == 0) {
                 float tt2 = qc.scale * q_ip[e];
                 tt2 = tt2 + sacc;
@@ -1141,14 +1146,19 @@ __global__ __launch_bounds__(kScanThreads, ((TR == 1 && scan_nb((uint32_t)DT) ==
         // (no register pin on the four factor loads: it made the wave WAIT for them before the code units were even requested)
         const float fa0 = P.f_add_ex[sl0], fr0 = P.f_rescale_ex[sl0], fa1 = P.f_add_ex[sl1], fr1 = P.f_rescale_ex[sl1];
         float sa, sb;
-        if (kDualN) ex_dot_pair_all<(EX ? EX : 2), (kDualN ? (int)kNU : 1)>(p0, p1, s_q, gl, sa, sb);
+        if constexpr (V != kVarAvx512) { // (not reached: the variants are DT = 0 instantiations, which never pair)
+            sa = ex_dot_var_rt<V>(P.ex_codes + (size_t)sl0 * exb, s_q, gl, nunits, D / 16, ex_bits);
+            sb = ex_dot_var_rt<V>(P.ex_codes + (size_t)sl1 * exb, s_q, gl, nunits, D / 16, ex_bits);
+        } else if (kDualN) ex_dot_pair_all<(EX ? EX : 2), (kDualN ? (int)kNU : 1)>(p0, p1, s_q, gl, sa, sb);
         else {
             const uint4 u0 = p0[0], u1 = p1[0];
             if (EX == 6) ex_dot_pair1<6>(u0, u1, s_q, gl, D / 16, sa, sb);
             else ex_dot_pair1<(EX ? EX : 2)>(u0, u1, s_q, gl, D / 16, sa, sb);
         }
-        sa = group16_reduce(sa);
-        sb = group16_reduce(sb);
+        if constexpr (V == kVarAvx512) {
+            sa = group16_reduce(sa);
+            sb = group16_reduce(sb);
+        }
         if (gl == 0) {
             {
                 float tt2 = qc.scale * q_ip[e0];
@@ -1179,10 +1189,10 @@ __global__ __launch_bounds__(kScanThreads, ((TR == 1 && scan_nb((uint32_t)DT) ==
         return m;
     };
     // lower bound of one candidate as a function of its accumulator value: the exact operation sequence of
-    // the epilogue (compute_batch_distances_u16, AVX2 body: only the first op is fused), so floating-point
-    // monotonicity carries over to the bound below
+    // the epilogue (compute_batch_distances_u16, AVX2 body: only the first op is fused; kVarPortable: the scalar body, not
+    // fused at all), so floating-point monotonicity carries over to the bound below
     auto lb_of = [&](const Meta& m, float accu_f, float& ip, float& est) -> float {
-        ip = fmaf(qc.delta, accu_f, qc.sum_vl);
+        ip = epi_ip(qc.delta, accu_f, qc.sum_vl, V == kVarPortable);
         const float tt = ip + qc.k1x;
         const float rs = m.f_rescale * tt;
         est = m.f_add + m.g_add;

@@ -103,7 +103,8 @@ __device__ __forceinline__ float lane_shfl_f32(float v, uint32_t src_lane) {
 // EX: compile-time ex_bits (0/2/6) when DT != 0; ignored (runtime P.ex_bits) when DT == 0.  TR: registers per lane of the
 // top-k (1: top_k <= 63; 2: <= 127; 4: <= 255).  Not served here (k_scan does): MSTG scans, heaps outside the registers, and
 // instantiations whose code object reports spilled registers (k_scanw.hip).
-template <int DT, int EX, int TR>
+// V: numeric variant, as k_scan's (instantiated for DT = 0 only).
+template <int DT, int EX, int TR, int V = kVarAvx512>
 __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES)) void k_scanw(ScanParams P) {
     extern __shared__ __align__(16) unsigned char smraw[];
     const uint32_t Dc = DT ? (uint32_t)DT : P.Dc; // code/LUT dimension (x64)
@@ -166,9 +167,9 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
     struct Meta { float f_add, f_rescale, f_error, g_add, g_err, dotqc; };
     struct TileRegs { WorkItem wi; CodeRegs<DT> cc; Meta m; };
     // lower bound of one candidate as a function of its accumulator value: the exact operation sequence of the epilogue
-    // (compute_batch_distances_u16, AVX2 body: only the first op is fused)
+    // (compute_batch_distances_u16, AVX2 body: only the first op is fused; kVarPortable: none is)
     auto lb_of = [&](const Meta& m, float accu_f, float& ip, float& est) -> float {
-        ip = fmaf(qc.delta, accu_f, qc.sum_vl);
+        ip = epi_ip(qc.delta, accu_f, qc.sum_vl, V == kVarPortable);
         const float tt = ip + qc.k1x;
         const float rs = m.f_rescale * tt;
         est = m.f_add + m.g_add;
@@ -414,7 +415,8 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
                 float v_d0 = 0.0f;
                 if (ex_bits && has0) { // (group-uniform)
                     float sa = 0.0f;
-                    if (kPre) sa = ex_dot_one_regs<(EX ? EX : 2), (int)(kPre ? kNU : 1u), (DT ? DT / 16 : 1)>(ea, s_q, gl);
+                    if constexpr (V != kVarAvx512) sa = ex_dot_var_rt<V>(P.ex_codes + (size_t)sl0 * exb, s_q, gl, nunits, D / 16, ex_bits);
+                    else if (kPre) sa = ex_dot_one_regs<(EX ? EX : 2), (int)(kPre ? kNU : 1u), (DT ? DT / 16 : 1)>(ea, s_q, gl);
                     else {
                         const uint8_t* ex = P.ex_codes + (size_t)sl0 * exb;
                         if (nunits <= (uint32_t)kExRegUnits) {
@@ -423,7 +425,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
                             sa = ex_bits == 6 ? ex_dot_all<6>(u, s_q, gl, nunits) : ex_dot_all<2>(u, s_q, gl, nunits);
                         } else sa = ex_bits == 6 ? ex_dot_units<6>(ex, s_q, gl, nunits) : ex_dot_units<2>(ex, s_q, gl, nunits);
                     }
-                    sa = group16_reduce(sa);
+                    if constexpr (V == kVarAvx512) sa = group16_reduce(sa);
                     float tt2 = qc.scale * ip0;
                     tt2 = tt2 + sa;
                     tt2 = tt2 + qc.kbx;

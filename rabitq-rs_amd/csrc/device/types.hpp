@@ -10,6 +10,9 @@ namespace rbq {
 
 constexpr int kThreads = 256;
 
+// numeric variants (RBQ_NUMERIC_* of rbq.h; kernels.hpp says what each reproduces)
+enum : int { kVarAvx512 = 0, kVarAvx2 = 1, kVarPortable = 2 };
+
 struct QueryConsts {
     float delta, sum_vl, k1x, kbx, scale, qnorm;
     float qnorm2;     // |q|^2 of the rotated query (approximate ranking, rank_mfma.hpp)
@@ -119,6 +122,8 @@ struct ScanParams {
     uint32_t* tie_log;
     uint32_t tie_log_cap;
     unsigned int* tie_stats;      // [4] counters: replays, entries replayed, real heap operations, overflowed logs (or null)
+    uint32_t numeric_variant;     // host-side dispatch only: kVarAvx512 / kVarAvx2 / kVarPortable (kernels.hpp) picks the
+                                  // instantiation; the kernels never read it
 };
 // traffic counters kept while a profile is open (rbq_profile_begin/end); [0] is written by the select kernels
 enum { kProfVectorsProbed = 0, kProfCodeBlocks = 1, kProfMetaBlocks = 2, kProfStreamEntries = 3, kProfExEvals = 4,

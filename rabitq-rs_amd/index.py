@@ -114,6 +114,10 @@ def lib():
         L.rbq_profile_stage_samples.argtypes = [vp, C.c_char_p, vp, C.c_uint64]
         L.rbq_profile_counters.restype = C.c_int
         L.rbq_profile_counters.argtypes = [vp, vp, C.c_uint32]
+        L.rbq_index_set_numeric_variant.restype = C.c_int
+        L.rbq_index_set_numeric_variant.argtypes = [vp, C.c_int]
+        L.rbq_index_numeric_variant.restype = C.c_int
+        L.rbq_index_numeric_variant.argtypes = [vp]
         _LIB = L
     return _LIB
 
@@ -310,6 +314,23 @@ class IvfRabitqIndex:
 
     def set_option(self, name, value):
         _check(lib().rbq_debug_set_option(self._h, name.encode(), int(value)))
+
+    def set_numeric_variant(self, variant):
+        """Which build of the reference the scores reproduce bit for bit: "native_avx512" (default: the crate built in its own
+        checkout on an AVX-512 host), "native_avx2" (the same on an AVX2-only host) or "portable" (RUSTFLAGS="" builds: crates.io
+        dependents, the PyPI wheel).  An int is passed through as RBQ_NUMERIC_* (anything else is rejected by the library)."""
+        if isinstance(variant, str):
+            if variant not in _abi.NUMERIC_VARIANTS:
+                from . import RabitqError
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "unknown numeric variant %r (one of %s)" % (variant, ", ".join(_abi.NUMERIC_VARIANTS)))
+            variant = _abi.NUMERIC_VARIANTS[variant]
+        _check(lib().rbq_index_set_numeric_variant(self._h, int(variant)))
+
+    @property
+    def numeric_variant(self):
+        """The current numeric variant by name ("native_avx512", "native_avx2" or "portable")."""
+        v = lib().rbq_index_numeric_variant(self._h)
+        return {i: n for n, i in _abi.NUMERIC_VARIANTS.items()}[v]
 
     def stage_resources(self, nq, top_k, nprobe):
         """{stage: {workgroups, threads, vgprs, lds_bytes, scratch_bytes}} of the kernels a call of this shape launches (nothing runs)"""
