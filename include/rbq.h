@@ -193,6 +193,8 @@ int rbq_posting_scan_batch(const rbq_index* idx, const float* queries, uint64_t 
                            uint32_t top_k, const uint32_t* list_ids, const uint32_t* list_counts,
                            uint32_t max_lists, uint64_t* out_ids, float* out_scores, uint32_t* out_counts);
 
+
+
 /* Same operation on DEVICE pointers (queries and outputs already in HBM of the index's device), ENQUEUED on
  * `hip_stream` (a hipStream_t passed as void*, NULL = default stream) and returning without host
  * synchronisation: results are valid once the stream reaches this point. Each stream gets its own scratch
@@ -333,4 +335,8 @@ uint32_t rbq_abi_version(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* The brute-force index (BruteForceRabitqIndex): rbq_bf_* in the companion header. */
+#include "rbq_bf.h"
+
 #endif /* RBQ_H */

@@ -133,6 +133,7 @@ extern "C" {
 const KNOWN_DETAILS: &[&str] = &[
     "unrecognized file header",
     "unsupported index format version (expected V3 with unified memory layout)",
+    "unsupported index format version",
     "dimension must be positive",
     "padded_dim must be >= dim",
     "unknown metric tag",

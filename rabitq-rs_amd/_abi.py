@@ -28,3 +28,12 @@ class ListView(C.Structure):
 class Diag(C.Structure):
     _fields_ = [("estimated", C.c_uint64), ("skipped_by_lower_bound", C.c_uint64),
                 ("extended_evaluations", C.c_uint64)]
+
+
+BF_FACTORS = ("delta", "vl", "f_add", "f_rescale", "f_error", "residual_norm", "f_add_ex", "f_rescale_ex")
+
+
+class BfView(C.Structure):
+    """rbq_bf_view: the per-vector arrays of a brute-force index."""
+    _fields_ = [("n", C.c_uint64), ("bin_codes", C.POINTER(C.c_uint8)), ("ex_codes", C.POINTER(C.c_uint8)),
+                ("ex_len", C.c_uint64)] + [(f, C.POINTER(C.c_float)) for f in BF_FACTORS]

@@ -1,0 +1,190 @@
+"""`BruteForceRabitqIndex` (reference src/brute_force.rs) over the C ABI of include/rbq.h (rbq_bf_*).
+
+Every vector is evaluated for every query on the GPU (k_bf_dist / k_bf_select); ids, counts and score bits equal the
+crate's.  Training runs on the CPU builder (builder.train_bruteforce), as for the IVF index."""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _abi
+from .index import _check, _detail  # noqa: F401  (shared error mapping)
+
+_BOUND = False
+
+
+def lib():
+    """librbq.so with the rbq_bf_* signatures bound (the same library object as index.lib())."""
+    global _BOUND
+    from .index import lib as base
+    L = base()
+    if not _BOUND:
+        vp = C.c_void_p
+        L.rbq_bf_create.restype = C.c_int
+        L.rbq_bf_create.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
+        L.rbq_bf_load_rbf1.restype = C.c_int
+        L.rbq_bf_load_rbf1.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp)]
+        L.rbq_bf_save_rbf1.restype = C.c_int
+        L.rbq_bf_save_rbf1.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
+        L.rbq_bf_free_bytes.restype = None
+        L.rbq_bf_free_bytes.argtypes = [C.POINTER(C.c_uint8)]
+        L.rbq_bf_destroy.restype = None
+        L.rbq_bf_destroy.argtypes = [vp]
+        L.rbq_bf_len.restype = C.c_uint64
+        L.rbq_bf_len.argtypes = [vp]
+        for n in ("rbq_bf_dim", "rbq_bf_padded_dim"):
+            getattr(L, n).restype = C.c_uint32
+            getattr(L, n).argtypes = [vp]
+        L.rbq_bf_search_batch.restype = C.c_int
+        L.rbq_bf_search_batch.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
+        L.rbq_bf_debug_heap_stats.restype = None
+        L.rbq_bf_debug_heap_stats.argtypes = [vp, vp]
+        _BOUND = True
+    return L
+
+
+@dataclass(frozen=True)
+class BruteForceSearchParams:
+    top_k: int
+
+
+@dataclass(frozen=True)
+class BruteForceSearchResult:
+    id: int
+    score: float
+
+
+def _filter_words(allowed_ids):
+    allowed = np.asarray(sorted(set(int(i) for i in allowed_ids)), dtype=np.uint64)
+    nbits = int(allowed.max()) + 1 if allowed.size else 0
+    words = np.zeros((nbits + 31) // 32 or 1, np.uint32)
+    if allowed.size:
+        np.bitwise_or.at(words, (allowed >> np.uint64(5)).astype(np.int64),
+                         (np.uint32(1) << (allowed & np.uint64(31)).astype(np.uint32)))
+    return words, nbits
+
+
+class BruteForceRabitqIndex:
+    """Device-resident brute-force RaBitQ index; methods mirror reference src/brute_force.rs."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @staticmethod
+    def _dev(device):
+        return -1 if device is None else int(device)
+
+    @classmethod
+    def train(cls, data, total_bits, metric, rotator_type, seed, use_faster_config, device=None):
+        """`BruteForceRabitqIndex::train` (src/brute_force.rs:214-287) on the CPU builder, then uploaded."""
+        from . import builder
+        return cls.from_built(builder.train_bruteforce(data, total_bits, metric, rotator_type, seed, use_faster_config), device)
+
+    @classmethod
+    def from_built(cls, built, device=None):
+        h = C.c_void_p()
+        _check(lib().rbq_bf_create(C.cast(built.hdr_ptr, C.c_void_p), C.cast(built.view_ptr, C.c_void_p), cls._dev(device), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def load_from_bytes(cls, data, device=None):
+        """`load_from_reader` (src/brute_force.rs:395-520) straight into HBM."""
+        h = C.c_void_p()
+        buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
+        _check(lib().rbq_bf_load_rbf1(buf, len(data), cls._dev(device), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def load_from_path(cls, path, device=None):
+        try:
+            with open(path, "rb") as f:
+                data = f.read()
+        except OSError as e:
+            from . import RabitqError
+            raise RabitqError(_abi.RBQ_IO, str(e))
+        return cls.load_from_bytes(data, device)
+
+    def save_to_bytes(self):
+        """`save_to_writer` (src/brute_force.rs:305-386), byte for byte."""
+        p = C.POINTER(C.c_uint8)()
+        n = C.c_uint64()
+        _check(lib().rbq_bf_save_rbf1(self._h, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            lib().rbq_bf_free_bytes(p)
+
+    def save_to_path(self, path):
+        data = self.save_to_bytes()
+        try:
+            with open(path, "wb") as f:
+                f.write(data)
+        except OSError as e:
+            from . import RabitqError
+            raise RabitqError(_abi.RBQ_IO, str(e))
+
+    def __len__(self):
+        return lib().rbq_bf_len(self._h)
+
+    def is_empty(self):
+        return len(self) == 0
+
+    @property
+    def dim(self):
+        return lib().rbq_bf_dim(self._h)
+
+    @property
+    def padded_dim(self):
+        return lib().rbq_bf_padded_dim(self._h)
+
+    def batch_search_raw(self, queries, params, filter_words=None, filter_nbits=0):
+        """Returns (ids[nq,k] u64, scores[nq,k] f32, counts[nq] u32)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq, qd = q.shape
+        k = int(params.top_k)
+        ids = np.full((nq, k), np.iinfo(np.uint64).max, np.uint64)
+        scores = np.full((nq, k), np.nan, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        fw = np.ascontiguousarray(filter_words, dtype=np.uint32) if filter_words is not None else None
+        _check(lib().rbq_bf_search_batch(self._h, q.ctypes.data, nq, qd, k, fw.ctypes.data if fw is not None else None,
+                                         int(filter_nbits), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        return ids, scores, counts
+
+    @staticmethod
+    def _results(ids, scores, counts, q):
+        return [BruteForceSearchResult(int(ids[q, i]), float(scores[q, i])) for i in range(int(counts[q]))]
+
+    def search(self, query, params):
+        """`search` (src/brute_force.rs:525-531)."""
+        ids, scores, counts = self.batch_search_raw(np.asarray(query, np.float32)[None, :], params)
+        return self._results(ids, scores, counts, 0)
+
+    def search_filtered(self, query, params, allowed_ids):
+        """`search_filtered` (src/brute_force.rs:535-543); `allowed_ids` plays the RoaringBitmap."""
+        words, nbits = _filter_words(allowed_ids)
+        ids, scores, counts = self.batch_search_raw(np.asarray(query, np.float32)[None, :], params, words, nbits)
+        return self._results(ids, scores, counts, 0)
+
+    def batch_search(self, queries, params):
+        """`search` for every row of `queries`, results in input order."""
+        ids, scores, counts = self.batch_search_raw(queries, params)
+        return [self._results(ids, scores, counts, q) for q in range(ids.shape[0])]
+
+    def heap_stats(self):
+        """{pushes, tie_pushes} of the BinaryHeap emulation since the index was created (rbq_bf_debug_heap_stats)."""
+        out = np.zeros(2, np.uint64)
+        lib().rbq_bf_debug_heap_stats(self._h, out.ctypes.data)
+        return {"pushes": int(out[0]), "tie_pushes": int(out[1])}
+
+    def close(self):
+        if self._h:
+            lib().rbq_bf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

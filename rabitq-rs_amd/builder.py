@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from ._abi import Header, ListView, RBQ_OK
+from ._abi import BF_FACTORS, BfView, Header, ListView, RBQ_OK
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -47,6 +47,14 @@ def lib():
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.rbq_build_pack_codes.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         L.rbq_build_rotate.argtypes = [C.POINTER(Header), C.c_void_p, C.c_void_p]
+        L.rbq_build_train_bruteforce.restype = C.c_int
+        L.rbq_build_train_bruteforce.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8,
+                                                 C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+        L.rbq_bf_built_header.restype = C.POINTER(Header)
+        L.rbq_bf_built_header.argtypes = [C.c_void_p]
+        L.rbq_bf_built_view.restype = C.POINTER(BfView)
+        L.rbq_bf_built_view.argtypes = [C.c_void_p]
+        L.rbq_bf_built_free.argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -173,3 +181,70 @@ def train(data, nlist, total_bits, metric, rotator_type, seed, use_faster_config
     """`IvfRabitqIndex::train` (src/ivf.rs:950-1021) with a plain Lloyd k-means harness."""
     cent, assign = kmeans(data, nlist, kmeans_iters, seed ^ 0x5A5A5A5A5A5A5A5A)
     return train_with_clusters(data, cent, assign, total_bits, metric, rotator_type, seed, use_faster_config)
+
+
+class BuiltBruteForce:
+    """Host-resident brute-force index: the per-vector arrays of `BruteForceRabitqIndex` (src/brute_force.rs:202-210)."""
+
+    def __init__(self, handle):
+        self._h = handle
+        self.hdr_ptr = lib().rbq_bf_built_header(handle)
+        self.view_ptr = lib().rbq_bf_built_view(handle)
+
+    @property
+    def header(self):
+        return self.hdr_ptr.contents
+
+    def __len__(self):
+        return int(self.view_ptr.contents.n)
+
+    def arrays(self):
+        """numpy copies: bin [n][D/8] u8, ex [n][ex_len] u8, and the 8 factor arrays by name."""
+        v, h = self.view_ptr.contents, self.header
+        n, D = int(v.n), int(h.padded_dim)
+        out = {"bin": np.ctypeslib.as_array(v.bin_codes, shape=(n, D // 8)).copy(),
+               "ex": (np.ctypeslib.as_array(v.ex_codes, shape=(n, int(v.ex_len))).copy() if v.ex_len
+                      else np.zeros((n, 0), np.uint8))}
+        for f in BF_FACTORS:
+            out[f] = np.ctypeslib.as_array(getattr(v, f), shape=(n,)).copy()
+        return out
+
+    def rotator_blob(self):
+        h = self.header
+        return bytes(np.ctypeslib.as_array(h.rotator_blob, shape=(int(h.rotator_len),))) if h.rotator_len else b""
+
+    def rotate(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        out = np.empty(self.header.padded_dim, np.float32)
+        lib().rbq_build_rotate(self.hdr_ptr, x.ctypes.data, out.ctypes.data)
+        return out
+
+    def close(self):
+        if self._h:
+            lib().rbq_bf_built_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def train_bruteforce(data, total_bits, metric, rotator_type, seed, use_faster_config):
+    """`BruteForceRabitqIndex::train` (src/brute_force.rs:214-287).  Errors in the crate's order."""
+    from . import RabitqError
+    from ._abi import RBQ_INVALID_CONFIG
+    data = np.ascontiguousarray(data, dtype=np.float32)
+    if data.ndim != 2 or data.shape[0] == 0:
+        raise RabitqError(RBQ_INVALID_CONFIG, "training data must be non-empty")
+    if not 1 <= int(total_bits) <= 16:
+        raise RabitqError(RBQ_INVALID_CONFIG, "total_bits must be between 1 and 16")
+    n, dim = data.shape
+    h = C.c_void_p()
+    rc = lib().rbq_build_train_bruteforce(data.ctypes.data, n, dim, int(total_bits), int(metric), int(rotator_type), int(seed),
+                                          int(bool(use_faster_config)), C.byref(h))
+    if rc != RBQ_OK:
+        raise RabitqError(rc, "total_bits %d (ex_bits %d) is not supported: only 1, 3 and 7 total bits" % (total_bits, total_bits - 1)
+                          if total_bits - 1 not in (0, 2, 6) else "train_bruteforce rejected its configuration")
+    return BuiltBruteForce(h)

@@ -194,4 +194,36 @@ hipError_t launch_centroid_arrays(const float* cent, uint32_t nlist, uint32_t D,
 hipError_t launch_rerank(const float* queries, uint32_t nq, uint32_t dim, const float* raw, uint64_t n_raw, int metric,
                          uint32_t top_k, uint64_t* ids, float* scores, const uint32_t* counts, hipStream_t s);
 
+// brute-force index (bf.hpp, k_bf.hip): distances of a (query sub-batch x vector chunk), then the per-query BinaryHeap replay
+struct BfDistParams {
+    const float* rot;          // [nq][D] rotated queries (k_prep)
+    const QueryConsts* consts; // [nq]
+    uint32_t nq, D, ex_bits;
+    uint64_t v0, nv;           // the chunk: vector ids v0 .. v0 + nv - 1
+    const uint8_t* bin;        // [n][D/8]
+    const uint8_t* ex;         // [n][D*ex_bits/8]
+    const float *f_add, *f_rescale, *f_add_ex, *f_rescale_ex; // [n]
+    const uint32_t* filter;    // dense id bitset or null
+    uint64_t filter_nbits;
+    float* dist;               // [nq][nv]
+};
+hipError_t launch_bf_dist(const BfDistParams& p, hipStream_t s);
+struct BfSelectParams {
+    const float* dist;         // [nq][nv]
+    uint32_t nq, top_k;
+    uint64_t v0, nv;
+    int metric;
+    int first, last;           // first / last vector chunk of the call
+    bool lds_heap;             // the heap lives in LDS during the launch (else in heap_d / heap_s)
+    float* heap_d;             // [nq][top_k + 1]: the heap between chunks (and during them when !lds_heap)
+    uint32_t* heap_s;
+    uint32_t* heap_len;        // [nq]
+    uint64_t* out_ids;         // [nq][top_k]
+    float* out_scores;
+    uint32_t* out_counts;      // [nq]
+    unsigned long long* stats; // [2]: heap pushes, pushes decided by a tie (rbq_bf_debug_heap_stats)
+};
+hipError_t launch_bf_select(const BfSelectParams& p, hipStream_t s);
+constexpr uint32_t kBfLdsHeapMaxTopK = 8191; // (top_k + 1) * 8 bytes of LDS heap <= 64 KiB
+
 } // namespace rbq

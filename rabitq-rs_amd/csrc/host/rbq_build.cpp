@@ -212,6 +212,7 @@ float const_scaling_factor(size_t dim, uint32_t ex_bits, uint64_t seed) {
 struct QV {
     std::vector<uint8_t> bin_packed, ex_packed;
     float f_add, f_rescale, f_error, f_add_ex, f_rescale_ex, delta, vl;
+    float residual_norm; // fourth output of compute_one_bit_factors (src/quantizer.rs:170): |residual|
 };
 
 void pack_binary_code(const uint8_t* bits, uint8_t* packed, size_t dim) {
@@ -282,6 +283,7 @@ void quantize_with_centroid(const float* data, const float* centroid, size_t dim
 
     // compute_one_bit_factors
     float l2_sqr = l2_norm_sqr(residual.data(), dim), l2_norm = std::sqrt(l2_sqr);
+    out.residual_norm = l2_norm;
     for (size_t i = 0; i < dim; ++i) tmp[i] = (float)bits[i] - 0.5f;
     float xu_norm_sqr = l2_norm_sqr(tmp.data(), dim);
     float ip_resi_xucb = dot8(residual.data(), tmp.data(), dim);
@@ -591,5 +593,78 @@ int rbq_build_kmeans(const float* data, uint64_t n, uint32_t dim, uint64_t k, in
     }
     return RBQ_OK;
 }
+
+} // extern "C"
+
+// ---------------------------------------------------------------- brute-force index
+struct rbq_bf_built {
+    rbq_header hdr;
+    std::vector<uint8_t> rotator_blob, bin, ex;
+    std::vector<float> f[8]; // delta, vl, f_add, f_rescale, f_error, residual_norm, f_add_ex, f_rescale_ex
+    rbq_bf_view view;
+};
+
+extern "C" {
+
+// BruteForceRabitqIndex::train (src/brute_force.rs:214-287): rotate every vector, quantize_with_centroid against a zero
+// centroid in id order.  Errors in the crate's order: empty data, total_bits outside 1..16 (then what this project cannot
+// serve: ex_bits outside {0, 2, 6}, an unknown rotator, dim 0).
+int rbq_build_train_bruteforce(const float* data, uint64_t n, uint32_t dim, uint32_t total_bits, uint8_t metric,
+                               uint8_t rotator_type, uint64_t seed, int use_faster_config, rbq_bf_built** out) {
+    *out = nullptr;
+    if (n == 0) return RBQ_INVALID_CONFIG;                             // "training data must be non-empty"
+    if (total_bits == 0 || total_bits > 16) return RBQ_INVALID_CONFIG; // "total_bits must be between 1 and 16"
+    const uint32_t ex_bits = total_bits - 1;
+    if (ex_bits != 0 && ex_bits != 2 && ex_bits != 6) return RBQ_INVALID_CONFIG;
+    if (dim == 0 || metric > 1 || rotator_type > RBQ_ROTATOR_FHT_KAC) return RBQ_INVALID_CONFIG;
+    const uint32_t D = rotator_type == RBQ_ROTATOR_FHT_KAC ? (dim + 63) / 64 * 64 : dim;
+    rbq_bf_built* b = new rbq_bf_built();
+    std::memset(&b->hdr, 0, sizeof b->hdr);
+    b->hdr.dim = dim; b->hdr.padded_dim = D; b->hdr.metric = metric; b->hdr.rotator = rotator_type; b->hdr.ex_bits = (uint8_t)ex_bits;
+    if (rotator_type == RBQ_ROTATOR_FHT_KAC) {
+        Rng rng(seed);
+        b->rotator_blob.resize(4 * D / 8);
+        for (auto& x : b->rotator_blob) x = (uint8_t)(rng.next() >> 56);
+    } else {
+        std::vector<float> m = make_matrix_rotator(D, seed);
+        b->rotator_blob.resize(m.size() * 4);
+        std::memcpy(b->rotator_blob.data(), m.data(), m.size() * 4);
+    }
+    const bool has_t = use_faster_config && ex_bits > 0;
+    const float t_const = has_t ? const_scaling_factor(D, ex_bits, seed) : 0.0f;
+    const size_t bin_len = (D + 7) / 8;
+    // ex_code_packed as quantize_with_centroid leaves it: D/16*2 zero bytes for 1-bit indexes (src/quantizer.rs:212-219)
+    const size_t ex_len = ex_bits == 0 ? (size_t)D / 16 * 2 : (size_t)D * ex_bits / 8;
+    b->bin.assign(n * bin_len, 0);
+    b->ex.assign(n * ex_len, 0);
+    for (auto& a : b->f) a.assign(n, 0.0f);
+    const std::vector<float> zero(D, 0.0f);
+#pragma omp parallel
+    {
+        std::vector<float> rv(D);
+        QV qv;
+#pragma omp for schedule(static)
+        for (int64_t i = 0; i < (int64_t)n; ++i) { // (each vector independently: the crate's sequential order changes nothing)
+            if (rotator_type == RBQ_ROTATOR_FHT_KAC) fht_kac_rotate(dim, D, b->rotator_blob.data(), data + (size_t)i * dim, rv.data());
+            else matrix_rotate(dim, D, (const float*)b->rotator_blob.data(), data + (size_t)i * dim, rv.data());
+            quantize_with_centroid(rv.data(), zero.data(), D, total_bits, has_t, t_const, metric, qv);
+            std::memcpy(b->bin.data() + (size_t)i * bin_len, qv.bin_packed.data(), bin_len);
+            if (ex_bits) std::memcpy(b->ex.data() + (size_t)i * ex_len, qv.ex_packed.data(), ex_len);
+            const float fs[8] = {qv.delta, qv.vl, qv.f_add, qv.f_rescale, qv.f_error, qv.residual_norm, qv.f_add_ex, qv.f_rescale_ex};
+            for (int k = 0; k < 8; ++k) b->f[k][i] = fs[k];
+        }
+    }
+    b->hdr.n_vectors = n;
+    b->hdr.rotator_blob = b->rotator_blob.data(); b->hdr.rotator_len = b->rotator_blob.size();
+    rbq_bf_view& v = b->view;
+    v.n = n; v.bin_codes = b->bin.data(); v.ex_codes = b->ex.empty() ? nullptr : b->ex.data(); v.ex_len = ex_len;
+    v.delta = b->f[0].data(); v.vl = b->f[1].data(); v.f_add = b->f[2].data(); v.f_rescale = b->f[3].data();
+    v.f_error = b->f[4].data(); v.residual_norm = b->f[5].data(); v.f_add_ex = b->f[6].data(); v.f_rescale_ex = b->f[7].data();
+    *out = b;
+    return RBQ_OK;
+}
+const rbq_header* rbq_bf_built_header(const rbq_bf_built* b) { return &b->hdr; }
+const rbq_bf_view* rbq_bf_built_view(const rbq_bf_built* b) { return &b->view; }
+void rbq_bf_built_free(rbq_bf_built* b) { delete b; }
 
 } // extern "C"

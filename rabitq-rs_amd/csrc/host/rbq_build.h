@@ -31,6 +31,16 @@ uint32_t rbq_build_crc32(const uint8_t* p, uint64_t n);
 void rbq_build_rotate(const rbq_header* h, const float* in, float* out);
 int  rbq_build_kmeans(const float* data, uint64_t n, uint32_t dim, uint64_t k, int iters, uint64_t seed,
                       float* centroids, uint32_t* assignments);
+
+/* BruteForceRabitqIndex::train (reference src/brute_force.rs:214-287): data [n][dim]; every vector quantised against a
+ * zero centroid.  total_bits 1, 3 or 7; rotator MATRIX or FHT_KAC.  The view's ex_len is padded_dim/8 for 1-bit indexes
+ * (the zero bytes the crate's quantiser leaves in ex_code_packed). */
+typedef struct rbq_bf_built rbq_bf_built;
+int rbq_build_train_bruteforce(const float* data, uint64_t n, uint32_t dim, uint32_t total_bits, uint8_t metric,
+                               uint8_t rotator_type, uint64_t seed, int use_faster_config, rbq_bf_built** out);
+const rbq_header*  rbq_bf_built_header(const rbq_bf_built* b);
+const rbq_bf_view* rbq_bf_built_view(const rbq_bf_built* b);
+void               rbq_bf_built_free(rbq_bf_built* b);
 #ifdef __cplusplus
 }
 #endif

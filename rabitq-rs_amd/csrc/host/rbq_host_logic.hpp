@@ -149,6 +149,111 @@ inline int rbq1_parse(const void* bytes, size_t len, rbq_header* hout, std::vect
     return RBQ_OK;
 }
 
+// ---- RBF1: the persisted form of BruteForceRabitqIndex (reference src/brute_force.rs:305-520) ----------------------------
+// One vector's record is  binary_code_packed [ceil(D/8)] | ex_code_packed [ex_len] | delta vl f_add f_rescale f_error
+// residual_norm f_add_ex f_rescale_ex (8 x f32 LE); records follow each other with no padding.
+struct BfSrc {
+    const uint8_t* rec0 = nullptr; // first record
+    size_t stride = 0;             // bytes per record
+    size_t bin_len = 0, ex_len = 0;
+    uint64_t n = 0;
+};
+
+// Parses and validates an RBF1 stream in place.  The checks, their order and their strings are load_from_reader's
+// (brute_force.rs:395-520; DynamicRotator::deserialize src/rotation.rs:213-219,491-497); truncation is RBQ_IO "failed to fill
+// whole buffer", as in rbq1_parse.  The reader expects ceil(D*ex/8) ex-code bytes per vector and none when ex_bits == 0, so
+// the 1-bit streams the crate writes (D/8 zero bytes of ex code per vector, see rbf1_write) end in "checksum mismatch" here as
+// they do in the crate.  What this build cannot serve (ex_bits outside {0,2,6} ...) is left to the caller.
+inline int rbf1_parse(const void* bytes, size_t len, rbq_header* hout, BfSrc* out, std::string* detail) {
+    auto fail = [&](int code, const char* msg) { if (detail) *detail = msg; return code; };
+    auto eof = [&] { return fail(RBQ_IO, "failed to fill whole buffer"); };
+    if (!bytes) return fail(RBQ_IO, "null buffer");
+    Reader r{(const uint8_t*)bytes, len};
+    char magic[4];
+    if (!r.take(magic, 4)) return eof();
+    if (std::memcmp(magic, "RBF1", 4) != 0) return fail(RBQ_INVALID_PERSISTENCE, "unrecognized file header");
+    uint32_t version;
+    if (!r.take(&version, 4)) return eof();
+    if (version != 1) return fail(RBQ_INVALID_PERSISTENCE, "unsupported index format version");
+    rbq_header h;
+    std::memset(&h, 0, sizeof h);
+    uint8_t tag;
+    if (!r.take(&h.dim, 4)) return eof();
+    if (h.dim == 0) return fail(RBQ_INVALID_PERSISTENCE, "dimension must be positive");
+    if (!r.take(&h.padded_dim, 4)) return eof();
+    if (h.padded_dim < h.dim) return fail(RBQ_INVALID_PERSISTENCE, "padded_dim must be >= dim");
+    if (!r.take(&tag, 1)) return eof();
+    if (tag > 1) return fail(RBQ_INVALID_PERSISTENCE, "unknown metric tag");
+    h.metric = tag;
+    if (!r.take(&tag, 1)) return eof();
+    if (tag > 1) return fail(RBQ_INVALID_PERSISTENCE, "unknown rotator type tag");
+    h.rotator = tag;
+    uint8_t ex_bits, total_bits;
+    if (!r.take(&ex_bits, 1)) return eof();
+    if (ex_bits > 16) return fail(RBQ_INVALID_PERSISTENCE, "ex_bits out of range");
+    if (!r.take(&total_bits, 1)) return eof();
+    if (total_bits == 0 || total_bits > 16) return fail(RBQ_INVALID_PERSISTENCE, "total_bits out of range");
+    if ((uint8_t)(total_bits - 1) != ex_bits) return fail(RBQ_INVALID_PERSISTENCE, "total_bits does not match ex_bits");
+    h.ex_bits = ex_bits;
+    uint64_t count, rot_len;
+    if (!r.take(&count, 8) || !r.take(&rot_len, 8)) return eof();
+    const uint8_t* blob = r.view(rot_len);
+    if (!blob) return eof();
+    h.rotator_blob = blob; h.rotator_len = rot_len; h.n_vectors = count; h.n_lists = 0;
+    { // DynamicRotator::deserialize length checks
+        const uint64_t want = h.rotator == RBQ_ROTATOR_FHT_KAC ? (uint64_t)4 * h.padded_dim / 8 : (uint64_t)h.padded_dim * h.padded_dim * 4;
+        if (rot_len != want)
+            return fail(RBQ_INVALID_PERSISTENCE, h.rotator == RBQ_ROTATOR_FHT_KAC ? "FHT rotator flip bits length mismatch" : "rotator matrix length mismatch");
+    }
+    BfSrc b;
+    b.n = count;
+    b.bin_len = ((size_t)h.padded_dim + 7) / 8;
+    b.ex_len = ex_bits ? ((size_t)h.padded_dim * ex_bits + 7) / 8 : 0;
+    b.stride = b.bin_len + b.ex_len + 32;
+    if (count > (len - r.off) / b.stride) return eof(); // the records do not fit what is left (also guards the product below)
+    b.rec0 = r.view((size_t)count * b.stride);
+    if (!b.rec0) return eof();
+    const size_t body_end = r.off;
+    uint32_t stored;
+    if (!r.take(&stored, 4)) return eof();
+    if (crc32_ieee((const uint8_t*)bytes + 8, body_end - 8) != stored) return fail(RBQ_INVALID_PERSISTENCE, "checksum mismatch");
+    *hout = h;
+    *out = b;
+    return RBQ_OK;
+}
+
+// save_to_writer (brute_force.rs:305-386), byte for byte: header fields, rotator blob, then for every vector its binary code,
+// `ex_len` bytes of ex code and the 8 factors, then the CRC-32 of everything after the version field.  `ex_len` is what the
+// index holds per vector: ceil(D*ex/8) for ex_bits > 0; for ex_bits == 0 the crate's freshly trained vectors carry
+// D/16*2 zero bytes (quantizer.rs:212-219) that it writes and its own reader does not expect, a loaded index carries none.
+// bin / ex: [n][bin_len] / [n][ex_len] (ex may be null when ex_len == 0 or for zeros); f[8]: the 8 factor arrays [n].
+inline std::vector<uint8_t> rbf1_write(const rbq_header& h, uint64_t n, const uint8_t* bin, const uint8_t* ex, size_t ex_len,
+                                       const float* const f[8]) {
+    const size_t bin_len = ((size_t)h.padded_dim + 7) / 8, stride = bin_len + ex_len + 32;
+    std::vector<uint8_t> o;
+    o.reserve(8 + 4 + 4 + 4 + 16 + h.rotator_len + (size_t)n * stride + 4);
+    auto put = [&](const void* p, size_t k) { const uint8_t* c = (const uint8_t*)p; o.insert(o.end(), c, c + k); };
+    put("RBF1", 4);
+    const uint32_t version = 1;
+    put(&version, 4);
+    put(&h.dim, 4);
+    put(&h.padded_dim, 4);
+    const uint8_t tags[4] = {h.metric, h.rotator, h.ex_bits, (uint8_t)(h.ex_bits + 1)};
+    put(tags, 4);
+    put(&n, 8);
+    put(&h.rotator_len, 8);
+    if (h.rotator_len) put(h.rotator_blob, h.rotator_len);
+    const std::vector<uint8_t> zeros(ex_len, 0);
+    for (uint64_t v = 0; v < n; ++v) {
+        put(bin + v * bin_len, bin_len);
+        put(ex ? ex + v * ex_len : zeros.data(), ex_len);
+        for (int k = 0; k < 8; ++k) put(&f[k][v], 4);
+    }
+    const uint32_t crc = crc32_ieee(o.data() + 8, o.size() - 8);
+    put(&crc, 4);
+    return o;
+}
+
 // layout of one sub-batch's results in the packed device / pinned buffers
 struct OutPack {
     size_t o_ids, o_scores, o_counts, o_diag, total;

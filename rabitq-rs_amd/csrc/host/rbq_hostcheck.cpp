@@ -36,6 +36,41 @@ int rbq_hostcheck_parse(const void* bytes, size_t len, char* detail, size_t deta
     return RBQ_OK;
 }
 
+// rbf1_parse + a read of every byte the parsed view claims; then rbf1_write of what was parsed, whose bytes must equal the input
+// (*same = 1).  Returns the parser's code.
+int rbq_hostcheck_parse_rbf1(const void* bytes, size_t len, char* detail, size_t detail_cap, uint64_t* n_vectors, uint64_t* checksum,
+                             int* same) {
+    rbq_header h;
+    rbq_host::BfSrc b;
+    std::string msg;
+    const int rc = rbq_host::rbf1_parse(bytes, len, &h, &b, &msg);
+    if (detail && detail_cap) {
+        const size_t c = std::min(detail_cap - 1, msg.size());
+        std::memcpy(detail, msg.data(), c);
+        detail[c] = 0;
+    }
+    if (rc != RBQ_OK) return rc;
+    uint64_t sum = 0;
+    for (size_t i = 0; i < h.rotator_len; ++i) sum += h.rotator_blob[i];
+    std::vector<uint8_t> bin(b.n * b.bin_len), ex(b.n * b.ex_len);
+    std::vector<float> f[8];
+    for (auto& a : f) a.resize(b.n);
+    for (uint64_t v = 0; v < b.n; ++v) {
+        const uint8_t* r = b.rec0 + v * b.stride;
+        for (size_t i = 0; i < b.stride; ++i) sum += r[i];
+        std::memcpy(bin.data() + v * b.bin_len, r, b.bin_len);
+        std::memcpy(ex.data() + v * b.ex_len, r + b.bin_len, b.ex_len);
+        for (int k = 0; k < 8; ++k) std::memcpy(&f[k][v], r + b.bin_len + b.ex_len + 4 * k, 4);
+    }
+    const float* fp[8];
+    for (int k = 0; k < 8; ++k) fp[k] = f[k].data();
+    const std::vector<uint8_t> again = rbq_host::rbf1_write(h, b.n, bin.data(), ex.data(), b.ex_len, fp);
+    if (same) *same = again.size() == len && std::memcmp(again.data(), bytes, len) == 0;
+    if (n_vectors) *n_vectors = b.n;
+    if (checksum) *checksum = sum;
+    return RBQ_OK;
+}
+
 uint32_t rbq_hostcheck_crc32(const void* p, size_t n) { return rbq_host::crc32_ieee((const uint8_t*)p, n); }
 
 void rbq_hostcheck_outpack(uint64_t n, uint32_t top_k, int diag, uint64_t out[5]) {
