@@ -120,6 +120,17 @@ int rbq_index_load_rbq1(const void* bytes, size_t len,
 int rbq_index_build_device(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
                            uint64_t n, float t_const, int device, rbq_index** out);
 
+/* rbq_index_build_device with the rescale factor chosen by `rescale`:
+ *   RBQ_RESCALE_CONST    RabitqConfig::faster — t_const for every vector (exactly rbq_index_build_device)
+ *   RBQ_RESCALE_OPTIMAL  RabitqConfig::new — every vector's own best_rescale_factor (src/quantizer.rs:337-427), searched
+ *                        on the GPU; t_const is ignored.  The result is identical, array for array, to rbq_index_create
+ *                        over train_with_clusters(..., use_faster_config = false).  Moot for 1-bit indexes (ex_bits 0).
+ * Any other value is RBQ_INVALID_CONFIG. */
+#define RBQ_RESCALE_CONST   0  /* RabitqConfig::faster: t_const for every vector (t_const > 0 when ex_bits > 0) */
+#define RBQ_RESCALE_OPTIMAL 1  /* RabitqConfig::new: best_rescale_factor per vector; t_const ignored            */
+int rbq_index_build_device_ex(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
+                              uint64_t n, int rescale, float t_const, int device, rbq_index** out);
+
 /* The same encoder fed chunk by chunk, for indexes whose raw vectors do not fit in HBM at once (100 M x 768 f32 =
  * 307 GB): `train_with_clusters` (src/ivf.rs:1025-1215) builds cluster by cluster and never needs all vectors
  * resident either.  Protocol:
@@ -137,6 +148,9 @@ int rbq_index_build_device(const rbq_header* hdr, const float* centroids, const 
  *   abort   frees a builder that was not finished. */
 int rbq_build_stream_begin(const rbq_header* hdr, const float* centroids, const uint32_t* list_sizes, float t_const,
                            int device, rbq_builder** out);
+/* rbq_build_stream_begin with a rescale mode (RBQ_RESCALE_*, as for rbq_index_build_device_ex). */
+int rbq_build_stream_begin_ex(const rbq_header* hdr, const float* centroids, const uint32_t* list_sizes, int rescale,
+                              float t_const, int device, rbq_builder** out);
 int rbq_build_stream_push(rbq_builder* b, const float* vectors, const uint32_t* assign, uint64_t first_id, uint64_t count);
 int rbq_build_stream_finish(rbq_builder* b, int n_devices, const int* devices, rbq_index** out);
 void rbq_build_stream_abort(rbq_builder* b);
@@ -291,6 +305,9 @@ uint64_t rbq_debug_heap_restarts(const rbq_index* idx);
 /* Diagnostic: copy one of the index's device arrays ("blocks", "ids", "ex", "fadd_ex", "fres_ex", "bsum", "lsum", "bsumx",
  * "centroids", "list_gb0", "list_n") to the host; `bytes` must be the array's exact size. */
 int rbq_debug_copy_index(rbq_index* idx, const char* name, void* dst, uint64_t bytes);
+/* test hook: t of best_rescale_factor for n rows of o = |r_i| / norm(r) (host [n][dim] f32, every value in [0, 1];
+ * dim <= 2048, 1 <= ex_bits <= 7) -> out_t [n] f64, computed by the device encoder's kernel */
+int rbq_debug_best_rescale(const float* o_abs, uint64_t n, uint32_t dim, uint32_t ex_bits, int device, double* out_t);
 /* Diagnostic: copy an intermediate buffer ("rot", "lut", "consts", "scores", "probe", "nstream", "wl", "nvec", "dead_skipped") of the
  * workspace that rbq_search_batch_device bound to `hip_stream`; the caller has synchronised that stream. */
 int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name, void* dst, uint64_t bytes);

@@ -84,6 +84,9 @@ pub const RBQ_EMPTY_INDEX: c_int = 3;
 pub const RBQ_IO: c_int = 4;
 pub const RBQ_INVALID_PERSISTENCE: c_int = 5;
 pub const RBQ_DEVICE: c_int = 6;
+// rescale modes of rbq_index_build_device_ex / rbq_build_stream_begin_ex
+pub const RBQ_RESCALE_CONST: c_int = 0; // RabitqConfig::faster
+pub const RBQ_RESCALE_OPTIMAL: c_int = 1; // RabitqConfig::new
 
 extern "C" {
     fn rbq_index_create(hdr: *const RbqHeader, lists: *const RbqListView, n_devices: c_int, devices: *const c_int,
@@ -92,8 +95,12 @@ extern "C" {
                            out: *mut *mut RbqIndex) -> c_int;
     fn rbq_index_build_device(hdr: *const RbqHeader, centroids: *const f32, d_data: *const f32, d_assign: *const u32,
                               n: u64, t_const: f32, device: c_int, out: *mut *mut RbqIndex) -> c_int;
+    fn rbq_index_build_device_ex(hdr: *const RbqHeader, centroids: *const f32, d_data: *const f32, d_assign: *const u32,
+                                 n: u64, rescale: c_int, t_const: f32, device: c_int, out: *mut *mut RbqIndex) -> c_int;
     fn rbq_build_stream_begin(hdr: *const RbqHeader, centroids: *const f32, list_sizes: *const u32, t_const: f32,
                               device: c_int, out: *mut *mut RbqBuilder) -> c_int;
+    fn rbq_build_stream_begin_ex(hdr: *const RbqHeader, centroids: *const f32, list_sizes: *const u32, rescale: c_int,
+                                 t_const: f32, device: c_int, out: *mut *mut RbqBuilder) -> c_int;
     fn rbq_build_stream_push(b: *mut RbqBuilder, vectors: *const f32, assign: *const u32, first_id: u64, count: u64) -> c_int;
     fn rbq_build_stream_finish(b: *mut RbqBuilder, n_devices: c_int, devices: *const c_int, out: *mut *mut RbqIndex) -> c_int;
     fn rbq_build_stream_abort(b: *mut RbqBuilder);
@@ -487,6 +494,8 @@ fn _boundary_is_complete() {
         rbq_index_create as usize,
         rbq_index_build_device as usize,
         rbq_build_stream_begin as usize,
+        rbq_index_build_device_ex as usize,
+        rbq_build_stream_begin_ex as usize,
         rbq_build_stream_push as usize,
         rbq_build_stream_finish as usize,
         rbq_build_stream_abort as usize,

@@ -8,6 +8,9 @@ ROTATOR_MATRIX, ROTATOR_FHT_KAC = 0, 1
 # numeric variants (RBQ_NUMERIC_*): which build of the reference the scores reproduce bit for bit
 NUMERIC_NATIVE_AVX512, NUMERIC_NATIVE_AVX2, NUMERIC_PORTABLE = 0, 1, 2
 NUMERIC_VARIANTS = {"native_avx512": NUMERIC_NATIVE_AVX512, "native_avx2": NUMERIC_NATIVE_AVX2, "portable": NUMERIC_PORTABLE}
+# rescale modes of the device encoder (RBQ_RESCALE_*): RabitqConfig::faster / RabitqConfig::new
+RESCALE_CONST, RESCALE_OPTIMAL = 0, 1
+RESCALE_MODES = {"const": RESCALE_CONST, "optimal": RESCALE_OPTIMAL}
 BATCH = 32
 
 

@@ -45,6 +45,8 @@ def lib():
         for name in ("rbq_build_pack_binary_code", "rbq_build_pack_ex_code_1bit",
                      "rbq_build_pack_ex_code_2bit", "rbq_build_pack_ex_code_6bit"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.rbq_build_best_rescale_factor.restype = C.c_double
+        L.rbq_build_best_rescale_factor.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32]
         L.rbq_build_pack_codes.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         L.rbq_build_rotate.argtypes = [C.POINTER(Header), C.c_void_p, C.c_void_p]
         L.rbq_build_train_bruteforce.restype = C.c_int
@@ -165,6 +167,12 @@ def train_with_clusters(data, centroids, assignments, total_bits, metric, rotato
         from . import RabitqError
         raise RabitqError(rc, "train_with_clusters rejected its configuration")
     return BuiltIndex(h)
+
+
+def best_rescale_factor(o_abs, ex_bits):
+    """best_rescale_factor (src/quantizer.rs:337-427) of one vector, o_abs [dim] = |r_i| / norm(r) (the CPU reference)."""
+    o = np.ascontiguousarray(o_abs, dtype=np.float32)
+    return float(lib().rbq_build_best_rescale_factor(o.ctypes.data, o.shape[0], int(ex_bits)))
 
 
 def kmeans(data, k, iters=10, seed=0):

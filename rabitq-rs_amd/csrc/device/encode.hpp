@@ -1,6 +1,6 @@
 // encode.hpp — GPU-side encoder: the quantisation loop of IvfRabitqIndex::train_with_clusters
-// (src/ivf.rs:1025-1215) for the "faster" configuration (constant rescale factor t_const), writing the device
-// layout of rbq_api.hip directly.
+// (src/ivf.rs:1025-1215), writing the device layout of rbq_api.hip directly: the "faster" configuration (constant
+// rescale factor t_const) or RabitqConfig::new (per-vector factor from k_rescale.hip).
 //
 //   k_rotate_rows   Rotator::rotate_into for a set of rows (k_prep's rotation code)
 //   k_encode        quantize_with_centroid (src/quantizer.rs:140-262, :264-308, :429-535): one THREAD per vector —
@@ -57,7 +57,9 @@ struct Dot8 {
 //   half-wave share one block and therefore one centroid row.
 // SCATTER = true: streamed build (rbq_build_stream_push) — rows are the chunk's vectors sorted by slot, row r goes
 //   to GLOBAL slot row_slot[r]; every row stages its own centroid tile.  Same arithmetic, expression for expression.
-template <bool SCATTER>
+// OPT = false: RabitqConfig::faster, the constant t_const (widened to f64) for every vector.
+// OPT = true: RabitqConfig::new, row r's own best_rescale_factor P.t_row[r] (k_rescale, f64 — never rounded to f32).
+template <bool SCATTER, bool OPT = false>
 __global__ __launch_bounds__(kEncThreads) void k_encode(EncodeParams P) {
     __shared__ float s_x[kEncThreads * kEncLd];
     __shared__ float s_c[SCATTER ? kEncThreads * kEncLd : 2 * kEncTile];
@@ -158,7 +160,7 @@ __global__ __launch_bounds__(kEncThreads) void k_encode(EncodeParams P) {
     if (ex_bits > 0) { // uniform
         const bool coded = norm > F32_EPS;
         const int32_t max_val = (1 << ex_bits) - 1;
-        const double t = (double)P.t_const;
+        const double t = OPT ? (valid ? P.t_row[slot] : 0.0) : (double)P.t_const;
         const float cb = -((float)(1u << ex_bits) - 0.5f);
         double ipnorm = 0.0;
         Dot8 d_ipr, d_ipc;

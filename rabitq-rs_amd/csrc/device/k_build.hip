@@ -21,7 +21,10 @@ hipError_t launch_rotate_rows(const float* src, const uint32_t* map, uint32_t nr
 hipError_t launch_encode(const EncodeParams& P, hipStream_t s) {
     if (!P.nslots) return hipSuccess;
     const dim3 grid((P.nslots + kEncThreads - 1) / kEncThreads);
-    if (P.row_slot) hipLaunchKernelGGL(k_encode<true>, grid, dim3(kEncThreads), 0, s, P);
+    if (P.t_row) {
+        if (P.row_slot) hipLaunchKernelGGL((k_encode<true, true>), grid, dim3(kEncThreads), 0, s, P);
+        else hipLaunchKernelGGL((k_encode<false, true>), grid, dim3(kEncThreads), 0, s, P);
+    } else if (P.row_slot) hipLaunchKernelGGL(k_encode<true>, grid, dim3(kEncThreads), 0, s, P);
     else hipLaunchKernelGGL(k_encode<false>, grid, dim3(kEncThreads), 0, s, P);
     return hipGetLastError();
 }

@@ -152,6 +152,12 @@ hipError_t launch_scanw(const ScanParams& P, uint32_t nq, int device, hipStream_
 hipError_t launch_rotate_rows(const float* src, const uint32_t* map, uint32_t nrows, uint32_t dim, uint32_t D, int rotator,
                               const uint8_t* rot_blob, uint32_t trunc, float fac, float* rows, hipStream_t s);
 hipError_t launch_encode(const EncodeParams& P, hipStream_t s);
+// k_rescale.hip: best_rescale_factor of every row (one workgroup per row).  raw_o = false: rows are rotated vectors, o is
+// |row - centroid of the row's list| / norm (block mode: list = block_list[r / 32]; row_slot != null: block_list[row_slot[r] / 32]);
+// raw_o = true: rows are o itself (test hook).  Rows with slot_src[r] == kNoSrc are skipped.  D <= 2048, 1 <= ex_bits <= 7.
+hipError_t launch_rescale(const float* rows, const float* centroids, const uint32_t* block_list, const uint32_t* row_slot,
+                          const uint32_t* slot_src, uint32_t nrows, uint32_t D, uint32_t ex_bits, bool raw_o, double* t,
+                          hipStream_t s);
 // raw ex codes [row][D] u8 -> lane-major units of slot (row_slot ? row_slot[row] : row) in `ex`
 hipError_t launch_pack_ex(const uint8_t* raw, const uint32_t* slot_src, const uint32_t* row_slot, uint32_t nrows, uint32_t D,
                           uint32_t ex_bits, uint8_t* ex, hipStream_t s);

@@ -796,8 +796,18 @@ int upload_block_tables(const std::vector<uint32_t>& ln, const std::vector<uint3
     return RBQ_OK;
 }
 
+// rescale: RBQ_RESCALE_CONST (t_const for every vector) or RBQ_RESCALE_OPTIMAL (k_rescale per vector; t_const ignored).
+// Returns whether the per-vector search runs (it is moot for 1-bit indexes), or -1 after fail() for an unknown mode.
+int rescale_mode(int rescale, const rbq_header* hdr) {
+    if (rescale != RBQ_RESCALE_CONST && rescale != RBQ_RESCALE_OPTIMAL) {
+        fail(RBQ_INVALID_CONFIG, "unknown rescale mode " + std::to_string(rescale) + " (RBQ_RESCALE_CONST or RBQ_RESCALE_OPTIMAL)");
+        return -1;
+    }
+    return rescale == RBQ_RESCALE_OPTIMAL && hdr && hdr->ex_bits > 0 ? 1 : 0;
+}
+
 int build_device_impl(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
-                      uint64_t n, float t_const, int dev, rbq_index** out) {
+                      uint64_t n, int rescale, float t_const, int dev, rbq_index** out) {
     if (!out) return fail(RBQ_INVALID_CONFIG, "null out pointer");
     *out = nullptr;
     int rc = validate_header(hdr);
@@ -805,7 +815,9 @@ int build_device_impl(const rbq_header* hdr, const float* centroids, const float
     if (!centroids || !d_data || !d_assign) return fail(RBQ_INVALID_CONFIG, "null buffer");
     if (n == 0) return fail(RBQ_INVALID_CONFIG, "no vectors");
     if (n > 0xfffffff0ull) return fail(RBQ_INVALID_CONFIG, "too many vectors for 32-bit slots");
-    if (hdr->ex_bits > 0 && !(t_const > 0.0f)) return fail(RBQ_INVALID_CONFIG, "the device encoder needs the constant rescale factor (faster config)");
+    const int opt = rescale_mode(rescale, hdr);
+    if (opt < 0) return RBQ_INVALID_CONFIG;
+    if (!opt && hdr->ex_bits > 0 && !(t_const > 0.0f)) return fail(RBQ_INVALID_CONFIG, "the device encoder needs the constant rescale factor (faster config)");
     std::vector<int> devs;
     if ((rc = resolve_devices(1, &dev, devs))) return rc;
     DeviceGuard g(dev);
@@ -864,15 +876,20 @@ int build_device_impl(const rbq_header* hdr, const float* centroids, const float
         const uint64_t chunk_slots = chunk_blocks * 32;
         float* d_rows = nullptr;
         uint8_t* d_raw = nullptr;
+        double* d_t = nullptr;
         HIP_TRY(t.alloc((void**)&d_rows, chunk_slots * D * 4));
         HIP_TRY(t.alloc((void**)&d_raw, ix->ex_bits ? chunk_slots * D : 16));
+        if (opt) HIP_TRY(t.alloc((void**)&d_t, chunk_slots * 8));
         for (uint64_t b0 = 0; b0 < nblocks; b0 += chunk_blocks) {
             const uint64_t nb = std::min<uint64_t>(chunk_blocks, nblocks - b0), ns = nb * 32, s0 = b0 * 32;
             HIP_TRY(launch_rotate_rows(d_data, d_slot_src + s0, (uint32_t)ns, dim, D, (int)ix->rotator, (const uint8_t*)ix->rot_blob.p,
                                        ix->trunc, ix->fac, d_rows, 0));
+            if (opt)
+                HIP_TRY(launch_rescale(d_rows, (const float*)ix->centroids.p, d_block_list + b0, nullptr, d_slot_src + s0, (uint32_t)ns, D,
+                                       (uint32_t)ix->ex_bits, false, d_t, 0));
             EncodeParams P;
             P.rows = d_rows; P.centroids = (const float*)ix->centroids.p; P.slot_src = d_slot_src + s0; P.block_list = d_block_list + b0;
-            P.row_slot = nullptr;
+            P.row_slot = nullptr; P.t_row = d_t;
             P.blocks = (uint8_t*)ix->blocks.p + b0 * dev_stride; P.raw_ex = d_raw;
             P.f_add_ex = (float*)ix->fadd_ex.p + s0; P.f_rescale_ex = (float*)ix->fres_ex.p + s0; P.ids = (uint64_t*)ix->ids.p + s0;
             P.src_base = 0; P.nslots = (uint32_t)ns; P.D = D; P.Dc = Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.t_const = t_const;
@@ -895,14 +912,15 @@ struct rbq_builder {
     Replica* ix = nullptr;
     int device = 0;
     float t_const = 0.0f;
+    bool opt = false; // per-vector rescale factor (RBQ_RESCALE_OPTIMAL with ex_bits > 0)
     std::vector<uint32_t> ln, gb0;
     uint64_t n_total = 0, pushed = 0, next_id = 0;
     uint32_t *d_cursor = nullptr, *d_chunk_first = nullptr, *d_block_list = nullptr, *d_block_nv = nullptr, *d_counts = nullptr;
-    DevBuf vec, assign, ko, vi, vo, tmp, row_src, row_slot, rows, raw;
+    DevBuf vec, assign, ko, vi, vo, tmp, row_src, row_slot, rows, raw, trow;
     TempDev tables;
     ~rbq_builder() {
         DeviceGuard g(device);
-        for (DevBuf* b : {&vec, &assign, &ko, &vi, &vo, &tmp, &row_src, &row_slot, &rows, &raw}) b->release();
+        for (DevBuf* b : {&vec, &assign, &ko, &vi, &vo, &tmp, &row_src, &row_slot, &rows, &raw, &trow}) b->release();
         if (ix) free_replica(ix);
     }
 };
@@ -931,20 +949,22 @@ bool is_pinned_host_range(const void* p, size_t bytes) {
     return true;
 }
 
-int stream_begin_impl(const rbq_header* hdr, const float* centroids, const uint32_t* list_sizes, float t_const, int dev,
-                      rbq_builder** out) {
+int stream_begin_impl(const rbq_header* hdr, const float* centroids, const uint32_t* list_sizes, int rescale, float t_const,
+                      int dev, rbq_builder** out) {
     if (!out) return fail(RBQ_INVALID_CONFIG, "null out pointer");
     *out = nullptr;
     int rc = validate_header(hdr);
     if (rc) return rc;
     if (!centroids || !list_sizes) return fail(RBQ_INVALID_CONFIG, "null buffer");
-    if (hdr->ex_bits > 0 && !(t_const > 0.0f)) return fail(RBQ_INVALID_CONFIG, "the device encoder needs the constant rescale factor (faster config)");
+    const int opt = rescale_mode(rescale, hdr);
+    if (opt < 0) return RBQ_INVALID_CONFIG;
+    if (!opt && hdr->ex_bits > 0 && !(t_const > 0.0f)) return fail(RBQ_INVALID_CONFIG, "the device encoder needs the constant rescale factor (faster config)");
     std::vector<int> devs;
     if ((rc = resolve_devices(1, &dev, devs))) return rc;
     DeviceGuard g(dev);
     if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
     std::unique_ptr<rbq_builder> b(new rbq_builder());
-    b->device = dev; b->t_const = t_const;
+    b->device = dev; b->t_const = t_const; b->opt = opt != 0;
     b->ix = new_replica(hdr, dev);
     const uint32_t nlist = (uint32_t)hdr->n_lists;
     b->ln.assign(list_sizes, list_sizes + nlist);
@@ -1003,7 +1023,8 @@ int stream_push_impl(rbq_builder* b, const float* vectors, const uint32_t* assig
         }
         if ((rc = b->ko.ensure((size_t)n * 4)) || (rc = b->vi.ensure((size_t)n * 4)) || (rc = b->vo.ensure((size_t)n * 4)) ||
             (rc = b->row_src.ensure((size_t)n * 4)) || (rc = b->row_slot.ensure((size_t)n * 4)) ||
-            (rc = b->rows.ensure((size_t)n * D * 4)) || (rc = b->raw.ensure(ix->ex_bits ? (size_t)n * D : 16)))
+            (rc = b->rows.ensure((size_t)n * D * 4)) || (rc = b->raw.ensure(ix->ex_bits ? (size_t)n * D : 16)) ||
+            (b->opt && (rc = b->trow.ensure((size_t)n * 8))))
             return rc;
         HIP_TRY(launch_iota((uint32_t*)b->vi.p, n, 0));
         size_t tb = 0;
@@ -1015,9 +1036,12 @@ int stream_push_impl(rbq_builder* b, const float* vectors, const uint32_t* assig
                                    b->d_chunk_first, (uint32_t*)b->row_src.p, (uint32_t*)b->row_slot.p, 0));
         HIP_TRY(launch_rotate_rows(d_vec, (const uint32_t*)b->row_src.p, n, dim, D, (int)ix->rotator, (const uint8_t*)ix->rot_blob.p,
                                    ix->trunc, ix->fac, (float*)b->rows.p, 0));
+        if (b->opt)
+            HIP_TRY(launch_rescale((const float*)b->rows.p, (const float*)ix->centroids.p, b->d_block_list, (const uint32_t*)b->row_slot.p,
+                                   (const uint32_t*)b->row_src.p, n, D, (uint32_t)ix->ex_bits, false, (double*)b->trow.p, 0));
         EncodeParams P;
         P.rows = (const float*)b->rows.p; P.centroids = (const float*)ix->centroids.p; P.slot_src = (const uint32_t*)b->row_src.p;
-        P.block_list = b->d_block_list; P.row_slot = (const uint32_t*)b->row_slot.p;
+        P.block_list = b->d_block_list; P.row_slot = (const uint32_t*)b->row_slot.p; P.t_row = b->opt ? (const double*)b->trow.p : nullptr;
         P.blocks = (uint8_t*)ix->blocks.p; P.raw_ex = (uint8_t*)b->raw.p;
         P.f_add_ex = (float*)ix->fadd_ex.p; P.f_rescale_ex = (float*)ix->fres_ex.p; P.ids = (uint64_t*)ix->ids.p;
         P.src_base = first_id + s0; P.nslots = n; P.D = D; P.Dc = Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.t_const = b->t_const;
@@ -1589,7 +1613,14 @@ int rbq_index_build_device(const rbq_header* hdr, const float* centroids, const 
                            uint64_t n, float t_const, int device, rbq_index** out) {
     g_err.clear();
     RBQ_GUARD_BEGIN
-    return build_device_impl(hdr, centroids, d_data, d_assign, n, t_const, device, out);
+    return build_device_impl(hdr, centroids, d_data, d_assign, n, RBQ_RESCALE_CONST, t_const, device, out);
+    RBQ_GUARD_END
+}
+int rbq_index_build_device_ex(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
+                              uint64_t n, int rescale, float t_const, int device, rbq_index** out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    return build_device_impl(hdr, centroids, d_data, d_assign, n, rescale, t_const, device, out);
     RBQ_GUARD_END
 }
 
@@ -1597,7 +1628,44 @@ int rbq_build_stream_begin(const rbq_header* hdr, const float* centroids, const 
                            rbq_builder** out) {
     g_err.clear();
     RBQ_GUARD_BEGIN
-    return stream_begin_impl(hdr, centroids, list_sizes, t_const, device, out);
+    return stream_begin_impl(hdr, centroids, list_sizes, RBQ_RESCALE_CONST, t_const, device, out);
+    RBQ_GUARD_END
+}
+int rbq_build_stream_begin_ex(const rbq_header* hdr, const float* centroids, const uint32_t* list_sizes, int rescale,
+                              float t_const, int device, rbq_builder** out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    return stream_begin_impl(hdr, centroids, list_sizes, rescale, t_const, device, out);
+    RBQ_GUARD_END
+}
+int rbq_debug_best_rescale(const float* o_abs, uint64_t n, uint32_t dim, uint32_t ex_bits, int device, double* out_t) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!o_abs || !out_t) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    if (dim == 0 || dim > 2048) return fail(RBQ_INVALID_CONFIG, "dim must be in 1..2048");
+    if (ex_bits == 0 || ex_bits > 7) return fail(RBQ_INVALID_CONFIG, "ex_bits must be in 1..7");
+    for (uint64_t i = 0; i < n * dim; ++i) // o = |r| / norm(r): the window bound of k_rescale relies on o <= 1
+        if (!(o_abs[i] >= 0.0f && o_abs[i] <= 1.0f)) return fail(RBQ_INVALID_CONFIG, "o_abs must lie in [0, 1]");
+    if (n == 0) return RBQ_OK;
+    std::vector<int> devs;
+    int rc;
+    if ((rc = resolve_devices(1, &device, devs))) return rc;
+    DeviceGuard g(device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    const uint64_t chunk = std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)dim * 4));
+    TempDev t;
+    float* d_o = nullptr;
+    double* d_t = nullptr;
+    const uint64_t rows = std::min(chunk, n);
+    HIP_TRY(t.alloc((void**)&d_o, rows * dim * 4));
+    HIP_TRY(t.alloc((void**)&d_t, rows * 8));
+    for (uint64_t r0 = 0; r0 < n; r0 += chunk) {
+        const uint64_t nr = std::min(chunk, n - r0);
+        HIP_TRY(hipMemcpy(d_o, o_abs + r0 * dim, nr * dim * 4, hipMemcpyHostToDevice));
+        HIP_TRY(launch_rescale(d_o, nullptr, nullptr, nullptr, nullptr, (uint32_t)nr, dim, ex_bits, true, d_t, 0));
+        HIP_TRY(hipMemcpy(out_t + r0, d_t, nr * 8, hipMemcpyDeviceToHost));
+    }
+    return RBQ_OK;
     RBQ_GUARD_END
 }
 int rbq_build_stream_push(rbq_builder* b, const float* vectors, const uint32_t* assign, uint64_t first_id, uint64_t count) {

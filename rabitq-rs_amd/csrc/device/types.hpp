@@ -207,6 +207,7 @@ struct EncodeParams {
     uint64_t src_base;          // ids[slot] = src_base + source index (scatter mode: src_base + row)
     uint32_t nslots, D, Dc, ex_bits, metric;
     float t_const;
+    const double* t_row;        // optimal rescale (k_encode<*, true>): [nrows] t of every row (k_rescale); else unused
 };
 constexpr int kEncThreads = 64;          // 64 vectors = 2 blocks per workgroup
 

@@ -538,6 +538,9 @@ void rbq_build_free_bytes(uint8_t* p) { std::free(p); }
 
 // --- primitives exported for the reference's literal known-answer tests -------
 void rbq_build_pack_binary_code(const uint8_t* bits, uint8_t* packed, uint64_t dim) { pack_binary_code(bits, packed, dim); }
+double rbq_build_best_rescale_factor(const float* o_abs, uint64_t dim, uint32_t ex_bits) {
+    return best_rescale_factor(o_abs, dim, ex_bits);
+}
 void rbq_build_pack_ex_code_1bit(const uint16_t* c, uint8_t* p, uint64_t dim) { pack_ex1(c, p, dim); }
 void rbq_build_pack_ex_code_2bit(const uint16_t* c, uint8_t* p, uint64_t dim) { pack_ex2(c, p, dim); }
 void rbq_build_pack_ex_code_6bit(const uint16_t* c, uint8_t* p, uint64_t dim) { pack_ex6(c, p, dim); }

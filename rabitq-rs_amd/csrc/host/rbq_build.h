@@ -22,6 +22,8 @@ void                 rbq_built_free(rbq_built* b);
 int  rbq_built_save_rbq1(const rbq_built* b, uint8_t** bytes, uint64_t* len);
 void rbq_build_free_bytes(uint8_t* p);
 
+/* best_rescale_factor (src/quantizer.rs:337-427) of one vector: o_abs [dim] = |r_i| / norm(r) -> t */
+double rbq_build_best_rescale_factor(const float* o_abs, uint64_t dim, uint32_t ex_bits);
 void rbq_build_pack_binary_code(const uint8_t* bits, uint8_t* packed, uint64_t dim);
 void rbq_build_pack_ex_code_1bit(const uint16_t* c, uint8_t* p, uint64_t dim);
 void rbq_build_pack_ex_code_2bit(const uint16_t* c, uint8_t* p, uint64_t dim);

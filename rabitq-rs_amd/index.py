@@ -75,6 +75,10 @@ def lib():
         L.rbq_debug_bounce_copies.argtypes = []
         L.rbq_index_build_device.restype = C.c_int
         L.rbq_index_build_device.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_int, vp]
+        L.rbq_index_build_device_ex.restype = C.c_int
+        L.rbq_index_build_device_ex.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_float, C.c_int, vp]
+        L.rbq_debug_best_rescale.restype = C.c_int
+        L.rbq_debug_best_rescale.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, vp]
         L.rbq_debug_copy_index.restype = C.c_int
         L.rbq_debug_copy_index.argtypes = [vp, C.c_char_p, vp, C.c_uint64]
         L.rbq_profile_set_sampling.restype = None
@@ -96,6 +100,8 @@ def lib():
         L.rbq_index_device_count.argtypes = [vp]
         L.rbq_build_stream_begin.restype = C.c_int
         L.rbq_build_stream_begin.argtypes = [vp, vp, vp, C.c_float, C.c_int, C.POINTER(vp)]
+        L.rbq_build_stream_begin_ex.restype = C.c_int
+        L.rbq_build_stream_begin_ex.argtypes = [vp, vp, vp, C.c_int, C.c_float, C.c_int, C.POINTER(vp)]
         L.rbq_build_stream_push.restype = C.c_int
         L.rbq_build_stream_push.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64]
         L.rbq_build_stream_finish.restype = C.c_int
@@ -134,6 +140,13 @@ def _check(rc):
         raise RabitqError(rc, _detail())
 
 
+def _rescale(mode, t_const):
+    """(RBQ_RESCALE_*, t_const as f32) for rescale="const" (RabitqConfig::faster) / "optimal" (RabitqConfig::new).
+    An unknown mode is passed through as an integer the library rejects (InvalidConfig)."""
+    m = _abi.RESCALE_MODES.get(mode, -1) if isinstance(mode, str) else int(mode)
+    return m, float(t_const) if t_const is not None else 0.0
+
+
 def _addr(ptr):
     return C.cast(ptr, C.c_void_p)
 
@@ -162,15 +175,57 @@ class IvfRabitqIndex:
         return cls(h)
 
     @classmethod
-    def build_on_device(cls, hdr_ptr, centroids, d_data, d_assign, n, t_const, device=0):
-        """GPU-side encoder (rbq_index_build_device): `hdr_ptr` is a ctypes pointer to an rbq_header (dim,
+    def build_on_device(cls, hdr_ptr, centroids, d_data, d_assign, n, t_const=None, device=0, rescale="const"):
+        """GPU-side encoder (rbq_index_build_device_ex): `hdr_ptr` is a ctypes pointer to an rbq_header (dim,
         padded_dim, metric, rotator + blob, ex_bits, n_lists), `centroids` a host [n_lists][dim] f32 array,
-        `d_data` / `d_assign` device pointers to [n][dim] f32 vectors and [n] u32 cluster ids."""
+        `d_data` / `d_assign` device pointers to [n][dim] f32 vectors and [n] u32 cluster ids.
+        rescale="const": RabitqConfig::faster, `t_const` for every vector (required unless 1-bit);
+        rescale="optimal": RabitqConfig::new, every vector's own best_rescale_factor (`t_const` may be None)."""
         cent = np.ascontiguousarray(centroids, dtype=np.float32)
+        mode, t = _rescale(rescale, t_const)
         h = C.c_void_p()
-        _check(lib().rbq_index_build_device(_addr(hdr_ptr), cent.ctypes.data, C.c_void_p(d_data), C.c_void_p(d_assign),
-                                            int(n), float(t_const), int(device), C.byref(h)))
+        _check(lib().rbq_index_build_device_ex(_addr(hdr_ptr), cent.ctypes.data, C.c_void_p(d_data), C.c_void_p(d_assign),
+                                               int(n), mode, t, int(device), C.byref(h)))
         return cls(h)
+
+    @classmethod
+    def train_on_device(cls, data, centroids, assignments, total_bits, metric, rotator_type, seed, use_faster_config,
+                        device=0):
+        """`train_with_clusters` (src/ivf.rs:1025-1215; the crate's Python `fit_with_clusters`) with the quantisation on
+        the GPU.  The header — rotator, and t_const for the faster configuration — depends only on (dim, bits, seed), so
+        it is taken from a CPU build over the first n_lists vectors; the whole set is then encoded on `device` with
+        rescale "const" (use_faster_config) or "optimal".  `data` [n][dim] and `assignments` [n] are host arrays or
+        CUDA tensors.  The index is identical, array for array, to the CPU build's."""
+        import torch
+        from . import RabitqError, builder
+        dev = torch.device("cuda", int(device))
+        xd = (data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32)))
+        xd = xd.to(device=dev, dtype=torch.float32).contiguous()
+        ad = (assignments if isinstance(assignments, torch.Tensor) else torch.from_numpy(np.asarray(assignments).astype(np.int64)))
+        ad = ad.to(device=dev, dtype=torch.int32).contiguous()
+        cent = np.ascontiguousarray(centroids.cpu().numpy() if isinstance(centroids, torch.Tensor) else centroids, dtype=np.float32)
+        if xd.dim() != 2 or ad.shape[0] != xd.shape[0] or cent.ndim != 2 or cent.shape[1] != xd.shape[1]:
+            raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data [n][dim], assignments [n], centroids [n_lists][dim]")
+        n, nlist = int(xd.shape[0]), int(cent.shape[0])
+        if nlist == 0 or nlist > n:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "train_with_clusters needs 1 <= n_lists <= n")
+        small = builder.train_with_clusters(xd[:nlist].cpu().numpy(), cent, np.arange(nlist, dtype=np.uint32), total_bits,
+                                            metric, rotator_type, seed, True)
+        try:
+            return cls.build_on_device(small.hdr_ptr, cent, xd.data_ptr(), ad.data_ptr(), n,
+                                       small.t_const if use_faster_config else None, device,
+                                       "const" if use_faster_config else "optimal")
+        finally:
+            small.close()
+
+    @staticmethod
+    def debug_best_rescale(o_abs, ex_bits, device=0):
+        """Test hook (rbq_debug_best_rescale): best_rescale_factor of every row of o_abs [n][dim] (|r| / norm(r)),
+        computed by the encoder's kernel; f64 [n]."""
+        o = np.ascontiguousarray(o_abs, dtype=np.float32)
+        out = np.empty(o.shape[0], np.float64)
+        _check(lib().rbq_debug_best_rescale(o.ctypes.data, o.shape[0], o.shape[1], int(ex_bits), int(device), out.ctypes.data))
+        return out
 
     def debug_copy_index(self, name, out):
         """Diagnostic: copy one of the index's device arrays into the numpy array `out` (exact size)."""
@@ -403,12 +458,14 @@ class StreamBuilder:
     """Streamed GPU-side encoder (rbq_build_stream_*): `train_with_clusters` (src/ivf.rs:1025-1215) with the
     vectors delivered chunk by chunk, for data sets that do not fit in HBM at once."""
 
-    def __init__(self, hdr_ptr, centroids, list_sizes, t_const, device=0):
+    def __init__(self, hdr_ptr, centroids, list_sizes, t_const=None, device=0, rescale="const"):
+        """rescale as for IvfRabitqIndex.build_on_device ("const": t_const; "optimal": per-vector factor)."""
         cent = np.ascontiguousarray(centroids, dtype=np.float32)
         ls = np.ascontiguousarray(list_sizes, dtype=np.uint32)
+        mode, t = _rescale(rescale, t_const)
         self._b = C.c_void_p()
-        _check(lib().rbq_build_stream_begin(_addr(hdr_ptr), cent.ctypes.data, ls.ctypes.data, float(t_const), int(device),
-                                            C.byref(self._b)))
+        _check(lib().rbq_build_stream_begin_ex(_addr(hdr_ptr), cent.ctypes.data, ls.ctypes.data, mode, t, int(device),
+                                               C.byref(self._b)))
 
     def push(self, vectors, assign, first_id, count=None):
         """vectors / assign: numpy arrays (host) or integer device pointers (then `count` is required)."""
