@@ -355,5 +355,7 @@ uint32_t rbq_abi_version(void);
 
 /* The brute-force index (BruteForceRabitqIndex): rbq_bf_* in the companion header. */
 #include "rbq_bf.h"
+/* The device k-means (run_kmeans_with_config): rbq_kmeans_device in its own header. */
+#include "rbq_kmeans.h"
 
 #endif /* RBQ_H */

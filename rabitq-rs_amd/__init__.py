@@ -8,6 +8,8 @@ Mirrors the reference's public query API for this path:
   IvfRabitqIndex.search / search_filtered / batch_search / len / cluster_count
                                src/ivf.rs:1705-1752,1218-1230
   BruteForceRabitqIndex        src/brute_force.rs (bruteforce.py)
+  KMeansConfig / run_kmeans_with_config, IvfRabitqIndex.train
+                               src/kmeans.rs, src/ivf.rs:950-1021 (kmeans.py)
 All compute goes through the C ABI of include/rbq.h (csrc/librbq.so, hand-written HIP for
 gfx950). There is no CPU fallback: if the HIP library is missing or no GPU is present the
 calls raise.
@@ -68,6 +70,8 @@ class SearchResult:
 from .index import IvfRabitqIndex, StreamBuilder  # noqa: E402
 from . import builder  # noqa: E402,F401
 from .bruteforce import BruteForceRabitqIndex, BruteForceSearchParams, BruteForceSearchResult  # noqa: E402
+from .kmeans import KMeansConfig, KMeansResult, run_kmeans_with_config  # noqa: E402
 
 __all__ = ["Metric", "RotatorType", "RabitqError", "SearchParams", "SearchResult", "IvfRabitqIndex",
-           "StreamBuilder", "builder", "BruteForceRabitqIndex", "BruteForceSearchParams", "BruteForceSearchResult"]
+           "StreamBuilder", "builder", "BruteForceRabitqIndex", "BruteForceSearchParams", "BruteForceSearchResult",
+           "KMeansConfig", "KMeansResult", "run_kmeans_with_config"]

@@ -12,6 +12,9 @@ NUMERIC_VARIANTS = {"native_avx512": NUMERIC_NATIVE_AVX512, "native_avx2": NUMER
 RESCALE_CONST, RESCALE_OPTIMAL = 0, 1
 RESCALE_MODES = {"const": RESCALE_CONST, "optimal": RESCALE_OPTIMAL}
 BATCH = 32
+# rbq_kmeans_device (include/rbq_kmeans.h): the config fields in ABI order and the stats slots
+KMEANS_CONFIG_FIELDS = ("niter", "nredo", "seed", "spherical", "max_points_per_centroid", "decode_block_size")
+KMEANS_STATS = ("shortlist_fallbacks", "empty_reseeded", "rng_draws", "max_shortlist")
 
 
 class Header(C.Structure):

@@ -42,6 +42,10 @@ def lib():
         L.rbq_build_kmeans.restype = C.c_int
         L.rbq_build_kmeans.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_uint64,
                                        C.c_void_p, C.c_void_p]
+        L.rbq_build_kmeans_faiss.restype = C.c_int
+        L.rbq_build_kmeans_faiss.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                             C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                                             C.c_void_p]
         for name in ("rbq_build_pack_binary_code", "rbq_build_pack_ex_code_1bit",
                      "rbq_build_pack_ex_code_2bit", "rbq_build_pack_ex_code_6bit"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
@@ -189,6 +193,32 @@ def train(data, nlist, total_bits, metric, rotator_type, seed, use_faster_config
     """`IvfRabitqIndex::train` (src/ivf.rs:950-1021) with a plain Lloyd k-means harness."""
     cent, assign = kmeans(data, nlist, kmeans_iters, seed ^ 0x5A5A5A5A5A5A5A5A)
     return train_with_clusters(data, cent, assign, total_bits, metric, rotator_type, seed, use_faster_config)
+
+
+def run_kmeans_with_config_cpu(data, k, config=None, stats=None):
+    """`run_kmeans_with_config` (src/kmeans.rs) in the pinned arithmetic of rbq_build.cpp, on the CPU: the specification the
+    GPU k-means (kmeans.run_kmeans_with_config) equals bit for bit.  `stats`, when a dict, receives empty_reseeded and rng_draws."""
+    from .kmeans import KMeansResult, _args, validate
+    data = np.ascontiguousarray(data, dtype=np.float32)
+    if data.ndim != 2:
+        from . import RabitqError
+        from ._abi import RBQ_DIMENSION_MISMATCH
+        raise RabitqError(RBQ_DIMENSION_MISMATCH, "data must be [n][dim]")
+    n, dim = data.shape
+    validate(n, dim, int(k), config, lambda: bool(np.isfinite(data).all()))
+    niter, nredo, seed, sph, mppc, dbs = _args(config)
+    cent = np.empty((int(k), dim), np.float32)
+    assign = np.empty(n, np.uint32)
+    obj = C.c_double()
+    st = np.zeros(2, np.uint64)
+    rc = lib().rbq_build_kmeans_faiss(data.ctypes.data, n, dim, int(k), niter, nredo, seed, sph, mppc, dbs, cent.ctypes.data,
+                                      assign.ctypes.data, C.byref(obj), st.ctypes.data)
+    if rc != RBQ_OK:
+        from . import RabitqError
+        raise RabitqError(rc, "run_kmeans_with_config rejected its configuration")
+    if stats is not None:
+        stats.update(empty_reseeded=int(st[0]), rng_draws=int(st[1]))
+    return KMeansResult(cent, assign, float(obj.value))
 
 
 class BuiltBruteForce:

@@ -4,8 +4,10 @@
 //   k_query.hip  k_prep / k_prep_wave, k_rank_* , k_select*, k_probes_given     (kernels.hpp, rank_mfma.hpp)
 //   k_scan.hip   k_scan<DT, EX, TR>                                               (scan.hpp)
 //   k_build.hip  encoder, reference-layout -> device-layout converters, sorting   (encode.hpp)
+//   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver
 #pragma once
 #include <atomic>
+#include <string>
 
 #include "types.hpp"
 
@@ -231,5 +233,22 @@ struct BfSelectParams {
 };
 hipError_t launch_bf_select(const BfSelectParams& p, hipStream_t s);
 constexpr uint32_t kBfLdsHeapMaxTopK = 8191; // (top_k + 1) * 8 bytes of LDS heap <= 64 KiB
+
+// ---- k-means (k_kmeans.hip): run_kmeans_with_config on the current device, arguments already validated (rbq_kmeans_device)
+constexpr uint64_t kKmeansChunkBytes = 512ull << 20; // per-chunk assignment workspace (R rows x (4k + 4Dp + shortlist) bytes, R >= 128)
+struct KMeansArgs {
+    const float* data; // device [n][dim]
+    uint64_t n;
+    uint32_t dim;
+    uint64_t k, niter, nredo, seed;
+    int spherical;
+    uint64_t mppc, dbs;
+    int device;
+    float* centroids;       // host [k][dim]
+    uint32_t* assignments;  // device [n]
+    double* objective;      // host
+    uint64_t* stats;        // host [4] or null: shortlist fallbacks, empty clusters reseeded, RNG draws, largest shortlist
+};
+int kmeans_device(const KMeansArgs& a, std::string& detail); // RBQ_* code; detail on failure
 
 } // namespace rbq

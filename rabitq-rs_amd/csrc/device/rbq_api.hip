@@ -1668,6 +1668,33 @@ int rbq_debug_best_rescale(const float* o_abs, uint64_t n, uint32_t dim, uint32_
     return RBQ_OK;
     RBQ_GUARD_END
 }
+int rbq_kmeans_device(const float* d_data, uint64_t n, uint32_t dim, uint64_t k, uint64_t niter, uint64_t nredo, uint64_t seed,
+                      int spherical, uint64_t max_points_per_centroid, uint64_t decode_block_size, int device, float* centroids,
+                      uint32_t* d_assignments, double* objective, uint64_t* stats) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    // validate_inputs (src/kmeans.rs) with the crate's messages, then what this project adds
+    if (n == 0) return fail(RBQ_INVALID_CONFIG, "k-means requires non-empty data");
+    if (k == 0) return fail(RBQ_INVALID_CONFIG, "k must be positive");
+    if (niter == 0) return fail(RBQ_INVALID_CONFIG, "max_iter must be positive");
+    if (k > n) return fail(RBQ_INVALID_CONFIG, "k cannot exceed number of samples");
+    if (nredo == 0) return fail(RBQ_INVALID_CONFIG, "nredo must be positive");
+    if (decode_block_size == 0) return fail(RBQ_INVALID_CONFIG, "decode_block_size must be positive");
+    if (dim == 0) return fail(RBQ_INVALID_CONFIG, "vectors must have at least one dimension");
+    if (n >= 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "k-means supports fewer than 2^32 - 1 vectors");
+    if (!d_data || !centroids || !d_assignments || !objective) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    std::vector<int> devs;
+    int rc;
+    if ((rc = resolve_devices(1, &device, devs))) return rc;
+    DeviceGuard g(device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    KMeansArgs a{d_data, n, dim, k, niter, nredo, seed, spherical, max_points_per_centroid, decode_block_size, device, centroids,
+                 d_assignments, objective, stats};
+    std::string detail;
+    rc = kmeans_device(a, detail);
+    return rc ? fail(rc, detail) : RBQ_OK;
+    RBQ_GUARD_END
+}
 int rbq_build_stream_push(rbq_builder* b, const float* vectors, const uint32_t* assign, uint64_t first_id, uint64_t count) {
     g_err.clear();
     RBQ_GUARD_BEGIN

@@ -32,39 +32,12 @@
 
 #include "../../../include/rbq.h"
 #include "rbq_build.h"
+#include "rbq_rng.h"
 
 namespace {
 
-// ---------------------------------------------------------------- RNG
-struct Rng {
-    uint64_t s[4];
-    explicit Rng(uint64_t seed) {
-        uint64_t z = seed;
-        for (int i = 0; i < 4; ++i) {
-            z += 0x9e3779b97f4a7c15ULL;
-            uint64_t x = z;
-            x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-            x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-            s[i] = x ^ (x >> 31);
-        }
-    }
-    static uint64_t rotl(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
-    uint64_t next() {
-        uint64_t r = rotl(s[1] * 5, 7) * 9, t = s[1] << 17;
-        s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3]; s[2] ^= t; s[3] = rotl(s[3], 45);
-        return r;
-    }
-    double uniform() { return (double)(next() >> 11) * (1.0 / 9007199254740992.0); }
-    bool have = false; double spare = 0;
-    double normal() {
-        if (have) { have = false; return spare; }
-        double u, v, r;
-        do { u = 2 * uniform() - 1; v = 2 * uniform() - 1; r = u * u + v * v; } while (r >= 1 || r == 0);
-        double f = std::sqrt(-2 * std::log(r) / r);
-        spare = v * f; have = true;
-        return u * f;
-    }
-};
+// ---------------------------------------------------------------- RNG (rbq_rng.h)
+using rbq_host::Rng;
 
 // ---------------------------------------------------------------- math.rs (AVX2 lane order)
 float dot8(const float* a, const float* b, size_t len) {
@@ -669,5 +642,210 @@ int rbq_build_train_bruteforce(const float* data, uint64_t n, uint32_t dim, uint
 const rbq_header* rbq_bf_built_header(const rbq_bf_built* b) { return &b->hdr; }
 const rbq_bf_view* rbq_bf_built_view(const rbq_bf_built* b) { return &b->view; }
 void rbq_bf_built_free(rbq_bf_built* b) { delete b; }
+
+} // extern "C"
+
+// ---------------------------------------------------------------- Faiss-style k-means (spec of the GPU k-means)
+// run_kmeans_with_config (reference src/kmeans.rs), every step, in one pinned arithmetic that k_kmeans.hip reproduces bit
+// for bit.  The crate's own result cannot be reproduced exactly: its sums are merged across Rayon threads in scheduling
+// order, its dot products come from matrixmultiply::sgemm and its RNG is ChaCha12.  Pinned here:
+//   RNG        the Rng above; a uniform index in 0..m is next() % m; shuffles are rand 0.8's SliceRandom::shuffle (i from
+//              len-1 down to 1: j = index in 0..=i, swap(i, j)); sampling_rng = Rng(seed), redo_rng = Rng(seed + r *
+//              0x9e3779b97f4a7c15) drives Forgy and then the reseed fallback draws.
+//   norms/dot  sequential unfused f32 chains in coordinate order; distance (|x|^2 + |c|^2) - 2 dot, clamped to 0 when
+//              negative; argmin with a strict < in ascending cluster order from +inf (ties: lowest cluster).
+//   update     per (cluster, coordinate) an f32 sum over member rows in ascending row order (the crate on one thread);
+//              c = sum * (1.0f / (float)count); spherical: c *= 1.0f / sqrtf(norm) when norm > 0.
+//   reseed     per decode_block_size chunk the 8 rows first under (distance desc, row asc), distance ordered by its bit
+//              pattern (distances are >= 0); the pool sorted the same way; empty clusters in ascending order take the
+//              next candidate, then next() % rows.
+//   objective  per row the sequential f64 sum of ((float)(x - c))^2, then the sequential f64 sum over rows.
+// Non-finite input is rejected (the crate does not check; the GPU's shortlist bound needs finite input).
+namespace {
+
+void km_shuffle(std::vector<uint64_t>& v, Rng& rng) {
+    for (size_t i = v.size(); i-- > 1;) std::swap(v[i], v[rng.next() % (i + 1)]);
+}
+
+float km_norm(const float* x, uint32_t dim) {
+    float s = 0.0f;
+    for (uint32_t j = 0; j < dim; ++j) { float p = x[j] * x[j]; s = s + p; }
+    return s;
+}
+
+inline uint64_t km_cand_key(float dist, uint64_t row) {
+    uint32_t b;
+    std::memcpy(&b, &dist, 4);
+    return ((uint64_t)b << 32) | (0xffffffffull - row);
+}
+
+// assignment of rows [0, rows) of x (norms nx) to the centroids (column copy ccol [dim][k], norms nc): best cluster + its distance.
+// Independent sequential chains over coordinates, 64 clusters at a time (vectorised across clusters, never within a chain).
+void km_assign(const float* x, const float* nx, uint64_t rows, uint32_t dim, uint64_t k, const float* ccol, const float* nc,
+               uint32_t* best, float* bestd) {
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t i = 0; i < (int64_t)rows; ++i) {
+        const float* xr = x + (size_t)i * dim;
+        float bd = INFINITY;
+        uint32_t bc = 0;
+        for (uint64_t c0 = 0; c0 < k; c0 += 64) {
+            const uint64_t nb = std::min<uint64_t>(64, k - c0);
+            float acc[64];
+            for (uint64_t c = 0; c < 64; ++c) acc[c] = 0.0f;
+            for (uint32_t j = 0; j < dim; ++j) {
+                const float xv = xr[j];
+                const float* cc = ccol + (size_t)j * k + c0;
+                if (nb == 64) {
+                    for (int c = 0; c < 64; ++c) { float p = xv * cc[c]; acc[c] = acc[c] + p; }
+                } else {
+                    for (uint64_t c = 0; c < nb; ++c) { float p = xv * cc[c]; acc[c] = acc[c] + p; }
+                }
+            }
+            for (uint64_t c = 0; c < nb; ++c) {
+                float d = (nx[i] + nc[c0 + c]) - 2.0f * acc[c];
+                if (d < 0.0f) d = 0.0f;
+                if (d < bd) { bd = d; bc = (uint32_t)(c0 + c); }
+            }
+        }
+        best[i] = bc;
+        if (bestd) bestd[i] = bd;
+    }
+}
+
+void km_views(const float* cent, uint64_t k, uint32_t dim, std::vector<float>& ccol, std::vector<float>& nc) {
+    ccol.assign((size_t)k * dim, 0.0f);
+    nc.assign(k, 0.0f);
+    for (uint64_t c = 0; c < k; ++c) {
+        for (uint32_t j = 0; j < dim; ++j) ccol[(size_t)j * k + c] = cent[(size_t)c * dim + j];
+        nc[c] = km_norm(cent + (size_t)c * dim, dim);
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+int rbq_build_kmeans_faiss(const float* data, uint64_t n, uint32_t dim, uint64_t k, uint64_t niter, uint64_t nredo, uint64_t seed,
+                           int spherical, uint64_t max_points_per_centroid, uint64_t decode_block_size, float* centroids,
+                           uint32_t* assignments, double* objective, uint64_t* stats) {
+    if (n == 0 || k == 0 || niter == 0 || k > n || nredo == 0 || decode_block_size == 0 || dim == 0 || n >= 0xffffffffull)
+        return RBQ_INVALID_CONFIG;
+    for (uint64_t i = 0; i < n * dim; ++i)
+        if (!std::isfinite(data[i])) return RBQ_INVALID_CONFIG;
+    uint64_t st_reseed = 0, st_draws = 0;
+    // select_training_indices
+    Rng sampling_rng(seed);
+    const uint64_t kp = max_points_per_centroid && k > UINT64_MAX / max_points_per_centroid ? UINT64_MAX : k * max_points_per_centroid;
+    const uint64_t target = std::max(std::min(n, kp), k);
+    std::vector<float> sample;
+    const float* x = data;
+    uint64_t rows = n;
+    if (target != n) {
+        std::vector<uint64_t> idx(n);
+        for (uint64_t i = 0; i < n; ++i) idx[i] = i;
+        km_shuffle(idx, sampling_rng);
+        idx.resize(target);
+        std::sort(idx.begin(), idx.end());
+        sample.resize((size_t)target * dim);
+        for (uint64_t i = 0; i < target; ++i) std::memcpy(&sample[(size_t)i * dim], data + idx[i] * dim, sizeof(float) * dim);
+        x = sample.data();
+        rows = target;
+    }
+    std::vector<float> nx(rows), full_nx(n);
+    for (uint64_t i = 0; i < rows; ++i) nx[i] = km_norm(x + (size_t)i * dim, dim);
+    for (uint64_t i = 0; i < n; ++i) full_nx[i] = km_norm(data + (size_t)i * dim, dim);
+    std::vector<float> cent((size_t)k * dim), ccol, nc, bestd(rows), sums;
+    std::vector<uint32_t> asg(rows), fin(n);
+    std::vector<uint64_t> counts;
+    double best_obj = 0.0;
+    for (uint64_t r = 0; r < nredo; ++r) {
+        Rng redo_rng(seed + r * 0x9e3779b97f4a7c15ull);
+        {   // Forgy
+            std::vector<uint64_t> idx(rows);
+            for (uint64_t i = 0; i < rows; ++i) idx[i] = i;
+            km_shuffle(idx, redo_rng);
+            for (uint64_t c = 0; c < k; ++c) std::memcpy(&cent[(size_t)c * dim], x + idx[c] * dim, sizeof(float) * dim);
+        }
+        for (uint64_t it = 0; it < niter; ++it) {
+            km_views(cent.data(), k, dim, ccol, nc);
+            km_assign(x, nx.data(), rows, dim, k, ccol.data(), nc.data(), asg.data(), bestd.data());
+            counts.assign(k, 0);
+            for (uint64_t i = 0; i < rows; ++i) counts[asg[i]]++;
+            sums.assign((size_t)k * dim, 0.0f);
+#pragma omp parallel
+            {   // coordinate ranges over threads: every (cluster, coordinate) sum stays one ascending-row chain
+#ifdef _OPENMP
+                const uint32_t nt = (uint32_t)omp_get_num_threads(), t = (uint32_t)omp_get_thread_num();
+#else
+                const uint32_t nt = 1, t = 0;
+#endif
+                const uint32_t j0 = (uint32_t)((uint64_t)dim * t / nt), j1 = (uint32_t)((uint64_t)dim * (t + 1) / nt);
+                for (uint64_t i = 0; i < rows; ++i) {
+                    float* s = &sums[(size_t)asg[i] * dim];
+                    const float* xr = x + (size_t)i * dim;
+                    for (uint32_t j = j0; j < j1; ++j) s[j] = s[j] + xr[j];
+                }
+            }
+            // reseed candidates: per chunk the 8 first under (distance desc, row asc)
+            std::vector<uint64_t> pool;
+            for (uint64_t s0 = 0; s0 < rows; s0 += decode_block_size) {
+                const uint64_t e = std::min(rows, s0 + decode_block_size);
+                std::vector<uint64_t> keys;
+                keys.reserve(e - s0);
+                for (uint64_t i = s0; i < e; ++i) keys.push_back(km_cand_key(bestd[i], i));
+                const size_t take = std::min<size_t>(8, keys.size());
+                std::partial_sort(keys.begin(), keys.begin() + take, keys.end(), std::greater<uint64_t>());
+                pool.insert(pool.end(), keys.begin(), keys.begin() + take);
+            }
+            std::sort(pool.begin(), pool.end(), std::greater<uint64_t>());
+            size_t next = 0;
+            for (uint64_t c = 0; c < k; ++c) {
+                float* cc = &cent[(size_t)c * dim];
+                if (counts[c] > 0) {
+                    const float inv = 1.0f / (float)counts[c];
+                    for (uint32_t j = 0; j < dim; ++j) cc[j] = sums[(size_t)c * dim + j] * inv;
+                } else {
+                    uint64_t src;
+                    if (next < pool.size()) src = 0xffffffffull - (pool[next++] & 0xffffffffull);
+                    else { src = redo_rng.next() % rows; ++st_draws; }
+                    ++st_reseed;
+                    std::memcpy(cc, x + src * dim, sizeof(float) * dim);
+                }
+            }
+            if (spherical) {
+                for (uint64_t c = 0; c < k; ++c) {
+                    float* cc = &cent[(size_t)c * dim];
+                    const float nrm = km_norm(cc, dim);
+                    if (nrm > 0.0f) {
+                        const float inv = 1.0f / std::sqrt(nrm);
+                        for (uint32_t j = 0; j < dim; ++j) cc[j] = cc[j] * inv;
+                    }
+                }
+            }
+        }
+        // assignment of the full dataset + objective
+        km_views(cent.data(), k, dim, ccol, nc);
+        km_assign(data, full_nx.data(), n, dim, k, ccol.data(), nc.data(), fin.data(), nullptr);
+        std::vector<double> rd(n);
+#pragma omp parallel for schedule(static)
+        for (int64_t i = 0; i < (int64_t)n; ++i) {
+            const float* xr = data + (size_t)i * dim;
+            const float* cc = &cent[(size_t)fin[i] * dim];
+            double s = 0.0;
+            for (uint32_t j = 0; j < dim; ++j) { double dl = (double)(xr[j] - cc[j]); s = s + dl * dl; }
+            rd[i] = s;
+        }
+        double obj = 0.0;
+        for (uint64_t i = 0; i < n; ++i) obj = obj + rd[i];
+        if (r == 0 || obj < best_obj) {
+            best_obj = obj;
+            std::memcpy(centroids, cent.data(), sizeof(float) * (size_t)k * dim);
+            std::memcpy(assignments, fin.data(), sizeof(uint32_t) * n);
+        }
+    }
+    *objective = best_obj;
+    if (stats) { stats[0] = st_reseed; stats[1] = st_draws; }
+    return RBQ_OK;
+}
 
 } // extern "C"

@@ -33,6 +33,13 @@ uint32_t rbq_build_crc32(const uint8_t* p, uint64_t n);
 void rbq_build_rotate(const rbq_header* h, const float* in, float* out);
 int  rbq_build_kmeans(const float* data, uint64_t n, uint32_t dim, uint64_t k, int iters, uint64_t seed,
                       float* centroids, uint32_t* assignments);
+/* run_kmeans_with_config (reference src/kmeans.rs) in the pinned arithmetic of rbq_build.cpp: the specification of the GPU
+ * k-means (rbq_kmeans_device).  data [n][dim] (finite); centroids [k][dim], assignments [n], objective.  stats (nullable) [2]:
+ * empty clusters reseeded, reseeds drawn from the RNG (summed over restarts).  RBQ_INVALID_CONFIG: n == 0, k == 0, k > n,
+ * niter == 0, nredo == 0, decode_block_size == 0, dim == 0, n >= 2^32 - 1 or a non-finite value. */
+int  rbq_build_kmeans_faiss(const float* data, uint64_t n, uint32_t dim, uint64_t k, uint64_t niter, uint64_t nredo, uint64_t seed,
+                            int spherical, uint64_t max_points_per_centroid, uint64_t decode_block_size, float* centroids,
+                            uint32_t* assignments, double* objective, uint64_t* stats);
 
 /* BruteForceRabitqIndex::train (reference src/brute_force.rs:214-287): data [n][dim]; every vector quantised against a
  * zero centroid.  total_bits 1, 3 or 7; rotator MATRIX or FHT_KAC.  The view's ex_len is padded_dim/8 for 1-bit indexes

@@ -124,6 +124,9 @@ def lib():
         L.rbq_index_set_numeric_variant.argtypes = [vp, C.c_int]
         L.rbq_index_numeric_variant.restype = C.c_int
         L.rbq_index_numeric_variant.argtypes = [vp]
+        L.rbq_kmeans_device.restype = C.c_int
+        L.rbq_kmeans_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
+                                        C.c_uint64, C.c_uint64, C.c_int, vp, vp, C.POINTER(C.c_double), vp]
         _LIB = L
     return _LIB
 
@@ -217,6 +220,31 @@ class IvfRabitqIndex:
                                        "const" if use_faster_config else "optimal")
         finally:
             small.close()
+
+    @classmethod
+    def train(cls, data, nlist, total_bits, metric, rotator_type, seed, use_faster_config, device=0):
+        """`IvfRabitqIndex::train` (src/ivf.rs:950-1021) end to end on `device`: the crate's checks and messages, k-means as
+        `run_kmeans(data, nlist, 30, rng)` (seed = first draw of Rng(seed ^ 0x5a5a5a5a5a5a5a5a), the other KMeansConfig fields at
+        their defaults) on the device, then train_on_device's rotation and quantisation (rescale "optimal" unless
+        use_faster_config).  `data` [n][dim] is a host array or a CUDA tensor; it is uploaded once.  The index equals
+        train_with_clusters over the CPU k-means restatement (builder.run_kmeans_with_config_cpu) with the same config."""
+        from . import RabitqError
+        from .kmeans import KMeansConfig, _run_device, first_draw, to_device
+        shape = getattr(data, "shape", None)
+        if shape is None or len(shape) == 0 or shape[0] == 0:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "training data must be non-empty")
+        if nlist == 0:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "nlist must be positive")
+        if total_bits == 0 or total_bits > 16:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "total_bits must be between 1 and 16")
+        if len(shape) != 2:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "input vectors must share the same dimension")
+        if nlist > shape[0]:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "nlist cannot exceed number of vectors")
+        xd = to_device(data, device)
+        cfg = KMeansConfig(niter=30, seed=first_draw(int(seed) ^ 0x5A5A5A5A5A5A5A5A))
+        cent, assign, _, _ = _run_device(xd, int(nlist), cfg, device)
+        return cls.train_on_device(xd, cent, assign, total_bits, metric, rotator_type, seed, use_faster_config, device)
 
     @staticmethod
     def debug_best_rescale(o_abs, ex_bits, device=0):
