@@ -357,5 +357,6 @@ uint32_t rbq_abi_version(void);
 #include "rbq_bf.h"
 /* The device k-means (run_kmeans_with_config): rbq_kmeans_device in its own header. */
 #include "rbq_kmeans.h"
+#include "rbq_persist.h"
 
 #endif /* RBQ_H */

@@ -157,14 +157,17 @@ __global__ __launch_bounds__(kEncThreads) void k_encode(EncodeParams P) {
     // ---- pass B: ex codes (t_const), ipnorm chain in f64, the two dots of compute_extended_factors
     float ipnorm_inv = 1.0f;
     float f_add_ex = 0.0f, f_rescale_ex = 0.0f;
+    // reconstruction factors: |u'|^2 and <r, u'> of the centred total code u'.  At ex_bits == 0, u' = bit - 0.5 is pass
+    // A's xu_cb, so the two values are xu_norm_sqr and ip_resi_xucb (the same dot8 chains); pass B forms them otherwise.
+    float nq2 = xu_norm_sqr, drq = ip_resi_xucb;
     if (ex_bits > 0) { // uniform
         const bool coded = norm > F32_EPS;
         const int32_t max_val = (1 << ex_bits) - 1;
         const double t = OPT ? (valid ? P.t_row[slot] : 0.0) : (double)P.t_const;
         const float cb = -((float)(1u << ex_bits) - 0.5f);
         double ipnorm = 0.0;
-        Dot8 d_ipr, d_ipc;
-        d_ipr.init(); d_ipc.init();
+        Dot8 d_ipr, d_ipc, d_nq;
+        d_ipr.init(); d_ipc.init(); d_nq.init();
         for (uint32_t t0 = 0; t0 < D; t0 += kEncTile) {
             const uint32_t w = stage(t0);
             const float* xr = s_x + tid * kEncLd;
@@ -188,6 +191,7 @@ __global__ __launch_bounds__(kEncThreads) void k_encode(EncodeParams P) {
                     const float xu = (float)(uint16_t)(code + ((bit ? 1u : 0u) << ex_bits)) + cb;
                     { const float p = r * xu; d_ipr.a[l & 7] = d_ipr.a[l & 7] + p; }
                     { const float p = c * xu; d_ipc.a[l & 7] = d_ipc.a[l & 7] + p; }
+                    if (P.delta) { const float p = xu * xu; d_nq.a[l & 7] = d_nq.a[l & 7] + p; }
                     pk[l >> 2] |= code << (8 * (l & 3));
                 }
                 if (valid) *reinterpret_cast<uint4*>(P.raw_ex + (size_t)slot * D + t0 + k0) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
@@ -198,6 +202,7 @@ __global__ __launch_bounds__(kEncThreads) void k_encode(EncodeParams P) {
             if (!isfinite(ipnorm_inv)) ipnorm_inv = 1.0f;
         }
         const float ip_r = d_ipr.finish(any8), ip_c = d_ipc.finish(any8);
+        nq2 = d_nq.finish(any8); drq = ip_r;
         const float safe = fabsf(ip_r) <= F32_EPS ? INFINITY : ip_r;
         if (P.metric == 0) {
             f_add_ex = l2_sqr + 2.0f * l2_sqr * ip_c / safe;
@@ -239,6 +244,18 @@ __global__ __launch_bounds__(kEncThreads) void k_encode(EncodeParams P) {
         if (ex_bits) {
             P.f_add_ex[s] = valid ? f_add_ex : 0.0f;
             P.f_rescale_ex[s] = valid ? f_rescale_ex : 0.0f;
+        }
+        if (P.delta) { // rbq_build.cpp's delta / vl; std::max / std::min spelt out (NaN passes through as there)
+            const float cb = -((float)(1u << ex_bits) - 0.5f);
+            const float nq = sqrtf(nq2);
+            float den = l2_norm * nq;
+            den = den < F32_EPS ? F32_EPS : den;
+            float cosv = drq / den;
+            cosv = cosv < -1.0f ? -1.0f : cosv;
+            cosv = 1.0f < cosv ? 1.0f : cosv;
+            const float delta = nq <= F32_EPS ? 0.0f : (l2_norm / nq) * cosv;
+            P.delta[s] = valid ? delta : 0.0f;
+            P.vl[s] = valid ? delta * cb : 0.0f;
         }
     }
 }

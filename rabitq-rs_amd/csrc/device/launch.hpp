@@ -5,6 +5,7 @@
 //   k_scan.hip   k_scan<DT, EX, TR>                                               (scan.hpp)
 //   k_build.hip  encoder, reference-layout -> device-layout converters, sorting   (encode.hpp)
 //   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver
+//   k_save.hip   RBQ1 writer: device layout -> save_to_writer's cluster bytes, CRC-32 on the GPU
 #pragma once
 #include <atomic>
 #include <string>
@@ -250,5 +251,24 @@ struct KMeansArgs {
     uint64_t* stats;        // host [4] or null: shortlist fallbacks, empty clusters reseeded, RNG draws, largest shortlist
 };
 int kmeans_device(const KMeansArgs& a, std::string& detail); // RBQ_* code; detail on failure
+
+// ---- RBQ1 writer (k_save.hip): words [w0, w0 + nw) of the cluster section of the stream, into out[0, nw)
+struct SaveParams {
+    const uint64_t* woff;     // [n_lists + 1] first word of every cluster within the cluster section
+    const uint32_t* list_gb0; // [n_lists] first block of every list
+    const uint32_t* list_n;   // [n_lists]
+    const float* centroids;   // [n_lists][D] rotated
+    const uint8_t* blocks;    // device block records (stride Dc * 4 + 384)
+    const uint64_t* ids;      // slot order
+    const uint8_t* ex;        // lane-major ex codes, exd bytes per slot (ex_bits > 0)
+    const float *fadd_ex, *fres_ex, *delta, *vl; // slot order (fadd_ex / fres_ex unused when ex_bits == 0)
+    uint64_t exd;
+    uint32_t n_lists, D, Dc, ex_bits, ex_words, cpu; // ex_words = D * ex_bits / 32; cpu = ex_cpu(ex_bits)
+};
+hipError_t launch_save_fill(const SaveParams& P, uint64_t w0, uint64_t nw, uint32_t* out, hipStream_t s);
+// CRC-32/IEEE of device bytes p[0, n) (any alignment) into *out (device); seg_scratch holds crc_scratch_words(n) u32
+constexpr uint32_t kCrcSegment = 4096;
+uint64_t crc_scratch_words(uint64_t n);
+hipError_t launch_crc32(const uint8_t* p, uint64_t n, uint32_t* seg_scratch, uint32_t* out, hipStream_t s);
 
 } // namespace rbq

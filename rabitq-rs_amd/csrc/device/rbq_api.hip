@@ -246,6 +246,11 @@ struct Replica {
         bsumx, lsum; // ex-factor ranges per block, factor ranges per list (lazy probe selection)
     Arr* arrays[18] = {&rot_blob, &centroids, &blocks, &ids, &ex, &fadd_ex, &fres_ex, &list_gb0, &list_n, &prof, &bsum, &cnorm2,
                        &fallbacks, &cent_hi, &cent_lo, &raw, &bsumx, &lsum};
+    // reconstruction factors delta / vl of every slot (RBQ1's per-vector arrays that search never reads): kept on the FIRST
+    // replica only, for rbq_index_save_rbq1 (not in `arrays`: clone_replica does not copy them)
+    Arr delta, vl;
+    bool has_recon = false; // false: created by rbq_index_create (no factors given) — such a handle cannot be saved
+    uint64_t save_chunk = 0; // TEST ONLY (option save_chunk): staging chunk of rbq_index_save_rbq1_stream in bytes (0 = default)
     float cnorm2_max = 0.0f;
     uint64_t n_raw = 0;      // raw vectors attached for the optional rerank
     bool raw_borrowed = false;
@@ -387,6 +392,8 @@ void free_replica(Replica* ix) {
     (void)hipDeviceSynchronize();
     for (Arr* a : ix->arrays)
         if (a->p && !(a == &ix->raw && ix->raw_borrowed)) (void)hipFree(a->p);
+    for (Arr* a : {&ix->delta, &ix->vl})
+        if (a->p) (void)hipFree(a->p);
     for (Workspace* w : ix->pool) { w->release(); delete w; }
     for (auto& kv : ix->stream_ws) { kv.second->release(); delete kv.second; }
     for (auto& sp : ix->stage_prof)
@@ -591,6 +598,10 @@ int create_from_sources(const rbq_header* hdr, const std::vector<ListSrc>& lists
     const size_t exd = ex_bytes_dev(D, exbits);
     std::vector<uint32_t> gb0(nlist), ln(nlist);
     uint64_t nblocks = 0, nvec = 0;
+    // the reconstruction factors are kept when every non-empty list brings them
+    bool recon = true;
+    for (uint32_t c = 0; c < nlist; ++c)
+        if (lists[c].n && (!lists[c].delta || !lists[c].vl)) recon = false;
     for (uint32_t c = 0; c < nlist; ++c) {
         const ListSrc& L = lists[c];
         if (L.n > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "list too large");
@@ -615,14 +626,19 @@ int create_from_sources(const rbq_header* hdr, const std::vector<ListSrc>& lists
     if ((rc = alloc_arr(ix->fadd_ex, exbits ? nslots * 4 : 0))) return rc;
     if ((rc = alloc_arr(ix->fres_ex, exbits ? nslots * 4 : 0))) return rc;
     if ((rc = alloc_arr(ix->bsum, nblocks * sizeof(BlockSummary)))) return rc;
+    if (recon) {
+        if ((rc = alloc_arr(ix->delta, nslots * 4))) return rc;
+        if ((rc = alloc_arr(ix->vl, nslots * 4))) return rc;
+    }
 
     // Chunks of whole blocks (a long list may span several), staged through two pinned buffers: the host fills
     // one while the GPU converts the other.  Staging layout (16-byte aligned sections):
-    //   recs [nb][ref_stride] | ex [nv][exb] | ids [nv] u64 | fadd [nv] f32 | fres [nv] f32 | dense0 [nb] u64 | nvb [nb] u32
-    const size_t per_block = ref_stride + 32 * (exb + 16) + 12 + 64;
+    //   recs [nb][ref_stride] | ex [nv][exb] | ids [nv] u64 | fadd [nv] f32 | fres [nv] f32 | delta [nv] f32 | vl [nv] f32 |
+    //   dense0 [nb] u64 | nvb [nb] u32
+    const size_t per_block = ref_stride + 32 * (exb + 24) + 12 + 64;
     uint64_t chunk_blocks = std::max<uint64_t>(1, ((size_t)64 << 20) / per_block);
     chunk_blocks = std::min<uint64_t>(chunk_blocks, std::max<uint64_t>(nblocks, 1));
-    const size_t cap = align_up(chunk_blocks * ref_stride, 16) + align_up(chunk_blocks * 32 * exb, 16) + chunk_blocks * 32 * 16 +
+    const size_t cap = align_up(chunk_blocks * ref_stride, 16) + align_up(chunk_blocks * 32 * exb, 16) + chunk_blocks * 32 * 24 +
                        chunk_blocks * 12 + 256;
     uint8_t* pin[2] = {nullptr, nullptr};
     uint8_t* dst[2] = {nullptr, nullptr};
@@ -645,7 +661,8 @@ int create_from_sources(const rbq_header* hdr, const std::vector<ListSrc>& lists
         const size_t o_recs = 0, o_ex = align_up(nb * ref_stride, 16);
         // the number of vectors of the chunk is known only after the walk: lay the dense arrays out for the maximum
         const size_t o_ids = o_ex + align_up(nb * 32 * exb, 16), o_fadd = o_ids + nb * 32 * 8, o_fres = o_fadd + nb * 32 * 4,
-                     o_d0 = o_fres + nb * 32 * 4, o_nv = o_d0 + nb * 8, total = o_nv + nb * 4;
+                     o_dl = o_fres + nb * 32 * 4, o_vl = o_dl + nb * 32 * 4, o_d0 = o_vl + nb * 32 * 4, o_nv = o_d0 + nb * 8,
+                     total = o_nv + nb * 4;
         uint64_t* dense0 = reinterpret_cast<uint64_t*>(base + o_d0);
         uint32_t* nvb = reinterpret_cast<uint32_t*>(base + o_nv);
         uint64_t filled = 0, dense = 0;
@@ -661,6 +678,10 @@ int create_from_sources(const rbq_header* hdr, const std::vector<ListSrc>& lists
                 else for (uint64_t v = 0; v < nv; ++v) std::memcpy(base + o_ex + (dense + v) * exb, L.ex + (v0 + v) * L.ex_stride, exb);
                 std::memcpy(base + o_fadd + dense * 4, L.fadd + v0 * 4, nv * 4);
                 std::memcpy(base + o_fres + dense * 4, L.fres + v0 * 4, nv * 4);
+            }
+            if (recon && nv) {
+                std::memcpy(base + o_dl + dense * 4, L.delta + v0 * 4, nv * 4);
+                std::memcpy(base + o_vl + dense * 4, L.vl + v0 * 4, nv * 4);
             }
             for (uint64_t b = 0; b < take; ++b) {
                 dense0[filled + b] = dense + b * 32;
@@ -684,6 +705,12 @@ int create_from_sources(const rbq_header* hdr, const std::vector<ListSrc>& lists
             HIP_TRY(launch_spread_f32(reinterpret_cast<const float*>(d + o_fres), d_d0, d_nv, (uint32_t)nb, 0.0f,
                                       (float*)ix->fres_ex.p + b0 * 32, cl.st));
         }
+        if (recon) {
+            HIP_TRY(launch_spread_f32(reinterpret_cast<const float*>(d + o_dl), d_d0, d_nv, (uint32_t)nb, 0.0f,
+                                      (float*)ix->delta.p + b0 * 32, cl.st));
+            HIP_TRY(launch_spread_f32(reinterpret_cast<const float*>(d + o_vl), d_d0, d_nv, (uint32_t)nb, 0.0f,
+                                      (float*)ix->vl.p + b0 * 32, cl.st));
+        }
         HIP_TRY(hipEventRecord(ev[i], cl.st));
         b0 += nb;
         ++turn;
@@ -692,18 +719,22 @@ int create_from_sources(const rbq_header* hdr, const std::vector<ListSrc>& lists
     HIP_TRY(hipStreamSynchronize(cl.st));
     if ((rc = finish_replica(ix, ln))) return rc;
     HIP_TRY(hipDeviceSynchronize());
+    ix->has_recon = recon;
     *out = ix;
     cl.ix = nullptr; // keep
     // (cl's reference member now refers to a null local copy: nothing freed)
     return RBQ_OK;
 }
 
-int create_impl(const rbq_header* hdr, const rbq_list_view* lists, int n_devices, const int* devices, rbq_index** out) {
+// delta / vl: null (rbq_index_create: no reconstruction factors) or n_lists pointers to n f32 each
+int create_impl(const rbq_header* hdr, const rbq_list_view* lists, const float* const* delta, const float* const* vl, int n_devices,
+                const int* devices, rbq_index** out) {
     if (!out) return fail(RBQ_INVALID_CONFIG, "null out pointer");
     *out = nullptr;
     int rc = validate_header(hdr);
     if (rc) return rc;
     if (!lists) return fail(RBQ_INVALID_CONFIG, "null lists");
+    if (!delta != !vl) return fail(RBQ_INVALID_CONFIG, "delta and vl are given together");
     std::vector<int> devs;
     if ((rc = resolve_devices(n_devices, devices, devs))) return rc;
     const size_t ref_stride = (size_t)hdr->padded_dim * 4 + 384, exb = (size_t)hdr->padded_dim * hdr->ex_bits / 8;
@@ -720,6 +751,10 @@ int create_impl(const rbq_header* hdr, const rbq_list_view* lists, int n_devices
         ListSrc& S = src[c];
         S.centroid = (const uint8_t*)L.centroid; S.n = L.n; S.ids = (const uint8_t*)L.ids; S.batch_data = L.batch_data;
         S.ex = L.ex_codes; S.ex_stride = exb; S.fadd = (const uint8_t*)L.f_add_ex; S.fres = (const uint8_t*)L.f_rescale_ex;
+        if (delta) {
+            if (L.n && (!delta[c] || !vl[c])) return fail(RBQ_INVALID_CONFIG, "null delta / vl array");
+            S.delta = (const uint8_t*)delta[c]; S.vl = (const uint8_t*)vl[c];
+        }
     }
     Replica* first = nullptr;
     if ((rc = create_from_sources(hdr, src, devs[0], &first))) return rc;
@@ -773,11 +808,15 @@ int encoder_prepare(Replica* ix, const rbq_header* hdr, const float* centroids, 
     if ((rc = alloc_arr(ix->fadd_ex, ix->ex_bits ? nslots * 4 : 0))) return rc;
     if ((rc = alloc_arr(ix->fres_ex, ix->ex_bits ? nslots * 4 : 0))) return rc;
     if ((rc = alloc_arr(ix->bsum, nblocks * sizeof(BlockSummary)))) return rc;
+    if ((rc = alloc_arr(ix->delta, nslots * 4))) return rc;
+    if ((rc = alloc_arr(ix->vl, nslots * 4))) return rc;
+    ix->has_recon = true;
     if (exd) HIP_TRY(hipMemset((uint8_t*)ix->ex.p + nslots * exd, 0, 256));
     if (zero_fill) { // streamed build: padding slots are never visited by the scatter kernels
         HIP_TRY(hipMemset(ix->ids.p, 0xff, nslots * 8));
         if (exd) HIP_TRY(hipMemset(ix->ex.p, 0, nslots * exd));
         if (ix->ex_bits) { HIP_TRY(hipMemset(ix->fadd_ex.p, 0, nslots * 4)); HIP_TRY(hipMemset(ix->fres_ex.p, 0, nslots * 4)); }
+        HIP_TRY(hipMemset(ix->delta.p, 0, nslots * 4)); HIP_TRY(hipMemset(ix->vl.p, 0, nslots * 4));
     }
     return RBQ_OK;
 }
@@ -892,6 +931,7 @@ int build_device_impl(const rbq_header* hdr, const float* centroids, const float
             P.row_slot = nullptr; P.t_row = d_t;
             P.blocks = (uint8_t*)ix->blocks.p + b0 * dev_stride; P.raw_ex = d_raw;
             P.f_add_ex = (float*)ix->fadd_ex.p + s0; P.f_rescale_ex = (float*)ix->fres_ex.p + s0; P.ids = (uint64_t*)ix->ids.p + s0;
+            P.delta = (float*)ix->delta.p + s0; P.vl = (float*)ix->vl.p + s0;
             P.src_base = 0; P.nslots = (uint32_t)ns; P.D = D; P.Dc = Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.t_const = t_const;
             HIP_TRY(launch_encode(P, 0));
             if (ix->ex_bits)
@@ -1044,6 +1084,7 @@ int stream_push_impl(rbq_builder* b, const float* vectors, const uint32_t* assig
         P.block_list = b->d_block_list; P.row_slot = (const uint32_t*)b->row_slot.p; P.t_row = b->opt ? (const double*)b->trow.p : nullptr;
         P.blocks = (uint8_t*)ix->blocks.p; P.raw_ex = (uint8_t*)b->raw.p;
         P.f_add_ex = (float*)ix->fadd_ex.p; P.f_rescale_ex = (float*)ix->fres_ex.p; P.ids = (uint64_t*)ix->ids.p;
+        P.delta = (float*)ix->delta.p; P.vl = (float*)ix->vl.p;
         P.src_base = first_id + s0; P.nslots = n; P.D = D; P.Dc = Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.t_const = b->t_const;
         HIP_TRY(launch_encode(P, 0));
         if (ix->ex_bits)
@@ -1568,7 +1609,7 @@ int rbq_last_error_detail(char* buf, size_t n) {
 int rbq_index_create(const rbq_header* hdr, const rbq_list_view* lists, int n_devices, const int* devices, rbq_index** out) {
     g_err.clear();
     RBQ_GUARD_BEGIN
-    return create_impl(hdr, lists, n_devices, devices, out);
+    return create_impl(hdr, lists, nullptr, nullptr, n_devices, devices, out);
     RBQ_GUARD_END
 }
 
@@ -2122,6 +2163,7 @@ int rbq_debug_set_option(rbq_index* h, const char* name, int value) {
         else if (!std::strcmp(name, "host_trace")) ix->host_trace = value != 0;
         else if (!std::strcmp(name, "lazy_fault_inject")) ix->lazy_fault_inject = value != 0;
         else if (!std::strcmp(name, "lazy_audit")) ix->lazy_audit = value != 0;
+        else if (!std::strcmp(name, "save_chunk")) ix->save_chunk = value > 0 ? (uint64_t)value : 0u;
         else if (!std::strcmp(name, "slack_term")) ix->slack_term = value;
         else if (!std::strcmp(name, "slack_milli")) { // TEST ONLY: term `slack_term` of block_ub()'s slack times value / 1000 (1000 = the product)
             float* f[6] = {&ix->slack.ge, &ix->slack.eip, &ix->slack.est, &ix->slack.lb, &ix->slack.et, &ix->slack.dist};
@@ -2249,9 +2291,225 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
     else if (!std::strcmp(name, "centroids")) { p = ix->centroids.p; have = ix->n_lists * ix->D * 4; }
     else if (!std::strcmp(name, "list_gb0")) { p = ix->list_gb0.p; have = ix->n_lists * 4; }
     else if (!std::strcmp(name, "list_n")) { p = ix->list_n.p; have = ix->n_lists * 4; }
+    else if (!std::strcmp(name, "delta") || !std::strcmp(name, "vl")) { // (first replica only)
+        ix = h->reps[0];
+        p = name[0] == 'd' ? ix->delta.p : ix->vl.p; have = ix->has_recon ? ix->n_blocks * 32 * 4 : 0;
+    }
     if (!p || bytes != have) return fail(RBQ_INVALID_CONFIG, "unknown array or size (have " + std::to_string(have) + " bytes)");
     DeviceGuard g(ix->device);
     HIP_TRY(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+
+} // extern "C"
+
+// ---- RBQ1 writer: save_to_writer, src/ivf.rs:1310-1474 ----------------------------------------------------------------
+namespace {
+
+constexpr uint64_t kSaveChunkBytes = 64ull << 20; // staging chunk (the load path's bound)
+
+struct SaveRes { // everything a save allocates, freed on every exit (the handle itself is only read)
+    hipStream_t st = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    TempDev dev;
+    void* pin[2] = {nullptr, nullptr};
+    ~SaveRes() {
+        if (st) (void)hipStreamSynchronize(st);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (void* p : pin) if (p) (void)hipHostFree(p);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
+// words of every cluster in the cluster section (src/ivf.rs:1415-1466): centroid | n | ids | batch_data_len | batch_data |
+// n x (len | ex code) | f_add_ex | f_rescale_ex | delta | vl
+void save_layout(const Replica* ix, std::vector<uint64_t>& woff) {
+    const uint64_t D = ix->D, exw = D * ix->ex_bits / 32;
+    woff.assign(ix->n_lists + 1, 0);
+    for (uint64_t c = 0; c < ix->n_lists; ++c) {
+        const uint64_t n = ix->h_list_n[c], nb = (n + 31) / 32;
+        woff[c + 1] = woff[c] + D + 4 + 2 * n + nb * (D + 96) + n * (2 + exw) + 4 * n;
+    }
+}
+
+int save_check(const rbq_index* h) {
+    if (!h || h->reps.empty()) return fail(RBQ_INVALID_CONFIG, "null index");
+    const Replica* ix = h->reps[0];
+    if (ix->rotator == RBQ_ROTATOR_NONE)
+        return fail(RBQ_INVALID_CONFIG, "posting-list handles (RBQ_ROTATOR_NONE) have no RBQ1 rotator tag and cannot be saved");
+    if (!ix->has_recon)
+        return fail(RBQ_INVALID_CONFIG, "the index holds no reconstruction factors (delta / vl): it was made by rbq_index_create; "
+                                        "use rbq_index_create_with_recon, rbq_index_load_rbq1 or a device encoder");
+    return RBQ_OK;
+}
+
+uint64_t save_total_bytes(const Replica* ix) {
+    std::vector<uint64_t> woff;
+    save_layout(ix, woff);
+    return 44 + ix->rot_blob.bytes + woff.back() * 4 + 4;
+}
+
+int save_impl(const rbq_index* h, rbq_write_fn write, void* user) {
+    int rc = save_check(h);
+    if (rc) return rc;
+    if (!write) return fail(RBQ_INVALID_CONFIG, "null writer");
+    const Replica* ix = h->reps[0];
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    const uint64_t rot_len = ix->rot_blob.bytes;
+    std::vector<uint64_t> woff;
+    save_layout(ix, woff);
+    const uint64_t total_w = woff.back();
+
+    SaveRes R;
+    HIP_TRY(hipStreamCreateWithFlags(&R.st, hipStreamNonBlocking));
+    for (auto& e : R.ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    uint64_t chunk_w = (ix->save_chunk ? ix->save_chunk : kSaveChunkBytes) / 4;
+    chunk_w = std::max<uint64_t>(1, std::min<uint64_t>(chunk_w, std::max<uint64_t>(total_w, 1)));
+    const uint64_t chunk_b = chunk_w * 4;
+    uint64_t* d_woff = nullptr;
+    uint32_t *d_seg = nullptr, *d_crc = nullptr;
+    uint8_t* d_stage[2] = {nullptr, nullptr};
+    HIP_TRY(R.dev.alloc((void**)&d_woff, woff.size() * 8));
+    HIP_TRY(R.dev.alloc((void**)&d_seg, std::max(crc_scratch_words(chunk_b), crc_scratch_words(rot_len)) * 4));
+    HIP_TRY(R.dev.alloc((void**)&d_crc, 3 * 4)); // [0], [1]: chunk CRC of buffer 0 / 1; [2]: rotator
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(R.dev.alloc((void**)&d_stage[i], chunk_b));
+        HIP_TRY(hipHostMalloc(&R.pin[i], chunk_b + 4, hipHostMallocDefault));
+    }
+    HIP_TRY(hipMemcpyAsync(d_woff, woff.data(), woff.size() * 8, hipMemcpyHostToDevice, R.st));
+
+    // header and rotator (save_to_writer: magic, version, then the hashed fields)
+    std::vector<uint8_t> head(44 + rot_len); // magic, version, 36 hashed header bytes, rotator
+    {
+        uint8_t* o = head.data();
+        auto put = [&](const void* p, size_t n) { std::memcpy(o, p, n); o += n; };
+        const uint32_t version = 3, dim = ix->dim, D = ix->D;
+        const uint8_t tags[4] = {ix->metric, ix->rotator, ix->ex_bits, (uint8_t)(ix->ex_bits + 1)};
+        const uint64_t nv = ix->n_vectors, nl = ix->n_lists;
+        put("RBQ1", 4); put(&version, 4); put(&dim, 4); put(&D, 4); put(tags, 4); put(&nv, 8); put(&nl, 8); put(&rot_len, 8);
+    }
+    uint32_t crc = rbq_host::crc32_update(0, head.data() + 8, 36);
+    if (rot_len) {
+        HIP_TRY(hipMemcpyAsync(head.data() + 44, ix->rot_blob.p, rot_len, hipMemcpyDeviceToHost, R.st));
+        HIP_TRY(launch_crc32((const uint8_t*)ix->rot_blob.p, rot_len, d_seg, d_crc + 2, R.st));
+        uint32_t rot_crc = 0;
+        HIP_TRY(hipMemcpyAsync(&rot_crc, d_crc + 2, 4, hipMemcpyDeviceToHost, R.st));
+        HIP_TRY(hipStreamSynchronize(R.st));
+        crc = rbq_host::crc32_combine(crc, rot_crc, rot_len);
+    }
+    if (write(user, head.data(), head.size()) != 0) return fail(RBQ_IO, "the writer failed (header)");
+
+    SaveParams P;
+    P.woff = d_woff; P.list_gb0 = (const uint32_t*)ix->list_gb0.p; P.list_n = (const uint32_t*)ix->list_n.p;
+    P.centroids = (const float*)ix->centroids.p; P.blocks = (const uint8_t*)ix->blocks.p; P.ids = (const uint64_t*)ix->ids.p;
+    P.ex = (const uint8_t*)ix->ex.p; P.fadd_ex = (const float*)ix->fadd_ex.p; P.fres_ex = (const float*)ix->fres_ex.p;
+    P.delta = (const float*)ix->delta.p; P.vl = (const float*)ix->vl.p;
+    P.exd = ex_bytes_dev(ix->D, ix->ex_bits); P.n_lists = (uint32_t)ix->n_lists; P.D = ix->D; P.Dc = ix->Dc; P.ex_bits = ix->ex_bits;
+    P.ex_words = ix->D * ix->ex_bits / 32; P.cpu = ex_cpu(ix->ex_bits);
+
+    // double-buffered chunks: the kernels fill chunk i + 1 (and its copy runs) while the writer takes chunk i
+    const uint64_t nchunks = (total_w + chunk_w - 1) / chunk_w;
+    auto issue = [&](uint64_t k) -> int {
+        const int b = (int)(k & 1);
+        const uint64_t w0 = k * chunk_w, nw = std::min(chunk_w, total_w - w0);
+        HIP_TRY(launch_save_fill(P, w0, nw, (uint32_t*)d_stage[b], R.st));
+        HIP_TRY(launch_crc32(d_stage[b], nw * 4, d_seg, d_crc + b, R.st));
+        HIP_TRY(hipMemcpyAsync(R.pin[b], d_stage[b], nw * 4, hipMemcpyDeviceToHost, R.st));
+        HIP_TRY(hipMemcpyAsync((uint8_t*)R.pin[b] + chunk_b, d_crc + b, 4, hipMemcpyDeviceToHost, R.st));
+        HIP_TRY(hipEventRecord(R.ev[b], R.st));
+        return RBQ_OK;
+    };
+    if (nchunks && (rc = issue(0))) return rc;
+    for (uint64_t k = 0; k < nchunks; ++k) {
+        if (k + 1 < nchunks && (rc = issue(k + 1))) return rc;
+        const int b = (int)(k & 1);
+        HIP_TRY(hipEventSynchronize(R.ev[b]));
+        const uint64_t nb = std::min(chunk_w, total_w - k * chunk_w) * 4;
+        uint32_t ccrc;
+        std::memcpy(&ccrc, (const uint8_t*)R.pin[b] + chunk_b, 4);
+        crc = rbq_host::crc32_combine(crc, ccrc, nb);
+        if (write(user, R.pin[b], nb) != 0) return fail(RBQ_IO, "the writer failed (chunk " + std::to_string(k) + ")");
+    }
+    if (write(user, &crc, 4) != 0) return fail(RBQ_IO, "the writer failed (checksum)");
+    HIP_TRY(hipStreamSynchronize(R.st));
+    return RBQ_OK;
+}
+
+struct BufSink { uint8_t* p; uint64_t cap, len; };
+int buf_sink(void* user, const void* bytes, uint64_t len) {
+    BufSink* s = (BufSink*)user;
+    if (s->len + len > s->cap) return 1;
+    std::memcpy(s->p + s->len, bytes, len);
+    s->len += len;
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int rbq_index_create_with_recon(const rbq_header* hdr, const rbq_list_view* lists, const float* const* delta, const float* const* vl,
+                                int n_devices, const int* devices, rbq_index** out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!delta || !vl) return fail(RBQ_INVALID_CONFIG, "null delta / vl table");
+    return create_impl(hdr, lists, delta, vl, n_devices, devices, out);
+    RBQ_GUARD_END
+}
+
+int rbq_index_save_rbq1_stream(const rbq_index* idx, rbq_write_fn write, void* user) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    return save_impl(idx, write, user);
+    RBQ_GUARD_END
+}
+
+int rbq_index_save_rbq1(const rbq_index* idx, uint8_t** bytes, uint64_t* len) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!bytes || !len) return fail(RBQ_INVALID_CONFIG, "null output");
+    *bytes = nullptr; *len = 0;
+    int rc = save_check(idx);
+    if (rc) return rc;
+    const uint64_t total = save_total_bytes(idx->reps[0]);
+    BufSink sink{(uint8_t*)std::malloc(total ? total : 1), total, 0};
+    if (!sink.p) return fail(RBQ_IO, "out of host memory");
+    rc = save_impl(idx, buf_sink, &sink);
+    if (rc == RBQ_OK && sink.len != total) rc = fail(RBQ_IO, "internal error: stream length");
+    if (rc) { std::free(sink.p); return rc; }
+    *bytes = sink.p; *len = total;
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+
+void rbq_persist_free_bytes(uint8_t* bytes) { std::free(bytes); }
+
+int rbq_debug_crc32_device(const void* d_bytes, uint64_t len, int device, uint32_t* out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!out || (len && !d_bytes)) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    std::vector<int> devs;
+    int rc = resolve_devices(1, &device, devs);
+    if (rc) return rc;
+    DeviceGuard g(device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    if (len) { // the range must lie inside one device allocation
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RBQ_INVALID_CONFIG, "not a device allocation");
+        }
+        if ((const uint8_t*)d_bytes + len > (const uint8_t*)base + size) return fail(RBQ_INVALID_CONFIG, "range exceeds the allocation");
+    }
+    TempDev t;
+    uint32_t *d_seg = nullptr, *d_out = nullptr;
+    HIP_TRY(t.alloc((void**)&d_seg, crc_scratch_words(len) * 4));
+    HIP_TRY(t.alloc((void**)&d_out, 4));
+    HIP_TRY(launch_crc32((const uint8_t*)d_bytes, len, d_seg, d_out, 0));
+    HIP_TRY(hipMemcpy(out, d_out, 4, hipMemcpyDeviceToHost));
     return RBQ_OK;
     RBQ_GUARD_END
 }

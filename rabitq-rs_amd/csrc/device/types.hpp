@@ -203,6 +203,8 @@ struct EncodeParams {
     uint8_t* raw_ex;            // [nrows][D] u8 scratch (ex_bits > 0)
     float* f_add_ex;            // like `blocks`
     float* f_rescale_ex;
+    float* delta;               // reconstruction factors delta / vl, slot order like f_add_ex (null: not written)
+    float* vl;
     uint64_t* ids;
     uint64_t src_base;          // ids[slot] = src_base + source index (scatter mode: src_base + row)
     uint32_t nslots, D, Dc, ex_bits, metric;

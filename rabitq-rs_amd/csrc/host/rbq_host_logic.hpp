@@ -29,6 +29,8 @@ struct ListSrc {
     size_t ex_stride = 0;
     const uint8_t* fadd = nullptr;       // n f32
     const uint8_t* fres = nullptr;       // n f32
+    const uint8_t* delta = nullptr;      // n f32 (reconstruction factors; null: the source has none)
+    const uint8_t* vl = nullptr;         // n f32
 };
 
 struct Reader {
@@ -36,6 +38,30 @@ struct Reader {
     bool take(void* dst, size_t n) { if (off + n > len || off + n < off) return false; std::memcpy(dst, p + off, n); off += n; return true; }
     const uint8_t* view(size_t n) { if (off + n > len || off + n < off) return nullptr; const uint8_t* r = p + off; off += n; return r; }
 };
+
+// GF(2) arithmetic of CRC-32/IEEE (reflected, polynomial 0xEDB88320), zlib's crc32_combine: with A = crc32(a) and
+// B = crc32(b), crc32(a || b) = (A * x^(8 len(b)) mod P) ^ B.  The device CRC (k_save.hip) uses the same formulas.
+inline uint32_t crc32_multmodp(uint32_t a, uint32_t b) { // a(x) * b(x) mod P(x), bit 31 = x^0
+    uint32_t m = 1u << 31, p = 0;
+    for (;;) {
+        if (a & m) { p ^= b; if ((a & (m - 1)) == 0) break; }
+        m >>= 1;
+        b = (b & 1) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
+    }
+    return p;
+}
+inline uint32_t crc32_x8nmodp(uint64_t n) { // x^(8n) mod P(x)
+    uint32_t p = 1u << 31, sq = 1u << 23;   // x^0; x^8
+    while (n) {
+        if (n & 1) p = crc32_multmodp(sq, p);
+        sq = crc32_multmodp(sq, sq);
+        n >>= 1;
+    }
+    return p;
+}
+inline uint32_t crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+    return crc32_multmodp(crc32_x8nmodp(len_b), crc_a) ^ crc_b;
+}
 
 inline uint32_t crc32_ieee(const uint8_t* p, size_t n) {
     static uint32_t table[8][256];
@@ -60,6 +86,12 @@ inline uint32_t crc32_ieee(const uint8_t* p, size_t n) {
     }
     while (n--) crc = table[0][(crc ^ *p++) & 0xff] ^ (crc >> 8);
     return ~crc;
+}
+
+// Incremental form: crc32_update(crc32_update(0, a), b) == crc32_ieee(a || b); crc32_update(0, p, n) == crc32_ieee(p, n).
+inline uint32_t crc32_update(uint32_t crc, const uint8_t* p, size_t n) {
+    if (!n) return crc;
+    return crc32_combine(crc, crc32_ieee(p, n), n);
 }
 
 // Parses and validates an RBQ1 v3 stream in place (the lists are byte ranges of `bytes`: nothing is copied).  Returns
@@ -136,7 +168,9 @@ inline int rbq1_parse(const void* bytes, size_t len, rbq_header* hout, std::vect
         L.fadd = r.view(n * 4);
         L.fres = r.view(n * 4);
         if (!L.fadd || !L.fres) return eof();
-        if (!r.view(n * 4) || !r.view(n * 4)) return eof(); // delta, vl: reconstruction only
+        L.delta = r.view(n * 4); // delta, vl: reconstruction only (kept for rbq_index_save_rbq1)
+        L.vl = r.view(n * 4);
+        if (!L.delta || !L.vl) return eof();
         actual += n;
     }
     if (actual != expected_vectors) return fail(RBQ_INVALID_PERSISTENCE, "vector count metadata mismatch");

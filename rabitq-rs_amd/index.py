@@ -127,8 +127,23 @@ def lib():
         L.rbq_kmeans_device.restype = C.c_int
         L.rbq_kmeans_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
                                         C.c_uint64, C.c_uint64, C.c_int, vp, vp, C.POINTER(C.c_double), vp]
+        # rbq_persist.h
+        L.rbq_index_create_with_recon.restype = C.c_int
+        L.rbq_index_create_with_recon.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.POINTER(vp)]
+        L.rbq_index_save_rbq1_stream.restype = C.c_int
+        L.rbq_index_save_rbq1_stream.argtypes = [vp, WRITE_FN, vp]
+        L.rbq_index_save_rbq1.restype = C.c_int
+        L.rbq_index_save_rbq1.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
+        L.rbq_persist_free_bytes.restype = None
+        L.rbq_persist_free_bytes.argtypes = [C.POINTER(C.c_uint8)]
+        L.rbq_debug_crc32_device.restype = C.c_int
+        L.rbq_debug_crc32_device.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]
         _LIB = L
     return _LIB
+
+
+# rbq_write_fn: int (*)(void* user, const void* bytes, uint64_t len)
+WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
 
 
 def _detail():
@@ -171,7 +186,23 @@ class IvfRabitqIndex:
 
     @classmethod
     def from_built(cls, built, device=None, devices=None):
-        """Upload a builder.BuiltIndex (ClusterData-shaped host arrays) via rbq_index_create."""
+        """Upload a builder.BuiltIndex (ClusterData-shaped host arrays) with its reconstruction factors delta / vl
+        (rbq_index_create_with_recon), so that the handle can be saved."""
+        from . import builder
+        h = C.c_void_p()
+        n, dev = cls._devices(device, devices)
+        nl = int(built.header.n_lists)
+        fp = C.POINTER(C.c_float)
+        delta, vl = (fp * nl)(), (fp * nl)()
+        for c in range(nl):
+            _check(builder.lib().rbq_built_list_recon(built._h, c, C.byref(delta[c]), C.byref(vl[c])))
+        _check(lib().rbq_index_create_with_recon(_addr(built.hdr_ptr), _addr(built.lists_ptr), C.cast(delta, C.c_void_p),
+                                                 C.cast(vl, C.c_void_p), n, dev, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_built_without_recon(cls, built, device=None, devices=None):
+        """rbq_index_create: the same index without its reconstruction factors (it searches alike but cannot be saved)."""
         h = C.c_void_p()
         n, dev = cls._devices(device, devices)
         _check(lib().rbq_index_create(_addr(built.hdr_ptr), _addr(built.lists_ptr), n, dev, C.byref(h)))
@@ -278,6 +309,52 @@ class IvfRabitqIndex:
             from . import RabitqError
             raise RabitqError(_abi.RBQ_IO, str(e))
         return cls.load_from_bytes(data, device)
+
+    # -- persistence: save_to_writer (src/ivf.rs:1310-1474), bytes assembled on the device ------------------------
+    def save_to_writer(self, fileobj):
+        """Write the RBQ1 stream to `fileobj` (anything with .write(bytes)), chunk by chunk
+        (rbq_index_save_rbq1_stream).  A writer exception stops the save and is re-raised."""
+        err = []
+
+        def cb(_user, p, n):
+            try:
+                fileobj.write(C.string_at(p, n) if n else b"")
+                return 0
+            except BaseException as e:  # noqa: BLE001 - handed back to the caller after the C call returns
+                err.append(e)
+                return 1
+        fn = WRITE_FN(cb)
+        rc = lib().rbq_index_save_rbq1_stream(self._h, fn, None)
+        if err:
+            raise err[0]
+        _check(rc)
+
+    def save_to_bytes(self):
+        """The whole RBQ1 stream as bytes (rbq_index_save_rbq1)."""
+        p = C.POINTER(C.c_uint8)()
+        n = C.c_uint64()
+        _check(lib().rbq_index_save_rbq1(self._h, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            lib().rbq_persist_free_bytes(p)
+
+    def save_to_path(self, path):
+        """save_to_path: the stream written to a file (created or truncated)."""
+        try:
+            f = open(path, "wb")
+        except OSError as e:
+            from . import RabitqError
+            raise RabitqError(_abi.RBQ_IO, str(e))
+        with f:
+            self.save_to_writer(f)
+
+    @staticmethod
+    def debug_crc32_device(d_ptr, n, device=0):
+        """Test hook (rbq_debug_crc32_device): CRC-32/IEEE of n device bytes at d_ptr, computed by the save path's kernels."""
+        out = C.c_uint32()
+        _check(lib().rbq_debug_crc32_device(C.c_void_p(d_ptr), int(n), int(device), C.byref(out)))
+        return out.value
 
     # -- accessors ----------------------------------------------------------------
     def __len__(self):
