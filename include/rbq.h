@@ -227,6 +227,20 @@ int rbq_search_batch_device(const rbq_index* idx, const float* d_queries, uint64
  * with this index again.  The stream must be idle. */
 int rbq_release_stream(rbq_index* idx, void* hip_stream);
 
+/* IvfRabitqIndex::fetch_embedding (src/ivf.rs:1247-1307) for n ids.  out [n][dim] f32, found [n] u8.
+ * Row i is the crate's fetch_embedding(ids[i]) bit for bit: the first occurrence of the id in (cluster, position) order,
+ * decoded, reconstructed in rotated space and inverse-rotated.  A missing id gives a zero row and found[i] = 0.
+ * Served from the first replica (it keeps the reconstruction factors).  The ids go through page-locked staging in chunks,
+ * so device memory stays bounded for any n.  The first fetch of a handle builds its id map (12 bytes per vector, kept
+ * until destroy).  Re-entrant; a fetch only reads the index, so searches may run alongside it.
+ * Errors: RBQ_INVALID_CONFIG for a handle without reconstruction factors (rbq_index_create), a RBQ_ROTATOR_NONE handle,
+ * or null pointers when n > 0; RBQ_DEVICE.  n == 0 returns RBQ_OK; on an empty index every id is not found. */
+int rbq_index_fetch_embeddings(const rbq_index* idx, const uint64_t* ids, uint64_t n, float* out, uint8_t* found);
+/* The same on device pointers, ENQUEUED on `hip_stream` (NULL = default stream) without host synchronisation (the first
+ * call of a handle may block while the id map is built).  d_ids must be device memory of the first replica's device. */
+int rbq_index_fetch_embeddings_device(const rbq_index* idx, const uint64_t* d_ids, uint64_t n, float* d_out,
+                                      uint8_t* d_found, void* hip_stream);
+
 /* Page-locked host memory for query / result buffers: rbq_search_batch DMA-s such buffers directly. */
 void* rbq_host_alloc(size_t bytes);
 void rbq_host_free(void* p);

@@ -121,6 +121,9 @@ extern "C" {
                                d_out_scores: *mut f32, d_out_counts: *mut u32, d_diag: *mut RbqDiag,
                                hip_stream: *mut c_void) -> c_int;
     fn rbq_release_stream(idx: *mut RbqIndex, hip_stream: *mut c_void) -> c_int;
+    fn rbq_index_fetch_embeddings(idx: *const RbqIndex, ids: *const u64, n: u64, out: *mut f32, found: *mut u8) -> c_int;
+    fn rbq_index_fetch_embeddings_device(idx: *const RbqIndex, d_ids: *const u64, n: u64, d_out: *mut f32, d_found: *mut u8,
+                                         hip_stream: *mut c_void) -> c_int;
     fn rbq_host_alloc(bytes: usize) -> *mut c_void;
     fn rbq_host_free(p: *mut c_void);
     fn rbq_index_set_rerank_vectors(idx: *mut RbqIndex, vectors: *const f32, n: u64) -> c_int;
@@ -375,6 +378,38 @@ impl GpuIvf {
             }
         }
         out.into_iter().map(|r| r.unwrap()).collect()
+    }
+
+    /// `IvfRabitqIndex::fetch_embedding` (src/ivf.rs:1247-1307): the stored vector reconstructed from its codes and
+    /// inverse-rotated on the GPU, bit for bit the crate's; `None` when the id is not in the index (or the call fails: the
+    /// crate's signature has no error, see `fetch_embeddings`).
+    pub fn fetch_embedding(&self, vector_id: usize) -> Option<Vec<f32>> {
+        match self.fetch_embeddings(&[vector_id]) {
+            Ok(mut v) => v.pop().flatten(),
+            Err(_) => None,
+        }
+    }
+
+    /// `fetch_embedding` for many ids in one call (`rbq_index_fetch_embeddings`), in input order.  Errors: `InvalidConfig`
+    /// for an index without reconstruction factors; device failures as `Io`.
+    pub fn fetch_embeddings(&self, ids: &[usize]) -> Result<Vec<Option<Vec<f32>>>, RabitqError> {
+        let n = ids.len();
+        let q: Vec<u64> = ids.iter().map(|&i| i as u64).collect();
+        let mut out = vec![0f32; n * self.dim];
+        let mut found = vec![0u8; n];
+        let rc = unsafe { rbq_index_fetch_embeddings(self.h, q.as_ptr(), n as u64, out.as_mut_ptr(), found.as_mut_ptr()) };
+        map_err(rc, 0, 0)?;
+        Ok((0..n).map(|i| if found[i] != 0 { Some(out[i * self.dim..(i + 1) * self.dim].to_vec()) } else { None }).collect())
+    }
+
+    /// Device form (`rbq_index_fetch_embeddings_device`): `n` ids at `d_ids` (HBM of the first device) -> `d_out` [n][dim] f32,
+    /// `d_found` [n] u8, enqueued on `hip_stream` (null = default stream) without host synchronisation.
+    ///
+    /// # Safety
+    /// The pointers must be device allocations of those sizes that stay valid until the stream has run the call.
+    pub unsafe fn fetch_embeddings_device(&self, d_ids: *const u64, n: usize, d_out: *mut f32, d_found: *mut u8,
+                                          hip_stream: *mut c_void) -> Result<(), RabitqError> {
+        map_err(rbq_index_fetch_embeddings_device(self.h, d_ids, n as u64, d_out, d_found, hip_stream), 0, 0)
     }
 
     /// Which build of this crate the GPU scores reproduce bit for bit (`rbq_index_set_numeric_variant`; INTEGRATION.md,

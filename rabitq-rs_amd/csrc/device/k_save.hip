@@ -6,6 +6,7 @@
 //                    k_spread (slot order -> dense list order, pad slots dropped)
 //   k_crc_segments   CRC-32/IEEE of fixed-size segments of a byte range, slice-by-4 tables in LDS
 //   k_crc_reduce     one workgroup folds the segment CRCs with zlib's crc32_combine (rbq_host_logic.hpp)
+// (the code decoders dev_code_byte / dev_ex_code live in codes.hpp, shared with k_fetch.hip)
 //
 // Every section of the cluster part is a multiple of 4 bytes long (D % 16 == 0), so the section starts at a word
 // boundary of the stream and a thread owns exactly one word; u64 fields are written as two words.  A word finds its
@@ -14,28 +15,11 @@
 
 #include "launch.hpp"
 #include "kernels.hpp"
+#include "codes.hpp"
 
 namespace rbq {
 
 namespace {
-
-// byte `col` of vector v's packed sign code in a device block (k_relayout_blocks' layout)
-__device__ __forceinline__ uint32_t dev_code_byte(const uint8_t* __restrict__ blk, uint32_t G16, uint32_t col, uint32_t v) {
-    const uint32_t g = col >> 4;
-    return g < G16 ? blk[(size_t)g * 512 + v * 16 + (col & 15u)] : blk[(size_t)G16 * 512 + v * 8 + (col & 7u)];
-}
-
-// ex code of dimension i of a slot (lane l = i % 16 owns dims 16t + l; unit t / cpu holds code t % cpu at bit (t % cpu) * ex_bits)
-__device__ __forceinline__ uint32_t dev_ex_code(const uint8_t* __restrict__ exs, uint32_t cpu, uint32_t ex_bits, uint32_t i) {
-    const uint32_t t = i >> 4, l = i & 15u, unit = t / cpu, k = t - unit * cpu;
-    const uint4 u = reinterpret_cast<const uint4*>(exs)[unit * 16 + l];
-    const uint32_t bit = k * ex_bits, idx = bit >> 5, sh = bit & 31u;
-    const uint32_t w0 = idx == 0 ? u.x : idx == 1 ? u.y : idx == 2 ? u.z : u.w;
-    const uint32_t w1 = idx == 0 ? u.y : idx == 1 ? u.z : idx == 2 ? u.w : 0u;
-    uint32_t raw = w0 >> sh;
-    if (sh + ex_bits > 32) raw |= w1 << (32 - sh);
-    return raw & ((1u << ex_bits) - 1u);
-}
 
 __device__ __forceinline__ uint32_t f32_bits(const float* __restrict__ a, size_t i) { return __float_as_uint(a[i]); }
 

@@ -6,6 +6,7 @@
 //   k_build.hip  encoder, reference-layout -> device-layout converters, sorting   (encode.hpp)
 //   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver
 //   k_save.hip   RBQ1 writer: device layout -> save_to_writer's cluster bytes, CRC-32 on the GPU
+//   k_fetch.hip  fetch_embedding: id map, decode + inverse rotation of stored vectors
 #pragma once
 #include <atomic>
 #include <string>
@@ -270,5 +271,30 @@ hipError_t launch_save_fill(const SaveParams& P, uint64_t w0, uint64_t nw, uint3
 constexpr uint32_t kCrcSegment = 4096;
 uint64_t crc_scratch_words(uint64_t n);
 hipError_t launch_crc32(const uint8_t* p, uint64_t n, uint32_t* seg_scratch, uint32_t* out, hipStream_t s);
+
+// ---- fetch_embedding (k_fetch.hip) -------------------------------------------------------------------------------------------
+// id map: the (id, slot) pairs of every real slot in (cluster, position) order, stably sorted by id.  vstart [n_lists + 1] =
+// exclusive prefix of list_n (host); ids_out / slots_out hold n_vectors entries.  tmp == null returns the scratch size in *tmp_bytes.
+hipError_t launch_fetch_gather(const uint64_t* vstart, const uint32_t* list_gb0, uint32_t n_lists, const uint64_t* slot_ids,
+                               uint64_t n_vectors, uint64_t* ids_out, uint32_t* slots_out, hipStream_t s);
+hipError_t sort_pairs_u64_u32(void* tmp, size_t* tmp_bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in,
+                              uint32_t* vals_out, size_t n, hipStream_t s);
+struct FetchParams {
+    const uint64_t* map_ids;    // [n_map] ascending
+    const uint32_t* map_slots;  // [n_map]
+    uint64_t n_map;
+    const uint32_t* list_gb0;   // [n_lists]
+    const float* centroids;     // [n_lists][D] rotated
+    const uint8_t* blocks;      // device block records (stride Dc * 4 + 384)
+    const uint8_t* ex;          // lane-major ex codes, exd bytes per slot (ex_bits > 0)
+    const float *delta, *vl;    // slot order
+    const uint8_t* rot_blob;    // FHT-Kac: 4 x D / 8 flip bytes; Matrix: [D][D] f32 row-major
+    uint64_t exd;
+    uint32_t n_lists, dim, D, Dc, ex_bits, cpu, rotator, trunc;
+    float rfac, rlen;           // 1 / fac and 1 / (FHT length), f32 divisions on the host
+};
+// n ids -> out [n][dim] f32, found [n] u8 (a missing id: zero row, 0).  Matrix rotator: `rows` is [n][D] f32 scratch.
+hipError_t launch_fetch(const FetchParams& P, const uint64_t* ids, uint64_t n, float* out, uint8_t* found, float* rows,
+                        hipStream_t s);
 
 } // namespace rbq

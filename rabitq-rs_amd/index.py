@@ -138,6 +138,10 @@ def lib():
         L.rbq_persist_free_bytes.argtypes = [C.POINTER(C.c_uint8)]
         L.rbq_debug_crc32_device.restype = C.c_int
         L.rbq_debug_crc32_device.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]
+        L.rbq_index_fetch_embeddings.restype = C.c_int
+        L.rbq_index_fetch_embeddings.argtypes = [vp, vp, C.c_uint64, vp, vp]
+        L.rbq_index_fetch_embeddings_device.restype = C.c_int
+        L.rbq_index_fetch_embeddings_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
         _LIB = L
     return _LIB
 
@@ -355,6 +359,28 @@ class IvfRabitqIndex:
         out = C.c_uint32()
         _check(lib().rbq_debug_crc32_device(C.c_void_p(d_ptr), int(n), int(device), C.byref(out)))
         return out.value
+
+    # -- fetch_embedding (src/ivf.rs:1247-1307), decoded and inverse-rotated on the device ----------------------------
+    def fetch_embeddings(self, ids):
+        """rbq_index_fetch_embeddings: (out [n, dim] f32, found [n] bool).  Row i is the crate's fetch_embedding(ids[i]) bit
+        for bit (the first occurrence in (cluster, position) order); a missing id gives a zero row and found False."""
+        q = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+        n = int(q.size)
+        out = np.empty((n, self.dim), np.float32)
+        found = np.empty(n, np.uint8)
+        _check(lib().rbq_index_fetch_embeddings(self._h, q.ctypes.data, n, out.ctypes.data, found.ctypes.data))
+        return out, found.astype(bool)
+
+    def fetch_embedding(self, vector_id):
+        """`IvfRabitqIndex::fetch_embedding`: the reconstructed vector [dim] f32, or None when the id is not in the index."""
+        out, found = self.fetch_embeddings([vector_id])
+        return out[0] if found[0] else None
+
+    def fetch_embeddings_device(self, d_ids, n, d_out, d_found, stream=None):
+        """rbq_index_fetch_embeddings_device: n u64 ids at d_ids (device memory of the first replica's device) -> d_out
+        [n][dim] f32, d_found [n] u8, enqueued on `stream` (a hipStream_t as int, None = default stream)."""
+        _check(lib().rbq_index_fetch_embeddings_device(self._h, C.c_void_p(d_ids), int(n), C.c_void_p(d_out), C.c_void_p(d_found),
+                                                       C.c_void_p(stream) if stream else None))
 
     # -- accessors ----------------------------------------------------------------
     def __len__(self):
