@@ -8,7 +8,10 @@ import os
 
 import numpy as np
 
-from ._abi import BF_FACTORS, BfView, Header, ListView, RBQ_OK
+from ._abi import BF_FACTORS, ROTATOR_FHT_KAC, BfView, Header, ListView, RBQ_OK
+
+# the device library's message for a padded_dim that is not a multiple of 16 (validate_header); the CPU builders return only the code
+NOT_MULTIPLE_OF_16 = "Dimension must be multiple of 16 for SIMD"
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -169,7 +172,8 @@ def train_with_clusters(data, centroids, assignments, total_bits, metric, rotato
         total_bits, metric, rotator_type, seed, int(use_faster_config), C.byref(h))
     if rc != RBQ_OK:
         from . import RabitqError
-        raise RabitqError(rc, "train_with_clusters rejected its configuration")
+        raise RabitqError(rc, NOT_MULTIPLE_OF_16 if rotator_type != ROTATOR_FHT_KAC and dim % 16 else
+                          "train_with_clusters rejected its configuration")
     return BuiltIndex(h)
 
 
@@ -284,5 +288,6 @@ def train_bruteforce(data, total_bits, metric, rotator_type, seed, use_faster_co
                                           int(bool(use_faster_config)), C.byref(h))
     if rc != RBQ_OK:
         raise RabitqError(rc, "total_bits %d (ex_bits %d) is not supported: only 1, 3 and 7 total bits" % (total_bits, total_bits - 1)
-                          if total_bits - 1 not in (0, 2, 6) else "train_bruteforce rejected its configuration")
+                          if total_bits - 1 not in (0, 2, 6) else NOT_MULTIPLE_OF_16 if rotator_type != ROTATOR_FHT_KAC and dim % 16
+                          else "train_bruteforce rejected its configuration")
     return BuiltBruteForce(h)

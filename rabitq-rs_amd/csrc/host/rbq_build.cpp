@@ -396,13 +396,14 @@ int rbq_build_train_with_clusters(const float* data, uint64_t n, uint32_t dim,
     std::memset(&b->hdr, 0, sizeof b->hdr);
     b->hdr.dim = dim; b->hdr.padded_dim = D; b->hdr.metric = metric; b->hdr.rotator = rotator_type; b->hdr.ex_bits = (uint8_t)ex_bits;
     if (rotator_type > RBQ_ROTATOR_NONE) { delete b; return RBQ_INVALID_CONFIG; }
-    if (rotator_type == RBQ_ROTATOR_NONE) {
-        if (dim % 16 != 0) { delete b; return RBQ_INVALID_CONFIG; } // FastScan asserts dim % 16 == 0
-    } else if (rotator_type == RBQ_ROTATOR_FHT_KAC) {
+    // FastScan asserts dim % 16 == 0, and the ex-code packers below write whole 16-dimension groups: the Matrix rotator and NONE
+    // keep padded_dim == dim, so a dim that is not a multiple of 16 is refused (it overran the packed codes' buffers)
+    if (rotator_type != RBQ_ROTATOR_FHT_KAC && dim % 16 != 0) { delete b; return RBQ_INVALID_CONFIG; }
+    if (rotator_type == RBQ_ROTATOR_FHT_KAC) {
         Rng rng(seed);
         b->rotator_blob.resize(4 * D / 8);
         for (auto& x : b->rotator_blob) x = (uint8_t)(rng.next() >> 56);
-    } else {
+    } else if (rotator_type != RBQ_ROTATOR_NONE) {
         std::vector<float> m = make_matrix_rotator(D, seed);
         b->rotator_blob.resize(m.size() * 4);
         std::memcpy(b->rotator_blob.data(), m.data(), m.size() * 4);
@@ -594,6 +595,9 @@ int rbq_build_train_bruteforce(const float* data, uint64_t n, uint32_t dim, uint
     if (ex_bits != 0 && ex_bits != 2 && ex_bits != 6) return RBQ_INVALID_CONFIG;
     if (dim == 0 || metric > 1 || rotator_type > RBQ_ROTATOR_FHT_KAC) return RBQ_INVALID_CONFIG;
     const uint32_t D = rotator_type == RBQ_ROTATOR_FHT_KAC ? (dim + 63) / 64 * 64 : dim;
+    // the crate packs the ex codes of a dim that is not a multiple of 16 in another (bit-serial) layout, which this project does not
+    // serve (bf_validate: "Dimension must be multiple of 16 for SIMD"); the packers below write whole 16-dimension groups
+    if (D % 16 != 0) return RBQ_INVALID_CONFIG;
     rbq_bf_built* b = new rbq_bf_built();
     std::memset(&b->hdr, 0, sizeof b->hdr);
     b->hdr.dim = dim; b->hdr.padded_dim = D; b->hdr.metric = metric; b->hdr.rotator = rotator_type; b->hdr.ex_bits = (uint8_t)ex_bits;

@@ -96,8 +96,8 @@ def test_device_recon_factors_match_cpu_bitwise():
     import torch
     data, cent, assign = _dataset(960, 0, 5)
     built = rq.builder.train_with_clusters(data, cent, assign, 7, 0, 1, 9, False)
-    idx = rq.IvfRabitqIndex.build_on_device(built.hdr_ptr, cent, torch.from_numpy(data).cuda().data_ptr(),
-                                            torch.from_numpy(assign.astype(np.int32)).cuda().data_ptr(), data.shape[0],
+    xd, ad = torch.from_numpy(data).cuda(), torch.from_numpy(assign.astype(np.int32)).cuda()  # (held: a temporary's memory is reused)
+    idx = rq.IvfRabitqIndex.build_on_device(built.hdr_ptr, cent, xd.data_ptr(), ad.data_ptr(), data.shape[0],
                                             rescale="optimal")
     nslots = sum((s + 31) // 32 for s in SIZES) * 32
     for name in ("delta", "vl"):
