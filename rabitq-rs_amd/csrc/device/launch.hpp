@@ -26,13 +26,14 @@ struct LdsAttrCache {
 
 // Launch probe (diagnostic: rbq_debug_stage_resources).  While the calling thread has a probe installed, the four stage
 // launchers record WHICH kernel instantiation they would launch, and its geometry, instead of launching it.
-struct KernelProbe { const void* fn = nullptr; uint32_t grid_x = 0, grid_y = 0, block = 0; size_t dyn_lds = 0; };
+struct KernelProbe { const void* fn = nullptr; uint32_t grid_x = 0, grid_y = 0, grid_z = 0, block = 0; size_t dyn_lds = 0; };
 struct StageProbes { KernelProbe k[4]; }; // prep, rank, select, scan
 StageProbes*& stage_probes(); // this thread's probe (null: launch normally)
 inline bool probe_stage(int stage, const void* fn, dim3 grid, uint32_t block, size_t lds) {
     StageProbes* p = stage_probes();
     if (!p) return false;
-    p->k[stage].fn = fn; p->k[stage].grid_x = grid.x; p->k[stage].grid_y = grid.y; p->k[stage].block = block; p->k[stage].dyn_lds = lds;
+    p->k[stage].fn = fn; p->k[stage].grid_x = grid.x; p->k[stage].grid_y = grid.y; p->k[stage].grid_z = grid.z;
+    p->k[stage].block = block; p->k[stage].dyn_lds = lds;
     return true;
 }
 

@@ -263,7 +263,7 @@ struct Replica {
     bool rerank = false;
     uint32_t numeric_variant = 0; // RBQ_NUMERIC_*: which build of the reference the kernels reproduce (kernels.hpp, kVar*)
     uint32_t host_lanes = 0, host_subbatch = 0, host_trace = 0; // rbq_debug_set_option: pipeline shape of rbq_search_batch (0 = default)
-    int rank_ksplit = 1;              // option rank_ksplit: 0 = never split the ranking GEMM's K loop, 1 = by batch size, n > 1 = forced
+    int rank_ksplit = 1;              // option rank_ksplit: 0 = never split the ranking GEMM's K loop, 1 = by batch size, n > 1 = forced (min(n, 4) parts)
     int host_taper = 0;               // option host_taper: weights of a call's sub-batches (rbq_host_logic.hpp; A/B runs)
     uint32_t host_zero_copy_min = 5;  // option host_zero_copy_min: smallest call whose queries are read in place (up to 4 queries take the
                                       // latency-first front: a hundred workgroups per query would each read it over PCIe)
@@ -1263,7 +1263,8 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
         const uint64_t tiles = (uint64_t)((nlist + T - 1) / T) * ((nq + T - 1) / T);
         ksplit = tiles >= 512 ? 1u : (tiles >= 256 ? 2u : 4u);
         while (ksplit > 1 && (D / 32) / ksplit < 6) ksplit >>= 1; // (at least six slabs per part)
-        if (ix->rank_ksplit > 1) ksplit = (uint32_t)ix->rank_ksplit; // (option: forced)
+        // (option: forced; at most 4 parts, the most the eps of k_select_mfma is derived for — rank_mfma.hpp header)
+        if (ix->rank_ksplit > 1) ksplit = (uint32_t)std::min(ix->rank_ksplit, 4);
     }
     const bool lat_front = ix->latency_path && nq <= kLatMaxQueries && ix->rotator != 0 && !ix->wg_prep && !ix->exact_rank && !big_nprobe &&
                            !ix->f32_rank && (uint64_t)nlist * D * 4 * nq <= kLatMaxBytes && D % 16 == 0 && smask == 0xfu;
@@ -2238,7 +2239,8 @@ int rbq_debug_stage_resources(rbq_index* h, uint64_t nq, uint32_t top_k, uint32_
             continue;
         }
         HIP_TRY(hipFuncGetAttributes(&fa, k.fn));
-        o[0] = k.grid_x * (k.grid_y ? k.grid_y : 1u); o[1] = k.block; o[2] = (uint32_t)fa.numRegs;
+        o[0] = k.grid_x * (k.grid_y ? k.grid_y : 1u) * (k.grid_z ? k.grid_z : 1u); // (z: the parts of a split-K GEMM)
+        o[1] = k.block; o[2] = (uint32_t)fa.numRegs;
         o[3] = (uint32_t)(fa.sharedSizeBytes + k.dyn_lds); o[4] = (uint32_t)fa.localSizeBytes; o[5] = 0;
     }
     return RBQ_OK;
@@ -2271,6 +2273,8 @@ int rbq_debug_copy_workspace(rbq_index* h, void* hip_stream, const char* name, v
     else if (!std::strcmp(name, "nvec")) b = &w->nvec;
     else if (!std::strcmp(name, "dead_skipped")) b = &w->dead_skipped;
     else if (!std::strcmp(name, "audit_dead")) b = &w->audit_dead;
+    else if (!std::strcmp(name, "rot_hi")) b = &w->rot_hi;
+    else if (!std::strcmp(name, "rot_lo")) b = &w->rot_lo;
     if (!b || !b->p || bytes > b->cap) return fail(RBQ_INVALID_CONFIG, "unknown buffer or size");
     DeviceGuard g(ix->device);
     HIP_TRY(hipMemcpy(dst, b->p, bytes, hipMemcpyDeviceToHost));
@@ -2298,6 +2302,9 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
     else if (!std::strcmp(name, "centroids")) { p = ix->centroids.p; have = ix->n_lists * ix->D * 4; }
     else if (!std::strcmp(name, "list_gb0")) { p = ix->list_gb0.p; have = ix->n_lists * 4; }
     else if (!std::strcmp(name, "list_n")) { p = ix->list_n.p; have = ix->n_lists * 4; }
+    else if (!std::strcmp(name, "cent_hi")) { p = ix->cent_hi.p; have = ix->n_lists * ix->D * 2; }
+    else if (!std::strcmp(name, "cent_lo")) { p = ix->cent_lo.p; have = ix->n_lists * ix->D * 2; }
+    else if (!std::strcmp(name, "cnorm2")) { p = ix->cnorm2.p; have = ix->n_lists * 4; }
     else if (!std::strcmp(name, "delta") || !std::strcmp(name, "vl")) { // (first replica only)
         ix = h->reps[0];
         p = name[0] == 'd' ? ix->delta.p : ix->vl.p; have = ix->has_recon ? ix->n_blocks * 32 * 4 : 0;
