@@ -324,7 +324,7 @@ int rbq_debug_copy_index(rbq_index* idx, const char* name, void* dst, uint64_t b
  * dim <= 2048, 1 <= ex_bits <= 7) -> out_t [n] f64, computed by the device encoder's kernel */
 int rbq_debug_best_rescale(const float* o_abs, uint64_t n, uint32_t dim, uint32_t ex_bits, int device, double* out_t);
 /* Diagnostic: copy an intermediate buffer ("rot", "lut", "consts", "scores", "probe", "nstream", "wl", "nvec", "dead_skipped",
- * "audit_dead"; "rot_hi", "rot_lo": the split-bf16 image of the rotated queries, [nq][D] u16, written only when the split-bf16
+ * "audit_dead", "head_ub"; "rot_hi", "rot_lo": the split-bf16 image of the rotated queries, [nq][D] u16, written only when the split-bf16
  * ranking GEMM serves the call) of the workspace that rbq_search_batch_device bound to `hip_stream`; the caller has synchronised
  * that stream. */
 int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name, void* dst, uint64_t bytes);
@@ -346,6 +346,10 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *                        logs the candidates it refines — 12 B each, up to 8192 per query in the calling stream's workspace — and the
  *                        tied query replays the log; rbq_debug_tie_log_stats)
  *   "scan_wave" 0/1/2    which scan kernel serves a call
+ *   "ub_tap" 1           the lazy selection exports its head bounds to the workspace buffer "head_ub", [nq][778] u32 per call (default
+ *                        0: nothing is written): ncand, the number of head lists h, the g_add / g_err bits each head list's bounds
+ *                        used (4 pairs), then per head candidate block (gblock, bits of its bound U, real vectors); ncand = 0 where
+ *                        the lazy path was not entered.  T_ub is the smallest finite U whose blocks of U' <= U hold top_k vectors
  *   "rank_ksplit" 0      never split the K loop of the ranking GEMM (default 1: calls of up to 256 queries split it 2-4 ways over
  *                        grid.z, the parts added atomically to a cleared row; n > 1 forces min(n, 4) parts, the most the
  *                        shortlist's error bound is derived for)

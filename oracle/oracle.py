@@ -68,6 +68,8 @@ def lib():
         L.ref_search.restype = C.c_int
         L.ref_search.argtypes = [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64,
                                  vp, vp, vp, vp]
+        L.ref_list_vectors.restype = C.c_int
+        L.ref_list_vectors.argtypes = [vp, vp, f32p, C.c_uint32, C.c_float, C.c_float, vp, f32p, f32p, f32p, f32p, f32p]
         L.ref_search_lists.restype = C.c_int
         L.ref_search_lists.argtypes = [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]
         L.ref_search_batch.restype = C.c_int
@@ -168,6 +170,33 @@ def select_probes(built, rq, nprobe):
     out = np.empty(built.n_lists, np.uint32)
     n = lib().ref_select_probes(_addr(built.hdr_ptr), _addr(built.lists_ptr), _p(rq), nprobe, _p(out))
     return out[:n].copy()
+
+
+def list_vectors(built, rq, cid, g_add, g_err):
+    """Every vector of list `cid` for the rotated query `rq` with the given g_add / g_error, computed by the code ref_search
+    runs per block (under the active variant): dict of accu (u16), ip, est, lb, dist (the refined distance; est when
+    ex_bits == 0) and exdot (the ex-code dot; 0 when ex_bits == 0), one entry per vector in list order.  Nothing is
+    skipped and no non-finite value is replaced."""
+    rq = np.ascontiguousarray(rq, dtype=np.float32)
+    n = int(built.lists_ptr[cid].n)
+    out = {"accu": np.zeros(n, np.uint16)}
+    for k in ("ip", "est", "lb", "dist", "exdot"):
+        out[k] = np.zeros(n, np.float32)
+    rc = lib().ref_list_vectors(_addr(built.hdr_ptr), _addr(built.lists_ptr), _p(rq), int(cid), float(np.float32(g_add)),
+                                float(np.float32(g_err)), _p(out["accu"]), _p(out["ip"]), _p(out["est"]), _p(out["lb"]),
+                                _p(out["dist"]), _p(out["exdot"]))
+    assert rc == 0, rc
+    return out
+
+
+def probe_geometry(built, rq, cid):
+    """(g_add, g_error) of list `cid` for the rotated query `rq` exactly as ref_search computes them (src/ivf.rs:1850-1857)."""
+    rq = np.ascontiguousarray(rq, dtype=np.float32)
+    cent = np.ascontiguousarray(built.centroid(cid))
+    D = built.padded_dim
+    dist = np.float32(lib().ref_l2_distance_sqr(_p(rq), _p(cent), D))
+    g_add = dist if built.header.metric == 0 else -np.float32(lib().ref_dot(_p(rq), _p(cent), D))
+    return np.float32(g_add), np.sqrt(dist, dtype=np.float32)
 
 
 def posting_scan_batch(built, queries, top_k, list_ids, list_counts, nthreads=0):

@@ -889,6 +889,67 @@ int ref_search_lists(const rbq_header* h, const rbq_list_view* lists, const floa
     return rc;
 }
 
+/* One 32-vector block of a probed list, as search_cluster_v2_batched evaluates it (src/ivf.rs:1901-2058): accumulate, then  */
+/* the estimator epilogue.  Shared by ref_search and ref_list_vectors, so that the per-vector values a test reads are the     */
+/* very ones the search compares against its threshold.                                                                     */
+static void block_values(const uint8_t* rec, const uint8_t* lut8, size_t D, float lut_delta, float lut_sum_vl,
+                         const float* f_add, const float* f_rescale, const float* f_error, float g_add, float g_error,
+                         const ref_query_consts* qc, uint16_t* accu, float* ip, float* est, float* lb) {
+    ref_accumulate_batch(rec, lut8, D, accu);
+    ref_compute_batch_distances(accu, lut_delta, lut_sum_vl, f_add, f_rescale, f_error, g_add, g_error, qc->k1x_sum_q, ip, est, lb);
+}
+
+/* The refined distance of vector gi of list cl (src/ivf.rs:2086-2099); *ex_dot_out (if given) receives the ex-code dot. */
+static float refine_distance(const rbq_header* h, const rbq_list_view* cl, const float* rq, size_t D, size_t ex_bytes, size_t gi,
+                             float ip, float g_add, const ref_query_consts* qc, float* ex_dot_out) {
+    float ex_dot = ref_ex_dot(rq, cl->ex_codes + gi * ex_bytes, D, h->ex_bits);
+    if (ex_dot_out) *ex_dot_out = ex_dot;
+    float t = qc->binary_scale * ip;
+    t = t + ex_dot;
+    t = t + qc->kbx_sum_q;
+    float a = cl->f_add_ex[gi] + g_add;
+    float m = cl->f_rescale_ex[gi] * t;
+    float distance = a + m;
+    if (g_variant & REF_VAR_CONTRACT) { /* `binary_scale * ip + ex_dot` and `f_rescale_ex * t + a` fused */
+        float t2 = fmaf(qc->binary_scale, ip, ex_dot);
+        t2 = t2 + qc->kbx_sum_q;
+        distance = fmaf(cl->f_rescale_ex[gi], t2, a);
+    }
+    return distance;
+}
+
+/* Every vector of ONE list for a rotated query and the given g_add / g_error: accu, ip, est, lb and the refined distance   */
+/* (est when ex_bits == 0), plus the ex-code dot (0 when ex_bits == 0) — the values ref_search computes per block, with no    */
+/* heap, no skipping and no replacement of a non-finite lower bound.  Test infrastructure for the GPU's pruning bounds.     */
+int ref_list_vectors(const rbq_header* h, const rbq_list_view* lists, const float* rq, uint32_t list_id, float g_add, float g_error,
+                     uint16_t* accu, float* ip, float* est, float* lb, float* dist, float* ex_dot) {
+    size_t D = h->padded_dim;
+    if (list_id >= h->n_lists) return RBQ_INVALID_CONFIG;
+    if (D > 2048 || (h->ex_bits != 0 && h->ex_bits != 2 && h->ex_bits != 6)) return RBQ_INVALID_CONFIG;
+    const rbq_list_view* cl = &lists[list_id];
+    uint8_t* lut8 = (uint8_t*)scratch(3, D * 4);
+    ref_query_consts qc;
+    ref_query_precompute(rq, D, h->ex_bits, &qc);
+    float lut_delta, lut_sum_vl;
+    ref_query_lut(rq, D, lut8, &lut_delta, &lut_sum_vl);
+    size_t stride = D * 4 + 384, ex_bytes = D * h->ex_bits / 8, nb = (cl->n + 31) / 32;
+    for (size_t b = 0; b < nb; ++b) {
+        const uint8_t* rec = cl->batch_data + b * stride;
+        const float* f_add = (const float*)(rec + D * 4);
+        uint16_t a[32];
+        float i32[32], e32[32], l32[32];
+        block_values(rec, lut8, D, lut_delta, lut_sum_vl, f_add, f_add + 32, f_add + 64, g_add, g_error, &qc, a, i32, e32, l32);
+        size_t start = b * 32, end = start + 32 < cl->n ? start + 32 : cl->n;
+        for (size_t gi = start; gi < end; ++gi) {
+            size_t i = gi - start;
+            accu[gi] = a[i]; ip[gi] = i32[i]; est[gi] = e32[i]; lb[gi] = l32[i];
+            ex_dot[gi] = 0.0f;
+            dist[gi] = h->ex_bits > 0 ? refine_distance(h, cl, rq, D, ex_bytes, gi, i32[i], g_add, &qc, &ex_dot[gi]) : e32[i];
+        }
+    }
+    return RBQ_OK;
+}
+
 int ref_search(const rbq_header* h, const rbq_list_view* lists, const float* query, uint32_t query_dim,
                uint32_t top_k, uint32_t nprobe_in, const uint32_t* filter_words, uint64_t filter_nbits,
                uint64_t* out_ids, float* out_scores, uint32_t* out_count, rbq_diag* diag) {
@@ -938,9 +999,7 @@ int ref_search(const rbq_header* h, const rbq_list_view* lists, const float* que
             const float* f_error = f_rescale + 32;
             uint16_t accu[32];
             float ip[32], est[32], lb[32];
-            ref_accumulate_batch(rec, lut8, D, accu);
-            ref_compute_batch_distances(accu, lut_delta, lut_sum_vl, f_add, f_rescale, f_error,
-                                        g_add, g_error, qc.k1x_sum_q, ip, est, lb);
+            block_values(rec, lut8, D, lut_delta, lut_sum_vl, f_add, f_rescale, f_error, g_add, g_error, &qc, accu, ip, est, lb);
             size_t start = b * 32, end = start + 32 < cl->n ? start + 32 : cl->n;
             for (size_t gi = start; gi < end; ++gi) {
                 size_t i = gi - start;
@@ -958,18 +1017,7 @@ int ref_search(const rbq_header* h, const rbq_list_view* lists, const float* que
                 float distance = est[i];
                 if (h->ex_bits > 0) {
                     if (diag) diag->extended_evaluations++;
-                    float ex_dot = ref_ex_dot(rq, cl->ex_codes + gi * ex_bytes, D, h->ex_bits);
-                    float t = qc.binary_scale * ip[i];
-                    t = t + ex_dot;
-                    t = t + qc.kbx_sum_q;
-                    float a = cl->f_add_ex[gi] + g_add;
-                    float m = cl->f_rescale_ex[gi] * t;
-                    distance = a + m;
-                    if (g_variant & REF_VAR_CONTRACT) { /* `binary_scale * ip + ex_dot` and `f_rescale_ex * t + a` fused */
-                        float t2 = fmaf(qc.binary_scale, ip[i], ex_dot);
-                        t2 = t2 + qc.kbx_sum_q;
-                        distance = fmaf(cl->f_rescale_ex[gi], t2, a);
-                    }
+                    distance = refine_distance(h, cl, rq, D, ex_bytes, gi, ip[i], g_add, &qc, NULL);
                 }
                 if (!isfinite(distance)) continue;
                 if (diag) diag->estimated++;

@@ -58,6 +58,8 @@ size_t   ref_select_probes(const rbq_header* h, const rbq_list_view* lists, cons
 int      ref_search(const rbq_header* h, const rbq_list_view* lists, const float* query, uint32_t query_dim,
                     uint32_t top_k, uint32_t nprobe, const uint32_t* filter_words, uint64_t filter_nbits,
                     uint64_t* out_ids, float* out_scores, uint32_t* out_count, rbq_diag* diag);
+int      ref_list_vectors(const rbq_header* h, const rbq_list_view* lists, const float* rq, uint32_t list_id, float g_add,
+                          float g_error, uint16_t* accu, float* ip, float* est, float* lb, float* dist, float* ex_dot);
 int      ref_search_lists(const rbq_header* h, const rbq_list_view* lists, const float* query, uint32_t query_dim,
                           uint32_t top_k, uint32_t nprobe, const uint32_t* filter_words, uint64_t filter_nbits,
                           uint64_t* out_ids, float* out_scores, uint32_t* out_count,

@@ -74,6 +74,8 @@ hipError_t launch_rank_gemm(const RankParams& p, int device, hipStream_t s);
 hipError_t launch_lat_front(const PrepParams& p, const RankParams& r, int device, hipStream_t s);
 
 constexpr uint32_t kAuditCap = 1023; // dead lists exported per query under lazy_audit (a shortlist holds fewer)
+// words per query of the head-bound tap (option ub_tap): ncand, h, g_add / g_err bits of the 4 head lists, 256 x (gblock, U bits, nvalid)
+constexpr uint32_t kHeadUbRow = 2 + 8 + 3 * 256;
 struct SelectParams {
     float* scores;
     uint32_t nq, nlist, nprobe;
@@ -117,6 +119,8 @@ struct SelectParams {
     uint32_t* audit_dead;         // null, or (option lazy_audit) [nq][kAuditCap + 1] u32: the number of lists this query's selection dropped as
                                   // a whole, then their ids — exported WITHOUT changing any decision, with or without diagnostics or a
                                   // filter, so that a test can ask the oracle what the reference did with exactly those lists
+    uint32_t* head_ub;            // null, or (option ub_tap) [nq][kHeadUbRow] u32: the head candidates of the lazy selection and their
+                                  // bounds U (block_ub), written WITHOUT changing any decision (layout at kHeadUbRow)
     uint32_t numeric_variant;     // kVarAvx512 / kVarAvx2 / kVarPortable (kernels.hpp): picks the instantiation (host side only)
     int fault_dead_all;           // TEST ONLY (debug option lazy_fault_inject, default 0): T_ub := -inf — every list behind the head is
                                   // declared dead whatever its bounds say: a deliberately WRONG selection, so that the

@@ -1287,12 +1287,21 @@ __global__ RBQ_SEL_BOUNDS void k_select_mfma(const SelectParams P, const SelectG
                 const BlockSummaryEx bx = P.bsumx[gb + b];
                 myU = block_ub(bs, bx, g_add, g_err, qc, D, P.ex_bits, P.slack, V == kVarPortable) + 1e-4f * eps; // (+: |g_add| in the rounding slack is taken at the upper end)
                 myN = (b + 1 == ((nvec + 31u) >> 5)) ? nvec - b * 32u : 32u;
+                if (P.head_ub) { // ub_tap: candidate tid (no decision changes)
+                    uint32_t* hu = P.head_ub + (size_t)q * kHeadUbRow + 10 + 3 * tid;
+                    hu[0] = gb + b; hu[1] = __float_as_uint(myU); hu[2] = myN;
+                }
             }
             float* candU = reinterpret_cast<float*>(part);
             candU[tid] = myU; hist[tid] = myN;
             if (tid < h) { // largest possible head cost
                 float g_add, g_err; uint32_t gb, nvec;
                 head_info(tid, g_add, g_err, gb, nvec);
+                if (P.head_ub) { // ub_tap: the g_add / g_err the head bounds used
+                    uint32_t* hu = P.head_ub + (size_t)q * kHeadUbRow;
+                    hu[2 + 2 * tid] = __float_as_uint(g_add); hu[3 + 2 * tid] = __float_as_uint(g_err);
+                    if (tid == 0) { hu[0] = ncand; hu[1] = h; }
+                }
                 atomicMax(reinterpret_cast<int*>(&s_maxh), total_key(g_add)); // (s_maxh starts at the key of -inf)
             }
             __syncthreads();

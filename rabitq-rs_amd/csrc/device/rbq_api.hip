@@ -112,14 +112,14 @@ struct PinBuf { // page-locked host staging
 
 struct Workspace {
     hipStream_t stream = nullptr;
-    DevBuf queries, rot, lut, consts, scores, probe, wl, nstream, nvec, out_pack, filter, rot_hi, rot_lo, dead_skipped, heap_ws, key_window, audit_dead, tie_log;
+    DevBuf queries, rot, lut, consts, scores, probe, wl, nstream, nvec, out_pack, filter, rot_hi, rot_lo, dead_skipped, heap_ws, key_window, audit_dead, tie_log, head_ub;
     PinBuf h_in, h_out;      // rbq_search_batch: staging of one sub-batch
     hipEvent_t done = nullptr; // results of the sub-batch in flight have reached h_out / the caller's buffers
     uint64_t call_nq = 0;       // queries of the WHOLE host call this launch chain belongs to (0: a device-entry call — its own nq counts)
     bool latency_first = false; // this launch chain belongs to a host call that waits for it (rbq_search_batch below kHostWaveMinQueries)
     void release() {
         for (DevBuf* b : {&queries, &rot, &lut, &consts, &scores, &probe, &wl, &nstream, &nvec, &rot_hi, &rot_lo, &out_pack, &filter, &dead_skipped,
-                          &heap_ws, &key_window, &audit_dead, &tie_log})
+                          &heap_ws, &key_window, &audit_dead, &tie_log, &head_ub})
             b->release();
         h_in.release(); h_out.release();
         if (done) (void)hipEventDestroy(done);
@@ -278,6 +278,7 @@ struct Replica {
     bool lazy_fault_inject = false; // TEST ONLY: makes the lazy selection wrong on purpose (tests/test_gpu_round4.py: the audit must notice)
     SlackMul slack;          // TEST ONLY (options slack_term / slack_milli): multipliers of block_ub()'s rounding-slack terms
     int slack_term = 0;
+    bool ub_tap = false;     // DIAGNOSTIC (option ub_tap): the select kernel exports its head bounds (workspace "head_ub")
     bool lazy_audit = false; // DIAGNOSTIC (option lazy_audit): the select kernel exports the lists it drops as a whole (workspace "audit_dead")
     bool lazy_select = true; // probe selection drops lists that are provably skipped as a whole (rank_mfma.hpp)
     int host_wave_policy = 0;  // option host_wave_policy (see search_host)
@@ -1325,6 +1326,12 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
         HIP_TRY(hipMemsetAsync(w->audit_dead.p, 0, nq * (size_t)(kAuditCap + 1) * 4, stream));
         sp.audit_dead = (uint32_t*)w->audit_dead.p;
     }
+    sp.head_ub = nullptr;
+    if (ix->ub_tap) { // diagnostic: the lazy selection's head candidates and their bounds (rbq_debug_copy_workspace "head_ub")
+        if ((rc = w->head_ub.ensure(nq * (size_t)kHeadUbRow * 4))) return rc;
+        HIP_TRY(hipMemsetAsync(w->head_ub.p, 0, nq * (size_t)kHeadUbRow * 4, stream));
+        sp.head_ub = (uint32_t*)w->head_ub.p;
+    }
     // lazy selection: not with a filter (filtered vectors are never pushed, so no select-time bound of the k-th distance
     // exists) and not when every probed block is to be streamed
     // (round 4: under a filter the exact head evaluation can still bound the k-th distance — it looks at real vectors and counts
@@ -2170,6 +2177,7 @@ int rbq_debug_set_option(rbq_index* h, const char* name, int value) {
         else if (!std::strcmp(name, "host_trace")) ix->host_trace = value != 0;
         else if (!std::strcmp(name, "lazy_fault_inject")) ix->lazy_fault_inject = value != 0;
         else if (!std::strcmp(name, "lazy_audit")) ix->lazy_audit = value != 0;
+        else if (!std::strcmp(name, "ub_tap")) ix->ub_tap = value != 0;
         else if (!std::strcmp(name, "save_chunk")) ix->save_chunk = value > 0 ? (uint64_t)value : 0u;
         else if (!std::strcmp(name, "fetch_chunk")) ix->fetch_chunk = value > 0 ? (uint64_t)value : 0u;
         else if (!std::strcmp(name, "slack_term")) ix->slack_term = value;
@@ -2273,6 +2281,7 @@ int rbq_debug_copy_workspace(rbq_index* h, void* hip_stream, const char* name, v
     else if (!std::strcmp(name, "nvec")) b = &w->nvec;
     else if (!std::strcmp(name, "dead_skipped")) b = &w->dead_skipped;
     else if (!std::strcmp(name, "audit_dead")) b = &w->audit_dead;
+    else if (!std::strcmp(name, "head_ub")) b = &w->head_ub;
     else if (!std::strcmp(name, "rot_hi")) b = &w->rot_hi;
     else if (!std::strcmp(name, "rot_lo")) b = &w->rot_lo;
     if (!b || !b->p || bytes > b->cap) return fail(RBQ_INVALID_CONFIG, "unknown buffer or size");
