@@ -1,0 +1,407 @@
+// api.hpp — internal header of librbq.so's host side: the C ABI of include/rbq.h over the HIP kernels, which the host
+// units (api_index, api_build, api_search, api_save, api_fetch, api_bf) reach through launch.hpp.  Not installed.
+// Host responsibilities: validate like the reference (src/ivf.rs:1754-1769,1484-1702), upload the reference's ClusterData
+// bytes and have the GPU re-lay them into the device layout (one-time, at create/load), own HBM on one or N devices
+// (replicas), and enqueue prep -> rank -> select -> scan for each query batch.  There is no CPU compute path: every failure
+// to reach the GPU surfaces as RBQ_DEVICE.  Everything declared here is hidden: only the units' extern "C" entry points
+// enter the dynamic symbol table.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <deque>
+#include <functional>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "rbq.h"
+#include "launch.hpp"
+#include "../host/rbq_host_logic.hpp"
+
+#pragma GCC visibility push(hidden)
+
+namespace rbq_api {
+
+using namespace rbq;
+using rbq_host::ListSrc;
+using rbq_host::OutPack;
+using rbq_host::align_up;
+
+inline thread_local std::string g_err;
+
+inline int fail(int code, const std::string& detail) {
+    g_err = detail;
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                               \
+    do {                                                                                            \
+        hipError_t _e = (expr);                                                                     \
+        if (_e != hipSuccess)                                                                       \
+            return fail(RBQ_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));             \
+    } while (0)
+
+// No C++ exception may cross the C boundary (the Rust host is panic = "abort", Cargo.toml:59; ctypes would
+// terminate): every entry point runs inside this guard.
+#define RBQ_GUARD_BEGIN try {
+#define RBQ_GUARD_END                                                                               \
+    } catch (const std::bad_alloc&) { return fail(RBQ_IO, "out of host memory"); }                 \
+    catch (const std::exception& e) { return fail(RBQ_IO, std::string("internal error: ") + e.what()); } \
+    catch (...) { return fail(RBQ_IO, "internal error"); }
+
+// Entry points switch to the index's device and put the caller's device back on exit.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+// Busy-waits (with the CPU's pause hint) until pred() holds or `limit` has passed; returns pred()'s last value.
+template <class Pred>
+bool spin_until(Pred pred, std::chrono::microseconds limit = std::chrono::microseconds::max()) {
+    const bool timed = limit != std::chrono::microseconds::max();
+    const auto t0 = timed ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
+    while (!pred()) {
+        if (timed && std::chrono::steady_clock::now() - t0 >= limit) return false;
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+    return true;
+}
+
+// A growing scratch buffer in device memory, or (Pinned) in page-locked host memory, freed with its owner.  The owner
+// destroys it under its DeviceGuard.
+template <bool Pinned>
+struct Buf {
+    void* p = nullptr;
+    size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { release(); }
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return RBQ_OK;
+        release();
+        const size_t want = bytes + bytes / 8 + (Pinned ? 4096 : 256);
+        if constexpr (Pinned) HIP_TRY(hipHostMalloc(&p, want, hipHostMallocPortable)); // portable: mapped for every device, not only the current one
+        else HIP_TRY(hipMalloc(&p, want));
+        cap = want;
+        return RBQ_OK;
+    }
+    void release() {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr; cap = 0;
+    }
+};
+using DevBuf = Buf<false>;
+using PinBuf = Buf<true>; // page-locked host staging
+
+// What one call allocates for itself (device and page-locked memory, events, a private stream), freed on every exit.
+// The stream is drained before anything is freed: work still queued on it may read or write the allocations.
+struct Scratch {
+    hipStream_t stream = nullptr;
+    std::vector<void*> dev, pin;
+    std::vector<hipEvent_t> events;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        for (void* p : pin) (void)hipHostFree(p);
+        for (void* p : dev) (void)hipFree(p);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    hipError_t make_stream() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
+    template <class T> hipError_t alloc(T** p, size_t bytes) {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+        if (e == hipSuccess) { dev.push_back(q); *p = (T*)q; }
+        return e;
+    }
+    template <class T> hipError_t alloc_pinned(T** p, size_t bytes) {
+        void* q = nullptr;
+        const hipError_t e = hipHostMalloc(&q, bytes ? bytes : 16, hipHostMallocDefault);
+        if (e == hipSuccess) { pin.push_back(q); *p = (T*)q; }
+        return e;
+    }
+    hipError_t event(hipEvent_t* ev) {
+        const hipError_t e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+        if (e == hipSuccess) events.push_back(*ev);
+        return e;
+    }
+};
+
+// Persistent host threads that run posted jobs (Job: a callable), started once and joined by shutdown().  A thread that
+// has just finished a job polls ~100 us for the next one before it blocks: callers that post back to back find it hot.
+template <class Job, int kThreads>
+struct WorkerPool {
+    std::thread th[kThreads];
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<Job> jobs;
+    std::atomic<uint32_t> pending{0};
+    bool stop = false;
+    void run() {
+        for (;;) {
+            Job job;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [this] { return stop || !jobs.empty(); });
+                if (jobs.empty()) return; // stop requested and nothing left
+                job = std::move(jobs.front());
+                jobs.pop_front();
+            }
+            job();
+            pending.fetch_sub(1, std::memory_order_release);
+            (void)spin_until([this] { return pending.load(std::memory_order_acquire) != 0; }, std::chrono::microseconds(100));
+        }
+    }
+    // false: a thread could not be created (the ones that did start are shut down again).  A pool is published only once
+    // start() has returned true: jobs posted to a half-started pool could wait forever.
+    bool start() {
+        try {
+            for (auto& t : th) t = std::thread([this] { run(); });
+        } catch (...) {
+            shutdown();
+            return false;
+        }
+        return true;
+    }
+    void post(Job j) {
+        pending.fetch_add(1, std::memory_order_release);
+        { std::lock_guard<std::mutex> lk(mu); jobs.push_back(std::move(j)); }
+        cv.notify_one();
+    }
+    void shutdown() {
+        { std::lock_guard<std::mutex> lk(mu); stop = true; }
+        cv.notify_all();
+        for (auto& t : th) if (t.joinable()) t.join();
+    }
+};
+
+// Persistent staging helpers of a replica (rbq_search_batch with PAGEABLE queries).  The queries of a call must be copied once
+// into page-locked memory before the GPU can read them; one thread copies 3.9 MB (1024 x 960 f32) in ~165 us — more than half of the
+// ~280 us the same call takes from page-locked buffers.  The sub-batches of a call have their own lanes and staging buffers, so
+// their copies are independent: the caller copies sub-batch 0 (and launches it at once), the helpers copy the others meanwhile.
+// Started on the first pageable call, joined when the replica is freed.
+struct StageJob {
+    void* dst = nullptr;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    std::atomic<int>* done = nullptr;
+    void operator()() const {
+        std::memcpy(dst, src, bytes);
+        done->store(1, std::memory_order_release);
+    }
+};
+using StagePool = WorkerPool<StageJob, 3>;
+
+// Persistent host threads per replica beyond the first (rbq_search_batch on N replicas): the shard of replica r is
+// enqueued and awaited by a worker of replica r while the caller's own thread serves replica 0.  Started on the first
+// multi-replica call, joined when the index is destroyed — no thread is created per call (8 replicas: seven thread start-ups
+// of 30-50 us each per call were as long as a 1024-query shard itself).  Two threads per replica, so that the shards of two
+// concurrent callers overlap on it.
+using ReplicaPool = WorkerPool<std::function<void()>, 2>;
+
+struct Workspace {
+    hipStream_t stream = nullptr;
+    DevBuf queries, rot, lut, consts, scores, probe, wl, nstream, nvec, out_pack, filter, rot_hi, rot_lo, dead_skipped, heap_ws, key_window, audit_dead, tie_log, head_ub;
+    PinBuf h_in, h_out;      // rbq_search_batch: staging of one sub-batch
+    hipEvent_t done = nullptr; // results of the sub-batch in flight have reached h_out / the caller's buffers
+    uint64_t call_nq = 0;       // queries of the WHOLE host call this launch chain belongs to (0: a device-entry call — its own nq counts)
+    bool latency_first = false; // this launch chain belongs to a host call that waits for it (rbq_search_batch below kHostWaveMinQueries)
+    Workspace() = default;
+    Workspace(const Workspace&) = delete;
+    ~Workspace() { // (deleted under the owner's DeviceGuard)
+        if (done) (void)hipEventDestroy(done);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+struct StageProf {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; // pairs recorded since rbq_profile_begin
+    double ms = 0;
+    uint64_t launches = 0;
+    std::vector<float> samples; // duration of every timed launch, in launch order
+};
+// Event pairs are created once and recycled: hipEventCreate inside the launch path cost ~15 % of the
+// overlapped throughput and broke down beyond three caller streams.
+struct EventPool {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> free_pairs;
+    bool take(std::pair<hipEvent_t, hipEvent_t>& p) {
+        if (!free_pairs.empty()) { p = free_pairs.back(); free_pairs.pop_back(); return true; }
+        // timing only: without the system-scope fence a default event performs when it completes (that fence sits
+        // between the kernels of a stream and shows up in the overlapped throughput)
+        if (hipEventCreateWithFlags(&p.first, hipEventDisableSystemFence) != hipSuccess) return false;
+        if (hipEventCreateWithFlags(&p.second, hipEventDisableSystemFence) != hipSuccess) { (void)hipEventDestroy(p.first); return false; }
+        return true;
+    }
+    void give(const std::pair<hipEvent_t, hipEvent_t>& p) { free_pairs.push_back(p); }
+    void destroy() {
+        for (auto& e : free_pairs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+        free_pairs.clear();
+    }
+};
+
+struct Arr { // one device array of a replica (size kept for cloning)
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+// What an index's header fixes about its vectors and queries (IVF replicas and the brute-force index alike).
+struct Geometry {
+    uint32_t dim = 0, D = 0, Dc = 0; // dimension, padded dimension, padded dimension rounded up to 64 (code blocks)
+    uint8_t metric = 0, rotator = 0, ex_bits = 0;
+    uint32_t trunc = 0; // the FHT rotator's length: the largest power of two <= dim
+    float fac = 1.0f;   // 1 / sqrt(trunc)
+};
+inline Geometry geometry_of(const rbq_header& h) {
+    Geometry g;
+    g.dim = h.dim; g.D = h.padded_dim; g.Dc = (h.padded_dim + 63u) / 64u * 64u;
+    g.metric = h.metric; g.rotator = h.rotator; g.ex_bits = h.ex_bits;
+    uint32_t lg = 0;
+    for (uint32_t x = h.dim; x >>= 1;) ++lg;
+    g.trunc = 1u << lg;
+    g.fac = 1.0f / std::sqrt((float)g.trunc);
+    return g;
+}
+
+// k_prep's parameters for nq queries at `queries` (device-visible): the index's geometry and rotator, the workspace's
+// rot / lut / consts (both workspace types name them alike).  No split-bf16 copies, one wave per query.
+template <class Ws>
+PrepParams prep_params(const Geometry& g, const Arr& rot_blob, Ws& w, const float* queries, uint64_t nq) {
+    PrepParams p;
+    p.queries = queries; p.nq = (uint32_t)nq; p.dim = g.dim; p.D = g.D; p.Dc = g.Dc; p.rotator = (int)g.rotator;
+    p.rot_blob = (const uint8_t*)rot_blob.p; p.trunc = g.trunc; p.fac = g.fac; p.ex_bits = g.ex_bits;
+    p.rot = (float*)w.rot.p; p.lut = (uint8_t*)w.lut.p; p.consts = (QueryConsts*)w.consts.p;
+    p.rot_hi = nullptr; p.rot_lo = nullptr; p.wg_prep = false;
+    return p;
+}
+
+// Default of the `scan_wave` option; RBQ_SCAN_WAVE=0|1|2 in the environment overrides it (A/B runs of the whole test suite).
+inline int scan_wave_default() {
+    static const int v = [] { const char* e = std::getenv("RBQ_SCAN_WAVE"); return e && *e ? std::atoi(e) : 2; }();
+    return v;
+}
+
+// Per-index settings (rbq_debug_set_option, rbq_index_set_numeric_variant), each with its default.  Every replica holds the
+// same values.
+struct Options {
+    uint32_t numeric_variant = 0; // RBQ_NUMERIC_*: which build of the reference the kernels reproduce (kernels.hpp, kVar*)
+    uint32_t host_lanes = 0, host_subbatch = 0, host_trace = 0; // pipeline shape of rbq_search_batch (0 = default)
+    int rank_ksplit = 1;          // 0 = never split the ranking GEMM's K loop, 1 = by batch size, n > 1 = forced (min(n, 4) parts)
+    bool host_zero_copy = true;   // rbq_search_batch: k_prep reads the queries from page-locked host memory in place (no H2D copy command)
+    bool host_stage_helpers = true; // rbq_search_batch: pageable queries of a call's later sub-batches are staged by helper threads
+    bool no_block_bound = false, f32_rank = false, wg_prep = false, exact_heap = false, force_rank_fallback = false, exact_rank = false;
+    bool head_exact = true;  // lazy selection: a bound of the k-th distance from real estimates of the nearest list's first vectors
+    bool lazy_filter = true; // search_filtered: lazy selection on the exact head evaluation's bound (filter-passing vectors only)
+    bool lazy_fault_inject = false; // TEST ONLY: makes the lazy selection wrong on purpose (tests/test_gpu_round4.py: the audit must notice)
+    SlackMul slack;          // TEST ONLY (options slack_term / slack_milli): multipliers of block_ub()'s rounding-slack terms
+    int slack_term = 0;
+    bool ub_tap = false;     // DIAGNOSTIC: the select kernel exports its head bounds (workspace "head_ub")
+    bool lazy_audit = false; // DIAGNOSTIC: the select kernel exports the lists it drops as a whole (workspace "audit_dead")
+    bool lazy_select = true; // probe selection drops lists that are provably skipped as a whole (rank_mfma.hpp)
+    uint32_t tie_log_cap = 0; // TEST ONLY: entries per query of the tie log (0 = the default sizes)
+    bool tie_log = true;      // k_scan logs the candidates it refines; a tied query replays the log (scan.hpp)
+    int latency_path = 1;     // small calls (see kLatMaxQueries) take the latency-first front (latency.hpp); 0 = never
+    int rank_tile = 0;        // tile of the split-bf16 ranking GEMM (0 = by problem size)
+    uint32_t stage_mask = 0xf; // DIAGNOSTIC: bit s = launch stage s (prep, rank, select, scan); a skipped stage leaves the workspace
+                               // of the stream as the last full call wrote it — results are then those of THAT batch (rate probes only)
+    int scan_wave = scan_wave_default(); // which scan kernel serves a call: 0 = k_scan (one workgroup per query), 1 = k_scanw (one wave per
+                                         // query) wherever it serves the call shape, 2 = by batch size (kScanWaveMinQueries)
+    bool profile_counters = true; // an open profile keeps the traffic counters (0: stage timings only — the counters cost the
+                                  // pipelined run 2-3 %, bench.py collects them in a pass of their own)
+    uint64_t save_chunk = 0;  // TEST ONLY: staging chunk of rbq_index_save_rbq1_stream in bytes (0 = default)
+    uint64_t fetch_chunk = 0; // TEST ONLY: ids per staging chunk of rbq_index_fetch_embeddings (0 = default)
+    // option `name` := value (the options of rbq_debug_set_option that live in Options); RBQ_INVALID_CONFIG for an unknown name
+    int set(const char* name, int value);
+};
+
+// One device-resident copy of the index.
+struct Replica : Geometry {
+    int device = 0;
+    uint64_t n_vectors = 0, n_lists = 0, n_blocks = 0;
+    Arr rot_blob, centroids, blocks, ids, ex, fadd_ex, fres_ex, list_gb0, list_n, prof, bsum, cnorm2, fallbacks, cent_hi, cent_lo, raw,
+        bsumx, lsum; // ex-factor ranges per block, factor ranges per list (lazy probe selection)
+    Arr* arrays[18] = {&rot_blob, &centroids, &blocks, &ids, &ex, &fadd_ex, &fres_ex, &list_gb0, &list_n, &prof, &bsum, &cnorm2,
+                       &fallbacks, &cent_hi, &cent_lo, &raw, &bsumx, &lsum};
+    // reconstruction factors delta / vl of every slot (RBQ1's per-vector arrays that search never reads): kept on the FIRST
+    // replica only, for rbq_index_save_rbq1 (not in `arrays`: clone_replica does not copy them)
+    Arr delta, vl;
+    bool has_recon = false; // false: created by rbq_index_create (no factors given) — such a handle cannot be saved
+    // fetch_embedding's id map (FIRST replica only): every vector's id, ascending (stably sorted: the first (cluster, position)
+    // occurrence first), and its slot — 12 bytes per vector, built by the first fetch under fetch_mu, kept until destroy
+    std::mutex fetch_mu;
+    Arr fmap_ids, fmap_slots;
+    bool fmap_ready = false;
+    float cnorm2_max = 0.0f;
+    uint64_t n_raw = 0;      // raw vectors attached for the optional rerank
+    bool raw_borrowed = false;
+    bool rerank = false;
+    Options opt;
+    std::unique_ptr<StagePool> stagers; // (created on the first pageable call, under `mu`; published only when all its threads run)
+    bool stagers_failed = false;        // thread creation failed once: pageable calls stage inline from then on
+    // host
+    std::vector<uint32_t> h_list_n;
+    std::vector<uint64_t> nblk_desc_prefix; // prefix sums of per-list block counts sorted descending
+    std::mutex mu;
+    std::vector<Workspace*> pool;
+    std::map<hipStream_t, Workspace*> stream_ws; // rbq_search_batch_device: one workspace per caller stream
+    // profiling
+    bool profiling = false;
+    uint32_t prof_mask = 0xf; // stages that are timed while `profiling` (bit s = stage s)
+    uint32_t prof_every = 1;  // time every n-th launch of a stage
+    uint32_t prof_seq[4] = {0, 0, 0, 0};
+    StageProf stage_prof[4]; // prep, rank, select, scan
+    EventPool ev_pool;
+    uint64_t prof_counters[kProfSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
+    Replica() = default;
+    Replica(const Replica&) = delete;
+};
+
+// shared by the units (api_index.hip)
+int alloc_arr(Arr& a, size_t bytes);
+int upload_arr(Arr& a, const void* src, size_t bytes);
+void free_replica(Replica* ix);
+struct ReplicaOwner { // frees a half-built replica on an early return
+    Replica* ix;
+    ~ReplicaOwner() { if (ix) free_replica(ix); }
+    Replica* release() { Replica* r = ix; ix = nullptr; return r; }
+};
+int validate_header(const rbq_header* h, bool brute_force = false);
+int resolve_devices(int n_devices, const int* devices, std::vector<int>& out);
+Replica* new_replica(const rbq_header* hdr, int dev);
+int finish_replica(Replica* ix, const std::vector<uint32_t>& ln);
+int wrap_and_replicate(Replica* first, const std::vector<int>& devs, rbq_index** out);
+
+} // namespace rbq_api
+
+struct rbq_index {
+    std::vector<rbq_api::Replica*> reps; // reps[r] lives on device reps[r]->device; all hold the same index
+    int debug_replica = 0;               // which replica the rbq_debug_copy_* calls read
+    std::mutex worker_mu;
+    std::vector<std::unique_ptr<rbq_api::ReplicaPool>> workers; // workers[r - 1] serves replica r (created on first use)
+};
+
+#pragma GCC visibility pop

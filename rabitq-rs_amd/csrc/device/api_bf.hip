@@ -1,0 +1,266 @@
+// api_bf.hip — brute-force index (rbq_bf_*): BruteForceRabitqIndex, reference src/brute_force.rs.
+// Host side: validation, upload, RBF1 in / out, and per call: queries -> k_prep (rotation + QueryPrecomputed constants, shared with
+// the IVF path) -> for each chunk of vectors k_bf_dist + k_bf_select (bf.hpp) -> results.  Each call takes a workspace and a stream
+// of its own from the handle's pool, so calls on one handle may overlap.
+#include "api.hpp"
+
+using namespace rbq_api;
+
+namespace rbq_api {
+namespace {
+constexpr uint32_t kBfTopKMax = 16384;
+constexpr uint64_t kBfDistBudget = 128ull << 20; // distance workspace of one sub-batch (bytes)
+constexpr uint64_t kBfHeapBudget = 48ull << 20;  // heap workspace (between vector chunks, or for top_k above the LDS heap)
+constexpr uint64_t kBfOutBudget = 48ull << 20;   // result buffers of one sub-batch
+constexpr uint64_t kBfMaxSubBatch = 1024;
+
+struct BfWorkspace {
+    hipStream_t stream = nullptr;
+    DevBuf q, rot, lut, consts, dist, heap_d, heap_s, heap_len, filter, ids, scores, counts, stats;
+    BfWorkspace() = default;
+    BfWorkspace(const BfWorkspace&) = delete;
+    ~BfWorkspace() { if (stream) (void)hipStreamDestroy(stream); } // (deleted under the index's DeviceGuard)
+};
+} // namespace
+} // namespace rbq_api
+
+struct rbq_bf_index : Geometry {
+    int device = 0;
+    rbq_header hdr;                    // rotator_blob -> blob below
+    std::vector<uint8_t> blob;         // host copy of the rotator (RBF1 writer)
+    uint64_t ex_len = 0;               // bytes of ex code per vector as the index holds them (rbq_bf_view::ex_len)
+    Arr rot_blob, bin, ex, f[8];       // f: delta, vl, f_add, f_rescale, f_error, residual_norm, f_add_ex, f_rescale_ex
+    std::mutex mu;
+    std::vector<BfWorkspace*> pool;
+    std::atomic<uint64_t> pushes{0}, tie_pushes{0};
+};
+
+namespace rbq_api {
+namespace {
+void bf_free(rbq_bf_index* ix) {
+    if (!ix) return;
+    DeviceGuard g(ix->device);
+    (void)hipDeviceSynchronize();
+    for (Arr* a : {&ix->rot_blob, &ix->bin, &ix->ex}) if (a->p) (void)hipFree(a->p);
+    for (Arr& a : ix->f) if (a.p) (void)hipFree(a.p);
+    for (BfWorkspace* w : ix->pool) delete w;
+    delete ix;
+}
+
+int bf_create_impl(const rbq_header* hdr, const rbq_bf_view* v, int device, rbq_bf_index** out) {
+    if (!out) return fail(RBQ_INVALID_CONFIG, "null output");
+    *out = nullptr;
+    int rc = validate_header(hdr, /*brute_force=*/true);
+    if (rc) return rc;
+    if (!v) return fail(RBQ_INVALID_CONFIG, "null view");
+    const uint64_t n = v->n, D = hdr->padded_dim, ex = hdr->ex_bits;
+    if (n > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "more than 2^32 vectors");
+    const uint64_t ex_want = D * ex / 8;
+    if (ex ? v->ex_len != ex_want : (v->ex_len != 0 && v->ex_len != D / 8)) return fail(RBQ_INVALID_CONFIG, "ex_len does not match the header");
+    const float* fs[8] = {v->delta, v->vl, v->f_add, v->f_rescale, v->f_error, v->residual_norm, v->f_add_ex, v->f_rescale_ex};
+    if (n) {
+        if (!v->bin_codes || (ex && !v->ex_codes)) return fail(RBQ_INVALID_CONFIG, "null code array");
+        for (const float* p : fs) if (!p) return fail(RBQ_INVALID_CONFIG, "null factor array");
+    }
+    int dev = device;
+    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+    int count = 0;
+    HIP_TRY(hipGetDeviceCount(&count));
+    if (dev >= count) return fail(RBQ_INVALID_CONFIG, "no such device: " + std::to_string(dev));
+    std::unique_ptr<rbq_bf_index> ix(new rbq_bf_index());
+    static_cast<Geometry&>(*ix) = geometry_of(*hdr);
+    ix->device = dev;
+    ix->hdr = *hdr;
+    ix->hdr.n_vectors = n; ix->hdr.n_lists = 0;
+    ix->blob.assign(hdr->rotator_blob, hdr->rotator_blob + hdr->rotator_len);
+    ix->hdr.rotator_blob = ix->blob.data();
+    ix->ex_len = v->ex_len;
+    DeviceGuard g(dev);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    rc = upload_arr(ix->rot_blob, ix->blob.data(), ix->blob.size());
+    if (!rc) rc = upload_arr(ix->bin, v->bin_codes, n * (D / 8));
+    if (!rc) rc = ex ? upload_arr(ix->ex, v->ex_codes, n * ex_want) : alloc_arr(ix->ex, 0);
+    for (int k = 0; k < 8 && !rc; ++k) rc = upload_arr(ix->f[k], fs[k], n * 4);
+    if (rc) { bf_free(ix.release()); return rc; }
+    *out = ix.release();
+    return RBQ_OK;
+}
+
+int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t top_k, const uint32_t* filter_words, uint64_t filter_nbits,
+                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+    const uint64_t n = ix->hdr.n_vectors, K = top_k;
+    const uint32_t dim = ix->hdr.dim, D = ix->hdr.padded_dim;
+    // plan: vector chunks of at most kBfDistBudget / 4 vectors, sub-batches of queries within the workspace budgets
+    const uint64_t nv_chunk = std::min<uint64_t>(n, kBfDistBudget / 4);
+    const uint64_t n_chunks = (n + nv_chunk - 1) / nv_chunk;
+    const bool lds_heap = top_k <= kBfLdsHeapMaxTopK;
+    const bool heap_ws = n_chunks > 1 || !lds_heap;
+    uint64_t sub = std::min<uint64_t>({nq, kBfMaxSubBatch, std::max<uint64_t>(1, kBfDistBudget / (nv_chunk * 4)),
+                                       std::max<uint64_t>(1, kBfOutBudget / (K * 12))});
+    if (heap_ws) sub = std::min<uint64_t>(sub, std::max<uint64_t>(1, kBfHeapBudget / ((K + 1) * 8)));
+    BfWorkspace* w = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        if (!ix->pool.empty()) { w = ix->pool.back(); ix->pool.pop_back(); }
+    }
+    if (!w) w = new BfWorkspace();
+    struct Give { rbq_bf_index* ix; BfWorkspace* w; ~Give() { std::lock_guard<std::mutex> lk(ix->mu); ix->pool.push_back(w); } } give{ix, w};
+    if (!w->stream) HIP_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
+    hipStream_t st = w->stream;
+    int rc;
+    if ((rc = w->q.ensure(sub * dim * 4)) || (rc = w->rot.ensure(sub * D * 4)) || (rc = w->lut.ensure(sub * 4 * ix->Dc)) ||
+        (rc = w->consts.ensure(sub * sizeof(QueryConsts))) || (rc = w->dist.ensure(sub * nv_chunk * 4)) ||
+        (rc = w->heap_len.ensure(sub * 4)) || (rc = w->ids.ensure(sub * K * 8)) || (rc = w->scores.ensure(sub * K * 4)) ||
+        (rc = w->counts.ensure(sub * 4)) || (rc = w->stats.ensure(16)))
+        return rc;
+    if (heap_ws && ((rc = w->heap_d.ensure(sub * (K + 1) * 4)) || (rc = w->heap_s.ensure(sub * (K + 1) * 4)))) return rc;
+    const uint32_t* d_filter = nullptr;
+    if (filter_words) {
+        const uint64_t words = (filter_nbits + 31) / 32;
+        if ((rc = w->filter.ensure(std::max<uint64_t>(words, 1) * 4))) return rc;
+        if (words) HIP_TRY(hipMemcpyAsync(w->filter.p, filter_words, words * 4, hipMemcpyHostToDevice, st));
+        d_filter = (const uint32_t*)w->filter.p;
+    }
+    HIP_TRY(hipMemsetAsync(w->stats.p, 0, 16, st));
+    for (uint64_t q0 = 0; q0 < nq; q0 += sub) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(sub, nq - q0);
+        HIP_TRY(hipMemcpyAsync(w->q.p, queries + q0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(launch_prep(prep_params(*ix, ix->rot_blob, *w, (const float*)w->q.p, m), ix->device, st));
+        for (uint64_t c = 0; c < n_chunks; ++c) {
+            const uint64_t v0 = c * nv_chunk, nv = std::min<uint64_t>(nv_chunk, n - v0);
+            BfDistParams dp;
+            dp.rot = (const float*)w->rot.p; dp.consts = (const QueryConsts*)w->consts.p; dp.nq = m; dp.D = D; dp.ex_bits = ix->hdr.ex_bits;
+            dp.v0 = v0; dp.nv = nv; dp.bin = (const uint8_t*)ix->bin.p; dp.ex = (const uint8_t*)ix->ex.p;
+            dp.f_add = (const float*)ix->f[2].p; dp.f_rescale = (const float*)ix->f[3].p;
+            dp.f_add_ex = (const float*)ix->f[6].p; dp.f_rescale_ex = (const float*)ix->f[7].p;
+            dp.filter = d_filter; dp.filter_nbits = filter_nbits; dp.dist = (float*)w->dist.p;
+            HIP_TRY(launch_bf_dist(dp, st));
+            BfSelectParams sp;
+            sp.dist = (const float*)w->dist.p; sp.nq = m; sp.top_k = top_k; sp.v0 = v0; sp.nv = nv; sp.metric = ix->hdr.metric;
+            sp.first = c == 0; sp.last = c + 1 == n_chunks; sp.lds_heap = lds_heap;
+            sp.heap_d = (float*)w->heap_d.p; sp.heap_s = (uint32_t*)w->heap_s.p; sp.heap_len = (uint32_t*)w->heap_len.p;
+            sp.out_ids = (uint64_t*)w->ids.p; sp.out_scores = (float*)w->scores.p; sp.out_counts = (uint32_t*)w->counts.p;
+            sp.stats = (unsigned long long*)w->stats.p;
+            HIP_TRY(launch_bf_select(sp, st));
+        }
+        HIP_TRY(hipMemcpyAsync(out_ids + q0 * K, w->ids.p, (size_t)m * K * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out_scores + q0 * K, w->scores.p, (size_t)m * K * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out_counts + q0, w->counts.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+    }
+    uint64_t stats[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(stats, w->stats.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ix->pushes += stats[0];
+    ix->tie_pushes += stats[1];
+    return RBQ_OK;
+}
+} // namespace
+} // namespace rbq_api
+
+extern "C" {
+int rbq_bf_create(const rbq_header* hdr, const rbq_bf_view* view, int device, rbq_bf_index** out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    return bf_create_impl(hdr, view, device, out);
+    RBQ_GUARD_END
+}
+
+int rbq_bf_load_rbf1(const void* bytes, size_t len, int device, rbq_bf_index** out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!out) return fail(RBQ_INVALID_CONFIG, "null output");
+    *out = nullptr;
+    rbq_header h;
+    rbq_host::BfSrc b;
+    std::string detail;
+    int rc = rbq_host::rbf1_parse(bytes, len, &h, &b, &detail);
+    if (rc) return fail(rc, detail);
+    rc = validate_header(&h, /*brute_force=*/true); // what this build cannot serve (ex_bits outside {0,2,6}, padded_dim > 2048 ...)
+    if (rc) return rc;
+    if (b.bin_len != h.padded_dim / 8 || b.ex_len != (size_t)h.padded_dim * h.ex_bits / 8) return fail(RBQ_INVALID_CONFIG, "unsupported code layout");
+    std::vector<uint8_t> bin(b.n * b.bin_len), ex(b.n * b.ex_len);
+    std::vector<float> f[8];
+    for (auto& a : f) a.resize(b.n);
+    for (uint64_t v = 0; v < b.n; ++v) {
+        const uint8_t* r = b.rec0 + v * b.stride;
+        std::memcpy(bin.data() + v * b.bin_len, r, b.bin_len);
+        if (b.ex_len) std::memcpy(ex.data() + v * b.ex_len, r + b.bin_len, b.ex_len);
+        for (int k = 0; k < 8; ++k) std::memcpy(&f[k][v], r + b.bin_len + b.ex_len + 4 * k, 4);
+    }
+    rbq_bf_view view;
+    view.n = b.n; view.bin_codes = bin.data(); view.ex_codes = ex.empty() ? nullptr : ex.data(); view.ex_len = b.ex_len;
+    view.delta = f[0].data(); view.vl = f[1].data(); view.f_add = f[2].data(); view.f_rescale = f[3].data();
+    view.f_error = f[4].data(); view.residual_norm = f[5].data(); view.f_add_ex = f[6].data(); view.f_rescale_ex = f[7].data();
+    return bf_create_impl(&h, &view, device, out);
+    RBQ_GUARD_END
+}
+
+int rbq_bf_save_rbf1(const rbq_bf_index* ch, uint8_t** bytes, uint64_t* len) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!ch) return fail(RBQ_INVALID_CONFIG, "null index");
+    if (!bytes || !len) return fail(RBQ_INVALID_CONFIG, "null output");
+    rbq_bf_index* ix = const_cast<rbq_bf_index*>(ch);
+    const uint64_t n = ix->hdr.n_vectors, D = ix->hdr.padded_dim, exb = D * ix->hdr.ex_bits / 8;
+    std::vector<uint8_t> bin(n * (D / 8)), ex(n * exb);
+    std::vector<float> f[8];
+    {
+        DeviceGuard g(ix->device);
+        if (n) HIP_TRY(hipMemcpy(bin.data(), ix->bin.p, bin.size(), hipMemcpyDeviceToHost));
+        if (!ex.empty()) HIP_TRY(hipMemcpy(ex.data(), ix->ex.p, ex.size(), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 8; ++k) {
+            f[k].resize(n);
+            if (n) HIP_TRY(hipMemcpy(f[k].data(), ix->f[k].p, n * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    const float* fp[8];
+    for (int k = 0; k < 8; ++k) fp[k] = f[k].data();
+    // ex_bits == 0: the ex_len zero bytes per vector of a trained index (null source = zeros)
+    const std::vector<uint8_t> o = rbq_host::rbf1_write(ix->hdr, n, bin.data(), exb ? ex.data() : nullptr, ix->ex_len, fp);
+    uint8_t* p = (uint8_t*)std::malloc(o.size());
+    if (!p) return fail(RBQ_IO, "out of host memory");
+    std::memcpy(p, o.data(), o.size());
+    *bytes = p;
+    *len = o.size();
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+
+void rbq_bf_free_bytes(uint8_t* p) { std::free(p); }
+void rbq_bf_destroy(rbq_bf_index* idx) { bf_free(idx); }
+uint64_t rbq_bf_len(const rbq_bf_index* idx) { return idx ? idx->hdr.n_vectors : 0; }
+uint32_t rbq_bf_dim(const rbq_bf_index* idx) { return idx ? idx->hdr.dim : 0; }
+uint32_t rbq_bf_padded_dim(const rbq_bf_index* idx) { return idx ? idx->hdr.padded_dim : 0; }
+
+void rbq_bf_debug_heap_stats(const rbq_bf_index* idx, uint64_t* out2) {
+    if (!idx || !out2) return;
+    out2[0] = idx->pushes.load();
+    out2[1] = idx->tie_pushes.load();
+}
+
+int rbq_bf_search_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                        const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!ch) return fail(RBQ_INVALID_CONFIG, "null index");
+    rbq_bf_index* ix = const_cast<rbq_bf_index*>(ch);
+    if (ix->hdr.n_vectors == 0) return fail(RBQ_EMPTY_INDEX, "index is empty");
+    if (query_dim != ix->hdr.dim) {
+        char b[96];
+        std::snprintf(b, sizeof b, "expected %u, got %u", ix->hdr.dim, query_dim);
+        return fail(RBQ_DIMENSION_MISMATCH, b);
+    }
+    if (nq == 0) return RBQ_OK;
+    if (top_k == 0) {
+        if (out_counts) std::memset(out_counts, 0, nq * 4);
+        return RBQ_OK;
+    }
+    if (top_k > kBfTopKMax) return fail(RBQ_INVALID_CONFIG, "top_k > 16384 is not supported by the brute-force index");
+    if (nq >= (1ull << 31)) return fail(RBQ_INVALID_CONFIG, "nq >= 2^31");
+    if (!queries || !out_ids || !out_scores || !out_counts) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    return bf_search_impl(ix, queries, nq, top_k, filter_words, filter_nbits, out_ids, out_scores, out_counts);
+    RBQ_GUARD_END
+}
+} // extern "C"

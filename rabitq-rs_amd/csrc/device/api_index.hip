@@ -1,0 +1,775 @@
+// api_index.hip — index handles: create / load / clone / destroy, header validation, rerank vectors, host allocation,
+// error strings and ABI version, numeric variant, options, profiling, debug counters and copies.
+#include "api.hpp"
+
+using namespace rbq_api;
+
+// The HIP runtime multiplexes a process's streams over its hardware queues; the queue count is a process-wide setting of the host
+// (GPU_MAX_HW_QUEUES, read when the runtime initialises) and the library leaves it alone.  rbq_process_defaults() used to raise it;
+// more queues than a card's slots is a state that has hung shared machines, so it now changes nothing and is kept for the ABI.
+extern "C" int rbq_process_defaults(void) {
+    return RBQ_OK;
+}
+
+namespace rbq_api {
+int alloc_arr(Arr& a, size_t bytes) {
+    HIP_TRY(hipMalloc(&a.p, bytes ? bytes : 16));
+    a.bytes = bytes;
+    return RBQ_OK;
+}
+int upload_arr(Arr& a, const void* src, size_t bytes) {
+    int rc = alloc_arr(a, bytes);
+    if (rc) return rc;
+    if (bytes) HIP_TRY(hipMemcpy(a.p, src, bytes, hipMemcpyHostToDevice));
+    return RBQ_OK;
+}
+
+void free_replica(Replica* ix) {
+    if (!ix) return;
+    if (ix->stagers) ix->stagers->shutdown();
+    DeviceGuard g(ix->device);
+    (void)hipDeviceSynchronize();
+    for (Arr* a : ix->arrays)
+        if (a->p && !(a == &ix->raw && ix->raw_borrowed)) (void)hipFree(a->p);
+    for (Arr* a : {&ix->delta, &ix->vl, &ix->fmap_ids, &ix->fmap_slots})
+        if (a->p) (void)hipFree(a->p);
+    for (Workspace* w : ix->pool) delete w;
+    for (auto& kv : ix->stream_ws) delete kv.second;
+    for (auto& sp : ix->stage_prof)
+        for (auto& e : sp.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    ix->ev_pool.destroy();
+    delete ix;
+}
+
+// The header checks of every index type.  brute_force: the brute-force index (no lists; the rotator is FHT-Kac or Matrix).
+int validate_header(const rbq_header* h, bool brute_force) {
+    if (!h) return fail(RBQ_INVALID_CONFIG, "null header");
+    if (h->dim == 0) return fail(RBQ_INVALID_CONFIG, "dimension must be positive");
+    if (h->padded_dim < h->dim) return fail(RBQ_INVALID_CONFIG, "padded_dim must be >= dim");
+    if (h->metric > 1) return fail(RBQ_INVALID_CONFIG, "unknown metric tag");
+    if (h->rotator > (brute_force ? RBQ_ROTATOR_FHT_KAC : RBQ_ROTATOR_NONE)) return fail(RBQ_INVALID_CONFIG, "unknown rotator type tag");
+    if (h->ex_bits != 0 && h->ex_bits != 2 && h->ex_bits != 6)
+        return fail(RBQ_INVALID_CONFIG, "Unsupported ex_bits: only 0 (1-bit total), 2 (3-bit total), and 6 (7-bit total) are supported");
+    if (h->padded_dim % 16 != 0) return fail(RBQ_INVALID_CONFIG, "Dimension must be multiple of 16 for SIMD");
+    if (h->padded_dim > 2048)
+        return fail(RBQ_INVALID_CONFIG, "padded_dim > 2048 (high-accuracy i32 LUT mode) is not supported");
+    if (h->rotator_len != 0 && !h->rotator_blob) return fail(RBQ_INVALID_CONFIG, "null rotator blob");
+    if (h->rotator == RBQ_ROTATOR_NONE) {
+        if (h->padded_dim != h->dim) return fail(RBQ_INVALID_CONFIG, "rotator NONE requires padded_dim == dim");
+        if (h->rotator_len != 0) return fail(RBQ_INVALID_CONFIG, "rotator NONE takes no rotator blob");
+    } else if (h->rotator == RBQ_ROTATOR_FHT_KAC) {
+        if (h->padded_dim % 64 != 0) return fail(RBQ_INVALID_CONFIG, "FHT rotator requires dimension to be multiple of 64");
+        if (h->rotator_len != (uint64_t)4 * h->padded_dim / 8) return fail(RBQ_INVALID_PERSISTENCE, "FHT rotator flip bits length mismatch");
+    } else {
+        if (h->rotator_len != (uint64_t)h->padded_dim * h->padded_dim * 4) return fail(RBQ_INVALID_PERSISTENCE, "rotator matrix length mismatch");
+    }
+    if (brute_force) return RBQ_OK;
+    if (h->n_lists == 0) return fail(RBQ_INVALID_CONFIG, "nlist must be positive");
+    if (h->n_lists > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "too many lists");
+    return RBQ_OK;
+}
+
+// device list: n_devices ordinals, or the current device
+int resolve_devices(int n_devices, const int* devices, std::vector<int>& out) {
+    if (n_devices < 1 || n_devices > 16) return fail(RBQ_INVALID_CONFIG, "n_devices must be in 1..16");
+    int count = 0;
+    HIP_TRY(hipGetDeviceCount(&count));
+    out.clear();
+    for (int i = 0; i < n_devices; ++i) {
+        int d = 0;
+        if (devices) d = devices[i];
+        else if (n_devices == 1) HIP_TRY(hipGetDevice(&d));
+        else d = i;
+        if (d < 0 || d >= count) return fail(RBQ_INVALID_CONFIG, "no such device: " + std::to_string(d));
+        out.push_back(d);
+    }
+    return RBQ_OK;
+}
+
+Replica* new_replica(const rbq_header* hdr, int dev) {
+    Replica* ix = new Replica();
+    static_cast<Geometry&>(*ix) = geometry_of(*hdr);
+    ix->device = dev;
+    ix->n_lists = hdr->n_lists;
+    return ix;
+}
+
+// what every construction path shares once list sizes and rotated centroids are on the device: block geometry on
+// the host side, centroid-derived arrays, counters, environment switches
+int finish_replica(Replica* ix, const std::vector<uint32_t>& ln) {
+    const uint32_t nlist = (uint32_t)ix->n_lists, D = ix->D;
+    ix->h_list_n = ln;
+    {
+        std::vector<uint64_t> nblk(nlist);
+        for (uint32_t c = 0; c < nlist; ++c) nblk[c] = (ln[c] + 31u) / 32u;
+        std::sort(nblk.begin(), nblk.end(), std::greater<uint64_t>());
+        ix->nblk_desc_prefix.assign((size_t)nlist + 1, 0);
+        for (uint32_t c = 0; c < nlist; ++c) ix->nblk_desc_prefix[c + 1] = ix->nblk_desc_prefix[c] + nblk[c];
+    }
+    int rc;
+    if ((rc = alloc_arr(ix->cnorm2, (size_t)nlist * 4))) return rc;
+    if ((rc = alloc_arr(ix->cent_hi, (size_t)nlist * D * 2))) return rc;
+    if ((rc = alloc_arr(ix->cent_lo, (size_t)nlist * D * 2))) return rc;
+    HIP_TRY(launch_centroid_arrays((const float*)ix->centroids.p, nlist, D, (float*)ix->cnorm2.p, (uint16_t*)ix->cent_hi.p,
+                                   (uint16_t*)ix->cent_lo.p, 0));
+    std::vector<float> cn(nlist);
+    HIP_TRY(hipMemcpy(cn.data(), ix->cnorm2.p, (size_t)nlist * 4, hipMemcpyDeviceToHost));
+    double mx = 0;
+    for (float v : cn) if (std::isfinite(v)) mx = std::max(mx, (double)v);
+    ix->cnorm2_max = (float)(mx * 1.000001); // rounded up
+    if ((rc = alloc_arr(ix->lsum, (size_t)nlist * sizeof(BlockSummary)))) return rc;
+    if ((rc = alloc_arr(ix->bsumx, ix->n_blocks * sizeof(BlockSummaryEx)))) return rc;
+    HIP_TRY(launch_list_summaries((const uint8_t*)ix->blocks.p, (const uint8_t*)ix->ex.p, (const float*)ix->fadd_ex.p,
+                                  (const float*)ix->fres_ex.p, (const float*)ix->centroids.p, (const BlockSummary*)ix->bsum.p,
+                                  (const uint32_t*)ix->list_gb0.p, (const uint32_t*)ix->list_n.p, nlist, D, ix->Dc, ix->ex_bits,
+                                  (BlockSummaryEx*)ix->bsumx.p, (BlockSummary*)ix->lsum.p, 0));
+    if ((rc = alloc_arr(ix->fallbacks, 32))) return rc;   // [0] rank fallbacks, [1] heap restarts, [2] exact-head guard trips, [3] exact-head evaluations,
+                                                          // [4..7] tie log: replays, entries replayed, real heap operations, overflowed logs
+    HIP_TRY(hipMemset(ix->fallbacks.p, 0, 32));
+    if ((rc = alloc_arr(ix->prof, (size_t)kProfStripes * kProfSlots * 8))) return rc;
+    HIP_TRY(hipMemset(ix->prof.p, 0, (size_t)kProfStripes * kProfSlots * 8));
+    const char* e = std::getenv("RBQ_EXACT_RANK");
+    ix->opt.exact_rank = e && e[0] == '1';
+    const char* f = std::getenv("RBQ_FORCE_RANK_FALLBACK");
+    ix->opt.force_rank_fallback = f && f[0] == '1';
+    const char* lz = std::getenv("RBQ_LAZY_SELECT");
+    ix->opt.lazy_select = !(lz && lz[0] == '0');
+    return RBQ_OK;
+}
+
+int Options::set(const char* name, int v) {
+    const auto is = [name](const char* n) { return !std::strcmp(name, n); };
+    if (is("block_bound")) no_block_bound = v == 0;
+    else if (is("exact_rank")) exact_rank = v != 0;
+    else if (is("exact_heap")) exact_heap = v != 0;
+    else if (is("lazy_select")) lazy_select = v != 0;
+    else if (is("rank_tile")) rank_tile = v;
+    else if (is("latency_path")) latency_path = v;
+    else if (is("tie_log")) tie_log = v != 0;
+    else if (is("tie_log_cap")) tie_log_cap = v > 0 ? (uint32_t)v : 0u;
+    else if (is("stage_mask")) stage_mask = (uint32_t)v & 0xfu;
+    else if (is("scan_wave")) scan_wave = v < 0 ? scan_wave_default() : (v > 2 ? 2 : v);
+    else if (is("profile_counters")) profile_counters = v != 0;
+    else if (is("f32_rank")) f32_rank = v != 0;
+    else if (is("wg_prep")) wg_prep = v != 0;
+    else if (is("force_rank_fallback")) force_rank_fallback = v != 0;
+    else if (is("host_lanes")) host_lanes = v > 0 ? (uint32_t)v : 0u;
+    else if (is("host_subbatch")) host_subbatch = v > 0 ? (uint32_t)v : 0u;
+    else if (is("host_trace")) host_trace = v != 0;
+    else if (is("lazy_fault_inject")) lazy_fault_inject = v != 0;
+    else if (is("lazy_audit")) lazy_audit = v != 0;
+    else if (is("ub_tap")) ub_tap = v != 0;
+    else if (is("save_chunk")) save_chunk = v > 0 ? (uint64_t)v : 0u;
+    else if (is("fetch_chunk")) fetch_chunk = v > 0 ? (uint64_t)v : 0u;
+    else if (is("slack_term")) slack_term = v;
+    else if (is("slack_milli")) { // TEST ONLY: term `slack_term` of block_ub()'s slack times v / 1000 (1000 = the product)
+        float* f[6] = {&slack.ge, &slack.eip, &slack.est, &slack.lb, &slack.et, &slack.dist};
+        if (slack_term < 0 || slack_term > 5) return fail(RBQ_INVALID_CONFIG, "slack_term is 0..5");
+        *f[slack_term] = (float)v * 1e-3f;
+    }
+    else if (is("head_exact")) head_exact = v != 0;
+    else if (is("lazy_filter")) lazy_filter = v != 0;
+    else if (is("host_zero_copy")) host_zero_copy = v != 0;
+    else if (is("rank_ksplit")) rank_ksplit = v < 0 ? 0 : v;
+    else if (is("host_stage_helpers")) host_stage_helpers = v != 0;
+    else return fail(RBQ_INVALID_CONFIG, std::string("unknown option ") + name);
+    return RBQ_OK;
+}
+} // namespace rbq_api
+
+namespace rbq_api {
+namespace {
+void free_index(rbq_index* h) {
+    if (!h) return;
+    for (auto& w : h->workers) w->shutdown();
+    for (Replica* r : h->reps) free_replica(r);
+    delete h;
+}
+
+// Device-to-device copy between two replicas' devices: peer copy over xGMI when the runtime can (peer access is enabled
+// when the devices report it; hipMemcpyPeer itself stages through the host otherwise); if that fails, an explicit bounce
+// through a page-locked host buffer, 64 MB at a time.
+// RBQ_FORCE_NO_PEER=1 in the environment (read when a handle replicates): every replica copy takes the bounce path, also
+// between two replicas on ONE device — the only way the path can run on a one-GPU box (tests/test_gpu_round4.py).
+std::atomic<uint64_t> g_bounce_copies{0}; // replica arrays copied through the page-locked bounce buffer (rbq_debug_bounce_copies)
+hipError_t copy_cross_device(void* dst, int ddev, const void* src, int sdev, size_t bytes) {
+    if (!bytes) return hipSuccess;
+    const char* fnp = std::getenv("RBQ_FORCE_NO_PEER");
+    const bool no_peer = fnp && fnp[0] == '1';
+    hipError_t e = hipSuccess;
+    if (!no_peer) {
+        if (ddev == sdev) return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice);
+        int can = 0;
+        if (hipDeviceCanAccessPeer(&can, ddev, sdev) == hipSuccess && can) {
+            const hipError_t pe = hipDeviceEnablePeerAccess(sdev, 0); // (current device = ddev)
+            if (pe != hipSuccess) (void)hipGetLastError();            // already enabled, or refused: the copy below decides
+        } else {
+            (void)hipGetLastError();
+        }
+        e = hipMemcpyPeer(dst, ddev, src, sdev, bytes);
+        if (e == hipSuccess) return e;
+        (void)hipGetLastError();
+    }
+    g_bounce_copies.fetch_add(1, std::memory_order_relaxed);
+    const size_t CH = (size_t)64 << 20;
+    void* bounce = nullptr;
+    e = hipHostMalloc(&bounce, std::min(bytes, CH), hipHostMallocPortable);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < bytes && e == hipSuccess; off += CH) {
+        const size_t n = std::min(CH, bytes - off);
+        e = hipSetDevice(sdev);
+        if (e == hipSuccess) e = hipMemcpy(bounce, (const uint8_t*)src + off, n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipSetDevice(ddev);
+        if (e == hipSuccess) e = hipMemcpy((uint8_t*)dst + off, bounce, n, hipMemcpyHostToDevice);
+    }
+    (void)hipSetDevice(ddev);
+    (void)hipHostFree(bounce);
+    return e;
+}
+
+// A second replica of `src` on device `dev` (may be the same device: exercised by tests on one GPU).
+int clone_replica(const Replica* src, int dev, Replica** out) {
+    DeviceGuard g(dev);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    Replica* ix = new Replica();
+    static_cast<Geometry&>(*ix) = *src;
+    ix->device = dev;
+    ix->n_vectors = src->n_vectors; ix->n_lists = src->n_lists; ix->n_blocks = src->n_blocks;
+    ix->cnorm2_max = src->cnorm2_max; ix->h_list_n = src->h_list_n; ix->nblk_desc_prefix = src->nblk_desc_prefix;
+    ix->opt = src->opt;
+    for (size_t i = 0; i < sizeof(ix->arrays) / sizeof(ix->arrays[0]); ++i) {
+        const Arr* s = src->arrays[i];
+        Arr* d = ix->arrays[i];
+        if (!s->p || s == &src->raw) continue;
+        hipError_t e = hipMalloc(&d->p, s->bytes ? s->bytes : 16);
+        if (e == hipSuccess && s->bytes) e = copy_cross_device(d->p, dev, s->p, src->device, s->bytes);
+        if (e != hipSuccess) { free_replica(ix); return fail(RBQ_DEVICE, std::string("replicating the index: ") + hipGetErrorString(e)); }
+        d->bytes = s->bytes;
+    }
+    hipError_t e = hipMemset(ix->fallbacks.p, 0, 32);
+    if (e == hipSuccess) e = hipMemset(ix->prof.p, 0, (size_t)kProfStripes * kProfSlots * 8);
+    if (e != hipSuccess) { free_replica(ix); return fail(RBQ_DEVICE, hipGetErrorString(e)); }
+    *out = ix;
+    return RBQ_OK;
+}
+} // namespace
+
+int wrap_and_replicate(Replica* first, const std::vector<int>& devs, rbq_index** out) {
+    rbq_index* h = new rbq_index();
+    h->reps.push_back(first);
+    for (size_t i = 1; i < devs.size(); ++i) {
+        Replica* r = nullptr;
+        int rc = clone_replica(first, devs[i], &r);
+        if (rc) { free_index(h); return rc; }
+        h->reps.push_back(r);
+    }
+    *out = h;
+    return RBQ_OK;
+}
+
+namespace {
+// ---- create / load: reference layout in, device layout out --------------------------------------------------------
+int create_from_sources(const rbq_header* hdr, const std::vector<ListSrc>& lists, int dev, Replica** out) {
+    DeviceGuard g(dev);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    ReplicaOwner own{new_replica(hdr, dev)};
+    Replica* ix = own.ix;
+    Scratch cl; // (released before `own`)
+    const uint32_t D = ix->D, Dc = ix->Dc, nlist = (uint32_t)ix->n_lists, exbits = ix->ex_bits;
+    const size_t ref_stride = (size_t)D * 4 + 384, dev_stride = (size_t)Dc * 4 + 384, exb = (size_t)D * exbits / 8;
+    const size_t exd = ex_bytes_dev(D, exbits);
+    std::vector<uint32_t> gb0(nlist), ln(nlist);
+    uint64_t nblocks = 0, nvec = 0;
+    // the reconstruction factors are kept when every non-empty list brings them
+    bool recon = true;
+    for (uint32_t c = 0; c < nlist; ++c)
+        if (lists[c].n && (!lists[c].delta || !lists[c].vl)) recon = false;
+    for (uint32_t c = 0; c < nlist; ++c) {
+        const ListSrc& L = lists[c];
+        if (L.n > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "list too large");
+        gb0[c] = (uint32_t)nblocks; ln[c] = (uint32_t)L.n;
+        nblocks += (L.n + 31) / 32; nvec += L.n;
+        if (nblocks * 32 > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "index too large for 32-bit vector slots");
+    }
+    ix->n_blocks = nblocks; ix->n_vectors = nvec;
+    const uint64_t nslots = nblocks * 32;
+    int rc;
+    if ((rc = upload_arr(ix->rot_blob, hdr->rotator_blob, hdr->rotator_len))) return rc;
+    if ((rc = upload_arr(ix->list_gb0, gb0.data(), (size_t)nlist * 4))) return rc;
+    if ((rc = upload_arr(ix->list_n, ln.data(), (size_t)nlist * 4))) return rc;
+    {
+        std::vector<float> cent((size_t)nlist * D);
+        for (uint32_t c = 0; c < nlist; ++c) std::memcpy(&cent[(size_t)c * D], lists[c].centroid, (size_t)D * 4);
+        if ((rc = upload_arr(ix->centroids, cent.data(), cent.size() * 4))) return rc;
+    }
+    if ((rc = alloc_arr(ix->blocks, nblocks * dev_stride))) return rc;
+    if ((rc = alloc_arr(ix->ids, nslots * 8))) return rc;
+    if ((rc = alloc_arr(ix->ex, exd ? nslots * exd + 256 : 0))) return rc;
+    if ((rc = alloc_arr(ix->fadd_ex, exbits ? nslots * 4 : 0))) return rc;
+    if ((rc = alloc_arr(ix->fres_ex, exbits ? nslots * 4 : 0))) return rc;
+    if ((rc = alloc_arr(ix->bsum, nblocks * sizeof(BlockSummary)))) return rc;
+    if (recon) {
+        if ((rc = alloc_arr(ix->delta, nslots * 4))) return rc;
+        if ((rc = alloc_arr(ix->vl, nslots * 4))) return rc;
+    }
+
+    // Chunks of whole blocks (a long list may span several), staged through two pinned buffers: the host fills
+    // one while the GPU converts the other.  Staging layout (16-byte aligned sections):
+    //   recs [nb][ref_stride] | ex [nv][exb] | ids [nv] u64 | fadd [nv] f32 | fres [nv] f32 | delta [nv] f32 | vl [nv] f32 |
+    //   dense0 [nb] u64 | nvb [nb] u32
+    const size_t per_block = ref_stride + 32 * (exb + 24) + 12 + 64;
+    uint64_t chunk_blocks = std::max<uint64_t>(1, ((size_t)64 << 20) / per_block);
+    chunk_blocks = std::min<uint64_t>(chunk_blocks, std::max<uint64_t>(nblocks, 1));
+    const size_t cap = align_up(chunk_blocks * ref_stride, 16) + align_up(chunk_blocks * 32 * exb, 16) + chunk_blocks * 32 * 24 +
+                       chunk_blocks * 12 + 256;
+    uint8_t* pin[2] = {nullptr, nullptr};
+    uint8_t* dst[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    HIP_TRY(cl.make_stream());
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(cl.alloc_pinned(&pin[i], cap));
+        HIP_TRY(cl.alloc(&dst[i], cap));
+        HIP_TRY(cl.event(&ev[i]));
+    }
+    uint32_t c = 0;      // list cursor
+    uint64_t lb = 0;     // next block inside list c
+    uint64_t b0 = 0;     // first global block of the chunk
+    int turn = 0;
+    while (b0 < nblocks) {
+        const uint64_t nb = std::min<uint64_t>(chunk_blocks, nblocks - b0);
+        const int i = turn & 1;
+        if (turn >= 2) HIP_TRY(hipEventSynchronize(ev[i]));
+        uint8_t* base = pin[i];
+        const size_t o_recs = 0, o_ex = align_up(nb * ref_stride, 16);
+        // the number of vectors of the chunk is known only after the walk: lay the dense arrays out for the maximum
+        const size_t o_ids = o_ex + align_up(nb * 32 * exb, 16), o_fadd = o_ids + nb * 32 * 8, o_fres = o_fadd + nb * 32 * 4,
+                     o_dl = o_fres + nb * 32 * 4, o_vl = o_dl + nb * 32 * 4, o_d0 = o_vl + nb * 32 * 4, o_nv = o_d0 + nb * 8,
+                     total = o_nv + nb * 4;
+        uint64_t* dense0 = reinterpret_cast<uint64_t*>(base + o_d0);
+        uint32_t* nvb = reinterpret_cast<uint32_t*>(base + o_nv);
+        uint64_t filled = 0, dense = 0;
+        while (filled < nb) {
+            while (c < nlist && lb >= ((uint64_t)ln[c] + 31) / 32) { ++c; lb = 0; }
+            const ListSrc& L = lists[c];
+            const uint64_t lnb = ((uint64_t)ln[c] + 31) / 32, take = std::min<uint64_t>(lnb - lb, nb - filled);
+            const uint64_t v0 = lb * 32, v1 = std::min<uint64_t>(L.n, (lb + take) * 32), nv = v1 - v0;
+            std::memcpy(base + o_recs + filled * ref_stride, L.batch_data + lb * ref_stride, take * ref_stride);
+            if (nv) std::memcpy(base + o_ids + dense * 8, L.ids + v0 * 8, nv * 8);
+            if (exbits && nv) {
+                if (L.ex_stride == exb) std::memcpy(base + o_ex + dense * exb, L.ex + v0 * exb, nv * exb);
+                else for (uint64_t v = 0; v < nv; ++v) std::memcpy(base + o_ex + (dense + v) * exb, L.ex + (v0 + v) * L.ex_stride, exb);
+                std::memcpy(base + o_fadd + dense * 4, L.fadd + v0 * 4, nv * 4);
+                std::memcpy(base + o_fres + dense * 4, L.fres + v0 * 4, nv * 4);
+            }
+            if (recon && nv) {
+                std::memcpy(base + o_dl + dense * 4, L.delta + v0 * 4, nv * 4);
+                std::memcpy(base + o_vl + dense * 4, L.vl + v0 * 4, nv * 4);
+            }
+            for (uint64_t b = 0; b < take; ++b) {
+                dense0[filled + b] = dense + b * 32;
+                nvb[filled + b] = (uint32_t)std::min<uint64_t>(32, L.n - (lb + b) * 32);
+            }
+            filled += take; dense += nv; lb += take;
+        }
+        uint8_t* d = dst[i];
+        HIP_TRY(hipMemcpyAsync(d, base, total, hipMemcpyHostToDevice, cl.stream));
+        const uint64_t* d_d0 = reinterpret_cast<const uint64_t*>(d + o_d0);
+        const uint32_t* d_nv = reinterpret_cast<const uint32_t*>(d + o_nv);
+        uint8_t* oblocks = (uint8_t*)ix->blocks.p + b0 * dev_stride;
+        HIP_TRY(launch_relayout_blocks(d + o_recs, (uint32_t)nb, D, Dc, oblocks, cl.stream));
+        HIP_TRY(launch_block_summary(oblocks, d_nv, (uint32_t)nb, Dc, (BlockSummary*)ix->bsum.p + b0, cl.stream));
+        HIP_TRY(launch_spread_u64(reinterpret_cast<const uint64_t*>(d + o_ids), d_d0, d_nv, (uint32_t)nb, ~0ull,
+                                  (uint64_t*)ix->ids.p + b0 * 32, cl.stream));
+        if (exbits) {
+            HIP_TRY(launch_relayout_ex(d + o_ex, d_d0, d_nv, (uint32_t)nb, D, exbits, (uint8_t*)ix->ex.p + b0 * 32 * exd, cl.stream));
+            HIP_TRY(launch_spread_f32(reinterpret_cast<const float*>(d + o_fadd), d_d0, d_nv, (uint32_t)nb, 0.0f,
+                                      (float*)ix->fadd_ex.p + b0 * 32, cl.stream));
+            HIP_TRY(launch_spread_f32(reinterpret_cast<const float*>(d + o_fres), d_d0, d_nv, (uint32_t)nb, 0.0f,
+                                      (float*)ix->fres_ex.p + b0 * 32, cl.stream));
+        }
+        if (recon) {
+            HIP_TRY(launch_spread_f32(reinterpret_cast<const float*>(d + o_dl), d_d0, d_nv, (uint32_t)nb, 0.0f,
+                                      (float*)ix->delta.p + b0 * 32, cl.stream));
+            HIP_TRY(launch_spread_f32(reinterpret_cast<const float*>(d + o_vl), d_d0, d_nv, (uint32_t)nb, 0.0f,
+                                      (float*)ix->vl.p + b0 * 32, cl.stream));
+        }
+        HIP_TRY(hipEventRecord(ev[i], cl.stream));
+        b0 += nb;
+        ++turn;
+    }
+    if (exd) HIP_TRY(hipMemsetAsync((uint8_t*)ix->ex.p + nslots * exd, 0, 256, cl.stream)); // read-ahead pad of the refine loads
+    HIP_TRY(hipStreamSynchronize(cl.stream));
+    if ((rc = finish_replica(ix, ln))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    ix->has_recon = recon;
+    *out = own.release();
+    return RBQ_OK;
+}
+
+// delta / vl: null (rbq_index_create: no reconstruction factors) or n_lists pointers to n f32 each
+int create_impl(const rbq_header* hdr, const rbq_list_view* lists, const float* const* delta, const float* const* vl, int n_devices,
+                const int* devices, rbq_index** out) {
+    if (!out) return fail(RBQ_INVALID_CONFIG, "null out pointer");
+    *out = nullptr;
+    int rc = validate_header(hdr);
+    if (rc) return rc;
+    if (!lists) return fail(RBQ_INVALID_CONFIG, "null lists");
+    if (!delta != !vl) return fail(RBQ_INVALID_CONFIG, "delta and vl are given together");
+    std::vector<int> devs;
+    if ((rc = resolve_devices(n_devices, devices, devs))) return rc;
+    const size_t ref_stride = (size_t)hdr->padded_dim * 4 + 384, exb = (size_t)hdr->padded_dim * hdr->ex_bits / 8;
+    std::vector<ListSrc> src(hdr->n_lists);
+    for (uint64_t c = 0; c < hdr->n_lists; ++c) {
+        const rbq_list_view& L = lists[c];
+        if (L.n > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "list too large");
+        const uint64_t nb = (L.n + 31) / 32;
+        if (L.batch_len != nb * ref_stride)
+            return fail(RBQ_INVALID_PERSISTENCE, "batch_data length mismatch - possible corruption or version incompatibility");
+        if (L.n && (!L.centroid || !L.ids || !L.batch_data || (hdr->ex_bits && (!L.ex_codes || !L.f_add_ex || !L.f_rescale_ex))))
+            return fail(RBQ_INVALID_CONFIG, "null list array");
+        if (!L.centroid) return fail(RBQ_INVALID_CONFIG, "null centroid");
+        ListSrc& S = src[c];
+        S.centroid = (const uint8_t*)L.centroid; S.n = L.n; S.ids = (const uint8_t*)L.ids; S.batch_data = L.batch_data;
+        S.ex = L.ex_codes; S.ex_stride = exb; S.fadd = (const uint8_t*)L.f_add_ex; S.fres = (const uint8_t*)L.f_rescale_ex;
+        if (delta) {
+            if (L.n && (!delta[c] || !vl[c])) return fail(RBQ_INVALID_CONFIG, "null delta / vl array");
+            S.delta = (const uint8_t*)delta[c]; S.vl = (const uint8_t*)vl[c];
+        }
+    }
+    Replica* first = nullptr;
+    if ((rc = create_from_sources(hdr, src, devs[0], &first))) return rc;
+    return wrap_and_replicate(first, devs, out);
+}
+
+int load_rbq1_impl(const void* bytes, size_t len, int n_devices, const int* devices, rbq_index** out) {
+    if (!out) return fail(RBQ_INVALID_CONFIG, "null out pointer");
+    *out = nullptr;
+    rbq_header h;
+    std::vector<ListSrc> lists; // byte ranges of the stream: nothing is copied on the host but the chunk staging
+    std::string detail;
+    int rc = rbq_host::rbq1_parse(bytes, len, &h, &lists, &detail); // load_from_reader's validation, CRC included
+    if (rc) return fail(rc, detail);
+    rc = validate_header(&h); // what this build cannot serve (ex_bits outside {0,2,6}, padded_dim > 2048 ...)
+    if (rc) return rc;
+    std::vector<int> devs;
+    if ((rc = resolve_devices(n_devices, devices, devs))) return rc;
+    Replica* first = nullptr;
+    if ((rc = create_from_sources(&h, lists, devs[0], &first))) return rc;
+    return wrap_and_replicate(first, devs, out);
+}
+} // namespace
+} // namespace rbq_api
+
+extern "C" {
+// (minor 1: rbq_debug_tie_log_stats; options latency_path, tie_log.  minor 2: rbq_index_set_numeric_variant / rbq_index_numeric_variant)
+uint32_t rbq_abi_version(void) { return (2u << 16) | 2u; }
+
+const char* rbq_strerror(int code) {
+    switch (code) {
+        case RBQ_OK: return "ok";
+        case RBQ_DIMENSION_MISMATCH: return "dimension mismatch";
+        case RBQ_INVALID_CONFIG: return "invalid configuration";
+        case RBQ_EMPTY_INDEX: return "index is empty";
+        case RBQ_IO: return "io error";
+        case RBQ_INVALID_PERSISTENCE: return "invalid persisted index";
+        case RBQ_DEVICE: return "device error";
+        default: return "unknown error";
+    }
+}
+
+int rbq_last_error_detail(char* buf, size_t n) {
+    if (buf && n) {
+        size_t c = std::min(n - 1, g_err.size());
+        std::memcpy(buf, g_err.data(), c);
+        buf[c] = 0;
+    }
+    return (int)g_err.size();
+}
+
+int rbq_index_create(const rbq_header* hdr, const rbq_list_view* lists, int n_devices, const int* devices, rbq_index** out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    return create_impl(hdr, lists, nullptr, nullptr, n_devices, devices, out);
+    RBQ_GUARD_END
+}
+
+void rbq_index_destroy(rbq_index* h) { try { free_index(h); } catch (...) {} }
+
+uint64_t rbq_index_len(const rbq_index* h) { return h && !h->reps.empty() ? h->reps[0]->n_vectors : 0; }
+uint64_t rbq_index_cluster_count(const rbq_index* h) { return h && !h->reps.empty() ? h->reps[0]->n_lists : 0; }
+uint32_t rbq_index_dim(const rbq_index* h) { return h && !h->reps.empty() ? h->reps[0]->dim : 0; }
+uint32_t rbq_index_padded_dim(const rbq_index* h) { return h && !h->reps.empty() ? h->reps[0]->D : 0; }
+uint32_t rbq_index_device_count(const rbq_index* h) { return h ? (uint32_t)h->reps.size() : 0; }
+
+
+int rbq_index_load_rbq1(const void* bytes, size_t len, int n_devices, const int* devices, rbq_index** out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    return load_rbq1_impl(bytes, len, n_devices, devices, out);
+    RBQ_GUARD_END
+}
+
+
+int rbq_index_create_with_recon(const rbq_header* hdr, const rbq_list_view* lists, const float* const* delta, const float* const* vl,
+                                int n_devices, const int* devices, rbq_index** out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!delta || !vl) return fail(RBQ_INVALID_CONFIG, "null delta / vl table");
+    return create_impl(hdr, lists, delta, vl, n_devices, devices, out);
+    RBQ_GUARD_END
+}
+
+
+// ---- optional full-precision rerank (NOT in the reference: its index stores no raw vectors, src/ivf.rs:207-242) ----
+int rbq_index_set_rerank_vectors(rbq_index* h, const float* vectors, uint64_t n) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!h || h->reps.empty()) return fail(RBQ_INVALID_CONFIG, "null index");
+    // all replicas or none: the new copies are made first; only when every one of them exists are the old ones released
+    // and the new ones attached (a failure half-way leaves every replica exactly as it was)
+    const size_t R = h->reps.size();
+    std::vector<Arr> fresh(R);
+    std::vector<char> borrowed(R, 0);
+    const bool attach = vectors && n;
+    if (attach) {
+        hipPointerAttribute_t a;
+        const bool on_dev = hipPointerGetAttributes(&a, vectors) == hipSuccess && a.type == hipMemoryTypeDevice;
+        if (!on_dev) (void)hipGetLastError();
+        int rc = RBQ_OK;
+        for (size_t r = 0; r < R && rc == RBQ_OK; ++r) {
+            Replica* ix = h->reps[r];
+            DeviceGuard g(ix->device);
+            if (!g.ok) { rc = fail(RBQ_DEVICE, "hipSetDevice failed"); break; }
+            const size_t bytes = (size_t)n * ix->dim * 4;
+            if (on_dev && a.device == ix->device) { // borrowed: stays owned by the caller, must outlive the index
+                fresh[r].p = const_cast<float*>(vectors); fresh[r].bytes = bytes; borrowed[r] = 1;
+                continue;
+            }
+            rc = alloc_arr(fresh[r], bytes);
+            if (rc == RBQ_OK) {
+                const hipError_t e = on_dev ? copy_cross_device(fresh[r].p, ix->device, vectors, a.device, bytes)
+                                            : hipMemcpy(fresh[r].p, vectors, bytes, hipMemcpyHostToDevice);
+                if (e != hipSuccess) rc = fail(RBQ_DEVICE, std::string("attaching the rerank vectors: ") + hipGetErrorString(e));
+            }
+        }
+        if (rc != RBQ_OK) {
+            const std::string keep = g_err;
+            for (size_t r = 0; r < R; ++r)
+                if (fresh[r].p && !borrowed[r]) { DeviceGuard g(h->reps[r]->device); (void)hipFree(fresh[r].p); }
+            return fail(rc, keep);
+        }
+    }
+    for (size_t r = 0; r < R; ++r) {
+        Replica* ix = h->reps[r];
+        DeviceGuard g(ix->device);
+        if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+        HIP_TRY(hipDeviceSynchronize());
+        if (ix->raw.p && !ix->raw_borrowed) (void)hipFree(ix->raw.p);
+        ix->raw = Arr(); ix->n_raw = 0; ix->rerank = false; ix->raw_borrowed = false;
+        if (!attach) continue; // detach
+        ix->raw = fresh[r]; ix->raw_borrowed = borrowed[r] != 0;
+        ix->n_raw = n; ix->rerank = true;
+    }
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+
+// ---- pinned host memory for callers that want zero-copy DMA of queries and results ---------------------
+void* rbq_host_alloc(size_t bytes) {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return p;
+}
+void rbq_host_free(void* p) { if (p) (void)hipHostFree(p); }
+
+// ---- profiling taps ---------------------------------------------------------------------------------
+void rbq_profile_begin(rbq_index* h) {
+    if (!h) return;
+    for (Replica* ix : h->reps) {
+        DeviceGuard g(ix->device);
+        std::lock_guard<std::mutex> lk(ix->mu);
+        for (auto& sp : ix->stage_prof) {
+            for (auto& e : sp.ev) ix->ev_pool.give(e);
+            sp.ev.clear(); sp.ms = 0; sp.launches = 0; sp.samples.clear();
+        }
+        for (auto& c : ix->prof_counters) c = 0;
+        (void)hipMemset(ix->prof.p, 0, (size_t)kProfStripes * kProfSlots * 8);
+        ix->profiling = true;
+    }
+}
+void rbq_profile_end(rbq_index* h) {
+    if (!h) return;
+    for (Replica* ix : h->reps) {
+        DeviceGuard g(ix->device);
+        (void)hipDeviceSynchronize();
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->profiling = false;
+        std::vector<unsigned long long> c((size_t)kProfStripes * kProfSlots, 0ull);
+        (void)hipMemcpy(c.data(), ix->prof.p, c.size() * 8, hipMemcpyDeviceToHost);
+        for (int i = 0; i < kProfSlots; ++i) {
+            ix->prof_counters[i] = 0;
+            for (uint32_t st = 0; st < kProfStripes; ++st) ix->prof_counters[i] += c[(size_t)st * kProfSlots + i];
+        }
+        for (auto& sp : ix->stage_prof) {
+            for (auto& e : sp.ev) {
+                float ms = 0;
+                if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) { sp.ms += ms; sp.launches++; sp.samples.push_back(ms); }
+                ix->ev_pool.give(e);
+            }
+            sp.ev.clear();
+        }
+    }
+}
+double rbq_profile_stage_ms(const rbq_index* h, const char* stage, uint64_t* launches) {
+    if (!h || h->reps.empty() || !stage) return -1;
+    int s = !std::strcmp(stage, "prep") ? 0 : !std::strcmp(stage, "rank") ? 1 : !std::strcmp(stage, "select") ? 2 : !std::strcmp(stage, "scan") ? 3 : -1;
+    if (s < 0) return -1;
+    double ms = 0; uint64_t n = 0;
+    for (const Replica* ix : h->reps) { ms += ix->stage_prof[s].ms; n += ix->stage_prof[s].launches; }
+    if (launches) *launches = n;
+    return n ? ms / (double)n : 0.0;
+}
+uint64_t rbq_profile_stage_samples(const rbq_index* h, const char* stage, float* out, uint64_t cap) {
+    if (!h || h->reps.empty() || !stage) return 0;
+    int s = !std::strcmp(stage, "prep") ? 0 : !std::strcmp(stage, "rank") ? 1 : !std::strcmp(stage, "select") ? 2 : !std::strcmp(stage, "scan") ? 3 : -1;
+    if (s < 0) return 0;
+    uint64_t n = 0;
+    for (const Replica* ix : h->reps)
+        for (float v : ix->stage_prof[s].samples) { if (out && n < cap) out[n] = v; ++n; }
+    return n;
+}
+uint64_t rbq_profile_scan_bytes(const rbq_index* h) {
+    if (!h || h->reps.empty()) return 0;
+    uint64_t v = 0;
+    for (const Replica* ix : h->reps) v += ix->prof_counters[kProfVectorsProbed];
+    return v * (uint64_t)(h->reps[0]->D / 8 + 12); // sum_q sum_{c in probe(q)} n_c * (D/8 + 12)
+}
+int rbq_profile_counters(const rbq_index* h, uint64_t* out, uint32_t n) {
+    if (!h || h->reps.empty() || !out) return RBQ_INVALID_CONFIG;
+    for (uint32_t i = 0; i < n; ++i) {
+        out[i] = 0;
+        if (i < (uint32_t)kProfSlots) for (const Replica* ix : h->reps) out[i] += ix->prof_counters[i];
+    }
+    return RBQ_OK;
+}
+void rbq_profile_select_stages(rbq_index* h, uint32_t mask) { if (h) for (Replica* ix : h->reps) ix->prof_mask = mask & 0xfu; }
+void rbq_profile_set_sampling(rbq_index* h, uint32_t every) { if (h) for (Replica* ix : h->reps) ix->prof_every = every ? every : 1u; }
+
+int rbq_index_set_numeric_variant(rbq_index* h, int variant) {
+    g_err.clear();
+    if (!h || h->reps.empty()) return fail(RBQ_INVALID_CONFIG, "null index");
+    if (variant != RBQ_NUMERIC_NATIVE_AVX512 && variant != RBQ_NUMERIC_NATIVE_AVX2 && variant != RBQ_NUMERIC_PORTABLE)
+        return fail(RBQ_INVALID_CONFIG, "numeric variant " + std::to_string(variant) +
+                                            " is not one of 0 (native_avx512), 1 (native_avx2), 2 (portable)");
+    static_assert(RBQ_NUMERIC_NATIVE_AVX512 == kVarAvx512 && RBQ_NUMERIC_NATIVE_AVX2 == kVarAvx2 && RBQ_NUMERIC_PORTABLE == kVarPortable,
+                  "the ABI values are the kernels' variant numbers");
+    for (Replica* ix : h->reps) ix->opt.numeric_variant = (uint32_t)variant;
+    return RBQ_OK;
+}
+int rbq_index_numeric_variant(const rbq_index* h) {
+    if (!h || h->reps.empty()) return -1;
+    return (int)h->reps[0]->opt.numeric_variant;
+}
+
+int rbq_debug_set_option(rbq_index* h, const char* name, int value) {
+    if (!h || h->reps.empty() || !name) return RBQ_INVALID_CONFIG;
+    if (!std::strcmp(name, "numeric_variant")) return rbq_index_set_numeric_variant(h, value);
+    if (!std::strcmp(name, "debug_replica")) {
+        if (value < 0 || (size_t)value >= h->reps.size()) return fail(RBQ_INVALID_CONFIG, "no such replica");
+        h->debug_replica = value;
+        return RBQ_OK;
+    }
+    for (Replica* ix : h->reps) {
+        int rc;
+        if (!std::strcmp(name, "rerank")) {
+            if (value && !ix->raw.p) return fail(RBQ_INVALID_CONFIG, "no raw vectors attached (rbq_index_set_rerank_vectors)");
+            ix->rerank = value != 0;
+        } else if ((rc = ix->opt.set(name, value))) {
+            return rc;
+        }
+    }
+    return RBQ_OK;
+}
+static uint64_t read_counter(const rbq_index* h, int slot) {
+    if (!h) return 0;
+    uint64_t tot = 0;
+    for (const Replica* ix : h->reps) {
+        unsigned int v = 0;
+        DeviceGuard g(ix->device);
+        (void)hipDeviceSynchronize();
+        (void)hipMemcpy(&v, (const unsigned int*)ix->fallbacks.p + slot, 4, hipMemcpyDeviceToHost);
+        tot += v;
+    }
+    return tot;
+}
+uint64_t rbq_debug_rank_fallbacks(const rbq_index* h) { return read_counter(h, 0); }
+void rbq_debug_tie_log_stats(const rbq_index* h, uint64_t* out4) { if (out4) for (int i = 0; i < 4; ++i) out4[i] = read_counter(h, 4 + i); }
+uint64_t rbq_debug_head_exact_guard_trips(const rbq_index* h) { return read_counter(h, 2); }
+uint64_t rbq_debug_head_exact_evaluations(const rbq_index* h) { return read_counter(h, 3); }
+
+
+uint64_t rbq_debug_bounce_copies(void) { return g_bounce_copies.load(std::memory_order_relaxed); }
+uint64_t rbq_debug_heap_restarts(const rbq_index* h) { return read_counter(h, 1); }
+
+
+/* Diagnostic: copy an intermediate buffer of the workspace bound to `hip_stream` (after the caller synchronised). */
+int rbq_debug_copy_workspace(rbq_index* h, void* hip_stream, const char* name, void* dst, uint64_t bytes) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!h || h->reps.empty() || !name || !dst) return RBQ_INVALID_CONFIG;
+    Replica* ix = h->reps[h->debug_replica];
+    Workspace* w = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        auto it = ix->stream_ws.find((hipStream_t)hip_stream);
+        if (it != ix->stream_ws.end()) w = it->second;
+    }
+    if (!w) return fail(RBQ_INVALID_CONFIG, "no workspace for this stream");
+    static const std::pair<const char*, DevBuf Workspace::*> kBufs[] = {
+        {"rot", &Workspace::rot}, {"lut", &Workspace::lut}, {"consts", &Workspace::consts}, {"scores", &Workspace::scores},
+        {"probe", &Workspace::probe}, {"nstream", &Workspace::nstream}, {"wl", &Workspace::wl}, {"nvec", &Workspace::nvec},
+        {"dead_skipped", &Workspace::dead_skipped}, {"audit_dead", &Workspace::audit_dead}, {"head_ub", &Workspace::head_ub},
+        {"rot_hi", &Workspace::rot_hi}, {"rot_lo", &Workspace::rot_lo}};
+    DevBuf* b = nullptr;
+    for (const auto& kb : kBufs) if (!std::strcmp(name, kb.first)) b = &(w->*kb.second);
+    if (!b || !b->p || bytes > b->cap) return fail(RBQ_INVALID_CONFIG, "unknown buffer or size");
+    DeviceGuard g(ix->device);
+    HIP_TRY(hipMemcpy(dst, b->p, bytes, hipMemcpyDeviceToHost));
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+
+/* Diagnostic: copy one of the index's device arrays to the host. */
+int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t bytes) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!h || h->reps.empty() || !name || !dst) return RBQ_INVALID_CONFIG;
+    Replica* ix = h->reps[h->debug_replica];
+    const size_t stride = (size_t)ix->Dc * 4 + 384, exd = ex_bytes_dev(ix->D, ix->ex_bits), slots = ix->n_blocks * 32;
+    const void* p = nullptr;
+    size_t have = 0;
+    if (!std::strcmp(name, "blocks")) { p = ix->blocks.p; have = ix->n_blocks * stride; }
+    else if (!std::strcmp(name, "ids")) { p = ix->ids.p; have = slots * 8; }
+    else if (!std::strcmp(name, "ex")) { p = ix->ex.p; have = slots * exd; }
+    else if (!std::strcmp(name, "fadd_ex")) { p = ix->fadd_ex.p; have = ix->ex_bits ? slots * 4 : 0; }
+    else if (!std::strcmp(name, "fres_ex")) { p = ix->fres_ex.p; have = ix->ex_bits ? slots * 4 : 0; }
+    else if (!std::strcmp(name, "bsum")) { p = ix->bsum.p; have = ix->n_blocks * sizeof(BlockSummary); }
+    else if (!std::strcmp(name, "lsum")) { p = ix->lsum.p; have = ix->n_lists * sizeof(BlockSummary); }
+    else if (!std::strcmp(name, "bsumx")) { p = ix->bsumx.p; have = ix->n_blocks * sizeof(BlockSummaryEx); }
+    else if (!std::strcmp(name, "centroids")) { p = ix->centroids.p; have = ix->n_lists * ix->D * 4; }
+    else if (!std::strcmp(name, "list_gb0")) { p = ix->list_gb0.p; have = ix->n_lists * 4; }
+    else if (!std::strcmp(name, "list_n")) { p = ix->list_n.p; have = ix->n_lists * 4; }
+    else if (!std::strcmp(name, "cent_hi")) { p = ix->cent_hi.p; have = ix->n_lists * ix->D * 2; }
+    else if (!std::strcmp(name, "cent_lo")) { p = ix->cent_lo.p; have = ix->n_lists * ix->D * 2; }
+    else if (!std::strcmp(name, "cnorm2")) { p = ix->cnorm2.p; have = ix->n_lists * 4; }
+    else if (!std::strcmp(name, "delta") || !std::strcmp(name, "vl")) { // (first replica only)
+        ix = h->reps[0];
+        p = name[0] == 'd' ? ix->delta.p : ix->vl.p; have = ix->has_recon ? ix->n_blocks * 32 * 4 : 0;
+    }
+    if (!p || bytes != have) return fail(RBQ_INVALID_CONFIG, "unknown array or size (have " + std::to_string(have) + " bytes)");
+    DeviceGuard g(ix->device);
+    HIP_TRY(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+} // extern "C"

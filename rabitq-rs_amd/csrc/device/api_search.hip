@@ -1,0 +1,758 @@
+// api_search.hip — search: the device entry, the host entry (rbq_search_batch, one replica or N), the MSTG posting-list
+// scan.  The hot path (search_host -> search_device -> scan_stage) stays in this one unit.
+#include "api.hpp"
+
+using namespace rbq_api;
+
+namespace rbq_api {
+namespace {
+// scan_wave = 2: batches of at least this many queries go to k_scanw (a query costs one resident wave instead of four: the
+// pipelined rate), smaller ones to k_scan (four waves shorten ONE query's chain: the latency of a small call)
+constexpr uint64_t kScanWaveMinQueries = 128;
+// ... and rbq_search_batch (host buffers; the caller waits for the call) from this many queries per call
+constexpr uint64_t kHostWaveMinQueries = 4096;
+// Latency-first front (latency.hpp): one launch rotates the query, builds its LUT and scores EVERY list exactly, spread over
+// n_lists / 32 workgroups per query.  It re-reads the centroid table once per query, so it serves calls of a few queries only
+// (every query's pass over the table must stay a few microseconds: n_lists x D x 4 bytes x nq within kLatMaxBytes).
+constexpr uint64_t kLatMaxQueries = 4; // (measured, GIST-1M shape: 1 / 2 / 4 queries per call -12 / -10 / -12 us against prep + GEMM; 8: no gain)
+constexpr uint64_t kLatMaxBytes = 96ull << 20;
+constexpr uint64_t kSplitKMaxCallQueries = 256; // calls up to here split the ranking GEMM's K loop over grid.z
+constexpr uint64_t kPrepWgMaxQueries = 512; // up to here the preparation runs one WORKGROUP per query (latency.hpp without the scorers)
+// rbq_search_batch reads page-locked queries in place from this many queries per call (up to 4 queries take the latency-first
+// front: a hundred workgroups per query would each read them over PCIe)
+constexpr uint64_t kZeroCopyMinQueries = 5;
+
+
+// The WHOLE range [p, p + bytes) is page-locked host memory of one allocation / registration: the kernels write (and the
+// DMA engines read) every byte of it, so a registration that covers only the first pages must not pass.
+bool is_pinned_host_range(const void* p, size_t bytes) {
+    if (!p) return false;
+    hipPointerAttribute_t a, b;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (a.type != hipMemoryTypeHost) return false;
+    if (bytes <= 1) return true;
+    const uint8_t* last = (const uint8_t*)p + bytes - 1;
+    if (hipPointerGetAttributes(&b, last) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (b.type != hipMemoryTypeHost) return false;
+    // same mapping: the device-side addresses of the two ends are as far apart as the host-side ones
+    if (a.devicePointer && b.devicePointer && (const uint8_t*)b.devicePointer - (const uint8_t*)a.devicePointer != (ptrdiff_t)(bytes - 1)) return false;
+    if (a.hostPointer && b.hostPointer && (const uint8_t*)b.hostPointer - (const uint8_t*)a.hostPointer != (ptrdiff_t)(bytes - 1)) return false;
+    return true;
+}
+
+
+// ---- search ---------------------------------------------------------------------------------------------------------
+Workspace* take_ws(Replica* ix) {
+    {
+        std::lock_guard<std::mutex> g(ix->mu);
+        if (!ix->pool.empty()) { Workspace* w = ix->pool.back(); ix->pool.pop_back(); return w; }
+    }
+    Workspace* w = new Workspace();
+    if (hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess) { delete w; return nullptr; }
+    if (hipEventCreateWithFlags(&w->done, hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(w->stream); delete w; return nullptr; }
+    return w;
+}
+void give_ws(Replica* ix, Workspace* w) {
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->pool.push_back(w);
+}
+
+struct ProfScope {
+    Replica* ix; int stage; hipStream_t s; std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    bool on = false, ext = false;
+    // ext: the launch itself carries the event pair (hipExtLaunchKernelGGL: start/stop come from the dispatch
+    // packet, no separate marker packets in the queue); otherwise the pair is recorded around the scope
+    ProfScope(Replica* ix_, int st, hipStream_t s_, bool ext_ = false) : ix(ix_), stage(st), s(s_), ext(ext_) {
+        if (ix->profiling && !stage_probes() && ((ix->prof_mask >> st) & 1u)) { // (a probed call launches nothing: no event pair for it)
+            {
+                std::lock_guard<std::mutex> g(ix->mu);
+                if (ix->prof_seq[st]++ % ix->prof_every == 0) on = ix->ev_pool.take(ev);
+            }
+            if (on && !ext) (void)hipEventRecord(ev.first, s);
+        }
+    }
+    hipEvent_t start() const { return on && ext ? ev.first : nullptr; }
+    hipEvent_t stop() const { return on && ext ? ev.second : nullptr; }
+    ~ProfScope() {
+        if (on) {
+            if (!ext) (void)hipEventRecord(ev.second, s);
+            std::lock_guard<std::mutex> g(ix->mu);
+            ix->stage_prof[stage].ev.push_back(ev);
+        }
+    }
+};
+
+// k_scan launch shared by the IVF search and the MSTG posting-list scan
+int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, uint32_t top_k, uint64_t wl_stride,
+               const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
+               rbq_diag* d_diag, bool mstg, const uint32_t* d_dead_skipped, hipStream_t stream) {
+    ProfScope ps(ix, 3, stream, /*ext=*/true);
+    ScanParams P;
+    P.blocks = (const uint8_t*)ix->blocks.p; P.ids = (const uint64_t*)ix->ids.p; P.ex_codes = (const uint8_t*)ix->ex.p;
+    P.f_add_ex = (const float*)ix->fadd_ex.p; P.f_rescale_ex = (const float*)ix->fres_ex.p;
+    P.lut = (const uint8_t*)w->lut.p; P.rot = (const float*)w->rot.p; P.consts = (const QueryConsts*)w->consts.p;
+    P.probe = (const ProbeInfo*)w->probe.p; P.wl = (const StreamItem*)w->wl.p; P.nstream = (const uint32_t*)w->nstream.p;
+    P.filter = d_filter; P.filter_nbits = filter_nbits; P.wl_stride = wl_stride;
+    P.out_ids = d_ids; P.out_scores = d_scores; P.out_counts = d_counts; P.diag = (unsigned long long*)d_diag;
+    P.D = ix->D; P.Dc = ix->Dc; P.nprobe = probe_stride; P.top_k = top_k; P.metric = ix->metric;
+    P.ex_bits = mstg ? 0u : ix->ex_bits; // MSTG search never evaluates the ex codes (src/mstg/index.rs:216-330)
+    P.no_block_bound = ix->opt.no_block_bound ? 1u : 0u;
+    P.exact_heap = ix->opt.exact_heap ? 1u : 0u;
+    P.heap_restarts = (unsigned int*)ix->fallbacks.p + 1;
+    P.tie_stats = (unsigned int*)ix->fallbacks.p + 4;
+    P.mstg = mstg ? 1u : 0u;
+    P.prof = (ix->profiling && ix->opt.profile_counters) ? (unsigned long long*)ix->prof.p : nullptr;
+    P.dead_skipped = d_dead_skipped;
+    P.numeric_variant = ix->opt.numeric_variant;
+    // scan_wave = 2 (default): the wave-per-query kernel serves the pruned regime of batches large enough to fill the chip with
+    // waves; with the block bound off (every probed block streamed: the roofline configuration) the four-wave kernel streams
+    // at twice its rate and serves the call.  Results are identical either way.
+    // A host call (rbq_search_batch) that waits for ONE chain of kernels is served by the kernel with the shorter chain (k_scan's
+    // four waves finish a 1024-query launch in 0.10 ms, k_scanw's single wave in 0.14 ms) until the call is large enough for the rate
+    // to matter more than the last chain's latency.
+    P.wave_kernel = (ix->opt.scan_wave == 1 || (ix->opt.scan_wave == 2 && nq >= kScanWaveMinQueries && !ix->opt.no_block_bound && !w->latency_first)) ? 1u : 0u;
+    // tie log (k_scan, no diagnostics, top-k in registers): a tied query replays its logged candidates instead of its lists
+    P.tie_log = nullptr; P.tie_log_cap = 0;
+    if (ix->opt.tie_log && !P.wave_kernel && !d_diag && !mstg && top_k >= 1 && top_k <= kTopKRegMax && !ix->opt.exact_heap && !stage_probes()) {
+        // entries per query: ~80 candidates are refined per query at top_k = 10 and ~400 at top_k = 100 on the bench data; a query that
+        // logs more than the capacity is scanned again, as before (option tie_log_cap: tests of that path)
+        const uint32_t cap = ix->opt.tie_log_cap ? ix->opt.tie_log_cap : (top_k < 64u ? 2048u : 8192u);
+        if ((uint64_t)nq * cap * 12u <= (1ull << 30)) {
+            if (w->tie_log.ensure((size_t)nq * cap * 12u) == RBQ_OK) { P.tie_log = (uint32_t*)w->tie_log.p; P.tie_log_cap = cap; }
+            else { (void)hipGetLastError(); g_err.clear(); } // (no memory for the log: the call is served without it)
+        }
+    }
+    P.heap_ws = nullptr;
+    if (top_k > kTopKMax || scan_lds_bytes(ix->Dc, ix->D, P.ex_bits, top_k) > kLdsPerWorkgroupMax) { // the heap does not fit the LDS
+        int rc = w->heap_ws.ensure((size_t)nq * 2 * ((size_t)top_k + 1) * 4);
+        if (rc) return rc;
+        P.heap_ws = (uint32_t*)w->heap_ws.p;
+    }
+    HIP_TRY(launch_scan(P, (uint32_t)nq, ix->device, stream, ps.start(), ps.stop()));
+    return RBQ_OK;
+}
+
+// Core: everything on device pointers, enqueued on `stream`. Workspace buffers come from `w`.
+int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe_in,
+                  const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
+                  rbq_diag* d_diag, hipStream_t stream) {
+    const uint32_t D = ix->D, Dc = ix->Dc;
+    const uint32_t nlist = (uint32_t)ix->n_lists;
+    uint32_t nprobe = nprobe_in < 1 ? 1 : nprobe_in;
+    if (nprobe > nlist) nprobe = nlist;
+    // nprobe > kNprobeMax: the exact all-pairs ranking with its key window in global memory; top_k > kTopKMax: the heap in
+    // global memory — both slow, both served (the reference clamps nprobe to n_lists and accepts any top_k)
+    const bool big_nprobe = nprobe > kNprobeMax;
+    // the 8 GiB bound is the global-memory heap's (top_k beyond what the LDS holds); calls whose heap lives in LDS need no workspace
+    const bool heap_in_global = top_k > kTopKMax || scan_lds_bytes(Dc, D, ix->ex_bits, top_k) > kLdsPerWorkgroupMax;
+    if (top_k > kTopKHardMax || (heap_in_global && (uint64_t)nq * ((uint64_t)top_k + 1) * 8 > (8ull << 30)))
+        return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20 and nq * top_k * 8 bytes of heap workspace <= 8 GiB)");
+    if (ix->rerank && top_k > 1024) return fail(RBQ_INVALID_CONFIG, "rerank supports top_k <= 1024");
+    const uint64_t wl_stride = std::max<uint64_t>(ix->nblk_desc_prefix[nprobe], 1);
+
+    int rc;
+    if ((rc = w->rot.ensure(nq * D * 4))) return rc;
+    if ((rc = w->lut.ensure(nq * (size_t)Dc * 4))) return rc;
+    if ((rc = w->consts.ensure(nq * sizeof(QueryConsts)))) return rc;
+    if ((rc = w->scores.ensure(nq * (size_t)nlist * 4))) return rc;
+    if ((rc = w->probe.ensure(nq * (size_t)nprobe * sizeof(ProbeInfo)))) return rc;
+    if ((rc = w->wl.ensure(nq * wl_stride * sizeof(StreamItem)))) return rc;
+    if ((rc = w->nstream.ensure(nq * 4))) return rc;
+    if ((rc = w->nvec.ensure(nq * 8))) return rc;
+    if ((rc = w->dead_skipped.ensure(nq * 16))) return rc;
+    const bool split_rank = !ix->opt.exact_rank && !ix->opt.f32_rank && D % 64 == 0; // k_rank_bf16_db (else k_rank_mfma)
+    if (split_rank) {
+        if ((rc = w->rot_hi.ensure(nq * D * 2))) return rc;
+        if ((rc = w->rot_lo.ensure(nq * D * 2))) return rc;
+    }
+    unsigned long long* prof = (ix->profiling && ix->opt.profile_counters) ? (unsigned long long*)ix->prof.p : nullptr;
+    const uint32_t smask = ix->opt.stage_mask;
+    // small calls: prep + exact scores of every list in one launch (the ranking GEMM and its launch boundary are skipped)
+    // split-K of the ranking GEMM for batches whose tiles leave the chip idle (the rows are cleared by the workgroup-per-query preparation)
+    uint32_t ksplit = 1;
+    // (only when the whole CALL is small: the sub-batches of a 1024-query host call overlap each other, and the extra workgroups and
+    // atomics of a split GEMM then cost more than its shorter K loop saves — 277 -> 295 us per call, measured)
+    if (ix->opt.rank_ksplit && ix->opt.latency_path && nq <= kPrepWgMaxQueries && (w->call_nq ? w->call_nq : nq) <= kSplitKMaxCallQueries && ix->rotator != 0 &&
+        !ix->opt.wg_prep && D % 16 == 0 && split_rank && !ix->opt.exact_rank && !big_nprobe && smask == 0xfu) {
+        const uint32_t T = ((uint64_t)((nlist + 127) / 128) * ((nq + 127) / 128) >= 192 && ix->opt.rank_tile != 64) || ix->opt.rank_tile == 128 ? 128u : 64u;
+        const uint64_t tiles = (uint64_t)((nlist + T - 1) / T) * ((nq + T - 1) / T);
+        ksplit = tiles >= 512 ? 1u : (tiles >= 256 ? 2u : 4u);
+        while (ksplit > 1 && (D / 32) / ksplit < 6) ksplit >>= 1; // (at least six slabs per part)
+        // (option: forced; at most 4 parts, the most the eps of k_select_mfma is derived for — rank_mfma.hpp header)
+        if (ix->opt.rank_ksplit > 1) ksplit = (uint32_t)std::min(ix->opt.rank_ksplit, 4);
+    }
+    const bool lat_front = ix->opt.latency_path && nq <= kLatMaxQueries && ix->rotator != 0 && !ix->opt.wg_prep && !ix->opt.exact_rank && !big_nprobe &&
+                           !ix->opt.f32_rank && (uint64_t)nlist * D * 4 * nq <= kLatMaxBytes && D % 16 == 0 && smask == 0xfu;
+    if (lat_front) {
+        ProfScope ps(ix, 0, stream);
+        const PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq);
+        RankParams r;
+        r.metric = ix->metric; r.cent = (const float*)ix->centroids.p; r.nlist = nlist; r.D = D; r.nq = (uint32_t)nq;
+        r.scores = (float*)w->scores.p;
+        HIP_TRY(launch_lat_front(p, r, ix->device, stream));
+    } else if (smask & 1u) {
+        ProfScope ps(ix, 0, stream);
+        PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq);
+        p.rot_hi = split_rank ? (uint16_t*)w->rot_hi.p : nullptr; p.rot_lo = split_rank ? (uint16_t*)w->rot_lo.p : nullptr;
+        p.wg_prep = ix->opt.wg_prep;
+        // batches a caller waits for (a few hundred queries: the chip is not full): a workgroup per query — the serial sums on one
+        // wave while the others build the LUT (latency.hpp, preparation only); full batches keep one wave per query (k_prep_wave)
+        if (ix->opt.latency_path && nq <= kPrepWgMaxQueries && ix->rotator != 0 && !ix->opt.wg_prep && D % 16 == 0) {
+            RankParams r;
+            r.metric = ix->metric; r.cent = nullptr; r.nlist = nlist; r.D = D; r.nq = (uint32_t)nq;
+            r.scores = ksplit > 1 ? (float*)w->scores.p : nullptr; r.ksplit = ksplit; // (split-K GEMM: this kernel clears the score rows)
+            HIP_TRY(launch_lat_front(p, r, ix->device, stream));
+        } else {
+            HIP_TRY(launch_prep(p, ix->device, stream));
+        }
+    }
+    RankParams rp;
+    rp.metric = ix->metric; rp.rot = (const float*)w->rot.p; rp.rot_hi = (const uint16_t*)w->rot_hi.p; rp.rot_lo = (const uint16_t*)w->rot_lo.p;
+    rp.cent = (const float*)ix->centroids.p; rp.cent_hi = (const uint16_t*)ix->cent_hi.p; rp.cent_lo = (const uint16_t*)ix->cent_lo.p;
+    rp.consts = (const QueryConsts*)w->consts.p; rp.cnorm2 = (const float*)ix->cnorm2.p; rp.nq = (uint32_t)nq; rp.nlist = nlist; rp.D = D;
+    rp.scores = (float*)w->scores.p; rp.split = split_rank; rp.ksplit = ksplit;
+    rp.big = (uint64_t)((nlist + 127) / 128) * ((nq + 127) / 128) >= 192; // enough 128x128 tiles to fill the chip
+    // option rank_tile: 0 = by problem size, 64 / 128 / 256 = forced (tests; A/B)
+    rp.wide = ix->opt.rank_tile == 256 || (ix->opt.rank_tile == 0 && (uint64_t)((nlist + 255) / 256) * ((nq + 127) / 128) >= 2048);
+    if (ix->opt.rank_tile == 64) rp.big = false;
+    if (ix->opt.rank_tile == 128) rp.big = true;
+    SelectParams sp;
+    sp.scores = (float*)w->scores.p; sp.nq = (uint32_t)nq; sp.nlist = nlist; sp.nprobe = nprobe; sp.metric = ix->metric;
+    sp.rot = (const float*)w->rot.p; sp.cent = (const float*)ix->centroids.p; sp.D = D; sp.consts = (const QueryConsts*)w->consts.p;
+    sp.cnorm2_max = ix->cnorm2_max; sp.list_gb0 = (const uint32_t*)ix->list_gb0.p; sp.list_n = (const uint32_t*)ix->list_n.p;
+    sp.probe = (ProbeInfo*)w->probe.p; sp.wl = (StreamItem*)w->wl.p; sp.wl_stride = wl_stride; sp.nstream = (uint32_t*)w->nstream.p;
+    sp.nvec = (unsigned long long*)w->nvec.p; sp.prof_total = prof; sp.fallback_count = (unsigned int*)ix->fallbacks.p;
+    sp.force_fallback = ix->opt.force_rank_fallback ? 1 : 0; sp.bsum = (const BlockSummary*)ix->bsum.p;
+    sp.cnorm2 = (const float*)ix->cnorm2.p; sp.lsum = (const BlockSummary*)ix->lsum.p; sp.bsumx = (const BlockSummaryEx*)ix->bsumx.p;
+    sp.dead_skipped = (uint32_t*)w->dead_skipped.p; sp.top_k = top_k; sp.ex_bits = ix->ex_bits;
+    sp.slack = ix->opt.slack;
+    sp.numeric_variant = ix->opt.numeric_variant;
+    sp.audit_dead = nullptr;
+    if (ix->opt.lazy_audit) { // diagnostic: the lists the selection drops as a whole are exported (rbq_debug_copy_workspace "audit_dead")
+        if ((rc = w->audit_dead.ensure(nq * (size_t)(kAuditCap + 1) * 4))) return rc;
+        HIP_TRY(hipMemsetAsync(w->audit_dead.p, 0, nq * (size_t)(kAuditCap + 1) * 4, stream));
+        sp.audit_dead = (uint32_t*)w->audit_dead.p;
+    }
+    sp.head_ub = nullptr;
+    if (ix->opt.ub_tap) { // diagnostic: the lazy selection's head candidates and their bounds (rbq_debug_copy_workspace "head_ub")
+        if ((rc = w->head_ub.ensure(nq * (size_t)kHeadUbRow * 4))) return rc;
+        HIP_TRY(hipMemsetAsync(w->head_ub.p, 0, nq * (size_t)kHeadUbRow * 4, stream));
+        sp.head_ub = (uint32_t*)w->head_ub.p;
+    }
+    // lazy selection: not with a filter (filtered vectors are never pushed, so no select-time bound of the k-th distance
+    // exists) and not when every probed block is to be streamed
+    // (round 4: under a filter the exact head evaluation can still bound the k-th distance — it looks at real vectors and counts
+    // the ones that pass; with diagnostics the skip counter of a dropped list would need every id's filter bit: eager then)
+    const bool lazy_with_filter = ix->opt.lazy_filter && ix->opt.head_exact && !d_diag;
+    sp.lazy = (ix->opt.lazy_select && (!d_filter || lazy_with_filter) && !ix->opt.no_block_bound) ? 1 : 0;
+    sp.filter = d_filter; sp.filter_nbits = filter_nbits; sp.ids = (const uint64_t*)ix->ids.p;
+    sp.exact_members = d_diag ? 1 : 0;
+    sp.fault_dead_all = ix->opt.lazy_fault_inject ? 1 : 0;
+    sp.lut = (const uint8_t*)w->lut.p; sp.blocks = (const uint8_t*)ix->blocks.p; sp.ex_codes = (const uint8_t*)ix->ex.p;
+    sp.f_add_ex = (const float*)ix->fadd_ex.p; sp.f_rescale_ex = (const float*)ix->fres_ex.p; sp.Dc = Dc;
+    sp.head_exact = ix->opt.head_exact ? 1 : 0;
+    sp.n_blocks = (uint32_t)ix->n_blocks;
+    if (ix->opt.exact_rank || big_nprobe) {
+        uint64_t* kw = nullptr;
+        if (big_nprobe) {
+            if ((rc = w->key_window.ensure((size_t)nq * select_exact_np2(nprobe) * 8))) return rc;
+            kw = (uint64_t*)w->key_window.p;
+        }
+        if (smask & 2u) { ProfScope ps(ix, 1, stream); HIP_TRY(launch_rank_exact(rp, stream)); }
+        if (smask & 4u) { ProfScope ps(ix, 2, stream); HIP_TRY(launch_select_exact(sp, ix->device, stream, kw)); }
+    } else {
+        if ((smask & 2u) && !lat_front) { ProfScope ps(ix, 1, stream); HIP_TRY(launch_rank_gemm(rp, ix->device, stream)); } // approximate scores: one MFMA GEMM
+        if (smask & 4u) { ProfScope ps(ix, 2, stream); HIP_TRY(launch_select_mfma(sp, ix->device, stream)); }         // shortlist + exact canonical scores + exact select
+    }
+    if ((smask & 8u) && (rc = scan_stage(ix, w, nq, nprobe, top_k, wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag,
+                         /*mstg=*/false, (ix->opt.exact_rank || big_nprobe) ? nullptr : (const uint32_t*)w->dead_skipped.p, stream)))
+        return rc;
+    if (ix->rerank && !stage_probes()) // optional, default off: exact re-scoring of the returned ids against the attached raw vectors
+        HIP_TRY(launch_rerank(d_queries, (uint32_t)nq, ix->dim, (const float*)ix->raw.p, ix->n_raw, ix->metric, top_k, d_ids, d_scores,
+                              d_counts, stream));
+    return RBQ_OK;
+}
+
+int check_query_args(const rbq_index* h, uint32_t query_dim) {
+    if (!h || h->reps.empty()) return fail(RBQ_INVALID_CONFIG, "null index");
+    const Replica* ix = h->reps[0];
+    if (ix->n_vectors == 0) return fail(RBQ_EMPTY_INDEX, "index is empty");
+    if (query_dim != ix->dim) {
+        char b[96];
+        std::snprintf(b, sizeof b, "expected %u, got %u", ix->dim, query_dim);
+        return fail(RBQ_DIMENSION_MISMATCH, b);
+    }
+    return RBQ_OK;
+}
+
+// rbq_search_batch on ONE replica.  The batch is cut into sub-batches of (by default) 1024 queries that travel through
+// up to six lanes (stream + workspace + pinned staging each), so the stages of neighbouring sub-batches overlap on the
+// GPU exactly like bench.py's device-resident batches do, and the host stages sub-batch j+1 while j runs.
+//  * results: k_scan writes ids / scores / counts / diagnostics STRAIGHT into page-locked host memory (the caller's
+//    buffers when they are page-locked — rbq_host_alloc / hipHostMalloc / hipHostRegister — else the lane's pinned
+//    staging, handed over with one memcpy): 123 KB per 1024 queries, no D2H copy command in the queue;
+//  * queries: page-locked caller buffers are DMA-ed as they are, pageable ones are staged through the lane's pinned
+//    buffer in pieces (the DMA of piece i runs under the memcpy of piece i+1);
+//  * one event per sub-batch, no stream synchronisation.
+int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t nprobe,
+                const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                rbq_diag* diag) {
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    using clk = std::chrono::steady_clock;
+    const bool trace = ix->opt.host_trace != 0;
+    double t_attr = 0, t_ws = 0, t_stage = 0, t_enq = 0, t_wait = 0, t_out = 0;
+    auto tick = [&](clk::time_point& t0, double& acc) { if (trace) { const auto t1 = clk::now(); acc += std::chrono::duration<double, std::micro>(t1 - t0).count(); t0 = t1; } };
+    clk::time_point tp = clk::now();
+    // sub-batches shrink towards the end of the call (rbq_host_logic.hpp): the last one's kernel chain is what the caller waits for
+    const std::vector<std::pair<uint64_t, uint64_t>> plan = rbq_host::subbatch_plan(nq, ix->opt.host_subbatch);
+    const uint64_t nsub = plan.size();
+    const uint32_t nlanes = (uint32_t)std::min<uint64_t>(nsub, ix->opt.host_lanes ? ix->opt.host_lanes : 6u);
+    const bool in_pinned = is_pinned_host_range(queries, nq * query_dim * 4);
+    bool out_pinned = !ix->rerank && is_pinned_host_range(out_ids, nq * top_k * 8) && is_pinned_host_range(out_scores, nq * top_k * 4) &&
+                      is_pinned_host_range(out_counts, nq * 4) && (!diag || is_pinned_host_range(diag, nq * sizeof(rbq_diag)));
+    // device-side addresses of page-locked caller buffers (identical under unified addressing; asked for, not assumed)
+    uint64_t* c_ids = nullptr; float* c_scores = nullptr; uint32_t* c_counts = nullptr; rbq_diag* c_diag = nullptr;
+    if (out_pinned) {
+        if (hipHostGetDevicePointer((void**)&c_ids, out_ids, 0) != hipSuccess || hipHostGetDevicePointer((void**)&c_scores, out_scores, 0) != hipSuccess ||
+            hipHostGetDevicePointer((void**)&c_counts, out_counts, 0) != hipSuccess ||
+            (diag && hipHostGetDevicePointer((void**)&c_diag, diag, 0) != hipSuccess)) {
+            (void)hipGetLastError();
+            out_pinned = false;
+        }
+    }
+    // page-locked queries are read by k_prep where they lie (device-side address of the caller's buffer)
+    // (measured, GIST-1M shape: 1024 queries per call 297 -> 280 us, 1536: 388 -> 376, 256: 212 -> 198 us; but one query 133 -> 147 us,
+    // 2048 per call 445 -> 457 and from 4096 the copy engine clearly beats the waves' own PCIe reads: 678 -> 778 us — hence the window)
+    // (pageable queries, read from the lane's pinned staging buffer: 1024 per call 381 -> 373 us, but 2048 per call 524 -> 591 us:
+    // there the staged DMA pieces overlap the host copy better than one big copy followed by in-place reads — window <= 1024)
+    // (round 5: the preparation kernels now request a query's elements eight at a time instead of one per round trip — 15 PCIe round
+    // trips per query at D = 960 became 2 — and the window opens at 5 queries: 8 per call 149 -> 142 us, 16: 156 -> 149, 24: 161 -> 153)
+    const bool zero_copy = ix->opt.host_zero_copy && nq >= kZeroCopyMinQueries && nq <= (in_pinned ? 1536u : 1024u);
+    const float* c_queries = nullptr;
+    if (zero_copy && in_pinned && hipHostGetDevicePointer((void**)&c_queries, const_cast<float*>(queries), 0) != hipSuccess) {
+        (void)hipGetLastError();
+        c_queries = nullptr;
+    }
+    tick(tp, t_attr);
+    std::vector<Workspace*> lanes;
+    struct Give { Replica* ix; std::vector<Workspace*>& l; bool drained = false;
+                  ~Give() { for (Workspace* w : l) { if (!drained) (void)hipStreamSynchronize(w->stream); give_ws(ix, w); } } } give{ix, lanes};
+    for (uint32_t i = 0; i < nlanes; ++i) {
+        Workspace* w = take_ws(ix);
+        if (!w) return fail(RBQ_DEVICE, "cannot create workspace stream");
+        lanes.push_back(w);
+    }
+    tick(tp, t_ws);
+    int rc;
+    const uint32_t* d_filter = nullptr;
+    if (filter_words) {
+        const size_t fb = (size_t)((filter_nbits + 31) / 32) * 4;
+        Workspace* w0 = lanes[0];
+        if ((rc = w0->filter.ensure(fb ? fb : 4))) return rc;
+        if (fb) HIP_TRY(hipMemcpyAsync(w0->filter.p, filter_words, fb, hipMemcpyHostToDevice, w0->stream));
+        HIP_TRY(hipEventRecord(w0->done, w0->stream));
+        for (uint32_t i = 1; i < nlanes; ++i) HIP_TRY(hipStreamWaitEvent(lanes[i]->stream, w0->done, 0));
+        d_filter = (const uint32_t*)w0->filter.p;
+    }
+    // hand the finished sub-batch j (in the lane's pinned buffer) to the caller's arrays
+    auto deliver = [&](Workspace* w, uint64_t j) -> int {
+        clk::time_point td = clk::now();
+        HIP_TRY(hipEventSynchronize(w->done));
+        tick(td, t_wait);
+        if (out_pinned) return RBQ_OK;
+        const uint64_t q0 = plan[j].first, n = plan[j].second;
+        const OutPack op(n, top_k, diag != nullptr);
+        const uint8_t* src = (const uint8_t*)w->h_out.p;
+        std::memcpy(out_ids + q0 * top_k, src + op.o_ids, n * top_k * 8);
+        std::memcpy(out_scores + q0 * top_k, src + op.o_scores, n * top_k * 4);
+        std::memcpy(out_counts + q0, src + op.o_counts, n * 4);
+        if (diag) std::memcpy(diag + q0, src + op.o_diag, n * sizeof(rbq_diag));
+        tick(td, t_out);
+        return RBQ_OK;
+    };
+    // pageable queries, every sub-batch on its own lane (nsub <= nlanes): the helpers stage sub-batches 1.. into their lanes' pinned
+    // buffers while this thread stages and launches sub-batch 0
+    constexpr uint64_t kMaxHelped = 8;
+    std::atomic<int> staged[kMaxHelped];
+    uint64_t n_helped = 0; // sub-batches 1 .. n_helped are staged by helpers
+    auto wait_staged = [&staged](uint64_t j) { spin_until([&] { return staged[j].load(std::memory_order_acquire) != 0; }); };
+    struct WaitHelpers { decltype(wait_staged)& wait; uint64_t& n; // (no job may outlive this frame: it writes the flags)
+        ~WaitHelpers() { for (uint64_t j = 1; j <= n; ++j) wait(j); } } wait_helpers{wait_staged, n_helped};
+    bool helpers = !in_pinned && ix->opt.host_stage_helpers && nsub >= 2 && nsub <= nlanes && nsub <= kMaxHelped && nq * query_dim * 4 >= (512u << 10);
+    if (helpers) {
+        // the helpers are published only once every thread of theirs runs (a half-started set used to stay installed, and
+        // jobs posted to it could wait forever); if a thread cannot be created the call stages inline, like a small one does
+        std::lock_guard<std::mutex> lk(ix->mu);
+        if (!ix->stagers && !ix->stagers_failed) {
+            std::unique_ptr<StagePool> sh(new (std::nothrow) StagePool());
+            if (sh && sh->start()) ix->stagers = std::move(sh);
+            else ix->stagers_failed = true;
+        }
+        helpers = ix->stagers != nullptr;
+    }
+    if (helpers) {
+        for (uint64_t j = 1; j < nsub; ++j) {
+            Workspace* wj = lanes[j];
+            if ((rc = wj->h_in.ensure(plan[j].second * query_dim * 4))) return rc; // (jobs posted so far are awaited by wait_helpers)
+            staged[j].store(0, std::memory_order_relaxed);
+            ix->stagers->post(StageJob{wj->h_in.p, queries + plan[j].first * query_dim, (size_t)(plan[j].second * query_dim * 4), &staged[j]});
+            n_helped = j;
+        }
+    }
+    for (uint64_t j = 0; j < nsub; ++j) {
+        Workspace* w = lanes[j % nlanes];
+        if (j >= nlanes && (rc = deliver(w, j - nlanes))) return rc;
+        const uint64_t q0 = plan[j].first, n = plan[j].second;
+        const OutPack op(n, top_k, diag != nullptr);
+        const bool staged_in_hbm = !(c_queries || (zero_copy && !in_pinned)); // an H2D copy into the lane's device buffer
+        if (staged_in_hbm && (rc = w->queries.ensure(n * query_dim * 4))) return rc;
+        const float* src = queries + q0 * query_dim;
+        tp = clk::now();
+        const float* d_q = (const float*)w->queries.p; // where k_prep reads this sub-batch
+        if (c_queries) {
+            d_q = c_queries + q0 * query_dim;
+        } else if (zero_copy && !in_pinned) { // pageable: one host copy into the lane's pinned buffer, read from there
+            if (j >= 1 && j <= n_helped) { // staged by a helper: wait for its copy
+                wait_staged(j);
+            } else {
+                if ((rc = w->h_in.ensure(n * query_dim * 4))) return rc;
+                std::memcpy(w->h_in.p, src, n * query_dim * 4);
+            }
+            float* hp = nullptr;
+            HIP_TRY(hipHostGetDevicePointer((void**)&hp, w->h_in.p, 0));
+            d_q = hp;
+        } else if (in_pinned) {
+            HIP_TRY(hipMemcpyAsync(w->queries.p, src, n * query_dim * 4, hipMemcpyHostToDevice, w->stream));
+        } else if (j >= 1 && j <= n_helped) { // pageable, staged by a helper: wait for its copy, one DMA
+            wait_staged(j);
+            HIP_TRY(hipMemcpyAsync(w->queries.p, w->h_in.p, n * query_dim * 4, hipMemcpyHostToDevice, w->stream));
+        } else {
+            if ((rc = w->h_in.ensure(n * query_dim * 4))) return rc;
+            const uint64_t piece = std::max<uint64_t>(64, (n + 3) / 4); // queries per piece
+            for (uint64_t p0 = 0; p0 < n; p0 += piece) {
+                const size_t off = p0 * query_dim * 4, len = std::min(piece, n - p0) * query_dim * 4;
+                std::memcpy((uint8_t*)w->h_in.p + off, (const uint8_t*)src + off, len);
+                HIP_TRY(hipMemcpyAsync((uint8_t*)w->queries.p + off, (const uint8_t*)w->h_in.p + off, len, hipMemcpyHostToDevice, w->stream));
+            }
+        }
+        tick(tp, t_stage);
+        uint64_t* k_ids; float* k_scores; uint32_t* k_counts; rbq_diag* k_diag; // where the kernels write
+        if (out_pinned) {
+            k_ids = c_ids + q0 * top_k; k_scores = c_scores + q0 * top_k; k_counts = c_counts + q0; k_diag = diag ? c_diag + q0 : nullptr;
+        } else if (!ix->rerank) {
+            if ((rc = w->h_out.ensure(op.total))) return rc;
+            uint8_t* hp = nullptr;
+            HIP_TRY(hipHostGetDevicePointer((void**)&hp, w->h_out.p, 0));
+            k_ids = (uint64_t*)(hp + op.o_ids); k_scores = (float*)(hp + op.o_scores); k_counts = (uint32_t*)(hp + op.o_counts);
+            k_diag = diag ? (rbq_diag*)(hp + op.o_diag) : nullptr;
+        } else { // the rerank kernel re-reads the ids: keep them in HBM, one D2H copy afterwards
+            if ((rc = w->out_pack.ensure(op.total))) return rc;
+            uint8_t* dp = (uint8_t*)w->out_pack.p;
+            k_ids = (uint64_t*)(dp + op.o_ids); k_scores = (float*)(dp + op.o_scores); k_counts = (uint32_t*)(dp + op.o_counts);
+            k_diag = diag ? (rbq_diag*)(dp + op.o_diag) : nullptr;
+        }
+        // every sub-batch of a call below kHostWaveMinQueries takes the short-chain kernel
+        w->latency_first = nq < kHostWaveMinQueries;
+        w->call_nq = nq;
+        rc = search_device(ix, w, d_q, n, top_k, nprobe, d_filter, filter_nbits, k_ids, k_scores, k_counts, k_diag, w->stream);
+        w->latency_first = false;
+        w->call_nq = 0;
+        if (rc) return rc;
+        if (ix->rerank) {
+            if ((rc = w->h_out.ensure(op.total))) return rc;
+            HIP_TRY(hipMemcpyAsync(w->h_out.p, w->out_pack.p, op.total, hipMemcpyDeviceToHost, w->stream));
+        }
+        HIP_TRY(hipEventRecord(w->done, w->stream));
+        tick(tp, t_enq);
+    }
+    for (uint64_t j = nsub > nlanes ? nsub - nlanes : 0; j < nsub; ++j)
+        if ((rc = deliver(lanes[j % nlanes], j))) return rc;
+    give.drained = true; // every lane's last event has been waited for
+    if (trace)
+        std::fprintf(stderr, "[rbq host] nq=%llu sub=%llu lanes=%u pinned(in,out)=%d,%d us: attr %.1f ws %.1f stage %.1f enqueue %.1f wait %.1f copy-out %.1f\n",
+                     (unsigned long long)nq, (unsigned long long)plan[0].second, nlanes, (int)in_pinned, (int)out_pinned, t_attr, t_ws, t_stage, t_enq, t_wait, t_out);
+    return RBQ_OK;
+}
+
+Replica* replica_of_pointer(rbq_index* h, const void* dptr) {
+    if (h->reps.size() == 1) return h->reps[0];
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, dptr) == hipSuccess) {
+        for (Replica* r : h->reps) if (r->device == a.device) return r;
+    } else {
+        (void)hipGetLastError();
+    }
+    return h->reps[0];
+}
+} // namespace
+} // namespace rbq_api
+
+extern "C" {
+// ---- search ---------------------------------------------------------------------------------------
+int rbq_search_batch_device(const rbq_index* ch, const float* d_queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                            uint32_t nprobe, const uint32_t* d_filter_words, uint64_t filter_nbits, uint64_t* d_out_ids,
+                            float* d_out_scores, uint32_t* d_out_counts, rbq_diag* d_diag, void* hip_stream) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    rbq_index* h = const_cast<rbq_index*>(ch);
+    int rc = check_query_args(h, query_dim);
+    if (rc) return rc;
+    if (nq == 0) return RBQ_OK;
+    if (nq > 0x7fffffffull) return fail(RBQ_INVALID_CONFIG, "batch too large");
+    Replica* ix = replica_of_pointer(h, d_queries);
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (top_k == 0) { // Ok(vec![]) for every query, src/ivf.rs:1792-1794
+        HIP_TRY(hipMemsetAsync(d_out_counts, 0, nq * 4, s));
+        return RBQ_OK;
+    }
+    // One workspace per caller stream, never handed to anyone else: successive calls on the same stream are
+    // stream-ordered, so their kernels may share the scratch buffers without any host synchronisation.
+    Workspace* w;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        Workspace*& slot = ix->stream_ws[s];
+        if (!slot) slot = new Workspace();
+        w = slot;
+    }
+    return search_device(ix, w, d_queries, nq, top_k, nprobe, d_filter_words, filter_nbits, d_out_ids, d_out_scores,
+                         d_out_counts, d_diag, s);
+    RBQ_GUARD_END
+}
+
+int rbq_release_stream(rbq_index* h, void* hip_stream) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!h) return fail(RBQ_INVALID_CONFIG, "null index");
+    for (Replica* ix : h->reps) {
+        Workspace* w = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(ix->mu);
+            auto it = ix->stream_ws.find((hipStream_t)hip_stream);
+            if (it != ix->stream_ws.end()) { w = it->second; ix->stream_ws.erase(it); }
+        }
+        if (w) { DeviceGuard g(ix->device); delete w; }
+    }
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+
+int rbq_search_batch(const rbq_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                     uint32_t nprobe, const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids,
+                     float* out_scores, uint32_t* out_counts, rbq_diag* diag) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    rbq_index* h = const_cast<rbq_index*>(ch);
+    int rc = check_query_args(h, query_dim);
+    if (rc) return rc;
+    if (nq == 0) return RBQ_OK;
+    if (top_k == 0) {
+        if (out_counts) std::memset(out_counts, 0, nq * 4);
+        if (diag) std::memset(diag, 0, nq * sizeof(rbq_diag));
+        return RBQ_OK;
+    }
+    if (!queries || !out_ids || !out_scores || !out_counts) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    const size_t R = h->reps.size();
+    if (R == 1 || nq < 2 * R) return search_host(h->reps[0], queries, nq, query_dim, top_k, nprobe, filter_words, filter_nbits, out_ids,
+                                                  out_scores, out_counts, diag);
+    // N replicas: contiguous shards [r*nq/R, (r+1)*nq/R) (batch_search is a par_iter over queries, src/ivf.rs:1743-1752);
+    // replica 0 is served by the calling thread, replica r > 0 by its persistent worker thread; results land straight in
+    // the caller's arrays, no exchange between devices
+    {
+        std::lock_guard<std::mutex> lk(h->worker_mu);
+        while (h->workers.size() + 1 < R) { // (published only once every thread of theirs runs)
+            std::unique_ptr<ReplicaPool> w(new ReplicaPool());
+            if (!w->start()) return fail(RBQ_IO, "cannot start the worker threads of a replica");
+            h->workers.push_back(std::move(w));
+        }
+    }
+    // Everything the posted jobs touch lives in one shared state they hold by value: a job that is still running when this
+    // frame unwinds (post() threw after earlier replicas were posted) writes into memory it co-owns, never into a dead stack.
+    struct ShardState {
+        std::mutex mu; std::condition_variable cv; size_t left = 0;
+        std::vector<int> rcs; std::vector<std::string> details;
+    };
+    auto st = std::make_shared<ShardState>();
+    st->rcs.assign(R, RBQ_OK);
+    st->details.resize(R);
+    st->left = R - 1;
+    auto shard = [st, h, R, nq, queries, query_dim, top_k, nprobe, filter_words, filter_nbits, out_ids, out_scores, out_counts, diag](size_t r) {
+        uint64_t q0, q1;
+        rbq_host::shard_range(r, R, nq, &q0, &q1);
+        try {
+            st->rcs[r] = search_host(h->reps[r], queries + q0 * query_dim, q1 - q0, query_dim, top_k, nprobe, filter_words, filter_nbits,
+                                     out_ids + q0 * top_k, out_scores + q0 * top_k, out_counts + q0, diag ? diag + q0 : nullptr);
+        } catch (...) { st->rcs[r] = RBQ_IO; g_err = "internal error"; }
+        st->details[r] = g_err; // thread-local in the worker
+    };
+    size_t posted = 0;
+    bool post_failed = false;
+    try {
+        for (size_t r = 1; r < R; ++r) {
+            h->workers[r - 1]->post([st, shard, r] {
+                shard(r);
+                std::lock_guard<std::mutex> lk(st->mu);
+                if (--st->left == 0) st->cv.notify_one();
+            });
+            ++posted;
+        }
+    } catch (...) { post_failed = true; }
+    if (post_failed) { // the caller's buffers must stay valid until the shards already under way have finished
+        std::unique_lock<std::mutex> lk(st->mu);
+        st->left -= (R - 1 - posted);
+        st->cv.wait(lk, [&] { return st->left == 0; });
+        return fail(RBQ_IO, "out of host memory");
+    }
+    shard(0);
+    {
+        // the other shards finish about when this one does: poll briefly before blocking on the latch
+        const auto t0 = std::chrono::steady_clock::now();
+        std::unique_lock<std::mutex> lk(st->mu);
+        while (st->left != 0) {
+            if (std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(200)) { lk.unlock(); std::this_thread::yield(); lk.lock(); }
+            else st->cv.wait(lk, [&] { return st->left == 0; });
+        }
+    }
+    for (size_t r = 0; r < R; ++r) if (st->rcs[r]) return fail(st->rcs[r], st->details[r]);
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+
+// ---- MSTG posting-list scan ------------------------------------------------------------
+int rbq_posting_scan_batch(const rbq_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                           const uint32_t* list_ids, const uint32_t* list_counts, uint32_t max_lists,
+                           uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    rbq_index* h = const_cast<rbq_index*>(ch);
+    int rc = check_query_args(h, query_dim);
+    if (rc) return rc;
+    Replica* ix = h->reps[0];
+    if (ix->rotator != RBQ_ROTATOR_NONE) return fail(RBQ_INVALID_CONFIG, "posting-list scan needs an index created with rotator NONE");
+    if (nq == 0) return RBQ_OK;
+    if (!queries || !list_ids || !list_counts || !out_ids || !out_scores || !out_counts) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    if (top_k == 0) { std::memset(out_counts, 0, nq * 4); return RBQ_OK; }
+    if (top_k > kTopKHardMax || (uint64_t)std::min<uint64_t>(nq, 16384) * ((uint64_t)top_k + 1) * 8 > (8ull << 30))
+        return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20)");
+    if (max_lists == 0) {
+        std::memset(out_counts, 0, nq * 4);
+        for (uint64_t i = 0; i < nq * top_k; ++i) { out_ids[i] = ~0ull; out_scores[i] = NAN; }
+        return RBQ_OK;
+    }
+    if (max_lists > (1u << 26)) return fail(RBQ_INVALID_CONFIG, "too many lists per query");
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    // exact work-list bound from the host copy of the list sizes (a list may legally repeat)
+    uint64_t wl_stride = 1;
+    for (uint64_t q = 0; q < nq; ++q) {
+        uint64_t tot = 0;
+        const uint32_t n = std::min(list_counts[q], max_lists);
+        for (uint32_t r = 0; r < n; ++r) {
+            const uint32_t cid = list_ids[q * max_lists + r];
+            if (cid < ix->n_lists) tot += (ix->h_list_n[cid] + 31u) / 32u;
+        }
+        wl_stride = std::max(wl_stride, tot);
+    }
+    if (wl_stride > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "posting lists too long for one query");
+    Workspace* w = take_ws(ix);
+    if (!w) return fail(RBQ_DEVICE, "cannot create workspace stream");
+    auto run = [&]() -> int {
+        int r2;
+        const uint32_t D = ix->D, Dc = ix->Dc;
+        const uint64_t CH = 16384;
+        DevBuf& d_lists = w->scores; // reuse: [n][max_lists] u32
+        DevBuf& d_cnts = w->nvec;    // reuse: [n] u32
+        for (uint64_t q0 = 0; q0 < nq; q0 += CH) {
+            const uint64_t n = std::min(CH, nq - q0);
+            const OutPack op(n, top_k, false);
+            if ((r2 = w->queries.ensure(n * query_dim * 4))) return r2;
+            if ((r2 = w->rot.ensure(n * D * 4))) return r2;
+            if ((r2 = w->lut.ensure(n * (size_t)Dc * 4))) return r2;
+            if ((r2 = w->consts.ensure(n * sizeof(QueryConsts)))) return r2;
+            if ((r2 = d_lists.ensure(n * (size_t)max_lists * 4))) return r2;
+            if ((r2 = d_cnts.ensure(n * 8))) return r2;
+            if ((r2 = w->probe.ensure(n * (size_t)max_lists * sizeof(ProbeInfo)))) return r2;
+            if ((r2 = w->wl.ensure(n * wl_stride * sizeof(StreamItem)))) return r2;
+            if ((r2 = w->nstream.ensure(n * 4))) return r2;
+            if ((r2 = w->out_pack.ensure(op.total))) return r2;
+            hipStream_t st = w->stream;
+            uint8_t* dp = (uint8_t*)w->out_pack.p;
+            HIP_TRY(hipMemcpyAsync(w->queries.p, queries + q0 * query_dim, n * query_dim * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_lists.p, list_ids + q0 * max_lists, n * (size_t)max_lists * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_cnts.p, list_counts + q0, n * 4, hipMemcpyHostToDevice, st));
+            {
+                ProfScope ps(ix, 0, st);
+                PrepParams p = prep_params(*ix, ix->rot_blob, *w, (const float*)w->queries.p, n);
+                p.ex_bits = 0u; // (MSTG: no ex codes)
+                HIP_TRY(launch_prep(p, ix->device, st));
+            }
+            {
+                ProfScope ps(ix, 2, st);
+                ProbesGivenParams p;
+                p.list_ids = (const uint32_t*)d_lists.p; p.list_counts = (const uint32_t*)d_cnts.p; p.max_lists = max_lists;
+                p.nq = (uint32_t)n; p.nlist = (uint32_t)ix->n_lists; p.metric = (int)ix->metric; p.rot = (const float*)w->rot.p;
+                p.cent = (const float*)ix->centroids.p; p.D = D; p.list_gb0 = (const uint32_t*)ix->list_gb0.p;
+                p.list_n = (const uint32_t*)ix->list_n.p; p.probe = (ProbeInfo*)w->probe.p; p.wl = (StreamItem*)w->wl.p;
+                p.wl_stride = wl_stride; p.nstream = (uint32_t*)w->nstream.p; p.consts = (const QueryConsts*)w->consts.p;
+                p.bsum = (const BlockSummary*)ix->bsum.p;
+                p.numeric_variant = ix->opt.numeric_variant;
+                HIP_TRY(launch_probes_given(p, st));
+            }
+            if ((r2 = scan_stage(ix, w, n, max_lists, top_k, wl_stride, nullptr, 0, (uint64_t*)(dp + op.o_ids), (float*)(dp + op.o_scores),
+                                 (uint32_t*)(dp + op.o_counts), nullptr, /*mstg=*/true, nullptr, st)))
+                return r2;
+            HIP_TRY(hipMemcpyAsync(out_ids + q0 * top_k, dp + op.o_ids, n * top_k * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_scores + q0 * top_k, dp + op.o_scores, n * top_k * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_counts + q0, dp + op.o_counts, n * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return RBQ_OK;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(w->stream);
+    give_ws(ix, w);
+    return rc;
+    RBQ_GUARD_END
+}
+
+
+// Which kernel instantiation each of the four stages launches for a call of this shape, and what it occupies.
+// out[stage][6] = workgroups, threads per workgroup, VGPRs per lane, LDS bytes per workgroup (static + dynamic), scratch bytes per
+// lane, 0; stages in the order prep, rank, select, scan.  Nothing is launched.
+int rbq_debug_stage_resources(rbq_index* h, uint64_t nq, uint32_t top_k, uint32_t nprobe, uint32_t* out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!h || h->reps.empty() || !out || nq == 0 || nq > 0x7fffffffull || top_k == 0) return fail(RBQ_INVALID_CONFIG, "bad argument");
+    Replica* ix = h->reps[0];
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    Workspace w; // scratch buffers are sized like a real call's (and freed on return); no kernel runs
+    StageProbes probes;
+    int rc;
+    {
+        // the probe comes off this thread on EVERY exit path (an exception out of search_device — bad_alloc from a
+        // workspace — used to leave it installed, and every later search of the thread then launched nothing and returned RBQ_OK)
+        struct ProbeGuard { ProbeGuard(StageProbes* p) { stage_probes() = p; } ~ProbeGuard() { stage_probes() = nullptr; } } guard(&probes);
+        rc = search_device(ix, &w, nullptr, nq, top_k, nprobe, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+    }
+    if (rc) return rc;
+    for (int st = 0; st < 4; ++st) {
+        const KernelProbe& k = probes.k[st];
+        hipFuncAttributes fa;
+        uint32_t* o = out + 6 * st;
+        if (!k.fn) { // a stage this call shape does not launch (the latency-first front of a small call covers prep AND rank): zeros
+            if (st != 1) return fail(RBQ_DEVICE, "stage was not probed");
+            for (int j = 0; j < 6; ++j) o[j] = 0;
+            continue;
+        }
+        HIP_TRY(hipFuncGetAttributes(&fa, k.fn));
+        o[0] = k.grid_x * (k.grid_y ? k.grid_y : 1u) * (k.grid_z ? k.grid_z : 1u); // (z: the parts of a split-K GEMM)
+        o[1] = k.block; o[2] = (uint32_t)fa.numRegs;
+        o[3] = (uint32_t)(fa.sharedSizeBytes + k.dyn_lds); o[4] = (uint32_t)fa.localSizeBytes; o[5] = 0;
+    }
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+} // extern "C"

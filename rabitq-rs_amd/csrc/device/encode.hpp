@@ -1,5 +1,5 @@
 // encode.hpp — GPU-side encoder: the quantisation loop of IvfRabitqIndex::train_with_clusters
-// (src/ivf.rs:1025-1215), writing the device layout of rbq_api.hip directly: the "faster" configuration (constant
+// (src/ivf.rs:1025-1215), writing the device layout of the host units (api.hpp) directly: the "faster" configuration (constant
 // rescale factor t_const) or RabitqConfig::new (per-vector factor from k_rescale.hip).
 //
 //   k_rotate_rows   Rotator::rotate_into for a set of rows (k_prep's rotation code)

@@ -186,10 +186,6 @@ hipError_t launch_select_mfma(const SelectParams& p, int device, hipStream_t s) 
     }
     lds += regionN;
     g.cand_cap = (uint32_t)(((g.stage ? (size_t)p.nprobe * 16 : 0) + (g.stage_rows ? rowsN - 16 : 0)) / 8); // (RM == 0 prefilter window)
-    {   // diagnostic: extra dynamic LDS per workgroup (occupancy experiments)
-        static const size_t pad = [] { const char* e = std::getenv("RBQ_SEL_LDS_PAD"); return e ? (size_t)std::atol(e) : (size_t)0; }();
-        lds += pad;
-    }
     if (p.nlist <= 4096) return launch_select_rm<2>(p, g, lds, device, s);
     if (g.row_in_lds) return launch_select_rm<1>(p, g, lds, device, s);
     return launch_select_rm<0>(p, g, lds, device, s);

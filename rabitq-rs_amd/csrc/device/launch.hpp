@@ -1,4 +1,4 @@
-// launch.hpp — host-callable launchers of the kernel translation units.  rbq_api.hip (pure host code) sees the
+// launch.hpp — host-callable launchers of the kernel translation units.  The api_*.hip units (pure host code) see the
 // kernels only through these; each .hip file below compiles on its own, so a change to the host side does not
 // rebuild k_scan's instantiations and vice versa.
 //   k_query.hip  k_prep / k_prep_wave, k_rank_* , k_select*, k_probes_given     (kernels.hpp, rank_mfma.hpp)

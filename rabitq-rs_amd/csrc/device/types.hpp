@@ -1,4 +1,4 @@
-// types.hpp — plain data shared by the host side (rbq_api.hip) and the kernel translation units
+// types.hpp — plain data shared by the host side (api_*.hip) and the kernel translation units
 // (k_query.hip, k_scan.hip, k_build.hip): kernel parameter blocks, device record layouts, launch geometry.
 // No device code in here, so the host TU can include it without instantiating a kernel.
 #pragma once

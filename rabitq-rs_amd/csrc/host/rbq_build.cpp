@@ -596,7 +596,7 @@ int rbq_build_train_bruteforce(const float* data, uint64_t n, uint32_t dim, uint
     if (dim == 0 || metric > 1 || rotator_type > RBQ_ROTATOR_FHT_KAC) return RBQ_INVALID_CONFIG;
     const uint32_t D = rotator_type == RBQ_ROTATOR_FHT_KAC ? (dim + 63) / 64 * 64 : dim;
     // the crate packs the ex codes of a dim that is not a multiple of 16 in another (bit-serial) layout, which this project does not
-    // serve (bf_validate: "Dimension must be multiple of 16 for SIMD"); the packers below write whole 16-dimension groups
+    // serve (validate_header: "Dimension must be multiple of 16 for SIMD"); the packers below write whole 16-dimension groups
     if (D % 16 != 0) return RBQ_INVALID_CONFIG;
     rbq_bf_built* b = new rbq_bf_built();
     std::memset(&b->hdr, 0, sizeof b->hdr);
