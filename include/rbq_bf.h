@@ -41,6 +41,24 @@ typedef struct {
 
 /* Upload an index (device = HIP ordinal, -1 = the current device).  Inputs are copied; nothing is retained. */
 int rbq_bf_create(const rbq_header* hdr, const rbq_bf_view* view, int device, rbq_bf_index** out);
+/* BruteForceRabitqIndex::train (reference src/brute_force.rs:214-285) on the device: every row of `data` is rotated,
+ * quantised against the zero centroid (quantize_with_centroid) in id order — the id of row i is i — and written straight
+ * into the index's arrays in HBM.  The handle equals, array for array and bit for bit, rbq_bf_create over the CPU builder's
+ * result for the same input, the padded_dim/8 zero bytes of ex code per vector of a 1-bit index (rbq_bf_view::ex_len)
+ * included, so rbq_bf_save_rbf1 writes the same stream for both.
+ *   hdr      dim, padded_dim, metric, rotator with its blob, ex_bits (0, 2 or 6); n_lists and n_vectors are ignored.  It
+ *            gets the checks of rbq_bf_create.
+ *   data     [n][dim] f32 in host or device memory (detected; host rows are copied a chunk at a time).  Finite values
+ *            only: like the IVF device encoder, the result for NaN or infinite input is not specified.
+ *   rescale  RBQ_RESCALE_CONST (RabitqConfig::faster: t_const > 0 required when ex_bits > 0) or RBQ_RESCALE_OPTIMAL
+ *            (RabitqConfig::new: best_rescale_factor per vector, t_const ignored; moot at ex_bits == 0), as for
+ *            rbq_index_build_device_ex.  Any other value is RBQ_INVALID_CONFIG.
+ *   max_chunk_rows  upper bound on the rows rotated and encoded per pass (callers short of HBM); 0 = as many as the
+ *            encoder's 512 MiB of rotated rows hold.  The result does not depend on it.
+ * Errors: n == 0 is RBQ_INVALID_CONFIG "training data must be non-empty"; a null pointer is RBQ_INVALID_CONFIG; every
+ * argument is checked before the first HIP call.  Never aborts: device failures are RBQ_DEVICE. */
+int rbq_bf_train_device(const rbq_header* hdr, const float* data, uint64_t n, int rescale, float t_const,
+                        uint64_t max_chunk_rows, int device, rbq_bf_index** out);
 /* Build the index from an RBF1 byte stream (save_to_writer, src/brute_force.rs:305-386) with the validation of
  * load_from_reader (:395-520) incl. CRC-32.  Like the crate, it refuses the 1-bit streams the crate writes ("checksum
  * mismatch"): its writer stores padded_dim/8 bytes of ex code per vector that its reader does not read. */

@@ -1,7 +1,9 @@
 """`BruteForceRabitqIndex` (reference src/brute_force.rs) over the C ABI of include/rbq.h (rbq_bf_*).
 
 Every vector is evaluated for every query on the GPU (k_bf_dist / k_bf_select); ids, counts and score bits equal the
-crate's.  Training runs on the CPU builder (builder.train_bruteforce), as for the IVF index."""
+crate's.  Training has two routes that give the same index, array for array and bit for bit: `train` runs the CPU builder
+(builder.train_bruteforce) and uploads its arrays; `train_on_device` rotates, quantises and packs on the GPU
+(rbq_bf_train_device) and writes the index in HBM directly, from a host array or a CUDA tensor."""
 import ctypes as C
 from dataclasses import dataclass
 
@@ -22,6 +24,8 @@ def lib():
         vp = C.c_void_p
         L.rbq_bf_create.restype = C.c_int
         L.rbq_bf_create.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
+        L.rbq_bf_train_device.restype = C.c_int
+        L.rbq_bf_train_device.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.POINTER(vp)]
         L.rbq_bf_load_rbf1.restype = C.c_int
         L.rbq_bf_load_rbf1.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp)]
         L.rbq_bf_save_rbf1.restype = C.c_int
@@ -79,6 +83,42 @@ class BruteForceRabitqIndex:
         """`BruteForceRabitqIndex::train` (src/brute_force.rs:214-287) on the CPU builder, then uploaded."""
         from . import builder
         return cls.from_built(builder.train_bruteforce(data, total_bits, metric, rotator_type, seed, use_faster_config), device)
+
+    @classmethod
+    def train_on_device(cls, data, total_bits, metric, rotator_type, seed, use_faster_config, device=None, max_chunk_rows=0):
+        """`BruteForceRabitqIndex::train` (src/brute_force.rs:214-285) with the rotation and quantisation on the GPU
+        (rbq_bf_train_device).  `data` [n][dim] is a host array or a CUDA tensor.  The crate's checks and messages come first, in
+        its order.  The header — rotator, and t_const for the faster configuration — depends only on (dim, bits, rotator, seed):
+        it is taken from the CPU builder over a single row.  `max_chunk_rows` bounds the rows encoded per pass (0: sized from the
+        encoder's scratch budget); the index does not depend on it and equals `train`'s."""
+        from . import RabitqError, builder
+        shape = tuple(getattr(data, "shape", None) or np.shape(data))
+        if len(shape) != 2 or shape[0] == 0:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "training data must be non-empty")
+        if not 1 <= int(total_bits) <= 16:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "total_bits must be between 1 and 16")
+        is_tensor = type(data).__module__.startswith("torch")
+        if is_tensor:
+            import torch
+            if data.is_cuda:
+                if device is not None and data.device.index != int(device):
+                    data = data.to(torch.device("cuda", int(device)))
+                x = data.to(dtype=torch.float32).contiguous()
+                ptr, row0, device = x.data_ptr(), x[:1].cpu().numpy(), x.device.index
+            else:
+                data, is_tensor = data.numpy(), False
+        if not is_tensor:
+            x = np.ascontiguousarray(data, dtype=np.float32)
+            ptr, row0 = x.ctypes.data, x[:1]
+        small = builder.train_bruteforce(row0, total_bits, metric, rotator_type, seed, use_faster_config)  # (its own checks)
+        try:
+            h = C.c_void_p()
+            _check(lib().rbq_bf_train_device(C.cast(small.hdr_ptr, C.c_void_p), ptr, int(shape[0]),
+                                             _abi.RESCALE_CONST if use_faster_config else _abi.RESCALE_OPTIMAL, small.t_const,
+                                             int(max_chunk_rows), cls._dev(device), C.byref(h)))
+            return cls(h)
+        finally:
+            small.close()
 
     @classmethod
     def from_built(cls, built, device=None):

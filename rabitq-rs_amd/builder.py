@@ -63,6 +63,8 @@ def lib():
         L.rbq_bf_built_header.argtypes = [C.c_void_p]
         L.rbq_bf_built_view.restype = C.POINTER(BfView)
         L.rbq_bf_built_view.argtypes = [C.c_void_p]
+        L.rbq_bf_built_t_const.restype = C.c_float
+        L.rbq_bf_built_t_const.argtypes = [C.c_void_p]
         L.rbq_bf_built_free.argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
@@ -236,6 +238,11 @@ class BuiltBruteForce:
     @property
     def header(self):
         return self.hdr_ptr.contents
+
+    @property
+    def t_const(self):
+        """Constant rescale factor of the faster config (0.0 when it was not used)."""
+        return float(lib().rbq_bf_built_t_const(self._h))
 
     def __len__(self):
         return int(self.view_ptr.contents.n)

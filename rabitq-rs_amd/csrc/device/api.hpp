@@ -89,6 +89,23 @@ bool spin_until(Pred pred, std::chrono::microseconds limit = std::chrono::micros
     return true;
 }
 
+// Whether a caller's buffer lives in device memory (else it is treated as host memory and copied)
+inline bool is_device_pointer(const void* p) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return a.type == hipMemoryTypeDevice;
+}
+
+// rescale: RBQ_RESCALE_CONST (t_const for every vector) or RBQ_RESCALE_OPTIMAL (k_rescale per vector; t_const ignored).
+// Returns whether the per-vector search runs (it is moot for 1-bit indexes), or -1 after fail() for an unknown mode.
+inline int rescale_mode(int rescale, const rbq_header* hdr) {
+    if (rescale != RBQ_RESCALE_CONST && rescale != RBQ_RESCALE_OPTIMAL) {
+        fail(RBQ_INVALID_CONFIG, "unknown rescale mode " + std::to_string(rescale) + " (RBQ_RESCALE_CONST or RBQ_RESCALE_OPTIMAL)");
+        return -1;
+    }
+    return rescale == RBQ_RESCALE_OPTIMAL && hdr && hdr->ex_bits > 0 ? 1 : 0;
+}
+
 // A growing scratch buffer in device memory, or (Pinned) in page-locked host memory, freed with its owner.  The owner
 // destroys it under its DeviceGuard.
 template <bool Pinned>

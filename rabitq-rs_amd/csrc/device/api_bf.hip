@@ -1,5 +1,5 @@
 // api_bf.hip — brute-force index (rbq_bf_*): BruteForceRabitqIndex, reference src/brute_force.rs.
-// Host side: validation, upload, RBF1 in / out, and per call: queries -> k_prep (rotation + QueryPrecomputed constants, shared with
+// Host side: validation, upload, training on the device (rbq_bf_train_device), RBF1 in / out, and per search call: queries -> k_prep (rotation + QueryPrecomputed constants, shared with
 // the IVF path) -> for each chunk of vectors k_bf_dist + k_bf_select (bf.hpp) -> results.  Each call takes a workspace and a stream
 // of its own from the handle's pool, so calls on one handle may overlap.
 #include "api.hpp"
@@ -13,6 +13,7 @@ constexpr uint64_t kBfDistBudget = 128ull << 20; // distance workspace of one su
 constexpr uint64_t kBfHeapBudget = 48ull << 20;  // heap workspace (between vector chunks, or for top_k above the LDS heap)
 constexpr uint64_t kBfOutBudget = 48ull << 20;   // result buffers of one sub-batch
 constexpr uint64_t kBfMaxSubBatch = 1024;
+constexpr uint64_t kBfTrainRowBudget = 512ull << 20; // rotated rows of one training pass (the IVF encoder's scratch budget)
 
 struct BfWorkspace {
     hipStream_t stream = nullptr;
@@ -83,6 +84,95 @@ int bf_create_impl(const rbq_header* hdr, const rbq_bf_view* v, int device, rbq_
     for (int k = 0; k < 8 && !rc; ++k) rc = upload_arr(ix->f[k], fs[k], n * 4);
     if (rc) { bf_free(ix.release()); return rc; }
     *out = ix.release();
+    return RBQ_OK;
+}
+
+struct BfOwner { // frees a half-built index on an early return
+    rbq_bf_index* ix;
+    ~BfOwner() { if (ix) bf_free(ix); }
+    rbq_bf_index* release() { rbq_bf_index* r = ix; ix = nullptr; return r; }
+};
+
+// BruteForceRabitqIndex::train (src/brute_force.rs:214-285) on the device, a chunk of rows at a time: k_rotate_rows ->
+// k_rescale (OPTIMAL) -> k_encode's flat mode against the zero centroid -> k_bf_pack_ex, straight into the index's arrays.
+int bf_train_impl(const rbq_header* hdr, const float* data, uint64_t n, int rescale, float t_const, uint64_t max_chunk_rows, int device,
+                  rbq_bf_index** out) {
+    if (!out) return fail(RBQ_INVALID_CONFIG, "null output");
+    *out = nullptr;
+    if (!hdr) return fail(RBQ_INVALID_CONFIG, "null header");
+    if (!data) return fail(RBQ_INVALID_CONFIG, "null data");
+    if (n == 0) return fail(RBQ_INVALID_CONFIG, "training data must be non-empty");
+    int rc = validate_header(hdr, /*brute_force=*/true);
+    if (rc) return rc;
+    if (n > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "more than 2^32 vectors");
+    const int opt = rescale_mode(rescale, hdr);
+    if (opt < 0) return RBQ_INVALID_CONFIG;
+    if (!opt && hdr->ex_bits > 0 && !(t_const > 0.0f)) return fail(RBQ_INVALID_CONFIG, "the device encoder needs the constant rescale factor (faster config)");
+    int dev = device;
+    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+    int count = 0;
+    HIP_TRY(hipGetDeviceCount(&count));
+    if (dev >= count) return fail(RBQ_INVALID_CONFIG, "no such device: " + std::to_string(dev));
+    DeviceGuard g(dev);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+
+    BfOwner own{new rbq_bf_index()};
+    rbq_bf_index* ix = own.ix;
+    static_cast<Geometry&>(*ix) = geometry_of(*hdr);
+    ix->device = dev;
+    ix->hdr = *hdr;
+    ix->hdr.n_vectors = n; ix->hdr.n_lists = 0;
+    ix->blob.assign(hdr->rotator_blob, hdr->rotator_blob + hdr->rotator_len);
+    ix->hdr.rotator_blob = ix->blob.data();
+    const uint32_t dim = ix->dim, D = ix->D, ex = ix->ex_bits;
+    const uint64_t bin_len = D / 8, ex_bytes = (uint64_t)D * ex / 8;
+    ix->ex_len = ex ? ex_bytes : D / 8; // a trained 1-bit index carries D/8 zero bytes of ex code per vector (rbq_bf_view::ex_len)
+    if ((rc = upload_arr(ix->rot_blob, ix->blob.data(), ix->blob.size())) || (rc = alloc_arr(ix->bin, n * bin_len)) ||
+        (rc = alloc_arr(ix->ex, n * ex_bytes)))
+        return rc;
+    for (Arr& a : ix->f) if ((rc = alloc_arr(a, n * 4))) return rc;
+
+    uint64_t rows = std::max<uint64_t>(64, (kBfTrainRowBudget / ((uint64_t)D * 4)) & ~63ull);
+    if (max_chunk_rows) rows = std::min(rows, max_chunk_rows);
+    rows = std::min(rows, n);
+    const bool on_device = is_device_pointer(data);
+    Scratch t;
+    float *d_in = nullptr, *d_rows = nullptr, *d_zero = nullptr;
+    uint8_t* d_raw = nullptr;
+    double* d_t = nullptr;
+    uint32_t* d_list = nullptr; // k_rescale's block -> list table: every block belongs to "list 0", the zero centroid
+    if (!on_device) HIP_TRY(t.alloc(&d_in, rows * dim * 4));
+    HIP_TRY(t.alloc(&d_rows, rows * D * 4));
+    HIP_TRY(t.alloc(&d_raw, ex ? rows * D : 16));
+    if (opt) {
+        const uint64_t nb = (rows + 31) / 32;
+        HIP_TRY(t.alloc(&d_t, rows * 8));
+        HIP_TRY(t.alloc(&d_zero, (size_t)D * 4));
+        HIP_TRY(t.alloc(&d_list, nb * 4));
+        HIP_TRY(hipMemset(d_zero, 0, (size_t)D * 4));
+        HIP_TRY(hipMemset(d_list, 0, nb * 4));
+    }
+    for (uint64_t r0 = 0; r0 < n; r0 += rows) {
+        const uint32_t nr = (uint32_t)std::min<uint64_t>(rows, n - r0);
+        const float* src = data + r0 * dim;
+        if (!on_device) {
+            HIP_TRY(hipMemcpy(d_in, src, (size_t)nr * dim * 4, hipMemcpyHostToDevice));
+            src = d_in;
+        }
+        HIP_TRY(launch_rotate_rows(src, nullptr, nr, dim, D, (int)ix->rotator, (const uint8_t*)ix->rot_blob.p, ix->trunc, ix->fac, d_rows, 0));
+        if (opt) HIP_TRY(launch_rescale(d_rows, d_zero, d_list, nullptr, nullptr, nr, D, ex, false, d_t, 0));
+        EncodeParams P;
+        P.rows = d_rows; P.centroids = nullptr; P.slot_src = nullptr; P.block_list = nullptr; P.row_slot = nullptr; P.t_row = d_t;
+        P.blocks = (uint8_t*)ix->bin.p + r0 * bin_len; P.raw_ex = d_raw; P.ids = nullptr; P.src_base = 0;
+        P.delta = (float*)ix->f[0].p + r0; P.vl = (float*)ix->f[1].p + r0; P.f_add = (float*)ix->f[2].p + r0;
+        P.f_rescale = (float*)ix->f[3].p + r0; P.f_error = (float*)ix->f[4].p + r0; P.residual_norm = (float*)ix->f[5].p + r0;
+        P.f_add_ex = (float*)ix->f[6].p + r0; P.f_rescale_ex = (float*)ix->f[7].p + r0;
+        P.nslots = nr; P.D = D; P.Dc = ix->Dc; P.ex_bits = ex; P.metric = ix->metric; P.t_const = t_const;
+        HIP_TRY(launch_bf_encode(P, 0));
+        if (ex) HIP_TRY(launch_bf_pack_ex(d_raw, nr, D, ex, (uint8_t*)ix->ex.p + r0 * ex_bytes, 0));
+        HIP_TRY(hipDeviceSynchronize()); // the scratch (and the staging copy of a host caller's rows) is reused by the next chunk
+    }
+    *out = own.release();
     return RBQ_OK;
 }
 
@@ -162,6 +252,14 @@ int rbq_bf_create(const rbq_header* hdr, const rbq_bf_view* view, int device, rb
     g_err.clear();
     RBQ_GUARD_BEGIN
     return bf_create_impl(hdr, view, device, out);
+    RBQ_GUARD_END
+}
+
+int rbq_bf_train_device(const rbq_header* hdr, const float* data, uint64_t n, int rescale, float t_const, uint64_t max_chunk_rows,
+                        int device, rbq_bf_index** out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    return bf_train_impl(hdr, data, n, rescale, t_const, max_chunk_rows, device, out);
     RBQ_GUARD_END
 }
 

@@ -83,16 +83,6 @@ int upload_block_tables(const std::vector<uint32_t>& ln, const std::vector<uint3
     return RBQ_OK;
 }
 
-// rescale: RBQ_RESCALE_CONST (t_const for every vector) or RBQ_RESCALE_OPTIMAL (k_rescale per vector; t_const ignored).
-// Returns whether the per-vector search runs (it is moot for 1-bit indexes), or -1 after fail() for an unknown mode.
-int rescale_mode(int rescale, const rbq_header* hdr) {
-    if (rescale != RBQ_RESCALE_CONST && rescale != RBQ_RESCALE_OPTIMAL) {
-        fail(RBQ_INVALID_CONFIG, "unknown rescale mode " + std::to_string(rescale) + " (RBQ_RESCALE_CONST or RBQ_RESCALE_OPTIMAL)");
-        return -1;
-    }
-    return rescale == RBQ_RESCALE_OPTIMAL && hdr && hdr->ex_bits > 0 ? 1 : 0;
-}
-
 int build_device_impl(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
                       uint64_t n, int rescale, float t_const, int dev, rbq_index** out) {
     if (!out) return fail(RBQ_INVALID_CONFIG, "null out pointer");
@@ -196,12 +186,6 @@ void free_builder(rbq_builder* b) {
     if (!b) return;
     DeviceGuard g(b->device);
     delete b;
-}
-
-bool is_device_pointer(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice;
 }
 
 

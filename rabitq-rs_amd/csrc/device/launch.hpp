@@ -7,6 +7,8 @@
 //   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver
 //   k_save.hip   RBQ1 writer: device layout -> save_to_writer's cluster bytes, CRC-32 on the GPU
 //   k_fetch.hip  fetch_embedding: id map, decode + inverse rotation of stored vectors
+//   k_bf.hip     brute-force index: distances and the BinaryHeap replay                  (bf.hpp)
+//   k_bf_train.hip  brute-force index: the encoder's flat output, ex_code_packed         (encode_vec.hpp)
 #pragma once
 #include <atomic>
 #include <string>
@@ -240,6 +242,11 @@ struct BfSelectParams {
 };
 hipError_t launch_bf_select(const BfSelectParams& p, hipStream_t s);
 constexpr uint32_t kBfLdsHeapMaxTopK = 8191; // (top_k + 1) * 8 bytes of LDS heap <= 64 KiB
+// k_bf_train.hip: BruteForceRabitqIndex::train.  launch_bf_encode: k_encode's flat mode over P.nslots rotated rows (see
+// EncodeParams; P.t_row != null: the per-vector rescale factors of launch_rescale).  launch_bf_pack_ex: raw ex codes [nrows][D]
+// u8 -> the crate's ex_code_packed [nrows][D * ex_bits / 8] (ex_bits 2 or 6)
+hipError_t launch_bf_encode(const EncodeParams& P, hipStream_t s);
+hipError_t launch_bf_pack_ex(const uint8_t* raw, uint64_t nrows, uint32_t D, uint32_t ex_bits, uint8_t* ex, hipStream_t s);
 
 // ---- k-means (k_kmeans.hip): run_kmeans_with_config on the current device, arguments already validated (rbq_kmeans_device)
 constexpr uint64_t kKmeansChunkBytes = 512ull << 20; // per-chunk assignment workspace (R rows x (4k + 4Dp + shortlist) bytes, R >= 128)

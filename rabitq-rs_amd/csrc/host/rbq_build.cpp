@@ -579,6 +579,7 @@ struct rbq_bf_built {
     std::vector<uint8_t> rotator_blob, bin, ex;
     std::vector<float> f[8]; // delta, vl, f_add, f_rescale, f_error, residual_norm, f_add_ex, f_rescale_ex
     rbq_bf_view view;
+    float t_const = 0.0f;
 };
 
 extern "C" {
@@ -612,6 +613,7 @@ int rbq_build_train_bruteforce(const float* data, uint64_t n, uint32_t dim, uint
     }
     const bool has_t = use_faster_config && ex_bits > 0;
     const float t_const = has_t ? const_scaling_factor(D, ex_bits, seed) : 0.0f;
+    b->t_const = t_const;
     const size_t bin_len = (D + 7) / 8;
     // ex_code_packed as quantize_with_centroid leaves it: D/16*2 zero bytes for 1-bit indexes (src/quantizer.rs:212-219)
     const size_t ex_len = ex_bits == 0 ? (size_t)D / 16 * 2 : (size_t)D * ex_bits / 8;
@@ -645,6 +647,7 @@ int rbq_build_train_bruteforce(const float* data, uint64_t n, uint32_t dim, uint
 }
 const rbq_header* rbq_bf_built_header(const rbq_bf_built* b) { return &b->hdr; }
 const rbq_bf_view* rbq_bf_built_view(const rbq_bf_built* b) { return &b->view; }
+float rbq_bf_built_t_const(const rbq_bf_built* b) { return b->t_const; }
 void rbq_bf_built_free(rbq_bf_built* b) { delete b; }
 
 } // extern "C"

@@ -49,6 +49,7 @@ int rbq_build_train_bruteforce(const float* data, uint64_t n, uint32_t dim, uint
                                uint8_t rotator_type, uint64_t seed, int use_faster_config, rbq_bf_built** out);
 const rbq_header*  rbq_bf_built_header(const rbq_bf_built* b);
 const rbq_bf_view* rbq_bf_built_view(const rbq_bf_built* b);
+float              rbq_bf_built_t_const(const rbq_bf_built* b); /* the faster config's constant rescale factor (0: not used) */
 void               rbq_bf_built_free(rbq_bf_built* b);
 #ifdef __cplusplus
 }
