@@ -1,0 +1,78 @@
+/*
+ * rbq_mstg.h — C ABI of the MSTG posting-list build: steps 2 and 3 of lqhl/rabitq-rs's `MstgIndex::build`
+ * (reference src/mstg/index.rs:40-110) on the device.  Closure assignment (ClosureAssigner::assign,
+ * src/mstg/closure.rs:24-107) decides which lists hold each vector; the encoder of rbq_index_build_device_ex then
+ * quantises every (vector, list) pair against the list's centroid in the raw space (PostingList::quantize_vectors,
+ * src/mstg/posting_list.rs:66-101).  The result is an ordinary rbq_index with rotator RBQ_ROTATOR_NONE, served by
+ * rbq_posting_scan_batch.  Step 1 (hierarchical balanced clustering), step 4 (HNSW over the centroids) and
+ * dynamic_prune stay with the caller.  A header of its own, not included by rbq.h.
+ */
+#ifndef RBQ_MSTG_H
+#define RBQ_MSTG_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "rbq.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RBQ_MSTG_MAX_REPLICAS 64   /* largest max_replicas served (the crate's default is 8) */
+#define RBQ_MSTG_SHORTLIST    256  /* entries per row of rbq_mstg_debug_closure_shortlist */
+
+/* ClosureAssigner{epsilon, max_replicas}.assign(row, centroids) for every row of `data`, bit for bit: distances are
+ * math::l2_distance_sqr in the order an AVX2 host takes (8 accumulators, src/math.rs:216-245), the sort is stable (equal
+ * distances keep ascending centroid index), the threshold is closest * (1.0f + epsilon) with the sum rounded first, and
+ * the RNG rule compares with a strict >.  The result equals rbq_build_closure_assign of the CPU builder.
+ *   centroids  [n_lists][dim] f32, host or device memory (detected)
+ *   data       [n][dim] f32, host or device memory (detected; host rows are copied a chunk at a time).  Any dim >= 1.
+ *   max_chunk_rows  upper bound on the rows per pass; 0 = as many as a 512 MiB workspace holds.  The result does not
+ *              depend on it.
+ *   device     HIP ordinal, -1 = the current device
+ *   out_lists  [n][max_replicas] u32, host or device memory (detected): row i holds the crate's Vec for vector i in its
+ *              order (closest list first); unused slots are UINT32_MAX.   out_counts [n] u32: the Vec's length (>= 1).
+ * Errors, all checked before the first HIP call: RBQ_INVALID_CONFIG for a null pointer, n == 0, n_lists == 0 or
+ * >= 2^32 - 1, dim == 0, n >= 2^32 - 16, max_replicas == 0 or > RBQ_MSTG_MAX_REPLICAS, epsilon negative or not finite
+ * (the crate panics on max_replicas == 0 and on a NaN distance).  A non-finite value in data or centroids is
+ * RBQ_INVALID_CONFIG too: it is found on the device, chunk by chunk, before the chunk is scored, so the rows of earlier
+ * chunks have been written by then.  After any error the contents of the outputs are unspecified.  Never aborts: device
+ * failures are RBQ_DEVICE. */
+int rbq_mstg_closure_assign(const float* centroids, uint64_t n_lists, uint32_t dim, const float* data, uint64_t n,
+                            float epsilon, uint32_t max_replicas, uint64_t max_chunk_rows, int device,
+                            uint32_t* out_lists, uint32_t* out_counts);
+
+/* MstgIndex::build steps 2 and 3: closure assignment of every row, then the posting lists.  List c holds the vectors
+ * assigned to it in ascending vector index (src/mstg/index.rs:61-66); a vector may sit in several lists; ids are the
+ * row indices.  The index equals, array for array, rbq_index_create_with_recon over the CPU builder's
+ * train_with_clusters fed the expanded (vector, list) pairs sorted by (list, vector).
+ *   hdr        dim, padded_dim == dim (a multiple of 16), metric, rotator RBQ_ROTATOR_NONE without blob, ex_bits,
+ *              n_lists = number of centroids; n_vectors is ignored
+ *   centroids  [n_lists][dim], data [n][dim]: host or device memory (detected).  Host data is uploaded whole: the
+ *              encoder gathers rows by list.
+ *   rescale    RBQ_RESCALE_CONST (t_const > 0 when ex_bits > 0: what PostingList::quantize_vectors derives with seed
+ *              42) or RBQ_RESCALE_OPTIMAL, as for rbq_index_build_device_ex
+ *   max_chunk_rows  as above; the result does not depend on it
+ * Errors as for rbq_mstg_closure_assign, plus a header that validate fails or whose rotator is not RBQ_ROTATOR_NONE,
+ * an unknown rescale mode and a missing t_const; all before the first HIP call.  One device only. */
+int rbq_mstg_build_device(const rbq_header* hdr, const float* centroids, const float* data, uint64_t n,
+                          float closure_epsilon, uint32_t max_replicas, int rescale, float t_const,
+                          uint64_t max_chunk_rows, int device, rbq_index** out);
+
+/* Diagnostic: rows, summed over every closure assignment of this process, whose shortlist could not be proven complete
+ * within RBQ_MSTG_SHORTLIST entries and that were scored exactly against every centroid instead. */
+uint64_t rbq_mstg_debug_closure_fallbacks(void);
+/* Diagnostic tap: the shortlist of every row as the closure assignment forms it, nothing else computed.  out_sl
+ * [n][RBQ_MSTG_SHORTLIST] u32 centroid indices ascending, out_sl_n [n] their number, or UINT32_MAX for a row that
+ * falls back to every centroid.  With n_lists <= RBQ_MSTG_SHORTLIST no shortlist is formed: every row lists all
+ * centroids.  Host outputs; arguments and errors as for rbq_mstg_closure_assign. */
+int rbq_mstg_debug_closure_shortlist(const float* centroids, uint64_t n_lists, uint32_t dim, const float* data, uint64_t n,
+                                     uint32_t max_replicas, uint64_t max_chunk_rows, int device, uint32_t* out_sl,
+                                     uint32_t* out_sl_n);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RBQ_MSTG_H */

@@ -10,6 +10,8 @@ Mirrors the reference's public query API for this path:
   BruteForceRabitqIndex        src/brute_force.rs (bruteforce.py)
   KMeansConfig / run_kmeans_with_config, IvfRabitqIndex.train
                                src/kmeans.rs, src/ivf.rs:950-1021 (kmeans.py)
+  closure_assign / build_postings_on_device: MstgIndex::build steps 2 and 3
+                               src/mstg/closure.rs, src/mstg/index.rs:40-110 (mstg.py)
 All compute goes through the C ABI of include/rbq.h (csrc/librbq.so, hand-written HIP for
 gfx950). There is no CPU fallback: if the HIP library is missing or no GPU is present the
 calls raise.
@@ -71,7 +73,9 @@ from .index import IvfRabitqIndex, StreamBuilder  # noqa: E402
 from . import builder  # noqa: E402,F401
 from .bruteforce import BruteForceRabitqIndex, BruteForceSearchParams, BruteForceSearchResult  # noqa: E402
 from .kmeans import KMeansConfig, KMeansResult, run_kmeans_with_config  # noqa: E402
+from .mstg import build_postings_on_device, closure_assign, closure_assign_cpu  # noqa: E402
 
 __all__ = ["Metric", "RotatorType", "RabitqError", "SearchParams", "SearchResult", "IvfRabitqIndex",
            "StreamBuilder", "builder", "BruteForceRabitqIndex", "BruteForceSearchParams", "BruteForceSearchResult",
-           "KMeansConfig", "KMeansResult", "run_kmeans_with_config"]
+           "KMeansConfig", "KMeansResult", "run_kmeans_with_config", "closure_assign", "closure_assign_cpu",
+           "build_postings_on_device"]

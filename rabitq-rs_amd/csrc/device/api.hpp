@@ -1,5 +1,5 @@
 // api.hpp — internal header of librbq.so's host side: the C ABI of include/rbq.h over the HIP kernels, which the host
-// units (api_index, api_build, api_search, api_save, api_fetch, api_bf) reach through launch.hpp.  Not installed.
+// units (api_index, api_build, api_search, api_save, api_fetch, api_bf, api_mstg) reach through launch.hpp.  Not installed.
 // Host responsibilities: validate like the reference (src/ivf.rs:1754-1769,1484-1702), upload the reference's ClusterData
 // bytes and have the GPU re-lay them into the device layout (one-time, at create/load), own HBM on one or N devices
 // (replicas), and enqueue prep -> rank -> select -> scan for each query batch.  There is no CPU compute path: every failure
@@ -411,6 +411,9 @@ int resolve_devices(int n_devices, const int* devices, std::vector<int>& out);
 Replica* new_replica(const rbq_header* hdr, int dev);
 int finish_replica(Replica* ix, const std::vector<uint32_t>& ln);
 int wrap_and_replicate(Replica* first, const std::vector<int>& devs, rbq_index** out);
+// api_build.hip: the device encoder over (vector, list) pairs (rbq_index_build_device_ex: one pair per vector; rbq_mstg_build_device)
+int build_device_pairs(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
+                       const uint32_t* d_vec, uint64_t n, int rescale, float t_const, int dev, rbq_index** out);
 
 } // namespace rbq_api
 

@@ -83,8 +83,12 @@ int upload_block_tables(const std::vector<uint32_t>& ln, const std::vector<uint3
     return RBQ_OK;
 }
 
-int build_device_impl(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
-                      uint64_t n, int rescale, float t_const, int dev, rbq_index** out) {
+} // namespace
+
+// The encoder over n (vector, list) pairs: pair j stores vector d_vec[j] (null: vector j, one list per vector) in list
+// d_assign[j].  The pairs arrive in ascending vector order, so the stable sort leaves every list in ascending vector index.
+int build_device_pairs(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
+                       const uint32_t* d_vec, uint64_t n, int rescale, float t_const, int dev, rbq_index** out) {
     if (!out) return fail(RBQ_INVALID_CONFIG, "null out pointer");
     *out = nullptr;
     int rc = validate_header(hdr);
@@ -128,17 +132,19 @@ int build_device_impl(const rbq_header* hdr, const float* centroids, const float
     {
         uint32_t *d_ko = nullptr, *d_vi = nullptr, *d_vo = nullptr;
         uint64_t* d_vstart = nullptr;
-        HIP_TRY(t.alloc(&d_ko, n * 4)); HIP_TRY(t.alloc(&d_vi, n * 4)); HIP_TRY(t.alloc(&d_vo, n * 4));
+        HIP_TRY(t.alloc(&d_ko, n * 4)); HIP_TRY(t.alloc(&d_vo, n * 4));
+        if (!d_vec) HIP_TRY(t.alloc(&d_vi, n * 4));
         HIP_TRY(t.alloc(&d_vstart, (size_t)nlist * 8));
         HIP_TRY(hipMemcpy(d_vstart, vstart.data(), (size_t)nlist * 8, hipMemcpyHostToDevice));
-        HIP_TRY(launch_iota(d_vi, n, 0));
+        if (!d_vec) HIP_TRY(launch_iota(d_vi, n, 0));
+        const uint32_t* d_src = d_vec ? d_vec : d_vi;
         unsigned bits = 1;
         while ((1ull << bits) < nlist) ++bits;
         size_t tb = 0;
-        HIP_TRY(sort_pairs_u32(nullptr, &tb, d_assign, d_ko, d_vi, d_vo, (size_t)n, bits, 0));
+        HIP_TRY(sort_pairs_u32(nullptr, &tb, d_assign, d_ko, d_src, d_vo, (size_t)n, bits, 0));
         void* d_tmp = nullptr;
         HIP_TRY(t.alloc(&d_tmp, tb));
-        HIP_TRY(sort_pairs_u32(d_tmp, &tb, d_assign, d_ko, d_vi, d_vo, (size_t)n, bits, 0));
+        HIP_TRY(sort_pairs_u32(d_tmp, &tb, d_assign, d_ko, d_src, d_vo, (size_t)n, bits, 0));
         HIP_TRY(t.alloc(&d_slot_src, nslots * 4));
         HIP_TRY(hipMemset(d_slot_src, 0xff, nslots * 4));
         HIP_TRY(launch_scatter_slots(d_ko, d_vo, n, (const uint32_t*)ix->list_gb0.p, d_vstart, d_slot_src, 0));
@@ -181,6 +187,12 @@ int build_device_impl(const rbq_header* hdr, const float* centroids, const float
     if ((rc = finish_replica(ix, ln))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     return wrap_and_replicate(own.release(), devs, out);
+}
+
+namespace {
+int build_device_impl(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
+                      uint64_t n, int rescale, float t_const, int dev, rbq_index** out) {
+    return build_device_pairs(hdr, centroids, d_data, d_assign, nullptr, n, rescale, t_const, dev, out);
 }
 void free_builder(rbq_builder* b) {
     if (!b) return;

@@ -30,19 +30,13 @@
 #include "rbq.h"
 #include "launch.hpp"
 #include "kernels.hpp"
+#include "km_common.hpp"
 #include "../host/rbq_rng.h"
 
 namespace rbq {
 
-constexpr uint32_t kShortlist = 256;           // shortlist capacity per row (k_km_scan)
-constexpr uint32_t kFallbackMark = 0xffffffffu; // sl_n value of a row k_km_exact scores against every cluster
 constexpr uint32_t kCands = 8;                 // RESEED_CANDIDATES (src/kmeans.rs)
 
-__device__ __forceinline__ float km_norm(const float* __restrict__ x, uint32_t dim) {
-    float s = 0.0f;
-    for (uint32_t j = 0; j < dim; ++j) { const float p = x[j] * x[j]; s = s + p; }
-    return s;
-}
 // canonical distance: sequential unfused dot in coordinate order, (nx + nc) - 2 dot, clamped to 0
 __device__ __forceinline__ float km_canon(const float* __restrict__ x, const float* __restrict__ c, uint32_t dim, float nx, float nc) {
     float s = 0.0f;
@@ -50,41 +44,6 @@ __device__ __forceinline__ float km_canon(const float* __restrict__ x, const flo
     float d = (nx + nc) - 2.0f * s;
     if (d < 0.0f) d = 0.0f;
     return d;
-}
-
-// any non-finite value in x[0, count) sets *bad
-__global__ __launch_bounds__(256) void k_km_nonfinite(const float* __restrict__ x, uint64_t count, uint32_t* __restrict__ bad) {
-    bool b = false;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256u) b |= !isfinite(x[i]);
-    if (__any(b) && (threadIdx.x & 63u) == 0) atomicOr(bad, 1u);
-}
-
-__global__ __launch_bounds__(256) void k_km_norms(const float* __restrict__ x, uint64_t rows, uint32_t dim, float* __restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i < rows) out[i] = km_norm(x + i * dim, dim);
-}
-
-// rows [0, nr) of x ([.][dim]) as bf16 hi / lo [nr][Dp], zero beyond dim
-__global__ __launch_bounds__(256) void k_km_split(const float* __restrict__ x, uint32_t nr, uint32_t dim, uint32_t Dp,
-                                                  uint16_t* __restrict__ hi, uint16_t* __restrict__ lo) {
-    const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (e >= (uint64_t)nr * Dp) return;
-    const uint64_t r = e / Dp;
-    const uint32_t j = (uint32_t)(e - r * Dp);
-    uint16_t h = 0, l = 0;
-    if (j < dim) bf16_split(x[r * dim + j], h, l);
-    hi[e] = h;
-    lo[e] = l;
-}
-
-// centroid norms (lane per cluster) and their maximum (bit pattern of a non-negative float; reset to 0 by the caller)
-__global__ __launch_bounds__(256) void k_km_cnorms(const float* __restrict__ cent, uint32_t k, uint32_t dim, float* __restrict__ nc,
-                                                   uint32_t* __restrict__ ncmax_bits) {
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-    if (c >= k) return;
-    const float v = km_norm(cent + (size_t)c * dim, dim);
-    nc[c] = v;
-    atomicMax(ncmax_bits, __float_as_uint(v));
 }
 
 // one wavefront per row of the chunk: Amin, eps, shortlist (ascending cluster order) or the fallback mark
@@ -269,25 +228,6 @@ __global__ __launch_bounds__(64) void k_km_sum64(const double* __restrict__ v, u
 }
 
 namespace {
-
-#define KM_TRY(expr)                                                                                                     \
-    do {                                                                                                                 \
-        hipError_t _e = (expr);                                                                                          \
-        if (_e != hipSuccess) { detail = std::string(#expr) + ": " + hipGetErrorString(_e); return RBQ_DEVICE; }          \
-    } while (0)
-
-struct KmTemp { // device workspace freed on scope exit
-    std::vector<void*> ptrs;
-    template <class T> hipError_t alloc(T** p, size_t elems) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, elems ? elems * sizeof(T) : 16);
-        if (e == hipSuccess) { ptrs.push_back(q); *p = (T*)q; }
-        return e;
-    }
-    ~KmTemp() { for (void* p : ptrs) (void)hipFree(p); }
-};
-
-inline unsigned grid_of(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 void km_shuffle(std::vector<uint32_t>& v, rbq_host::Rng& rng) {
     for (size_t i = v.size(); i-- > 1;) std::swap(v[i], v[rng.next() % (i + 1)]);

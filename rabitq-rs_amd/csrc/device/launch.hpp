@@ -9,6 +9,7 @@
 //   k_fetch.hip  fetch_embedding: id map, decode + inverse rotation of stored vectors
 //   k_bf.hip     brute-force index: distances and the BinaryHeap replay                  (bf.hpp)
 //   k_bf_train.hip  brute-force index: the encoder's flat output, ex_code_packed         (encode_vec.hpp)
+//   k_mstg.hip   MSTG closure assignment (ClosureAssigner::assign) and its host driver       (km_common.hpp)
 #pragma once
 #include <atomic>
 #include <string>
@@ -264,6 +265,29 @@ struct KMeansArgs {
     uint64_t* stats;        // host [4] or null: shortlist fallbacks, empty clusters reseeded, RNG draws, largest shortlist
 };
 int kmeans_device(const KMeansArgs& a, std::string& detail); // RBQ_* code; detail on failure
+
+// ---- MSTG closure assignment (k_mstg.hip): ClosureAssigner::assign of every row, arguments already validated
+constexpr uint32_t kMstgMaxReplicas = 64;
+struct ClosureArgs {
+    const float* centroids; // [k][dim], host or device (cent_on_device)
+    uint64_t k;
+    uint32_t dim;
+    const float* data;      // [n][dim], host or device (data_on_device)
+    uint64_t n;
+    float epsilon;
+    uint32_t max_replicas;
+    uint64_t max_chunk_rows; // 0 = by the workspace budget
+    bool cent_on_device, data_on_device, out_on_device;
+    uint32_t* out_lists;    // [n][max_replicas] (unused slots UINT32_MAX) and [n]; null with a tap
+    uint32_t* out_counts;
+    uint32_t* tap_sl;       // host, null or [n][kShortlist] / [n]: the shortlists only (rbq_mstg_debug_closure_shortlist)
+    uint32_t* tap_sl_n;
+    uint64_t* fallbacks;    // host out: rows scored against every centroid
+};
+int closure_device(const ClosureArgs& a, int device, std::string& detail); // RBQ_* code; detail on failure
+// (vector, list) pairs of the closure in vector-major order: pair off[i] + j = (i, lists[i][j]) for j < counts[i]
+hipError_t launch_closure_expand(const uint32_t* lists, const uint32_t* counts, const uint32_t* off, uint64_t n, uint32_t max_replicas,
+                                 uint32_t* pair_list, uint32_t* pair_vec, hipStream_t s);
 
 // ---- RBQ1 writer (k_save.hip): words [w0, w0 + nw) of the cluster section of the stream, into out[0, nw)
 struct SaveParams {

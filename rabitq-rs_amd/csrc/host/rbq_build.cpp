@@ -856,3 +856,59 @@ int rbq_build_kmeans_faiss(const float* data, uint64_t n, uint32_t dim, uint64_t
 }
 
 } // extern "C"
+
+// ---------------------------------------------------------------- MSTG closure assignment (src/mstg/closure.rs:24-107)
+namespace {
+// math::l2_distance_sqr, AVX2 lane order (src/math.rs:216-245)
+float l2_sqr8(const float* a, const float* b, size_t len) {
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    size_t chunks = len / 8, i = 0;
+    for (; i < chunks * 8; i += 8)
+        for (int l = 0; l < 8; ++l) { float d = a[i + l] - b[i + l]; float p = d * d; acc[l] = acc[l] + p; }
+    float sum = 0.0f;
+    if (chunks) { sum = -0.0f; for (int l = 0; l < 8; ++l) sum = sum + acc[l]; }
+    for (; i < len; ++i) { float d = a[i] - b[i]; float p = d * d; sum = sum + p; }
+    return sum;
+}
+} // namespace
+
+extern "C" {
+
+int rbq_build_closure_assign(const float* centroids, uint64_t n_lists, uint32_t dim, const float* data, uint64_t n, float epsilon,
+                             uint32_t max_replicas, uint32_t* out_lists, uint32_t* out_counts) {
+    if (!centroids || !data || !out_lists || !out_counts) return RBQ_INVALID_CONFIG;
+    if (n == 0 || n_lists == 0 || dim == 0 || n_lists >= 0xffffffffull) return RBQ_INVALID_CONFIG;
+    if (max_replicas == 0 || !(epsilon >= 0.0f) || !std::isfinite(epsilon)) return RBQ_INVALID_CONFIG;
+    const size_t take = (size_t)std::min<uint64_t>(max_replicas, n_lists);
+#pragma omp parallel
+    {
+        std::vector<std::pair<float, uint32_t>> d(n_lists);
+        std::vector<uint32_t> cand, kept;
+#pragma omp for schedule(dynamic, 64)
+        for (int64_t i = 0; i < (int64_t)n; ++i) {
+            const float* x = data + (size_t)i * dim;
+            for (uint64_t c = 0; c < n_lists; ++c) d[c] = {l2_sqr8(x, centroids + (size_t)c * dim, dim), (uint32_t)c};
+            // the first `take` entries of the stable sort: (distance, index) ascending
+            std::partial_sort(d.begin(), d.begin() + take, d.end());
+            const float one_eps = 1.0f + epsilon;
+            const float threshold = d[0].first * one_eps;
+            cand.clear();
+            for (size_t r = 0; r < take; ++r)
+                if (d[r].first <= threshold) cand.push_back((uint32_t)r);
+            kept.clear();
+            for (uint32_t r : cand) { // RNG rule against the clusters kept so far
+                bool keep = true;
+                for (uint32_t s : kept)
+                    if (d[r].first > l2_sqr8(centroids + (size_t)d[s].second * dim, centroids + (size_t)d[r].second * dim, dim)) { keep = false; break; }
+                if (keep) kept.push_back(r);
+            }
+            // (the closest cluster is cand[0], which the loop always keeps: closure.rs:102-104 changes nothing)
+            uint32_t* o = out_lists + (size_t)i * max_replicas;
+            for (uint32_t r = 0; r < max_replicas; ++r) o[r] = r < kept.size() ? d[kept[r]].second : 0xffffffffu;
+            out_counts[i] = (uint32_t)kept.size();
+        }
+    }
+    return RBQ_OK;
+}
+
+} // extern "C"

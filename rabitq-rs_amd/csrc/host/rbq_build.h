@@ -51,6 +51,15 @@ const rbq_header*  rbq_bf_built_header(const rbq_bf_built* b);
 const rbq_bf_view* rbq_bf_built_view(const rbq_bf_built* b);
 float              rbq_bf_built_t_const(const rbq_bf_built* b); /* the faster config's constant rescale factor (0: not used) */
 void               rbq_bf_built_free(rbq_bf_built* b);
+
+/* ClosureAssigner::assign (reference src/mstg/closure.rs:24-107) for every row of data [n][dim] against centroids
+ * [n_lists][dim]: the parity yardstick of rbq_mstg_closure_assign (include/rbq_mstg.h), OpenMP over the rows.  Distances
+ * are math::l2_distance_sqr in its AVX2 order; the sort is stable (equal distances keep ascending centroid index).
+ * out_lists [n][max_replicas] (unused slots UINT32_MAX, the crate's Vec order), out_counts [n].
+ * RBQ_INVALID_CONFIG: a null pointer, n == 0, n_lists == 0, dim == 0, max_replicas == 0, epsilon negative or not finite
+ * (the crate panics on the last two).  Non-finite data is not checked: the result is then unspecified. */
+int rbq_build_closure_assign(const float* centroids, uint64_t n_lists, uint32_t dim, const float* data, uint64_t n,
+                             float epsilon, uint32_t max_replicas, uint32_t* out_lists, uint32_t* out_counts);
 #ifdef __cplusplus
 }
 #endif

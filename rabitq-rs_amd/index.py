@@ -142,6 +142,18 @@ def lib():
         L.rbq_index_fetch_embeddings.argtypes = [vp, vp, C.c_uint64, vp, vp]
         L.rbq_index_fetch_embeddings_device.restype = C.c_int
         L.rbq_index_fetch_embeddings_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+        # rbq_mstg.h
+        L.rbq_mstg_closure_assign.restype = C.c_int
+        L.rbq_mstg_closure_assign.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint64, C.c_int,
+                                              vp, vp]
+        L.rbq_mstg_build_device.restype = C.c_int
+        L.rbq_mstg_build_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_int, C.c_float, C.c_uint64, C.c_int,
+                                            C.POINTER(vp)]
+        L.rbq_mstg_debug_closure_fallbacks.restype = C.c_uint64
+        L.rbq_mstg_debug_closure_fallbacks.argtypes = []
+        L.rbq_mstg_debug_closure_shortlist.restype = C.c_int
+        L.rbq_mstg_debug_closure_shortlist.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int,
+                                                       vp, vp]
         _LIB = L
     return _LIB
 

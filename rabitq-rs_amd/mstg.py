@@ -1,0 +1,129 @@
+"""MSTG posting-list build, steps 2 and 3 of `MstgIndex::build` (reference src/mstg/index.rs:40-110), on the GPU
+(include/rbq_mstg.h): closure assignment with the RNG rule (`ClosureAssigner::assign`, src/mstg/closure.rs) and the posting
+lists of the expanded (vector, list) pairs.
+
+The arithmetic is the crate's on an AVX2 host; `closure_assign_cpu` (csrc/host/rbq_build.cpp) restates it on the CPU and the
+device result equals it exactly.  Clustering, HNSW and dynamic_prune stay with the caller."""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+
+NONE = 0xFFFFFFFF  # unused slot of a closure row
+
+
+def _host_f32(a):
+    if hasattr(a, "detach"):  # a torch tensor
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _shapes(data, centroids):
+    from . import RabitqError
+    if len(data.shape) != 2 or len(centroids.shape) != 2 or data.shape[1] != centroids.shape[1]:
+        raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data [n][dim], centroids [n_lists][dim]")
+    return int(data.shape[0]), int(centroids.shape[0]), int(data.shape[1])
+
+
+def _ptr(a, device):
+    """(pointer, keep-alive) of a [rows][dim] f32 array: a CUDA tensor is used in place, anything else is host memory."""
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    if torch is not None and isinstance(a, torch.Tensor):
+        if a.is_cuda:
+            t = a.to(dtype=torch.float32).contiguous()
+            return C.c_void_p(t.data_ptr()), t
+        a = a.numpy()
+    h = np.ascontiguousarray(a, dtype=np.float32)
+    return C.c_void_p(h.ctypes.data), h
+
+
+def closure_assign_cpu(data, centroids, epsilon, max_replicas):
+    """`ClosureAssigner::new(epsilon, max_replicas).assign(row, centroids)` for every row, on the CPU (OpenMP over the rows):
+    (lists [n][max_replicas] u32 in the crate's Vec order with NONE in unused slots, counts [n] u32)."""
+    from . import RabitqError, builder
+    x, c = _host_f32(data), _host_f32(centroids)
+    n, k, dim = _shapes(x, c)
+    lists = np.empty((n, max(int(max_replicas), 0)), np.uint32)
+    counts = np.empty(n, np.uint32)
+    rc = builder.lib().rbq_build_closure_assign(c.ctypes.data, k, dim, x.ctypes.data, n, float(epsilon), int(max_replicas),
+                                                lists.ctypes.data, counts.ctypes.data)
+    if rc != _abi.RBQ_OK:
+        raise RabitqError(rc, "closure assignment rejected its configuration")
+    return lists, counts
+
+
+def closure_assign(data, centroids, epsilon, max_replicas, device=None, max_chunk_rows=0):
+    """The same on the GPU (rbq_mstg_closure_assign).  `data` and `centroids` are NumPy arrays (host rows are copied a chunk at a
+    time) or CUDA tensors (used in place).  Returns host arrays equal to closure_assign_cpu's."""
+    from .index import _check, lib
+    n, k, dim = _shapes(data, centroids)
+    dev = -1 if device is None else int(device)
+    xp, _x = _ptr(data, dev)
+    cp, _c = _ptr(centroids, dev)
+    lists = np.empty((n, max(int(max_replicas), 0)), np.uint32)
+    counts = np.empty(n, np.uint32)
+    _check(lib().rbq_mstg_closure_assign(cp, k, dim, xp, n, float(epsilon), int(max_replicas), int(max_chunk_rows), dev,
+                                         lists.ctypes.data, counts.ctypes.data))
+    return lists, counts
+
+
+def closure_fallbacks():
+    """Rows of every closure assignment so far that were scored against every centroid (rbq_mstg_debug_closure_fallbacks)."""
+    from .index import lib
+    return int(lib().rbq_mstg_debug_closure_fallbacks())
+
+
+def debug_closure_shortlist(data, centroids, max_replicas, device=None, max_chunk_rows=0):
+    """Test hook (rbq_mstg_debug_closure_shortlist): (sl [n][256] u32, sl_n [n] u32; sl_n NONE = the row falls back)."""
+    from .index import _check, lib
+    n, k, dim = _shapes(data, centroids)
+    dev = -1 if device is None else int(device)
+    xp, _x = _ptr(data, dev)
+    cp, _c = _ptr(centroids, dev)
+    sl = np.empty((n, 256), np.uint32)
+    sl_n = np.empty(n, np.uint32)
+    _check(lib().rbq_mstg_debug_closure_shortlist(cp, k, dim, xp, n, int(max_replicas), int(max_chunk_rows), dev, sl.ctypes.data,
+                                                  sl_n.ctypes.data))
+    return sl, sl_n
+
+
+def expand_pairs(lists, counts):
+    """(pair_vec, pair_list) of a closure, sorted by (list, vector): the order the posting lists hold them in."""
+    lists, counts = np.asarray(lists), np.asarray(counts)
+    keep = np.arange(lists.shape[1])[None, :] < counts[:, None]
+    vec = np.broadcast_to(np.arange(lists.shape[0], dtype=np.int64)[:, None], lists.shape)[keep]
+    lst = lists[keep].astype(np.int64)
+    order = np.lexsort((vec, lst))
+    return vec[order], lst[order].astype(np.uint32)
+
+
+def build_postings_on_device(data, centroids, total_bits, metric, closure_epsilon=0.15, max_replicas=8, faster_config=False,
+                             device=None, max_chunk_rows=0):
+    """MstgIndex::build steps 2 and 3 on the GPU (rbq_mstg_build_device): an IvfRabitqIndex handle with rotator NoRotation that
+    `posting_scan` serves; list c holds its vectors in ascending index, ids are the row indices.  The header, and t_const for
+    `faster_config` (what PostingList::quantize_vectors derives with seed 42), come from the CPU builder over one row: both
+    depend on (dim, bits, seed) only, and the copy of the header that is handed over names all the lists."""
+    from . import RabitqError, RotatorType, builder
+    from .index import IvfRabitqIndex, _check, _rescale, lib
+    n, k, dim = _shapes(data, centroids)
+    dev = -1 if device is None else int(device)
+    xp, _x = _ptr(data, dev)
+    cent = _host_f32(centroids)
+    if n == 0 or k == 0:
+        raise RabitqError(_abi.RBQ_INVALID_CONFIG, "data and centroids must be non-empty")
+    small = builder.train_with_clusters(cent[:1], cent[:1], np.zeros(1, np.uint32), total_bits, metric, RotatorType.NoRotation, 42, True)
+    try:
+        hdr = _abi.Header.from_buffer_copy(small.header)  # (NoRotation: no rotator blob to keep alive)
+        t_const = small.t_const
+    finally:
+        small.close()
+    hdr.n_lists, hdr.n_vectors = k, 0
+    mode, t = _rescale("const" if faster_config else "optimal", t_const if faster_config else None)
+    h = C.c_void_p()
+    _check(lib().rbq_mstg_build_device(C.byref(hdr), cent.ctypes.data, xp, n, float(closure_epsilon), int(max_replicas), mode, t,
+                                       int(max_chunk_rows), dev, C.byref(h)))
+    return IvfRabitqIndex(h)
