@@ -4,8 +4,10 @@
  * src/mstg/closure.rs:24-107) decides which lists hold each vector; the encoder of rbq_index_build_device_ex then
  * quantises every (vector, list) pair against the list's centroid in the raw space (PostingList::quantize_vectors,
  * src/mstg/posting_list.rs:66-101).  The result is an ordinary rbq_index with rotator RBQ_ROTATOR_NONE, served by
- * rbq_posting_scan_batch.  Step 1 (hierarchical balanced clustering), step 4 (HNSW over the centroids) and
- * dynamic_prune stay with the caller.  A header of its own, not included by rbq.h.
+ * rbq_posting_scan_batch, and by rbq_mstg_search_batch below, which answers `MstgIndex::search` / `batch_search`
+ * (src/mstg/index.rs:149-213, 340-346) in one call: the centroid ranking and dynamic_prune run on the device too.
+ * Step 1 (hierarchical balanced clustering) and step 4 (HNSW over the centroids) stay with the caller; step 4 is not
+ * needed for searching through this library.  A header of its own, not included by rbq.h (DESIGN.md sections 15, 16).
  */
 #ifndef RBQ_MSTG_H
 #define RBQ_MSTG_H
@@ -70,6 +72,60 @@ uint64_t rbq_mstg_debug_closure_fallbacks(void);
 int rbq_mstg_debug_closure_shortlist(const float* centroids, uint64_t n_lists, uint32_t dim, const float* data, uint64_t n,
                                      uint32_t max_replicas, uint64_t max_chunk_rows, int device, uint32_t* out_sl,
                                      uint32_t* out_sl_n);
+
+/* MstgIndex::search for every query, in one call: the centroid search, dynamic_prune and the posting-list scan.
+ *
+ * The selection.  The crate's candidate lists come from an HNSW built by parallel_insert: approximate, and different
+ * from run to run.  This call returns what that HNSW approximates, the exact ef_search nearest centroids.  Per query:
+ *  1. S(c) = math::l2_distance_sqr(query, centroid c) in the AVX2 order, the value rbq_posting_scan_batch takes g_add
+ *     from.  L2 for both metrics, as the crate's centroid index (DistL2, src/mstg/hnsw.rs:91-97), on the full-precision
+ *     centroids of the handle.
+ *  2. The centroids are ordered by (bit pattern of S, centroid index) ascending and the first
+ *     ef = min(ef_search, n_lists) are kept.  This refines the crate's order by sqrtf(S): where two different S round
+ *     to one square root the HNSW's order is unspecified anyway.
+ *  3. d(c) = sqrtf(S(c)) correctly rounded, thr = d(first) * (1.0f + pruning_epsilon) in f32 with the sum rounded
+ *     first (dynamic_prune, src/mstg/index.rs:349-362); a candidate is kept while d(c) <= thr, which is a prefix.
+ *     No pruning_epsilon is rejected: a negative one can prune even the closest list and NaN prunes every list, as
+ *     the crate's comparison does.  The one deliberate rule: when any S(c) of a query is NaN, or its smallest S is
+ *     +inf, nothing is selected (the HNSW's behaviour there is undefined).
+ *  4. The kept lists are scanned in that order exactly as rbq_posting_scan_batch scans a caller's lists: binary
+ *     estimate only, g_add = S (L2) or the canonical -dot (inner product), non-finite estimates dropped, L2 estimates
+ *     clamped to >= 0, the smallest top_k kept, the earlier candidate in (list order, vector order) winning a tie;
+ *     distances are reported for both metrics.
+ *  5. ef_search == 0 or top_k == 0: RBQ_OK with every count 0.  Empty lists contribute nothing.
+ * The result equals rbq_build_mstg_select_lists of the CPU builder followed by rbq_posting_scan_batch, bit for bit.
+ *
+ *   queries     [nq][query_dim] f32, host memory; cut into chunks that keep the work list and the score matrix inside
+ *               a fixed workspace (1 GiB); the result does not depend on the chunking
+ *   out_ids     [nq][top_k] u64, out_scores [nq][top_k] f32 ascending, out_counts [nq] u32; unused slots are
+ *               UINT64_MAX / NaN
+ *   out_list_ids [nq][min(ef_search, n_lists)] u32: the selected lists in scan order, unused slots UINT32_MAX;
+ *   out_list_counts [nq] u32: how many.  Either may be NULL.
+ * Every ef_search and every n_lists the handle can hold is served.  Handles of up to RBQ_MSTG_SHORTLIST lists score
+ * every centroid exactly; larger ones take a GEMM shortlist that is rescored exactly, and a query
+ * whose shortlist cannot be proven complete within RBQ_MSTG_SEARCH_SHORTLIST entries is scored against every centroid
+ * and counted (rbq_mstg_debug_search_fallbacks), never approximated.
+ * Errors, all checked before the first HIP call, in this order: a null index; RBQ_EMPTY_INDEX; RBQ_DIMENSION_MISMATCH;
+ * RBQ_INVALID_CONFIG for an index whose rotator is not RBQ_ROTATOR_NONE; (nq == 0 is RBQ_OK;) RBQ_INVALID_CONFIG for a
+ * null queries / out_counts, a null out_ids / out_scores unless top_k == 0 (they then hold no element), or
+ * top_k > 2^20.  One device: the first replica serves the call. */
+#define RBQ_MSTG_SEARCH_SHORTLIST 2048
+int rbq_mstg_search_batch(const rbq_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                          uint32_t ef_search, float pruning_epsilon, uint64_t* out_ids, float* out_scores,
+                          uint32_t* out_counts, uint32_t* out_list_ids, uint32_t* out_list_counts);
+
+/* The same on device pointers, enqueued on the caller's stream without host synchronisation, under the conventions of
+ * rbq_search_batch_device: one workspace per (index, stream), released by rbq_release_stream; calls on one stream are
+ * stream-ordered.  The first call on a handle of more than RBQ_MSTG_SHORTLIST lists prepares the centroid images and
+ * waits for them once.  d_out_list_ids / d_out_list_counts may be NULL. */
+int rbq_mstg_search_batch_device(const rbq_index* idx, const float* d_queries, uint64_t nq, uint32_t query_dim,
+                                 uint32_t top_k, uint32_t ef_search, float pruning_epsilon, uint64_t* d_out_ids,
+                                 float* d_out_scores, uint32_t* d_out_counts, uint32_t* d_out_list_ids,
+                                 uint32_t* d_out_list_counts, void* hip_stream);
+
+/* Diagnostic: queries, summed over every MSTG search of this process, that were scored against every centroid because
+ * their shortlist could not be proven complete.  Waits for the devices' work. */
+uint64_t rbq_mstg_debug_search_fallbacks(void);
 
 #ifdef __cplusplus
 }

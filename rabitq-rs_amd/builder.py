@@ -69,6 +69,9 @@ def lib():
         L.rbq_build_closure_assign.restype = C.c_int
         L.rbq_build_closure_assign.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_float, C.c_uint32,
                                                C.c_void_p, C.c_void_p]
+        L.rbq_build_mstg_select_lists.restype = C.c_int
+        L.rbq_build_mstg_select_lists.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float,
+                                                  C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 

@@ -244,6 +244,7 @@ using ReplicaPool = WorkerPool<std::function<void()>, 2>;
 struct Workspace {
     hipStream_t stream = nullptr;
     DevBuf queries, rot, lut, consts, scores, probe, wl, nstream, nvec, out_pack, filter, rot_hi, rot_lo, dead_skipped, heap_ws, key_window, audit_dead, tie_log, head_ub;
+    DevBuf ms_sl, ms_lists; // rbq_mstg_search_batch*: shortlists | their lengths | query norms; the selected lists | their counts
     PinBuf h_in, h_out;      // rbq_search_batch: staging of one sub-batch
     hipEvent_t done = nullptr; // results of the sub-batch in flight have reached h_out / the caller's buffers
     uint64_t call_nq = 0;       // queries of the WHOLE host call this launch chain belongs to (0: a device-entry call — its own nq counts)
@@ -351,6 +352,7 @@ struct Options {
                                   // pipelined run 2-3 %, bench.py collects them in a pass of their own)
     uint64_t save_chunk = 0;  // TEST ONLY: staging chunk of rbq_index_save_rbq1_stream in bytes (0 = default)
     uint64_t fetch_chunk = 0; // TEST ONLY: ids per staging chunk of rbq_index_fetch_embeddings (0 = default)
+    uint64_t mstg_search_budget = 0; // TEST ONLY: per-chunk workspace of rbq_mstg_search_batch* in bytes (0 = default)
     // option `name` := value (the options of rbq_debug_set_option that live in Options); RBQ_INVALID_CONFIG for an unknown name
     int set(const char* name, int value);
 };
@@ -372,6 +374,11 @@ struct Replica : Geometry {
     std::mutex fetch_mu;
     Arr fmap_ids, fmap_slots;
     bool fmap_ready = false;
+    // rbq_mstg_search_batch*: split-bf16 images of the centroids (padded to 32), their norms | largest norm | non-finite flag; built
+    // by the first search that takes the GEMM shortlist, under `mu`, kept until destroy (not in `arrays`: built per replica)
+    Arr ms_hi, ms_lo, ms_nc;
+    bool ms_ready = false;
+    uint32_t ms_bad = 0;
     float cnorm2_max = 0.0f;
     uint64_t n_raw = 0;      // raw vectors attached for the optional rerank
     bool raw_borrowed = false;

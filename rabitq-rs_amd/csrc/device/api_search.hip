@@ -1,6 +1,7 @@
 // api_search.hip — search: the device entry, the host entry (rbq_search_batch, one replica or N), the MSTG posting-list
-// scan.  The hot path (search_host -> search_device -> scan_stage) stays in this one unit.
+// scan and the MSTG search in one call (rbq_mstg_search_batch*, include/rbq_mstg.h).  The hot path (search_host -> search_device -> scan_stage) stays in this one unit.
 #include "api.hpp"
+#include "rbq_mstg.h"
 
 using namespace rbq_api;
 
@@ -475,6 +476,138 @@ int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_d
     return RBQ_OK;
 }
 
+// ---- MSTG search (include/rbq_mstg.h): centroid ranking and dynamic_prune on the device, then the posting-list scan -------
+constexpr uint64_t kMstgSearchBudget = 1ull << 30; // per-chunk workspace of rbq_mstg_search_batch* (option mstg_search_budget)
+std::mutex g_ms_mu;
+unsigned long long* g_ms_fallbacks[16] = {}; // per device: queries scored against every centroid (never freed)
+
+// the counter of the current device `dev`
+int ms_fallback_counter(int dev, unsigned long long** out) {
+    std::lock_guard<std::mutex> lk(g_ms_mu);
+    if (dev < 0 || dev >= 16) return fail(RBQ_DEVICE, "device ordinal out of range");
+    if (!g_ms_fallbacks[dev]) {
+        unsigned long long* p = nullptr;
+        HIP_TRY(hipMalloc(&p, 8));
+        if (hipMemset(p, 0, 8) != hipSuccess) { (void)hipFree(p); return fail(RBQ_DEVICE, "hipMemset failed"); }
+        g_ms_fallbacks[dev] = p;
+    }
+    *out = g_ms_fallbacks[dev];
+    return RBQ_OK;
+}
+
+// split-bf16 images and norms of the centroids, once per replica (the first search that takes the GEMM shortlist)
+int ms_prepare(Replica* ix) {
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->ms_ready) return RBQ_OK;
+    const uint32_t k = (uint32_t)ix->n_lists, Dp = mstg_select_dp(ix->D);
+    int rc;
+    if ((rc = alloc_arr(ix->ms_hi, (size_t)k * Dp * 2))) return rc;
+    if ((rc = alloc_arr(ix->ms_lo, (size_t)k * Dp * 2))) return rc;
+    if ((rc = alloc_arr(ix->ms_nc, (size_t)k * 4 + 8))) return rc; // nc [k] | ncmax bits | bad
+    uint32_t* aux = (uint32_t*)ix->ms_nc.p + k;
+    HIP_TRY(launch_mstg_centroid_prep((const float*)ix->centroids.p, k, ix->D, (float*)ix->ms_nc.p, aux, aux + 1, (uint16_t*)ix->ms_hi.p,
+                                      (uint16_t*)ix->ms_lo.p, nullptr));
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpy(&bad, aux + 1, 4, hipMemcpyDeviceToHost));
+    ix->ms_bad = bad;
+    ix->ms_ready = true;
+    return RBQ_OK;
+}
+
+struct MstgShape {
+    uint32_t ef;        // min(ef_search, n_lists) >= 1: the stride of the list rows
+    uint64_t wl_stride; // the ef longest lists together, in blocks
+    uint64_t chunk;     // queries per pass
+};
+
+// The chunk keeps the work list and the score matrix inside the budget; the result does not depend on it.
+MstgShape ms_shape(const Replica* ix, uint64_t nq, uint32_t top_k, uint32_t ef_search, bool host) {
+    MstgShape sh;
+    const uint64_t k = ix->n_lists;
+    sh.ef = (uint32_t)std::min<uint64_t>(ef_search, k);
+    sh.wl_stride = std::max<uint64_t>(ix->nblk_desc_prefix[sh.ef], 1);
+    uint64_t per = (uint64_t)ix->D * 4 + (uint64_t)ix->Dc * 4 + sizeof(QueryConsts) + (uint64_t)sh.ef * (4 + sizeof(ProbeInfo)) +
+                   sh.wl_stride * sizeof(StreamItem) + (uint64_t)top_k * 12 + 16;
+    if (host) per += (uint64_t)ix->dim * 4;
+    if (mstg_select_gemm(k, ix->D)) per += 4 * k + 4ull * mstg_select_dp(ix->D) + 4ull * kMsCap + 8;
+    else if (k > RBQ_MSTG_SHORTLIST) per += 4;
+    per += 8ull * mstg_select_knp2(k);
+    const uint64_t budget = ix->opt.mstg_search_budget ? ix->opt.mstg_search_budget : kMstgSearchBudget;
+    sh.chunk = std::min<uint64_t>(std::min<uint64_t>(std::max<uint64_t>(budget / per, 1), 16384), nq);
+    return sh;
+}
+
+// n queries at d_q (device), everything enqueued on `stream`; d_lists [n][sh.ef] and d_lcnt [n] receive the selection
+int ms_chunk(Replica* ix, Workspace* w, const float* d_q, uint64_t n, uint32_t top_k, uint32_t ef_search, float pruning_epsilon,
+             const MstgShape& sh, unsigned long long* d_fallbacks, uint64_t* d_ids, float* d_scores, uint32_t* d_counts, uint32_t* d_lists,
+             uint32_t* d_lcnt, hipStream_t stream) {
+    int rc;
+    const uint32_t D = ix->D, Dc = ix->Dc, k = (uint32_t)ix->n_lists, Dp = mstg_select_dp(D);
+    const bool gemm = mstg_select_gemm(k, D);
+    const uint64_t np = (n + 127) / 128 * 128; // (the GEMM's row tiles)
+    if ((rc = w->rot.ensure(n * D * 4))) return rc;
+    if ((rc = w->lut.ensure(n * (size_t)Dc * 4))) return rc;
+    if ((rc = w->consts.ensure(n * sizeof(QueryConsts)))) return rc;
+    if ((rc = w->probe.ensure(n * (size_t)sh.ef * sizeof(ProbeInfo)))) return rc;
+    if ((rc = w->wl.ensure(n * sh.wl_stride * sizeof(StreamItem)))) return rc;
+    if ((rc = w->nstream.ensure(n * 4))) return rc;
+    if ((rc = w->ms_sl.ensure(n * ((size_t)(gemm ? kMsCap : 0) + 2) * 4))) return rc; // sl [n][kMsCap] | sl_n [n] | nx [n]
+    if (gemm) {
+        if ((rc = w->scores.ensure(np * (size_t)k * 4))) return rc;
+        if ((rc = w->rot_hi.ensure(np * (size_t)Dp * 2))) return rc;
+        if ((rc = w->rot_lo.ensure(np * (size_t)Dp * 2))) return rc;
+    }
+    const uint32_t knp2 = mstg_select_knp2(k);
+    if (knp2 && (rc = w->key_window.ensure(n * (size_t)knp2 * 8))) return rc;
+    {
+        ProfScope ps(ix, 0, stream);
+        PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_q, n);
+        p.ex_bits = 0u; // (MSTG: no ex codes)
+        HIP_TRY(launch_prep(p, ix->device, stream));
+    }
+    {
+        ProfScope ps(ix, 1, stream);
+        MstgSelectParams p{};
+        p.rot = (const float*)w->rot.p; p.nq = (uint32_t)n; p.D = D; p.k = k; p.ef_search = ef_search; p.pruning_epsilon = pruning_epsilon;
+        p.cent = (const float*)ix->centroids.p;
+        p.cent_hi = (const uint16_t*)ix->ms_hi.p; p.cent_lo = (const uint16_t*)ix->ms_lo.p; p.nc = (const float*)ix->ms_nc.p;
+        p.ncmax_bits = (const uint32_t*)ix->ms_nc.p + k; p.cent_bad = ix->ms_bad;
+        p.q_hi = (uint16_t*)w->rot_hi.p; p.q_lo = (uint16_t*)w->rot_lo.p;
+        p.sl = (uint32_t*)w->ms_sl.p; p.sl_n = p.sl + n * (size_t)(gemm ? kMsCap : 0); p.nx = (float*)(p.sl_n + n);
+        p.dots = (float*)w->scores.p; p.keys_g = knp2 ? (unsigned long long*)w->key_window.p : nullptr;
+        p.fallbacks = d_fallbacks; p.out_lists = d_lists; p.out_counts = d_lcnt;
+        HIP_TRY(launch_mstg_select(p, ix->device, stream));
+    }
+    {
+        ProfScope ps(ix, 2, stream);
+        ProbesGivenParams p;
+        p.list_ids = d_lists; p.list_counts = d_lcnt; p.max_lists = sh.ef;
+        p.nq = (uint32_t)n; p.nlist = k; p.metric = (int)ix->metric; p.rot = (const float*)w->rot.p;
+        p.cent = (const float*)ix->centroids.p; p.D = D; p.list_gb0 = (const uint32_t*)ix->list_gb0.p;
+        p.list_n = (const uint32_t*)ix->list_n.p; p.probe = (ProbeInfo*)w->probe.p; p.wl = (StreamItem*)w->wl.p;
+        p.wl_stride = sh.wl_stride; p.nstream = (uint32_t*)w->nstream.p; p.consts = (const QueryConsts*)w->consts.p;
+        p.bsum = (const BlockSummary*)ix->bsum.p;
+        p.numeric_variant = ix->opt.numeric_variant;
+        HIP_TRY(launch_probes_given(p, stream));
+    }
+    return scan_stage(ix, w, n, sh.ef, top_k, sh.wl_stride, nullptr, 0, d_ids, d_scores, d_counts, nullptr, /*mstg=*/true, nullptr, stream);
+}
+
+// what rbq_posting_scan_batch checks, in its order; *done: the call is answered without the device
+int ms_check(const rbq_index* h, const void* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, const void* out_ids,
+             const void* out_scores, const void* out_counts) {
+    int rc = check_query_args(h, query_dim);
+    if (rc) return rc;
+    if (h->reps[0]->rotator != RBQ_ROTATOR_NONE) return fail(RBQ_INVALID_CONFIG, "MSTG search needs an index created with rotator NONE");
+    if (nq == 0) return RBQ_OK;
+    if (nq > 0x7fffffffull) return fail(RBQ_INVALID_CONFIG, "batch too large");
+    // (top_k == 0: out_ids and out_scores hold no element, so they have no address to ask for)
+    if (!queries || !out_counts || (top_k && (!out_ids || !out_scores))) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    if (top_k > kTopKHardMax || (uint64_t)std::min<uint64_t>(nq, 16384) * ((uint64_t)top_k + 1) * 8 > (8ull << 30))
+        return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20)");
+    return RBQ_OK;
+}
+
 Replica* replica_of_pointer(rbq_index* h, const void* dptr) {
     if (h->reps.size() == 1) return h->reps[0];
     hipPointerAttribute_t a;
@@ -717,6 +850,128 @@ int rbq_posting_scan_batch(const rbq_index* ch, const float* queries, uint64_t n
     RBQ_GUARD_END
 }
 
+
+// ---- MSTG search (include/rbq_mstg.h) ------------------------------------------------------------------
+int rbq_mstg_search_batch(const rbq_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t ef_search,
+                          float pruning_epsilon, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_list_ids,
+                          uint32_t* out_list_counts) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    rbq_index* h = const_cast<rbq_index*>(ch);
+    int rc = ms_check(h, queries, nq, query_dim, top_k, out_ids, out_scores, out_counts);
+    if (rc || nq == 0) return rc;
+    Replica* ix = h->reps[0];
+    const uint32_t ef = (uint32_t)std::min<uint64_t>(ef_search, ix->n_lists);
+    if (top_k == 0 || ef == 0) { // no candidate: every count 0, every slot unused
+        std::memset(out_counts, 0, nq * 4);
+        if (out_list_counts) std::memset(out_list_counts, 0, nq * 4);
+        if (out_list_ids) std::memset(out_list_ids, 0xff, nq * (size_t)ef * 4);
+        for (uint64_t i = 0; i < nq * top_k; ++i) { out_ids[i] = ~0ull; out_scores[i] = NAN; }
+        return RBQ_OK;
+    }
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    if (mstg_select_gemm(ix->n_lists, ix->D) && (rc = ms_prepare(ix))) return rc;
+    unsigned long long* d_fb = nullptr;
+    if ((rc = ms_fallback_counter(ix->device, &d_fb))) return rc;
+    const MstgShape sh = ms_shape(ix, nq, top_k, ef_search, true);
+    if (sh.wl_stride > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "posting lists too long for one query");
+    Workspace* w = take_ws(ix);
+    if (!w) return fail(RBQ_DEVICE, "cannot create workspace stream");
+    auto run = [&]() -> int {
+        int r2;
+        hipStream_t st = w->stream;
+        for (uint64_t q0 = 0; q0 < nq; q0 += sh.chunk) {
+            const uint64_t n = std::min(sh.chunk, nq - q0);
+            const OutPack op(n, top_k, false);
+            if ((r2 = w->queries.ensure(n * query_dim * 4))) return r2;
+            if ((r2 = w->out_pack.ensure(op.total))) return r2;
+            if ((r2 = w->ms_lists.ensure(n * ((size_t)sh.ef + 1) * 4))) return r2;
+            uint8_t* dp = (uint8_t*)w->out_pack.p;
+            uint32_t* d_lists = (uint32_t*)w->ms_lists.p;
+            uint32_t* d_lcnt = d_lists + n * (size_t)sh.ef;
+            HIP_TRY(hipMemcpyAsync(w->queries.p, queries + q0 * query_dim, n * query_dim * 4, hipMemcpyHostToDevice, st));
+            if ((r2 = ms_chunk(ix, w, (const float*)w->queries.p, n, top_k, ef_search, pruning_epsilon, sh, d_fb, (uint64_t*)(dp + op.o_ids),
+                               (float*)(dp + op.o_scores), (uint32_t*)(dp + op.o_counts), d_lists, d_lcnt, st)))
+                return r2;
+            HIP_TRY(hipMemcpyAsync(out_ids + q0 * top_k, dp + op.o_ids, n * top_k * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_scores + q0 * top_k, dp + op.o_scores, n * top_k * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_counts + q0, dp + op.o_counts, n * 4, hipMemcpyDeviceToHost, st));
+            if (out_list_ids) HIP_TRY(hipMemcpyAsync(out_list_ids + q0 * sh.ef, d_lists, n * (size_t)sh.ef * 4, hipMemcpyDeviceToHost, st));
+            if (out_list_counts) HIP_TRY(hipMemcpyAsync(out_list_counts + q0, d_lcnt, n * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return RBQ_OK;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(w->stream);
+    give_ws(ix, w);
+    return rc;
+    RBQ_GUARD_END
+}
+
+int rbq_mstg_search_batch_device(const rbq_index* ch, const float* d_queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                                 uint32_t ef_search, float pruning_epsilon, uint64_t* d_out_ids, float* d_out_scores,
+                                 uint32_t* d_out_counts, uint32_t* d_out_list_ids, uint32_t* d_out_list_counts, void* hip_stream) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    rbq_index* h = const_cast<rbq_index*>(ch);
+    int rc = ms_check(h, d_queries, nq, query_dim, top_k, d_out_ids, d_out_scores, d_out_counts);
+    if (rc || nq == 0) return rc;
+    Replica* ix = replica_of_pointer(h, d_queries);
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    hipStream_t s = (hipStream_t)hip_stream;
+    const uint32_t ef = (uint32_t)std::min<uint64_t>(ef_search, ix->n_lists);
+    if (top_k == 0 || ef == 0) { // (all-ones words: UINT64_MAX ids, UINT32_MAX lists, NaN scores)
+        HIP_TRY(hipMemsetAsync(d_out_counts, 0, nq * 4, s));
+        if (d_out_list_counts) HIP_TRY(hipMemsetAsync(d_out_list_counts, 0, nq * 4, s));
+        if (d_out_list_ids && ef) HIP_TRY(hipMemsetAsync(d_out_list_ids, 0xff, nq * (size_t)ef * 4, s));
+        if (top_k) {
+            HIP_TRY(hipMemsetAsync(d_out_ids, 0xff, nq * (size_t)top_k * 8, s));
+            HIP_TRY(hipMemsetAsync(d_out_scores, 0xff, nq * (size_t)top_k * 4, s));
+        }
+        return RBQ_OK;
+    }
+    if (mstg_select_gemm(ix->n_lists, ix->D) && (rc = ms_prepare(ix))) return rc;
+    unsigned long long* d_fb = nullptr;
+    if ((rc = ms_fallback_counter(ix->device, &d_fb))) return rc;
+    const MstgShape sh = ms_shape(ix, nq, top_k, ef_search, false);
+    if (sh.wl_stride > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "posting lists too long for one query");
+    Workspace* w; // one per caller stream, as rbq_search_batch_device: the chunks of a call and successive calls are stream-ordered
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        Workspace*& slot = ix->stream_ws[s];
+        if (!slot) slot = new Workspace();
+        w = slot;
+    }
+    const bool own_lists = !d_out_list_ids || !d_out_list_counts;
+    if (own_lists && (rc = w->ms_lists.ensure(sh.chunk * ((size_t)sh.ef + 1) * 4))) return rc;
+    for (uint64_t q0 = 0; q0 < nq; q0 += sh.chunk) {
+        const uint64_t n = std::min(sh.chunk, nq - q0);
+        uint32_t* d_lists = d_out_list_ids ? d_out_list_ids + q0 * sh.ef : (uint32_t*)w->ms_lists.p;
+        uint32_t* d_lcnt = d_out_list_counts ? d_out_list_counts + q0 : (uint32_t*)w->ms_lists.p + sh.chunk * (size_t)sh.ef;
+        if ((rc = ms_chunk(ix, w, d_queries + q0 * query_dim, n, top_k, ef_search, pruning_epsilon, sh, d_fb, d_out_ids + q0 * top_k,
+                           d_out_scores + q0 * top_k, d_out_counts + q0, d_lists, d_lcnt, s)))
+            return rc;
+    }
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+
+uint64_t rbq_mstg_debug_search_fallbacks(void) {
+    uint64_t total = 0;
+    for (int dev = 0; dev < 16; ++dev) {
+        unsigned long long* p;
+        { std::lock_guard<std::mutex> lk(g_ms_mu); p = g_ms_fallbacks[dev]; }
+        if (!p) continue;
+        DeviceGuard g(dev);
+        unsigned long long v = 0;
+        if (g.ok && hipMemcpy(&v, p, 8, hipMemcpyDeviceToHost) == hipSuccess) total += v;
+        else (void)hipGetLastError();
+    }
+    return total;
+}
 
 // Which kernel instantiation each of the four stages launches for a call of this shape, and what it occupies.
 // out[stage][6] = workgroups, threads per workgroup, VGPRs per lane, LDS bytes per workgroup (static + dynamic), scratch bytes per

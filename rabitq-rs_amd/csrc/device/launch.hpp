@@ -10,6 +10,7 @@
 //   k_bf.hip     brute-force index: distances and the BinaryHeap replay                  (bf.hpp)
 //   k_bf_train.hip  brute-force index: the encoder's flat output, ex_code_packed         (encode_vec.hpp)
 //   k_mstg.hip   MSTG closure assignment (ClosureAssigner::assign) and its host driver       (km_common.hpp)
+//   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, rank_mfma.hpp)
 #pragma once
 #include <atomic>
 #include <string>
@@ -288,6 +289,36 @@ int closure_device(const ClosureArgs& a, int device, std::string& detail); // RB
 // (vector, list) pairs of the closure in vector-major order: pair off[i] + j = (i, lists[i][j]) for j < counts[i]
 hipError_t launch_closure_expand(const uint32_t* lists, const uint32_t* counts, const uint32_t* off, uint64_t n, uint32_t max_replicas,
                                  uint32_t* pair_list, uint32_t* pair_vec, hipStream_t s);
+
+// ---- MSTG search (k_mstg_search.hip): the exact ef_search nearest centroids of every query and dynamic_prune's cut
+constexpr uint32_t kMsCap = 2048; // shortlist capacity per query (the exact pass sorts it in LDS)
+struct MstgSelectParams {
+    const float* rot;       // [nq][D] the queries as k_prep leaves them (rotator NONE: the raw query)
+    uint32_t nq, D, k;
+    uint32_t ef_search;
+    float pruning_epsilon;
+    const float* cent;      // [k][D]
+    // the GEMM path (mstg_select_gemm): centroid images and norms of launch_mstg_centroid_prep, per-chunk scratch
+    const uint16_t *cent_hi, *cent_lo; // [k][Dp]
+    const float* nc;        // [k]
+    const uint32_t* ncmax_bits;
+    uint32_t cent_bad;      // a centroid coordinate is not finite: every query is scored against every centroid
+    uint16_t *q_hi, *q_lo;  // [nq rounded up to 128][Dp]
+    float* nx;              // [nq]
+    float* dots;            // [nq rounded up to 128][k]
+    uint32_t* sl;           // [nq][kMsCap]
+    uint32_t* sl_n;         // [nq] (k > 256)
+    unsigned long long* keys_g; // [nq][mstg_select_knp2(k)] (k > kMsCap), else null
+    unsigned long long* fallbacks; // device counter: queries scored against every centroid
+    uint32_t* out_lists;    // [nq][min(ef_search, k)] in scan order, unused slots UINT32_MAX
+    uint32_t* out_counts;   // [nq]
+};
+uint32_t mstg_select_dp(uint32_t D);            // the padded dimension of the split images
+bool mstg_select_gemm(uint64_t k, uint32_t D);  // whether this shape takes the GEMM shortlist
+uint32_t mstg_select_knp2(uint64_t k);          // keys per query of keys_g (0: not needed)
+hipError_t launch_mstg_centroid_prep(const float* cent, uint32_t k, uint32_t D, float* nc, uint32_t* ncmax_bits, uint32_t* bad,
+                                     uint16_t* hi, uint16_t* lo, hipStream_t s);
+hipError_t launch_mstg_select(const MstgSelectParams& p, int device, hipStream_t s);
 
 // ---- RBQ1 writer (k_save.hip): words [w0, w0 + nw) of the cluster section of the stream, into out[0, nw)
 struct SaveParams {

@@ -911,4 +911,43 @@ int rbq_build_closure_assign(const float* centroids, uint64_t n_lists, uint32_t 
     return RBQ_OK;
 }
 
+// MstgIndex::search's list selection (include/rbq_mstg.h): the exact ef_search nearest centroids under (bits of the squared
+// distance, centroid index), then dynamic_prune's cut at closest * (1.0 + pruning_epsilon) on the square roots
+int rbq_build_mstg_select_lists(const float* centroids, uint64_t n_lists, uint32_t dim, const float* queries, uint64_t nq,
+                                uint32_t ef_search, float pruning_epsilon, uint32_t* out_lists, uint32_t* out_counts) {
+    if (!centroids || !queries || !out_counts) return RBQ_INVALID_CONFIG;
+    if (n_lists == 0 || dim == 0 || n_lists >= 0xffffffffull) return RBQ_INVALID_CONFIG;
+    const size_t ef = (size_t)std::min<uint64_t>(ef_search, n_lists);
+    if (ef && !out_lists) return RBQ_INVALID_CONFIG;
+#pragma omp parallel
+    {
+        std::vector<uint64_t> key(n_lists);
+#pragma omp for schedule(dynamic, 16)
+        for (int64_t i = 0; i < (int64_t)nq; ++i) {
+            const float* q = queries + (size_t)i * dim;
+            bool nan = false;
+            for (uint64_t c = 0; c < n_lists; ++c) {
+                const float s = l2_sqr8(q, centroids + (size_t)c * dim, dim);
+                nan |= s != s;
+                uint32_t b;
+                std::memcpy(&b, &s, 4);
+                key[c] = ((uint64_t)b << 32) | c; // (s >= 0 unless it is NaN: the bit patterns order like the values)
+            }
+            uint32_t* o = out_lists + (size_t)i * ef;
+            size_t kept = 0;
+            if (!nan && ef) {
+                std::partial_sort(key.begin(), key.begin() + ef, key.end());
+                const auto dist = [&](size_t r) { const uint32_t b = (uint32_t)(key[r] >> 32); float s; std::memcpy(&s, &b, 4); return std::sqrt(s); };
+                const float one_eps = 1.0f + pruning_epsilon;
+                const float threshold = dist(0) * one_eps;
+                if (std::isfinite(dist(0)))
+                    while (kept < ef && dist(kept) <= threshold) ++kept;
+            }
+            for (size_t r = 0; r < ef; ++r) o[r] = r < kept ? (uint32_t)key[r] : 0xffffffffu;
+            out_counts[i] = (uint32_t)kept;
+        }
+    }
+    return RBQ_OK;
+}
+
 } // extern "C"

@@ -60,6 +60,15 @@ void               rbq_bf_built_free(rbq_bf_built* b);
  * (the crate panics on the last two).  Non-finite data is not checked: the result is then unspecified. */
 int rbq_build_closure_assign(const float* centroids, uint64_t n_lists, uint32_t dim, const float* data, uint64_t n,
                              float epsilon, uint32_t max_replicas, uint32_t* out_lists, uint32_t* out_counts);
+
+/* The list selection of MstgIndex::search as rbq_mstg_search_batch defines it (include/rbq_mstg.h, "the selection"): for
+ * every query the min(ef_search, n_lists) nearest centroids under (bits of math::l2_distance_sqr in its AVX2 order,
+ * centroid index), cut where sqrtf(distance) > sqrtf(closest) * (1.0f + pruning_epsilon).  The parity yardstick of the
+ * device selection, OpenMP over the queries.  out_lists [nq][min(ef_search, n_lists)] in scan order (unused slots
+ * UINT32_MAX), out_counts [nq].  Any pruning_epsilon is taken; a query with a NaN distance, or whose closest distance is
+ * +inf, selects nothing.  RBQ_INVALID_CONFIG: a null pointer, n_lists == 0 or >= 2^32 - 1, dim == 0. */
+int rbq_build_mstg_select_lists(const float* centroids, uint64_t n_lists, uint32_t dim, const float* queries, uint64_t nq,
+                                uint32_t ef_search, float pruning_epsilon, uint32_t* out_lists, uint32_t* out_counts);
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,13 @@ def lib():
         L.rbq_mstg_debug_closure_shortlist.restype = C.c_int
         L.rbq_mstg_debug_closure_shortlist.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int,
                                                        vp, vp]
+        L.rbq_mstg_search_batch.restype = C.c_int
+        L.rbq_mstg_search_batch.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp]
+        L.rbq_mstg_search_batch_device.restype = C.c_int
+        L.rbq_mstg_search_batch_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp,
+                                                   vp]
+        L.rbq_mstg_debug_search_fallbacks.restype = C.c_uint64
+        L.rbq_mstg_debug_search_fallbacks.argtypes = []
         _LIB = L
     return _LIB
 

@@ -1,10 +1,13 @@
-"""MSTG posting-list build, steps 2 and 3 of `MstgIndex::build` (reference src/mstg/index.rs:40-110), on the GPU
-(include/rbq_mstg.h): closure assignment with the RNG rule (`ClosureAssigner::assign`, src/mstg/closure.rs) and the posting
-lists of the expanded (vector, list) pairs.
+"""MSTG on the GPU (include/rbq_mstg.h).  Build: steps 2 and 3 of `MstgIndex::build` (reference src/mstg/index.rs:40-110),
+closure assignment with the RNG rule (`ClosureAssigner::assign`, src/mstg/closure.rs) and the posting lists of the expanded
+(vector, list) pairs.  Search: `MstgIndex::search` / `batch_search` in one call (`mstg_search`): the exact ef_search nearest
+centroids, dynamic_prune and the posting-list scan.
 
 The arithmetic is the crate's on an AVX2 host; `closure_assign_cpu` (csrc/host/rbq_build.cpp) restates it on the CPU and the
-device result equals it exactly.  Clustering, HNSW and dynamic_prune stay with the caller."""
+device result equals it exactly; `select_lists_cpu` does the same for the search's list selection
+(section 16).  Clustering and the HNSW stay with the caller; the HNSW is not needed for searching through this library."""
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -127,3 +130,85 @@ def build_postings_on_device(data, centroids, total_bits, metric, closure_epsilo
     _check(lib().rbq_mstg_build_device(C.byref(hdr), cent.ctypes.data, xp, n, float(closure_epsilon), int(max_replicas), mode, t,
                                        int(max_chunk_rows), dev, C.byref(h)))
     return IvfRabitqIndex(h)
+
+
+@dataclass(frozen=True)
+class MstgSearchParams:
+    """The crate's SearchParams of an MSTG index (src/mstg/config.rs): how many centroids are ranked, and dynamic_prune's epsilon."""
+    ef_search: int = 150
+    pruning_epsilon: float = 0.6
+
+    @staticmethod
+    def balanced():
+        return MstgSearchParams(150, 0.6)
+
+    @staticmethod
+    def high_recall():
+        return MstgSearchParams(300, 0.8)
+
+    @staticmethod
+    def low_latency():
+        return MstgSearchParams(50, 0.4)
+
+
+def select_lists_cpu(queries, centroids, ef_search, pruning_epsilon):
+    """The list selection of `mstg_search` on the CPU (rbq_build_mstg_select_lists, OpenMP over the queries): (lists
+    [nq][min(ef_search, n_lists)] u32 in scan order with NONE in unused slots, counts [nq] u32)."""
+    from . import RabitqError, builder
+    q, c = _host_f32(queries), _host_f32(centroids)
+    nq, k, dim = _shapes(q, c)
+    ef = min(max(int(ef_search), 0), k)
+    lists = np.empty((nq, ef), np.uint32)
+    counts = np.empty(nq, np.uint32)
+    rc = builder.lib().rbq_build_mstg_select_lists(c.ctypes.data, k, dim, q.ctypes.data, nq, int(ef_search), float(pruning_epsilon),
+                                                   lists.ctypes.data, counts.ctypes.data)
+    if rc != _abi.RBQ_OK:
+        raise RabitqError(rc, "list selection rejected its configuration")
+    return lists, counts
+
+
+def search_fallbacks():
+    """Queries of every MSTG search so far that were scored against every centroid (rbq_mstg_debug_search_fallbacks)."""
+    from .index import lib
+    return int(lib().rbq_mstg_debug_search_fallbacks())
+
+
+def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, return_lists=False):
+    """`MstgIndex::batch_search` on an MSTG handle (rotator NoRotation, e.g. from build_postings_on_device) in one call:
+    (ids [nq][top_k] u64, distances [nq][top_k] f32 ascending, counts [nq] u32), plus (lists, list_counts) of the selected
+    posting lists in scan order with `return_lists`.  NumPy queries take rbq_mstg_search_batch and return arrays; a CUDA tensor
+    takes rbq_mstg_search_batch_device on the current stream, without synchronising, and returns tensors (ids as int64 bit
+    patterns, lists as int32 bit patterns: torch has no unsigned 64 / 32-bit arithmetic)."""
+    from .index import _check, lib
+    top_k, ef_search = int(top_k), int(ef_search)
+    ef = min(max(ef_search, 0), index.cluster_count())
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    if torch is not None and isinstance(queries, torch.Tensor) and queries.is_cuda:
+        q = queries.to(dtype=torch.float32).contiguous()
+        nq, qd = q.shape
+        with torch.cuda.device(q.device):
+            ids = torch.empty((nq, top_k), dtype=torch.int64, device=q.device)
+            sc = torch.empty((nq, top_k), dtype=torch.float32, device=q.device)
+            cnt = torch.empty(nq, dtype=torch.int32, device=q.device)
+            li = torch.empty((nq, ef), dtype=torch.int32, device=q.device) if return_lists else None
+            lc = torch.empty(nq, dtype=torch.int32, device=q.device) if return_lists else None
+            stream = torch.cuda.current_stream().cuda_stream
+            _check(lib().rbq_mstg_search_batch_device(index._h, q.data_ptr(), nq, qd, top_k, ef_search, float(pruning_epsilon),
+                                                      ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(),
+                                                      li.data_ptr() if return_lists else None, lc.data_ptr() if return_lists else None,
+                                                      C.c_void_p(stream)))
+        return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
+    q = _host_f32(queries)
+    nq, qd = q.shape
+    ids = np.empty((nq, top_k), np.uint64)
+    sc = np.empty((nq, top_k), np.float32)
+    cnt = np.zeros(nq, np.uint32)
+    li = np.empty((nq, ef), np.uint32) if return_lists else None
+    lc = np.empty(nq, np.uint32) if return_lists else None
+    _check(lib().rbq_mstg_search_batch(index._h, q.ctypes.data, nq, qd, top_k, ef_search, float(pruning_epsilon), ids.ctypes.data,
+                                       sc.ctypes.data, cnt.ctypes.data, li.ctypes.data if return_lists else None,
+                                       lc.ctypes.data if return_lists else None))
+    return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
