@@ -6,8 +6,9 @@
  * src/mstg/posting_list.rs:66-101).  The result is an ordinary rbq_index with rotator RBQ_ROTATOR_NONE, served by
  * rbq_posting_scan_batch, and by rbq_mstg_search_batch below, which answers `MstgIndex::search` / `batch_search`
  * (src/mstg/index.rs:149-213, 340-346) in one call: the centroid ranking and dynamic_prune run on the device too.
- * Step 1 (hierarchical balanced clustering) and step 4 (HNSW over the centroids) stay with the caller; step 4 is not
- * needed for searching through this library.  A header of its own, not included by rbq.h (DESIGN.md sections 15, 16).
+ * Step 1, the hierarchical balanced clustering that yields the centroids (HierarchicalClustering::cluster,
+ * src/mstg/clustering.rs), is rbq_mstg_cluster_device.  Step 4 (HNSW over the centroids) is not built: it is not needed for
+ * searching through this library.  A header of its own, not included by rbq.h (DESIGN.md sections 15, 16, 17).
  */
 #ifndef RBQ_MSTG_H
 #define RBQ_MSTG_H
@@ -61,6 +62,42 @@ int rbq_mstg_closure_assign(const float* centroids, uint64_t n_lists, uint32_t d
 int rbq_mstg_build_device(const rbq_header* hdr, const float* centroids, const float* data, uint64_t n,
                           float closure_epsilon, uint32_t max_replicas, int rescale, float t_const,
                           uint64_t max_chunk_rows, int device, rbq_index** out);
+
+/* MstgIndex::build step 1: HierarchicalClustering{max_posting_size, branching_factor, balance_weight, max_iterations}
+ * .cluster(data) on the device.  The crate's own result cannot be reproduced (its k-means merges sums in thread order and
+ * its RNG is ChaCha12); the specification is the CPU restatement rbq_build_hcluster of the CPU builder, whose pins
+ * csrc/host/rbq_hcluster.hpp states, and every array of the result equals it bit for bit.
+ *   data       [n][dim] f32, host or device memory (detected; host data is uploaded once).  Any dim >= 1.
+ *   max_posting_size  a cluster of at most this many rows is final (MstgConfig::max_posting_size)
+ *   branching_factor  k of every split's k-means; up to 256 a direct assignment kernel runs, above it the GEMM shortlist of
+ *              rbq_kmeans_device
+ *   balance_weight    any value: NaN or <= 0 means no balancing, +inf that no subcluster is ever oversized
+ *   max_iterations    Lloyd iterations per split (the crate: 100)
+ *   host_below a cluster of at most this many rows is clustered on the host together with its whole subtree (small splits
+ *              are bound by launch latency).  0 = never; RBQ_MSTG_HOST_BELOW_DEFAULT = the library's choice
+ *              (RBQ_MSTG_HOST_BELOW).  The result does not depend on it.
+ *   device     HIP ordinal, -1 = the current device
+ *   out        a handle read through the accessors below and released with rbq_hclustered_free: the final clusters in
+ *              the crate's pop order; centroids [count][dim]; offsets [count + 1]; members [n] u32, the row indices cluster
+ *              by cluster, each cluster in its own order; stats [6]: splits, balance moves, empty clusters reseeded,
+ *              reseeds drawn from the RNG, splits that ran on the host, bytes of device workspace.
+ * RBQ_INVALID_CONFIG, checked before the first HIP call: a null pointer, n == 0, dim == 0, n >= 2^32 - 1,
+ * max_iterations == 0, branching_factor < 2 (the crate panics on 0 and never ends with 1) or > max_posting_size + 1 (a
+ * cluster one row over the limit has fewer rows than centroids: the crate panics).  Found later: a non-finite value
+ * (on the device, before any split), and a split that leaves a single non-empty subcluster, on which the crate would
+ * loop for ever (identical rows without balancing).  One device.  Never aborts: device failures are RBQ_DEVICE. */
+#define RBQ_MSTG_HOST_BELOW_DEFAULT UINT64_MAX
+#define RBQ_MSTG_HOST_BELOW 0 /* not measured yet: every split runs on the device */
+typedef struct rbq_hclustered rbq_hclustered;
+int rbq_mstg_cluster_device(const float* data, uint64_t n, uint32_t dim, uint64_t max_posting_size, uint64_t branching_factor,
+                            float balance_weight, uint64_t max_iterations, uint64_t host_below, int device,
+                            rbq_hclustered** out);
+uint64_t        rbq_hclustered_count(const rbq_hclustered* h);
+const float*    rbq_hclustered_centroids(const rbq_hclustered* h);
+const uint64_t* rbq_hclustered_offsets(const rbq_hclustered* h);
+const uint32_t* rbq_hclustered_members(const rbq_hclustered* h);
+const uint64_t* rbq_hclustered_stats(const rbq_hclustered* h);
+void            rbq_hclustered_free(rbq_hclustered* h);
 
 /* Diagnostic: rows, summed over every closure assignment of this process, whose shortlist could not be proven complete
  * within RBQ_MSTG_SHORTLIST entries and that were scored exactly against every centroid instead. */

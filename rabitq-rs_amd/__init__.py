@@ -14,6 +14,8 @@ Mirrors the reference's public query API for this path:
                                src/mstg/closure.rs, src/mstg/index.rs:40-110 (mstg.py)
   mstg_search / select_lists_cpu / MstgSearchParams: MstgIndex::search and batch_search
                                src/mstg/index.rs:149-213,340-362 (mstg.py)
+  hierarchical_cluster / hierarchical_cluster_cpu / MstgIndex: HierarchicalClustering::cluster, PyMstgIndex
+                               src/mstg/clustering.rs, src/python_bindings.rs (mstg.py)
 All compute goes through the C ABI of include/rbq.h (csrc/librbq.so, hand-written HIP for
 gfx950). There is no CPU fallback: if the HIP library is missing or no GPU is present the
 calls raise.
@@ -75,10 +77,11 @@ from .index import IvfRabitqIndex, StreamBuilder  # noqa: E402
 from . import builder  # noqa: E402,F401
 from .bruteforce import BruteForceRabitqIndex, BruteForceSearchParams, BruteForceSearchResult  # noqa: E402
 from .kmeans import KMeansConfig, KMeansResult, run_kmeans_with_config  # noqa: E402
-from .mstg import (MstgSearchParams, build_postings_on_device, closure_assign, closure_assign_cpu, mstg_search,  # noqa: E402
-                   select_lists_cpu)
+from .mstg import (MstgIndex, MstgSearchParams, build_postings_on_device, closure_assign, closure_assign_cpu,  # noqa: E402
+                   hierarchical_cluster, hierarchical_cluster_cpu, mstg_search, select_lists_cpu)
 
 __all__ = ["Metric", "RotatorType", "RabitqError", "SearchParams", "SearchResult", "IvfRabitqIndex",
            "StreamBuilder", "builder", "BruteForceRabitqIndex", "BruteForceSearchParams", "BruteForceSearchResult",
            "KMeansConfig", "KMeansResult", "run_kmeans_with_config", "closure_assign", "closure_assign_cpu",
-           "build_postings_on_device", "MstgSearchParams", "mstg_search", "select_lists_cpu"]
+           "build_postings_on_device", "MstgSearchParams", "mstg_search", "select_lists_cpu", "hierarchical_cluster",
+           "hierarchical_cluster_cpu", "MstgIndex"]

@@ -72,8 +72,37 @@ def lib():
         L.rbq_build_mstg_select_lists.restype = C.c_int
         L.rbq_build_mstg_select_lists.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float,
                                                   C.c_void_p, C.c_void_p]
+        L.rbq_build_hcluster.restype = C.c_int
+        L.rbq_build_hcluster.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_uint64,
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)]
+        bind_hclustered(L)
         _LIB = L
     return _LIB
+
+
+HCLUSTER_STATS = ("splits", "balance_moves", "empty_reseeded", "rng_draws", "host_splits", "arena_bytes")
+
+
+def bind_hclustered(L):
+    """The accessors of an rbq_hclustered handle (the same in librbq_build.so and librbq.so)."""
+    for name, res in (("count", C.c_uint64), ("centroids", C.POINTER(C.c_float)), ("offsets", C.POINTER(C.c_uint64)),
+                      ("members", C.POINTER(C.c_uint32)), ("stats", C.POINTER(C.c_uint64))):
+        f = getattr(L, "rbq_hclustered_" + name)
+        f.restype, f.argtypes = res, [C.c_void_p]
+    L.rbq_hclustered_free.restype, L.rbq_hclustered_free.argtypes = None, [C.c_void_p]
+
+
+def take_hclustered(L, h, n, dim):
+    """(centroids [count][dim] f32, offsets [count + 1] u64, members [n] u32, stats dict) copied out of the handle, which is freed."""
+    try:
+        cnt = int(L.rbq_hclustered_count(h))
+        cent = np.ctypeslib.as_array(L.rbq_hclustered_centroids(h), shape=(cnt, dim)).copy() if cnt else np.zeros((0, dim), np.float32)
+        off = np.ctypeslib.as_array(L.rbq_hclustered_offsets(h), shape=(cnt + 1,)).copy()
+        mem = np.ctypeslib.as_array(L.rbq_hclustered_members(h), shape=(n,)).copy()
+        st = dict(zip(HCLUSTER_STATS, (int(L.rbq_hclustered_stats(h)[i]) for i in range(len(HCLUSTER_STATS)))))
+    finally:
+        L.rbq_hclustered_free(h)
+    return cent, off, mem, st
 
 
 class BuiltIndex:

@@ -1,9 +1,12 @@
-// api_mstg.hip — MSTG posting-list build (include/rbq_mstg.h): closure assignment on the device (k_mstg.hip) and the device
-// encoder of api_build.hip fed the expanded (vector, list) pairs.
+// api_mstg.hip — MSTG build (include/rbq_mstg.h): hierarchical balanced clustering (k_hcluster.hip), closure assignment on the
+// device (k_mstg.hip) and the device encoder of api_build.hip fed the expanded (vector, list) pairs.
 #include "api.hpp"
 #include "rbq_mstg.h"
+#include "../host/rbq_hcluster.hpp"
 
 using namespace rbq_api;
+
+struct rbq_hclustered { rbq_host::HcResult r; };
 
 static_assert(RBQ_MSTG_MAX_REPLICAS == kMstgMaxReplicas, "rbq_mstg.h and launch.hpp disagree");
 
@@ -124,6 +127,47 @@ int rbq_mstg_build_device(const rbq_header* hdr, const float* centroids, const f
     return build_impl(hdr, centroids, data, n, closure_epsilon, max_replicas, rescale, t_const, max_chunk_rows, device, out);
     RBQ_GUARD_END
 }
+
+int rbq_mstg_cluster_device(const float* data, uint64_t n, uint32_t dim, uint64_t max_posting_size, uint64_t branching_factor,
+                            float balance_weight, uint64_t max_iterations, uint64_t host_below, int device, rbq_hclustered** out) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!out) return fail(RBQ_INVALID_CONFIG, "null out pointer");
+    *out = nullptr;
+    if (const char* why = rbq_host::hc_check(data, n, dim, max_posting_size, branching_factor, max_iterations))
+        return fail(RBQ_INVALID_CONFIG, why);
+    std::vector<int> devs;
+    int rc;
+    if ((rc = resolve_devices(1, device < 0 ? nullptr : &device, devs))) return rc;
+    DeviceGuard g(devs[0]);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    Scratch t;
+    HClusterArgs a{};
+    a.n = n; a.dim = dim; a.max_size = max_posting_size; a.k = branching_factor; a.niter = max_iterations;
+    a.balance_weight = balance_weight; a.device = devs[0];
+    a.host_below = host_below == RBQ_MSTG_HOST_BELOW_DEFAULT ? RBQ_MSTG_HOST_BELOW : host_below;
+    if (is_device_pointer(data)) {
+        a.d_data = data;
+    } else {   // uploaded once
+        float* p = nullptr;
+        HIP_TRY(t.alloc(&p, n * dim * 4));
+        HIP_TRY(hipMemcpy(p, data, n * dim * 4, hipMemcpyHostToDevice));
+        a.d_data = p;
+        a.h_data = data;
+    }
+    std::unique_ptr<rbq_hclustered> h(new rbq_hclustered());
+    std::string detail;
+    if ((rc = hcluster_device(a, h->r, detail))) return fail(rc, detail);
+    *out = h.release();
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+uint64_t rbq_hclustered_count(const rbq_hclustered* h) { return h->r.offsets.size() - 1; }
+const float* rbq_hclustered_centroids(const rbq_hclustered* h) { return h->r.centroids.data(); }
+const uint64_t* rbq_hclustered_offsets(const rbq_hclustered* h) { return h->r.offsets.data(); }
+const uint32_t* rbq_hclustered_members(const rbq_hclustered* h) { return h->r.members.data(); }
+const uint64_t* rbq_hclustered_stats(const rbq_hclustered* h) { return h->r.stats; }
+void rbq_hclustered_free(rbq_hclustered* h) { delete h; }
 
 uint64_t rbq_mstg_debug_closure_fallbacks(void) { return g_closure_fallbacks.load(std::memory_order_relaxed); }
 

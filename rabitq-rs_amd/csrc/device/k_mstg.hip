@@ -40,38 +40,6 @@ namespace rbq {
 constexpr uint32_t kClMaxDp = 16384;          // the shortlist's error bound is stated up to this padded dimension
 constexpr uint32_t kNone = 0xffffffffu;
 
-// math::l2_distance_sqr (AVX2 order, src/math.rs:216-245) by a group of 8 lanes: lane g of the group owns accumulator g.  Every
-// lane of the group returns the distance.  All 64 lanes must call it together (a and b may be equal: a group with nothing to do).
-__device__ __forceinline__ float cl_canon8(const float* a, const float* b, uint32_t dim, uint32_t lane) {
-    const uint32_t g = lane & 7u, base = lane & ~7u, main = dim & ~7u;
-    float acc = 0.0f;
-    for (uint32_t i = g; i < main; i += 8u) {
-        const float d = a[i] - b[i];
-        const float p = d * d;
-        acc = acc + p;
-    }
-    float sum = 0.0f;
-    if (main) {
-        sum = -0.0f;
-#pragma unroll
-        for (uint32_t l = 0; l < 8u; ++l) sum = sum + __shfl(acc, (int)(base + l));
-    }
-    for (uint32_t i = main; i < dim; ++i) {
-        const float d = a[i] - b[i];
-        const float p = d * d;
-        sum = sum + p;
-    }
-    return sum;
-}
-
-__device__ __forceinline__ unsigned long long cl_wave_min(unsigned long long v) {
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned long long other = __shfl_xor(v, o);
-        v = other < v ? other : v;
-    }
-    return v;
-}
-
 // one wavefront per row of the chunk (k > kShortlist >= 64: every lane sees a centroid): T, eps, shortlist or the fallback mark
 __global__ __launch_bounds__(256) void k_cl_scan(const float* __restrict__ dots, uint32_t nr, uint32_t k, uint32_t Dp, uint32_t m,
                                                  const float* __restrict__ nx, const float* __restrict__ nc,

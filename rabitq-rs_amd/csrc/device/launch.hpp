@@ -17,6 +17,8 @@
 
 #include "types.hpp"
 
+namespace rbq_host { struct HcResult; } // csrc/host/rbq_hcluster.hpp
+
 namespace rbq {
 
 // Raises a kernel's dynamic-LDS limit once per (kernel, device, size): hipFuncSetAttribute is slow and serialises
@@ -289,6 +291,19 @@ int closure_device(const ClosureArgs& a, int device, std::string& detail); // RB
 // (vector, list) pairs of the closure in vector-major order: pair off[i] + j = (i, lists[i][j]) for j < counts[i]
 hipError_t launch_closure_expand(const uint32_t* lists, const uint32_t* counts, const uint32_t* off, uint64_t n, uint32_t max_replicas,
                                  uint32_t* pair_list, uint32_t* pair_vec, hipStream_t s);
+
+// ---- MSTG hierarchical balanced clustering (k_hcluster.hip): HierarchicalClustering::cluster, arguments already validated
+struct HClusterArgs {
+    const float* d_data;  // device [n][dim]
+    const float* h_data;  // the same rows in host memory, or null (rows handed to the host are then copied back)
+    uint64_t n;
+    uint32_t dim;
+    uint64_t max_size, k, niter;
+    float balance_weight;
+    uint64_t host_below;  // a cluster of at most this many rows goes to the host with its subtree; 0 = never
+    int device;
+};
+int hcluster_device(const HClusterArgs& a, rbq_host::HcResult& out, std::string& detail); // RBQ_* code; detail on failure
 
 // ---- MSTG search (k_mstg_search.hip): the exact ef_search nearest centroids of every query and dynamic_prune's cut
 constexpr uint32_t kMsCap = 2048; // shortlist capacity per query (the exact pass sorts it in LDS)

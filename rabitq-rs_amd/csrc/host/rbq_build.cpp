@@ -33,6 +33,7 @@
 #include "../../../include/rbq.h"
 #include "rbq_build.h"
 #include "rbq_rng.h"
+#include "rbq_hcluster.hpp"
 
 namespace {
 
@@ -668,68 +669,7 @@ void rbq_bf_built_free(rbq_bf_built* b) { delete b; }
 //              next candidate, then next() % rows.
 //   objective  per row the sequential f64 sum of ((float)(x - c))^2, then the sequential f64 sum over rows.
 // Non-finite input is rejected (the crate does not check; the GPU's shortlist bound needs finite input).
-namespace {
-
-void km_shuffle(std::vector<uint64_t>& v, Rng& rng) {
-    for (size_t i = v.size(); i-- > 1;) std::swap(v[i], v[rng.next() % (i + 1)]);
-}
-
-float km_norm(const float* x, uint32_t dim) {
-    float s = 0.0f;
-    for (uint32_t j = 0; j < dim; ++j) { float p = x[j] * x[j]; s = s + p; }
-    return s;
-}
-
-inline uint64_t km_cand_key(float dist, uint64_t row) {
-    uint32_t b;
-    std::memcpy(&b, &dist, 4);
-    return ((uint64_t)b << 32) | (0xffffffffull - row);
-}
-
-// assignment of rows [0, rows) of x (norms nx) to the centroids (column copy ccol [dim][k], norms nc): best cluster + its distance.
-// Independent sequential chains over coordinates, 64 clusters at a time (vectorised across clusters, never within a chain).
-void km_assign(const float* x, const float* nx, uint64_t rows, uint32_t dim, uint64_t k, const float* ccol, const float* nc,
-               uint32_t* best, float* bestd) {
-#pragma omp parallel for schedule(dynamic, 64)
-    for (int64_t i = 0; i < (int64_t)rows; ++i) {
-        const float* xr = x + (size_t)i * dim;
-        float bd = INFINITY;
-        uint32_t bc = 0;
-        for (uint64_t c0 = 0; c0 < k; c0 += 64) {
-            const uint64_t nb = std::min<uint64_t>(64, k - c0);
-            float acc[64];
-            for (uint64_t c = 0; c < 64; ++c) acc[c] = 0.0f;
-            for (uint32_t j = 0; j < dim; ++j) {
-                const float xv = xr[j];
-                const float* cc = ccol + (size_t)j * k + c0;
-                if (nb == 64) {
-                    for (int c = 0; c < 64; ++c) { float p = xv * cc[c]; acc[c] = acc[c] + p; }
-                } else {
-                    for (uint64_t c = 0; c < nb; ++c) { float p = xv * cc[c]; acc[c] = acc[c] + p; }
-                }
-            }
-            for (uint64_t c = 0; c < nb; ++c) {
-                float d = (nx[i] + nc[c0 + c]) - 2.0f * acc[c];
-                if (d < 0.0f) d = 0.0f;
-                if (d < bd) { bd = d; bc = (uint32_t)(c0 + c); }
-            }
-        }
-        best[i] = bc;
-        if (bestd) bestd[i] = bd;
-    }
-}
-
-void km_views(const float* cent, uint64_t k, uint32_t dim, std::vector<float>& ccol, std::vector<float>& nc) {
-    ccol.assign((size_t)k * dim, 0.0f);
-    nc.assign(k, 0.0f);
-    for (uint64_t c = 0; c < k; ++c) {
-        for (uint32_t j = 0; j < dim; ++j) ccol[(size_t)j * k + c] = cent[(size_t)c * dim + j];
-        nc[c] = km_norm(cent + (size_t)c * dim, dim);
-    }
-}
-
-} // namespace
-
+// (the text is in rbq_hcluster.hpp, which the device library compiles too)
 extern "C" {
 
 int rbq_build_kmeans_faiss(const float* data, uint64_t n, uint32_t dim, uint64_t k, uint64_t niter, uint64_t nredo, uint64_t seed,
@@ -739,138 +679,15 @@ int rbq_build_kmeans_faiss(const float* data, uint64_t n, uint32_t dim, uint64_t
         return RBQ_INVALID_CONFIG;
     for (uint64_t i = 0; i < n * dim; ++i)
         if (!std::isfinite(data[i])) return RBQ_INVALID_CONFIG;
-    uint64_t st_reseed = 0, st_draws = 0;
-    // select_training_indices
-    Rng sampling_rng(seed);
-    const uint64_t kp = max_points_per_centroid && k > UINT64_MAX / max_points_per_centroid ? UINT64_MAX : k * max_points_per_centroid;
-    const uint64_t target = std::max(std::min(n, kp), k);
-    std::vector<float> sample;
-    const float* x = data;
-    uint64_t rows = n;
-    if (target != n) {
-        std::vector<uint64_t> idx(n);
-        for (uint64_t i = 0; i < n; ++i) idx[i] = i;
-        km_shuffle(idx, sampling_rng);
-        idx.resize(target);
-        std::sort(idx.begin(), idx.end());
-        sample.resize((size_t)target * dim);
-        for (uint64_t i = 0; i < target; ++i) std::memcpy(&sample[(size_t)i * dim], data + idx[i] * dim, sizeof(float) * dim);
-        x = sample.data();
-        rows = target;
-    }
-    std::vector<float> nx(rows), full_nx(n);
-    for (uint64_t i = 0; i < rows; ++i) nx[i] = km_norm(x + (size_t)i * dim, dim);
-    for (uint64_t i = 0; i < n; ++i) full_nx[i] = km_norm(data + (size_t)i * dim, dim);
-    std::vector<float> cent((size_t)k * dim), ccol, nc, bestd(rows), sums;
-    std::vector<uint32_t> asg(rows), fin(n);
-    std::vector<uint64_t> counts;
-    double best_obj = 0.0;
-    for (uint64_t r = 0; r < nredo; ++r) {
-        Rng redo_rng(seed + r * 0x9e3779b97f4a7c15ull);
-        {   // Forgy
-            std::vector<uint64_t> idx(rows);
-            for (uint64_t i = 0; i < rows; ++i) idx[i] = i;
-            km_shuffle(idx, redo_rng);
-            for (uint64_t c = 0; c < k; ++c) std::memcpy(&cent[(size_t)c * dim], x + idx[c] * dim, sizeof(float) * dim);
-        }
-        for (uint64_t it = 0; it < niter; ++it) {
-            km_views(cent.data(), k, dim, ccol, nc);
-            km_assign(x, nx.data(), rows, dim, k, ccol.data(), nc.data(), asg.data(), bestd.data());
-            counts.assign(k, 0);
-            for (uint64_t i = 0; i < rows; ++i) counts[asg[i]]++;
-            sums.assign((size_t)k * dim, 0.0f);
-#pragma omp parallel
-            {   // coordinate ranges over threads: every (cluster, coordinate) sum stays one ascending-row chain
-#ifdef _OPENMP
-                const uint32_t nt = (uint32_t)omp_get_num_threads(), t = (uint32_t)omp_get_thread_num();
-#else
-                const uint32_t nt = 1, t = 0;
-#endif
-                const uint32_t j0 = (uint32_t)((uint64_t)dim * t / nt), j1 = (uint32_t)((uint64_t)dim * (t + 1) / nt);
-                for (uint64_t i = 0; i < rows; ++i) {
-                    float* s = &sums[(size_t)asg[i] * dim];
-                    const float* xr = x + (size_t)i * dim;
-                    for (uint32_t j = j0; j < j1; ++j) s[j] = s[j] + xr[j];
-                }
-            }
-            // reseed candidates: per chunk the 8 first under (distance desc, row asc)
-            std::vector<uint64_t> pool;
-            for (uint64_t s0 = 0; s0 < rows; s0 += decode_block_size) {
-                const uint64_t e = std::min(rows, s0 + decode_block_size);
-                std::vector<uint64_t> keys;
-                keys.reserve(e - s0);
-                for (uint64_t i = s0; i < e; ++i) keys.push_back(km_cand_key(bestd[i], i));
-                const size_t take = std::min<size_t>(8, keys.size());
-                std::partial_sort(keys.begin(), keys.begin() + take, keys.end(), std::greater<uint64_t>());
-                pool.insert(pool.end(), keys.begin(), keys.begin() + take);
-            }
-            std::sort(pool.begin(), pool.end(), std::greater<uint64_t>());
-            size_t next = 0;
-            for (uint64_t c = 0; c < k; ++c) {
-                float* cc = &cent[(size_t)c * dim];
-                if (counts[c] > 0) {
-                    const float inv = 1.0f / (float)counts[c];
-                    for (uint32_t j = 0; j < dim; ++j) cc[j] = sums[(size_t)c * dim + j] * inv;
-                } else {
-                    uint64_t src;
-                    if (next < pool.size()) src = 0xffffffffull - (pool[next++] & 0xffffffffull);
-                    else { src = redo_rng.next() % rows; ++st_draws; }
-                    ++st_reseed;
-                    std::memcpy(cc, x + src * dim, sizeof(float) * dim);
-                }
-            }
-            if (spherical) {
-                for (uint64_t c = 0; c < k; ++c) {
-                    float* cc = &cent[(size_t)c * dim];
-                    const float nrm = km_norm(cc, dim);
-                    if (nrm > 0.0f) {
-                        const float inv = 1.0f / std::sqrt(nrm);
-                        for (uint32_t j = 0; j < dim; ++j) cc[j] = cc[j] * inv;
-                    }
-                }
-            }
-        }
-        // assignment of the full dataset + objective
-        km_views(cent.data(), k, dim, ccol, nc);
-        km_assign(data, full_nx.data(), n, dim, k, ccol.data(), nc.data(), fin.data(), nullptr);
-        std::vector<double> rd(n);
-#pragma omp parallel for schedule(static)
-        for (int64_t i = 0; i < (int64_t)n; ++i) {
-            const float* xr = data + (size_t)i * dim;
-            const float* cc = &cent[(size_t)fin[i] * dim];
-            double s = 0.0;
-            for (uint32_t j = 0; j < dim; ++j) { double dl = (double)(xr[j] - cc[j]); s = s + dl * dl; }
-            rd[i] = s;
-        }
-        double obj = 0.0;
-        for (uint64_t i = 0; i < n; ++i) obj = obj + rd[i];
-        if (r == 0 || obj < best_obj) {
-            best_obj = obj;
-            std::memcpy(centroids, cent.data(), sizeof(float) * (size_t)k * dim);
-            std::memcpy(assignments, fin.data(), sizeof(uint32_t) * n);
-        }
-    }
-    *objective = best_obj;
-    if (stats) { stats[0] = st_reseed; stats[1] = st_draws; }
+    rbq_host::kmeans_faiss_core(data, n, dim, k, niter, nredo, seed, spherical, max_points_per_centroid, decode_block_size, centroids,
+                                assignments, objective, stats);
     return RBQ_OK;
 }
 
 } // extern "C"
 
 // ---------------------------------------------------------------- MSTG closure assignment (src/mstg/closure.rs:24-107)
-namespace {
-// math::l2_distance_sqr, AVX2 lane order (src/math.rs:216-245)
-float l2_sqr8(const float* a, const float* b, size_t len) {
-    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    size_t chunks = len / 8, i = 0;
-    for (; i < chunks * 8; i += 8)
-        for (int l = 0; l < 8; ++l) { float d = a[i + l] - b[i + l]; float p = d * d; acc[l] = acc[l] + p; }
-    float sum = 0.0f;
-    if (chunks) { sum = -0.0f; for (int l = 0; l < 8; ++l) sum = sum + acc[l]; }
-    for (; i < len; ++i) { float d = a[i] - b[i]; float p = d * d; sum = sum + p; }
-    return sum;
-}
-} // namespace
+using rbq_host::l2_sqr8; // math::l2_distance_sqr, AVX2 lane order (rbq_hcluster.hpp)
 
 extern "C" {
 
@@ -949,5 +766,50 @@ int rbq_build_mstg_select_lists(const float* centroids, uint64_t n_lists, uint32
     }
     return RBQ_OK;
 }
+
+} // extern "C"
+
+// ---------------------------------------------------------------- MSTG hierarchical balanced clustering (src/mstg/clustering.rs)
+struct rbq_hclustered { rbq_host::HcResult r; };
+
+extern "C" {
+
+int rbq_build_hcluster(const float* data, uint64_t n, uint32_t dim, uint64_t max_posting_size, uint64_t branching_factor,
+                       float balance_weight, uint64_t max_iterations, rbq_hclustered** out, const char** detail) {
+    static const char* const kNonFinite = "clustering input must be finite";
+    const char* none = nullptr;
+    if (!detail) detail = &none;
+    *detail = nullptr;
+    if (!out) { *detail = "null out pointer"; return RBQ_INVALID_CONFIG; }
+    *out = nullptr;
+    if ((*detail = rbq_host::hc_check(data, n, dim, max_posting_size, branching_factor, max_iterations))) return RBQ_INVALID_CONFIG;
+    for (uint64_t i = 0; i < n * dim; ++i)
+        if (!std::isfinite(data[i])) { *detail = kNonFinite; return RBQ_INVALID_CONFIG; }
+    const rbq_host::HcParams p{max_posting_size, branching_factor, max_iterations, balance_weight};
+    rbq_host::HcStats st;
+    Rng rng(rbq_host::kHcSeed);
+    std::vector<uint32_t> root(n);
+    for (uint64_t i = 0; i < n; ++i) root[i] = (uint32_t)i;
+    std::vector<std::vector<uint32_t>> fin;
+    if (!rbq_host::hc_subtree(data, dim, std::move(root), p, rng, fin, st)) { *detail = rbq_host::hc_stuck(); return RBQ_INVALID_CONFIG; }
+    rbq_hclustered* h = new rbq_hclustered();
+    h->r.dim = dim;
+    h->r.set_members(fin);
+    h->r.set_stats(st);
+    const uint64_t nc = fin.size();
+    h->r.centroids.resize((size_t)nc * dim);
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t c = 0; c < (int64_t)nc; ++c)
+        rbq_host::hc_centroid(data, dim, h->r.members.data() + h->r.offsets[c], h->r.offsets[c + 1] - h->r.offsets[c],
+                              &h->r.centroids[(size_t)c * dim]);
+    *out = h;
+    return RBQ_OK;
+}
+uint64_t rbq_hclustered_count(const rbq_hclustered* h) { return h->r.offsets.size() - 1; }
+const float* rbq_hclustered_centroids(const rbq_hclustered* h) { return h->r.centroids.data(); }
+const uint64_t* rbq_hclustered_offsets(const rbq_hclustered* h) { return h->r.offsets.data(); }
+const uint32_t* rbq_hclustered_members(const rbq_hclustered* h) { return h->r.members.data(); }
+const uint64_t* rbq_hclustered_stats(const rbq_hclustered* h) { return h->r.stats; }
+void rbq_hclustered_free(rbq_hclustered* h) { delete h; }
 
 } // extern "C"

@@ -69,6 +69,26 @@ int rbq_build_closure_assign(const float* centroids, uint64_t n_lists, uint32_t 
  * +inf, selects nothing.  RBQ_INVALID_CONFIG: a null pointer, n_lists == 0 or >= 2^32 - 1, dim == 0. */
 int rbq_build_mstg_select_lists(const float* centroids, uint64_t n_lists, uint32_t dim, const float* queries, uint64_t nq,
                                 uint32_t ef_search, float pruning_epsilon, uint32_t* out_lists, uint32_t* out_counts);
+
+/* HierarchicalClustering{max_cluster_size, branching_factor, balance_weight, max_iterations}.cluster(data) (reference
+ * src/mstg/clustering.rs), step 1 of MstgIndex::build, in the pinned arithmetic stated in rbq_hcluster.hpp: the specification
+ * of rbq_mstg_cluster_device (include/rbq_mstg.h), which equals it bit for bit.  data [n][dim], finite.  The handle holds the
+ * final clusters in the crate's pop order: centroids [count][dim], offsets [count + 1], members [n] (row indices, cluster by
+ * cluster, each in its own order) and stats [6]: splits, balance moves, empty clusters reseeded, reseeds drawn from the RNG,
+ * host splits (0 here) and arena bytes (0 here).
+ * RBQ_INVALID_CONFIG, with a static message in *detail (nullable): a null pointer, n == 0, dim == 0, n >= 2^32 - 1,
+ * max_iterations == 0, branching_factor < 2 or > max_posting_size + 1, a non-finite value; and, found while running, a split
+ * that leaves a single non-empty subcluster (the crate would loop for ever).  Any balance_weight is taken: NaN or <= 0 means
+ * no balancing. */
+typedef struct rbq_hclustered rbq_hclustered;
+int rbq_build_hcluster(const float* data, uint64_t n, uint32_t dim, uint64_t max_posting_size, uint64_t branching_factor,
+                       float balance_weight, uint64_t max_iterations, rbq_hclustered** out, const char** detail);
+uint64_t        rbq_hclustered_count(const rbq_hclustered* h);
+const float*    rbq_hclustered_centroids(const rbq_hclustered* h);
+const uint64_t* rbq_hclustered_offsets(const rbq_hclustered* h);
+const uint32_t* rbq_hclustered_members(const rbq_hclustered* h);
+const uint64_t* rbq_hclustered_stats(const rbq_hclustered* h);
+void            rbq_hclustered_free(rbq_hclustered* h);
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,11 @@ def lib():
                                                    vp]
         L.rbq_mstg_debug_search_fallbacks.restype = C.c_uint64
         L.rbq_mstg_debug_search_fallbacks.argtypes = []
+        L.rbq_mstg_cluster_device.restype = C.c_int
+        L.rbq_mstg_cluster_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_uint64, C.c_uint64,
+                                              C.c_int, C.POINTER(vp)]
+        from .builder import bind_hclustered
+        bind_hclustered(L)
         _LIB = L
     return _LIB
 

@@ -5,7 +5,9 @@ centroids, dynamic_prune and the posting-list scan.
 
 The arithmetic is the crate's on an AVX2 host; `closure_assign_cpu` (csrc/host/rbq_build.cpp) restates it on the CPU and the
 device result equals it exactly; `select_lists_cpu` does the same for the search's list selection
-(section 16).  Clustering and the HNSW stay with the caller; the HNSW is not needed for searching through this library."""
+(section 16).  Step 1, `HierarchicalClustering::cluster` (src/mstg/clustering.rs), is `hierarchical_cluster` (restated by
+`hierarchical_cluster_cpu`, section 17), and `MstgIndex` strings the steps together as the crate's Python binding does.  The HNSW
+over the centroids is not built: the search ranks the centroids exactly."""
 import ctypes as C
 from dataclasses import dataclass
 
@@ -212,3 +214,131 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
                                        sc.ctypes.data, cnt.ctypes.data, li.ctypes.data if return_lists else None,
                                        lc.ctypes.data if return_lists else None))
     return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
+
+
+def _hc_args(max_posting_size, branching_factor, max_iterations):
+    from . import RabitqError
+    v = [int(max_posting_size), int(branching_factor), int(max_iterations)]
+    if min(v) < 0:
+        raise RabitqError(_abi.RBQ_INVALID_CONFIG, "max_posting_size, branching_factor and max_iterations must not be negative")
+    return v
+
+
+def hierarchical_cluster_cpu(data, max_posting_size, branching_factor=10, balance_weight=1.0, max_iterations=100, device=None,
+                             host_below=None):
+    """`HierarchicalClustering{max_posting_size, branching_factor, balance_weight, max_iterations}.cluster(data)` on the CPU
+    (rbq_build_hcluster): (centroids [count][dim] f32, offsets [count + 1] u64, members [n] u32, stats) with the final clusters
+    in the crate's pop order and every cluster's rows in its own order.  `device` and `host_below` are accepted and ignored, so
+    that both functions take the same arguments."""
+    from . import RabitqError, builder
+    x = _host_f32(data)
+    if len(x.shape) != 2:
+        raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data [n][dim]")
+    n, dim = int(x.shape[0]), int(x.shape[1])
+    mps, k, it = _hc_args(max_posting_size, branching_factor, max_iterations)
+    h, detail = C.c_void_p(), C.c_char_p()
+    L = builder.lib()
+    rc = L.rbq_build_hcluster(x.ctypes.data if n and dim else None, n, dim, mps, k, float(balance_weight), it, C.byref(h), C.byref(detail))
+    if rc != _abi.RBQ_OK:
+        raise RabitqError(rc, (detail.value or b"").decode())
+    return builder.take_hclustered(L, h, n, dim)
+
+
+def hierarchical_cluster(data, max_posting_size, branching_factor=10, balance_weight=1.0, max_iterations=100, device=None,
+                         host_below=None):
+    """The same on the GPU (rbq_mstg_cluster_device), bit for bit.  `data` is a NumPy array (uploaded once) or a CUDA tensor (used
+    in place).  A cluster of at most `host_below` rows is handed to the host with its whole subtree (small splits are bound by
+    launch latency); the result does not depend on it.  None takes the library's default, 0 never hands over."""
+    from . import RabitqError, builder
+    from .index import _check, lib
+    if len(data.shape) != 2:
+        raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data [n][dim]")
+    n, dim = int(data.shape[0]), int(data.shape[1])
+    mps, k, it = _hc_args(max_posting_size, branching_factor, max_iterations)
+    dev = -1 if device is None else int(device)
+    xp, _x = _ptr(data, dev)
+    hb = HOST_BELOW_DEFAULT if host_below is None else int(host_below)
+    h = C.c_void_p()
+    L = lib()
+    _check(L.rbq_mstg_cluster_device(xp if n and dim else None, n, dim, mps, k, float(balance_weight), it, hb, dev, C.byref(h)))
+    return builder.take_hclustered(L, h, n, dim)
+
+
+HOST_BELOW_DEFAULT = 0xFFFFFFFFFFFFFFFF  # RBQ_MSTG_HOST_BELOW_DEFAULT: let the library choose
+
+_METRICS = {"euclidean": 0, "l2": 0, "angular": 1, "ip": 1, "inner_product": 1}
+
+
+class MstgIndex:
+    """The crate's `PyMstgIndex` (src/python_bindings.rs) on the GPU: the same constructor arguments and defaults, `fit`,
+    `set_query_arguments`, `query`, `batch_query`.  `fit` runs hierarchical_cluster and build_postings_on_device, so the
+    dimension must be a multiple of 16; queries go through mstg_search.
+
+    `hnsw_m`, `hnsw_ef_construction` and `centroid_precision` are accepted and recorded, and unused: the crate needs them for the
+    HNSW over its (quantised) centroids, while this library ranks the full-precision centroids exactly (rbq_mstg.h, "the
+    selection").  `save` / `load` are not provided.  As in the crate, results are [count][2] f32 arrays of (id, distance), which
+    hold ids exactly only below 2^24; `mstg_search(index.handle, ...)` returns u64 ids."""
+
+    def __init__(self, dimension, metric="euclidean", max_posting_size=16, branching_factor=10, balance_weight=1.0,
+                 closure_epsilon=0.15, max_replicas=8, rabitq_bits=7, faster_config=True, hnsw_m=32, hnsw_ef_construction=400,
+                 centroid_precision="bf16", default_ef_search=150, pruning_epsilon=0.6, device=None, max_iterations=100,
+                 host_below=None):
+        if metric not in _METRICS:
+            raise ValueError(f"Invalid metric: {metric}. Use 'euclidean' or 'angular'")
+        if centroid_precision not in ("fp32", "bf16", "fp16", "int8"):
+            raise ValueError(f"Invalid precision: {centroid_precision}. Use 'fp32', 'bf16', 'fp16', or 'int8'")
+        self.dimension, self.metric = int(dimension), _METRICS[metric]
+        self.max_posting_size, self.branching_factor, self.balance_weight = int(max_posting_size), int(branching_factor), float(balance_weight)
+        self.closure_epsilon, self.max_replicas = float(closure_epsilon), int(max_replicas)
+        self.rabitq_bits, self.faster_config = int(rabitq_bits), bool(faster_config)
+        self.hnsw_m, self.hnsw_ef_construction, self.centroid_precision = int(hnsw_m), int(hnsw_ef_construction), centroid_precision
+        self.default_ef_search, self.pruning_epsilon = int(default_ef_search), float(pruning_epsilon)
+        self.device, self.max_iterations, self.host_below = device, int(max_iterations), host_below
+        self.handle, self.centroids, self.cluster_stats, self._n = None, None, None, 0
+
+    def fit(self, data):
+        if len(data.shape) != 2:
+            raise ValueError("Data must be 2D array (N x D)")
+        if data.shape[1] != self.dimension:
+            raise ValueError(f"Data dimension {data.shape[1]} does not match expected {self.dimension}")
+        cent, _off, _mem, st = hierarchical_cluster(data, self.max_posting_size, self.branching_factor, self.balance_weight,
+                                                    self.max_iterations, self.device, self.host_below)
+        self.handle = build_postings_on_device(data, cent, self.rabitq_bits, self.metric, self.closure_epsilon, self.max_replicas,
+                                               self.faster_config, self.device)
+        self.centroids, self.cluster_stats, self._n = cent, st, int(data.shape[0])
+        return self
+
+    def set_query_arguments(self, ef_search=None, pruning_epsilon=None):
+        if ef_search is not None:
+            self.default_ef_search = int(ef_search)
+        if pruning_epsilon is not None:
+            self.pruning_epsilon = float(pruning_epsilon)
+
+    def _built(self):
+        if self.handle is None:
+            raise RuntimeError("Index not built yet. Call fit() first.")
+        return self.handle
+
+    def batch_query(self, queries, k):
+        h = self._built()
+        q = _host_f32(queries)
+        if len(q.shape) != 2:
+            raise ValueError("Queries must be 2D array (N x D)")
+        if q.shape[1] != self.dimension:
+            raise ValueError(f"Query dimension {q.shape[1]} does not match expected {self.dimension}")
+        ids, dist, cnt = mstg_search(h, q, k, self.default_ef_search, self.pruning_epsilon)
+        return [np.stack([ids[i, :cnt[i]].astype(np.float32), dist[i, :cnt[i]]], axis=1) for i in range(q.shape[0])]
+
+    def query(self, query, k):
+        q = _host_f32(query)
+        if q.ndim != 1 or q.shape[0] != self.dimension:
+            raise ValueError(f"Query dimension {q.shape[-1] if q.ndim else 0} does not match expected {self.dimension}")
+        return self.batch_query(q[None, :], k)[0]
+
+    def __len__(self):
+        return self._n
+
+    def __repr__(self):
+        built = f"{self._n} vectors, {len(self.centroids)} posting lists" if self.handle is not None else "not built"
+        return (f"MstgIndex(dimension={self.dimension}, metric={'l2' if self.metric == 0 else 'ip'}, "
+                f"max_posting_size={self.max_posting_size}, rabitq_bits={self.rabitq_bits}, {built})")
