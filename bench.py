@@ -24,6 +24,15 @@ region (`timed_regions`, `region_ms`).
 float32 .npy files) and the batch's queries.  Inputs are seeded and the harness k-means is deterministic, so two runs with the
 same arguments search the same index with the same queries and their dumps can be compared file by file.
 
+A plain run (no --full) does what the headline figure needs and nothing else: it builds the index and the exact ground truth,
+warms up, times the K steps, writes --dump-outputs, measures the recall that `metric` states (every batch once more on one
+stream, against the ground truth) and prints the line; every object below `value / ms_per_step` is then null.  --full adds the
+supplementary legs (each takes GPU or CPU runs of its own): the counter pass behind `pruned`, `roofline`, the per-stage pass and
+`regime`, the GPU encoder comparison, `host_call` / `pcie_inclusive`, `latency`, `self_check`, `datasets`, `sensitivity` and
+`cpu_baseline`; --no-cpu, --no-extras, --no-latency, --ab and --no-wave-roofline trim a --full run and mean nothing without it.
+The timed region, its inputs and the dumped arrays are the same with and without --full.  (--in-library is a mode of its own:
+one measurement with its own checks, the same with and without --full.)
+
 Prints one JSON line (rank 0).  What the objects mean:
   value / ms_per_step   whole path, queries and results resident in HBM, batches pipelined over --streams HIP streams
   roofline              k_scan with the block-level bound switched OFF (every probed block streamed, results
@@ -99,6 +108,9 @@ def parse():
     ap.add_argument("--batch", type=int, default=HEADLINE["batch"])
     ap.add_argument("--top-k", type=int, default=HEADLINE["top_k"])
     ap.add_argument("--nbatches", type=int, default=32, help="distinct query batches the steps rotate through")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the supplementary legs (counter pass, roofline, per-stage pass, GPU encoder comparison, host entry, "
+                         "latency, self check, other data sets, CPU baseline); without it only what the headline figure needs runs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample duration")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--ab", action="store_true", help="kernel A/B runs: only the per-stage pass of the supplementary legs")
@@ -405,8 +417,9 @@ def main():
                                # device encoder produces the identical index (tests/test_gpu_parity.py)
     if a.stream_build:
         a.device_build = True
-    extras = not a.no_extras and not a.ab and rank == 0
-    stage_pass = (extras or a.ab) and rank == 0
+    full = a.full  # the supplementary legs run only on request; every flag below that trims them presupposes it
+    extras = full and not a.no_extras and not a.ab and rank == 0
+    stage_pass = full and (extras or a.ab) and rank == 0
     is_headline = all(getattr(a, k) == v for k, v in HEADLINE.items()) and a.dataset == "mixture_id32"
 
     def progress(msg):
@@ -851,9 +864,12 @@ def main():
         print(json.dumps(out))
         return
 
-    mark("timed regions + counter pass")
+    mark("timed regions + counter pass" if full else "timed regions")
     ns = max(1, a.streams)
-    dts, own_dts, prof = run_measured(idx, q_all, a.nprobe, a.steps, a.warmup, ns, gather=True, min_seconds=a.min_seconds)
+    if full:
+        dts, own_dts, prof = run_measured(idx, q_all, a.nprobe, a.steps, a.warmup, ns, gather=True, min_seconds=a.min_seconds)
+    else:  # the same timed regions, without the untimed counter pass behind them
+        dts, own_dts, prof = run_timed(idx, q_all, a.nprobe, a.steps, a.warmup, ns, True, a.min_seconds, counters=False)
     last = prof.pop("last_out")
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, last["ids"].cpu().numpy().view(np.uint64), last["scores"].cpu().numpy(),
@@ -874,14 +890,15 @@ def main():
     ids_all = search_ids(idx, q_all, a.nprobe)
     gtn = gt.cpu().numpy().reshape(NB, a.batch, a.top_k)
     recall = recall_of(ids_all.reshape(-1, a.top_k), gtn.reshape(-1, a.top_k), a.top_k)
-    pruned = pruned_object(prof, prof["counter_steps"])
+    pruned = pruned_object(prof, prof["counter_steps"]) if full else None
 
     # the roofline figure: the same kernel with the block-level bound switched off streams EVERY probed block — the
     # algorithmic bytes are really moved (results identical, only the work changes); one stream, k_scan alone on the chip
-    mark("roofline leg (block bound off) + per-stage pass")
+    if full:
+        mark("roofline leg (block bound off) + per-stage pass")
     roofline = None
     serial = None
-    if rank == 0:
+    if rank == 0 and full:
         n_rf = max(6, min(a.steps // 4, 50))
         idx.set_option("block_bound", 0)
         _, _, p2 = run_timed(idx, q_all, a.nprobe, n_rf, 2, 1, gather=False)
@@ -941,7 +958,8 @@ def main():
 
     # the host-buffer entry point (rbq_search_batch: H2D of the queries, the four kernels, D2H of the results) — what a
     # CPU-side caller such as the Rust shim binds (src/ivf.rs:1743-1752)
-    mark("host entry legs")
+    if full:
+        mark("host entry legs")
     pcie = None
     host_call = None
     if extras:
@@ -1062,7 +1080,8 @@ def main():
                         "approach the device-resident rate.  `value` is the device-resident rate; these are the rates a host-side "
                         "caller sees.")
 
-    mark("latency leg")
+    if full:
+        mark("latency leg")
     latency = latency_leg() if (extras and not a.no_latency) else None
     if host_call is not None and latency is not None and "64" in latency:
         host_call["model_us_per_call"] = a.batch / (value / world) * 1e6 + latency["64"]["p50_us"]
@@ -1070,7 +1089,8 @@ def main():
     # Self-check for indexes no CPU oracle run can cover (device-built: cfg5 at 100 M vectors): the first 256 queries again
     # with every shortcut switched off — canonical all-pairs ranking instead of the MFMA shortlist, BinaryHeap emulation from
     # the first candidate, no block-level bound — must give the same bits.
-    mark("self check")
+    if full:
+        mark("self check")
     self_check = None
     if extras:
         nsc = min(256, a.batch)
@@ -1096,9 +1116,11 @@ def main():
                                  "first candidate) and block_bound=0 (every probed block scanned)"}
 
     # second data set of the pair (rank 0, headline workload only): SURVEY 8d's isotropic mixture
-    mark("second data set")
-    datasets = {a.dataset: {"recall_at_k": recall, "queries_per_s": value / world, "nprobe": a.nprobe,
-                            "block_skip_frac": pruned["block_skip_frac"], "role": "headline"}}
+    datasets = None
+    if full:
+        mark("second data set")
+        datasets = {a.dataset: {"recall_at_k": recall, "queries_per_s": value / world, "nprobe": a.nprobe,
+                                "block_skip_frac": pruned["block_skip_frac"], "role": "headline"}}
     if extras and is_headline:
         del x
         torch.cuda.empty_cache()
@@ -1134,9 +1156,10 @@ def main():
     # wait.  Per stage: the kernel instantiation this call shape launches and what it occupies (rbq_debug_stage_resources: live,
     # from the code object), its duration alone and under overlap (HIP events on the dispatch packets); resident wave-time per
     # step against the wave slots the chip offers in one step time.
-    mark("regime + sensitivity")
+    if full:
+        mark("regime + sensitivity")
     regime = None
-    if rank == 0:
+    if rank == 0 and full:
         try:
             res = idx.stage_resources(a.batch, a.top_k, a.nprobe)
         except Exception as e:  # noqa: BLE001
@@ -1245,6 +1268,7 @@ def main():
         "vs_baseline": None,
         "dtype": "u8",
         "data": "synthetic",
+        "full": full,  # False: a plain run, the supplementary objects below are null
         # (the driver's record keeps `config` with its values but cuts strings at 128 characters and keeps only the NAMES of other
         # top-level objects: the short workload string and the numbers a reader of the one line needs live here)
         "config": {"workload": f"synthetic {a.dataset} N={a.n} d={a.dim} nlist={a.nlist} {a.bits}-bit {'L2' if a.metric == 0 else 'IP'} nprobe={a.nprobe} "
@@ -1282,8 +1306,9 @@ def main():
         "datasets": datasets,
     }
 
-    mark("cpu baseline")
-    if rank == 0 and world == 1 and not a.no_cpu and built is not None:
+    if full:
+        mark("cpu baseline")
+    if full and rank == 0 and world == 1 and not a.no_cpu and built is not None:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle  # CPU oracle: checker + reported baseline only
         qh0 = q_all[0].cpu().numpy()

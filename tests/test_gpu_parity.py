@@ -607,7 +607,7 @@ def test_bench_two_rank_rehearsal():
     env = dict(os.environ, RBQ_BENCH_REHEARSAL="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-extras", "--nbatches", "3", "--min-seconds", "0", "--no-latency"], env=env,
+                          "--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--no-extras", "--nbatches", "3", "--min-seconds", "0", "--no-latency"], env=env,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -632,7 +632,7 @@ def test_bench_rccl_single_rank_group():
     env.pop("RBQ_BENCH_REHEARSAL", None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                          "--gpus", "1", "--steps", "12", "--warmup", "2", "--no-extras", "--no-cpu", "--nbatches", "4", "--min-seconds", "0", "--no-latency"], env=env,
+                          "--gpus", "1", "--steps", "12", "--warmup", "2", "--full", "--no-extras", "--no-cpu", "--nbatches", "4", "--min-seconds", "0", "--no-latency"], env=env,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -433,7 +433,7 @@ def test_full_size_baseline_configs_properties(name, n, dim, nlist, bits, metric
         inside the index; recall@10 against exact f32 brute force is at the level bench.py reports.
     And, since round 3, the oracle itself on the first 128 queries: the CPU build of the same index (arrays byte-identical to
     the device encoder's) searched by oracle.search_batch — ids, counts and SearchDiagnostics exactly, scores at 1e-4.
-    (bench.py also compares two 1024-query batches of the full-size cfg3 index with the oracle on every run.)"""
+    (bench.py also compares two 1024-query batches of the full-size cfg3 index with the oracle on every --full run.)"""
     import torch
     import bench
     dev = torch.device("cuda", 0)

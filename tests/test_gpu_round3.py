@@ -151,7 +151,7 @@ def test_bench_gpus_2_starts_itself():
     """`python bench.py --gpus 2` with NO torchrun wrapper: bench.py starts its two ranks as a child process (before it
     touches the GPU), relays their JSON line and exit code.  Two ranks share this one GPU over gloo here
     (RBQ_BENCH_REHEARSAL); on an 8-GPU node the same path runs RCCL."""
-    d = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--no-extras", "--nbatches", "3", "--min-seconds", "0", "--no-latency",
+    d = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--no-extras", "--nbatches", "3", "--min-seconds", "0", "--no-latency",
                     "--n", "200000", "--nlist", "1024", "--nprobe", "32"], {"RBQ_BENCH_REHEARSAL": "1"})
     assert d["n_gpus"] == 2 and d["value"] > 0 and len(d["per_rank_queries_per_s"]) == 2 and all(v > 0 for v in d["per_rank_queries_per_s"])
     assert d["rccl_world_size"] is None  # gloo rehearsal: no RCCL group

@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 for v in "$@"; do
   if [ "$v" = default ]; then unset RBQ_LIB_PATH; else export RBQ_LIB_PATH=$PWD/rabitq-rs_amd/csrc/variants/librbq_$v.so; fi
-  python bench.py --steps 40 --no-cpu --ab ${BENCH_ARGS} 2>/dev/null | python -c "
+  python bench.py --full --steps 40 --no-cpu --ab ${BENCH_ARGS} 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -2,7 +2,7 @@
 # tools/final_records.sh : the bench records committed under profiles/rN/ (GPU box; writes gpurun_out/final/*.json)
 cd "$(dirname "$0")/.."
 out=gpurun_out/final; rm -rf $out; mkdir -p $out
-run() { name=$1; shift; python bench.py "$@" 2> $out/$name.err | grep '^{' | tail -n 1 > $out/$name.json; python - $out/$name.json <<'PY'
+run() { name=$1; shift; python bench.py --full "$@" 2> $out/$name.err | grep '^{' | tail -n 1 > $out/$name.json; python - $out/$name.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); p = d.get('pruned') or {}
 rec = [v for k, v in d.items() if k.startswith('recall_at')]

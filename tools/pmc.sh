@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 out=$1; shift
-rocprofv3 --kernel-trace --pmc $1 --output-format csv -d $out -- python3 bench.py --steps 3 --warmup 1 --no-cpu ${BENCH_ARGS} > $out.log 2>&1
+rocprofv3 --kernel-trace --pmc $1 --output-format csv -d $out -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu ${BENCH_ARGS} > $out.log 2>&1
 python3 - "$out" <<'PY'
 import sys, glob, csv, collections
 d = collections.defaultdict(lambda: collections.defaultdict(list))

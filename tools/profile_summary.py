@@ -35,7 +35,7 @@ if b:
           f"pruned: {b['pruned']['avg_launch_ms']:.4f} ms/launch overlapped, {b['pruned']['bytes_requested_per_launch'] / 1e9:.3f} GB requested, "
           f"skip {b['pruned']['block_skip_frac']:.4f}\n")
 
-print("## `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --no-cpu --no-extras`\n")
+print("## `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --no-cpu --no-extras`\n")
 ns = b["config"]["streams"] if b else "N"
 print(f"One process: {ns} setup + 8 warm-up + 20 timed steps on {ns} streams (bound on, every step a different batch; traffic counters off), "
       f"{ns} setup + 32 launches of the counter pass (the same batches, counters on), 32 single-stream verification launches, then the "

@@ -3,7 +3,7 @@
 # Per-configuration records carry cpu_baseline and the oracle id check (round-3 VERDICT item 6).
 cd "$(dirname "$0")/.."
 out=gpurun_out/final_r5; rm -rf $out; mkdir -p $out
-run() { name=$1; shift; python bench.py "$@" 2> $out/$name.err | grep '^{' | tail -n 1 > $out/$name.json; python - $out/$name.json <<'PY'
+run() { name=$1; shift; python bench.py --full "$@" 2> $out/$name.err | grep '^{' | tail -n 1 > $out/$name.json; python - $out/$name.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); p = d.get('pruned') or {}
 rec = [v for k, v in d.items() if k.startswith('recall_at')]
