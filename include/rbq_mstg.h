@@ -8,7 +8,8 @@
  * (src/mstg/index.rs:149-213, 340-346) in one call: the centroid ranking and dynamic_prune run on the device too.
  * Step 1, the hierarchical balanced clustering that yields the centroids (HierarchicalClustering::cluster,
  * src/mstg/clustering.rs), is rbq_mstg_cluster_device.  Step 4 (HNSW over the centroids) is not built: it is not needed for
- * searching through this library.  A header of its own, not included by rbq.h (DESIGN.md sections 15, 16, 17).
+ * searching through this library.  A header of its own, not included by rbq.h (DESIGN.md sections 15, 16, 17).  Saving and
+ * loading the result in the crate's `.mstg` format: rbq_mstg_persist.h (section 18).
  */
 #ifndef RBQ_MSTG_H
 #define RBQ_MSTG_H
@@ -17,6 +18,7 @@
 #include <stdint.h>
 
 #include "rbq.h"
+#include "rbq_mstg_persist.h" /* rbq_mstg_save* / rbq_mstg_load*: the crate's `.mstg` file */
 
 #ifdef __cplusplus
 extern "C" {

@@ -16,6 +16,8 @@ Mirrors the reference's public query API for this path:
                                src/mstg/index.rs:149-213,340-362 (mstg.py)
   hierarchical_cluster / hierarchical_cluster_cpu / MstgIndex: HierarchicalClustering::cluster, PyMstgIndex
                                src/mstg/clustering.rs, src/python_bindings.rs (mstg.py)
+  save_mstg / load_mstg, MstgIndex.save / load / get_memory_usage: MstgIndex::save_main_index / load_main_index
+                               src/mstg/io.rs:129-245 (mstg.py)
 All compute goes through the C ABI of include/rbq.h (csrc/librbq.so, hand-written HIP for
 gfx950). There is no CPU fallback: if the HIP library is missing or no GPU is present the
 calls raise.
@@ -78,10 +80,10 @@ from . import builder  # noqa: E402,F401
 from .bruteforce import BruteForceRabitqIndex, BruteForceSearchParams, BruteForceSearchResult  # noqa: E402
 from .kmeans import KMeansConfig, KMeansResult, run_kmeans_with_config  # noqa: E402
 from .mstg import (MstgIndex, MstgSearchParams, build_postings_on_device, closure_assign, closure_assign_cpu,  # noqa: E402
-                   hierarchical_cluster, hierarchical_cluster_cpu, mstg_search, select_lists_cpu)
+                   hierarchical_cluster, hierarchical_cluster_cpu, load_mstg, mstg_search, save_mstg, select_lists_cpu)
 
 __all__ = ["Metric", "RotatorType", "RabitqError", "SearchParams", "SearchResult", "IvfRabitqIndex",
            "StreamBuilder", "builder", "BruteForceRabitqIndex", "BruteForceSearchParams", "BruteForceSearchResult",
            "KMeansConfig", "KMeansResult", "run_kmeans_with_config", "closure_assign", "closure_assign_cpu",
            "build_postings_on_device", "MstgSearchParams", "mstg_search", "select_lists_cpu", "hierarchical_cluster",
-           "hierarchical_cluster_cpu", "MstgIndex"]
+           "hierarchical_cluster_cpu", "MstgIndex", "save_mstg", "load_mstg"]

@@ -43,3 +43,27 @@ class BfView(C.Structure):
     """rbq_bf_view: the per-vector arrays of a brute-force index."""
     _fields_ = [("n", C.c_uint64), ("bin_codes", C.POINTER(C.c_uint8)), ("ex_codes", C.POINTER(C.c_uint8)),
                 ("ex_len", C.c_uint64)] + [(f, C.POINTER(C.c_float)) for f in BF_FACTORS]
+
+
+MSTG_CONFIG_FIELDS = ("max_posting_size", "branching_factor", "balance_weight", "closure_epsilon", "max_replicas", "rabitq_bits",
+                      "faster_config", "metric", "hnsw_m", "hnsw_ef_construction", "centroid_precision", "default_ef_search",
+                      "pruning_epsilon")
+MSTG_PRECISIONS = ("fp32", "bf16", "fp16", "int8")  # ScalarPrecision's variant order (src/mstg/config.rs)
+
+
+class MstgConfig(C.Structure):
+    """rbq_mstg_config (include/rbq_mstg_persist.h): the crate's MstgConfig, field for field."""
+    _fields_ = [("max_posting_size", C.c_uint64), ("branching_factor", C.c_uint64), ("balance_weight", C.c_float),
+                ("closure_epsilon", C.c_float), ("max_replicas", C.c_uint64), ("rabitq_bits", C.c_uint64),
+                ("faster_config", C.c_uint8), ("metric", C.c_uint32), ("hnsw_m", C.c_uint64),
+                ("hnsw_ef_construction", C.c_uint64), ("centroid_precision", C.c_uint32), ("default_ef_search", C.c_uint64),
+                ("pruning_epsilon", C.c_float)]
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(**{f: (int(bool(d[f])) if f == "faster_config" else d[f]) for f in MSTG_CONFIG_FIELDS})
+
+    def to_dict(self):
+        d = {f: getattr(self, f) for f in MSTG_CONFIG_FIELDS}
+        d["faster_config"] = bool(d["faster_config"])
+        return d

@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from ._abi import BF_FACTORS, ROTATOR_FHT_KAC, BfView, Header, ListView, RBQ_OK
+from ._abi import BF_FACTORS, ROTATOR_FHT_KAC, BfView, Header, ListView, MstgConfig, RBQ_OK
 
 # the device library's message for a padded_dim that is not a multiple of 16 (validate_header); the CPU builders return only the code
 NOT_MULTIPLE_OF_16 = "Dimension must be multiple of 16 for SIMD"
@@ -36,6 +36,10 @@ def lib():
         L.rbq_built_t_const.argtypes = [C.c_void_p]
         L.rbq_built_list_recon.restype = C.c_int
         L.rbq_built_list_recon.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float))]
+        L.rbq_built_list_residual_norm.restype = C.c_int
+        L.rbq_built_list_residual_norm.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.POINTER(C.c_float))]
+        L.rbq_build_mstg_file_check.restype = C.c_int
+        L.rbq_build_mstg_file_check.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(MstgConfig), C.c_void_p]
         L.rbq_built_free.argtypes = [C.c_void_p]
         L.rbq_built_save_rbq1.restype = C.c_int
         L.rbq_built_save_rbq1.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
@@ -166,6 +170,13 @@ class BuiltIndex:
                 "f_add_ex": arr(lv.f_add_ex, (n,), np.float32), "f_rescale_ex": arr(lv.f_rescale_ex, (n,), np.float32),
                 "delta": arr(d, (n,), np.float32), "vl": arr(v, (n,), np.float32)}
 
+    def list_residual_norm(self, c):
+        """QuantizedVector::residual_norm of list c's vectors (what the `.mstg` format stores next to the other factors)."""
+        n = int(self.lists_ptr[c].n)
+        p = C.POINTER(C.c_float)()
+        assert lib().rbq_built_list_residual_norm(self._h, c, C.byref(p)) == RBQ_OK
+        return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.float32)
+
     def rotator_blob(self):
         h = self.header
         return bytes(np.ctypeslib.as_array(h.rotator_blob, shape=(int(h.rotator_len),))) if h.rotator_len else b""
@@ -212,6 +223,19 @@ def train_with_clusters(data, centroids, assignments, total_bits, metric, rotato
         raise RabitqError(rc, NOT_MULTIPLE_OF_16 if rotator_type != ROTATOR_FHT_KAC and dim % 16 else
                           "train_with_clusters rejected its configuration")
     return BuiltIndex(h)
+
+
+def mstg_file_check(data):
+    """The `.mstg` loader's validation on the CPU (rbq_build_mstg_file_check): (code, detail, config dict or None, info dict or
+    None) — framing, every record's inner fields and the checksum, as rbq_mstg_load refuses or accepts them."""
+    data = (C.c_uint8 * len(data)).from_buffer_copy(bytes(data))  # an exact-size heap copy: a read past the end is a sanitizer report
+    detail = C.create_string_buffer(512)
+    cfg = MstgConfig()
+    out = np.zeros(4, np.uint64)
+    rc = lib().rbq_build_mstg_file_check(data, len(data), detail, 512, C.byref(cfg), out.ctypes.data)
+    if rc != RBQ_OK:
+        return rc, detail.value.decode(), None, None
+    return rc, "", cfg.to_dict(), dict(zip(("lists", "vectors", "dim", "ex_bits"), (int(v) for v in out)))
 
 
 def best_rescale_factor(o_abs, ex_bits):

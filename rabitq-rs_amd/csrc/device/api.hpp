@@ -1,5 +1,5 @@
 // api.hpp — internal header of librbq.so's host side: the C ABI of include/rbq.h over the HIP kernels, which the host
-// units (api_index, api_build, api_search, api_save, api_fetch, api_bf, api_mstg) reach through launch.hpp.  Not installed.
+// units (api_index, api_build, api_search, api_save, api_fetch, api_bf, api_mstg, api_mstg_persist) reach through launch.hpp.  Not installed.
 // Host responsibilities: validate like the reference (src/ivf.rs:1754-1769,1484-1702), upload the reference's ClusterData
 // bytes and have the GPU re-lay them into the device layout (one-time, at create/load), own HBM on one or N devices
 // (replicas), and enqueue prep -> rank -> select -> scan for each query batch.  There is no CPU compute path: every failure
@@ -352,6 +352,7 @@ struct Options {
                                   // pipelined run 2-3 %, bench.py collects them in a pass of their own)
     uint64_t save_chunk = 0;  // TEST ONLY: staging chunk of rbq_index_save_rbq1_stream in bytes (0 = default)
     uint64_t fetch_chunk = 0; // TEST ONLY: ids per staging chunk of rbq_index_fetch_embeddings (0 = default)
+    uint64_t mstg_chunk = 0;  // TEST ONLY: staging chunk of rbq_mstg_save* in bytes, any value >= 1 (0 = default)
     uint64_t mstg_search_budget = 0; // TEST ONLY: per-chunk workspace of rbq_mstg_search_batch* in bytes (0 = default)
     // option `name` := value (the options of rbq_debug_set_option that live in Options); RBQ_INVALID_CONFIG for an unknown name
     int set(const char* name, int value);
@@ -368,6 +369,11 @@ struct Replica : Geometry {
     // reconstruction factors delta / vl of every slot (RBQ1's per-vector arrays that search never reads): kept on the FIRST
     // replica only, for rbq_index_save_rbq1 (not in `arrays`: clone_replica does not copy them)
     Arr delta, vl;
+    // MSTG handles only (rbq_mstg_build_device, rbq_mstg_load*; FIRST replica, slot order, pad slots 0): QuantizedVector::residual_norm,
+    // which the `.mstg` format stores and no search reads — 4 bytes per vector — and the RabitqConfig::t_const the lists were built with
+    Arr rnorm;
+    bool has_rnorm = false, tc_some = false;
+    float tc_value = 0.0f;
     bool has_recon = false; // false: created by rbq_index_create (no factors given) — such a handle cannot be saved
     // fetch_embedding's id map (FIRST replica only): every vector's id, ascending (stably sorted: the first (cluster, position)
     // occurrence first), and its slot — 12 bytes per vector, built by the first fetch under fetch_mu, kept until destroy

@@ -124,6 +124,12 @@ int build_device_pairs(const rbq_header* hdr, const float* centroids, const floa
     }
     if ((rc = encoder_prepare(ix, hdr, centroids, ln, gb0, /*zero_fill=*/false))) return rc;
     const uint64_t nblocks = ix->n_blocks, nslots = nblocks * 32;
+    if (ix->rotator == RBQ_ROTATOR_NONE) { // a posting-list handle: what the `.mstg` format stores beyond the search's arrays
+        if ((rc = alloc_arr(ix->rnorm, nslots * 4))) return rc;
+        ix->has_rnorm = true;
+        ix->tc_some = !opt && ix->ex_bits > 0; // RabitqConfig::faster: Some(t_const) unless 1-bit; RabitqConfig::new: None
+        ix->tc_value = ix->tc_some ? t_const : 0.0f;
+    }
     std::vector<uint64_t> vstart(nlist);
     { uint64_t run = 0; for (uint32_t c = 0; c < nlist; ++c) { vstart[c] = run; run += ln[c]; } }
 
@@ -176,6 +182,7 @@ int build_device_pairs(const rbq_header* hdr, const float* centroids, const floa
             P.blocks = (uint8_t*)ix->blocks.p + b0 * dev_stride; P.raw_ex = d_raw;
             P.f_add_ex = (float*)ix->fadd_ex.p + s0; P.f_rescale_ex = (float*)ix->fres_ex.p + s0; P.ids = (uint64_t*)ix->ids.p + s0;
             P.delta = (float*)ix->delta.p + s0; P.vl = (float*)ix->vl.p + s0;
+            if (ix->has_rnorm) P.residual_norm = (float*)ix->rnorm.p + s0;
             P.src_base = 0; P.nslots = (uint32_t)ns; P.D = D; P.Dc = Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.t_const = t_const;
             HIP_TRY(launch_encode(P, 0));
             if (ix->ex_bits)

@@ -31,7 +31,7 @@ void free_replica(Replica* ix) {
     (void)hipDeviceSynchronize();
     for (Arr* a : ix->arrays)
         if (a->p && !(a == &ix->raw && ix->raw_borrowed)) (void)hipFree(a->p);
-    for (Arr* a : {&ix->delta, &ix->vl, &ix->fmap_ids, &ix->fmap_slots, &ix->ms_hi, &ix->ms_lo, &ix->ms_nc})
+    for (Arr* a : {&ix->delta, &ix->vl, &ix->rnorm, &ix->fmap_ids, &ix->fmap_slots, &ix->ms_hi, &ix->ms_lo, &ix->ms_nc})
         if (a->p) (void)hipFree(a->p);
     for (Workspace* w : ix->pool) delete w;
     for (auto& kv : ix->stream_ws) delete kv.second;
@@ -161,6 +161,7 @@ int Options::set(const char* name, int v) {
     else if (is("ub_tap")) ub_tap = v != 0;
     else if (is("save_chunk")) save_chunk = v > 0 ? (uint64_t)v : 0u;
     else if (is("fetch_chunk")) fetch_chunk = v > 0 ? (uint64_t)v : 0u;
+    else if (is("mstg_chunk")) mstg_chunk = v > 0 ? (uint64_t)v : 0u;
     else if (is("mstg_search_budget")) mstg_search_budget = v > 0 ? (uint64_t)v : 0u;
     else if (is("slack_term")) slack_term = v;
     else if (is("slack_milli")) { // TEST ONLY: term `slack_term` of block_ub()'s slack times v / 1000 (1000 = the product)
@@ -766,6 +767,10 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
     else if (!std::strcmp(name, "delta") || !std::strcmp(name, "vl")) { // (first replica only)
         ix = h->reps[0];
         p = name[0] == 'd' ? ix->delta.p : ix->vl.p; have = ix->has_recon ? ix->n_blocks * 32 * 4 : 0;
+    }
+    else if (!std::strcmp(name, "rnorm")) { // (first replica only; MSTG handles)
+        ix = h->reps[0];
+        p = ix->rnorm.p; have = ix->has_rnorm ? ix->n_blocks * 32 * 4 : 0;
     }
     if (!p || bytes != have) return fail(RBQ_INVALID_CONFIG, "unknown array or size (have " + std::to_string(have) + " bytes)");
     DeviceGuard g(ix->device);

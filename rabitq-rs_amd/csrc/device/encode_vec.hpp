@@ -256,6 +256,7 @@ __global__ __launch_bounds__(kEncThreads) void k_encode(EncodeParams P) {
             P.delta[s] = valid ? delta : 0.0f;
             P.vl[s] = valid ? delta * cb : 0.0f;
         }
+        if (!FLAT && P.residual_norm) P.residual_norm[s] = valid ? l2_norm : 0.0f; // MSTG handles keep it for the `.mstg` format
     }
 }
 

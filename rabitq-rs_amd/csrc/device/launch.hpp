@@ -10,6 +10,7 @@
 //   k_bf.hip     brute-force index: distances and the BinaryHeap replay                  (bf.hpp)
 //   k_bf_train.hip  brute-force index: the encoder's flat output, ex_code_packed         (encode_vec.hpp)
 //   k_mstg.hip   MSTG closure assignment (ClosureAssigner::assign) and its host driver       (km_common.hpp)
+//   k_mstg_save.hip  `.mstg` writer and loader: device layout <-> the crate's bincode records
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, rank_mfma.hpp)
 #pragma once
 #include <atomic>
@@ -353,6 +354,41 @@ hipError_t launch_save_fill(const SaveParams& P, uint64_t w0, uint64_t nw, uint3
 constexpr uint32_t kCrcSegment = 4096;
 uint64_t crc_scratch_words(uint64_t n);
 hipError_t launch_crc32(const uint8_t* p, uint64_t n, uint32_t* seg_scratch, uint32_t* out, hipStream_t s);
+
+// ---- `.mstg` writer and loader (k_mstg_save.hip; include/rbq_mstg_persist.h, csrc/host/rbq_mstg_file.hpp) ------------------------
+// The posting-list section of the stream: list c starts (with its u64 length prefix) at section byte loff[c]; loff[n_lists] is
+// the section's length.  R = bytes of one record, E = bytes of its ex_code_packed.
+struct MstgSaveParams {
+    const uint64_t* loff;     // [n_lists + 1]
+    const uint32_t* list_gb0; // [n_lists] first block of every list
+    const uint32_t* list_n;   // [n_lists]
+    const float* centroids;   // [n_lists][D]
+    const uint8_t* blocks;    // device block records (stride Dc * 4 + 384)
+    const uint64_t* ids;      // slot order
+    const uint8_t* ex;        // lane-major ex codes, exd bytes per slot (ex_bits > 0)
+    const float *fadd_ex, *fres_ex, *delta, *vl, *rnorm; // slot order (fadd_ex / fres_ex unused when ex_bits == 0)
+    uint64_t exd;
+    uint32_t n_lists, D, Dc, ex_bits, cpu, has_t, t_bits, R, E; // (has_t, t_bits): the non-empty lists' RabitqConfig::t_const
+};
+// section bytes [b0, b0 + nb) into out[0, nb) (out: 4-byte aligned, room for nb rounded up to 4; b0 and nb are arbitrary)
+hipError_t launch_mstg_save_fill(const MstgSaveParams& P, uint64_t b0, uint64_t nb, uint32_t* out, hipStream_t s);
+// A span of the stream (bytes [span_off, ...) at `span`, any alignment inside) that holds every record of blocks
+// gb_first .. gb_first + nb - 1: block b's first record lies at stream offset boff[b].  One workgroup per block writes the
+// device layout of its 32 slots (pad slots as the encoder leaves them) and ORs what its records get wrong (kMstgBad*) into *err.
+struct MstgLoadParams {
+    const uint8_t* span;
+    uint64_t span_off;
+    const uint64_t* boff;       // [n_blocks]
+    const uint32_t* block_nv;   // [n_blocks] real vectors of every block (1..32)
+    uint32_t gb_first, nb;
+    uint8_t* blocks;
+    uint64_t* ids;
+    uint8_t* ex;
+    float *fadd_ex, *fres_ex, *delta, *vl, *rnorm;
+    uint32_t* err;
+    uint32_t D, Dc, ex_bits, R, E;
+};
+hipError_t launch_mstg_load_scatter(const MstgLoadParams& P, hipStream_t s);
 
 // ---- fetch_embedding (k_fetch.hip) -------------------------------------------------------------------------------------------
 // id map: the (id, slot) pairs of every real slot in (cluster, position) order, stably sorted by id.  vstart [n_lists + 1] =

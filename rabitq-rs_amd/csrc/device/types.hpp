@@ -212,6 +212,7 @@ struct EncodeParams {
     const double* t_row;        // optimal rescale (k_encode<*, true>): [nrows] t of every row (k_rescale); else unused
     // flat mode (k_encode<false, *, true>, the brute-force index): `blocks` is bin[nslots][D/8]; slot_src, block_list, centroids
     // and ids are unused; f_add_ex, f_rescale_ex, delta, vl and the four arrays below are the index's per-vector factors
+    // (residual_norm alone, in the block-ordered mode: slot order like delta — MSTG handles; null: not written)
     float *f_add = nullptr, *f_rescale = nullptr, *f_error = nullptr, *residual_norm = nullptr;
 };
 constexpr int kEncThreads = 64;          // 64 vectors = 2 blocks per workgroup

@@ -34,6 +34,7 @@
 #include "rbq_build.h"
 #include "rbq_rng.h"
 #include "rbq_hcluster.hpp"
+#include "rbq_mstg_file.hpp"
 
 namespace {
 
@@ -358,6 +359,7 @@ struct rbq_built {
         std::vector<uint64_t> ids;
         std::vector<uint8_t> batch_data, ex_codes;
         std::vector<float> f_add_ex, f_rescale_ex, delta, vl;
+        std::vector<float> rnorm; // QuantizedVector::residual_norm (the `.mstg` format stores it; no search reads it)
     };
     std::vector<List> lists;
     std::vector<rbq_list_view> views;
@@ -435,6 +437,7 @@ int rbq_build_train_with_clusters(const float* data, uint64_t n, uint32_t dim,
         L.batch_data.assign(nb * stride, 0);
         L.ex_codes.assign(m * exb, 0);
         L.f_add_ex.assign(m, 0.0f); L.f_rescale_ex.assign(m, 0.0f); L.delta.assign(m, 0.0f); L.vl.assign(m, 0.0f);
+        L.rnorm.assign(m, 0.0f);
         std::vector<float> rv(D);
         std::vector<QV> qv(32);
         for (size_t bi = 0; bi < nb; ++bi) {
@@ -452,7 +455,7 @@ int rbq_build_train_with_clusters(const float* data, uint64_t n, uint32_t dim,
                     f_add[j] = qv[j].f_add; f_rescale[j] = qv[j].f_rescale; f_error[j] = qv[j].f_error;
                     if (exb) std::memcpy(L.ex_codes.data() + v * exb, qv[j].ex_packed.data(), exb);
                     if (ex_bits > 0) { L.f_add_ex[v] = qv[j].f_add_ex; L.f_rescale_ex[v] = qv[j].f_rescale_ex; }
-                    L.delta[v] = qv[j].delta; L.vl[v] = qv[j].vl;
+                    L.delta[v] = qv[j].delta; L.vl[v] = qv[j].vl; L.rnorm[v] = qv[j].residual_norm;
                 } else {
                     ptrs[j] = nullptr; // zero-padded tail: codes 0, factors 0 (src/ivf.rs:466-491)
                     f_add[j] = 0.0f; f_rescale[j] = 0.0f; f_error[j] = 0.0f;
@@ -476,7 +479,35 @@ int rbq_built_list_recon(const rbq_built* b, uint64_t c, const float** delta, co
     *delta = b->lists[c].delta.data(); *vl = b->lists[c].vl.data();
     return RBQ_OK;
 }
+// QuantizedVector::residual_norm of list c's vectors (kept by the `.mstg` format, include/rbq_mstg_persist.h)
+int rbq_built_list_residual_norm(const rbq_built* b, uint64_t c, const float** rnorm) {
+    if (!b || c >= b->lists.size() || !rnorm) return RBQ_INVALID_CONFIG;
+    *rnorm = b->lists[c].rnorm.data();
+    return RBQ_OK;
+}
 void rbq_built_free(rbq_built* b) { delete b; }
+
+// The `.mstg` loader's whole validation without a GPU (rbq_mstg_file.hpp): framing, every record's inner fields, the
+// checksum.  Returns the loader's code with its message in detail; out4 (or null) receives lists, vectors, dim, ex_bits.
+int rbq_build_mstg_file_check(const void* bytes, uint64_t len, char* detail, uint64_t detail_cap, rbq_mstg_config* cfg_out,
+                              uint64_t* out4) {
+    rbq_host::MstgFraming F;
+    std::string msg;
+    int rc = RBQ_INVALID_PERSISTENCE;
+    try {
+        if (!bytes && len) msg = "null buffer";
+        else rc = rbq_host::mstg_check_bytes((const uint8_t*)bytes, len, F, msg);
+    } catch (...) { msg = "out of host memory"; rc = RBQ_IO; }
+    if (detail && detail_cap) {
+        const size_t c = std::min<size_t>(detail_cap - 1, msg.size());
+        std::memcpy(detail, msg.data(), c);
+        detail[c] = 0;
+    }
+    if (rc != RBQ_OK) return rc;
+    if (cfg_out) *cfg_out = F.cfg;
+    if (out4) { out4[0] = F.lists.size(); out4[1] = F.n_vectors; out4[2] = F.D; out4[3] = F.ex_bits; }
+    return RBQ_OK;
+}
 
 // save_to_writer, src/ivf.rs:1317-1474. Caller frees *bytes with rbq_build_free_bytes.
 int rbq_built_save_rbq1(const rbq_built* b, uint8_t** bytes, uint64_t* len) {

@@ -164,6 +164,17 @@ def lib():
         L.rbq_mstg_cluster_device.restype = C.c_int
         L.rbq_mstg_cluster_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_uint64, C.c_uint64,
                                               C.c_int, C.POINTER(vp)]
+        # rbq_mstg_persist.h
+        L.rbq_mstg_save_stream.restype = C.c_int
+        L.rbq_mstg_save_stream.argtypes = [vp, vp, WRITE_FN, vp]
+        L.rbq_mstg_save.restype = C.c_int
+        L.rbq_mstg_save.argtypes = [vp, vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
+        L.rbq_mstg_load.restype = C.c_int
+        L.rbq_mstg_load.argtypes = [vp, C.c_uint64, C.c_int, vp, C.POINTER(vp)]
+        L.rbq_mstg_load_stream.restype = C.c_int
+        L.rbq_mstg_load_stream.argtypes = [READ_FN, vp, C.c_uint64, C.c_int, vp, C.POINTER(vp)]
+        L.rbq_mstg_memory_usage.restype = C.c_uint64
+        L.rbq_mstg_memory_usage.argtypes = [vp]
         from .builder import bind_hclustered
         bind_hclustered(L)
         _LIB = L
@@ -172,6 +183,8 @@ def lib():
 
 # rbq_write_fn: int (*)(void* user, const void* bytes, uint64_t len)
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
+# rbq_read_fn: int (*)(void* user, uint64_t offset, void* dst, uint64_t len)
+READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
 
 
 def _detail():

@@ -7,7 +7,12 @@ The arithmetic is the crate's on an AVX2 host; `closure_assign_cpu` (csrc/host/r
 device result equals it exactly; `select_lists_cpu` does the same for the search's list selection
 (section 16).  Step 1, `HierarchicalClustering::cluster` (src/mstg/clustering.rs), is `hierarchical_cluster` (restated by
 `hierarchical_cluster_cpu`, section 17), and `MstgIndex` strings the steps together as the crate's Python binding does.  The HNSW
-over the centroids is not built: the search ranks the centroids exactly."""
+over the centroids is not built: the search ranks the centroids exactly.
+
+Persistence (include/rbq_mstg_persist.h): `save_mstg` / `load_mstg` and `MstgIndex.save` / `load` write and
+read the crate's `{path}.mstg` (src/mstg/io.rs), assembled and taken apart on the GPU.  The crate's HNSW side files
+(`{path}.hnsw.graph`, `{path}.hnsw.data`) are neither written nor read: a crate-written index loads here, while the crate cannot
+reopen a file written here without side files of its own making."""
 import ctypes as C
 from dataclasses import dataclass
 
@@ -216,6 +221,98 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
     return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
 
 
+def _config_struct(config):
+    cfg = config if isinstance(config, _abi.MstgConfig) else _abi.MstgConfig.from_dict(config)
+    return cfg
+
+
+def save_mstg(index, config, dest):
+    """Write the `.mstg` stream of an MSTG handle (rbq_mstg_save_stream).  `config` is a dict of the thirteen MstgConfig fields
+    (_abi.MSTG_CONFIG_FIELDS; metric 0 / 1, centroid_precision 0..3) or an _abi.MstgConfig; `dest` a path (the file is created or
+    truncated; the crate's name is `{base}.mstg`) or anything with .write(bytes).  Chunks arrive as the device finishes them; a
+    writer exception stops the save and is re-raised."""
+    from . import RabitqError
+    from .index import WRITE_FN, _check, lib
+    cfg = _config_struct(config)
+    if isinstance(dest, (str, bytes)) or hasattr(dest, "__fspath__"):
+        try:
+            f = open(dest, "wb")
+        except OSError as e:
+            raise RabitqError(_abi.RBQ_IO, str(e))
+        with f:
+            return save_mstg(index, cfg, f)
+    err = []
+
+    def cb(_user, p, n):
+        try:
+            dest.write(C.string_at(p, n) if n else b"")
+            return 0
+        except BaseException as e:  # noqa: BLE001 - handed back to the caller after the C call returns
+            err.append(e)
+            return 1
+    rc = lib().rbq_mstg_save_stream(index._h, C.byref(cfg), WRITE_FN(cb), None)
+    if err:
+        raise err[0]
+    _check(rc)
+
+
+def save_mstg_bytes(index, config):
+    """The whole `.mstg` stream as bytes (rbq_mstg_save)."""
+    from .index import _check, lib
+    cfg = _config_struct(config)
+    p, n = C.POINTER(C.c_uint8)(), C.c_uint64()
+    _check(lib().rbq_mstg_save(index._h, C.byref(cfg), C.byref(p), C.byref(n)))
+    try:
+        return C.string_at(p, n.value)
+    finally:
+        lib().rbq_persist_free_bytes(p)
+
+
+def load_mstg(src, device=None):
+    """(handle, config dict) of a `.mstg` stream: `src` is bytes (rbq_mstg_load), or a path or a seekable binary file, read
+    through rbq_mstg_load_stream (the framing first, then the records span by span: host memory stays two spans)."""
+    from . import RabitqError
+    from .index import READ_FN, IvfRabitqIndex, _check, lib
+    dev = -1 if device is None else int(device)
+    cfg, h = _abi.MstgConfig(), C.c_void_p()
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        data = bytes(src)
+        _check(lib().rbq_mstg_load(data, len(data), dev, C.byref(cfg), C.byref(h)))
+        return IvfRabitqIndex(h), cfg.to_dict()
+    if isinstance(src, str) or hasattr(src, "__fspath__"):
+        try:
+            f = open(src, "rb")
+        except OSError as e:
+            raise RabitqError(_abi.RBQ_IO, str(e))
+        with f:
+            return load_mstg(f, device)
+    total = src.seek(0, 2)
+    err = []
+
+    def cb(_user, off, dst, n):
+        try:
+            src.seek(off)
+            got = src.read(n)
+            if len(got) != n:
+                return 1
+            C.memmove(dst, got, n)
+            return 0
+        except BaseException as e:  # noqa: BLE001 - handed back to the caller after the C call returns
+            err.append(e)
+            return 1
+    rc = lib().rbq_mstg_load_stream(READ_FN(cb), None, total, dev, C.byref(cfg), C.byref(h))
+    if err:
+        raise err[0]
+    _check(rc)
+    return IvfRabitqIndex(h), cfg.to_dict()
+
+
+def memory_usage(index):
+    """Device bytes an MSTG handle holds on its first device (rbq_mstg_memory_usage)."""
+    from .index import lib
+    return int(lib().rbq_mstg_memory_usage(index._h))
+
+
 def _hc_args(max_posting_size, branching_factor, max_iterations):
     from . import RabitqError
     v = [int(max_posting_size), int(branching_factor), int(max_iterations)]
@@ -276,7 +373,9 @@ class MstgIndex:
 
     `hnsw_m`, `hnsw_ef_construction` and `centroid_precision` are accepted and recorded, and unused: the crate needs them for the
     HNSW over its (quantised) centroids, while this library ranks the full-precision centroids exactly (rbq_mstg.h, "the
-    selection").  `save` / `load` are not provided.  As in the crate, results are [count][2] f32 arrays of (id, distance), which
+    selection").  `save(path)` / `load(path)` write and read the crate's `{path}.mstg` on the GPU; the crate's HNSW side files are
+    neither written nor read, so the crate cannot reopen a file saved here.  `get_memory_usage()` is the
+    device footprint in bytes.  As in the crate, results are [count][2] f32 arrays of (id, distance), which
     hold ids exactly only below 2^24; `mstg_search(index.handle, ...)` returns u64 ids."""
 
     def __init__(self, dimension, metric="euclidean", max_posting_size=16, branching_factor=10, balance_weight=1.0,
@@ -334,6 +433,41 @@ class MstgIndex:
         if q.ndim != 1 or q.shape[0] != self.dimension:
             raise ValueError(f"Query dimension {q.shape[-1] if q.ndim else 0} does not match expected {self.dimension}")
         return self.batch_query(q[None, :], k)[0]
+
+    def config(self):
+        """The crate's MstgConfig of this index (what `save` writes)."""
+        return dict(max_posting_size=self.max_posting_size, branching_factor=self.branching_factor, balance_weight=self.balance_weight,
+                    closure_epsilon=self.closure_epsilon, max_replicas=self.max_replicas, rabitq_bits=self.rabitq_bits,
+                    faster_config=self.faster_config, metric=self.metric, hnsw_m=self.hnsw_m,
+                    hnsw_ef_construction=self.hnsw_ef_construction,
+                    centroid_precision=_abi.MSTG_PRECISIONS.index(self.centroid_precision),
+                    default_ef_search=self.default_ef_search, pruning_epsilon=self.pruning_epsilon)
+
+    def save(self, path):
+        """`MstgIndex::save_to_path`'s main file: writes `{path}.mstg` (only: see the class docstring on the HNSW side files)."""
+        save_mstg(self._built(), self.config(), str(path) + ".mstg")
+
+    @staticmethod
+    def load(path, device=None):
+        """Reads `{path}.mstg` onto `device`: every constructor field comes from the file's config, the centroids from the
+        posting lists, and len() is 1 + the largest vector id."""
+        handle, cfg = load_mstg(str(path) + ".mstg", device)
+        self = MstgIndex(int(handle.dim), "euclidean" if cfg["metric"] == 0 else "angular", cfg["max_posting_size"], cfg["branching_factor"],
+                         cfg["balance_weight"], cfg["closure_epsilon"], cfg["max_replicas"], cfg["rabitq_bits"], cfg["faster_config"],
+                         cfg["hnsw_m"], cfg["hnsw_ef_construction"], _abi.MSTG_PRECISIONS[cfg["centroid_precision"]],
+                         cfg["default_ef_search"], cfg["pruning_epsilon"], device)
+        k, D = int(handle.cluster_count()), int(handle.dim)
+        self.handle = handle
+        self.centroids = handle.debug_copy_index("centroids", np.empty((k, D), np.float32))
+        ln = handle.debug_copy_index("list_n", np.empty(k, np.uint32))
+        ids = handle.debug_copy_index("ids", np.empty(int(((ln.astype(np.int64) + 31) // 32).sum()) * 32, np.uint64))
+        real = ids[ids != np.uint64(0xFFFFFFFFFFFFFFFF)]
+        self._n = int(real.max()) + 1 if real.size else 0
+        return self
+
+    def get_memory_usage(self):
+        """Device bytes held by the index (the crate's get_memory_usage reports its host footprint)."""
+        return memory_usage(self._built())
 
     def __len__(self):
         return self._n
