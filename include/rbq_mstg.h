@@ -162,6 +162,37 @@ int rbq_mstg_search_batch_device(const rbq_index* idx, const float* d_queries, u
                                  float* d_out_scores, uint32_t* d_out_counts, uint32_t* d_out_list_ids,
                                  uint32_t* d_out_list_counts, void* hip_stream);
 
+/* The refined search: opt-in, a pure function of what rbq_mstg_search_batch returns.  The crate's MSTG
+ * search ranks by the 1-bit estimate only and may return one id several times (closure assignment puts a vector into up to
+ * max_replicas lists); this call re-scores a pool of binary candidates with the stored ex codes and returns distinct ids.
+ * Per query, with pool = max(refine_pool, top_k):
+ *  1. The pool is the result of rbq_mstg_search_batch with top_k := pool: same lists, list order, estimate, clamp, drop of
+ *     non-finite estimates and tie rule.  Entry r of it is the candidate of rank r, a (list, position) entry: two ranks may carry
+ *     one id.  out_list_ids / out_list_counts are that call's.
+ *  2. The refined distance of a candidate is the crate's IVF refinement (src/ivf.rs:2086-2099): with ip the candidate's binary
+ *     ip_x0_qr, t = binary_scale * ip; t += ex_dot; t += kbx_sum_q; dist = (f_add_ex + g_add) + f_rescale_ex * t, g_add the
+ *     value the binary stage used for the candidate's list, ex_dot in the handle's numeric variant
+ *     (rbq_index_set_numeric_variant: all three are served).  With ex_bits == 0 it is the binary estimate.  A non-finite
+ *     refined distance drops the candidate; an L2 distance below zero is reported as zero; distances are reported for both metrics.
+ *  3. Among the candidates with one id the smallest refined distance is kept, on equal values the smaller rank.
+ *  4. The kept candidates are ordered by (refined distance by value, rank) ascending and the first top_k are returned:
+ *     out_counts their number, unused slots UINT64_MAX / NaN.
+ *  5. top_k == 0 or ef_search == 0: RBQ_OK with every count 0; nq == 0: RBQ_OK.
+ * Errors: those of rbq_mstg_search_batch in its order, then RBQ_INVALID_CONFIG for pool > RBQ_MSTG_REFINE_POOL_MAX (one
+ * workgroup sorts a query's pool in LDS); all before the first HIP call.  The result does not depend on the chunking (the pool's
+ * slots, estimates and counts are part of the 1 GiB workspace).  The first refined call on a handle builds an identity slot map
+ * (8 bytes per slot, through which the unchanged scan kernels report positions) and waits for it once. */
+#define RBQ_MSTG_REFINE_POOL_MAX 4096
+int rbq_mstg_search_refined_batch(const rbq_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                                  uint32_t ef_search, float pruning_epsilon, uint32_t refine_pool, uint64_t* out_ids,
+                                  float* out_scores, uint32_t* out_counts, uint32_t* out_list_ids, uint32_t* out_list_counts);
+/* The same on device pointers under the conventions of rbq_mstg_search_batch_device: enqueued on the caller's stream without
+ * host synchronisation (but for the one-time preparations), one workspace per (index, stream). */
+int rbq_mstg_search_refined_batch_device(const rbq_index* idx, const float* d_queries, uint64_t nq, uint32_t query_dim,
+                                         uint32_t top_k, uint32_t ef_search, float pruning_epsilon, uint32_t refine_pool,
+                                         uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_counts,
+                                         uint32_t* d_out_list_ids, uint32_t* d_out_list_counts, void* hip_stream);
+
 /* Diagnostic: queries, summed over every MSTG search of this process, that were scored against every centroid because
  * their shortlist could not be proven complete.  Waits for the devices' work. */
 uint64_t rbq_mstg_debug_search_fallbacks(void);

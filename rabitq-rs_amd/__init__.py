@@ -14,6 +14,8 @@ Mirrors the reference's public query API for this path:
                                src/mstg/closure.rs, src/mstg/index.rs:40-110 (mstg.py)
   mstg_search / select_lists_cpu / MstgSearchParams: MstgIndex::search and batch_search
                                src/mstg/index.rs:149-213,340-362 (mstg.py)
+  mstg_search(..., refine_pool=n): opt-in, no crate counterpart: the binary candidates re-scored with the ex codes
+                               (the refinement of src/ivf.rs:2086-2099), every id once (mstg.py)
   hierarchical_cluster / hierarchical_cluster_cpu / MstgIndex: HierarchicalClustering::cluster, PyMstgIndex
                                src/mstg/clustering.rs, src/python_bindings.rs (mstg.py)
   save_mstg / load_mstg, MstgIndex.save / load / get_memory_usage: MstgIndex::save_main_index / load_main_index

@@ -49,6 +49,7 @@ MSTG_CONFIG_FIELDS = ("max_posting_size", "branching_factor", "balance_weight", 
                       "faster_config", "metric", "hnsw_m", "hnsw_ef_construction", "centroid_precision", "default_ef_search",
                       "pruning_epsilon")
 MSTG_PRECISIONS = ("fp32", "bf16", "fp16", "int8")  # ScalarPrecision's variant order (src/mstg/config.rs)
+MSTG_REFINE_POOL_MAX = 4096  # RBQ_MSTG_REFINE_POOL_MAX: the largest max(refine_pool, top_k) of the refined MSTG search
 
 
 class MstgConfig(C.Structure):

@@ -245,6 +245,7 @@ struct Workspace {
     hipStream_t stream = nullptr;
     DevBuf queries, rot, lut, consts, scores, probe, wl, nstream, nvec, out_pack, filter, rot_hi, rot_lo, dead_skipped, heap_ws, key_window, audit_dead, tie_log, head_ub;
     DevBuf ms_sl, ms_lists; // rbq_mstg_search_batch*: shortlists | their lengths | query norms; the selected lists | their counts
+    DevBuf mr_pool;         // rbq_mstg_search_refined_batch*: the pool's slots [n][pool] u64 | estimates [n][pool] f32 | counts [n] u32
     PinBuf h_in, h_out;      // rbq_search_batch: staging of one sub-batch
     hipEvent_t done = nullptr; // results of the sub-batch in flight have reached h_out / the caller's buffers
     uint64_t call_nq = 0;       // queries of the WHOLE host call this launch chain belongs to (0: a device-entry call — its own nq counts)
@@ -385,6 +386,10 @@ struct Replica : Geometry {
     Arr ms_hi, ms_lo, ms_nc;
     bool ms_ready = false;
     uint32_t ms_bad = 0;
+    // rbq_mstg_search_refined_batch*: the identity slot map the scan reports positions through (8 bytes per slot) and the list of
+    // every block; built by the first refined search, under `mu`, kept until destroy (not in `arrays`: built per replica)
+    Arr mr_slot_map, mr_blk_list;
+    bool mr_ready = false;
     float cnorm2_max = 0.0f;
     uint64_t n_raw = 0;      // raw vectors attached for the optional rerank
     bool raw_borrowed = false;

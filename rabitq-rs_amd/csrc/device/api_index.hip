@@ -31,7 +31,8 @@ void free_replica(Replica* ix) {
     (void)hipDeviceSynchronize();
     for (Arr* a : ix->arrays)
         if (a->p && !(a == &ix->raw && ix->raw_borrowed)) (void)hipFree(a->p);
-    for (Arr* a : {&ix->delta, &ix->vl, &ix->rnorm, &ix->fmap_ids, &ix->fmap_slots, &ix->ms_hi, &ix->ms_lo, &ix->ms_nc})
+    for (Arr* a : {&ix->delta, &ix->vl, &ix->rnorm, &ix->fmap_ids, &ix->fmap_slots, &ix->ms_hi, &ix->ms_lo, &ix->ms_nc,
+                   &ix->mr_slot_map, &ix->mr_blk_list})
         if (a->p) (void)hipFree(a->p);
     for (Workspace* w : ix->pool) delete w;
     for (auto& kv : ix->stream_ws) delete kv.second;

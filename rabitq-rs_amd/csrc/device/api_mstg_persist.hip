@@ -327,7 +327,8 @@ uint64_t rbq_mstg_memory_usage(const rbq_index* idx) {
     uint64_t total = 0;
     for (const Arr* a : ix->arrays)
         if (a->p && !(a == &ix->raw && ix->raw_borrowed)) total += a->bytes;
-    for (const Arr* a : {&ix->delta, &ix->vl, &ix->rnorm, &ix->fmap_ids, &ix->fmap_slots, &ix->ms_hi, &ix->ms_lo, &ix->ms_nc})
+    for (const Arr* a : {&ix->delta, &ix->vl, &ix->rnorm, &ix->fmap_ids, &ix->fmap_slots, &ix->ms_hi, &ix->ms_lo, &ix->ms_nc,
+                         &ix->mr_slot_map, &ix->mr_blk_list})
         if (a->p) total += a->bytes;
     return total;
 }

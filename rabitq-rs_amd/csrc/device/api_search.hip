@@ -86,10 +86,11 @@ struct ProfScope {
 // k_scan launch shared by the IVF search and the MSTG posting-list scan
 int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, uint32_t top_k, uint64_t wl_stride,
                const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
-               rbq_diag* d_diag, bool mstg, const uint32_t* d_dead_skipped, hipStream_t stream) {
+               rbq_diag* d_diag, bool mstg, const uint32_t* d_dead_skipped, hipStream_t stream, const uint64_t* d_slot_ids = nullptr) {
     ProfScope ps(ix, 3, stream, /*ext=*/true);
     ScanParams P;
-    P.blocks = (const uint8_t*)ix->blocks.p; P.ids = (const uint64_t*)ix->ids.p; P.ex_codes = (const uint8_t*)ix->ex.p;
+    // (d_slot_ids, the refined MSTG search: the identity slot map stands in for the ids, so the result names positions)
+    P.blocks = (const uint8_t*)ix->blocks.p; P.ids = d_slot_ids ? d_slot_ids : (const uint64_t*)ix->ids.p; P.ex_codes = (const uint8_t*)ix->ex.p;
     P.f_add_ex = (const float*)ix->fadd_ex.p; P.f_rescale_ex = (const float*)ix->fres_ex.p;
     P.lut = (const uint8_t*)w->lut.p; P.rot = (const float*)w->rot.p; P.consts = (const QueryConsts*)w->consts.p;
     P.probe = (const ProbeInfo*)w->probe.p; P.wl = (const StreamItem*)w->wl.p; P.nstream = (const uint32_t*)w->nstream.p;
@@ -521,7 +522,8 @@ struct MstgShape {
 };
 
 // The chunk keeps the work list and the score matrix inside the budget; the result does not depend on it.
-MstgShape ms_shape(const Replica* ix, uint64_t nq, uint32_t top_k, uint32_t ef_search, bool host) {
+// pool: the candidates per query of the refined search (0: the plain search), whose slots, estimates and counts join the chunk
+MstgShape ms_shape(const Replica* ix, uint64_t nq, uint32_t top_k, uint32_t ef_search, bool host, uint32_t pool = 0) {
     MstgShape sh;
     const uint64_t k = ix->n_lists;
     sh.ef = (uint32_t)std::min<uint64_t>(ef_search, k);
@@ -529,6 +531,7 @@ MstgShape ms_shape(const Replica* ix, uint64_t nq, uint32_t top_k, uint32_t ef_s
     uint64_t per = (uint64_t)ix->D * 4 + (uint64_t)ix->Dc * 4 + sizeof(QueryConsts) + (uint64_t)sh.ef * (4 + sizeof(ProbeInfo)) +
                    sh.wl_stride * sizeof(StreamItem) + (uint64_t)top_k * 12 + 16;
     if (host) per += (uint64_t)ix->dim * 4;
+    if (pool) per += (uint64_t)pool * 12 + 4;
     if (mstg_select_gemm(k, ix->D)) per += 4 * k + 4ull * mstg_select_dp(ix->D) + 4ull * kMsCap + 8;
     else if (k > RBQ_MSTG_SHORTLIST) per += 4;
     per += 8ull * mstg_select_knp2(k);
@@ -540,7 +543,7 @@ MstgShape ms_shape(const Replica* ix, uint64_t nq, uint32_t top_k, uint32_t ef_s
 // n queries at d_q (device), everything enqueued on `stream`; d_lists [n][sh.ef] and d_lcnt [n] receive the selection
 int ms_chunk(Replica* ix, Workspace* w, const float* d_q, uint64_t n, uint32_t top_k, uint32_t ef_search, float pruning_epsilon,
              const MstgShape& sh, unsigned long long* d_fallbacks, uint64_t* d_ids, float* d_scores, uint32_t* d_counts, uint32_t* d_lists,
-             uint32_t* d_lcnt, hipStream_t stream) {
+             uint32_t* d_lcnt, hipStream_t stream, const uint64_t* d_slot_map = nullptr) {
     int rc;
     const uint32_t D = ix->D, Dc = ix->Dc, k = (uint32_t)ix->n_lists, Dp = mstg_select_dp(D);
     const bool gemm = mstg_select_gemm(k, D);
@@ -562,7 +565,9 @@ int ms_chunk(Replica* ix, Workspace* w, const float* d_q, uint64_t n, uint32_t t
     {
         ProfScope ps(ix, 0, stream);
         PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_q, n);
-        p.ex_bits = 0u; // (MSTG: no ex codes)
+        // (MSTG: no ex codes.  The refined search keeps the handle's ex_bits: kbx, scale and the ex-dot range of the query
+        // constants follow it, and nothing the binary stage reads does)
+        if (!d_slot_map) p.ex_bits = 0u;
         HIP_TRY(launch_prep(p, ix->device, stream));
     }
     {
@@ -590,22 +595,67 @@ int ms_chunk(Replica* ix, Workspace* w, const float* d_q, uint64_t n, uint32_t t
         p.numeric_variant = ix->opt.numeric_variant;
         HIP_TRY(launch_probes_given(p, stream));
     }
-    return scan_stage(ix, w, n, sh.ef, top_k, sh.wl_stride, nullptr, 0, d_ids, d_scores, d_counts, nullptr, /*mstg=*/true, nullptr, stream);
+    return scan_stage(ix, w, n, sh.ef, top_k, sh.wl_stride, nullptr, 0, d_ids, d_scores, d_counts, nullptr, /*mstg=*/true, nullptr, stream,
+                      d_slot_map);
 }
 
-// what rbq_posting_scan_batch checks, in its order; *done: the call is answered without the device
-int ms_check(const rbq_index* h, const void* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, const void* out_ids,
-             const void* out_scores, const void* out_counts) {
-    int rc = check_query_args(h, query_dim);
-    if (rc) return rc;
-    if (h->reps[0]->rotator != RBQ_ROTATOR_NONE) return fail(RBQ_INVALID_CONFIG, "MSTG search needs an index created with rotator NONE");
-    if (nq == 0) return RBQ_OK;
-    if (nq > 0x7fffffffull) return fail(RBQ_INVALID_CONFIG, "batch too large");
-    // (top_k == 0: out_ids and out_scores hold no element, so they have no address to ask for)
-    if (!queries || !out_counts || (top_k && (!out_ids || !out_scores))) return fail(RBQ_INVALID_CONFIG, "null buffer");
-    if (top_k > kTopKHardMax || (uint64_t)std::min<uint64_t>(nq, 16384) * ((uint64_t)top_k + 1) * 8 > (8ull << 30))
-        return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20)");
+// ---- refined MSTG search (rbq_mstg_search_refined_batch*, k_mstg_refine.hip) --------------------------------------------------
+// the identity slot map and the list of every block, once per replica (the first refined search waits for them)
+int mr_prepare(Replica* ix) {
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->mr_ready) return RBQ_OK;
+    int rc;
+    if ((rc = alloc_arr(ix->mr_slot_map, (size_t)ix->n_blocks * 32 * 8))) return rc;
+    if ((rc = alloc_arr(ix->mr_blk_list, (size_t)ix->n_blocks * 4))) return rc;
+    HIP_TRY(launch_mstg_refine_maps((const uint32_t*)ix->list_gb0.p, (const uint32_t*)ix->list_n.p, (uint32_t)ix->n_lists, (uint32_t)ix->n_blocks,
+                                    (uint64_t*)ix->mr_slot_map.p, (uint32_t*)ix->mr_blk_list.p, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    ix->mr_ready = true;
     return RBQ_OK;
+}
+
+// ms_chunk with top_k := pool over the slot map, then the refinement of the pool into the caller's top_k
+int mr_chunk(Replica* ix, Workspace* w, const float* d_q, uint64_t n, uint32_t top_k, uint32_t pool, uint32_t ef_search, float pruning_epsilon,
+             const MstgShape& sh, unsigned long long* d_fallbacks, uint64_t* d_ids, float* d_scores, uint32_t* d_counts, uint32_t* d_lists,
+             uint32_t* d_lcnt, hipStream_t stream) {
+    int rc;
+    if ((rc = w->mr_pool.ensure(n * ((size_t)pool * 12 + 4)))) return rc;
+    uint64_t* p_slots = (uint64_t*)w->mr_pool.p;
+    float* p_est = (float*)(p_slots + n * (size_t)pool);
+    uint32_t* p_cnt = (uint32_t*)(p_est + n * (size_t)pool);
+    if ((rc = ms_chunk(ix, w, d_q, n, pool, ef_search, pruning_epsilon, sh, d_fallbacks, p_slots, p_est, p_cnt, d_lists, d_lcnt, stream,
+                       (const uint64_t*)ix->mr_slot_map.p)))
+        return rc;
+    MstgRefineParams P{};
+    P.blocks = (const uint8_t*)ix->blocks.p; P.ids = (const uint64_t*)ix->ids.p; P.ex_codes = (const uint8_t*)ix->ex.p;
+    P.f_add_ex = (const float*)ix->fadd_ex.p; P.f_rescale_ex = (const float*)ix->fres_ex.p;
+    P.blk_list = (const uint32_t*)ix->mr_blk_list.p; P.n_slots = ix->n_blocks * 32;
+    P.lut = (const uint8_t*)w->lut.p; P.rot = (const float*)w->rot.p; P.consts = (const QueryConsts*)w->consts.p;
+    P.probe = (const ProbeInfo*)w->probe.p; P.list_counts = d_lcnt; P.probe_stride = sh.ef;
+    P.pool_slots = p_slots; P.pool_scores = p_est; P.pool_counts = p_cnt; P.pool = pool;
+    P.pool_np2 = 1;
+    while (P.pool_np2 < pool) P.pool_np2 <<= 1;
+    P.out_ids = d_ids; P.out_scores = d_scores; P.out_counts = d_counts;
+    P.nq = (uint32_t)n; P.D = ix->D; P.Dc = ix->Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.top_k = top_k;
+    P.numeric_variant = ix->opt.numeric_variant;
+    HIP_TRY(launch_mstg_refine(P, ix->device, stream));
+    return RBQ_OK;
+}
+
+// the argument errors of the MSTG searches (rbq_host::mstg_search_check: what rbq_posting_scan_batch checks, in its order, then
+// the refined call's pool); *pool = max(refine_pool, top_k) of a refined call
+int ms_check(const rbq_index* h, const void* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, const void* out_ids,
+             const void* out_scores, const void* out_counts, bool refined = false, uint32_t refine_pool = 0, uint32_t* pool = nullptr) {
+    static_assert(rbq_host::kMstgTopKHardMax == kTopKHardMax && rbq_host::kMstgRefinePoolMax == RBQ_MSTG_REFINE_POOL_MAX, "host logic and device side disagree");
+    rbq_host::MstgSearchArgs a;
+    a.have_index = h && !h->reps.empty();
+    if (a.have_index) { const Replica* ix = h->reps[0]; a.n_vectors = ix->n_vectors; a.dim = ix->dim; a.rotator = ix->rotator; }
+    a.query_dim = query_dim; a.nq = nq; a.top_k = top_k; a.refined = refined; a.refine_pool = refine_pool;
+    a.queries = queries != nullptr; a.out_ids = out_ids != nullptr; a.out_scores = out_scores != nullptr; a.out_counts = out_counts != nullptr;
+    std::string detail;
+    bool done = false;
+    const int rc = rbq_host::mstg_search_check(a, &detail, &done, pool);
+    return rc ? fail(rc, detail) : RBQ_OK;
 }
 
 Replica* replica_of_pointer(rbq_index* h, const void* dptr) {
@@ -852,13 +902,15 @@ int rbq_posting_scan_batch(const rbq_index* ch, const float* queries, uint64_t n
 
 
 // ---- MSTG search (include/rbq_mstg.h) ------------------------------------------------------------------
-int rbq_mstg_search_batch(const rbq_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t ef_search,
-                          float pruning_epsilon, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_list_ids,
-                          uint32_t* out_list_counts) {
+// refined: rbq_mstg_search_refined_batch (the pool is max(refine_pool, top_k)); else rbq_mstg_search_batch
+static int ms_search_host(const rbq_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t ef_search,
+                          float pruning_epsilon, bool refined, uint32_t refine_pool, uint64_t* out_ids, float* out_scores,
+                          uint32_t* out_counts, uint32_t* out_list_ids, uint32_t* out_list_counts) {
     g_err.clear();
     RBQ_GUARD_BEGIN
     rbq_index* h = const_cast<rbq_index*>(ch);
-    int rc = ms_check(h, queries, nq, query_dim, top_k, out_ids, out_scores, out_counts);
+    uint32_t pool = 0;
+    int rc = ms_check(h, queries, nq, query_dim, top_k, out_ids, out_scores, out_counts, refined, refine_pool, &pool);
     if (rc || nq == 0) return rc;
     Replica* ix = h->reps[0];
     const uint32_t ef = (uint32_t)std::min<uint64_t>(ef_search, ix->n_lists);
@@ -874,7 +926,8 @@ int rbq_mstg_search_batch(const rbq_index* ch, const float* queries, uint64_t nq
     if (mstg_select_gemm(ix->n_lists, ix->D) && (rc = ms_prepare(ix))) return rc;
     unsigned long long* d_fb = nullptr;
     if ((rc = ms_fallback_counter(ix->device, &d_fb))) return rc;
-    const MstgShape sh = ms_shape(ix, nq, top_k, ef_search, true);
+    if (refined && (rc = mr_prepare(ix))) return rc;
+    const MstgShape sh = ms_shape(ix, nq, top_k, ef_search, true, pool);
     if (sh.wl_stride > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "posting lists too long for one query");
     Workspace* w = take_ws(ix);
     if (!w) return fail(RBQ_DEVICE, "cannot create workspace stream");
@@ -891,9 +944,11 @@ int rbq_mstg_search_batch(const rbq_index* ch, const float* queries, uint64_t nq
             uint32_t* d_lists = (uint32_t*)w->ms_lists.p;
             uint32_t* d_lcnt = d_lists + n * (size_t)sh.ef;
             HIP_TRY(hipMemcpyAsync(w->queries.p, queries + q0 * query_dim, n * query_dim * 4, hipMemcpyHostToDevice, st));
-            if ((r2 = ms_chunk(ix, w, (const float*)w->queries.p, n, top_k, ef_search, pruning_epsilon, sh, d_fb, (uint64_t*)(dp + op.o_ids),
-                               (float*)(dp + op.o_scores), (uint32_t*)(dp + op.o_counts), d_lists, d_lcnt, st)))
-                return r2;
+            r2 = refined ? mr_chunk(ix, w, (const float*)w->queries.p, n, top_k, pool, ef_search, pruning_epsilon, sh, d_fb, (uint64_t*)(dp + op.o_ids),
+                                    (float*)(dp + op.o_scores), (uint32_t*)(dp + op.o_counts), d_lists, d_lcnt, st)
+                         : ms_chunk(ix, w, (const float*)w->queries.p, n, top_k, ef_search, pruning_epsilon, sh, d_fb, (uint64_t*)(dp + op.o_ids),
+                                    (float*)(dp + op.o_scores), (uint32_t*)(dp + op.o_counts), d_lists, d_lcnt, st);
+            if (r2) return r2;
             HIP_TRY(hipMemcpyAsync(out_ids + q0 * top_k, dp + op.o_ids, n * top_k * 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(out_scores + q0 * top_k, dp + op.o_scores, n * top_k * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(out_counts + q0, dp + op.o_counts, n * 4, hipMemcpyDeviceToHost, st));
@@ -910,13 +965,15 @@ int rbq_mstg_search_batch(const rbq_index* ch, const float* queries, uint64_t nq
     RBQ_GUARD_END
 }
 
-int rbq_mstg_search_batch_device(const rbq_index* ch, const float* d_queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
-                                 uint32_t ef_search, float pruning_epsilon, uint64_t* d_out_ids, float* d_out_scores,
-                                 uint32_t* d_out_counts, uint32_t* d_out_list_ids, uint32_t* d_out_list_counts, void* hip_stream) {
+static int ms_search_device(const rbq_index* ch, const float* d_queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                            uint32_t ef_search, float pruning_epsilon, bool refined, uint32_t refine_pool, uint64_t* d_out_ids,
+                            float* d_out_scores, uint32_t* d_out_counts, uint32_t* d_out_list_ids, uint32_t* d_out_list_counts,
+                            void* hip_stream) {
     g_err.clear();
     RBQ_GUARD_BEGIN
     rbq_index* h = const_cast<rbq_index*>(ch);
-    int rc = ms_check(h, d_queries, nq, query_dim, top_k, d_out_ids, d_out_scores, d_out_counts);
+    uint32_t pool = 0;
+    int rc = ms_check(h, d_queries, nq, query_dim, top_k, d_out_ids, d_out_scores, d_out_counts, refined, refine_pool, &pool);
     if (rc || nq == 0) return rc;
     Replica* ix = replica_of_pointer(h, d_queries);
     DeviceGuard g(ix->device);
@@ -936,7 +993,8 @@ int rbq_mstg_search_batch_device(const rbq_index* ch, const float* d_queries, ui
     if (mstg_select_gemm(ix->n_lists, ix->D) && (rc = ms_prepare(ix))) return rc;
     unsigned long long* d_fb = nullptr;
     if ((rc = ms_fallback_counter(ix->device, &d_fb))) return rc;
-    const MstgShape sh = ms_shape(ix, nq, top_k, ef_search, false);
+    if (refined && (rc = mr_prepare(ix))) return rc; // (the first refined call on a handle waits for its maps once)
+    const MstgShape sh = ms_shape(ix, nq, top_k, ef_search, false, pool);
     if (sh.wl_stride > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "posting lists too long for one query");
     Workspace* w; // one per caller stream, as rbq_search_batch_device: the chunks of a call and successive calls are stream-ordered
     {
@@ -951,12 +1009,40 @@ int rbq_mstg_search_batch_device(const rbq_index* ch, const float* d_queries, ui
         const uint64_t n = std::min(sh.chunk, nq - q0);
         uint32_t* d_lists = d_out_list_ids ? d_out_list_ids + q0 * sh.ef : (uint32_t*)w->ms_lists.p;
         uint32_t* d_lcnt = d_out_list_counts ? d_out_list_counts + q0 : (uint32_t*)w->ms_lists.p + sh.chunk * (size_t)sh.ef;
-        if ((rc = ms_chunk(ix, w, d_queries + q0 * query_dim, n, top_k, ef_search, pruning_epsilon, sh, d_fb, d_out_ids + q0 * top_k,
-                           d_out_scores + q0 * top_k, d_out_counts + q0, d_lists, d_lcnt, s)))
-            return rc;
+        rc = refined ? mr_chunk(ix, w, d_queries + q0 * query_dim, n, top_k, pool, ef_search, pruning_epsilon, sh, d_fb, d_out_ids + q0 * top_k,
+                                d_out_scores + q0 * top_k, d_out_counts + q0, d_lists, d_lcnt, s)
+                     : ms_chunk(ix, w, d_queries + q0 * query_dim, n, top_k, ef_search, pruning_epsilon, sh, d_fb, d_out_ids + q0 * top_k,
+                                d_out_scores + q0 * top_k, d_out_counts + q0, d_lists, d_lcnt, s);
+        if (rc) return rc;
     }
     return RBQ_OK;
     RBQ_GUARD_END
+}
+
+int rbq_mstg_search_batch(const rbq_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t ef_search,
+                          float pruning_epsilon, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_list_ids,
+                          uint32_t* out_list_counts) {
+    return ms_search_host(idx, queries, nq, query_dim, top_k, ef_search, pruning_epsilon, false, 0, out_ids, out_scores, out_counts,
+                          out_list_ids, out_list_counts);
+}
+int rbq_mstg_search_batch_device(const rbq_index* idx, const float* d_queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                                 uint32_t ef_search, float pruning_epsilon, uint64_t* d_out_ids, float* d_out_scores,
+                                 uint32_t* d_out_counts, uint32_t* d_out_list_ids, uint32_t* d_out_list_counts, void* hip_stream) {
+    return ms_search_device(idx, d_queries, nq, query_dim, top_k, ef_search, pruning_epsilon, false, 0, d_out_ids, d_out_scores,
+                            d_out_counts, d_out_list_ids, d_out_list_counts, hip_stream);
+}
+int rbq_mstg_search_refined_batch(const rbq_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                                  uint32_t ef_search, float pruning_epsilon, uint32_t refine_pool, uint64_t* out_ids, float* out_scores,
+                                  uint32_t* out_counts, uint32_t* out_list_ids, uint32_t* out_list_counts) {
+    return ms_search_host(idx, queries, nq, query_dim, top_k, ef_search, pruning_epsilon, true, refine_pool, out_ids, out_scores, out_counts,
+                          out_list_ids, out_list_counts);
+}
+int rbq_mstg_search_refined_batch_device(const rbq_index* idx, const float* d_queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                                         uint32_t ef_search, float pruning_epsilon, uint32_t refine_pool, uint64_t* d_out_ids,
+                                         float* d_out_scores, uint32_t* d_out_counts, uint32_t* d_out_list_ids,
+                                         uint32_t* d_out_list_counts, void* hip_stream) {
+    return ms_search_device(idx, d_queries, nq, query_dim, top_k, ef_search, pruning_epsilon, true, refine_pool, d_out_ids, d_out_scores,
+                            d_out_counts, d_out_list_ids, d_out_list_counts, hip_stream);
 }
 
 uint64_t rbq_mstg_debug_search_fallbacks(void) {

@@ -12,6 +12,7 @@
 //   k_mstg.hip   MSTG closure assignment (ClosureAssigner::assign) and its host driver       (km_common.hpp)
 //   k_mstg_save.hip  `.mstg` writer and loader: device layout <-> the crate's bincode records
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, rank_mfma.hpp)
+//   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan.hpp)
 #pragma once
 #include <atomic>
 #include <string>
@@ -335,6 +336,36 @@ uint32_t mstg_select_knp2(uint64_t k);          // keys per query of keys_g (0: 
 hipError_t launch_mstg_centroid_prep(const float* cent, uint32_t k, uint32_t D, float* nc, uint32_t* ncmax_bits, uint32_t* bad,
                                      uint16_t* hi, uint16_t* lo, hipStream_t s);
 hipError_t launch_mstg_select(const MstgSelectParams& p, int device, hipStream_t s);
+
+// ---- refined MSTG search (k_mstg_refine.hip): the binary scan's pool re-scored with the ex codes, one entry per id, top_k
+constexpr uint32_t kMrPoolMax = 4096; // RBQ_MSTG_REFINE_POOL_MAX: the pool of one query is sorted in LDS
+struct MstgRefineParams {
+    const uint8_t* blocks;      // the index, as ScanParams names it
+    const uint64_t* ids;
+    const uint8_t* ex_codes;
+    const float *f_add_ex, *f_rescale_ex;
+    const uint32_t* blk_list;   // [n_blocks] the list of every block (launch_mstg_refine_maps)
+    uint64_t n_slots;           // n_blocks * 32
+    const uint8_t* lut;         // [nq][4Dc], rot [nq][D], consts [nq]: as k_prep left them (with the handle's ex_bits)
+    const float* rot;
+    const QueryConsts* consts;
+    const ProbeInfo* probe;     // [nq][probe_stride] as k_probes_given wrote them; list_counts [nq] rows in use
+    const uint32_t* list_counts;
+    uint32_t probe_stride;
+    const uint64_t* pool_slots; // [nq][pool] the binary scan's result over the identity slot map, pool_scores [nq][pool] its
+    const float* pool_scores;   // estimates (ascending), pool_counts [nq]
+    const uint32_t* pool_counts;
+    uint32_t pool, pool_np2;    // pool_np2: the power of two >= pool (<= kMrPoolMax)
+    uint64_t* out_ids;          // [nq][top_k], out_scores [nq][top_k], out_counts [nq]
+    float* out_scores;
+    uint32_t* out_counts;
+    uint32_t nq, D, Dc, ex_bits, metric, top_k, numeric_variant;
+};
+size_t mstg_refine_lds_bytes(uint32_t D, uint32_t Dc, uint32_t ex_bits, uint32_t pool_np2);
+// slot_map [n_blocks * 32] u64 = the identity; blk_list [n_blocks] u32
+hipError_t launch_mstg_refine_maps(const uint32_t* list_gb0, const uint32_t* list_n, uint32_t n_lists, uint32_t n_blocks, uint64_t* slot_map,
+                                   uint32_t* blk_list, hipStream_t s);
+hipError_t launch_mstg_refine(const MstgRefineParams& P, int device, hipStream_t s);
 
 // ---- RBQ1 writer (k_save.hip): words [w0, w0 + nw) of the cluster section of the stream, into out[0, nw)
 struct SaveParams {

@@ -339,4 +339,42 @@ inline std::vector<std::pair<uint64_t, uint64_t>> subbatch_plan(uint64_t nq, uin
     return plan;
 }
 
+// The argument errors of rbq_mstg_search_batch* and rbq_mstg_search_refined_batch* (include/rbq_mstg.h), in their order; no
+// device is needed to find any of them.  RBQ_OK with *done set: the call is answered as it stands (nq == 0).
+struct MstgSearchArgs {
+    bool have_index = false;       // a non-null handle with a replica
+    uint64_t n_vectors = 0;
+    uint32_t dim = 0, query_dim = 0;
+    int rotator = 0;
+    uint64_t nq = 0;
+    bool queries = false, out_ids = false, out_scores = false, out_counts = false; // which buffers are non-null
+    uint32_t top_k = 0;
+    bool refined = false;          // rbq_mstg_search_refined_batch*: the pool is max(refine_pool, top_k)
+    uint32_t refine_pool = 0;
+};
+constexpr uint32_t kMstgTopKHardMax = 1u << 20;  // (kTopKHardMax of the device side)
+constexpr uint32_t kMstgRefinePoolMax = 4096;    // RBQ_MSTG_REFINE_POOL_MAX
+inline int mstg_search_check(const MstgSearchArgs& a, std::string* detail, bool* done, uint32_t* pool) {
+    auto fail = [&](int code, const std::string& msg) { if (detail) *detail = msg; return code; };
+    if (done) *done = false;
+    if (pool) *pool = 0;
+    if (!a.have_index) return fail(RBQ_INVALID_CONFIG, "null index");
+    if (a.n_vectors == 0) return fail(RBQ_EMPTY_INDEX, "index is empty");
+    if (a.query_dim != a.dim) return fail(RBQ_DIMENSION_MISMATCH, "expected " + std::to_string(a.dim) + ", got " + std::to_string(a.query_dim));
+    if (a.rotator != RBQ_ROTATOR_NONE) return fail(RBQ_INVALID_CONFIG, "MSTG search needs an index created with rotator NONE");
+    if (a.nq == 0) { if (done) *done = true; return RBQ_OK; }
+    if (a.nq > 0x7fffffffull) return fail(RBQ_INVALID_CONFIG, "batch too large");
+    // (top_k == 0: out_ids and out_scores hold no element, so they have no address to ask for)
+    if (!a.queries || !a.out_counts || (a.top_k && (!a.out_ids || !a.out_scores))) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    if (a.top_k > kMstgTopKHardMax || (uint64_t)std::min<uint64_t>(a.nq, 16384) * ((uint64_t)a.top_k + 1) * 8 > (8ull << 30))
+        return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20)");
+    if (a.refined) {
+        const uint32_t p = std::max(a.refine_pool, a.top_k);
+        if (p > kMstgRefinePoolMax)
+            return fail(RBQ_INVALID_CONFIG, "refine pool too large: max(refine_pool, top_k) <= " + std::to_string(kMstgRefinePoolMax));
+        if (pool) *pool = p;
+    }
+    return RBQ_OK;
+}
+
 } // namespace rbq_host

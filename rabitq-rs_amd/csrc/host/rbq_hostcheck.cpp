@@ -85,4 +85,25 @@ uint64_t rbq_hostcheck_plan(uint64_t nq, uint64_t forced, uint64_t* out, uint64_
     return plan.size();
 }
 
+// mstg_search_check over plain values: flags bit 0 = a handle, 1 = queries, 2 = out_ids, 3 = out_scores, 4 = out_counts, 5 = the
+// refined call; out[0] = done, out[1] = pool
+int rbq_hostcheck_mstg_search_args(uint32_t flags, uint64_t n_vectors, uint32_t dim, uint32_t query_dim, int rotator, uint64_t nq,
+                                   uint32_t top_k, uint32_t refine_pool, char* detail, size_t detail_cap, uint32_t out[2]) {
+    rbq_host::MstgSearchArgs a;
+    a.have_index = flags & 1u; a.queries = flags & 2u; a.out_ids = flags & 4u; a.out_scores = flags & 8u; a.out_counts = flags & 16u;
+    a.refined = flags & 32u;
+    a.n_vectors = n_vectors; a.dim = dim; a.query_dim = query_dim; a.rotator = rotator; a.nq = nq; a.top_k = top_k; a.refine_pool = refine_pool;
+    std::string msg;
+    bool done = false;
+    uint32_t pool = 0;
+    const int rc = rbq_host::mstg_search_check(a, &msg, &done, &pool);
+    if (detail && detail_cap) {
+        const size_t c = std::min(detail_cap - 1, msg.size());
+        std::memcpy(detail, msg.data(), c);
+        detail[c] = 0;
+    }
+    if (out) { out[0] = done ? 1u : 0u; out[1] = pool; }
+    return rc;
+}
+
 } // extern "C"

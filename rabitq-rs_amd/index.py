@@ -159,6 +159,12 @@ def lib():
         L.rbq_mstg_search_batch_device.restype = C.c_int
         L.rbq_mstg_search_batch_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp,
                                                    vp]
+        L.rbq_mstg_search_refined_batch.restype = C.c_int
+        L.rbq_mstg_search_refined_batch.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp, vp,
+                                                    vp, vp]
+        L.rbq_mstg_search_refined_batch_device.restype = C.c_int
+        L.rbq_mstg_search_refined_batch_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp,
+                                                           vp, vp, vp, vp, vp]
         L.rbq_mstg_debug_search_fallbacks.restype = C.c_uint64
         L.rbq_mstg_debug_search_fallbacks.argtypes = []
         L.rbq_mstg_cluster_device.restype = C.c_int

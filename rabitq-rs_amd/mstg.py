@@ -180,14 +180,26 @@ def search_fallbacks():
     return int(lib().rbq_mstg_debug_search_fallbacks())
 
 
-def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, return_lists=False):
+REFINE_POOL_MAX = _abi.MSTG_REFINE_POOL_MAX
+
+
+def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, return_lists=False, refine_pool=None):
     """`MstgIndex::batch_search` on an MSTG handle (rotator NoRotation, e.g. from build_postings_on_device) in one call:
     (ids [nq][top_k] u64, distances [nq][top_k] f32 ascending, counts [nq] u32), plus (lists, list_counts) of the selected
     posting lists in scan order with `return_lists`.  NumPy queries take rbq_mstg_search_batch and return arrays; a CUDA tensor
     takes rbq_mstg_search_batch_device on the current stream, without synchronising, and returns tensors (ids as int64 bit
-    patterns, lists as int32 bit patterns: torch has no unsigned 64 / 32-bit arithmetic)."""
+    patterns, lists as int32 bit patterns: torch has no unsigned 64 / 32-bit arithmetic).
+
+    `refine_pool=None` is the crate's search: 1-bit estimates, and an id may come back once per list that holds it.  An int takes
+    rbq_mstg_search_refined_batch*: the max(refine_pool, top_k) best binary candidates are re-scored with the stored ex codes,
+    reduced to one entry per id and the top_k nearest returned (at most REFINE_POOL_MAX candidates)."""
     from .index import _check, lib
     top_k, ef_search = int(top_k), int(ef_search)
+    L = lib()
+    if refine_pool is None:
+        host_fn, dev_fn, extra = L.rbq_mstg_search_batch, L.rbq_mstg_search_batch_device, ()
+    else:
+        host_fn, dev_fn, extra = L.rbq_mstg_search_refined_batch, L.rbq_mstg_search_refined_batch_device, (int(refine_pool),)
     ef = min(max(ef_search, 0), index.cluster_count())
     try:
         import torch
@@ -203,10 +215,10 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
             li = torch.empty((nq, ef), dtype=torch.int32, device=q.device) if return_lists else None
             lc = torch.empty(nq, dtype=torch.int32, device=q.device) if return_lists else None
             stream = torch.cuda.current_stream().cuda_stream
-            _check(lib().rbq_mstg_search_batch_device(index._h, q.data_ptr(), nq, qd, top_k, ef_search, float(pruning_epsilon),
-                                                      ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(),
-                                                      li.data_ptr() if return_lists else None, lc.data_ptr() if return_lists else None,
-                                                      C.c_void_p(stream)))
+            _check(dev_fn(index._h, q.data_ptr(), nq, qd, top_k, ef_search, float(pruning_epsilon), *extra,
+                          ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(),
+                          li.data_ptr() if return_lists else None, lc.data_ptr() if return_lists else None,
+                          C.c_void_p(stream)))
         return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
     q = _host_f32(queries)
     nq, qd = q.shape
@@ -215,9 +227,9 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
     cnt = np.zeros(nq, np.uint32)
     li = np.empty((nq, ef), np.uint32) if return_lists else None
     lc = np.empty(nq, np.uint32) if return_lists else None
-    _check(lib().rbq_mstg_search_batch(index._h, q.ctypes.data, nq, qd, top_k, ef_search, float(pruning_epsilon), ids.ctypes.data,
-                                       sc.ctypes.data, cnt.ctypes.data, li.ctypes.data if return_lists else None,
-                                       lc.ctypes.data if return_lists else None))
+    _check(host_fn(index._h, q.ctypes.data, nq, qd, top_k, ef_search, float(pruning_epsilon), *extra, ids.ctypes.data,
+                   sc.ctypes.data, cnt.ctypes.data, li.ctypes.data if return_lists else None,
+                   lc.ctypes.data if return_lists else None))
     return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
 
 
@@ -363,6 +375,7 @@ def hierarchical_cluster(data, max_posting_size, branching_factor=10, balance_we
 
 HOST_BELOW_DEFAULT = 0xFFFFFFFFFFFFFFFF  # RBQ_MSTG_HOST_BELOW_DEFAULT: let the library choose
 
+_KEEP = object()  # set_query_arguments: "leave refine_pool as it is" (None is a value of its own)
 _METRICS = {"euclidean": 0, "l2": 0, "angular": 1, "ip": 1, "inner_product": 1}
 
 
@@ -394,6 +407,7 @@ class MstgIndex:
         self.default_ef_search, self.pruning_epsilon = int(default_ef_search), float(pruning_epsilon)
         self.device, self.max_iterations, self.host_below = device, int(max_iterations), host_below
         self.handle, self.centroids, self.cluster_stats, self._n = None, None, None, 0
+        self.refine_pool = None  # the crate's search; set_query_arguments(refine_pool=...) switches to the refined one
 
     def fit(self, data):
         if len(data.shape) != 2:
@@ -407,11 +421,15 @@ class MstgIndex:
         self.centroids, self.cluster_stats, self._n = cent, st, int(data.shape[0])
         return self
 
-    def set_query_arguments(self, ef_search=None, pruning_epsilon=None):
+    def set_query_arguments(self, ef_search=None, pruning_epsilon=None, refine_pool=_KEEP):
+        """`refine_pool`: None = the crate's search (the default); an int = the refined search of `mstg_search` over a pool of that
+        many binary candidates (ex-code distances, every id once).  Left out, it keeps its value."""
         if ef_search is not None:
             self.default_ef_search = int(ef_search)
         if pruning_epsilon is not None:
             self.pruning_epsilon = float(pruning_epsilon)
+        if refine_pool is not _KEEP:
+            self.refine_pool = None if refine_pool is None else int(refine_pool)
 
     def _built(self):
         if self.handle is None:
@@ -425,7 +443,7 @@ class MstgIndex:
             raise ValueError("Queries must be 2D array (N x D)")
         if q.shape[1] != self.dimension:
             raise ValueError(f"Query dimension {q.shape[1]} does not match expected {self.dimension}")
-        ids, dist, cnt = mstg_search(h, q, k, self.default_ef_search, self.pruning_epsilon)
+        ids, dist, cnt = mstg_search(h, q, k, self.default_ef_search, self.pruning_epsilon, refine_pool=self.refine_pool)
         return [np.stack([ids[i, :cnt[i]].astype(np.float32), dist[i, :cnt[i]]], axis=1) for i in range(q.shape[0])]
 
     def query(self, query, k):
