@@ -1,5 +1,5 @@
 // api.hpp — internal header of librbq.so's host side: the C ABI of include/rbq.h over the HIP kernels, which the host
-// units (api_index, api_build, api_search, api_save, api_fetch, api_bf, api_mstg, api_mstg_persist) reach through launch.hpp.  Not installed.
+// units (api_index, api_build, api_search, api_mstg_search, api_save, api_fetch, api_bf, api_mstg, api_mstg_persist) reach through launch.hpp.  Not installed.
 // Host responsibilities: validate like the reference (src/ivf.rs:1754-1769,1484-1702), upload the reference's ClusterData
 // bytes and have the GPU re-lay them into the device layout (one-time, at create/load), own HBM on one or N devices
 // (replicas), and enqueue prep -> rank -> select -> scan for each query batch.  There is no CPU compute path: every failure
@@ -402,7 +402,7 @@ struct Replica : Geometry {
     std::vector<uint64_t> nblk_desc_prefix; // prefix sums of per-list block counts sorted descending
     std::mutex mu;
     std::vector<Workspace*> pool;
-    std::map<hipStream_t, Workspace*> stream_ws; // rbq_search_batch_device: one workspace per caller stream
+    std::map<hipStream_t, Workspace*> stream_ws; // stream_workspace(): one workspace per caller stream
     // profiling
     bool profiling = false;
     uint32_t prof_mask = 0xf; // stages that are timed while `profiling` (bit s = stage s)
@@ -432,6 +432,41 @@ int wrap_and_replicate(Replica* first, const std::vector<int>& devs, rbq_index**
 // api_build.hip: the device encoder over (vector, list) pairs (rbq_index_build_device_ex: one pair per vector; rbq_mstg_build_device)
 int build_device_pairs(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
                        const uint32_t* d_vec, uint64_t n, int rescale, float t_const, int dev, rbq_index** out);
+
+// shared by the search units (api_search.hip): workspaces from the replica's pool and per caller stream, the stage timer, the scan launch
+Workspace* take_ws(Replica* ix);
+void give_ws(Replica* ix, Workspace* w);
+Workspace* stream_workspace(Replica* ix, hipStream_t s);
+int check_query_args(const rbq_index* h, uint32_t query_dim);
+Replica* replica_of_pointer(rbq_index* h, const void* dptr);
+struct ProfScope {
+    Replica* ix; int stage; hipStream_t s; std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    bool on = false, ext = false;
+    // ext: the launch itself carries the event pair (hipExtLaunchKernelGGL: start/stop come from the dispatch
+    // packet, no separate marker packets in the queue); otherwise the pair is recorded around the scope
+    ProfScope(Replica* ix_, int st, hipStream_t s_, bool ext_ = false) : ix(ix_), stage(st), s(s_), ext(ext_) {
+        if (ix->profiling && !stage_probes() && ((ix->prof_mask >> st) & 1u)) { // (a probed call launches nothing: no event pair for it)
+            {
+                std::lock_guard<std::mutex> g(ix->mu);
+                if (ix->prof_seq[st]++ % ix->prof_every == 0) on = ix->ev_pool.take(ev);
+            }
+            if (on && !ext) (void)hipEventRecord(ev.first, s);
+        }
+    }
+    hipEvent_t start() const { return on && ext ? ev.first : nullptr; }
+    hipEvent_t stop() const { return on && ext ? ev.second : nullptr; }
+    ~ProfScope() {
+        if (on) {
+            if (!ext) (void)hipEventRecord(ev.second, s);
+            std::lock_guard<std::mutex> g(ix->mu);
+            ix->stage_prof[stage].ev.push_back(ev);
+        }
+    }
+};
+// (mstg, d_slot_ids: the MSTG scans; the IVF search passes no slot map)
+int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, uint32_t top_k, uint64_t wl_stride,
+               const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
+               rbq_diag* d_diag, bool mstg, const uint32_t* d_dead_skipped, hipStream_t stream, const uint64_t* d_slot_ids = nullptr);
 
 } // namespace rbq_api
 

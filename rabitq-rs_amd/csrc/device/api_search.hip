@@ -1,7 +1,6 @@
-// api_search.hip — search: the device entry, the host entry (rbq_search_batch, one replica or N), the MSTG posting-list
-// scan and the MSTG search in one call (rbq_mstg_search_batch*, include/rbq_mstg.h).  The hot path (search_host -> search_device -> scan_stage) stays in this one unit.
+// api_search.hip — the IVF search: the device entry and the host entry (rbq_search_batch, one replica or N).  The hot path
+// (search_host -> search_device -> scan_stage) stays in this one unit; api_mstg_search.hip shares its workspaces and scan_stage.
 #include "api.hpp"
-#include "rbq_mstg.h"
 
 using namespace rbq_api;
 
@@ -40,9 +39,9 @@ bool is_pinned_host_range(const void* p, size_t bytes) {
     if (a.hostPointer && b.hostPointer && (const uint8_t*)b.hostPointer - (const uint8_t*)a.hostPointer != (ptrdiff_t)(bytes - 1)) return false;
     return true;
 }
+} // namespace
 
-
-// ---- search ---------------------------------------------------------------------------------------------------------
+// ---- shared with api_mstg_search.hip (declared in api.hpp) ---------------------------------------------------------------------
 Workspace* take_ws(Replica* ix) {
     {
         std::lock_guard<std::mutex> g(ix->mu);
@@ -58,35 +57,42 @@ void give_ws(Replica* ix, Workspace* w) {
     ix->pool.push_back(w);
 }
 
-struct ProfScope {
-    Replica* ix; int stage; hipStream_t s; std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    bool on = false, ext = false;
-    // ext: the launch itself carries the event pair (hipExtLaunchKernelGGL: start/stop come from the dispatch
-    // packet, no separate marker packets in the queue); otherwise the pair is recorded around the scope
-    ProfScope(Replica* ix_, int st, hipStream_t s_, bool ext_ = false) : ix(ix_), stage(st), s(s_), ext(ext_) {
-        if (ix->profiling && !stage_probes() && ((ix->prof_mask >> st) & 1u)) { // (a probed call launches nothing: no event pair for it)
-            {
-                std::lock_guard<std::mutex> g(ix->mu);
-                if (ix->prof_seq[st]++ % ix->prof_every == 0) on = ix->ev_pool.take(ev);
-            }
-            if (on && !ext) (void)hipEventRecord(ev.first, s);
-        }
+// One workspace per caller stream, never handed to anyone else: successive calls on the same stream are
+// stream-ordered, so their kernels may share the scratch buffers without any host synchronisation.
+Workspace* stream_workspace(Replica* ix, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(ix->mu);
+    Workspace*& slot = ix->stream_ws[s];
+    if (!slot) slot = new Workspace();
+    return slot;
+}
+
+int check_query_args(const rbq_index* h, uint32_t query_dim) {
+    if (!h || h->reps.empty()) return fail(RBQ_INVALID_CONFIG, "null index");
+    const Replica* ix = h->reps[0];
+    if (ix->n_vectors == 0) return fail(RBQ_EMPTY_INDEX, "index is empty");
+    if (query_dim != ix->dim) {
+        char b[96];
+        std::snprintf(b, sizeof b, "expected %u, got %u", ix->dim, query_dim);
+        return fail(RBQ_DIMENSION_MISMATCH, b);
     }
-    hipEvent_t start() const { return on && ext ? ev.first : nullptr; }
-    hipEvent_t stop() const { return on && ext ? ev.second : nullptr; }
-    ~ProfScope() {
-        if (on) {
-            if (!ext) (void)hipEventRecord(ev.second, s);
-            std::lock_guard<std::mutex> g(ix->mu);
-            ix->stage_prof[stage].ev.push_back(ev);
-        }
+    return RBQ_OK;
+}
+
+Replica* replica_of_pointer(rbq_index* h, const void* dptr) {
+    if (h->reps.size() == 1) return h->reps[0];
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, dptr) == hipSuccess) {
+        for (Replica* r : h->reps) if (r->device == a.device) return r;
+    } else {
+        (void)hipGetLastError();
     }
-};
+    return h->reps[0];
+}
 
 // k_scan launch shared by the IVF search and the MSTG posting-list scan
 int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, uint32_t top_k, uint64_t wl_stride,
                const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
-               rbq_diag* d_diag, bool mstg, const uint32_t* d_dead_skipped, hipStream_t stream, const uint64_t* d_slot_ids = nullptr) {
+               rbq_diag* d_diag, bool mstg, const uint32_t* d_dead_skipped, hipStream_t stream, const uint64_t* d_slot_ids) {
     ProfScope ps(ix, 3, stream, /*ext=*/true);
     ScanParams P;
     // (d_slot_ids, the refined MSTG search: the identity slot map stands in for the ids, so the result names positions)
@@ -134,6 +140,7 @@ int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, ui
     return RBQ_OK;
 }
 
+namespace {
 // Core: everything on device pointers, enqueued on `stream`. Workspace buffers come from `w`.
 int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe_in,
                   const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
@@ -272,18 +279,6 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
     if (ix->rerank && !stage_probes()) // optional, default off: exact re-scoring of the returned ids against the attached raw vectors
         HIP_TRY(launch_rerank(d_queries, (uint32_t)nq, ix->dim, (const float*)ix->raw.p, ix->n_raw, ix->metric, top_k, d_ids, d_scores,
                               d_counts, stream));
-    return RBQ_OK;
-}
-
-int check_query_args(const rbq_index* h, uint32_t query_dim) {
-    if (!h || h->reps.empty()) return fail(RBQ_INVALID_CONFIG, "null index");
-    const Replica* ix = h->reps[0];
-    if (ix->n_vectors == 0) return fail(RBQ_EMPTY_INDEX, "index is empty");
-    if (query_dim != ix->dim) {
-        char b[96];
-        std::snprintf(b, sizeof b, "expected %u, got %u", ix->dim, query_dim);
-        return fail(RBQ_DIMENSION_MISMATCH, b);
-    }
     return RBQ_OK;
 }
 
@@ -476,198 +471,6 @@ int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_d
                      (unsigned long long)nq, (unsigned long long)plan[0].second, nlanes, (int)in_pinned, (int)out_pinned, t_attr, t_ws, t_stage, t_enq, t_wait, t_out);
     return RBQ_OK;
 }
-
-// ---- MSTG search (include/rbq_mstg.h): centroid ranking and dynamic_prune on the device, then the posting-list scan -------
-constexpr uint64_t kMstgSearchBudget = 1ull << 30; // per-chunk workspace of rbq_mstg_search_batch* (option mstg_search_budget)
-std::mutex g_ms_mu;
-unsigned long long* g_ms_fallbacks[16] = {}; // per device: queries scored against every centroid (never freed)
-
-// the counter of the current device `dev`
-int ms_fallback_counter(int dev, unsigned long long** out) {
-    std::lock_guard<std::mutex> lk(g_ms_mu);
-    if (dev < 0 || dev >= 16) return fail(RBQ_DEVICE, "device ordinal out of range");
-    if (!g_ms_fallbacks[dev]) {
-        unsigned long long* p = nullptr;
-        HIP_TRY(hipMalloc(&p, 8));
-        if (hipMemset(p, 0, 8) != hipSuccess) { (void)hipFree(p); return fail(RBQ_DEVICE, "hipMemset failed"); }
-        g_ms_fallbacks[dev] = p;
-    }
-    *out = g_ms_fallbacks[dev];
-    return RBQ_OK;
-}
-
-// split-bf16 images and norms of the centroids, once per replica (the first search that takes the GEMM shortlist)
-int ms_prepare(Replica* ix) {
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if (ix->ms_ready) return RBQ_OK;
-    const uint32_t k = (uint32_t)ix->n_lists, Dp = mstg_select_dp(ix->D);
-    int rc;
-    if ((rc = alloc_arr(ix->ms_hi, (size_t)k * Dp * 2))) return rc;
-    if ((rc = alloc_arr(ix->ms_lo, (size_t)k * Dp * 2))) return rc;
-    if ((rc = alloc_arr(ix->ms_nc, (size_t)k * 4 + 8))) return rc; // nc [k] | ncmax bits | bad
-    uint32_t* aux = (uint32_t*)ix->ms_nc.p + k;
-    HIP_TRY(launch_mstg_centroid_prep((const float*)ix->centroids.p, k, ix->D, (float*)ix->ms_nc.p, aux, aux + 1, (uint16_t*)ix->ms_hi.p,
-                                      (uint16_t*)ix->ms_lo.p, nullptr));
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpy(&bad, aux + 1, 4, hipMemcpyDeviceToHost));
-    ix->ms_bad = bad;
-    ix->ms_ready = true;
-    return RBQ_OK;
-}
-
-struct MstgShape {
-    uint32_t ef;        // min(ef_search, n_lists) >= 1: the stride of the list rows
-    uint64_t wl_stride; // the ef longest lists together, in blocks
-    uint64_t chunk;     // queries per pass
-};
-
-// The chunk keeps the work list and the score matrix inside the budget; the result does not depend on it.
-// pool: the candidates per query of the refined search (0: the plain search), whose slots, estimates and counts join the chunk
-MstgShape ms_shape(const Replica* ix, uint64_t nq, uint32_t top_k, uint32_t ef_search, bool host, uint32_t pool = 0) {
-    MstgShape sh;
-    const uint64_t k = ix->n_lists;
-    sh.ef = (uint32_t)std::min<uint64_t>(ef_search, k);
-    sh.wl_stride = std::max<uint64_t>(ix->nblk_desc_prefix[sh.ef], 1);
-    uint64_t per = (uint64_t)ix->D * 4 + (uint64_t)ix->Dc * 4 + sizeof(QueryConsts) + (uint64_t)sh.ef * (4 + sizeof(ProbeInfo)) +
-                   sh.wl_stride * sizeof(StreamItem) + (uint64_t)top_k * 12 + 16;
-    if (host) per += (uint64_t)ix->dim * 4;
-    if (pool) per += (uint64_t)pool * 12 + 4;
-    if (mstg_select_gemm(k, ix->D)) per += 4 * k + 4ull * mstg_select_dp(ix->D) + 4ull * kMsCap + 8;
-    else if (k > RBQ_MSTG_SHORTLIST) per += 4;
-    per += 8ull * mstg_select_knp2(k);
-    const uint64_t budget = ix->opt.mstg_search_budget ? ix->opt.mstg_search_budget : kMstgSearchBudget;
-    sh.chunk = std::min<uint64_t>(std::min<uint64_t>(std::max<uint64_t>(budget / per, 1), 16384), nq);
-    return sh;
-}
-
-// n queries at d_q (device), everything enqueued on `stream`; d_lists [n][sh.ef] and d_lcnt [n] receive the selection
-int ms_chunk(Replica* ix, Workspace* w, const float* d_q, uint64_t n, uint32_t top_k, uint32_t ef_search, float pruning_epsilon,
-             const MstgShape& sh, unsigned long long* d_fallbacks, uint64_t* d_ids, float* d_scores, uint32_t* d_counts, uint32_t* d_lists,
-             uint32_t* d_lcnt, hipStream_t stream, const uint64_t* d_slot_map = nullptr) {
-    int rc;
-    const uint32_t D = ix->D, Dc = ix->Dc, k = (uint32_t)ix->n_lists, Dp = mstg_select_dp(D);
-    const bool gemm = mstg_select_gemm(k, D);
-    const uint64_t np = (n + 127) / 128 * 128; // (the GEMM's row tiles)
-    if ((rc = w->rot.ensure(n * D * 4))) return rc;
-    if ((rc = w->lut.ensure(n * (size_t)Dc * 4))) return rc;
-    if ((rc = w->consts.ensure(n * sizeof(QueryConsts)))) return rc;
-    if ((rc = w->probe.ensure(n * (size_t)sh.ef * sizeof(ProbeInfo)))) return rc;
-    if ((rc = w->wl.ensure(n * sh.wl_stride * sizeof(StreamItem)))) return rc;
-    if ((rc = w->nstream.ensure(n * 4))) return rc;
-    if ((rc = w->ms_sl.ensure(n * ((size_t)(gemm ? kMsCap : 0) + 2) * 4))) return rc; // sl [n][kMsCap] | sl_n [n] | nx [n]
-    if (gemm) {
-        if ((rc = w->scores.ensure(np * (size_t)k * 4))) return rc;
-        if ((rc = w->rot_hi.ensure(np * (size_t)Dp * 2))) return rc;
-        if ((rc = w->rot_lo.ensure(np * (size_t)Dp * 2))) return rc;
-    }
-    const uint32_t knp2 = mstg_select_knp2(k);
-    if (knp2 && (rc = w->key_window.ensure(n * (size_t)knp2 * 8))) return rc;
-    {
-        ProfScope ps(ix, 0, stream);
-        PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_q, n);
-        // (MSTG: no ex codes.  The refined search keeps the handle's ex_bits: kbx, scale and the ex-dot range of the query
-        // constants follow it, and nothing the binary stage reads does)
-        if (!d_slot_map) p.ex_bits = 0u;
-        HIP_TRY(launch_prep(p, ix->device, stream));
-    }
-    {
-        ProfScope ps(ix, 1, stream);
-        MstgSelectParams p{};
-        p.rot = (const float*)w->rot.p; p.nq = (uint32_t)n; p.D = D; p.k = k; p.ef_search = ef_search; p.pruning_epsilon = pruning_epsilon;
-        p.cent = (const float*)ix->centroids.p;
-        p.cent_hi = (const uint16_t*)ix->ms_hi.p; p.cent_lo = (const uint16_t*)ix->ms_lo.p; p.nc = (const float*)ix->ms_nc.p;
-        p.ncmax_bits = (const uint32_t*)ix->ms_nc.p + k; p.cent_bad = ix->ms_bad;
-        p.q_hi = (uint16_t*)w->rot_hi.p; p.q_lo = (uint16_t*)w->rot_lo.p;
-        p.sl = (uint32_t*)w->ms_sl.p; p.sl_n = p.sl + n * (size_t)(gemm ? kMsCap : 0); p.nx = (float*)(p.sl_n + n);
-        p.dots = (float*)w->scores.p; p.keys_g = knp2 ? (unsigned long long*)w->key_window.p : nullptr;
-        p.fallbacks = d_fallbacks; p.out_lists = d_lists; p.out_counts = d_lcnt;
-        HIP_TRY(launch_mstg_select(p, ix->device, stream));
-    }
-    {
-        ProfScope ps(ix, 2, stream);
-        ProbesGivenParams p;
-        p.list_ids = d_lists; p.list_counts = d_lcnt; p.max_lists = sh.ef;
-        p.nq = (uint32_t)n; p.nlist = k; p.metric = (int)ix->metric; p.rot = (const float*)w->rot.p;
-        p.cent = (const float*)ix->centroids.p; p.D = D; p.list_gb0 = (const uint32_t*)ix->list_gb0.p;
-        p.list_n = (const uint32_t*)ix->list_n.p; p.probe = (ProbeInfo*)w->probe.p; p.wl = (StreamItem*)w->wl.p;
-        p.wl_stride = sh.wl_stride; p.nstream = (uint32_t*)w->nstream.p; p.consts = (const QueryConsts*)w->consts.p;
-        p.bsum = (const BlockSummary*)ix->bsum.p;
-        p.numeric_variant = ix->opt.numeric_variant;
-        HIP_TRY(launch_probes_given(p, stream));
-    }
-    return scan_stage(ix, w, n, sh.ef, top_k, sh.wl_stride, nullptr, 0, d_ids, d_scores, d_counts, nullptr, /*mstg=*/true, nullptr, stream,
-                      d_slot_map);
-}
-
-// ---- refined MSTG search (rbq_mstg_search_refined_batch*, k_mstg_refine.hip) --------------------------------------------------
-// the identity slot map and the list of every block, once per replica (the first refined search waits for them)
-int mr_prepare(Replica* ix) {
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if (ix->mr_ready) return RBQ_OK;
-    int rc;
-    if ((rc = alloc_arr(ix->mr_slot_map, (size_t)ix->n_blocks * 32 * 8))) return rc;
-    if ((rc = alloc_arr(ix->mr_blk_list, (size_t)ix->n_blocks * 4))) return rc;
-    HIP_TRY(launch_mstg_refine_maps((const uint32_t*)ix->list_gb0.p, (const uint32_t*)ix->list_n.p, (uint32_t)ix->n_lists, (uint32_t)ix->n_blocks,
-                                    (uint64_t*)ix->mr_slot_map.p, (uint32_t*)ix->mr_blk_list.p, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    ix->mr_ready = true;
-    return RBQ_OK;
-}
-
-// ms_chunk with top_k := pool over the slot map, then the refinement of the pool into the caller's top_k
-int mr_chunk(Replica* ix, Workspace* w, const float* d_q, uint64_t n, uint32_t top_k, uint32_t pool, uint32_t ef_search, float pruning_epsilon,
-             const MstgShape& sh, unsigned long long* d_fallbacks, uint64_t* d_ids, float* d_scores, uint32_t* d_counts, uint32_t* d_lists,
-             uint32_t* d_lcnt, hipStream_t stream) {
-    int rc;
-    if ((rc = w->mr_pool.ensure(n * ((size_t)pool * 12 + 4)))) return rc;
-    uint64_t* p_slots = (uint64_t*)w->mr_pool.p;
-    float* p_est = (float*)(p_slots + n * (size_t)pool);
-    uint32_t* p_cnt = (uint32_t*)(p_est + n * (size_t)pool);
-    if ((rc = ms_chunk(ix, w, d_q, n, pool, ef_search, pruning_epsilon, sh, d_fallbacks, p_slots, p_est, p_cnt, d_lists, d_lcnt, stream,
-                       (const uint64_t*)ix->mr_slot_map.p)))
-        return rc;
-    MstgRefineParams P{};
-    P.blocks = (const uint8_t*)ix->blocks.p; P.ids = (const uint64_t*)ix->ids.p; P.ex_codes = (const uint8_t*)ix->ex.p;
-    P.f_add_ex = (const float*)ix->fadd_ex.p; P.f_rescale_ex = (const float*)ix->fres_ex.p;
-    P.blk_list = (const uint32_t*)ix->mr_blk_list.p; P.n_slots = ix->n_blocks * 32;
-    P.lut = (const uint8_t*)w->lut.p; P.rot = (const float*)w->rot.p; P.consts = (const QueryConsts*)w->consts.p;
-    P.probe = (const ProbeInfo*)w->probe.p; P.list_counts = d_lcnt; P.probe_stride = sh.ef;
-    P.pool_slots = p_slots; P.pool_scores = p_est; P.pool_counts = p_cnt; P.pool = pool;
-    P.pool_np2 = 1;
-    while (P.pool_np2 < pool) P.pool_np2 <<= 1;
-    P.out_ids = d_ids; P.out_scores = d_scores; P.out_counts = d_counts;
-    P.nq = (uint32_t)n; P.D = ix->D; P.Dc = ix->Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.top_k = top_k;
-    P.numeric_variant = ix->opt.numeric_variant;
-    HIP_TRY(launch_mstg_refine(P, ix->device, stream));
-    return RBQ_OK;
-}
-
-// the argument errors of the MSTG searches (rbq_host::mstg_search_check: what rbq_posting_scan_batch checks, in its order, then
-// the refined call's pool); *pool = max(refine_pool, top_k) of a refined call
-int ms_check(const rbq_index* h, const void* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, const void* out_ids,
-             const void* out_scores, const void* out_counts, bool refined = false, uint32_t refine_pool = 0, uint32_t* pool = nullptr) {
-    static_assert(rbq_host::kMstgTopKHardMax == kTopKHardMax && rbq_host::kMstgRefinePoolMax == RBQ_MSTG_REFINE_POOL_MAX, "host logic and device side disagree");
-    rbq_host::MstgSearchArgs a;
-    a.have_index = h && !h->reps.empty();
-    if (a.have_index) { const Replica* ix = h->reps[0]; a.n_vectors = ix->n_vectors; a.dim = ix->dim; a.rotator = ix->rotator; }
-    a.query_dim = query_dim; a.nq = nq; a.top_k = top_k; a.refined = refined; a.refine_pool = refine_pool;
-    a.queries = queries != nullptr; a.out_ids = out_ids != nullptr; a.out_scores = out_scores != nullptr; a.out_counts = out_counts != nullptr;
-    std::string detail;
-    bool done = false;
-    const int rc = rbq_host::mstg_search_check(a, &detail, &done, pool);
-    return rc ? fail(rc, detail) : RBQ_OK;
-}
-
-Replica* replica_of_pointer(rbq_index* h, const void* dptr) {
-    if (h->reps.size() == 1) return h->reps[0];
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, dptr) == hipSuccess) {
-        for (Replica* r : h->reps) if (r->device == a.device) return r;
-    } else {
-        (void)hipGetLastError();
-    }
-    return h->reps[0];
-}
 } // namespace
 } // namespace rbq_api
 
@@ -691,16 +494,7 @@ int rbq_search_batch_device(const rbq_index* ch, const float* d_queries, uint64_
         HIP_TRY(hipMemsetAsync(d_out_counts, 0, nq * 4, s));
         return RBQ_OK;
     }
-    // One workspace per caller stream, never handed to anyone else: successive calls on the same stream are
-    // stream-ordered, so their kernels may share the scratch buffers without any host synchronisation.
-    Workspace* w;
-    {
-        std::lock_guard<std::mutex> lk(ix->mu);
-        Workspace*& slot = ix->stream_ws[s];
-        if (!slot) slot = new Workspace();
-        w = slot;
-    }
-    return search_device(ix, w, d_queries, nq, top_k, nprobe, d_filter_words, filter_nbits, d_out_ids, d_out_scores,
+    return search_device(ix, stream_workspace(ix, s), d_queries, nq, top_k, nprobe, d_filter_words, filter_nbits, d_out_ids, d_out_scores,
                          d_out_counts, d_diag, s);
     RBQ_GUARD_END
 }
@@ -801,262 +595,6 @@ int rbq_search_batch(const rbq_index* ch, const float* queries, uint64_t nq, uin
     for (size_t r = 0; r < R; ++r) if (st->rcs[r]) return fail(st->rcs[r], st->details[r]);
     return RBQ_OK;
     RBQ_GUARD_END
-}
-
-// ---- MSTG posting-list scan ------------------------------------------------------------
-int rbq_posting_scan_batch(const rbq_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
-                           const uint32_t* list_ids, const uint32_t* list_counts, uint32_t max_lists,
-                           uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
-    g_err.clear();
-    RBQ_GUARD_BEGIN
-    rbq_index* h = const_cast<rbq_index*>(ch);
-    int rc = check_query_args(h, query_dim);
-    if (rc) return rc;
-    Replica* ix = h->reps[0];
-    if (ix->rotator != RBQ_ROTATOR_NONE) return fail(RBQ_INVALID_CONFIG, "posting-list scan needs an index created with rotator NONE");
-    if (nq == 0) return RBQ_OK;
-    if (!queries || !list_ids || !list_counts || !out_ids || !out_scores || !out_counts) return fail(RBQ_INVALID_CONFIG, "null buffer");
-    if (top_k == 0) { std::memset(out_counts, 0, nq * 4); return RBQ_OK; }
-    if (top_k > kTopKHardMax || (uint64_t)std::min<uint64_t>(nq, 16384) * ((uint64_t)top_k + 1) * 8 > (8ull << 30))
-        return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20)");
-    if (max_lists == 0) {
-        std::memset(out_counts, 0, nq * 4);
-        for (uint64_t i = 0; i < nq * top_k; ++i) { out_ids[i] = ~0ull; out_scores[i] = NAN; }
-        return RBQ_OK;
-    }
-    if (max_lists > (1u << 26)) return fail(RBQ_INVALID_CONFIG, "too many lists per query");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
-    // exact work-list bound from the host copy of the list sizes (a list may legally repeat)
-    uint64_t wl_stride = 1;
-    for (uint64_t q = 0; q < nq; ++q) {
-        uint64_t tot = 0;
-        const uint32_t n = std::min(list_counts[q], max_lists);
-        for (uint32_t r = 0; r < n; ++r) {
-            const uint32_t cid = list_ids[q * max_lists + r];
-            if (cid < ix->n_lists) tot += (ix->h_list_n[cid] + 31u) / 32u;
-        }
-        wl_stride = std::max(wl_stride, tot);
-    }
-    if (wl_stride > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "posting lists too long for one query");
-    Workspace* w = take_ws(ix);
-    if (!w) return fail(RBQ_DEVICE, "cannot create workspace stream");
-    auto run = [&]() -> int {
-        int r2;
-        const uint32_t D = ix->D, Dc = ix->Dc;
-        const uint64_t CH = 16384;
-        DevBuf& d_lists = w->scores; // reuse: [n][max_lists] u32
-        DevBuf& d_cnts = w->nvec;    // reuse: [n] u32
-        for (uint64_t q0 = 0; q0 < nq; q0 += CH) {
-            const uint64_t n = std::min(CH, nq - q0);
-            const OutPack op(n, top_k, false);
-            if ((r2 = w->queries.ensure(n * query_dim * 4))) return r2;
-            if ((r2 = w->rot.ensure(n * D * 4))) return r2;
-            if ((r2 = w->lut.ensure(n * (size_t)Dc * 4))) return r2;
-            if ((r2 = w->consts.ensure(n * sizeof(QueryConsts)))) return r2;
-            if ((r2 = d_lists.ensure(n * (size_t)max_lists * 4))) return r2;
-            if ((r2 = d_cnts.ensure(n * 8))) return r2;
-            if ((r2 = w->probe.ensure(n * (size_t)max_lists * sizeof(ProbeInfo)))) return r2;
-            if ((r2 = w->wl.ensure(n * wl_stride * sizeof(StreamItem)))) return r2;
-            if ((r2 = w->nstream.ensure(n * 4))) return r2;
-            if ((r2 = w->out_pack.ensure(op.total))) return r2;
-            hipStream_t st = w->stream;
-            uint8_t* dp = (uint8_t*)w->out_pack.p;
-            HIP_TRY(hipMemcpyAsync(w->queries.p, queries + q0 * query_dim, n * query_dim * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_lists.p, list_ids + q0 * max_lists, n * (size_t)max_lists * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_cnts.p, list_counts + q0, n * 4, hipMemcpyHostToDevice, st));
-            {
-                ProfScope ps(ix, 0, st);
-                PrepParams p = prep_params(*ix, ix->rot_blob, *w, (const float*)w->queries.p, n);
-                p.ex_bits = 0u; // (MSTG: no ex codes)
-                HIP_TRY(launch_prep(p, ix->device, st));
-            }
-            {
-                ProfScope ps(ix, 2, st);
-                ProbesGivenParams p;
-                p.list_ids = (const uint32_t*)d_lists.p; p.list_counts = (const uint32_t*)d_cnts.p; p.max_lists = max_lists;
-                p.nq = (uint32_t)n; p.nlist = (uint32_t)ix->n_lists; p.metric = (int)ix->metric; p.rot = (const float*)w->rot.p;
-                p.cent = (const float*)ix->centroids.p; p.D = D; p.list_gb0 = (const uint32_t*)ix->list_gb0.p;
-                p.list_n = (const uint32_t*)ix->list_n.p; p.probe = (ProbeInfo*)w->probe.p; p.wl = (StreamItem*)w->wl.p;
-                p.wl_stride = wl_stride; p.nstream = (uint32_t*)w->nstream.p; p.consts = (const QueryConsts*)w->consts.p;
-                p.bsum = (const BlockSummary*)ix->bsum.p;
-                p.numeric_variant = ix->opt.numeric_variant;
-                HIP_TRY(launch_probes_given(p, st));
-            }
-            if ((r2 = scan_stage(ix, w, n, max_lists, top_k, wl_stride, nullptr, 0, (uint64_t*)(dp + op.o_ids), (float*)(dp + op.o_scores),
-                                 (uint32_t*)(dp + op.o_counts), nullptr, /*mstg=*/true, nullptr, st)))
-                return r2;
-            HIP_TRY(hipMemcpyAsync(out_ids + q0 * top_k, dp + op.o_ids, n * top_k * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_scores + q0 * top_k, dp + op.o_scores, n * top_k * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_counts + q0, dp + op.o_counts, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        return RBQ_OK;
-    };
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(w->stream);
-    give_ws(ix, w);
-    return rc;
-    RBQ_GUARD_END
-}
-
-
-// ---- MSTG search (include/rbq_mstg.h) ------------------------------------------------------------------
-// refined: rbq_mstg_search_refined_batch (the pool is max(refine_pool, top_k)); else rbq_mstg_search_batch
-static int ms_search_host(const rbq_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t ef_search,
-                          float pruning_epsilon, bool refined, uint32_t refine_pool, uint64_t* out_ids, float* out_scores,
-                          uint32_t* out_counts, uint32_t* out_list_ids, uint32_t* out_list_counts) {
-    g_err.clear();
-    RBQ_GUARD_BEGIN
-    rbq_index* h = const_cast<rbq_index*>(ch);
-    uint32_t pool = 0;
-    int rc = ms_check(h, queries, nq, query_dim, top_k, out_ids, out_scores, out_counts, refined, refine_pool, &pool);
-    if (rc || nq == 0) return rc;
-    Replica* ix = h->reps[0];
-    const uint32_t ef = (uint32_t)std::min<uint64_t>(ef_search, ix->n_lists);
-    if (top_k == 0 || ef == 0) { // no candidate: every count 0, every slot unused
-        std::memset(out_counts, 0, nq * 4);
-        if (out_list_counts) std::memset(out_list_counts, 0, nq * 4);
-        if (out_list_ids) std::memset(out_list_ids, 0xff, nq * (size_t)ef * 4);
-        for (uint64_t i = 0; i < nq * top_k; ++i) { out_ids[i] = ~0ull; out_scores[i] = NAN; }
-        return RBQ_OK;
-    }
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
-    if (mstg_select_gemm(ix->n_lists, ix->D) && (rc = ms_prepare(ix))) return rc;
-    unsigned long long* d_fb = nullptr;
-    if ((rc = ms_fallback_counter(ix->device, &d_fb))) return rc;
-    if (refined && (rc = mr_prepare(ix))) return rc;
-    const MstgShape sh = ms_shape(ix, nq, top_k, ef_search, true, pool);
-    if (sh.wl_stride > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "posting lists too long for one query");
-    Workspace* w = take_ws(ix);
-    if (!w) return fail(RBQ_DEVICE, "cannot create workspace stream");
-    auto run = [&]() -> int {
-        int r2;
-        hipStream_t st = w->stream;
-        for (uint64_t q0 = 0; q0 < nq; q0 += sh.chunk) {
-            const uint64_t n = std::min(sh.chunk, nq - q0);
-            const OutPack op(n, top_k, false);
-            if ((r2 = w->queries.ensure(n * query_dim * 4))) return r2;
-            if ((r2 = w->out_pack.ensure(op.total))) return r2;
-            if ((r2 = w->ms_lists.ensure(n * ((size_t)sh.ef + 1) * 4))) return r2;
-            uint8_t* dp = (uint8_t*)w->out_pack.p;
-            uint32_t* d_lists = (uint32_t*)w->ms_lists.p;
-            uint32_t* d_lcnt = d_lists + n * (size_t)sh.ef;
-            HIP_TRY(hipMemcpyAsync(w->queries.p, queries + q0 * query_dim, n * query_dim * 4, hipMemcpyHostToDevice, st));
-            r2 = refined ? mr_chunk(ix, w, (const float*)w->queries.p, n, top_k, pool, ef_search, pruning_epsilon, sh, d_fb, (uint64_t*)(dp + op.o_ids),
-                                    (float*)(dp + op.o_scores), (uint32_t*)(dp + op.o_counts), d_lists, d_lcnt, st)
-                         : ms_chunk(ix, w, (const float*)w->queries.p, n, top_k, ef_search, pruning_epsilon, sh, d_fb, (uint64_t*)(dp + op.o_ids),
-                                    (float*)(dp + op.o_scores), (uint32_t*)(dp + op.o_counts), d_lists, d_lcnt, st);
-            if (r2) return r2;
-            HIP_TRY(hipMemcpyAsync(out_ids + q0 * top_k, dp + op.o_ids, n * top_k * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_scores + q0 * top_k, dp + op.o_scores, n * top_k * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_counts + q0, dp + op.o_counts, n * 4, hipMemcpyDeviceToHost, st));
-            if (out_list_ids) HIP_TRY(hipMemcpyAsync(out_list_ids + q0 * sh.ef, d_lists, n * (size_t)sh.ef * 4, hipMemcpyDeviceToHost, st));
-            if (out_list_counts) HIP_TRY(hipMemcpyAsync(out_list_counts + q0, d_lcnt, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        return RBQ_OK;
-    };
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(w->stream);
-    give_ws(ix, w);
-    return rc;
-    RBQ_GUARD_END
-}
-
-static int ms_search_device(const rbq_index* ch, const float* d_queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
-                            uint32_t ef_search, float pruning_epsilon, bool refined, uint32_t refine_pool, uint64_t* d_out_ids,
-                            float* d_out_scores, uint32_t* d_out_counts, uint32_t* d_out_list_ids, uint32_t* d_out_list_counts,
-                            void* hip_stream) {
-    g_err.clear();
-    RBQ_GUARD_BEGIN
-    rbq_index* h = const_cast<rbq_index*>(ch);
-    uint32_t pool = 0;
-    int rc = ms_check(h, d_queries, nq, query_dim, top_k, d_out_ids, d_out_scores, d_out_counts, refined, refine_pool, &pool);
-    if (rc || nq == 0) return rc;
-    Replica* ix = replica_of_pointer(h, d_queries);
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
-    hipStream_t s = (hipStream_t)hip_stream;
-    const uint32_t ef = (uint32_t)std::min<uint64_t>(ef_search, ix->n_lists);
-    if (top_k == 0 || ef == 0) { // (all-ones words: UINT64_MAX ids, UINT32_MAX lists, NaN scores)
-        HIP_TRY(hipMemsetAsync(d_out_counts, 0, nq * 4, s));
-        if (d_out_list_counts) HIP_TRY(hipMemsetAsync(d_out_list_counts, 0, nq * 4, s));
-        if (d_out_list_ids && ef) HIP_TRY(hipMemsetAsync(d_out_list_ids, 0xff, nq * (size_t)ef * 4, s));
-        if (top_k) {
-            HIP_TRY(hipMemsetAsync(d_out_ids, 0xff, nq * (size_t)top_k * 8, s));
-            HIP_TRY(hipMemsetAsync(d_out_scores, 0xff, nq * (size_t)top_k * 4, s));
-        }
-        return RBQ_OK;
-    }
-    if (mstg_select_gemm(ix->n_lists, ix->D) && (rc = ms_prepare(ix))) return rc;
-    unsigned long long* d_fb = nullptr;
-    if ((rc = ms_fallback_counter(ix->device, &d_fb))) return rc;
-    if (refined && (rc = mr_prepare(ix))) return rc; // (the first refined call on a handle waits for its maps once)
-    const MstgShape sh = ms_shape(ix, nq, top_k, ef_search, false, pool);
-    if (sh.wl_stride > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "posting lists too long for one query");
-    Workspace* w; // one per caller stream, as rbq_search_batch_device: the chunks of a call and successive calls are stream-ordered
-    {
-        std::lock_guard<std::mutex> lk(ix->mu);
-        Workspace*& slot = ix->stream_ws[s];
-        if (!slot) slot = new Workspace();
-        w = slot;
-    }
-    const bool own_lists = !d_out_list_ids || !d_out_list_counts;
-    if (own_lists && (rc = w->ms_lists.ensure(sh.chunk * ((size_t)sh.ef + 1) * 4))) return rc;
-    for (uint64_t q0 = 0; q0 < nq; q0 += sh.chunk) {
-        const uint64_t n = std::min(sh.chunk, nq - q0);
-        uint32_t* d_lists = d_out_list_ids ? d_out_list_ids + q0 * sh.ef : (uint32_t*)w->ms_lists.p;
-        uint32_t* d_lcnt = d_out_list_counts ? d_out_list_counts + q0 : (uint32_t*)w->ms_lists.p + sh.chunk * (size_t)sh.ef;
-        rc = refined ? mr_chunk(ix, w, d_queries + q0 * query_dim, n, top_k, pool, ef_search, pruning_epsilon, sh, d_fb, d_out_ids + q0 * top_k,
-                                d_out_scores + q0 * top_k, d_out_counts + q0, d_lists, d_lcnt, s)
-                     : ms_chunk(ix, w, d_queries + q0 * query_dim, n, top_k, ef_search, pruning_epsilon, sh, d_fb, d_out_ids + q0 * top_k,
-                                d_out_scores + q0 * top_k, d_out_counts + q0, d_lists, d_lcnt, s);
-        if (rc) return rc;
-    }
-    return RBQ_OK;
-    RBQ_GUARD_END
-}
-
-int rbq_mstg_search_batch(const rbq_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t ef_search,
-                          float pruning_epsilon, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_list_ids,
-                          uint32_t* out_list_counts) {
-    return ms_search_host(idx, queries, nq, query_dim, top_k, ef_search, pruning_epsilon, false, 0, out_ids, out_scores, out_counts,
-                          out_list_ids, out_list_counts);
-}
-int rbq_mstg_search_batch_device(const rbq_index* idx, const float* d_queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
-                                 uint32_t ef_search, float pruning_epsilon, uint64_t* d_out_ids, float* d_out_scores,
-                                 uint32_t* d_out_counts, uint32_t* d_out_list_ids, uint32_t* d_out_list_counts, void* hip_stream) {
-    return ms_search_device(idx, d_queries, nq, query_dim, top_k, ef_search, pruning_epsilon, false, 0, d_out_ids, d_out_scores,
-                            d_out_counts, d_out_list_ids, d_out_list_counts, hip_stream);
-}
-int rbq_mstg_search_refined_batch(const rbq_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
-                                  uint32_t ef_search, float pruning_epsilon, uint32_t refine_pool, uint64_t* out_ids, float* out_scores,
-                                  uint32_t* out_counts, uint32_t* out_list_ids, uint32_t* out_list_counts) {
-    return ms_search_host(idx, queries, nq, query_dim, top_k, ef_search, pruning_epsilon, true, refine_pool, out_ids, out_scores, out_counts,
-                          out_list_ids, out_list_counts);
-}
-int rbq_mstg_search_refined_batch_device(const rbq_index* idx, const float* d_queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
-                                         uint32_t ef_search, float pruning_epsilon, uint32_t refine_pool, uint64_t* d_out_ids,
-                                         float* d_out_scores, uint32_t* d_out_counts, uint32_t* d_out_list_ids,
-                                         uint32_t* d_out_list_counts, void* hip_stream) {
-    return ms_search_device(idx, d_queries, nq, query_dim, top_k, ef_search, pruning_epsilon, true, refine_pool, d_out_ids, d_out_scores,
-                            d_out_counts, d_out_list_ids, d_out_list_counts, hip_stream);
-}
-
-uint64_t rbq_mstg_debug_search_fallbacks(void) {
-    uint64_t total = 0;
-    for (int dev = 0; dev < 16; ++dev) {
-        unsigned long long* p;
-        { std::lock_guard<std::mutex> lk(g_ms_mu); p = g_ms_fallbacks[dev]; }
-        if (!p) continue;
-        DeviceGuard g(dev);
-        unsigned long long v = 0;
-        if (g.ok && hipMemcpy(&v, p, 8, hipMemcpyDeviceToHost) == hipSuccess) total += v;
-        else (void)hipGetLastError();
-    }
-    return total;
 }
 
 // Which kernel instantiation each of the four stages launches for a call of this shape, and what it occupies.

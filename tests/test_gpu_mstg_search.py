@@ -154,6 +154,30 @@ def test_result_does_not_depend_on_the_chunk_budget():
     idx.close()
 
 
+def test_posting_scan_does_not_depend_on_its_own_chunks():
+    """rbq_posting_scan_batch cuts a call into chunks of 16384 queries: one call over 16384 + 5 queries (two chunks) equals two
+    calls over the rows of each chunk.  Lists of 0, 1, 32 and 33 vectors; the queries of the second chunk name the longest twice."""
+    rng = np.random.default_rng(101)
+    lens, dim, cut = (0, 1, 32, 33), 16, 16384
+    nq = cut + 5
+    assign = np.repeat(np.arange(4), lens).astype(np.uint32)
+    cent = (rng.standard_normal((4, dim)) * 3).astype(np.float32)
+    data = (cent[assign] + 0.3 * rng.standard_normal((len(assign), dim))).astype(np.float32)
+    built = rq.builder.train_with_clusters(data, cent, assign, 3, 0, rq.RotatorType.NoRotation, 101, True)
+    q = (data[rng.integers(0, len(data), nq)] + 0.2 * rng.standard_normal((nq, dim))).astype(np.float32)
+    lists = np.tile(np.arange(4, dtype=np.uint32), (nq, 1))
+    lists[cut:, 0] = 3
+    counts = np.full(nq, 4, np.uint32)
+    idx = rq.IvfRabitqIndex.from_built(built)
+    ids, sc, cnt = idx.posting_scan(q, 3, lists, counts)
+    assert (cnt == 3).all()  # (every query scans at least the 32 + 33 vectors of lists 2 and 3)
+    for rows in (slice(0, cut), slice(cut, nq)):
+        pids, psc, pcnt = idx.posting_scan(q[rows], 3, lists[rows], counts[rows])
+        assert np.array_equal(cnt[rows], pcnt) and np.array_equal(ids[rows], pids)
+        assert np.array_equal(sc[rows].view(np.uint32), psc.view(np.uint32))
+    idx.close()
+
+
 def test_handle_built_on_the_device_is_searched_end_to_end():
     rng = np.random.default_rng(12)
     cent = (rng.standard_normal((300, 64)) * 3).astype(np.float32)
