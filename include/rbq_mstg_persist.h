@@ -63,8 +63,7 @@ int rbq_mstg_save_stream(const rbq_index* idx, const rbq_mstg_config* cfg, rbq_w
 /* Whole-stream convenience: *bytes (free with rbq_persist_free_bytes) holds *len bytes. */
 int rbq_mstg_save(const rbq_index* idx, const rbq_mstg_config* cfg, uint8_t** bytes, uint64_t* len);
 
-/* Reads `len` bytes at stream offset `offset` into dst; returns 0, or anything else when the range cannot be read. */
-typedef int (*rbq_read_fn)(void* user, uint64_t offset, void* dst, uint64_t len);
+/* (rbq_read_fn, the reader callback of the stream loaders, is declared in rbq_persist.h.) */
 
 /* Loads a `.mstg` stream onto `device` (-1: the current device).  The framing (config, ids, list headers) is parsed on
  * the host; the records are uploaded in spans of whole lists or 32-vector blocks (at most 64 MB unless one block is larger,

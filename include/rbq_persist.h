@@ -42,6 +42,28 @@ void rbq_persist_free_bytes(uint8_t* bytes);
 /* Test hook: CRC-32/IEEE of `len` device bytes at `d_bytes` (any alignment) on `device`, with the save path's kernels. */
 int rbq_debug_crc32_device(const void* d_bytes, uint64_t len, int device, uint32_t* out);
 
+/* Reads `len` bytes at stream offset `offset` into dst; returns 0, or anything else when the range cannot be read. */
+typedef int (*rbq_read_fn)(void* user, uint64_t offset, void* dst, uint64_t len);
+
+/* rbq_index_load_rbq1 over a reader: the same handle, bit for bit, and the same errors (code and rbq_last_error_detail) as
+ * rbq_index_load_rbq1 gives for the same `total_len` bytes, without the stream ever lying in host memory as a whole.
+ * A framing pass on the host reads the header, the rotator and, per cluster, the two fields that fix its layout (the
+ * vector count and batch_data's length).  The cluster region is then read in spans of at most 64 MB cut at field
+ * boundaries (whole batch records, whole length-prefixed ex codes, whole ids, whole f32s: a span may end inside a list and
+ * inside any of its sections); the read of span i + 1 overlaps the kernels on span i.  The GPU checksums every span
+ * (the span CRCs are combined with the host CRC of header and rotator), checks every ex-code length prefix and scatters
+ * the span into the device layout.  Host memory: two page-locked spans, their piece tables and 12 bytes per list.
+ * `read` is called on the calling thread only, for ranges inside [0, total_len) of at most one span each; a non-zero
+ * return is RBQ_IO "read callback failed".  A null `read` or `out` is RBQ_INVALID_CONFIG.  *out is null after any error
+ * and nothing is leaked.  Bytes after the checksum are ignored. */
+int rbq_index_load_rbq1_stream(rbq_read_fn read, void* user, uint64_t total_len, int n_devices, const int* devices,
+                               rbq_index** out);
+
+/* Test hook, process-wide: the span size of rbq_index_load_rbq1_stream in bytes; returns the previous value (0: the 64 MB
+ * default, which 0 also restores).  A value below the largest indivisible unit of the stream being loaded (one batch
+ * record) is raised to that unit; one above 1 GiB is lowered to 1 GiB.  The loaded index does not depend on it. */
+uint64_t rbq_debug_set_load_span(uint64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 //   k_bf_train.hip  brute-force index: the encoder's flat output, ex_code_packed         (encode_vec.hpp)
 //   k_mstg.hip   MSTG closure assignment (ClosureAssigner::assign) and its host driver       (km_common.hpp)
 //   k_mstg_save.hip  `.mstg` writer and loader: device layout <-> the crate's bincode records
+//   k_load.hip   streamed RBQ1 loader: spans of the stream -> device layout, ex-code prefix check
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, rank_mfma.hpp)
 //   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan.hpp)
 #pragma once
@@ -20,6 +21,7 @@
 #include "types.hpp"
 
 namespace rbq_host { struct HcResult; } // csrc/host/rbq_hcluster.hpp
+namespace rbq_host { struct LoadPiece; } // csrc/host/rbq_load_stream.hpp
 
 namespace rbq {
 
@@ -420,6 +422,30 @@ struct MstgLoadParams {
     uint32_t D, Dc, ex_bits, R, E;
 };
 hipError_t launch_mstg_load_scatter(const MstgLoadParams& P, hipStream_t s);
+
+// ---- streamed RBQ1 loader (k_load.hip; rbq_index_load_rbq1_stream, csrc/host/rbq_load_stream.hpp) -------------------------------
+// One span of the stream's cluster region (file bytes [span_off, ...) at `span`, 256-byte aligned) and its pieces.  Workgroup w
+// serves the piece with the largest wg0 <= w: it writes that piece's units into the device layout (scatter != 0: centroids,
+// un-interleaved batch records, ids / factors over the 32-padded slots with their fills, re-packed ex codes) and folds the file
+// position of every ex-code length prefix that is not exb into *bad_prefix with an atomic minimum.  scatter == 0: the prefix check
+// only (a stream this build cannot serve, or one whose framing already failed); the output arrays are then not touched.
+struct LoadSpanParams {
+    const uint8_t* span;
+    uint64_t span_off;
+    const rbq_host::LoadPiece* pieces;
+    uint32_t n_pieces, scatter;
+    uint32_t D, Dc, ex_bits;
+    uint64_t exb;               // bytes of a packed ex code in the stream (D * ex_bits / 8)
+    uint32_t* centroids;        // [n_lists][D] f32 bit patterns
+    uint8_t* blocks;
+    uint64_t* ids;
+    uint8_t* ex;
+    uint32_t *fadd_ex, *fres_ex, *delta, *vl; // f32 bit patterns, slot order
+    unsigned long long* bad_prefix;
+};
+hipError_t launch_load_span(const LoadSpanParams& P, uint64_t n_workgroups, hipStream_t s);
+// block_nv[b] = real vectors of global block b (1..32), from the lists' first blocks and sizes
+hipError_t launch_load_block_nv(const uint32_t* list_gb0, const uint32_t* list_n, uint32_t n_lists, uint32_t* block_nv, hipStream_t s);
 
 // ---- fetch_embedding (k_fetch.hip) -------------------------------------------------------------------------------------------
 // id map: the (id, slot) pairs of every real slot in (cluster, position) order, stably sorted by id.  vstart [n_lists + 1] =

@@ -138,6 +138,10 @@ def lib():
         L.rbq_persist_free_bytes.argtypes = [C.POINTER(C.c_uint8)]
         L.rbq_debug_crc32_device.restype = C.c_int
         L.rbq_debug_crc32_device.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]
+        L.rbq_index_load_rbq1_stream.restype = C.c_int
+        L.rbq_index_load_rbq1_stream.argtypes = [READ_FN, vp, C.c_uint64, C.c_int, vp, C.POINTER(vp)]
+        L.rbq_debug_set_load_span.restype = C.c_uint64
+        L.rbq_debug_set_load_span.argtypes = [C.c_uint64]
         L.rbq_index_fetch_embeddings.restype = C.c_int
         L.rbq_index_fetch_embeddings.argtypes = [vp, vp, C.c_uint64, vp, vp]
         L.rbq_index_fetch_embeddings_device.restype = C.c_int
@@ -356,6 +360,45 @@ class IvfRabitqIndex:
             from . import RabitqError
             raise RabitqError(_abi.RBQ_IO, str(e))
         return cls.load_from_bytes(data, device)
+
+    @classmethod
+    def load_from_reader(cls, fileobj, device=None, devices=None):
+        """`load_from_reader` over a binary file object (rbq_index_load_rbq1_stream): the stream runs from the object's
+        current position to its end and is read span by span (at most 64 MB each) straight into the loader's page-locked
+        buffers; the GPU checksums it and lays it out.  The index equals load_from_bytes' of the same bytes.  `fileobj`
+        needs seek, tell and readinto (or read).  An exception raised by the file object stops the load and is re-raised."""
+        start = fileobj.tell()
+        fileobj.seek(0, os.SEEK_END)
+        total = fileobj.tell() - start
+        readinto = getattr(fileobj, "readinto", None)
+        err = []
+
+        def cb(_user, off, dst, n):
+            try:
+                fileobj.seek(start + off)
+                view = memoryview((C.c_ubyte * n).from_address(dst)).cast("B")
+                got = 0
+                while got < n:
+                    if readinto is not None:
+                        k = readinto(view[got:])
+                    else:
+                        chunk = fileobj.read(n - got)
+                        k = len(chunk)
+                        view[got:got + k] = chunk
+                    if not k:
+                        return 1  # the object ended before the range did
+                    got += k
+                return 0
+            except BaseException as e:  # noqa: BLE001 - handed back to the caller after the C call returns
+                err.append(e)
+                return 1
+        h = C.c_void_p()
+        n, dev = cls._devices(device, devices)
+        rc = lib().rbq_index_load_rbq1_stream(READ_FN(cb), None, max(int(total), 0), n, dev, C.byref(h))
+        if err:
+            raise err[0]
+        _check(rc)
+        return cls(h)
 
     # -- persistence: save_to_writer (src/ivf.rs:1310-1474), bytes assembled on the device ------------------------
     def save_to_writer(self, fileobj):
