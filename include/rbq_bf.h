@@ -87,6 +87,13 @@ int rbq_bf_search_batch(const rbq_bf_index* idx, const float* queries, uint64_t 
  * BinaryHeap emulation, out2[1] = those among them whose outcome depends on the heap's layout (a key equal to the root, or a
  * push made while equal keys sat on the heap's root-to-last-slot path: the ties of the reference's BinaryHeap). */
 void rbq_bf_debug_heap_stats(const rbq_bf_index* idx, uint64_t* out2);
+/* TEST ONLY, process-wide: at most `vectors` vectors per chunk of rbq_bf_search_batch; returns the previous value (0: the
+ * default, as many as the 128 MiB distance workspace holds for one query, which 0 also restores).  A call reads it once,
+ * before its first launch.  The budgets that size the query sub-batch are untouched and results do not depend on it: it
+ * exists so that a test can run the several-chunk path (heap state carried between chunks) on a small index. */
+uint64_t rbq_bf_debug_set_chunk_vectors(uint64_t vectors);
+/* TEST ONLY, process-wide: selection launches of every rbq_bf_search_batch so far, one per (query sub-batch, vector chunk). */
+uint64_t rbq_bf_debug_select_launches(void);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,14 @@ int rbq_kmeans_device(const float* d_data, uint64_t n, uint32_t dim, uint64_t k,
                       int spherical, uint64_t max_points_per_centroid, uint64_t decode_block_size, int device, float* centroids,
                       uint32_t* d_assignments, double* objective, uint64_t* stats);
 
+/* TEST ONLY, process-wide: at most `rows` rows per pass of the chunked assignment (rounded down to a multiple of 128, at
+ * least 128); returns the previous value (0: the default, by the 512 MiB workspace, which 0 also restores).  It applies to
+ * rbq_kmeans_device and to the splits of rbq_mstg_cluster_device above 256 subclusters, read when a call sizes its
+ * workspace; the closure assignment keeps its own max_chunk_rows.  Results and stats do not depend on it. */
+uint64_t rbq_debug_set_kmeans_chunk_rows(uint64_t rows);
+/* TEST ONLY, process-wide: passes of the chunked assignment run so far (one per chunk of rows per assignment). */
+uint64_t rbq_debug_kmeans_assign_passes(void);
+
 #ifdef __cplusplus
 }
 #endif

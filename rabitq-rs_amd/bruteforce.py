@@ -43,6 +43,10 @@ def lib():
         L.rbq_bf_search_batch.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
         L.rbq_bf_debug_heap_stats.restype = None
         L.rbq_bf_debug_heap_stats.argtypes = [vp, vp]
+        L.rbq_bf_debug_set_chunk_vectors.restype = C.c_uint64
+        L.rbq_bf_debug_set_chunk_vectors.argtypes = [C.c_uint64]
+        L.rbq_bf_debug_select_launches.restype = C.c_uint64
+        L.rbq_bf_debug_select_launches.argtypes = []
         _BOUND = True
     return L
 

@@ -14,6 +14,8 @@ constexpr uint64_t kBfHeapBudget = 48ull << 20;  // heap workspace (between vect
 constexpr uint64_t kBfOutBudget = 48ull << 20;   // result buffers of one sub-batch
 constexpr uint64_t kBfMaxSubBatch = 1024;
 constexpr uint64_t kBfTrainRowBudget = 512ull << 20; // rotated rows of one training pass (the IVF encoder's scratch budget)
+std::atomic<uint64_t> g_bf_chunk_vectors{0};   // rbq_bf_debug_set_chunk_vectors (0: the default)
+std::atomic<uint64_t> g_bf_select_launches{0}; // rbq_bf_debug_select_launches
 
 struct BfWorkspace {
     hipStream_t stream = nullptr;
@@ -181,7 +183,8 @@ int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t
     const uint64_t n = ix->hdr.n_vectors, K = top_k;
     const uint32_t dim = ix->hdr.dim, D = ix->hdr.padded_dim;
     // plan: vector chunks of at most kBfDistBudget / 4 vectors, sub-batches of queries within the workspace budgets
-    const uint64_t nv_chunk = std::min<uint64_t>(n, kBfDistBudget / 4);
+    const uint64_t cap = g_bf_chunk_vectors.load(std::memory_order_relaxed); // (test hook: read once per call)
+    const uint64_t nv_chunk = std::min<uint64_t>({n, kBfDistBudget / 4, cap ? cap : UINT64_MAX});
     const uint64_t n_chunks = (n + nv_chunk - 1) / nv_chunk;
     const bool lds_heap = top_k <= kBfLdsHeapMaxTopK;
     const bool heap_ws = n_chunks > 1 || !lds_heap;
@@ -232,6 +235,7 @@ int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t
             sp.out_ids = (uint64_t*)w->ids.p; sp.out_scores = (float*)w->scores.p; sp.out_counts = (uint32_t*)w->counts.p;
             sp.stats = (unsigned long long*)w->stats.p;
             HIP_TRY(launch_bf_select(sp, st));
+            g_bf_select_launches.fetch_add(1, std::memory_order_relaxed);
         }
         HIP_TRY(hipMemcpyAsync(out_ids + q0 * K, w->ids.p, (size_t)m * K * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(out_scores + q0 * K, w->scores.p, (size_t)m * K * 4, hipMemcpyDeviceToHost, st));
@@ -335,6 +339,8 @@ void rbq_bf_debug_heap_stats(const rbq_bf_index* idx, uint64_t* out2) {
     out2[0] = idx->pushes.load();
     out2[1] = idx->tie_pushes.load();
 }
+uint64_t rbq_bf_debug_set_chunk_vectors(uint64_t vectors) { return g_bf_chunk_vectors.exchange(vectors, std::memory_order_relaxed); }
+uint64_t rbq_bf_debug_select_launches(void) { return g_bf_select_launches.load(std::memory_order_relaxed); }
 
 int rbq_bf_search_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
                         const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {

@@ -428,6 +428,8 @@ int rbq_kmeans_device(const float* d_data, uint64_t n, uint32_t dim, uint64_t k,
     return rc ? fail(rc, detail) : RBQ_OK;
     RBQ_GUARD_END
 }
+uint64_t rbq_debug_set_kmeans_chunk_rows(uint64_t rows) { return g_km_chunk_rows_cap.exchange(rows, std::memory_order_relaxed); }
+uint64_t rbq_debug_kmeans_assign_passes(void) { return g_km_assign_passes.load(std::memory_order_relaxed); }
 int rbq_build_stream_push(rbq_builder* b, const float* vectors, const uint32_t* assign, uint64_t first_id, uint64_t count) {
     g_err.clear();
     RBQ_GUARD_BEGIN

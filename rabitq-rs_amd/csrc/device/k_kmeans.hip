@@ -35,6 +35,8 @@
 
 namespace rbq {
 
+std::atomic<uint64_t> g_km_chunk_rows_cap{0}, g_km_assign_passes{0}; // launch.hpp
+
 // spherical: c *= 1 / sqrt(|c|^2) when |c|^2 > 0 (correctly rounded sqrt and division)
 __global__ __launch_bounds__(256) void k_km_normalize(float* __restrict__ cent, uint32_t k, uint32_t dim) {
     const uint32_t c = blockIdx.x * 256u + threadIdx.x;

@@ -270,6 +270,8 @@ struct KmGemmAssign {
     static uint64_t chunk_rows(uint64_t rows, uint64_t k, uint32_t Dp) {
         const uint64_t per_row = 4 * k + 4ull * Dp + 4ull * kShortlist + 4;
         uint64_t r = (kKmeansChunkBytes / per_row) / 128 * 128;
+        const uint64_t cap = g_km_chunk_rows_cap.load(std::memory_order_relaxed); // (test hook; 0: none)
+        if (cap && cap / 128 * 128 < r) r = cap / 128 * 128; // (below 128: the floor that follows)
         r = r > 128 ? r : 128;
         const uint64_t all = (rows + 127) / 128 * 128;
         return r < all ? r : all;
@@ -298,6 +300,7 @@ struct KmGemmAssign {
         for (uint64_t r0 = 0; r0 < m; r0 += R) {
             const uint32_t nr = (uint32_t)(m - r0 < R ? m - r0 : R);
             const float* xc = xs + r0 * dim;
+            g_km_assign_passes.fetch_add(1, std::memory_order_relaxed);
             hipLaunchKernelGGL(k_km_split, dim3((unsigned)(((uint64_t)nr * Dp + 255) / 256)), dim3(256), 0, s, xc, nr, dim, Dp, xh, xl);
             hipError_t e = hipGetLastError();
             if (e) return e;

@@ -258,6 +258,9 @@ hipError_t launch_bf_pack_ex(const uint8_t* raw, uint64_t nrows, uint32_t D, uin
 
 // ---- k-means (k_kmeans.hip): run_kmeans_with_config on the current device, arguments already validated (rbq_kmeans_device)
 constexpr uint64_t kKmeansChunkBytes = 512ull << 20; // per-chunk assignment workspace (R rows x (4k + 4Dp + shortlist) bytes, R >= 128)
+// test hooks of KmGemmAssign (km_common.hpp), defined in k_kmeans.hip: a cap on the rows per pass (rbq_debug_set_kmeans_chunk_rows,
+// 0: none) and the passes run so far (rbq_debug_kmeans_assign_passes)
+extern std::atomic<uint64_t> g_km_chunk_rows_cap, g_km_assign_passes;
 struct KMeansArgs {
     const float* data; // device [n][dim]
     uint64_t n;

@@ -127,6 +127,10 @@ def lib():
         L.rbq_kmeans_device.restype = C.c_int
         L.rbq_kmeans_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
                                         C.c_uint64, C.c_uint64, C.c_int, vp, vp, C.POINTER(C.c_double), vp]
+        L.rbq_debug_set_kmeans_chunk_rows.restype = C.c_uint64
+        L.rbq_debug_set_kmeans_chunk_rows.argtypes = [C.c_uint64]
+        L.rbq_debug_kmeans_assign_passes.restype = C.c_uint64
+        L.rbq_debug_kmeans_assign_passes.argtypes = []
         # rbq_persist.h
         L.rbq_index_create_with_recon.restype = C.c_int
         L.rbq_index_create_with_recon.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.POINTER(vp)]
