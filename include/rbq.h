@@ -317,15 +317,18 @@ uint64_t rbq_debug_head_exact_guard_trips(const rbq_index* idx);
  * std BinaryHeap, whose tie behaviour depends on its layout). Diagnostic. */
 uint64_t rbq_debug_heap_restarts(const rbq_index* idx);
 /* Diagnostic: copy one of the index's device arrays ("blocks", "ids", "ex", "fadd_ex", "fres_ex", "bsum", "lsum", "bsumx",
- * "centroids", "list_gb0", "list_n"; the ranking GEMM's operands "cent_hi", "cent_lo" — the split-bf16 image of the centroids,
- * [nlist][D] u16 — and "cnorm2", [nlist] f32) to the host; `bytes` must be the array's exact size. */
+ * "centroids", "list_gb0", "list_n"; the ranking GEMM's operand "cent_hl" — the split-bf16 image of the centroids as the device
+ * keeps it, [nlist][2 D] u16 with the 32 hi and the 32 lo values of every 32-element K slab side by side (one 128-byte line per row
+ * and slab) — and its logical planes "cent_hi", "cent_lo", [nlist][D] u16, de-interleaved by the copy; "cnorm2", [nlist] f32) to the
+ * host; `bytes` must be the array's exact size. */
 int rbq_debug_copy_index(rbq_index* idx, const char* name, void* dst, uint64_t bytes);
 /* test hook: t of best_rescale_factor for n rows of o = |r_i| / norm(r) (host [n][dim] f32, every value in [0, 1];
  * dim <= 2048, 1 <= ex_bits <= 7) -> out_t [n] f64, computed by the device encoder's kernel */
 int rbq_debug_best_rescale(const float* o_abs, uint64_t n, uint32_t dim, uint32_t ex_bits, int device, double* out_t);
 /* Diagnostic: copy an intermediate buffer ("rot", "lut", "consts", "scores", "probe", "nstream", "wl", "nvec", "dead_skipped",
- * "audit_dead", "head_ub"; "rot_hi", "rot_lo": the split-bf16 image of the rotated queries, [nq][D] u16, written only when the split-bf16
- * ranking GEMM serves the call) of the workspace that rbq_search_batch_device bound to `hip_stream`; the caller has synchronised
+ * "audit_dead", "head_ub"; "rot_hl": the split-bf16 image of the rotated queries, [nq][2 D] u16 in the layout of "cent_hl", written only
+ * when the split-bf16 ranking GEMM serves the call, and "rot_hi", "rot_lo": its planes, [nq][D] u16, de-interleaved by the copy) of the
+ * workspace that rbq_search_batch_device bound to `hip_stream`; the caller has synchronised
  * that stream. */
 int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name, void* dst, uint64_t bytes);
 /* Diagnostic switches; results are identical under every setting, only the work done changes:
@@ -353,6 +356,8 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *   "rank_ksplit" 0      never split the K loop of the ranking GEMM (default 1: calls of up to 256 queries split it 2-4 ways over
  *                        grid.z, the parts added atomically to a cleared row; n > 1 forces min(n, 4) parts, the most the
  *                        shortlist's error bound is derived for)
+ *   "rank_planar" 1      TEST ONLY: the split-bf16 ranking GEMM reads planar copies of its operands (two planes [rows][D] each,
+ *                        de-interleaved per call) instead of the interleaved images — same kernel, same scores bit for bit
  * and three that are not result-neutral:
  *   "rerank" 0/1         the optional full-precision rerank (needs rbq_index_set_rerank_vectors)
  *   "numeric_variant" v  rbq_index_set_numeric_variant(idx, v): which build of the reference the scores reproduce

@@ -243,7 +243,9 @@ using ReplicaPool = WorkerPool<std::function<void()>, 2>;
 
 struct Workspace {
     hipStream_t stream = nullptr;
-    DevBuf queries, rot, lut, consts, scores, probe, wl, nstream, nvec, out_pack, filter, rot_hi, rot_lo, dead_skipped, heap_ws, key_window, audit_dead, tie_log, head_ub;
+    DevBuf queries, rot, lut, consts, scores, probe, wl, nstream, nvec, out_pack, filter, rot_hl, rank_planes, dead_skipped, heap_ws, key_window, audit_dead, tie_log, head_ub;
+    // rot_hl: the split-bf16 image of the rotated queries, hi | lo interleaved per K slab (hl_layout.hpp); rank_planes: planar
+    // copies of both GEMM operands (debug option rank_planar)
     DevBuf ms_sl, ms_lists; // rbq_mstg_search_batch*: shortlists | their lengths | query norms; the selected lists | their counts
     DevBuf mr_pool;         // rbq_mstg_search_refined_batch*: the pool's slots [n][pool] u64 | estimates [n][pool] f32 | counts [n] u32
     PinBuf h_in, h_out;      // rbq_search_batch: staging of one sub-batch
@@ -314,7 +316,7 @@ PrepParams prep_params(const Geometry& g, const Arr& rot_blob, Ws& w, const floa
     p.queries = queries; p.nq = (uint32_t)nq; p.dim = g.dim; p.D = g.D; p.Dc = g.Dc; p.rotator = (int)g.rotator;
     p.rot_blob = (const uint8_t*)rot_blob.p; p.trunc = g.trunc; p.fac = g.fac; p.ex_bits = g.ex_bits;
     p.rot = (float*)w.rot.p; p.lut = (uint8_t*)w.lut.p; p.consts = (QueryConsts*)w.consts.p;
-    p.rot_hi = nullptr; p.rot_lo = nullptr; p.wg_prep = false;
+    p.rot_hl = nullptr; p.wg_prep = false;
     return p;
 }
 
@@ -345,6 +347,7 @@ struct Options {
     bool tie_log = true;      // k_scan logs the candidates it refines; a tied query replays the log (scan.hpp)
     int latency_path = 1;     // small calls (see kLatMaxQueries) take the latency-first front (latency.hpp); 0 = never
     int rank_tile = 0;        // tile of the split-bf16 ranking GEMM (0 = by problem size)
+    bool rank_planar = false; // TEST ONLY: the split-bf16 ranking GEMM reads planar copies of its operands (de-interleaved per call)
     uint32_t stage_mask = 0xf; // DIAGNOSTIC: bit s = launch stage s (prep, rank, select, scan); a skipped stage leaves the workspace
                                // of the stream as the last full call wrote it — results are then those of THAT batch (rate probes only)
     int scan_wave = scan_wave_default(); // which scan kernel serves a call: 0 = k_scan (one workgroup per query), 1 = k_scanw (one wave per
@@ -363,10 +366,10 @@ struct Options {
 struct Replica : Geometry {
     int device = 0;
     uint64_t n_vectors = 0, n_lists = 0, n_blocks = 0;
-    Arr rot_blob, centroids, blocks, ids, ex, fadd_ex, fres_ex, list_gb0, list_n, prof, bsum, cnorm2, fallbacks, cent_hi, cent_lo, raw,
+    Arr rot_blob, centroids, blocks, ids, ex, fadd_ex, fres_ex, list_gb0, list_n, prof, bsum, cnorm2, fallbacks, cent_hl, raw,
         bsumx, lsum; // ex-factor ranges per block, factor ranges per list (lazy probe selection)
-    Arr* arrays[18] = {&rot_blob, &centroids, &blocks, &ids, &ex, &fadd_ex, &fres_ex, &list_gb0, &list_n, &prof, &bsum, &cnorm2,
-                       &fallbacks, &cent_hi, &cent_lo, &raw, &bsumx, &lsum};
+    Arr* arrays[17] = {&rot_blob, &centroids, &blocks, &ids, &ex, &fadd_ex, &fres_ex, &list_gb0, &list_n, &prof, &bsum, &cnorm2,
+                       &fallbacks, &cent_hl, &raw, &bsumx, &lsum};
     // reconstruction factors delta / vl of every slot (RBQ1's per-vector arrays that search never reads): kept on the FIRST
     // replica only, for rbq_index_save_rbq1 (not in `arrays`: clone_replica does not copy them)
     Arr delta, vl;

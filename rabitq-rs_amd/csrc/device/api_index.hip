@@ -109,10 +109,8 @@ int finish_replica(Replica* ix, const std::vector<uint32_t>& ln) {
     }
     int rc;
     if ((rc = alloc_arr(ix->cnorm2, (size_t)nlist * 4))) return rc;
-    if ((rc = alloc_arr(ix->cent_hi, (size_t)nlist * D * 2))) return rc;
-    if ((rc = alloc_arr(ix->cent_lo, (size_t)nlist * D * 2))) return rc;
-    HIP_TRY(launch_centroid_arrays((const float*)ix->centroids.p, nlist, D, (float*)ix->cnorm2.p, (uint16_t*)ix->cent_hi.p,
-                                   (uint16_t*)ix->cent_lo.p, 0));
+    if ((rc = alloc_arr(ix->cent_hl, (size_t)nlist * D * 4))) return rc;
+    HIP_TRY(launch_centroid_arrays((const float*)ix->centroids.p, nlist, D, (float*)ix->cnorm2.p, (uint16_t*)ix->cent_hl.p, 0));
     std::vector<float> cn(nlist);
     HIP_TRY(hipMemcpy(cn.data(), ix->cnorm2.p, (size_t)nlist * 4, hipMemcpyDeviceToHost));
     double mx = 0;
@@ -145,6 +143,7 @@ int Options::set(const char* name, int v) {
     else if (is("exact_heap")) exact_heap = v != 0;
     else if (is("lazy_select")) lazy_select = v != 0;
     else if (is("rank_tile")) rank_tile = v;
+    else if (is("rank_planar")) rank_planar = v != 0;
     else if (is("latency_path")) latency_path = v;
     else if (is("tie_log")) tie_log = v != 0;
     else if (is("tie_log_cap")) tie_log_cap = v > 0 ? (uint32_t)v : 0u;
@@ -715,6 +714,20 @@ uint64_t rbq_debug_bounce_copies(void) { return g_bounce_copies.load(std::memory
 uint64_t rbq_debug_heap_restarts(const rbq_index* h) { return read_counter(h, 1); }
 
 
+namespace {
+// 0 / 1 when `name` is the hi / lo plane's name, else -1
+int hl_plane_of(const char* name, const char* hi, const char* lo) { return !std::strcmp(name, hi) ? 0 : (!std::strcmp(name, lo) ? 1 : -1); }
+// host mirror of the interleaved split-bf16 image (hl_layout.hpp): plane `plane` of `rows` rows at d_hl, [rows][D] u16, to dst
+int copy_hl_plane(const void* d_hl, uint64_t rows, uint32_t D, int plane, void* dst) {
+    std::vector<uint16_t> hl((size_t)rows * 2 * D);
+    HIP_TRY(hipMemcpy(hl.data(), d_hl, hl.size() * 2, hipMemcpyDeviceToHost));
+    uint16_t* out = (uint16_t*)dst;
+    for (uint64_t r = 0; r < rows; ++r)
+        for (uint32_t i = 0; i < D; ++i) out[r * D + i] = hl[r * 2 * D + hl_offset(i, (uint32_t)plane, D)];
+    return RBQ_OK;
+}
+} // namespace
+
 /* Diagnostic: copy an intermediate buffer of the workspace bound to `hip_stream` (after the caller synchronised). */
 int rbq_debug_copy_workspace(rbq_index* h, void* hip_stream, const char* name, void* dst, uint64_t bytes) {
     g_err.clear();
@@ -732,11 +745,16 @@ int rbq_debug_copy_workspace(rbq_index* h, void* hip_stream, const char* name, v
         {"rot", &Workspace::rot}, {"lut", &Workspace::lut}, {"consts", &Workspace::consts}, {"scores", &Workspace::scores},
         {"probe", &Workspace::probe}, {"nstream", &Workspace::nstream}, {"wl", &Workspace::wl}, {"nvec", &Workspace::nvec},
         {"dead_skipped", &Workspace::dead_skipped}, {"audit_dead", &Workspace::audit_dead}, {"head_ub", &Workspace::head_ub},
-        {"rot_hi", &Workspace::rot_hi}, {"rot_lo", &Workspace::rot_lo}};
+        {"rot_hl", &Workspace::rot_hl}};
+    DeviceGuard g(ix->device);
+    if (const int plane = hl_plane_of(name, "rot_hi", "rot_lo"); plane >= 0) { // logical view: whole rows of [D] u16
+        const size_t row = (size_t)ix->D * 2;
+        if (!w->rot_hl.p || bytes % row || bytes * 2 > w->rot_hl.cap) return fail(RBQ_INVALID_CONFIG, "unknown buffer or size");
+        return copy_hl_plane(w->rot_hl.p, bytes / row, ix->D, plane, dst);
+    }
     DevBuf* b = nullptr;
     for (const auto& kb : kBufs) if (!std::strcmp(name, kb.first)) b = &(w->*kb.second);
     if (!b || !b->p || bytes > b->cap) return fail(RBQ_INVALID_CONFIG, "unknown buffer or size");
-    DeviceGuard g(ix->device);
     HIP_TRY(hipMemcpy(dst, b->p, bytes, hipMemcpyDeviceToHost));
     return RBQ_OK;
     RBQ_GUARD_END
@@ -762,8 +780,13 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
     else if (!std::strcmp(name, "centroids")) { p = ix->centroids.p; have = ix->n_lists * ix->D * 4; }
     else if (!std::strcmp(name, "list_gb0")) { p = ix->list_gb0.p; have = ix->n_lists * 4; }
     else if (!std::strcmp(name, "list_n")) { p = ix->list_n.p; have = ix->n_lists * 4; }
-    else if (!std::strcmp(name, "cent_hi")) { p = ix->cent_hi.p; have = ix->n_lists * ix->D * 2; }
-    else if (!std::strcmp(name, "cent_lo")) { p = ix->cent_lo.p; have = ix->n_lists * ix->D * 2; }
+    else if (!std::strcmp(name, "cent_hl")) { p = ix->cent_hl.p; have = ix->n_lists * ix->D * 4; }
+    else if (const int plane = hl_plane_of(name, "cent_hi", "cent_lo"); plane >= 0) { // logical view of "cent_hl"
+        if (!ix->cent_hl.p || bytes != ix->n_lists * ix->D * 2)
+            return fail(RBQ_INVALID_CONFIG, "unknown array or size (have " + std::to_string(ix->n_lists * ix->D * 2) + " bytes)");
+        DeviceGuard g(ix->device);
+        return copy_hl_plane(ix->cent_hl.p, ix->n_lists, ix->D, plane, dst);
+    }
     else if (!std::strcmp(name, "cnorm2")) { p = ix->cnorm2.p; have = ix->n_lists * 4; }
     else if (!std::strcmp(name, "delta") || !std::strcmp(name, "vl")) { // (first replica only)
         ix = h->reps[0];

@@ -256,8 +256,7 @@ int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uin
     if ((rc = w->ms_sl.ensure(n * ((size_t)(gemm ? kMsCap : 0) + 2) * 4))) return rc; // sl [n][kMsCap] | sl_n [n] | nx [n]
     if (gemm) {
         if ((rc = w->scores.ensure(np * (size_t)k * 4))) return rc;
-        if ((rc = w->rot_hi.ensure(np * (size_t)Dp * 2))) return rc;
-        if ((rc = w->rot_lo.ensure(np * (size_t)Dp * 2))) return rc;
+        if ((rc = w->rot_hl.ensure(np * (size_t)Dp * 4))) return rc; // (here as two planes [np][Dp]: k_km_split's)
     }
     const uint32_t knp2 = mstg_select_knp2(k);
     if (knp2 && (rc = w->key_window.ensure(n * (size_t)knp2 * 8))) return rc;
@@ -269,7 +268,7 @@ int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uin
         p.cent = (const float*)ix->centroids.p;
         p.cent_hi = (const uint16_t*)ix->ms_hi.p; p.cent_lo = (const uint16_t*)ix->ms_lo.p; p.nc = (const float*)ix->ms_nc.p;
         p.ncmax_bits = (const uint32_t*)ix->ms_nc.p + k; p.cent_bad = ix->ms_bad;
-        p.q_hi = (uint16_t*)w->rot_hi.p; p.q_lo = (uint16_t*)w->rot_lo.p;
+        p.q_hi = (uint16_t*)w->rot_hl.p; p.q_lo = p.q_hi + np * (size_t)Dp;
         p.sl = (uint32_t*)w->ms_sl.p; p.sl_n = p.sl + n * (size_t)(gemm ? kMsCap : 0); p.nx = (float*)(p.sl_n + n);
         p.dots = (float*)w->scores.p; p.keys_g = knp2 ? (unsigned long long*)w->key_window.p : nullptr;
         p.fallbacks = c.d_fallbacks; p.out_lists = d_lists; p.out_counts = d_lcnt;

@@ -171,8 +171,8 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
     if ((rc = w->dead_skipped.ensure(nq * 16))) return rc;
     const bool split_rank = !ix->opt.exact_rank && !ix->opt.f32_rank && D % 64 == 0; // k_rank_bf16_db (else k_rank_mfma)
     if (split_rank) {
-        if ((rc = w->rot_hi.ensure(nq * D * 2))) return rc;
-        if ((rc = w->rot_lo.ensure(nq * D * 2))) return rc;
+        if ((rc = w->rot_hl.ensure(nq * D * 4))) return rc;
+        if (ix->opt.rank_planar && (rc = w->rank_planes.ensure((nq + nlist) * (size_t)D * 4))) return rc;
     }
     unsigned long long* prof = (ix->profiling && ix->opt.profile_counters) ? (unsigned long long*)ix->prof.p : nullptr;
     const uint32_t smask = ix->opt.stage_mask;
@@ -202,7 +202,7 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
     } else if (smask & 1u) {
         ProfScope ps(ix, 0, stream);
         PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq);
-        p.rot_hi = split_rank ? (uint16_t*)w->rot_hi.p : nullptr; p.rot_lo = split_rank ? (uint16_t*)w->rot_lo.p : nullptr;
+        p.rot_hl = split_rank ? (uint16_t*)w->rot_hl.p : nullptr;
         p.wg_prep = ix->opt.wg_prep;
         // batches a caller waits for (a few hundred queries: the chip is not full): a workgroup per query — the serial sums on one
         // wave while the others build the LUT (latency.hpp, preparation only); full batches keep one wave per query (k_prep_wave)
@@ -216,8 +216,8 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
         }
     }
     RankParams rp;
-    rp.metric = ix->metric; rp.rot = (const float*)w->rot.p; rp.rot_hi = (const uint16_t*)w->rot_hi.p; rp.rot_lo = (const uint16_t*)w->rot_lo.p;
-    rp.cent = (const float*)ix->centroids.p; rp.cent_hi = (const uint16_t*)ix->cent_hi.p; rp.cent_lo = (const uint16_t*)ix->cent_lo.p;
+    rp.metric = ix->metric; rp.rot = (const float*)w->rot.p; rp.rot_hi = (const uint16_t*)w->rot_hl.p; rp.rot_lo = nullptr; rp.rot_hl = true;
+    rp.cent = (const float*)ix->centroids.p; rp.cent_hi = (const uint16_t*)ix->cent_hl.p; rp.cent_lo = nullptr; rp.cent_hl = true;
     rp.consts = (const QueryConsts*)w->consts.p; rp.cnorm2 = (const float*)ix->cnorm2.p; rp.nq = (uint32_t)nq; rp.nlist = nlist; rp.D = D;
     rp.scores = (float*)w->scores.p; rp.split = split_rank; rp.ksplit = ksplit;
     rp.big = (uint64_t)((nlist + 127) / 128) * ((nq + 127) / 128) >= 192; // enough 128x128 tiles to fill the chip
@@ -270,6 +270,14 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
         if (smask & 2u) { ProfScope ps(ix, 1, stream); HIP_TRY(launch_rank_exact(rp, stream)); }
         if (smask & 4u) { ProfScope ps(ix, 2, stream); HIP_TRY(launch_select_exact(sp, ix->device, stream, kw)); }
     } else {
+        if ((smask & 2u) && !lat_front && split_rank && ix->opt.rank_planar && !stage_probes()) { // TEST ONLY: the same GEMM on planar copies of its operands
+            uint16_t* pl = (uint16_t*)w->rank_planes.p; // rot hi | rot lo | cent hi | cent lo
+            const size_t nr = (size_t)nq * D, nc = (size_t)nlist * D;
+            HIP_TRY(launch_hl_planes((const uint16_t*)w->rot_hl.p, nq, D, pl, pl + nr, stream));
+            HIP_TRY(launch_hl_planes((const uint16_t*)ix->cent_hl.p, nlist, D, pl + 2 * nr, pl + 2 * nr + nc, stream));
+            rp.rot_hi = pl; rp.rot_lo = pl + nr; rp.rot_hl = false;
+            rp.cent_hi = pl + 2 * nr; rp.cent_lo = pl + 2 * nr + nc; rp.cent_hl = false;
+        }
         if ((smask & 2u) && !lat_front) { ProfScope ps(ix, 1, stream); HIP_TRY(launch_rank_gemm(rp, ix->device, stream)); } // approximate scores: one MFMA GEMM
         if (smask & 4u) { ProfScope ps(ix, 2, stream); HIP_TRY(launch_select_mfma(sp, ix->device, stream)); }         // shortlist + exact canonical scores + exact select
     }

@@ -107,9 +107,14 @@ hipError_t launch_spread_f32(const float* src, const uint64_t* block_dense0, con
     hipLaunchKernelGGL(k_spread<float>, dim3((nb + 7) / 8), dim3(256), 0, s, src, block_dense0, block_nv, nb, fill, dst);
     return hipGetLastError();
 }
-hipError_t launch_centroid_arrays(const float* cent, uint32_t nlist, uint32_t D, float* cnorm2, uint16_t* hi, uint16_t* lo,
-                                  hipStream_t s) {
-    hipLaunchKernelGGL(k_centroid_arrays, dim3((nlist + 3) / 4), dim3(256), 0, s, cent, nlist, D, cnorm2, hi, lo);
+hipError_t launch_centroid_arrays(const float* cent, uint32_t nlist, uint32_t D, float* cnorm2, uint16_t* hl, hipStream_t s) {
+    hipLaunchKernelGGL(k_centroid_arrays, dim3((nlist + 3) / 4), dim3(256), 0, s, cent, nlist, D, cnorm2, hl);
+    return hipGetLastError();
+}
+
+hipError_t launch_hl_planes(const uint16_t* hl, uint64_t rows, uint32_t D, uint16_t* hi, uint16_t* lo, hipStream_t s) {
+    if (!rows) return hipSuccess;
+    hipLaunchKernelGGL(k_hl_planes, dim3((unsigned)((rows * D + 255) / 256)), dim3(256), 0, s, hl, rows, D, hi, lo);
     return hipGetLastError();
 }
 hipError_t launch_rerank(const float* queries, uint32_t nq, uint32_t dim, const float* raw, uint64_t n_raw, int metric,

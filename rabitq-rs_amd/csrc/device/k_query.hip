@@ -24,7 +24,7 @@ hipError_t launch_prep(const PrepParams& p, int device, hipStream_t s) {
         hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_prep), lds, device);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_prep, dim3(p.nq), dim3(kThreads), lds, s, p.queries, p.dim, p.D, p.Dc, p.rotator, p.rot_blob, p.trunc,
-                           p.fac, p.ex_bits, p.rot, p.lut, p.consts, p.rot_hi, p.rot_lo);
+                           p.fac, p.ex_bits, p.rot, p.lut, p.consts, p.rot_hl);
     } else { // FHT-Kac / identity: one wave per query
         static LdsAttrCache attr;
         const uint32_t qpw = kThreads / 64;
@@ -33,7 +33,7 @@ hipError_t launch_prep(const PrepParams& p, int device, hipStream_t s) {
         hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_prep_wave), lds, device); // 66.5 KB at D = 2048
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_prep_wave, dim3((p.nq + qpw - 1) / qpw), dim3(kThreads), lds, s, p.queries, p.nq, p.dim, p.D, p.Dc,
-                           p.rotator, p.rot_blob, p.trunc, p.fac, p.ex_bits, p.rot, p.lut, p.consts, p.rot_hi, p.rot_lo);
+                           p.rotator, p.rot_blob, p.trunc, p.fac, p.ex_bits, p.rot, p.lut, p.consts, p.rot_hl);
     }
     return hipGetLastError();
 }
@@ -45,7 +45,7 @@ hipError_t launch_lat_front(const PrepParams& p, const RankParams& r, int device
     P.queries = p.queries; P.nq = p.nq; P.dim = p.dim; P.D = p.D; P.Dc = p.Dc; P.rotator = p.rotator; P.rot_blob = p.rot_blob;
     P.trunc = p.trunc; P.fac = p.fac; P.ex_bits = p.ex_bits; P.rot = p.rot; P.lut = p.lut; P.consts = p.consts;
     P.cent = r.cent; P.nlist = r.nlist; P.metric = r.metric; P.scores = r.scores;
-    P.rot_hi = p.rot_hi; P.rot_lo = p.rot_lo; P.scorers = (r.scores && !r.ksplit) ? (r.nlist + kLatLists - 1) / kLatLists : 0u;
+    P.rot_hl = p.rot_hl; P.scorers = (r.scores && !r.ksplit) ? (r.nlist + kLatLists - 1) / kLatLists : 0u;
     P.zero_scores = r.ksplit > 1 ? r.scores : nullptr; // (split-K ranking GEMM behind this preparation: its parts are added to a zeroed row)
     const dim3 grid(lat_front_grid(P.scorers, p.nq));
     const size_t lds = (size_t)p.D * 4 * 2 + p.D / 2;
@@ -74,8 +74,15 @@ hipError_t launch_rank_split(const RankParams& p, dim3 grid, int device, hipStre
     if (probe_stage(1, reinterpret_cast<const void*>(&k_rank_bf16_db<M, TM, TN, WM, WN>), grid, 64 * WM * WN, lds)) return hipSuccess;
     hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_rank_bf16_db<M, TM, TN, WM, WN>), lds, device);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_rank_bf16_db<M, TM, TN, WM, WN>), grid, dim3(64 * WM * WN), lds, s, p.rot_hi, p.rot_lo, p.cent_hi, p.cent_lo,
-                       p.consts, p.cnorm2, p.nq, p.nlist, p.D, p.scores);
+    // operands: planar (two planes, rows of 2 D bytes, slabs of 64) or interleaved (one image at *_hi: the lo plane 64 bytes behind the hi
+    // plane, rows of 4 D bytes, slabs of 128)
+    const unsigned char* ah = reinterpret_cast<const unsigned char*>(p.rot_hi);
+    const unsigned char* al = p.rot_hl ? ah + 64 : reinterpret_cast<const unsigned char*>(p.rot_lo);
+    const unsigned char* bh = reinterpret_cast<const unsigned char*>(p.cent_hi);
+    const unsigned char* bl = p.cent_hl ? bh + 64 : reinterpret_cast<const unsigned char*>(p.cent_lo);
+    hipLaunchKernelGGL((k_rank_bf16_db<M, TM, TN, WM, WN>), grid, dim3(64 * WM * WN), lds, s, ah, al, p.D * (p.rot_hl ? 4u : 2u),
+                       p.rot_hl ? 128u : 64u, bh, bl, p.D * (p.cent_hl ? 4u : 2u), p.cent_hl ? 128u : 64u, p.consts, p.cnorm2, p.nq, p.nlist,
+                       p.D, p.scores);
     return hipGetLastError();
 }
 template <int M, int TW>

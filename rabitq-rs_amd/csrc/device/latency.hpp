@@ -37,7 +37,7 @@ struct LatFrontParams {
     uint32_t nlist;
     int metric;
     float* scores;        // [nq][nlist] exact canonical scores (L2: squared distance; IP: dot)
-    uint16_t *rot_hi, *rot_lo; // null, or the split-bf16 image of the rotated query (the ranking GEMM's operand: `scorers` = 0)
+    uint16_t* rot_hl;     // null, or the split-bf16 image of the rotated query, hi | lo per K slab (the ranking GEMM's operand: `scorers` = 0)
     float* zero_scores;   // null, or the score rows [nq][nlist] to clear (a split-K ranking GEMM adds its parts to them)
     uint32_t scorers;     // G = ceil(nlist / 32) scoring workgroups per query, or 0: preparation only, the ranking GEMM follows (medium
                           // batches: a workgroup per query finishes a query's preparation in ~2/3 of the time one wave of k_prep_wave needs)
@@ -150,11 +150,11 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
         const float v = x[i];
         x2[i] = v * v;
         P.rot[(size_t)q * D + i] = v;
-        if (P.rot_hi) { // split-bf16 image for k_rank_bf16_db
+        if (P.rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
             uint16_t h, l;
             bf16_split(v, h, l);
-            P.rot_hi[(size_t)q * D + i] = h;
-            P.rot_lo[(size_t)q * D + i] = l;
+            P.rot_hl[(size_t)q * 2 * D + hl_offset(i, 0, D)] = h;
+            P.rot_hl[(size_t)q * 2 * D + hl_offset(i, 1, D)] = l;
         }
     }
     if (P.zero_scores) { // (the row a split-K ranking GEMM adds its parts to)

@@ -58,7 +58,7 @@ struct PrepParams {
     float* rot;          // [nq][D]
     uint8_t* lut;        // [nq][4Dc]
     QueryConsts* consts; // [nq]
-    uint16_t *rot_hi, *rot_lo; // split-bf16 image or null
+    uint16_t* rot_hl;    // split-bf16 image [nq][2 D] (hi | lo per K slab, hl_layout.hpp) or null
     bool wg_prep;        // one workgroup per query (always for the matrix rotator)
 };
 hipError_t launch_prep(const PrepParams& p, int device, hipStream_t s);
@@ -69,6 +69,9 @@ struct RankParams {
     const uint16_t *rot_hi, *rot_lo;
     const float* cent;
     const uint16_t *cent_hi, *cent_lo;
+    // the split-bf16 operands: two planes [rows][D] each, or (rot_hl / cent_hl) ONE image [rows][2 D] at *_hi with hi | lo interleaved
+    // per K slab (hl_layout.hpp), *_lo unused
+    bool rot_hl = false, cent_hl = false;
     const QueryConsts* consts;
     const float* cnorm2;
     uint32_t nq, nlist, D;
@@ -213,8 +216,9 @@ hipError_t launch_spread_u64(const uint64_t* src, const uint64_t* block_dense0, 
 hipError_t launch_spread_f32(const float* src, const uint64_t* block_dense0, const uint32_t* block_nv, uint32_t nb, float fill,
                              float* dst, hipStream_t s);
 // centroid-derived arrays: squared norms (f64 accumulate, as the host did) and the split-bf16 image
-hipError_t launch_centroid_arrays(const float* cent, uint32_t nlist, uint32_t D, float* cnorm2, uint16_t* hi, uint16_t* lo,
-                                  hipStream_t s);
+hipError_t launch_centroid_arrays(const float* cent, uint32_t nlist, uint32_t D, float* cnorm2, uint16_t* hl, hipStream_t s);
+// the planar hi / lo planes [rows][D] of an interleaved split-bf16 image [rows][2 D] (hl_layout.hpp): debug option rank_planar
+hipError_t launch_hl_planes(const uint16_t* hl, uint64_t rows, uint32_t D, uint16_t* hi, uint16_t* lo, hipStream_t s);
 // exact re-scoring of the returned ids against caller-supplied raw vectors (optional rerank, default off)
 hipError_t launch_rerank(const float* queries, uint32_t nq, uint32_t dim, const float* raw, uint64_t n_raw, int metric,
                          uint32_t top_k, uint64_t* ids, float* scores, const uint32_t* counts, hipStream_t s);

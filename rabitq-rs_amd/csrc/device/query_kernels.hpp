@@ -24,7 +24,7 @@ __global__ __launch_bounds__(kThreads) void k_prep(const float* __restrict__ que
                                                    uint32_t trunc, float fac, uint32_t ex_bits,
                                                    float* __restrict__ rot_out, uint8_t* __restrict__ lut_out,
                                                    QueryConsts* __restrict__ consts,
-                                                   uint16_t* __restrict__ rot_hi, uint16_t* __restrict__ rot_lo) {
+                                                   uint16_t* __restrict__ rot_hl) {
     extern __shared__ __align__(16) float sm[];
     float* x = sm;         // [D]
     float* y = sm + D;     // [D] (matrix rotator input)
@@ -41,11 +41,11 @@ __global__ __launch_bounds__(kThreads) void k_prep(const float* __restrict__ que
 
     for (uint32_t i = tid; i < D; i += kThreads) {
         rot_out[(size_t)q * D + i] = x[i];
-        if (rot_hi) { // split-bf16 image for k_rank_bf16_db
+        if (rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
             uint16_t h, l;
             bf16_split(x[i], h, l);
-            rot_hi[(size_t)q * D + i] = h;
-            rot_lo[(size_t)q * D + i] = l;
+            rot_hl[(size_t)q * 2 * D + hl_offset(i, 0, D)] = h;
+            rot_hl[(size_t)q * 2 * D + hl_offset(i, 1, D)] = l;
         }
     }
 
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict_
                                                         uint32_t trunc, float fac, uint32_t ex_bits,
                                                         float* __restrict__ rot_out, uint8_t* __restrict__ lut_out,
                                                         QueryConsts* __restrict__ consts,
-                                                        uint16_t* __restrict__ rot_hi, uint16_t* __restrict__ rot_lo) {
+                                                        uint16_t* __restrict__ rot_hl) {
     extern __shared__ __align__(16) float sm[];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t q = blockIdx.x * (kThreads / 64) + wave;
@@ -399,11 +399,11 @@ __global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict_
         sp += fmaxf(v, 0.0f);
         sn += fminf(v, 0.0f);
         rot_out[(size_t)q * D + i] = v;
-        if (rot_hi) { // split-bf16 image for k_rank_bf16_db
+        if (rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
             uint16_t h, l;
             bf16_split(v, h, l);
-            rot_hi[(size_t)q * D + i] = h;
-            rot_lo[(size_t)q * D + i] = l;
+            rot_hl[(size_t)q * 2 * D + hl_offset(i, 0, D)] = h;
+            rot_hl[(size_t)q * 2 * D + hl_offset(i, 1, D)] = l;
         }
     }
     group_sync<64>();

@@ -125,9 +125,22 @@ __device__ __forceinline__ f32x16 mfma_x8(bf16x8 a, bf16x8 b, f32x16 c) { // one
 // barriers.
 // Rows are padded to 80 bytes (16 lanes of a ds_read_b128 group: 16 distinct 4-bank sets).  D % 32 == 0.
 // dynamic LDS: 2 x { Ah | Al [BM][80 B] | Bh | Bl [BN][80 B] }
+// OPERANDS.  Each of A (queries) and B (centroids) comes as the bases of its hi and lo planes, a row stride and a K-slab stride, in bytes:
+//   planar      two arrays [rows][D] bf16: row stride 2 D, slab stride 64.  Four consecutive lanes fetch the 64 bytes of one row and
+//               plane, so a wave-level 16-byte load touches 16 lines of 128 bytes and uses half of each; the other half is the NEXT
+//               slab's, by which time the workgroup has pulled a whole slab of both operands through the vector L1.
+//   interleaved ONE array [rows][2 D] (hl_layout.hpp: slab s of a row = 128 bytes, hi | lo): the lo base is 64 bytes behind the
+//               hi base, row stride 4 D, slab stride 128 — what selects this lane map.  A wave-level load then covers 8 rows x 128
+//               bytes, whole lines: lanes 0..31 the hi halves of rows r..r+7 (4 lanes per row), lanes 32..63 their lo halves, and a
+//               thread's second load of a pair is 8 rows further on instead of in the other plane.  Within a plane the rows go
+//               0, 4, 1, 5, 2, 6, 3, 7: a ds_write_b128 is served in groups of 8 lanes over 32 banks, and with rows of 80 bytes (20
+//               banks) rows r and r + 4 are 16 banks apart — no conflict, where the planar map's r and r + 1 share four banks.
+// Same number of loads per thread either way, and the LDS images — hence fragments, MFMA order and scores — are byte for byte the same.
 template <int METRIC, int TM, int TN, int WM, int WN>
-__global__ __launch_bounds__(64 * WM * WN) void k_rank_bf16_db(const uint16_t* __restrict__ rot_hi, const uint16_t* __restrict__ rot_lo,
-                                                      const uint16_t* __restrict__ cent_hi, const uint16_t* __restrict__ cent_lo,
+__global__ __launch_bounds__(64 * WM * WN) void k_rank_bf16_db(const unsigned char* __restrict__ a_hi, const unsigned char* __restrict__ a_lo,
+                                                      uint32_t a_row, uint32_t a_slab,
+                                                      const unsigned char* __restrict__ b_hi, const unsigned char* __restrict__ b_lo,
+                                                      uint32_t b_row, uint32_t b_slab,
                                                       const QueryConsts* __restrict__ consts,
                                                       const float* __restrict__ cnorm2, uint32_t nq, uint32_t nlist,
                                                       uint32_t D, float* __restrict__ scores) {
@@ -145,26 +158,51 @@ __global__ __launch_bounds__(64 * WM * WN) void k_rank_bf16_db(const uint16_t* _
         for (int b = 0; b < TN; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+    static_assert(BM % 16 == 0 && BN % 16 == 0, "the interleaved lane map takes 16 rows per wave-level pair of loads");
+    // pair i of a thread's loads: ga_h / ga_l (gb_h / gb_l) are its two addresses, soa (sob) the LDS offset of the first and soa + dla
+    // (sob + dlb) that of the second — planar: (row, hi) and (row, lo); interleaved: (row, plane) and (row + 8, plane)
     const unsigned char* ga_h[NLA];
     const unsigned char* ga_l[NLA];
     const unsigned char* gb_h[NLB];
     const unsigned char* gb_l[NLB];
     uint32_t soa[NLA], sob[NLB];
+    const bool a_il = a_slab == 4u * BK, b_il = b_slab == 4u * BK; // (uniform)
+    const uint32_t dla = a_il ? 8u * LDB : (uint32_t)BM * LDB, dlb = b_il ? 8u * LDB : (uint32_t)BN * LDB;
 #pragma unroll
     for (int i = 0; i < NLA; ++i) {
-        const uint32_t idx = tid + (uint32_t)NT * i, row = idx / SEG, seg = idx % SEG;
-        const uint32_t ra = q0 + row < nq ? q0 + row : nq - 1u;
-        ga_h[i] = reinterpret_cast<const unsigned char*>(rot_hi) + (size_t)ra * D * 2 + seg * 16;
-        ga_l[i] = reinterpret_cast<const unsigned char*>(rot_lo) + (size_t)ra * D * 2 + seg * 16;
-        soa[i] = row * LDB + seg * 16;
+        const uint32_t idx = tid + (uint32_t)NT * i;
+        if (a_il) {
+            const uint32_t q4 = (idx & 31u) >> 2, row = (idx >> 6) * 16u + ((q4 & 1u) << 2 | q4 >> 1), plane = (idx >> 5) & 1u, seg = idx & 3u;
+            const uint32_t r0 = q0 + row < nq ? q0 + row : nq - 1u, r1 = q0 + row + 8u < nq ? q0 + row + 8u : nq - 1u;
+            const unsigned char* pb = (plane ? a_lo : a_hi) + seg * 16;
+            ga_h[i] = pb + (size_t)r0 * a_row;
+            ga_l[i] = pb + (size_t)r1 * a_row;
+            soa[i] = plane * BM * LDB + row * LDB + seg * 16;
+        } else {
+            const uint32_t row = idx / SEG, seg = idx % SEG;
+            const uint32_t ra = q0 + row < nq ? q0 + row : nq - 1u;
+            ga_h[i] = a_hi + (size_t)ra * a_row + seg * 16;
+            ga_l[i] = a_lo + (size_t)ra * a_row + seg * 16;
+            soa[i] = row * LDB + seg * 16;
+        }
     }
 #pragma unroll
     for (int i = 0; i < NLB; ++i) {
-        const uint32_t idx = tid + (uint32_t)NT * i, row = idx / SEG, seg = idx % SEG;
-        const uint32_t rb = c0 + row < nlist ? c0 + row : nlist - 1u;
-        gb_h[i] = reinterpret_cast<const unsigned char*>(cent_hi) + (size_t)rb * D * 2 + seg * 16;
-        gb_l[i] = reinterpret_cast<const unsigned char*>(cent_lo) + (size_t)rb * D * 2 + seg * 16;
-        sob[i] = 2 * BM * LDB + row * LDB + seg * 16;
+        const uint32_t idx = tid + (uint32_t)NT * i;
+        if (b_il) {
+            const uint32_t q4 = (idx & 31u) >> 2, row = (idx >> 6) * 16u + ((q4 & 1u) << 2 | q4 >> 1), plane = (idx >> 5) & 1u, seg = idx & 3u;
+            const uint32_t r0 = c0 + row < nlist ? c0 + row : nlist - 1u, r1 = c0 + row + 8u < nlist ? c0 + row + 8u : nlist - 1u;
+            const unsigned char* pb = (plane ? b_lo : b_hi) + seg * 16;
+            gb_h[i] = pb + (size_t)r0 * b_row;
+            gb_l[i] = pb + (size_t)r1 * b_row;
+            sob[i] = 2 * BM * LDB + plane * BN * LDB + row * LDB + seg * 16;
+        } else {
+            const uint32_t row = idx / SEG, seg = idx % SEG;
+            const uint32_t rb = c0 + row < nlist ? c0 + row : nlist - 1u;
+            gb_h[i] = b_hi + (size_t)rb * b_row + seg * 16;
+            gb_l[i] = b_lo + (size_t)rb * b_row + seg * 16;
+            sob[i] = 2 * BM * LDB + row * LDB + seg * 16;
+        }
     }
     u32x4 pah[NLA], pal[NLA], pbh[NLB], pbl[NLB];
     // SPLIT-K (gridDim.z > 1; small batches, whose few tiles leave most of the chip idle while each walks all D / 32 slabs): workgroup z
@@ -175,22 +213,22 @@ __global__ __launch_bounds__(64 * WM * WN) void k_rank_bf16_db(const uint16_t* _
     if (s_first >= nslab_all) return; // (whole workgroup)
     const uint32_t nslab = nslab_all - s_first < per_z ? nslab_all - s_first : per_z;
     {
-        const size_t k_first = (size_t)s_first * BK * 2;
+        const size_t ka_first = (size_t)s_first * a_slab, kb_first = (size_t)s_first * b_slab;
 #pragma unroll
-        for (int i = 0; i < NLA; ++i) { ga_h[i] += k_first; ga_l[i] += k_first; }
+        for (int i = 0; i < NLA; ++i) { ga_h[i] += ka_first; ga_l[i] += ka_first; }
 #pragma unroll
-        for (int i = 0; i < NLB; ++i) { gb_h[i] += k_first; gb_l[i] += k_first; }
+        for (int i = 0; i < NLB; ++i) { gb_h[i] += kb_first; gb_l[i] += kb_first; }
     }
 #define RBQ_RANK_FETCH(S)                                                                                              \
     do {                                                                                                               \
-        const size_t ko = (size_t)(S) * BK * 2;                                                                        \
+        const size_t koa = (size_t)(S) * a_slab, kob = (size_t)(S) * b_slab;                                           \
         _Pragma("unroll") for (int i = 0; i < NLA; ++i) {                                                              \
-            pah[i] = *reinterpret_cast<const u32x4*>(ga_h[i] + ko);                                                    \
-            pal[i] = *reinterpret_cast<const u32x4*>(ga_l[i] + ko);                                                    \
+            pah[i] = *reinterpret_cast<const u32x4*>(ga_h[i] + koa);                                                   \
+            pal[i] = *reinterpret_cast<const u32x4*>(ga_l[i] + koa);                                                   \
         }                                                                                                              \
         _Pragma("unroll") for (int i = 0; i < NLB; ++i) {                                                              \
-            pbh[i] = *reinterpret_cast<const u32x4*>(gb_h[i] + ko);                                                    \
-            pbl[i] = *reinterpret_cast<const u32x4*>(gb_l[i] + ko);                                                    \
+            pbh[i] = *reinterpret_cast<const u32x4*>(gb_h[i] + kob);                                                   \
+            pbl[i] = *reinterpret_cast<const u32x4*>(gb_l[i] + kob);                                                   \
         }                                                                                                              \
     } while (0)
 #define RBQ_RANK_STORE(B)                                                                                              \
@@ -198,11 +236,11 @@ __global__ __launch_bounds__(64 * WM * WN) void k_rank_bf16_db(const uint16_t* _
         unsigned char* base = smraw + (B) * BUF;                                                                       \
         _Pragma("unroll") for (int i = 0; i < NLA; ++i) {                                                              \
             *reinterpret_cast<u32x4*>(base + soa[i]) = pah[i];                                                         \
-            *reinterpret_cast<u32x4*>(base + BM * LDB + soa[i]) = pal[i];                                              \
+            *reinterpret_cast<u32x4*>(base + dla + soa[i]) = pal[i];                                                   \
         }                                                                                                              \
         _Pragma("unroll") for (int i = 0; i < NLB; ++i) {                                                              \
             *reinterpret_cast<u32x4*>(base + sob[i]) = pbh[i];                                                         \
-            *reinterpret_cast<u32x4*>(base + BN * LDB + sob[i]) = pbl[i];                                              \
+            *reinterpret_cast<u32x4*>(base + dlb + sob[i]) = pbl[i];                                                   \
         }                                                                                                              \
     } while (0)
     // fragment sets of the two 16-wide K steps of a slab; A/B operand of the MFMA: lane l holds row (l & 31),

@@ -99,9 +99,9 @@ __global__ __launch_bounds__(256) void k_spread(const T* __restrict__ src, const
     dst[slot] = v < block_nv[b] ? src[block_dense0[b] + v] : fill;
 }
 
-// squared norms (f64 accumulate) and split-bf16 image of the rotated centroids
+// squared norms (f64 accumulate) and split-bf16 image (hi | lo per K slab: hl_offset) of the rotated centroids
 __global__ __launch_bounds__(256) void k_centroid_arrays(const float* __restrict__ cent, uint32_t nlist, uint32_t D,
-                                                         float* __restrict__ cnorm2, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo) {
+                                                         float* __restrict__ cnorm2, uint16_t* __restrict__ hl) {
     const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (c >= nlist) return;
     const float* row = cent + (size_t)c * D;
@@ -111,12 +111,23 @@ __global__ __launch_bounds__(256) void k_centroid_arrays(const float* __restrict
         a += (double)x * (double)x;
         uint16_t h, l;
         bf16_split(x, h, l);
-        hi[(size_t)c * D + i] = h;
-        lo[(size_t)c * D + i] = l;
+        hl[(size_t)c * 2 * D + hl_offset(i, 0, D)] = h;
+        hl[(size_t)c * 2 * D + hl_offset(i, 1, D)] = l;
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) a += __shfl_xor(a, d, 64);
     if (lane == 0) cnorm2[c] = (float)a;
+}
+
+// hi / lo planes of an interleaved split-bf16 image (one thread per element)
+__global__ __launch_bounds__(256) void k_hl_planes(const uint16_t* __restrict__ hl, uint64_t rows, uint32_t D, uint16_t* __restrict__ hi,
+                                                   uint16_t* __restrict__ lo) {
+    const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (x >= rows * D) return;
+    const uint64_t r = x / D;
+    const uint32_t i = (uint32_t)(x - r * D);
+    hi[x] = hl[r * 2 * D + hl_offset(i, 0, D)];
+    lo[x] = hl[r * 2 * D + hl_offset(i, 1, D)];
 }
 
 // ---- streamed build: slots of one pushed chunk -------------------------------------------------------------------

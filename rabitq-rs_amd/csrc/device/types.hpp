@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "hl_layout.hpp"
+
 namespace rbq {
 
 constexpr int kThreads = 256;
@@ -84,6 +86,7 @@ __host__ __device__ inline void bf16_split(float x, uint16_t& hi, uint16_t& lo) 
     hi = bf16_rne(x);
     lo = bf16_rne(x - bf16_to_f32(hi));
 }
+// (the interleaved image of the two planes that the ranking GEMM reads: hl_layout.hpp, hl_offset)
 
 // ---- k_scan ---------------------------------------------------------------------------------------------------
 struct ScanParams {
