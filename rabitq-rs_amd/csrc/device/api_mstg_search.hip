@@ -106,20 +106,25 @@ int ms_fallback_counter(int dev, unsigned long long** out) {
     return RBQ_OK;
 }
 
+// the centroids as the list selection sees them: ms_nc holds nc [k] | ncmax bits | the non-finite flag (images: GEMM shapes only)
+CentView ms_view(const Replica* ix) {
+    const uint32_t k = (uint32_t)ix->n_lists;
+    return {k, ix->D, km_dp(ix->D), (float*)ix->ms_nc.p, (uint32_t*)ix->ms_nc.p + k, (uint16_t*)ix->ms_hi.p, (uint16_t*)ix->ms_lo.p};
+}
+
 // split-bf16 images and norms of the centroids, once per replica (the first search that takes the GEMM shortlist)
 int ms_prepare(Replica* ix) {
     std::lock_guard<std::mutex> lk(ix->mu);
     if (ix->ms_ready) return RBQ_OK;
-    const uint32_t k = (uint32_t)ix->n_lists, Dp = mstg_select_dp(ix->D);
+    const uint32_t k = (uint32_t)ix->n_lists, Dp = km_dp(ix->D);
     int rc;
     if ((rc = alloc_arr(ix->ms_hi, (size_t)k * Dp * 2))) return rc;
     if ((rc = alloc_arr(ix->ms_lo, (size_t)k * Dp * 2))) return rc;
-    if ((rc = alloc_arr(ix->ms_nc, (size_t)k * 4 + 8))) return rc; // nc [k] | ncmax bits | bad
-    uint32_t* aux = (uint32_t*)ix->ms_nc.p + k;
-    HIP_TRY(launch_mstg_centroid_prep((const float*)ix->centroids.p, k, ix->D, (float*)ix->ms_nc.p, aux, aux + 1, (uint16_t*)ix->ms_hi.p,
-                                      (uint16_t*)ix->ms_lo.p, nullptr));
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpy(&bad, aux + 1, 4, hipMemcpyDeviceToHost));
+    if ((rc = alloc_arr(ix->ms_nc, (size_t)k * 4 + 8))) return rc;
+    const CentView cv = ms_view(ix);
+    bool bad = false;
+    HIP_TRY(launch_split_centroids((const float*)ix->centroids.p, cv, nullptr));
+    HIP_TRY(nonfinite_sync((const float*)ix->centroids.p, (uint64_t)k * ix->D, cv.ncmax_bits + 1, nullptr, &bad));
     ix->ms_bad = bad;
     ix->ms_ready = true;
     return RBQ_OK;
@@ -156,7 +161,7 @@ MstgShape ms_shape(const Replica* ix, uint64_t nq, uint32_t top_k, uint32_t ef_s
                    sh.wl_stride * sizeof(StreamItem) + (uint64_t)top_k * 12 + 16;
     if (host) per += (uint64_t)ix->dim * 4;
     if (pool) per += (uint64_t)pool * 12 + 4;
-    if (mstg_select_gemm(k, ix->D)) per += 4 * k + 4ull * mstg_select_dp(ix->D) + 4ull * kMsCap + 8;
+    if (mstg_select_gemm(k, ix->D)) per += gemm_shortlist_row_bytes(k, km_dp(ix->D), kMsCap) + 4; // (+ the query's norm)
     else if (k > RBQ_MSTG_SHORTLIST) per += 4;
     per += 8ull * mstg_select_knp2(k);
     const uint64_t budget = ix->opt.mstg_search_budget ? ix->opt.mstg_search_budget : kMstgSearchBudget;
@@ -250,13 +255,13 @@ int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uin
         s_scores = (float*)(s_ids + n * (size_t)c.pool);
         s_counts = (uint32_t*)(s_scores + n * (size_t)c.pool);
     }
-    const uint32_t D = ix->D, k = (uint32_t)ix->n_lists, Dp = mstg_select_dp(D);
+    const uint32_t D = ix->D, k = (uint32_t)ix->n_lists, Dp = km_dp(D);
     const bool gemm = mstg_select_gemm(k, D);
     const uint64_t np = (n + 127) / 128 * 128; // (the GEMM's row tiles)
     if ((rc = w->ms_sl.ensure(n * ((size_t)(gemm ? kMsCap : 0) + 2) * 4))) return rc; // sl [n][kMsCap] | sl_n [n] | nx [n]
     if (gemm) {
         if ((rc = w->scores.ensure(np * (size_t)k * 4))) return rc;
-        if ((rc = w->rot_hl.ensure(np * (size_t)Dp * 4))) return rc; // (here as two planes [np][Dp]: k_km_split's)
+        if ((rc = w->rot_hl.ensure(np * (size_t)Dp * 4))) return rc; // (here as two planes [np][Dp]: launch_approx_dots')
     }
     const uint32_t knp2 = mstg_select_knp2(k);
     if (knp2 && (rc = w->key_window.ensure(n * (size_t)knp2 * 8))) return rc;
@@ -264,10 +269,8 @@ int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uin
     {
         ProfScope ps(ix, 1, stream);
         MstgSelectParams p{};
-        p.rot = (const float*)w->rot.p; p.nq = (uint32_t)n; p.D = D; p.k = k; p.ef_search = c.ef_search; p.pruning_epsilon = c.pruning_epsilon;
-        p.cent = (const float*)ix->centroids.p;
-        p.cent_hi = (const uint16_t*)ix->ms_hi.p; p.cent_lo = (const uint16_t*)ix->ms_lo.p; p.nc = (const float*)ix->ms_nc.p;
-        p.ncmax_bits = (const uint32_t*)ix->ms_nc.p + k; p.cent_bad = ix->ms_bad;
+        p.rot = (const float*)w->rot.p; p.nq = (uint32_t)n; p.ef_search = c.ef_search; p.pruning_epsilon = c.pruning_epsilon;
+        p.cent = (const float*)ix->centroids.p; p.cv = ms_view(ix); p.cent_bad = ix->ms_bad;
         p.q_hi = (uint16_t*)w->rot_hl.p; p.q_lo = p.q_hi + np * (size_t)Dp;
         p.sl = (uint32_t*)w->ms_sl.p; p.sl_n = p.sl + n * (size_t)(gemm ? kMsCap : 0); p.nx = (float*)(p.sl_n + n);
         p.dots = (float*)w->scores.p; p.keys_g = knp2 ? (unsigned long long*)w->key_window.p : nullptr;

@@ -9,7 +9,7 @@
 //                        chains, each the pinned sequential f32 dot in coordinate order, then (nx + nc) - 2 dot clamped at 0 and the
 //                        strict-< argmin as a min of (distance bits, cluster); the winning distance feeds the reseed candidates.
 //                        The centroid tile is staged per coordinate chunk, so it fits the LDS at every k x dim.
-//   k > 256:  KmGemmAssign (km_common.hpp): the GEMM shortlist of k_kmeans.hip
+//   k > 256:  KmGemmAssign (k_gemm_shortlist.hip): the GEMM shortlist of k-means
 //   update               stable sort of (cluster, row), k_km_bounds, k_km_candidates, k_hc_reseed, k_km_update: no host
 //                        synchronisation inside the Lloyd loop.  k_hc_reseed (one wavefront) gives the empty clusters in ascending
 //                        order the next candidate under (distance desc, row asc), then next() % rows from the xoshiro state in
@@ -240,17 +240,11 @@ int hcluster_device(const HClusterArgs& a, rbq_host::HcResult& out, std::string&
     const bool direct = k <= kHcDirectMaxK;
     hipStream_t s = 0;
     KmTemp t;
-    {   // finite input only, as for k-means
-        uint32_t* bad = nullptr;
-        uint32_t h_bad = 0;
-        KM_TRY(t.alloc(&bad, 1));
-        KM_TRY(hipMemsetAsync(bad, 0, 4, s));
-        hipLaunchKernelGGL(k_km_nonfinite, dim3((unsigned)std::min<uint64_t>(4096, grid_of(n * dim, 256))), dim3(256), 0, s, a.d_data,
-                           n * dim, bad);
-        KM_TRY(hipGetLastError());
-        KM_TRY(hipMemcpy(&h_bad, bad, 4, hipMemcpyDeviceToHost));
-        if (h_bad) { detail = "clustering input must be finite"; return RBQ_INVALID_CONFIG; }
-    }
+    uint32_t* flag = nullptr; // finite input only, as for k-means
+    bool bad = false;
+    KM_TRY(t.alloc(&flag, 1));
+    KM_TRY(nonfinite_sync(a.d_data, n * dim, flag, s, &bad));
+    if (bad) { detail = "clustering input must be finite"; return RBQ_INVALID_CONFIG; }
     const HcParams prm{a.max_size, k, a.niter, a.balance_weight};
     HcStats st;
     Rng rng(kHcSeed);
@@ -263,12 +257,13 @@ int hcluster_device(const HClusterArgs& a, rbq_host::HcResult& out, std::string&
     const uint64_t kp = k > UINT64_MAX / kHcPointsPerCentroid ? UINT64_MAX : k * kHcPointsPerCentroid;
     const uint64_t tmax = std::max(std::min(n, kp), k); // most training rows of any split (a split has more than k - 1 rows)
     uint32_t *members = nullptr, *mtmp = nullptr, *d_src = nullptr, *d_start = nullptr, *d_end = nullptr, *asg = nullptr, *fasg = nullptr,
-             *keys = nullptr, *iota = nullptr, *vals = nullptr, *ncmax = nullptr;
-    float *xs = nullptr, *xt = nullptr, *full_nx = nullptr, *nx_t = nullptr, *bestd = nullptr, *cent = nullptr, *nc = nullptr;
+             *keys = nullptr, *iota = nullptr, *vals = nullptr;
+    float *xs = nullptr, *xt = nullptr, *full_nx = nullptr, *nx_t = nullptr, *bestd = nullptr, *cent = nullptr;
     unsigned long long *cands = nullptr, *d_rng = nullptr, *d_arg = nullptr;
     void* sort_tmp = nullptr;
     size_t sort_bytes = 0;
-    KmGemmAssign ga;
+    KmGemmAssign ga;                                                    // k > 256
+    CentView dv{(uint32_t)k, dim, 0, nullptr, nullptr, nullptr, nullptr}; // k <= 256: the centroid norms of the direct path
     unsigned kbits = 1;
     while (kbits < 32 && (1ull << kbits) < k) ++kbits; // sort keys < k
     const uint64_t max_cand_chunks = tmax / kHcDecodeBlock + 1;
@@ -293,7 +288,7 @@ int hcluster_device(const HClusterArgs& a, rbq_host::HcResult& out, std::string&
         KM_TRY(t.alloc(&d_rng, 6));
         KM_TRY(t.alloc(&d_arg, 1));
         KM_TRY(hipMemsetAsync(d_rng, 0, 48, s));
-        if (direct) { KM_TRY(t.alloc(&nc, k)); KM_TRY(t.alloc(&ncmax, 1)); }
+        if (direct) { KM_TRY(t.alloc(&dv.nc, k)); KM_TRY(t.alloc(&dv.ncmax_bits, 1)); }
         else KM_TRY(ga.alloc(t, n, k, dim, a.device, s));
         KM_TRY(sort_pairs_u32(nullptr, &sort_bytes, fasg, keys, iota, vals, n, kbits, s));
         KM_TRY(t.alloc((unsigned char**)&sort_tmp, sort_bytes));
@@ -304,14 +299,9 @@ int hcluster_device(const HClusterArgs& a, rbq_host::HcResult& out, std::string&
     // assignment of rows [0, m) of xa (norms xn) to `cent`
     auto assign = [&](const float* xa, const float* xn, uint64_t m, uint32_t* o, float* bd) -> hipError_t {
         hipError_t e;
-        if (!direct) {
-            if ((e = ga.prep(cent, s))) return e;
-            return ga.run(xa, xn, m, cent, o, bd, s);
-        }
-        if ((e = hipMemsetAsync(ncmax, 0, 4, s))) return e;
-        hipLaunchKernelGGL(k_km_cnorms, dim3(grid_of(k, 256)), dim3(256), 0, s, cent, (uint32_t)k, dim, nc, ncmax);
-        if ((e = hipGetLastError())) return e;
-        hipLaunchKernelGGL(k_hc_assign_direct, dim3(grid_of(m, kDaRows)), dim3(256), 0, s, xa, (uint32_t)m, dim, xn, cent, nc, (uint32_t)k, o,
+        if (!direct) return ga.run(xa, xn, m, cent, o, bd, s);
+        if ((e = launch_centroid_norms(cent, dv, s))) return e;
+        hipLaunchKernelGGL(k_hc_assign_direct, dim3(grid_of(m, kDaRows)), dim3(256), 0, s, xa, (uint32_t)m, dim, xn, cent, dv.nc, (uint32_t)k, o,
                            bd);
         return hipGetLastError();
     };
@@ -368,8 +358,7 @@ int hcluster_device(const HClusterArgs& a, rbq_host::HcResult& out, std::string&
         hipLaunchKernelGGL(k_hc_gather, dim3((unsigned)std::min<uint64_t>(4096, grid_of(m * dim, 256))), dim3(256), 0, s, a.d_data, seg, m,
                            dim, xs);
         KM_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_km_norms, dim3(grid_of(m, 256)), dim3(256), 0, s, xs, m, dim, full_nx);
-        KM_TRY(hipGetLastError());
+        KM_TRY(launch_row_norms(xs, m, dim, full_nx, s));
         const uint64_t target = std::max(std::min(m, kp), k);
         const uint32_t rows = (uint32_t)target;
         const float *x = xs, *nx = full_nx;
@@ -384,8 +373,7 @@ int hcluster_device(const HClusterArgs& a, rbq_host::HcResult& out, std::string&
             hipLaunchKernelGGL(k_hc_gather, dim3((unsigned)std::min<uint64_t>(4096, grid_of(target * dim, 256))), dim3(256), 0, s, xs, d_src,
                                target, dim, xt);
             KM_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_km_norms, dim3(grid_of(rows, 256)), dim3(256), 0, s, xt, (uint64_t)rows, dim, nx_t);
-            KM_TRY(hipGetLastError());
+            KM_TRY(launch_row_norms(xt, rows, dim, nx_t, s));
             x = xt;
             nx = nx_t;
         }

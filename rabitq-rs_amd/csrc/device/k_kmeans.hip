@@ -1,9 +1,9 @@
 // k_kmeans.hip — Faiss-style k-means on the device: run_kmeans_with_config (reference src/kmeans.rs) in the pinned arithmetic of
 // the CPU restatement rbq_build_kmeans_faiss (csrc/host/rbq_build.cpp), which this unit reproduces bit for bit.  gfx950 only.
 //
-// Assignment of a chunk of rows (no N x k score matrix: R rows at a time, R x k approximate scores):
-//   k_km_split      the chunk's rows as split-bf16 hi / lo images, zero-padded to Dp = dim rounded up to 32
-//   k_rank_bf16_db  (rank_mfma.hpp, the ranking GEMM's inner-product form, launched through launch_rank_gemm) dA(x, c)
+// Assignment of a chunk of rows (KmGemmAssign, k_gemm_shortlist.hip; no N x k score matrix: R rows at a time, R x k approximate scores):
+//   launch_approx_dots  the chunk's rows as split-bf16 hi / lo images, zero-padded to Dp = dim rounded up to 32, then dA(x, c) by
+//                   the ranking GEMM's inner-product form (k_rank_bf16_db, rank_mfma.hpp)
 //   k_km_scan       per row: A = max(0, fmaf(-2, dA, nx + nc)), Amin, shortlist {c : A(c) <= Amin + 2 eps} in cluster order;
 //                   a shortlist over kShortlist entries (or a score far from finite) marks the row for the fallback
 //   k_km_exact      one wavefront per row: canonical distances of the shortlist, or of all k clusters for a marked row (the
@@ -34,8 +34,6 @@
 #include "../host/rbq_rng.h"
 
 namespace rbq {
-
-std::atomic<uint64_t> g_km_chunk_rows_cap{0}, g_km_assign_passes{0}; // launch.hpp
 
 // spherical: c *= 1 / sqrt(|c|^2) when |c|^2 > 0 (correctly rounded sqrt and division)
 __global__ __launch_bounds__(256) void k_km_normalize(float* __restrict__ cent, uint32_t k, uint32_t dim) {
@@ -95,17 +93,11 @@ int kmeans_device(const KMeansArgs& a, std::string& detail) {
     const uint32_t dim = a.dim;
     hipStream_t s = 0;
     KmTemp t;
-    {   // finite input only: the shortlist's error bound needs it (the crate does not check)
-        uint32_t* bad = nullptr;
-        uint32_t h_bad = 0;
-        KM_TRY(t.alloc(&bad, 1));
-        KM_TRY(hipMemsetAsync(bad, 0, 4, s));
-        hipLaunchKernelGGL(k_km_nonfinite, dim3((unsigned)std::min<uint64_t>(4096, grid_of(n * dim, 256))), dim3(256), 0, s, a.data,
-                           n * dim, bad);
-        KM_TRY(hipGetLastError());
-        KM_TRY(hipMemcpy(&h_bad, bad, 4, hipMemcpyDeviceToHost));
-        if (h_bad) { detail = "k-means input must be finite"; return RBQ_INVALID_CONFIG; }
-    }
+    uint32_t* flag = nullptr; // finite input only: the shortlist's error bound needs it (the crate does not check)
+    bool bad = false;
+    KM_TRY(t.alloc(&flag, 1));
+    KM_TRY(nonfinite_sync(a.data, n * dim, flag, s, &bad));
+    if (bad) { detail = "k-means input must be finite"; return RBQ_INVALID_CONFIG; }
     // ---- sampling (select_training_indices) on the host, the sample gathered on the device
     rbq_host::Rng sampling_rng(a.seed);
     const uint64_t kp = a.mppc && k > UINT64_MAX / a.mppc ? UINT64_MAX : k * a.mppc;
@@ -144,7 +136,7 @@ int kmeans_device(const KMeansArgs& a, std::string& detail) {
     float *nx = nullptr, *full_nx = nullptr, *bestd = nullptr, *cent = nullptr;
     uint32_t *asg = nullptr, *keys = nullptr, *vals_in = nullptr, *vals = nullptr, *fin = nullptr;
     unsigned long long* cands = nullptr;
-    KmGemmAssign ga; // the assignment's workspace (km_common.hpp)
+    KmGemmAssign ga; // the assignment's workspace (k_gemm_shortlist.hip)
     double *objrow = nullptr, *obj = nullptr;
     KM_TRY(t.alloc(&nx, rows));
     KM_TRY(t.alloc(&full_nx, n));
@@ -164,10 +156,8 @@ int kmeans_device(const KMeansArgs& a, std::string& detail) {
     void* sort_tmp = nullptr;
     KM_TRY(t.alloc((unsigned char**)&sort_tmp, sort_bytes));
     KM_TRY(launch_iota(vals_in, rows, s));
-    hipLaunchKernelGGL(k_km_norms, dim3(grid_of(rows, 256)), dim3(256), 0, s, x, (uint64_t)rows, dim, nx);
-    KM_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_km_norms, dim3(grid_of(n, 256)), dim3(256), 0, s, a.data, n, dim, full_nx);
-    KM_TRY(hipGetLastError());
+    KM_TRY(launch_row_norms(x, rows, dim, nx, s));
+    KM_TRY(launch_row_norms(a.data, n, dim, full_nx, s));
 
     std::vector<uint32_t> h_start(k), h_end(k), h_src(k);
     std::vector<unsigned long long> h_cands(nchunks_c * kCands), pool;
@@ -187,7 +177,6 @@ int kmeans_device(const KMeansArgs& a, std::string& detail) {
             KM_TRY(hipGetLastError());
         }
         for (uint64_t it = 0; it < a.niter; ++it) {
-            KM_TRY(ga.prep(cent, s));
             KM_TRY(ga.run(x, nx, rows, cent, asg, bestd, s));
             KM_TRY(sort_pairs_u32(sort_tmp, &sort_bytes, asg, keys, vals_in, vals, rows, kbits, s));
             KM_TRY(hipMemsetAsync(d_start, 0, k * 4, s));
@@ -224,7 +213,6 @@ int kmeans_device(const KMeansArgs& a, std::string& detail) {
             }
         }
         // assignment of the full dataset and the objective
-        KM_TRY(ga.prep(cent, s));
         KM_TRY(ga.run(a.data, full_nx, n, cent, fin, nullptr, s));
         hipLaunchKernelGGL(k_km_objrow, dim3(grid_of(n, 256)), dim3(256), 0, s, a.data, n, dim, fin, cent, objrow);
         KM_TRY(hipGetLastError());

@@ -2,8 +2,8 @@
 // row, bit for bit the CPU restatement rbq_build_closure_assign (csrc/host/rbq_build.cpp).  gfx950 only.
 //
 // A chunk of R rows at a time (no n x k score matrix), m = min(max_replicas, k):
-//   k_km_split      the chunk's rows as split-bf16 hi / lo images, zero-padded to Dp = dim rounded up to 32   (km_common.hpp)
-//   k_rank_bf16_db  (rank_mfma.hpp, the ranking GEMM's inner-product form, through launch_rank_gemm) dA(x, c)
+//   launch_approx_dots  (k_gemm_shortlist.hip) the chunk's rows as split-bf16 hi / lo images, zero-padded to Dp = dim rounded up
+//                   to 32, then dA(x, c) by the ranking GEMM's inner-product form (k_rank_bf16_db, rank_mfma.hpp)
 //   k_cl_scan       per row: A = max(0, fmaf(-2, dA, nx + nc)); T = the m-th smallest of the 64 lanes' minima of A (m distinct
 //                   centroids have A <= T); shortlist {c : A(c) <= T + 2 eps} in centroid order; over kShortlist entries (or
 //                   norms near overflow): the row is marked for the fallback
@@ -16,8 +16,8 @@
 //   |A - E| <= gamma_(dim+2) (|x|^2 + |c|^2)                                (the sequential norms and their sum)
 //            + (3.01 * 2^-16 + 6 Dp u)(|x|^2 + |c|^2)                       (2 |dA - P|, rank_mfma.hpp, S <= (|x|^2 + |c|^2) / 2)
 //            + 2.1 u (|x|^2 + |c|^2)                                        (the fmaf's rounding; max(., 0) is 1-Lipschitz, E >= 0)
-//   eps = ((10 Dp + 64) u + 4 * 2^-16)(nx + max nc)(1 + 2^-6) + 2^-100 covers all of it for Dp <= 16384, the norms' own error, the
-//   margin and underflow included.
+//   eps = ((10 Dp + 64) u + 4 * 2^-16)(nx + max nc)(1 + 2^-6) + 2^-100 (closure_eps, km_common.hpp) covers all of it for
+//   Dp <= 16384, the norms' own error, the margin and underflow included.
 // Completeness: let c be among the m first of the exact stable order and suppose A(c) > T + 2 eps.  Then C(c) > T + eps, while the
 // m centroids with A <= T have C <= T + eps < C(c): m centroids come strictly before c.  So every such c is shortlisted, ties at
 // the cut included, and the shortlist's own (distance, centroid) order is the exact order restricted to it.
@@ -50,27 +50,15 @@ __global__ __launch_bounds__(256) void k_cl_scan(const float* __restrict__ dots,
     const float* d = dots + (size_t)row * k;
     const float x2 = nx[row];
     float lmin = INFINITY;
-    for (uint32_t c = lane; c < k; c += 64u) lmin = fminf(lmin, fmaxf(fmaf(-2.0f, d[c], x2 + nc[c]), 0.0f));
+    for (uint32_t c = lane; c < k; c += 64u) lmin = fminf(lmin, km_approx_dist(d, nc, x2, c));
     // the m-th smallest lane minimum (m <= 64): m rounds of a wave minimum over the keys above the last one
     const unsigned long long mine = ((unsigned long long)__float_as_uint(lmin) << 32) | lane;
     unsigned long long last = 0;
     for (uint32_t r = 0; r < m; ++r) last = cl_wave_min(r == 0 || mine > last ? mine : ~0ull);
     const float T = __uint_as_float((uint32_t)(last >> 32));
     const float span = x2 + __uint_as_float(*ncmax_bits);
-    const float eps = ((float)(10u * Dp + 64u) * 5.9604644775390625e-08f + 6.103515625e-05f) * span * 1.015625f + 7.888609052210118e-31f;
-    const float thr = T + 2.01f * eps;
-    uint32_t cnt = 0;
-    bool over = !(span < 1e37f) || !(thr < 1e37f);
-    for (uint32_t c0 = 0; c0 < k && !over; c0 += 64u) {
-        const uint32_t c = c0 + lane;
-        bool in = false;
-        if (c < k) in = fmaxf(fmaf(-2.0f, d[c], x2 + nc[c]), 0.0f) <= thr;
-        const unsigned long long mask = __ballot(in);
-        const uint32_t pos = cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        if (in && pos < kShortlist) sl[(size_t)row * kShortlist + pos] = c;
-        cnt += (uint32_t)__popcll(mask);
-        if (cnt > kShortlist) over = true;
-    }
+    bool over = !(span < 1e37f);
+    const uint32_t cnt = shortlist_collect(d, nc, x2, k, T + 2.01f * closure_eps(Dp, span), kShortlist, sl + (size_t)row * kShortlist, lane, over);
     if (lane == 0) {
         sl_n[row] = over ? kFallbackMark : cnt;
         if (over) atomicAdd(&stats[0], 1ull);
@@ -166,11 +154,11 @@ hipError_t launch_closure_expand(const uint32_t* lists, const uint32_t* counts, 
     return hipGetLastError();
 }
 
-// Bytes of the per-chunk workspace per row: scores (4k), split image (4 Dp), shortlist, a host caller's staged row, the output row.
+// Bytes of the per-chunk workspace per row: the GEMM front's (or the scores alone), a host caller's staged row, the output row.
 static uint64_t cl_chunk_rows(const ClosureArgs& a, uint32_t Dp, bool gemm, bool ident) {
     uint64_t per_row = 4ull * a.max_replicas + 8;
-    if (!ident) per_row += 4 * a.k;
-    if (gemm) per_row += 4ull * Dp + 4ull * kShortlist + 4;
+    if (gemm) per_row += gemm_shortlist_row_bytes(a.k, Dp, kShortlist);
+    else if (!ident) per_row += 4 * a.k;
     if (!a.data_on_device) per_row += 4ull * a.dim;
     uint64_t r = std::max<uint64_t>(kKmeansChunkBytes / per_row, 1);
     if (a.max_chunk_rows) r = std::min(r, a.max_chunk_rows);
@@ -179,18 +167,18 @@ static uint64_t cl_chunk_rows(const ClosureArgs& a, uint32_t Dp, bool gemm, bool
 
 int closure_device(const ClosureArgs& a, int device, std::string& detail) {
     const uint64_t n = a.n, k = a.k;
-    const uint32_t dim = a.dim, Dp = (dim + 31u) / 32u * 32u, M = a.max_replicas;
+    const uint32_t dim = a.dim, Dp = km_dp(dim), M = a.max_replicas;
     const bool ident = k <= kShortlist, gemm = !ident && Dp <= kClMaxDp, tap = a.tap_sl != nullptr;
     const uint64_t R = cl_chunk_rows(a, Dp, gemm, ident), Rp = (R + 127) / 128 * 128; // (the GEMM's row tiles)
     hipStream_t s = 0;
     KmTemp t;
-    float *cent = nullptr, *d_in = nullptr, *nx = nullptr, *nc = nullptr, *dots = nullptr;
-    uint32_t *bad = nullptr, *ncmax = nullptr, *sl = nullptr, *sl_n = nullptr, *o_lists = nullptr, *o_counts = nullptr;
-    uint16_t *xh = nullptr, *xl = nullptr, *ch = nullptr, *cl = nullptr;
+    float *cent = nullptr, *d_in = nullptr, *nx = nullptr, *dots = nullptr;
+    uint32_t *flag = nullptr, *sl = nullptr, *sl_n = nullptr, *o_lists = nullptr, *o_counts = nullptr;
+    uint16_t *xh = nullptr, *xl = nullptr;
+    CentView cv{(uint32_t)k, dim, Dp, nullptr, nullptr, nullptr, nullptr};
     unsigned long long* stats = nullptr;
-    KM_TRY(t.alloc(&bad, 1));
+    KM_TRY(t.alloc(&flag, 1));
     KM_TRY(t.alloc(&stats, 2));
-    KM_TRY(hipMemsetAsync(bad, 0, 4, s));
     KM_TRY(hipMemsetAsync(stats, 0, 16, s));
     if (a.cent_on_device) cent = const_cast<float*>(a.centroids);
     else {
@@ -198,31 +186,25 @@ int closure_device(const ClosureArgs& a, int device, std::string& detail) {
         KM_TRY(hipMemcpy(cent, a.centroids, k * dim * 4, hipMemcpyHostToDevice));
     }
     // finite input only (the crate would panic on a NaN distance): checked before a chunk is scored or any of its rows written
-    uint32_t h_bad = 0;
-    hipLaunchKernelGGL(k_km_nonfinite, dim3((unsigned)std::min<uint64_t>(4096, grid_of(k * dim, 256))), dim3(256), 0, s, cent, k * dim, bad);
-    KM_TRY(hipGetLastError());
-    KM_TRY(hipMemcpy(&h_bad, bad, 4, hipMemcpyDeviceToHost));
-    if (h_bad) { detail = "closure assignment input must be finite"; return RBQ_INVALID_CONFIG; }
+    bool bad = false;
+    KM_TRY(nonfinite_sync(cent, k * dim, flag, s, &bad));
+    if (bad) { detail = "closure assignment input must be finite"; return RBQ_INVALID_CONFIG; }
     if (!a.data_on_device) KM_TRY(t.alloc(&d_in, R * dim));
-    if (!ident) KM_TRY(t.alloc(&dots, Rp * k));
     if (!ident) {
+        KM_TRY(t.alloc(&dots, Rp * k));
         KM_TRY(t.alloc(&sl, R * kShortlist));
         KM_TRY(t.alloc(&sl_n, R));
         KM_TRY(hipMemsetAsync(sl_n, 0xff, R * 4, s)); // (without the GEMM every row stays marked)
     }
     if (gemm) {
         KM_TRY(t.alloc(&nx, R));
-        KM_TRY(t.alloc(&nc, k));
-        KM_TRY(t.alloc(&ncmax, 1));
+        KM_TRY(t.alloc(&cv.nc, k));
+        KM_TRY(t.alloc(&cv.ncmax_bits, 1));
         KM_TRY(t.alloc(&xh, Rp * Dp));
         KM_TRY(t.alloc(&xl, Rp * Dp));
-        KM_TRY(t.alloc(&ch, k * Dp));
-        KM_TRY(t.alloc(&cl, k * Dp));
-        KM_TRY(hipMemsetAsync(ncmax, 0, 4, s));
-        hipLaunchKernelGGL(k_km_cnorms, dim3(grid_of(k, 256)), dim3(256), 0, s, cent, (uint32_t)k, dim, nc, ncmax);
-        KM_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_km_split, dim3(grid_of(k * Dp, 256)), dim3(256), 0, s, cent, (uint32_t)k, dim, Dp, ch, cl);
-        KM_TRY(hipGetLastError());
+        KM_TRY(t.alloc(&cv.hi, k * Dp));
+        KM_TRY(t.alloc(&cv.lo, k * Dp));
+        KM_TRY(launch_split_centroids(cent, cv, s));
     }
     if (!tap && !a.out_on_device) {
         KM_TRY(t.alloc(&o_lists, R * M));
@@ -237,23 +219,12 @@ int closure_device(const ClosureArgs& a, int device, std::string& detail) {
             KM_TRY(hipMemcpy(d_in, xc, (size_t)nr * dim * 4, hipMemcpyHostToDevice));
             xc = d_in;
         }
-        hipLaunchKernelGGL(k_km_nonfinite, dim3((unsigned)std::min<uint64_t>(4096, grid_of((uint64_t)nr * dim, 256))), dim3(256), 0, s, xc,
-                           (uint64_t)nr * dim, bad);
-        KM_TRY(hipGetLastError());
-        KM_TRY(hipMemcpy(&h_bad, bad, 4, hipMemcpyDeviceToHost));
-        if (h_bad) { detail = "closure assignment input must be finite"; return RBQ_INVALID_CONFIG; }
+        KM_TRY(nonfinite_sync(xc, (uint64_t)nr * dim, flag, s, &bad));
+        if (bad) { detail = "closure assignment input must be finite"; return RBQ_INVALID_CONFIG; }
         if (gemm) {
-            hipLaunchKernelGGL(k_km_norms, dim3(grid_of(nr, 256)), dim3(256), 0, s, xc, (uint64_t)nr, dim, nx);
-            KM_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_km_split, dim3(grid_of((uint64_t)nr * Dp, 256)), dim3(256), 0, s, xc, nr, dim, Dp, xh, xl);
-            KM_TRY(hipGetLastError());
-            RankParams p{};
-            p.metric = 1; // inner products only: the norms are added by k_cl_scan
-            p.rot_hi = xh; p.rot_lo = xl; p.cent_hi = ch; p.cent_lo = cl;
-            p.nq = nr; p.nlist = (uint32_t)k; p.D = Dp; p.scores = dots;
-            p.split = true; p.wide = true; p.big = true; p.ksplit = 0;
-            KM_TRY(launch_rank_gemm(p, device, s));
-            hipLaunchKernelGGL(k_cl_scan, dim3(grid_of(nr, 4)), dim3(256), 0, s, dots, nr, (uint32_t)k, Dp, m, nx, nc, ncmax, sl, sl_n, stats);
+            KM_TRY(launch_row_norms(xc, nr, dim, nx, s));
+            KM_TRY(launch_approx_dots(xc, nr, dim, cv, xh, xl, dots, device, s));
+            hipLaunchKernelGGL(k_cl_scan, dim3(grid_of(nr, 4)), dim3(256), 0, s, dots, nr, (uint32_t)k, Dp, m, nx, cv.nc, cv.ncmax_bits, sl, sl_n, stats);
             KM_TRY(hipGetLastError());
         } else if (!ident) {
             marked += nr;

@@ -3,7 +3,7 @@
 // threshold; bit for bit the CPU restatement rbq_build_mstg_select_lists (csrc/host/rbq_build.cpp).  gfx950 only.
 //
 // A chunk of R queries at a time, ef = min(ef_search, k):
-//   k_km_norms / k_km_split / k_rank_bf16_db   as the closure assignment (k_mstg.hip): dA(q, c) for every centroid
+//   launch_row_norms / launch_approx_dots   (k_gemm_shortlist.hip) the front of every GEMM-shortlist path: dA(q, c) for every centroid
 //   k_ms_scan    one wavefront per query, no barrier: A = max(0, fmaf(-2, dA, nq + nc)); T = the ef-th smallest A, by a radix
 //                select over its bit pattern (four passes of a 256-bin histogram); U = an upper bound of every A a list that
 //                survives dynamic_prune can have; shortlist {c : A(c) <= min(T, U) + 2 eps} in centroid order; over kMsCap
@@ -13,7 +13,7 @@
 //                the ef first; d = sqrtf(S); thr = d(first) * (1 + pruning_epsilon); the kept prefix, in scan order
 // The selected lists then go through k_probes_given and the scan exactly as a caller's own lists do (rbq_posting_scan_batch).
 //
-// eps is k_cl_scan's (k_mstg.hip): |A(c) - S(c)| <= eps for finite input with nq + max nc < 1e37.
+// eps is closure_eps (km_common.hpp; derived in k_mstg.hip and DESIGN.md section 15): |A(c) - S(c)| <= eps for finite input with nq + max nc < 1e37.
 // Completeness.  B = min(T, U).  A centroid c with A(c) > B + 2 eps has S(c) > B + eps.
 //   B = T: the ef centroids with A <= T have S <= T + eps < S(c), so ef centroids come strictly before c: c is not among the ef
 //          first, and the shortlist's first ef under (bits, index) are the exact ones.
@@ -49,10 +49,6 @@ __device__ __forceinline__ uint32_t ms_wave_excl(uint32_t v, uint32_t lane, uint
     return inc - v;
 }
 
-__device__ __forceinline__ uint32_t ms_abits(const float* d, const float* nc, float x2, uint32_t c) {
-    return __float_as_uint(fmaxf(fmaf(-2.0f, d[c], x2 + nc[c]), 0.0f)); // (fmaxf drops a NaN: never negative, never NaN)
-}
-
 // one wavefront per query of the chunk (k > kShortlist: the GEMM path).  ef in 1..k.
 __global__ __launch_bounds__(256) void k_ms_scan(const float* __restrict__ dots, uint32_t nr, uint32_t k, uint32_t Dp, uint32_t ef,
                                                  float ope, const float* __restrict__ nx, const float* __restrict__ nc,
@@ -64,7 +60,7 @@ __global__ __launch_bounds__(256) void k_ms_scan(const float* __restrict__ dots,
     const float* d = dots + (size_t)row * k;
     const float x2 = nx[row];
     const float span = x2 + __uint_as_float(*ncmax_bits);
-    const float eps = ((float)(10u * Dp + 64u) * 5.9604644775390625e-08f + 6.103515625e-05f) * span * 1.015625f + 7.888609052210118e-31f;
+    const float eps = closure_eps(Dp, span);
     bool over = cent_bad != 0u || !(span < 1e37f);
     uint32_t* hist = s_hist[w];
     uint32_t prefix = 0, rank = ef, minb = 0x7f800000u;
@@ -73,7 +69,7 @@ __global__ __launch_bounds__(256) void k_ms_scan(const float* __restrict__ dots,
         for (uint32_t b = lane; b < 256u; b += 64u) hist[b] = 0u;
         __threadfence_block();
         for (uint32_t c = lane; c < k; c += 64u) {
-            const uint32_t a = ms_abits(d, nc, x2, c);
+            const uint32_t a = __float_as_uint(km_approx_dist(d, nc, x2, c));
             if (pass == 0) minb = min(minb, a);
             if (pass == 0 || (a >> (shift + 8u)) == (prefix >> (shift + 8u))) atomicAdd(&hist[(a >> shift) & 255u], 1u);
         }
@@ -99,17 +95,7 @@ __global__ __launch_bounds__(256) void k_ms_scan(const float* __restrict__ dots,
             const float U = fmaf((__uint_as_float(minb) + eps) * ope * ope, 1.0001220703125f, 7.888609052210118e-31f);
             B = fminf(T, U); // (U = inf or NaN after an overflow: fminf keeps T)
         }
-        const float thr = B + 2.01f * eps;
-        over = !(thr < 1e37f);
-        for (uint32_t c0 = 0; c0 < k && !over; c0 += 64u) {
-            const uint32_t c = c0 + lane;
-            const bool in = c < k && __uint_as_float(ms_abits(d, nc, x2, c)) <= thr;
-            const unsigned long long mask = __ballot(in);
-            const uint32_t pos = cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (in && pos < kMsCap) sl[(size_t)row * kMsCap + pos] = c;
-            cnt += (uint32_t)__popcll(mask);
-            if (cnt > kMsCap) over = true;
-        }
+        cnt = shortlist_collect(d, nc, x2, k, B + 2.01f * eps, kMsCap, sl + (size_t)row * kMsCap, lane, over);
     }
     if (lane == 0) {
         sl_n[row] = over ? kFallbackMark : cnt;
@@ -191,8 +177,7 @@ __global__ __launch_bounds__(256) void k_ms_fill_none(uint32_t* __restrict__ lis
     if (i < nr) counts[i] = 0u;
 }
 
-uint32_t mstg_select_dp(uint32_t D) { return (D + 31u) / 32u * 32u; }
-bool mstg_select_gemm(uint64_t k, uint32_t D) { return k > kShortlist && mstg_select_dp(D) <= 16384u; }
+bool mstg_select_gemm(uint64_t k, uint32_t D) { return k > kShortlist && km_dp(D) <= 16384u; }
 uint32_t mstg_select_knp2(uint64_t k) {
     if (k <= kMsCap) return 0;
     uint32_t p = 1;
@@ -200,44 +185,25 @@ uint32_t mstg_select_knp2(uint64_t k) {
     return p;
 }
 
-hipError_t launch_mstg_centroid_prep(const float* cent, uint32_t k, uint32_t D, float* nc, uint32_t* ncmax_bits, uint32_t* bad,
-                                     uint16_t* hi, uint16_t* lo, hipStream_t s) {
-    const uint32_t Dp = mstg_select_dp(D);
-    hipError_t e = hipMemsetAsync(ncmax_bits, 0, 4, s);
-    if (e != hipSuccess) return e;
-    if ((e = hipMemsetAsync(bad, 0, 4, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_km_nonfinite, dim3((unsigned)std::min<uint64_t>(4096, grid_of((uint64_t)k * D, 256))), dim3(256), 0, s, cent, (uint64_t)k * D, bad);
-    hipLaunchKernelGGL(k_km_cnorms, dim3(grid_of(k, 256)), dim3(256), 0, s, cent, k, D, nc, ncmax_bits);
-    hipLaunchKernelGGL(k_km_split, dim3(grid_of((uint64_t)k * Dp, 256)), dim3(256), 0, s, cent, k, D, Dp, hi, lo);
-    return hipGetLastError();
-}
-
 hipError_t launch_mstg_select(const MstgSelectParams& p, int device, hipStream_t s) {
-    const uint32_t Dp = mstg_select_dp(p.D), ef = (uint32_t)std::min<uint64_t>(p.ef_search, p.k);
+    const uint32_t D = p.cv.dim, k = p.cv.k, ef = std::min(p.ef_search, k);
     if (ef == 0) { // no list can be selected: counts 0 (the list rows have no slot)
         hipLaunchKernelGGL(k_ms_fill_none, dim3(grid_of(p.nq, 256)), dim3(256), 0, s, p.out_lists, (uint64_t)0, p.out_counts, p.nq);
         return hipGetLastError();
     }
     const float ope = 1.0f + p.pruning_epsilon;
-    const bool ident = p.k <= kShortlist;
-    if (!ident && mstg_select_gemm(p.k, p.D)) {
-        hipLaunchKernelGGL(k_km_norms, dim3(grid_of(p.nq, 256)), dim3(256), 0, s, p.rot, (uint64_t)p.nq, p.D, p.nx);
-        hipLaunchKernelGGL(k_km_split, dim3(grid_of((uint64_t)p.nq * Dp, 256)), dim3(256), 0, s, p.rot, p.nq, p.D, Dp, p.q_hi, p.q_lo);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        RankParams r{};
-        r.metric = 1; // inner products only: the norms are added by k_ms_scan
-        r.rot_hi = p.q_hi; r.rot_lo = p.q_lo; r.cent_hi = p.cent_hi; r.cent_lo = p.cent_lo;
-        r.nq = p.nq; r.nlist = p.k; r.D = Dp; r.scores = p.dots;
-        r.split = true; r.wide = true; r.big = true; r.ksplit = 0;
-        if ((e = launch_rank_gemm(r, device, s)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ms_scan, dim3(grid_of(p.nq, 4)), dim3(256), 0, s, p.dots, p.nq, p.k, Dp, ef, ope, p.nx, p.nc, p.ncmax_bits,
+    const bool ident = k <= kShortlist;
+    if (!ident && mstg_select_gemm(k, D)) {
+        hipError_t e;
+        if ((e = launch_row_norms(p.rot, p.nq, D, p.nx, s)) || (e = launch_approx_dots(p.rot, p.nq, D, p.cv, p.q_hi, p.q_lo, p.dots, device, s)))
+            return e;
+        hipLaunchKernelGGL(k_ms_scan, dim3(grid_of(p.nq, 4)), dim3(256), 0, s, p.dots, p.nq, k, p.cv.Dp, ef, ope, p.nx, p.cv.nc, p.cv.ncmax_bits,
                            p.cent_bad, p.sl, p.sl_n, p.fallbacks);
     } else if (!ident) {
         hipLaunchKernelGGL(k_ms_mark, dim3(grid_of(p.nq, 256)), dim3(256), 0, s, p.sl_n, p.nq, p.fallbacks);
     }
-    hipLaunchKernelGGL(k_ms_exact, dim3(p.nq), dim3(kThreads), 0, s, p.rot, p.D, p.cent, p.k, p.sl, ident ? nullptr : p.sl_n, p.keys_g,
-                       mstg_select_knp2(p.k), ef, ope, p.out_lists, p.out_counts);
+    hipLaunchKernelGGL(k_ms_exact, dim3(p.nq), dim3(kThreads), 0, s, p.rot, D, p.cent, k, p.sl, ident ? nullptr : p.sl_n, p.keys_g,
+                       mstg_select_knp2(k), ef, ope, p.out_lists, p.out_counts);
     return hipGetLastError();
 }
 

@@ -4,7 +4,9 @@
 //   k_query.hip  k_prep / k_prep_wave, k_rank_* , k_select*, k_probes_given     (kernels.hpp, rank_mfma.hpp)
 //   k_scan.hip   k_scan<DT, EX, TR>                                               (scan.hpp)
 //   k_build.hip  encoder, reference-layout -> device-layout converters, sorting   (encode.hpp)
-//   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver
+//   k_gemm_shortlist.hip  the front of the GEMM-shortlist paths (finite check, norms, split images, dots), KmGemmAssign (km_common.hpp)
+//   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver         (km_common.hpp)
+//   k_hcluster.hip  MSTG hierarchical balanced k-means and its host driver                (km_common.hpp)
 //   k_save.hip   RBQ1 writer: device layout -> save_to_writer's cluster bytes, CRC-32 on the GPU
 //   k_fetch.hip  fetch_embedding: id map, decode + inverse rotation of stored vectors
 //   k_bf.hip     brute-force index: distances and the BinaryHeap replay                  (bf.hpp)
@@ -260,10 +262,31 @@ constexpr uint32_t kBfLdsHeapMaxTopK = 8191; // (top_k + 1) * 8 bytes of LDS hea
 hipError_t launch_bf_encode(const EncodeParams& P, hipStream_t s);
 hipError_t launch_bf_pack_ex(const uint8_t* raw, uint64_t nrows, uint32_t D, uint32_t ex_bits, uint8_t* ex, hipStream_t s);
 
+// ---- the GEMM-shortlist front (k_gemm_shortlist.hip): what k-means, hierarchical clustering, the MSTG closure assignment and the
+// MSTG list selection do before their own scan and exact kernels.  Non-owning: every buffer is the caller's.
+inline uint32_t km_dp(uint32_t dim) { return (dim + 31u) / 32u * 32u; } // the padded dimension of the split images
+// workspace bytes per row of a chunk: scores (4k), split image (4 Dp), shortlist of `cap` entries and its length
+inline uint64_t gemm_shortlist_row_bytes(uint64_t k, uint32_t Dp, uint32_t cap) { return 4 * k + 4ull * Dp + 4ull * cap + 4; }
+struct CentView {          // prepared centroids
+    uint32_t k, dim, Dp;
+    float* nc;             // [k] canonical norms
+    uint32_t* ncmax_bits;  // their maximum (bit pattern of a non-negative float)
+    uint16_t *hi, *lo;     // [k][Dp] split-bf16 planes, zero beyond dim (launch_centroid_norms: unused)
+};
+hipError_t launch_centroid_norms(const float* cent, const CentView& v, hipStream_t s);  // nc and ncmax_bits
+hipError_t launch_split_centroids(const float* cent, const CentView& v, hipStream_t s); // the same, then hi / lo
+// *bad = x[0, count) holds a non-finite value; d_flag is one device word of scratch; returns once the answer is known
+hipError_t nonfinite_sync(const float* x, uint64_t count, uint32_t* d_flag, hipStream_t s, bool* bad);
+hipError_t launch_row_norms(const float* x, uint64_t rows, uint32_t dim, float* out, hipStream_t s); // canonical norms of x [rows][dim]
+// dots = approximate inner products of rows [0, nr) of x with the centroids: the ranking GEMM's inner-product form over the rows' split
+// image in xh / xl.  xh, xl [nr rounded up to 128][Dp], dots [nr rounded up to 128][k]; image rows beyond nr are stale, their scores unused.
+hipError_t launch_approx_dots(const float* x, uint32_t nr, uint32_t dim, const CentView& v, uint16_t* xh, uint16_t* xl, float* dots,
+                              int device, hipStream_t s);
+
 // ---- k-means (k_kmeans.hip): run_kmeans_with_config on the current device, arguments already validated (rbq_kmeans_device)
-constexpr uint64_t kKmeansChunkBytes = 512ull << 20; // per-chunk assignment workspace (R rows x (4k + 4Dp + shortlist) bytes, R >= 128)
-// test hooks of KmGemmAssign (km_common.hpp), defined in k_kmeans.hip: a cap on the rows per pass (rbq_debug_set_kmeans_chunk_rows,
-// 0: none) and the passes run so far (rbq_debug_kmeans_assign_passes)
+constexpr uint64_t kKmeansChunkBytes = 512ull << 20; // per-chunk assignment workspace (R rows x gemm_shortlist_row_bytes, R >= 128)
+// test hooks of KmGemmAssign (km_common.hpp), defined in k_gemm_shortlist.hip: a cap on the rows per pass
+// (rbq_debug_set_kmeans_chunk_rows, 0: none) and the passes run so far (rbq_debug_kmeans_assign_passes)
 extern std::atomic<uint64_t> g_km_chunk_rows_cap, g_km_assign_passes;
 struct KMeansArgs {
     const float* data; // device [n][dim]
@@ -319,16 +342,14 @@ int hcluster_device(const HClusterArgs& a, rbq_host::HcResult& out, std::string&
 // ---- MSTG search (k_mstg_search.hip): the exact ef_search nearest centroids of every query and dynamic_prune's cut
 constexpr uint32_t kMsCap = 2048; // shortlist capacity per query (the exact pass sorts it in LDS)
 struct MstgSelectParams {
-    const float* rot;       // [nq][D] the queries as k_prep leaves them (rotator NONE: the raw query)
-    uint32_t nq, D, k;
+    const float* rot;       // [nq][cv.dim] the queries as k_prep leaves them (rotator NONE: the raw query)
+    uint32_t nq;
     uint32_t ef_search;
     float pruning_epsilon;
-    const float* cent;      // [k][D]
-    // the GEMM path (mstg_select_gemm): centroid images and norms of launch_mstg_centroid_prep, per-chunk scratch
-    const uint16_t *cent_hi, *cent_lo; // [k][Dp]
-    const float* nc;        // [k]
-    const uint32_t* ncmax_bits;
+    const float* cent;      // [cv.k][cv.dim]
+    CentView cv;            // k, dim, Dp always; the GEMM path (mstg_select_gemm): as launch_split_centroids left it
     uint32_t cent_bad;      // a centroid coordinate is not finite: every query is scored against every centroid
+    // per-chunk scratch of the GEMM path
     uint16_t *q_hi, *q_lo;  // [nq rounded up to 128][Dp]
     float* nx;              // [nq]
     float* dots;            // [nq rounded up to 128][k]
@@ -339,11 +360,8 @@ struct MstgSelectParams {
     uint32_t* out_lists;    // [nq][min(ef_search, k)] in scan order, unused slots UINT32_MAX
     uint32_t* out_counts;   // [nq]
 };
-uint32_t mstg_select_dp(uint32_t D);            // the padded dimension of the split images
 bool mstg_select_gemm(uint64_t k, uint32_t D);  // whether this shape takes the GEMM shortlist
 uint32_t mstg_select_knp2(uint64_t k);          // keys per query of keys_g (0: not needed)
-hipError_t launch_mstg_centroid_prep(const float* cent, uint32_t k, uint32_t D, float* nc, uint32_t* ncmax_bits, uint32_t* bad,
-                                     uint16_t* hi, uint16_t* lo, hipStream_t s);
 hipError_t launch_mstg_select(const MstgSelectParams& p, int device, hipStream_t s);
 
 // ---- refined MSTG search (k_mstg_refine.hip): the binary scan's pool re-scored with the ex codes, one entry per id, top_k
