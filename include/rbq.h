@@ -385,5 +385,7 @@ uint32_t rbq_abi_version(void);
 /* The device k-means (run_kmeans_with_config): rbq_kmeans_device in its own header. */
 #include "rbq_kmeans.h"
 #include "rbq_persist.h"
+/* Growing a device-resident index (FAISS-style add): rbq_index_append in its own header. */
+#include "rbq_append.h"
 
 #endif /* RBQ_H */

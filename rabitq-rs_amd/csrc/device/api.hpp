@@ -1,5 +1,5 @@
 // api.hpp — internal header of librbq.so's host side: the C ABI of include/rbq.h over the HIP kernels, which the host
-// units (api_index, api_build, api_search, api_mstg_search, api_save, api_load, api_fetch, api_bf, api_mstg, api_mstg_persist) reach through launch.hpp.  Not installed.
+// units (api_index, api_build, api_append, api_search, api_mstg_search, api_save, api_load, api_fetch, api_bf, api_mstg, api_mstg_persist) reach through launch.hpp.  Not installed.
 // Host responsibilities: validate like the reference (src/ivf.rs:1754-1769,1484-1702), upload the reference's ClusterData
 // bytes and have the GPU re-lay them into the device layout (one-time, at create/load), own HBM on one or N devices
 // (replicas), and enqueue prep -> rank -> select -> scan for each query batch.  There is no CPU compute path: every failure
@@ -414,6 +414,11 @@ struct Replica : Geometry {
     StageProf stage_prof[4]; // prep, rank, select, scan
     EventPool ev_pool;
     uint64_t prof_counters[kProfSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // rbq_index_id_bound (FIRST replica only): 1 + the largest stored id, found by one reduction over `ids` on first use, under
+    // idb_mu, kept until destroy (rbq_index_append sets it for the handle it returns)
+    std::mutex idb_mu;
+    uint64_t id_bound = 0;
+    bool idb_ready = false;
     Replica() = default;
     Replica(const Replica&) = delete;
 };
@@ -435,6 +440,19 @@ int wrap_and_replicate(Replica* first, const std::vector<int>& devs, rbq_index**
 // api_build.hip: the device encoder over (vector, list) pairs (rbq_index_build_device_ex: one pair per vector; rbq_mstg_build_device)
 int build_device_pairs(const rbq_header* hdr, const float* centroids, const float* d_data, const uint32_t* d_assign,
                        const uint32_t* d_vec, uint64_t n, int rescale, float t_const, int dev, rbq_index** out);
+
+// api_build.hip: what the streamed builder and rbq_index_append share.  encode_rows_at_cursors rotates, encodes and scatters n
+// device-resident rows (ids id_base + row) into the slots their lists' cursors point at, advances the cursors and returns once
+// the device is idle (the scratch, and a caller's staging buffers, may be reused).  d_block_list: the list of every block;
+// d_cursor [n_lists]: vectors each list holds so far; d_chunk_first [n_lists]: scratch.
+struct EncodeScratch { DevBuf vec, assign, ko, vi, vo, tmp, row_src, row_slot, rows, raw, trow; };
+int encode_rows_at_cursors(Replica* ix, EncodeScratch& sc, const float* d_vec, const uint32_t* d_asg, uint32_t n, uint64_t id_base,
+                           bool opt, float t_const, const uint32_t* d_block_list, uint32_t* d_cursor, uint32_t* d_chunk_first);
+// rows per encode chunk: the 512 MiB budget of the rotated rows
+inline uint64_t encode_chunk_rows(uint32_t D) { return std::max<uint64_t>(1024, ((512ull << 20) / ((size_t)D * 4)) & ~63ull); }
+// block -> list and block -> number of real vectors, on the device
+int upload_block_tables(const std::vector<uint32_t>& ln, const std::vector<uint32_t>& gb0, uint64_t nblocks, Scratch& t,
+                        uint32_t** d_block_list, uint32_t** d_block_nv);
 
 // shared by the search units (api_search.hip): workspaces from the replica's pool and per caller stream, the stage timer, the scan launch
 Workspace* take_ws(Replica* ix);

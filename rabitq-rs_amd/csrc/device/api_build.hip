@@ -13,7 +13,7 @@ struct rbq_builder {
     std::vector<uint32_t> ln, gb0;
     uint64_t n_total = 0, pushed = 0, next_id = 0;
     uint32_t *d_cursor = nullptr, *d_chunk_first = nullptr, *d_block_list = nullptr, *d_block_nv = nullptr, *d_counts = nullptr;
-    DevBuf vec, assign, ko, vi, vo, tmp, row_src, row_slot, rows, raw, trow;
+    EncodeScratch sc;
     Scratch tables;
     ~rbq_builder() { if (ix) free_replica(ix); } // (deleted under a DeviceGuard of `device`: the scratch is freed there)
 };
@@ -69,6 +69,8 @@ int encoder_prepare(Replica* ix, const rbq_header* hdr, const float* centroids, 
     return RBQ_OK;
 }
 
+} // namespace
+
 // block -> list and block -> number of real vectors, on the device
 int upload_block_tables(const std::vector<uint32_t>& ln, const std::vector<uint32_t>& gb0, uint64_t nblocks, Scratch& t,
                         uint32_t** d_block_list, uint32_t** d_block_nv) {
@@ -83,7 +85,45 @@ int upload_block_tables(const std::vector<uint32_t>& ln, const std::vector<uint3
     return RBQ_OK;
 }
 
-} // namespace
+int encode_rows_at_cursors(Replica* ix, EncodeScratch& sc, const float* d_vec, const uint32_t* d_asg, uint32_t n, uint64_t id_base,
+                           bool opt, float t_const, const uint32_t* d_block_list, uint32_t* d_cursor, uint32_t* d_chunk_first) {
+    const uint32_t D = ix->D, Dc = ix->Dc, dim = ix->dim, nlist = (uint32_t)ix->n_lists;
+    unsigned bits = 1;
+    while ((1ull << bits) < nlist) ++bits;
+    int rc;
+    if ((rc = sc.ko.ensure((size_t)n * 4)) || (rc = sc.vi.ensure((size_t)n * 4)) || (rc = sc.vo.ensure((size_t)n * 4)) ||
+        (rc = sc.row_src.ensure((size_t)n * 4)) || (rc = sc.row_slot.ensure((size_t)n * 4)) ||
+        (rc = sc.rows.ensure((size_t)n * D * 4)) || (rc = sc.raw.ensure(ix->ex_bits ? (size_t)n * D : 16)) ||
+        (opt && (rc = sc.trow.ensure((size_t)n * 8))))
+        return rc;
+    HIP_TRY(launch_iota((uint32_t*)sc.vi.p, n, 0));
+    size_t tb = 0;
+    HIP_TRY(sort_pairs_u32(nullptr, &tb, d_asg, (uint32_t*)sc.ko.p, (const uint32_t*)sc.vi.p, (uint32_t*)sc.vo.p, n, bits, 0));
+    if ((rc = sc.tmp.ensure(tb))) return rc;
+    HIP_TRY(sort_pairs_u32(sc.tmp.p, &tb, d_asg, (uint32_t*)sc.ko.p, (const uint32_t*)sc.vi.p, (uint32_t*)sc.vo.p, n, bits, 0));
+    HIP_TRY(launch_chunk_first((const uint32_t*)sc.ko.p, n, d_chunk_first, 0));
+    HIP_TRY(launch_chunk_slots((const uint32_t*)sc.ko.p, (const uint32_t*)sc.vo.p, n, (const uint32_t*)ix->list_gb0.p, d_cursor,
+                               d_chunk_first, (uint32_t*)sc.row_src.p, (uint32_t*)sc.row_slot.p, 0));
+    HIP_TRY(launch_rotate_rows(d_vec, (const uint32_t*)sc.row_src.p, n, dim, D, (int)ix->rotator, (const uint8_t*)ix->rot_blob.p,
+                               ix->trunc, ix->fac, (float*)sc.rows.p, 0));
+    if (opt)
+        HIP_TRY(launch_rescale((const float*)sc.rows.p, (const float*)ix->centroids.p, d_block_list, (const uint32_t*)sc.row_slot.p,
+                               (const uint32_t*)sc.row_src.p, n, D, (uint32_t)ix->ex_bits, false, (double*)sc.trow.p, 0));
+    EncodeParams P;
+    P.rows = (const float*)sc.rows.p; P.centroids = (const float*)ix->centroids.p; P.slot_src = (const uint32_t*)sc.row_src.p;
+    P.block_list = d_block_list; P.row_slot = (const uint32_t*)sc.row_slot.p; P.t_row = opt ? (const double*)sc.trow.p : nullptr;
+    P.blocks = (uint8_t*)ix->blocks.p; P.raw_ex = (uint8_t*)sc.raw.p;
+    P.f_add_ex = (float*)ix->fadd_ex.p; P.f_rescale_ex = (float*)ix->fres_ex.p; P.ids = (uint64_t*)ix->ids.p;
+    P.delta = (float*)ix->delta.p; P.vl = (float*)ix->vl.p;
+    P.src_base = id_base; P.nslots = n; P.D = D; P.Dc = Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.t_const = t_const;
+    HIP_TRY(launch_encode(P, 0));
+    if (ix->ex_bits)
+        HIP_TRY(launch_pack_ex((const uint8_t*)sc.raw.p, (const uint32_t*)sc.row_src.p, (const uint32_t*)sc.row_slot.p, n, D,
+                               (uint32_t)ix->ex_bits, (uint8_t*)ix->ex.p, 0));
+    HIP_TRY(launch_chunk_advance((const uint32_t*)sc.ko.p, n, d_chunk_first, d_cursor, 0));
+    HIP_TRY(hipDeviceSynchronize()); // the scratch (and a host caller's buffers) are reused by the next sub-chunk
+    return RBQ_OK;
+}
 
 // The encoder over n (vector, list) pairs: pair j stores vector d_vec[j] (null: vector j, one list per vector) in list
 // d_assign[j].  The pairs arrive in ascending vector order, so the stable sort leaves every list in ascending vector index.
@@ -249,27 +289,24 @@ int stream_push_impl(rbq_builder* b, const float* vectors, const uint32_t* assig
     DeviceGuard g(b->device);
     if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
     Replica* ix = b->ix;
-    const uint32_t D = ix->D, Dc = ix->Dc, dim = ix->dim, nlist = (uint32_t)ix->n_lists;
-    const size_t exd = ex_bytes_dev(D, ix->ex_bits);
+    const uint32_t dim = ix->dim, nlist = (uint32_t)ix->n_lists;
     const bool vec_dev = is_device_pointer(vectors), asg_dev = is_device_pointer(assign);
     // sub-chunks bounded by the scratch for the rotated rows (512 MB)
-    const uint64_t SUB = std::max<uint64_t>(1024, ((512ull << 20) / ((size_t)D * 4)) & ~63ull);
-    unsigned bits = 1;
-    while ((1ull << bits) < nlist) ++bits;
+    const uint64_t SUB = encode_chunk_rows(ix->D);
     int rc;
     for (uint64_t s0 = 0; s0 < count; s0 += SUB) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(SUB, count - s0);
         const float* d_vec = vectors + s0 * dim;
         const uint32_t* d_asg = assign + s0;
         if (!vec_dev) {
-            if ((rc = b->vec.ensure((size_t)n * dim * 4))) return rc;
-            HIP_TRY(hipMemcpy(b->vec.p, vectors + s0 * dim, (size_t)n * dim * 4, hipMemcpyHostToDevice));
-            d_vec = (const float*)b->vec.p;
+            if ((rc = b->sc.vec.ensure((size_t)n * dim * 4))) return rc;
+            HIP_TRY(hipMemcpy(b->sc.vec.p, vectors + s0 * dim, (size_t)n * dim * 4, hipMemcpyHostToDevice));
+            d_vec = (const float*)b->sc.vec.p;
         }
         if (!asg_dev) {
-            if ((rc = b->assign.ensure((size_t)n * 4))) return rc;
-            HIP_TRY(hipMemcpy(b->assign.p, assign + s0, (size_t)n * 4, hipMemcpyHostToDevice));
-            d_asg = (const uint32_t*)b->assign.p;
+            if ((rc = b->sc.assign.ensure((size_t)n * 4))) return rc;
+            HIP_TRY(hipMemcpy(b->sc.assign.p, assign + s0, (size_t)n * 4, hipMemcpyHostToDevice));
+            d_asg = (const uint32_t*)b->sc.assign.p;
         }
         // counts so far incl. this sub-chunk: no list may outgrow its announced size (its slots are fixed)
         HIP_TRY(launch_count_assign(d_asg, n, nlist, b->d_counts, b->d_counts + nlist, 0));
@@ -280,38 +317,9 @@ int stream_push_impl(rbq_builder* b, const float* vectors, const uint32_t* assig
             for (uint32_t c = 0; c < nlist; ++c)
                 if (hc[c] > b->ln[c]) return fail(RBQ_INVALID_CONFIG, "list " + std::to_string(c) + " received more vectors than announced");
         }
-        if ((rc = b->ko.ensure((size_t)n * 4)) || (rc = b->vi.ensure((size_t)n * 4)) || (rc = b->vo.ensure((size_t)n * 4)) ||
-            (rc = b->row_src.ensure((size_t)n * 4)) || (rc = b->row_slot.ensure((size_t)n * 4)) ||
-            (rc = b->rows.ensure((size_t)n * D * 4)) || (rc = b->raw.ensure(ix->ex_bits ? (size_t)n * D : 16)) ||
-            (b->opt && (rc = b->trow.ensure((size_t)n * 8))))
+        if ((rc = encode_rows_at_cursors(ix, b->sc, d_vec, d_asg, n, first_id + s0, b->opt, b->t_const, b->d_block_list, b->d_cursor,
+                                         b->d_chunk_first)))
             return rc;
-        HIP_TRY(launch_iota((uint32_t*)b->vi.p, n, 0));
-        size_t tb = 0;
-        HIP_TRY(sort_pairs_u32(nullptr, &tb, d_asg, (uint32_t*)b->ko.p, (const uint32_t*)b->vi.p, (uint32_t*)b->vo.p, n, bits, 0));
-        if ((rc = b->tmp.ensure(tb))) return rc;
-        HIP_TRY(sort_pairs_u32(b->tmp.p, &tb, d_asg, (uint32_t*)b->ko.p, (const uint32_t*)b->vi.p, (uint32_t*)b->vo.p, n, bits, 0));
-        HIP_TRY(launch_chunk_first((const uint32_t*)b->ko.p, n, b->d_chunk_first, 0));
-        HIP_TRY(launch_chunk_slots((const uint32_t*)b->ko.p, (const uint32_t*)b->vo.p, n, (const uint32_t*)ix->list_gb0.p, b->d_cursor,
-                                   b->d_chunk_first, (uint32_t*)b->row_src.p, (uint32_t*)b->row_slot.p, 0));
-        HIP_TRY(launch_rotate_rows(d_vec, (const uint32_t*)b->row_src.p, n, dim, D, (int)ix->rotator, (const uint8_t*)ix->rot_blob.p,
-                                   ix->trunc, ix->fac, (float*)b->rows.p, 0));
-        if (b->opt)
-            HIP_TRY(launch_rescale((const float*)b->rows.p, (const float*)ix->centroids.p, b->d_block_list, (const uint32_t*)b->row_slot.p,
-                                   (const uint32_t*)b->row_src.p, n, D, (uint32_t)ix->ex_bits, false, (double*)b->trow.p, 0));
-        EncodeParams P;
-        P.rows = (const float*)b->rows.p; P.centroids = (const float*)ix->centroids.p; P.slot_src = (const uint32_t*)b->row_src.p;
-        P.block_list = b->d_block_list; P.row_slot = (const uint32_t*)b->row_slot.p; P.t_row = b->opt ? (const double*)b->trow.p : nullptr;
-        P.blocks = (uint8_t*)ix->blocks.p; P.raw_ex = (uint8_t*)b->raw.p;
-        P.f_add_ex = (float*)ix->fadd_ex.p; P.f_rescale_ex = (float*)ix->fres_ex.p; P.ids = (uint64_t*)ix->ids.p;
-        P.delta = (float*)ix->delta.p; P.vl = (float*)ix->vl.p;
-        P.src_base = first_id + s0; P.nslots = n; P.D = D; P.Dc = Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.t_const = b->t_const;
-        HIP_TRY(launch_encode(P, 0));
-        if (ix->ex_bits)
-            HIP_TRY(launch_pack_ex((const uint8_t*)b->raw.p, (const uint32_t*)b->row_src.p, (const uint32_t*)b->row_slot.p, n, D,
-                                   (uint32_t)ix->ex_bits, (uint8_t*)ix->ex.p, 0));
-        (void)exd;
-        HIP_TRY(launch_chunk_advance((const uint32_t*)b->ko.p, n, b->d_chunk_first, b->d_cursor, 0));
-        HIP_TRY(hipDeviceSynchronize()); // the scratch (and a host caller's buffers) are reused by the next sub-chunk
     }
     b->pushed += count;
     b->next_id = first_id + count;

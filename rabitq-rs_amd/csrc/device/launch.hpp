@@ -16,6 +16,7 @@
 //   k_load.hip   streamed RBQ1 loader: spans of the stream -> device layout, ex-code prefix check
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, rank_mfma.hpp)
 //   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan.hpp)
+//   k_append.hip rbq_index_append: carry of an index into a larger geometry, id bound, nearest list of rotated rows (km_common.hpp)
 #pragma once
 #include <atomic>
 #include <string>
@@ -471,6 +472,31 @@ struct LoadSpanParams {
 hipError_t launch_load_span(const LoadSpanParams& P, uint64_t n_workgroups, hipStream_t s);
 // block_nv[b] = real vectors of global block b (1..32), from the lists' first blocks and sizes
 hipError_t launch_load_block_nv(const uint32_t* list_gb0, const uint32_t* list_n, uint32_t n_lists, uint32_t* block_nv, hipStream_t s);
+
+// ---- rbq_index_append (k_append.hip; csrc/host/rbq_append_plan.hpp) ------------------------------------
+// The arrays of an index moved into the geometry of a grown one: new block b of list c = block_list[b] takes old block
+// append_src_block(b, gb0_new[c], gb0_old[c], n_old[c]) — its record, ids, ex codes, ex factors and reconstruction factors — or,
+// where the list had no such block, what the streamed builder's zero fill leaves: zeros, and ids of all ones.
+struct AppendCarryParams {
+    const uint32_t* block_list;                 // [nb_new] list of every block of the grown index
+    const uint32_t *gb0_new, *gb0_old, *n_old;  // [n_lists]
+    uint32_t nb_new, nb_old;
+    uint32_t rec16, ex16;                       // 16-byte units of a block record / of a block's 32 ex codes (0: 1-bit index)
+    const uint8_t *blocks_s, *ex_s;
+    uint8_t *blocks_d, *ex_d;
+    const uint64_t* ids_s;
+    uint64_t* ids_d;
+    const float *fadd_s, *fres_s, *delta_s, *vl_s; // fadd / fres: null for a 1-bit index
+    float *fadd_d, *fres_d, *delta_d, *vl_d;
+};
+hipError_t launch_append_carry(const AppendCarryParams& P, int device, hipStream_t s);
+// *out (device, zeroed by the caller) = max over the real slots of id + 1 (saturating); block_nv [n_blocks] as launch_load_block_nv leaves it
+hipError_t launch_append_id_bound(const uint64_t* ids, const uint32_t* block_nv, uint64_t n_blocks, unsigned long long* out, hipStream_t s);
+// Nearest list of rotated rows by DESIGN.md section 11's canonical distance: KmGemmAssign over rows [.][D] against cent [k][D].
+struct AppendAssign; // workspace for up to `rows` rows per run
+hipError_t append_assign_create(uint64_t rows, uint64_t k, uint32_t D, int device, AppendAssign** out);
+hipError_t append_assign_run(AppendAssign* a, const float* rows, uint32_t n, const float* cent, uint32_t* out, hipStream_t s);
+void append_assign_free(AppendAssign* a);
 
 // ---- fetch_embedding (k_fetch.hip) -------------------------------------------------------------------------------------------
 // id map: the (id, slot) pairs of every real slot in (cluster, position) order, stably sorted by id.  vstart [n_lists + 1] =

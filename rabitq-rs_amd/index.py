@@ -150,6 +150,15 @@ def lib():
         L.rbq_index_fetch_embeddings.argtypes = [vp, vp, C.c_uint64, vp, vp]
         L.rbq_index_fetch_embeddings_device.restype = C.c_int
         L.rbq_index_fetch_embeddings_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+        # rbq_append.h
+        L.rbq_index_append.restype = C.c_int
+        L.rbq_index_append.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_uint64, C.c_int, vp, vp, C.POINTER(vp)]
+        L.rbq_index_id_bound.restype = C.c_int
+        L.rbq_index_id_bound.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rbq_debug_append_passes.restype = C.c_uint64
+        L.rbq_debug_append_passes.argtypes = []
+        L.rbq_debug_append_carry_ns.restype = C.c_uint64
+        L.rbq_debug_append_carry_ns.argtypes = []
         # rbq_mstg.h
         L.rbq_mstg_closure_assign.restype = C.c_int
         L.rbq_mstg_closure_assign.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint64, C.c_int,
@@ -227,8 +236,9 @@ def _addr(ptr):
 class IvfRabitqIndex:
     """Device-resident IVF+RaBitQ index; query methods mirror reference src/ivf.rs:1705-1752."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, rescale=None):
         self._h = handle
+        self._rescale = rescale  # (mode, t_const) the encoder ran with, where this object knows it: add()'s default
 
     # -- construction -------------------------------------------------------------
     @staticmethod
@@ -275,7 +285,7 @@ class IvfRabitqIndex:
         h = C.c_void_p()
         _check(lib().rbq_index_build_device_ex(_addr(hdr_ptr), cent.ctypes.data, C.c_void_p(d_data), C.c_void_p(d_assign),
                                                int(n), mode, t, int(device), C.byref(h)))
-        return cls(h)
+        return cls(h, (rescale, t_const))
 
     @classmethod
     def train_on_device(cls, data, centroids, assignments, total_bits, metric, rotator_type, seed, use_faster_config,
@@ -471,6 +481,57 @@ class IvfRabitqIndex:
         [n][dim] f32, d_found [n] u8, enqueued on `stream` (a hipStream_t as int, None = default stream)."""
         _check(lib().rbq_index_fetch_embeddings_device(self._h, C.c_void_p(d_ids), int(n), C.c_void_p(d_out), C.c_void_p(d_found),
                                                        C.c_void_p(stream) if stream else None))
+
+    # -- growth (rbq_index_append) --------------------------------------------------------------------------------
+    def id_bound(self):
+        """1 + the largest stored id; 0 for an index without vectors (rbq_index_id_bound)."""
+        out = C.c_uint64()
+        _check(lib().rbq_index_id_bound(self._h, C.byref(out)))
+        return int(out.value)
+
+    def add(self, data, assignments=None, first_id=None, rescale=None, t_const=None, max_chunk_rows=0, devices=None):
+        """FAISS-style add (rbq_index_append): the rows of `data` [count][dim] (a host array or a CUDA tensor) join the index with
+        ids first_id .. (default: id_bound()), in the lists `assignments` [count] names (host array or CUDA tensor; None: the
+        nearest rotated centroid of every row).  The index afterwards equals, array for array, a one-shot build over the old and
+        the new rows.  rescale / t_const default to what train, train_on_device or build_on_device encoded this object with; a
+        loaded object has to be given them.  The object's handle is swapped for the grown one (on `devices`, default the first
+        replica's device) and the old one closed.  Returns the list of every row, [count] u32."""
+        import torch
+        from . import RabitqError
+        if rescale is None:
+            if self._rescale is None:
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "this index does not know what it was encoded with (a loaded index does not "
+                                  "store it): pass rescale= and t_const= to add()")
+            rescale, t_known = self._rescale
+            if t_const is None:
+                t_const = t_known
+        if isinstance(data, torch.Tensor):
+            x = data.to(dtype=torch.float32).contiguous()
+            if not x.is_cuda:
+                x = x.numpy()
+        else:
+            x = np.ascontiguousarray(data, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data must be [count][%d]" % self.dim)
+        count = int(x.shape[0])
+        a = None
+        if assignments is not None:
+            if isinstance(assignments, torch.Tensor) and assignments.is_cuda:
+                a = assignments.to(dtype=torch.int32).contiguous()
+            else:
+                a = np.ascontiguousarray(assignments.numpy() if isinstance(assignments, torch.Tensor) else assignments).astype(np.uint32)
+            if a.ndim != 1 or a.shape[0] != count:
+                raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "assignments must be [count]")
+        ptr = lambda v: None if v is None else C.c_void_p(v.data_ptr() if isinstance(v, torch.Tensor) else v.ctypes.data)  # noqa: E731
+        mode, t = _rescale(rescale, t_const)
+        out = np.empty(count, np.uint32)
+        nd, dv = (1, None) if devices is None else self._devices(None, devices)
+        h = C.c_void_p()
+        _check(lib().rbq_index_append(self._h, ptr(x), ptr(a), count, self.id_bound() if first_id is None else int(first_id), mode, t,
+                                      int(max_chunk_rows), nd, dv, out.ctypes.data, C.byref(h)))
+        old, self._h, self._rescale = self._h, h, (rescale, t_const)
+        lib().rbq_index_destroy(old)
+        return out
 
     # -- accessors ----------------------------------------------------------------
     def __len__(self):
