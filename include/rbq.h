@@ -387,5 +387,7 @@ uint32_t rbq_abi_version(void);
 #include "rbq_persist.h"
 /* Growing a device-resident index (FAISS-style add): rbq_index_append in its own header. */
 #include "rbq_append.h"
+/* Shrinking a device-resident index (FAISS-style remove_ids): rbq_index_remove_ids in its own header. */
+#include "rbq_remove.h"
 
 #endif /* RBQ_H */

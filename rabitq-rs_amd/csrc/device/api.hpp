@@ -1,5 +1,5 @@
 // api.hpp — internal header of librbq.so's host side: the C ABI of include/rbq.h over the HIP kernels, which the host
-// units (api_index, api_build, api_append, api_search, api_mstg_search, api_save, api_load, api_fetch, api_bf, api_mstg, api_mstg_persist) reach through launch.hpp.  Not installed.
+// units (api_index, api_build, api_append, api_remove, api_search, api_mstg_search, api_save, api_load, api_fetch, api_bf, api_mstg, api_mstg_persist) reach through launch.hpp.  Not installed.
 // Host responsibilities: validate like the reference (src/ivf.rs:1754-1769,1484-1702), upload the reference's ClusterData
 // bytes and have the GPU re-lay them into the device layout (one-time, at create/load), own HBM on one or N devices
 // (replicas), and enqueue prep -> rank -> select -> scan for each query batch.  There is no CPU compute path: every failure
@@ -453,6 +453,29 @@ inline uint64_t encode_chunk_rows(uint32_t D) { return std::max<uint64_t>(1024, 
 // block -> list and block -> number of real vectors, on the device
 int upload_block_tables(const std::vector<uint32_t>& ln, const std::vector<uint32_t>& gb0, uint64_t nblocks, Scratch& t,
                         uint32_t** d_block_list, uint32_t** d_block_nv);
+
+// what rbq_index_append and rbq_index_remove_ids (api_append.hip, api_remove.hip) share
+struct EventPair { // times one launch on the null stream; freed on every exit
+    hipEvent_t a = nullptr, b = nullptr;
+    bool ok = false;
+    EventPair() {
+        ok = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+    }
+    EventPair(const EventPair&) = delete;
+    ~EventPair() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    void start() { if (ok) ok = hipEventRecord(a, 0) == hipSuccess; }
+    void stop() { if (ok) ok = hipEventRecord(b, 0) == hipSuccess; }
+    bool ns(uint64_t* out) {
+        float ms = 0.0f;
+        if (!ok || hipEventSynchronize(b) != hipSuccess || hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return false; }
+        *out = (uint64_t)((double)ms * 1e6);
+        return true;
+    }
+};
 
 // shared by the search units (api_search.hip): workspaces from the replica's pool and per caller stream, the stage timer, the scan launch
 Workspace* take_ws(Replica* ix);

@@ -12,27 +12,6 @@ namespace {
 std::atomic<uint64_t> g_append_passes{0}; // rbq_debug_append_passes
 std::atomic<uint64_t> g_carry_ns{0};      // rbq_debug_append_carry_ns: device time of the last carry kernel
 
-struct EventPair { // times one launch on the null stream; freed on every exit
-    hipEvent_t a = nullptr, b = nullptr;
-    bool ok = false;
-    EventPair() {
-        ok = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-    }
-    ~EventPair() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-    void start() { if (ok) ok = hipEventRecord(a, 0) == hipSuccess; }
-    void stop() { if (ok) ok = hipEventRecord(b, 0) == hipSuccess; }
-    bool ns(uint64_t* out) {
-        float ms = 0.0f;
-        if (!ok || hipEventSynchronize(b) != hipSuccess || hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return false; }
-        *out = (uint64_t)((double)ms * 1e6);
-        return true;
-    }
-};
-
 struct AssignOwner { // frees the assignment workspace on every exit
     AppendAssign* a = nullptr;
     ~AssignOwner() { append_assign_free(a); }

@@ -17,6 +17,7 @@
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, rank_mfma.hpp)
 //   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan.hpp)
 //   k_append.hip rbq_index_append: carry of an index into a larger geometry, id bound, nearest list of rotated rows (km_common.hpp)
+//   k_remove.hip rbq_index_remove_ids: keep masks against a sorted id set, slot map, gather of an index into a smaller geometry
 #pragma once
 #include <atomic>
 #include <string>
@@ -497,6 +498,37 @@ struct AppendAssign; // workspace for up to `rows` rows per run
 hipError_t append_assign_create(uint64_t rows, uint64_t k, uint32_t D, int device, AppendAssign** out);
 hipError_t append_assign_run(AppendAssign* a, const float* rows, uint32_t n, const float* cent, uint32_t* out, hipStream_t s);
 void append_assign_free(AppendAssign* a);
+
+// ---- rbq_index_remove_ids (k_remove.hip; csrc/host/rbq_remove_plan.hpp) -------------------------------
+// rocprim's radix sort of u64 keys; tmp == null returns the scratch size in *tmp_bytes
+hipError_t sort_keys_u64(void* tmp, size_t* tmp_bytes, const uint64_t* keys_in, uint64_t* keys_out, size_t n, hipStream_t s);
+// mask[b] bit v = slot v of block b is real (v < block_nv[b]) and its id is not in `set` ([n_set] u64, ascending)
+hipError_t launch_remove_mark(const uint64_t* ids, const uint32_t* block_nv, uint64_t n_blocks, const uint64_t* set, uint64_t n_set,
+                              uint32_t* mask, hipStream_t s);
+// scan[i] = kept slots (set mask bits) of blocks [0, i), i < n; tmp == null returns the scratch size in *tmp_bytes
+hipError_t remove_scan_kept(void* tmp, size_t* tmp_bytes, const uint32_t* mask, uint32_t* scan, uint64_t n, hipStream_t s);
+// kept[c] = kept slots of list c; scan [n_blocks + 1] as remove_scan_kept leaves it
+hipError_t launch_remove_list_kept(const uint32_t* scan, const uint32_t* gb0_old, const uint32_t* n_old, uint32_t n_lists,
+                                   uint64_t n_blocks, uint32_t* kept, hipStream_t s);
+// map[remove_dst_slot(..)] = old slot for every kept old slot; the caller fills map [nb_new * 32] with all ones (pads) first
+hipError_t launch_remove_slot_map(const uint32_t* mask, const uint32_t* scan, const uint32_t* block_list_old, const uint32_t* gb0_old,
+                                  const uint32_t* gb0_new, uint64_t nb_old, uint64_t nb_new, uint32_t* map, hipStream_t s);
+// The arrays of an index gathered into the geometry of a shrunk one: new slot s takes old slot map[s] — its lane of the block
+// record (code granules, tail granule, factor rows), its ex code, id, ex factors and reconstruction factors — or, for a pad
+// (all ones), the builder's fill: zeros, and an id of all ones.
+struct RemoveGatherParams {
+    const uint32_t* map;                        // [nb_new * 32] source slot of every new slot
+    uint32_t nb_new, n_slots_old;
+    uint32_t rec, G16, tail;                    // bytes of a block record (4 Dc + 384), full code granules (Dc / 128), Dc % 128 == 64
+    uint32_t ex16;                              // 16-byte units of one slot's ex code (0: 1-bit index)
+    const uint8_t *blocks_s, *ex_s;
+    uint8_t *blocks_d, *ex_d;
+    const uint64_t* ids_s;
+    uint64_t* ids_d;
+    const float *fadd_s, *fres_s, *delta_s, *vl_s; // fadd / fres: null for a 1-bit index
+    float *fadd_d, *fres_d, *delta_d, *vl_d;
+};
+hipError_t launch_remove_gather(const RemoveGatherParams& P, int device, hipStream_t s);
 
 // ---- fetch_embedding (k_fetch.hip) -------------------------------------------------------------------------------------------
 // id map: the (id, slot) pairs of every real slot in (cluster, position) order, stably sorted by id.  vstart [n_lists + 1] =

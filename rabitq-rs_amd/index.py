@@ -159,6 +159,11 @@ def lib():
         L.rbq_debug_append_passes.argtypes = []
         L.rbq_debug_append_carry_ns.restype = C.c_uint64
         L.rbq_debug_append_carry_ns.argtypes = []
+        # rbq_remove.h
+        L.rbq_index_remove_ids.restype = C.c_int
+        L.rbq_index_remove_ids.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.POINTER(C.c_uint64), C.POINTER(vp)]
+        L.rbq_debug_remove_gather_ns.restype = C.c_uint64
+        L.rbq_debug_remove_gather_ns.argtypes = []
         # rbq_mstg.h
         L.rbq_mstg_closure_assign.restype = C.c_int
         L.rbq_mstg_closure_assign.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint64, C.c_int,
@@ -532,6 +537,32 @@ class IvfRabitqIndex:
         old, self._h, self._rescale = self._h, h, (rescale, t_const)
         lib().rbq_index_destroy(old)
         return out
+
+    # -- shrinking (rbq_index_remove_ids) ------------------------------------------------------------------------------
+    def remove_ids(self, ids, devices=None):
+        """FAISS-style remove_ids (rbq_index_remove_ids): every stored vector whose id is in `ids` (a host array, a list, or a
+        CUDA int64 / uint64 tensor; any order, repeats allowed, ids that are not stored ignored) leaves the index.  The index
+        afterwards equals, array for array, a one-shot build over the rows that stay, with their original ids.  The object's handle
+        is swapped for the shrunk one (on `devices`, default the first replica's device) and the old one closed; the remembered
+        rescale mode stays.  Returns the number of slots removed; an empty `ids` returns 0 without a call."""
+        import torch
+        from . import RabitqError
+        if isinstance(ids, torch.Tensor) and ids.is_cuda:
+            if ids.dtype not in (torch.int64, torch.uint64):
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "ids on the device must be int64 or uint64")
+            v = ids.contiguous().reshape(-1)
+            n, p = int(v.numel()), v.data_ptr()
+        else:
+            v = np.ascontiguousarray(ids.numpy() if isinstance(ids, torch.Tensor) else ids).astype(np.uint64).reshape(-1)
+            n, p = int(v.size), v.ctypes.data
+        if n == 0:
+            return 0
+        nd, dv = (1, None) if devices is None else self._devices(None, devices)
+        h, removed = C.c_void_p(), C.c_uint64()
+        _check(lib().rbq_index_remove_ids(self._h, C.c_void_p(p), n, nd, dv, C.byref(removed), C.byref(h)))
+        old, self._h = self._h, h
+        lib().rbq_index_destroy(old)
+        return int(removed.value)
 
     # -- accessors ----------------------------------------------------------------
     def __len__(self):
