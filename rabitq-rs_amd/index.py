@@ -553,7 +553,11 @@ class IvfRabitqIndex:
             v = ids.contiguous().reshape(-1)
             n, p = int(v.numel()), v.data_ptr()
         else:
-            v = np.ascontiguousarray(ids.numpy() if isinstance(ids, torch.Tensor) else ids).astype(np.uint64).reshape(-1)
+            if isinstance(ids, torch.Tensor):
+                ids = ids.numpy()
+            if not isinstance(ids, np.ndarray):  # (numpy would make float64 of a list that mixes ints below and above 2^63)
+                ids = np.asarray(ids if hasattr(ids, "__len__") else list(ids), dtype=np.uint64)
+            v = np.ascontiguousarray(ids).astype(np.uint64).reshape(-1)
             n, p = int(v.size), v.ctypes.data
         if n == 0:
             return 0
