@@ -246,6 +246,7 @@ struct Workspace {
     DevBuf queries, rot, lut, consts, scores, probe, wl, nstream, nvec, out_pack, filter, rot_hl, rank_planes, dead_skipped, heap_ws, key_window, audit_dead, tie_log, head_ub;
     // rot_hl: the split-bf16 image of the rotated queries, hi | lo interleaved per K slab (hl_layout.hpp); rank_planes: planar
     // copies of both GEMM operands (debug option rank_planar)
+    DevBuf rot_f16, rank_resid; // one-product f16 route: the f16 image [nq][D] of the rotated queries and |q - f16(q)| per query
     DevBuf ms_sl, ms_lists; // rbq_mstg_search_batch*: shortlists | their lengths | query norms; the selected lists | their counts
     DevBuf mr_pool;         // rbq_mstg_search_refined_batch*: the pool's slots [n][pool] u64 | estimates [n][pool] f32 | counts [n] u32
     PinBuf h_in, h_out;      // rbq_search_batch: staging of one sub-batch
@@ -347,6 +348,7 @@ struct Options {
     bool tie_log = true;      // k_scan logs the candidates it refines; a tied query replays the log (scan.hpp)
     int latency_path = 1;     // small calls (see kLatMaxQueries) take the latency-first front (latency.hpp); 0 = never
     int rank_tile = 0;        // tile of the split-bf16 ranking GEMM (0 = by problem size)
+    int rank_f16 = -1;        // one-product f16 ranking GEMM: -1 = by rule (big or wide calls at D >= 256), 0 = never, 1 = whenever possible
     bool rank_planar = false; // TEST ONLY: the split-bf16 ranking GEMM reads planar copies of its operands (de-interleaved per call)
     uint32_t stage_mask = 0xf; // DIAGNOSTIC: bit s = launch stage s (prep, rank, select, scan); a skipped stage leaves the workspace
                                // of the stream as the last full call wrote it — results are then those of THAT batch (rate probes only)
@@ -367,9 +369,10 @@ struct Replica : Geometry {
     int device = 0;
     uint64_t n_vectors = 0, n_lists = 0, n_blocks = 0;
     Arr rot_blob, centroids, blocks, ids, ex, fadd_ex, fres_ex, list_gb0, list_n, prof, bsum, cnorm2, fallbacks, cent_hl, raw,
-        bsumx, lsum; // ex-factor ranges per block, factor ranges per list (lazy probe selection)
-    Arr* arrays[17] = {&rot_blob, &centroids, &blocks, &ids, &ex, &fadd_ex, &fres_ex, &list_gb0, &list_n, &prof, &bsum, &cnorm2,
-                       &fallbacks, &cent_hl, &raw, &bsumx, &lsum};
+        bsumx, lsum, // ex-factor ranges per block, factor ranges per list (lazy probe selection)
+        cent_f16, cent_f16_resid; // one-product f16 image [nlist][D] of the centroids and |c - f16(c)| per centroid (rank_mfma.hpp header)
+    Arr* arrays[19] = {&rot_blob, &centroids, &blocks, &ids, &ex, &fadd_ex, &fres_ex, &list_gb0, &list_n, &prof, &bsum, &cnorm2,
+                       &fallbacks, &cent_hl, &raw, &bsumx, &lsum, &cent_f16, &cent_f16_resid};
     // reconstruction factors delta / vl of every slot (RBQ1's per-vector arrays that search never reads): kept on the FIRST
     // replica only, for rbq_index_save_rbq1 (not in `arrays`: clone_replica does not copy them)
     Arr delta, vl;
@@ -394,6 +397,10 @@ struct Replica : Geometry {
     Arr mr_slot_map, mr_blk_list;
     bool mr_ready = false;
     float cnorm2_max = 0.0f;
+    // one-product f16 ranking: sqrt(cnorm2_max) and the largest |c - f16(c)|, both rounded up; rank_f16_ok: every stored half is
+    // finite and rc_max <= 2^-11 cnorm_max (else the index ranks on split-bf16 for good)
+    float cnorm_max = 0.0f, rc_max = 0.0f;
+    bool rank_f16_ok = false;
     uint64_t n_raw = 0;      // raw vectors attached for the optional rerank
     bool raw_borrowed = false;
     bool rerank = false;

@@ -116,6 +116,20 @@ int finish_replica(Replica* ix, const std::vector<uint32_t>& ln) {
     double mx = 0;
     for (float v : cn) if (std::isfinite(v)) mx = std::max(mx, (double)v);
     ix->cnorm2_max = (float)(mx * 1.000001); // rounded up
+    {   // one-product f16 image of the centroids, its residuals and the gate of the route (rank_mfma.hpp header)
+        if ((rc = alloc_arr(ix->cent_f16, (size_t)nlist * D * 2))) return rc;
+        if ((rc = alloc_arr(ix->cent_f16_resid, (size_t)nlist * 4))) return rc;
+        HIP_TRY(launch_centroid_f16((const float*)ix->centroids.p, nlist, D, (uint16_t*)ix->cent_f16.p, (float*)ix->cent_f16_resid.p, 0));
+        std::vector<float> rs(nlist);
+        HIP_TRY(hipMemcpy(rs.data(), ix->cent_f16_resid.p, (size_t)nlist * 4, hipMemcpyDeviceToHost));
+        bool finite = true;
+        float rmx = 0.0f;
+        for (float v : rs) { finite = finite && std::isfinite(v); if (v > rmx) rmx = v; } // (the kernel rounded them up)
+        for (float v : cn) finite = finite && std::isfinite(v);
+        ix->rc_max = rmx;
+        ix->cnorm_max = (float)(std::sqrt(mx * 1.000001) * 1.000001);
+        ix->rank_f16_ok = finite && (double)ix->rc_max <= std::ldexp((double)ix->cnorm_max, -11);
+    }
     if ((rc = alloc_arr(ix->lsum, (size_t)nlist * sizeof(BlockSummary)))) return rc;
     if ((rc = alloc_arr(ix->bsumx, ix->n_blocks * sizeof(BlockSummaryEx)))) return rc;
     HIP_TRY(launch_list_summaries((const uint8_t*)ix->blocks.p, (const uint8_t*)ix->ex.p, (const float*)ix->fadd_ex.p,
@@ -144,6 +158,7 @@ int Options::set(const char* name, int v) {
     else if (is("lazy_select")) lazy_select = v != 0;
     else if (is("rank_tile")) rank_tile = v;
     else if (is("rank_planar")) rank_planar = v != 0;
+    else if (is("rank_f16")) rank_f16 = v < 0 ? -1 : (v ? 1 : 0);
     else if (is("latency_path")) latency_path = v;
     else if (is("tie_log")) tie_log = v != 0;
     else if (is("tie_log_cap")) tie_log_cap = v > 0 ? (uint32_t)v : 0u;
@@ -237,7 +252,7 @@ int clone_replica(const Replica* src, int dev, Replica** out) {
     static_cast<Geometry&>(*ix) = *src;
     ix->device = dev;
     ix->n_vectors = src->n_vectors; ix->n_lists = src->n_lists; ix->n_blocks = src->n_blocks;
-    ix->cnorm2_max = src->cnorm2_max; ix->h_list_n = src->h_list_n; ix->nblk_desc_prefix = src->nblk_desc_prefix;
+    ix->cnorm2_max = src->cnorm2_max; ix->cnorm_max = src->cnorm_max; ix->rc_max = src->rc_max; ix->rank_f16_ok = src->rank_f16_ok; ix->h_list_n = src->h_list_n; ix->nblk_desc_prefix = src->nblk_desc_prefix;
     ix->opt = src->opt;
     for (size_t i = 0; i < sizeof(ix->arrays) / sizeof(ix->arrays[0]); ++i) {
         const Arr* s = src->arrays[i];
@@ -745,7 +760,7 @@ int rbq_debug_copy_workspace(rbq_index* h, void* hip_stream, const char* name, v
         {"rot", &Workspace::rot}, {"lut", &Workspace::lut}, {"consts", &Workspace::consts}, {"scores", &Workspace::scores},
         {"probe", &Workspace::probe}, {"nstream", &Workspace::nstream}, {"wl", &Workspace::wl}, {"nvec", &Workspace::nvec},
         {"dead_skipped", &Workspace::dead_skipped}, {"audit_dead", &Workspace::audit_dead}, {"head_ub", &Workspace::head_ub},
-        {"rot_hl", &Workspace::rot_hl}};
+        {"rot_hl", &Workspace::rot_hl}, {"rot_f16", &Workspace::rot_f16}, {"rank_resid", &Workspace::rank_resid}};
     DeviceGuard g(ix->device);
     if (const int plane = hl_plane_of(name, "rot_hi", "rot_lo"); plane >= 0) { // logical view: whole rows of [D] u16
         const size_t row = (size_t)ix->D * 2;
@@ -787,6 +802,8 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
         DeviceGuard g(ix->device);
         return copy_hl_plane(ix->cent_hl.p, ix->n_lists, ix->D, plane, dst);
     }
+    else if (!std::strcmp(name, "cent_f16")) { p = ix->cent_f16.p; have = ix->n_lists * ix->D * 2; }
+    else if (!std::strcmp(name, "cent_f16_resid")) { p = ix->cent_f16_resid.p; have = ix->n_lists * 4; }
     else if (!std::strcmp(name, "cnorm2")) { p = ix->cnorm2.p; have = ix->n_lists * 4; }
     else if (!std::strcmp(name, "delta") || !std::strcmp(name, "vl")) { // (first replica only)
         ix = h->reps[0];

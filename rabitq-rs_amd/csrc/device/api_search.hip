@@ -192,6 +192,17 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
     }
     const bool lat_front = ix->opt.latency_path && nq <= kLatMaxQueries && ix->rotator != 0 && !ix->opt.wg_prep && !ix->opt.exact_rank && !big_nprobe &&
                            !ix->opt.f32_rank && (uint64_t)nlist * D * 4 * nq <= kLatMaxBytes && D % 16 == 0 && smask == 0xfu;
+    // one-product f16 ranking (rank_mfma.hpp header, "ONE f16 PRODUCT").  Possible: the index qualifies, the call ranks on the split GEMM
+    // without split-K, planar copies or the exact front.  By rule (rank_f16 = -1): on top of that no forced tile, a big or wide call (the
+    // GEMM is a stage worth routing) and D >= 256.
+    const uint64_t tiles128 = (uint64_t)((nlist + 127) / 128) * ((nq + 127) / 128), tiles256 = (uint64_t)((nlist + 255) / 256) * ((nq + 127) / 128);
+    const bool f16_possible = ix->rank_f16_ok && split_rank && ksplit == 1 && !ix->opt.rank_planar && !big_nprobe && !lat_front;
+    const bool rank_f16 = ix->opt.rank_f16 != 0 && f16_possible &&
+                          (ix->opt.rank_f16 > 0 || (ix->opt.rank_tile == 0 && (tiles128 >= 192 || tiles256 >= 2048) && D >= 256));
+    if (rank_f16) {
+        if ((rc = w->rot_f16.ensure(nq * D * 2))) return rc;
+        if ((rc = w->rank_resid.ensure(nq * 4))) return rc;
+    }
     if (lat_front) {
         ProfScope ps(ix, 0, stream);
         const PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq);
@@ -203,6 +214,7 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
         ProfScope ps(ix, 0, stream);
         PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq);
         p.rot_hl = split_rank ? (uint16_t*)w->rot_hl.p : nullptr;
+        if (rank_f16) { p.rot_hl = (uint16_t*)w->rot_f16.p; p.rank_resid = (float*)w->rank_resid.p; }
         p.wg_prep = ix->opt.wg_prep;
         // batches a caller waits for (a few hundred queries: the chip is not full): a workgroup per query — the serial sums on one
         // wave while the others build the LUT (latency.hpp, preparation only); full batches keep one wave per query (k_prep_wave)
@@ -220,6 +232,7 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
     rp.cent = (const float*)ix->centroids.p; rp.cent_hi = (const uint16_t*)ix->cent_hl.p; rp.cent_lo = nullptr; rp.cent_hl = true;
     rp.consts = (const QueryConsts*)w->consts.p; rp.cnorm2 = (const float*)ix->cnorm2.p; rp.nq = (uint32_t)nq; rp.nlist = nlist; rp.D = D;
     rp.scores = (float*)w->scores.p; rp.split = split_rank; rp.ksplit = ksplit;
+    if (rank_f16) { rp.f16 = true; rp.rot_hi = (const uint16_t*)w->rot_f16.p; rp.cent_hi = (const uint16_t*)ix->cent_f16.p; }
     rp.big = (uint64_t)((nlist + 127) / 128) * ((nq + 127) / 128) >= 192; // enough 128x128 tiles to fill the chip
     // option rank_tile: 0 = by problem size, 64 / 128 / 256 = forced (tests; A/B)
     rp.wide = ix->opt.rank_tile == 256 || (ix->opt.rank_tile == 0 && (uint64_t)((nlist + 255) / 256) * ((nq + 127) / 128) >= 2048);
@@ -228,6 +241,7 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
     SelectParams sp;
     sp.scores = (float*)w->scores.p; sp.nq = (uint32_t)nq; sp.nlist = nlist; sp.nprobe = nprobe; sp.metric = ix->metric;
     sp.rot = (const float*)w->rot.p; sp.cent = (const float*)ix->centroids.p; sp.D = D; sp.consts = (const QueryConsts*)w->consts.p;
+    if (rank_f16) { sp.rank_resid = (const float*)w->rank_resid.p; sp.cnorm_max = ix->cnorm_max; sp.rc_max = ix->rc_max; }
     sp.cnorm2_max = ix->cnorm2_max; sp.list_gb0 = (const uint32_t*)ix->list_gb0.p; sp.list_n = (const uint32_t*)ix->list_n.p;
     sp.probe = (ProbeInfo*)w->probe.p; sp.wl = (StreamItem*)w->wl.p; sp.wl_stride = wl_stride; sp.nstream = (uint32_t*)w->nstream.p;
     sp.nvec = (unsigned long long*)w->nvec.p; sp.prof_total = prof; sp.fallback_count = (unsigned int*)ix->fallbacks.p;
@@ -607,7 +621,8 @@ int rbq_search_batch(const rbq_index* ch, const float* queries, uint64_t nq, uin
 
 // Which kernel instantiation each of the four stages launches for a call of this shape, and what it occupies.
 // out[stage][6] = workgroups, threads per workgroup, VGPRs per lane, LDS bytes per workgroup (static + dynamic), scratch bytes per
-// lane, 0; stages in the order prep, rank, select, scan.  Nothing is launched.
+// lane, operand format (rank: kRankOps* — 1 split-bf16, 2 one f16 product, 3 f32; else 0); stages in the order prep, rank, select, scan.
+// Nothing is launched.
 int rbq_debug_stage_resources(rbq_index* h, uint64_t nq, uint32_t top_k, uint32_t nprobe, uint32_t* out) {
     g_err.clear();
     RBQ_GUARD_BEGIN
@@ -632,12 +647,13 @@ int rbq_debug_stage_resources(rbq_index* h, uint64_t nq, uint32_t top_k, uint32_
         if (!k.fn) { // a stage this call shape does not launch (the latency-first front of a small call covers prep AND rank): zeros
             if (st != 1) return fail(RBQ_DEVICE, "stage was not probed");
             for (int j = 0; j < 6; ++j) o[j] = 0;
+            o[5] = kRankOpsF32; // (the front's exact scores)
             continue;
         }
         HIP_TRY(hipFuncGetAttributes(&fa, k.fn));
         o[0] = k.grid_x * (k.grid_y ? k.grid_y : 1u) * (k.grid_z ? k.grid_z : 1u); // (z: the parts of a split-K GEMM)
         o[1] = k.block; o[2] = (uint32_t)fa.numRegs;
-        o[3] = (uint32_t)(fa.sharedSizeBytes + k.dyn_lds); o[4] = (uint32_t)fa.localSizeBytes; o[5] = 0;
+        o[3] = (uint32_t)(fa.sharedSizeBytes + k.dyn_lds); o[4] = (uint32_t)fa.localSizeBytes; o[5] = k.operands;
     }
     return RBQ_OK;
     RBQ_GUARD_END

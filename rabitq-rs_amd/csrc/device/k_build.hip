@@ -111,6 +111,10 @@ hipError_t launch_centroid_arrays(const float* cent, uint32_t nlist, uint32_t D,
     hipLaunchKernelGGL(k_centroid_arrays, dim3((nlist + 3) / 4), dim3(256), 0, s, cent, nlist, D, cnorm2, hl);
     return hipGetLastError();
 }
+hipError_t launch_centroid_f16(const float* cent, uint32_t nlist, uint32_t D, uint16_t* img, float* resid, hipStream_t s) {
+    hipLaunchKernelGGL(k_centroid_f16, dim3((nlist + 3) / 4), dim3(256), 0, s, cent, nlist, D, img, resid);
+    return hipGetLastError();
+}
 
 hipError_t launch_hl_planes(const uint16_t* hl, uint64_t rows, uint32_t D, uint16_t* hi, uint16_t* lo, hipStream_t s) {
     if (!rows) return hipSuccess;

@@ -24,7 +24,7 @@ hipError_t launch_prep(const PrepParams& p, int device, hipStream_t s) {
         hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_prep), lds, device);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_prep, dim3(p.nq), dim3(kThreads), lds, s, p.queries, p.dim, p.D, p.Dc, p.rotator, p.rot_blob, p.trunc,
-                           p.fac, p.ex_bits, p.rot, p.lut, p.consts, p.rot_hl);
+                           p.fac, p.ex_bits, p.rot, p.lut, p.consts, p.rot_hl, p.rank_resid);
     } else { // FHT-Kac / identity: one wave per query
         static LdsAttrCache attr;
         const uint32_t qpw = kThreads / 64;
@@ -33,7 +33,7 @@ hipError_t launch_prep(const PrepParams& p, int device, hipStream_t s) {
         hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_prep_wave), lds, device); // 66.5 KB at D = 2048
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_prep_wave, dim3((p.nq + qpw - 1) / qpw), dim3(kThreads), lds, s, p.queries, p.nq, p.dim, p.D, p.Dc,
-                           p.rotator, p.rot_blob, p.trunc, p.fac, p.ex_bits, p.rot, p.lut, p.consts, p.rot_hl);
+                           p.rotator, p.rot_blob, p.trunc, p.fac, p.ex_bits, p.rot, p.lut, p.consts, p.rot_hl, p.rank_resid);
     }
     return hipGetLastError();
 }
@@ -45,7 +45,7 @@ hipError_t launch_lat_front(const PrepParams& p, const RankParams& r, int device
     P.queries = p.queries; P.nq = p.nq; P.dim = p.dim; P.D = p.D; P.Dc = p.Dc; P.rotator = p.rotator; P.rot_blob = p.rot_blob;
     P.trunc = p.trunc; P.fac = p.fac; P.ex_bits = p.ex_bits; P.rot = p.rot; P.lut = p.lut; P.consts = p.consts;
     P.cent = r.cent; P.nlist = r.nlist; P.metric = r.metric; P.scores = r.scores;
-    P.rot_hl = p.rot_hl; P.scorers = (r.scores && !r.ksplit) ? (r.nlist + kLatLists - 1) / kLatLists : 0u;
+    P.rot_hl = p.rot_hl; P.rank_resid = p.rank_resid; P.scorers = (r.scores && !r.ksplit) ? (r.nlist + kLatLists - 1) / kLatLists : 0u;
     P.zero_scores = r.ksplit > 1 ? r.scores : nullptr; // (split-K ranking GEMM behind this preparation: its parts are added to a zeroed row)
     const dim3 grid(lat_front_grid(P.scorers, p.nq));
     const size_t lds = (size_t)p.D * 4 * 2 + p.D / 2;
@@ -58,7 +58,7 @@ hipError_t launch_lat_front(const PrepParams& p, const RankParams& r, int device
 
 hipError_t launch_rank_exact(const RankParams& p, hipStream_t s) {
     dim3 grid((p.nlist + 31) / 32, (p.nq + 31) / 32);
-    if (probe_stage(1, p.metric == 0 ? reinterpret_cast<const void*>(&k_rank_scores<0>) : reinterpret_cast<const void*>(&k_rank_scores<1>), grid, kThreads, 0)) return hipSuccess;
+    if (probe_stage(1, p.metric == 0 ? reinterpret_cast<const void*>(&k_rank_scores<0>) : reinterpret_cast<const void*>(&k_rank_scores<1>), grid, kThreads, 0, kRankOpsF32)) return hipSuccess;
     if (p.metric == 0) hipLaunchKernelGGL(k_rank_scores<0>, grid, dim3(kThreads), 0, s, p.rot, p.cent, p.nq, p.nlist, p.D, p.scores);
     else hipLaunchKernelGGL(k_rank_scores<1>, grid, dim3(kThreads), 0, s, p.rot, p.cent, p.nq, p.nlist, p.D, p.scores);
     return hipGetLastError();
@@ -71,7 +71,7 @@ template <int M, int TM, int TN, int WM, int WN>
 hipError_t launch_rank_split(const RankParams& p, dim3 grid, int device, hipStream_t s) {
     static LdsAttrCache attr;
     const size_t lds = (size_t)(2 * 32 * TM * WM + 2 * 32 * TN * WN) * 80 * 2; // two slabs of 32, rows of 80 B
-    if (probe_stage(1, reinterpret_cast<const void*>(&k_rank_bf16_db<M, TM, TN, WM, WN>), grid, 64 * WM * WN, lds)) return hipSuccess;
+    if (probe_stage(1, reinterpret_cast<const void*>(&k_rank_bf16_db<M, TM, TN, WM, WN>), grid, 64 * WM * WN, lds, kRankOpsBf16x3)) return hipSuccess;
     hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_rank_bf16_db<M, TM, TN, WM, WN>), lds, device);
     if (e != hipSuccess) return e;
     // operands: planar (two planes, rows of 2 D bytes, slabs of 64) or interleaved (one image at *_hi: the lo plane 64 bytes behind the hi
@@ -85,9 +85,21 @@ hipError_t launch_rank_split(const RankParams& p, dim3 grid, int device, hipStre
                        p.D, p.scores);
     return hipGetLastError();
 }
+// the one-product f16 form of the same tiles (k_rank_f16_db): two slabs of 64, rows of 144 B
+template <int M, int TM, int TN, int WM, int WN>
+hipError_t launch_rank_f16(const RankParams& p, dim3 grid, int device, hipStream_t s) {
+    static LdsAttrCache attr;
+    const size_t lds = (size_t)(32 * TM * WM + 32 * TN * WN) * 144 * 2;
+    if (probe_stage(1, reinterpret_cast<const void*>(&k_rank_f16_db<M, TM, TN, WM, WN>), grid, 64 * WM * WN, lds, kRankOpsF16)) return hipSuccess;
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_rank_f16_db<M, TM, TN, WM, WN>), lds, device);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_rank_f16_db<M, TM, TN, WM, WN>), grid, dim3(64 * WM * WN), lds, s, reinterpret_cast<const unsigned char*>(p.rot_hi),
+                       reinterpret_cast<const unsigned char*>(p.cent_hi), p.consts, p.cnorm2, p.nq, p.nlist, p.D, p.scores);
+    return hipGetLastError();
+}
 template <int M, int TW>
 hipError_t launch_rank_f32(const RankParams& p, dim3 grid, hipStream_t s) {
-    if (probe_stage(1, reinterpret_cast<const void*>(&k_rank_mfma<M, TW>), grid, 256, 0)) return hipSuccess;
+    if (probe_stage(1, reinterpret_cast<const void*>(&k_rank_mfma<M, TW>), grid, 256, 0, kRankOpsF32)) return hipSuccess;
     hipLaunchKernelGGL((k_rank_mfma<M, TW>), grid, dim3(256), 0, s, p.rot, p.cent, p.consts, p.cnorm2, p.nq, p.nlist, p.D, p.scores);
     return hipGetLastError();
 }
@@ -98,10 +110,15 @@ hipError_t launch_rank_gemm(const RankParams& p, int device, hipStream_t s) {
         // very large problems (cfg5: 16 384 x 65 536): 128 x 256 tiles, each wave a 64 x 64 sub-tile — 8 LDS fragment reads per 12 MFMAs
         // instead of 6 per 6, one workgroup (123 KB of LDS) per compute unit
         dim3 grid((p.nlist + 255) / 256, (p.nq + 127) / 128);
+        if (p.f16) return p.metric == 0 ? launch_rank_f16<0, 2, 2, 2, 4>(p, grid, device, s) : launch_rank_f16<1, 2, 2, 2, 4>(p, grid, device, s);
         return p.metric == 0 ? launch_rank_split<0, 2, 2, 2, 4>(p, grid, device, s) : launch_rank_split<1, 2, 2, 2, 4>(p, grid, device, s);
     }
     const uint32_t T = p.big ? 128u : 64u;
     dim3 grid((p.nlist + T - 1) / T, (p.nq + T - 1) / T, p.split && p.ksplit > 1 ? p.ksplit : 1u); // (z: split-K, the row zeroed by the preparation)
+    if (p.split && p.f16) {
+        if (p.metric == 0) return p.big ? launch_rank_f16<0, 2, 1, 2, 4>(p, grid, device, s) : launch_rank_f16<0, 1, 1, 2, 2>(p, grid, device, s);
+        return p.big ? launch_rank_f16<1, 2, 1, 2, 4>(p, grid, device, s) : launch_rank_f16<1, 1, 1, 2, 2>(p, grid, device, s);
+    }
     if (p.split) {
         if (p.metric == 0) return p.big ? launch_rank_split<0, 2, 1, 2, 4>(p, grid, device, s) : launch_rank_split<0, 1, 1, 2, 2>(p, grid, device, s);
         return p.big ? launch_rank_split<1, 2, 1, 2, 4>(p, grid, device, s) : launch_rank_split<1, 1, 1, 2, 2>(p, grid, device, s);

@@ -38,6 +38,7 @@ struct LatFrontParams {
     int metric;
     float* scores;        // [nq][nlist] exact canonical scores (L2: squared distance; IP: dot)
     uint16_t* rot_hl;     // null, or the split-bf16 image of the rotated query, hi | lo per K slab (the ranking GEMM's operand: `scorers` = 0)
+    float* rank_resid;    // non-null (the one-product f16 route): rot_hl receives the f16 image [nq][D] and rank_resid[q] = |q - f16(q)|
     float* zero_scores;   // null, or the score rows [nq][nlist] to clear (a split-K ranking GEMM adds its parts to them)
     uint32_t scorers;     // G = ceil(nlist / 32) scoring workgroups per query, or 0: preparation only, the ranking GEMM follows (medium
                           // batches: a workgroup per query finishes a query's preparation in ~2/3 of the time one wave of k_prep_wave needs)
@@ -55,6 +56,7 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
     __shared__ int s_kmin, s_kmax;
     __shared__ unsigned int s_amin, s_amax;
     __shared__ float s_sum, s_n2, s_sp, s_sn;
+    __shared__ double s_rr[kThreads / 64]; // (one-product f16 route) squared residual of the image, per wave
     const uint32_t D = P.D, Dc = P.Dc, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t G = P.scorers;
     uint32_t q = blockIdx.x, g = 0;
@@ -146,16 +148,26 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
 #ifdef RBQ_PREP_STAMPS
     const unsigned long long pt1 = __builtin_amdgcn_s_memtime();
 #endif
+    double rr = 0.0;
     for (uint32_t i = tid; i < D; i += kThreads) {
         const float v = x[i];
         x2[i] = v * v;
         P.rot[(size_t)q * D + i] = v;
-        if (P.rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
+        if (P.rank_resid) { // one-product f16 image [nq][D] for k_rank_f16_db and its residual
+            float r;
+            P.rot_hl[(size_t)q * D + i] = f16_image(v, r);
+            rr += (double)r * (double)r;
+        } else if (P.rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
             uint16_t h, l;
             bf16_split(v, h, l);
             P.rot_hl[(size_t)q * 2 * D + hl_offset(i, 0, D)] = h;
             P.rot_hl[(size_t)q * 2 * D + hl_offset(i, 1, D)] = l;
         }
+    }
+    if (P.rank_resid) { // (uniform) per-wave sums now, their total behind the barrier below
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) rr += __shfl_xor(rr, d, 64);
+        if (lane == 0) s_rr[wave] = rr;
     }
     if (P.zero_scores) { // (the row a split-K ranking GEMM adds its parts to)
         float* zr = P.zero_scores + (size_t)q * P.nlist;
@@ -164,6 +176,7 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
     }
     if (tid == 0) { s_kmin = 0x7fffffff; s_kmax = (int)0x80000000; s_amin = 0; s_amax = 0; }
     __syncthreads();
+    if (P.rank_resid && tid == 0) P.rank_resid[q] = f16_resid_norm(s_rr, kThreads / 64);
     const uint32_t ncb = D / 4;
     if (wave == 0) {
         // sums of the positive / negative elements (ex_dot_range), k_prep_wave's order: strided per lane, xor tree

@@ -40,12 +40,15 @@ struct LdsAttrCache {
 
 // Launch probe (diagnostic: rbq_debug_stage_resources).  While the calling thread has a probe installed, the four stage
 // launchers record WHICH kernel instantiation they would launch, and its geometry, instead of launching it.
-struct KernelProbe { const void* fn = nullptr; uint32_t grid_x = 0, grid_y = 0, grid_z = 0, block = 0; size_t dyn_lds = 0; };
+struct KernelProbe { const void* fn = nullptr; uint32_t grid_x = 0, grid_y = 0, grid_z = 0, block = 0; size_t dyn_lds = 0;
+                     uint32_t operands = 0; }; // (rank stage) what the GEMM multiplies: kRankOps*
+constexpr uint32_t kRankOpsBf16x3 = 1, kRankOpsF16 = 2, kRankOpsF32 = 3;
 struct StageProbes { KernelProbe k[4]; }; // prep, rank, select, scan
 StageProbes*& stage_probes(); // this thread's probe (null: launch normally)
-inline bool probe_stage(int stage, const void* fn, dim3 grid, uint32_t block, size_t lds) {
+inline bool probe_stage(int stage, const void* fn, dim3 grid, uint32_t block, size_t lds, uint32_t operands = 0) {
     StageProbes* p = stage_probes();
     if (!p) return false;
+    p->k[stage].operands = operands;
     p->k[stage].fn = fn; p->k[stage].grid_x = grid.x; p->k[stage].grid_y = grid.y; p->k[stage].grid_z = grid.z;
     p->k[stage].block = block; p->k[stage].dyn_lds = lds;
     return true;
@@ -63,6 +66,8 @@ struct PrepParams {
     uint8_t* lut;        // [nq][4Dc]
     QueryConsts* consts; // [nq]
     uint16_t* rot_hl;    // split-bf16 image [nq][2 D] (hi | lo per K slab, hl_layout.hpp) or null
+    float* rank_resid = nullptr; // non-null (the one-product f16 route): rot_hl receives the f16 image [nq][D] instead and
+                                 // rank_resid[q] = |q - f16(q)|, rounded up
     bool wg_prep;        // one workgroup per query (always for the matrix rotator)
 };
 hipError_t launch_prep(const PrepParams& p, int device, hipStream_t s);
@@ -83,6 +88,7 @@ struct RankParams {
     bool split;    // split-bf16 MFMA GEMM (else f32 MFMA)
     bool big;      // 128x128 tiles
     bool wide;     // 128x256 tiles (split-bf16 only): problems of at least 2048 such tiles
+    bool f16 = false; // one-product f16 GEMM (k_rank_f16_db): rot_hi / cent_hi are the f16 images [rows][D]; needs split, ksplit <= 1
     uint32_t ksplit = 0; // > 1: split-K over grid.z (split-bf16, 64 / 128 tiles): parts added atomically to a row the preparation zeroed
 };
 hipError_t launch_rank_exact(const RankParams& p, hipStream_t s);
@@ -102,6 +108,8 @@ struct SelectParams {
     uint32_t D;
     const QueryConsts* consts;
     float cnorm2_max;
+    const float* rank_resid = nullptr; // non-null: the scores come from the one-product f16 GEMM — [nq] |q - f16(q)|, and
+    float cnorm_max = 0.0f, rc_max = 0.0f; // sqrt(cnorm2_max) and the largest |c - f16(c)|, both rounded up (eps: rank_mfma.hpp header)
     const uint32_t *list_gb0, *list_n;
     ProbeInfo* probe;
     StreamItem* wl;
@@ -221,6 +229,8 @@ hipError_t launch_spread_f32(const float* src, const uint64_t* block_dense0, con
                              float* dst, hipStream_t s);
 // centroid-derived arrays: squared norms (f64 accumulate, as the host did) and the split-bf16 image
 hipError_t launch_centroid_arrays(const float* cent, uint32_t nlist, uint32_t D, float* cnorm2, uint16_t* hl, hipStream_t s);
+// the one-product f16 image [nlist][D] of the centroids and |c - f16(c)| per centroid, rounded up (relayout.hpp)
+hipError_t launch_centroid_f16(const float* cent, uint32_t nlist, uint32_t D, uint16_t* img, float* resid, hipStream_t s);
 // the planar hi / lo planes [rows][D] of an interleaved split-bf16 image [rows][2 D] (hl_layout.hpp): debug option rank_planar
 hipError_t launch_hl_planes(const uint16_t* hl, uint64_t rows, uint32_t D, uint16_t* hi, uint16_t* lo, hipStream_t s);
 // exact re-scoring of the returned ids against caller-supplied raw vectors (optional rerank, default off)

@@ -19,13 +19,22 @@ __device__ __forceinline__ void ex_dot_range(float sum_pos, float sum_neg, uint3
     hi = cmax * sum_pos + slack;
 }
 
+// |q - f16(q)| of a query image from n partial sums of its squared element residuals (f64: the squares are exact, the sum is good to
+// 2^-53 per term), the root rounded up; not finite when the image is not
+__device__ __forceinline__ float f16_resid_norm(const double* part, int n) {
+    double a = 0.0;
+    for (int i = 0; i < n; ++i) a += part[i];
+    return (float)(sqrt(a) * 1.000001);
+}
+
 __global__ __launch_bounds__(kThreads) void k_prep(const float* __restrict__ queries, uint32_t dim, uint32_t D,
                                                    uint32_t Dc, int rotator, const uint8_t* __restrict__ rot_blob,
                                                    uint32_t trunc, float fac, uint32_t ex_bits,
                                                    float* __restrict__ rot_out, uint8_t* __restrict__ lut_out,
                                                    QueryConsts* __restrict__ consts,
-                                                   uint16_t* __restrict__ rot_hl) {
+                                                   uint16_t* __restrict__ rot_hl, float* __restrict__ rank_resid) {
     extern __shared__ __align__(16) float sm[];
+    __shared__ double s_rr[kThreads / 64]; // (one-product f16 route) squared residual of the image, per wave
     float* x = sm;         // [D]
     float* y = sm + D;     // [D] (matrix rotator input)
     __shared__ int s_kmin, s_kmax;
@@ -39,14 +48,24 @@ __global__ __launch_bounds__(kThreads) void k_prep(const float* __restrict__ que
 
     rotate_into_lds<kThreads>(x, y, qin, dim, D, rotator, rot_blob, trunc, fac, tid);
 
+    double rr = 0.0;
     for (uint32_t i = tid; i < D; i += kThreads) {
         rot_out[(size_t)q * D + i] = x[i];
-        if (rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
+        if (rank_resid) { // one-product f16 image [nq][D] for k_rank_f16_db and its residual
+            float r;
+            rot_hl[(size_t)q * D + i] = f16_image(x[i], r);
+            rr += (double)r * (double)r;
+        } else if (rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
             uint16_t h, l;
             bf16_split(x[i], h, l);
             rot_hl[(size_t)q * 2 * D + hl_offset(i, 0, D)] = h;
             rot_hl[(size_t)q * 2 * D + hl_offset(i, 1, D)] = l;
         }
+    }
+    if (rank_resid) { // (uniform) per-wave sums now, their total behind the barrier below
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) rr += __shfl_xor(rr, d, 64);
+        if ((tid & 63u) == 0) s_rr[tid >> 6] = rr;
     }
 
 #ifdef RBQ_PREP_STAMPS
@@ -76,6 +95,7 @@ __global__ __launch_bounds__(kThreads) void k_prep(const float* __restrict__ que
         s_pos = sp; s_neg = sn;
     }
     __syncthreads();
+    if (rank_resid && tid == 0) rank_resid[q] = f16_resid_norm(s_rr, kThreads / 64);
 
 #ifdef RBQ_PREP_STAMPS
     const unsigned long long pt2 = __builtin_amdgcn_s_memtime();
@@ -357,7 +377,7 @@ __global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict_
                                                         uint32_t trunc, float fac, uint32_t ex_bits,
                                                         float* __restrict__ rot_out, uint8_t* __restrict__ lut_out,
                                                         QueryConsts* __restrict__ consts,
-                                                        uint16_t* __restrict__ rot_hl) {
+                                                        uint16_t* __restrict__ rot_hl, float* __restrict__ rank_resid) {
     extern __shared__ __align__(16) float sm[];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t q = blockIdx.x * (kThreads / 64) + wave;
@@ -393,18 +413,28 @@ __global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict_
     }
 
     float sp = 0.0f, sn = 0.0f; // sums of the positive / negative elements (ex_dot_range)
+    double rr = 0.0;            // (one-product f16 route) squared residual of the image
     for (uint32_t i = lane; i < D; i += 64) {
         const float v = x[i];
         x2[i] = v * v;
         sp += fmaxf(v, 0.0f);
         sn += fminf(v, 0.0f);
         rot_out[(size_t)q * D + i] = v;
-        if (rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
+        if (rank_resid) { // one-product f16 image [nq][D] for k_rank_f16_db and its residual
+            float r;
+            rot_hl[(size_t)q * D + i] = f16_image(v, r);
+            rr += (double)r * (double)r;
+        } else if (rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
             uint16_t h, l;
             bf16_split(v, h, l);
             rot_hl[(size_t)q * 2 * D + hl_offset(i, 0, D)] = h;
             rot_hl[(size_t)q * 2 * D + hl_offset(i, 1, D)] = l;
         }
+    }
+    if (rank_resid) { // (uniform)
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) rr += __shfl_xor(rr, d, 64);
+        if (lane == 0) rank_resid[q] = f16_resid_norm(&rr, 1);
     }
     group_sync<64>();
 #ifdef RBQ_PREP_STAMPS

@@ -20,6 +20,23 @@
 // Any true top-nprobe member has canonical <= (largest canonical among the approximate top-nprobe) <= tau+eps,
 // hence A <= tau + 2 eps: it is in the shortlist.  If the shortlist overflows its LDS capacity (many
 // near-equal scores) or a score is not finite, the query falls back to canonical scores for ALL lists.
+//
+// ONE f16 PRODUCT (k_rank_f16_db; api_search.hip decides per call).  Both operands are rounded once to f16, xh = f16(x) to nearest
+// even with every result below 2^-14 stored as a signed zero (types.hpp, f16_rne_flush), and q.c ~ qh.ch on
+// v_mfma_f32_32x32x16_f16: n exact products (11 x 11 significant bits, exponents within f32's range) instead of 3n, f32 accumulate.
+//   residuals  xl := x - xh is EXACT in f32: a stored normal half lies within a factor 2 of x (Sterbenz), a flushed one is 0 and
+//              leaves x itself, so the flush is simply part of xl.  |ql| is measured per query by the preparation kernel, |cl| per
+//              centroid when the index is made — squares and sums in f64, roots rounded up — from the bits actually stored.
+//              Nothing is assumed about the data's range.
+//   split      q.c - qh.ch = ql.c + qh.cl, so |q.c - qh.ch| <= |ql||c| + |qh||cl| (Cauchy-Schwarz), and |qh| <= |q| + |ql|.
+//   sum        n products: 2 gamma_{n+2} (sum|qh_i||ch_i| <= (|qh|^2+|ch|^2)/2) plus the norm terms stays below
+//              (4/3) n u (|q|^2+|c|^2) (1 + 2^-10)^2 even if the MFMA adder truncates (u -> 2u) — well inside the 4 n u the
+//              split-bf16 form already takes of the 6 n u.  No split-K on this route; the + 16 u allowance stays.
+//   eps      = ((6 n + 16) u (|q|^2 + max|c|^2) + 2.01 (|ql| max|c| + (|q| + |ql|) max|cl|)) * 1.001
+//              (2 x the split term for the L2 score's -2 q.c; .01 and .001: the f32 evaluation of this very expression.)
+// The route needs every stored centroid half finite and max|cl| <= 2^-11 max|c| (an index whose centroids lose more than f16's
+// relative rounding error to the flush stays on split-bf16); a query whose image is not finite has |ql| and eps not finite and
+// takes the fallback.  At D = 960 on unit-scale data eps is about twice the split-bf16 one.
 #pragma once
 #include "kernels.hpp"
 
@@ -322,6 +339,130 @@ __global__ __launch_bounds__(64 * WM * WN) void k_rank_bf16_db(const unsigned ch
                     if (gridDim.z == 1) scores[(size_t)qi * nlist + c] = METRIC == 0 ? fmaf(-2.0f, dot, qn[a][r] + cn) : dot;
                     else atomicAdd(&scores[(size_t)qi * nlist + c], METRIC == 0 ? (blockIdx.z == 0 ? fmaf(-2.0f, dot, qn[a][r] + cn) : -2.0f * dot) : dot);
                 }
+            }
+        }
+}
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// One-product f16 GEMM (header: "ONE f16 PRODUCT"): the structure of k_rank_bf16_db — same tiles, double-buffered LDS, one barrier per
+// slab, same epilogue — on ONE image per operand, [rows][D] f16, with K slabs of 64: a slab of a row is one aligned 128-byte line.
+//   loads  eight consecutive lanes fetch the eight 16-byte segments of one row's line, so a wave-level load covers 8 rows x 128 bytes,
+//          whole lines, and the same eight lanes store them with one ds_write_b128 group: 128 consecutive bytes, 32 distinct banks.
+//   LDS    rows of 144 bytes (128 + 16): 9 slots of 16 bytes, odd, so the 16 rows of a ds_read_b128 lane group ({0-3, 12-15, 20-27}
+//          and its likes: 16 distinct residues mod 16) fall on 16 distinct 4-bank sets of the 64 banks — conflict-free.
+//          dynamic LDS: 2 x { A [BM][144 B] | B [BN][144 B] }
+//   K loop four 16-wide steps per slab on two alternating fragment sets: the LDS reads of step k + 1 are requested before the MFMAs of
+//          step k; the next slab's step 0 is read behind the barrier, under the MFMAs of this slab's step 3.
+// No split-K (gridDim.z == 1).  D % 64 == 0.
+template <int METRIC, int TM, int TN, int WM, int WN>
+__global__ __launch_bounds__(64 * WM * WN) void k_rank_f16_db(const unsigned char* __restrict__ a, const unsigned char* __restrict__ b,
+                                                     const QueryConsts* __restrict__ consts, const float* __restrict__ cnorm2,
+                                                     uint32_t nq, uint32_t nlist, uint32_t D, float* __restrict__ scores) {
+    constexpr int NT = 64 * WM * WN, BM = 32 * TM * WM, BN = 32 * TN * WN, BK = 64, LDB = BK * 2 + 16, SEG = BK / 8;
+    constexpr int NLA = BM * SEG / NT, NLB = BN * SEG / NT; // 16-byte loads per thread and operand
+    constexpr int BUF = (BM + BN) * LDB;
+    static_assert(BM * SEG % NT == 0 && BN * SEG % NT == 0, "tile rows must divide over the threads");
+    extern __shared__ __align__(16) unsigned char smraw[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6, wm = w / WN, wn = w % WN;
+    const uint32_t q0 = blockIdx.y * BM, c0 = blockIdx.x * BN;
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int x = 0; x < TM; ++x)
+#pragma unroll
+        for (int y = 0; y < TN; ++y)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.0f;
+    const unsigned char* ga[NLA];
+    const unsigned char* gb[NLB];
+    uint32_t soa[NLA], sob[NLB];
+    const size_t row_bytes = (size_t)D * 2;
+#pragma unroll
+    for (int i = 0; i < NLA; ++i) { // (rows past the end re-read the last row: their scores are never stored)
+        const uint32_t idx = tid + (uint32_t)NT * i, row = idx / SEG, seg = idx % SEG;
+        const uint32_t ra = q0 + row < nq ? q0 + row : nq - 1u;
+        ga[i] = a + (size_t)ra * row_bytes + seg * 16;
+        soa[i] = row * LDB + seg * 16;
+    }
+#pragma unroll
+    for (int i = 0; i < NLB; ++i) {
+        const uint32_t idx = tid + (uint32_t)NT * i, row = idx / SEG, seg = idx % SEG;
+        const uint32_t rb = c0 + row < nlist ? c0 + row : nlist - 1u;
+        gb[i] = b + (size_t)rb * row_bytes + seg * 16;
+        sob[i] = BM * LDB + row * LDB + seg * 16;
+    }
+    u32x4 pa[NLA], pb[NLB];
+    const uint32_t nslab = D / BK;
+#define RBQ_RANK_FETCH(S)                                                                                              \
+    do {                                                                                                               \
+        const size_t ko = (size_t)(S) * (BK * 2);                                                                      \
+        _Pragma("unroll") for (int i = 0; i < NLA; ++i) pa[i] = *reinterpret_cast<const u32x4*>(ga[i] + ko);           \
+        _Pragma("unroll") for (int i = 0; i < NLB; ++i) pb[i] = *reinterpret_cast<const u32x4*>(gb[i] + ko);           \
+    } while (0)
+#define RBQ_RANK_STORE(B)                                                                                              \
+    do {                                                                                                               \
+        unsigned char* base = smraw + (B) * BUF;                                                                       \
+        _Pragma("unroll") for (int i = 0; i < NLA; ++i) *reinterpret_cast<u32x4*>(base + soa[i]) = pa[i];              \
+        _Pragma("unroll") for (int i = 0; i < NLB; ++i) *reinterpret_cast<u32x4*>(base + sob[i]) = pb[i];              \
+    } while (0)
+    // A/B operand of v_mfma_f32_32x32x16_f16: lane l holds row (l & 31), k = 8 * (l >> 5) .. + 7 of the 16-wide step
+    f16x8 f0a[TM], f0b[TN], f1a[TM], f1b[TN];
+    const uint32_t fo = (lane & 31u) * LDB + (lane >> 5) * 16;
+#define RBQ_RANK_FRAGS(B, KC, FA, FB)                                                                                  \
+    do {                                                                                                               \
+        const unsigned char* sA = smraw + (B) * BUF;                                                                   \
+        const unsigned char* sB = sA + BM * LDB;                                                                       \
+        _Pragma("unroll") for (int x = 0; x < TM; ++x)                                                                 \
+            FA[x] = *reinterpret_cast<const f16x8*>(sA + (wm * 32 * TM + x * 32) * LDB + fo + (KC) * 32);              \
+        _Pragma("unroll") for (int y = 0; y < TN; ++y)                                                                 \
+            FB[y] = *reinterpret_cast<const f16x8*>(sB + (wn * 32 * TN + y * 32) * LDB + fo + (KC) * 32);              \
+    } while (0)
+#define RBQ_RANK_MMA(FA, FB)                                                                                           \
+    _Pragma("unroll") for (int x = 0; x < TM; ++x) _Pragma("unroll") for (int y = 0; y < TN; ++y)                      \
+        acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(FA[x], FB[y], acc[x][y], 0, 0, 0);
+    RBQ_RANK_FETCH(0);
+    RBQ_RANK_STORE(0);
+    if (nslab > 1) RBQ_RANK_FETCH(1);
+    __syncthreads();
+    RBQ_RANK_FRAGS(0, 0, f0a, f0b);
+    for (uint32_t s = 0; s < nslab; ++s) {
+        const uint32_t cur = s & 1u;
+        RBQ_RANK_FRAGS(cur, 1, f1a, f1b);
+        if (s + 1 < nslab) RBQ_RANK_STORE(cur ^ 1u); // (that buffer's last reads were waited for in front of the previous barrier)
+        if (s + 2 < nslab) RBQ_RANK_FETCH(s + 2);
+        RBQ_RANK_MMA(f0a, f0b);
+        RBQ_RANK_FRAGS(cur, 2, f0a, f0b);
+        RBQ_RANK_MMA(f1a, f1b);
+        RBQ_RANK_FRAGS(cur, 3, f1a, f1b);
+        RBQ_RANK_MMA(f0a, f0b);
+        __builtin_amdgcn_sched_barrier(0); // keep these MFMAs in front of the barrier: they cover the reads of step 3
+        __syncthreads();
+        if (s + 1 < nslab) RBQ_RANK_FRAGS(cur ^ 1u, 0, f0a, f0b);
+        RBQ_RANK_MMA(f1a, f1b);
+    }
+#undef RBQ_RANK_FRAGS
+#undef RBQ_RANK_MMA
+#undef RBQ_RANK_FETCH
+#undef RBQ_RANK_STORE
+    // the epilogue of k_rank_bf16_db without its split-K branch
+    float qn[TM][16];
+#pragma unroll
+    for (int x = 0; x < TM; ++x)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const uint32_t qi = q0 + wm * 32 * TM + x * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            qn[x][r] = METRIC == 0 ? consts[qi < nq ? qi : nq - 1u].qnorm2 : 0.0f;
+        }
+#pragma unroll
+    for (int x = 0; x < TM; ++x)
+#pragma unroll
+        for (int y = 0; y < TN; ++y) {
+            const uint32_t c = c0 + wn * 32 * TN + y * 32 + (lane & 31u);
+            const float cn = (METRIC == 0 && c < nlist) ? cnorm2[c] : 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const uint32_t qi = q0 + wm * 32 * TM + x * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (qi < nq && c < nlist) scores[(size_t)qi * nlist + c] = METRIC == 0 ? fmaf(-2.0f, acc[x][y][r], qn[x][r] + cn) : acc[x][y][r];
             }
         }
 }
@@ -1075,7 +1216,12 @@ __global__ RBQ_SEL_BOUNDS void k_select_mfma(const SelectParams P, const SelectG
     const QueryConsts qc = P.consts[q];
     // (+ 16 x 2^-24: up to four split-K parts of the GEMM are added to the row in no fixed order, each addition rounding a sum of
     // magnitude <= 2 (|q|^2 + |c|^2))
-    const float eps = ((6.0f * (float)D + 16.0f) * 5.9604645e-8f + 4.0f * 1.52587890625e-5f) * (qc.qnorm2 + P.cnorm2_max) * 1.001f;
+    float eps = ((6.0f * (float)D + 16.0f) * 5.9604645e-8f + 4.0f * 1.52587890625e-5f) * (qc.qnorm2 + P.cnorm2_max) * 1.001f;
+    if (P.rank_resid) { // scores of the one-product f16 GEMM (header, "ONE f16 PRODUCT"): the measured residuals replace the split's 4 * 2^-16
+        const float rq = P.rank_resid[q];
+        const float qn = sqrtf(qc.qnorm2) * 1.0000002f; // (square roots rounded up; P.cnorm_max and P.rc_max are, by the host)
+        eps = ((6.0f * (float)D + 16.0f) * 5.9604645e-8f * (qc.qnorm2 + P.cnorm2_max) + 2.01f * (rq * P.cnorm_max + (qn + rq) * P.rc_max)) * 1.001f;
+    }
     // ordered key of (the score of `key` moved 2 eps towards worse); 0xffffffff if that is not finite
     auto widen = [&](uint32_t key) -> uint32_t {
         int32_t k = (int32_t)(key ^ 0x80000000u);
@@ -1166,7 +1312,7 @@ __global__ RBQ_SEL_BOUNDS void k_select_mfma(const SelectParams P, const SelectG
                     s_z0 = 0; s_tub = (uint32_t)total_key(INFINITY); s_flag = 0; s_need = 0; s_dead = 0; s_maxh = (uint32_t)total_key(-INFINITY); s_memvec = 0; s_nh = 0; s_nk = 0; }
     if (tid < kSelHead) s_head[tid] = 0xffffffffu;
     __syncthreads();
-    bool fallback = s_bad != 0 || P.force_fallback != 0;
+    bool fallback = s_bad != 0 || P.force_fallback != 0 || !finite_f(eps); // (eps: a query whose f16 image is not finite)
     if (!fallback) {
         uint32_t cle = 0, mab = 0xffffffffu;
         each_key([&](uint32_t i, uint32_t key) {

@@ -119,6 +119,24 @@ __global__ __launch_bounds__(256) void k_centroid_arrays(const float* __restrict
     if (lane == 0) cnorm2[c] = (float)a;
 }
 
+// f16 image [nlist][D] of the rotated centroids (f16_rne_flush) and, per centroid, |c - f16(c)| from the bits stored: exact
+// element residuals, squares and sum in f64, the root rounded up.  Not finite where a stored half is not.
+__global__ __launch_bounds__(256) void k_centroid_f16(const float* __restrict__ cent, uint32_t nlist, uint32_t D,
+                                                      uint16_t* __restrict__ img, float* __restrict__ resid) {
+    const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (c >= nlist) return;
+    const float* row = cent + (size_t)c * D;
+    double a = 0.0;
+    for (uint32_t i = lane; i < D; i += 64) {
+        float r;
+        img[(size_t)c * D + i] = f16_image(row[i], r);
+        a += (double)r * (double)r;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) a += __shfl_xor(a, d, 64);
+    if (lane == 0) resid[c] = (float)(sqrt(a) * 1.000001);
+}
+
 // hi / lo planes of an interleaved split-bf16 image (one thread per element)
 __global__ __launch_bounds__(256) void k_hl_planes(const uint16_t* __restrict__ hl, uint64_t rows, uint32_t D, uint16_t* __restrict__ hi,
                                                    uint16_t* __restrict__ lo) {

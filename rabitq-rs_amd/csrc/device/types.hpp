@@ -88,6 +88,36 @@ __host__ __device__ inline void bf16_split(float x, uint16_t& hi, uint16_t& lo) 
 }
 // (the interleaved image of the two planes that the ranking GEMM reads: hl_layout.hpp, hl_offset)
 
+// One-product f16 operands of the ranking GEMM (k_rank_f16_db): round-to-nearest-even f32 -> f16 bits, and every result below the
+// smallest normal half (2^-14) stored as a signed zero, so that the MFMA never meets a subnormal whatever the denormal mode.
+// Values that round to 2^16 or more become inf, NaN stays NaN.  (|x| in [2^-14 - 2^-25, 2^-14) rounds UP to the smallest normal at
+// the subnormal spacing 2^-24, ties to even: what IEEE conversion followed by the flush gives.)
+__host__ __device__ inline uint16_t f16_rne_flush(float x) {
+    uint32_t u;
+    __builtin_memcpy(&u, &x, 4);
+    const uint32_t sign = (u >> 16) & 0x8000u;
+    u &= 0x7fffffffu;
+    if (u > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);                         // NaN
+    if (u < 0x38800000u) return (uint16_t)(sign | (u >= 0x387fe000u ? 0x0400u : 0u)); // below 2^-14
+    u += 0xfffu + ((u >> 13) & 1u);
+    if (u >= 0x47800000u) return (uint16_t)(sign | 0x7c00u);                        // 2^16 and beyond
+    return (uint16_t)(sign | ((u - 0x38000000u) >> 13));
+}
+__host__ __device__ inline float f16_to_f32(uint16_t h) { // (images only: no subnormal halves)
+    const uint32_t m = h & 0x7fffu;
+    uint32_t u = ((uint32_t)(h & 0x8000u) << 16) | (m >= 0x7c00u ? 0x7f800000u | ((m & 0x3ffu) << 13) : (m ? (m << 13) + 0x38000000u : 0u));
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+}
+// image element and its residual x - f16(x): exact in f32 (a stored normal half is within a factor 2 of x — Sterbenz; a flushed one
+// leaves x itself); not finite when the image is not
+__host__ __device__ inline uint16_t f16_image(float x, float& resid) {
+    const uint16_t h = f16_rne_flush(x);
+    resid = x - f16_to_f32(h);
+    return h;
+}
+
 // ---- k_scan ---------------------------------------------------------------------------------------------------
 struct ScanParams {
     const uint8_t* blocks;   // [n_blocks][4Dc + 384]: lane-major sign codes | f_add[32] | f_rescale[32] | f_error[32]

@@ -705,11 +705,15 @@ class IvfRabitqIndex:
         return {i: n for n, i in _abi.NUMERIC_VARIANTS.items()}[v]
 
     def stage_resources(self, nq, top_k, nprobe):
-        """{stage: {workgroups, threads, vgprs, lds_bytes, scratch_bytes}} of the kernels a call of this shape launches (nothing runs)"""
+        """{stage: {workgroups, threads, vgprs, lds_bytes, scratch_bytes}} of the kernels a call of this shape launches (nothing runs);
+        the rank stage also names its operand format: "operands" is "bf16x3", "f16" or "f32" there"""
         out = np.zeros((4, 6), np.uint32)
         _check(lib().rbq_debug_stage_resources(self._h, nq, top_k, nprobe, out.ctypes.data))
-        return {s: {"workgroups": int(o[0]), "threads": int(o[1]), "vgprs": int(o[2]), "lds_bytes": int(o[3]), "scratch_bytes": int(o[4])}
-                for s, o in zip(("prep", "rank", "select", "scan"), out)}
+        res = {s: {"workgroups": int(o[0]), "threads": int(o[1]), "vgprs": int(o[2]), "lds_bytes": int(o[3]), "scratch_bytes": int(o[4])}
+               for s, o in zip(("prep", "rank", "select", "scan"), out)}
+        # what the ranking stage multiplies: three split-bf16 products, one f16 product, or f32 (the f32 GEMM and the exact scorers)
+        res["rank"]["operands"] = {1: "bf16x3", 2: "f16", 3: "f32"}[int(out[1][5])]
+        return res
 
     def head_exact_stats(self):
         """(queries whose probe selection ran the exact head evaluation, guard trips — must be 0)"""
