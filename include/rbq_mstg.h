@@ -9,7 +9,8 @@
  * Step 1, the hierarchical balanced clustering that yields the centroids (HierarchicalClustering::cluster,
  * src/mstg/clustering.rs), is rbq_mstg_cluster_device.  Step 4 (HNSW over the centroids) is not built: it is not needed for
  * searching through this library.  A header of its own, not included by rbq.h (DESIGN.md sections 15, 16, 17).  Saving and
- * loading the result in the crate's `.mstg` format: rbq_mstg_persist.h (section 18).
+ * loading the result in the crate's `.mstg` format: rbq_mstg_persist.h (section 18).  Appending rows to the result and removing
+ * ids from it without a rebuild: rbq_mstg_mutate.h (section 24).
  */
 #ifndef RBQ_MSTG_H
 #define RBQ_MSTG_H
@@ -19,6 +20,7 @@
 
 #include "rbq.h"
 #include "rbq_mstg_persist.h" /* rbq_mstg_save* / rbq_mstg_load*: the crate's `.mstg` file */
+#include "rbq_mstg_mutate.h"  /* rbq_mstg_append / rbq_mstg_remove_ids: add and remove_ids on the GPU */
 
 #ifdef __cplusplus
 extern "C" {

@@ -20,6 +20,8 @@ Mirrors the reference's public query API for this path:
                                src/mstg/clustering.rs, src/python_bindings.rs (mstg.py)
   save_mstg / load_mstg, MstgIndex.save / load / get_memory_usage: MstgIndex::save_main_index / load_main_index
                                src/mstg/io.rs:129-245 (mstg.py)
+  append_postings / remove_postings, MstgIndex.add / remove_ids / id_bound: no crate counterpart (its MstgIndex is immutable):
+                               FAISS-style add and remove_ids on posting-list handles, equal to a rebuild (mstg.py)
 All compute goes through the C ABI of include/rbq.h (csrc/librbq.so, hand-written HIP for
 gfx950). There is no CPU fallback: if the HIP library is missing or no GPU is present the
 calls raise.
@@ -81,11 +83,12 @@ from .index import IvfRabitqIndex, StreamBuilder  # noqa: E402
 from . import builder  # noqa: E402,F401
 from .bruteforce import BruteForceRabitqIndex, BruteForceSearchParams, BruteForceSearchResult  # noqa: E402
 from .kmeans import KMeansConfig, KMeansResult, run_kmeans_with_config  # noqa: E402
-from .mstg import (MstgIndex, MstgSearchParams, build_postings_on_device, closure_assign, closure_assign_cpu,  # noqa: E402
-                   hierarchical_cluster, hierarchical_cluster_cpu, load_mstg, mstg_search, save_mstg, select_lists_cpu)
+from .mstg import (MstgIndex, MstgSearchParams, append_postings, build_postings_on_device, closure_assign,  # noqa: E402
+                   closure_assign_cpu, hierarchical_cluster, hierarchical_cluster_cpu, load_mstg, mstg_search, remove_postings,
+                   save_mstg, select_lists_cpu)
 
 __all__ = ["Metric", "RotatorType", "RabitqError", "SearchParams", "SearchResult", "IvfRabitqIndex",
            "StreamBuilder", "builder", "BruteForceRabitqIndex", "BruteForceSearchParams", "BruteForceSearchResult",
            "KMeansConfig", "KMeansResult", "run_kmeans_with_config", "closure_assign", "closure_assign_cpu",
            "build_postings_on_device", "MstgSearchParams", "mstg_search", "select_lists_cpu", "hierarchical_cluster",
-           "hierarchical_cluster_cpu", "MstgIndex", "save_mstg", "load_mstg"]
+           "hierarchical_cluster_cpu", "MstgIndex", "save_mstg", "load_mstg", "append_postings", "remove_postings"]

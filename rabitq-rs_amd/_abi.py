@@ -68,3 +68,14 @@ class MstgConfig(C.Structure):
         d = {f: getattr(self, f) for f in MSTG_CONFIG_FIELDS}
         d["faster_config"] = bool(d["faster_config"])
         return d
+
+
+# include/rbq_mstg_mutate.h: (restype, argtypes) of every entry point, argument for argument (index.lib() applies them)
+_VP, _U64, _U32 = C.c_void_p, C.c_uint64, C.c_uint32
+MSTG_MUTATE_PROTOTYPES = {
+    # idx, vectors, count, first_id, closure_epsilon, max_replicas, max_chunk_rows, out_lists, out_counts, out
+    "rbq_mstg_append": (C.c_int, [_VP, _VP, _U64, _U64, C.c_float, _U32, _U64, _VP, _VP, C.POINTER(_VP)]),
+    # idx, ids, n_ids, out_removed, out
+    "rbq_mstg_remove_ids": (C.c_int, [_VP, _VP, _U64, C.POINTER(_U64), C.POINTER(_VP)]),
+    "rbq_debug_mstg_append_passes": (_U64, []),
+}

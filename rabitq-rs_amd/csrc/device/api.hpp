@@ -1,5 +1,5 @@
 // api.hpp — internal header of librbq.so's host side: the C ABI of include/rbq.h over the HIP kernels, which the host
-// units (api_index, api_build, api_append, api_remove, api_search, api_mstg_search, api_save, api_load, api_fetch, api_bf, api_mstg, api_mstg_persist) reach through launch.hpp.  Not installed.
+// units (api_index, api_build, api_append, api_remove, api_search, api_mstg_search, api_save, api_load, api_fetch, api_bf, api_mstg, api_mstg_mutate, api_mstg_persist) reach through launch.hpp.  Not installed.
 // Host responsibilities: validate like the reference (src/ivf.rs:1754-1769,1484-1702), upload the reference's ClusterData
 // bytes and have the GPU re-lay them into the device layout (one-time, at create/load), own HBM on one or N devices
 // (replicas), and enqueue prep -> rank -> select -> scan for each query batch.  There is no CPU compute path: every failure
@@ -29,6 +29,7 @@
 #include "rbq.h"
 #include "launch.hpp"
 #include "../host/rbq_host_logic.hpp"
+#include "../host/rbq_append_plan.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -452,9 +453,13 @@ int build_device_pairs(const rbq_header* hdr, const float* centroids, const floa
 // device-resident rows (ids id_base + row) into the slots their lists' cursors point at, advances the cursors and returns once
 // the device is idle (the scratch, and a caller's staging buffers, may be reused).  d_block_list: the list of every block;
 // d_cursor [n_lists]: vectors each list holds so far; d_chunk_first [n_lists]: scratch.
+// d_pair_row (rbq_mstg_append; null: row j is pair j): the n entries are (row, list) PAIRS in ascending row order, pair j stores row
+// d_pair_row[j] of d_vec in list d_asg[j] under the id id_base + d_pair_row[j]: several slots share one source row and one id.
+// A replica with `rnorm` gets the residual norm of every slot written too.
 struct EncodeScratch { DevBuf vec, assign, ko, vi, vo, tmp, row_src, row_slot, rows, raw, trow; };
 int encode_rows_at_cursors(Replica* ix, EncodeScratch& sc, const float* d_vec, const uint32_t* d_asg, uint32_t n, uint64_t id_base,
-                           bool opt, float t_const, const uint32_t* d_block_list, uint32_t* d_cursor, uint32_t* d_chunk_first);
+                           bool opt, float t_const, const uint32_t* d_block_list, uint32_t* d_cursor, uint32_t* d_chunk_first,
+                           const uint32_t* d_pair_row = nullptr);
 // rows per encode chunk: the 512 MiB budget of the rotated rows
 inline uint64_t encode_chunk_rows(uint32_t D) { return std::max<uint64_t>(1024, ((512ull << 20) / ((size_t)D * 4)) & ~63ull); }
 // block -> list and block -> number of real vectors, on the device
@@ -483,6 +488,20 @@ struct EventPair { // times one launch on the null stream; freed on every exit
         return true;
     }
 };
+
+// What rbq_index_append and rbq_mstg_append share (api_append.hip): the replica of the grown geometry — centroids and rotator bit
+// for bit those of `old`, every array allocated (rnorm too where `old` has it), the old arrays carried over by k_append_carry — and
+// its block tables in `t`.  own.ix is the new replica (freed by `own` on an early return).
+int append_grow(Replica* old, const rbq_host::AppendPlan& plan, Scratch& t, ReplicaOwner& own, uint32_t** d_block_list,
+                uint32_t** d_block_nv);
+// What rbq_index_remove_ids and rbq_mstg_remove_ids share (api_remove.hip): everything after the argument checks.  A handle with
+// `rnorm` (an MSTG handle) has it gathered with the other slot arrays and hands on tc_some / tc_value.
+int remove_ids_core(const rbq_index* idx, const uint64_t* ids, uint64_t n_ids, const std::vector<int>& devs, uint64_t* out_removed,
+                    rbq_index** out);
+// api_mstg.hip: closure_device with the argument's memories detected; `count` adds its fallbacks to rbq_mstg_debug_closure_fallbacks
+int run_closure(ClosureArgs& a, int dev, bool count);
+// 1 + the largest stored id of a handle's first replica, computed once (api_append.hip)
+int id_bound_of(Replica* ix, uint64_t* out);
 
 // shared by the search units (api_search.hip): workspaces from the replica's pool and per caller stream, the stage timer, the scan launch
 Workspace* take_ws(Replica* ix);

@@ -86,21 +86,23 @@ int upload_block_tables(const std::vector<uint32_t>& ln, const std::vector<uint3
 }
 
 int encode_rows_at_cursors(Replica* ix, EncodeScratch& sc, const float* d_vec, const uint32_t* d_asg, uint32_t n, uint64_t id_base,
-                           bool opt, float t_const, const uint32_t* d_block_list, uint32_t* d_cursor, uint32_t* d_chunk_first) {
+                           bool opt, float t_const, const uint32_t* d_block_list, uint32_t* d_cursor, uint32_t* d_chunk_first,
+                           const uint32_t* d_pair_row) {
     const uint32_t D = ix->D, Dc = ix->Dc, dim = ix->dim, nlist = (uint32_t)ix->n_lists;
     unsigned bits = 1;
     while ((1ull << bits) < nlist) ++bits;
     int rc;
-    if ((rc = sc.ko.ensure((size_t)n * 4)) || (rc = sc.vi.ensure((size_t)n * 4)) || (rc = sc.vo.ensure((size_t)n * 4)) ||
+    if ((rc = sc.ko.ensure((size_t)n * 4)) || (!d_pair_row && (rc = sc.vi.ensure((size_t)n * 4))) || (rc = sc.vo.ensure((size_t)n * 4)) ||
         (rc = sc.row_src.ensure((size_t)n * 4)) || (rc = sc.row_slot.ensure((size_t)n * 4)) ||
         (rc = sc.rows.ensure((size_t)n * D * 4)) || (rc = sc.raw.ensure(ix->ex_bits ? (size_t)n * D : 16)) ||
         (opt && (rc = sc.trow.ensure((size_t)n * 8))))
         return rc;
-    HIP_TRY(launch_iota((uint32_t*)sc.vi.p, n, 0));
+    if (!d_pair_row) HIP_TRY(launch_iota((uint32_t*)sc.vi.p, n, 0));
+    const uint32_t* d_src = d_pair_row ? d_pair_row : (const uint32_t*)sc.vi.p; // the source row of every entry, ascending
     size_t tb = 0;
-    HIP_TRY(sort_pairs_u32(nullptr, &tb, d_asg, (uint32_t*)sc.ko.p, (const uint32_t*)sc.vi.p, (uint32_t*)sc.vo.p, n, bits, 0));
+    HIP_TRY(sort_pairs_u32(nullptr, &tb, d_asg, (uint32_t*)sc.ko.p, d_src, (uint32_t*)sc.vo.p, n, bits, 0));
     if ((rc = sc.tmp.ensure(tb))) return rc;
-    HIP_TRY(sort_pairs_u32(sc.tmp.p, &tb, d_asg, (uint32_t*)sc.ko.p, (const uint32_t*)sc.vi.p, (uint32_t*)sc.vo.p, n, bits, 0));
+    HIP_TRY(sort_pairs_u32(sc.tmp.p, &tb, d_asg, (uint32_t*)sc.ko.p, d_src, (uint32_t*)sc.vo.p, n, bits, 0));
     HIP_TRY(launch_chunk_first((const uint32_t*)sc.ko.p, n, d_chunk_first, 0));
     HIP_TRY(launch_chunk_slots((const uint32_t*)sc.ko.p, (const uint32_t*)sc.vo.p, n, (const uint32_t*)ix->list_gb0.p, d_cursor,
                                d_chunk_first, (uint32_t*)sc.row_src.p, (uint32_t*)sc.row_slot.p, 0));
@@ -115,6 +117,7 @@ int encode_rows_at_cursors(Replica* ix, EncodeScratch& sc, const float* d_vec, c
     P.blocks = (uint8_t*)ix->blocks.p; P.raw_ex = (uint8_t*)sc.raw.p;
     P.f_add_ex = (float*)ix->fadd_ex.p; P.f_rescale_ex = (float*)ix->fres_ex.p; P.ids = (uint64_t*)ix->ids.p;
     P.delta = (float*)ix->delta.p; P.vl = (float*)ix->vl.p;
+    if (ix->has_rnorm) P.residual_norm = (float*)ix->rnorm.p; // (an MSTG handle: slot order, like delta)
     P.src_base = id_base; P.nslots = n; P.D = D; P.Dc = Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.t_const = t_const;
     HIP_TRY(launch_encode(P, 0));
     if (ix->ex_bits)

@@ -29,7 +29,9 @@ int check_closure_args(const float* centroids, uint64_t n_lists, uint32_t dim, c
     return RBQ_OK;
 }
 
-int run_closure(ClosureArgs& a, int dev, bool count) {
+} // namespace
+
+int run_closure(ClosureArgs& a, int dev, bool count) { // (api.hpp: rbq_mstg_append runs it too)
     a.cent_on_device = is_device_pointer(a.centroids);
     a.data_on_device = is_device_pointer(a.data);
     a.out_on_device = a.out_lists && is_device_pointer(a.out_lists);
@@ -43,6 +45,8 @@ int run_closure(ClosureArgs& a, int dev, bool count) {
     if (count) g_closure_fallbacks.fetch_add(fb, std::memory_order_relaxed);
     return RBQ_OK;
 }
+
+namespace {
 
 int build_impl(const rbq_header* hdr, const float* centroids, const float* data, uint64_t n, float epsilon, uint32_t max_replicas,
                int rescale, float t_const, uint64_t max_chunk_rows, int device, rbq_index** out) {

@@ -28,7 +28,16 @@ int remove_impl(const rbq_index* idx, const uint64_t* ids, uint64_t n_ids, int n
     if (n_devices <= 1 && !devices) devs.push_back(dev);
     else if ((rc = resolve_devices(n_devices, devices, devs))) return rc;
     if (devs[0] != dev) return fail(RBQ_INVALID_CONFIG, "devices[0] must be the device of the index's first replica");
+    return remove_ids_core(idx, ids, n_ids, devs, out_removed, out);
+}
+} // namespace
 
+// Everything after the argument checks (api.hpp): rbq_index_remove_ids and rbq_mstg_remove_ids
+int remove_ids_core(const rbq_index* idx, const uint64_t* ids, uint64_t n_ids, const std::vector<int>& devs, uint64_t* out_removed,
+                    rbq_index** out) {
+    Replica* old = idx->reps[0];
+    const int dev = old->device;
+    int rc;
     DeviceGuard g(dev);
     if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
     rbq_header hdr{};
@@ -110,6 +119,10 @@ int remove_impl(const rbq_index* idx, const uint64_t* ids, uint64_t n_ids, int n
     if ((rc = alloc_arr(ix->delta, nslots * 4))) return rc;
     if ((rc = alloc_arr(ix->vl, nslots * 4))) return rc;
     ix->has_recon = true;
+    if (old->has_rnorm) { // an MSTG handle: what the `.mstg` format stores beyond the search's arrays
+        if ((rc = alloc_arr(ix->rnorm, nslots * 4))) return rc;
+        ix->has_rnorm = true; ix->tc_some = old->tc_some; ix->tc_value = old->tc_value;
+    }
     if (exd) HIP_TRY(hipMemset((uint8_t*)ix->ex.p + nslots * exd, 0, 256)); // read-ahead pad of the refine loads
 
     // ---- the slot map, then the gather
@@ -132,6 +145,7 @@ int remove_impl(const rbq_index* idx, const uint64_t* ids, uint64_t n_ids, int n
         }
         P.delta_s = (const float*)old->delta.p; P.delta_d = (float*)ix->delta.p;
         P.vl_s = (const float*)old->vl.p; P.vl_d = (float*)ix->vl.p;
+        if (ix->has_rnorm) { P.rnorm_s = (const float*)old->rnorm.p; P.rnorm_d = (float*)ix->rnorm.p; }
         EventPair ev;
         ev.start();
         HIP_TRY(launch_remove_gather(P, dev, 0));
@@ -151,7 +165,6 @@ int remove_impl(const rbq_index* idx, const uint64_t* ids, uint64_t n_ids, int n
     if (out_removed) *out_removed = removed;
     return RBQ_OK;
 }
-} // namespace
 } // namespace rbq_api
 
 extern "C" {

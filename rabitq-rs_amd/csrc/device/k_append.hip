@@ -20,7 +20,8 @@ __device__ __forceinline__ void carry_unit(const float* s, float* d, size_t si, 
 
 // One workgroup per block of the grown index (grid-stride).  The block's record and its 32 ex codes are one run of 16-byte units
 // that the 256 lanes walk together: a wave instruction moves 1 KiB of contiguous bytes, whole 128-byte lines (both strides are
-// multiples of 128).  The five per-slot arrays are 256 + 4 x 128 bytes per block: 48 lanes of the last wave take one unit each.
+// multiples of 128).  The five per-slot arrays are 256 + 4 x 128 bytes per block: 48 lanes of the last wave take one unit each,
+// and 8 more the residual norms of an MSTG handle (128 bytes per block; null for an IVF handle).
 // A block without a source gets the streamed builder's fill.  Bandwidth-bound: no LDS, nothing kept between blocks.
 __global__ __launch_bounds__(256) void k_append_carry(AppendCarryParams P) {
     const uint32_t tid = threadIdx.x;
@@ -56,6 +57,9 @@ __global__ __launch_bounds__(256) void k_append_carry(AppendCarryParams P) {
                 else if (a == 1u) { if (P.fres_d) carry_unit(P.fres_s, P.fres_d, si, di, has); }
                 else if (a == 2u) carry_unit(P.delta_s, P.delta_d, si, di, has);
                 else carry_unit(P.vl_s, P.vl_d, si, di, has);
+            } else if (l < 56u) { // rnorm (MSTG handles): 8 units, the next lanes of the same wave
+                const uint32_t u = l - 48u;
+                if (P.rnorm_d) carry_unit(P.rnorm_s, P.rnorm_d, (size_t)(has ? sb : 0u) * 8u + u, (size_t)b * 8u + u, has);
             }
         }
     }

@@ -76,7 +76,8 @@ __device__ __forceinline__ void gather_f32(const float* s, float* d, uint32_t sr
 // its source slot from the map once and walks the code granules tid / 32, + 8, ... from the source block's lane to its own, 16
 // bytes each, so a wave instruction stores 1 KiB of contiguous bytes and loads contiguous bytes wherever a run of survivors is.
 // The 8-byte tail granule, the three factor rows and the five per-slot arrays are per-lane gathers spread over the eight half
-// waves.  The ex codes of a slot are contiguous: 8 lanes per slot copy them 128 bytes at a time (the source slot comes from the
+// waves (half waves 0-4 the slot arrays, 5-7 the factor rows; half wave 5 also the residual norms of an MSTG handle, a sixth
+// slot array that an IVF handle does not have).  The ex codes of a slot are contiguous: 8 lanes per slot copy them 128 bytes at a time (the source slot comes from the
 // lane that holds it, by a shuffle).  A pad lane gets the builder's fill: zeros, and an id of all ones.  Bandwidth-bound: no LDS,
 // nothing kept between blocks.
 __global__ __launch_bounds__(256) void k_remove_gather(RemoveGatherParams P) {
@@ -115,6 +116,7 @@ __global__ __launch_bounds__(256) void k_remove_gather(RemoveGatherParams P) {
         else if (grp == 2u) { if (P.fres_d) gather_f32(P.fres_s, P.fres_d, src, ds, has); }
         else if (grp == 3u) gather_f32(P.delta_s, P.delta_d, src, ds, has);
         else if (grp == 4u) gather_f32(P.vl_s, P.vl_d, src, ds, has);
+        else if (grp == 5u) { if (P.rnorm_d) gather_f32(P.rnorm_s, P.rnorm_d, src, ds, has); } // (its second task, after a factor row)
         if (P.ex16) { // slot tid / 8 of the block, unit tid % 8, + 8, ...; lane (slot % 32) of this wave holds the slot's source
             const uint32_t slot = tid >> 3, j = tid & 7u;
             const uint32_t s2 = (uint32_t)__shfl((int)src, (int)(slot & 31u));

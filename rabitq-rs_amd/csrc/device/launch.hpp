@@ -499,6 +499,8 @@ struct AppendCarryParams {
     uint64_t* ids_d;
     const float *fadd_s, *fres_s, *delta_s, *vl_s; // fadd / fres: null for a 1-bit index
     float *fadd_d, *fres_d, *delta_d, *vl_d;
+    const float* rnorm_s;                       // MSTG handles (rbq_mstg_append): residual norms, a sixth per-slot array; null: none
+    float* rnorm_d;
 };
 hipError_t launch_append_carry(const AppendCarryParams& P, int device, hipStream_t s);
 // *out (device, zeroed by the caller) = max over the real slots of id + 1 (saturating); block_nv [n_blocks] as launch_load_block_nv leaves it
@@ -537,6 +539,8 @@ struct RemoveGatherParams {
     uint64_t* ids_d;
     const float *fadd_s, *fres_s, *delta_s, *vl_s; // fadd / fres: null for a 1-bit index
     float *fadd_d, *fres_d, *delta_d, *vl_d;
+    const float* rnorm_s;                       // MSTG handles (rbq_mstg_remove_ids): residual norms, a sixth per-slot array; null: none
+    float* rnorm_d;
 };
 hipError_t launch_remove_gather(const RemoveGatherParams& P, int device, hipStream_t s);
 

@@ -203,6 +203,10 @@ def lib():
         L.rbq_mstg_load_stream.argtypes = [READ_FN, vp, C.c_uint64, C.c_int, vp, C.POINTER(vp)]
         L.rbq_mstg_memory_usage.restype = C.c_uint64
         L.rbq_mstg_memory_usage.argtypes = [vp]
+        # rbq_mstg_mutate.h
+        for n_, (res, args) in _abi.MSTG_MUTATE_PROTOTYPES.items():
+            getattr(L, n_).restype = res
+            getattr(L, n_).argtypes = args
         from .builder import bind_hclustered
         bind_hclustered(L)
         _LIB = L

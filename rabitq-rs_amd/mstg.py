@@ -139,6 +139,72 @@ def build_postings_on_device(data, centroids, total_bits, metric, closure_epsilo
     return IvfRabitqIndex(h)
 
 
+def append_postings(handle, data, first_id=None, closure_epsilon=0.15, max_replicas=8, max_chunk_rows=0, return_lists=False):
+    """FAISS-style add on an MSTG handle (rbq_mstg_append): a NEW handle that holds `handle`'s slots and those of the rows of
+    `data` [count][dim] (a NumPy array, copied a chunk at a time, or a CUDA tensor, used in place), with ids first_id ..
+    (None: handle.id_bound()).  Every row joins the lists its closure against the handle's own centroids names and is encoded
+    with the rescale mode the handle remembers; the result equals build_postings_on_device over the old and the new rows with
+    the same centroids, array for array.  `handle` stays valid; the caller closes it.  With `return_lists`, also (lists
+    [count][max_replicas], counts [count]) as closure_assign returns them: NumPy u32 arrays for NumPy data, int32 tensors (bit
+    patterns) on the data's device for a CUDA tensor."""
+    from . import RabitqError
+    from .index import IvfRabitqIndex, _check, lib
+    if len(data.shape) != 2 or int(data.shape[1]) != int(handle.dim):
+        raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data must be [count][%d]" % int(handle.dim))
+    count, M = int(data.shape[0]), int(max_replicas)
+    xp, x = _ptr(data, -1)
+    on_dev = not isinstance(x, np.ndarray)
+    lists = counts = lp = cp = None
+    if return_lists:
+        if on_dev:
+            import torch
+            lists = torch.empty((count, max(M, 0)), dtype=torch.int32, device=x.device)
+            counts = torch.empty(count, dtype=torch.int32, device=x.device)
+            lp, cp = C.c_void_p(lists.data_ptr()), C.c_void_p(counts.data_ptr())
+        else:
+            lists, counts = np.empty((count, max(M, 0)), np.uint32), np.empty(count, np.uint32)
+            lp, cp = C.c_void_p(lists.ctypes.data), C.c_void_p(counts.ctypes.data)
+    h = C.c_void_p()
+    _check(lib().rbq_mstg_append(handle._h, xp, count, handle.id_bound() if first_id is None else int(first_id),
+                                 float(closure_epsilon), M, int(max_chunk_rows), lp, cp, C.byref(h)))
+    new = IvfRabitqIndex(h)
+    return (new, lists, counts) if return_lists else new
+
+
+def remove_postings(handle, ids):
+    """FAISS-style remove_ids on an MSTG handle (rbq_mstg_remove_ids): (a NEW handle without the slots whose id is in `ids`,
+    the number of slots removed — a vector held by three lists counts three).  `ids` is a NumPy u64 array (or anything that
+    converts to one) or a CUDA int64 / uint64 tensor; any order, repeats allowed, ids that are not stored ignored.  The result
+    equals build_postings_on_device over the rows that stay, with their original ids.  `handle` stays valid."""
+    from . import RabitqError
+    from .index import IvfRabitqIndex, _check, lib
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    if torch is not None and isinstance(ids, torch.Tensor) and ids.is_cuda:
+        if ids.dtype not in (torch.int64, torch.uint64):
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "ids on the device must be int64 or uint64")
+        v = ids.contiguous().reshape(-1)
+        n, p = int(v.numel()), v.data_ptr()
+    else:
+        if torch is not None and isinstance(ids, torch.Tensor):
+            ids = ids.numpy()
+        if not isinstance(ids, np.ndarray):
+            ids = np.asarray(ids if hasattr(ids, "__len__") else list(ids), dtype=np.uint64)
+        v = np.ascontiguousarray(ids).astype(np.uint64).reshape(-1)
+        n, p = int(v.size), v.ctypes.data
+    h, removed = C.c_void_p(), C.c_uint64()
+    _check(lib().rbq_mstg_remove_ids(handle._h, C.c_void_p(p) if n else None, n, C.byref(removed), C.byref(h)))
+    return IvfRabitqIndex(h), int(removed.value)
+
+
+def append_passes():
+    """Encode passes of every append_postings so far (rbq_debug_mstg_append_passes)."""
+    from .index import lib
+    return int(lib().rbq_debug_mstg_append_passes())
+
+
 @dataclass(frozen=True)
 class MstgSearchParams:
     """The crate's SearchParams of an MSTG index (src/mstg/config.rs): how many centroids are ranked, and dynamic_prune's epsilon."""
@@ -482,6 +548,35 @@ class MstgIndex:
         real = ids[ids != np.uint64(0xFFFFFFFFFFFFFFFF)]
         self._n = int(real.max()) + 1 if real.size else 0
         return self
+
+    def id_bound(self):
+        """1 + the largest stored id (rbq_index_id_bound)."""
+        return self._built().id_bound()
+
+    def add(self, data):
+        """FAISS-style add (append_postings with this object's closure_epsilon and max_replicas): the rows of `data` join the
+        posting lists with the ids id_bound() ..; nothing is re-clustered, the centroids stay.  The handle is swapped for the
+        grown one and the old one closed.  Returns the first new id."""
+        h = self._built()
+        if len(data.shape) != 2:
+            raise ValueError("Data must be 2D array (N x D)")
+        if data.shape[1] != self.dimension:
+            raise ValueError(f"Data dimension {data.shape[1]} does not match expected {self.dimension}")
+        first = h.id_bound()
+        self.handle = append_postings(h, data, first, self.closure_epsilon, self.max_replicas)
+        h.close()
+        self._n = self.handle.id_bound()
+        return first
+
+    def remove_ids(self, ids):
+        """FAISS-style remove_ids (remove_postings): every slot whose id is in `ids` leaves its list.  The handle is swapped for
+        the shrunk one and the old one closed; len() becomes 1 + the largest id that stays.  Returns the number of slots removed
+        (a vector counts once per list that held it)."""
+        h = self._built()
+        self.handle, removed = remove_postings(h, ids)
+        h.close()
+        self._n = self.handle.id_bound()
+        return removed
 
     def get_memory_usage(self):
         """Device bytes held by the index (the crate's get_memory_usage reports its host footprint)."""
