@@ -42,10 +42,8 @@ hipError_t launch_prep(const PrepParams& p, int device, hipStream_t s) {
 hipError_t launch_lat_front(const PrepParams& p, const RankParams& r, int device, hipStream_t s) {
     static LdsAttrCache attr;
     LatFrontParams P;
-    P.queries = p.queries; P.nq = p.nq; P.dim = p.dim; P.D = p.D; P.Dc = p.Dc; P.rotator = p.rotator; P.rot_blob = p.rot_blob;
-    P.trunc = p.trunc; P.fac = p.fac; P.ex_bits = p.ex_bits; P.rot = p.rot; P.lut = p.lut; P.consts = p.consts;
-    P.cent = r.cent; P.nlist = r.nlist; P.metric = r.metric; P.scores = r.scores;
-    P.rot_hl = p.rot_hl; P.rank_resid = p.rank_resid; P.scorers = (r.scores && !r.ksplit) ? (r.nlist + kLatLists - 1) / kLatLists : 0u;
+    P.prep = p; P.cent = r.cent; P.nlist = r.nlist; P.metric = r.metric; P.scores = r.scores;
+    P.scorers = (r.scores && !r.ksplit) ? (r.nlist + kLatLists - 1) / kLatLists : 0u;
     P.zero_scores = r.ksplit > 1 ? r.scores : nullptr; // (split-K ranking GEMM behind this preparation: its parts are added to a zeroed row)
     const dim3 grid(lat_front_grid(P.scorers, p.nq));
     const size_t lds = (size_t)p.D * 4 * 2 + p.D / 2;

@@ -14,8 +14,12 @@
 //     contract holds with room to spare, nothing downstream changes;
 //   * workgroup G writes the rotated query, the query constants and the u8 LUT: the two strictly sequential sums on two lanes of
 //     wave 0 WHILE waves 1-3 find the LUT's value range; the quantisation by all four waves.
-// Same arithmetic as k_prep / k_prep_wave, operation for operation (the stage-level parity test compares bits).
+// The preparation's steps are the device functions of query_kernels.hpp that k_prep and k_prep_wave call too (rotation by one wave,
+// image and residual, LUT entries, range, quantisation and store, constants); the positive / negative sums are taken in
+// k_prep_wave's order.  This kernel's own: the scorers, the split of the serial sums (wave 0, prefetching form) from the LUT's range
+// (waves 1-3), and the LDS atomics that join the four waves.
 #pragma once
+#include "launch.hpp"
 #include "query_kernels.hpp"
 
 namespace rbq {
@@ -23,22 +27,12 @@ namespace rbq {
 constexpr uint32_t kLatLists = 32; // lists scored per workgroup (eight lanes each)
 
 struct LatFrontParams {
-    const float* queries; // [nq][dim]
-    uint32_t nq, dim, D, Dc;
-    int rotator;          // 1 = FhtKac, 2 = none (the matrix rotator is O(D^2) per query: k_prep serves it)
-    const uint8_t* rot_blob;
-    uint32_t trunc;
-    float fac;
-    uint32_t ex_bits;
-    float* rot;           // [nq][D]
-    uint8_t* lut;         // [nq][4Dc]
-    QueryConsts* consts;  // [nq]
+    PrepParams prep;      // rotator: 1 = FhtKac, 2 = none (the matrix rotator is O(D^2) per query: k_prep serves it); rot_hl, the ranking
+                          // GEMM's operand image, only with `scorers` = 0
     const float* cent;    // [nlist][D] rotated centroids
     uint32_t nlist;
     int metric;
     float* scores;        // [nq][nlist] exact canonical scores (L2: squared distance; IP: dot)
-    uint16_t* rot_hl;     // null, or the split-bf16 image of the rotated query, hi | lo per K slab (the ranking GEMM's operand: `scorers` = 0)
-    float* rank_resid;    // non-null (the one-product f16 route): rot_hl receives the f16 image [nq][D] and rank_resid[q] = |q - f16(q)|
     float* zero_scores;   // null, or the score rows [nq][nlist] to clear (a split-K ranking GEMM adds its parts to them)
     uint32_t scorers;     // G = ceil(nlist / 32) scoring workgroups per query, or 0: preparation only, the ranking GEMM follows (medium
                           // batches: a workgroup per query finishes a query's preparation in ~2/3 of the time one wave of k_prep_wave needs)
@@ -57,44 +51,29 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
     __shared__ unsigned int s_amin, s_amax;
     __shared__ float s_sum, s_n2, s_sp, s_sn;
     __shared__ double s_rr[kThreads / 64]; // (one-product f16 route) squared residual of the image, per wave
-    const uint32_t D = P.D, Dc = P.Dc, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint32_t D = P.prep.D, Dc = P.prep.Dc, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t G = P.scorers;
     uint32_t q = blockIdx.x, g = 0;
     if (G) {
         const uint32_t slot = blockIdx.x >> 3;
-        q = slot % P.nq;
-        g = (slot / P.nq) * 8u + (blockIdx.x & 7u);
+        q = slot % P.prep.nq;
+        g = (slot / P.prep.nq) * 8u + (blockIdx.x & 7u);
         if (g > G) return; // (padding of the role count to a multiple of 8)
     }
     float* x = sm;
     float* x2 = sm + D;
     uint8_t* flips = reinterpret_cast<uint8_t*>(sm + (size_t)2 * D);
-    const float* qin = P.queries + (size_t)q * P.dim;
-    const uint32_t trunc = P.trunc;
-#ifdef RBQ_PREP_STAMPS
-    const unsigned long long pt0 = __builtin_amdgcn_s_memtime();
-#endif
-    const bool wave_fht = P.rotator == 1 && trunc >= 64 && trunc <= 2048;
-    if (P.rotator == 1) {
-        for (uint32_t i = tid; i < D / 8; i += kThreads) reinterpret_cast<uint32_t*>(flips)[i] = reinterpret_cast<const uint32_t*>(P.rot_blob)[i]; // (4 D / 8 flip bytes as dwords: one trip)
-        if (wave == 0 && wave_fht) fhtkac_initial_load(x, qin, P.dim, D, trunc, P.rot_blob, lane);
+    const float* qin = P.prep.queries + (size_t)q * P.prep.dim;
+    const uint32_t trunc = P.prep.trunc;
+    PrepStamps ps;
+    ps.mark(0);
+    const bool wave_fht = P.prep.rotator == 1 && trunc >= 64 && trunc <= 2048;
+    if (P.prep.rotator == 1) {
+        for (uint32_t i = tid; i < D / 8; i += kThreads) reinterpret_cast<uint32_t*>(flips)[i] = reinterpret_cast<const uint32_t*>(P.prep.rot_blob)[i]; // (4 D / 8 flip bytes as dwords: one trip)
+        if (wave == 0 && wave_fht) fhtkac_initial_load(x, qin, P.prep.dim, D, trunc, P.prep.rot_blob, lane);
         __syncthreads();
     }
-    if (wave == 0) { // k_prep_wave's rotation, by one wave (no barrier inside)
-        if (P.rotator == 1) {
-            switch (trunc) {
-                case 64: rotate_fhtkac_wave<1>(x, D, flips, P.fac, lane); break;
-                case 128: rotate_fhtkac_wave<2>(x, D, flips, P.fac, lane); break;
-                case 256: rotate_fhtkac_wave<4>(x, D, flips, P.fac, lane); break;
-                case 512: rotate_fhtkac_wave<8>(x, D, flips, P.fac, lane); break;
-                case 1024: rotate_fhtkac_wave<16>(x, D, flips, P.fac, lane); break;
-                case 2048: rotate_fhtkac_wave<32>(x, D, flips, P.fac, lane); break;
-                default: rotate_into_lds<64>(x, nullptr, qin, P.dim, D, P.rotator, flips, trunc, P.fac, lane); break;
-            }
-        } else {
-            rotate_into_lds<64>(x, nullptr, qin, P.dim, D, P.rotator, P.rot_blob, trunc, P.fac, lane);
-        }
-    }
+    if (wave == 0) rotate_by_wave(x, qin, P.prep.dim, D, P.prep.rotator, P.prep.rot_blob, flips, trunc, P.prep.fac, lane); // (no barrier inside)
     __syncthreads(); // x[0..D) = the rotated query
 
     if (g < G) {
@@ -145,28 +124,15 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
     }
 
     // ---- workgroup G: rotated query, constants, LUT of query q
-#ifdef RBQ_PREP_STAMPS
-    const unsigned long long pt1 = __builtin_amdgcn_s_memtime();
-#endif
+    ps.mark(1);
     double rr = 0.0;
     for (uint32_t i = tid; i < D; i += kThreads) {
         const float v = x[i];
         x2[i] = v * v;
-        P.rot[(size_t)q * D + i] = v;
-        if (P.rank_resid) { // one-product f16 image [nq][D] for k_rank_f16_db and its residual
-            float r;
-            P.rot_hl[(size_t)q * D + i] = f16_image(v, r);
-            rr += (double)r * (double)r;
-        } else if (P.rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
-            uint16_t h, l;
-            bf16_split(v, h, l);
-            P.rot_hl[(size_t)q * 2 * D + hl_offset(i, 0, D)] = h;
-            P.rot_hl[(size_t)q * 2 * D + hl_offset(i, 1, D)] = l;
-        }
+        store_rotated(v, q, i, D, P.prep.rot, P.prep.rot_hl, P.prep.rank_resid != nullptr, rr);
     }
-    if (P.rank_resid) { // (uniform) per-wave sums now, their total behind the barrier below
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) rr += __shfl_xor(rr, d, 64);
+    if (P.prep.rank_resid) { // (uniform) per-wave sums now, their total behind the barrier below
+        rr = wave_sum(rr);
         if (lane == 0) s_rr[wave] = rr;
     }
     if (P.zero_scores) { // (the row a split-K ranking GEMM adds its parts to)
@@ -176,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
     }
     if (tid == 0) { s_kmin = 0x7fffffff; s_kmax = (int)0x80000000; s_amin = 0; s_amax = 0; }
     __syncthreads();
-    if (P.rank_resid && tid == 0) P.rank_resid[q] = f16_resid_norm(s_rr, kThreads / 64);
+    if (P.prep.rank_resid && tid == 0) P.prep.rank_resid[q] = f16_resid_norm(s_rr, kThreads / 64);
     const uint32_t ncb = D / 4;
     if (wave == 0) {
         // sums of the positive / negative elements (ex_dot_range), k_prep_wave's order: strided per lane, xor tree
@@ -223,12 +189,7 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
         for (uint32_t c = tid - 64u; c < ncb; c += kThreads - 64u) {
             float l[16];
             lut_entries(x + 4 * c, l);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int k = total_key(l[j]);
-                kmin = k < kmin ? k : kmin;
-                kmax = k > kmax ? k : kmax;
-            }
+            lut_key_range(l, kmin, kmax);
         }
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) {
@@ -239,37 +200,21 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
         if (lane == 0) { atomicMin(&s_kmin, kmin); atomicMax(&s_kmax, kmax); }
     }
     __syncthreads();
-#ifdef RBQ_PREP_STAMPS
-    const unsigned long long pt2 = __builtin_amdgcn_s_memtime();
-#endif
+    ps.mark(2);
     const float vl = key_to_float(s_kmin), vr = key_to_float(s_kmax);
     const float delta = (vr - vl) / 255.0f;
     uint32_t amin = 0, amax = 0;
     for (uint32_t c = tid; c < Dc / 4; c += kThreads) { // pass 2: quantise (all four waves)
-        uint32_t w[4] = {0, 0, 0, 0};
+        uint4 w = make_uint4(0, 0, 0, 0); // (padding codebook)
         if (c < ncb) {
             float l[16];
             lut_entries(x + 4 * c, l);
-            uint32_t emin = 255, emax = 0;
-            if (delta > 0.0f) {
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    float v = roundf((l[j] - vl) / delta);
-                    v = v >= 0.0f ? v : 0.0f; // also maps NaN -> 0 like `as u8`
-                    v = v > 255.0f ? 255.0f : v;
-                    const uint32_t e = (uint32_t)v;
-                    emin = e < emin ? e : emin;
-                    emax = e > emax ? e : emax;
-                    w[j >> 2] |= e << (8 * (j & 3));
-                }
-            } else {
-                emin = 0;
-            }
+            uint32_t emin, emax;
+            w = lut_quantise(l, vl, delta, emin, emax);
             amin += emin;
             amax += emax;
         }
-        // device LUT order: adjacent codebooks swapped (position p holds codebook p^1); padding codebooks are all-zero tables
-        *reinterpret_cast<uint4*>(P.lut + (size_t)q * Dc * 4 + (size_t)(c ^ 1u) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        lut_store(P.prep.lut, q, Dc, c, w);
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) {
@@ -278,24 +223,7 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
     }
     if (lane == 0) { atomicAdd(&s_amin, amin); atomicAdd(&s_amax, amax); }
     __syncthreads();
-    if (tid == 0) {
-        QueryConsts qc;
-        qc.amin = (float)s_amin;
-        qc.amax = (float)s_amax;
-        qc.delta = delta;
-        qc.sum_vl = vl * (float)(D / 4);
-        qc.qnorm = sqrtf(s_n2);
-        qc.qnorm2 = s_n2; qc.q1norm = (s_sp - s_sn) * 1.001f;
-        ex_dot_range(s_sp, s_sn, P.ex_bits, qc.exlo, qc.exhi);
-#ifdef RBQ_PREP_STAMPS
-        qc.exlo = (float)(pt1 - pt0); qc.exhi = (float)(pt2 - pt1); qc.q1norm = (float)(__builtin_amdgcn_s_memtime() - pt2); // (lazy selection is off in this build)
-#endif
-        qc.k1x = -0.5f * s_sum;
-        const float cb = -((float)(1u << P.ex_bits) - 0.5f);
-        qc.kbx = cb * s_sum;
-        qc.scale = (float)(1u << P.ex_bits);
-        P.consts[q] = qc;
-    }
+    if (tid == 0) P.prep.consts[q] = query_consts(s_amin, s_amax, delta, vl, D, s_sum, s_n2, s_sp, s_sn, P.prep.ex_bits, ps);
 }
 
 } // namespace rbq

@@ -1,6 +1,14 @@
 // query_kernels.hpp — the kernels of the query stages in front of the scan that are not templates on the GEMM shape:
 // k_prep / k_prep_wave (rotate + constants + LUT), k_rank_scores and k_select (the all-pairs canonical ranking kept as
 // the exact_rank option).  Included by k_query.hip only (non-template __global__ functions: one definition).
+//
+// Query preparation has three kernels: k_prep and k_prep_wave here, k_lat_front in latency.hpp.  What they compute is ONE copy of
+// device functions — rotate_by_wave, store_rotated (the rotated query, its GEMM image, the f16 residual), lut_entries,
+// lut_key_range, lut_quantise, lut_store, query_consts (with ex_dot_range and f16_resid_norm) — so their outputs agree bit for bit by
+// construction.  What differs is structure, measured and kept per kernel: who rotates and which barriers exist, the form of the
+// strictly sequential sums, how ranges and sums are reduced (LDS atomics or wave shuffles), and where the positive / negative sums
+// are taken: serially on one thread in k_prep, strided per lane and a xor tree in the other two, so q1norm, exlo and exhi of k_prep
+// differ from theirs in the last bits (tests/test_gpu_prep_kernels_agree.py holds all of this together on one input).
 #pragma once
 #include "kernels.hpp"
 
@@ -25,170 +33,6 @@ __device__ __forceinline__ float f16_resid_norm(const double* part, int n) {
     double a = 0.0;
     for (int i = 0; i < n; ++i) a += part[i];
     return (float)(sqrt(a) * 1.000001);
-}
-
-__global__ __launch_bounds__(kThreads) void k_prep(const float* __restrict__ queries, uint32_t dim, uint32_t D,
-                                                   uint32_t Dc, int rotator, const uint8_t* __restrict__ rot_blob,
-                                                   uint32_t trunc, float fac, uint32_t ex_bits,
-                                                   float* __restrict__ rot_out, uint8_t* __restrict__ lut_out,
-                                                   QueryConsts* __restrict__ consts,
-                                                   uint16_t* __restrict__ rot_hl, float* __restrict__ rank_resid) {
-    extern __shared__ __align__(16) float sm[];
-    __shared__ double s_rr[kThreads / 64]; // (one-product f16 route) squared residual of the image, per wave
-    float* x = sm;         // [D]
-    float* y = sm + D;     // [D] (matrix rotator input)
-    __shared__ int s_kmin, s_kmax;
-    __shared__ unsigned int s_amin, s_amax;
-    __shared__ float s_sum, s_n2, s_pos, s_neg;
-    const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    const float* qin = queries + (size_t)q * dim;
-#ifdef RBQ_PREP_STAMPS
-    const unsigned long long pt0 = __builtin_amdgcn_s_memtime();
-#endif
-
-    rotate_into_lds<kThreads>(x, y, qin, dim, D, rotator, rot_blob, trunc, fac, tid);
-
-    double rr = 0.0;
-    for (uint32_t i = tid; i < D; i += kThreads) {
-        rot_out[(size_t)q * D + i] = x[i];
-        if (rank_resid) { // one-product f16 image [nq][D] for k_rank_f16_db and its residual
-            float r;
-            rot_hl[(size_t)q * D + i] = f16_image(x[i], r);
-            rr += (double)r * (double)r;
-        } else if (rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
-            uint16_t h, l;
-            bf16_split(x[i], h, l);
-            rot_hl[(size_t)q * 2 * D + hl_offset(i, 0, D)] = h;
-            rot_hl[(size_t)q * 2 * D + hl_offset(i, 1, D)] = l;
-        }
-    }
-    if (rank_resid) { // (uniform) per-wave sums now, their total behind the barrier below
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) rr += __shfl_xor(rr, d, 64);
-        if ((tid & 63u) == 0) s_rr[tid >> 6] = rr;
-    }
-
-#ifdef RBQ_PREP_STAMPS
-    const unsigned long long pt1 = __builtin_amdgcn_s_memtime();
-#endif
-    // QueryPrecomputed::new — strictly sequential sums (Rust iter().sum() folds from -0.0)
-    if (tid == 0) {
-        float s = -0.0f;
-        for (uint32_t i = 0; i < D; ++i) s = s + x[i];
-        s_sum = s;
-        s_kmin = 0x7fffffff;
-        s_kmax = (int)0x80000000;
-        s_amin = 0;
-        s_amax = 0;
-    }
-    if (tid == 64) {
-        float n2 = -0.0f;
-        for (uint32_t i = 0; i < D; ++i) {
-            float p = x[i] * x[i];
-            n2 = n2 + p;
-        }
-        s_n2 = n2;
-    }
-    if (tid == 128) { // sums of the positive / negative elements: range of the ex-code dot product (ex_dot_range)
-        float sp = 0.0f, sn = 0.0f;
-        for (uint32_t i = 0; i < D; ++i) { sp += fmaxf(x[i], 0.0f); sn += fminf(x[i], 0.0f); }
-        s_pos = sp; s_neg = sn;
-    }
-    __syncthreads();
-    if (rank_resid && tid == 0) rank_resid[q] = f16_resid_norm(s_rr, kThreads / 64);
-
-#ifdef RBQ_PREP_STAMPS
-    const unsigned long long pt2 = __builtin_amdgcn_s_memtime();
-#endif
-    // pack_lut_f32 + QueryLut::new.  D <= 2048 -> at most 2 codebooks per thread.
-    const uint32_t ncb = D / 4;
-    float l[2][16];
-    int kmin = 0x7fffffff, kmax = (int)0x80000000;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        uint32_t c = tid + u * kThreads;
-        if (c < ncb) {
-            const float q0 = x[4 * c], q1 = x[4 * c + 1], q2 = x[4 * c + 2], q3 = x[4 * c + 3];
-            // lut[j] = lut[j - lowbit(j)] + q[KPOS[j]],  KPOS = {3,3,2,3,1,3,2,3,0,3,2,3,1,3,2,3}
-            l[u][0] = 0.0f;
-            l[u][1] = l[u][0] + q3;
-            l[u][2] = l[u][0] + q2;
-            l[u][3] = l[u][2] + q3;
-            l[u][4] = l[u][0] + q1;
-            l[u][5] = l[u][4] + q3;
-            l[u][6] = l[u][4] + q2;
-            l[u][7] = l[u][6] + q3;
-            l[u][8] = l[u][0] + q0;
-            l[u][9] = l[u][8] + q3;
-            l[u][10] = l[u][8] + q2;
-            l[u][11] = l[u][10] + q3;
-            l[u][12] = l[u][8] + q1;
-            l[u][13] = l[u][12] + q3;
-            l[u][14] = l[u][12] + q2;
-            l[u][15] = l[u][14] + q3;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                int k = total_key(l[u][j]);
-                kmin = k < kmin ? k : kmin;
-                kmax = k > kmax ? k : kmax;
-            }
-        }
-    }
-    atomicMin(&s_kmin, kmin);
-    atomicMax(&s_kmax, kmax);
-    __syncthreads();
-    const float vl = key_to_float(s_kmin), vr = key_to_float(s_kmax);
-    const float delta = (vr - vl) / 255.0f;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        uint32_t c = tid + u * kThreads;
-        if (c < ncb) {
-            uint32_t w[4] = {0, 0, 0, 0};
-            uint32_t emin = 255, emax = 0;
-            if (delta > 0.0f) {
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    float v = roundf((l[u][j] - vl) / delta);
-                    v = v >= 0.0f ? v : 0.0f; // also maps NaN -> 0 like `as u8`
-                    v = v > 255.0f ? 255.0f : v;
-                    const uint32_t e = (uint32_t)v;
-                    emin = e < emin ? e : emin;
-                    emax = e > emax ? e : emax;
-                    w[j >> 2] |= e << (8 * (j & 3));
-                }
-            } else {
-                emin = 0;
-            }
-            atomicAdd(&s_amin, emin);
-            atomicAdd(&s_amax, emax);
-            // device LUT order: adjacent codebooks swapped (position p holds codebook p^1) so that
-            // nibble m of a little-endian code dword indexes table (8*dword + m) directly.
-            uint4* dst = reinterpret_cast<uint4*>(lut_out + (size_t)q * Dc * 4 + (size_t)(c ^ 1u) * 16);
-            *dst = make_uint4(w[0], w[1], w[2], w[3]);
-        } else if (c < Dc / 4) { // code-layout padding (D not a multiple of 64): all-zero tables
-            uint4* dst = reinterpret_cast<uint4*>(lut_out + (size_t)q * Dc * 4 + (size_t)(c ^ 1u) * 16);
-            *dst = make_uint4(0, 0, 0, 0);
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        QueryConsts qc;
-        qc.amin = (float)s_amin;
-        qc.amax = (float)s_amax;
-        qc.delta = delta;
-        qc.sum_vl = vl * (float)(D / 4);
-        qc.qnorm = sqrtf(s_n2);
-        qc.qnorm2 = s_n2; qc.q1norm = (s_pos - s_neg) * 1.001f;
-        ex_dot_range(s_pos, s_neg, ex_bits, qc.exlo, qc.exhi);
-#ifdef RBQ_PREP_STAMPS
-        qc.exlo = (float)(pt1 - pt0); qc.exhi = (float)(pt2 - pt1); qc.q1norm = (float)(__builtin_amdgcn_s_memtime() - pt2); // (lazy selection is off in this build)
-#endif
-        qc.k1x = -0.5f * s_sum;
-        const float cb = -((float)(1u << ex_bits) - 0.5f);
-        qc.kbx = cb * s_sum;
-        qc.scale = (float)(1u << ex_bits);
-        consts[q] = qc;
-    }
 }
 
 // In-register FHT of one wave over n = 64*EPL floats at `part` (LDS): lane holds elements lane*EPL .. +EPL-1, so
@@ -367,36 +211,12 @@ __device__ __forceinline__ void lut_entries(const float* x4, float (&l)[16]) {
     l[15] = l[14] + q3;
 }
 
-// k_prep for the FHT-Kac and identity rotators with ONE WAVE per query (4 queries per workgroup): no workgroup
-// barrier anywhere — the butterflies synchronise through the wave's in-order LDS traffic, the min/max and the
-// amin/amax sums are wave reductions, and the two strictly sequential sums (sum q, |q|^2: Rust iter().sum())
-// run side by side on lanes 0 and 1 of each wave.  Same arithmetic as k_prep, operation for operation.
-// dynamic LDS: 4 x 2 x D floats (vector + squares per wave) | 4*D/8 flip bytes
-__global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict__ queries, uint32_t nq, uint32_t dim, uint32_t D,
-                                                        uint32_t Dc, int rotator, const uint8_t* __restrict__ rot_blob,
-                                                        uint32_t trunc, float fac, uint32_t ex_bits,
-                                                        float* __restrict__ rot_out, uint8_t* __restrict__ lut_out,
-                                                        QueryConsts* __restrict__ consts,
-                                                        uint16_t* __restrict__ rot_hl, float* __restrict__ rank_resid) {
-    extern __shared__ __align__(16) float sm[];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t q = blockIdx.x * (kThreads / 64) + wave;
-    uint8_t* flips = reinterpret_cast<uint8_t*>(sm + (size_t)2 * (kThreads / 64) * D); // 4*D/8 bytes (FHT-Kac)
-#ifdef RBQ_PREP_STAMPS
-    const unsigned long long pt0 = __builtin_amdgcn_s_memtime();
-#endif
-    float* x = sm + (size_t)wave * 2 * D;
-    float* x2 = x + D; // squares, for the |q|^2 chain
-    const float* qin = queries + (size_t)q * dim;
-    const bool wave_fht = rotator == 1 && trunc >= 64 && trunc <= 2048; // (else the generic LDS butterflies)
-    if (rotator == 1) {
-        for (uint32_t i = threadIdx.x; i < D / 8; i += kThreads) reinterpret_cast<uint32_t*>(flips)[i] = reinterpret_cast<const uint32_t*>(rot_blob)[i]; // (4 D / 8 flip bytes as dwords: one trip)
-        // the query is requested together with the flip table (round 0's flips straight from the global table): one
-        // round trip in front of the barrier instead of two around it
-        if (q < nq && wave_fht) fhtkac_initial_load(x, qin, dim, D, trunc, rot_blob, lane);
-        __syncthreads(); // the only workgroup barrier: before any wave can leave
-    }
-    if (q >= nq) return; // whole wave
+// ---- the steps the three preparation kernels share (k_prep and k_prep_wave below, k_lat_front in latency.hpp) ----
+
+// DynamicRotator::rotate (src/rotation.rs:350-401) of the query at x (LDS) by ONE wave, for the FHT-Kac (`flips`: the LDS copy of its
+// flip bits; the caller has run fhtkac_initial_load) and the identity rotator
+__device__ __forceinline__ void rotate_by_wave(float* x, const float* qin, uint32_t dim, uint32_t D, int rotator, const uint8_t* rot_blob,
+                                               const uint8_t* flips, uint32_t trunc, float fac, uint32_t lane) {
     if (rotator == 1) {
         switch (trunc) {
             case 64: rotate_fhtkac_wave<1>(x, D, flips, fac, lane); break;
@@ -411,6 +231,220 @@ __global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict_
     } else {
         rotate_into_lds<64>(x, nullptr, qin, dim, D, rotator, rot_blob, trunc, fac, lane);
     }
+}
+
+// element i of query q's rotated vector, and of its image for the ranking GEMM; rr collects the squared residual of the f16 image
+__device__ __forceinline__ void store_rotated(float v, uint32_t q, uint32_t i, uint32_t D, float* rot_out, uint16_t* rot_hl, bool f16, double& rr) {
+    rot_out[(size_t)q * D + i] = v;
+    if (f16) { // one-product f16 image [nq][D] for k_rank_f16_db and its residual
+        float r;
+        rot_hl[(size_t)q * D + i] = f16_image(v, r);
+        rr += (double)r * (double)r;
+    } else if (rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
+        uint16_t h, l;
+        bf16_split(v, h, l);
+        rot_hl[(size_t)q * 2 * D + hl_offset(i, 0, D)] = h;
+        rot_hl[(size_t)q * 2 * D + hl_offset(i, 1, D)] = l;
+    }
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// QueryLut::new, pass 1: the value range of a codebook's entries, as total-order keys
+__device__ __forceinline__ void lut_key_range(const float (&l)[16], int& kmin, int& kmax) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int k = total_key(l[j]);
+        kmin = k < kmin ? k : kmin;
+        kmax = k > kmax ? k : kmax;
+    }
+}
+// pass 2: the sixteen u8 entries of a codebook (four dwords) and the smallest / largest of them
+__device__ __forceinline__ uint4 lut_quantise(const float (&l)[16], float vl, float delta, uint32_t& emin, uint32_t& emax) {
+    uint32_t w[4] = {0, 0, 0, 0};
+    emin = 255; emax = 0;
+    if (delta > 0.0f) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            float v = roundf((l[j] - vl) / delta);
+            v = v >= 0.0f ? v : 0.0f; // also maps NaN -> 0 like `as u8`
+            v = v > 255.0f ? 255.0f : v;
+            const uint32_t e = (uint32_t)v;
+            emin = e < emin ? e : emin;
+            emax = e > emax ? e : emax;
+            w[j >> 2] |= e << (8 * (j & 3));
+        }
+    } else {
+        emin = 0;
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+// device LUT order: adjacent codebooks swapped (position p holds codebook p^1) so that nibble m of a little-endian code dword
+// indexes table (8*dword + m) directly; the code-layout padding (D not a multiple of 64) holds all-zero tables
+__device__ __forceinline__ void lut_store(uint8_t* lut_out, uint32_t q, uint32_t Dc, uint32_t c, uint4 w) {
+    *reinterpret_cast<uint4*>(lut_out + (size_t)q * Dc * 4 + (size_t)(c ^ 1u) * 16) = w;
+}
+
+// -DRBQ_PREP_STAMPS: the clock at the three phase boundaries of a preparation kernel; query_consts reports the phases' cycles in
+// place of exlo / exhi / q1norm (lazy selection is off in this build)
+struct PrepStamps {
+#ifdef RBQ_PREP_STAMPS
+    unsigned long long t[3];
+    __device__ __forceinline__ void mark(int i) { t[i] = __builtin_amdgcn_s_memtime(); }
+#else
+    __device__ __forceinline__ void mark(int) {}
+#endif
+};
+
+// QueryPrecomputed::new (src/ivf.rs:862-878) and the constants of QueryLut::new from the query's sums: s_sum and s_n2 the strictly
+// sequential ones, sp / sn the sums of the positive / negative elements (ex_dot_range), amin / amax over the codebooks
+__device__ __forceinline__ QueryConsts query_consts(uint32_t amin, uint32_t amax, float delta, float vl, uint32_t D, float s_sum, float s_n2,
+                                                    float sp, float sn, uint32_t ex_bits, const PrepStamps& ps) {
+    QueryConsts qc;
+    qc.amin = (float)amin;
+    qc.amax = (float)amax;
+    qc.delta = delta;
+    qc.sum_vl = vl * (float)(D / 4);
+    qc.qnorm = sqrtf(s_n2);
+    qc.qnorm2 = s_n2; qc.q1norm = (sp - sn) * 1.001f;
+    ex_dot_range(sp, sn, ex_bits, qc.exlo, qc.exhi);
+#ifdef RBQ_PREP_STAMPS
+    qc.exlo = (float)(ps.t[1] - ps.t[0]); qc.exhi = (float)(ps.t[2] - ps.t[1]); qc.q1norm = (float)(__builtin_amdgcn_s_memtime() - ps.t[2]);
+#endif
+    qc.k1x = -0.5f * s_sum;
+    const float cb = -((float)(1u << ex_bits) - 0.5f);
+    qc.kbx = cb * s_sum;
+    qc.scale = (float)(1u << ex_bits);
+    return qc;
+}
+
+// One WORKGROUP per query, every rotator (the only kernel that serves the matrix rotator: O(D^2) per query).  Structure of its own:
+// the whole workgroup rotates; the sequential sums run on three separate threads, the positive / negative sums among them, serially
+// (so q1norm, exlo and exhi differ from the other two kernels' in the last bits); each thread keeps the entries of its (at most two)
+// codebooks in registers across the barrier behind the range; ranges and u8 sums meet through LDS atomics.
+// dynamic LDS: 2 x D floats (vector | matrix rotator input)
+__global__ __launch_bounds__(kThreads) void k_prep(const float* __restrict__ queries, uint32_t dim, uint32_t D,
+                                                   uint32_t Dc, int rotator, const uint8_t* __restrict__ rot_blob,
+                                                   uint32_t trunc, float fac, uint32_t ex_bits,
+                                                   float* __restrict__ rot_out, uint8_t* __restrict__ lut_out,
+                                                   QueryConsts* __restrict__ consts,
+                                                   uint16_t* __restrict__ rot_hl, float* __restrict__ rank_resid) {
+    extern __shared__ __align__(16) float sm[];
+    __shared__ double s_rr[kThreads / 64]; // (one-product f16 route) squared residual of the image, per wave
+    float* x = sm;         // [D]
+    float* y = sm + D;     // [D] (matrix rotator input)
+    __shared__ int s_kmin, s_kmax;
+    __shared__ unsigned int s_amin, s_amax;
+    __shared__ float s_sum, s_n2, s_pos, s_neg;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const float* qin = queries + (size_t)q * dim;
+    PrepStamps ps;
+    ps.mark(0);
+
+    rotate_into_lds<kThreads>(x, y, qin, dim, D, rotator, rot_blob, trunc, fac, tid);
+
+    double rr = 0.0;
+    for (uint32_t i = tid; i < D; i += kThreads) store_rotated(x[i], q, i, D, rot_out, rot_hl, rank_resid != nullptr, rr);
+    if (rank_resid) { // (uniform) per-wave sums now, their total behind the barrier below
+        rr = wave_sum(rr);
+        if ((tid & 63u) == 0) s_rr[tid >> 6] = rr;
+    }
+
+    ps.mark(1);
+    // QueryPrecomputed::new — strictly sequential sums (Rust iter().sum() folds from -0.0)
+    if (tid == 0) {
+        float s = -0.0f;
+        for (uint32_t i = 0; i < D; ++i) s = s + x[i];
+        s_sum = s;
+        s_kmin = 0x7fffffff;
+        s_kmax = (int)0x80000000;
+        s_amin = 0;
+        s_amax = 0;
+    }
+    if (tid == 64) {
+        float n2 = -0.0f;
+        for (uint32_t i = 0; i < D; ++i) {
+            float p = x[i] * x[i];
+            n2 = n2 + p;
+        }
+        s_n2 = n2;
+    }
+    if (tid == 128) { // sums of the positive / negative elements: range of the ex-code dot product (ex_dot_range)
+        float sp = 0.0f, sn = 0.0f;
+        for (uint32_t i = 0; i < D; ++i) { sp += fmaxf(x[i], 0.0f); sn += fminf(x[i], 0.0f); }
+        s_pos = sp; s_neg = sn;
+    }
+    __syncthreads();
+    if (rank_resid && tid == 0) rank_resid[q] = f16_resid_norm(s_rr, kThreads / 64);
+
+    ps.mark(2);
+    // pack_lut_f32 + QueryLut::new.  D <= 2048 -> at most 2 codebooks per thread.
+    const uint32_t ncb = D / 4;
+    float l[2][16];
+    int kmin = 0x7fffffff, kmax = (int)0x80000000;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        uint32_t c = tid + u * kThreads;
+        if (c < ncb) {
+            lut_entries(x + 4 * c, l[u]);
+            lut_key_range(l[u], kmin, kmax);
+        }
+    }
+    atomicMin(&s_kmin, kmin);
+    atomicMax(&s_kmax, kmax);
+    __syncthreads();
+    const float vl = key_to_float(s_kmin), vr = key_to_float(s_kmax);
+    const float delta = (vr - vl) / 255.0f;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        uint32_t c = tid + u * kThreads;
+        if (c < ncb) {
+            uint32_t emin, emax;
+            const uint4 w = lut_quantise(l[u], vl, delta, emin, emax);
+            atomicAdd(&s_amin, emin);
+            atomicAdd(&s_amax, emax);
+            lut_store(lut_out, q, Dc, c, w);
+        } else if (c < Dc / 4) {
+            lut_store(lut_out, q, Dc, c, make_uint4(0, 0, 0, 0));
+        }
+    }
+    __syncthreads();
+    if (tid == 0) consts[q] = query_consts(s_amin, s_amax, delta, vl, D, s_sum, s_n2, s_pos, s_neg, ex_bits, ps);
+}
+
+// One WAVE per query (4 queries per workgroup), FHT-Kac and identity rotators: the batch path.  Structure of its own: no workgroup
+// barrier after the flip bits are in LDS — the butterflies synchronise through the wave's in-order LDS traffic; the positive /
+// negative sums are taken strided per lane in the pass that writes the query and reduced by a xor tree, as are the range and the u8
+// sums; the two strictly sequential sums (sum q, |q|^2: Rust iter().sum()) run side by side on lanes 0 and 1, 16 elements per step.
+// dynamic LDS: 4 x 2 x D floats (vector + squares per wave) | 4*D/8 flip bytes
+__global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict__ queries, uint32_t nq, uint32_t dim, uint32_t D,
+                                                        uint32_t Dc, int rotator, const uint8_t* __restrict__ rot_blob,
+                                                        uint32_t trunc, float fac, uint32_t ex_bits,
+                                                        float* __restrict__ rot_out, uint8_t* __restrict__ lut_out,
+                                                        QueryConsts* __restrict__ consts,
+                                                        uint16_t* __restrict__ rot_hl, float* __restrict__ rank_resid) {
+    extern __shared__ __align__(16) float sm[];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t q = blockIdx.x * (kThreads / 64) + wave;
+    uint8_t* flips = reinterpret_cast<uint8_t*>(sm + (size_t)2 * (kThreads / 64) * D); // 4*D/8 bytes (FHT-Kac)
+    PrepStamps ps;
+    ps.mark(0);
+    float* x = sm + (size_t)wave * 2 * D;
+    float* x2 = x + D; // squares, for the |q|^2 chain
+    const float* qin = queries + (size_t)q * dim;
+    const bool wave_fht = rotator == 1 && trunc >= 64 && trunc <= 2048; // (else the generic LDS butterflies)
+    if (rotator == 1) {
+        for (uint32_t i = threadIdx.x; i < D / 8; i += kThreads) reinterpret_cast<uint32_t*>(flips)[i] = reinterpret_cast<const uint32_t*>(rot_blob)[i]; // (4 D / 8 flip bytes as dwords: one trip)
+        // the query is requested together with the flip table (round 0's flips straight from the global table): one
+        // round trip in front of the barrier instead of two around it
+        if (q < nq && wave_fht) fhtkac_initial_load(x, qin, dim, D, trunc, rot_blob, lane);
+        __syncthreads(); // the only workgroup barrier: before any wave can leave
+    }
+    if (q >= nq) return; // whole wave
+    rotate_by_wave(x, qin, dim, D, rotator, rot_blob, flips, trunc, fac, lane);
 
     float sp = 0.0f, sn = 0.0f; // sums of the positive / negative elements (ex_dot_range)
     double rr = 0.0;            // (one-product f16 route) squared residual of the image
@@ -419,27 +453,14 @@ __global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict_
         x2[i] = v * v;
         sp += fmaxf(v, 0.0f);
         sn += fminf(v, 0.0f);
-        rot_out[(size_t)q * D + i] = v;
-        if (rank_resid) { // one-product f16 image [nq][D] for k_rank_f16_db and its residual
-            float r;
-            rot_hl[(size_t)q * D + i] = f16_image(v, r);
-            rr += (double)r * (double)r;
-        } else if (rot_hl) { // split-bf16 image for k_rank_bf16_db (hi | lo per K slab: hl_offset)
-            uint16_t h, l;
-            bf16_split(v, h, l);
-            rot_hl[(size_t)q * 2 * D + hl_offset(i, 0, D)] = h;
-            rot_hl[(size_t)q * 2 * D + hl_offset(i, 1, D)] = l;
-        }
+        store_rotated(v, q, i, D, rot_out, rot_hl, rank_resid != nullptr, rr);
     }
     if (rank_resid) { // (uniform)
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) rr += __shfl_xor(rr, d, 64);
+        rr = wave_sum(rr);
         if (lane == 0) rank_resid[q] = f16_resid_norm(&rr, 1);
     }
     group_sync<64>();
-#ifdef RBQ_PREP_STAMPS
-    const unsigned long long pt1 = __builtin_amdgcn_s_memtime();
-#endif
+    ps.mark(1);
     // QueryPrecomputed::new — strictly sequential sums (Rust iter().sum() folds from -0.0): lane 0 adds the
     // elements, lane 1 their squares
     float acc = -0.0f;
@@ -460,21 +481,14 @@ __global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict_
     }
     const float s_sum = __shfl(acc, 0, 64), s_n2 = __shfl(acc, 1, 64);
 
-#ifdef RBQ_PREP_STAMPS
-    const unsigned long long pt2 = __builtin_amdgcn_s_memtime();
-#endif
+    ps.mark(2);
     // pack_lut_f32 + QueryLut::new: pass 1 finds the value range, pass 2 quantises
     const uint32_t ncb = D / 4;
     int kmin = 0x7fffffff, kmax = (int)0x80000000;
     for (uint32_t c = lane; c < ncb; c += 64) {
         float l[16];
         lut_entries(x + 4 * c, l);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int k = total_key(l[j]);
-            kmin = k < kmin ? k : kmin;
-            kmax = k > kmax ? k : kmax;
-        }
+        lut_key_range(l, kmin, kmax);
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) {
@@ -486,31 +500,16 @@ __global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict_
     const float delta = (vr - vl) / 255.0f;
     uint32_t amin = 0, amax = 0;
     for (uint32_t c = lane; c < Dc / 4; c += 64) {
-        uint32_t w[4] = {0, 0, 0, 0};
+        uint4 w = make_uint4(0, 0, 0, 0); // (padding codebook)
         if (c < ncb) {
             float l[16];
             lut_entries(x + 4 * c, l);
-            uint32_t emin = 255, emax = 0;
-            if (delta > 0.0f) {
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    float v = roundf((l[j] - vl) / delta);
-                    v = v >= 0.0f ? v : 0.0f; // also maps NaN -> 0 like `as u8`
-                    v = v > 255.0f ? 255.0f : v;
-                    const uint32_t e = (uint32_t)v;
-                    emin = e < emin ? e : emin;
-                    emax = e > emax ? e : emax;
-                    w[j >> 2] |= e << (8 * (j & 3));
-                }
-            } else {
-                emin = 0;
-            }
+            uint32_t emin, emax;
+            w = lut_quantise(l, vl, delta, emin, emax);
             amin += emin;
             amax += emax;
         }
-        // device LUT order: adjacent codebooks swapped (position p holds codebook p^1) so that nibble m of a
-        // little-endian code dword indexes table (8*dword + m) directly; padding codebooks are all-zero tables
-        *reinterpret_cast<uint4*>(lut_out + (size_t)q * Dc * 4 + (size_t)(c ^ 1u) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        lut_store(lut_out, q, Dc, c, w);
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) {
@@ -519,24 +518,7 @@ __global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict_
         sp += __shfl_xor(sp, d, 64);
         sn += __shfl_xor(sn, d, 64);
     }
-    if (lane == 0) {
-        QueryConsts qc;
-        qc.amin = (float)amin;
-        qc.amax = (float)amax;
-        qc.delta = delta;
-        qc.sum_vl = vl * (float)(D / 4);
-        qc.qnorm = sqrtf(s_n2);
-        qc.qnorm2 = s_n2; qc.q1norm = (sp - sn) * 1.001f;
-        ex_dot_range(sp, sn, ex_bits, qc.exlo, qc.exhi);
-#ifdef RBQ_PREP_STAMPS
-        qc.exlo = (float)(pt1 - pt0); qc.exhi = (float)(pt2 - pt1); qc.q1norm = (float)(__builtin_amdgcn_s_memtime() - pt2); // (lazy selection is off in this build)
-#endif
-        qc.k1x = -0.5f * s_sum;
-        const float cb = -((float)(1u << ex_bits) - 0.5f);
-        qc.kbx = cb * s_sum;
-        qc.scale = (float)(1u << ex_bits);
-        consts[q] = qc;
-    }
+    if (lane == 0) consts[q] = query_consts(amin, amax, delta, vl, D, s_sum, s_n2, sp, sn, ex_bits, ps);
 }
 
 // ---------------------------------------------------------------------------------------------
