@@ -98,4 +98,8 @@ uint64_t rbq_bf_debug_select_launches(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* Growing, shrinking and reading back a brute-force index (rbq_bf_append, rbq_bf_remove_ids, rbq_bf_fetch_embeddings*). */
+#include "rbq_bf_mutate.h"
+
 #endif /* RBQ_BF_H */

@@ -47,6 +47,17 @@ def lib():
         L.rbq_bf_debug_set_chunk_vectors.argtypes = [C.c_uint64]
         L.rbq_bf_debug_select_launches.restype = C.c_uint64
         L.rbq_bf_debug_select_launches.argtypes = []
+        L.rbq_bf_append.restype = C.c_int
+        L.rbq_bf_append.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_float, C.c_uint64, C.POINTER(vp)]
+        L.rbq_bf_remove_ids.restype = C.c_int
+        L.rbq_bf_remove_ids.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(vp)]
+        L.rbq_bf_fetch_embeddings.restype = C.c_int
+        L.rbq_bf_fetch_embeddings.argtypes = [vp, vp, C.c_uint64, vp, vp]
+        L.rbq_bf_fetch_embeddings_device.restype = C.c_int
+        L.rbq_bf_fetch_embeddings_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+        for n in ("rbq_bf_debug_append_carry_ns", "rbq_bf_debug_remove_gather_ns"):
+            getattr(L, n).restype = C.c_uint64
+            getattr(L, n).argtypes = []
         _BOUND = True
     return L
 
@@ -75,8 +86,9 @@ def _filter_words(allowed_ids):
 class BruteForceRabitqIndex:
     """Device-resident brute-force RaBitQ index; methods mirror reference src/brute_force.rs."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, rescale=None):
         self._h = handle
+        self._rescale = rescale  # (mode, t_const) the encoder ran with, where this object knows it: add()'s default
 
     @staticmethod
     def _dev(device):
@@ -86,7 +98,10 @@ class BruteForceRabitqIndex:
     def train(cls, data, total_bits, metric, rotator_type, seed, use_faster_config, device=None):
         """`BruteForceRabitqIndex::train` (src/brute_force.rs:214-287) on the CPU builder, then uploaded."""
         from . import builder
-        return cls.from_built(builder.train_bruteforce(data, total_bits, metric, rotator_type, seed, use_faster_config), device)
+        built = builder.train_bruteforce(data, total_bits, metric, rotator_type, seed, use_faster_config)
+        idx = cls.from_built(built, device)
+        idx._rescale = ("const", built.t_const) if use_faster_config else ("optimal", None)
+        return idx
 
     @classmethod
     def train_on_device(cls, data, total_bits, metric, rotator_type, seed, use_faster_config, device=None, max_chunk_rows=0):
@@ -120,7 +135,7 @@ class BruteForceRabitqIndex:
             _check(lib().rbq_bf_train_device(C.cast(small.hdr_ptr, C.c_void_p), ptr, int(shape[0]),
                                              _abi.RESCALE_CONST if use_faster_config else _abi.RESCALE_OPTIMAL, small.t_const,
                                              int(max_chunk_rows), cls._dev(device), C.byref(h)))
-            return cls(h)
+            return cls(h, ("const", small.t_const) if use_faster_config else ("optimal", None))
         finally:
             small.close()
 
@@ -215,6 +230,93 @@ class BruteForceRabitqIndex:
         """`search` for every row of `queries`, results in input order."""
         ids, scores, counts = self.batch_search_raw(queries, params)
         return [self._results(ids, scores, counts, q) for q in range(ids.shape[0])]
+
+    # -- growth, shrinking and read-back (include/rbq_bf_mutate.h) ----------------------------------------------------
+    def add(self, data, rescale=None, t_const=None, max_chunk_rows=0):
+        """FAISS-style add (rbq_bf_append): the rows of `data` [count][dim] (a host array or a CUDA tensor) join the index with the
+        ids len(self) .. .  The index afterwards equals, array for array, `train` over the old and the new rows.  rescale
+        ("const" / "optimal") and t_const default to what train or train_on_device encoded this object with; an object from
+        load_from_* or from_built has to be given them.  The object's handle is swapped for the grown one and the old one
+        closed.  Returns the id of the first new row."""
+        from . import RabitqError
+        from .index import _rescale
+        if rescale is None:
+            if self._rescale is None:
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "this index does not know what it was encoded with (a loaded index does not "
+                                  "store it): pass rescale= and t_const= to add()")
+            rescale, t_known = self._rescale
+            if t_const is None:
+                t_const = t_known
+        if type(data).__module__.startswith("torch"):
+            import torch
+            x = data.to(dtype=torch.float32).contiguous()
+            if x.is_cuda:
+                ptr = x.data_ptr()
+            else:
+                x = x.numpy()
+                ptr = x.ctypes.data
+        else:
+            x = np.ascontiguousarray(data, dtype=np.float32)
+            ptr = x.ctypes.data
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data must be [count][%d]" % self.dim)
+        mode, t = _rescale(rescale, t_const)
+        first = len(self)
+        h = C.c_void_p()
+        _check(lib().rbq_bf_append(self._h, C.c_void_p(ptr), int(x.shape[0]), mode, t, int(max_chunk_rows), C.byref(h)))
+        old, self._h, self._rescale = self._h, h, (rescale, t_const)
+        lib().rbq_bf_destroy(old)
+        return first
+
+    def remove_ids(self, ids):
+        """FAISS IndexFlat-style remove_ids (rbq_bf_remove_ids): the vectors at the positions `ids` (a host array, a list, or a
+        CUDA int64 / uint64 tensor; any order, repeats allowed, ids >= len ignored) leave the index.  A brute-force index has no id
+        array: the id of a vector is its position, so the survivors keep their order and are RENUMBERED 0 .. len - 1.  The index
+        afterwards equals, array for array, `train` over the rows that stay.  The object's handle is swapped for the shrunk one
+        and the old one closed; the remembered rescale mode stays.  Returns the number of rows removed; an empty `ids` returns 0
+        without a call."""
+        from . import RabitqError
+        if type(ids).__module__.startswith("torch") and ids.is_cuda:
+            import torch
+            if ids.dtype not in (torch.int64, torch.uint64):
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "ids on the device must be int64 or uint64")
+            v = ids.contiguous().reshape(-1)
+            n, p = int(v.numel()), v.data_ptr()
+        else:
+            if type(ids).__module__.startswith("torch"):
+                ids = ids.numpy()
+            if not isinstance(ids, np.ndarray):  # (numpy would make float64 of a list that mixes ints below and above 2^63)
+                ids = np.asarray(ids if hasattr(ids, "__len__") else list(ids), dtype=np.uint64)
+            v = np.ascontiguousarray(ids).astype(np.uint64).reshape(-1)
+            n, p = int(v.size), v.ctypes.data
+        if n == 0:
+            return 0
+        h, removed = C.c_void_p(), C.c_uint64()
+        _check(lib().rbq_bf_remove_ids(self._h, C.c_void_p(p), n, C.byref(removed), C.byref(h)))
+        old, self._h = self._h, h
+        lib().rbq_bf_destroy(old)
+        return int(removed.value)
+
+    def fetch_embeddings(self, ids):
+        """rbq_bf_fetch_embeddings: (out [n, dim] f32, found [n] bool).  Row i is the crate's IVF fetch_embedding of vector ids[i]
+        against the zero centroid, bit for bit; an id >= len gives a zero row and found False."""
+        q = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+        n = int(q.size)
+        out = np.empty((n, self.dim), np.float32)
+        found = np.empty(n, np.uint8)
+        _check(lib().rbq_bf_fetch_embeddings(self._h, q.ctypes.data, n, out.ctypes.data, found.ctypes.data))
+        return out, found.astype(bool)
+
+    def fetch_embedding(self, vector_id):
+        """The reconstructed vector [dim] as a list of floats, or None when the id is not in the index."""
+        out, found = self.fetch_embeddings([vector_id])
+        return out[0].tolist() if found[0] else None
+
+    def fetch_embeddings_device(self, d_ids, n, d_out, d_found, stream=None):
+        """rbq_bf_fetch_embeddings_device: n u64 ids at d_ids (device memory of the index's device) -> d_out [n][dim] f32,
+        d_found [n] u8, enqueued on `stream` (a hipStream_t as int, None = default stream)."""
+        _check(lib().rbq_bf_fetch_embeddings_device(self._h, C.c_void_p(d_ids), int(n), C.c_void_p(d_out), C.c_void_p(d_found),
+                                                    C.c_void_p(stream) if stream else None))
 
     def heap_stats(self):
         """{pushes, tie_pushes} of the BinaryHeap emulation since the index was created (rbq_bf_debug_heap_stats)."""

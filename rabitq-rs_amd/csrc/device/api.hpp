@@ -1,5 +1,5 @@
 // api.hpp — internal header of librbq.so's host side: the C ABI of include/rbq.h over the HIP kernels, which the host
-// units (api_index, api_build, api_append, api_remove, api_search, api_mstg_search, api_save, api_load, api_fetch, api_bf, api_mstg, api_mstg_mutate, api_mstg_persist) reach through launch.hpp.  Not installed.
+// units (api_index, api_build, api_append, api_remove, api_search, api_mstg_search, api_save, api_load, api_fetch, api_bf, api_bf_mutate, api_mstg, api_mstg_mutate, api_mstg_persist) reach through launch.hpp.  Not installed.
 // Host responsibilities: validate like the reference (src/ivf.rs:1754-1769,1484-1702), upload the reference's ClusterData
 // bytes and have the GPU re-lay them into the device layout (one-time, at create/load), own HBM on one or N devices
 // (replicas), and enqueue prep -> rank -> select -> scan for each query batch.  There is no CPU compute path: every failure

@@ -2,7 +2,7 @@
 // Host side: validation, upload, training on the device (rbq_bf_train_device), RBF1 in / out, and per search call: queries -> k_prep (rotation + QueryPrecomputed constants, shared with
 // the IVF path) -> for each chunk of vectors k_bf_dist + k_bf_select (bf.hpp) -> results.  Each call takes a workspace and a stream
 // of its own from the handle's pool, so calls on one handle may overlap.
-#include "api.hpp"
+#include "bf_index.hpp"
 
 using namespace rbq_api;
 
@@ -16,30 +16,8 @@ constexpr uint64_t kBfMaxSubBatch = 1024;
 constexpr uint64_t kBfTrainRowBudget = 512ull << 20; // rotated rows of one training pass (the IVF encoder's scratch budget)
 std::atomic<uint64_t> g_bf_chunk_vectors{0};   // rbq_bf_debug_set_chunk_vectors (0: the default)
 std::atomic<uint64_t> g_bf_select_launches{0}; // rbq_bf_debug_select_launches
-
-struct BfWorkspace {
-    hipStream_t stream = nullptr;
-    DevBuf q, rot, lut, consts, dist, heap_d, heap_s, heap_len, filter, ids, scores, counts, stats;
-    BfWorkspace() = default;
-    BfWorkspace(const BfWorkspace&) = delete;
-    ~BfWorkspace() { if (stream) (void)hipStreamDestroy(stream); } // (deleted under the index's DeviceGuard)
-};
 } // namespace
-} // namespace rbq_api
 
-struct rbq_bf_index : Geometry {
-    int device = 0;
-    rbq_header hdr;                    // rotator_blob -> blob below
-    std::vector<uint8_t> blob;         // host copy of the rotator (RBF1 writer)
-    uint64_t ex_len = 0;               // bytes of ex code per vector as the index holds them (rbq_bf_view::ex_len)
-    Arr rot_blob, bin, ex, f[8];       // f: delta, vl, f_add, f_rescale, f_error, residual_norm, f_add_ex, f_rescale_ex
-    std::mutex mu;
-    std::vector<BfWorkspace*> pool;
-    std::atomic<uint64_t> pushes{0}, tie_pushes{0};
-};
-
-namespace rbq_api {
-namespace {
 void bf_free(rbq_bf_index* ix) {
     if (!ix) return;
     DeviceGuard g(ix->device);
@@ -50,6 +28,73 @@ void bf_free(rbq_bf_index* ix) {
     delete ix;
 }
 
+int bf_new_index(const rbq_header* hdr, uint64_t n, uint64_t ex_len, int dev, BfOwner& own) {
+    own.ix = new rbq_bf_index();
+    rbq_bf_index* ix = own.ix;
+    static_cast<Geometry&>(*ix) = geometry_of(*hdr);
+    ix->device = dev;
+    ix->hdr = *hdr;
+    ix->hdr.n_vectors = n; ix->hdr.n_lists = 0;
+    ix->blob.assign(hdr->rotator_blob, hdr->rotator_blob + hdr->rotator_len);
+    ix->hdr.rotator_blob = ix->blob.data();
+    ix->ex_len = ex_len;
+    const uint64_t D = ix->D;
+    int rc;
+    if ((rc = upload_arr(ix->rot_blob, ix->blob.data(), ix->blob.size())) || (rc = alloc_arr(ix->bin, n * (D / 8))) ||
+        (rc = alloc_arr(ix->ex, n * (D * ix->ex_bits / 8))))
+        return rc;
+    for (Arr& a : ix->f) if ((rc = alloc_arr(a, n * 4))) return rc;
+    return RBQ_OK;
+}
+
+int bf_encode_rows(rbq_bf_index* ix, const float* data, uint64_t n, uint64_t row0, bool opt, float t_const, uint64_t max_chunk_rows) {
+    const uint32_t dim = ix->dim, D = ix->D, ex = ix->ex_bits;
+    const uint64_t bin_len = D / 8, ex_bytes = (uint64_t)D * ex / 8;
+    uint64_t rows = std::max<uint64_t>(64, (kBfTrainRowBudget / ((uint64_t)D * 4)) & ~63ull);
+    if (max_chunk_rows) rows = std::min(rows, max_chunk_rows);
+    rows = std::min(rows, n);
+    const bool on_device = is_device_pointer(data);
+    Scratch t;
+    float *d_in = nullptr, *d_rows = nullptr, *d_zero = nullptr;
+    uint8_t* d_raw = nullptr;
+    double* d_t = nullptr;
+    uint32_t* d_list = nullptr; // k_rescale's block -> list table: every block belongs to "list 0", the zero centroid
+    if (!on_device) HIP_TRY(t.alloc(&d_in, rows * dim * 4));
+    HIP_TRY(t.alloc(&d_rows, rows * D * 4));
+    HIP_TRY(t.alloc(&d_raw, ex ? rows * D : 16));
+    if (opt) {
+        const uint64_t nb = (rows + 31) / 32;
+        HIP_TRY(t.alloc(&d_t, rows * 8));
+        HIP_TRY(t.alloc(&d_zero, (size_t)D * 4));
+        HIP_TRY(t.alloc(&d_list, nb * 4));
+        HIP_TRY(hipMemset(d_zero, 0, (size_t)D * 4));
+        HIP_TRY(hipMemset(d_list, 0, nb * 4));
+    }
+    for (uint64_t c0 = 0; c0 < n; c0 += rows) {
+        const uint32_t nr = (uint32_t)std::min<uint64_t>(rows, n - c0);
+        const uint64_t r0 = row0 + c0;
+        const float* src = data + c0 * dim;
+        if (!on_device) {
+            HIP_TRY(hipMemcpy(d_in, src, (size_t)nr * dim * 4, hipMemcpyHostToDevice));
+            src = d_in;
+        }
+        HIP_TRY(launch_rotate_rows(src, nullptr, nr, dim, D, (int)ix->rotator, (const uint8_t*)ix->rot_blob.p, ix->trunc, ix->fac, d_rows, 0));
+        if (opt) HIP_TRY(launch_rescale(d_rows, d_zero, d_list, nullptr, nullptr, nr, D, ex, false, d_t, 0));
+        EncodeParams P;
+        P.rows = d_rows; P.centroids = nullptr; P.slot_src = nullptr; P.block_list = nullptr; P.row_slot = nullptr; P.t_row = d_t;
+        P.blocks = (uint8_t*)ix->bin.p + r0 * bin_len; P.raw_ex = d_raw; P.ids = nullptr; P.src_base = 0;
+        P.delta = (float*)ix->f[0].p + r0; P.vl = (float*)ix->f[1].p + r0; P.f_add = (float*)ix->f[2].p + r0;
+        P.f_rescale = (float*)ix->f[3].p + r0; P.f_error = (float*)ix->f[4].p + r0; P.residual_norm = (float*)ix->f[5].p + r0;
+        P.f_add_ex = (float*)ix->f[6].p + r0; P.f_rescale_ex = (float*)ix->f[7].p + r0;
+        P.nslots = nr; P.D = D; P.Dc = ix->Dc; P.ex_bits = ex; P.metric = ix->metric; P.t_const = t_const;
+        HIP_TRY(launch_bf_encode(P, 0));
+        if (ex) HIP_TRY(launch_bf_pack_ex(d_raw, nr, D, ex, (uint8_t*)ix->ex.p + r0 * ex_bytes, 0));
+        HIP_TRY(hipDeviceSynchronize()); // the scratch (and the staging copy of a host caller's rows) is reused by the next chunk
+    }
+    return RBQ_OK;
+}
+
+namespace {
 int bf_create_impl(const rbq_header* hdr, const rbq_bf_view* v, int device, rbq_bf_index** out) {
     if (!out) return fail(RBQ_INVALID_CONFIG, "null output");
     *out = nullptr;
@@ -89,12 +134,6 @@ int bf_create_impl(const rbq_header* hdr, const rbq_bf_view* v, int device, rbq_
     return RBQ_OK;
 }
 
-struct BfOwner { // frees a half-built index on an early return
-    rbq_bf_index* ix;
-    ~BfOwner() { if (ix) bf_free(ix); }
-    rbq_bf_index* release() { rbq_bf_index* r = ix; ix = nullptr; return r; }
-};
-
 // BruteForceRabitqIndex::train (src/brute_force.rs:214-285) on the device, a chunk of rows at a time: k_rotate_rows ->
 // k_rescale (OPTIMAL) -> k_encode's flat mode against the zero centroid -> k_bf_pack_ex, straight into the index's arrays.
 int bf_train_impl(const rbq_header* hdr, const float* data, uint64_t n, int rescale, float t_const, uint64_t max_chunk_rows, int device,
@@ -118,62 +157,11 @@ int bf_train_impl(const rbq_header* hdr, const float* data, uint64_t n, int resc
     DeviceGuard g(dev);
     if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
 
-    BfOwner own{new rbq_bf_index()};
-    rbq_bf_index* ix = own.ix;
-    static_cast<Geometry&>(*ix) = geometry_of(*hdr);
-    ix->device = dev;
-    ix->hdr = *hdr;
-    ix->hdr.n_vectors = n; ix->hdr.n_lists = 0;
-    ix->blob.assign(hdr->rotator_blob, hdr->rotator_blob + hdr->rotator_len);
-    ix->hdr.rotator_blob = ix->blob.data();
-    const uint32_t dim = ix->dim, D = ix->D, ex = ix->ex_bits;
-    const uint64_t bin_len = D / 8, ex_bytes = (uint64_t)D * ex / 8;
-    ix->ex_len = ex ? ex_bytes : D / 8; // a trained 1-bit index carries D/8 zero bytes of ex code per vector (rbq_bf_view::ex_len)
-    if ((rc = upload_arr(ix->rot_blob, ix->blob.data(), ix->blob.size())) || (rc = alloc_arr(ix->bin, n * bin_len)) ||
-        (rc = alloc_arr(ix->ex, n * ex_bytes)))
-        return rc;
-    for (Arr& a : ix->f) if ((rc = alloc_arr(a, n * 4))) return rc;
-
-    uint64_t rows = std::max<uint64_t>(64, (kBfTrainRowBudget / ((uint64_t)D * 4)) & ~63ull);
-    if (max_chunk_rows) rows = std::min(rows, max_chunk_rows);
-    rows = std::min(rows, n);
-    const bool on_device = is_device_pointer(data);
-    Scratch t;
-    float *d_in = nullptr, *d_rows = nullptr, *d_zero = nullptr;
-    uint8_t* d_raw = nullptr;
-    double* d_t = nullptr;
-    uint32_t* d_list = nullptr; // k_rescale's block -> list table: every block belongs to "list 0", the zero centroid
-    if (!on_device) HIP_TRY(t.alloc(&d_in, rows * dim * 4));
-    HIP_TRY(t.alloc(&d_rows, rows * D * 4));
-    HIP_TRY(t.alloc(&d_raw, ex ? rows * D : 16));
-    if (opt) {
-        const uint64_t nb = (rows + 31) / 32;
-        HIP_TRY(t.alloc(&d_t, rows * 8));
-        HIP_TRY(t.alloc(&d_zero, (size_t)D * 4));
-        HIP_TRY(t.alloc(&d_list, nb * 4));
-        HIP_TRY(hipMemset(d_zero, 0, (size_t)D * 4));
-        HIP_TRY(hipMemset(d_list, 0, nb * 4));
-    }
-    for (uint64_t r0 = 0; r0 < n; r0 += rows) {
-        const uint32_t nr = (uint32_t)std::min<uint64_t>(rows, n - r0);
-        const float* src = data + r0 * dim;
-        if (!on_device) {
-            HIP_TRY(hipMemcpy(d_in, src, (size_t)nr * dim * 4, hipMemcpyHostToDevice));
-            src = d_in;
-        }
-        HIP_TRY(launch_rotate_rows(src, nullptr, nr, dim, D, (int)ix->rotator, (const uint8_t*)ix->rot_blob.p, ix->trunc, ix->fac, d_rows, 0));
-        if (opt) HIP_TRY(launch_rescale(d_rows, d_zero, d_list, nullptr, nullptr, nr, D, ex, false, d_t, 0));
-        EncodeParams P;
-        P.rows = d_rows; P.centroids = nullptr; P.slot_src = nullptr; P.block_list = nullptr; P.row_slot = nullptr; P.t_row = d_t;
-        P.blocks = (uint8_t*)ix->bin.p + r0 * bin_len; P.raw_ex = d_raw; P.ids = nullptr; P.src_base = 0;
-        P.delta = (float*)ix->f[0].p + r0; P.vl = (float*)ix->f[1].p + r0; P.f_add = (float*)ix->f[2].p + r0;
-        P.f_rescale = (float*)ix->f[3].p + r0; P.f_error = (float*)ix->f[4].p + r0; P.residual_norm = (float*)ix->f[5].p + r0;
-        P.f_add_ex = (float*)ix->f[6].p + r0; P.f_rescale_ex = (float*)ix->f[7].p + r0;
-        P.nslots = nr; P.D = D; P.Dc = ix->Dc; P.ex_bits = ex; P.metric = ix->metric; P.t_const = t_const;
-        HIP_TRY(launch_bf_encode(P, 0));
-        if (ex) HIP_TRY(launch_bf_pack_ex(d_raw, nr, D, ex, (uint8_t*)ix->ex.p + r0 * ex_bytes, 0));
-        HIP_TRY(hipDeviceSynchronize()); // the scratch (and the staging copy of a host caller's rows) is reused by the next chunk
-    }
+    BfOwner own{nullptr};
+    // a trained 1-bit index carries D/8 zero bytes of ex code per vector (rbq_bf_view::ex_len)
+    const uint64_t D = hdr->padded_dim;
+    if ((rc = bf_new_index(hdr, n, hdr->ex_bits ? D * hdr->ex_bits / 8 : D / 8, dev, own))) return rc;
+    if ((rc = bf_encode_rows(own.ix, data, n, 0, opt != 0, t_const, max_chunk_rows))) return rc;
     *out = own.release();
     return RBQ_OK;
 }

@@ -27,4 +27,16 @@ __device__ __forceinline__ uint32_t dev_ex_code(const uint8_t* __restrict__ exs,
     return raw & ((1u << ex_bits) - 1u);
 }
 
+// ex code of dimension i of one vector's ex_code_packed as the brute-force index holds it (the cpp-compat packings, rbq_build.cpp
+// pack_ex2 / pack_ex6): per 16 dimensions, 2 bits: 4 bytes, byte b bits 2g = dimension 4g + b; 6 bits: 12 bytes, byte b < 8 holds
+// the low nibbles of dimensions b and b + 8, bytes 8-11 the top two bits laid out like the 2-bit packing
+__device__ __forceinline__ uint32_t flat_ex_code(const uint8_t* __restrict__ row, uint32_t ex_bits, uint32_t i) {
+    const uint32_t t = i >> 4, j = i & 15u, g = j >> 2, b = j & 3u;
+    if (ex_bits == 2) return ((uint32_t)row[t * 4u + b] >> (2u * g)) & 3u;
+    const uint8_t* u = row + t * 12u;
+    const uint32_t lo = ((uint32_t)u[j & 7u] >> (j < 8u ? 0u : 4u)) & 15u;
+    const uint32_t top = ((uint32_t)u[8u + b] >> (2u * g)) & 3u;
+    return lo | (top << 4);
+}
+
 } // namespace rbq

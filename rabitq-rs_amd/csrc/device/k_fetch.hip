@@ -20,13 +20,11 @@
 #include "launch.hpp"
 #include "kernels.hpp"
 #include "codes.hpp"
+#include "fetch.hpp"
 
 namespace rbq {
 
 namespace {
-
-constexpr uint32_t kFetchThreads = 256;
-constexpr uint32_t kFetchMaxD = 2048; // validate_header's padded_dim bound: 8 KB of LDS per vector
 
 __global__ __launch_bounds__(256) void k_fetch_gather(const uint64_t* __restrict__ vstart, const uint32_t* __restrict__ list_gb0,
                                                       uint32_t n_lists, const uint64_t* __restrict__ slot_ids, uint64_t n_vectors,
@@ -62,42 +60,6 @@ __device__ __forceinline__ float fetch_recon(const FetchParams& P, const uint8_t
     const uint32_t code = ex + (bit << P.ex_bits);
     const float t = cent[i] + delta * (float)code;
     return t + vl;
-}
-
-__device__ __forceinline__ void lds_scale(float* s, uint32_t a, uint32_t e, float f) {
-    for (uint32_t i = a + threadIdx.x; i < e; i += blockDim.x) s[i] = s[i] * f;
-    __syncthreads();
-}
-
-// flip_sign with round r's flip bits (bit i % 8 of byte i / 8, LSB first)
-__device__ __forceinline__ void lds_flip(float* s, uint32_t D, const uint8_t* __restrict__ flip) {
-    for (uint32_t i = threadIdx.x; i < D; i += blockDim.x)
-        if ((flip[i >> 3] >> (i & 7u)) & 1u) s[i] = -s[i];
-    __syncthreads();
-}
-
-// fht over s[0, n), n a power of two: stage h pairs (j, j + h); every butterfly is (x + y, x - y)
-__device__ __forceinline__ void lds_fht(float* s, uint32_t n) {
-    for (uint32_t h = 1; h < n; h <<= 1) {
-        for (uint32_t k = threadIdx.x; k < n / 2; k += blockDim.x) {
-            const uint32_t j = ((k & ~(h - 1)) << 1) | (k & (h - 1));
-            const float x = s[j], y = s[j + h];
-            s[j] = x + y;
-            s[j + h] = x - y;
-        }
-        __syncthreads();
-    }
-}
-
-// kacs_walk over s[0, D)
-__device__ __forceinline__ void lds_kac(float* s, uint32_t D) {
-    const uint32_t half = D / 2;
-    for (uint32_t i = threadIdx.x; i < half; i += blockDim.x) {
-        const float x = s[i], y = s[i + half];
-        s[i] = x + y;
-        s[i + half] = x - y;
-    }
-    __syncthreads();
 }
 
 template <bool kMatrix>
@@ -153,27 +115,7 @@ __global__ __launch_bounds__(kFetchThreads) void k_fetch_vec(FetchParams P, cons
             for (uint32_t i = tid; i < D; i += blockDim.x) s[i] = fetch_recon(P, blk, exs, cent, slot & 31u, delta, vl, i);
             __syncthreads();
         }
-        const uint32_t fo = D / 8;
-        if (P.trunc == D) { // rounds 4..1: *= 1/fac, fht, *= 1/D, flip
-            for (int r = 3; r >= 0; --r) {
-                lds_scale(s, 0, D, P.rfac);
-                lds_fht(s, D);
-                lds_scale(s, 0, D, P.rlen);
-                lds_flip(s, D, P.rot_blob + r * fo);
-            }
-        } else {            // *= 4, then rounds 4..1: *= 0.5, kacs_walk, on the segment *= 1/fac, fht, *= 1/trunc, flip
-            const uint32_t T = P.trunc, start = D - T;
-            lds_scale(s, 0, D, 4.0f);
-            for (int r = 3; r >= 0; --r) {
-                const uint32_t a = (r & 1) ? start : 0u; // rounds 4 and 2: [start..]; 3 and 1: [..trunc]
-                lds_scale(s, 0, D, 0.5f);
-                lds_kac(s, D);
-                lds_scale(s, a, a + T, P.rfac);
-                lds_fht(s + a, T);
-                lds_scale(s, a, a + T, P.rlen);
-                lds_flip(s, D, P.rot_blob + r * fo);
-            }
-        }
+        lds_inverse_fht_kac(s, D, P.trunc, P.rfac, P.rlen, P.rot_blob);
         for (uint32_t i = tid; i < dim; i += blockDim.x) o[i] = s[i];
         __syncthreads(); // s is rewritten by the next id
     }
@@ -262,10 +204,15 @@ hipError_t launch_fetch(const FetchParams& P, const uint64_t* ids, uint64_t n, f
     hipLaunchKernelGGL(k_fetch_vec<true>, dim3(grid), dim3(kFetchThreads), 0, s, P, ids, n, out, found, rows);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_fetch_matrix((const float*)P.rot_blob, rows, found, n, P.D, P.dim, out, s);
+}
+
+hipError_t launch_fetch_matrix(const float* R, const float* rows, const uint8_t* found, uint64_t n, uint32_t D, uint32_t dim, float* out,
+                               hipStream_t s) {
+    if (!n) return hipSuccess;
     const uint64_t gx = (n + kMatT - 1) / kMatT;
     if (gx > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_fetch_matrix, dim3((uint32_t)gx, (P.dim + kMatT - 1) / kMatT), dim3(256), 0, s, (const float*)P.rot_blob,
-                       (const float*)rows, (const uint8_t*)found, n, P.D, P.dim, out);
+    hipLaunchKernelGGL(k_fetch_matrix, dim3((uint32_t)gx, (dim + kMatT - 1) / kMatT), dim3(256), 0, s, R, rows, found, n, D, dim, out);
     return hipGetLastError();
 }
 

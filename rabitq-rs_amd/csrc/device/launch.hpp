@@ -568,5 +568,41 @@ struct FetchParams {
 // n ids -> out [n][dim] f32, found [n] u8 (a missing id: zero row, 0).  Matrix rotator: `rows` is [n][D] f32 scratch.
 hipError_t launch_fetch(const FetchParams& P, const uint64_t* ids, uint64_t n, float* out, uint8_t* found, float* rows,
                         hipStream_t s);
+// The Matrix rotator's inverse alone (k_fetch_matrix): out[v][col] = found[v] ? sum over r of R[r][col] * rows[v][r] : 0
+hipError_t launch_fetch_matrix(const float* R, const float* rows, const uint8_t* found, uint64_t n, uint32_t D, uint32_t dim, float* out,
+                               hipStream_t s);
+
+// ---- rbq_bf_remove_ids / rbq_bf_fetch_embeddings (k_bf_mutate.hip; include/rbq_bf_mutate.h) -----------------
+// keep[i] = 0 for every i = ids[j] < n; the caller fills keep [n] with ones first (ids are positions: no sort)
+hipError_t launch_bf_mark(const uint64_t* ids, uint64_t n_ids, uint64_t n, uint8_t* keep, hipStream_t s);
+// rank[i] = kept rows (keep[j] != 0) before row i, i < n; tmp == null returns the scratch size in *tmp_bytes.  The caller scans
+// one entry more than the index has rows (keep's last entry 0): rank's last value is the number of survivors.
+hipError_t bf_scan_kept(void* tmp, size_t* tmp_bytes, const uint8_t* keep, uint32_t* rank, uint64_t n, hipStream_t s);
+// map[rank[i]] = i for every kept row i < n
+hipError_t launch_bf_row_map(const uint8_t* keep, const uint32_t* rank, uint64_t n, uint32_t* map, hipStream_t s);
+// The flat arrays of a brute-force index gathered into those of a shrunk one: new row r takes old row map[r] — its sign code
+// (bin_len bytes), its ex code (ex_len bytes; 0: none held) and its eight factors.
+struct BfGatherParams {
+    const uint32_t* map; // [n_new], ascending, every entry < n_old
+    uint64_t n_new, n_old;
+    uint32_t bin_len, ex_len;
+    const uint8_t *bin_s, *ex_s;
+    uint8_t *bin_d, *ex_d;
+    const float* f_s[8];
+    float* f_d[8];
+};
+hipError_t launch_bf_gather(const BfGatherParams& P, int device, hipStream_t s);
+// fetch_embedding against the zero centroid from the flat layout: n ids -> out [n][dim] f32, found [n] u8 (an id >= n_vectors:
+// zero row, 0).  Matrix rotator: `rows` is [n][D] f32 scratch, and launch_fetch_matrix follows.
+struct BfFetchParams {
+    const uint8_t *bin, *ex;  // [n_vectors][D / 8] MSB-first sign bits; [n_vectors][D * ex_bits / 8] cpp-compat ex codes
+    const float *delta, *vl;  // [n_vectors]
+    const uint8_t* rot_blob;  // FHT-Kac: 4 x D / 8 flip bytes; Matrix: [D][D] f32 row-major
+    uint64_t n_vectors;
+    uint32_t dim, D, ex_bits, rotator, trunc;
+    float rfac, rlen;         // 1 / fac and 1 / (FHT length), f32 divisions on the host
+};
+hipError_t launch_bf_fetch(const BfFetchParams& P, const uint64_t* ids, uint64_t n, float* out, uint8_t* found, float* rows,
+                           hipStream_t s);
 
 } // namespace rbq
