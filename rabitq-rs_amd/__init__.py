@@ -31,9 +31,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _abi
-from ._abi import (METRIC_IP, METRIC_L2, ROTATOR_FHT_KAC, ROTATOR_MATRIX, RBQ_OK)
-
-ROTATOR_NONE = 2
+from ._abi import (METRIC_IP, METRIC_L2, ROTATOR_FHT_KAC, ROTATOR_MATRIX, ROTATOR_NONE, RBQ_OK)
 
 
 class Metric:

@@ -9,57 +9,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _abi
-from .index import _check, _detail  # noqa: F401  (shared error mapping)
-
-_BOUND = False
-
-
-def lib():
-    """librbq.so with the rbq_bf_* signatures bound (the same library object as index.lib())."""
-    global _BOUND
-    from .index import lib as base
-    L = base()
-    if not _BOUND:
-        vp = C.c_void_p
-        L.rbq_bf_create.restype = C.c_int
-        L.rbq_bf_create.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
-        L.rbq_bf_train_device.restype = C.c_int
-        L.rbq_bf_train_device.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.POINTER(vp)]
-        L.rbq_bf_load_rbf1.restype = C.c_int
-        L.rbq_bf_load_rbf1.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp)]
-        L.rbq_bf_save_rbf1.restype = C.c_int
-        L.rbq_bf_save_rbf1.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
-        L.rbq_bf_free_bytes.restype = None
-        L.rbq_bf_free_bytes.argtypes = [C.POINTER(C.c_uint8)]
-        L.rbq_bf_destroy.restype = None
-        L.rbq_bf_destroy.argtypes = [vp]
-        L.rbq_bf_len.restype = C.c_uint64
-        L.rbq_bf_len.argtypes = [vp]
-        for n in ("rbq_bf_dim", "rbq_bf_padded_dim"):
-            getattr(L, n).restype = C.c_uint32
-            getattr(L, n).argtypes = [vp]
-        L.rbq_bf_search_batch.restype = C.c_int
-        L.rbq_bf_search_batch.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
-        L.rbq_bf_debug_heap_stats.restype = None
-        L.rbq_bf_debug_heap_stats.argtypes = [vp, vp]
-        L.rbq_bf_debug_set_chunk_vectors.restype = C.c_uint64
-        L.rbq_bf_debug_set_chunk_vectors.argtypes = [C.c_uint64]
-        L.rbq_bf_debug_select_launches.restype = C.c_uint64
-        L.rbq_bf_debug_select_launches.argtypes = []
-        L.rbq_bf_append.restype = C.c_int
-        L.rbq_bf_append.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_float, C.c_uint64, C.POINTER(vp)]
-        L.rbq_bf_remove_ids.restype = C.c_int
-        L.rbq_bf_remove_ids.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(vp)]
-        L.rbq_bf_fetch_embeddings.restype = C.c_int
-        L.rbq_bf_fetch_embeddings.argtypes = [vp, vp, C.c_uint64, vp, vp]
-        L.rbq_bf_fetch_embeddings_device.restype = C.c_int
-        L.rbq_bf_fetch_embeddings_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
-        for n in ("rbq_bf_debug_append_carry_ns", "rbq_bf_debug_remove_gather_ns"):
-            getattr(L, n).restype = C.c_uint64
-            getattr(L, n).argtypes = []
-        _BOUND = True
-    return L
+from . import _abi, _marshal
+from .index import _check, _detail, lib  # noqa: F401  (shared error mapping; the rbq_bf_* entry points live in the same librbq.so)
 
 
 @dataclass(frozen=True)
@@ -116,19 +67,14 @@ class BruteForceRabitqIndex:
             raise RabitqError(_abi.RBQ_INVALID_CONFIG, "training data must be non-empty")
         if not 1 <= int(total_bits) <= 16:
             raise RabitqError(_abi.RBQ_INVALID_CONFIG, "total_bits must be between 1 and 16")
-        is_tensor = type(data).__module__.startswith("torch")
-        if is_tensor:
-            import torch
-            if data.is_cuda:
-                if device is not None and data.device.index != int(device):
-                    data = data.to(torch.device("cuda", int(device)))
-                x = data.to(dtype=torch.float32).contiguous()
-                ptr, row0, device = x.data_ptr(), x[:1].cpu().numpy(), x.device.index
-            else:
-                data, is_tensor = data.numpy(), False
-        if not is_tensor:
-            x = np.ascontiguousarray(data, dtype=np.float32)
-            ptr, row0 = x.ctypes.data, x[:1]
+        torch = _marshal.torch_of(data)
+        if torch is not None and data.is_cuda and device is not None and data.device.index != int(device):
+            data = data.to(torch.device("cuda", int(device)))
+        ptr, x = _marshal.rows_arg(data)  # (x owns what ptr names)
+        if isinstance(x, np.ndarray):
+            row0 = x[:1]
+        else:
+            row0, device = x[:1].cpu().numpy(), x.device.index
         small = builder.train_bruteforce(row0, total_bits, metric, rotator_type, seed, use_faster_config)  # (its own checks)
         try:
             h = C.c_void_p()
@@ -165,13 +111,7 @@ class BruteForceRabitqIndex:
 
     def save_to_bytes(self):
         """`save_to_writer` (src/brute_force.rs:305-386), byte for byte."""
-        p = C.POINTER(C.c_uint8)()
-        n = C.c_uint64()
-        _check(lib().rbq_bf_save_rbf1(self._h, C.byref(p), C.byref(n)))
-        try:
-            return C.string_at(p, n.value)
-        finally:
-            lib().rbq_bf_free_bytes(p)
+        return _marshal.owned_bytes(lambda p, n: _check(lib().rbq_bf_save_rbf1(self._h, p, n)), lib().rbq_bf_free_bytes)
 
     def save_to_path(self, path):
         data = self.save_to_bytes()
@@ -240,33 +180,22 @@ class BruteForceRabitqIndex:
         closed.  Returns the id of the first new row."""
         from . import RabitqError
         from .index import _rescale
-        if rescale is None:
-            if self._rescale is None:
-                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "this index does not know what it was encoded with (a loaded index does not "
-                                  "store it): pass rescale= and t_const= to add()")
-            rescale, t_known = self._rescale
-            if t_const is None:
-                t_const = t_known
-        if type(data).__module__.startswith("torch"):
-            import torch
-            x = data.to(dtype=torch.float32).contiguous()
-            if x.is_cuda:
-                ptr = x.data_ptr()
-            else:
-                x = x.numpy()
-                ptr = x.ctypes.data
-        else:
-            x = np.ascontiguousarray(data, dtype=np.float32)
-            ptr = x.ctypes.data
+        rescale, t_const = _marshal.known_rescale(self._rescale, rescale, t_const)
+        ptr, x = _marshal.rows_arg(data)  # (x owns what ptr names)
         if x.ndim != 2 or x.shape[1] != self.dim:
             raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data must be [count][%d]" % self.dim)
         mode, t = _rescale(rescale, t_const)
         first = len(self)
         h = C.c_void_p()
-        _check(lib().rbq_bf_append(self._h, C.c_void_p(ptr), int(x.shape[0]), mode, t, int(max_chunk_rows), C.byref(h)))
-        old, self._h, self._rescale = self._h, h, (rescale, t_const)
-        lib().rbq_bf_destroy(old)
+        _check(lib().rbq_bf_append(self._h, ptr, int(x.shape[0]), mode, t, int(max_chunk_rows), C.byref(h)))
+        self._rescale = (rescale, t_const)
+        self._swap(h)
         return first
+
+    def _swap(self, h):
+        """The handle a mutation returned takes the place of the old one, which is closed."""
+        old, self._h = self._h, h
+        lib().rbq_bf_destroy(old)
 
     def remove_ids(self, ids):
         """FAISS IndexFlat-style remove_ids (rbq_bf_remove_ids): the vectors at the positions `ids` (a host array, a list, or a
@@ -275,37 +204,18 @@ class BruteForceRabitqIndex:
         afterwards equals, array for array, `train` over the rows that stay.  The object's handle is swapped for the shrunk one
         and the old one closed; the remembered rescale mode stays.  Returns the number of rows removed; an empty `ids` returns 0
         without a call."""
-        from . import RabitqError
-        if type(ids).__module__.startswith("torch") and ids.is_cuda:
-            import torch
-            if ids.dtype not in (torch.int64, torch.uint64):
-                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "ids on the device must be int64 or uint64")
-            v = ids.contiguous().reshape(-1)
-            n, p = int(v.numel()), v.data_ptr()
-        else:
-            if type(ids).__module__.startswith("torch"):
-                ids = ids.numpy()
-            if not isinstance(ids, np.ndarray):  # (numpy would make float64 of a list that mixes ints below and above 2^63)
-                ids = np.asarray(ids if hasattr(ids, "__len__") else list(ids), dtype=np.uint64)
-            v = np.ascontiguousarray(ids).astype(np.uint64).reshape(-1)
-            n, p = int(v.size), v.ctypes.data
+        n, p, _ids = _marshal.ids_arg(ids)  # (_ids owns what p names)
         if n == 0:
             return 0
         h, removed = C.c_void_p(), C.c_uint64()
-        _check(lib().rbq_bf_remove_ids(self._h, C.c_void_p(p), n, C.byref(removed), C.byref(h)))
-        old, self._h = self._h, h
-        lib().rbq_bf_destroy(old)
+        _check(lib().rbq_bf_remove_ids(self._h, p, n, C.byref(removed), C.byref(h)))
+        self._swap(h)
         return int(removed.value)
 
     def fetch_embeddings(self, ids):
         """rbq_bf_fetch_embeddings: (out [n, dim] f32, found [n] bool).  Row i is the crate's IVF fetch_embedding of vector ids[i]
         against the zero centroid, bit for bit; an id >= len gives a zero row and found False."""
-        q = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
-        n = int(q.size)
-        out = np.empty((n, self.dim), np.float32)
-        found = np.empty(n, np.uint8)
-        _check(lib().rbq_bf_fetch_embeddings(self._h, q.ctypes.data, n, out.ctypes.data, found.ctypes.data))
-        return out, found.astype(bool)
+        return _marshal.fetch_embeddings(lib().rbq_bf_fetch_embeddings, self._h, self.dim, ids)
 
     def fetch_embedding(self, vector_id):
         """The reconstructed vector [dim] as a list of floats, or None when the id is not in the index."""
@@ -315,8 +225,7 @@ class BruteForceRabitqIndex:
     def fetch_embeddings_device(self, d_ids, n, d_out, d_found, stream=None):
         """rbq_bf_fetch_embeddings_device: n u64 ids at d_ids (device memory of the index's device) -> d_out [n][dim] f32,
         d_found [n] u8, enqueued on `stream` (a hipStream_t as int, None = default stream)."""
-        _check(lib().rbq_bf_fetch_embeddings_device(self._h, C.c_void_p(d_ids), int(n), C.c_void_p(d_out), C.c_void_p(d_found),
-                                                    C.c_void_p(stream) if stream else None))
+        _marshal.fetch_embeddings_device(lib().rbq_bf_fetch_embeddings_device, self._h, d_ids, n, d_out, d_found, stream)
 
     def heap_stats(self):
         """{pushes, tie_pushes} of the BinaryHeap emulation since the index was created (rbq_bf_debug_heap_stats)."""

@@ -8,7 +8,8 @@ import os
 
 import numpy as np
 
-from ._abi import BF_FACTORS, ROTATOR_FHT_KAC, BfView, Header, ListView, MstgConfig, RBQ_OK
+from ._abi import BF_FACTORS, LIBRBQ_BUILD, ROTATOR_FHT_KAC, RBQ_OK, MstgConfig, bind
+from ._marshal import owned_bytes
 
 # the device library's message for a padded_dim that is not a multiple of 16 (validate_header); the CPU builders return only the code
 NOT_MULTIPLE_OF_16 = "Dimension must be multiple of 16 for SIMD"
@@ -23,77 +24,11 @@ def lib():
         path = os.environ.get("RBQ_BUILD_LIB") or os.path.join(_HERE, "csrc", "librbq_build.so")  # (override: the sanitizer build)
         if not os.path.exists(path):
             raise RuntimeError(f"{path} missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        L = C.CDLL(path)
-        L.rbq_build_train_with_clusters.restype = C.c_int
-        L.rbq_build_train_with_clusters.argtypes = [
-            C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
-            C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
-        L.rbq_built_header.restype = C.POINTER(Header)
-        L.rbq_built_header.argtypes = [C.c_void_p]
-        L.rbq_built_lists.restype = C.POINTER(ListView)
-        L.rbq_built_lists.argtypes = [C.c_void_p]
-        L.rbq_built_t_const.restype = C.c_float
-        L.rbq_built_t_const.argtypes = [C.c_void_p]
-        L.rbq_built_list_recon.restype = C.c_int
-        L.rbq_built_list_recon.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float))]
-        L.rbq_built_list_residual_norm.restype = C.c_int
-        L.rbq_built_list_residual_norm.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.POINTER(C.c_float))]
-        L.rbq_build_mstg_file_check.restype = C.c_int
-        L.rbq_build_mstg_file_check.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(MstgConfig), C.c_void_p]
-        L.rbq_built_free.argtypes = [C.c_void_p]
-        L.rbq_built_save_rbq1.restype = C.c_int
-        L.rbq_built_save_rbq1.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
-        L.rbq_build_free_bytes.argtypes = [C.POINTER(C.c_uint8)]
-        L.rbq_build_crc32.restype = C.c_uint32
-        L.rbq_build_crc32.argtypes = [C.c_void_p, C.c_uint64]
-        L.rbq_build_kmeans.restype = C.c_int
-        L.rbq_build_kmeans.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_uint64,
-                                       C.c_void_p, C.c_void_p]
-        L.rbq_build_kmeans_faiss.restype = C.c_int
-        L.rbq_build_kmeans_faiss.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
-                                             C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
-                                             C.c_void_p]
-        for name in ("rbq_build_pack_binary_code", "rbq_build_pack_ex_code_1bit",
-                     "rbq_build_pack_ex_code_2bit", "rbq_build_pack_ex_code_6bit"):
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
-        L.rbq_build_best_rescale_factor.restype = C.c_double
-        L.rbq_build_best_rescale_factor.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32]
-        L.rbq_build_pack_codes.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
-        L.rbq_build_rotate.argtypes = [C.POINTER(Header), C.c_void_p, C.c_void_p]
-        L.rbq_build_train_bruteforce.restype = C.c_int
-        L.rbq_build_train_bruteforce.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8,
-                                                 C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
-        L.rbq_bf_built_header.restype = C.POINTER(Header)
-        L.rbq_bf_built_header.argtypes = [C.c_void_p]
-        L.rbq_bf_built_view.restype = C.POINTER(BfView)
-        L.rbq_bf_built_view.argtypes = [C.c_void_p]
-        L.rbq_bf_built_t_const.restype = C.c_float
-        L.rbq_bf_built_t_const.argtypes = [C.c_void_p]
-        L.rbq_bf_built_free.argtypes = [C.c_void_p]
-        L.rbq_build_closure_assign.restype = C.c_int
-        L.rbq_build_closure_assign.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_float, C.c_uint32,
-                                               C.c_void_p, C.c_void_p]
-        L.rbq_build_mstg_select_lists.restype = C.c_int
-        L.rbq_build_mstg_select_lists.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float,
-                                                  C.c_void_p, C.c_void_p]
-        L.rbq_build_hcluster.restype = C.c_int
-        L.rbq_build_hcluster.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_uint64,
-                                         C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)]
-        bind_hclustered(L)
-        _LIB = L
+        _LIB = bind(C.CDLL(path), LIBRBQ_BUILD)
     return _LIB
 
 
 HCLUSTER_STATS = ("splits", "balance_moves", "empty_reseeded", "rng_draws", "host_splits", "arena_bytes")
-
-
-def bind_hclustered(L):
-    """The accessors of an rbq_hclustered handle (the same in librbq_build.so and librbq.so)."""
-    for name, res in (("count", C.c_uint64), ("centroids", C.POINTER(C.c_float)), ("offsets", C.POINTER(C.c_uint64)),
-                      ("members", C.POINTER(C.c_uint32)), ("stats", C.POINTER(C.c_uint64))):
-        f = getattr(L, "rbq_hclustered_" + name)
-        f.restype, f.argtypes = res, [C.c_void_p]
-    L.rbq_hclustered_free.restype, L.rbq_hclustered_free.argtypes = None, [C.c_void_p]
 
 
 def take_hclustered(L, h, n, dim):
@@ -188,13 +123,9 @@ class BuiltIndex:
         return out
 
     def save_rbq1(self):
-        p = C.POINTER(C.c_uint8)()
-        n = C.c_uint64()
-        rc = lib().rbq_built_save_rbq1(self._h, C.byref(p), C.byref(n))
-        assert rc == RBQ_OK
-        data = bytes(C.cast(p, C.POINTER(C.c_uint8 * n.value)).contents)
-        lib().rbq_build_free_bytes(p)
-        return data
+        def call(p, n):
+            assert lib().rbq_built_save_rbq1(self._h, p, n) == RBQ_OK
+        return owned_bytes(call, lib().rbq_build_free_bytes)
 
     def close(self):
         if self._h:

@@ -3,6 +3,7 @@
 #define RBQ_BUILD_H
 #include <stdint.h>
 #include "../../../include/rbq.h"
+#include "../../../include/rbq_mstg_persist.h" /* rbq_mstg_config */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -17,10 +18,20 @@ int rbq_build_train_with_clusters(const float* data, uint64_t n, uint32_t dim,
 const rbq_header*    rbq_built_header(const rbq_built* b);
 const rbq_list_view* rbq_built_lists(const rbq_built* b);
 float                rbq_built_t_const(const rbq_built* b);
+/* ClusterData.delta / .vl of list c (persisted by save_to_writer, unused by search: not part of rbq_list_view), and
+ * QuantizedVector::residual_norm of its vectors (kept by the `.mstg` format); [n] each, owned by b.
+ * RBQ_INVALID_CONFIG: a null pointer or c >= n_lists. */
+int rbq_built_list_recon(const rbq_built* b, uint64_t c, const float** delta, const float** vl);
+int rbq_built_list_residual_norm(const rbq_built* b, uint64_t c, const float** rnorm);
 void                 rbq_built_free(rbq_built* b);
 /* IvfRabitqIndex::save_to_writer (src/ivf.rs:1317-1474) into a malloc'd buffer. */
 int  rbq_built_save_rbq1(const rbq_built* b, uint8_t** bytes, uint64_t* len);
 void rbq_build_free_bytes(uint8_t* p);
+/* The `.mstg` loader's whole validation without a GPU (rbq_mstg_file.hpp): framing, every record's inner fields, the checksum.
+ * Returns the loader's code with its message in detail [detail_cap]; cfg_out (nullable) receives the file's config, out4
+ * (nullable) lists, vectors, dim, ex_bits. */
+int rbq_build_mstg_file_check(const void* bytes, uint64_t len, char* detail, uint64_t detail_cap, rbq_mstg_config* cfg_out,
+                              uint64_t* out4);
 
 /* best_rescale_factor (src/quantizer.rs:337-427) of one vector: o_abs [dim] = |r_i| / norm(r) -> t */
 double rbq_build_best_rescale_factor(const float* o_abs, uint64_t dim, uint32_t ex_bits);

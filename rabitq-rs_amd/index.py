@@ -4,7 +4,8 @@ import os
 
 import numpy as np
 
-from . import _abi
+from . import _abi, _marshal
+from ._abi import READ_FN, WRITE_FN  # noqa: F401  (their home is the prototype table; callers know them by this module)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -35,188 +36,8 @@ def lib():
                 f"{LIB_PATH} missing: the HIP extension must be built first "
                 "(python -c 'import __graft_entry__ as g; g.build()'); there is no CPU fallback")
         _hip_runtime_of_torch_first()
-        L = C.CDLL(LIB_PATH)
-        vp = C.c_void_p
-        L.rbq_index_create.restype = C.c_int
-        L.rbq_index_create.argtypes = [vp, vp, C.c_int, vp, C.POINTER(vp)]
-        L.rbq_index_load_rbq1.restype = C.c_int
-        L.rbq_index_load_rbq1.argtypes = [vp, C.c_size_t, C.c_int, vp, C.POINTER(vp)]
-        L.rbq_index_destroy.argtypes = [vp]
-        for n in ("rbq_index_len", "rbq_index_cluster_count"):
-            getattr(L, n).restype = C.c_uint64
-            getattr(L, n).argtypes = [vp]
-        for n in ("rbq_index_dim", "rbq_index_padded_dim"):
-            getattr(L, n).restype = C.c_uint32
-            getattr(L, n).argtypes = [vp]
-        L.rbq_search_batch.restype = C.c_int
-        L.rbq_search_batch.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64,
-                                       vp, vp, vp, vp]
-        L.rbq_search_batch_device.restype = C.c_int
-        L.rbq_search_batch_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp,
-                                              C.c_uint64, vp, vp, vp, vp, vp]
-        L.rbq_posting_scan_batch.restype = C.c_int
-        L.rbq_posting_scan_batch.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp]
-        L.rbq_profile_begin.argtypes = [vp]
-        L.rbq_profile_end.argtypes = [vp]
-        L.rbq_profile_stage_ms.restype = C.c_double
-        L.rbq_profile_stage_ms.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64)]
-        L.rbq_profile_scan_bytes.restype = C.c_uint64
-        L.rbq_profile_scan_bytes.argtypes = [vp]
-        L.rbq_debug_rank_fallbacks.restype = C.c_uint64
-        L.rbq_debug_rank_fallbacks.argtypes = [vp]
-        L.rbq_debug_stage_resources.restype = C.c_int
-        L.rbq_debug_stage_resources.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]
-        for n_ in ("rbq_debug_head_exact_evaluations", "rbq_debug_head_exact_guard_trips"):
-            getattr(L, n_).restype = C.c_uint64
-            getattr(L, n_).argtypes = [vp]
-        L.rbq_debug_tie_log_stats.restype = None
-        L.rbq_debug_tie_log_stats.argtypes = [vp, vp]
-        L.rbq_debug_bounce_copies.restype = C.c_uint64
-        L.rbq_debug_bounce_copies.argtypes = []
-        L.rbq_index_build_device.restype = C.c_int
-        L.rbq_index_build_device.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_int, vp]
-        L.rbq_index_build_device_ex.restype = C.c_int
-        L.rbq_index_build_device_ex.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_float, C.c_int, vp]
-        L.rbq_debug_best_rescale.restype = C.c_int
-        L.rbq_debug_best_rescale.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, vp]
-        L.rbq_debug_copy_index.restype = C.c_int
-        L.rbq_debug_copy_index.argtypes = [vp, C.c_char_p, vp, C.c_uint64]
-        L.rbq_profile_set_sampling.restype = None
-        L.rbq_profile_set_sampling.argtypes = [vp, C.c_uint32]
-        L.rbq_profile_select_stages.restype = None
-        L.rbq_profile_select_stages.argtypes = [vp, C.c_uint32]
-        L.rbq_debug_copy_workspace.restype = C.c_int
-        L.rbq_debug_copy_workspace.argtypes = [vp, vp, C.c_char_p, vp, C.c_uint64]
-        L.rbq_debug_heap_restarts.restype = C.c_uint64
-        L.rbq_debug_heap_restarts.argtypes = [vp]
-        L.rbq_debug_set_option.restype = C.c_int
-        L.rbq_debug_set_option.argtypes = [vp, C.c_char_p, C.c_int]
-        L.rbq_strerror.restype = C.c_char_p
-        L.rbq_strerror.argtypes = [C.c_int]
-        L.rbq_last_error_detail.restype = C.c_int
-        L.rbq_last_error_detail.argtypes = [C.c_char_p, C.c_size_t]
-        L.rbq_abi_version.restype = C.c_uint32
-        L.rbq_index_device_count.restype = C.c_uint32
-        L.rbq_index_device_count.argtypes = [vp]
-        L.rbq_build_stream_begin.restype = C.c_int
-        L.rbq_build_stream_begin.argtypes = [vp, vp, vp, C.c_float, C.c_int, C.POINTER(vp)]
-        L.rbq_build_stream_begin_ex.restype = C.c_int
-        L.rbq_build_stream_begin_ex.argtypes = [vp, vp, vp, C.c_int, C.c_float, C.c_int, C.POINTER(vp)]
-        L.rbq_build_stream_push.restype = C.c_int
-        L.rbq_build_stream_push.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64]
-        L.rbq_build_stream_finish.restype = C.c_int
-        L.rbq_build_stream_finish.argtypes = [vp, C.c_int, vp, C.POINTER(vp)]
-        L.rbq_build_stream_abort.restype = None
-        L.rbq_build_stream_abort.argtypes = [vp]
-        L.rbq_release_stream.restype = C.c_int
-        L.rbq_release_stream.argtypes = [vp, vp]
-        L.rbq_host_alloc.restype = vp
-        L.rbq_host_alloc.argtypes = [C.c_size_t]
-        L.rbq_host_free.restype = None
-        L.rbq_host_free.argtypes = [vp]
-        L.rbq_index_set_rerank_vectors.restype = C.c_int
-        L.rbq_index_set_rerank_vectors.argtypes = [vp, vp, C.c_uint64]
-        L.rbq_profile_stage_samples.restype = C.c_uint64
-        L.rbq_profile_stage_samples.argtypes = [vp, C.c_char_p, vp, C.c_uint64]
-        L.rbq_profile_counters.restype = C.c_int
-        L.rbq_profile_counters.argtypes = [vp, vp, C.c_uint32]
-        L.rbq_index_set_numeric_variant.restype = C.c_int
-        L.rbq_index_set_numeric_variant.argtypes = [vp, C.c_int]
-        L.rbq_index_numeric_variant.restype = C.c_int
-        L.rbq_index_numeric_variant.argtypes = [vp]
-        L.rbq_kmeans_device.restype = C.c_int
-        L.rbq_kmeans_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
-                                        C.c_uint64, C.c_uint64, C.c_int, vp, vp, C.POINTER(C.c_double), vp]
-        L.rbq_debug_set_kmeans_chunk_rows.restype = C.c_uint64
-        L.rbq_debug_set_kmeans_chunk_rows.argtypes = [C.c_uint64]
-        L.rbq_debug_kmeans_assign_passes.restype = C.c_uint64
-        L.rbq_debug_kmeans_assign_passes.argtypes = []
-        # rbq_persist.h
-        L.rbq_index_create_with_recon.restype = C.c_int
-        L.rbq_index_create_with_recon.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.POINTER(vp)]
-        L.rbq_index_save_rbq1_stream.restype = C.c_int
-        L.rbq_index_save_rbq1_stream.argtypes = [vp, WRITE_FN, vp]
-        L.rbq_index_save_rbq1.restype = C.c_int
-        L.rbq_index_save_rbq1.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
-        L.rbq_persist_free_bytes.restype = None
-        L.rbq_persist_free_bytes.argtypes = [C.POINTER(C.c_uint8)]
-        L.rbq_debug_crc32_device.restype = C.c_int
-        L.rbq_debug_crc32_device.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]
-        L.rbq_index_load_rbq1_stream.restype = C.c_int
-        L.rbq_index_load_rbq1_stream.argtypes = [READ_FN, vp, C.c_uint64, C.c_int, vp, C.POINTER(vp)]
-        L.rbq_debug_set_load_span.restype = C.c_uint64
-        L.rbq_debug_set_load_span.argtypes = [C.c_uint64]
-        L.rbq_index_fetch_embeddings.restype = C.c_int
-        L.rbq_index_fetch_embeddings.argtypes = [vp, vp, C.c_uint64, vp, vp]
-        L.rbq_index_fetch_embeddings_device.restype = C.c_int
-        L.rbq_index_fetch_embeddings_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
-        # rbq_append.h
-        L.rbq_index_append.restype = C.c_int
-        L.rbq_index_append.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_uint64, C.c_int, vp, vp, C.POINTER(vp)]
-        L.rbq_index_id_bound.restype = C.c_int
-        L.rbq_index_id_bound.argtypes = [vp, C.POINTER(C.c_uint64)]
-        L.rbq_debug_append_passes.restype = C.c_uint64
-        L.rbq_debug_append_passes.argtypes = []
-        L.rbq_debug_append_carry_ns.restype = C.c_uint64
-        L.rbq_debug_append_carry_ns.argtypes = []
-        # rbq_remove.h
-        L.rbq_index_remove_ids.restype = C.c_int
-        L.rbq_index_remove_ids.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.POINTER(C.c_uint64), C.POINTER(vp)]
-        L.rbq_debug_remove_gather_ns.restype = C.c_uint64
-        L.rbq_debug_remove_gather_ns.argtypes = []
-        # rbq_mstg.h
-        L.rbq_mstg_closure_assign.restype = C.c_int
-        L.rbq_mstg_closure_assign.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint64, C.c_int,
-                                              vp, vp]
-        L.rbq_mstg_build_device.restype = C.c_int
-        L.rbq_mstg_build_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_int, C.c_float, C.c_uint64, C.c_int,
-                                            C.POINTER(vp)]
-        L.rbq_mstg_debug_closure_fallbacks.restype = C.c_uint64
-        L.rbq_mstg_debug_closure_fallbacks.argtypes = []
-        L.rbq_mstg_debug_closure_shortlist.restype = C.c_int
-        L.rbq_mstg_debug_closure_shortlist.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int,
-                                                       vp, vp]
-        L.rbq_mstg_search_batch.restype = C.c_int
-        L.rbq_mstg_search_batch.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp]
-        L.rbq_mstg_search_batch_device.restype = C.c_int
-        L.rbq_mstg_search_batch_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp,
-                                                   vp]
-        L.rbq_mstg_search_refined_batch.restype = C.c_int
-        L.rbq_mstg_search_refined_batch.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp, vp,
-                                                    vp, vp]
-        L.rbq_mstg_search_refined_batch_device.restype = C.c_int
-        L.rbq_mstg_search_refined_batch_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp,
-                                                           vp, vp, vp, vp, vp]
-        L.rbq_mstg_debug_search_fallbacks.restype = C.c_uint64
-        L.rbq_mstg_debug_search_fallbacks.argtypes = []
-        L.rbq_mstg_cluster_device.restype = C.c_int
-        L.rbq_mstg_cluster_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_uint64, C.c_uint64,
-                                              C.c_int, C.POINTER(vp)]
-        # rbq_mstg_persist.h
-        L.rbq_mstg_save_stream.restype = C.c_int
-        L.rbq_mstg_save_stream.argtypes = [vp, vp, WRITE_FN, vp]
-        L.rbq_mstg_save.restype = C.c_int
-        L.rbq_mstg_save.argtypes = [vp, vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
-        L.rbq_mstg_load.restype = C.c_int
-        L.rbq_mstg_load.argtypes = [vp, C.c_uint64, C.c_int, vp, C.POINTER(vp)]
-        L.rbq_mstg_load_stream.restype = C.c_int
-        L.rbq_mstg_load_stream.argtypes = [READ_FN, vp, C.c_uint64, C.c_int, vp, C.POINTER(vp)]
-        L.rbq_mstg_memory_usage.restype = C.c_uint64
-        L.rbq_mstg_memory_usage.argtypes = [vp]
-        # rbq_mstg_mutate.h
-        for n_, (res, args) in _abi.MSTG_MUTATE_PROTOTYPES.items():
-            getattr(L, n_).restype = res
-            getattr(L, n_).argtypes = args
-        from .builder import bind_hclustered
-        bind_hclustered(L)
-        _LIB = L
+        _LIB = _abi.bind(C.CDLL(LIB_PATH), _abi.LIBRBQ)
     return _LIB
-
-
-# rbq_write_fn: int (*)(void* user, const void* bytes, uint64_t len)
-WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
-# rbq_read_fn: int (*)(void* user, uint64_t offset, void* dst, uint64_t len)
-READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
 
 
 def _detail():
@@ -393,31 +214,10 @@ class IvfRabitqIndex:
         start = fileobj.tell()
         fileobj.seek(0, os.SEEK_END)
         total = fileobj.tell() - start
-        readinto = getattr(fileobj, "readinto", None)
-        err = []
-
-        def cb(_user, off, dst, n):
-            try:
-                fileobj.seek(start + off)
-                view = memoryview((C.c_ubyte * n).from_address(dst)).cast("B")
-                got = 0
-                while got < n:
-                    if readinto is not None:
-                        k = readinto(view[got:])
-                    else:
-                        chunk = fileobj.read(n - got)
-                        k = len(chunk)
-                        view[got:got + k] = chunk
-                    if not k:
-                        return 1  # the object ended before the range did
-                    got += k
-                return 0
-            except BaseException as e:  # noqa: BLE001 - handed back to the caller after the C call returns
-                err.append(e)
-                return 1
+        fn, err = _marshal.reader_callback(fileobj, start)
         h = C.c_void_p()
         n, dev = cls._devices(device, devices)
-        rc = lib().rbq_index_load_rbq1_stream(READ_FN(cb), None, max(int(total), 0), n, dev, C.byref(h))
+        rc = lib().rbq_index_load_rbq1_stream(fn, None, max(int(total), 0), n, dev, C.byref(h))
         if err:
             raise err[0]
         _check(rc)
@@ -427,16 +227,7 @@ class IvfRabitqIndex:
     def save_to_writer(self, fileobj):
         """Write the RBQ1 stream to `fileobj` (anything with .write(bytes)), chunk by chunk
         (rbq_index_save_rbq1_stream).  A writer exception stops the save and is re-raised."""
-        err = []
-
-        def cb(_user, p, n):
-            try:
-                fileobj.write(C.string_at(p, n) if n else b"")
-                return 0
-            except BaseException as e:  # noqa: BLE001 - handed back to the caller after the C call returns
-                err.append(e)
-                return 1
-        fn = WRITE_FN(cb)
+        fn, err = _marshal.writer_callback(fileobj)
         rc = lib().rbq_index_save_rbq1_stream(self._h, fn, None)
         if err:
             raise err[0]
@@ -444,13 +235,7 @@ class IvfRabitqIndex:
 
     def save_to_bytes(self):
         """The whole RBQ1 stream as bytes (rbq_index_save_rbq1)."""
-        p = C.POINTER(C.c_uint8)()
-        n = C.c_uint64()
-        _check(lib().rbq_index_save_rbq1(self._h, C.byref(p), C.byref(n)))
-        try:
-            return C.string_at(p, n.value)
-        finally:
-            lib().rbq_persist_free_bytes(p)
+        return _marshal.owned_bytes(lambda p, n: _check(lib().rbq_index_save_rbq1(self._h, p, n)), lib().rbq_persist_free_bytes)
 
     def save_to_path(self, path):
         """save_to_path: the stream written to a file (created or truncated)."""
@@ -473,12 +258,7 @@ class IvfRabitqIndex:
     def fetch_embeddings(self, ids):
         """rbq_index_fetch_embeddings: (out [n, dim] f32, found [n] bool).  Row i is the crate's fetch_embedding(ids[i]) bit
         for bit (the first occurrence in (cluster, position) order); a missing id gives a zero row and found False."""
-        q = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
-        n = int(q.size)
-        out = np.empty((n, self.dim), np.float32)
-        found = np.empty(n, np.uint8)
-        _check(lib().rbq_index_fetch_embeddings(self._h, q.ctypes.data, n, out.ctypes.data, found.ctypes.data))
-        return out, found.astype(bool)
+        return _marshal.fetch_embeddings(lib().rbq_index_fetch_embeddings, self._h, self.dim, ids)
 
     def fetch_embedding(self, vector_id):
         """`IvfRabitqIndex::fetch_embedding`: the reconstructed vector [dim] f32, or None when the id is not in the index."""
@@ -488,8 +268,7 @@ class IvfRabitqIndex:
     def fetch_embeddings_device(self, d_ids, n, d_out, d_found, stream=None):
         """rbq_index_fetch_embeddings_device: n u64 ids at d_ids (device memory of the first replica's device) -> d_out
         [n][dim] f32, d_found [n] u8, enqueued on `stream` (a hipStream_t as int, None = default stream)."""
-        _check(lib().rbq_index_fetch_embeddings_device(self._h, C.c_void_p(d_ids), int(n), C.c_void_p(d_out), C.c_void_p(d_found),
-                                                       C.c_void_p(stream) if stream else None))
+        _marshal.fetch_embeddings_device(lib().rbq_index_fetch_embeddings_device, self._h, d_ids, n, d_out, d_found, stream)
 
     # -- growth (rbq_index_append) --------------------------------------------------------------------------------
     def id_bound(self):
@@ -505,42 +284,37 @@ class IvfRabitqIndex:
         the new rows.  rescale / t_const default to what train, train_on_device or build_on_device encoded this object with; a
         loaded object has to be given them.  The object's handle is swapped for the grown one (on `devices`, default the first
         replica's device) and the old one closed.  Returns the list of every row, [count] u32."""
-        import torch
         from . import RabitqError
-        if rescale is None:
-            if self._rescale is None:
-                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "this index does not know what it was encoded with (a loaded index does not "
-                                  "store it): pass rescale= and t_const= to add()")
-            rescale, t_known = self._rescale
-            if t_const is None:
-                t_const = t_known
-        if isinstance(data, torch.Tensor):
-            x = data.to(dtype=torch.float32).contiguous()
-            if not x.is_cuda:
-                x = x.numpy()
-        else:
-            x = np.ascontiguousarray(data, dtype=np.float32)
+        rescale, t_const = _marshal.known_rescale(self._rescale, rescale, t_const)
+        xp, x = _marshal.rows_arg(data)
         if x.ndim != 2 or x.shape[1] != self.dim:
             raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data must be [count][%d]" % self.dim)
         count = int(x.shape[0])
-        a = None
+        ap = a = None
         if assignments is not None:
-            if isinstance(assignments, torch.Tensor) and assignments.is_cuda:
+            torch = _marshal.torch_of(assignments)
+            if torch is not None and assignments.is_cuda:
                 a = assignments.to(dtype=torch.int32).contiguous()
+                ap = C.c_void_p(a.data_ptr())
             else:
-                a = np.ascontiguousarray(assignments.numpy() if isinstance(assignments, torch.Tensor) else assignments).astype(np.uint32)
+                a = np.ascontiguousarray(assignments.numpy() if torch is not None else assignments).astype(np.uint32)
+                ap = C.c_void_p(a.ctypes.data)
             if a.ndim != 1 or a.shape[0] != count:
                 raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "assignments must be [count]")
-        ptr = lambda v: None if v is None else C.c_void_p(v.data_ptr() if isinstance(v, torch.Tensor) else v.ctypes.data)  # noqa: E731
         mode, t = _rescale(rescale, t_const)
         out = np.empty(count, np.uint32)
         nd, dv = (1, None) if devices is None else self._devices(None, devices)
         h = C.c_void_p()
-        _check(lib().rbq_index_append(self._h, ptr(x), ptr(a), count, self.id_bound() if first_id is None else int(first_id), mode, t,
-                                      int(max_chunk_rows), nd, dv, out.ctypes.data, C.byref(h)))
-        old, self._h, self._rescale = self._h, h, (rescale, t_const)
-        lib().rbq_index_destroy(old)
+        _check(lib().rbq_index_append(self._h, xp, ap, count, self.id_bound() if first_id is None else int(first_id), mode, t,
+                                      int(max_chunk_rows), nd, dv, out.ctypes.data, C.byref(h)))  # (x and a own what xp and ap name)
+        self._rescale = (rescale, t_const)
+        self._swap(h)
         return out
+
+    def _swap(self, h):
+        """The handle a mutation returned takes the place of the old one, which is closed."""
+        old, self._h = self._h, h
+        lib().rbq_index_destroy(old)
 
     # -- shrinking (rbq_index_remove_ids) ------------------------------------------------------------------------------
     def remove_ids(self, ids, devices=None):
@@ -549,27 +323,13 @@ class IvfRabitqIndex:
         afterwards equals, array for array, a one-shot build over the rows that stay, with their original ids.  The object's handle
         is swapped for the shrunk one (on `devices`, default the first replica's device) and the old one closed; the remembered
         rescale mode stays.  Returns the number of slots removed; an empty `ids` returns 0 without a call."""
-        import torch
-        from . import RabitqError
-        if isinstance(ids, torch.Tensor) and ids.is_cuda:
-            if ids.dtype not in (torch.int64, torch.uint64):
-                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "ids on the device must be int64 or uint64")
-            v = ids.contiguous().reshape(-1)
-            n, p = int(v.numel()), v.data_ptr()
-        else:
-            if isinstance(ids, torch.Tensor):
-                ids = ids.numpy()
-            if not isinstance(ids, np.ndarray):  # (numpy would make float64 of a list that mixes ints below and above 2^63)
-                ids = np.asarray(ids if hasattr(ids, "__len__") else list(ids), dtype=np.uint64)
-            v = np.ascontiguousarray(ids).astype(np.uint64).reshape(-1)
-            n, p = int(v.size), v.ctypes.data
+        n, p, _ids = _marshal.ids_arg(ids)  # (_ids owns what p names)
         if n == 0:
             return 0
         nd, dv = (1, None) if devices is None else self._devices(None, devices)
         h, removed = C.c_void_p(), C.c_uint64()
-        _check(lib().rbq_index_remove_ids(self._h, C.c_void_p(p), n, nd, dv, C.byref(removed), C.byref(h)))
-        old, self._h = self._h, h
-        lib().rbq_index_destroy(old)
+        _check(lib().rbq_index_remove_ids(self._h, p, n, nd, dv, C.byref(removed), C.byref(h)))
+        self._swap(h)
         return int(removed.value)
 
     # -- accessors ----------------------------------------------------------------

@@ -19,6 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _abi
+from ._marshal import ids_arg, owned_bytes, reader_callback, rows_arg, torch_of, writer_callback
 
 NONE = 0xFFFFFFFF  # unused slot of a closure row
 
@@ -34,21 +35,6 @@ def _shapes(data, centroids):
     if len(data.shape) != 2 or len(centroids.shape) != 2 or data.shape[1] != centroids.shape[1]:
         raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data [n][dim], centroids [n_lists][dim]")
     return int(data.shape[0]), int(centroids.shape[0]), int(data.shape[1])
-
-
-def _ptr(a, device):
-    """(pointer, keep-alive) of a [rows][dim] f32 array: a CUDA tensor is used in place, anything else is host memory."""
-    try:
-        import torch
-    except ImportError:
-        torch = None
-    if torch is not None and isinstance(a, torch.Tensor):
-        if a.is_cuda:
-            t = a.to(dtype=torch.float32).contiguous()
-            return C.c_void_p(t.data_ptr()), t
-        a = a.numpy()
-    h = np.ascontiguousarray(a, dtype=np.float32)
-    return C.c_void_p(h.ctypes.data), h
 
 
 def closure_assign_cpu(data, centroids, epsilon, max_replicas):
@@ -72,8 +58,8 @@ def closure_assign(data, centroids, epsilon, max_replicas, device=None, max_chun
     from .index import _check, lib
     n, k, dim = _shapes(data, centroids)
     dev = -1 if device is None else int(device)
-    xp, _x = _ptr(data, dev)
-    cp, _c = _ptr(centroids, dev)
+    xp, _x = rows_arg(data)
+    cp, _c = rows_arg(centroids)
     lists = np.empty((n, max(int(max_replicas), 0)), np.uint32)
     counts = np.empty(n, np.uint32)
     _check(lib().rbq_mstg_closure_assign(cp, k, dim, xp, n, float(epsilon), int(max_replicas), int(max_chunk_rows), dev,
@@ -92,8 +78,8 @@ def debug_closure_shortlist(data, centroids, max_replicas, device=None, max_chun
     from .index import _check, lib
     n, k, dim = _shapes(data, centroids)
     dev = -1 if device is None else int(device)
-    xp, _x = _ptr(data, dev)
-    cp, _c = _ptr(centroids, dev)
+    xp, _x = rows_arg(data)
+    cp, _c = rows_arg(centroids)
     sl = np.empty((n, 256), np.uint32)
     sl_n = np.empty(n, np.uint32)
     _check(lib().rbq_mstg_debug_closure_shortlist(cp, k, dim, xp, n, int(max_replicas), int(max_chunk_rows), dev, sl.ctypes.data,
@@ -121,7 +107,7 @@ def build_postings_on_device(data, centroids, total_bits, metric, closure_epsilo
     from .index import IvfRabitqIndex, _check, _rescale, lib
     n, k, dim = _shapes(data, centroids)
     dev = -1 if device is None else int(device)
-    xp, _x = _ptr(data, dev)
+    xp, _x = rows_arg(data)
     cent = _host_f32(centroids)
     if n == 0 or k == 0:
         raise RabitqError(_abi.RBQ_INVALID_CONFIG, "data and centroids must be non-empty")
@@ -152,7 +138,7 @@ def append_postings(handle, data, first_id=None, closure_epsilon=0.15, max_repli
     if len(data.shape) != 2 or int(data.shape[1]) != int(handle.dim):
         raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "data must be [count][%d]" % int(handle.dim))
     count, M = int(data.shape[0]), int(max_replicas)
-    xp, x = _ptr(data, -1)
+    xp, x = rows_arg(data)
     on_dev = not isinstance(x, np.ndarray)
     lists = counts = lp = cp = None
     if return_lists:
@@ -176,26 +162,10 @@ def remove_postings(handle, ids):
     the number of slots removed — a vector held by three lists counts three).  `ids` is a NumPy u64 array (or anything that
     converts to one) or a CUDA int64 / uint64 tensor; any order, repeats allowed, ids that are not stored ignored.  The result
     equals build_postings_on_device over the rows that stay, with their original ids.  `handle` stays valid."""
-    from . import RabitqError
     from .index import IvfRabitqIndex, _check, lib
-    try:
-        import torch
-    except ImportError:
-        torch = None
-    if torch is not None and isinstance(ids, torch.Tensor) and ids.is_cuda:
-        if ids.dtype not in (torch.int64, torch.uint64):
-            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "ids on the device must be int64 or uint64")
-        v = ids.contiguous().reshape(-1)
-        n, p = int(v.numel()), v.data_ptr()
-    else:
-        if torch is not None and isinstance(ids, torch.Tensor):
-            ids = ids.numpy()
-        if not isinstance(ids, np.ndarray):
-            ids = np.asarray(ids if hasattr(ids, "__len__") else list(ids), dtype=np.uint64)
-        v = np.ascontiguousarray(ids).astype(np.uint64).reshape(-1)
-        n, p = int(v.size), v.ctypes.data
+    n, p, _ids = ids_arg(ids)  # (_ids owns what p names)
     h, removed = C.c_void_p(), C.c_uint64()
-    _check(lib().rbq_mstg_remove_ids(handle._h, C.c_void_p(p) if n else None, n, C.byref(removed), C.byref(h)))
+    _check(lib().rbq_mstg_remove_ids(handle._h, p if n else None, n, C.byref(removed), C.byref(h)))
     return IvfRabitqIndex(h), int(removed.value)
 
 
@@ -267,11 +237,8 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
     else:
         host_fn, dev_fn, extra = L.rbq_mstg_search_refined_batch, L.rbq_mstg_search_refined_batch_device, (int(refine_pool),)
     ef = min(max(ef_search, 0), index.cluster_count())
-    try:
-        import torch
-    except ImportError:
-        torch = None
-    if torch is not None and isinstance(queries, torch.Tensor) and queries.is_cuda:
+    torch = torch_of(queries)
+    if torch is not None and queries.is_cuda:
         q = queries.to(dtype=torch.float32).contiguous()
         nq, qd = q.shape
         with torch.cuda.device(q.device):
@@ -310,7 +277,7 @@ def save_mstg(index, config, dest):
     truncated; the crate's name is `{base}.mstg`) or anything with .write(bytes).  Chunks arrive as the device finishes them; a
     writer exception stops the save and is re-raised."""
     from . import RabitqError
-    from .index import WRITE_FN, _check, lib
+    from .index import _check, lib
     cfg = _config_struct(config)
     if isinstance(dest, (str, bytes)) or hasattr(dest, "__fspath__"):
         try:
@@ -319,16 +286,8 @@ def save_mstg(index, config, dest):
             raise RabitqError(_abi.RBQ_IO, str(e))
         with f:
             return save_mstg(index, cfg, f)
-    err = []
-
-    def cb(_user, p, n):
-        try:
-            dest.write(C.string_at(p, n) if n else b"")
-            return 0
-        except BaseException as e:  # noqa: BLE001 - handed back to the caller after the C call returns
-            err.append(e)
-            return 1
-    rc = lib().rbq_mstg_save_stream(index._h, C.byref(cfg), WRITE_FN(cb), None)
+    fn, err = writer_callback(dest)
+    rc = lib().rbq_mstg_save_stream(index._h, C.byref(cfg), fn, None)
     if err:
         raise err[0]
     _check(rc)
@@ -338,19 +297,14 @@ def save_mstg_bytes(index, config):
     """The whole `.mstg` stream as bytes (rbq_mstg_save)."""
     from .index import _check, lib
     cfg = _config_struct(config)
-    p, n = C.POINTER(C.c_uint8)(), C.c_uint64()
-    _check(lib().rbq_mstg_save(index._h, C.byref(cfg), C.byref(p), C.byref(n)))
-    try:
-        return C.string_at(p, n.value)
-    finally:
-        lib().rbq_persist_free_bytes(p)
+    return owned_bytes(lambda p, n: _check(lib().rbq_mstg_save(index._h, C.byref(cfg), p, n)), lib().rbq_persist_free_bytes)
 
 
 def load_mstg(src, device=None):
     """(handle, config dict) of a `.mstg` stream: `src` is bytes (rbq_mstg_load), or a path or a seekable binary file, read
     through rbq_mstg_load_stream (the framing first, then the records span by span: host memory stays two spans)."""
     from . import RabitqError
-    from .index import READ_FN, IvfRabitqIndex, _check, lib
+    from .index import IvfRabitqIndex, _check, lib
     dev = -1 if device is None else int(device)
     cfg, h = _abi.MstgConfig(), C.c_void_p()
     if isinstance(src, (bytes, bytearray, memoryview)):
@@ -365,20 +319,8 @@ def load_mstg(src, device=None):
         with f:
             return load_mstg(f, device)
     total = src.seek(0, 2)
-    err = []
-
-    def cb(_user, off, dst, n):
-        try:
-            src.seek(off)
-            got = src.read(n)
-            if len(got) != n:
-                return 1
-            C.memmove(dst, got, n)
-            return 0
-        except BaseException as e:  # noqa: BLE001 - handed back to the caller after the C call returns
-            err.append(e)
-            return 1
-    rc = lib().rbq_mstg_load_stream(READ_FN(cb), None, total, dev, C.byref(cfg), C.byref(h))
+    fn, err = reader_callback(src, 0)
+    rc = lib().rbq_mstg_load_stream(fn, None, total, dev, C.byref(cfg), C.byref(h))
     if err:
         raise err[0]
     _check(rc)
@@ -431,7 +373,7 @@ def hierarchical_cluster(data, max_posting_size, branching_factor=10, balance_we
     n, dim = int(data.shape[0]), int(data.shape[1])
     mps, k, it = _hc_args(max_posting_size, branching_factor, max_iterations)
     dev = -1 if device is None else int(device)
-    xp, _x = _ptr(data, dev)
+    xp, _x = rows_arg(data)
     hb = HOST_BELOW_DEFAULT if host_below is None else int(host_below)
     h = C.c_void_p()
     L = lib()

@@ -2,20 +2,18 @@
 no GPU (argument checks, RBQ1 parsing errors) behaves like the reference.  No compute calls here."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
 import rabitq_rs_amd as rq
+from c_header import c_functions
 from conftest import ROOT, build_index
 from rabitq_rs_amd import index as ix
 
 
 def _declared():
-    src = open(os.path.join(ROOT, "include", "rbq.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(rbq_[a-z0-9_]+)\s*\(", src)))
+    return sorted(c_functions(open(os.path.join(ROOT, "include", "rbq.h")).read()))
 
 
 def test_library_exports_every_declared_symbol():

@@ -3,11 +3,11 @@ that rbq_index_append finds before its first HIP call come back as RBQ_INVALID_C
 provoked without a live handle (null idx, null out)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 
 import rabitq_rs_amd as rq
+from c_header import c_functions
 from conftest import ROOT
 from rabitq_rs_amd import index as ix
 
@@ -15,8 +15,7 @@ from rabitq_rs_amd import index as ix
 def test_header_is_included_and_symbols_are_exported():
     hdr = open(os.path.join(ROOT, "include", "rbq.h")).read()
     assert '#include "rbq_append.h"' in hdr
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rbq_append.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(rbq_[a-z0-9_]+)\s*\(", src)))
+    names = sorted(c_functions(open(os.path.join(ROOT, "include", "rbq_append.h")).read()))
     assert names == ["rbq_debug_append_carry_ns", "rbq_debug_append_passes", "rbq_index_append", "rbq_index_id_bound"]
     lib = ix.lib()
     for n in names:

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import rabitq_rs_amd as rq
+from c_header import c_functions, strip_c_comments
 from conftest import ROOT
 from rabitq_rs_amd import bruteforce as bfm
 from rabitq_rs_amd import index as ix
@@ -31,10 +32,10 @@ PROTOTYPES = [
 def test_header_is_included_and_symbols_are_exported_and_declared():
     assert '#include "rbq_bf_mutate.h"' in open(os.path.join(ROOT, "include", "rbq_bf.h")).read()
     text = open(os.path.join(ROOT, "include", "rbq_bf_mutate.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    src = strip_c_comments(text)
     for proto in PROTOTYPES:
         assert re.search(proto, src), proto
-    names = sorted(set(re.findall(r"\b(rbq_[a-z0-9_]+)\s*\(", src)))
+    names = sorted(c_functions(text))
     assert names == ["rbq_bf_append", "rbq_bf_debug_append_carry_ns", "rbq_bf_debug_remove_gather_ns", "rbq_bf_fetch_embeddings",
                      "rbq_bf_fetch_embeddings_device", "rbq_bf_remove_ids"]
     lib = bfm.lib()

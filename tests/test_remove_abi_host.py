@@ -4,11 +4,11 @@ order — those that can be provoked without a live handle (null out, then null 
 tests/test_gpu_remove.py)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 
 import rabitq_rs_amd as rq
+from c_header import c_functions
 from conftest import ROOT
 from rabitq_rs_amd import index as ix
 
@@ -16,8 +16,7 @@ from rabitq_rs_amd import index as ix
 def test_header_is_included_and_symbols_are_exported():
     hdr = open(os.path.join(ROOT, "include", "rbq.h")).read()
     assert '#include "rbq_remove.h"' in hdr and hdr.index('#include "rbq_append.h"') < hdr.index('#include "rbq_remove.h"')
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rbq_remove.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(rbq_[a-z0-9_]+)\s*\(", src)))
+    names = sorted(c_functions(open(os.path.join(ROOT, "include", "rbq_remove.h")).read()))
     assert names == ["rbq_debug_remove_gather_ns", "rbq_index_remove_ids"]
     lib = ix.lib()
     for n in names:

@@ -7,80 +7,11 @@ import re
 
 import pytest
 
+from c_header import c_functions, c_structs, c_type, split_args
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "rbq.h")).read()
 RS = open(os.path.join(ROOT, "integration", "gpu_ivf.rs")).read()
-
-C_SCALARS = {"uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int": "c_int", "size_t": "usize", "float": "f32",
-             "double": "f64", "void": "c_void", "char": "c_char", "rbq_index": "RbqIndex", "rbq_builder": "RbqBuilder",
-             "rbq_header": "RbqHeader", "rbq_list_view": "RbqListView", "rbq_diag": "RbqDiag"}
-
-
-def strip_c_comments(s):
-    return re.sub(r"/\*.*?\*/", " ", s, flags=re.S)
-
-
-def c_type(tokens):
-    """canonical form of a C type: nested ('ptr', 'const'|'mut', inner) around a scalar name"""
-    toks = [t for t in re.findall(r"\w+|\*", tokens)]
-    # leading type (with optional const either side), then a chain of '*' each optionally followed by const
-    const = False
-    base = None
-    i = 0
-    while i < len(toks) and toks[i] != "*":
-        if toks[i] == "const":
-            const = True
-        elif toks[i] in ("struct", "unsigned", "signed"):
-            pass
-        else:
-            base = toks[i]
-        i += 1
-    assert base in C_SCALARS, (tokens, base)
-    t = C_SCALARS[base]
-    while i < len(toks):
-        assert toks[i] == "*", tokens
-        t = ("ptr", "const" if const else "mut", t)
-        const = False
-        i += 1
-        if i < len(toks) and toks[i] == "const":
-            const = True
-            i += 1
-    return t
-
-
-def split_args(s):
-    return [a.strip() for a in s.split(",") if a.strip()]
-
-
-def c_functions():
-    src = strip_c_comments(HDR)
-    out = {}
-    for m in re.finditer(r"([\w\s\*]+?)\b(rbq_\w+)\s*\(([^;{}]*?)\)\s*;", src):
-        ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
-        if "typedef" in ret:
-            continue
-        params = []
-        if args and args != "void":
-            for a in split_args(args):
-                mm = re.match(r"(.*?)(\w+)$", a.strip())
-                params.append((mm.group(2), c_type(mm.group(1))))
-        out[name] = (None if ret == "void" else c_type(ret), params)
-    return out
-
-
-def c_structs():
-    src = strip_c_comments(HDR)
-    out = {}
-    for m in re.finditer(r"typedef\s+struct\s*\{(.*?)\}\s*(rbq_\w+)\s*;", src, flags=re.S):
-        fields = []
-        for decl in m.group(1).split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            mm = re.match(r"(.*?)(\w+)$", decl)
-            fields.append((mm.group(2), c_type(mm.group(1))))
-        out[C_SCALARS[m.group(2)]] = fields
-    return out
 
 
 def rs_type(s):
@@ -133,7 +64,7 @@ PRODUCT_API = ["rbq_index_create", "rbq_index_load_rbq1", "rbq_index_build_devic
 
 
 def test_every_extern_signature_matches_the_header():
-    cf, rf = c_functions(), rs_functions()
+    cf, rf = c_functions(HDR), rs_functions()
     assert len(cf) >= 30, sorted(cf)
     for name, (rret, rparams) in rf.items():
         assert name in cf, f"{name} is not declared in include/rbq.h"
@@ -147,7 +78,7 @@ def test_every_extern_signature_matches_the_header():
 
 
 def test_repr_c_structs_match_the_header():
-    cs, rs = c_structs(), rs_structs()
+    cs, rs = c_structs(HDR), rs_structs()
     for name in ("RbqHeader", "RbqListView", "RbqDiag"):
         assert name in rs, name
         assert [t for _, t in rs[name]] == [t for _, t in cs[name]], (name, rs[name], cs[name])
