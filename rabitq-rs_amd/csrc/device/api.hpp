@@ -344,7 +344,7 @@ struct Options {
     int slack_term = 0;
     bool ub_tap = false;     // DIAGNOSTIC: the select kernel exports its head bounds (workspace "head_ub")
     bool lazy_audit = false; // DIAGNOSTIC: the select kernel exports the lists it drops as a whole (workspace "audit_dead")
-    bool lazy_select = true; // probe selection drops lists that are provably skipped as a whole (rank_mfma.hpp)
+    bool lazy_select = true; // probe selection drops lists that are provably skipped as a whole (select_mfma.hpp)
     uint32_t tie_log_cap = 0; // TEST ONLY: entries per query of the tie log (0 = the default sizes)
     bool tie_log = true;      // k_scan logs the candidates it refines; a tied query replays the log (scan.hpp)
     int latency_path = 1;     // small calls (see kLatMaxQueries) take the latency-first front (latency.hpp); 0 = never

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void k_block_summary(const uint8_t* __restrict
     }
 }
 
-// One workgroup per list (lazy probe selection, rank_mfma.hpp): BlockSummaryEx of every block and the factor ranges of
+// One workgroup per list (lazy probe selection, select_mfma.hpp): BlockSummaryEx of every block and the factor ranges of
 // the WHOLE list (a BlockSummary over its blocks' summaries; an empty list gets an unusable one).
 //
 // BlockSummaryEx regroups the estimator around the list's centroid c.  With u' the centred total code of a vector

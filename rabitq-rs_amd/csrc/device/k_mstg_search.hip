@@ -30,7 +30,7 @@
 #include "rbq_mstg.h"
 #include "launch.hpp"
 #include "kernels.hpp"
-#include "rank_mfma.hpp"
+#include "canon_score.hpp"
 #include "km_common.hpp"
 
 namespace rbq {

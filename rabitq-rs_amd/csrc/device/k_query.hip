@@ -8,6 +8,8 @@
 #include "launch.hpp"
 #include "query_kernels.hpp"
 #include "rank_mfma.hpp"
+#include "select_given.hpp"
+#include "select_mfma.hpp"
 #include "latency.hpp"
 
 namespace rbq {
@@ -63,14 +65,25 @@ hipError_t launch_rank_exact(const RankParams& p, hipStream_t s) {
 }
 
 namespace {
-// big problems: 128x128 tiles, 8 waves (each 64x32) — the tile traffic of the 4-wave form with twice the waves to
-// hide the staging behind the MFMAs; small ones: 64x64 tiles, 4 waves
-template <int M, int TM, int TN, int WM, int WN>
+// shape of a ranking GEMM: metric M; workgroups of WM x WN waves, each wave TM x TN MFMA blocks of 32 x 32
+template <int M, int TM_, int TN_, int WM_, int WN_>
+struct RankShape { static constexpr int metric = M, TM = TM_, TN = TN_, WM = WM_, WN = WN_; };
+// THE metric and tile table of the three GEMMs, f(shape) with the call's shape as a type.  wide (very large problems, cfg5: 16 384 x
+// 65 536): 128 x 256 tiles, each wave a 64 x 64 sub-tile — 8 LDS fragment reads per 12 MFMAs instead of 6 per 6, one workgroup (123 KB of
+// LDS) per compute unit; big: 128 x 128 tiles, 8 waves (each 64 x 32) — the tile traffic of the 4-wave form with twice the waves to hide
+// the staging behind the MFMAs; else 64 x 64 tiles, 4 waves.  (k_rank_mfma: square tiles of 64 TM on four waves, no wide form.)
+template <class F>
+hipError_t with_rank_shape(int metric, bool wide, bool big, F&& f) {
+    if (metric == 0) return wide ? f(RankShape<0, 2, 2, 2, 4>{}) : big ? f(RankShape<0, 2, 1, 2, 4>{}) : f(RankShape<0, 1, 1, 2, 2>{});
+    return wide ? f(RankShape<1, 2, 2, 2, 4>{}) : big ? f(RankShape<1, 2, 1, 2, 4>{}) : f(RankShape<1, 1, 1, 2, 2>{});
+}
+template <class S>
 hipError_t launch_rank_split(const RankParams& p, dim3 grid, int device, hipStream_t s) {
+    constexpr auto kernel = &k_rank_bf16_db<S::metric, S::TM, S::TN, S::WM, S::WN>;
     static LdsAttrCache attr;
-    const size_t lds = (size_t)(2 * 32 * TM * WM + 2 * 32 * TN * WN) * 80 * 2; // two slabs of 32, rows of 80 B
-    if (probe_stage(1, reinterpret_cast<const void*>(&k_rank_bf16_db<M, TM, TN, WM, WN>), grid, 64 * WM * WN, lds, kRankOpsBf16x3)) return hipSuccess;
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_rank_bf16_db<M, TM, TN, WM, WN>), lds, device);
+    const size_t lds = (size_t)(2 * 32 * S::TM * S::WM + 2 * 32 * S::TN * S::WN) * 80 * 2; // two slabs of 32, rows of 80 B
+    if (probe_stage(1, reinterpret_cast<const void*>(kernel), grid, 64 * S::WM * S::WN, lds, kRankOpsBf16x3)) return hipSuccess;
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(kernel), lds, device);
     if (e != hipSuccess) return e;
     // operands: planar (two planes, rows of 2 D bytes, slabs of 64) or interleaved (one image at *_hi: the lo plane 64 bytes behind the hi
     // plane, rows of 4 D bytes, slabs of 128)
@@ -78,51 +91,43 @@ hipError_t launch_rank_split(const RankParams& p, dim3 grid, int device, hipStre
     const unsigned char* al = p.rot_hl ? ah + 64 : reinterpret_cast<const unsigned char*>(p.rot_lo);
     const unsigned char* bh = reinterpret_cast<const unsigned char*>(p.cent_hi);
     const unsigned char* bl = p.cent_hl ? bh + 64 : reinterpret_cast<const unsigned char*>(p.cent_lo);
-    hipLaunchKernelGGL((k_rank_bf16_db<M, TM, TN, WM, WN>), grid, dim3(64 * WM * WN), lds, s, ah, al, p.D * (p.rot_hl ? 4u : 2u),
-                       p.rot_hl ? 128u : 64u, bh, bl, p.D * (p.cent_hl ? 4u : 2u), p.cent_hl ? 128u : 64u, p.consts, p.cnorm2, p.nq, p.nlist,
-                       p.D, p.scores);
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * S::WM * S::WN), lds, s, ah, al, p.D * (p.rot_hl ? 4u : 2u), p.rot_hl ? 128u : 64u, bh, bl,
+                       p.D * (p.cent_hl ? 4u : 2u), p.cent_hl ? 128u : 64u, p.consts, p.cnorm2, p.nq, p.nlist, p.D, p.scores);
     return hipGetLastError();
 }
 // the one-product f16 form of the same tiles (k_rank_f16_db): two slabs of 64, rows of 144 B
-template <int M, int TM, int TN, int WM, int WN>
+template <class S>
 hipError_t launch_rank_f16(const RankParams& p, dim3 grid, int device, hipStream_t s) {
+    constexpr auto kernel = &k_rank_f16_db<S::metric, S::TM, S::TN, S::WM, S::WN>;
     static LdsAttrCache attr;
-    const size_t lds = (size_t)(32 * TM * WM + 32 * TN * WN) * 144 * 2;
-    if (probe_stage(1, reinterpret_cast<const void*>(&k_rank_f16_db<M, TM, TN, WM, WN>), grid, 64 * WM * WN, lds, kRankOpsF16)) return hipSuccess;
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_rank_f16_db<M, TM, TN, WM, WN>), lds, device);
+    const size_t lds = (size_t)(32 * S::TM * S::WM + 32 * S::TN * S::WN) * 144 * 2;
+    if (probe_stage(1, reinterpret_cast<const void*>(kernel), grid, 64 * S::WM * S::WN, lds, kRankOpsF16)) return hipSuccess;
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(kernel), lds, device);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_rank_f16_db<M, TM, TN, WM, WN>), grid, dim3(64 * WM * WN), lds, s, reinterpret_cast<const unsigned char*>(p.rot_hi),
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * S::WM * S::WN), lds, s, reinterpret_cast<const unsigned char*>(p.rot_hi),
                        reinterpret_cast<const unsigned char*>(p.cent_hi), p.consts, p.cnorm2, p.nq, p.nlist, p.D, p.scores);
     return hipGetLastError();
 }
-template <int M, int TW>
+template <class S>
 hipError_t launch_rank_f32(const RankParams& p, dim3 grid, hipStream_t s) {
-    if (probe_stage(1, reinterpret_cast<const void*>(&k_rank_mfma<M, TW>), grid, 256, 0, kRankOpsF32)) return hipSuccess;
-    hipLaunchKernelGGL((k_rank_mfma<M, TW>), grid, dim3(256), 0, s, p.rot, p.cent, p.consts, p.cnorm2, p.nq, p.nlist, p.D, p.scores);
+    constexpr auto kernel = &k_rank_mfma<S::metric, S::TM>;
+    if (probe_stage(1, reinterpret_cast<const void*>(kernel), grid, 256, 0, kRankOpsF32)) return hipSuccess;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, p.rot, p.cent, p.consts, p.cnorm2, p.nq, p.nlist, p.D, p.scores);
     return hipGetLastError();
 }
 } // namespace
 
 hipError_t launch_rank_gemm(const RankParams& p, int device, hipStream_t s) {
-    if (p.split && p.wide) {
-        // very large problems (cfg5: 16 384 x 65 536): 128 x 256 tiles, each wave a 64 x 64 sub-tile — 8 LDS fragment reads per 12 MFMAs
-        // instead of 6 per 6, one workgroup (123 KB of LDS) per compute unit
-        dim3 grid((p.nlist + 255) / 256, (p.nq + 127) / 128);
-        if (p.f16) return p.metric == 0 ? launch_rank_f16<0, 2, 2, 2, 4>(p, grid, device, s) : launch_rank_f16<1, 2, 2, 2, 4>(p, grid, device, s);
-        return p.metric == 0 ? launch_rank_split<0, 2, 2, 2, 4>(p, grid, device, s) : launch_rank_split<1, 2, 2, 2, 4>(p, grid, device, s);
-    }
+    const bool wide = p.split && p.wide;
     const uint32_t T = p.big ? 128u : 64u;
-    dim3 grid((p.nlist + T - 1) / T, (p.nq + T - 1) / T, p.split && p.ksplit > 1 ? p.ksplit : 1u); // (z: split-K, the row zeroed by the preparation)
-    if (p.split && p.f16) {
-        if (p.metric == 0) return p.big ? launch_rank_f16<0, 2, 1, 2, 4>(p, grid, device, s) : launch_rank_f16<0, 1, 1, 2, 2>(p, grid, device, s);
-        return p.big ? launch_rank_f16<1, 2, 1, 2, 4>(p, grid, device, s) : launch_rank_f16<1, 1, 1, 2, 2>(p, grid, device, s);
-    }
-    if (p.split) {
-        if (p.metric == 0) return p.big ? launch_rank_split<0, 2, 1, 2, 4>(p, grid, device, s) : launch_rank_split<0, 1, 1, 2, 2>(p, grid, device, s);
-        return p.big ? launch_rank_split<1, 2, 1, 2, 4>(p, grid, device, s) : launch_rank_split<1, 1, 1, 2, 2>(p, grid, device, s);
-    }
-    if (p.metric == 0) return p.big ? launch_rank_f32<0, 2>(p, grid, s) : launch_rank_f32<0, 1>(p, grid, s);
-    return p.big ? launch_rank_f32<1, 2>(p, grid, s) : launch_rank_f32<1, 1>(p, grid, s);
+    const dim3 grid = wide ? dim3((p.nlist + 255) / 256, (p.nq + 127) / 128)
+                           : dim3((p.nlist + T - 1) / T, (p.nq + T - 1) / T, p.split && p.ksplit > 1 ? p.ksplit : 1u); // (z: split-K, the row zeroed by the preparation)
+    return with_rank_shape(p.metric, wide, p.big, [&](auto shape) {
+        using S = decltype(shape);
+        if (p.split && p.f16) return launch_rank_f16<S>(p, grid, device, s);
+        if (p.split) return launch_rank_split<S>(p, grid, device, s);
+        return launch_rank_f32<S>(p, grid, s);
+    });
 }
 
 uint32_t select_exact_np2(uint32_t nprobe) { return next_pow2(nprobe); }
@@ -132,18 +137,15 @@ hipError_t launch_select_exact(const SelectParams& p, int device, hipStream_t s,
     // key_window != null: [nq][np2] u64 in global memory (nprobe > kNprobeMax)
     const size_t lds = (key_window ? 0 : (size_t)np2 * 8) + (size_t)p.D * 4 + kThreads * 4;
     static LdsAttrCache attr, attr_unf; // nprobe > 4096: more than the default 64 KB of dynamic LDS
-    const bool unf = p.numeric_variant == (uint32_t)kVarPortable;
-    const void* fn = unf ? reinterpret_cast<const void*>(&k_select<true>) : reinterpret_cast<const void*>(&k_select<false>);
-    if (probe_stage(2, fn, dim3(p.nq), kThreads, lds)) return hipSuccess;
-    hipError_t e = (unf ? attr_unf : attr).ensure(fn, lds, device);
-    if (e != hipSuccess) return e;
-    if (unf) hipLaunchKernelGGL(k_select<true>, dim3(p.nq), dim3(kThreads), lds, s, (const float*)p.scores, p.nlist, p.nprobe, np2, p.metric, p.rot,
-                                p.cent, p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream, p.nvec, p.prof_total, p.consts,
-                                p.bsum, key_window);
-    else hipLaunchKernelGGL(k_select<false>, dim3(p.nq), dim3(kThreads), lds, s, (const float*)p.scores, p.nlist, p.nprobe, np2, p.metric, p.rot,
-                       p.cent, p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream, p.nvec, p.prof_total, p.consts,
-                       p.bsum, key_window);
-    return hipGetLastError();
+    const auto launch = [&](auto kernel, LdsAttrCache& cache) -> hipError_t {
+        if (probe_stage(2, reinterpret_cast<const void*>(kernel), dim3(p.nq), kThreads, lds)) return hipSuccess;
+        hipError_t e = cache.ensure(reinterpret_cast<const void*>(kernel), lds, device);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(p.nq), dim3(kThreads), lds, s, (const float*)p.scores, p.nlist, p.nprobe, np2, p.metric, p.rot, p.cent,
+                           p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream, p.nvec, p.prof_total, p.consts, p.bsum, key_window);
+        return hipGetLastError();
+    };
+    return p.numeric_variant == (uint32_t)kVarPortable ? launch(&k_select<true>, attr_unf) : launch(&k_select<false>, attr);
 }
 
 namespace {
@@ -194,7 +196,7 @@ hipError_t launch_select_mfma(const SelectParams& p, int device, hipStream_t s) 
 #endif
     const size_t rowsN = RBQ_SEL_ROWS * ((size_t)p.D + 8) * 4 + 16;
     g.stage_rows = (p.lazy && lds + rowsN <= 64 * 1024) ? (uint32_t)RBQ_SEL_ROWS : 0u;
-    // exact head evaluation (rank_mfma.hpp, step 3b): its scratch shares the rows' region (used before the scoring round)
+    // exact head evaluation (select_mfma.hpp, step 3b): its scratch shares the rows' region (used before the scoring round)
     g.hx_nv = 0;
     size_t regionN = g.stage_rows ? rowsN : 0;
     if (p.lazy && p.head_exact && p.lut && p.top_k <= kHxMaxVec && p.D % 16 == 0) {
@@ -214,13 +216,12 @@ hipError_t launch_select_mfma(const SelectParams& p, int device, hipStream_t s) 
 }
 
 hipError_t launch_probes_given(const ProbesGivenParams& p, hipStream_t s) {
-    if (p.numeric_variant == (uint32_t)kVarPortable)
-        hipLaunchKernelGGL(k_probes_given<true>, dim3(p.nq), dim3(kThreads), (size_t)p.D * 4 + kThreads * 4, s, p.list_ids, p.list_counts,
-                           p.max_lists, p.nlist, p.metric, p.rot, p.cent, p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream,
-                           p.consts, p.bsum);
-    else hipLaunchKernelGGL(k_probes_given<false>, dim3(p.nq), dim3(kThreads), (size_t)p.D * 4 + kThreads * 4, s, p.list_ids, p.list_counts,
-                            p.max_lists, p.nlist, p.metric, p.rot, p.cent, p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream,
-                            p.consts, p.bsum);
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(p.nq), dim3(kThreads), (size_t)p.D * 4 + kThreads * 4, s, p.list_ids, p.list_counts, p.max_lists,
+                           p.nlist, p.metric, p.rot, p.cent, p.D, p.list_gb0, p.list_n, p.probe, p.wl, p.wl_stride, p.nstream, p.consts, p.bsum);
+    };
+    if (p.numeric_variant == (uint32_t)kVarPortable) launch(&k_probes_given<true>);
+    else launch(&k_probes_given<false>);
     return hipGetLastError();
 }
 

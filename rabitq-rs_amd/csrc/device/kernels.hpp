@@ -274,6 +274,18 @@ __device__ __forceinline__ float key_to_float(int32_t k) {
 }
 __device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
+// wave-wide sum of one u32 per lane, on DPP (row_shr 1/2/4/8, row_bcast 15/31; missing lanes read 0, the result is read from lane 63)
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+    int x = (int)v;
+    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
+    return (uint32_t)__builtin_amdgcn_readlane(x, 63);
+}
+
 // Exclusive prefix sum of one value per thread over a 256-thread workgroup (s_w: 4 words of LDS scratch, free
 // again on return); `total` receives the sum of all values.
 __device__ __forceinline__ uint32_t block_scan_excl256(uint32_t v, uint32_t* s_w, uint32_t tid, uint32_t& total) {

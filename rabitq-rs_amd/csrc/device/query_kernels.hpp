@@ -1,6 +1,6 @@
 // query_kernels.hpp — the kernels of the query stages in front of the scan that are not templates on the GEMM shape:
-// k_prep / k_prep_wave (rotate + constants + LUT), k_rank_scores and k_select (the all-pairs canonical ranking kept as
-// the exact_rank option).  Included by k_query.hip only (non-template __global__ functions: one definition).
+// k_prep / k_prep_wave (rotate + constants + LUT) and k_rank_scores (the all-pairs canonical ranking kept as the exact_rank option;
+// its selection, k_select, is in select_given.hpp).  Included by k_query.hip only (non-template __global__ functions: one definition).
 //
 // Query preparation has three kernels: k_prep and k_prep_wave here, k_lat_front in latency.hpp.  What they compute is ONE copy of
 // device functions — rotate_by_wave, store_rotated (the rotated query, its GEMM image, the f16 residual), lut_entries,
@@ -628,144 +628,5 @@ __global__ __launch_bounds__(kThreads) void k_rank_scores(const float* __restric
             }
         }
 }
-
-
-// UNF: the epilogue's first operation is not fused (kVarPortable: block_lbmin)
-template <bool UNF = false>
-__global__ __launch_bounds__(kThreads) void k_select(const float* __restrict__ scores, uint32_t nlist, uint32_t nprobe,
-                                                     uint32_t np2, int metric, const float* __restrict__ rot,
-                                                     const float* __restrict__ cent, uint32_t D,
-                                                     const uint32_t* __restrict__ list_gb0,
-                                                     const uint32_t* __restrict__ list_n,
-                                                     ProbeInfo* __restrict__ probe, StreamItem* __restrict__ wl,
-                                                     uint64_t wl_stride, uint32_t* __restrict__ nstream,
-                                                     unsigned long long* __restrict__ nvec_probed,
-                                                     unsigned long long* __restrict__ prof_total,
-                                                     const QueryConsts* __restrict__ consts,
-                                                     const BlockSummary* __restrict__ bsum, uint64_t* gsel) {
-    // gsel != null: the key window [nq][np2] lives in global memory (nprobe beyond what the LDS of one compute unit holds:
-    // the reference only clamps nprobe to the number of lists, src/ivf.rs:1791 — slow here, but served)
-    extern __shared__ __align__(16) unsigned char smraw[];
-    uint64_t* sel = gsel ? gsel + (size_t)blockIdx.x * np2 : reinterpret_cast<uint64_t*>(smraw);
-    float* qrot = reinterpret_cast<float*>(smraw + (gsel ? (size_t)0 : (size_t)np2 * 8));
-    uint32_t* part = reinterpret_cast<uint32_t*>(qrot + D);
-    __shared__ uint32_t hist[256];
-    __shared__ uint64_t s_prefix, s_mask;
-    __shared__ uint32_t s_k, s_cnt;
-    __shared__ unsigned long long s_nvec;
-    const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    const float* sc = scores + (size_t)q * nlist;
-
-    for (uint32_t i = tid; i < D; i += kThreads) qrot[i] = rot[(size_t)q * D + i];
-    if (tid == 0) { s_prefix = 0; s_mask = 0; s_k = nprobe - 1; s_cnt = 0; s_nvec = 0; }
-    __syncthreads();
-
-    if (nprobe < nlist) {
-        for (int pass = 7; pass >= 0; --pass) {
-            const int shift = pass * 8;
-            hist[tid] = 0;
-            __syncthreads();
-            const uint64_t prefix = s_prefix, mask = s_mask;
-            for (uint32_t i = tid; i < nlist; i += kThreads) {
-                uint64_t key = make_key(sc[i], i, metric);
-                if ((key & mask) == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                uint32_t k = s_k, cum = 0, b = 0;
-                for (; b < 256; ++b) {
-                    uint32_t h = hist[b];
-                    if (k < cum + h) break;
-                    cum += h;
-                }
-                s_k = k - cum;
-                s_prefix = prefix | ((uint64_t)b << shift);
-                s_mask = mask | (0xffull << shift);
-            }
-            __syncthreads();
-        }
-    } else if (tid == 0) {
-        s_prefix = ~0ull;
-    }
-    __syncthreads();
-    const uint64_t kstar = s_prefix;
-    for (uint32_t i = tid; i < np2; i += kThreads) sel[i] = ~0ull;
-    if (gsel) __threadfence_block();
-    __syncthreads();
-    for (uint32_t i = tid; i < nlist; i += kThreads) {
-        uint64_t key = make_key(sc[i], i, metric);
-        if (key <= kstar) {
-            uint32_t pos = atomicAdd(&s_cnt, 1u);
-            if (pos < np2) sel[pos] = key;
-        }
-    }
-    if (gsel) __threadfence_block(); // (global window: the workgroup's own writes are read back by other lanes)
-    __syncthreads();
-    // bitonic sort ascending
-    for (uint32_t k = 2; k <= np2; k <<= 1)
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = tid; i < np2; i += kThreads) {
-                uint32_t ixj = i ^ j;
-                if (ixj > i) {
-                    uint64_t a = sel[i], b = sel[ixj];
-                    bool up = (i & k) == 0;
-                    if ((a > b) == up) { sel[i] = b; sel[ixj] = a; }
-                }
-            }
-            if (gsel) __threadfence_block();
-            __syncthreads();
-        }
-
-    // per-probe constants (src/ivf.rs:1850-1857) + block counts
-    const uint32_t per = (nprobe + kThreads - 1) / kThreads;
-    const uint32_t r0 = tid * per, r1 = (r0 + per < nprobe) ? r0 + per : nprobe;
-    uint32_t local = 0;
-    unsigned long long local_vec = 0;
-    for (uint32_t r = r0; r < r1; ++r) {
-        uint32_t cid = (uint32_t)(sel[r] & 0xffffffffu);
-        float s = sc[cid], dist, dot;
-        const float* c = cent + (size_t)cid * D;
-        // L2: score IS the centroid distance; the dot product only feeds the non-finite lower-bound
-        // fallback of the IP metric (src/ivf.rs:2031-2042), so it is not computed here.
-        if (metric == 0) { dist = s; dot = 0.0f; }
-        else { dot = s; dist = canon_l2(qrot, c, D); }
-        ProbeInfo pi;
-        pi.g_add = metric == 0 ? dist : -dot;
-        pi.g_err = sqrtf(dist);
-        pi.dotqc = dot;
-        pi.cid = cid;
-        probe[(size_t)q * nprobe + r] = pi;
-        local += (list_n[cid] + 31u) >> 5;
-        local_vec += list_n[cid];
-    }
-    part[tid] = local;
-    if (local_vec) atomicAdd(&s_nvec, local_vec);
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t run = 0;
-        for (uint32_t i = 0; i < kThreads; ++i) { uint32_t v = part[i]; part[i] = run; run += v; }
-        nstream[q] = run;
-        nvec_probed[q] = s_nvec; // sum of n_c over the probed lists: the scan's algorithmic work
-        if (prof_total) atomicAdd(prof_total + prof_stripe(q), s_nvec);
-    }
-    __syncthreads();
-    uint64_t pos = (uint64_t)q * wl_stride + part[tid];
-    const QueryConsts qc = consts[q];
-    for (uint32_t r = r0; r < r1; ++r) {
-        uint32_t cid = (uint32_t)(sel[r] & 0xffffffffu);
-        uint32_t n = list_n[cid], gb = list_gb0[cid], nb = (n + 31u) >> 5;
-        const ProbeInfo pi = probe[(size_t)q * nprobe + r]; // written by this thread above
-        for (uint32_t b = 0; b < nb; ++b) {
-            uint32_t nv = (b + 1 == nb) ? n - b * 32u : 32u;
-            StreamItem wi;
-            wi.gblock = gb + b;
-            wi.rank_nvalid = (r << 6) | nv;
-            wi.lbmin = block_lbmin(bsum[gb + b], pi.g_add, pi.g_err, qc, UNF);
-            wi.pad = 0;
-            wl[pos++] = wi;
-        }
-    }
-}
-
 
 } // namespace rbq

@@ -79,16 +79,6 @@ __host__ __device__ inline size_t scanw_lds_bytes(uint32_t Dc, uint32_t D, uint3
 }
 
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_readlane(x, 63);
-}
 // number of set bits of a wave-uniform mask below this lane (v_mbcnt: no per-lane 64-bit lane mask to keep in registers)
 __device__ __forceinline__ uint32_t mask_rank(unsigned long long m) {
     return (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));

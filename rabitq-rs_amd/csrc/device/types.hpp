@@ -19,7 +19,7 @@ struct QueryConsts {
     float delta, sum_vl, k1x, kbx, scale, qnorm;
     float qnorm2;     // |q|^2 of the rotated query (approximate ranking, rank_mfma.hpp)
     float exlo, exhi; // the ex-code dot product sum_i code_i * q_i of ANY code (code_i in [0, 2^ex - 1]) lies in [exlo, exhi],
-                      // rounding of the kernel's own summation included (lazy probe selection, rank_mfma.hpp)
+                      // rounding of the kernel's own summation included (lazy probe selection, select_mfma.hpp)
     float q1norm;     // sum_i |q_i| of the rotated query (rounding slack of that selection)
     float amin, amax; // sum over codebooks of the smallest / largest u8 entry: accu of ANY code lies in [amin, amax]
 };

@@ -49,7 +49,7 @@ LAZY_CASES = [
 
 @pytest.mark.parametrize("n,dim,nlist,bits,metric,nq,top_k,nprobe", LAZY_CASES)
 def test_lazy_selection_matches_oracle_and_eager(n, dim, nlist, bits, metric, nq, top_k, nprobe):
-    """Lazy probe selection (rank_mfma.hpp): results and diagnostics equal the oracle's; the lists that go to the scan are
+    """Lazy probe selection (select_mfma.hpp): results and diagnostics equal the oracle's; the lists that go to the scan are
     a subsequence of the reference's probe order (src/ivf.rs:1803-1835) with bit-exact g_add; dead_skipped is the size of
     the probed lists left out; and lazy_select = 0 (every probed list scored and streamed) gives the same bits."""
     data, built = build_index(n=n, dim=dim, nlist=nlist, total_bits=bits, metric=metric, normalize=(metric == 1), seed=900 + dim + bits)
