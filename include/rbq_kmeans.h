@@ -42,6 +42,16 @@ int rbq_kmeans_device(const float* d_data, uint64_t n, uint32_t dim, uint64_t k,
 uint64_t rbq_debug_set_kmeans_chunk_rows(uint64_t rows);
 /* TEST ONLY, process-wide: passes of the chunked assignment run so far (one per chunk of rows per assignment). */
 uint64_t rbq_debug_kmeans_assign_passes(void);
+/* TEST ONLY: the front that k-means, the hierarchical splits, rbq_index_append's nearest list, the MSTG closure assignment and
+ * the MSTG list selection share, alone, through the launchers those drivers call: canonical norms, split-bf16 images padded
+ * with zeros to Dp = dim rounded up to 32, and the ranking GEMM's approximate inner products.  centroids [k][dim] and rows
+ * [n][dim] are HOST pointers (k >= 1, dim >= 1, any n); a non-finite value is RBQ_INVALID_CONFIG, as in the drivers.  Rows go
+ * through in passes of the chunked assignment's size (rbq_debug_set_kmeans_chunk_rows applies), every pass reusing one set of
+ * buffers.  Outputs (HOST): out_dots [n][k] f32, out_nx [n] f32, out_nc [k] f32, *out_ncmax (the largest of out_nc);
+ * out_row_hi / out_row_lo [n][Dp] u16 and out_cent_hi / out_cent_lo [k][Dp] u16, each pair NULL or given. */
+int rbq_debug_gemm_shortlist_front(const float* centroids, uint64_t k, uint32_t dim, const float* rows, uint64_t n, int device,
+                                   float* out_dots, float* out_nx, float* out_nc, float* out_ncmax, uint16_t* out_row_hi,
+                                   uint16_t* out_row_lo, uint16_t* out_cent_hi, uint16_t* out_cent_lo);
 
 #ifdef __cplusplus
 }

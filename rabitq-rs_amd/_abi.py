@@ -179,6 +179,7 @@ LIBRBQ_BY_HEADER = {
         "rbq_kmeans_device": (_INT, [_VP, _U64, _U32, _U64, _U64, _U64, _U64, _INT, _U64, _U64, _INT, _VP, _VP, C.POINTER(_F64), _VP]),
         "rbq_debug_set_kmeans_chunk_rows": (_U64, [_U64]),
         "rbq_debug_kmeans_assign_passes": (_U64, []),
+        "rbq_debug_gemm_shortlist_front": (_INT, [_VP, _U64, _U32, _VP, _U64, _INT, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     },
     # include/rbq_persist.h
     "rbq_persist.h": {

@@ -441,6 +441,26 @@ int rbq_kmeans_device(const float* d_data, uint64_t n, uint32_t dim, uint64_t k,
 }
 uint64_t rbq_debug_set_kmeans_chunk_rows(uint64_t rows) { return g_km_chunk_rows_cap.exchange(rows, std::memory_order_relaxed); }
 uint64_t rbq_debug_kmeans_assign_passes(void) { return g_km_assign_passes.load(std::memory_order_relaxed); }
+int rbq_debug_gemm_shortlist_front(const float* centroids, uint64_t k, uint32_t dim, const float* rows, uint64_t n, int device,
+                                   float* out_dots, float* out_nx, float* out_nc, float* out_ncmax, uint16_t* out_row_hi,
+                                   uint16_t* out_row_lo, uint16_t* out_cent_hi, uint16_t* out_cent_lo) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (k == 0 || k > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "k must be in 1..2^32 - 1");
+    if (dim == 0 || dim > 0xffffffe0u) return fail(RBQ_INVALID_CONFIG, "dim must be in 1..2^32 - 32");
+    if (!centroids || !out_nc || !out_ncmax || (n && (!rows || !out_dots || !out_nx))) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    if (!out_row_hi != !out_row_lo || !out_cent_hi != !out_cent_lo) return fail(RBQ_INVALID_CONFIG, "hi and lo images go together");
+    std::vector<int> devs;
+    int rc;
+    if ((rc = resolve_devices(1, &device, devs))) return rc;
+    DeviceGuard g(device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    FrontTapArgs a{centroids, k, dim, rows, n, out_dots, out_nx, out_nc, out_ncmax, out_row_hi, out_row_lo, out_cent_hi, out_cent_lo};
+    std::string detail;
+    rc = gemm_shortlist_front_tap(a, device, detail);
+    return rc ? fail(rc, detail) : RBQ_OK;
+    RBQ_GUARD_END
+}
 int rbq_build_stream_push(rbq_builder* b, const float* vectors, const uint32_t* assign, uint64_t first_id, uint64_t count) {
     g_err.clear();
     RBQ_GUARD_BEGIN

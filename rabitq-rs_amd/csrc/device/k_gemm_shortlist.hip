@@ -5,7 +5,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <string>
 
+#include "rbq.h"
 #include "launch.hpp"
 #include "kernels.hpp"
 #include "km_common.hpp"
@@ -191,6 +193,56 @@ hipError_t KmGemmAssign::run(const float* xs, const float* xn, uint64_t m, const
         e = hipGetLastError();
     }
     return e;
+}
+
+// TEST ONLY: what the drivers' front leaves behind, copied out pass by pass (nothing here is computed by other code than theirs)
+int gemm_shortlist_front_tap(const FrontTapArgs& a, int device, std::string& detail) {
+    const uint64_t n = a.n, k = a.k;
+    const uint32_t dim = a.dim, Dp = km_dp(dim);
+    const uint64_t R = km_chunk_rows(n, k, Dp);
+    hipStream_t s = 0;
+    KmTemp t;
+    float *cent = nullptr, *d_in = nullptr, *nx = nullptr, *dots = nullptr;
+    uint32_t* flag = nullptr;
+    uint16_t *xh = nullptr, *xl = nullptr;
+    CentView cv{(uint32_t)k, dim, Dp, nullptr, nullptr, nullptr, nullptr};
+    KM_TRY(t.alloc(&flag, 1));
+    KM_TRY(t.alloc(&cent, k * dim));
+    KM_TRY(t.alloc(&cv.nc, k));
+    KM_TRY(t.alloc(&cv.ncmax_bits, 1));
+    KM_TRY(t.alloc(&cv.hi, k * Dp));
+    KM_TRY(t.alloc(&cv.lo, k * Dp));
+    KM_TRY(t.alloc(&d_in, R * dim));
+    KM_TRY(t.alloc(&nx, R));
+    KM_TRY(t.alloc(&xh, R * Dp));
+    KM_TRY(t.alloc(&xl, R * Dp));
+    KM_TRY(t.alloc(&dots, R * k));
+    KM_TRY(hipMemcpy(cent, a.centroids, k * dim * 4, hipMemcpyHostToDevice));
+    bool bad = false;
+    KM_TRY(nonfinite_sync(cent, k * dim, flag, s, &bad));
+    if (bad) { detail = "GEMM-shortlist front input must be finite"; return RBQ_INVALID_CONFIG; }
+    KM_TRY(launch_split_centroids(cent, cv, s));
+    KM_TRY(hipMemcpy(a.nc, cv.nc, k * 4, hipMemcpyDeviceToHost));
+    KM_TRY(hipMemcpy(a.ncmax, cv.ncmax_bits, 4, hipMemcpyDeviceToHost));
+    if (a.cent_hi) {
+        KM_TRY(hipMemcpy(a.cent_hi, cv.hi, k * Dp * 2, hipMemcpyDeviceToHost));
+        KM_TRY(hipMemcpy(a.cent_lo, cv.lo, k * Dp * 2, hipMemcpyDeviceToHost));
+    }
+    for (uint64_t r0 = 0; r0 < n; r0 += R) {
+        const uint32_t nr = (uint32_t)(n - r0 < R ? n - r0 : R);
+        KM_TRY(hipMemcpy(d_in, a.rows + r0 * dim, (size_t)nr * dim * 4, hipMemcpyHostToDevice));
+        KM_TRY(nonfinite_sync(d_in, (uint64_t)nr * dim, flag, s, &bad));
+        if (bad) { detail = "GEMM-shortlist front input must be finite"; return RBQ_INVALID_CONFIG; }
+        KM_TRY(launch_row_norms(d_in, nr, dim, nx, s));
+        KM_TRY(launch_approx_dots(d_in, nr, dim, cv, xh, xl, dots, device, s));
+        KM_TRY(hipMemcpy(a.nx + r0, nx, (size_t)nr * 4, hipMemcpyDeviceToHost));
+        KM_TRY(hipMemcpy(a.dots + r0 * k, dots, (size_t)nr * k * 4, hipMemcpyDeviceToHost));
+        if (a.row_hi) {
+            KM_TRY(hipMemcpy(a.row_hi + r0 * Dp, xh, (size_t)nr * Dp * 2, hipMemcpyDeviceToHost));
+            KM_TRY(hipMemcpy(a.row_lo + r0 * Dp, xl, (size_t)nr * Dp * 2, hipMemcpyDeviceToHost));
+        }
+    }
+    return RBQ_OK;
 }
 
 } // namespace rbq

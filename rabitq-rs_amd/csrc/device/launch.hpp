@@ -294,6 +294,18 @@ hipError_t launch_row_norms(const float* x, uint64_t rows, uint32_t dim, float* 
 // image in xh / xl.  xh, xl [nr rounded up to 128][Dp], dots [nr rounded up to 128][k]; image rows beyond nr are stale, their scores unused.
 hipError_t launch_approx_dots(const float* x, uint32_t nr, uint32_t dim, const CentView& v, uint16_t* xh, uint16_t* xl, float* dots,
                               int device, hipStream_t s);
+// TEST ONLY (rbq_debug_gemm_shortlist_front, include/rbq_kmeans.h): the front alone over HOST rows and centroids, in passes of
+// km_chunk_rows rows, through the launchers above and nothing else; every pointer is the caller's host memory
+struct FrontTapArgs {
+    const float* centroids; // [k][dim]
+    uint64_t k;
+    uint32_t dim;
+    const float* rows;      // [n][dim]
+    uint64_t n;
+    float *dots, *nx, *nc, *ncmax;                  // [n][k], [n], [k], [1]
+    uint16_t *row_hi, *row_lo, *cent_hi, *cent_lo;  // [n][Dp] / [k][Dp], each pair null or given
+};
+int gemm_shortlist_front_tap(const FrontTapArgs& a, int device, std::string& detail); // RBQ_* code; detail on failure
 
 // ---- k-means (k_kmeans.hip): run_kmeans_with_config on the current device, arguments already validated (rbq_kmeans_device)
 constexpr uint64_t kKmeansChunkBytes = 512ull << 20; // per-chunk assignment workspace (R rows x gemm_shortlist_row_bytes, R >= 128)

@@ -107,6 +107,29 @@ def to_device(data, device):
     return x
 
 
+def debug_gemm_shortlist_front(centroids, rows, device=0, images=True):
+    """TEST ONLY (rbq_debug_gemm_shortlist_front): what the shared front of the nearest-centroid paths computes for host
+    `rows` [n][dim] against host `centroids` [k][dim].  A dict: dots [n][k], nx [n], nc [k] f32, ncmax (f32 scalar), and with
+    `images` the split-bf16 planes row_hi, row_lo [n][Dp], cent_hi, cent_lo [k][Dp] u16 (Dp = dim rounded up to 32)."""
+    from .index import _check, lib
+    c = np.ascontiguousarray(centroids, dtype=np.float32)
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if c.ndim != 2 or x.ndim != 2 or x.shape[1] != c.shape[1]:
+        from . import RabitqError
+        raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "centroids [k][dim] and rows [n][dim] must share dim")
+    (k, dim), n = c.shape, x.shape[0]
+    Dp =(dim + 31) // 32 * 32
+    out = {"dots": np.empty((n, k), np.float32), "nx": np.empty(n, np.float32), "nc": np.empty(k, np.float32),
+           "ncmax": np.empty(1, np.float32)}
+    if images:
+        out.update(row_hi=np.empty((n, Dp), np.uint16), row_lo=np.empty((n, Dp), np.uint16),
+                   cent_hi=np.empty((k, Dp), np.uint16), cent_lo=np.empty((k, Dp), np.uint16))
+    ptr = [out[f].ctypes.data if f in out else None for f in ("dots", "nx", "nc", "ncmax", "row_hi", "row_lo", "cent_hi", "cent_lo")]
+    _check(lib().rbq_debug_gemm_shortlist_front(c.ctypes.data, k, dim, x.ctypes.data, n, int(device), *ptr))
+    out["ncmax"] = out["ncmax"][0]
+    return out
+
+
 def run_kmeans_with_config(data, k, config=None, device=0, stats=None):
     """`run_kmeans_with_config` on `device`.  `data` [n][dim]: a numpy array (uploaded once) or a CUDA tensor (used in place
     when it is contiguous f32 on `device`).  Returns a KMeansResult with host arrays.  `stats`, when a dict, receives the run's
