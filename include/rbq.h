@@ -251,7 +251,17 @@ void rbq_host_free(void* p);
  * on the replica's device: borrowed, must outlive the index) indexed by id; passing NULL detaches.  While enabled,
  * every search re-scores its returned ids with the exact l2_distance_sqr / dot (canonical order of
  * src/math.rs:154-245) against these vectors and re-sorts them; ids >= n get NaN.  top_k <= 1024.
- * Toggle with rbq_debug_set_option(idx, "rerank", 0/1) once vectors are attached (attaching switches it on). */
+ * Toggle with rbq_debug_set_option(idx, "rerank", 0/1) once vectors are attached (attaching switches it on).
+ * Pool: rbq_debug_set_option(idx, "rerank_pool", v), on every replica, with or without vectors attached.  v <= 0 stores 0
+ * (the default: everything above); v > 4096 is RBQ_INVALID_CONFIG.  While the rerank is on and v > top_k >= 1, every search
+ * entry (rbq_search_batch on every replica, rbq_search_batch_device on the caller's stream) returns per query: the POOL is
+ * what the same call returns with top_k := v and the rerank off (same nprobe, filter, numeric variant and options; `diag`
+ * is that call's), entries (id, rank r) for r = 0 .. c-1, c <= v; each is scored exactly as above (ids >= n get the NaN
+ * 0x7fc00000); the entries are ordered by f32::total_cmp of the exact score (descending for inner product: NaN then
+ * comes first), then by r; the first min(top_k, c) are written, out_counts is their number, unused slots are UINT64_MAX /
+ * NaN.  For v <= 1024 that is the first top_k entries of the unpooled rerank's result at top_k := v, bit for bit.  The
+ * bounds on top_k (2^20, 8 GiB of heap workspace) are then evaluated for v, and top_k itself may exceed 1024.  With
+ * v <= top_k nothing changes, the refusal of top_k > 1024 with the rerank on included. */
 int rbq_index_set_rerank_vectors(rbq_index* idx, const float* vectors, uint64_t n);
 
 /* Numeric variant: which build of the reference the kernels reproduce bit for bit.  The reference picks its arithmetic at
@@ -358,8 +368,9 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *                        shortlist's error bound is derived for)
  *   "rank_planar" 1      TEST ONLY: the split-bf16 ranking GEMM reads planar copies of its operands (two planes [rows][D] each,
  *                        de-interleaved per call) instead of the interleaved images — same kernel, same scores bit for bit
- * and three that are not result-neutral:
+ * and four that are not result-neutral:
  *   "rerank" 0/1         the optional full-precision rerank (needs rbq_index_set_rerank_vectors)
+ *   "rerank_pool" v      candidates the rerank re-scores per query, 0 = off, at most 4096 (rbq_index_set_rerank_vectors)
  *   "numeric_variant" v  rbq_index_set_numeric_variant(idx, v): which build of the reference the scores reproduce
  *   "debug_replica" r    which replica rbq_debug_copy_index / rbq_debug_copy_workspace read */
 int rbq_debug_set_option(rbq_index* idx, const char* name, int value);

@@ -250,6 +250,7 @@ struct Workspace {
     DevBuf rot_f16, rank_resid; // one-product f16 route: the f16 image [nq][D] of the rotated queries and |q - f16(q)| per query
     DevBuf ms_sl, ms_lists; // rbq_mstg_search_batch*: shortlists | their lengths | query norms; the selected lists | their counts
     DevBuf mr_pool;         // rbq_mstg_search_refined_batch*: the pool's slots [n][pool] u64 | estimates [n][pool] f32 | counts [n] u32
+    DevBuf rr_ids, rr_est, rr_counts; // pooled rerank: the pool's ids [n][pool] u64, estimates [n][pool] f32, counts [n] u32
     PinBuf h_in, h_out;      // rbq_search_batch: staging of one sub-batch
     hipEvent_t done = nullptr; // results of the sub-batch in flight have reached h_out / the caller's buffers
     uint64_t call_nq = 0;       // queries of the WHOLE host call this launch chain belongs to (0: a device-entry call — its own nq counts)
@@ -361,6 +362,8 @@ struct Options {
     uint64_t fetch_chunk = 0; // TEST ONLY: ids per staging chunk of rbq_index_fetch_embeddings (0 = default)
     uint64_t mstg_chunk = 0;  // TEST ONLY: staging chunk of rbq_mstg_save* in bytes, any value >= 1 (0 = default)
     uint64_t mstg_search_budget = 0; // TEST ONLY: per-chunk workspace of rbq_mstg_search_batch* in bytes (0 = default)
+    uint32_t rerank_pool = 0; // while rerank is on and rerank_pool > top_k: the search runs at top_k := rerank_pool, the pool is scored
+                              // exactly against the attached vectors and the best top_k are returned (0 = off; <= kRerankPoolMax)
     // option `name` := value (the options of rbq_debug_set_option that live in Options); RBQ_INVALID_CONFIG for an unknown name
     int set(const char* name, int value);
 };

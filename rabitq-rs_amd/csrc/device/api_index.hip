@@ -189,6 +189,10 @@ int Options::set(const char* name, int v) {
     else if (is("host_zero_copy")) host_zero_copy = v != 0;
     else if (is("rank_ksplit")) rank_ksplit = v < 0 ? 0 : v;
     else if (is("host_stage_helpers")) host_stage_helpers = v != 0;
+    else if (is("rerank_pool")) { // (may be set with or without vectors attached; it acts while the rerank is on and it exceeds top_k)
+        if (v > (int)kRerankPoolMax) return fail(RBQ_INVALID_CONFIG, "rerank_pool " + std::to_string(v) + " exceeds the limit of " + std::to_string(kRerankPoolMax));
+        rerank_pool = v > 0 ? (uint32_t)v : 0u;
+    }
     else return fail(RBQ_INVALID_CONFIG, std::string("unknown option ") + name);
     return RBQ_OK;
 }

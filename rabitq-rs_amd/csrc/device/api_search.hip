@@ -142,9 +142,10 @@ int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, ui
 
 namespace {
 // Core: everything on device pointers, enqueued on `stream`. Workspace buffers come from `w`.
-int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe_in,
-                  const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
-                  rbq_diag* d_diag, hipStream_t stream) {
+// `rerank`: the unpooled rerank (k_rerank over the returned ids) follows the scan
+int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe_in,
+                const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
+                rbq_diag* d_diag, hipStream_t stream, bool rerank) {
     const uint32_t D = ix->D, Dc = ix->Dc;
     const uint32_t nlist = (uint32_t)ix->n_lists;
     uint32_t nprobe = nprobe_in < 1 ? 1 : nprobe_in;
@@ -156,7 +157,7 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
     const bool heap_in_global = top_k > kTopKMax || scan_lds_bytes(Dc, D, ix->ex_bits, top_k) > kLdsPerWorkgroupMax;
     if (top_k > kTopKHardMax || (heap_in_global && (uint64_t)nq * ((uint64_t)top_k + 1) * 8 > (8ull << 30)))
         return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20 and nq * top_k * 8 bytes of heap workspace <= 8 GiB)");
-    if (ix->rerank && top_k > 1024) return fail(RBQ_INVALID_CONFIG, "rerank supports top_k <= 1024");
+    if (rerank && top_k > 1024) return fail(RBQ_INVALID_CONFIG, "rerank supports top_k <= 1024");
     const uint64_t wl_stride = std::max<uint64_t>(ix->nblk_desc_prefix[nprobe], 1);
 
     int rc;
@@ -298,9 +299,34 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
     if ((smask & 8u) && (rc = scan_stage(ix, w, nq, nprobe, top_k, wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag,
                          /*mstg=*/false, (ix->opt.exact_rank || big_nprobe) ? nullptr : (const uint32_t*)w->dead_skipped.p, stream)))
         return rc;
-    if (ix->rerank && !stage_probes()) // optional, default off: exact re-scoring of the returned ids against the attached raw vectors
+    if (rerank && !stage_probes()) // optional, default off: exact re-scoring of the returned ids against the attached raw vectors
         HIP_TRY(launch_rerank(d_queries, (uint32_t)nq, ix->dim, (const float*)ix->raw.p, ix->n_raw, ix->metric, top_k, d_ids, d_scores,
                               d_counts, stream));
+    return RBQ_OK;
+}
+
+// The search of one batch on device pointers.  With the rerank on and a pool above top_k (option rerank_pool) the pipeline above runs
+// unchanged at top_k := pool into the workspace, with the diagnostics of that call, and k_rerank_pool writes the caller's top_k:
+// the pool's entries by (exact score, rank in the pool).  Every bound on top_k is then the inner call's, on `pool`.
+int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe,
+                  const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
+                  rbq_diag* d_diag, hipStream_t stream) {
+    const uint32_t pool = ix->opt.rerank_pool;
+    if (!ix->rerank || pool <= top_k)
+        return search_core(ix, w, d_queries, nq, top_k, nprobe, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag, stream, ix->rerank);
+    int rc;
+    if ((rc = w->rr_ids.ensure(nq * (size_t)pool * 8))) return rc;
+    if ((rc = w->rr_est.ensure(nq * (size_t)pool * 4))) return rc;
+    if ((rc = w->rr_counts.ensure(nq * 4))) return rc;
+    if ((rc = search_core(ix, w, d_queries, nq, pool, nprobe, d_filter, filter_nbits, (uint64_t*)w->rr_ids.p, (float*)w->rr_est.p,
+                          (uint32_t*)w->rr_counts.p, d_diag, stream, /*rerank=*/false)))
+        return rc;
+    if (stage_probes()) return RBQ_OK; // (the four stages of the inner call are what a probe reports)
+    RerankPoolParams P;
+    P.queries = d_queries; P.raw = (const float*)ix->raw.p; P.n_raw = ix->n_raw; P.nq = (uint32_t)nq; P.dim = ix->dim; P.metric = ix->metric;
+    P.pool = pool; P.top_k = top_k; P.pool_ids = (const uint64_t*)w->rr_ids.p; P.pool_counts = (const uint32_t*)w->rr_counts.p;
+    P.out_ids = d_ids; P.out_scores = d_scores; P.out_counts = d_counts;
+    HIP_TRY(launch_rerank_pool(P, ix->device, stream));
     return RBQ_OK;
 }
 

@@ -16,6 +16,7 @@
 //   k_load.hip   streamed RBQ1 loader: spans of the stream -> device layout, ex-code prefix check
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, canon_score.hpp)
 //   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan.hpp)
+//   k_rerank_pool.hip  pooled rerank: exact scores of a candidate pool from whole lines of the raw rows, order in LDS (kernels.hpp)
 //   k_append.hip rbq_index_append: carry of an index into a larger geometry, id bound, nearest list of rotated rows (km_common.hpp)
 //   k_remove.hip rbq_index_remove_ids: keep masks against a sorted id set, slot map, gather of an index into a smaller geometry
 #pragma once
@@ -236,6 +237,23 @@ hipError_t launch_hl_planes(const uint16_t* hl, uint64_t rows, uint32_t D, uint1
 // exact re-scoring of the returned ids against caller-supplied raw vectors (optional rerank, default off)
 hipError_t launch_rerank(const float* queries, uint32_t nq, uint32_t dim, const float* raw, uint64_t n_raw, int metric,
                          uint32_t top_k, uint64_t* ids, float* scores, const uint32_t* counts, hipStream_t s);
+// pooled rerank (option rerank_pool; k_rerank_pool.hip): the exact scores of a query's pool of candidates
+// (the result of the search at top_k := pool), ordered by (exact score, rank in the pool); the first top_k are the answer
+constexpr uint32_t kRerankPoolMax = 4096; // one workgroup orders a query's pool in LDS (the figure of kMrPoolMax, for its reason)
+struct RerankPoolParams {
+    const float* queries;        // [nq][dim], input space
+    const float* raw;            // [n_raw][dim]
+    uint64_t n_raw;
+    uint32_t nq, dim, metric;
+    uint32_t pool, top_k;        // top_k < pool <= kRerankPoolMax
+    const uint64_t* pool_ids;    // [nq][pool]
+    const uint32_t* pool_counts; // [nq]
+    uint64_t* out_ids;           // [nq][top_k]
+    float* out_scores;           // [nq][top_k]
+    uint32_t* out_counts;        // [nq]
+};
+size_t rerank_pool_lds_bytes(uint32_t dim, uint32_t pool);
+hipError_t launch_rerank_pool(const RerankPoolParams& P, int device, hipStream_t s);
 
 // brute-force index (bf.hpp, k_bf.hip): distances of a (query sub-batch x vector chunk), then the per-query BinaryHeap replay
 struct BfDistParams {

@@ -10,6 +10,7 @@ from ._abi import READ_FN, WRITE_FN  # noqa: F401  (their home is the prototype 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 LIB_PATH = os.environ.get("RBQ_LIB_PATH") or os.path.join(_HERE, "csrc", "librbq.so")  # override: kernel A/B builds
+RERANK_POOL_MAX = 4096  # largest pool of IvfRabitqIndex.set_rerank_pool (kRerankPoolMax: one workgroup orders a pool in LDS)
 
 
 def _hip_runtime_of_torch_first():
@@ -516,9 +517,10 @@ class IvfRabitqIndex:
     def release_stream(self, stream):
         _check(lib().rbq_release_stream(self._h, C.c_void_p(stream)))
 
-    def set_rerank_vectors(self, vectors=None, device_ptr=None, n=0):
+    def set_rerank_vectors(self, vectors=None, device_ptr=None, n=0, pool=None):
         """OPTIONAL extension (default off, not reference behaviour): attach raw vectors for the exact rerank.
-        `vectors` = host array [n][dim], or `device_ptr` + n; None detaches."""
+        `vectors` = host array [n][dim], or `device_ptr` + n; None detaches.  `pool` (not None): set_rerank_pool(pool)
+        once the vectors are attached."""
         if device_ptr is not None:
             _check(lib().rbq_index_set_rerank_vectors(self._h, C.c_void_p(device_ptr), int(n)))
         elif vectors is None:
@@ -526,6 +528,14 @@ class IvfRabitqIndex:
         else:
             v = np.ascontiguousarray(vectors, dtype=np.float32)
             _check(lib().rbq_index_set_rerank_vectors(self._h, v.ctypes.data, v.shape[0]))
+        if pool is not None:
+            self.set_rerank_pool(pool)
+
+    def set_rerank_pool(self, n):
+        """Candidates the rerank re-scores per query (option "rerank_pool", at most RERANK_POOL_MAX): while raw vectors are
+        attached and n > top_k, a search takes its n best candidates by the estimate, scores them exactly and returns the
+        best top_k.  None or 0 switches it off: the rerank then re-scores the top_k returned ids only."""
+        self.set_option("rerank_pool", 0 if n is None else int(n))
 
     def close(self):
         if self._h:
