@@ -20,7 +20,12 @@
 //          RankRun merge per half (scan.hpp)
 // No barrier, no hand-over, the threshold is never stale inside a tile's replay.  Vector-memory results come back in issue
 // order, so the order of the requests is the order of use: a round's code units first, then (once per tile) the next tile's
-// block records, which arrive while the round is decoded and replayed.  A query costs one wave for about 1.6 x the time k_scan
+// block records, which arrive while the round is decoded and replayed.  That holds only where the compiler's wait for the codes
+// is counted (`s_waitcnt vmcnt(N)`, N = the loads behind them): it has to assume the fewest loads any path to the wait can have
+// issued, and a load it must count as possibly pending makes every later reuse of its registers a full wait.  So below top_k 64
+// (`kOnce`) the records are requested at ONE place per tile, outside the loop of the rounds, the wait for the codes sits at the end
+// of that branch, and loaded values that only a rare path reads are read (by an empty asm) where the others are; from top_k 64 the
+// loop is as it was (there the same change costs registers: up to 14 more, and scratch at D = 1024).  A query costs one wave for about 1.6 x the time k_scan
 // keeps four.  Exactness is k_scan's: the tile prunes with the threshold of its start (T only shrinks: `lb >= T_then` implies
 // the reference skipped the candidate too), everything else is replayed in stream order against the running threshold.
 // Equal distances: the LAZY-TIE rule (below, at `amb_min`).
@@ -33,7 +38,7 @@ namespace rbq {
 #define RBQ_SCANW_WAVES 4     // launch-bounds occupancy target (waves per SIMD) of the RankRun instantiations (top_k >= 64): 128 VGPRs
 #endif
 #ifndef RBQ_SCANW_WAVES1
-#define RBQ_SCANW_WAVES1 5    // ... of the top_k < 64 instantiations: 96 VGPRs (they need 84 at D = 960), and 8 KB of LDS per query at D = 960
+#define RBQ_SCANW_WAVES1 5    // ... of the top_k < 64 instantiations: 96 VGPRs (they need 80 at D = 960), and 8 KB of LDS per query at D = 960
 #endif
 #ifndef RBQ_W_PREF_FIRST
 #define RBQ_W_PREF_FIRST 0    // 1: the next tile's records are requested BEFORE the first refine round's codes (else behind them)
@@ -108,6 +113,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
     static_assert(kWQueueCap * sizeof(WorkItem) + 32 == 512, "TR = 1: queue + batch list are the 64-entry heap scratch of the final sort");
     float* heap_d = (TR > 1 || RBQ_W_RANKRUN1) ? reinterpret_cast<float*>(s_b + 8) : reinterpret_cast<float*>(s_queue); // [64 TR]
     uint32_t* heap_s = reinterpret_cast<uint32_t*>(heap_d + 64 * TR);
+    constexpr bool kOnce = TR == 1 && !RBQ_W_RANKRUN1; // the records request outside the loop of the rounds, counted waits (top_k < 64)
 
     const uint32_t q = blockIdx.x, lane = threadIdx.x, half = lane >> 5, l32 = lane & 31u;
     const lds_lut_ptr lut0 = (lds_lut_ptr)(uint32_t)0; // == s_lut
@@ -249,6 +255,9 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
             StreamItem si;
             si.gblock = 0; si.rank_nvalid = 0; si.lbmin = 0.0f; si.pad = 0;
             if (live) si = wl[i];
+            // (read here on every path: a load the compiler must count as possibly pending behind this loop costs every later
+            // reuse of its registers a full vector-memory wait)
+            if (kOnce) asm volatile("" :: "v"(si.gblock), "v"(si.rank_nvalid), "v"(si.lbmin));
             if (live && bound_ok && si.lbmin >= T) { // block_lbmin(): no real vector of the block can pass
                 live = false;
                 if (count_skips) n_skip_l += si.rank_nvalid & 63u;
@@ -283,6 +292,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
                 qhead = (qhead + n) % kWQueueCap;
                 qcount -= n;
                 const uint8_t* blk = P.blocks + (size_t)cur.wi.gblock * stride;
+                if (kOnce) asm volatile("" :: "v"(cur.m.dotqc)); // (used on a rare path only: read here, so that it is never pending behind the tile step)
                 // per-lane bound with the threshold: the whole wave may be prunable without looking anything up
                 const bool live_c = !bound_ok || (__ballot(lane_prunable(cur.wi, cur.m, T)) != ~0ull);
                 const uint32_t nvalid = cur.wi.rank_nvalid & 63u;
@@ -492,31 +502,67 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
         WSTAMP_BEGIN();
         TileRegs nxt = {};
         uint32_t n_next = 0;
-        bool first = true;
-#if RBQ_W_PREF_FIRST
-        first = false;
-        fill_until();
-        n_next = qcount < 2u ? qcount : 2u;
-        if (n_next) issue_tile(nxt, qhead, n_next);
-#endif
-        collect(G);
-        do {
-            if (ncol && ex_bits) request(kDual);
-            if (first) {
-                // The next tile's records are requested HERE: behind the first round's own loads.  Vector-memory results come back
-                // in issue order, so a round whose loads were issued after this prefetch would wait for the (cold) records as well;
-                // this way the dot product waits for its codes only, and the records arrive while it and the replay run.
-                first = false;
+        if constexpr (kOnce) {
+            // the next tile's records: requested once per tile, here, outside the loop of the rounds (the header comment says why)
+            auto prefetch = [&]() __attribute__((always_inline)) {
                 fill_until();
                 n_next = qcount < 2u ? qcount : 2u;
-                if (n_next) issue_tile(nxt, qhead, n_next);
-            }
-            if (ncol) {
+                if (n_next) {
+                    issue_tile(nxt, qhead, n_next);
+                    // The wait for the first round's codes goes HERE, at the end of the branch that requested the records (the empty
+                    // asm reads them): here the compiler knows how many loads were issued behind the codes and leaves the records in
+                    // flight; behind the join of the two branches it has to assume none and would wait for the records as well.
+                    if (kPre && ex_bits && !RBQ_W_PREF_FIRST) {
+#pragma unroll
+                        for (int j = 0; j < (int)(kPre ? kNU : 1u); ++j) asm volatile("" :: "v"(ea[j].x), "v"(ea[j].y), "v"(ea[j].z), "v"(ea[j].w));
+                        asm volatile("" :: "v"(fa0), "v"(fr0));
+                    }
+                }
+            };
+#if RBQ_W_PREF_FIRST
+            prefetch();
+#endif
+            collect(G);
+            if (ncol && ex_bits) request(kDual);
+#if !RBQ_W_PREF_FIRST
+            // BEHIND the first round's own loads: vector-memory results come back in issue order, so a round whose loads were issued
+            // after this prefetch would wait for the (cold) records as well; this way the dot product waits for its codes only, and
+            // the records arrive while it and the replay run.
+            prefetch();
+#endif
+            while (ncol) {
                 finish(kDual);
                 if (fast && tie) break;
                 collect(G);
+                if (ncol && ex_bits) request(kDual);
             }
-        } while (ncol);
+        } else {
+            // top_k >= 64: the loop as it was (the records requested inside it, in its first trip)
+            bool first = true;
+#if RBQ_W_PREF_FIRST
+            first = false;
+            fill_until();
+            n_next = qcount < 2u ? qcount : 2u;
+            if (n_next) issue_tile(nxt, qhead, n_next);
+#endif
+            collect(G);
+            do {
+                if (ncol && ex_bits) request(kDual);
+                if (first) {
+                    // The next tile's records are requested HERE: behind the first round's own loads.  Vector-memory results come back
+                    // in issue order, so a round whose loads were issued after this prefetch would wait for the (cold) records as well.
+                    first = false;
+                    fill_until();
+                    n_next = qcount < 2u ? qcount : 2u;
+                    if (n_next) issue_tile(nxt, qhead, n_next);
+                }
+                if (ncol) {
+                    finish(kDual);
+                    if (fast && tie) break;
+                    collect(G);
+                }
+            } while (ncol);
+        }
         WSTAMP_END(st_rounds);
         if (fast && tie) break; // leave the pass now: the query is re-run with the exact heap
         T = cur_distk();
