@@ -347,7 +347,7 @@ struct Options {
     bool lazy_audit = false; // DIAGNOSTIC: the select kernel exports the lists it drops as a whole (workspace "audit_dead")
     bool lazy_select = true; // probe selection drops lists that are provably skipped as a whole (select_mfma.hpp)
     uint32_t tie_log_cap = 0; // TEST ONLY: entries per query of the tie log (0 = the default sizes)
-    bool tie_log = true;      // k_scan logs the candidates it refines; a tied query replays the log (scan.hpp)
+    bool tie_log = true;      // k_scan logs the candidates it refines; a tied query replays the log (topk.hpp)
     int latency_path = 1;     // small calls (see kLatMaxQueries) take the latency-first front (latency.hpp); 0 = never
     int rank_tile = 0;        // tile of the split-bf16 ranking GEMM (0 = by problem size)
     int rank_f16 = -1;        // one-product f16 ranking GEMM: -1 = by rule (big or wide calls at D >= 256), 0 = never, 1 = whenever possible

@@ -5,7 +5,7 @@
 //                Filtered-out vectors get NaN: the reference `continue`s on both, so a filtered vector and a non-finite
 //                distance are the same thing to the heap below.
 //   k_bf_select  one wave per query: the reference's BinaryHeap push / pop loop over the query's distances in id order
-//                (LdsHeap of scan.hpp: Rust's std BinaryHeap operation for operation), then into_sorted_vec.
+//                (LdsHeap of topk.hpp: Rust's std BinaryHeap operation for operation), then into_sorted_vec.
 //
 // Arithmetic (brute_force.rs:581-615; the crate is plain scalar Rust without fast-math, so no build of it reorders or fuses):
 //   bd   = sum_i (float)bit_i * rq_i        sequential from +0.0f, multiply then add (never fused)
@@ -26,7 +26,7 @@
 #include <stdint.h>
 
 #include "kernels.hpp"
-#include "scan.hpp"
+#include "topk.hpp"
 #include "types.hpp"
 
 namespace rbq {
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(64) void k_bf_select(BfSelectParams P) {
     __syncthreads();
     LdsHeap h{hd, hs, len};
     // Skipping: once the heap is full, the reference's push of a key above the root followed by its pop leaves the array as it
-    // was (scan.hpp, tie_log_replay: the key climbs the path from slot top_k to the root and the pop walks back down the same
+    // was (topk.hpp, tie_log_replay: the key climbs the path from slot top_k to the root and the pop walks back down the same
     // path) unless some node of that path equals its off-path child.  `ptie` is that condition, re-evaluated after every real
     // insertion; while it is false such a candidate is skipped.  Keys equal to the root are never skipped.
     auto path_tie = [&]() -> bool {

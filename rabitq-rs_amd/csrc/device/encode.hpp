@@ -9,7 +9,6 @@
 // The arithmetic is the CPU builder's (rbq_build.cpp), expression for expression; -ffp-contract=off.
 #pragma once
 #include "kernels.hpp"
-#include "scan.hpp"
 #include "encode_vec.hpp"
 
 namespace rbq {

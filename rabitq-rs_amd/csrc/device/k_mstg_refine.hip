@@ -28,7 +28,7 @@
 #include "rbq_mstg.h"
 #include "launch.hpp"
 #include "kernels.hpp"
-#include "scan.hpp" // lds_lut_ptr, accumulate_block_rt: the scan's own lookup of one vector's sign code
+#include "scan_codes.hpp" // lds_lut_ptr, accumulate_block_rt: the scan's own lookup of one vector's sign code
 
 namespace rbq {
 

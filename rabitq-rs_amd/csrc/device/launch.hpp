@@ -2,20 +2,20 @@
 // kernels only through these; each .hip file below compiles on its own, so a change to the host side does not
 // rebuild k_scan's instantiations and vice versa.
 //   k_query.hip  k_prep / k_prep_wave, k_rank_* , k_select*, k_probes_given     (kernels.hpp, rank_mfma.hpp, canon_score.hpp, select_*.hpp)
-//   k_scan.hip   k_scan<DT, EX, TR>                                               (scan.hpp)
+//   k_scan.hip   k_scan<DT, EX, TR>                                               (scan.hpp, scan_codes.hpp, topk.hpp)
 //   k_build.hip  encoder, reference-layout -> device-layout converters, sorting   (encode.hpp)
 //   k_gemm_shortlist.hip  the front of the GEMM-shortlist paths (finite check, norms, split images, dots), KmGemmAssign (km_common.hpp)
 //   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver         (km_common.hpp)
 //   k_hcluster.hip  MSTG hierarchical balanced k-means and its host driver                (km_common.hpp)
 //   k_save.hip   RBQ1 writer: device layout -> save_to_writer's cluster bytes, CRC-32 on the GPU
 //   k_fetch.hip  fetch_embedding: id map, decode + inverse rotation of stored vectors
-//   k_bf.hip     brute-force index: distances and the BinaryHeap replay                  (bf.hpp)
+//   k_bf.hip     brute-force index: distances and the BinaryHeap replay                  (bf.hpp, topk.hpp)
 //   k_bf_train.hip  brute-force index: the encoder's flat output, ex_code_packed         (encode_vec.hpp)
 //   k_mstg.hip   MSTG closure assignment (ClosureAssigner::assign) and its host driver       (km_common.hpp)
 //   k_mstg_save.hip  `.mstg` writer and loader: device layout <-> the crate's bincode records
 //   k_load.hip   streamed RBQ1 loader: spans of the stream -> device layout, ex-code prefix check
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, canon_score.hpp)
-//   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan.hpp)
+//   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan_codes.hpp)
 //   k_rerank_pool.hip  pooled rerank: exact scores of a candidate pool from whole lines of the raw rows, order in LDS (kernels.hpp)
 //   k_append.hip rbq_index_append: carry of an index into a larger geometry, id bound, nearest list of rotated rows (km_common.hpp)
 //   k_remove.hip rbq_index_remove_ids: keep masks against a sorted id set, slot map, gather of an index into a smaller geometry

@@ -1,6 +1,6 @@
 // scanw.hpp — k_scanw: the candidate scan with ONE WAVE PER QUERY (gfx950, wave64).
 //
-// Same semantics, inputs and outputs as k_scan (scan.hpp): search_cluster_v2_batched (src/ivf.rs:1901-2129) over the
+// Same semantics, inputs and outputs as k_scan (scan.hpp; the code lookups and the top-k are shared: scan_codes.hpp, topk.hpp): search_cluster_v2_batched (src/ivf.rs:1901-2129) over the
 // block stream k_select_mfma wrote for one query — accumulate_batch (src/simd.rs:972-1184), compute_batch_distances_u16
 // (:2090-2140), lower-bound pruning (src/ivf.rs:2013-2058), ip_packed_ex{2,6}_f32 (src/simd.rs:1835-1915), BinaryHeap
 // top-k (src/ivf.rs:904-931, :2116-2126).
@@ -17,7 +17,7 @@
 //   rounds lazy refine: the next (up to 4; from top_k 64: 8, finished as two halves) candidates whose lower bound is below the
 //          current TRUE threshold, 16 lanes per candidate, every code unit of the round requested before the first is decoded;
 //          then the reference's exact sequential prune / push / pop loop over them in scalar registers (top_k < 64) or one
-//          RankRun merge per half (scan.hpp)
+//          RankRun merge per half (topk.hpp)
 // No barrier, no hand-over, the threshold is never stale inside a tile's replay.  Vector-memory results come back in issue
 // order, so the order of the requests is the order of use: a round's code units first, then (once per tile) the next tile's
 // block records, which arrive while the round is decoded and replayed.  That holds only where the compiler's wait for the codes
@@ -30,7 +30,9 @@
 // the reference skipped the candidate too), everything else is replayed in stream order against the running threshold.
 // Equal distances: the LAZY-TIE rule (below, at `amb_min`).
 #pragma once
-#include "scan.hpp"
+#include "kernels.hpp"
+#include "scan_codes.hpp"
+#include "topk.hpp"
 
 namespace rbq {
 
@@ -40,32 +42,17 @@ namespace rbq {
 #ifndef RBQ_SCANW_WAVES1
 #define RBQ_SCANW_WAVES1 5    // ... of the top_k < 64 instantiations: 96 VGPRs (they need 80 at D = 960), and 8 KB of LDS per query at D = 960
 #endif
-#ifndef RBQ_W_PREF_FIRST
-#define RBQ_W_PREF_FIRST 0    // 1: the next tile's records are requested BEFORE the first refine round's codes (else behind them)
-#endif
-#ifndef RBQ_W_RANKRUN1
-#define RBQ_W_RANKRUN1 0        // 1: RankRun (a data-parallel merge of a whole batch) also below top_k 64 (measured: no gain over the sorted run)
-#endif
-#ifndef RBQ_W_PAIRS_RANK
-#define RBQ_W_PAIRS_RANK 1     // ... for the RankRun instantiations (top_k >= 64: five times the refinements of top_k = 10, half the rounds)
-#endif
-#ifndef RBQ_W_PAIRS
-#define RBQ_W_PAIRS 0          // a refine round requests two candidates per 16-lane group (finished as two halves of four)
-#endif
-#ifndef RBQ_W_FILL_BELOW
-#define RBQ_W_FILL_BELOW 4    // fill when fewer live blocks than this are queued (two tiles: one running, one to prefetch)
-#endif
-#ifndef RBQ_W_WIN0
-#define RBQ_W_WIN0 2          // stream entries examined by the first fill step (one tile's worth)
-#endif
-#ifndef RBQ_W_WIN_GROW
-#define RBQ_W_WIN_GROW 4
-#endif
+// Measured and not kept: the next tile's records requested BEFORE the first refine round's codes (they come back in issue order: the
+// round then waits for the cold records too); RankRun below top_k 64 (no gain over the sorted run); two candidates per 16-lane group
+// below top_k 64 (at top_k >= 64 there are five times the refinements of top_k = 10, and pairs halve the rounds).
+constexpr uint32_t kWFillBelow = 4;  // fill when fewer live blocks than this are queued (two tiles: one running, one to prefetch)
+constexpr uint32_t kWWin0 = 2;       // stream entries examined by the first fill step (one tile's worth)
+constexpr uint32_t kWWinGrow = 4;    // growth of the fill window per step
 // live-block ring and the largest fill window.  60 entries + the 8-word batch list = 512 bytes: at D = 960 / 7 bits a query then needs
 // exactly 8 KB of LDS (LUT 3840 + rotated query 3840 + 512), i.e. 20 waves per compute unit = five per SIMD.
 constexpr uint32_t kWQueueCap = 60;
 constexpr uint32_t kWWinMax = 56;
-static_assert(RBQ_W_FILL_BELOW - 1 + kWWinMax <= kWQueueCap, "live queue too small");
+static_assert(kWFillBelow - 1 + kWWinMax <= kWQueueCap, "live queue too small");
 // rotated query in LDS: the compile-time-dimension kernels decode exactly D / 16 codes per lane (no zero padding behind D needed)
 __host__ __device__ inline uint32_t scanw_qlen(uint32_t D, uint32_t ex_bits, bool compile_time_dim) {
     if (!ex_bits) return 0u;
@@ -80,7 +67,7 @@ __host__ __device__ inline bool scanw_compile_time_dim(uint32_t D, uint32_t Dc) 
 // heap).  TR = 1: the 512 bytes of queue + batch serve the final heap-sort (both are dead by then).
 __host__ __device__ inline size_t scanw_lds_bytes(uint32_t Dc, uint32_t D, uint32_t ex_bits, int tr) {
     return (size_t)Dc * 4 + (size_t)scanw_qlen(D, ex_bits, scanw_compile_time_dim(D, Dc)) * 4 + kWQueueCap * sizeof(WorkItem) + 32 +
-           ((tr > 1 || RBQ_W_RANKRUN1) ? (size_t)tr * 64 * 8 : (size_t)0);
+           (tr > 1 ? (size_t)tr * 64 * 8 : (size_t)0);
 }
 
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
@@ -111,9 +98,9 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
     WorkItem* s_queue = reinterpret_cast<WorkItem*>(s_q + qlen);
     uint32_t* s_b = reinterpret_cast<uint32_t*>(s_queue + kWQueueCap); // [8] lanes of a refine round's candidates, in order
     static_assert(kWQueueCap * sizeof(WorkItem) + 32 == 512, "TR = 1: queue + batch list are the 64-entry heap scratch of the final sort");
-    float* heap_d = (TR > 1 || RBQ_W_RANKRUN1) ? reinterpret_cast<float*>(s_b + 8) : reinterpret_cast<float*>(s_queue); // [64 TR]
+    float* heap_d = TR > 1 ? reinterpret_cast<float*>(s_b + 8) : reinterpret_cast<float*>(s_queue); // [64 TR]
     uint32_t* heap_s = reinterpret_cast<uint32_t*>(heap_d + 64 * TR);
-    constexpr bool kOnce = TR == 1 && !RBQ_W_RANKRUN1; // the records request outside the loop of the rounds, counted waits (top_k < 64)
+    constexpr bool kOnce = TR == 1; // the records request outside the loop of the rounds, counted waits (top_k < 64)
 
     const uint32_t q = blockIdx.x, lane = threadIdx.x, half = lane >> 5, l32 = lane & 31u;
     const lds_lut_ptr lut0 = (lds_lut_ptr)(uint32_t)0; // == s_lut
@@ -194,7 +181,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
     };
 
     // ---- top-k state (the same registers serve the sorted run / RankRun and, after a distance tie, the exact heap) ----
-    constexpr bool kRank = RBQ_W_RANKRUN1 || TR > 1; // RankRun (a data-parallel merge of a whole batch) also for one register per lane
+    constexpr bool kRank = TR > 1; // RankRun (a data-parallel merge of a whole batch) from top_k 64, the one-register sorted run below
     bool fast = !P.exact_heap; // sorted run (SortedRun / RankRun) until a distance tie shows up
     RegHeap<TR> rh;
     rh.hd = 0; rh.hs = 0u; rh.xd = 0; rh.xs = 0u; rh.len = 0u;
@@ -218,7 +205,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
     };
 
     constexpr uint32_t kNU = ex_w4((uint32_t)(DT ? DT : 16), (uint32_t)(EX ? EX : 2)); // code units per lane and vector
-    constexpr bool kDual = (RBQ_W_PAIRS || (RBQ_W_PAIRS_RANK && TR > 1)) && DT != 0 && EX != 0 && kNU <= 3u; // two candidates per 16-lane group (packed FMAs: one query read for both)
+    constexpr bool kDual = TR > 1 && DT != 0 && EX != 0 && kNU <= 3u; // two candidates per 16-lane group (packed FMAs: one query read for both)
     constexpr uint32_t G = kDual ? 8u : 4u; // candidates refined per round
     // the ex-code units of a round are requested into registers and decoded later (compile-time dimensions up to 4 units per
     // lane: D <= 1344 at 6 bits); otherwise they are loaded where they are decoded
@@ -242,13 +229,13 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
   for (;;) { // a second pass only after a distance tie on the sorted fast path
     uint32_t pos = 0;                 // next unexamined stream entry
     uint32_t qhead = 0, qcount = 0;   // live-block ring
-    uint32_t win = (uint32_t)RBQ_W_WIN0;
+    uint32_t win = kWWin0;
     float T = INFINITY;               // the threshold the tiles prune with (k-th distance when the last tile but one was replayed)
     bool tie = false;
 
     // fill steps until two tiles' worth of live blocks are queued (or the stream ends)
     auto fill_until = [&]() __attribute__((always_inline)) {
-        while (pos < ns && qcount < (uint32_t)RBQ_W_FILL_BELOW) {
+        while (pos < ns && qcount < kWFillBelow) {
             WSTAMP_BEGIN();
             const uint32_t i = pos + lane;
             bool live = lane < win && i < ns;
@@ -270,7 +257,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
             }
             qcount += (uint32_t)__popcll(lm);
             pos += win;
-            win = win * (uint32_t)RBQ_W_WIN_GROW < kWWinMax ? win * (uint32_t)RBQ_W_WIN_GROW : kWWinMax;
+            win = win * kWWinGrow < kWWinMax ? win * kWWinGrow : kWWinMax;
             wave_lds_sync();
             WSTAMP_END(st_fill);
         }
@@ -426,12 +413,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
                         } else sa = ex_bits == 6 ? ex_dot_units<6>(ex, s_q, gl, nunits) : ex_dot_units<2>(ex, s_q, gl, nunits);
                     }
                     if constexpr (V == kVarAvx512) sa = group16_reduce(sa);
-                    float tt2 = qc.scale * ip0;
-                    tt2 = tt2 + sa;
-                    tt2 = tt2 + qc.kbx;
-                    const float a = fa0 + ga0;
-                    const float mm = fr0 * tt2;
-                    v_d0 = a + mm;
+                    v_d0 = refined_distance(qc.scale, ip0, sa, qc.kbx, fa0, ga0, fr0);
                 }
                 // the refined distances go back to the candidates' lanes: candidate k of the half sits in lane 16 (k & 3) of v_d0;
                 // at ex_bits = 0 a candidate's distance is its estimate
@@ -442,53 +424,35 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
 #endif
                 WRS(st_r2);
                 // ---- replay the half's candidates in stream order
-                if (fast && kRank) {
-                    // the whole batch in one data-parallel step (RankRun, scan.hpp)
-                    uint32_t c_skip = 0, c_ext = 0, c_est = 0;
-                    int dk = bag_dk;
-                    const bool t1 = RankRun<TR>::merge_batch(rh, top_k, mph, __float_as_int(A_lb), __float_as_int(dj), A_slot, lane, count_skips,
-                                                             reinterpret_cast<int*>(heap_d), heap_s, c_skip, c_ext, c_est, dk, true, amb_min);
-                    bag_dk = dk;
-                    n_skip_u += c_skip; n_ext += c_ext; n_est += c_est;
-                    tie |= t1;
-                } else {
-                    // one taken candidate after the other, everything in scalar registers (all of it is wave-uniform)
+                const int lbb = __float_as_int(A_lb), djb = __float_as_int(dj);
+                if (fast && kRank) // the whole batch in one data-parallel step
+                    tie |= RankRun<TR>::replay(rh, top_k, mph, lbb, djb, A_slot, lane, count_skips, reinterpret_cast<int*>(heap_d), heap_s,
+                                               n_skip_u, n_ext, n_est, bag_dk, amb_min);
+                else {
+                    // One taken candidate after the other, everything in scalar registers (all of it is wave-uniform): topk.hpp's
+                    // replay_sorted and replay_heap as ONE loop on the runtime `fast`, left inline here.  The sorted run's decisions are
+                    // SortedRun::may_enter / ::offer, shared with k_scan.  (Tried: calls to replay_sorted / replay_heap, and one function
+                    // of this very text — by reference, by value, with local copies of the counters and of the heap, plain `inline`.
+                    // Every form moved scalar registers of the top_k >= 64 instantiations, which sit at the limit of 106, into VGPR
+                    // lanes (v_writelane 20 -> 38 at D = 768), and seven of the 27 of k_scanw.hip then had scratch (before: one), 12 to 188 bytes
+                    // per lane — which hands their calls to k_scan (k_scanw.hip).  This form keeps every instantiation's registers.)
                     uint32_t len_s = HeapOps::uni(rh.len);
                     int dk = fast ? SortedRun<TR>::kth(rh.hd, rh.xd, len_s, top_k) : 0;
                     unsigned long long todo = mph;
-                    if (fast && !count_skips && len_s == top_k) {
-                        // One data-parallel test in front of the serial loop: the threshold only falls inside the batch, so a candidate
-                        // whose lower bound or whose distance is not below the threshold at the START of the batch is skipped or
-                        // rejected by the reference as well (an EQUAL distance stays in: the serial loop must report the tie).
-                        const int kk0 = HeapOps::key(dk);
-                        const int db = __float_as_int(dj);
-                        const bool pass = ((mph >> lane) & 1ull) && A_lb < __int_as_float(dk) && (db & 0x7f800000) != 0x7f800000 && HeapOps::key(db) <= kk0;
-                        todo = __ballot(pass);
-                    }
+                    if (fast && !count_skips && len_s == top_k) todo = SortedRun<TR>::may_enter(mph, lbb, djb, dk, lane);
                     while (todo) {
                         const uint32_t j = (uint32_t)__builtin_ctzll(todo);
                         todo &= todo - 1ull;
-                        const float lb = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(A_lb), (int)j));
+                        const float lb = __int_as_float(__builtin_amdgcn_readlane(lbb, (int)j));
                         const float distk = fast ? __int_as_float(dk) : (rh.len < top_k ? INFINITY : __int_as_float(rh.d_at(0)));
                         if (!(lb < distk)) { ++n_skip_u; continue; }            // `lower_bound >= distk`: skipped
                         ++n_ext;
-                        const int dbits = __builtin_amdgcn_readlane(__float_as_int(dj), (int)j);
+                        const int dbits = __builtin_amdgcn_readlane(djb, (int)j);
                         if ((dbits & 0x7f800000) == 0x7f800000) continue;          // non-finite distance: dropped
                         ++n_est;
                         const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)A_slot, (int)j);
-                        if (fast) {
-                            const int ke = HeapOps::key(dbits);
-                            const bool was_full = len_s == top_k;
-                            const int kk2 = HeapOps::key(dk);
-                            if (was_full) {
-                                if (ke > kk2) continue;                             // pushed and popped again: no change
-                                if (ke == kk2) { amb_min = amb_min < kk2 ? amb_min : kk2; continue; } // turned away with the maximum's key (lazy tie)
-                            }
-                            (void)SortedRun<TR>::insert(rh.hd, rh.hs, rh.xd, rh.xs, len_s, dbits, slot, lane); // (equal keys: side by side)
-                            len_s = len_s < top_k ? len_s + 1u : len_s; // a full run drops its (new) entry top_k
-                            dk = SortedRun<TR>::kth(rh.hd, rh.xd, len_s, top_k);
-                            if (was_full && HeapOps::key(dk) == kk2) amb_min = amb_min < kk2 ? amb_min : kk2; // the old maximum left, its twin stays
-                        } else {
+                        if (fast) SortedRun<TR>::offer(rh, len_s, dk, top_k, dbits, slot, lane, amb_min);
+                        else {
                             rh.push(dbits, slot);
                             if (rh.len > top_k) rh.pop();
                         }
@@ -512,24 +476,19 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
                     // The wait for the first round's codes goes HERE, at the end of the branch that requested the records (the empty
                     // asm reads them): here the compiler knows how many loads were issued behind the codes and leaves the records in
                     // flight; behind the join of the two branches it has to assume none and would wait for the records as well.
-                    if (kPre && ex_bits && !RBQ_W_PREF_FIRST) {
+                    if (kPre && ex_bits) {
 #pragma unroll
                         for (int j = 0; j < (int)(kPre ? kNU : 1u); ++j) asm volatile("" :: "v"(ea[j].x), "v"(ea[j].y), "v"(ea[j].z), "v"(ea[j].w));
                         asm volatile("" :: "v"(fa0), "v"(fr0));
                     }
                 }
             };
-#if RBQ_W_PREF_FIRST
-            prefetch();
-#endif
             collect(G);
             if (ncol && ex_bits) request(kDual);
-#if !RBQ_W_PREF_FIRST
             // BEHIND the first round's own loads: vector-memory results come back in issue order, so a round whose loads were issued
             // after this prefetch would wait for the (cold) records as well; this way the dot product waits for its codes only, and
             // the records arrive while it and the replay run.
             prefetch();
-#endif
             while (ncol) {
                 finish(kDual);
                 if (fast && tie) break;
@@ -539,12 +498,6 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
         } else {
             // top_k >= 64: the loop as it was (the records requested inside it, in its first trip)
             bool first = true;
-#if RBQ_W_PREF_FIRST
-            first = false;
-            fill_until();
-            n_next = qcount < 2u ? qcount : 2u;
-            if (n_next) issue_tile(nxt, qhead, n_next);
-#endif
             collect(G);
             do {
                 if (ncol && ex_bits) request(kDual);
@@ -569,26 +522,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
         cur = nxt;
         n = n_next;
     }
-    if (fast && !tie) { // the final look of the lazy-tie rule
-        const uint32_t lenf = HeapOps::uni(rh.len);
-        bool eq = false;
-        int maxkey = (int)0x80000000;
-#pragma unroll
-        for (int r = 0; r < TR; ++r) {
-            const uint32_t i = (uint32_t)r * 64u + lane;
-            const int b = r == 0 ? rh.hd : rh.xd[r];
-            const int kv = kRank ? b : HeapOps::key(b);
-            int below = __builtin_amdgcn_update_dpp((int)0x80000000, kv, 0x138, 0xf, 0xf, false); // wave_shr:1
-            if (r > 0) {
-                const int pb = r == 1 ? rh.hd : rh.xd[r - 1];
-                const int carry = __builtin_amdgcn_readlane(kRank ? pb : HeapOps::key(pb), 63);
-                below = lane == 0 ? carry : below;
-            }
-            eq |= i >= 1u && i < lenf && kv == below;
-            if (lenf && (lenf - 1u) >> 6 == (uint32_t)r) maxkey = __builtin_amdgcn_readlane(kv, (int)((lenf - 1u) & 63u));
-        }
-        tie = __ballot(eq) != 0ull || (lenf == top_k && maxkey == amb_min);
-    }
+    if (fast && !tie) tie = lazy_tie_final(rh, kRank, top_k, amb_min, lane);
     if (!(fast && tie)) break;
     if (lane == 0 && P.heap_restarts) atomicAdd(P.heap_restarts, 1u);
     fast = false;
@@ -602,17 +536,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
     // ---- results ----------------------------------------------------------------------------------------------------
     uint32_t len = HeapOps::uni(rh.len);
     if (!fast) { // the exact heap: spill to LDS, into_sorted_vec by one lane
-#pragma unroll
-        for (int r = 0; r < TR; ++r)
-            if ((uint32_t)r * 64u + lane < len) {
-                heap_d[r * 64 + lane] = __int_as_float(r == 0 ? rh.hd : rh.xd[r]);
-                heap_s[r * 64 + lane] = r == 0 ? rh.hs : rh.xs[r];
-            }
-        wave_lds_sync();
-        if (lane == 0) {
-            LdsHeap lh{heap_d, heap_s, len};
-            lh.into_sorted();
-        }
+        spill_heap_sorted(rh, true, len, heap_d, heap_s, lane, wave_lds_sync);
         wave_lds_sync();
     }
 #pragma unroll
@@ -625,8 +549,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
                 float dv;
                 uint32_t sl;
                 if (fast) {
-                    const int b = r == 0 ? rh.hd : rh.xd[r];
-                    dv = __int_as_float(!kRank ? b : HeapOps::key(b));
+                    dv = __int_as_float(run_distance_bits(rh, r, kRank));
                     sl = r == 0 ? rh.hs : rh.xs[r];
                 } else { dv = heap_d[i]; sl = heap_s[i]; }
                 id = P.ids[sl];

@@ -36,7 +36,7 @@ constexpr uint32_t kHxMaxVec = 256;  // one thread per vector
 __host__ __device__ inline size_t hx_scratch_bytes(uint32_t D, uint32_t Dc, uint32_t ex_bits, uint32_t nv) {
     return (size_t)Dc * 4 + (ex_bits ? (size_t)ex_qlen(D, ex_bits) * 4 : 0) + (size_t)nv * 16 + 16;
 }
-__device__ __forceinline__ uint32_t hx_look8(uint32_t x, const uint8_t* p) { // scan.hpp look8 on a plain LDS pointer
+__device__ __forceinline__ uint32_t hx_look8(uint32_t x, const uint8_t* p) { // scan_codes.hpp look8 on a plain LDS pointer
     uint32_t s = p[x & 15u];
     s += p[16 + ((x >> 4) & 15u)];
     s += p[32 + ((x >> 8) & 15u)];

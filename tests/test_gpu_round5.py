@@ -69,8 +69,14 @@ def test_wave_kernel_matches_oracle_and_workgroup_kernel(n, dim, nlist, bits, me
     idx.close()
 
 
-@pytest.mark.parametrize("top_k", [1, 2, 9, 10, 31, 62, 63, 64, 65, 100, 127, 128, 129, 200, 255, 256, 300])
-def test_wave_kernel_at_every_top_k_register_class(top_k):
+# the `exact_heap` rows start both kernels on the BinaryHeap emulation in registers (topk.hpp: k_scan's replay_heap, the heap side of
+# k_scanw's loop), which a query otherwise reaches only after a tie — in k_scan not at all while the tie log serves the restart
+TOP_K_CLASSES = [pytest.param(k, 0, id=str(k)) for k in (1, 2, 9, 10, 31, 62, 63, 64, 65, 100, 127, 128, 129, 200, 255, 256, 300)] + \
+                [pytest.param(k, 1, id="%d-exact_heap" % k) for k in (63, 64, 128)]
+
+
+@pytest.mark.parametrize("top_k,exact_heap", TOP_K_CLASSES)
+def test_wave_kernel_at_every_top_k_register_class(top_k, exact_heap):
     """k_scanw keeps the top-k in 1 / 2 / 4 registers per lane (top_k <= 63 / 127 / 255); beyond that (and for instantiations
     that would spill registers) the library runs k_scan: every class against the oracle, ties included."""
     base = make_dataset(2500, 128, 8, 61)
@@ -78,6 +84,7 @@ def test_wave_kernel_at_every_top_k_register_class(top_k):
     _, built = build_index(nlist=20, total_bits=7, data=data, dim=128)
     idx = rq.IvfRabitqIndex.from_built(built)
     q = np.ascontiguousarray(np.concatenate([base[:24], make_dataset(24, 128, 8, 62)]))
+    idx.set_option("exact_heap", exact_heap)
     _both_kernels(built, idx, q, top_k, 10)
     idx.close()
 
