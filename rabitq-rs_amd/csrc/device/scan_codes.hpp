@@ -80,6 +80,13 @@ __device__ __forceinline__ uint32_t lookup_codes(CodeRegs<DT>& c, const uint8_t*
     return acc;
 }
 
+// Measured and not kept (k_scanw below top_k 64; records: profiles/lds_pipeline): this sum software-pipelined over the code dwords.  look8's
+// pin makes the wave drain the LDS queue once per dword (8 ds_read_u8, `s_waitcnt lgkmcnt(6) (4) (2) (0)` between the adds, the next
+// dword's reads behind that lgkmcnt(0)): 29 full drains per tile at D = 960.  With the reads of stage t + 1 issued before the sums of
+// stage t (the pin kept, on the accumulator alone) the ISA had no drain left and only counted waits — and a wave alone on its SIMD took
+// LONGER per tile: 5010 cycles with stages of half a dword, 4934 with whole dwords, against 4573; queries/s did not differ.  The eight
+// reads of a dword already overlap each other; what the drain exposes is less than what the staging adds.
+
 // generic (runtime Dc) path: no register prefetch
 __device__ __forceinline__ uint32_t accumulate_block_rt(const uint8_t* __restrict__ blk, lds_lut_ptr lut,
                                                         uint32_t l32, uint32_t Dc) {
@@ -225,11 +232,48 @@ __device__ __forceinline__ void ex_dot_pair_regs(const uint4* a, const uint4* b,
     }
     s0 = acc.x; s1 = acc.y;
 }
-template <int EX, int NU, int NCODES>
+// AHEAD > 0 (k_scanw below top_k 64): in the plain form (AHEAD = 0, below) the pin's "memory" clobber keeps the query reads of a stretch
+// behind the previous stretch's FMAs, and the wave drains the LDS queue about every second FMA (one or two ds_read2_b32 in flight, then
+// `s_waitcnt lgkmcnt(0)`): 27 drains per candidate at D = 960.  Here code c of the vector reads sq[gl + 16 c] (the units are
+// contiguous in c), the codes are cut into stretches of kPairPin in index order across the unit boundaries, and the query values of
+// stretch s + AHEAD are requested between the pins that end stretches s - 1 and s: a read in front of a "memory" clobber stays there.
+// With AHEAD = 2 a whole stretch of reads is outstanding behind the ones an FMA waits for, wherever the scheduler puts the requests
+// between two pins; with AHEAD = 1 (four registers less) it put them behind the stretch's second FMA: half a stretch.  The values are
+// not operands of the pin (an asm operand is a use).  The FMA chain is the same: one fmaf per code, codes in index order.
+template <int EX, int NU, int NCODES, int AHEAD = 0>
 __device__ __forceinline__ float ex_dot_one_regs(const uint4* a, const float* sq, uint32_t gl) {
     constexpr int CPU = 128 / EX;
     constexpr uint32_t mask = (1u << EX) - 1u;
     float acc = 0.0f;
+    if constexpr (AHEAD > 0) {
+        constexpr int NS = (NCODES + kPairPin - 1) / kPairPin;
+        const float* qb = sq + gl;
+        float qv[AHEAD + 1][kPairPin];
+#pragma unroll
+        for (int t = 0; t < AHEAD * kPairPin; ++t) qv[t / kPairPin][t % kPairPin] = t < NCODES ? qb[16 * t] : 0.0f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+#pragma unroll
+            for (int t = 0; t < kPairPin; ++t) {
+                const int c = (s + AHEAD) * kPairPin + t;
+                if (c < NCODES) qv[(s + AHEAD) % (AHEAD + 1)][t] = qb[16 * c];
+            }
+#pragma unroll
+            for (int t = 0; t < kPairPin; ++t) {
+                const int c = s * kPairPin + t;
+                if (c < NCODES) {
+                    const int j = c / CPU, bit = (c % CPU) * EX, idx = bit >> 5, sh = bit & 31;
+                    const uint32_t w0[5] = {a[j].x, a[j].y, a[j].z, a[j].w, 0u};
+                    uint32_t c0;
+                    if (sh + EX <= 32) c0 = (w0[idx] >> sh) & mask;
+                    else c0 = ((w0[idx] >> sh) | (w0[idx + 1] << (32 - sh))) & mask;
+                    acc = fmaf((float)c0, qv[s % (AHEAD + 1)][t], acc);
+                }
+            }
+            asm volatile("" : "+v"(acc) :: "memory");
+        }
+        return acc;
+    }
 #pragma unroll
     for (int j = 0; j < NU; ++j) {
         const uint32_t w0[5] = {a[j].x, a[j].y, a[j].z, a[j].w, 0u};

@@ -29,6 +29,12 @@
 // keeps four.  Exactness is k_scan's: the tile prunes with the threshold of its start (T only shrinks: `lb >= T_then` implies
 // the reference skipped the candidate too), everything else is replayed in stream order against the running threshold.
 // Equal distances: the LAZY-TIE rule (below, at `amb_min`).
+// The ex dot product's "memory"-clobber pin kept a stretch's query reads behind the previous stretch's FMAs: a full `s_waitcnt lgkmcnt(0)`
+// about every second FMA.  Below top_k 64 it is software-pipelined in the source (scan_codes.hpp: ex_dot_one_regs<.., AHEAD>): the query
+// values are requested one or two stretches ahead, the waits in between are counted, no value in flight is an operand of a pin, and no
+// wait is hand-placed.  The price is registers (`kStageDot` below says where which depth applies): every instantiation keeps its waves per
+// SIMD, and the TR > 1 ones, which sit at 128 registers, keep the plain dot product.  The same staging of the LUT lookups removed their
+// drains too and made the tile phase slower (scan_codes.hpp, above accumulate_block_rt): the lookups are k_scan's.
 #pragma once
 #include "kernels.hpp"
 #include "scan_codes.hpp"
@@ -40,7 +46,7 @@ namespace rbq {
 #define RBQ_SCANW_WAVES 4     // launch-bounds occupancy target (waves per SIMD) of the RankRun instantiations (top_k >= 64): 128 VGPRs
 #endif
 #ifndef RBQ_SCANW_WAVES1
-#define RBQ_SCANW_WAVES1 5    // ... of the top_k < 64 instantiations: 96 VGPRs (they need 80 at D = 960), and 8 KB of LDS per query at D = 960
+#define RBQ_SCANW_WAVES1 5    // ... of the top_k < 64 instantiations: 96 VGPRs (they need 88 at D = 960), and 8 KB of LDS per query at D = 960
 #endif
 // Measured and not kept: the next tile's records requested BEFORE the first refine round's codes (they come back in issue order: the
 // round then waits for the cold records too); RankRun below top_k 64 (no gain over the sorted run); two candidates per 16-lane group
@@ -210,6 +216,18 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
     // the ex-code units of a round are requested into registers and decoded later (compile-time dimensions up to 4 units per
     // lane: D <= 1344 at 6 bits); otherwise they are loaded where they are decoded
     constexpr bool kPre = DT != 0 && EX != 0 && kNU <= 4u;
+    // stretches of query values requested ahead of the dot product's FMAs (scan_codes.hpp: ex_dot_one_regs).  Two at D = 960, where the
+    // 8 KB of LDS per query bound the kernel at five waves per SIMD and 96 registers are free to use (88 used); one at the other
+    // dimensions (two cost <768, 6, 1> its sixth wave: 85 registers); none from top_k 64, where the same cost <960, 6, 4> and
+    // <1024, 6, 4> 40 and 68 bytes of scratch (the launcher's limit is 16).
+    // <384, 6, 1>, <512, 6, 1> and <1024, 2, 1> sit at the top of a register class (72, 72, 69 of 72) and lose a wave per SIMD to the
+    // four registers of one stretch: they keep the unstaged form.  The list holds for the compiler it was read from (the register counts
+    // of `tools/kernel_resources.sh k_scanw` and `k_scanw2`, recorded in profiles/lds_pipeline/kernel_resources.txt): after a compiler
+    // update, or a change to this kernel, run both again and compare with that record — a TR == 1 row whose occupancy column fell (other
+    // than the two D = 960 rows that the LDS bounds at five waves anyway) belongs here, a row here that has four registers to spare does
+    // not; a row with more than 16 bytes of scratch is handed to k_scan by the launcher and has to come back under it.
+    constexpr bool kDotAtLimit = ((DT == 384 || DT == 512) && EX == 6) || (DT == 1024 && EX == 2);
+    constexpr int kStageDot = (TR != 1 || kDotAtLimit) ? 0 : DT == 960 ? 2 : 1;
 
 #ifdef RBQ_WSTAMPS
     unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_fill = 0, st_tile = 0, st_rounds = 0, st_a;
@@ -403,7 +421,7 @@ __global__ __launch_bounds__(64, (TR == 1 ? RBQ_SCANW_WAVES1 : RBQ_SCANW_WAVES))
                 if (ex_bits && has0) { // (group-uniform)
                     float sa = 0.0f;
                     if constexpr (V != kVarAvx512) sa = ex_dot_var_rt<V>(P.ex_codes + (size_t)sl0 * exb, s_q, gl, nunits, D / 16, ex_bits);
-                    else if (kPre) sa = ex_dot_one_regs<(EX ? EX : 2), (int)(kPre ? kNU : 1u), (DT ? DT / 16 : 1)>(ea, s_q, gl);
+                    else if (kPre) sa = ex_dot_one_regs<(EX ? EX : 2), (int)(kPre ? kNU : 1u), (DT ? DT / 16 : 1), kStageDot>(ea, s_q, gl);
                     else {
                         const uint8_t* ex = P.ex_codes + (size_t)sl0 * exb;
                         if (nunits <= (uint32_t)kExRegUnits) {
