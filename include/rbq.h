@@ -263,6 +263,21 @@ void rbq_host_free(void* p);
  * bounds on top_k (2^20, 8 GiB of heap workspace) are then evaluated for v, and top_k itself may exceed 1024.  With
  * v <= top_k nothing changes, the refusal of top_k > 1024 with the rerank on included. */
 int rbq_index_set_rerank_vectors(rbq_index* idx, const float* vectors, uint64_t n);
+/* Rows in 16 bits.  No entry point is added for them: the option "rerank_raw_dtype" (rbq_debug_set_option, every replica; the
+ * default is RBQ_RAW_F32) says what the pointer of the NEXT rbq_index_set_rerank_vectors holds — rows of `dim` elements of that
+ * type, dim * sizeof(element) bytes apart, passed through the `const float*` parameter as they are.  Any other value is
+ * RBQ_INVALID_CONFIG (detail set) and the handle keeps what it had; rows already attached keep the type they were attached with.
+ * rbq_debug_copy_index(idx, "rerank_raw_dtype", &v, 4) reads the RBQ_RAW_* of the attached rows as one int32, -1 with none.
+ * A 16-bit element is widened to f32 EXACTLY where a kernel loads it (f16 subnormals, signed zeros, infinities and quiet
+ * NaNs included; bf16 is bits << 16) and enters the same canonical sums, multiply and add unfused: a search over 16-bit rows X16
+ * returns, bit for bit (ids, counts, score bits), what it returns with widen(X16) attached as f32, pooled or not, on every
+ * search entry.  A signalling NaN scores some NaN.  The library never rounds: rounding f32 data to 16 bits is the caller's choice
+ * and the caller's recall.  A borrowed device pointer to 16-bit rows must be 2-byte aligned (else RBQ_INVALID_CONFIG); rows that
+ * all start 4-byte aligned (base 4-byte aligned and dim even) are read 16 bytes per lane, any others element by element, with the
+ * same results, slower.  Nothing outside [vectors, vectors + n * dim * sizeof(element)) is read. */
+#define RBQ_RAW_F32  0
+#define RBQ_RAW_F16  1   /* IEEE binary16 */
+#define RBQ_RAW_BF16 2   /* upper 16 bits of an f32 */
 
 /* Numeric variant: which build of the reference the kernels reproduce bit for bit.  The reference picks its arithmetic at
  * compile time (cfg(target_feature) in src/simd.rs), so two builds of it return different last bits of the scores:

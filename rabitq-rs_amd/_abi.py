@@ -15,6 +15,9 @@ NUMERIC_VARIANTS = {"native_avx512": NUMERIC_NATIVE_AVX512, "native_avx2": NUMER
 # rescale modes of the device encoder (RBQ_RESCALE_*): RabitqConfig::faster / RabitqConfig::new
 RESCALE_CONST, RESCALE_OPTIMAL = 0, 1
 RESCALE_MODES = {"const": RESCALE_CONST, "optimal": RESCALE_OPTIMAL}
+# element types of the rerank's raw rows (RBQ_RAW_*): the values of the option "rerank_raw_dtype"
+RAW_F32, RAW_F16, RAW_BF16 = 0, 1, 2
+RAW_DTYPES = {"f32": RAW_F32, "f16": RAW_F16, "bf16": RAW_BF16}
 BATCH = 32
 # rbq_kmeans_device (include/rbq_kmeans.h): the config fields in ABI order and the stats slots
 KMEANS_CONFIG_FIELDS = ("niter", "nredo", "seed", "spherical", "max_points_per_centroid", "decode_block_size")

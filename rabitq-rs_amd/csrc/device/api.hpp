@@ -362,6 +362,7 @@ struct Options {
     uint64_t fetch_chunk = 0; // TEST ONLY: ids per staging chunk of rbq_index_fetch_embeddings (0 = default)
     uint64_t mstg_chunk = 0;  // TEST ONLY: staging chunk of rbq_mstg_save* in bytes, any value >= 1 (0 = default)
     uint64_t mstg_search_budget = 0; // TEST ONLY: per-chunk workspace of rbq_mstg_search_batch* in bytes (0 = default)
+    int rerank_raw_dtype = 0; // RBQ_RAW_*: the element type the next rbq_index_set_rerank_vectors reads its pointer as (0: f32)
     uint32_t rerank_pool = 0; // while rerank is on and rerank_pool > top_k: the search runs at top_k := rerank_pool, the pool is scored
                               // exactly against the attached vectors and the best top_k are returned (0 = off; <= kRerankPoolMax)
     // option `name` := value (the options of rbq_debug_set_option that live in Options); RBQ_INVALID_CONFIG for an unknown name
@@ -406,6 +407,7 @@ struct Replica : Geometry {
     float cnorm_max = 0.0f, rc_max = 0.0f;
     bool rank_f16_ok = false;
     uint64_t n_raw = 0;      // raw vectors attached for the optional rerank
+    int raw_dtype = 0;       // RBQ_RAW_* of the attached rows (kRawF32 while nothing is attached)
     bool raw_borrowed = false;
     bool rerank = false;
     Options opt;

@@ -193,6 +193,11 @@ int Options::set(const char* name, int v) {
         if (v > (int)kRerankPoolMax) return fail(RBQ_INVALID_CONFIG, "rerank_pool " + std::to_string(v) + " exceeds the limit of " + std::to_string(kRerankPoolMax));
         rerank_pool = v > 0 ? (uint32_t)v : 0u;
     }
+    else if (is("rerank_raw_dtype")) { // what the pointer of the next rbq_index_set_rerank_vectors holds (attached rows keep their own)
+        if (v != RBQ_RAW_F32 && v != RBQ_RAW_F16 && v != RBQ_RAW_BF16)
+            return fail(RBQ_INVALID_CONFIG, "rerank vectors: unknown dtype " + std::to_string(v) + " (RBQ_RAW_F32, RBQ_RAW_F16 or RBQ_RAW_BF16)");
+        rerank_raw_dtype = v;
+    }
     else return fail(RBQ_INVALID_CONFIG, std::string("unknown option ") + name);
     return RBQ_OK;
 }
@@ -542,10 +547,15 @@ int rbq_index_create_with_recon(const rbq_header* hdr, const rbq_list_view* list
 
 
 // ---- optional full-precision rerank (NOT in the reference: its index stores no raw vectors, src/ivf.rs:207-242) ----
-int rbq_index_set_rerank_vectors(rbq_index* h, const float* vectors, uint64_t n) {
+// The rows are dim elements of the handle's option "rerank_raw_dtype" (RBQ_RAW_*, f32 unless set; Options::set admits no other
+// value): a 16-bit element is widened exactly where a kernel loads it, nothing is converted here.
+int rbq_index_set_rerank_vectors(rbq_index* h, const float* vectors_f32, uint64_t n) {
     g_err.clear();
     RBQ_GUARD_BEGIN
     if (!h || h->reps.empty()) return fail(RBQ_INVALID_CONFIG, "null index");
+    const void* vectors = vectors_f32;
+    const int dtype = h->reps[0]->opt.rerank_raw_dtype;
+    const size_t esize = raw_elem_bytes(dtype);
     // all replicas or none: the new copies are made first; only when every one of them exists are the old ones released
     // and the new ones attached (a failure half-way leaves every replica exactly as it was)
     const size_t R = h->reps.size();
@@ -556,14 +566,16 @@ int rbq_index_set_rerank_vectors(rbq_index* h, const float* vectors, uint64_t n)
         hipPointerAttribute_t a;
         const bool on_dev = hipPointerGetAttributes(&a, vectors) == hipSuccess && a.type == hipMemoryTypeDevice;
         if (!on_dev) (void)hipGetLastError();
+        if (on_dev && esize == 2 && (reinterpret_cast<uintptr_t>(vectors) & 1u))
+            return fail(RBQ_INVALID_CONFIG, "rerank vectors: a device pointer to 16-bit rows must be 2-byte aligned");
         int rc = RBQ_OK;
         for (size_t r = 0; r < R && rc == RBQ_OK; ++r) {
             Replica* ix = h->reps[r];
             DeviceGuard g(ix->device);
             if (!g.ok) { rc = fail(RBQ_DEVICE, "hipSetDevice failed"); break; }
-            const size_t bytes = (size_t)n * ix->dim * 4;
+            const size_t bytes = (size_t)n * ix->dim * esize;
             if (on_dev && a.device == ix->device) { // borrowed: stays owned by the caller, must outlive the index
-                fresh[r].p = const_cast<float*>(vectors); fresh[r].bytes = bytes; borrowed[r] = 1;
+                fresh[r].p = const_cast<void*>(vectors); fresh[r].bytes = bytes; borrowed[r] = 1;
                 continue;
             }
             rc = alloc_arr(fresh[r], bytes);
@@ -586,9 +598,9 @@ int rbq_index_set_rerank_vectors(rbq_index* h, const float* vectors, uint64_t n)
         if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
         HIP_TRY(hipDeviceSynchronize());
         if (ix->raw.p && !ix->raw_borrowed) (void)hipFree(ix->raw.p);
-        ix->raw = Arr(); ix->n_raw = 0; ix->rerank = false; ix->raw_borrowed = false;
+        ix->raw = Arr(); ix->n_raw = 0; ix->rerank = false; ix->raw_borrowed = false; ix->raw_dtype = RBQ_RAW_F32;
         if (!attach) continue; // detach
-        ix->raw = fresh[r]; ix->raw_borrowed = borrowed[r] != 0;
+        ix->raw = fresh[r]; ix->raw_borrowed = borrowed[r] != 0; ix->raw_dtype = dtype;
         ix->n_raw = n; ix->rerank = true;
     }
     return RBQ_OK;
@@ -788,6 +800,12 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
     const size_t stride = (size_t)ix->Dc * 4 + 384, exd = ex_bytes_dev(ix->D, ix->ex_bits), slots = ix->n_blocks * 32;
     const void* p = nullptr;
     size_t have = 0;
+    if (!std::strcmp(name, "rerank_raw_dtype")) { // (not an array: RBQ_RAW_* of the attached rerank rows as one int32, -1 with none attached)
+        if (bytes != 4) return fail(RBQ_INVALID_CONFIG, "rerank_raw_dtype is one int32");
+        const int32_t v = h->reps[0]->raw.p ? h->reps[0]->raw_dtype : -1;
+        std::memcpy(dst, &v, 4);
+        return RBQ_OK;
+    }
     if (!std::strcmp(name, "blocks")) { p = ix->blocks.p; have = ix->n_blocks * stride; }
     else if (!std::strcmp(name, "ids")) { p = ix->ids.p; have = slots * 8; }
     else if (!std::strcmp(name, "ex")) { p = ix->ex.p; have = slots * exd; }

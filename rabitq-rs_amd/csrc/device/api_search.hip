@@ -300,7 +300,7 @@ int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, 
                          /*mstg=*/false, (ix->opt.exact_rank || big_nprobe) ? nullptr : (const uint32_t*)w->dead_skipped.p, stream)))
         return rc;
     if (rerank && !stage_probes()) // optional, default off: exact re-scoring of the returned ids against the attached raw vectors
-        HIP_TRY(launch_rerank(d_queries, (uint32_t)nq, ix->dim, (const float*)ix->raw.p, ix->n_raw, ix->metric, top_k, d_ids, d_scores,
+        HIP_TRY(launch_rerank(d_queries, (uint32_t)nq, ix->dim, ix->raw.p, ix->raw_dtype, ix->n_raw, ix->metric, top_k, d_ids, d_scores,
                               d_counts, stream));
     return RBQ_OK;
 }
@@ -323,7 +323,7 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
         return rc;
     if (stage_probes()) return RBQ_OK; // (the four stages of the inner call are what a probe reports)
     RerankPoolParams P;
-    P.queries = d_queries; P.raw = (const float*)ix->raw.p; P.n_raw = ix->n_raw; P.nq = (uint32_t)nq; P.dim = ix->dim; P.metric = ix->metric;
+    P.queries = d_queries; P.raw = ix->raw.p; P.raw_dtype = ix->raw_dtype; P.n_raw = ix->n_raw; P.nq = (uint32_t)nq; P.dim = ix->dim; P.metric = ix->metric;
     P.pool = pool; P.top_k = top_k; P.pool_ids = (const uint64_t*)w->rr_ids.p; P.pool_counts = (const uint32_t*)w->rr_counts.p;
     P.out_ids = d_ids; P.out_scores = d_scores; P.out_counts = d_counts;
     HIP_TRY(launch_rerank_pool(P, ix->device, stream));

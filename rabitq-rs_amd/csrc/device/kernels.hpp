@@ -403,14 +403,22 @@ __device__ __forceinline__ void rotate_into_lds(float* x, float* y, const float*
 
 }
 
-// canonical single-pair reductions used for the second per-probe quantity
-__device__ inline float canon_l2(const float* a, const float* __restrict__ b, uint32_t D) {
+// Elements of a row of raw vectors as the rerank stores them (RBQ_RAW_*): f32, or 16 bits that widen to an f32 exactly.
+struct RawF16 { uint16_t bits; };  // IEEE binary16
+struct RawBf16 { uint16_t bits; }; // the upper 16 bits of an f32
+__device__ __forceinline__ float raw_widen(float x) { return x; }
+__device__ __forceinline__ float raw_widen(RawF16 x) { return (float)__builtin_bit_cast(_Float16, x.bits); }
+__device__ __forceinline__ float raw_widen(RawBf16 x) { return __uint_as_float((uint32_t)x.bits << 16); }
+
+// canonical single-pair reductions used for the second per-probe quantity (b: a row of f32, or of 16-bit elements widened on load)
+template <typename T>
+__device__ inline float canon_l2(const float* a, const T* __restrict__ b, uint32_t D) {
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const uint32_t Dmain = D & ~7u;
     for (uint32_t i = 0; i < Dmain; i += 8)
 #pragma unroll
         for (int l = 0; l < 8; ++l) {
-            float d = a[i + l] - b[i + l];
+            float d = a[i + l] - raw_widen(b[i + l]);
             float p = d * d;
             acc[l] = acc[l] + p;
         }
@@ -421,19 +429,20 @@ __device__ inline float canon_l2(const float* a, const float* __restrict__ b, ui
         for (int l = 0; l < 8; ++l) sum = sum + acc[l];
     }
     for (uint32_t i = Dmain; i < D; ++i) {
-        float d = a[i] - b[i];
+        float d = a[i] - raw_widen(b[i]);
         float p = d * d;
         sum = sum + p;
     }
     return sum;
 }
-__device__ inline float canon_dot(const float* a, const float* __restrict__ b, uint32_t D) {
+template <typename T>
+__device__ inline float canon_dot(const float* a, const T* __restrict__ b, uint32_t D) {
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const uint32_t Dmain = D & ~7u;
     for (uint32_t i = 0; i < Dmain; i += 8)
 #pragma unroll
         for (int l = 0; l < 8; ++l) {
-            float p = a[i + l] * b[i + l];
+            float p = a[i + l] * raw_widen(b[i + l]);
             acc[l] = acc[l] + p;
         }
     float sum = 0.0f;
@@ -443,7 +452,7 @@ __device__ inline float canon_dot(const float* a, const float* __restrict__ b, u
         for (int l = 0; l < 8; ++l) sum = sum + acc[l];
     }
     for (uint32_t i = Dmain; i < D; ++i) {
-        float p = a[i] * b[i];
+        float p = a[i] * raw_widen(b[i]);
         sum = sum + p;
     }
     return sum;

@@ -176,7 +176,9 @@ __global__ void k_chunk_advance(const uint32_t* __restrict__ sorted_list, uint32
 // One workgroup per query: exact squared distance / dot of the query (input space) with the raw vector of every
 // returned id in the canonical 8-accumulator order of math::l2_distance_sqr / dot (src/math.rs:154-245), then the
 // top_k (<= 1024 here) results re-sorted by (exact score, position) — ascending distance for L2, descending for IP.
-__global__ __launch_bounds__(kThreads) void k_rerank(const float* __restrict__ queries, uint32_t dim, const float* __restrict__ raw,
+// T: the element of a raw row (float, RawF16, RawBf16: kernels.hpp); a 16-bit element is widened exactly as it is loaded.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_rerank(const float* __restrict__ queries, uint32_t dim, const T* __restrict__ raw,
                                                      uint64_t n_raw, int metric, uint32_t top_k, uint64_t* __restrict__ ids,
                                                      float* __restrict__ scores, const uint32_t* __restrict__ counts) {
     extern __shared__ __align__(16) unsigned char smraw[];

@@ -517,19 +517,47 @@ class IvfRabitqIndex:
     def release_stream(self, stream):
         _check(lib().rbq_release_stream(self._h, C.c_void_p(stream)))
 
-    def set_rerank_vectors(self, vectors=None, device_ptr=None, n=0, pool=None):
+    def set_rerank_vectors(self, vectors=None, device_ptr=None, n=0, pool=None, dtype=None):
         """OPTIONAL extension (default off, not reference behaviour): attach raw vectors for the exact rerank.
         `vectors` = host array [n][dim], or `device_ptr` + n; None detaches.  `pool` (not None): set_rerank_pool(pool)
-        once the vectors are attached."""
+        once the vectors are attached.
+        `dtype`: the element type the rows are kept in, "f32", "f16" or "bf16" (or RBQ_RAW_*).  16-bit rows take half the bytes
+        and are widened exactly where they are scored: the results are those of the widened rows attached as f32.
+        None: a numpy.float16 array attaches as f16, anything else as f32 (as before).  With `device_ptr` it says what the
+        pointer holds.  "f16" with a host array of another type converts with astype(numpy.float16) (round to nearest even: the
+        caller's choice, and the caller's recall); "bf16" with a host array takes a uint16 array of bit patterns (NumPy has no
+        bf16; the library never rounds)."""
+        from . import RabitqError
+        if dtype is None:
+            code = _abi.RAW_F16 if (device_ptr is None and isinstance(vectors, np.ndarray) and vectors.dtype == np.float16) else _abi.RAW_F32
+        elif isinstance(dtype, str):
+            if dtype not in _abi.RAW_DTYPES:
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "unknown rerank dtype %r (one of %s)" % (dtype, ", ".join(_abi.RAW_DTYPES)))
+            code = _abi.RAW_DTYPES[dtype]
+        else:
+            code = int(dtype)
+        if device_ptr is not None or vectors is not None:  # what the next attach reads its pointer as (option "rerank_raw_dtype")
+            self.set_option("rerank_raw_dtype", code)
         if device_ptr is not None:
             _check(lib().rbq_index_set_rerank_vectors(self._h, C.c_void_p(device_ptr), int(n)))
         elif vectors is None:
             _check(lib().rbq_index_set_rerank_vectors(self._h, None, 0))
         else:
-            v = np.ascontiguousarray(vectors, dtype=np.float32)
+            if code == _abi.RAW_BF16:
+                if not (isinstance(vectors, np.ndarray) and vectors.dtype == np.uint16):
+                    raise RabitqError(_abi.RBQ_INVALID_CONFIG, "bf16 rows on the host are a uint16 array of bit patterns")
+                v = np.ascontiguousarray(vectors)
+            else:
+                v = np.ascontiguousarray(vectors, dtype=np.float16 if code == _abi.RAW_F16 else np.float32)
             _check(lib().rbq_index_set_rerank_vectors(self._h, v.ctypes.data, v.shape[0]))
         if pool is not None:
             self.set_rerank_pool(pool)
+
+    def rerank_dtype(self):
+        """"f32" / "f16" / "bf16": the element type of the attached rerank vectors; None with nothing attached."""
+        v = np.full(1, -1, np.int32)
+        _check(lib().rbq_debug_copy_index(self._h, b"rerank_raw_dtype", v.ctypes.data, 4))
+        return {i: n for n, i in _abi.RAW_DTYPES.items()}.get(int(v[0]))
 
     def set_rerank_pool(self, n):
         """Candidates the rerank re-scores per query (option "rerank_pool", at most RERANK_POOL_MAX): while raw vectors are

@@ -13,7 +13,11 @@ The yardstick for a pool p <= 1024 is what the library could do before the optio
 rerank on (k_rerank over p ids), of which the caller keeps the first 10 — the `sliced` legs, timed in the same rounds.
 --traced runs every leg a fixed number of times with no timing (for a kernel trace of its own); --kernel-table reads that trace:
 the two rerank kernels' dispatches are assigned to their legs by their order (the legs run one after the other, each a fixed
-number of calls), and each is reported as requested bytes (sum of counts x dim x 4) over kernel time."""
+number of calls), and each is reported as requested bytes (sum of counts x dim x element size) over kernel time.
+--raw-dtype f32 f16 bf16 (any of them): the element type the attached rows are kept in.  For f16 / bf16 the
+benchmark's rows are rounded once on the device (round to nearest even) and that copy is borrowed; recall stays against the float64
+exact top 10 of the UNROUNDED rows.  With several types every round visits every leg of every type in turn (names of legs other
+than f32's end in _f16 / _bf16), so the types are measured beside each other; --pools / --nprobes restrict the legs."""
 import argparse
 import csv
 import glob
@@ -50,15 +54,20 @@ def exact_topk_f64(torch, x, q, k):
     return bi
 
 
-def legs():
-    """(name, nprobe, rerank, pool option, top_k of the call)"""
+ELEM_BYTES = {"f32": 4, "f16": 2, "bf16": 2}
+
+
+def legs(a):
+    """(name, nprobe, rerank, pool option, top_k of the call, raw dtype)"""
     out = []
-    for nprobe in NPROBES:
-        out.append((f"np{nprobe}_off", nprobe, 0, 0, 10))
-        out.append((f"np{nprobe}_rerank_unpooled", nprobe, 1, 0, 10))
-        for p in POOLS:
-            out.append((f"np{nprobe}_pool{p}", nprobe, 1, p, 10))
-            out.append((f"np{nprobe}_sliced{p}", nprobe, 1, 0, p))
+    for nprobe in a.nprobes:
+        out.append((f"np{nprobe}_off", nprobe, 0, 0, 10, a.raw_dtype[0]))
+        for dt in a.raw_dtype:
+            sfx = "" if dt == "f32" else "_" + dt
+            out.append((f"np{nprobe}_rerank_unpooled{sfx}", nprobe, 1, 0, 10, dt))
+            for p in a.pools:
+                out.append((f"np{nprobe}_pool{p}{sfx}", nprobe, 1, p, 10, dt))
+                out.append((f"np{nprobe}_sliced{p}{sfx}", nprobe, 1, 0, p, dt))
     return out
 
 
@@ -72,20 +81,28 @@ def kernel_table(a):
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     pooled = [r for r in rows if "k_rerank_pool" in r["Kernel_Name"]]
     plain = [r for r in rows if "k_rerank" in r["Kernel_Name"] and "k_rerank_pool" not in r["Kernel_Name"]]
-    # the order of legs(): per nprobe the unpooled rerank (k_rerank), then per pool the pooled leg (k_rerank_pool) and the sliced one (k_rerank)
-    if len(pooled) != n * len(NPROBES) * len(POOLS) or len(plain) != n * len(NPROBES) * (len(POOLS) + 1):
+    # the order of legs(): every leg with the rerank on dispatches one rerank kernel per call, k_rerank_pool where its pool exceeds
+    # its top_k and k_rerank otherwise
+    a.raw_dtype, a.pools, a.nprobes = traced.get("raw_dtype", ["f32"]), traced.get("pools", list(POOLS)), traced.get("nprobes", list(NPROBES))
+    L = [leg for leg in legs(a) if leg[2]]
+    want_pooled = n * sum(1 for leg in L if leg[3] > leg[4])
+    if len(pooled) != want_pooled or len(plain) != n * len(L) - want_pooled:
         raise SystemExit(f"unexpected dispatch counts: k_rerank_pool {len(pooled)}, k_rerank {len(plain)}")
     rec = {"source": "rocprofv3 --kernel-trace, a run of its own", "calls_per_leg": n,
            "hbm_peak_TBps": HBM_PEAK_TBS, "hbm_measured_copy_TBps": HBM_MEASURED_TBS, "kernels": {}}
-    for j, nprobe in enumerate(NPROBES):
-        for pi, p in enumerate(POOLS):
-            for leg, d in (("pool", pooled[(j * len(POOLS) + pi) * n:][:n]), ("sliced", plain[(j * (len(POOLS) + 1) + 1 + pi) * n:][:n])):
-                us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in d]
-                req = rate["legs"][f"np{nprobe}_pool{p}"]["pool_entries"] * dim * 4
-                med = statistics.median(us)
-                rec["kernels"][f"np{nprobe}_{leg}{p}"] = {"kernel": "k_rerank_pool" if leg == "pool" else "k_rerank", "dispatches": len(us),
-                                                          "median_us": round(med, 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2),
-                                                          "requested_bytes": req, "requested_TBps": round(req / (med * 1e-6) / 1e12, 3)}
+    for name, nprobe, _, pool, k, dt in L:
+        src = pooled if pool > k else plain
+        d, src[:] = src[:n], src[n:]
+        if not pool and k == 10:
+            continue  # (the unpooled rerank of the answer itself: ten rows per query, not a rate)
+        us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in d]
+        assert all(("k_rerank_pool" in r["Kernel_Name"]) == (pool > k) for r in d)
+        entries = next(v["pool_entries"] for nm, v in rate["legs"].items() if nm.split("_")[:2] == [f"np{nprobe}", f"pool{pool or k}"])
+        req = entries * dim * ELEM_BYTES[dt]  # (the pool's entries do not depend on the type the rows are kept in)
+        med = statistics.median(us)
+        rec["kernels"][name] = {"kernel": d[0]["Kernel_Name"], "raw_dtype": dt, "dispatches": len(us),
+                                "median_us": round(med, 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2),
+                                "requested_bytes": req, "requested_TBps": round(req / (med * 1e-6) / 1e12, 3)}
     with open(a.out, "w") as f:
         json.dump(rec, f, indent=1)
         f.write("\n")
@@ -100,6 +117,9 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--calls", type=int, default=20, help="calls per timed window")
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--raw-dtype", nargs="+", choices=("f32", "f16", "bf16"), default=["f32"])
+    ap.add_argument("--pools", nargs="+", type=int, default=list(POOLS))
+    ap.add_argument("--nprobes", nargs="+", type=int, default=list(NPROBES))
     ap.add_argument("--traced", action="store_true")
     ap.add_argument("--kernel-table", default=None, metavar="DIR")
     ap.add_argument("--rate", default=None)
@@ -122,13 +142,20 @@ def main():
                                            rq.RotatorType.FhtKacRotator, 20260104, True)
     a32 = assign.to(torch.int32).contiguous()
     idx = rq.IvfRabitqIndex.build_on_device(small.hdr_ptr, cent_h, x.data_ptr(), a32.data_ptr(), a.n, small.t_const, device=0)
-    idx.set_rerank_vectors(device_ptr=x.data_ptr(), n=a.n)
+    rows = {"f32": x}  # what each type's legs borrow; 16-bit: the rows rounded once (to nearest even), as a caller would keep them
+    for dt in a.raw_dtype:
+        if dt != "f32":
+            rows[dt] = x.to(torch.float16 if dt == "f16" else torch.bfloat16).contiguous()
+    attached = [None]
     gt = None if a.traced else exact_topk_f64(torch, x, q, top_k).cpu().numpy()
     st = torch.cuda.Stream(dev)
     bufs = {}
 
     def run(leg, calls):
-        _, nprobe, rerank, pool, k = leg
+        _, nprobe, rerank, pool, k, dt = leg
+        if attached[0] != dt:  # (outside the timed window)
+            idx.set_rerank_vectors(device_ptr=rows[dt].data_ptr(), n=a.n, **({} if dt == "f32" else {"dtype": dt}))
+            attached[0] = dt
         if k not in bufs:
             bufs[k] = (torch.zeros(a.batch, k, dtype=torch.int64, device=dev), torch.zeros(a.batch, k, dtype=torch.float32, device=dev),
                        torch.zeros(a.batch, dtype=torch.int32, device=dev))
@@ -144,9 +171,10 @@ def main():
 
     rec = {"n": a.n, "dim": a.dim, "nlist": a.nlist, "bits": 7, "metric": "L2", "batch": a.batch, "top_k": top_k, "dataset": "mixture_id32",
            "calls_per_window": a.calls, "rounds": a.rounds, "legs": {}}
-    L = legs()
+    rec.update({"raw_dtype": a.raw_dtype, "pools": a.pools, "nprobes": a.nprobes})
+    L = legs(a)
     if a.traced:
-        rec = {"calls_per_leg": 6}
+        rec = {"calls_per_leg": 6, "raw_dtype": a.raw_dtype, "pools": a.pools, "nprobes": a.nprobes}
         for leg in L:
             run(leg, rec["calls_per_leg"])
     else:
@@ -155,7 +183,7 @@ def main():
             ids = d_i.cpu().numpy()[:, :top_k]
             r = {"recall_at_10": round(bench.recall_of(ids, gt, top_k), 4), "mean_count": float(d_c.float().mean())}
             if leg[3]:  # entries of the pools: what the plain search at top_k := pool returns
-                _, _, p_c = run((None, leg[1], 0, 0, leg[3]), 1)
+                _, _, p_c = run((None, leg[1], 0, 0, leg[3], leg[5]), 1)
                 r["pool_entries"] = int(p_c.sum())
             rec["legs"][leg[0]] = r
         times = {leg[0]: [] for leg in L}
