@@ -182,6 +182,13 @@ uint32_t rbq_index_device_count(const rbq_index* idx); /* number of replicas */
  * registers), top_k <= 16384 (exact heap in the LDS of one compute unit: one workgroup per CU from top_k ~ 7000; above it
  * the heap lives in global memory).  top_k > 2^20, or nq * top_k * 8 bytes of heap workspace > 8 GiB in one device call, is
  * RBQ_INVALID_CONFIG; nq < 2^31 per call of the device entry.
+ * RANGE SEARCH (option "range_search" 1 with the radius r of "range_radius_bits", rbq_debug_set_option; also through
+ * rbq_search_batch_device): top_k is read as the CAPACITY of a query's row (<= 2^20; no heap workspace, no 8 GiB rule).  A vector
+ * of the probed lists matches iff the reference's loop (src/ivf.rs:2013-2127) with the constant r in the place of the running
+ * k-th distance evaluates it and finds distance < r (L2) or score > r (inner product).  out_counts[q] is the TOTAL number of
+ * matches and may exceed top_k: that is how a caller sees truncation.  The first min(total, top_k) matches in scan order (probe
+ * order, then position inside the list; not sorted by score) are written, the other slots are UINT64_MAX / NaN.  diag counts as in
+ * that loop and does not depend on top_k.  Errors and the top_k == 0 case are as above.
  * Re-entrant on one handle.  The batch is cut into sub-batches that are pipelined over a few streams: host
  * staging and PCIe copies of one sub-batch overlap the kernels of the others.  Buffers that are page-locked
  * (rbq_host_alloc, hipHostMalloc, hipHostRegister) are DMA-ed directly; pageable ones are staged through the
@@ -383,9 +390,13 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *                        shortlist's error bound is derived for)
  *   "rank_planar" 1      TEST ONLY: the split-bf16 ranking GEMM reads planar copies of its operands (two planes [rows][D] each,
  *                        de-interleaved per call) instead of the interleaved images — same kernel, same scores bit for bit
- * and four that are not result-neutral:
+ * and six that are not result-neutral:
  *   "rerank" 0/1         the optional full-precision rerank (needs rbq_index_set_rerank_vectors)
  *   "rerank_pool" v      candidates the rerank re-scores per query, 0 = off, at most 4096 (rbq_index_set_rerank_vectors)
+ *   "range_radius_bits" v  the 32 bits of an f32 radius r, passed through the int (every pattern is accepted; default +inf)
+ *   "range_search" 0/1   range search (default 0): rbq_search_batch / rbq_search_batch_device return every vector of the probed
+ *                        lists with distance < r (L2) or score > r (inner product), see rbq_search_batch; RBQ_INVALID_CONFIG
+ *                        while the rerank is on; the MSTG entry points and MSTG handles ignore it
  *   "numeric_variant" v  rbq_index_set_numeric_variant(idx, v): which build of the reference the scores reproduce
  *   "debug_replica" r    which replica rbq_debug_copy_index / rbq_debug_copy_workspace read */
 int rbq_debug_set_option(rbq_index* idx, const char* name, int value);

@@ -198,6 +198,8 @@ int Options::set(const char* name, int v) {
             return fail(RBQ_INVALID_CONFIG, "rerank vectors: unknown dtype " + std::to_string(v) + " (RBQ_RAW_F32, RBQ_RAW_F16 or RBQ_RAW_BF16)");
         rerank_raw_dtype = v;
     }
+    else if (is("range_search")) range_search = v != 0;
+    else if (is("range_radius_bits")) range_radius_bits = (uint32_t)v; // the 32 bits of an f32 radius: every pattern is a radius
     else return fail(RBQ_INVALID_CONFIG, std::string("unknown option ") + name);
     return RBQ_OK;
 }

@@ -1,5 +1,6 @@
 // api_search.hip — the IVF search: the device entry and the host entry (rbq_search_batch, one replica or N).  The hot path
-// (search_host -> search_device -> scan_stage) stays in this one unit; api_mstg_search.hip shares its workspaces and scan_stage.
+// (search_host -> search_device -> search_front -> scan_stage, or range_stage while the option range_search is on) stays in this one
+// unit; api_mstg_search.hip shares its workspaces and scan_stage.
 #include "api.hpp"
 
 using namespace rbq_api;
@@ -140,24 +141,50 @@ int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, ui
     return RBQ_OK;
 }
 
-namespace {
-// Core: everything on device pointers, enqueued on `stream`. Workspace buffers come from `w`.
-// `rerank`: the unpooled rerank (k_rerank over the returned ids) follows the scan
-int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe_in,
+// k_range launch: the range search's stage, where a top-k call has scan_stage.  `cap` = the capacity of a query's output row.  No heap
+// workspace, no tie log and no dead_skipped: the range path selects eagerly, so every probed list is in the stream.
+int range_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, uint32_t cap, uint64_t wl_stride,
                 const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
-                rbq_diag* d_diag, hipStream_t stream, bool rerank) {
+                rbq_diag* d_diag, hipStream_t stream) {
+    ProfScope ps(ix, 3, stream, /*ext=*/true); // (the profile stage "scan" times k_range while the option is on)
+    RangeParams P;
+    P.blocks = (const uint8_t*)ix->blocks.p; P.ids = (const uint64_t*)ix->ids.p; P.ex_codes = (const uint8_t*)ix->ex.p;
+    P.f_add_ex = (const float*)ix->fadd_ex.p; P.f_rescale_ex = (const float*)ix->fres_ex.p;
+    P.lut = (const uint8_t*)w->lut.p; P.rot = (const float*)w->rot.p; P.consts = (const QueryConsts*)w->consts.p;
+    P.probe = (const ProbeInfo*)w->probe.p; P.wl = (const StreamItem*)w->wl.p; P.nstream = (const uint32_t*)w->nstream.p;
+    P.filter = d_filter; P.filter_nbits = filter_nbits; P.wl_stride = wl_stride;
+    P.out_ids = d_ids; P.out_scores = d_scores; P.out_counts = d_counts; P.diag = (unsigned long long*)d_diag;
+    P.D = ix->D; P.Dc = ix->Dc; P.nprobe = probe_stride; P.top_k = cap; P.metric = ix->metric; P.ex_bits = ix->ex_bits;
+    P.no_block_bound = ix->opt.no_block_bound ? 1u : 0u;
+    P.exact_heap = 0; P.heap_restarts = nullptr; P.tie_stats = nullptr; P.mstg = 0; P.prof = nullptr; P.heap_ws = nullptr;
+    P.dead_skipped = nullptr; P.wave_kernel = 0; P.tie_log = nullptr; P.tie_log_cap = 0;
+    P.numeric_variant = ix->opt.numeric_variant;
+    // the caller's radius bounds the distance for L2 and the score for inner product: both are `distance < R` on the internal distance
+    float r;
+    std::memcpy(&r, &ix->opt.range_radius_bits, 4);
+    P.R = ix->metric == 0 ? r : -r;
+    HIP_TRY(launch_range(P, (uint32_t)nq, ix->device, stream, ps.start(), ps.stop()));
+    return RBQ_OK;
+}
+
+namespace {
+// range search on this handle?  (MSTG handles — RBQ_ROTATOR_NONE — never take it)
+inline bool range_on(const Replica* ix) { return ix->opt.range_search && ix->rotator != 2; }
+
+// What the front leaves for the stage that follows it
+struct Front { uint32_t nprobe; uint64_t wl_stride; bool exact_select; };
+
+// Front of a search on device pointers, enqueued on `stream`, shared by the top-k scan and the range scan: workspace sizing, prep /
+// latency front, ranking GEMM or exact ranking, selection.  `range`: the selection is eager (no threshold exists to drop a list against).
+int search_front(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe_in,
+                 const uint32_t* d_filter, uint64_t filter_nbits, rbq_diag* d_diag, hipStream_t stream, bool range, Front& front) {
     const uint32_t D = ix->D, Dc = ix->Dc;
     const uint32_t nlist = (uint32_t)ix->n_lists;
     uint32_t nprobe = nprobe_in < 1 ? 1 : nprobe_in;
     if (nprobe > nlist) nprobe = nlist;
-    // nprobe > kNprobeMax: the exact all-pairs ranking with its key window in global memory; top_k > kTopKMax: the heap in
-    // global memory — both slow, both served (the reference clamps nprobe to n_lists and accepts any top_k)
+    // nprobe > kNprobeMax: the exact all-pairs ranking with its key window in global memory (slow, but served: the reference clamps
+    // nprobe to n_lists)
     const bool big_nprobe = nprobe > kNprobeMax;
-    // the 8 GiB bound is the global-memory heap's (top_k beyond what the LDS holds); calls whose heap lives in LDS need no workspace
-    const bool heap_in_global = top_k > kTopKMax || scan_lds_bytes(Dc, D, ix->ex_bits, top_k) > kLdsPerWorkgroupMax;
-    if (top_k > kTopKHardMax || (heap_in_global && (uint64_t)nq * ((uint64_t)top_k + 1) * 8 > (8ull << 30)))
-        return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20 and nq * top_k * 8 bytes of heap workspace <= 8 GiB)");
-    if (rerank && top_k > 1024) return fail(RBQ_INVALID_CONFIG, "rerank supports top_k <= 1024");
     const uint64_t wl_stride = std::max<uint64_t>(ix->nblk_desc_prefix[nprobe], 1);
 
     int rc;
@@ -268,7 +295,7 @@ int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, 
     // (round 4: under a filter the exact head evaluation can still bound the k-th distance — it looks at real vectors and counts
     // the ones that pass; with diagnostics the skip counter of a dropped list would need every id's filter bit: eager then)
     const bool lazy_with_filter = ix->opt.lazy_filter && ix->opt.head_exact && !d_diag;
-    sp.lazy = (ix->opt.lazy_select && (!d_filter || lazy_with_filter) && !ix->opt.no_block_bound) ? 1 : 0;
+    sp.lazy = (ix->opt.lazy_select && (!d_filter || lazy_with_filter) && !ix->opt.no_block_bound && !range) ? 1 : 0;
     sp.filter = d_filter; sp.filter_nbits = filter_nbits; sp.ids = (const uint64_t*)ix->ids.p;
     sp.exact_members = d_diag ? 1 : 0;
     sp.fault_dead_all = ix->opt.lazy_fault_inject ? 1 : 0;
@@ -296,8 +323,35 @@ int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, 
         if ((smask & 2u) && !lat_front) { ProfScope ps(ix, 1, stream); HIP_TRY(launch_rank_gemm(rp, ix->device, stream)); } // approximate scores: one MFMA GEMM
         if (smask & 4u) { ProfScope ps(ix, 2, stream); HIP_TRY(launch_select_mfma(sp, ix->device, stream)); }         // shortlist + exact canonical scores + exact select
     }
-    if ((smask & 8u) && (rc = scan_stage(ix, w, nq, nprobe, top_k, wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag,
-                         /*mstg=*/false, (ix->opt.exact_rank || big_nprobe) ? nullptr : (const uint32_t*)w->dead_skipped.p, stream)))
+    front.nprobe = nprobe; front.wl_stride = wl_stride; front.exact_select = ix->opt.exact_rank || big_nprobe;
+    return RBQ_OK;
+}
+
+// Core: the front, then the stage that reads its stream — the top-k scan, or the range scan while the option range_search is on.
+// `rerank`: the unpooled rerank (k_rerank over the returned ids) follows the scan
+int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe_in,
+                const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
+                rbq_diag* d_diag, hipStream_t stream, bool rerank) {
+    const bool range = range_on(ix);
+    int rc;
+    Front f;
+    if (range) {
+        // top_k is the capacity of a query's output row; no heap exists, so the heap workspace's 8 GiB rule does not apply
+        if (top_k > kTopKHardMax) return fail(RBQ_INVALID_CONFIG, "range search: the capacity of a query's row is at most 2^20");
+        if ((rc = search_front(ix, w, d_queries, nq, top_k, nprobe_in, d_filter, filter_nbits, d_diag, stream, true, f))) return rc;
+        if (ix->opt.stage_mask & 8u)
+            return range_stage(ix, w, nq, f.nprobe, top_k, f.wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag, stream);
+        return RBQ_OK;
+    }
+    // top_k > kTopKMax: the heap in global memory — slow, but served (the reference accepts any top_k)
+    // the 8 GiB bound is the global-memory heap's (top_k beyond what the LDS holds); calls whose heap lives in LDS need no workspace
+    const bool heap_in_global = top_k > kTopKMax || scan_lds_bytes(ix->Dc, ix->D, ix->ex_bits, top_k) > kLdsPerWorkgroupMax;
+    if (top_k > kTopKHardMax || (heap_in_global && (uint64_t)nq * ((uint64_t)top_k + 1) * 8 > (8ull << 30)))
+        return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20 and nq * top_k * 8 bytes of heap workspace <= 8 GiB)");
+    if (rerank && top_k > 1024) return fail(RBQ_INVALID_CONFIG, "rerank supports top_k <= 1024");
+    if ((rc = search_front(ix, w, d_queries, nq, top_k, nprobe_in, d_filter, filter_nbits, d_diag, stream, false, f))) return rc;
+    if ((ix->opt.stage_mask & 8u) && (rc = scan_stage(ix, w, nq, f.nprobe, top_k, f.wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag,
+                                                      /*mstg=*/false, f.exact_select ? nullptr : (const uint32_t*)w->dead_skipped.p, stream)))
         return rc;
     if (rerank && !stage_probes()) // optional, default off: exact re-scoring of the returned ids against the attached raw vectors
         HIP_TRY(launch_rerank(d_queries, (uint32_t)nq, ix->dim, ix->raw.p, ix->raw_dtype, ix->n_raw, ix->metric, top_k, d_ids, d_scores,
@@ -311,6 +365,8 @@ int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, 
 int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe,
                   const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
                   rbq_diag* d_diag, hipStream_t stream) {
+    if (range_on(ix) && ix->rerank)
+        return fail(RBQ_INVALID_CONFIG, "range search does not run with the rerank on: set the option rerank 0 or detach the vectors");
     const uint32_t pool = ix->opt.rerank_pool;
     if (!ix->rerank || pool <= top_k)
         return search_core(ix, w, d_queries, nq, top_k, nprobe, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag, stream, ix->rerank);

@@ -3,6 +3,7 @@
 // rebuild k_scan's instantiations and vice versa.
 //   k_query.hip  k_prep / k_prep_wave, k_rank_* , k_select*, k_probes_given     (kernels.hpp, rank_mfma.hpp, canon_score.hpp, select_*.hpp)
 //   k_scan.hip   k_scan<DT, EX, TR>                                               (scan.hpp, scan_codes.hpp, topk.hpp)
+//   k_range.hip  k_range<DT, EX>: the range search's scan against a constant radius     (range.hpp, scan_codes.hpp)
 //   k_build.hip  encoder, reference-layout -> device-layout converters, sorting   (encode.hpp)
 //   k_gemm_shortlist.hip  the front of the GEMM-shortlist paths (finite check, norms, split images, dots), KmGemmAssign (km_common.hpp)
 //   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver         (km_common.hpp)
@@ -180,6 +181,8 @@ hipError_t launch_probes_given(const ProbesGivenParams& p, hipStream_t s);
 hipError_t launch_scan(const ScanParams& P, uint32_t nq, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 // k_scanw (scanw.hpp): the same scan with one wave per query; scanw_serves(): the call shapes it takes (launch_scan routes
 // to it when ScanParams::wave_kernel is set and it serves the call)
+// k_range (range.hpp, k_range.hip): the range search's scan — the same stream against a constant threshold, matches in scan order
+hipError_t launch_range(const RangeParams& P, uint32_t nq, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 bool scanw_serves(const ScanParams& P);
 hipError_t launch_scanw(const ScanParams& P, uint32_t nq, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 

@@ -224,6 +224,23 @@ __host__ __device__ inline size_t scan_lds_bytes(uint32_t Dc, uint32_t D, uint32
            (size_t)nb * kTileCand * 4 + 2 * (size_t)nb * kTileBlocks * 4 + kQueueCap * 8 + kNScan * kFillK * 8 + 32 + (kScanThreads / 16) * 8;
 }
 
+// ---- k_range (range.hpp): every probed vector within a radius ---------------------------------------------------------------
+// The scan's parameters with top_k read as the CAPACITY of a query's output row, and the constant threshold R that stands where the
+// reference's running `distk` does (R = r for L2, -r for inner product).  heap_ws, tie_log, dead_skipped, exact_heap, wave_kernel
+// and prof are not read.
+struct RangeParams : ScanParams {
+    float R = 0.0f;
+};
+constexpr int kRangeThreads = 256;                   // four waves, all scanning
+constexpr int kRangeBlocks = kRangeThreads / 32;     // stream entries per tile: one per half-wave
+constexpr int kRangeCand = kRangeBlocks * 32;        // candidates per tile
+// LDS carve-up of k_range (dynamic only, LUT at byte 0):
+//   lut[4Dc] u8 | qrot[ex_qlen] f32 | slot, ip, gadd, d [kRangeCand] (a tile's survivors, stream order) |
+//   mask[2][kRangeBlocks] u32 | wave counts [8] u32 | nskip + pad [4] u32
+__host__ __device__ inline size_t range_lds_bytes(uint32_t Dc, uint32_t D, uint32_t ex_bits) {
+    return (size_t)Dc * 4 + (size_t)ex_qlen(D, ex_bits) * 4 + (size_t)kRangeCand * 16 + 2 * (size_t)kRangeBlocks * 4 + 8 * 4 + 4 * 4;
+}
+
 // ---- encoder ----------------------------------------------------------------------------------------------------
 constexpr uint32_t kNoSrc = 0xffffffffu;
 struct EncodeParams {

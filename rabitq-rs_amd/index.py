@@ -70,6 +70,7 @@ class IvfRabitqIndex:
     def __init__(self, handle, rescale=None):
         self._h = handle
         self._rescale = rescale  # (mode, t_const) the encoder ran with, where this object knows it: add()'s default
+        self._range = None       # the radius set_range_search left on the handle (None: range search off)
 
     # -- construction -------------------------------------------------------------
     @staticmethod
@@ -315,6 +316,7 @@ class IvfRabitqIndex:
     def _swap(self, h):
         """The handle a mutation returned takes the place of the old one, which is closed."""
         old, self._h = self._h, h
+        self._range = None  # (options are per handle: the new one starts with the range search off)
         lib().rbq_index_destroy(old)
 
     # -- shrinking (rbq_index_remove_ids) ------------------------------------------------------------------------------
@@ -427,6 +429,83 @@ class IvfRabitqIndex:
                             stream=None, d_filter=None, filter_nbits=0, d_diag=None):
         _check(lib().rbq_search_batch_device(self._h, d_queries, nq, query_dim, top_k, nprobe, d_filter,
                                              filter_nbits, d_ids, d_scores, d_counts, d_diag, stream))
+
+    # -- range search: every probed vector within a radius ------------------------------------
+    def set_range_search(self, radius):
+        """Options "range_radius_bits" / "range_search": with a radius (any f32, passed by its bits), batch_search_raw and
+        search_batch_device return, per query, every vector of the probed lists with distance < radius (L2) or score > radius
+        (inner product), in scan order (probe order, then position inside the list): top_k is the capacity of the row,
+        counts the TOTAL number of matches (it may exceed the capacity), unused slots are UINT64_MAX / NaN.  None switches
+        it off and puts the radius back to +inf."""
+        if radius is None:
+            self.set_option("range_search", 0)
+            self.set_option("range_radius_bits", 0x7F800000)
+        else:
+            self.set_option("range_radius_bits", int(np.array([radius], np.float32).view(np.int32)[0]))
+            self.set_option("range_search", 1)
+        self._range = radius
+
+    @staticmethod
+    def _filter_words(allowed_ids):
+        allowed = np.asarray(sorted(set(int(i) for i in allowed_ids)), dtype=np.uint64)
+        nbits = int(allowed.max()) + 1 if allowed.size else 0
+        words = np.zeros((nbits + 31) // 32 or 1, np.uint32)
+        if allowed.size:
+            np.bitwise_or.at(words, (allowed >> np.uint64(5)).astype(np.int64),
+                             (np.uint32(1) << (allowed & np.uint64(31)).astype(np.uint32)))
+        return words, nbits
+
+    @staticmethod
+    def _range_csr(ids, scores, counts, sort):
+        """Rows of capacity cap with their totals -> FAISS's (lims [nq + 1], ids, scores); a row holds min(total, cap)."""
+        kept = np.minimum(counts.astype(np.int64), ids.shape[1])
+        lims = np.zeros(len(kept) + 1, np.int64)
+        np.cumsum(kept, out=lims[1:])
+        take = np.arange(ids.shape[1])[None, :] < kept[:, None]
+        out_ids, out_sc = ids[take], scores[take]  # (row-major: rows in query order, scan order inside a row)
+        if sort:
+            for q in range(len(kept)):
+                o = np.argsort(out_sc[lims[q]:lims[q + 1]], kind="stable")  # (score, scan order)
+                out_ids[lims[q]:lims[q + 1]] = out_ids[lims[q]:lims[q + 1]][o]
+                out_sc[lims[q]:lims[q + 1]] = out_sc[lims[q]:lims[q + 1]][o]
+        return lims, out_ids, out_sc
+
+    def range_search(self, queries, radius, nprobe, max_results=None, allowed_ids=None, want_diag=False, sort=False):
+        """FAISS-style range_search over the probed lists: (lims [nq + 1] i64, ids u64, scores f32) — query q's matches are
+        ids[lims[q]:lims[q + 1]], in scan order, or ascending by (score, scan order) with sort=True.  A match has distance <
+        radius (L2) or score > radius (inner product).  max_results=None: complete rows (a first call with rows of 1024; where
+        a total exceeds that, one more with rows of the largest total — the totals are exact, so one repeat suffices).
+        max_results=m: at most the first m matches of every query, and the totals [nq] u32 as a fourth value.  want_diag: the
+        SearchDiagnostics [nq, 3] u64 as the last value.  `allowed_ids` as search_filtered.  The handle's range options are
+        set for the call and put back afterwards."""
+        from . import SearchParams
+        words, nbits = self._filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
+        cap = max_results or 1024
+        before = getattr(self, "_range", None)
+        self.set_range_search(radius)
+        try:
+            ids, sc, cnt, diag = self.batch_search_raw(queries, SearchParams(cap, nprobe), words, nbits, want_diag)
+            if max_results is None and cnt.size and int(cnt.max()) > cap:
+                ids, sc, cnt, diag = self.batch_search_raw(queries, SearchParams(int(cnt.max()), nprobe), words, nbits, want_diag)
+        finally:
+            self.set_range_search(before)
+        out = self._range_csr(ids, sc, cnt, sort)
+        if max_results is not None:
+            out += (cnt,)
+        return out + (diag,) if want_diag else out
+
+    def range_search_device(self, d_queries, nq, query_dim, radius, nprobe, cap, d_ids, d_scores, d_counts, stream=None,
+                            d_filter=None, filter_nbits=0, d_diag=None):
+        """range_search on device pointers (search_batch_device with the range options set for the call): rows of capacity
+        `cap` at d_ids / d_scores, the totals at d_counts, enqueued on `stream` without host synchronisation.  The caller
+        reads d_counts once the stream has got there and repeats with a larger `cap` where a total exceeds it."""
+        before = getattr(self, "_range", None)
+        self.set_range_search(radius)
+        try:
+            self.search_batch_device(d_queries, nq, query_dim, cap, nprobe, d_ids, d_scores, d_counts, stream, d_filter,
+                                     filter_nbits, d_diag)
+        finally:
+            self.set_range_search(before)
 
     def profile_begin(self, stages=("prep", "rank", "select", "scan"), every=1):
         mask = sum(1 << ("prep", "rank", "select", "scan").index(s) for s in stages)
