@@ -189,6 +189,14 @@ uint32_t rbq_index_device_count(const rbq_index* idx); /* number of replicas */
  * matches and may exceed top_k: that is how a caller sees truncation.  The first min(total, top_k) matches in scan order (probe
  * order, then position inside the list; not sorted by score) are written, the other slots are UINT64_MAX / NaN.  diag counts as in
  * that loop and does not depend on top_k.  Errors and the top_k == 0 case are as above.
+ * 16-BIT QUERIES (option "query_dtype" RBQ_RAW_F16 / RBQ_RAW_BF16, rbq_debug_set_option): `queries` is read as nq rows of
+ * query_dim 16-bit elements, 2 * query_dim bytes apart, passed through the `const float*` parameter as they are; query_dim stays a
+ * count of elements, every check keeps its order and its text.  An element is widened to f32 exactly where a kernel loads it (f16
+ * by the IEEE conversion, subnormals included; bf16 is bits << 16); the library never rounds a query.  The pointer must be 2-byte
+ * aligned, else RBQ_INVALID_CONFIG ("queries: pointer not aligned to its 16-bit elements") before any device call; rows of odd
+ * query_dim are 2-byte aligned only, and served.  Contract: ids, counts, score bits, diag, list outputs and errors of a call with
+ * 16-bit queries equal those of the same call with "query_dtype" RBQ_RAW_F32 on the rows widened to f32.  The option is state of
+ * the handle: changing it while a call is in flight on that handle is the caller's problem.
  * Re-entrant on one handle.  The batch is cut into sub-batches that are pipelined over a few streams: host
  * staging and PCIe copies of one sub-batch overlap the kernels of the others.  Buffers that are page-locked
  * (rbq_host_alloc, hipHostMalloc, hipHostRegister) are DMA-ed directly; pageable ones are staged through the
@@ -282,6 +290,7 @@ int rbq_index_set_rerank_vectors(rbq_index* idx, const float* vectors, uint64_t 
  * and the caller's recall.  A borrowed device pointer to 16-bit rows must be 2-byte aligned (else RBQ_INVALID_CONFIG); rows that
  * all start 4-byte aligned (base 4-byte aligned and dim even) are read 16 bytes per lane, any others element by element, with the
  * same results, slower.  Nothing outside [vectors, vectors + n * dim * sizeof(element)) is read. */
+/* element types of 16-bit rows (and f32, the default of both options): the values of "rerank_raw_dtype" and of "query_dtype" */
 #define RBQ_RAW_F32  0
 #define RBQ_RAW_F16  1   /* IEEE binary16 */
 #define RBQ_RAW_BF16 2   /* upper 16 bits of an f32 */
@@ -390,7 +399,17 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *                        shortlist's error bound is derived for)
  *   "rank_planar" 1      TEST ONLY: the split-bf16 ranking GEMM reads planar copies of its operands (two planes [rows][D] each,
  *                        de-interleaved per call) instead of the interleaved images — same kernel, same scores bit for bit
- * and six that are not result-neutral:
+ * and seven that are not result-neutral:
+ *   "query_dtype" v      RBQ_RAW_F32 (0, default), RBQ_RAW_F16 or RBQ_RAW_BF16, on every replica: what every entry point that takes
+ *                        queries on this handle — rbq_search_batch (one replica or several), rbq_search_batch_device,
+ *                        rbq_posting_scan_batch, rbq_mstg_search_batch / _device, rbq_mstg_search_refined_batch / _device — reads
+ *                        its `queries` / `d_queries` pointer as: nq rows of query_dim elements of that type (2 * query_dim bytes
+ *                        apart for the 16-bit types), see rbq_search_batch.  Any other value is RBQ_INVALID_CONFIG (detail set)
+ *                        and the handle keeps what it had.  rbq_debug_copy_index(idx, "query_dtype", &v, 4) reads it back as one
+ *                        int32.  It composes with the filter, diag, range search, the rerank (pooled or not, raw rows of any
+ *                        type), every numeric variant and every diagnostic option; a call in flight while it changes is the
+ *                        caller's problem.  Contract: ids, counts, score bits, diag, list outputs and errors of a call with 16-bit
+ *                        queries equal those of the same call with "query_dtype" RBQ_RAW_F32 on the rows widened to f32
  *   "rerank" 0/1         the optional full-precision rerank (needs rbq_index_set_rerank_vectors)
  *   "rerank_pool" v      candidates the rerank re-scores per query, 0 = off, at most 4096 (rbq_index_set_rerank_vectors)
  *   "range_radius_bits" v  the 32 bits of an f32 radius r, passed through the int (every pattern is accepted; default +inf)

@@ -49,6 +49,52 @@ def rows_arg(data):
     return C.c_void_p(h.ctypes.data), h
 
 
+def query_arg(queries, dtype=None):
+    """(keep-alive, RBQ_RAW_* code) of a query argument (option "query_dtype"): a contiguous NumPy array or torch tensor whose
+    elements the library reads as they are, and what they are.  numpy.float32 -> f32 as ever; numpy.float16 -> f16; torch.half ->
+    f16 and torch.bfloat16 -> bf16, on the host or on a device; a numpy.uint16 array holds bit patterns and needs `dtype` "f16" or
+    "bf16" (set_rerank_vectors' convention).  Anything else becomes f32 on the host (a tensor: where it lives), as before.
+    `dtype` "f16" with other host data converts with astype(numpy.float16), "f32" widens: the caller's rounding, never the library's.
+    data_ptr(keep-alive) is the pointer."""
+    from . import RabitqError
+    code = None
+    if dtype is not None:
+        if isinstance(dtype, str) and dtype not in _abi.RAW_DTYPES:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "unknown query dtype %r (one of %s)" % (dtype, ", ".join(_abi.RAW_DTYPES)))
+        code = _abi.RAW_DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+    torch = torch_of(queries)
+    if torch is not None:
+        own = {torch.float16: _abi.RAW_F16, torch.bfloat16: _abi.RAW_BF16}.get(queries.dtype, _abi.RAW_F32)
+        if code is None:
+            code = own
+        if code != own or queries.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            want = {_abi.RAW_F32: torch.float32, _abi.RAW_F16: torch.float16, _abi.RAW_BF16: torch.bfloat16}.get(code)
+            if want is None:
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "unknown query dtype %r" % (dtype,))
+            queries = queries.to(dtype=want)
+        return queries.contiguous(), code
+    if isinstance(queries, np.ndarray) and queries.dtype == np.uint16:
+        if code not in (_abi.RAW_F16, _abi.RAW_BF16):
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, 'uint16 queries are bit patterns: pass dtype="f16" or dtype="bf16"')
+        return np.ascontiguousarray(queries), code
+    if code is None:
+        code = _abi.RAW_F16 if isinstance(queries, np.ndarray) and queries.dtype == np.float16 else _abi.RAW_F32
+    if code == _abi.RAW_BF16:
+        raise RabitqError(_abi.RBQ_INVALID_CONFIG, "bf16 queries on the host are a uint16 array of bit patterns or a torch.bfloat16 tensor")
+    if code not in (_abi.RAW_F32, _abi.RAW_F16):
+        raise RabitqError(_abi.RBQ_INVALID_CONFIG, "unknown query dtype %r" % (dtype,))
+    return np.ascontiguousarray(queries, dtype=np.float16 if code == _abi.RAW_F16 else np.float32), code
+
+
+def data_ptr(x):
+    """The address of the first element of what query_arg returned."""
+    return int(x.data_ptr()) if torch_of(x) is not None else int(x.ctypes.data)
+
+
+def on_device(x):
+    return torch_of(x) is not None and x.is_cuda
+
+
 def known_rescale(remembered, rescale, t_const):
     """(rescale, t_const) of an add(): what the caller passed, else what the object remembers it was encoded with."""
     if rescale is None:

@@ -313,10 +313,11 @@ inline Geometry geometry_of(const rbq_header& h) {
 
 // k_prep's parameters for nq queries at `queries` (device-visible): the index's geometry and rotator, the workspace's
 // rot / lut / consts (both workspace types name them alike).  No split-bf16 copies, one wave per query.
+// query_dtype: RBQ_RAW_* of the rows at `queries` (the option "query_dtype" of an IVF / MSTG handle; the brute-force index: f32).
 template <class Ws>
-PrepParams prep_params(const Geometry& g, const Arr& rot_blob, Ws& w, const float* queries, uint64_t nq) {
+PrepParams prep_params(const Geometry& g, const Arr& rot_blob, Ws& w, const void* queries, uint64_t nq, int query_dtype = kRawF32) {
     PrepParams p;
-    p.queries = queries; p.nq = (uint32_t)nq; p.dim = g.dim; p.D = g.D; p.Dc = g.Dc; p.rotator = (int)g.rotator;
+    p.queries = queries; p.query_dtype = query_dtype; p.nq = (uint32_t)nq; p.dim = g.dim; p.D = g.D; p.Dc = g.Dc; p.rotator = (int)g.rotator;
     p.rot_blob = (const uint8_t*)rot_blob.p; p.trunc = g.trunc; p.fac = g.fac; p.ex_bits = g.ex_bits;
     p.rot = (float*)w.rot.p; p.lut = (uint8_t*)w.lut.p; p.consts = (QueryConsts*)w.consts.p;
     p.rot_hl = nullptr; p.wg_prep = false;
@@ -362,6 +363,7 @@ struct Options {
     uint64_t fetch_chunk = 0; // TEST ONLY: ids per staging chunk of rbq_index_fetch_embeddings (0 = default)
     uint64_t mstg_chunk = 0;  // TEST ONLY: staging chunk of rbq_mstg_save* in bytes, any value >= 1 (0 = default)
     uint64_t mstg_search_budget = 0; // TEST ONLY: per-chunk workspace of rbq_mstg_search_batch* in bytes (0 = default)
+    int query_dtype = 0;      // RBQ_RAW_*: what every entry point that takes queries reads its pointer as (0: f32)
     int rerank_raw_dtype = 0; // RBQ_RAW_*: the element type the next rbq_index_set_rerank_vectors reads its pointer as (0: f32)
     uint32_t rerank_pool = 0; // while rerank is on and rerank_pool > top_k: the search runs at top_k := rerank_pool, the pool is scored
                               // exactly against the attached vectors and the best top_k are returned (0 = off; <= kRerankPoolMax)
@@ -518,6 +520,10 @@ Workspace* take_ws(Replica* ix);
 void give_ws(Replica* ix, Workspace* w);
 Workspace* stream_workspace(Replica* ix, hipStream_t s);
 int check_query_args(const rbq_index* h, uint32_t query_dim);
+// the handle's query rows (option "query_dtype") of `query_dim` elements; check_query_pointer: RBQ_INVALID_CONFIG for a pointer that
+// cannot hold them (16-bit rows at an odd address) — no HIP call is made to find out
+inline rbq_host::QueryRows query_rows(const Replica* ix, uint32_t query_dim) { return rbq_host::QueryRows{ix->opt.query_dtype, query_dim}; }
+int check_query_pointer(const rbq_index* h, const void* queries);
 Replica* replica_of_pointer(rbq_index* h, const void* dptr);
 struct ProfScope {
     Replica* ix; int stage; hipStream_t s; std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};

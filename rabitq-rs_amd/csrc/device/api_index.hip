@@ -198,6 +198,11 @@ int Options::set(const char* name, int v) {
             return fail(RBQ_INVALID_CONFIG, "rerank vectors: unknown dtype " + std::to_string(v) + " (RBQ_RAW_F32, RBQ_RAW_F16 or RBQ_RAW_BF16)");
         rerank_raw_dtype = v;
     }
+    else if (is("query_dtype")) { // what every entry point that takes queries reads its pointer as
+        if (v != RBQ_RAW_F32 && v != RBQ_RAW_F16 && v != RBQ_RAW_BF16)
+            return fail(RBQ_INVALID_CONFIG, "queries: unknown dtype " + std::to_string(v) + " (RBQ_RAW_F32, RBQ_RAW_F16 or RBQ_RAW_BF16)");
+        query_dtype = v;
+    }
     else if (is("range_search")) range_search = v != 0;
     else if (is("range_radius_bits")) range_radius_bits = (uint32_t)v; // the 32 bits of an f32 radius: every pattern is a radius
     else return fail(RBQ_INVALID_CONFIG, std::string("unknown option ") + name);
@@ -805,6 +810,12 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
     if (!std::strcmp(name, "rerank_raw_dtype")) { // (not an array: RBQ_RAW_* of the attached rerank rows as one int32, -1 with none attached)
         if (bytes != 4) return fail(RBQ_INVALID_CONFIG, "rerank_raw_dtype is one int32");
         const int32_t v = h->reps[0]->raw.p ? h->reps[0]->raw_dtype : -1;
+        std::memcpy(dst, &v, 4);
+        return RBQ_OK;
+    }
+    if (!std::strcmp(name, "query_dtype")) { // (not an array: the option "query_dtype" as the handle holds it, one int32)
+        if (bytes != 4) return fail(RBQ_INVALID_CONFIG, "query_dtype is one int32");
+        const int32_t v = h->reps[0]->opt.query_dtype;
         std::memcpy(dst, &v, 4);
         return RBQ_OK;
     }

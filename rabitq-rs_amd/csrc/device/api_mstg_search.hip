@@ -19,7 +19,7 @@ int mstg_prep(Replica* ix, Workspace* w, const float* d_q, uint64_t n, bool keep
     if ((rc = w->lut.ensure(n * (size_t)ix->Dc * 4))) return rc;
     if ((rc = w->consts.ensure(n * sizeof(QueryConsts)))) return rc;
     ProfScope ps(ix, 0, stream);
-    PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_q, n);
+    PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_q, n, ix->opt.query_dtype);
     if (!keep_ex_bits) p.ex_bits = 0u;
     HIP_TRY(launch_prep(p, ix->device, stream));
     return RBQ_OK;
@@ -56,16 +56,17 @@ int scan_posting_lists(Replica* ix, Workspace* w, uint64_t n, const uint32_t* d_
 template <class Body>
 int host_chunks(Replica* ix, Workspace* w, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint64_t chunk,
                 uint64_t* out_ids, float* out_scores, uint32_t* out_counts, Body body) {
+    const rbq_host::QueryRows qr = query_rows(ix, query_dim);
     auto run = [&]() -> int {
         int rc;
         hipStream_t st = w->stream;
         for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
             const uint64_t n = std::min(chunk, nq - q0);
             const OutPack op(n, top_k, false);
-            if ((rc = w->queries.ensure(n * query_dim * 4))) return rc;
+            if ((rc = w->queries.ensure(qr.bytes(n)))) return rc;
             if ((rc = w->out_pack.ensure(op.total))) return rc;
             uint8_t* dp = (uint8_t*)w->out_pack.p;
-            HIP_TRY(hipMemcpyAsync(w->queries.p, queries + q0 * query_dim, n * query_dim * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(w->queries.p, qr.at(queries, q0), qr.bytes(n), hipMemcpyHostToDevice, st));
             if ((rc = body(q0, n, (const float*)w->queries.p, (uint64_t*)(dp + op.o_ids), (float*)(dp + op.o_scores), (uint32_t*)(dp + op.o_counts), st)))
                 return rc;
             HIP_TRY(hipMemcpyAsync(out_ids + q0 * top_k, dp + op.o_ids, n * top_k * 8, hipMemcpyDeviceToHost, st));
@@ -209,6 +210,7 @@ int ms_check(const rbq_index* h, const MstgArgs& c, uint32_t* pool) {
 int mstg_begin(rbq_index* h, const MstgArgs& a, bool host, hipStream_t s, MstgCall* c) {
     int rc = ms_check(h, a, &c->pool);
     if (rc || a.nq == 0) return rc;
+    if ((rc = check_query_pointer(h, a.queries))) return rc;
     Replica* ix = c->ix = host ? h->reps[0] : replica_of_pointer(h, a.queries);
     const uint32_t ef = (uint32_t)std::min<uint64_t>(a.ef_search, ix->n_lists);
     const bool empty = a.top_k == 0 || ef == 0;
@@ -240,7 +242,7 @@ int mstg_begin(rbq_index* h, const MstgArgs& a, bool host, hipStream_t s, MstgCa
     return RBQ_OK;
 }
 
-// n queries at d_q (device), everything enqueued on `stream`; d_lists [n][sh.ef] and d_lcnt [n] receive the selection.
+// n queries at d_q (device; rows of the handle's query_dtype, read by mstg_prep alone), everything enqueued on `stream`; d_lists [n][sh.ef] and d_lcnt [n] receive the selection.
 // Refined (c.pool, k_mstg_refine.hip): the scan runs with top_k := pool over the slot map into the workspace's pool, which is
 // then refined into the caller's top_k.
 int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
@@ -333,7 +335,7 @@ int ms_search_device(const rbq_index* ch, const MstgArgs& a, void* hip_stream) {
         const uint64_t n = std::min(sh.chunk, a.nq - q0);
         uint32_t* d_lists = a.out_list_ids ? a.out_list_ids + q0 * sh.ef : (uint32_t*)w->ms_lists.p;
         uint32_t* d_lcnt = a.out_list_counts ? a.out_list_counts + q0 : (uint32_t*)w->ms_lists.p + sh.chunk * (size_t)sh.ef;
-        if ((rc = run_chunk(c, w, a.queries + q0 * a.query_dim, n, a.out_ids + q0 * a.top_k, a.out_scores + q0 * a.top_k, a.out_counts + q0,
+        if ((rc = run_chunk(c, w, query_rows(c.ix, a.query_dim).at(a.queries, q0), n, a.out_ids + q0 * a.top_k, a.out_scores + q0 * a.top_k, a.out_counts + q0,
                             d_lists, d_lcnt, s)))
             return rc;
     }
@@ -357,6 +359,7 @@ int rbq_posting_scan_batch(const rbq_index* ch, const float* queries, uint64_t n
     if (ix->rotator != RBQ_ROTATOR_NONE) return fail(RBQ_INVALID_CONFIG, "posting-list scan needs an index created with rotator NONE");
     if (nq == 0) return RBQ_OK;
     if (!queries || !list_ids || !list_counts || !out_ids || !out_scores || !out_counts) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    if ((rc = check_query_pointer(h, queries))) return rc;
     if (top_k == 0) { std::memset(out_counts, 0, nq * 4); return RBQ_OK; }
     if (top_k > kTopKHardMax || (uint64_t)std::min<uint64_t>(nq, 16384) * ((uint64_t)top_k + 1) * 8 > (8ull << 30))
         return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20)");

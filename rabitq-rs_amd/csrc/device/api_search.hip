@@ -79,6 +79,11 @@ int check_query_args(const rbq_index* h, uint32_t query_dim) {
     return RBQ_OK;
 }
 
+int check_query_pointer(const rbq_index* h, const void* queries) {
+    if (!query_rows(h->reps[0], 0).aligned(queries)) return fail(RBQ_INVALID_CONFIG, "queries: pointer not aligned to its 16-bit elements");
+    return RBQ_OK;
+}
+
 Replica* replica_of_pointer(rbq_index* h, const void* dptr) {
     if (h->reps.size() == 1) return h->reps[0];
     hipPointerAttribute_t a;
@@ -233,14 +238,14 @@ int search_front(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq,
     }
     if (lat_front) {
         ProfScope ps(ix, 0, stream);
-        const PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq);
+        const PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq, ix->opt.query_dtype);
         RankParams r;
         r.metric = ix->metric; r.cent = (const float*)ix->centroids.p; r.nlist = nlist; r.D = D; r.nq = (uint32_t)nq;
         r.scores = (float*)w->scores.p;
         HIP_TRY(launch_lat_front(p, r, ix->device, stream));
     } else if (smask & 1u) {
         ProfScope ps(ix, 0, stream);
-        PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq);
+        PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq, ix->opt.query_dtype);
         p.rot_hl = split_rank ? (uint16_t*)w->rot_hl.p : nullptr;
         if (rank_f16) { p.rot_hl = (uint16_t*)w->rot_f16.p; p.rank_resid = (float*)w->rank_resid.p; }
         p.wg_prep = ix->opt.wg_prep;
@@ -354,12 +359,13 @@ int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, 
                                                       /*mstg=*/false, f.exact_select ? nullptr : (const uint32_t*)w->dead_skipped.p, stream)))
         return rc;
     if (rerank && !stage_probes()) // optional, default off: exact re-scoring of the returned ids against the attached raw vectors
-        HIP_TRY(launch_rerank(d_queries, (uint32_t)nq, ix->dim, ix->raw.p, ix->raw_dtype, ix->n_raw, ix->metric, top_k, d_ids, d_scores,
+        HIP_TRY(launch_rerank(d_queries, ix->opt.query_dtype, (uint32_t)nq, ix->dim, ix->raw.p, ix->raw_dtype, ix->n_raw, ix->metric, top_k, d_ids, d_scores,
                               d_counts, stream));
     return RBQ_OK;
 }
 
-// The search of one batch on device pointers.  With the rerank on and a pool above top_k (option rerank_pool) the pipeline above runs
+// The search of one batch on device pointers (d_queries: nq rows of the handle's query_dtype behind the float pointer — only the
+// preparation and the rerank's copy of the query read them).  With the rerank on and a pool above top_k (option rerank_pool) the pipeline above runs
 // unchanged at top_k := pool into the workspace, with the diagnostics of that call, and k_rerank_pool writes the caller's top_k:
 // the pool's entries by (exact score, rank in the pool).  Every bound on top_k is then the inner call's, on `pool`.
 int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe,
@@ -379,7 +385,7 @@ int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq
         return rc;
     if (stage_probes()) return RBQ_OK; // (the four stages of the inner call are what a probe reports)
     RerankPoolParams P;
-    P.queries = d_queries; P.raw = ix->raw.p; P.raw_dtype = ix->raw_dtype; P.n_raw = ix->n_raw; P.nq = (uint32_t)nq; P.dim = ix->dim; P.metric = ix->metric;
+    P.queries = d_queries; P.query_dtype = ix->opt.query_dtype; P.raw = ix->raw.p; P.raw_dtype = ix->raw_dtype; P.n_raw = ix->n_raw; P.nq = (uint32_t)nq; P.dim = ix->dim; P.metric = ix->metric;
     P.pool = pool; P.top_k = top_k; P.pool_ids = (const uint64_t*)w->rr_ids.p; P.pool_counts = (const uint32_t*)w->rr_counts.p;
     P.out_ids = d_ids; P.out_scores = d_scores; P.out_counts = d_counts;
     HIP_TRY(launch_rerank_pool(P, ix->device, stream));
@@ -409,7 +415,8 @@ int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_d
     const std::vector<std::pair<uint64_t, uint64_t>> plan = rbq_host::subbatch_plan(nq, ix->opt.host_subbatch);
     const uint64_t nsub = plan.size();
     const uint32_t nlanes = (uint32_t)std::min<uint64_t>(nsub, ix->opt.host_lanes ? ix->opt.host_lanes : 6u);
-    const bool in_pinned = is_pinned_host_range(queries, nq * query_dim * 4);
+    const rbq_host::QueryRows qr = query_rows(ix, query_dim); // every byte length and row offset on the queries below is its arithmetic
+    const bool in_pinned = is_pinned_host_range(queries, qr.bytes(nq));
     bool out_pinned = !ix->rerank && is_pinned_host_range(out_ids, nq * top_k * 8) && is_pinned_host_range(out_scores, nq * top_k * 4) &&
                       is_pinned_host_range(out_counts, nq * 4) && (!diag || is_pinned_host_range(diag, nq * sizeof(rbq_diag)));
     // device-side addresses of page-locked caller buffers (identical under unified addressing; asked for, not assumed)
@@ -480,7 +487,7 @@ int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_d
     auto wait_staged = [&staged](uint64_t j) { spin_until([&] { return staged[j].load(std::memory_order_acquire) != 0; }); };
     struct WaitHelpers { decltype(wait_staged)& wait; uint64_t& n; // (no job may outlive this frame: it writes the flags)
         ~WaitHelpers() { for (uint64_t j = 1; j <= n; ++j) wait(j); } } wait_helpers{wait_staged, n_helped};
-    bool helpers = !in_pinned && ix->opt.host_stage_helpers && nsub >= 2 && nsub <= nlanes && nsub <= kMaxHelped && nq * query_dim * 4 >= (512u << 10);
+    bool helpers = !in_pinned && ix->opt.host_stage_helpers && nsub >= 2 && nsub <= nlanes && nsub <= kMaxHelped && qr.bytes(nq) >= (512u << 10);
     if (helpers) {
         // the helpers are published only once every thread of theirs runs (a half-started set used to stay installed, and
         // jobs posted to it could wait forever); if a thread cannot be created the call stages inline, like a small one does
@@ -495,9 +502,9 @@ int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_d
     if (helpers) {
         for (uint64_t j = 1; j < nsub; ++j) {
             Workspace* wj = lanes[j];
-            if ((rc = wj->h_in.ensure(plan[j].second * query_dim * 4))) return rc; // (jobs posted so far are awaited by wait_helpers)
+            if ((rc = wj->h_in.ensure(qr.bytes(plan[j].second)))) return rc; // (jobs posted so far are awaited by wait_helpers)
             staged[j].store(0, std::memory_order_relaxed);
-            ix->stagers->post(StageJob{wj->h_in.p, queries + plan[j].first * query_dim, (size_t)(plan[j].second * query_dim * 4), &staged[j]});
+            ix->stagers->post(StageJob{wj->h_in.p, qr.at(queries, plan[j].first), qr.bytes(plan[j].second), &staged[j]});
             n_helped = j;
         }
     }
@@ -507,32 +514,32 @@ int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_d
         const uint64_t q0 = plan[j].first, n = plan[j].second;
         const OutPack op(n, top_k, diag != nullptr);
         const bool staged_in_hbm = !(c_queries || (zero_copy && !in_pinned)); // an H2D copy into the lane's device buffer
-        if (staged_in_hbm && (rc = w->queries.ensure(n * query_dim * 4))) return rc;
-        const float* src = queries + q0 * query_dim;
+        if (staged_in_hbm && (rc = w->queries.ensure(qr.bytes(n)))) return rc;
+        const float* src = qr.at(queries, q0);
         tp = clk::now();
         const float* d_q = (const float*)w->queries.p; // where k_prep reads this sub-batch
         if (c_queries) {
-            d_q = c_queries + q0 * query_dim;
+            d_q = qr.at(c_queries, q0);
         } else if (zero_copy && !in_pinned) { // pageable: one host copy into the lane's pinned buffer, read from there
             if (j >= 1 && j <= n_helped) { // staged by a helper: wait for its copy
                 wait_staged(j);
             } else {
-                if ((rc = w->h_in.ensure(n * query_dim * 4))) return rc;
-                std::memcpy(w->h_in.p, src, n * query_dim * 4);
+                if ((rc = w->h_in.ensure(qr.bytes(n)))) return rc;
+                std::memcpy(w->h_in.p, src, qr.bytes(n));
             }
             float* hp = nullptr;
             HIP_TRY(hipHostGetDevicePointer((void**)&hp, w->h_in.p, 0));
             d_q = hp;
         } else if (in_pinned) {
-            HIP_TRY(hipMemcpyAsync(w->queries.p, src, n * query_dim * 4, hipMemcpyHostToDevice, w->stream));
+            HIP_TRY(hipMemcpyAsync(w->queries.p, src, qr.bytes(n), hipMemcpyHostToDevice, w->stream));
         } else if (j >= 1 && j <= n_helped) { // pageable, staged by a helper: wait for its copy, one DMA
             wait_staged(j);
-            HIP_TRY(hipMemcpyAsync(w->queries.p, w->h_in.p, n * query_dim * 4, hipMemcpyHostToDevice, w->stream));
+            HIP_TRY(hipMemcpyAsync(w->queries.p, w->h_in.p, qr.bytes(n), hipMemcpyHostToDevice, w->stream));
         } else {
-            if ((rc = w->h_in.ensure(n * query_dim * 4))) return rc;
+            if ((rc = w->h_in.ensure(qr.bytes(n)))) return rc;
             const uint64_t piece = std::max<uint64_t>(64, (n + 3) / 4); // queries per piece
             for (uint64_t p0 = 0; p0 < n; p0 += piece) {
-                const size_t off = p0 * query_dim * 4, len = std::min(piece, n - p0) * query_dim * 4;
+                const size_t off = qr.bytes(p0), len = qr.bytes(std::min(piece, n - p0));
                 std::memcpy((uint8_t*)w->h_in.p + off, (const uint8_t*)src + off, len);
                 HIP_TRY(hipMemcpyAsync((uint8_t*)w->queries.p + off, (const uint8_t*)w->h_in.p + off, len, hipMemcpyHostToDevice, w->stream));
             }
@@ -590,6 +597,7 @@ int rbq_search_batch_device(const rbq_index* ch, const float* d_queries, uint64_
     if (rc) return rc;
     if (nq == 0) return RBQ_OK;
     if (nq > 0x7fffffffull) return fail(RBQ_INVALID_CONFIG, "batch too large");
+    if ((rc = check_query_pointer(h, d_queries))) return rc;
     Replica* ix = replica_of_pointer(h, d_queries);
     DeviceGuard g(ix->device);
     if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
@@ -635,6 +643,7 @@ int rbq_search_batch(const rbq_index* ch, const float* queries, uint64_t nq, uin
         return RBQ_OK;
     }
     if (!queries || !out_ids || !out_scores || !out_counts) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    if ((rc = check_query_pointer(h, queries))) return rc;
     const size_t R = h->reps.size();
     if (R == 1 || nq < 2 * R) return search_host(h->reps[0], queries, nq, query_dim, top_k, nprobe, filter_words, filter_nbits, out_ids,
                                                   out_scores, out_counts, diag);
@@ -663,7 +672,7 @@ int rbq_search_batch(const rbq_index* ch, const float* queries, uint64_t nq, uin
         uint64_t q0, q1;
         rbq_host::shard_range(r, R, nq, &q0, &q1);
         try {
-            st->rcs[r] = search_host(h->reps[r], queries + q0 * query_dim, q1 - q0, query_dim, top_k, nprobe, filter_words, filter_nbits,
+            st->rcs[r] = search_host(h->reps[r], query_rows(h->reps[r], query_dim).at(queries, q0), q1 - q0, query_dim, top_k, nprobe, filter_words, filter_nbits,
                                      out_ids + q0 * top_k, out_scores + q0 * top_k, out_counts + q0, diag ? diag + q0 : nullptr);
         } catch (...) { st->rcs[r] = RBQ_IO; g_err = "internal error"; }
         st->details[r] = g_err; // thread-local in the worker

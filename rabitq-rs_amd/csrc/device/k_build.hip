@@ -121,16 +121,16 @@ hipError_t launch_hl_planes(const uint16_t* hl, uint64_t rows, uint32_t D, uint1
     hipLaunchKernelGGL(k_hl_planes, dim3((unsigned)((rows * D + 255) / 256)), dim3(256), 0, s, hl, rows, D, hi, lo);
     return hipGetLastError();
 }
-hipError_t launch_rerank(const float* queries, uint32_t nq, uint32_t dim, const void* raw, int raw_dtype, uint64_t n_raw, int metric,
+hipError_t launch_rerank(const void* queries, int query_dtype, uint32_t nq, uint32_t dim, const void* raw, int raw_dtype, uint64_t n_raw, int metric,
                          uint32_t top_k, uint64_t* ids, float* scores, const uint32_t* counts, hipStream_t s) {
     if (!nq) return hipSuccess;
     const size_t lds = (size_t)((dim + 1u) & ~1u) * 4 + (size_t)top_k * 16;
     if (raw_dtype == kRawF32)
-        hipLaunchKernelGGL(k_rerank<float>, dim3(nq), dim3(kThreads), lds, s, queries, dim, (const float*)raw, n_raw, metric, top_k, ids, scores, counts);
+        hipLaunchKernelGGL(k_rerank<float>, dim3(nq), dim3(kThreads), lds, s, queries, query_dtype, dim, (const float*)raw, n_raw, metric, top_k, ids, scores, counts);
     else if (raw_dtype == kRawF16)
-        hipLaunchKernelGGL(k_rerank<RawF16>, dim3(nq), dim3(kThreads), lds, s, queries, dim, (const RawF16*)raw, n_raw, metric, top_k, ids, scores, counts);
+        hipLaunchKernelGGL(k_rerank<RawF16>, dim3(nq), dim3(kThreads), lds, s, queries, query_dtype, dim, (const RawF16*)raw, n_raw, metric, top_k, ids, scores, counts);
     else if (raw_dtype == kRawBf16)
-        hipLaunchKernelGGL(k_rerank<RawBf16>, dim3(nq), dim3(kThreads), lds, s, queries, dim, (const RawBf16*)raw, n_raw, metric, top_k, ids, scores, counts);
+        hipLaunchKernelGGL(k_rerank<RawBf16>, dim3(nq), dim3(kThreads), lds, s, queries, query_dtype, dim, (const RawBf16*)raw, n_raw, metric, top_k, ids, scores, counts);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -18,42 +18,62 @@ namespace {
 uint32_t next_pow2(uint32_t x) { uint32_t p = 1; while (p < x) p <<= 1; return p; }
 } // namespace
 
-hipError_t launch_prep(const PrepParams& p, int device, hipStream_t s) {
+namespace {
+// the preparation kernels are templates on the element of the query rows: every instantiation has its own kernel address, hence its
+// own LDS-limit cache and its own identity under a stage probe
+template <typename QT>
+hipError_t launch_prep_of(const PrepParams& p, int device, hipStream_t s) {
+    const QT* queries = static_cast<const QT*>(p.queries);
     if (p.rotator == 0 /* matrix: O(D^2) per query */ || p.wg_prep) {
         static LdsAttrCache attr;
         const size_t lds = (size_t)p.D * 4 * 2;
-        if (probe_stage(0, reinterpret_cast<const void*>(&k_prep), dim3(p.nq), kThreads, lds)) return hipSuccess;
-        hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_prep), lds, device);
+        if (probe_stage(0, reinterpret_cast<const void*>(&k_prep<QT>), dim3(p.nq), kThreads, lds)) return hipSuccess;
+        hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_prep<QT>), lds, device);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_prep, dim3(p.nq), dim3(kThreads), lds, s, p.queries, p.dim, p.D, p.Dc, p.rotator, p.rot_blob, p.trunc,
+        hipLaunchKernelGGL(k_prep<QT>, dim3(p.nq), dim3(kThreads), lds, s, queries, p.dim, p.D, p.Dc, p.rotator, p.rot_blob, p.trunc,
                            p.fac, p.ex_bits, p.rot, p.lut, p.consts, p.rot_hl, p.rank_resid);
     } else { // FHT-Kac / identity: one wave per query
         static LdsAttrCache attr;
         const uint32_t qpw = kThreads / 64;
         const size_t lds = (size_t)p.D * 4 * 2 * qpw + p.D / 2;
-        if (probe_stage(0, reinterpret_cast<const void*>(&k_prep_wave), dim3((p.nq + qpw - 1) / qpw), kThreads, lds)) return hipSuccess;
-        hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_prep_wave), lds, device); // 66.5 KB at D = 2048
+        if (probe_stage(0, reinterpret_cast<const void*>(&k_prep_wave<QT>), dim3((p.nq + qpw - 1) / qpw), kThreads, lds)) return hipSuccess;
+        hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_prep_wave<QT>), lds, device); // 66.5 KB at D = 2048
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_prep_wave, dim3((p.nq + qpw - 1) / qpw), dim3(kThreads), lds, s, p.queries, p.nq, p.dim, p.D, p.Dc,
+        hipLaunchKernelGGL(k_prep_wave<QT>, dim3((p.nq + qpw - 1) / qpw), dim3(kThreads), lds, s, queries, p.nq, p.dim, p.D, p.Dc,
                            p.rotator, p.rot_blob, p.trunc, p.fac, p.ex_bits, p.rot, p.lut, p.consts, p.rot_hl, p.rank_resid);
     }
     return hipGetLastError();
 }
+template <typename QT>
+hipError_t launch_lat_front_of(const LatFrontParams& P, int device, hipStream_t s) {
+    static LdsAttrCache attr;
+    const dim3 grid(lat_front_grid(P.scorers, P.prep.nq));
+    const size_t lds = (size_t)P.prep.D * 4 * 2 + P.prep.D / 2;
+    if (probe_stage(0, reinterpret_cast<const void*>(&k_lat_front<QT>), grid, kThreads, lds)) return hipSuccess;
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_lat_front<QT>), lds, device);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_lat_front<QT>, grid, dim3(kThreads), lds, s, P);
+    return hipGetLastError();
+}
+} // namespace
+
+hipError_t launch_prep(const PrepParams& p, int device, hipStream_t s) {
+    if (p.query_dtype == kRawF16) return launch_prep_of<RawF16>(p, device, s);
+    if (p.query_dtype == kRawBf16) return launch_prep_of<RawBf16>(p, device, s);
+    if (p.query_dtype != kRawF32) return hipErrorInvalidValue;
+    return launch_prep_of<float>(p, device, s);
+}
 
 // latency-first front of a small call (latency.hpp): rotation + constants + LUT + the exact canonical score of every list, one launch
 hipError_t launch_lat_front(const PrepParams& p, const RankParams& r, int device, hipStream_t s) {
-    static LdsAttrCache attr;
     LatFrontParams P;
     P.prep = p; P.cent = r.cent; P.nlist = r.nlist; P.metric = r.metric; P.scores = r.scores;
     P.scorers = (r.scores && !r.ksplit) ? (r.nlist + kLatLists - 1) / kLatLists : 0u;
     P.zero_scores = r.ksplit > 1 ? r.scores : nullptr; // (split-K ranking GEMM behind this preparation: its parts are added to a zeroed row)
-    const dim3 grid(lat_front_grid(P.scorers, p.nq));
-    const size_t lds = (size_t)p.D * 4 * 2 + p.D / 2;
-    if (probe_stage(0, reinterpret_cast<const void*>(&k_lat_front), grid, kThreads, lds)) return hipSuccess;
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_lat_front), lds, device);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_lat_front, grid, dim3(kThreads), lds, s, P);
-    return hipGetLastError();
+    if (p.query_dtype == kRawF16) return launch_lat_front_of<RawF16>(P, device, s);
+    if (p.query_dtype == kRawBf16) return launch_lat_front_of<RawBf16>(P, device, s);
+    if (p.query_dtype != kRawF32) return hipErrorInvalidValue;
+    return launch_lat_front_of<float>(P, device, s);
 }
 
 hipError_t launch_rank_exact(const RankParams& p, hipStream_t s) {

@@ -168,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void k_rerank_pool(RerankPoolParams P) {
     uint32_t np2 = 1;
     while (np2 < cnt) np2 <<= 1; // <= np2(pool), what the launch sized the LDS for
     const uint64_t* pid = P.pool_ids + (size_t)q * P.pool;
-    for (uint32_t i = tid; i < dim; i += kThreads) sq[i] = P.queries[(size_t)q * dim + i];
+    copy_query_widened<kThreads>(sq, P.queries, P.query_dtype, (size_t)q * dim, dim, tid);
     for (uint32_t i = cnt + tid; i < np2; i += kThreads) key[i] = ~0ull; // (above every real key: those carry a rank < 4096)
     __syncthreads();
 

@@ -340,15 +340,32 @@ __device__ __forceinline__ void fht_lds(float* a, uint32_t n, uint32_t tid) {
     }
 }
 
+// Elements of a row of raw vectors as the rerank stores them, and of a query row as the caller passes it (RBQ_RAW_*; option
+// "query_dtype"): f32, or 16 bits that widen to an f32 exactly.
+struct RawF16 { uint16_t bits; };  // IEEE binary16
+struct RawBf16 { uint16_t bits; }; // the upper 16 bits of an f32
+__device__ __forceinline__ float raw_widen(float x) { return x; }
+__device__ __forceinline__ float raw_widen(RawF16 x) { return (float)__builtin_bit_cast(_Float16, x.bits); }
+__device__ __forceinline__ float raw_widen(RawBf16 x) { return __uint_as_float((uint32_t)x.bits << 16); }
+// n query elements from element `first` of `queries` (elements of dtype: the values of RBQ_RAW_*) into dst (LDS), widened, by the
+// GS threads of a group: the cold copy in front of the two rerank kernels (one runtime switch, outside the loops)
+template <int GS>
+__device__ __forceinline__ void copy_query_widened(float* dst, const void* queries, int dtype, size_t first, uint32_t n, uint32_t tid) {
+    if (dtype == kRawF16) { const RawF16* q = static_cast<const RawF16*>(queries) + first; for (uint32_t i = tid; i < n; i += GS) dst[i] = raw_widen(q[i]); }
+    else if (dtype == kRawBf16) { const RawBf16* q = static_cast<const RawBf16*>(queries) + first; for (uint32_t i = tid; i < n; i += GS) dst[i] = raw_widen(q[i]); }
+    else { const float* q = static_cast<const float*>(queries) + first; for (uint32_t i = tid; i < n; i += GS) dst[i] = q[i]; }
+}
+
 // Rotator::rotate_into for one vector, by GS threads (one workgroup or one wave): the rotated vector ends up in x[0..D)
 // (LDS); y[0..D) is scratch for the matrix rotator.  Butterflies/adds are the reference's, stage by stage
 // (src/rotation.rs:248-401), so the result is bit-identical to the CPU path.
-template <int GS>
-__device__ __forceinline__ void rotate_into_lds(float* x, float* y, const float* __restrict__ qin, uint32_t dim, uint32_t D,
+// QT: the element of the input row (float, RawF16, RawBf16), widened exactly as it is loaded.
+template <int GS, typename QT>
+__device__ __forceinline__ void rotate_into_lds(float* x, float* y, const QT* __restrict__ qin, uint32_t dim, uint32_t D,
                                                 int rotator, const uint8_t* __restrict__ rot_blob, uint32_t trunc,
                                                 float fac, uint32_t tid) {
     if (rotator == 1) { // FhtKacRotator::rotate_into
-        for (uint32_t i = tid; i < D; i += GS) x[i] = i < dim ? qin[i] : 0.0f;
+        for (uint32_t i = tid; i < D; i += GS) x[i] = i < dim ? raw_widen(qin[i]) : 0.0f;
         group_sync<GS>();
         const uint32_t fo = D / 8;
         if (trunc == D) {
@@ -383,10 +400,10 @@ __device__ __forceinline__ void rotate_into_lds(float* x, float* y, const float*
             group_sync<GS>();
         }
     } else if (rotator == 2) { // RBQ_ROTATOR_NONE: MSTG posting lists are quantised in the raw space
-        for (uint32_t i = tid; i < D; i += GS) x[i] = i < dim ? qin[i] : 0.0f;
+        for (uint32_t i = tid; i < D; i += GS) x[i] = i < dim ? raw_widen(qin[i]) : 0.0f;
         group_sync<GS>();
     } else { // MatrixRotator::rotate_into: sequential unfused accumulate per output row
-        for (uint32_t i = tid; i < D; i += GS) y[i] = i < dim ? qin[i] : 0.0f;
+        for (uint32_t i = tid; i < D; i += GS) y[i] = i < dim ? raw_widen(qin[i]) : 0.0f;
         group_sync<GS>();
         const float* M = reinterpret_cast<const float*>(rot_blob);
         for (uint32_t r = tid; r < D; r += GS) {
@@ -402,13 +419,6 @@ __device__ __forceinline__ void rotate_into_lds(float* x, float* y, const float*
     }
 
 }
-
-// Elements of a row of raw vectors as the rerank stores them (RBQ_RAW_*): f32, or 16 bits that widen to an f32 exactly.
-struct RawF16 { uint16_t bits; };  // IEEE binary16
-struct RawBf16 { uint16_t bits; }; // the upper 16 bits of an f32
-__device__ __forceinline__ float raw_widen(float x) { return x; }
-__device__ __forceinline__ float raw_widen(RawF16 x) { return (float)__builtin_bit_cast(_Float16, x.bits); }
-__device__ __forceinline__ float raw_widen(RawBf16 x) { return __uint_as_float((uint32_t)x.bits << 16); }
 
 // canonical single-pair reductions used for the second per-probe quantity (b: a row of f32, or of 16-bit elements widened on load)
 template <typename T>

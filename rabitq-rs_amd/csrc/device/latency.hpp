@@ -45,6 +45,7 @@ __host__ __device__ inline uint32_t lat_front_grid(uint32_t scorers, uint32_t nq
 }
 
 // dynamic LDS: x[D] f32 (the rotated query) | x2[D] f32 (its squares: the |q|^2 chain) | 4*D/8 flip bytes
+template <typename QT>
 __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) {
     extern __shared__ __align__(16) float sm[];
     __shared__ int s_kmin, s_kmax;
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(kThreads) void k_lat_front(const LatFrontParams P) 
     float* x = sm;
     float* x2 = sm + D;
     uint8_t* flips = reinterpret_cast<uint8_t*>(sm + (size_t)2 * D);
-    const float* qin = P.prep.queries + (size_t)q * P.prep.dim;
+    const QT* qin = static_cast<const QT*>(P.prep.queries) + (size_t)q * P.prep.dim;
     const uint32_t trunc = P.prep.trunc;
     PrepStamps ps;
     ps.mark(0);

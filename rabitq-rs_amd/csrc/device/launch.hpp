@@ -57,9 +57,10 @@ inline bool probe_stage(int stage, const void* fn, dim3 grid, uint32_t block, si
 }
 
 struct PrepParams {
-    const float* queries; // [nq][dim]
+    const void* queries;  // [nq][dim] elements of query_dtype
     uint32_t nq, dim, D, Dc;
     int rotator;
+    int query_dtype = kRawF32; // kRawF32 / kRawF16 / kRawBf16: picks the instantiation of the preparation kernel (host side only)
     const uint8_t* rot_blob;
     uint32_t trunc;
     float fac;
@@ -237,17 +238,16 @@ hipError_t launch_centroid_arrays(const float* cent, uint32_t nlist, uint32_t D,
 hipError_t launch_centroid_f16(const float* cent, uint32_t nlist, uint32_t D, uint16_t* img, float* resid, hipStream_t s);
 // the planar hi / lo planes [rows][D] of an interleaved split-bf16 image [rows][2 D] (hl_layout.hpp): debug option rank_planar
 hipError_t launch_hl_planes(const uint16_t* hl, uint64_t rows, uint32_t D, uint16_t* hi, uint16_t* lo, hipStream_t s);
-// element type of the attached raw rows: the values of RBQ_RAW_* (rbq.h); a 16-bit element widens to an f32 exactly
-constexpr int kRawF32 = 0, kRawF16 = 1, kRawBf16 = 2;
-constexpr size_t raw_elem_bytes(int raw_dtype) { return raw_dtype == kRawF32 ? 4 : 2; }
+// (kRawF32 / kRawF16 / kRawBf16, the element types of the raw rows and of the query rows: types.hpp)
 // exact re-scoring of the returned ids against caller-supplied raw vectors (optional rerank, default off)
-hipError_t launch_rerank(const float* queries, uint32_t nq, uint32_t dim, const void* raw, int raw_dtype, uint64_t n_raw, int metric,
+// (queries: [nq][dim] elements of query_dtype, widened as they are copied into LDS)
+hipError_t launch_rerank(const void* queries, int query_dtype, uint32_t nq, uint32_t dim, const void* raw, int raw_dtype, uint64_t n_raw, int metric,
                          uint32_t top_k, uint64_t* ids, float* scores, const uint32_t* counts, hipStream_t s);
 // pooled rerank (option rerank_pool; k_rerank_pool.hip): the exact scores of a query's pool of candidates
 // (the result of the search at top_k := pool), ordered by (exact score, rank in the pool); the first top_k are the answer
 constexpr uint32_t kRerankPoolMax = 4096; // one workgroup orders a query's pool in LDS (the figure of kMrPoolMax, for its reason)
 struct RerankPoolParams {
-    const float* queries;        // [nq][dim], input space
+    const void* queries;         // [nq][dim] elements of query_dtype, input space
     const void* raw;             // [n_raw][dim] elements of raw_dtype
     uint64_t n_raw;
     uint32_t nq, dim, metric;
@@ -258,6 +258,7 @@ struct RerankPoolParams {
     float* out_scores;           // [nq][top_k]
     uint32_t* out_counts;        // [nq]
     int raw_dtype = kRawF32;     // kRawF32 / kRawF16 / kRawBf16
+    int query_dtype = kRawF32;   // the same values: what `queries` holds
     uint32_t raw_by_element = 0; // set by the launch: 16-bit rows that do not all start 4-byte aligned (odd dim, or raw at 2 mod 4)
 };
 size_t rerank_pool_lds_bytes(uint32_t dim, uint32_t pool);

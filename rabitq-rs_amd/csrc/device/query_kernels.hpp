@@ -1,6 +1,6 @@
 // query_kernels.hpp — the kernels of the query stages in front of the scan that are not templates on the GEMM shape:
 // k_prep / k_prep_wave (rotate + constants + LUT) and k_rank_scores (the all-pairs canonical ranking kept as the exact_rank option;
-// its selection, k_select, is in select_given.hpp).  Included by k_query.hip only (non-template __global__ functions: one definition).
+// its selection, k_select, is in select_given.hpp).  Included by k_query.hip only.
 //
 // Query preparation has three kernels: k_prep and k_prep_wave here, k_lat_front in latency.hpp.  What they compute is ONE copy of
 // device functions — rotate_by_wave, store_rotated (the rotated query, its GEMM image, the f16 residual), lut_entries,
@@ -131,24 +131,63 @@ __device__ __forceinline__ void fht_wave(float* part, uint32_t lane, float fac, 
 // the rotation was 17 of the 27 us of a single query's preparation.
 // The initial load (with round 0's flips unless the dimension is a power of two) — a separate step so that the caller can issue
 // it BEFORE the barrier behind the copy of the flip bits into LDS: `flips0` may be the global table.
-__device__ __forceinline__ void fhtkac_initial_load(float* x, const float* __restrict__ qin, uint32_t dim, uint32_t D, uint32_t trunc,
+// QT: the element of the query row (float, RawF16, RawBf16: kernels.hpp).  16-bit rows: a row that starts
+// 4-byte aligned is loaded two adjacent elements per 32-bit load (fhtkac_initial_load_pairs); a row that starts 2-byte aligned only
+// (odd dim, a base offset by one element) keeps the loop below with one 16-bit load per element.  Same values into the same x[i].
+template <typename QT>
+__device__ __forceinline__ void fhtkac_initial_load_pairs(float* x, const QT* __restrict__ qin, uint32_t dim, uint32_t D, uint32_t trunc,
+                                                          const uint8_t* __restrict__ flips0, uint32_t lane) {
+    // lane l owns the element pairs (2l, 2l + 1) + 128 u: eight 32-bit loads are requested before the first LDS write, as below, and
+    // cover 1024 elements; the writes are 8 bytes per lane at a stride of 8 bytes — conflict-free.  D is even, so a pair never
+    // straddles D; it can straddle dim (odd dim): that last element is loaded alone, nothing behind the row is read.
+    constexpr int KU = 8;
+    for (uint32_t i0 = 2u * lane; i0 < D; i0 += 128 * KU) {
+        uint32_t w[KU], f[KU];
+#pragma unroll
+        for (int u = 0; u < KU; ++u) {
+            const uint32_t i = i0 + 128u * u;
+            w[u] = i + 1 < dim ? *reinterpret_cast<const uint32_t*>(qin + i) : (i < dim ? (uint32_t)qin[i].bits : 0u);
+            f[u] = (trunc != D && i < D) ? (uint32_t)flips0[i >> 3] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < KU; ++u) {
+            const uint32_t i = i0 + 128u * u;
+            if (i < D) {
+                const float a = raw_widen(QT{(uint16_t)(w[u] & 0xffffu)}), b = raw_widen(QT{(uint16_t)(w[u] >> 16)});
+                const uint32_t fb = f[u] >> (i & 7u); // (i is even: both bits lie in the one byte)
+                *reinterpret_cast<float2*>(x + i) = make_float2((fb & 1u) ? -a : a, (fb & 2u) ? -b : b);
+            }
+        }
+    }
+}
+template <typename QT>
+__device__ __forceinline__ void fhtkac_initial_load(float* x, const QT* __restrict__ qin, uint32_t dim, uint32_t D, uint32_t trunc,
                                                     const uint8_t* __restrict__ flips0, uint32_t lane) {
+    if constexpr (sizeof(QT) == 2) { // (uniform over the wave: one query per wave)
+        if ((reinterpret_cast<uintptr_t>(qin) & 3u) == 0) return fhtkac_initial_load_pairs(x, qin, dim, D, trunc, flips0, lane);
+    }
     // eight elements per lane are REQUESTED before the first is written to LDS: as a plain loop hipcc waited for every load in front
     // of its ds_write — D / 64 dependent global round trips (15 at D = 960) at the head of every query's preparation (round 5)
     constexpr int KU = 8;
     for (uint32_t i0 = lane; i0 < D; i0 += 64 * KU) {
-        float v[KU];
+        QT v[KU];
         uint32_t f[KU];
 #pragma unroll
         for (int u = 0; u < KU; ++u) {
             const uint32_t i = i0 + 64u * u;
-            v[u] = i < dim ? qin[i] : 0.0f; // (dim <= D)
+            // (dim <= D)  16-bit rows: the load itself is unguarded — a lane beyond dim reads element 0 of its row and drops it below.
+            // Behind a guard the compiler sinks the widening into the guarded block and waits there for every single load: eight
+            // dependent round trips per round, what this function exists to avoid (seen in the ISA)
+            if constexpr (sizeof(QT) == 2) v[u] = qin[i < dim ? i : 0u];
+            else v[u] = i < dim ? qin[i] : QT{};
             f[u] = (trunc != D && i < D) ? (uint32_t)flips0[i >> 3] : 0u;
         }
 #pragma unroll
         for (int u = 0; u < KU; ++u) {
             const uint32_t i = i0 + 64u * u;
-            if (i < D) x[i] = ((f[u] >> (i & 7u)) & 1u) ? -v[u] : v[u];
+            float w = raw_widen(v[u]);
+            if constexpr (sizeof(QT) == 2) w = i < dim ? w : 0.0f;
+            if (i < D) x[i] = ((f[u] >> (i & 7u)) & 1u) ? -w : w;
         }
     }
 }
@@ -215,7 +254,8 @@ __device__ __forceinline__ void lut_entries(const float* x4, float (&l)[16]) {
 
 // DynamicRotator::rotate (src/rotation.rs:350-401) of the query at x (LDS) by ONE wave, for the FHT-Kac (`flips`: the LDS copy of its
 // flip bits; the caller has run fhtkac_initial_load) and the identity rotator
-__device__ __forceinline__ void rotate_by_wave(float* x, const float* qin, uint32_t dim, uint32_t D, int rotator, const uint8_t* rot_blob,
+template <typename QT>
+__device__ __forceinline__ void rotate_by_wave(float* x, const QT* qin, uint32_t dim, uint32_t D, int rotator, const uint8_t* rot_blob,
                                                const uint8_t* flips, uint32_t trunc, float fac, uint32_t lane) {
     if (rotator == 1) {
         switch (trunc) {
@@ -326,7 +366,10 @@ __device__ __forceinline__ QueryConsts query_consts(uint32_t amin, uint32_t amax
 // (so q1norm, exlo and exhi differ from the other two kernels' in the last bits); each thread keeps the entries of its (at most two)
 // codebooks in registers across the barrier behind the range; ranges and u8 sums meet through LDS atomics.
 // dynamic LDS: 2 x D floats (vector | matrix rotator input)
-__global__ __launch_bounds__(kThreads) void k_prep(const float* __restrict__ queries, uint32_t dim, uint32_t D,
+// QT (here and in k_prep_wave, k_lat_front): the element of the query rows, widened where the rotation loads it; nothing behind the
+// rotation's input sees it
+template <typename QT>
+__global__ __launch_bounds__(kThreads) void k_prep(const QT* __restrict__ queries, uint32_t dim, uint32_t D,
                                                    uint32_t Dc, int rotator, const uint8_t* __restrict__ rot_blob,
                                                    uint32_t trunc, float fac, uint32_t ex_bits,
                                                    float* __restrict__ rot_out, uint8_t* __restrict__ lut_out,
@@ -340,7 +383,7 @@ __global__ __launch_bounds__(kThreads) void k_prep(const float* __restrict__ que
     __shared__ unsigned int s_amin, s_amax;
     __shared__ float s_sum, s_n2, s_pos, s_neg;
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    const float* qin = queries + (size_t)q * dim;
+    const QT* qin = queries + (size_t)q * dim;
     PrepStamps ps;
     ps.mark(0);
 
@@ -420,7 +463,8 @@ __global__ __launch_bounds__(kThreads) void k_prep(const float* __restrict__ que
 // negative sums are taken strided per lane in the pass that writes the query and reduced by a xor tree, as are the range and the u8
 // sums; the two strictly sequential sums (sum q, |q|^2: Rust iter().sum()) run side by side on lanes 0 and 1, 16 elements per step.
 // dynamic LDS: 4 x 2 x D floats (vector + squares per wave) | 4*D/8 flip bytes
-__global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict__ queries, uint32_t nq, uint32_t dim, uint32_t D,
+template <typename QT>
+__global__ __launch_bounds__(kThreads) void k_prep_wave(const QT* __restrict__ queries, uint32_t nq, uint32_t dim, uint32_t D,
                                                         uint32_t Dc, int rotator, const uint8_t* __restrict__ rot_blob,
                                                         uint32_t trunc, float fac, uint32_t ex_bits,
                                                         float* __restrict__ rot_out, uint8_t* __restrict__ lut_out,
@@ -434,7 +478,7 @@ __global__ __launch_bounds__(kThreads) void k_prep_wave(const float* __restrict_
     ps.mark(0);
     float* x = sm + (size_t)wave * 2 * D;
     float* x2 = x + D; // squares, for the |q|^2 chain
-    const float* qin = queries + (size_t)q * dim;
+    const QT* qin = queries + (size_t)q * dim;
     const bool wave_fht = rotator == 1 && trunc >= 64 && trunc <= 2048; // (else the generic LDS butterflies)
     if (rotator == 1) {
         for (uint32_t i = threadIdx.x; i < D / 8; i += kThreads) reinterpret_cast<uint32_t*>(flips)[i] = reinterpret_cast<const uint32_t*>(rot_blob)[i]; // (4 D / 8 flip bytes as dwords: one trip)

@@ -178,7 +178,7 @@ __global__ void k_chunk_advance(const uint32_t* __restrict__ sorted_list, uint32
 // top_k (<= 1024 here) results re-sorted by (exact score, position) — ascending distance for L2, descending for IP.
 // T: the element of a raw row (float, RawF16, RawBf16: kernels.hpp); a 16-bit element is widened exactly as it is loaded.
 template <typename T>
-__global__ __launch_bounds__(kThreads) void k_rerank(const float* __restrict__ queries, uint32_t dim, const T* __restrict__ raw,
+__global__ __launch_bounds__(kThreads) void k_rerank(const void* __restrict__ queries, int query_dtype, uint32_t dim, const T* __restrict__ raw,
                                                      uint64_t n_raw, int metric, uint32_t top_k, uint64_t* __restrict__ ids,
                                                      float* __restrict__ scores, const uint32_t* __restrict__ counts) {
     extern __shared__ __align__(16) unsigned char smraw[];
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void k_rerank(const float* __restrict__ q
     unsigned long long* idv = key + top_k;                                // [top_k]
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
     const uint32_t cnt = counts[q] < top_k ? counts[q] : top_k;
-    for (uint32_t i = tid; i < dim; i += kThreads) sq[i] = queries[(size_t)q * dim + i];
+    copy_query_widened<kThreads>(sq, queries, query_dtype, (size_t)q * dim, dim, tid); // (query elements of query_dtype: RBQ_RAW_*)
     __syncthreads();
     for (uint32_t i = tid; i < cnt; i += kThreads) {
         const uint64_t id = ids[(size_t)q * top_k + i];

@@ -11,6 +11,10 @@
 namespace rbq {
 
 constexpr int kThreads = 256;
+// element type of the attached raw rows and of a call's query rows: the values of RBQ_RAW_* (rbq.h); a 16-bit element widens to
+// an f32 exactly
+constexpr int kRawF32 = 0, kRawF16 = 1, kRawBf16 = 2;
+constexpr size_t raw_elem_bytes(int raw_dtype) { return raw_dtype == kRawF32 ? 4 : 2; }
 
 // numeric variants (RBQ_NUMERIC_* of rbq.h; kernels.hpp says what each reproduces)
 enum : int { kVarAvx512 = 0, kVarAvx2 = 1, kVarPortable = 2 };

@@ -297,6 +297,20 @@ struct OutPack {
     }
 };
 
+// The query rows of a search call as the entry points take them (option "query_dtype": RBQ_RAW_F32, or RBQ_RAW_F16 / RBQ_RAW_BF16 —
+// rows of `dim` 16-bit elements, 2 * dim bytes apart, behind the `const float*` parameter).  THE copy of the byte arithmetic on
+// query rows: lengths of copies and staging buffers, and the first byte of query q (of a sub-batch, a shard, a chunk).
+struct QueryRows {
+    int dtype = RBQ_RAW_F32;
+    uint32_t dim = 0;
+    size_t elem_bytes() const { return dtype == RBQ_RAW_F32 ? 4 : 2; }
+    size_t row_bytes() const { return (size_t)dim * elem_bytes(); }
+    size_t bytes(uint64_t n) const { return (size_t)n * row_bytes(); } // n whole rows
+    const float* at(const float* base, uint64_t q) const { return (const float*)((const uint8_t*)base + bytes(q)); } // row q
+    // whether `p` may hold such rows: 16-bit rows need a 2-byte aligned base (f32 rows: as ever, not looked at)
+    bool aligned(const void* p) const { return dtype == RBQ_RAW_F32 || ((uintptr_t)p & 1u) == 0; }
+};
+
 // replica r of R serves the contiguous query shard [q0, q1) of a batch of nq (batch_search is a par_iter over queries)
 inline void shard_range(uint64_t r, uint64_t R, uint64_t nq, uint64_t* q0, uint64_t* q1) { *q0 = r * nq / R; *q1 = (r + 1) * nq / R; }
 

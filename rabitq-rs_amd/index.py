@@ -1,4 +1,5 @@
 """`IvfRabitqIndex` query façade over the C ABI (include/rbq.h)."""
+import contextlib
 import ctypes as C
 import os
 
@@ -354,35 +355,99 @@ class IvfRabitqIndex:
         return lib().rbq_index_padded_dim(self._h)
 
     # -- queries ------------------------------------------------------------------
-    def batch_search_raw(self, queries, params, filter_words=None, filter_nbits=0, want_diag=False):
-        """Returns (ids[nq,k] u64, scores[nq,k] f32, counts[nq] u32, diag[nq,3] u64|None)."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
+    def batch_search_raw(self, queries, params, filter_words=None, filter_nbits=0, want_diag=False, dtype=None):
+        """Returns (ids[nq,k] u64, scores[nq,k] f32, counts[nq] u32, diag[nq,3] u64|None).
+        `queries`: f32 rows, or 16-bit rows read as they are (option "query_dtype", set for this call): a numpy.float16 array, a
+        torch.half / torch.bfloat16 tensor, or a numpy.uint16 array of bit patterns with dtype="f16" | "bf16" (_marshal.query_arg).
+        A CUDA tensor takes rbq_search_batch_device on the current stream; the arrays come back on the host either way."""
+        q, code = _marshal.query_arg(queries, dtype)
         if q.ndim == 1:
             q = q[None, :]
         nq, qd = q.shape
         k = params.top_k
+        fw = np.ascontiguousarray(filter_words, dtype=np.uint32) if filter_words is not None else None
+        if _marshal.on_device(q):
+            return self._search_device_tensor(q, code, k, params.nprobe, fw, filter_nbits, want_diag)
         ids = np.empty((nq, k), np.uint64)
         scores = np.empty((nq, k), np.float32)
         counts = np.zeros(nq, np.uint32)
         diag = np.zeros((nq, 3), np.uint64) if want_diag else None
-        fw = np.ascontiguousarray(filter_words, dtype=np.uint32) if filter_words is not None else None
-        rc = lib().rbq_search_batch(self._h, q.ctypes.data, nq, qd, k, params.nprobe,
-                                    fw.ctypes.data if fw is not None else None, filter_nbits,
-                                    ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
-                                    diag.ctypes.data if diag is not None else None)
+        with self._query_dtype_for_call(code):
+            rc = lib().rbq_search_batch(self._h, _marshal.data_ptr(q), nq, qd, k, params.nprobe,
+                                        fw.ctypes.data if fw is not None else None, filter_nbits,
+                                        ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
+                                        diag.ctypes.data if diag is not None else None)
         _check(rc)
         return ids, scores, counts, diag
+
+    def _search_device_tensor(self, q, code, k, nprobe, fw, filter_nbits, want_diag):
+        """batch_search_raw for a CUDA tensor: the device entry on the tensor's current stream, results copied to the host."""
+        import torch
+        nq, qd = q.shape
+        with torch.cuda.device(q.device):
+            ids = torch.empty((nq, max(k, 1)), dtype=torch.int64, device=q.device)
+            sc = torch.empty((nq, max(k, 1)), dtype=torch.float32, device=q.device)
+            cnt = torch.zeros(nq, dtype=torch.int32, device=q.device)
+            dg = torch.zeros((nq, 3), dtype=torch.int64, device=q.device) if want_diag else None
+            dfw = torch.from_numpy(fw.view(np.int32)).to(q.device) if fw is not None else None
+            st = torch.cuda.current_stream()
+            with self._query_dtype_for_call(code):
+                self.search_batch_device(q.data_ptr(), nq, qd, k, nprobe, ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(),
+                                         stream=C.c_void_p(st.cuda_stream), d_filter=dfw.data_ptr() if dfw is not None else None,
+                                         filter_nbits=filter_nbits, d_diag=dg.data_ptr() if dg is not None else None)
+            st.synchronize()
+        return (ids.cpu().numpy().view(np.uint64)[:, :k], sc.cpu().numpy()[:, :k], cnt.cpu().numpy().view(np.uint32),
+                dg.cpu().numpy().view(np.uint64) if dg is not None else None)
+
+    # -- 16-bit queries (option "query_dtype", DESIGN.md section 30) ------------------------------------------------------
+    def set_query_dtype(self, dtype):
+        """What every entry point of this handle reads its query pointer as from now on: "f32" (default), "f16" or "bf16" (or
+        RBQ_RAW_*) - rows of `dim` elements, 2 * dim bytes apart for the 16-bit types, widened exactly where a kernel loads
+        them.  For callers that pass raw pointers (search_batch_device, range_search_device, the device entries of MSTG); the
+        array-taking methods set it for the call from the array's own type and put this value back.  None: "f32"."""
+        if dtype is None:
+            dtype = _abi.RAW_F32
+        if isinstance(dtype, str):
+            if dtype not in _abi.RAW_DTYPES:
+                from . import RabitqError
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "unknown query dtype %r (one of %s)" % (dtype, ", ".join(_abi.RAW_DTYPES)))
+            dtype = _abi.RAW_DTYPES[dtype]
+        self.set_option("query_dtype", int(dtype))
+
+    def _query_dtype_code(self):
+        v = C.c_int32(-1)
+        _check(lib().rbq_debug_copy_index(self._h, b"query_dtype", C.byref(v), 4))
+        return int(v.value)
+
+    def query_dtype(self):
+        """"f32" / "f16" / "bf16": the option "query_dtype" as the handle holds it."""
+        return {i: n for n, i in _abi.RAW_DTYPES.items()}[self._query_dtype_code()]
+
+    @contextlib.contextmanager
+    def _query_dtype_for_call(self, code):
+        """Context of one call whose queries are of type `code`: the option is set where it differs from what the HANDLE holds
+        (read back from it: set_option("query_dtype", ...) and set_query_dtype are one and the same to this) and the handle's
+        value put back afterwards, error or not.  f32 input on a handle at f32 makes no option call."""
+        before = self._query_dtype_code()
+        if code == before:
+            yield
+            return
+        self.set_option("query_dtype", code)
+        try:
+            yield
+        finally:
+            self.set_option("query_dtype", before)
 
     def _results(self, ids, scores, counts, q):
         from . import SearchResult
         return [SearchResult(int(ids[q, i]), float(scores[q, i])) for i in range(int(counts[q]))]
 
-    def search(self, query, params):
+    def search(self, query, params, dtype=None):
         """`IvfRabitqIndex::search` (src/ivf.rs:1705-1711)."""
-        ids, scores, counts, _ = self.batch_search_raw(np.asarray(query, np.float32)[None, :], params)
+        ids, scores, counts, _ = self.batch_search_raw(query, params, dtype=dtype)
         return self._results(ids, scores, counts, 0)
 
-    def search_filtered(self, query, params, allowed_ids):
+    def search_filtered(self, query, params, allowed_ids, dtype=None):
         """`search_filtered` (src/ivf.rs:1723-1730); `allowed_ids` plays the RoaringBitmap."""
         allowed = np.asarray(sorted(set(int(i) for i in allowed_ids)), dtype=np.uint64)
         nbits = int(allowed.max()) + 1 if allowed.size else 0
@@ -390,38 +455,43 @@ class IvfRabitqIndex:
         if allowed.size:
             np.bitwise_or.at(words, (allowed >> np.uint64(5)).astype(np.int64),
                              (np.uint32(1) << (allowed & np.uint64(31)).astype(np.uint32)))
-        ids, scores, counts, _ = self.batch_search_raw(np.asarray(query, np.float32)[None, :], params,
-                                                       words, nbits)
+        ids, scores, counts, _ = self.batch_search_raw(query, params, words, nbits, dtype=dtype)
         return self._results(ids, scores, counts, 0)
 
-    def batch_search(self, queries, params):
+    def batch_search(self, queries, params, dtype=None):
         """`batch_search` (src/ivf.rs:1743-1752): per-query results in input order."""
-        ids, scores, counts, _ = self.batch_search_raw(queries, params)
+        ids, scores, counts, _ = self.batch_search_raw(queries, params, dtype=dtype)
         return [self._results(ids, scores, counts, q) for q in range(ids.shape[0])]
 
-    def batch_query(self, queries, top_k, nprobe):
+    def batch_query(self, queries, top_k, nprobe, dtype=None):
         """Python-binding shape of the reference (`batch_query`, src/python_bindings.rs:593-665):
         list of (k,2) f32 arrays [id, score] (ids cast to f32 exactly as the reference does)."""
         from . import SearchParams
-        ids, scores, counts, _ = self.batch_search_raw(queries, SearchParams(top_k, nprobe))
+        ids, scores, counts, _ = self.batch_search_raw(queries, SearchParams(top_k, nprobe), dtype=dtype)
         out = []
         for q in range(ids.shape[0]):
             c = int(counts[q])
             out.append(np.stack([ids[q, :c].astype(np.float32), scores[q, :c]], axis=1))
         return out
 
-    def posting_scan(self, queries, top_k, list_ids, list_counts):
+    def posting_scan(self, queries, top_k, list_ids, list_counts, dtype=None):
         """MSTG posting-list scan (reference src/mstg/index.rs:149-330): the caller has already chosen each
-        query's posting lists. Returns (ids[nq,k] u64, distances[nq,k] f32 ascending, counts[nq] u32)."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
+        query's posting lists. Returns (ids[nq,k] u64, distances[nq,k] f32 ascending, counts[nq] u32).
+        `queries` (host) and `dtype` as batch_search_raw."""
+        from . import RabitqError
+        q, code = _marshal.query_arg(queries, dtype)
+        if _marshal.on_device(q):
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "posting_scan takes host queries")
         li = np.ascontiguousarray(list_ids, dtype=np.uint32)
         lc = np.ascontiguousarray(list_counts, dtype=np.uint32)
         nq, qd = q.shape
         ids = np.empty((nq, top_k), np.uint64)
         scores = np.empty((nq, top_k), np.float32)
         counts = np.zeros(nq, np.uint32)
-        _check(lib().rbq_posting_scan_batch(self._h, q.ctypes.data, nq, qd, top_k, li.ctypes.data, lc.ctypes.data,
-                                            li.shape[1], ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        with self._query_dtype_for_call(code):
+            rc = lib().rbq_posting_scan_batch(self._h, _marshal.data_ptr(q), nq, qd, top_k, li.ctypes.data, lc.ctypes.data,
+                                              li.shape[1], ids.ctypes.data, scores.ctypes.data, counts.ctypes.data)
+        _check(rc)
         return ids, scores, counts
 
     # -- device-pointer entry (bench / torch interop) --------------------------------
@@ -470,23 +540,24 @@ class IvfRabitqIndex:
                 out_sc[lims[q]:lims[q + 1]] = out_sc[lims[q]:lims[q + 1]][o]
         return lims, out_ids, out_sc
 
-    def range_search(self, queries, radius, nprobe, max_results=None, allowed_ids=None, want_diag=False, sort=False):
+    def range_search(self, queries, radius, nprobe, max_results=None, allowed_ids=None, want_diag=False, sort=False, dtype=None):
         """FAISS-style range_search over the probed lists: (lims [nq + 1] i64, ids u64, scores f32) — query q's matches are
         ids[lims[q]:lims[q + 1]], in scan order, or ascending by (score, scan order) with sort=True.  A match has distance <
         radius (L2) or score > radius (inner product).  max_results=None: complete rows (a first call with rows of 1024; where
         a total exceeds that, one more with rows of the largest total — the totals are exact, so one repeat suffices).
         max_results=m: at most the first m matches of every query, and the totals [nq] u32 as a fourth value.  want_diag: the
         SearchDiagnostics [nq, 3] u64 as the last value.  `allowed_ids` as search_filtered.  The handle's range options are
-        set for the call and put back afterwards."""
+        set for the call and put back afterwards.  `queries` and `dtype` as batch_search_raw."""
         from . import SearchParams
+        queries, dtype = _marshal.query_arg(queries, dtype)
         words, nbits = self._filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
         cap = max_results or 1024
         before = getattr(self, "_range", None)
         self.set_range_search(radius)
         try:
-            ids, sc, cnt, diag = self.batch_search_raw(queries, SearchParams(cap, nprobe), words, nbits, want_diag)
+            ids, sc, cnt, diag = self.batch_search_raw(queries, SearchParams(cap, nprobe), words, nbits, want_diag, dtype)
             if max_results is None and cnt.size and int(cnt.max()) > cap:
-                ids, sc, cnt, diag = self.batch_search_raw(queries, SearchParams(int(cnt.max()), nprobe), words, nbits, want_diag)
+                ids, sc, cnt, diag = self.batch_search_raw(queries, SearchParams(int(cnt.max()), nprobe), words, nbits, want_diag, dtype)
         finally:
             self.set_range_search(before)
         out = self._range_csr(ids, sc, cnt, sort)

@@ -219,7 +219,7 @@ def search_fallbacks():
 REFINE_POOL_MAX = _abi.MSTG_REFINE_POOL_MAX
 
 
-def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, return_lists=False, refine_pool=None):
+def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, return_lists=False, refine_pool=None, dtype=None):
     """`MstgIndex::batch_search` on an MSTG handle (rotator NoRotation, e.g. from build_postings_on_device) in one call:
     (ids [nq][top_k] u64, distances [nq][top_k] f32 ascending, counts [nq] u32), plus (lists, list_counts) of the selected
     posting lists in scan order with `return_lists`.  NumPy queries take rbq_mstg_search_batch and return arrays; a CUDA tensor
@@ -228,7 +228,11 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
 
     `refine_pool=None` is the crate's search: 1-bit estimates, and an id may come back once per list that holds it.  An int takes
     rbq_mstg_search_refined_batch*: the max(refine_pool, top_k) best binary candidates are re-scored with the stored ex codes,
-    reduced to one entry per id and the top_k nearest returned (at most REFINE_POOL_MAX candidates)."""
+    reduced to one entry per id and the top_k nearest returned (at most REFINE_POOL_MAX candidates).
+
+    Queries of 16 bits (a numpy.float16 array, a torch.half / torch.bfloat16 tensor, a numpy.uint16 array of bit patterns with
+    dtype="f16" | "bf16") are read as they are: the handle's option "query_dtype" is set for the call and put back afterwards."""
+    from . import _marshal
     from .index import _check, lib
     top_k, ef_search = int(top_k), int(ef_search)
     L = lib()
@@ -237,9 +241,9 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
     else:
         host_fn, dev_fn, extra = L.rbq_mstg_search_refined_batch, L.rbq_mstg_search_refined_batch_device, (int(refine_pool),)
     ef = min(max(ef_search, 0), index.cluster_count())
-    torch = torch_of(queries)
-    if torch is not None and queries.is_cuda:
-        q = queries.to(dtype=torch.float32).contiguous()
+    q, code = _marshal.query_arg(queries, dtype)
+    torch = torch_of(q)
+    if torch is not None and q.is_cuda:
         nq, qd = q.shape
         with torch.cuda.device(q.device):
             ids = torch.empty((nq, top_k), dtype=torch.int64, device=q.device)
@@ -248,21 +252,24 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
             li = torch.empty((nq, ef), dtype=torch.int32, device=q.device) if return_lists else None
             lc = torch.empty(nq, dtype=torch.int32, device=q.device) if return_lists else None
             stream = torch.cuda.current_stream().cuda_stream
-            _check(dev_fn(index._h, q.data_ptr(), nq, qd, top_k, ef_search, float(pruning_epsilon), *extra,
-                          ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(),
-                          li.data_ptr() if return_lists else None, lc.data_ptr() if return_lists else None,
-                          C.c_void_p(stream)))
+            with index._query_dtype_for_call(code):
+                rc = dev_fn(index._h, q.data_ptr(), nq, qd, top_k, ef_search, float(pruning_epsilon), *extra,
+                            ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(),
+                            li.data_ptr() if return_lists else None, lc.data_ptr() if return_lists else None,
+                            C.c_void_p(stream))
+            _check(rc)
         return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
-    q = _host_f32(queries)
     nq, qd = q.shape
     ids = np.empty((nq, top_k), np.uint64)
     sc = np.empty((nq, top_k), np.float32)
     cnt = np.zeros(nq, np.uint32)
     li = np.empty((nq, ef), np.uint32) if return_lists else None
     lc = np.empty(nq, np.uint32) if return_lists else None
-    _check(host_fn(index._h, q.ctypes.data, nq, qd, top_k, ef_search, float(pruning_epsilon), *extra, ids.ctypes.data,
-                   sc.ctypes.data, cnt.ctypes.data, li.ctypes.data if return_lists else None,
-                   lc.ctypes.data if return_lists else None))
+    with index._query_dtype_for_call(code):
+        rc = host_fn(index._h, _marshal.data_ptr(q), nq, qd, top_k, ef_search, float(pruning_epsilon), *extra, ids.ctypes.data,
+                     sc.ctypes.data, cnt.ctypes.data, li.ctypes.data if return_lists else None,
+                     lc.ctypes.data if return_lists else None)
+    _check(rc)
     return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
 
 
@@ -444,21 +451,26 @@ class MstgIndex:
             raise RuntimeError("Index not built yet. Call fit() first.")
         return self.handle
 
-    def batch_query(self, queries, k):
+    def batch_query(self, queries, k, dtype=None):
+        """`queries` [N][D]: f32, or 16-bit rows read as they are (mstg_search's `queries` and `dtype`; host arrays or tensors)."""
+        from . import _marshal
         h = self._built()
-        q = _host_f32(queries)
+        q, dtype = _marshal.query_arg(queries, dtype)
+        if _marshal.torch_of(q) is not None and q.is_cuda:
+            raise ValueError("Queries must be on the host (mstg_search takes CUDA tensors)")
         if len(q.shape) != 2:
             raise ValueError("Queries must be 2D array (N x D)")
         if q.shape[1] != self.dimension:
             raise ValueError(f"Query dimension {q.shape[1]} does not match expected {self.dimension}")
-        ids, dist, cnt = mstg_search(h, q, k, self.default_ef_search, self.pruning_epsilon, refine_pool=self.refine_pool)
+        ids, dist, cnt = mstg_search(h, q, k, self.default_ef_search, self.pruning_epsilon, refine_pool=self.refine_pool, dtype=dtype)
         return [np.stack([ids[i, :cnt[i]].astype(np.float32), dist[i, :cnt[i]]], axis=1) for i in range(q.shape[0])]
 
-    def query(self, query, k):
-        q = _host_f32(query)
+    def query(self, query, k, dtype=None):
+        from . import _marshal
+        q, dtype = _marshal.query_arg(query, dtype)
         if q.ndim != 1 or q.shape[0] != self.dimension:
             raise ValueError(f"Query dimension {q.shape[-1] if q.ndim else 0} does not match expected {self.dimension}")
-        return self.batch_query(q[None, :], k)[0]
+        return self.batch_query(q[None, :], k, dtype)[0]
 
     def config(self):
         """The crate's MstgConfig of this index (what `save` writes)."""
