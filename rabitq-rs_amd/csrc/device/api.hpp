@@ -30,6 +30,7 @@
 #include "launch.hpp"
 #include "../host/rbq_host_logic.hpp"
 #include "../host/rbq_append_plan.hpp"
+#include "../host/rbq_search_plan.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -376,6 +377,17 @@ struct Options {
     int set(const char* name, int value);
 };
 
+// The option fields the search routing reads (rbq_host::plan_search): THE place where Options meets the plan.
+inline rbq_host::RouteOptions route_options(const Options& o) {
+    rbq_host::RouteOptions r;
+    r.exact_rank = o.exact_rank; r.f32_rank = o.f32_rank; r.wg_prep = o.wg_prep; r.latency_path = o.latency_path;
+    r.rank_ksplit = o.rank_ksplit; r.rank_tile = o.rank_tile; r.rank_f16 = o.rank_f16; r.rank_planar = o.rank_planar;
+    r.stage_mask = o.stage_mask; r.lazy_select = o.lazy_select; r.lazy_filter = o.lazy_filter; r.head_exact = o.head_exact;
+    r.no_block_bound = o.no_block_bound; r.scan_wave = o.scan_wave; r.tie_log = o.tie_log; r.tie_log_cap = o.tie_log_cap;
+    r.exact_heap = o.exact_heap;
+    return r;
+}
+
 // One device-resident copy of the index.
 struct Replica : Geometry {
     int device = 0;
@@ -549,9 +561,13 @@ struct ProfScope {
         }
     }
 };
-// (mstg, d_slot_ids: the MSTG scans; the IVF search passes no slot map)
-int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, uint32_t top_k, uint64_t wl_stride,
-               const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
+// The routing plan of one launch chain of nq queries on workspace w (rbq_search_plan.hpp).  mstg: the posting scan behind the MSTG
+// front (nprobe: the list stride; only the plan's scan part is read).
+rbq_host::SearchPlan search_plan(const Replica* ix, const Workspace* w, uint64_t nq, uint32_t top_k, uint32_t nprobe, bool has_filter,
+                                 bool has_diag, bool range, bool mstg);
+// (plan: which scan kernel, the tie log, where the heap lives.  mstg, d_slot_ids: the MSTG scans; the IVF search passes no slot map)
+int scan_stage(Replica* ix, Workspace* w, const rbq_host::SearchPlan& plan, uint64_t nq, uint32_t probe_stride, uint32_t top_k,
+               uint64_t wl_stride, const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
                rbq_diag* d_diag, bool mstg, const uint32_t* d_dead_skipped, hipStream_t stream, const uint64_t* d_slot_ids = nullptr);
 
 } // namespace rbq_api

@@ -660,9 +660,15 @@ void rbq_profile_end(rbq_index* h) {
         }
     }
 }
-double rbq_profile_stage_ms(const rbq_index* h, const char* stage, uint64_t* launches) {
+// index of a profiled stage in Replica::stage_prof, or -1 (no handle, no replica, unknown name)
+static int profile_stage_index(const rbq_index* h, const char* stage) {
     if (!h || h->reps.empty() || !stage) return -1;
-    int s = !std::strcmp(stage, "prep") ? 0 : !std::strcmp(stage, "rank") ? 1 : !std::strcmp(stage, "select") ? 2 : !std::strcmp(stage, "scan") ? 3 : -1;
+    static const char* const names[4] = {"prep", "rank", "select", "scan"};
+    for (int s = 0; s < 4; ++s) if (!std::strcmp(stage, names[s])) return s;
+    return -1;
+}
+double rbq_profile_stage_ms(const rbq_index* h, const char* stage, uint64_t* launches) {
+    const int s = profile_stage_index(h, stage);
     if (s < 0) return -1;
     double ms = 0; uint64_t n = 0;
     for (const Replica* ix : h->reps) { ms += ix->stage_prof[s].ms; n += ix->stage_prof[s].launches; }
@@ -670,8 +676,7 @@ double rbq_profile_stage_ms(const rbq_index* h, const char* stage, uint64_t* lau
     return n ? ms / (double)n : 0.0;
 }
 uint64_t rbq_profile_stage_samples(const rbq_index* h, const char* stage, float* out, uint64_t cap) {
-    if (!h || h->reps.empty() || !stage) return 0;
-    int s = !std::strcmp(stage, "prep") ? 0 : !std::strcmp(stage, "rank") ? 1 : !std::strcmp(stage, "select") ? 2 : !std::strcmp(stage, "scan") ? 3 : -1;
+    const int s = profile_stage_index(h, stage);
     if (s < 0) return 0;
     uint64_t n = 0;
     for (const Replica* ix : h->reps)

@@ -46,8 +46,9 @@ int scan_posting_lists(Replica* ix, Workspace* w, uint64_t n, const uint32_t* d_
         p.numeric_variant = ix->opt.numeric_variant;
         HIP_TRY(launch_probes_given(p, stream));
     }
-    return scan_stage(ix, w, n, list_stride, top_k, wl_stride, nullptr, 0, d_ids, d_scores, d_counts, nullptr, /*mstg=*/true, nullptr, stream,
-                      d_slot_map);
+    const rbq_host::SearchPlan plan = search_plan(ix, w, n, top_k, list_stride, false, false, /*range=*/false, /*mstg=*/true);
+    return scan_stage(ix, w, plan, n, list_stride, top_k, wl_stride, nullptr, 0, d_ids, d_scores, d_counts, nullptr, /*mstg=*/true, nullptr,
+                      stream, d_slot_map);
 }
 
 // A host call in chunks on the pool workspace w: each chunk's queries are uploaded, body(q0, n, d_q, d_ids, d_scores, d_counts, stream)

@@ -1,29 +1,13 @@
 // api_search.hip — the IVF search: the device entry and the host entry (rbq_search_batch, one replica or N).  The hot path
 // (search_host -> search_device -> search_front -> scan_stage, or range_stage while the option range_search is on) stays in this one
-// unit; api_mstg_search.hip shares its workspaces and scan_stage.
+// unit; api_mstg_search.hip shares its workspaces and scan_stage.  Which kernels a call runs is decided once, in plain host code
+// (rbq_host::plan_search, csrc/host/rbq_search_plan.hpp); this unit sizes buffers, fills parameter blocks and launches what the plan says.
 #include "api.hpp"
 
 using namespace rbq_api;
 
 namespace rbq_api {
 namespace {
-// scan_wave = 2: batches of at least this many queries go to k_scanw (a query costs one resident wave instead of four: the
-// pipelined rate), smaller ones to k_scan (four waves shorten ONE query's chain: the latency of a small call)
-constexpr uint64_t kScanWaveMinQueries = 128;
-// ... and rbq_search_batch (host buffers; the caller waits for the call) from this many queries per call
-constexpr uint64_t kHostWaveMinQueries = 4096;
-// Latency-first front (latency.hpp): one launch rotates the query, builds its LUT and scores EVERY list exactly, spread over
-// n_lists / 32 workgroups per query.  It re-reads the centroid table once per query, so it serves calls of a few queries only
-// (every query's pass over the table must stay a few microseconds: n_lists x D x 4 bytes x nq within kLatMaxBytes).
-constexpr uint64_t kLatMaxQueries = 4; // (measured, GIST-1M shape: 1 / 2 / 4 queries per call -12 / -10 / -12 us against prep + GEMM; 8: no gain)
-constexpr uint64_t kLatMaxBytes = 96ull << 20;
-constexpr uint64_t kSplitKMaxCallQueries = 256; // calls up to here split the ranking GEMM's K loop over grid.z
-constexpr uint64_t kPrepWgMaxQueries = 512; // up to here the preparation runs one WORKGROUP per query (latency.hpp without the scorers)
-// rbq_search_batch reads page-locked queries in place from this many queries per call (up to 4 queries take the latency-first
-// front: a hundred workgroups per query would each read them over PCIe)
-constexpr uint64_t kZeroCopyMinQueries = 5;
-
-
 // The WHOLE range [p, p + bytes) is page-locked host memory of one allocation / registration: the kernels write (and the
 // DMA engines read) every byte of it, so a registration that covers only the first pages must not pass.
 bool is_pinned_host_range(const void* p, size_t bytes) {
@@ -95,9 +79,19 @@ Replica* replica_of_pointer(rbq_index* h, const void* dptr) {
     return h->reps[0];
 }
 
+rbq_host::SearchPlan search_plan(const Replica* ix, const Workspace* w, uint64_t nq, uint32_t top_k, uint32_t nprobe, bool has_filter,
+                                 bool has_diag, bool range, bool mstg) {
+    rbq_host::SearchShape s;
+    s.nq = nq; s.call_nq = w->call_nq; s.top_k = top_k; s.nprobe = nprobe; s.n_lists = ix->n_lists; s.D = ix->D; s.Dc = ix->Dc;
+    s.rotator = ix->rotator; s.ex_bits = ix->ex_bits; s.rank_f16_ok = ix->rank_f16_ok; s.has_filter = has_filter; s.has_diag = has_diag;
+    s.range = range; s.latency_first = w->latency_first; s.mstg = mstg; s.probe_installed = stage_probes() != nullptr;
+    if (!mstg) { s.nblk_desc_prefix = ix->nblk_desc_prefix.data(); s.nblk_desc_prefix_len = ix->nblk_desc_prefix.size(); }
+    return rbq_host::plan_search(s, route_options(ix->opt));
+}
+
 // k_scan launch shared by the IVF search and the MSTG posting-list scan
-int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, uint32_t top_k, uint64_t wl_stride,
-               const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
+int scan_stage(Replica* ix, Workspace* w, const rbq_host::SearchPlan& plan, uint64_t nq, uint32_t probe_stride, uint32_t top_k,
+               uint64_t wl_stride, const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
                rbq_diag* d_diag, bool mstg, const uint32_t* d_dead_skipped, hipStream_t stream, const uint64_t* d_slot_ids) {
     ProfScope ps(ix, 3, stream, /*ext=*/true);
     ScanParams P;
@@ -118,26 +112,14 @@ int scan_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, ui
     P.prof = (ix->profiling && ix->opt.profile_counters) ? (unsigned long long*)ix->prof.p : nullptr;
     P.dead_skipped = d_dead_skipped;
     P.numeric_variant = ix->opt.numeric_variant;
-    // scan_wave = 2 (default): the wave-per-query kernel serves the pruned regime of batches large enough to fill the chip with
-    // waves; with the block bound off (every probed block streamed: the roofline configuration) the four-wave kernel streams
-    // at twice its rate and serves the call.  Results are identical either way.
-    // A host call (rbq_search_batch) that waits for ONE chain of kernels is served by the kernel with the shorter chain (k_scan's
-    // four waves finish a 1024-query launch in 0.10 ms, k_scanw's single wave in 0.14 ms) until the call is large enough for the rate
-    // to matter more than the last chain's latency.
-    P.wave_kernel = (ix->opt.scan_wave == 1 || (ix->opt.scan_wave == 2 && nq >= kScanWaveMinQueries && !ix->opt.no_block_bound && !w->latency_first)) ? 1u : 0u;
-    // tie log (k_scan, no diagnostics, top-k in registers): a tied query replays its logged candidates instead of its lists
+    P.wave_kernel = plan.wave_kernel ? 1u : 0u;
     P.tie_log = nullptr; P.tie_log_cap = 0;
-    if (ix->opt.tie_log && !P.wave_kernel && !d_diag && !mstg && top_k >= 1 && top_k <= kTopKRegMax && !ix->opt.exact_heap && !stage_probes()) {
-        // entries per query: ~80 candidates are refined per query at top_k = 10 and ~400 at top_k = 100 on the bench data; a query that
-        // logs more than the capacity is scanned again, as before (option tie_log_cap: tests of that path)
-        const uint32_t cap = ix->opt.tie_log_cap ? ix->opt.tie_log_cap : (top_k < 64u ? 2048u : 8192u);
-        if ((uint64_t)nq * cap * 12u <= (1ull << 30)) {
-            if (w->tie_log.ensure((size_t)nq * cap * 12u) == RBQ_OK) { P.tie_log = (uint32_t*)w->tie_log.p; P.tie_log_cap = cap; }
-            else { (void)hipGetLastError(); g_err.clear(); } // (no memory for the log: the call is served without it)
-        }
+    if (plan.tie_log) {
+        if (w->tie_log.ensure((size_t)nq * plan.tie_log_cap * 12u) == RBQ_OK) { P.tie_log = (uint32_t*)w->tie_log.p; P.tie_log_cap = plan.tie_log_cap; }
+        else { (void)hipGetLastError(); g_err.clear(); } // (no memory for the log: the call is served without it)
     }
     P.heap_ws = nullptr;
-    if (top_k > kTopKMax || scan_lds_bytes(ix->Dc, ix->D, P.ex_bits, top_k) > kLdsPerWorkgroupMax) { // the heap does not fit the LDS
+    if (plan.heap_in_global) {
         int rc = w->heap_ws.ensure((size_t)nq * 2 * ((size_t)top_k + 1) * 4);
         if (rc) return rc;
         P.heap_ws = (uint32_t*)w->heap_ws.p;
@@ -176,22 +158,21 @@ namespace {
 // range search on this handle?  (MSTG handles — RBQ_ROTATOR_NONE — never take it)
 inline bool range_on(const Replica* ix) { return ix->opt.range_search && ix->rotator != 2; }
 
-// What the front leaves for the stage that follows it
-struct Front { uint32_t nprobe; uint64_t wl_stride; bool exact_select; };
+using rbq_host::PrepForm;
+using rbq_host::RankRoute;
+using rbq_host::SearchPlan;
 
-// Front of a search on device pointers, enqueued on `stream`, shared by the top-k scan and the range scan: workspace sizing, prep /
-// latency front, ranking GEMM or exact ranking, selection.  `range`: the selection is eager (no threshold exists to drop a list against).
-int search_front(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe_in,
-                 const uint32_t* d_filter, uint64_t filter_nbits, rbq_diag* d_diag, hipStream_t stream, bool range, Front& front) {
+// Front of a search on device pointers, enqueued on `stream`, shared by the top-k scan and the range scan: what `plan` says, in the
+// order plan -> buffers -> the three parameter blocks -> launches (prep / latency front, ranking GEMM or exact ranking, selection).
+int search_front(Replica* ix, Workspace* w, const SearchPlan& plan, const float* d_queries, uint64_t nq, uint32_t top_k,
+                 const uint32_t* d_filter, uint64_t filter_nbits, rbq_diag* d_diag, hipStream_t stream) {
     const uint32_t D = ix->D, Dc = ix->Dc;
     const uint32_t nlist = (uint32_t)ix->n_lists;
-    uint32_t nprobe = nprobe_in < 1 ? 1 : nprobe_in;
-    if (nprobe > nlist) nprobe = nlist;
-    // nprobe > kNprobeMax: the exact all-pairs ranking with its key window in global memory (slow, but served: the reference clamps
-    // nprobe to n_lists)
-    const bool big_nprobe = nprobe > kNprobeMax;
-    const uint64_t wl_stride = std::max<uint64_t>(ix->nblk_desc_prefix[nprobe], 1);
+    const uint32_t nprobe = plan.nprobe, smask = plan.stage_mask;
+    const uint64_t wl_stride = plan.wl_stride;
+    const bool f16 = plan.rank == RankRoute::f16;
 
+    // ---- buffers ---------------------------------------------------------------------------------------------------------------
     int rc;
     if ((rc = w->rot.ensure(nq * D * 4))) return rc;
     if ((rc = w->lut.ensure(nq * (size_t)Dc * 4))) return rc;
@@ -202,79 +183,47 @@ int search_front(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq,
     if ((rc = w->nstream.ensure(nq * 4))) return rc;
     if ((rc = w->nvec.ensure(nq * 8))) return rc;
     if ((rc = w->dead_skipped.ensure(nq * 16))) return rc;
-    const bool split_rank = !ix->opt.exact_rank && !ix->opt.f32_rank && D % 64 == 0; // k_rank_bf16_db (else k_rank_mfma)
-    if (split_rank) {
-        if ((rc = w->rot_hl.ensure(nq * D * 4))) return rc;
-        if (ix->opt.rank_planar && (rc = w->rank_planes.ensure((nq + nlist) * (size_t)D * 4))) return rc;
-    }
+    if (plan.need_rot_hl && (rc = w->rot_hl.ensure(nq * D * 4))) return rc;
+    if (plan.need_rank_planes && (rc = w->rank_planes.ensure((nq + nlist) * (size_t)D * 4))) return rc;
+    if (plan.need_rot_f16 && (rc = w->rot_f16.ensure(nq * D * 2))) return rc;
+    if (plan.need_rank_resid && (rc = w->rank_resid.ensure(nq * 4))) return rc;
+    if (plan.need_key_window && (rc = w->key_window.ensure((size_t)nq * select_exact_np2(nprobe) * 8))) return rc;
+    if (ix->opt.lazy_audit && (rc = w->audit_dead.ensure(nq * (size_t)(kAuditCap + 1) * 4))) return rc;
+    if (ix->opt.ub_tap && (rc = w->head_ub.ensure(nq * (size_t)kHeadUbRow * 4))) return rc;
     unsigned long long* prof = (ix->profiling && ix->opt.profile_counters) ? (unsigned long long*)ix->prof.p : nullptr;
-    const uint32_t smask = ix->opt.stage_mask;
-    // small calls: prep + exact scores of every list in one launch (the ranking GEMM and its launch boundary are skipped)
-    // split-K of the ranking GEMM for batches whose tiles leave the chip idle (the rows are cleared by the workgroup-per-query preparation)
-    uint32_t ksplit = 1;
-    // (only when the whole CALL is small: the sub-batches of a 1024-query host call overlap each other, and the extra workgroups and
-    // atomics of a split GEMM then cost more than its shorter K loop saves — 277 -> 295 us per call, measured)
-    if (ix->opt.rank_ksplit && ix->opt.latency_path && nq <= kPrepWgMaxQueries && (w->call_nq ? w->call_nq : nq) <= kSplitKMaxCallQueries && ix->rotator != 0 &&
-        !ix->opt.wg_prep && D % 16 == 0 && split_rank && !ix->opt.exact_rank && !big_nprobe && smask == 0xfu) {
-        const uint32_t T = ((uint64_t)((nlist + 127) / 128) * ((nq + 127) / 128) >= 192 && ix->opt.rank_tile != 64) || ix->opt.rank_tile == 128 ? 128u : 64u;
-        const uint64_t tiles = (uint64_t)((nlist + T - 1) / T) * ((nq + T - 1) / T);
-        ksplit = tiles >= 512 ? 1u : (tiles >= 256 ? 2u : 4u);
-        while (ksplit > 1 && (D / 32) / ksplit < 6) ksplit >>= 1; // (at least six slabs per part)
-        // (option: forced; at most 4 parts, the most the eps of k_select_mfma is derived for — rank_mfma.hpp header)
-        if (ix->opt.rank_ksplit > 1) ksplit = (uint32_t)std::min(ix->opt.rank_ksplit, 4);
-    }
-    const bool lat_front = ix->opt.latency_path && nq <= kLatMaxQueries && ix->rotator != 0 && !ix->opt.wg_prep && !ix->opt.exact_rank && !big_nprobe &&
-                           !ix->opt.f32_rank && (uint64_t)nlist * D * 4 * nq <= kLatMaxBytes && D % 16 == 0 && smask == 0xfu;
-    // one-product f16 ranking (rank_mfma.hpp header, "ONE f16 PRODUCT").  Possible: the index qualifies, the call ranks on the split GEMM
-    // without split-K, planar copies or the exact front.  By rule (rank_f16 = -1): on top of that no forced tile, a big or wide call (the
-    // GEMM is a stage worth routing) and D >= 256.
-    const uint64_t tiles128 = (uint64_t)((nlist + 127) / 128) * ((nq + 127) / 128), tiles256 = (uint64_t)((nlist + 255) / 256) * ((nq + 127) / 128);
-    const bool f16_possible = ix->rank_f16_ok && split_rank && ksplit == 1 && !ix->opt.rank_planar && !big_nprobe && !lat_front;
-    const bool rank_f16 = ix->opt.rank_f16 != 0 && f16_possible &&
-                          (ix->opt.rank_f16 > 0 || (ix->opt.rank_tile == 0 && (tiles128 >= 192 || tiles256 >= 2048) && D >= 256));
-    if (rank_f16) {
-        if ((rc = w->rot_f16.ensure(nq * D * 2))) return rc;
-        if ((rc = w->rank_resid.ensure(nq * 4))) return rc;
-    }
-    if (lat_front) {
-        ProfScope ps(ix, 0, stream);
-        const PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq, ix->opt.query_dtype);
-        RankParams r;
-        r.metric = ix->metric; r.cent = (const float*)ix->centroids.p; r.nlist = nlist; r.D = D; r.nq = (uint32_t)nq;
-        r.scores = (float*)w->scores.p;
-        HIP_TRY(launch_lat_front(p, r, ix->device, stream));
-    } else if (smask & 1u) {
-        ProfScope ps(ix, 0, stream);
-        PrepParams p = prep_params(*ix, ix->rot_blob, *w, d_queries, nq, ix->opt.query_dtype);
-        p.rot_hl = split_rank ? (uint16_t*)w->rot_hl.p : nullptr;
-        if (rank_f16) { p.rot_hl = (uint16_t*)w->rot_f16.p; p.rank_resid = (float*)w->rank_resid.p; }
-        p.wg_prep = ix->opt.wg_prep;
-        // batches a caller waits for (a few hundred queries: the chip is not full): a workgroup per query — the serial sums on one
-        // wave while the others build the LUT (latency.hpp, preparation only); full batches keep one wave per query (k_prep_wave)
-        if (ix->opt.latency_path && nq <= kPrepWgMaxQueries && ix->rotator != 0 && !ix->opt.wg_prep && D % 16 == 0) {
-            RankParams r;
-            r.metric = ix->metric; r.cent = nullptr; r.nlist = nlist; r.D = D; r.nq = (uint32_t)nq;
-            r.scores = ksplit > 1 ? (float*)w->scores.p : nullptr; r.ksplit = ksplit; // (split-K GEMM: this kernel clears the score rows)
-            HIP_TRY(launch_lat_front(p, r, ix->device, stream));
-        } else {
-            HIP_TRY(launch_prep(p, ix->device, stream));
-        }
+
+    // ---- the three parameter blocks ------------------------------------------------------------------------------------------------
+    PrepParams pp = prep_params(*ix, ix->rot_blob, *w, d_queries, nq, ix->opt.query_dtype);
+    RankParams pr; // what the latency kernel reads of the ranking: with its scorers the exact scores, else the rows to clear
+    pr.metric = ix->metric; pr.cent = nullptr; pr.nlist = nlist; pr.D = D; pr.nq = (uint32_t)nq; pr.scores = nullptr;
+    if (plan.lat_front()) {
+        pr.cent = (const float*)ix->centroids.p; pr.scores = (float*)w->scores.p;
+    } else {
+        pp.rot_hl = plan.need_rot_hl ? (uint16_t*)w->rot_hl.p : nullptr;
+        if (f16) { pp.rot_hl = (uint16_t*)w->rot_f16.p; pp.rank_resid = (float*)w->rank_resid.p; }
+        pp.wg_prep = ix->opt.wg_prep;
+        pr.ksplit = 1;
+        // (a split-K GEMM follows: this kernel clears the score rows its parts are added to; launch_lat_front reads that off ksplit > 1)
+        if (plan.prep == PrepForm::wg_zero) { pr.scores = (float*)w->scores.p; pr.ksplit = std::max(plan.ksplit, 2u); }
     }
     RankParams rp;
     rp.metric = ix->metric; rp.rot = (const float*)w->rot.p; rp.rot_hi = (const uint16_t*)w->rot_hl.p; rp.rot_lo = nullptr; rp.rot_hl = true;
     rp.cent = (const float*)ix->centroids.p; rp.cent_hi = (const uint16_t*)ix->cent_hl.p; rp.cent_lo = nullptr; rp.cent_hl = true;
     rp.consts = (const QueryConsts*)w->consts.p; rp.cnorm2 = (const float*)ix->cnorm2.p; rp.nq = (uint32_t)nq; rp.nlist = nlist; rp.D = D;
-    rp.scores = (float*)w->scores.p; rp.split = split_rank; rp.ksplit = ksplit;
-    if (rank_f16) { rp.f16 = true; rp.rot_hi = (const uint16_t*)w->rot_f16.p; rp.cent_hi = (const uint16_t*)ix->cent_f16.p; }
-    rp.big = (uint64_t)((nlist + 127) / 128) * ((nq + 127) / 128) >= 192; // enough 128x128 tiles to fill the chip
-    // option rank_tile: 0 = by problem size, 64 / 128 / 256 = forced (tests; A/B)
-    rp.wide = ix->opt.rank_tile == 256 || (ix->opt.rank_tile == 0 && (uint64_t)((nlist + 255) / 256) * ((nq + 127) / 128) >= 2048);
-    if (ix->opt.rank_tile == 64) rp.big = false;
-    if (ix->opt.rank_tile == 128) rp.big = true;
+    rp.scores = (float*)w->scores.p; rp.split = plan.split_route(); rp.ksplit = plan.ksplit;
+    if (f16) { rp.f16 = true; rp.rot_hi = (const uint16_t*)w->rot_f16.p; rp.cent_hi = (const uint16_t*)ix->cent_f16.p; }
+    rp.big = plan.tile == 128; rp.wide = plan.tile == 256;
+    // TEST ONLY: the same GEMM on planar copies of its operands (made below, before the GEMM)
+    uint16_t* const pl = plan.planar ? (uint16_t*)w->rank_planes.p : nullptr; // rot hi | rot lo | cent hi | cent lo
+    const size_t nr = (size_t)nq * D, nc = (size_t)nlist * D;
+    if (pl) {
+        rp.rot_hi = pl; rp.rot_lo = pl + nr; rp.rot_hl = false;
+        rp.cent_hi = pl + 2 * nr; rp.cent_lo = pl + 2 * nr + nc; rp.cent_hl = false;
+    }
     SelectParams sp;
     sp.scores = (float*)w->scores.p; sp.nq = (uint32_t)nq; sp.nlist = nlist; sp.nprobe = nprobe; sp.metric = ix->metric;
     sp.rot = (const float*)w->rot.p; sp.cent = (const float*)ix->centroids.p; sp.D = D; sp.consts = (const QueryConsts*)w->consts.p;
-    if (rank_f16) { sp.rank_resid = (const float*)w->rank_resid.p; sp.cnorm_max = ix->cnorm_max; sp.rc_max = ix->rc_max; }
+    if (f16) { sp.rank_resid = (const float*)w->rank_resid.p; sp.cnorm_max = ix->cnorm_max; sp.rc_max = ix->rc_max; }
     sp.cnorm2_max = ix->cnorm2_max; sp.list_gb0 = (const uint32_t*)ix->list_gb0.p; sp.list_n = (const uint32_t*)ix->list_n.p;
     sp.probe = (ProbeInfo*)w->probe.p; sp.wl = (StreamItem*)w->wl.p; sp.wl_stride = wl_stride; sp.nstream = (uint32_t*)w->nstream.p;
     sp.nvec = (unsigned long long*)w->nvec.p; sp.prof_total = prof; sp.fallback_count = (unsigned int*)ix->fallbacks.p;
@@ -283,24 +232,11 @@ int search_front(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq,
     sp.dead_skipped = (uint32_t*)w->dead_skipped.p; sp.top_k = top_k; sp.ex_bits = ix->ex_bits;
     sp.slack = ix->opt.slack;
     sp.numeric_variant = ix->opt.numeric_variant;
-    sp.audit_dead = nullptr;
-    if (ix->opt.lazy_audit) { // diagnostic: the lists the selection drops as a whole are exported (rbq_debug_copy_workspace "audit_dead")
-        if ((rc = w->audit_dead.ensure(nq * (size_t)(kAuditCap + 1) * 4))) return rc;
-        HIP_TRY(hipMemsetAsync(w->audit_dead.p, 0, nq * (size_t)(kAuditCap + 1) * 4, stream));
-        sp.audit_dead = (uint32_t*)w->audit_dead.p;
-    }
-    sp.head_ub = nullptr;
-    if (ix->opt.ub_tap) { // diagnostic: the lazy selection's head candidates and their bounds (rbq_debug_copy_workspace "head_ub")
-        if ((rc = w->head_ub.ensure(nq * (size_t)kHeadUbRow * 4))) return rc;
-        HIP_TRY(hipMemsetAsync(w->head_ub.p, 0, nq * (size_t)kHeadUbRow * 4, stream));
-        sp.head_ub = (uint32_t*)w->head_ub.p;
-    }
-    // lazy selection: not with a filter (filtered vectors are never pushed, so no select-time bound of the k-th distance
-    // exists) and not when every probed block is to be streamed
-    // (round 4: under a filter the exact head evaluation can still bound the k-th distance — it looks at real vectors and counts
-    // the ones that pass; with diagnostics the skip counter of a dropped list would need every id's filter bit: eager then)
-    const bool lazy_with_filter = ix->opt.lazy_filter && ix->opt.head_exact && !d_diag;
-    sp.lazy = (ix->opt.lazy_select && (!d_filter || lazy_with_filter) && !ix->opt.no_block_bound && !range) ? 1 : 0;
+    // diagnostics: the lists the selection drops as a whole, the lazy selection's head candidates and their bounds
+    // (rbq_debug_copy_workspace "audit_dead" / "head_ub"; cleared below, before the selection)
+    sp.audit_dead = ix->opt.lazy_audit ? (uint32_t*)w->audit_dead.p : nullptr;
+    sp.head_ub = ix->opt.ub_tap ? (uint32_t*)w->head_ub.p : nullptr;
+    sp.lazy = plan.lazy ? 1 : 0;
     sp.filter = d_filter; sp.filter_nbits = filter_nbits; sp.ids = (const uint64_t*)ix->ids.p;
     sp.exact_members = d_diag ? 1 : 0;
     sp.fault_dead_all = ix->opt.lazy_fault_inject ? 1 : 0;
@@ -308,55 +244,55 @@ int search_front(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq,
     sp.f_add_ex = (const float*)ix->fadd_ex.p; sp.f_rescale_ex = (const float*)ix->fres_ex.p; sp.Dc = Dc;
     sp.head_exact = ix->opt.head_exact ? 1 : 0;
     sp.n_blocks = (uint32_t)ix->n_blocks;
-    if (ix->opt.exact_rank || big_nprobe) {
-        uint64_t* kw = nullptr;
-        if (big_nprobe) {
-            if ((rc = w->key_window.ensure((size_t)nq * select_exact_np2(nprobe) * 8))) return rc;
-            kw = (uint64_t*)w->key_window.p;
-        }
-        if (smask & 2u) { ProfScope ps(ix, 1, stream); HIP_TRY(launch_rank_exact(rp, stream)); }
-        if (smask & 4u) { ProfScope ps(ix, 2, stream); HIP_TRY(launch_select_exact(sp, ix->device, stream, kw)); }
-    } else {
-        if ((smask & 2u) && !lat_front && split_rank && ix->opt.rank_planar && !stage_probes()) { // TEST ONLY: the same GEMM on planar copies of its operands
-            uint16_t* pl = (uint16_t*)w->rank_planes.p; // rot hi | rot lo | cent hi | cent lo
-            const size_t nr = (size_t)nq * D, nc = (size_t)nlist * D;
-            HIP_TRY(launch_hl_planes((const uint16_t*)w->rot_hl.p, nq, D, pl, pl + nr, stream));
-            HIP_TRY(launch_hl_planes((const uint16_t*)ix->cent_hl.p, nlist, D, pl + 2 * nr, pl + 2 * nr + nc, stream));
-            rp.rot_hi = pl; rp.rot_lo = pl + nr; rp.rot_hl = false;
-            rp.cent_hi = pl + 2 * nr; rp.cent_lo = pl + 2 * nr + nc; rp.cent_hl = false;
-        }
-        if ((smask & 2u) && !lat_front) { ProfScope ps(ix, 1, stream); HIP_TRY(launch_rank_gemm(rp, ix->device, stream)); } // approximate scores: one MFMA GEMM
-        if (smask & 4u) { ProfScope ps(ix, 2, stream); HIP_TRY(launch_select_mfma(sp, ix->device, stream)); }         // shortlist + exact canonical scores + exact select
+
+    // ---- launches --------------------------------------------------------------------------------------------------------------
+    if (smask & 1u) { // (the latency front runs under the full mask only)
+        ProfScope ps(ix, 0, stream);
+        if (plan.prep == PrepForm::prep || plan.prep == PrepForm::prep_wave) HIP_TRY(launch_prep(pp, ix->device, stream));
+        else HIP_TRY(launch_lat_front(pp, pr, ix->device, stream));
     }
-    front.nprobe = nprobe; front.wl_stride = wl_stride; front.exact_select = ix->opt.exact_rank || big_nprobe;
+    if (ix->opt.lazy_audit) HIP_TRY(hipMemsetAsync(w->audit_dead.p, 0, nq * (size_t)(kAuditCap + 1) * 4, stream));
+    if (ix->opt.ub_tap) HIP_TRY(hipMemsetAsync(w->head_ub.p, 0, nq * (size_t)kHeadUbRow * 4, stream));
+    if (pl && (smask & 2u)) {
+        HIP_TRY(launch_hl_planes((const uint16_t*)w->rot_hl.p, nq, D, pl, pl + nr, stream));
+        HIP_TRY(launch_hl_planes((const uint16_t*)ix->cent_hl.p, nlist, D, pl + 2 * nr, pl + 2 * nr + nc, stream));
+    }
+    if ((smask & 2u) && plan.rank != RankRoute::none) {
+        ProfScope ps(ix, 1, stream);
+        if (plan.rank == RankRoute::exact) HIP_TRY(launch_rank_exact(rp, stream));
+        else HIP_TRY(launch_rank_gemm(rp, ix->device, stream)); // approximate scores: one MFMA GEMM
+    }
+    if (smask & 4u) {
+        ProfScope ps(ix, 2, stream);
+        if (plan.exact_select) HIP_TRY(launch_select_exact(sp, ix->device, stream, plan.need_key_window ? (uint64_t*)w->key_window.p : nullptr));
+        else HIP_TRY(launch_select_mfma(sp, ix->device, stream)); // shortlist + exact canonical scores + exact select
+    }
     return RBQ_OK;
 }
 
-// Core: the front, then the stage that reads its stream — the top-k scan, or the range scan while the option range_search is on.
-// `rerank`: the unpooled rerank (k_rerank over the returned ids) follows the scan
+// Core: the plan, then the front, then the stage that reads its stream — the top-k scan, or the range scan while the option
+// range_search is on.  `rerank`: the unpooled rerank (k_rerank over the returned ids) follows the scan
 int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe_in,
                 const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
                 rbq_diag* d_diag, hipStream_t stream, bool rerank) {
     const bool range = range_on(ix);
+    const SearchPlan plan = search_plan(ix, w, nq, top_k, nprobe_in, d_filter != nullptr, d_diag != nullptr, range, /*mstg=*/false);
     int rc;
-    Front f;
     if (range) {
         // top_k is the capacity of a query's output row; no heap exists, so the heap workspace's 8 GiB rule does not apply
         if (top_k > kTopKHardMax) return fail(RBQ_INVALID_CONFIG, "range search: the capacity of a query's row is at most 2^20");
-        if ((rc = search_front(ix, w, d_queries, nq, top_k, nprobe_in, d_filter, filter_nbits, d_diag, stream, true, f))) return rc;
-        if (ix->opt.stage_mask & 8u)
-            return range_stage(ix, w, nq, f.nprobe, top_k, f.wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag, stream);
+        if ((rc = search_front(ix, w, plan, d_queries, nq, top_k, d_filter, filter_nbits, d_diag, stream))) return rc;
+        if (plan.stage_mask & 8u)
+            return range_stage(ix, w, nq, plan.nprobe, top_k, plan.wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag, stream);
         return RBQ_OK;
     }
-    // top_k > kTopKMax: the heap in global memory — slow, but served (the reference accepts any top_k)
     // the 8 GiB bound is the global-memory heap's (top_k beyond what the LDS holds); calls whose heap lives in LDS need no workspace
-    const bool heap_in_global = top_k > kTopKMax || scan_lds_bytes(ix->Dc, ix->D, ix->ex_bits, top_k) > kLdsPerWorkgroupMax;
-    if (top_k > kTopKHardMax || (heap_in_global && (uint64_t)nq * ((uint64_t)top_k + 1) * 8 > (8ull << 30)))
+    if (top_k > kTopKHardMax || (plan.heap_in_global && (uint64_t)nq * ((uint64_t)top_k + 1) * 8 > (8ull << 30)))
         return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20 and nq * top_k * 8 bytes of heap workspace <= 8 GiB)");
     if (rerank && top_k > 1024) return fail(RBQ_INVALID_CONFIG, "rerank supports top_k <= 1024");
-    if ((rc = search_front(ix, w, d_queries, nq, top_k, nprobe_in, d_filter, filter_nbits, d_diag, stream, false, f))) return rc;
-    if ((ix->opt.stage_mask & 8u) && (rc = scan_stage(ix, w, nq, f.nprobe, top_k, f.wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag,
-                                                      /*mstg=*/false, f.exact_select ? nullptr : (const uint32_t*)w->dead_skipped.p, stream)))
+    if ((rc = search_front(ix, w, plan, d_queries, nq, top_k, d_filter, filter_nbits, d_diag, stream))) return rc;
+    if ((plan.stage_mask & 8u) && (rc = scan_stage(ix, w, plan, nq, plan.nprobe, top_k, plan.wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts,
+                                                   d_diag, /*mstg=*/false, plan.exact_select ? nullptr : (const uint32_t*)w->dead_skipped.p, stream)))
         return rc;
     if (rerank && !stage_probes()) // optional, default off: exact re-scoring of the returned ids against the attached raw vectors
         HIP_TRY(launch_rerank(d_queries, ix->opt.query_dtype, (uint32_t)nq, ix->dim, ix->raw.p, ix->raw_dtype, ix->n_raw, ix->metric, top_k, d_ids, d_scores,
@@ -414,9 +350,13 @@ int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_d
     // sub-batches shrink towards the end of the call (rbq_host_logic.hpp): the last one's kernel chain is what the caller waits for
     const std::vector<std::pair<uint64_t, uint64_t>> plan = rbq_host::subbatch_plan(nq, ix->opt.host_subbatch);
     const uint64_t nsub = plan.size();
-    const uint32_t nlanes = (uint32_t)std::min<uint64_t>(nsub, ix->opt.host_lanes ? ix->opt.host_lanes : 6u);
     const rbq_host::QueryRows qr = query_rows(ix, query_dim); // every byte length and row offset on the queries below is its arithmetic
     const bool in_pinned = is_pinned_host_range(queries, qr.bytes(nq));
+    // lanes, the zero-copy window, helpers, the short-chain scan: the call's decisions, with their measurements, in rbq_host_logic.hpp
+    rbq_host::HostCallOptions hopt;
+    hopt.host_lanes = ix->opt.host_lanes; hopt.host_zero_copy = ix->opt.host_zero_copy; hopt.host_stage_helpers = ix->opt.host_stage_helpers;
+    const rbq_host::HostCallPlan call = rbq_host::host_call_plan(nq, in_pinned, qr.bytes(nq), nsub, hopt);
+    const uint32_t nlanes = call.nlanes;
     bool out_pinned = !ix->rerank && is_pinned_host_range(out_ids, nq * top_k * 8) && is_pinned_host_range(out_scores, nq * top_k * 4) &&
                       is_pinned_host_range(out_counts, nq * 4) && (!diag || is_pinned_host_range(diag, nq * sizeof(rbq_diag)));
     // device-side addresses of page-locked caller buffers (identical under unified addressing; asked for, not assumed)
@@ -430,13 +370,7 @@ int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_d
         }
     }
     // page-locked queries are read by k_prep where they lie (device-side address of the caller's buffer)
-    // (measured, GIST-1M shape: 1024 queries per call 297 -> 280 us, 1536: 388 -> 376, 256: 212 -> 198 us; but one query 133 -> 147 us,
-    // 2048 per call 445 -> 457 and from 4096 the copy engine clearly beats the waves' own PCIe reads: 678 -> 778 us — hence the window)
-    // (pageable queries, read from the lane's pinned staging buffer: 1024 per call 381 -> 373 us, but 2048 per call 524 -> 591 us:
-    // there the staged DMA pieces overlap the host copy better than one big copy followed by in-place reads — window <= 1024)
-    // (round 5: the preparation kernels now request a query's elements eight at a time instead of one per round trip — 15 PCIe round
-    // trips per query at D = 960 became 2 — and the window opens at 5 queries: 8 per call 149 -> 142 us, 16: 156 -> 149, 24: 161 -> 153)
-    const bool zero_copy = ix->opt.host_zero_copy && nq >= kZeroCopyMinQueries && nq <= (in_pinned ? 1536u : 1024u);
+    const bool zero_copy = call.zero_copy;
     const float* c_queries = nullptr;
     if (zero_copy && in_pinned && hipHostGetDevicePointer((void**)&c_queries, const_cast<float*>(queries), 0) != hipSuccess) {
         (void)hipGetLastError();
@@ -481,13 +415,12 @@ int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_d
     };
     // pageable queries, every sub-batch on its own lane (nsub <= nlanes): the helpers stage sub-batches 1.. into their lanes' pinned
     // buffers while this thread stages and launches sub-batch 0
-    constexpr uint64_t kMaxHelped = 8;
-    std::atomic<int> staged[kMaxHelped];
+    std::atomic<int> staged[rbq_host::kMaxHelped];
     uint64_t n_helped = 0; // sub-batches 1 .. n_helped are staged by helpers
     auto wait_staged = [&staged](uint64_t j) { spin_until([&] { return staged[j].load(std::memory_order_acquire) != 0; }); };
     struct WaitHelpers { decltype(wait_staged)& wait; uint64_t& n; // (no job may outlive this frame: it writes the flags)
         ~WaitHelpers() { for (uint64_t j = 1; j <= n; ++j) wait(j); } } wait_helpers{wait_staged, n_helped};
-    bool helpers = !in_pinned && ix->opt.host_stage_helpers && nsub >= 2 && nsub <= nlanes && nsub <= kMaxHelped && qr.bytes(nq) >= (512u << 10);
+    bool helpers = call.helpers;
     if (helpers) {
         // the helpers are published only once every thread of theirs runs (a half-started set used to stay installed, and
         // jobs posted to it could wait forever); if a thread cannot be created the call stages inline, like a small one does
@@ -561,7 +494,7 @@ int search_host(Replica* ix, const float* queries, uint64_t nq, uint32_t query_d
             k_diag = diag ? (rbq_diag*)(dp + op.o_diag) : nullptr;
         }
         // every sub-batch of a call below kHostWaveMinQueries takes the short-chain kernel
-        w->latency_first = nq < kHostWaveMinQueries;
+        w->latency_first = call.latency_first;
         w->call_nq = nq;
         rc = search_device(ix, w, d_q, n, top_k, nprobe, d_filter, filter_nbits, k_ids, k_scores, k_counts, k_diag, w->stream);
         w->latency_first = false;

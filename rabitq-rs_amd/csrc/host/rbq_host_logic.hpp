@@ -353,6 +353,44 @@ inline std::vector<std::pair<uint64_t, uint64_t>> subbatch_plan(uint64_t nq, uin
     return plan;
 }
 
+// The per-call decisions of rbq_search_batch on one replica (search_host, api_search.hip), beside the sub-batches above.
+// scan_wave = 2 sends batches of at least kScanWaveMinQueries (rbq_search_plan.hpp) to k_scanw; a host call (host buffers; the caller
+// waits for the call) only from this many queries per call: every sub-batch of a smaller call takes the short-chain kernel
+constexpr uint64_t kHostWaveMinQueries = 4096;
+// rbq_search_batch reads page-locked queries in place from this many queries per call (up to 4 queries take the latency-first
+// front: a hundred workgroups per query would each read them over PCIe)
+constexpr uint64_t kZeroCopyMinQueries = 5;
+// ... and up to this many: page-locked queries are read by k_prep where they lie (device-side address of the caller's buffer)
+// (measured, GIST-1M shape: 1024 queries per call 297 -> 280 us, 1536: 388 -> 376, 256: 212 -> 198 us; but one query 133 -> 147 us,
+// 2048 per call 445 -> 457 and from 4096 the copy engine clearly beats the waves' own PCIe reads: 678 -> 778 us — hence the window)
+// (pageable queries, read from the lane's pinned staging buffer: 1024 per call 381 -> 373 us, but 2048 per call 524 -> 591 us:
+// there the staged DMA pieces overlap the host copy better than one big copy followed by in-place reads — window <= 1024)
+// (round 5: the preparation kernels now request a query's elements eight at a time instead of one per round trip — 15 PCIe round
+// trips per query at D = 960 became 2 — and the window opens at 5 queries: 8 per call 149 -> 142 us, 16: 156 -> 149, 24: 161 -> 153)
+constexpr uint64_t kZeroCopyMaxPinned = 1536, kZeroCopyMaxPageable = 1024;
+// pageable queries, every sub-batch on its own lane (nsub <= nlanes): helper threads stage sub-batches 1.. into their lanes' pinned
+// buffers while the calling thread stages and launches sub-batch 0 — at most kMaxHelped sub-batches, calls of at least 512 KB of queries
+constexpr uint64_t kMaxHelped = 8;
+constexpr uint64_t kHelpersMinBytes = 512u << 10;
+struct HostCallOptions {
+    uint32_t host_lanes = 0;        // 0 = default (six)
+    bool host_zero_copy = true, host_stage_helpers = true;
+};
+struct HostCallPlan {
+    uint32_t nlanes = 0;        // lanes (stream + workspace + pinned staging each) the sub-batches travel through
+    bool zero_copy = false;     // the preparation reads the queries from page-locked host memory in place
+    bool helpers = false;       // helper threads are wanted for sub-batches 1.. (the caller still has to get them started)
+    bool latency_first = false; // every sub-batch takes the short-chain scan kernel
+};
+inline HostCallPlan host_call_plan(uint64_t nq, bool in_pinned, size_t query_bytes, uint64_t nsub, const HostCallOptions& o) {
+    HostCallPlan p;
+    p.nlanes = (uint32_t)std::min<uint64_t>(nsub, o.host_lanes ? o.host_lanes : 6u);
+    p.zero_copy = o.host_zero_copy && nq >= kZeroCopyMinQueries && nq <= (in_pinned ? kZeroCopyMaxPinned : kZeroCopyMaxPageable);
+    p.helpers = !in_pinned && o.host_stage_helpers && nsub >= 2 && nsub <= p.nlanes && nsub <= kMaxHelped && query_bytes >= kHelpersMinBytes;
+    p.latency_first = nq < kHostWaveMinQueries;
+    return p;
+}
+
 // The argument errors of rbq_mstg_search_batch* and rbq_mstg_search_refined_batch* (include/rbq_mstg.h), in their order; no
 // device is needed to find any of them.  RBQ_OK with *done set: the call is answered as it stands (nq == 0).
 struct MstgSearchArgs {
