@@ -97,13 +97,21 @@ def _base_refs(metric, bits, dim, n, nprobe=6):
     return built, q, radii, refs
 
 
-def _base(metric, bits, dim, n):
+def _base(metric, bits, dim, n, range_kernel=False):
     nprobe = 6
     built, q, radii, refs = _base_refs(metric, bits, dim, n, nprobe)
     idx = rq.IvfRabitqIndex.from_built(built)
     try:
         for r, ref in zip(radii, refs):
             cap = max(len(x[0]) for x in ref) + 3
+            if range_kernel:  # the stage probe while the option is on (nothing is launched): k_range — 256 threads, no scratch
+                assert built.padded_dim == dim
+                idx.set_range_search(r)
+                try:
+                    res = idx.stage_resources(len(q), cap, nprobe)["scan"]
+                finally:
+                    idx.set_range_search(None)
+                assert res["workgroups"] == len(q) and res["threads"] == 256 and res["scratch_bytes"] == 0, res
             _same(_call(idx, q, r, nprobe, cap), ref, cap, what=f"radius {r}")
             _same(_call(idx, q, r, nprobe, cap, diag=False), ref, cap, diag=False, what=f"radius {r}, no diagnostics")
     finally:
@@ -119,6 +127,20 @@ def test_base_shape(metric, bits, dim):
 
 def test_dim_960():
     _base(0, 7, 960, 2000)
+
+
+# the other compile-time instantiations, k_range<768, *> and k_range<960, 0 / 2> (k_range.hip: launch_range_d), and that it is
+# k_range the stage probe reports for them
+@pytest.mark.parametrize("bits", [1, 3, 7])
+@pytest.mark.parametrize("metric", [0, 1], ids=["L2", "IP"])
+def test_dim_768(metric, bits):
+    _base(metric, bits, 768, 2000, range_kernel=True)
+
+
+@pytest.mark.parametrize("bits", [1, 3])
+@pytest.mark.parametrize("metric", [0, 1], ids=["L2", "IP"])
+def test_dim_960_one_and_three_bits(metric, bits):
+    _base(metric, bits, 960, 2000, range_kernel=True)
 
 
 # ---- 2. capacity ------------------------------------------------------------------------------------------------------------------

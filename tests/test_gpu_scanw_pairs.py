@@ -10,8 +10,9 @@ k_scanw (`scan_wave = 1`) against k_scan (`scan_wave = 0`) bit for bit (`_both_k
   is infinite, every vector of the tile is wanted), lists shorter than eight vectors and shorter than top_k, tie-heavy data
   (the replay and the exact-heap restart), a filtered call, twelve streams at once;
 * top_k 100 (two registers per lane: the loop of rounds as it was) beside them.
-Both kernels give the same results by construction, so these tests cannot tell which one served a call: that a k_scanw
-instantiation is launched at all (16 bytes of scratch at the most) is read from profiles/scanw_pairs_lds/kernel_resources.txt."""
+Both kernels give the same results by construction, so the results of these tests do not tell which one served a call; the
+stage probe does (`stage_resources(...)["scan"]`: 64 threads and 16 bytes of scratch at the most is k_scanw, 256 threads k_scan),
+and tests/test_gpu_scan_instantiations.py asserts it for every compile-time instantiation, these among them."""
 import functools
 
 import numpy as np
