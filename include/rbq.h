@@ -189,6 +189,20 @@ uint32_t rbq_index_device_count(const rbq_index* idx); /* number of replicas */
  * matches and may exceed top_k: that is how a caller sees truncation.  The first min(total, top_k) matches in scan order (probe
  * order, then position inside the list; not sorted by score) are written, the other slots are UINT64_MAX / NaN.  diag counts as in
  * that loop and does not depend on top_k.  Errors and the top_k == 0 case are as above.
+ * EXACT RANGE SEARCH (options "range_exact" 1 with the exact radius x of "range_exact_radius_bits", while "range_search" is 1, raw
+ * vectors are attached with rbq_index_set_rerank_vectors and the option "rerank" is 1): the matches of the range search above at
+ * its radius r — the same call with "range_exact" 0 and the rerank off, at unlimited capacity, in its scan order, with the filter,
+ * numeric variant, "query_dtype" and diagnostic options acting as they do there — are only CANDIDATES.  r stays on the estimate's
+ * scale and bounds the work; with r = +inf (L2) or -inf (inner product) every probed vector that the reference's loop evaluates to
+ * a finite distance is a candidate.  Each candidate id is scored exactly as the rerank scores it (the canonical l2_distance_sqr /
+ * dot of src/math.rs between the caller's unrotated query and raw row id, 16-bit query or row elements widened where they are
+ * loaded, raw rows of any "rerank_raw_dtype"; id >= n_raw scores the NaN 0x7fc00000) and matches iff exact distance < x (L2) or
+ * exact dot product > x (inner product); NaN never matches.  out_counts[q] is the total number of matches and may exceed top_k (the
+ * capacity, <= 2^20); the first min(total, top_k) matches are written in scan order with their EXACT scores, the other slots are
+ * UINT64_MAX / NaN; the same call gives the same rows every time.  diag is that of the candidate call and depends on neither x nor
+ * top_k.  "rerank_pool" is not read in range mode; "range_exact" has no effect while "range_search" is 0.  RBQ_INVALID_CONFIG
+ * (detail set): "range_search" 1 and "range_exact" 1 without raw vectors attached or with "rerank" 0 — nothing is silently
+ * approximated — and "range_search" 1 with the rerank on and "range_exact" 0.
  * 16-BIT QUERIES (option "query_dtype" RBQ_RAW_F16 / RBQ_RAW_BF16, rbq_debug_set_option): `queries` is read as nq rows of
  * query_dim 16-bit elements, 2 * query_dim bytes apart, passed through the `const float*` parameter as they are; query_dim stays a
  * count of elements, every check keeps its order and its text.  An element is widened to f32 exactly where a kernel loads it (f16
@@ -399,7 +413,7 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *                        shortlist's error bound is derived for)
  *   "rank_planar" 1      TEST ONLY: the split-bf16 ranking GEMM reads planar copies of its operands (two planes [rows][D] each,
  *                        de-interleaved per call) instead of the interleaved images — same kernel, same scores bit for bit
- * and seven that are not result-neutral:
+ * and nine that are not result-neutral:
  *   "query_dtype" v      RBQ_RAW_F32 (0, default), RBQ_RAW_F16 or RBQ_RAW_BF16, on every replica: what every entry point that takes
  *                        queries on this handle — rbq_search_batch (one replica or several), rbq_search_batch_device,
  *                        rbq_posting_scan_batch, rbq_mstg_search_batch / _device, rbq_mstg_search_refined_batch / _device — reads
@@ -415,7 +429,12 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *   "range_radius_bits" v  the 32 bits of an f32 radius r, passed through the int (every pattern is accepted; default +inf)
  *   "range_search" 0/1   range search (default 0): rbq_search_batch / rbq_search_batch_device return every vector of the probed
  *                        lists with distance < r (L2) or score > r (inner product), see rbq_search_batch; RBQ_INVALID_CONFIG
- *                        while the rerank is on; the MSTG entry points and MSTG handles ignore it
+ *                        while the rerank is on and "range_exact" is 0; the MSTG entry points and MSTG handles ignore it
+ *   "range_exact" 0/1    exact range search (default 0; see rbq_search_batch): while "range_search" is 1, the estimate's matches
+ *                        at r are candidates, scored exactly against the attached raw rows and kept iff exact distance < x (L2)
+ *                        or exact dot product > x (inner product).  Needs raw vectors attached and "rerank" 1, else the search is
+ *                        RBQ_INVALID_CONFIG; no effect while "range_search" is 0; MSTG handles ignore it
+ *   "range_exact_radius_bits" v  the 32 bits of the f32 x, passed through the int (every pattern is accepted; default +inf)
  *   "numeric_variant" v  rbq_index_set_numeric_variant(idx, v): which build of the reference the scores reproduce
  *   "debug_replica" r    which replica rbq_debug_copy_index / rbq_debug_copy_workspace read */
 int rbq_debug_set_option(rbq_index* idx, const char* name, int value);

@@ -373,6 +373,11 @@ struct Options {
     // scan order, with top_k read as the capacity of the output row and out_counts as the total
     bool range_search = false;
     uint32_t range_radius_bits = 0x7f800000u; // +inf
+    // exact range search: while range_search and range_exact are on (raw vectors attached, rerank 1), the
+    // matches of the estimate at range_radius_bits are only candidates; each is scored exactly against its raw row and kept iff
+    // exact distance < x (L2) or exact dot product > x (inner product), x the f32 of these bits
+    bool range_exact = false;
+    uint32_t range_exact_radius_bits = 0x7f800000u; // +inf
     // option `name` := value (the options of rbq_debug_set_option that live in Options); RBQ_INVALID_CONFIG for an unknown name
     int set(const char* name, int value);
 };

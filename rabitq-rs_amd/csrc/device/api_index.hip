@@ -205,6 +205,8 @@ int Options::set(const char* name, int v) {
     }
     else if (is("range_search")) range_search = v != 0;
     else if (is("range_radius_bits")) range_radius_bits = (uint32_t)v; // the 32 bits of an f32 radius: every pattern is a radius
+    else if (is("range_exact")) range_exact = v != 0; // (acts while range_search is on: DESIGN.md section 33)
+    else if (is("range_exact_radius_bits")) range_exact_radius_bits = (uint32_t)v; // the 32 bits of an f32: every pattern is accepted
     else return fail(RBQ_INVALID_CONFIG, std::string("unknown option ") + name);
     return RBQ_OK;
 }
@@ -821,6 +823,12 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
     if (!std::strcmp(name, "query_dtype")) { // (not an array: the option "query_dtype" as the handle holds it, one int32)
         if (bytes != 4) return fail(RBQ_INVALID_CONFIG, "query_dtype is one int32");
         const int32_t v = h->reps[0]->opt.query_dtype;
+        std::memcpy(dst, &v, 4);
+        return RBQ_OK;
+    }
+    if (!std::strcmp(name, "metric")) { // (not an array: the handle's metric as one int32, 0 = L2, 1 = inner product)
+        if (bytes != 4) return fail(RBQ_INVALID_CONFIG, "metric is one int32");
+        const int32_t v = (int32_t)h->reps[0]->metric;
         std::memcpy(dst, &v, 4);
         return RBQ_OK;
     }

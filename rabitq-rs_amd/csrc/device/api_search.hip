@@ -130,11 +130,13 @@ int scan_stage(Replica* ix, Workspace* w, const rbq_host::SearchPlan& plan, uint
 
 // k_range launch: the range search's stage, where a top-k call has scan_stage.  `cap` = the capacity of a query's output row.  No heap
 // workspace, no tie log and no dead_skipped: the range path selects eagerly, so every probed list is in the stream.
-int range_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, uint32_t cap, uint64_t wl_stride,
+// While the option range_exact is on (search_device has checked that raw vectors are attached and the rerank is on) the exact
+// variant is launched: the same parameters, plus the caller's queries, the raw rows and the exact radius x.
+int range_stage(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t probe_stride, uint32_t cap, uint64_t wl_stride,
                 const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
                 rbq_diag* d_diag, hipStream_t stream) {
     ProfScope ps(ix, 3, stream, /*ext=*/true); // (the profile stage "scan" times k_range while the option is on)
-    RangeParams P;
+    RangeExactParams P; // (the estimate-only launch takes its RangeParams part)
     P.blocks = (const uint8_t*)ix->blocks.p; P.ids = (const uint64_t*)ix->ids.p; P.ex_codes = (const uint8_t*)ix->ex.p;
     P.f_add_ex = (const float*)ix->fadd_ex.p; P.f_rescale_ex = (const float*)ix->fres_ex.p;
     P.lut = (const uint8_t*)w->lut.p; P.rot = (const float*)w->rot.p; P.consts = (const QueryConsts*)w->consts.p;
@@ -150,7 +152,15 @@ int range_stage(Replica* ix, Workspace* w, uint64_t nq, uint32_t probe_stride, u
     float r;
     std::memcpy(&r, &ix->opt.range_radius_bits, 4);
     P.R = ix->metric == 0 ? r : -r;
-    HIP_TRY(launch_range(P, (uint32_t)nq, ix->device, stream, ps.start(), ps.stop()));
+    if (!ix->opt.range_exact) {
+        HIP_TRY(launch_range(P, (uint32_t)nq, ix->device, stream, ps.start(), ps.stop()));
+        return RBQ_OK;
+    }
+    // r stays on the estimate's scale and bounds the work; x is compared with the exact score itself (distance < x, dot > x)
+    P.queries = d_queries; P.query_dtype = ix->opt.query_dtype; P.raw = ix->raw.p; P.raw_dtype = ix->raw_dtype; P.n_raw = ix->n_raw;
+    P.dim = ix->dim;
+    std::memcpy(&P.X, &ix->opt.range_exact_radius_bits, 4);
+    HIP_TRY(launch_range_exact(P, (uint32_t)nq, ix->device, stream, ps.start(), ps.stop()));
     return RBQ_OK;
 }
 
@@ -283,7 +293,7 @@ int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, 
         if (top_k > kTopKHardMax) return fail(RBQ_INVALID_CONFIG, "range search: the capacity of a query's row is at most 2^20");
         if ((rc = search_front(ix, w, plan, d_queries, nq, top_k, d_filter, filter_nbits, d_diag, stream))) return rc;
         if (plan.stage_mask & 8u)
-            return range_stage(ix, w, nq, plan.nprobe, top_k, plan.wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag, stream);
+            return range_stage(ix, w, d_queries, nq, plan.nprobe, top_k, plan.wl_stride, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag, stream);
         return RBQ_OK;
     }
     // the 8 GiB bound is the global-memory heap's (top_k beyond what the LDS holds); calls whose heap lives in LDS need no workspace
@@ -307,8 +317,18 @@ int search_core(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, 
 int search_device(Replica* ix, Workspace* w, const float* d_queries, uint64_t nq, uint32_t top_k, uint32_t nprobe,
                   const uint32_t* d_filter, uint64_t filter_nbits, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
                   rbq_diag* d_diag, hipStream_t stream) {
-    if (range_on(ix) && ix->rerank)
-        return fail(RBQ_INVALID_CONFIG, "range search does not run with the rerank on: set the option rerank 0 or detach the vectors");
+    if (range_on(ix)) {
+        // the exact range search (option range_exact) decides a match by the raw rows: it runs with the rerank
+        // on and only then — nothing is silently approximated.  rerank_pool is not read in range mode.
+        if (ix->opt.range_exact) {
+            if (!ix->rerank)
+                return fail(RBQ_INVALID_CONFIG, ix->raw.p ? "exact range search needs the rerank on: set the option rerank 1 or range_exact 0"
+                                                          : "exact range search needs raw vectors attached (rbq_index_set_rerank_vectors) or range_exact 0");
+            return search_core(ix, w, d_queries, nq, top_k, nprobe, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag, stream, /*rerank=*/false);
+        }
+        if (ix->rerank)
+            return fail(RBQ_INVALID_CONFIG, "range search does not run with the rerank on: set the option rerank 0 or detach the vectors");
+    }
     const uint32_t pool = ix->opt.rerank_pool;
     if (!ix->rerank || pool <= top_k)
         return search_core(ix, w, d_queries, nq, top_k, nprobe, d_filter, filter_nbits, d_ids, d_scores, d_counts, d_diag, stream, ix->rerank);

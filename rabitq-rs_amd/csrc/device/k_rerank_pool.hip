@@ -4,9 +4,10 @@
 // the kernel of the unpooled rerank; what this one returns for pool <= 1024 is the head of k_rerank's result at top_k := pool.
 //
 //   k_rerank_pool<IP, RAW>   one workgroup (4 waves) per query.  RAW: the element the raw rows are kept in (kRawF32, or kRawF16 /
-//     kRawBf16: rp_score16 below, DESIGN.md section 28 — a 16-bit element is widened exactly and enters the same chains); what
+//     kRawBf16: rp_score16, DESIGN.md section 28 — a 16-bit element is widened exactly and enters the same chains); what
 //     follows describes the f32 rows.
-//     S  the exact score, the bits of canon_l2 / canon_dot (kernels.hpp).  Eight lanes serve one candidate, lane j of the eight
+//     S  the exact score, the bits of canon_l2 / canon_dot (kernels.hpp): rp_score_row of rerank_score.hpp, the one copy of the
+//        scorer, which the exact range scan (range.hpp) calls too.  Eight lanes serve one candidate, lane j of the eight
 //        owns accumulator j: a wave scores 8 candidates at a time, the workgroup 32.  The raw row is NOT read the way the
 //        accumulators consume it (lane j element 8 m + j: 4 bytes per lane, 32 bytes per candidate and load): each lane loads 16
 //        bytes, the eight lanes one contiguous 128-byte span of the row, kRpSpans spans per step and the next step's already in
@@ -30,132 +31,9 @@
 
 #pragma clang fp contract(off)
 
+#include "rerank_score.hpp" // (after the pragma: the scorer's sums are unfused)
+
 namespace rbq {
-
-constexpr uint32_t kRpSpans = 4; // 128-byte spans of a row per candidate and step (twice that in flight)
-
-// component c of (x, y, z, w) as two levels of selects (no branch: every operand is already in a register)
-__device__ __forceinline__ float rp_pick(float x, float y, float z, float w, uint32_t c) {
-    const bool odd = (c & 1u) != 0u, high = (c & 2u) != 0u;
-    const float lo = odd ? y : x, hi = odd ? w : z;
-    return high ? hi : lo;
-}
-// 16 bytes at a 4-byte aligned address, one load
-__device__ __forceinline__ float4 rp_load16(const float* p) {
-    struct __attribute__((packed, aligned(4))) F4 { float x, y, z, w; };
-    const F4 v = *reinterpret_cast<const F4*>(p);
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-
-// ---- rows of 16-bit elements (RAW = kRawF16 / kRawBf16) --------------------------------------------------
-// eight 16-bit elements at a 4-byte aligned address, one load
-__device__ __forceinline__ uint4 rp_load16h(const uint16_t* p) {
-    struct __attribute__((packed, aligned(4))) U4 { uint32_t x, y, z, w; };
-    const U4 v = *reinterpret_cast<const U4*>(p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-// the two elements of a dword (the lower half is the element at the lower address), widened exactly
-template <int RAW>
-__device__ __forceinline__ float rp_widen_lo(uint32_t d) {
-    if (RAW == kRawF16) return (float)__builtin_bit_cast(_Float16, (uint16_t)d);
-    return __uint_as_float(d << 16);
-}
-template <int RAW>
-__device__ __forceinline__ float rp_widen_hi(uint32_t d) {
-    if (RAW == kRawF16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(d >> 16));
-    return __uint_as_float(d & 0xffff0000u);
-}
-template <int RAW>
-__device__ __forceinline__ float rp_widen(uint16_t h) {
-    return rp_widen_lo<RAW>(h);
-}
-template <bool IP>
-__device__ __forceinline__ float rp_add(float acc, float a, float b) {
-    float p;
-    if (IP) {
-        p = a * b;
-    } else {
-        const float d = a - b;
-        p = d * d;
-    }
-    return acc + p;
-}
-// The 8 x 8 transpose of 16-bit elements over the eight lanes of a group.  In: lane l holds chunk l of a span, elements 2k, 2k+1 in
-// d[k].  Out: lane j holds element j of chunk m in half m & 1 of d[m >> 1].  Three exchanges of half of the lane's data with the
-// lane at distance 4, 2, 1: two dwords through ds_swizzle, two through a quad permute (DPP), then the four dwords through a quad
-// permute and one v_perm_b32 each that keeps the own half and takes the partner's.  The picks are selects on lane constants
-// (b0, b1, b2: the bits of the lane's index in its group; sel: the v_perm selector of its parity).  Every lane of the wave runs this.
-__device__ __forceinline__ void rp_transpose8x8(uint32_t (&d)[4], bool b0, bool b1, bool b2, uint32_t sel) {
-    const uint32_t s0 = b2 ? d[0] : d[2], s1 = b2 ? d[1] : d[3];
-    const uint32_t r0 = (uint32_t)__builtin_amdgcn_ds_swizzle((int)s0, 0x101f); // lane ^ 4
-    const uint32_t r1 = (uint32_t)__builtin_amdgcn_ds_swizzle((int)s1, 0x101f);
-    const uint32_t a00 = b2 ? r0 : d[0], a01 = b2 ? r1 : d[1], a10 = b2 ? d[2] : r0, a11 = b2 ? d[3] : r1;
-    const uint32_t t0 = b1 ? a00 : a01, t1 = b1 ? a10 : a11;
-    const uint32_t u0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t0, 0x4e, 0xf, 0xf, false); // quad_perm [2,3,0,1]: lane ^ 2
-    const uint32_t u1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t1, 0x4e, 0xf, 0xf, false);
-    const uint32_t x[4] = {b1 ? u0 : a00, b1 ? a01 : u0, b1 ? u1 : a10, b1 ? a11 : u1};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x[k], 0xb1, 0xf, 0xf, false); // quad_perm [1,0,3,2]: lane ^ 1
-        d[k] = __builtin_amdgcn_perm(y, x[k], sel);
-    }
-}
-// The canonical score of one row of 16-bit elements on the eight lanes of a group (lane j: accumulator j), the same chains as the
-// f32 rows take.  Span path (every row starts 4-byte aligned): a span is 64 elements, lane l loads chunk l (16 bytes), the transpose
-// hands lane j element j of the chunks m = 0 .. 7, which it adds in that order.  A span that does not lie wholly inside the row's
-// main part is replaced by the row's first 16 bytes and never accumulated.  by_element (rows at 2 mod 4; wave-uniform, the slow
-// path): lane j loads its elements 8 m + j two bytes at a time.  Either way nothing outside the row is read.
-template <bool IP, int RAW>
-__device__ __forceinline__ float rp_score16(const uint16_t* row, const float* sq, uint32_t dim, uint32_t j, uint32_t base, bool by_element) {
-    const uint32_t Dmain = dim & ~7u;
-    float acc = 0.0f;
-    if (by_element) {
-        constexpr uint32_t KB = 8; // loads in flight per lane
-        for (uint32_t i0 = j; i0 < Dmain; i0 += 8u * KB) {
-            uint16_t h[KB];
-#pragma unroll
-            for (uint32_t k = 0; k < KB; ++k) h[k] = row[i0 + 8u * k < Dmain ? i0 + 8u * k : 0u];
-#pragma unroll
-            for (uint32_t k = 0; k < KB; ++k)
-                if (i0 - j + 8u * k < Dmain) acc = rp_add<IP>(acc, sq[i0 + 8u * k], rp_widen<RAW>(h[k]));
-        }
-    } else {
-        const bool b0 = (j & 1u) != 0u, b1 = (j & 2u) != 0u, b2 = (j & 4u) != 0u;
-        const uint32_t sel = b0 ? 0x03020706u : 0x05040100u;
-        auto load_spans = [&](uint4* v, uint32_t e0) {
-#pragma unroll
-            for (uint32_t s = 0; s < kRpSpans; ++s) {
-                const uint32_t e = e0 + 64u * s + 8u * j;
-                v[s] = rp_load16h(row + (e + 8u <= Dmain ? e : 0u));
-            }
-        };
-        uint4 v[kRpSpans], nx[kRpSpans];
-        if (Dmain) load_spans(v, 0u);
-        for (uint32_t e0 = 0; e0 < Dmain; e0 += 64u * kRpSpans) {
-            load_spans(nx, e0 + 64u * kRpSpans); // the next spans travel while these are consumed
-#pragma unroll
-            for (uint32_t s = 0; s < kRpSpans; ++s) {
-                uint32_t d[4] = {v[s].x, v[s].y, v[s].z, v[s].w};
-                rp_transpose8x8(d, b0, b1, b2, sel);
-#pragma unroll
-                for (uint32_t m = 0; m < 8u; ++m) {
-                    const uint32_t c0 = e0 + 64u * s + 8u * m; // chunk of eight elements (wave-uniform)
-                    if (c0 < Dmain) acc = rp_add<IP>(acc, sq[c0 + j], (m & 1u) ? rp_widen_hi<RAW>(d[m >> 1]) : rp_widen_lo<RAW>(d[m >> 1]));
-                }
-            }
-#pragma unroll
-            for (uint32_t s = 0; s < kRpSpans; ++s) v[s] = nx[s];
-        }
-    }
-    float sum = 0.0f;
-    if (Dmain) {
-        sum = -0.0f;
-#pragma unroll
-        for (uint32_t l = 0; l < 8u; ++l) sum = sum + __shfl(acc, (int)(base | l));
-    }
-    for (uint32_t i = Dmain; i < dim; ++i) sum = rp_add<IP>(sum, sq[i], rp_widen<RAW>(row[i]));
-    return sum;
-}
 
 template <bool IP, int RAW>
 __global__ __launch_bounds__(kThreads) void k_rerank_pool(RerankPoolParams P) {
@@ -163,7 +41,7 @@ __global__ __launch_bounds__(kThreads) void k_rerank_pool(RerankPoolParams P) {
     float* sq = reinterpret_cast<float*>(smraw);                                                    // [dim]
     unsigned long long* key = reinterpret_cast<unsigned long long*>(sq + ((P.dim + 1u) & ~1u));     // [np2]
     const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t dim = P.dim, Dmain = dim & ~7u;
+    const uint32_t dim = P.dim;
     const uint32_t cnt = min(P.pool_counts[q], P.pool);
     uint32_t np2 = 1;
     while (np2 < cnt) np2 <<= 1; // <= np2(pool), what the launch sized the LDS for
@@ -174,79 +52,12 @@ __global__ __launch_bounds__(kThreads) void k_rerank_pool(RerankPoolParams P) {
 
     // ---- S: eight lanes per candidate, wave-uniform trip counts (a group without a candidate writes nothing)
     const uint32_t j = lane & 7u, grp = lane >> 3, base = lane & ~7u;
-    const uint32_t jq = j & 3u, jh = j >> 2;
     for (uint32_t r0 = wave * 8u; r0 < cnt; r0 += (kThreads / 64u) * 8u) {
         const uint32_t r = r0 + grp;
         const bool have = r < cnt;
         const uint64_t id = have ? pid[r] : ~0ull;
         const bool act = have && id < P.n_raw;
-        float sum = 0.0f;
-        if constexpr (RAW == kRawF32) {
-        const float* row = (const float*)P.raw + (act ? (size_t)id * dim : (size_t)0); // (no candidate, or no raw row: row 0, read and discarded)
-        float acc = 0.0f;
-        // This lane's 16 bytes of the kRpSpans spans that start at element e0.  Every lane loads, without a branch: a span that does not
-        // lie wholly in the row's main part is replaced by the row's first 16 bytes (Dmain >= 8 here; its chunks are never
-        // accumulated), and a lane group without a candidate reads row 0 (n_raw >= 1) and writes nothing.
-        auto load_spans = [&](float4* v, uint32_t e0) {
-#pragma unroll
-            for (uint32_t s = 0; s < kRpSpans; ++s) {
-                const uint32_t e = e0 + 32u * s + 4u * j;
-                v[s] = rp_load16(row + (e + 4u <= Dmain ? e : 0u));
-            }
-        };
-        float4 v[kRpSpans], nx[kRpSpans];
-        if (Dmain) load_spans(v, 0u);
-        for (uint32_t e0 = 0; e0 < Dmain; e0 += 32u * kRpSpans) {
-            load_spans(nx, e0 + 32u * kRpSpans); // the next spans travel while these are consumed
-#pragma unroll
-            for (uint32_t s = 0; s < kRpSpans; ++s) {
-                float w[4];
-#pragma unroll
-                for (uint32_t t = 0; t < 4u; ++t) {
-                    const float mine = rp_pick(v[s].x, v[s].y, v[s].z, v[s].w, ((j >> 1) - t) & 3u);
-                    const uint32_t m = (t + jq) & 3u;
-                    w[t] = __shfl(mine, (int)(base | (2u * m + jh)));
-                }
-#pragma unroll
-                for (uint32_t m = 0; m < 4u; ++m) {
-                    const uint32_t c0 = e0 + 32u * s + 8u * m; // chunk of eight elements (wave-uniform)
-                    if (c0 < Dmain) {
-                        const float b = rp_pick(w[0], w[1], w[2], w[3], (m - jq) & 3u);
-                        const float a = sq[c0 + j];
-                        float p;
-                        if (IP) {
-                            p = a * b;
-                        } else {
-                            const float d = a - b;
-                            p = d * d;
-                        }
-                        acc = acc + p;
-                    }
-                }
-            }
-#pragma unroll
-            for (uint32_t s = 0; s < kRpSpans; ++s) v[s] = nx[s];
-        }
-        if (Dmain) {
-            sum = -0.0f;
-#pragma unroll
-            for (uint32_t l = 0; l < 8u; ++l) sum = sum + __shfl(acc, (int)(base | l));
-        }
-        for (uint32_t i = Dmain; i < dim; ++i) {
-            const float a = sq[i], b = row[i];
-            float p;
-            if (IP) {
-                p = a * b;
-            } else {
-                const float d = a - b;
-                p = d * d;
-            }
-            sum = sum + p;
-        }
-        } else {
-            const uint16_t* row = (const uint16_t*)P.raw + (act ? (size_t)id * dim : (size_t)0); // (as above: row 0 stands in)
-            sum = rp_score16<IP, RAW>(row, sq, dim, j, base, P.raw_by_element != 0u);
-        }
+        const float sum = rp_score_row<IP, RAW>(P.raw, id, act, sq, dim, j, base, P.raw_by_element != 0u); // (no candidate, or no raw row: row 0, read and discarded)
         if (have && j == 0u) {
             int32_t k = total_key(act ? sum : __int_as_float(0x7fc00000));
             if (IP) k = ~k;

@@ -4,6 +4,7 @@
 //   k_query.hip  k_prep / k_prep_wave, k_rank_* , k_select*, k_probes_given     (kernels.hpp, rank_mfma.hpp, canon_score.hpp, select_*.hpp)
 //   k_scan.hip   k_scan<DT, EX, TR>                                               (scan.hpp, scan_codes.hpp, topk.hpp)
 //   k_range.hip  k_range<DT, EX>: the range search's scan against a constant radius     (range.hpp, scan_codes.hpp)
+//   k_range_exact.hip  k_range<0, 0, V, XR, XIP>: the same scan, its matches decided by the raw rows  (range.hpp, rerank_score.hpp)
 //   k_build.hip  encoder, reference-layout -> device-layout converters, sorting   (encode.hpp)
 //   k_gemm_shortlist.hip  the front of the GEMM-shortlist paths (finite check, norms, split images, dots), KmGemmAssign (km_common.hpp)
 //   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver         (km_common.hpp)
@@ -17,7 +18,7 @@
 //   k_load.hip   streamed RBQ1 loader: spans of the stream -> device layout, ex-code prefix check
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, canon_score.hpp)
 //   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan_codes.hpp)
-//   k_rerank_pool.hip  pooled rerank: exact scores of a candidate pool from whole lines of the raw rows, order in LDS (kernels.hpp)
+//   k_rerank_pool.hip  pooled rerank: exact scores of a candidate pool from whole lines of the raw rows, order in LDS (rerank_score.hpp)
 //   k_append.hip rbq_index_append: carry of an index into a larger geometry, id bound, nearest list of rotated rows (km_common.hpp)
 //   k_remove.hip rbq_index_remove_ids: keep masks against a sorted id set, slot map, gather of an index into a smaller geometry
 #pragma once
@@ -184,6 +185,9 @@ hipError_t launch_scan(const ScanParams& P, uint32_t nq, int device, hipStream_t
 // to it when ScanParams::wave_kernel is set and it serves the call)
 // k_range (range.hpp, k_range.hip): the range search's scan — the same stream against a constant threshold, matches in scan order
 hipError_t launch_range(const RangeParams& P, uint32_t nq, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+// the exact range scan (k_range_exact.hip): the estimate's matches scored against their raw rows, kept by the exact score.
+// hipErrorInvalidValue without raw rows (raw null or n_raw 0), for an unknown raw_dtype, or when the LDS does not fit
+hipError_t launch_range_exact(const RangeExactParams& P, uint32_t nq, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 bool scanw_serves(const ScanParams& P);
 hipError_t launch_scanw(const ScanParams& P, uint32_t nq, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 

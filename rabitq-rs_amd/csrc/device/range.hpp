@@ -15,16 +15,31 @@
 //      and written at (matches so far + rank) while that is below the capacity; the count runs on.
 // The append position is a function of the stream alone (tile, half-wave, lane), never of wave timing: the same call gives the same
 // rows every time.
+//
+// The exact variant (XR = the element of the attached raw rows, kRawF32 / kRawF16 / kRawBf16; XIP = inner product; options
+// range_exact / range_exact_radius_bits; instantiated in k_range_exact.hip): the matches of step 5 are only
+// CANDIDATES.  Per tile that has one:
+//   6. the candidates' ids are compacted in stream order (the prefix over the waves' match masks of step 5);
+//   7. groups of eight lanes score one candidate each, 32 per round, exactly against its raw row: the chains of k_rerank_pool
+//      (rerank_score.hpp) between the caller's unrotated query, held in LDS widened to f32, and the row; id >= n_raw scores NaN;
+//   8. every candidate lane tests ITS exact score against X (distance < X, or dot > X for inner product; NaN never passes); a second
+//      prefix over the waves' hit masks gives the write position (hits so far + rank), and the exact score is what is written.
+// The total counts hits; SearchDiagnostics are those of steps 1 - 5 and depend on neither X nor the capacity.  A tile without a
+// candidate costs nothing beyond step 5 (the test is uniform).  XR = kRangeEstimate compiles to the kernel without steps 6 - 8.
 #pragma once
+#include <type_traits>
+
 #include "kernels.hpp"
 #include "scan_codes.hpp"
+#include "rerank_score.hpp"
 
 namespace rbq {
 
 // EX: compile-time ex_bits (0/2/6) when DT != 0; ignored (runtime P.ex_bits) when DT == 0.  V: numeric variant, instantiated for the
 // runtime-dimension kernel only (as k_scan).
-template <int DT, int EX, int V = kVarAvx512>
-__global__ __launch_bounds__(kRangeThreads) void k_range(RangeParams P) {
+template <int DT, int EX, int V = kVarAvx512, int XR = kRangeEstimate, bool XIP = false>
+__global__ __launch_bounds__(kRangeThreads) void k_range(std::conditional_t<XR == kRangeEstimate, RangeParams, RangeExactParams> P) {
+    constexpr bool kExact = XR != kRangeEstimate;
     extern __shared__ __align__(16) unsigned char smraw[];
     const uint32_t Dc = DT ? (uint32_t)DT : P.Dc; // code/LUT dimension (x64)
     const uint32_t D = DT ? (uint32_t)DT : P.D;   // padded_dim (ex codes, rotated query)
@@ -39,6 +54,11 @@ __global__ __launch_bounds__(kRangeThreads) void k_range(RangeParams P) {
     uint32_t* s_mask = reinterpret_cast<uint32_t*>(c_d + kRangeCand); // [2][kRangeBlocks] survivor masks (buffer = tile & 1)
     uint32_t* s_wcnt = s_mask + 2 * kRangeBlocks;                     // [4] matches per wave | [4] finite distances per wave
     uint32_t* s_nskip = s_wcnt + 8;
+    // the exact variant's region (types.hpp: range_exact_lds_bytes), 16-byte aligned; never touched when !kExact
+    unsigned long long* x_id = reinterpret_cast<unsigned long long*>(s_nskip + 4); // [kRangeCand] the tile's candidates, stream order
+    float* x_sc = reinterpret_cast<float*>(x_id + kRangeCand);                     // [kRangeCand] their exact scores
+    uint32_t* s_hcnt = reinterpret_cast<uint32_t*>(x_sc + kRangeCand);             // [4] hits per wave
+    float* x_q = reinterpret_cast<float*>(s_hcnt + 4);                             // [dim] the caller's query, widened
     // no static __shared__ in this kernel: the dynamic region must start at LDS address 0 (see lds_lut_ptr)
     const lds_lut_ptr lut0 = (lds_lut_ptr)(uint32_t)0; // == s_lut
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smraw != 0u) __builtin_trap();
@@ -58,6 +78,7 @@ __global__ __launch_bounds__(kRangeThreads) void k_range(RangeParams P) {
         float4* rd = reinterpret_cast<float4*>(s_q);
         for (uint32_t i = tid; i < qlen / 4; i += kRangeThreads) rd[i] = i < D / 4 ? rs[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (tid == 0) *s_nskip = 0;
+        if constexpr (kExact) copy_query_widened<kRangeThreads>(x_q, P.queries, P.query_dtype, (size_t)q * P.dim, P.dim, tid);
     }
     const QueryConsts qc = P.consts[q];
     const ProbeInfo* probe = P.probe + (size_t)q * P.nprobe;
@@ -187,14 +208,61 @@ __global__ __launch_bounds__(kRangeThreads) void k_range(RangeParams P) {
             tm += c;
             tf += s_wcnt[4 + j];
         }
-        if (match) {
-            const uint32_t at = total + wbase + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull));
-            if (at < cap) { // the count runs on past the capacity; writes at or beyond it are dropped
-                P.out_ids[(size_t)q * cap + at] = P.ids[slot];
-                P.out_scores[(size_t)q * cap + at] = P.metric == 0 ? d : -d;
+        if constexpr (!kExact) {
+            if (match) {
+                const uint32_t at = total + wbase + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull));
+                if (at < cap) { // the count runs on past the capacity; writes at or beyond it are dropped
+                    P.out_ids[(size_t)q * cap + at] = P.ids[slot];
+                    P.out_scores[(size_t)q * cap + at] = P.metric == 0 ? d : -d;
+                }
             }
+            n_ext += S; n_est += tf; total += tm;
+        } else {
+            n_ext += S; n_est += tf;
+            if (tm == 0) continue; // (uniform) no candidate in this tile
+            // ------------------------------------------------------------ the candidates' ids, compacted in stream order
+            const uint32_t mp = wbase + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull)); // < tm <= kRangeCand
+            unsigned long long id = 0;
+            if (match) { id = P.ids[slot]; x_id[mp] = id; }
+            lds_barrier(); // E: the candidates' ids
+            // ------------------------------------------------------------ exact scores: eight lanes per candidate, 32 per round
+            {
+                const uint32_t j = lane & 7u, gbase = lane & ~7u;
+                for (uint32_t c0 = 0; c0 < tm; c0 += (uint32_t)(kRangeThreads / 8)) { // (uniform trip count: every lane scores)
+                    const uint32_t c = c0 + (tid >> 3);
+                    const bool have = c < tm;
+                    const unsigned long long cid = have ? x_id[c] : ~0ull;
+                    const bool act = have && cid < P.n_raw;
+                    const float sum = rp_score_row<XIP, kExact ? XR : kRawF32>(P.raw, cid, act, x_q, P.dim, j, gbase, P.raw_by_element != 0u);
+                    if (have && j == 0u) x_sc[c] = act ? sum : __int_as_float(0x7fc00000);
+                }
+            }
+            lds_barrier(); // F: the exact scores
+            float xs = 0.0f;
+            bool hit = false;
+            if (match) {
+                xs = x_sc[mp];
+                hit = XIP ? xs > P.X : xs < P.X; // (a NaN score, and any score against a NaN X, never passes)
+            }
+            const unsigned long long bh = __ballot(hit);
+            if (lane == 0) s_hcnt[wave] = (uint32_t)__popcll(bh);
+            lds_barrier(); // G: the waves' hit counts
+            uint32_t hbase = 0, th = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t c = s_hcnt[w];
+                hbase += (uint32_t)w < wave ? c : 0u;
+                th += c;
+            }
+            if (hit) {
+                const uint32_t at = total + hbase + (uint32_t)__popcll(bh & ((1ull << lane) - 1ull));
+                if (at < cap) { // the count runs on past the capacity; writes at or beyond it are dropped
+                    P.out_ids[(size_t)q * cap + at] = id;
+                    P.out_scores[(size_t)q * cap + at] = xs;
+                }
+            }
+            total += th;
         }
-        n_ext += S; n_est += tf; total += tm;
     }
     if (P.diag && n_skip) atomicAdd(s_nskip, n_skip);
     __syncthreads();

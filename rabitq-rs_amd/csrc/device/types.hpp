@@ -203,6 +203,27 @@ constexpr int kRangeCand = kRangeBlocks * 32;        // candidates per tile
 __host__ __device__ inline size_t range_lds_bytes(uint32_t Dc, uint32_t D, uint32_t ex_bits) {
     return (size_t)Dc * 4 + (size_t)ex_qlen(D, ex_bits) * 4 + (size_t)kRangeCand * 16 + 2 * (size_t)kRangeBlocks * 4 + 8 * 4 + 4 * 4;
 }
+// The exact range scan (options range_exact / range_exact_radius_bits): k_range<..., XR, XIP> scores every match
+// of the estimate exactly against its raw row and keeps those whose exact score passes X.  XR = kRangeEstimate: today's kernel, which
+// takes RangeParams and reads nothing of what follows.
+constexpr int kRangeEstimate = -1;
+struct RangeExactParams : RangeParams {
+    const void* queries = nullptr; // [nq][dim] elements of query_dtype: the caller's unrotated queries
+    const void* raw = nullptr;     // [n_raw][dim] elements of raw_dtype (n_raw >= 1)
+    uint64_t n_raw = 0;
+    uint32_t dim = 0;
+    int query_dtype = kRawF32;
+    int raw_dtype = kRawF32;       // host-side dispatch only: picks the instantiation
+    uint32_t raw_by_element = 0;   // set by the launch: 16-bit rows that do not all start 4-byte aligned (odd dim, or raw at 2 mod 4)
+    float X = 0.0f;                // a candidate matches iff exact distance < X (L2) or exact dot > X (inner product)
+};
+// LDS carve-up of the exact variant: k_range's region above (a multiple of 16 bytes), then
+//   id[kRangeCand] u64 (a tile's matches of the estimate, stream order) | exact score[kRangeCand] f32 | hits per wave [4] u32 |
+//   query[dim] f32 (the caller's, widened)
+// 8 KiB of LUT + 8 KiB of rotated query + 4 KiB of survivors + 3 KiB + 8 KiB of query at padded_dim 2048, of the CU's 160 KiB.
+__host__ __device__ inline size_t range_exact_lds_bytes(uint32_t Dc, uint32_t D, uint32_t ex_bits, uint32_t dim) {
+    return range_lds_bytes(Dc, D, ex_bits) + (size_t)kRangeCand * 12 + 4 * 4 + (size_t)dim * 4;
+}
 
 // ---- encoder ----------------------------------------------------------------------------------------------------
 constexpr uint32_t kNoSrc = 0xffffffffu;

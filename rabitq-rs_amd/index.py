@@ -72,6 +72,7 @@ class IvfRabitqIndex:
         self._h = handle
         self._rescale = rescale  # (mode, t_const) the encoder ran with, where this object knows it: add()'s default
         self._range = None       # the radius set_range_search left on the handle (None: range search off)
+        self._range_exact = None  # the exact radius set_range_exact left on the handle (None: off)
 
     # -- construction -------------------------------------------------------------
     @staticmethod
@@ -318,6 +319,7 @@ class IvfRabitqIndex:
         """The handle a mutation returned takes the place of the old one, which is closed."""
         old, self._h = self._h, h
         self._range = None  # (options are per handle: the new one starts with the range search off)
+        self._range_exact = None
         lib().rbq_index_destroy(old)
 
     # -- shrinking (rbq_index_remove_ids) ------------------------------------------------------------------------------
@@ -515,6 +517,49 @@ class IvfRabitqIndex:
             self.set_option("range_search", 1)
         self._range = radius
 
+    # -- exact range search: the estimate's matches are candidates, the raw vectors decide --------
+    def set_range_exact(self, exact_radius):
+        """Options "range_exact_radius_bits" / "range_exact": with an exact radius x (any f32, passed by its bits), a range
+        search (set_range_search) on a handle with raw vectors attached (set_rerank_vectors) treats the estimate's matches at
+        its own radius as candidates, scores each exactly against its raw row and returns those with exact distance < x (L2)
+        or exact dot product > x (inner product), in scan order with their exact scores.  None switches it off and puts x
+        back to +inf.  Without raw vectors attached (or with the option "rerank" 0) the search then raises InvalidConfig."""
+        if exact_radius is None:
+            self.set_option("range_exact", 0)
+            self.set_option("range_exact_radius_bits", 0x7F800000)
+        else:
+            self.set_option("range_exact_radius_bits", int(np.array([exact_radius], np.float32).view(np.int32)[0]))
+            self.set_option("range_exact", 1)
+        self._range_exact = exact_radius
+
+    @contextlib.contextmanager
+    def _range_for_call(self, radius, exact, candidate_radius):
+        """The range options of one call, put back afterwards, error or not.  exact=False: `radius` is the estimate's.
+        exact=True: `radius` is the exact radius x and `candidate_radius` the estimate's r (None: +inf for L2, -inf for inner
+        product — every probed vector is a candidate)."""
+        from . import RabitqError
+        before, before_x = getattr(self, "_range", None), getattr(self, "_range_exact", None)
+        if exact:
+            if candidate_radius is None:
+                m = np.full(1, -1, np.int32)
+                _check(lib().rbq_debug_copy_index(self._h, b"metric", m.ctypes.data, 4))
+                candidate_radius = np.float32(np.inf) if int(m[0]) == 0 else np.float32(-np.inf)
+            r, x = candidate_radius, radius
+        else:
+            if candidate_radius is not None:
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "candidate_radius goes with exact=True")
+            r, x = radius, None
+        touch_x = exact or before_x is not None  # (a plain call on a handle that never had range_exact on sets nothing more than before)
+        try:
+            if touch_x:
+                self.set_range_exact(x)
+            self.set_range_search(r)
+            yield
+        finally:
+            self.set_range_search(before)
+            if touch_x:
+                self.set_range_exact(before_x)
+
     @staticmethod
     def _filter_words(allowed_ids):
         allowed = np.asarray(sorted(set(int(i) for i in allowed_ids)), dtype=np.uint64)
@@ -540,43 +585,42 @@ class IvfRabitqIndex:
                 out_sc[lims[q]:lims[q + 1]] = out_sc[lims[q]:lims[q + 1]][o]
         return lims, out_ids, out_sc
 
-    def range_search(self, queries, radius, nprobe, max_results=None, allowed_ids=None, want_diag=False, sort=False, dtype=None):
+    def range_search(self, queries, radius, nprobe, max_results=None, allowed_ids=None, want_diag=False, sort=False, dtype=None,
+                     exact=False, candidate_radius=None):
         """FAISS-style range_search over the probed lists: (lims [nq + 1] i64, ids u64, scores f32) — query q's matches are
         ids[lims[q]:lims[q + 1]], in scan order, or ascending by (score, scan order) with sort=True.  A match has distance <
         radius (L2) or score > radius (inner product).  max_results=None: complete rows (a first call with rows of 1024; where
         a total exceeds that, one more with rows of the largest total — the totals are exact, so one repeat suffices).
         max_results=m: at most the first m matches of every query, and the totals [nq] u32 as a fourth value.  want_diag: the
         SearchDiagnostics [nq, 3] u64 as the last value.  `allowed_ids` as search_filtered.  The handle's range options are
-        set for the call and put back afterwards.  `queries` and `dtype` as batch_search_raw."""
+        set for the call and put back afterwards.  `queries` and `dtype` as batch_search_raw.
+        exact=True (raw vectors attached with set_rerank_vectors): `radius` is the EXACT radius x — a match has exact distance <
+        x (L2) or exact dot product > x (inner product), and the scores returned are exact — and `candidate_radius` is the
+        estimate's radius r that picks the candidates to score (set_range_exact).  candidate_radius=None: +inf (L2) / -inf
+        (inner product), every probed vector — complete over the probed lists, slow, and the default because it is the one that
+        cannot lose a match.  The diagnostics are those of the candidate scan."""
         from . import SearchParams
         queries, dtype = _marshal.query_arg(queries, dtype)
         words, nbits = self._filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
         cap = max_results or 1024
-        before = getattr(self, "_range", None)
-        self.set_range_search(radius)
-        try:
+        with self._range_for_call(radius, exact, candidate_radius):
             ids, sc, cnt, diag = self.batch_search_raw(queries, SearchParams(cap, nprobe), words, nbits, want_diag, dtype)
             if max_results is None and cnt.size and int(cnt.max()) > cap:
                 ids, sc, cnt, diag = self.batch_search_raw(queries, SearchParams(int(cnt.max()), nprobe), words, nbits, want_diag, dtype)
-        finally:
-            self.set_range_search(before)
         out = self._range_csr(ids, sc, cnt, sort)
         if max_results is not None:
             out += (cnt,)
         return out + (diag,) if want_diag else out
 
     def range_search_device(self, d_queries, nq, query_dim, radius, nprobe, cap, d_ids, d_scores, d_counts, stream=None,
-                            d_filter=None, filter_nbits=0, d_diag=None):
+                            d_filter=None, filter_nbits=0, d_diag=None, exact=False, candidate_radius=None):
         """range_search on device pointers (search_batch_device with the range options set for the call): rows of capacity
         `cap` at d_ids / d_scores, the totals at d_counts, enqueued on `stream` without host synchronisation.  The caller
-        reads d_counts once the stream has got there and repeats with a larger `cap` where a total exceeds it."""
-        before = getattr(self, "_range", None)
-        self.set_range_search(radius)
-        try:
+        reads d_counts once the stream has got there and repeats with a larger `cap` where a total exceeds it.
+        `exact` / `candidate_radius` as range_search."""
+        with self._range_for_call(radius, exact, candidate_radius):
             self.search_batch_device(d_queries, nq, query_dim, cap, nprobe, d_ids, d_scores, d_counts, stream, d_filter,
                                      filter_nbits, d_diag)
-        finally:
-            self.set_range_search(before)
 
     def profile_begin(self, stages=("prep", "rank", "select", "scan"), every=1):
         mask = sum(1 << ("prep", "rank", "select", "scan").index(s) for s in stages)
