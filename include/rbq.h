@@ -413,7 +413,7 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *                        shortlist's error bound is derived for)
  *   "rank_planar" 1      TEST ONLY: the split-bf16 ranking GEMM reads planar copies of its operands (two planes [rows][D] each,
  *                        de-interleaved per call) instead of the interleaved images — same kernel, same scores bit for bit
- * and nine that are not result-neutral:
+ * and ten that are not result-neutral:
  *   "query_dtype" v      RBQ_RAW_F32 (0, default), RBQ_RAW_F16 or RBQ_RAW_BF16, on every replica: what every entry point that takes
  *                        queries on this handle — rbq_search_batch (one replica or several), rbq_search_batch_device,
  *                        rbq_posting_scan_batch, rbq_mstg_search_batch / _device, rbq_mstg_search_refined_batch / _device — reads
@@ -426,6 +426,11 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *                        queries equal those of the same call with "query_dtype" RBQ_RAW_F32 on the rows widened to f32
  *   "rerank" 0/1         the optional full-precision rerank (needs rbq_index_set_rerank_vectors)
  *   "rerank_pool" v      candidates the rerank re-scores per query, 0 = off, at most 4096 (rbq_index_set_rerank_vectors)
+ *   "mstg_rerank" 0/1    exact rerank of the MSTG candidate pool (default 0; rbq_mstg.h, rbq_mstg_search_refined_batch): the refined
+ *                        MSTG entries, and only they, reduce the pool to one entry per id and score it exactly against the
+ *                        attached raw rows.  Needs raw vectors attached and "rerank" 1, else the refined call is
+ *                        RBQ_INVALID_CONFIG; may be set with or without vectors attached.  rbq_debug_copy_index(idx, "mstg_rerank",
+ *                        &v, 4) reads it back as one int32
  *   "range_radius_bits" v  the 32 bits of an f32 radius r, passed through the int (every pattern is accepted; default +inf)
  *   "range_search" 0/1   range search (default 0): rbq_search_batch / rbq_search_batch_device return every vector of the probed
  *                        lists with distance < r (L2) or score > r (inner product), see rbq_search_batch; RBQ_INVALID_CONFIG

@@ -183,7 +183,21 @@ int rbq_mstg_search_batch_device(const rbq_index* idx, const float* d_queries, u
  * Errors: those of rbq_mstg_search_batch in its order, then RBQ_INVALID_CONFIG for pool > RBQ_MSTG_REFINE_POOL_MAX (one
  * workgroup sorts a query's pool in LDS); all before the first HIP call.  The result does not depend on the chunking (the pool's
  * slots, estimates and counts are part of the 1 GiB workspace).  The first refined call on a handle builds an identity slot map
- * (8 bytes per slot, through which the unchanged scan kernels report positions) and waits for it once. */
+ * (8 bytes per slot, through which the unchanged scan kernels report positions) and waits for it once.
+ *
+ * Exact rerank of the pool: with rbq_debug_set_option(idx, "mstg_rerank", 1) (every replica, default 0, any
+ * non-zero value stores 1, with or without vectors attached) the two refined entries, and only they, replace steps 2 to 4:
+ *  2'. Among the pool's entries with one id the one of the smallest rank stays (the exact score depends on the id alone, so every
+ *      distinct id's raw row is read once per query).  The id of an entry is the stored id of its (list, position).
+ *  3'. The distance of an entry is exact: the bits of the canonical l2_distance_sqr (L2) or of minus the canonical dot (inner
+ *      product: a distance, with the sign of the MSTG estimate) between the caller's query row, widened as "query_dtype" says, and
+ *      row `id` of the vectors attached with rbq_index_set_rerank_vectors (f32, f16 or bf16 rows).  An entry whose id is >= n, or
+ *      whose exact distance is not finite, is dropped.  The stored ex codes are not read and the numeric variant does not enter.
+ *  4'. The entries are ordered by (distance by value, -0.0 equal to +0.0; then rank) and the first top_k are returned as in step 4.
+ * Step 1, step 5 and the list outputs are unchanged.  Errors: the refined call's, then RBQ_INVALID_CONFIG (detail set) if the
+ * replica that serves the call has no raw vectors attached or its "rerank" is 0 — nothing is silently approximated; the check
+ * comes before any kernel launch and also refuses a call with top_k == 0 or ef_search == 0.  With the option 0 a refined call never
+ * looks at attached vectors.  rbq_mstg_search_batch*, rbq_posting_scan_batch and the IVF entry points never read the option. */
 #define RBQ_MSTG_REFINE_POOL_MAX 4096
 int rbq_mstg_search_refined_batch(const rbq_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
                                   uint32_t ef_search, float pruning_epsilon, uint32_t refine_pool, uint64_t* out_ids,

@@ -16,6 +16,8 @@ Mirrors the reference's public query API for this path:
                                src/mstg/index.rs:149-213,340-362 (mstg.py)
   mstg_search(..., refine_pool=n): opt-in, no crate counterpart: the binary candidates re-scored with the ex codes
                                (the refinement of src/ivf.rs:2086-2099), every id once (mstg.py)
+  mstg_search(..., refine_pool=n, exact=True), MstgIndex.set_rerank_vectors: opt-in, no crate counterpart: the pool scored
+                               exactly against attached raw vectors (l2_distance_sqr / dot of src/math.rs), every id once (mstg.py)
   hierarchical_cluster / hierarchical_cluster_cpu / MstgIndex: HierarchicalClustering::cluster, PyMstgIndex
                                src/mstg/clustering.rs, src/python_bindings.rs (mstg.py)
   save_mstg / load_mstg, MstgIndex.save / load / get_memory_usage: MstgIndex::save_main_index / load_main_index

@@ -368,6 +368,8 @@ struct Options {
     int rerank_raw_dtype = 0; // RBQ_RAW_*: the element type the next rbq_index_set_rerank_vectors reads its pointer as (0: f32)
     uint32_t rerank_pool = 0; // while rerank is on and rerank_pool > top_k: the search runs at top_k := rerank_pool, the pool is scored
                               // exactly against the attached vectors and the best top_k are returned (0 = off; <= kRerankPoolMax)
+    bool mstg_rerank = false; // rbq_mstg_search_refined_batch* only: the pool is reduced to one entry per id and
+                              // scored exactly against the attached raw vectors instead of the ex codes (needs vectors attached, rerank 1)
     // range search: while range_search is on, rbq_search_batch / rbq_search_batch_device return every probed
     // vector whose distance is below the radius (an f32 passed by its bits; distance < r for L2, score > r for inner product), in
     // scan order, with top_k read as the capacity of the output row and out_counts as the total

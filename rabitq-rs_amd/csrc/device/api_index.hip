@@ -203,6 +203,7 @@ int Options::set(const char* name, int v) {
             return fail(RBQ_INVALID_CONFIG, "queries: unknown dtype " + std::to_string(v) + " (RBQ_RAW_F32, RBQ_RAW_F16 or RBQ_RAW_BF16)");
         query_dtype = v;
     }
+    else if (is("mstg_rerank")) mstg_rerank = v != 0; // (with or without vectors attached; read by rbq_mstg_search_refined_batch* alone)
     else if (is("range_search")) range_search = v != 0;
     else if (is("range_radius_bits")) range_radius_bits = (uint32_t)v; // the 32 bits of an f32 radius: every pattern is a radius
     else if (is("range_exact")) range_exact = v != 0; // (acts while range_search is on: DESIGN.md section 33)
@@ -817,6 +818,12 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
     if (!std::strcmp(name, "rerank_raw_dtype")) { // (not an array: RBQ_RAW_* of the attached rerank rows as one int32, -1 with none attached)
         if (bytes != 4) return fail(RBQ_INVALID_CONFIG, "rerank_raw_dtype is one int32");
         const int32_t v = h->reps[0]->raw.p ? h->reps[0]->raw_dtype : -1;
+        std::memcpy(dst, &v, 4);
+        return RBQ_OK;
+    }
+    if (!std::strcmp(name, "mstg_rerank")) { // (not an array: the option "mstg_rerank" as the handle holds it, one int32)
+        if (bytes != 4) return fail(RBQ_INVALID_CONFIG, "mstg_rerank is one int32");
+        const int32_t v = h->reps[0]->opt.mstg_rerank ? 1 : 0;
         std::memcpy(dst, &v, 4);
         return RBQ_OK;
     }

@@ -187,6 +187,7 @@ struct MstgCall {
     uint32_t top_k = 0, ef_search = 0;
     float pruning_epsilon = 0;
     uint32_t pool = 0;        // candidates per query that the refined search scans for and refines (0: the plain search)
+    bool exact = false;       // option mstg_rerank on a refined call: the pool is scored against the raw rows (k_mstg_rerank.hip)
     unsigned long long* d_fallbacks = nullptr;
     MstgShape sh{};
 };
@@ -213,6 +214,11 @@ int mstg_begin(rbq_index* h, const MstgArgs& a, bool host, hipStream_t s, MstgCa
     if (rc || a.nq == 0) return rc;
     if ((rc = check_query_pointer(h, a.queries))) return rc;
     Replica* ix = c->ix = host ? h->reps[0] : replica_of_pointer(h, a.queries);
+    if (a.refined) { // the exact rerank of the pool reads the raw rows of the replica that serves the call, or the call is refused
+        std::string detail;
+        if ((rc = rbq_host::mstg_rerank_check(ix->opt.mstg_rerank, ix->raw.p != nullptr && ix->n_raw != 0, ix->rerank, &detail))) return fail(rc, detail);
+        c->exact = ix->opt.mstg_rerank;
+    }
     const uint32_t ef = (uint32_t)std::min<uint64_t>(a.ef_search, ix->n_lists);
     const bool empty = a.top_k == 0 || ef == 0;
     if (host && empty) {
@@ -245,7 +251,8 @@ int mstg_begin(rbq_index* h, const MstgArgs& a, bool host, hipStream_t s, MstgCa
 
 // n queries at d_q (device; rows of the handle's query_dtype, read by mstg_prep alone), everything enqueued on `stream`; d_lists [n][sh.ef] and d_lcnt [n] receive the selection.
 // Refined (c.pool, k_mstg_refine.hip): the scan runs with top_k := pool over the slot map into the workspace's pool, which is
-// then refined into the caller's top_k.
+// then refined into the caller's top_k — with the ex codes, or (c.exact, k_mstg_rerank.hip) exactly against the raw rows, for
+// which d_q is read once more, as the caller's rows in input space.
 int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
               uint32_t* d_lists, uint32_t* d_lcnt, hipStream_t stream) {
     int rc;
@@ -268,7 +275,7 @@ int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uin
     }
     const uint32_t knp2 = mstg_select_knp2(k);
     if (knp2 && (rc = w->key_window.ensure(n * (size_t)knp2 * 8))) return rc;
-    if ((rc = mstg_prep(ix, w, d_q, n, /*keep_ex_bits=*/c.pool != 0, stream))) return rc;
+    if ((rc = mstg_prep(ix, w, d_q, n, /*keep_ex_bits=*/c.pool != 0 && !c.exact, stream))) return rc; // (the exact rerank reads no ex code)
     {
         ProfScope ps(ix, 1, stream);
         MstgSelectParams p{};
@@ -283,6 +290,19 @@ int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uin
     rc = scan_posting_lists(ix, w, n, d_lists, d_lcnt, sh.ef, sh.wl_stride, c.pool ? c.pool : c.top_k, s_ids, s_scores, s_counts,
                             c.pool ? (const uint64_t*)ix->mr_slot_map.p : nullptr, stream);
     if (rc || !c.pool) return rc;
+    uint32_t pool_np2 = 1;
+    while (pool_np2 < c.pool) pool_np2 <<= 1;
+    if (c.exact) {
+        MstgRerankParams X{};
+        X.ids = (const uint64_t*)ix->ids.p; X.blk_list = (const uint32_t*)ix->mr_blk_list.p; X.n_slots = ix->n_blocks * 32;
+        X.probe = (const ProbeInfo*)w->probe.p; X.list_counts = d_lcnt; X.probe_stride = sh.ef;
+        X.pool_slots = s_ids; X.pool_scores = s_scores; X.pool_counts = s_counts; X.pool = c.pool; X.pool_np2 = pool_np2;
+        X.queries = d_q; X.query_dtype = ix->opt.query_dtype; X.raw = ix->raw.p; X.raw_dtype = ix->raw_dtype; X.n_raw = ix->n_raw;
+        X.out_ids = d_ids; X.out_scores = d_scores; X.out_counts = d_counts;
+        X.nq = (uint32_t)n; X.dim = ix->dim; X.metric = ix->metric; X.top_k = c.top_k;
+        HIP_TRY(launch_mstg_rerank(X, ix->device, stream));
+        return RBQ_OK;
+    }
     MstgRefineParams P{};
     P.blocks = (const uint8_t*)ix->blocks.p; P.ids = (const uint64_t*)ix->ids.p; P.ex_codes = (const uint8_t*)ix->ex.p;
     P.f_add_ex = (const float*)ix->fadd_ex.p; P.f_rescale_ex = (const float*)ix->fres_ex.p;
@@ -290,8 +310,7 @@ int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uin
     P.lut = (const uint8_t*)w->lut.p; P.rot = (const float*)w->rot.p; P.consts = (const QueryConsts*)w->consts.p;
     P.probe = (const ProbeInfo*)w->probe.p; P.list_counts = d_lcnt; P.probe_stride = sh.ef;
     P.pool_slots = s_ids; P.pool_scores = s_scores; P.pool_counts = s_counts; P.pool = c.pool;
-    P.pool_np2 = 1;
-    while (P.pool_np2 < c.pool) P.pool_np2 <<= 1;
+    P.pool_np2 = pool_np2;
     P.out_ids = d_ids; P.out_scores = d_scores; P.out_counts = d_counts;
     P.nq = (uint32_t)n; P.D = D; P.Dc = ix->Dc; P.ex_bits = ix->ex_bits; P.metric = ix->metric; P.top_k = c.top_k;
     P.numeric_variant = ix->opt.numeric_variant;

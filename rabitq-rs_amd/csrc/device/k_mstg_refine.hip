@@ -12,6 +12,7 @@
 //        sequence of its pushes and pops; the contract's order there is (list order, vector order), the order of the CPU
 //        restatement.  Equal estimates are neighbours, so a candidate's rank is the start of its run of equal values plus the
 //        candidates of the run with a smaller (j, slot).  Runs are one candidate long unless estimates tie exactly.
+//        (The search for j of phase A and this phase are mp_find_list / mp_rank of mstg_pool.hpp, shared with k_mstg_rerank.hip.)
 //     B  the refined distance.  ex_bits > 0: 16 lanes per candidate, as the scan's refine_batch: ex_dot in the handle's numeric
 //        variant (ex_dot_units + group16_reduce, or ex_dot_var_rt), then src/ivf.rs:2086-2099 in its operation order.
 //        ex_bits == 0: one lane per candidate, the binary estimate in the scan's operation order.
@@ -28,12 +29,12 @@
 #include "rbq_mstg.h"
 #include "launch.hpp"
 #include "kernels.hpp"
+#include "mstg_pool.hpp"  // mp_find_list, mp_rank, mr_sort: shared with k_mstg_rerank.hip
 #include "scan_codes.hpp" // lds_lut_ptr, accumulate_block_rt: the scan's own lookup of one vector's sign code
 
 namespace rbq {
 
 static_assert(RBQ_MSTG_REFINE_POOL_MAX == kMrPoolMax, "rbq_mstg.h and launch.hpp disagree");
-constexpr unsigned long long kMrDropped = ~0ull;
 
 __global__ __launch_bounds__(256) void k_mr_slot_map(uint64_t* __restrict__ slot_map, uint64_t n_slots) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -47,23 +48,6 @@ __global__ __launch_bounds__(256) void k_mr_blk_list(const uint32_t* __restrict_
     const uint32_t gb = list_gb0[c], nb = (list_n[c] + 31u) >> 5;
     for (uint32_t b = 0; b < nb; ++b)
         if ((uint64_t)gb + b < n_blocks) blk_list[gb + b] = c;
-}
-
-// ascending bitonic sort of np2 (a power of two) entries by the workgroup: by (k1, k2), or by k2 alone with k1 carried along
-template <bool BY_K1>
-__device__ __forceinline__ void mr_sort(unsigned long long* k1, unsigned long long* k2, uint32_t np2, uint32_t tid) {
-    for (uint32_t size = 2; size <= np2; size <<= 1)
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (uint32_t i = tid; i < (np2 >> 1); i += kThreads) {
-                const uint32_t lo = ((i & ~(stride - 1u)) << 1) | (i & (stride - 1u)), hi = lo | stride;
-                const bool up = (lo & size) == 0u;
-                const unsigned long long a1 = k1[lo], b1 = k1[hi], a2 = k2[lo], b2 = k2[hi];
-                const bool gt = BY_K1 ? (a1 > b1 || (a1 == b1 && a2 > b2)) : a2 > b2;
-                if (gt == up) { k1[lo] = b1; k1[hi] = a1; k2[lo] = b2; k2[hi] = a2; }
-            }
-        }
-    __syncthreads();
 }
 
 template <int V>
@@ -116,18 +100,12 @@ __global__ __launch_bounds__(kThreads) void k_mstg_refine(MstgRefineParams P) {
     // ---- A: one lane per candidate
     for (uint32_t r = tid; r < np2; r += kThreads) {
         const unsigned long long slot = r < cnt ? pslots[r] : kMrDropped;
-        uint32_t jfound = 0xffffffffu;
-        float g_add = 0.0f;
-        uint32_t gblock = 0, l32 = 0;
-        if (slot < P.n_slots) {
-            gblock = (uint32_t)(slot >> 5); l32 = (uint32_t)slot & 31u;
-            const uint32_t cid = P.blk_list[gblock];
-            for (uint32_t j = 0; j < lc; ++j)
-                if (probe[j].cid == cid) { g_add = probe[j].g_add; jfound = j; break; }
-        }
+        float g_add;
+        const uint32_t jfound = mp_find_list(P.blk_list, probe, lc, slot, P.n_slots, &g_add);
+        const uint32_t gblock = jfound != kMpNoList ? (uint32_t)(slot >> 5) : 0u, l32 = (uint32_t)slot & 31u;
         s_j[r] = jfound;
         // (a slot out of range or a block of no selected list cannot come out of the scan: such an entry would be dropped)
-        if (jfound == 0xffffffffu) { k1[r] = kMrDropped; k2[r] = kMrDropped; continue; }
+        if (jfound == kMpNoList) { k1[r] = kMrDropped; k2[r] = kMrDropped; continue; }
         const uint8_t* blk = P.blocks + (size_t)gblock * stride;
         const uint32_t accu = accumulate_block_rt(blk, lut, l32, Dc) & 0xffffu;
         const float ip = epi_ip(qc.delta, (float)accu, qc.sum_vl, V == kVarPortable);
@@ -137,16 +115,7 @@ __global__ __launch_bounds__(kThreads) void k_mstg_refine(MstgRefineParams P) {
     __syncthreads();
     // ---- R: ranks among equal estimates by (list order, vector order)
     for (uint32_t r = tid; r < cnt; r += kThreads) {
-        const float e = pest[r];
-        const uint32_t j = s_j[r], sl = (uint32_t)k1[r];
-        uint32_t lo = r;
-        while (lo > 0u && pest[lo - 1u] == e) --lo;
-        uint32_t before = 0;
-        for (uint32_t i = lo; i < cnt && pest[i] == e; ++i) {
-            const uint32_t j2 = s_j[i], s2 = (uint32_t)k1[i];
-            if (i != r && (j2 < j || (j2 == j && s2 < sl))) ++before;
-        }
-        s_rank[r] = lo + before;
+        s_rank[r] = mp_rank(pest, cnt, r, [&](uint32_t i) { return s_j[i]; }, [&](uint32_t i) { return (uint32_t)k1[i]; });
     }
     __syncthreads();
     // ---- B: the refined distance

@@ -17,7 +17,8 @@
 //   k_mstg_save.hip  `.mstg` writer and loader: device layout <-> the crate's bincode records
 //   k_load.hip   streamed RBQ1 loader: spans of the stream -> device layout, ex-code prefix check
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, canon_score.hpp)
-//   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan_codes.hpp)
+//   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan_codes.hpp, mstg_pool.hpp)
+//   k_mstg_rerank.hip  exact rerank of the MSTG pool: one entry per id, exact scores from the raw rows (mstg_pool.hpp, rerank_score.hpp)
 //   k_rerank_pool.hip  pooled rerank: exact scores of a candidate pool from whole lines of the raw rows, order in LDS (rerank_score.hpp)
 //   k_append.hip rbq_index_append: carry of an index into a larger geometry, id bound, nearest list of rotated rows (km_common.hpp)
 //   k_remove.hip rbq_index_remove_ids: keep masks against a sorted id set, slot map, gather of an index into a smaller geometry
@@ -448,6 +449,33 @@ size_t mstg_refine_lds_bytes(uint32_t D, uint32_t Dc, uint32_t ex_bits, uint32_t
 hipError_t launch_mstg_refine_maps(const uint32_t* list_gb0, const uint32_t* list_n, uint32_t n_lists, uint32_t n_blocks, uint64_t* slot_map,
                                    uint32_t* blk_list, hipStream_t s);
 hipError_t launch_mstg_refine(const MstgRefineParams& P, int device, hipStream_t s);
+
+// ---- exact rerank of the MSTG pool (option mstg_rerank; k_mstg_rerank.hip): the same pool, one entry per
+// id, each distinct id scored exactly against its raw row, ordered by (distance, rank), top_k.  The distance is canon_l2 or -canon_dot.
+struct MstgRerankParams {
+    const uint64_t* ids;        // the index's ids in slot order
+    const uint32_t* blk_list;   // [n_blocks] the list of every block (launch_mstg_refine_maps)
+    uint64_t n_slots;           // n_blocks * 32
+    const ProbeInfo* probe;     // [nq][probe_stride] as k_probes_given wrote them; list_counts [nq] rows in use
+    const uint32_t* list_counts;
+    uint32_t probe_stride;
+    const uint64_t* pool_slots; // [nq][pool] the binary scan's result over the identity slot map, pool_scores [nq][pool] its
+    const float* pool_scores;   // estimates (ascending), pool_counts [nq]
+    const uint32_t* pool_counts;
+    uint32_t pool, pool_np2;    // pool_np2: the power of two >= pool (<= kMrPoolMax); top_k <= pool
+    const void* queries;        // [nq][dim] elements of query_dtype, input space (the caller's rows)
+    const void* raw;            // [n_raw][dim] elements of raw_dtype, n_raw >= 1
+    uint64_t n_raw;
+    uint64_t* out_ids;          // [nq][top_k], out_scores [nq][top_k], out_counts [nq]
+    float* out_scores;
+    uint32_t* out_counts;
+    uint32_t nq, dim, metric, top_k;
+    int raw_dtype = kRawF32;     // kRawF32 / kRawF16 / kRawBf16
+    int query_dtype = kRawF32;   // the same values: what `queries` holds
+    uint32_t raw_by_element = 0; // set by the launch: 16-bit rows that do not all start 4-byte aligned (odd dim, or raw at 2 mod 4)
+};
+size_t mstg_rerank_lds_bytes(uint32_t dim, uint32_t pool_np2);
+hipError_t launch_mstg_rerank(const MstgRerankParams& P, int device, hipStream_t s);
 
 // ---- RBQ1 writer (k_save.hip): words [w0, w0 + nw) of the cluster section of the stream, into out[0, nw)
 struct SaveParams {

@@ -429,4 +429,15 @@ inline int mstg_search_check(const MstgSearchArgs& a, std::string* detail, bool*
     return RBQ_OK;
 }
 
+// The refined MSTG call with the option mstg_rerank scores its pool exactly against the raw rows attached to
+// the replica that serves it: without rows, or with the handle's "rerank" 0, the call is refused — nothing is silently approximated.
+// Comes after mstg_search_check's errors and before any kernel launch.  option 0: the call never looks at the rows.
+inline int mstg_rerank_check(bool option, bool have_raw, bool rerank_on, std::string* detail) {
+    if (!option || (have_raw && rerank_on)) return RBQ_OK;
+    if (detail)
+        *detail = !have_raw ? "exact MSTG rerank needs raw vectors attached (rbq_index_set_rerank_vectors) or mstg_rerank 0"
+                            : "exact MSTG rerank needs the rerank on: set the option rerank 1 or mstg_rerank 0";
+    return RBQ_INVALID_CONFIG;
+}
+
 } // namespace rbq_host

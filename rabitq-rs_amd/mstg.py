@@ -13,6 +13,7 @@ Persistence (include/rbq_mstg_persist.h): `save_mstg` / `l
 read the crate's `{path}.mstg` (src/mstg/io.rs), assembled and taken apart on the GPU.  The crate's HNSW side files
 (`{path}.hnsw.graph`, `{path}.hnsw.data`) are neither written nor read: a crate-written index loads here, while the crate cannot
 reopen a file written here without side files of its own making."""
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 
@@ -219,7 +220,28 @@ def search_fallbacks():
 REFINE_POOL_MAX = _abi.MSTG_REFINE_POOL_MAX
 
 
-def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, return_lists=False, refine_pool=None, dtype=None):
+@contextlib.contextmanager
+def _mstg_rerank_for_call(index, exact):
+    """Context of one refined call: with `exact` the handle's option "mstg_rerank" is set to 1 where it is not (read back from the
+    handle) and the handle's value put back afterwards, error or not.  exact=False makes no option call: a handle whose option the
+    caller set by hand keeps serving as it was told."""
+    if not exact:
+        yield
+        return
+    v = C.c_int32(-1)
+    from .index import _check, lib
+    _check(lib().rbq_debug_copy_index(index._h, b"mstg_rerank", C.byref(v), 4))
+    if v.value == 1:
+        yield
+        return
+    index.set_option("mstg_rerank", 1)
+    try:
+        yield
+    finally:
+        index.set_option("mstg_rerank", 0)
+
+
+def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, return_lists=False, refine_pool=None, dtype=None, exact=False):
     """`MstgIndex::batch_search` on an MSTG handle (rotator NoRotation, e.g. from build_postings_on_device) in one call:
     (ids [nq][top_k] u64, distances [nq][top_k] f32 ascending, counts [nq] u32), plus (lists, list_counts) of the selected
     posting lists in scan order with `return_lists`.  NumPy queries take rbq_mstg_search_batch and return arrays; a CUDA tensor
@@ -230,12 +252,19 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
     rbq_mstg_search_refined_batch*: the max(refine_pool, top_k) best binary candidates are re-scored with the stored ex codes,
     reduced to one entry per id and the top_k nearest returned (at most REFINE_POOL_MAX candidates).
 
+    `exact=True` (needs an int `refine_pool`, and raw vectors attached to the handle with set_rerank_vectors): the pool is reduced
+    to one entry per id and every distinct id is scored exactly against its raw row instead of the ex codes (option "mstg_rerank",
+    set for the call and put back afterwards).  Distances are the canonical l2_distance_sqr, or minus the
+    canonical dot product.  Without vectors attached, or with the handle's "rerank" off, the library refuses the call.
+
     Queries of 16 bits (a numpy.float16 array, a torch.half / torch.bfloat16 tensor, a numpy.uint16 array of bit patterns with
     dtype="f16" | "bf16") are read as they are: the handle's option "query_dtype" is set for the call and put back afterwards."""
     from . import _marshal
     from .index import _check, lib
     top_k, ef_search = int(top_k), int(ef_search)
     L = lib()
+    if exact and refine_pool is None:
+        raise ValueError("exact=True needs refine_pool: the exact rerank scores the pool of the refined search")
     if refine_pool is None:
         host_fn, dev_fn, extra = L.rbq_mstg_search_batch, L.rbq_mstg_search_batch_device, ()
     else:
@@ -252,7 +281,7 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
             li = torch.empty((nq, ef), dtype=torch.int32, device=q.device) if return_lists else None
             lc = torch.empty(nq, dtype=torch.int32, device=q.device) if return_lists else None
             stream = torch.cuda.current_stream().cuda_stream
-            with index._query_dtype_for_call(code):
+            with index._query_dtype_for_call(code), _mstg_rerank_for_call(index, exact):
                 rc = dev_fn(index._h, q.data_ptr(), nq, qd, top_k, ef_search, float(pruning_epsilon), *extra,
                             ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(),
                             li.data_ptr() if return_lists else None, lc.data_ptr() if return_lists else None,
@@ -265,7 +294,7 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
     cnt = np.zeros(nq, np.uint32)
     li = np.empty((nq, ef), np.uint32) if return_lists else None
     lc = np.empty(nq, np.uint32) if return_lists else None
-    with index._query_dtype_for_call(code):
+    with index._query_dtype_for_call(code), _mstg_rerank_for_call(index, exact):
         rc = host_fn(index._h, _marshal.data_ptr(q), nq, qd, top_k, ef_search, float(pruning_epsilon), *extra, ids.ctypes.data,
                      sc.ctypes.data, cnt.ctypes.data, li.ctypes.data if return_lists else None,
                      lc.ctypes.data if return_lists else None)
@@ -423,6 +452,7 @@ class MstgIndex:
         self.device, self.max_iterations, self.host_below = device, int(max_iterations), host_below
         self.handle, self.centroids, self.cluster_stats, self._n = None, None, None, 0
         self.refine_pool = None  # the crate's search; set_query_arguments(refine_pool=...) switches to the refined one
+        self.exact = False       # set_query_arguments(exact=True): the refined search scores its pool against the attached raw vectors
 
     def fit(self, data):
         if len(data.shape) != 2:
@@ -436,15 +466,25 @@ class MstgIndex:
         self.centroids, self.cluster_stats, self._n = cent, st, int(data.shape[0])
         return self
 
-    def set_query_arguments(self, ef_search=None, pruning_epsilon=None, refine_pool=_KEEP):
+    def set_rerank_vectors(self, vectors=None, device_ptr=None, n=0, dtype=None):
+        """Attach raw vectors to the handle (IvfRabitqIndex.set_rerank_vectors: a host array [n][dim] or `device_ptr` + n, as
+        "f32", "f16" or "bf16"; None detaches): row i is the vector of id i.  Only queries with `exact=True` read them.  `add` and
+        `remove_ids` swap the handle, and the new one has no vectors attached: attach rows that cover the new ids again."""
+        self._built().set_rerank_vectors(vectors, device_ptr, n, dtype=dtype)
+
+    def set_query_arguments(self, ef_search=None, pruning_epsilon=None, refine_pool=_KEEP, exact=_KEEP):
         """`refine_pool`: None = the crate's search (the default); an int = the refined search of `mstg_search` over a pool of that
-        many binary candidates (ex-code distances, every id once).  Left out, it keeps its value."""
+        many binary candidates (ex-code distances, every id once).  Left out, it keeps its value.
+        `exact`: True = the refined search scores its pool exactly against the vectors of set_rerank_vectors (mstg_search's
+        `exact`; needs an int refine_pool).  Left out, it keeps its value."""
         if ef_search is not None:
             self.default_ef_search = int(ef_search)
         if pruning_epsilon is not None:
             self.pruning_epsilon = float(pruning_epsilon)
         if refine_pool is not _KEEP:
             self.refine_pool = None if refine_pool is None else int(refine_pool)
+        if exact is not _KEEP:
+            self.exact = bool(exact)
 
     def _built(self):
         if self.handle is None:
@@ -462,7 +502,8 @@ class MstgIndex:
             raise ValueError("Queries must be 2D array (N x D)")
         if q.shape[1] != self.dimension:
             raise ValueError(f"Query dimension {q.shape[1]} does not match expected {self.dimension}")
-        ids, dist, cnt = mstg_search(h, q, k, self.default_ef_search, self.pruning_epsilon, refine_pool=self.refine_pool, dtype=dtype)
+        ids, dist, cnt = mstg_search(h, q, k, self.default_ef_search, self.pruning_epsilon, refine_pool=self.refine_pool, dtype=dtype,
+                                     exact=self.exact)
         return [np.stack([ids[i, :cnt[i]].astype(np.float32), dist[i, :cnt[i]]], axis=1) for i in range(q.shape[0])]
 
     def query(self, query, k, dtype=None):
@@ -510,7 +551,9 @@ class MstgIndex:
     def add(self, data):
         """FAISS-style add (append_postings with this object's closure_epsilon and max_replicas): the rows of `data` join the
         posting lists with the ids id_bound() ..; nothing is re-clustered, the centroids stay.  The handle is swapped for the
-        grown one and the old one closed.  Returns the first new id."""
+        grown one and the old one closed.  Returns the first new id.
+        The new handle has no raw vectors attached: a query with exact=True is refused by the library (RabitqError) until
+        set_rerank_vectors attaches rows that cover the new ids too.  Nothing is re-attached silently."""
         h = self._built()
         if len(data.shape) != 2:
             raise ValueError("Data must be 2D array (N x D)")
@@ -525,7 +568,9 @@ class MstgIndex:
     def remove_ids(self, ids):
         """FAISS-style remove_ids (remove_postings): every slot whose id is in `ids` leaves its list.  The handle is swapped for
         the shrunk one and the old one closed; len() becomes 1 + the largest id that stays.  Returns the number of slots removed
-        (a vector counts once per list that held it)."""
+        (a vector counts once per list that held it).
+        The new handle has no raw vectors attached: a query with exact=True is refused by the library (RabitqError) until
+        set_rerank_vectors attaches them again.  Nothing is re-attached silently."""
         h = self._built()
         self.handle, removed = remove_postings(h, ids)
         h.close()
