@@ -29,6 +29,7 @@
 #include "rbq.h"
 #include "launch.hpp"
 #include "../host/rbq_host_logic.hpp"
+#include "../host/rbq_index_layout.hpp"
 #include "../host/rbq_append_plan.hpp"
 #include "../host/rbq_search_plan.hpp"
 
@@ -402,10 +403,8 @@ struct Replica : Geometry {
     Arr rot_blob, centroids, blocks, ids, ex, fadd_ex, fres_ex, list_gb0, list_n, prof, bsum, cnorm2, fallbacks, cent_hl, raw,
         bsumx, lsum, // ex-factor ranges per block, factor ranges per list (lazy probe selection)
         cent_f16, cent_f16_resid; // one-product f16 image [nlist][D] of the centroids and |c - f16(c)| per centroid (rank_mfma.hpp header)
-    Arr* arrays[19] = {&rot_blob, &centroids, &blocks, &ids, &ex, &fadd_ex, &fres_ex, &list_gb0, &list_n, &prof, &bsum, &cnorm2,
-                       &fallbacks, &cent_hl, &raw, &bsumx, &lsum, &cent_f16, &cent_f16_resid};
     // reconstruction factors delta / vl of every slot (RBQ1's per-vector arrays that search never reads): kept on the FIRST
-    // replica only, for rbq_index_save_rbq1 (not in `arrays`: clone_replica does not copy them)
+    // replica only, for rbq_index_save_rbq1 (clone_replica does not copy them)
     Arr delta, vl;
     // MSTG handles only (rbq_mstg_build_device, rbq_mstg_load*; FIRST replica, slot order, pad slots 0): QuantizedVector::residual_norm,
     // which the `.mstg` format stores and no search reads — 4 bytes per vector — and the RabitqConfig::t_const the lists were built with
@@ -419,14 +418,20 @@ struct Replica : Geometry {
     Arr fmap_ids, fmap_slots;
     bool fmap_ready = false;
     // rbq_mstg_search_batch*: split-bf16 images of the centroids (padded to 32), their norms | largest norm | non-finite flag; built
-    // by the first search that takes the GEMM shortlist, under `mu`, kept until destroy (not in `arrays`: built per replica)
+    // by the first search that takes the GEMM shortlist, under `mu`, kept until destroy (built per replica)
     Arr ms_hi, ms_lo, ms_nc;
     bool ms_ready = false;
     uint32_t ms_bad = 0;
     // rbq_mstg_search_refined_batch*: the identity slot map the scan reports positions through (8 bytes per slot) and the list of
-    // every block; built by the first refined search, under `mu`, kept until destroy (not in `arrays`: built per replica)
+    // every block; built by the first refined search, under `mu`, kept until destroy (built per replica)
     Arr mr_slot_map, mr_blk_list;
     bool mr_ready = false;
+    // THE list of the device arrays a replica owns (free_replica, rbq_mstg_memory_usage): the first kCloned are what clone_replica
+    // copies (`raw` excepted), the others stay with the replica that built them
+    static constexpr size_t kCloned = 19;
+    Arr* arrays[29] = {&rot_blob, &centroids, &blocks, &ids, &ex, &fadd_ex, &fres_ex, &list_gb0, &list_n, &prof, &bsum, &cnorm2,
+                       &fallbacks, &cent_hl, &raw, &bsumx, &lsum, &cent_f16, &cent_f16_resid,
+                       &delta, &vl, &rnorm, &fmap_ids, &fmap_slots, &ms_hi, &ms_lo, &ms_nc, &mr_slot_map, &mr_blk_list};
     float cnorm2_max = 0.0f;
     // one-product f16 ranking: sqrt(cnorm2_max) and the largest |c - f16(c)|, both rounded up; rank_f16_ok: every stored half is
     // finite and rc_max <= 2^-11 cnorm_max (else the index ranks on split-bf16 for good)
@@ -462,6 +467,13 @@ struct Replica : Geometry {
     Replica(const Replica&) = delete;
 };
 
+// The byte size of every array of a replica (csrc/host/rbq_index_layout.hpp)
+static_assert(sizeof(BlockSummary) == rbq_host::kBlockSummaryBytes && sizeof(BlockSummaryEx) == rbq_host::kBlockSummaryBytes,
+              "index_bytes() sizes bsum, bsumx and lsum");
+inline rbq_host::IndexBytes index_bytes_of(const Replica* ix) {
+    return rbq_host::index_bytes(ix->D, ix->Dc, ix->ex_bits, ix->n_blocks, ix->n_lists);
+}
+
 // shared by the units (api_index.hip)
 int alloc_arr(Arr& a, size_t bytes);
 int upload_arr(Arr& a, const void* src, size_t bytes);
@@ -474,6 +486,12 @@ struct ReplicaOwner { // frees a half-built replica on an early return
 int validate_header(const rbq_header* h, bool brute_force = false);
 int resolve_devices(int n_devices, const int* devices, std::vector<int>& out);
 Replica* new_replica(const rbq_header* hdr, int dev);
+// THE allocation of a replica's slot and block arrays, shared by every construction path: sets n_blocks, n_vectors, has_recon and
+// has_rnorm, uploads list_gb0 / list_n, allocates blocks, ids, ex, fadd_ex, fres_ex, bsum (delta and vl with `recon`, rnorm with
+// `rnorm`) at index_bytes' sizes and zeroes the read-ahead pad of `ex`.  rot_blob, centroids, a path's own fills and tc_some /
+// tc_value stay with the caller.
+int alloc_index_arrays(Replica* ix, const std::vector<uint32_t>& ln, const std::vector<uint32_t>& gb0, uint64_t n_blocks,
+                       uint64_t n_vectors, bool recon, bool rnorm);
 int finish_replica(Replica* ix, const std::vector<uint32_t>& ln);
 int wrap_and_replicate(Replica* first, const std::vector<int>& devs, rbq_index** out);
 // api_build.hip: the device encoder over (vector, list) pairs (rbq_index_build_device_ex: one pair per vector; rbq_mstg_build_device)
@@ -520,6 +538,14 @@ struct EventPair { // times one launch on the null stream; freed on every exit
     }
 };
 
+// the per-slot arrays of a replica for the carry / gather kernels (null where it holds none)
+inline SlotArrays slot_arrays(const Replica* ix) {
+    SlotArrays a{};
+    a.blocks = (uint8_t*)ix->blocks.p; a.ids = (uint64_t*)ix->ids.p; a.delta = (float*)ix->delta.p; a.vl = (float*)ix->vl.p;
+    if (ix->ex_bits) { a.ex = (uint8_t*)ix->ex.p; a.fadd = (float*)ix->fadd_ex.p; a.fres = (float*)ix->fres_ex.p; }
+    if (ix->has_rnorm) a.rnorm = (float*)ix->rnorm.p;
+    return a;
+}
 // What rbq_index_append and rbq_mstg_append share (api_append.hip): the replica of the grown geometry — centroids and rotator bit
 // for bit those of `old`, every array allocated (rnorm too where `old` has it), the old arrays carried over by k_append_carry — and
 // its block tables in `t`.  own.ix is the new replica (freed by `own` on an early return).

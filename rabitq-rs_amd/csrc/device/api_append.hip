@@ -52,33 +52,19 @@ int append_grow(Replica* old, const rbq_host::AppendPlan& plan, Scratch& t, Repl
     hdr.dim = old->dim; hdr.padded_dim = old->D; hdr.metric = old->metric; hdr.rotator = old->rotator; hdr.ex_bits = old->ex_bits;
     hdr.n_lists = old->n_lists;
     const int dev = old->device;
-    const uint32_t Dc = old->Dc, nlist = (uint32_t)old->n_lists;
-    const size_t dev_stride = (size_t)Dc * 4 + 384, exd = ex_bytes_dev(old->D, old->ex_bits);
     int rc;
     own.ix = new_replica(&hdr, dev);
     Replica* ix = own.ix;
-    const uint64_t nblocks = plan.new_blocks, nslots = nblocks * 32;
-    ix->n_blocks = nblocks; ix->n_vectors = plan.new_vectors;
+    const uint64_t nblocks = plan.new_blocks;
     for (Arr Replica::*m : {&Replica::rot_blob, &Replica::centroids}) { // bit for bit those of the old handle
         if ((rc = alloc_arr(ix->*m, (old->*m).bytes))) return rc;
         if ((old->*m).bytes) HIP_TRY(hipMemcpy((ix->*m).p, (old->*m).p, (old->*m).bytes, hipMemcpyDeviceToDevice));
     }
-    if ((rc = upload_arr(ix->list_gb0, plan.new_gb0.data(), (size_t)nlist * 4))) return rc;
-    if ((rc = upload_arr(ix->list_n, plan.new_n.data(), (size_t)nlist * 4))) return rc;
-    if ((rc = alloc_arr(ix->blocks, nblocks * dev_stride))) return rc;
-    if ((rc = alloc_arr(ix->ids, nslots * 8))) return rc;
-    if ((rc = alloc_arr(ix->ex, exd ? nslots * exd + 256 : 0))) return rc;
-    if ((rc = alloc_arr(ix->fadd_ex, ix->ex_bits ? nslots * 4 : 0))) return rc;
-    if ((rc = alloc_arr(ix->fres_ex, ix->ex_bits ? nslots * 4 : 0))) return rc;
-    if ((rc = alloc_arr(ix->bsum, nblocks * sizeof(BlockSummary)))) return rc;
-    if ((rc = alloc_arr(ix->delta, nslots * 4))) return rc;
-    if ((rc = alloc_arr(ix->vl, nslots * 4))) return rc;
-    ix->has_recon = true;
-    if (old->has_rnorm) { // an MSTG handle: what the `.mstg` format stores beyond the search's arrays
-        if ((rc = alloc_arr(ix->rnorm, nslots * 4))) return rc;
-        ix->has_rnorm = true; ix->tc_some = old->tc_some; ix->tc_value = old->tc_value;
-    }
-    if (exd) HIP_TRY(hipMemset((uint8_t*)ix->ex.p + nslots * exd, 0, 256)); // read-ahead pad of the refine loads
+    // (rnorm: an MSTG handle keeps what the `.mstg` format stores beyond the search's arrays)
+    if ((rc = alloc_index_arrays(ix, plan.new_n, plan.new_gb0, nblocks, plan.new_vectors, /*recon=*/true, old->has_rnorm))) return rc;
+    if (old->has_rnorm) { ix->tc_some = old->tc_some; ix->tc_value = old->tc_value; }
+    const rbq_host::IndexBytes B = index_bytes_of(ix);
+    const size_t dev_stride = B.block_stride, exd = B.ex_slot;
 
     if ((rc = upload_block_tables(plan.new_n, plan.new_gb0, nblocks, t, d_block_list, d_block_nv))) return rc;
     AppendCarryParams P{};
@@ -86,16 +72,7 @@ int append_grow(Replica* old, const rbq_host::AppendPlan& plan, Scratch& t, Repl
     P.gb0_new = (const uint32_t*)ix->list_gb0.p; P.gb0_old = (const uint32_t*)old->list_gb0.p; P.n_old = (const uint32_t*)old->list_n.p;
     P.nb_new = (uint32_t)nblocks; P.nb_old = (uint32_t)old->n_blocks;
     P.rec16 = (uint32_t)(dev_stride / 16); P.ex16 = (uint32_t)(exd * 32 / 16);
-    P.blocks_s = (const uint8_t*)old->blocks.p; P.blocks_d = (uint8_t*)ix->blocks.p;
-    P.ex_s = exd ? (const uint8_t*)old->ex.p : nullptr; P.ex_d = exd ? (uint8_t*)ix->ex.p : nullptr;
-    P.ids_s = (const uint64_t*)old->ids.p; P.ids_d = (uint64_t*)ix->ids.p;
-    if (ix->ex_bits) {
-        P.fadd_s = (const float*)old->fadd_ex.p; P.fadd_d = (float*)ix->fadd_ex.p;
-        P.fres_s = (const float*)old->fres_ex.p; P.fres_d = (float*)ix->fres_ex.p;
-    }
-    P.delta_s = (const float*)old->delta.p; P.delta_d = (float*)ix->delta.p;
-    P.vl_s = (const float*)old->vl.p; P.vl_d = (float*)ix->vl.p;
-    if (ix->has_rnorm) { P.rnorm_s = (const float*)old->rnorm.p; P.rnorm_d = (float*)ix->rnorm.p; }
+    P.src = slot_arrays(old); P.dst = slot_arrays(ix);
     EventPair ev;
     ev.start();
     HIP_TRY(launch_append_carry(P, dev, 0));

@@ -22,11 +22,10 @@ namespace rbq_api {
 namespace {
 // ---- GPU-side encoder: the device analogue of train_with_clusters' quantisation loop ------------------------------
 // rotated centroids + list geometry + final arrays of an index that the encoder fills (shared by the one-shot and the
-// streamed build).  `counts` = vectors per list.
+// streamed build).  `ln` = vectors per list; rnorm: the handle keeps every slot's residual norm (a posting-list handle).
 int encoder_prepare(Replica* ix, const rbq_header* hdr, const float* centroids, const std::vector<uint32_t>& ln,
-                    std::vector<uint32_t>& gb0, bool zero_fill) {
-    const uint32_t D = ix->D, Dc = ix->Dc, dim = ix->dim, nlist = (uint32_t)ix->n_lists;
-    const size_t dev_stride = (size_t)Dc * 4 + 384, exd = ex_bytes_dev(D, ix->ex_bits);
+                    std::vector<uint32_t>& gb0, bool zero_fill, bool rnorm) {
+    const uint32_t D = ix->D, dim = ix->dim, nlist = (uint32_t)ix->n_lists;
     int rc;
     if ((rc = upload_arr(ix->rot_blob, hdr->rotator_blob, hdr->rotator_len))) return rc;
     {
@@ -39,32 +38,20 @@ int encoder_prepare(Replica* ix, const rbq_header* hdr, const float* centroids, 
                                    (float*)ix->centroids.p, 0));
         HIP_TRY(hipDeviceSynchronize());
     }
-    uint64_t nblocks = 0, nvec = 0;
-    gb0.resize(nlist);
-    for (uint32_t c = 0; c < nlist; ++c) {
-        gb0[c] = (uint32_t)nblocks; nblocks += (ln[c] + 31u) / 32u; nvec += ln[c];
-        if (nblocks * 32 > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "index too large for 32-bit vector slots");
+    rbq_host::ListLayout lay;
+    {
+        std::string detail;
+        if (!rbq_host::list_layout(ln.data(), ln.size(), &lay, &detail)) return fail(RBQ_INVALID_CONFIG, detail);
     }
-    ix->n_blocks = nblocks; ix->n_vectors = nvec;
-    const uint64_t nslots = nblocks * 32;
-    if ((rc = upload_arr(ix->list_gb0, gb0.data(), (size_t)nlist * 4))) return rc;
-    if ((rc = upload_arr(ix->list_n, ln.data(), (size_t)nlist * 4))) return rc;
-    if ((rc = alloc_arr(ix->blocks, nblocks * dev_stride))) return rc;
-    HIP_TRY(hipMemset(ix->blocks.p, 0, nblocks * dev_stride));
-    if ((rc = alloc_arr(ix->ids, nslots * 8))) return rc;
-    if ((rc = alloc_arr(ix->ex, exd ? nslots * exd + 256 : 0))) return rc;
-    if ((rc = alloc_arr(ix->fadd_ex, ix->ex_bits ? nslots * 4 : 0))) return rc;
-    if ((rc = alloc_arr(ix->fres_ex, ix->ex_bits ? nslots * 4 : 0))) return rc;
-    if ((rc = alloc_arr(ix->bsum, nblocks * sizeof(BlockSummary)))) return rc;
-    if ((rc = alloc_arr(ix->delta, nslots * 4))) return rc;
-    if ((rc = alloc_arr(ix->vl, nslots * 4))) return rc;
-    ix->has_recon = true;
-    if (exd) HIP_TRY(hipMemset((uint8_t*)ix->ex.p + nslots * exd, 0, 256));
+    gb0 = std::move(lay.gb0);
+    if ((rc = alloc_index_arrays(ix, ln, gb0, lay.blocks, lay.vectors, /*recon=*/true, rnorm))) return rc;
+    const rbq_host::IndexBytes B = index_bytes_of(ix);
+    HIP_TRY(hipMemset(ix->blocks.p, 0, B.blocks));
     if (zero_fill) { // streamed build: padding slots are never visited by the scatter kernels
-        HIP_TRY(hipMemset(ix->ids.p, 0xff, nslots * 8));
-        if (exd) HIP_TRY(hipMemset(ix->ex.p, 0, nslots * exd));
-        if (ix->ex_bits) { HIP_TRY(hipMemset(ix->fadd_ex.p, 0, nslots * 4)); HIP_TRY(hipMemset(ix->fres_ex.p, 0, nslots * 4)); }
-        HIP_TRY(hipMemset(ix->delta.p, 0, nslots * 4)); HIP_TRY(hipMemset(ix->vl.p, 0, nslots * 4));
+        HIP_TRY(hipMemset(ix->ids.p, 0xff, B.ids));
+        if (B.ex) HIP_TRY(hipMemset(ix->ex.p, 0, B.ex));
+        if (ix->ex_bits) { HIP_TRY(hipMemset(ix->fadd_ex.p, 0, B.fadd_ex)); HIP_TRY(hipMemset(ix->fres_ex.p, 0, B.fres_ex)); }
+        HIP_TRY(hipMemset(ix->delta.p, 0, B.delta)); HIP_TRY(hipMemset(ix->vl.p, 0, B.vl));
     }
     return RBQ_OK;
 }
@@ -74,11 +61,8 @@ int encoder_prepare(Replica* ix, const rbq_header* hdr, const float* centroids, 
 // block -> list and block -> number of real vectors, on the device
 int upload_block_tables(const std::vector<uint32_t>& ln, const std::vector<uint32_t>& gb0, uint64_t nblocks, Scratch& t,
                         uint32_t** d_block_list, uint32_t** d_block_nv) {
-    std::vector<uint32_t> bl(nblocks), bn(nblocks);
-    for (size_t c = 0; c < ln.size(); ++c) {
-        const uint32_t nb = (ln[c] + 31u) / 32u;
-        for (uint32_t b = 0; b < nb; ++b) { bl[gb0[c] + b] = (uint32_t)c; bn[gb0[c] + b] = std::min<uint32_t>(32u, ln[c] - b * 32u); }
-    }
+    std::vector<uint32_t> bl, bn;
+    rbq_host::block_tables(ln, gb0, nblocks, &bl, &bn);
     HIP_TRY(t.alloc(d_block_list, nblocks * 4)); HIP_TRY(t.alloc(d_block_nv, nblocks * 4));
     HIP_TRY(hipMemcpy(*d_block_list, bl.data(), nblocks * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(*d_block_nv, bn.data(), nblocks * 4, hipMemcpyHostToDevice));
@@ -150,7 +134,6 @@ int build_device_pairs(const rbq_header* hdr, const float* centroids, const floa
     ReplicaOwner own{new_replica(hdr, dev)};
     Replica* ix = own.ix;
     const uint32_t D = ix->D, Dc = ix->Dc, dim = ix->dim, nlist = (uint32_t)ix->n_lists;
-    const size_t dev_stride = (size_t)Dc * 4 + 384, exd = ex_bytes_dev(D, ix->ex_bits);
     Scratch t;
 
     // list sizes
@@ -165,11 +148,12 @@ int build_device_pairs(const rbq_header* hdr, const float* centroids, const floa
         if (hc[nlist]) return fail(RBQ_INVALID_CONFIG, "assignment out of range");
         std::copy(hc.begin(), hc.begin() + nlist, ln.begin());
     }
-    if ((rc = encoder_prepare(ix, hdr, centroids, ln, gb0, /*zero_fill=*/false))) return rc;
-    const uint64_t nblocks = ix->n_blocks, nslots = nblocks * 32;
-    if (ix->rotator == RBQ_ROTATOR_NONE) { // a posting-list handle: what the `.mstg` format stores beyond the search's arrays
-        if ((rc = alloc_arr(ix->rnorm, nslots * 4))) return rc;
-        ix->has_rnorm = true;
+    // (a posting-list handle keeps what the `.mstg` format stores beyond the search's arrays)
+    if ((rc = encoder_prepare(ix, hdr, centroids, ln, gb0, /*zero_fill=*/false, /*rnorm=*/ix->rotator == RBQ_ROTATOR_NONE))) return rc;
+    const rbq_host::IndexBytes B = index_bytes_of(ix);
+    const uint64_t nblocks = ix->n_blocks, nslots = B.slots;
+    const size_t dev_stride = B.block_stride, exd = B.ex_slot;
+    if (ix->has_rnorm) {
         ix->tc_some = !opt && ix->ex_bits > 0; // RabitqConfig::faster: Some(t_const) unless 1-bit; RabitqConfig::new: None
         ix->tc_value = ix->tc_some ? t_const : 0.0f;
     }
@@ -272,7 +256,7 @@ int stream_begin_impl(const rbq_header* hdr, const float* centroids, const uint3
     b->ln.assign(list_sizes, list_sizes + nlist);
     for (uint32_t c = 0; c < nlist; ++c) b->n_total += b->ln[c];
     if (b->n_total == 0) return fail(RBQ_INVALID_CONFIG, "no vectors");
-    if ((rc = encoder_prepare(b->ix, hdr, centroids, b->ln, b->gb0, /*zero_fill=*/true))) return rc;
+    if ((rc = encoder_prepare(b->ix, hdr, centroids, b->ln, b->gb0, /*zero_fill=*/true, /*rnorm=*/false))) return rc;
     if ((rc = upload_block_tables(b->ln, b->gb0, b->ix->n_blocks, b->tables, &b->d_block_list, &b->d_block_nv))) return rc;
     HIP_TRY(b->tables.alloc(&b->d_cursor, (size_t)nlist * 4));
     HIP_TRY(b->tables.alloc(&b->d_chunk_first, (size_t)nlist * 4));

@@ -24,6 +24,25 @@ int upload_arr(Arr& a, const void* src, size_t bytes) {
     return RBQ_OK;
 }
 
+int alloc_index_arrays(Replica* ix, const std::vector<uint32_t>& ln, const std::vector<uint32_t>& gb0, uint64_t n_blocks,
+                       uint64_t n_vectors, bool recon, bool rnorm) {
+    ix->n_blocks = n_blocks; ix->n_vectors = n_vectors; ix->has_recon = recon; ix->has_rnorm = rnorm;
+    const rbq_host::IndexBytes B = index_bytes_of(ix);
+    int rc;
+    if ((rc = upload_arr(ix->list_gb0, gb0.data(), B.list_gb0))) return rc;
+    if ((rc = upload_arr(ix->list_n, ln.data(), B.list_n))) return rc;
+    if ((rc = alloc_arr(ix->blocks, B.blocks))) return rc;
+    if ((rc = alloc_arr(ix->ids, B.ids))) return rc;
+    if ((rc = alloc_arr(ix->ex, B.ex_alloc))) return rc;
+    if ((rc = alloc_arr(ix->fadd_ex, B.fadd_ex))) return rc;
+    if ((rc = alloc_arr(ix->fres_ex, B.fres_ex))) return rc;
+    if ((rc = alloc_arr(ix->bsum, B.bsum))) return rc;
+    if (recon && ((rc = alloc_arr(ix->delta, B.delta)) || (rc = alloc_arr(ix->vl, B.vl)))) return rc;
+    if (rnorm && (rc = alloc_arr(ix->rnorm, B.rnorm))) return rc;
+    if (B.ex_alloc) HIP_TRY(hipMemset((uint8_t*)ix->ex.p + B.ex, 0, rbq_host::kExReadAhead)); // read-ahead pad of the refine loads
+    return RBQ_OK;
+}
+
 void free_replica(Replica* ix) {
     if (!ix) return;
     if (ix->stagers) ix->stagers->shutdown();
@@ -31,9 +50,6 @@ void free_replica(Replica* ix) {
     (void)hipDeviceSynchronize();
     for (Arr* a : ix->arrays)
         if (a->p && !(a == &ix->raw && ix->raw_borrowed)) (void)hipFree(a->p);
-    for (Arr* a : {&ix->delta, &ix->vl, &ix->rnorm, &ix->fmap_ids, &ix->fmap_slots, &ix->ms_hi, &ix->ms_lo, &ix->ms_nc,
-                   &ix->mr_slot_map, &ix->mr_blk_list})
-        if (a->p) (void)hipFree(a->p);
     for (Workspace* w : ix->pool) delete w;
     for (auto& kv : ix->stream_ws) delete kv.second;
     for (auto& sp : ix->stage_prof)
@@ -100,16 +116,11 @@ Replica* new_replica(const rbq_header* hdr, int dev) {
 int finish_replica(Replica* ix, const std::vector<uint32_t>& ln) {
     const uint32_t nlist = (uint32_t)ix->n_lists, D = ix->D;
     ix->h_list_n = ln;
-    {
-        std::vector<uint64_t> nblk(nlist);
-        for (uint32_t c = 0; c < nlist; ++c) nblk[c] = (ln[c] + 31u) / 32u;
-        std::sort(nblk.begin(), nblk.end(), std::greater<uint64_t>());
-        ix->nblk_desc_prefix.assign((size_t)nlist + 1, 0);
-        for (uint32_t c = 0; c < nlist; ++c) ix->nblk_desc_prefix[c + 1] = ix->nblk_desc_prefix[c] + nblk[c];
-    }
+    ix->nblk_desc_prefix = rbq_host::nblk_desc_prefix(ln);
+    const rbq_host::IndexBytes B = index_bytes_of(ix);
     int rc;
-    if ((rc = alloc_arr(ix->cnorm2, (size_t)nlist * 4))) return rc;
-    if ((rc = alloc_arr(ix->cent_hl, (size_t)nlist * D * 4))) return rc;
+    if ((rc = alloc_arr(ix->cnorm2, B.cnorm2))) return rc;
+    if ((rc = alloc_arr(ix->cent_hl, B.cent_hl))) return rc;
     HIP_TRY(launch_centroid_arrays((const float*)ix->centroids.p, nlist, D, (float*)ix->cnorm2.p, (uint16_t*)ix->cent_hl.p, 0));
     std::vector<float> cn(nlist);
     HIP_TRY(hipMemcpy(cn.data(), ix->cnorm2.p, (size_t)nlist * 4, hipMemcpyDeviceToHost));
@@ -117,8 +128,8 @@ int finish_replica(Replica* ix, const std::vector<uint32_t>& ln) {
     for (float v : cn) if (std::isfinite(v)) mx = std::max(mx, (double)v);
     ix->cnorm2_max = (float)(mx * 1.000001); // rounded up
     {   // one-product f16 image of the centroids, its residuals and the gate of the route (rank_mfma.hpp header)
-        if ((rc = alloc_arr(ix->cent_f16, (size_t)nlist * D * 2))) return rc;
-        if ((rc = alloc_arr(ix->cent_f16_resid, (size_t)nlist * 4))) return rc;
+        if ((rc = alloc_arr(ix->cent_f16, B.cent_f16))) return rc;
+        if ((rc = alloc_arr(ix->cent_f16_resid, B.cent_f16_resid))) return rc;
         HIP_TRY(launch_centroid_f16((const float*)ix->centroids.p, nlist, D, (uint16_t*)ix->cent_f16.p, (float*)ix->cent_f16_resid.p, 0));
         std::vector<float> rs(nlist);
         HIP_TRY(hipMemcpy(rs.data(), ix->cent_f16_resid.p, (size_t)nlist * 4, hipMemcpyDeviceToHost));
@@ -130,8 +141,8 @@ int finish_replica(Replica* ix, const std::vector<uint32_t>& ln) {
         ix->cnorm_max = (float)(std::sqrt(mx * 1.000001) * 1.000001);
         ix->rank_f16_ok = finite && (double)ix->rc_max <= std::ldexp((double)ix->cnorm_max, -11);
     }
-    if ((rc = alloc_arr(ix->lsum, (size_t)nlist * sizeof(BlockSummary)))) return rc;
-    if ((rc = alloc_arr(ix->bsumx, ix->n_blocks * sizeof(BlockSummaryEx)))) return rc;
+    if ((rc = alloc_arr(ix->lsum, B.lsum))) return rc;
+    if ((rc = alloc_arr(ix->bsumx, B.bsumx))) return rc;
     HIP_TRY(launch_list_summaries((const uint8_t*)ix->blocks.p, (const uint8_t*)ix->ex.p, (const float*)ix->fadd_ex.p,
                                   (const float*)ix->fres_ex.p, (const float*)ix->centroids.p, (const BlockSummary*)ix->bsum.p,
                                   (const uint32_t*)ix->list_gb0.p, (const uint32_t*)ix->list_n.p, nlist, D, ix->Dc, ix->ex_bits,
@@ -273,7 +284,7 @@ int clone_replica(const Replica* src, int dev, Replica** out) {
     ix->n_vectors = src->n_vectors; ix->n_lists = src->n_lists; ix->n_blocks = src->n_blocks;
     ix->cnorm2_max = src->cnorm2_max; ix->cnorm_max = src->cnorm_max; ix->rc_max = src->rc_max; ix->rank_f16_ok = src->rank_f16_ok; ix->h_list_n = src->h_list_n; ix->nblk_desc_prefix = src->nblk_desc_prefix;
     ix->opt = src->opt;
-    for (size_t i = 0; i < sizeof(ix->arrays) / sizeof(ix->arrays[0]); ++i) {
+    for (size_t i = 0; i < Replica::kCloned; ++i) {
         const Arr* s = src->arrays[i];
         Arr* d = ix->arrays[i];
         if (!s->p || s == &src->raw) continue;
@@ -312,41 +323,31 @@ int create_from_sources(const rbq_header* hdr, const std::vector<ListSrc>& lists
     Replica* ix = own.ix;
     Scratch cl; // (released before `own`)
     const uint32_t D = ix->D, Dc = ix->Dc, nlist = (uint32_t)ix->n_lists, exbits = ix->ex_bits;
-    const size_t ref_stride = (size_t)D * 4 + 384, dev_stride = (size_t)Dc * 4 + 384, exb = (size_t)D * exbits / 8;
-    const size_t exd = ex_bytes_dev(D, exbits);
-    std::vector<uint32_t> gb0(nlist), ln(nlist);
-    uint64_t nblocks = 0, nvec = 0;
+    const size_t ref_stride = (size_t)D * 4 + 384, exb = (size_t)D * exbits / 8;
+    std::vector<uint32_t> ln(nlist);
     // the reconstruction factors are kept when every non-empty list brings them
     bool recon = true;
     for (uint32_t c = 0; c < nlist; ++c)
         if (lists[c].n && (!lists[c].delta || !lists[c].vl)) recon = false;
     for (uint32_t c = 0; c < nlist; ++c) {
-        const ListSrc& L = lists[c];
-        if (L.n > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "list too large");
-        gb0[c] = (uint32_t)nblocks; ln[c] = (uint32_t)L.n;
-        nblocks += (L.n + 31) / 32; nvec += L.n;
-        if (nblocks * 32 > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "index too large for 32-bit vector slots");
+        if (lists[c].n > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "list too large"); // (create_impl and rbq1_parse have refused it)
+        ln[c] = (uint32_t)lists[c].n;
     }
-    ix->n_blocks = nblocks; ix->n_vectors = nvec;
-    const uint64_t nslots = nblocks * 32;
+    rbq_host::ListLayout lay;
+    std::string detail;
+    if (!rbq_host::list_layout(ln.data(), nlist, &lay, &detail)) return fail(RBQ_INVALID_CONFIG, detail);
+    const uint64_t nblocks = lay.blocks;
     int rc;
     if ((rc = upload_arr(ix->rot_blob, hdr->rotator_blob, hdr->rotator_len))) return rc;
-    if ((rc = upload_arr(ix->list_gb0, gb0.data(), (size_t)nlist * 4))) return rc;
-    if ((rc = upload_arr(ix->list_n, ln.data(), (size_t)nlist * 4))) return rc;
+    // (the pad of `ex` is zeroed here, synchronously, not behind the chunk loop on its stream: the chunk kernels write slot bytes
+    // only, never those 256, and the device is idle before the replica is handed on)
+    if ((rc = alloc_index_arrays(ix, ln, lay.gb0, nblocks, lay.vectors, recon, /*rnorm=*/false))) return rc;
+    const rbq_host::IndexBytes B = index_bytes_of(ix);
+    const size_t dev_stride = B.block_stride, exd = B.ex_slot;
     {
         std::vector<float> cent((size_t)nlist * D);
         for (uint32_t c = 0; c < nlist; ++c) std::memcpy(&cent[(size_t)c * D], lists[c].centroid, (size_t)D * 4);
         if ((rc = upload_arr(ix->centroids, cent.data(), cent.size() * 4))) return rc;
-    }
-    if ((rc = alloc_arr(ix->blocks, nblocks * dev_stride))) return rc;
-    if ((rc = alloc_arr(ix->ids, nslots * 8))) return rc;
-    if ((rc = alloc_arr(ix->ex, exd ? nslots * exd + 256 : 0))) return rc;
-    if ((rc = alloc_arr(ix->fadd_ex, exbits ? nslots * 4 : 0))) return rc;
-    if ((rc = alloc_arr(ix->fres_ex, exbits ? nslots * 4 : 0))) return rc;
-    if ((rc = alloc_arr(ix->bsum, nblocks * sizeof(BlockSummary)))) return rc;
-    if (recon) {
-        if ((rc = alloc_arr(ix->delta, nslots * 4))) return rc;
-        if ((rc = alloc_arr(ix->vl, nslots * 4))) return rc;
     }
 
     // Chunks of whole blocks (a long list may span several), staged through two pinned buffers: the host fills
@@ -385,9 +386,9 @@ int create_from_sources(const rbq_header* hdr, const std::vector<ListSrc>& lists
         uint32_t* nvb = reinterpret_cast<uint32_t*>(base + o_nv);
         uint64_t filled = 0, dense = 0;
         while (filled < nb) {
-            while (c < nlist && lb >= ((uint64_t)ln[c] + 31) / 32) { ++c; lb = 0; }
+            while (c < nlist && lb >= rbq_host::blocks_of(ln[c])) { ++c; lb = 0; }
             const ListSrc& L = lists[c];
-            const uint64_t lnb = ((uint64_t)ln[c] + 31) / 32, take = std::min<uint64_t>(lnb - lb, nb - filled);
+            const uint64_t lnb = rbq_host::blocks_of(ln[c]), take = std::min<uint64_t>(lnb - lb, nb - filled);
             const uint64_t v0 = lb * 32, v1 = std::min<uint64_t>(L.n, (lb + take) * 32), nv = v1 - v0;
             std::memcpy(base + o_recs + filled * ref_stride, L.batch_data + lb * ref_stride, take * ref_stride);
             if (nv) std::memcpy(base + o_ids + dense * 8, L.ids + v0 * 8, nv * 8);
@@ -433,11 +434,9 @@ int create_from_sources(const rbq_header* hdr, const std::vector<ListSrc>& lists
         b0 += nb;
         ++turn;
     }
-    if (exd) HIP_TRY(hipMemsetAsync((uint8_t*)ix->ex.p + nslots * exd, 0, 256, cl.stream)); // read-ahead pad of the refine loads
     HIP_TRY(hipStreamSynchronize(cl.stream));
     if ((rc = finish_replica(ix, ln))) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    ix->has_recon = recon;
     *out = own.release();
     return RBQ_OK;
 }
@@ -458,7 +457,7 @@ int create_impl(const rbq_header* hdr, const rbq_list_view* lists, const float* 
     for (uint64_t c = 0; c < hdr->n_lists; ++c) {
         const rbq_list_view& L = lists[c];
         if (L.n > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "list too large");
-        const uint64_t nb = (L.n + 31) / 32;
+        const uint64_t nb = rbq_host::blocks_of(L.n);
         if (L.batch_len != nb * ref_stride)
             return fail(RBQ_INVALID_PERSISTENCE, "batch_data length mismatch - possible corruption or version incompatibility");
         if (L.n && (!L.centroid || !L.ids || !L.batch_data || (hdr->ex_bits && (!L.ex_codes || !L.f_add_ex || !L.f_rescale_ex))))
@@ -812,7 +811,16 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
     RBQ_GUARD_BEGIN
     if (!h || h->reps.empty() || !name || !dst) return RBQ_INVALID_CONFIG;
     Replica* ix = h->reps[h->debug_replica];
-    const size_t stride = (size_t)ix->Dc * 4 + 384, exd = ex_bytes_dev(ix->D, ix->ex_bits), slots = ix->n_blocks * 32;
+    using rbq_host::IndexBytes;
+    const IndexBytes B = index_bytes_of(ix); // (every replica has the first one's geometry)
+    static const struct { const char* name; Arr Replica::*arr; size_t IndexBytes::*bytes; } kArrays[] = {
+        {"blocks", &Replica::blocks, &IndexBytes::blocks}, {"ids", &Replica::ids, &IndexBytes::ids}, {"ex", &Replica::ex, &IndexBytes::ex},
+        {"fadd_ex", &Replica::fadd_ex, &IndexBytes::fadd_ex}, {"fres_ex", &Replica::fres_ex, &IndexBytes::fres_ex},
+        {"bsum", &Replica::bsum, &IndexBytes::bsum}, {"lsum", &Replica::lsum, &IndexBytes::lsum}, {"bsumx", &Replica::bsumx, &IndexBytes::bsumx},
+        {"centroids", &Replica::centroids, &IndexBytes::centroids}, {"list_gb0", &Replica::list_gb0, &IndexBytes::list_gb0},
+        {"list_n", &Replica::list_n, &IndexBytes::list_n}, {"cent_hl", &Replica::cent_hl, &IndexBytes::cent_hl},
+        {"cent_f16", &Replica::cent_f16, &IndexBytes::cent_f16}, {"cent_f16_resid", &Replica::cent_f16_resid, &IndexBytes::cent_f16_resid},
+        {"cnorm2", &Replica::cnorm2, &IndexBytes::cnorm2}};
     const void* p = nullptr;
     size_t have = 0;
     if (!std::strcmp(name, "rerank_raw_dtype")) { // (not an array: RBQ_RAW_* of the attached rerank rows as one int32, -1 with none attached)
@@ -839,34 +847,21 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
         std::memcpy(dst, &v, 4);
         return RBQ_OK;
     }
-    if (!std::strcmp(name, "blocks")) { p = ix->blocks.p; have = ix->n_blocks * stride; }
-    else if (!std::strcmp(name, "ids")) { p = ix->ids.p; have = slots * 8; }
-    else if (!std::strcmp(name, "ex")) { p = ix->ex.p; have = slots * exd; }
-    else if (!std::strcmp(name, "fadd_ex")) { p = ix->fadd_ex.p; have = ix->ex_bits ? slots * 4 : 0; }
-    else if (!std::strcmp(name, "fres_ex")) { p = ix->fres_ex.p; have = ix->ex_bits ? slots * 4 : 0; }
-    else if (!std::strcmp(name, "bsum")) { p = ix->bsum.p; have = ix->n_blocks * sizeof(BlockSummary); }
-    else if (!std::strcmp(name, "lsum")) { p = ix->lsum.p; have = ix->n_lists * sizeof(BlockSummary); }
-    else if (!std::strcmp(name, "bsumx")) { p = ix->bsumx.p; have = ix->n_blocks * sizeof(BlockSummaryEx); }
-    else if (!std::strcmp(name, "centroids")) { p = ix->centroids.p; have = ix->n_lists * ix->D * 4; }
-    else if (!std::strcmp(name, "list_gb0")) { p = ix->list_gb0.p; have = ix->n_lists * 4; }
-    else if (!std::strcmp(name, "list_n")) { p = ix->list_n.p; have = ix->n_lists * 4; }
-    else if (!std::strcmp(name, "cent_hl")) { p = ix->cent_hl.p; have = ix->n_lists * ix->D * 4; }
-    else if (const int plane = hl_plane_of(name, "cent_hi", "cent_lo"); plane >= 0) { // logical view of "cent_hl"
-        if (!ix->cent_hl.p || bytes != ix->n_lists * ix->D * 2)
-            return fail(RBQ_INVALID_CONFIG, "unknown array or size (have " + std::to_string(ix->n_lists * ix->D * 2) + " bytes)");
+    if (const int plane = hl_plane_of(name, "cent_hi", "cent_lo"); plane >= 0) { // logical view of "cent_hl"
+        if (!ix->cent_hl.p || bytes != B.cent_hl / 2)
+            return fail(RBQ_INVALID_CONFIG, "unknown array or size (have " + std::to_string(B.cent_hl / 2) + " bytes)");
         DeviceGuard g(ix->device);
         return copy_hl_plane(ix->cent_hl.p, ix->n_lists, ix->D, plane, dst);
     }
-    else if (!std::strcmp(name, "cent_f16")) { p = ix->cent_f16.p; have = ix->n_lists * ix->D * 2; }
-    else if (!std::strcmp(name, "cent_f16_resid")) { p = ix->cent_f16_resid.p; have = ix->n_lists * 4; }
-    else if (!std::strcmp(name, "cnorm2")) { p = ix->cnorm2.p; have = ix->n_lists * 4; }
-    else if (!std::strcmp(name, "delta") || !std::strcmp(name, "vl")) { // (first replica only)
+    for (const auto& a : kArrays)
+        if (!std::strcmp(name, a.name)) { p = (ix->*a.arr).p; have = B.*a.bytes; }
+    if (!std::strcmp(name, "delta") || !std::strcmp(name, "vl")) { // (first replica only)
         ix = h->reps[0];
-        p = name[0] == 'd' ? ix->delta.p : ix->vl.p; have = ix->has_recon ? ix->n_blocks * 32 * 4 : 0;
+        p = name[0] == 'd' ? ix->delta.p : ix->vl.p; have = ix->has_recon ? B.delta : 0;
     }
     else if (!std::strcmp(name, "rnorm")) { // (first replica only; MSTG handles)
         ix = h->reps[0];
-        p = ix->rnorm.p; have = ix->has_rnorm ? ix->n_blocks * 32 * 4 : 0;
+        p = ix->rnorm.p; have = ix->has_rnorm ? B.rnorm : 0;
     }
     if (!p || bytes != have) return fail(RBQ_INVALID_CONFIG, "unknown array or size (have " + std::to_string(have) + " bytes)");
     DeviceGuard g(ix->device);

@@ -45,9 +45,10 @@ int load_stream_impl(rbq_read_fn read, void* user, uint64_t total, int n_devices
     int dev = 0;
     if (dv_rc == RBQ_OK) dev = devs[0];
     else HIP_TRY(hipGetDevice(&dev));
-    uint64_t nblocks = 0;
-    bool too_large = false;
-    for (uint32_t n : F.list_n) { nblocks += ((uint64_t)n + 31) / 32; if (nblocks * 32 > 0xffffffffull) too_large = true; }
+    rbq_host::ListLayout lay;
+    std::string too_large_detail;
+    const bool too_large = !rbq_host::list_layout(F.list_n.data(), F.list_n.size(), &lay, &too_large_detail); // (no early return: below)
+    const uint64_t nblocks = lay.blocks;
     // the index is built while the spans pass when the stream is framed to its end and this build can serve it
     const bool scatter = F.complete() && vh_rc == RBQ_OK && dv_rc == RBQ_OK && !too_large;
     const bool want_crc = F.complete();
@@ -76,28 +77,13 @@ int load_stream_impl(rbq_read_fn read, void* user, uint64_t total, int n_devices
     Replica* ix = nullptr;
     Scratch t; // (released before `own`)
     const uint32_t nlist = (uint32_t)F.list_n.size();
-    const uint64_t nslots = nblocks * 32;
     int rc;
     if (scatter) {
         hdr.rotator_blob = blob.data();
         own.ix = ix = new_replica(&hdr, dev);
-        const size_t dev_stride = (size_t)ix->Dc * 4 + 384, exd = ex_bytes_dev(ix->D, ix->ex_bits);
-        std::vector<uint32_t> gb0(nlist);
-        uint64_t b = 0;
-        for (uint32_t c = 0; c < nlist; ++c) { gb0[c] = (uint32_t)b; b += ((uint64_t)F.list_n[c] + 31) / 32; }
-        ix->n_blocks = nblocks; ix->n_vectors = F.actual;
         if ((rc = upload_arr(ix->rot_blob, blob.data(), F.h.rotator_len))) return rc;
-        if ((rc = upload_arr(ix->list_gb0, gb0.data(), (size_t)nlist * 4))) return rc;
-        if ((rc = upload_arr(ix->list_n, F.list_n.data(), (size_t)nlist * 4))) return rc;
-        if ((rc = alloc_arr(ix->centroids, (size_t)nlist * ix->D * 4))) return rc;
-        if ((rc = alloc_arr(ix->blocks, nblocks * dev_stride))) return rc;
-        if ((rc = alloc_arr(ix->ids, nslots * 8))) return rc;
-        if ((rc = alloc_arr(ix->ex, exd ? nslots * exd + 256 : 0))) return rc;
-        if ((rc = alloc_arr(ix->fadd_ex, ix->ex_bits ? nslots * 4 : 0))) return rc;
-        if ((rc = alloc_arr(ix->fres_ex, ix->ex_bits ? nslots * 4 : 0))) return rc;
-        if ((rc = alloc_arr(ix->bsum, nblocks * sizeof(BlockSummary)))) return rc;
-        if ((rc = alloc_arr(ix->delta, nslots * 4))) return rc;
-        if ((rc = alloc_arr(ix->vl, nslots * 4))) return rc;
+        if ((rc = alloc_index_arrays(ix, F.list_n, lay.gb0, nblocks, F.actual, /*recon=*/true, /*rnorm=*/false))) return rc;
+        if ((rc = alloc_arr(ix->centroids, index_bytes_of(ix).centroids))) return rc;
         blob = std::vector<uint8_t>();
     }
 
@@ -123,7 +109,6 @@ int load_stream_impl(rbq_read_fn read, void* user, uint64_t total, int n_devices
         HIP_TRY(t.event(&ev[i]));
     }
     HIP_TRY(hipMemsetAsync(d_bad, 0xff, 8, t.stream));
-    if (scatter && ix->ex.bytes) HIP_TRY(hipMemsetAsync((uint8_t*)ix->ex.p + ix->ex.bytes - 256, 0, 256, t.stream)); // read-ahead pad of the refine loads
 
     LoadSpanParams P;
     std::memset(&P, 0, sizeof P);
@@ -177,7 +162,7 @@ int load_stream_impl(rbq_read_fn read, void* user, uint64_t total, int n_devices
     if ((rc = rbq_host::load_verdict_crc(crc, stored, &detail))) return fail(rc, detail);
     if (vh_rc) return fail(vh_rc, vh_detail);
     if (dv_rc) return fail(dv_rc, dv_detail);
-    if (too_large) return fail(RBQ_INVALID_CONFIG, "index too large for 32-bit vector slots");
+    if (too_large) return fail(RBQ_INVALID_CONFIG, too_large_detail);
 
     uint32_t* d_bnv = nullptr;
     HIP_TRY(t.alloc(&d_bnv, nblocks * 4));
@@ -186,7 +171,6 @@ int load_stream_impl(rbq_read_fn read, void* user, uint64_t total, int n_devices
     HIP_TRY(hipStreamSynchronize(t.stream));
     if ((rc = finish_replica(ix, F.list_n))) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    ix->has_recon = true;
     return wrap_and_replicate(own.release(), devs, out);
 }
 } // namespace

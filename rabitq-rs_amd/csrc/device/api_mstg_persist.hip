@@ -168,28 +168,20 @@ int mstg_load_impl(rbq_read_fn read, void* user, uint64_t total, int device, rbq
     Replica* ix = own.ix;
     Scratch t; // (released before `own`)
     const uint32_t Dc = ix->Dc;
-    const size_t dev_stride = (size_t)Dc * 4 + 384, exd = ex_bytes_dev(D, ex_bits);
     const uint64_t R = rbq_host::mstg_record_len(D, ex_bits);
-    std::vector<uint32_t> ln(nlist), gb0(nlist);
-    uint64_t nblocks = 0;
-    for (uint32_t c = 0; c < nlist; ++c) { ln[c] = (uint32_t)F.lists[c].n; gb0[c] = (uint32_t)nblocks; nblocks += (F.lists[c].n + 31) / 32; }
-    ix->n_blocks = nblocks; ix->n_vectors = F.n_vectors;
-    const uint64_t nslots = nblocks * 32;
+    std::vector<uint32_t> ln(nlist);
+    for (uint32_t c = 0; c < nlist; ++c) ln[c] = (uint32_t)F.lists[c].n;
+    rbq_host::ListLayout lay;
+    {   // (the framing has refused a stream whose lists pass 2^32 - 1 slots, with its own message)
+        std::string detail;
+        if (!rbq_host::list_layout(ln.data(), nlist, &lay, &detail)) return fail(RBQ_INVALID_PERSISTENCE, detail);
+    }
+    const std::vector<uint32_t>& gb0 = lay.gb0;
+    const uint64_t nblocks = lay.blocks;
     if ((rc = upload_arr(ix->rot_blob, nullptr, 0))) return rc;
     if ((rc = upload_arr(ix->centroids, F.centroids.data(), F.centroids.size() * 4))) return rc;
-    if ((rc = upload_arr(ix->list_gb0, gb0.data(), (size_t)nlist * 4))) return rc;
-    if ((rc = upload_arr(ix->list_n, ln.data(), (size_t)nlist * 4))) return rc;
-    if ((rc = alloc_arr(ix->blocks, nblocks * dev_stride))) return rc;
-    if ((rc = alloc_arr(ix->ids, nslots * 8))) return rc;
-    if ((rc = alloc_arr(ix->ex, exd ? nslots * exd + 256 : 0))) return rc;
-    if ((rc = alloc_arr(ix->fadd_ex, ex_bits ? nslots * 4 : 0))) return rc;
-    if ((rc = alloc_arr(ix->fres_ex, ex_bits ? nslots * 4 : 0))) return rc;
-    if ((rc = alloc_arr(ix->bsum, nblocks * sizeof(BlockSummary)))) return rc;
-    if ((rc = alloc_arr(ix->delta, nslots * 4))) return rc;
-    if ((rc = alloc_arr(ix->vl, nslots * 4))) return rc;
-    if ((rc = alloc_arr(ix->rnorm, nslots * 4))) return rc;
-    ix->has_recon = true; ix->has_rnorm = true; ix->tc_some = F.has_t; ix->tc_value = F.t_const;
-    if (exd) HIP_TRY(hipMemset((uint8_t*)ix->ex.p + nslots * exd, 0, 256)); // read-ahead pad of the refine loads
+    if ((rc = alloc_index_arrays(ix, ln, gb0, nblocks, F.n_vectors, /*recon=*/true, /*rnorm=*/true))) return rc;
+    ix->tc_some = F.has_t; ix->tc_value = F.t_const;
 
     // block tables and the spans: units (a list's prefix and header, a block's records) are joined while they fit the budget
     std::vector<uint64_t> boff(nblocks);
@@ -327,9 +319,6 @@ uint64_t rbq_mstg_memory_usage(const rbq_index* idx) {
     uint64_t total = 0;
     for (const Arr* a : ix->arrays)
         if (a->p && !(a == &ix->raw && ix->raw_borrowed)) total += a->bytes;
-    for (const Arr* a : {&ix->delta, &ix->vl, &ix->rnorm, &ix->fmap_ids, &ix->fmap_slots, &ix->ms_hi, &ix->ms_lo, &ix->ms_nc,
-                         &ix->mr_slot_map, &ix->mr_blk_list})
-        if (a->p) total += a->bytes;
     return total;
 }
 } // extern "C"

@@ -43,8 +43,7 @@ int remove_ids_core(const rbq_index* idx, const uint64_t* ids, uint64_t n_ids, c
     rbq_header hdr{};
     hdr.dim = old->dim; hdr.padded_dim = old->D; hdr.metric = old->metric; hdr.rotator = old->rotator; hdr.ex_bits = old->ex_bits;
     hdr.n_lists = old->n_lists;
-    const uint32_t D = old->D, Dc = old->Dc, nlist = (uint32_t)old->n_lists;
-    const size_t dev_stride = (size_t)Dc * 4 + 384, exd = ex_bytes_dev(D, old->ex_bits);
+    const uint32_t Dc = old->Dc, nlist = (uint32_t)old->n_lists;
     const uint64_t nb_old = old->n_blocks;
     Scratch t;
 
@@ -66,12 +65,10 @@ int remove_ids_core(const rbq_index* idx, const uint64_t* ids, uint64_t n_ids, c
         HIP_TRY(t.alloc(&d_tmp, tb));
         HIP_TRY(sort_keys_u64(d_tmp, &tb, d_in, d_set, (size_t)n_ids, 0));
 
-        std::vector<uint32_t> gb0_old(nlist);
-        uint64_t run = 0;
-        for (uint32_t c = 0; c < nlist && c < old->h_list_n.size(); ++c) { gb0_old[c] = (uint32_t)run; run += ((uint64_t)old->h_list_n[c] + 31u) / 32u; }
-        if (old->h_list_n.size() != nlist || run != nb_old)
+        rbq_host::ListLayout lay_old;
+        if (old->h_list_n.size() != nlist || !rbq_host::list_layout(old->h_list_n.data(), nlist, &lay_old, nullptr) || lay_old.blocks != nb_old)
             return fail(RBQ_IO, "internal error: the handle's block count does not match its list sizes");
-        if ((rc = upload_block_tables(old->h_list_n, gb0_old, nb_old, t, &d_bl_old, &d_nv_old))) return rc;
+        if ((rc = upload_block_tables(old->h_list_n, lay_old.gb0, nb_old, t, &d_bl_old, &d_nv_old))) return rc;
         HIP_TRY(t.alloc(&d_mask, (nb_old + 1) * 4)); // (one entry more: the scan's last value is the total)
         HIP_TRY(t.alloc(&d_scan, (nb_old + 1) * 4));
         HIP_TRY(t.alloc(&d_kept, (size_t)nlist * 4));
@@ -102,28 +99,16 @@ int remove_ids_core(const rbq_index* idx, const uint64_t* ids, uint64_t n_ids, c
         return fail(RBQ_INVALID_CONFIG, "the ids cover every vector of the index: an index without vectors cannot be built");
     ReplicaOwner own{new_replica(&hdr, dev)};
     Replica* ix = own.ix;
-    const uint64_t nblocks = plan.new_blocks, nslots = nblocks * 32;
-    ix->n_blocks = nblocks; ix->n_vectors = plan.new_vectors;
+    const uint64_t nblocks = plan.new_blocks;
     for (Arr Replica::*m : {&Replica::rot_blob, &Replica::centroids}) { // bit for bit those of the old handle
         if ((rc = alloc_arr(ix->*m, (old->*m).bytes))) return rc;
         if ((old->*m).bytes) HIP_TRY(hipMemcpy((ix->*m).p, (old->*m).p, (old->*m).bytes, hipMemcpyDeviceToDevice));
     }
-    if ((rc = upload_arr(ix->list_gb0, plan.new_gb0.data(), (size_t)nlist * 4))) return rc;
-    if ((rc = upload_arr(ix->list_n, plan.new_n.data(), (size_t)nlist * 4))) return rc;
-    if ((rc = alloc_arr(ix->blocks, nblocks * dev_stride))) return rc;
-    if ((rc = alloc_arr(ix->ids, nslots * 8))) return rc;
-    if ((rc = alloc_arr(ix->ex, exd ? nslots * exd + 256 : 0))) return rc;
-    if ((rc = alloc_arr(ix->fadd_ex, ix->ex_bits ? nslots * 4 : 0))) return rc;
-    if ((rc = alloc_arr(ix->fres_ex, ix->ex_bits ? nslots * 4 : 0))) return rc;
-    if ((rc = alloc_arr(ix->bsum, nblocks * sizeof(BlockSummary)))) return rc;
-    if ((rc = alloc_arr(ix->delta, nslots * 4))) return rc;
-    if ((rc = alloc_arr(ix->vl, nslots * 4))) return rc;
-    ix->has_recon = true;
-    if (old->has_rnorm) { // an MSTG handle: what the `.mstg` format stores beyond the search's arrays
-        if ((rc = alloc_arr(ix->rnorm, nslots * 4))) return rc;
-        ix->has_rnorm = true; ix->tc_some = old->tc_some; ix->tc_value = old->tc_value;
-    }
-    if (exd) HIP_TRY(hipMemset((uint8_t*)ix->ex.p + nslots * exd, 0, 256)); // read-ahead pad of the refine loads
+    // (rnorm: an MSTG handle keeps what the `.mstg` format stores beyond the search's arrays)
+    if ((rc = alloc_index_arrays(ix, plan.new_n, plan.new_gb0, nblocks, plan.new_vectors, /*recon=*/true, old->has_rnorm))) return rc;
+    if (old->has_rnorm) { ix->tc_some = old->tc_some; ix->tc_value = old->tc_value; }
+    const rbq_host::IndexBytes B = index_bytes_of(ix);
+    const size_t dev_stride = B.block_stride, exd = B.ex_slot, nslots = B.slots;
 
     // ---- the slot map, then the gather
     uint32_t *d_block_list = nullptr, *d_block_nv = nullptr, *d_map = nullptr;
@@ -136,16 +121,7 @@ int remove_ids_core(const rbq_index* idx, const uint64_t* ids, uint64_t n_ids, c
         RemoveGatherParams P{};
         P.map = d_map; P.nb_new = (uint32_t)nblocks; P.n_slots_old = (uint32_t)(nb_old * 32);
         P.rec = (uint32_t)dev_stride; P.G16 = Dc / 128u; P.tail = Dc % 128u == 64u ? 1u : 0u; P.ex16 = (uint32_t)(exd / 16);
-        P.blocks_s = (const uint8_t*)old->blocks.p; P.blocks_d = (uint8_t*)ix->blocks.p;
-        P.ex_s = exd ? (const uint8_t*)old->ex.p : nullptr; P.ex_d = exd ? (uint8_t*)ix->ex.p : nullptr;
-        P.ids_s = (const uint64_t*)old->ids.p; P.ids_d = (uint64_t*)ix->ids.p;
-        if (ix->ex_bits) {
-            P.fadd_s = (const float*)old->fadd_ex.p; P.fadd_d = (float*)ix->fadd_ex.p;
-            P.fres_s = (const float*)old->fres_ex.p; P.fres_d = (float*)ix->fres_ex.p;
-        }
-        P.delta_s = (const float*)old->delta.p; P.delta_d = (float*)ix->delta.p;
-        P.vl_s = (const float*)old->vl.p; P.vl_d = (float*)ix->vl.p;
-        if (ix->has_rnorm) { P.rnorm_s = (const float*)old->rnorm.p; P.rnorm_d = (float*)ix->rnorm.p; }
+        P.src = slot_arrays(old); P.dst = slot_arrays(ix);
         EventPair ev;
         ev.start();
         HIP_TRY(launch_remove_gather(P, dev, 0));

@@ -32,10 +32,10 @@ __global__ __launch_bounds__(256) void k_append_carry(AppendCarryParams P) {
         uint32_t sb = rbq_host::append_src_block(b, P.gb0_new[c], P.gb0_old[c], P.n_old[c]);
         if (sb >= P.nb_old) sb = rbq_host::kAppendNoBlock; // (never for a plan that matches the old index)
         const bool has = sb != rbq_host::kAppendNoBlock; // uniform
-        const uint4* rs = reinterpret_cast<const uint4*>(P.blocks_s) + (size_t)(has ? sb : 0u) * P.rec16;
-        const uint4* es = reinterpret_cast<const uint4*>(P.ex_s) + (size_t)(has ? sb : 0u) * P.ex16;
-        uint4* rd = reinterpret_cast<uint4*>(P.blocks_d) + (size_t)b * P.rec16;
-        uint4* ed = reinterpret_cast<uint4*>(P.ex_d) + (size_t)b * P.ex16;
+        const uint4* rs = reinterpret_cast<const uint4*>(P.src.blocks) + (size_t)(has ? sb : 0u) * P.rec16;
+        const uint4* es = reinterpret_cast<const uint4*>(P.src.ex) + (size_t)(has ? sb : 0u) * P.ex16;
+        uint4* rd = reinterpret_cast<uint4*>(P.dst.blocks) + (size_t)b * P.rec16;
+        uint4* ed = reinterpret_cast<uint4*>(P.dst.ex) + (size_t)b * P.ex16;
         for (uint32_t i = tid; i < tot16; i += 256u) {
             const bool rec = i < P.rec16;
             uint4 v = zero;
@@ -46,20 +46,20 @@ __global__ __launch_bounds__(256) void k_append_carry(AppendCarryParams P) {
         if (tid >= 192u) {
             const uint32_t l = tid - 192u;
             if (l < 16u) { // ids: 16 units
-                const uint4* s = reinterpret_cast<const uint4*>(P.ids_s) + (size_t)(has ? sb : 0u) * 16u + l;
+                const uint4* s = reinterpret_cast<const uint4*>(P.src.ids) + (size_t)(has ? sb : 0u) * 16u + l;
                 uint4 v = ones; // (not `has ? *s : ones`: the compiler then selects between addresses and parks `ones` in scratch)
                 if (has) v = *s;
-                reinterpret_cast<uint4*>(P.ids_d)[(size_t)b * 16u + l] = v;
+                reinterpret_cast<uint4*>(P.dst.ids)[(size_t)b * 16u + l] = v;
             } else if (l < 48u) { // fadd_ex, fres_ex, delta, vl: 8 units each (branches, not a pointer table: no scratch)
                 const uint32_t a = (l - 16u) >> 3, u = (l - 16u) & 7u;
                 const size_t si = (size_t)(has ? sb : 0u) * 8u + u, di = (size_t)b * 8u + u;
-                if (a == 0u) { if (P.fadd_d) carry_unit(P.fadd_s, P.fadd_d, si, di, has); }
-                else if (a == 1u) { if (P.fres_d) carry_unit(P.fres_s, P.fres_d, si, di, has); }
-                else if (a == 2u) carry_unit(P.delta_s, P.delta_d, si, di, has);
-                else carry_unit(P.vl_s, P.vl_d, si, di, has);
+                if (a == 0u) { if (P.dst.fadd) carry_unit(P.src.fadd, P.dst.fadd, si, di, has); }
+                else if (a == 1u) { if (P.dst.fres) carry_unit(P.src.fres, P.dst.fres, si, di, has); }
+                else if (a == 2u) carry_unit(P.src.delta, P.dst.delta, si, di, has);
+                else carry_unit(P.src.vl, P.dst.vl, si, di, has);
             } else if (l < 56u) { // rnorm (MSTG handles): 8 units, the next lanes of the same wave
                 const uint32_t u = l - 48u;
-                if (P.rnorm_d) carry_unit(P.rnorm_s, P.rnorm_d, (size_t)(has ? sb : 0u) * 8u + u, (size_t)b * 8u + u, has);
+                if (P.dst.rnorm) carry_unit(P.src.rnorm, P.dst.rnorm, (size_t)(has ? sb : 0u) * 8u + u, (size_t)b * 8u + u, has);
             }
         }
     }

@@ -89,8 +89,8 @@ __global__ __launch_bounds__(256) void k_remove_gather(RemoveGatherParams P) {
         if (src >= P.n_slots_old) src = rbq_host::kRemoveNoSlot; // (a pad; never anything else for a map of this index)
         const bool has = src != rbq_host::kRemoveNoSlot;
         const uint32_t sb = has ? src >> 5 : 0u, sl = has ? src & 31u : 0u;
-        const uint8_t* rs = P.blocks_s + (size_t)sb * P.rec;
-        uint8_t* rd = P.blocks_d + (size_t)b * P.rec;
+        const uint8_t* rs = P.src.blocks + (size_t)sb * P.rec;
+        uint8_t* rd = P.dst.blocks + (size_t)b * P.rec;
         for (uint32_t g = grp; g < P.G16; g += 8u) {
             uint4 x = zero;
             if (has) x = *reinterpret_cast<const uint4*>(rs + (size_t)g * 512u + sl * 16u);
@@ -110,19 +110,19 @@ __global__ __launch_bounds__(256) void k_remove_gather(RemoveGatherParams P) {
         const size_t ds = (size_t)b * 32u + v;
         if (grp == 0u) { // (branches, not a pointer table: no scratch)
             uint64_t x = ~0ull;
-            if (has) x = P.ids_s[src];
-            P.ids_d[ds] = x;
-        } else if (grp == 1u) { if (P.fadd_d) gather_f32(P.fadd_s, P.fadd_d, src, ds, has); }
-        else if (grp == 2u) { if (P.fres_d) gather_f32(P.fres_s, P.fres_d, src, ds, has); }
-        else if (grp == 3u) gather_f32(P.delta_s, P.delta_d, src, ds, has);
-        else if (grp == 4u) gather_f32(P.vl_s, P.vl_d, src, ds, has);
-        else if (grp == 5u) { if (P.rnorm_d) gather_f32(P.rnorm_s, P.rnorm_d, src, ds, has); } // (its second task, after a factor row)
+            if (has) x = P.src.ids[src];
+            P.dst.ids[ds] = x;
+        } else if (grp == 1u) { if (P.dst.fadd) gather_f32(P.src.fadd, P.dst.fadd, src, ds, has); }
+        else if (grp == 2u) { if (P.dst.fres) gather_f32(P.src.fres, P.dst.fres, src, ds, has); }
+        else if (grp == 3u) gather_f32(P.src.delta, P.dst.delta, src, ds, has);
+        else if (grp == 4u) gather_f32(P.src.vl, P.dst.vl, src, ds, has);
+        else if (grp == 5u) { if (P.dst.rnorm) gather_f32(P.src.rnorm, P.dst.rnorm, src, ds, has); } // (its second task, after a factor row)
         if (P.ex16) { // slot tid / 8 of the block, unit tid % 8, + 8, ...; lane (slot % 32) of this wave holds the slot's source
             const uint32_t slot = tid >> 3, j = tid & 7u;
             const uint32_t s2 = (uint32_t)__shfl((int)src, (int)(slot & 31u));
             const bool has2 = s2 != rbq_host::kRemoveNoSlot;
-            const uint4* es = reinterpret_cast<const uint4*>(P.ex_s) + (size_t)(has2 ? s2 : 0u) * P.ex16;
-            uint4* ed = reinterpret_cast<uint4*>(P.ex_d) + ((size_t)b * 32u + slot) * P.ex16;
+            const uint4* es = reinterpret_cast<const uint4*>(P.src.ex) + (size_t)(has2 ? s2 : 0u) * P.ex16;
+            uint4* ed = reinterpret_cast<uint4*>(P.dst.ex) + ((size_t)b * 32u + slot) * P.ex16;
             for (uint32_t u = j; u < P.ex16; u += 8u) {
                 uint4 x = zero;
                 if (has2) x = es[u];

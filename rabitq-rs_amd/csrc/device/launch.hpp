@@ -555,6 +555,14 @@ hipError_t launch_load_span(const LoadSpanParams& P, uint64_t n_workgroups, hipS
 // block_nv[b] = real vectors of global block b (1..32), from the lists' first blocks and sizes
 hipError_t launch_load_block_nv(const uint32_t* list_gb0, const uint32_t* list_n, uint32_t n_lists, uint32_t* block_nv, hipStream_t s);
 
+// The per-slot arrays of a replica as the carry and the gather kernel move them from an old index (src) into a new one (dst)
+struct SlotArrays {
+    uint8_t *blocks, *ex;             // ex: null for a 1-bit index
+    uint64_t* ids;
+    float *fadd, *fres, *delta, *vl;  // fadd / fres: null for a 1-bit index
+    float* rnorm;                     // MSTG handles (rbq_mstg_append, rbq_mstg_remove_ids): residual norms, a sixth per-slot array; null: none
+};
+
 // ---- rbq_index_append (k_append.hip; csrc/host/rbq_append_plan.hpp) ------------------------------------
 // The arrays of an index moved into the geometry of a grown one: new block b of list c = block_list[b] takes old block
 // append_src_block(b, gb0_new[c], gb0_old[c], n_old[c]) — its record, ids, ex codes, ex factors and reconstruction factors — or,
@@ -564,14 +572,7 @@ struct AppendCarryParams {
     const uint32_t *gb0_new, *gb0_old, *n_old;  // [n_lists]
     uint32_t nb_new, nb_old;
     uint32_t rec16, ex16;                       // 16-byte units of a block record / of a block's 32 ex codes (0: 1-bit index)
-    const uint8_t *blocks_s, *ex_s;
-    uint8_t *blocks_d, *ex_d;
-    const uint64_t* ids_s;
-    uint64_t* ids_d;
-    const float *fadd_s, *fres_s, *delta_s, *vl_s; // fadd / fres: null for a 1-bit index
-    float *fadd_d, *fres_d, *delta_d, *vl_d;
-    const float* rnorm_s;                       // MSTG handles (rbq_mstg_append): residual norms, a sixth per-slot array; null: none
-    float* rnorm_d;
+    SlotArrays src, dst;
 };
 hipError_t launch_append_carry(const AppendCarryParams& P, int device, hipStream_t s);
 // *out (device, zeroed by the caller) = max over the real slots of id + 1 (saturating); block_nv [n_blocks] as launch_load_block_nv leaves it
@@ -604,14 +605,7 @@ struct RemoveGatherParams {
     uint32_t nb_new, n_slots_old;
     uint32_t rec, G16, tail;                    // bytes of a block record (4 Dc + 384), full code granules (Dc / 128), Dc % 128 == 64
     uint32_t ex16;                              // 16-byte units of one slot's ex code (0: 1-bit index)
-    const uint8_t *blocks_s, *ex_s;
-    uint8_t *blocks_d, *ex_d;
-    const uint64_t* ids_s;
-    uint64_t* ids_d;
-    const float *fadd_s, *fres_s, *delta_s, *vl_s; // fadd / fres: null for a 1-bit index
-    float *fadd_d, *fres_d, *delta_d, *vl_d;
-    const float* rnorm_s;                       // MSTG handles (rbq_mstg_remove_ids): residual norms, a sixth per-slot array; null: none
-    float* rnorm_d;
+    SlotArrays src, dst;
 };
 hipError_t launch_remove_gather(const RemoveGatherParams& P, int device, hipStream_t s);
 

@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "rbq_index_layout.hpp"
+
 #if defined(__HIPCC__)
 #define RBQ_APPEND_HD __host__ __device__
 #else
@@ -37,23 +39,19 @@ struct AppendPlan {
 // false (with *detail) when a list would pass 2^32 - 1 vectors or the index 2^32 vector slots
 inline bool append_plan(const uint32_t* old_n, const uint64_t* added, size_t n_lists, AppendPlan* out, std::string* detail) {
     AppendPlan p;
-    p.new_n.resize(n_lists); p.new_gb0.resize(n_lists); p.old_gb0.resize(n_lists); p.cursor.resize(n_lists);
-    for (size_t c = 0; c < n_lists; ++c) {
-        const uint64_t n = (uint64_t)old_n[c] + added[c];
-        if (added[c] > 0xffffffffull || n > 0xffffffffull) {
-            if (detail) *detail = "list " + std::to_string(c) + " would hold more than 2^32 - 1 vectors";
-            return false;
-        }
-        p.old_gb0[c] = (uint32_t)p.old_blocks; p.new_gb0[c] = (uint32_t)p.new_blocks;
-        p.new_n[c] = (uint32_t)n; p.cursor[c] = old_n[c];
-        p.old_blocks += ((uint64_t)old_n[c] + 31u) / 32u;
-        p.new_blocks += (n + 31u) / 32u;
-        p.new_vectors += n;
-        if (p.old_blocks * 32u > 0xffffffffull || p.new_blocks * 32u > 0xffffffffull) {
-            if (detail) *detail = "index too large for 32-bit vector slots";
-            return false;
-        }
+    p.new_n.resize(n_lists); p.cursor.assign(old_n, old_n + n_lists);
+    size_t ok = 0; // lists before the first one that would hold too many vectors
+    for (; ok < n_lists && added[ok] <= 0xffffffffull && (uint64_t)old_n[ok] + added[ok] <= 0xffffffffull; ++ok)
+        p.new_n[ok] = (uint32_t)(old_n[ok] + added[ok]);
+    // (the slots of the lists before it are checked first: the first failure in list order is the one reported)
+    ListLayout before, after;
+    if (!list_layout(old_n, ok, &before, detail) || !list_layout(p.new_n.data(), ok, &after, detail)) return false;
+    if (ok < n_lists) {
+        if (detail) *detail = "list " + std::to_string(ok) + " would hold more than 2^32 - 1 vectors";
+        return false;
     }
+    p.old_gb0 = std::move(before.gb0); p.new_gb0 = std::move(after.gb0);
+    p.old_blocks = before.blocks; p.new_blocks = after.blocks; p.new_vectors = after.vectors;
     *out = std::move(p);
     return true;
 }

@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "rbq_index_layout.hpp"
+
 #if defined(__HIPCC__)
 #define RBQ_REMOVE_HD __host__ __device__
 #else
@@ -38,24 +40,19 @@ struct RemovePlan {
 
 // false (with *detail) when a list is said to keep more vectors than it holds or the old index passes 2^32 vector slots
 inline bool remove_plan(const uint32_t* old_n, const uint32_t* kept, size_t n_lists, RemovePlan* out, std::string* detail) {
-    RemovePlan p;
-    p.new_n.resize(n_lists); p.new_gb0.resize(n_lists); p.old_gb0.resize(n_lists);
-    for (size_t c = 0; c < n_lists; ++c) {
-        if (kept[c] > old_n[c]) {
-            if (detail) *detail = "list " + std::to_string(c) + " would keep more vectors than it holds";
-            return false;
-        }
-        p.old_gb0[c] = (uint32_t)p.old_blocks; p.new_gb0[c] = (uint32_t)p.new_blocks;
-        p.new_n[c] = kept[c];
-        p.old_blocks += ((uint64_t)old_n[c] + 31u) / 32u;
-        p.new_blocks += ((uint64_t)kept[c] + 31u) / 32u;
-        p.old_vectors += old_n[c];
-        p.new_vectors += kept[c];
-        if (p.old_blocks * 32u > 0xffffffffull || p.new_blocks * 32u > 0xffffffffull) {
-            if (detail) *detail = "index too large for 32-bit vector slots";
-            return false;
-        }
+    size_t ok = 0; // lists before the first one that would keep too many vectors
+    while (ok < n_lists && kept[ok] <= old_n[ok]) ++ok;
+    // (the slots of the lists before it are checked first: the first failure in list order is the one reported)
+    ListLayout before, after;
+    if (!list_layout(old_n, ok, &before, detail) || !list_layout(kept, ok, &after, detail)) return false;
+    if (ok < n_lists) {
+        if (detail) *detail = "list " + std::to_string(ok) + " would keep more vectors than it holds";
+        return false;
     }
+    RemovePlan p;
+    p.new_n.assign(kept, kept + n_lists);
+    p.old_gb0 = std::move(before.gb0); p.new_gb0 = std::move(after.gb0);
+    p.old_blocks = before.blocks; p.new_blocks = after.blocks; p.old_vectors = before.vectors; p.new_vectors = after.vectors;
     *out = std::move(p);
     return true;
 }
