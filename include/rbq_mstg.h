@@ -10,7 +10,8 @@
  * src/mstg/clustering.rs), is rbq_mstg_cluster_device.  Step 4 (HNSW over the centroids) is not built: it is not needed for
  * searching through this library.  A header of its own, not included by rbq.h (DESIGN.md sections 15, 16, 17).  Saving and
  * loading the result in the crate's `.mstg` format: rbq_mstg_persist.h (section 18).  Appending rows to the result and removing
- * ids from it without a rebuild: rbq_mstg_mutate.h (section 24).
+ * ids from it without a rebuild: rbq_mstg_mutate.h (section 24).  Range search over the lists the search selects:
+ * ext/rbq_mstg_range.h (section 37), a header of its own that includes this one.
  */
 #ifndef RBQ_MSTG_H
 #define RBQ_MSTG_H

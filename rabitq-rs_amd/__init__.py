@@ -18,6 +18,8 @@ Mirrors the reference's public query API for this path:
                                (the refinement of src/ivf.rs:2086-2099), every id once (mstg.py)
   mstg_search(..., refine_pool=n, exact=True), MstgIndex.set_rerank_vectors: opt-in, no crate counterpart: the pool scored
                                exactly against attached raw vectors (l2_distance_sqr / dot of src/math.rs), every id once (mstg.py)
+  mstg_range_search / mstg_range_rows, MstgIndex.range_query: no crate counterpart: every vector of the scanned lists
+                               whose estimate is below a radius, in scan order, every id once (mstg.py)
   hierarchical_cluster / hierarchical_cluster_cpu / MstgIndex: HierarchicalClustering::cluster, PyMstgIndex
                                src/mstg/clustering.rs, src/python_bindings.rs (mstg.py)
   save_mstg / load_mstg, MstgIndex.save / load / get_memory_usage: MstgIndex::save_main_index / load_main_index
@@ -84,11 +86,12 @@ from . import builder  # noqa: E402,F401
 from .bruteforce import BruteForceRabitqIndex, BruteForceSearchParams, BruteForceSearchResult  # noqa: E402
 from .kmeans import KMeansConfig, KMeansResult, run_kmeans_with_config  # noqa: E402
 from .mstg import (MstgIndex, MstgSearchParams, append_postings, build_postings_on_device, closure_assign,  # noqa: E402
-                   closure_assign_cpu, hierarchical_cluster, hierarchical_cluster_cpu, load_mstg, mstg_search, remove_postings,
-                   save_mstg, select_lists_cpu)
+                   closure_assign_cpu, hierarchical_cluster, hierarchical_cluster_cpu, load_mstg, mstg_range_search,
+                   mstg_range_rows, mstg_search, remove_postings, save_mstg, select_lists_cpu)
 
 __all__ = ["Metric", "RotatorType", "RabitqError", "SearchParams", "SearchResult", "IvfRabitqIndex",
            "StreamBuilder", "builder", "BruteForceRabitqIndex", "BruteForceSearchParams", "BruteForceSearchResult",
            "KMeansConfig", "KMeansResult", "run_kmeans_with_config", "closure_assign", "closure_assign_cpu",
            "build_postings_on_device", "MstgSearchParams", "mstg_search", "select_lists_cpu", "hierarchical_cluster",
-           "hierarchical_cluster_cpu", "MstgIndex", "save_mstg", "load_mstg", "append_postings", "remove_postings"]
+           "hierarchical_cluster_cpu", "MstgIndex", "save_mstg", "load_mstg", "append_postings", "remove_postings",
+           "mstg_range_search", "mstg_range_rows"]

@@ -57,6 +57,7 @@ MSTG_CONFIG_FIELDS = ("max_posting_size", "branching_factor", "balance_weight", 
                       "pruning_epsilon")
 MSTG_PRECISIONS = ("fp32", "bf16", "fp16", "int8")  # ScalarPrecision's variant order (src/mstg/config.rs)
 MSTG_REFINE_POOL_MAX = 4096  # RBQ_MSTG_REFINE_POOL_MAX: the largest max(refine_pool, top_k) of the refined MSTG search
+MSTG_RANGE_DISTINCT_MAX = 4096  # RBQ_MSTG_RANGE_DISTINCT_MAX: the most matches of one query the distinct MSTG range search reduces
 
 
 class MstgConfig(C.Structure):
@@ -236,6 +237,16 @@ LIBRBQ_BY_HEADER = {
     },
 }
 LIBRBQ = {name: proto for group in LIBRBQ_BY_HEADER.values() for name, proto in group.items()}
+
+# Entries of librbq.so declared in headers under include/ext/ (keys: paths below include/).  A table of its own, bound on a
+# function table of its own (index.lib_ext()): LIBRBQ stays the declarations of include/*.h, name for name.
+LIBRBQ_EXT_BY_HEADER = {
+    "ext/rbq_mstg_range.h": {
+        "rbq_mstg_range_batch": (_INT, [_VP, _VP, _U64, _U32, _U32, _U32, _F32, _F32, _U32, _VP, _VP, _VP, _VP, _VP]),
+        "rbq_mstg_range_batch_device": (_INT, [_VP, _VP, _U64, _U32, _U32, _U32, _F32, _F32, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    },
+}
+LIBRBQ_EXT = {name: proto for group in LIBRBQ_EXT_BY_HEADER.values() for name, proto in group.items()}
 
 # csrc/host/rbq_build.h
 LIBRBQ_BUILD = {

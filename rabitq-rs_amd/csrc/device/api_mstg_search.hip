@@ -1,9 +1,10 @@
 // api_mstg_search.hip — MSTG search: the posting-list scan over lists the caller chose (rbq_posting_scan_batch) and the search in
-// one call, plain or refined, on host or device buffers (rbq_mstg_search_*batch*, include/rbq_mstg.h).  The scan itself is api_search.hip's scan_stage.
+// one call, plain or refined, and the range search, on host or device buffers (rbq_mstg_search_*batch*, rbq_mstg_range_batch* of include/ext/rbq_mstg_range.h; include/rbq_mstg.h).  The scan itself is api_search.hip's scan_stage.
 #include <optional>
 
 #include "api.hpp"
 #include "rbq_mstg.h"
+#include "ext/rbq_mstg_range.h"
 
 using namespace rbq_api;
 
@@ -25,30 +26,70 @@ int mstg_prep(Replica* ix, Workspace* w, const float* d_q, uint64_t n, bool keep
     return RBQ_OK;
 }
 
-// Stages 2 and 3 over the lists d_lists [n][list_stride] / d_lcnt [n] (device) of n prepared queries: the probes and work lists, then
-// the scan.  d_slot_map (or null): the scan names its candidates through this map instead of the ids (the refined search).
-int scan_posting_lists(Replica* ix, Workspace* w, uint64_t n, const uint32_t* d_lists, const uint32_t* d_lcnt, uint32_t list_stride,
-                       uint64_t wl_stride, uint32_t top_k, uint64_t* d_ids, float* d_scores, uint32_t* d_counts, const uint64_t* d_slot_map,
-                       hipStream_t stream) {
+// Stage 2 over the lists d_lists [n][list_stride] / d_lcnt [n] (device) of n prepared queries: the probes and the block work lists.
+int probes_given(Replica* ix, Workspace* w, uint64_t n, const uint32_t* d_lists, const uint32_t* d_lcnt, uint32_t list_stride, uint64_t wl_stride,
+                 hipStream_t stream) {
     int rc;
     if ((rc = w->probe.ensure(n * (size_t)list_stride * sizeof(ProbeInfo)))) return rc;
     if ((rc = w->wl.ensure(n * wl_stride * sizeof(StreamItem)))) return rc;
     if ((rc = w->nstream.ensure(n * 4))) return rc;
-    {
-        ProfScope ps(ix, 2, stream);
-        ProbesGivenParams p;
-        p.list_ids = d_lists; p.list_counts = d_lcnt; p.max_lists = list_stride;
-        p.nq = (uint32_t)n; p.nlist = (uint32_t)ix->n_lists; p.metric = (int)ix->metric; p.rot = (const float*)w->rot.p;
-        p.cent = (const float*)ix->centroids.p; p.D = ix->D; p.list_gb0 = (const uint32_t*)ix->list_gb0.p;
-        p.list_n = (const uint32_t*)ix->list_n.p; p.probe = (ProbeInfo*)w->probe.p; p.wl = (StreamItem*)w->wl.p;
-        p.wl_stride = wl_stride; p.nstream = (uint32_t*)w->nstream.p; p.consts = (const QueryConsts*)w->consts.p;
-        p.bsum = (const BlockSummary*)ix->bsum.p;
-        p.numeric_variant = ix->opt.numeric_variant;
-        HIP_TRY(launch_probes_given(p, stream));
-    }
+    ProfScope ps(ix, 2, stream);
+    ProbesGivenParams p;
+    p.list_ids = d_lists; p.list_counts = d_lcnt; p.max_lists = list_stride;
+    p.nq = (uint32_t)n; p.nlist = (uint32_t)ix->n_lists; p.metric = (int)ix->metric; p.rot = (const float*)w->rot.p;
+    p.cent = (const float*)ix->centroids.p; p.D = ix->D; p.list_gb0 = (const uint32_t*)ix->list_gb0.p;
+    p.list_n = (const uint32_t*)ix->list_n.p; p.probe = (ProbeInfo*)w->probe.p; p.wl = (StreamItem*)w->wl.p;
+    p.wl_stride = wl_stride; p.nstream = (uint32_t*)w->nstream.p; p.consts = (const QueryConsts*)w->consts.p;
+    p.bsum = (const BlockSummary*)ix->bsum.p;
+    p.numeric_variant = ix->opt.numeric_variant;
+    HIP_TRY(launch_probes_given(p, stream));
+    return RBQ_OK;
+}
+
+// Stages 2 and 3 over those lists: the probes and work lists, then the scan.  d_slot_map (or null): the scan names its candidates
+// through this map instead of the ids (the refined search).
+int scan_posting_lists(Replica* ix, Workspace* w, uint64_t n, const uint32_t* d_lists, const uint32_t* d_lcnt, uint32_t list_stride,
+                       uint64_t wl_stride, uint32_t top_k, uint64_t* d_ids, float* d_scores, uint32_t* d_counts, const uint64_t* d_slot_map,
+                       hipStream_t stream) {
+    int rc;
+    if ((rc = probes_given(ix, w, n, d_lists, d_lcnt, list_stride, wl_stride, stream))) return rc;
     const rbq_host::SearchPlan plan = search_plan(ix, w, n, top_k, list_stride, false, false, /*range=*/false, /*mstg=*/true);
     return scan_stage(ix, w, plan, n, list_stride, top_k, wl_stride, nullptr, 0, d_ids, d_scores, d_counts, nullptr, /*mstg=*/true, nullptr,
                       stream, d_slot_map);
+}
+
+// Stages 2 and 3 of the range search (rbq_mstg_range_batch*, k_mstg_range.hip) over those lists: every vector whose estimate is below
+// `radius`, in scan order, into rows of `cap`.  distinct: the scan writes rows of RBQ_MSTG_RANGE_DISTINCT_MAX into the workspace and
+// k_mstg_range_distinct reduces each to one entry per id in the caller's row.
+int range_posting_lists(Replica* ix, Workspace* w, uint64_t n, const uint32_t* d_lists, const uint32_t* d_lcnt, uint32_t list_stride,
+                        uint64_t wl_stride, uint32_t cap, float radius, bool distinct, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
+                        hipStream_t stream) {
+    int rc;
+    if ((rc = probes_given(ix, w, n, d_lists, d_lcnt, list_stride, wl_stride, stream))) return rc;
+    const rbq_host::SearchPlan plan = search_plan(ix, w, n, cap, list_stride, false, false, /*range=*/true, /*mstg=*/true);
+    MstgRangeParams P{};
+    P.out_ids = d_ids; P.out_scores = d_scores; P.out_counts = d_counts; P.cap = cap;
+    if (distinct) {
+        if ((rc = w->mr_pool.ensure(n * ((size_t)kMstgRangeDistinctMax * 12 + 4)))) return rc;
+        P.out_ids = (uint64_t*)w->mr_pool.p;
+        P.out_scores = (float*)(P.out_ids + n * (size_t)kMstgRangeDistinctMax);
+        P.out_counts = (uint32_t*)(P.out_scores + n * (size_t)kMstgRangeDistinctMax);
+        P.cap = kMstgRangeDistinctMax;
+        P.no_fill = 1u; // (k_mstg_range_distinct reads the first `total` entries of a row and nothing of a row beyond the limit)
+    }
+    P.blocks = (const uint8_t*)ix->blocks.p; P.ids = (const uint64_t*)ix->ids.p;
+    P.lut = (const uint8_t*)w->lut.p; P.consts = (const QueryConsts*)w->consts.p;
+    P.probe = (const ProbeInfo*)w->probe.p; P.wl = (const StreamItem*)w->wl.p; P.nstream = (const uint32_t*)w->nstream.p;
+    P.wl_stride = wl_stride; P.nq = (uint32_t)n; P.D = ix->D; P.Dc = ix->Dc; P.nprobe = plan.nprobe; P.metric = ix->metric;
+    P.no_block_bound = ix->opt.no_block_bound ? 1u : 0u; P.numeric_variant = ix->opt.numeric_variant; P.R = radius;
+    ProfScope ps(ix, 3, stream); // (the profile stage "scan" times both kernels)
+    HIP_TRY(launch_mstg_range(P, ix->device, stream));
+    if (!distinct) return RBQ_OK;
+    MstgRangeDistinctParams X{};
+    X.raw_ids = P.out_ids; X.raw_scores = P.out_scores; X.raw_counts = P.out_counts;
+    X.out_ids = d_ids; X.out_scores = d_scores; X.out_counts = d_counts; X.nq = (uint32_t)n; X.cap = cap;
+    HIP_TRY(launch_mstg_range_distinct(X, ix->device, stream));
+    return RBQ_OK;
 }
 
 // A host call in chunks on the pool workspace w: each chunk's queries are uploaded, body(q0, n, d_q, d_ids, d_scores, d_counts, stream)
@@ -177,6 +218,9 @@ struct MstgArgs {
     uint64_t* out_ids; float* out_scores; uint32_t* out_counts; uint32_t* out_list_ids; uint32_t* out_list_counts;
     bool refined = false;     // rbq_mstg_search_refined_batch*: the pool is max(refine_pool, top_k)
     uint32_t refine_pool = 0;
+    bool range = false;       // rbq_mstg_range_batch*: top_k is the capacity of a row
+    float radius = 0.0f;
+    bool distinct = false;
 };
 
 // One search call once mstg_begin has checked and prepared it: what every chunk of it needs.
@@ -188,6 +232,8 @@ struct MstgCall {
     float pruning_epsilon = 0;
     uint32_t pool = 0;        // candidates per query that the refined search scans for and refines (0: the plain search)
     bool exact = false;       // option mstg_rerank on a refined call: the pool is scored against the raw rows (k_mstg_rerank.hip)
+    bool range = false, distinct = false; // rbq_mstg_range_batch*: every estimate below `radius`; one entry per id
+    float radius = 0.0f;
     unsigned long long* d_fallbacks = nullptr;
     MstgShape sh{};
 };
@@ -199,7 +245,7 @@ int ms_check(const rbq_index* h, const MstgArgs& c, uint32_t* pool) {
     rbq_host::MstgSearchArgs a;
     a.have_index = h && !h->reps.empty();
     if (a.have_index) { const Replica* ix = h->reps[0]; a.n_vectors = ix->n_vectors; a.dim = ix->dim; a.rotator = ix->rotator; }
-    a.query_dim = c.query_dim; a.nq = c.nq; a.top_k = c.top_k; a.refined = c.refined; a.refine_pool = c.refine_pool;
+    a.query_dim = c.query_dim; a.nq = c.nq; a.top_k = c.top_k; a.refined = c.refined; a.refine_pool = c.refine_pool; a.range = c.range;
     a.queries = c.queries != nullptr; a.out_ids = c.out_ids != nullptr; a.out_scores = c.out_scores != nullptr; a.out_counts = c.out_counts != nullptr;
     std::string detail;
     bool done = false;
@@ -243,13 +289,16 @@ int mstg_begin(rbq_index* h, const MstgArgs& a, bool host, hipStream_t s, MstgCa
     if ((rc = ms_fallback_counter(ix->device, &c->d_fallbacks))) return rc;
     if (a.refined && (rc = mr_prepare(ix))) return rc; // (the first refined call on a handle waits for its maps once)
     c->top_k = a.top_k; c->ef_search = a.ef_search; c->pruning_epsilon = a.pruning_epsilon;
-    c->sh = ms_shape(ix, a.nq, a.top_k, a.ef_search, host, c->pool);
+    c->range = a.range; c->distinct = a.distinct; c->radius = a.radius;
+    // (the rows the distinct range search reduces are part of the workspace like the refined search's pool)
+    c->sh = ms_shape(ix, a.nq, a.top_k, a.ef_search, host, a.range && a.distinct ? kMstgRangeDistinctMax : c->pool);
     if (c->sh.wl_stride > 0xffffffffull) return fail(RBQ_INVALID_CONFIG, "posting lists too long for one query");
     c->done = false;
     return RBQ_OK;
 }
 
 // n queries at d_q (device; rows of the handle's query_dtype, read by mstg_prep alone), everything enqueued on `stream`; d_lists [n][sh.ef] and d_lcnt [n] receive the selection.
+// Range (c.range, k_mstg_range.hip): the scan is the range scan at the constant c.radius, top_k the capacity of a row.
 // Refined (c.pool, k_mstg_refine.hip): the scan runs with top_k := pool over the slot map into the workspace's pool, which is
 // then refined into the caller's top_k — with the ex codes, or (c.exact, k_mstg_rerank.hip) exactly against the raw rows, for
 // which d_q is read once more, as the caller's rows in input space.
@@ -287,6 +336,8 @@ int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uin
         p.fallbacks = c.d_fallbacks; p.out_lists = d_lists; p.out_counts = d_lcnt;
         HIP_TRY(launch_mstg_select(p, ix->device, stream));
     }
+    if (c.range)
+        return range_posting_lists(ix, w, n, d_lists, d_lcnt, sh.ef, sh.wl_stride, c.top_k, c.radius, c.distinct, d_ids, d_scores, d_counts, stream);
     rc = scan_posting_lists(ix, w, n, d_lists, d_lcnt, sh.ef, sh.wl_stride, c.pool ? c.pool : c.top_k, s_ids, s_scores, s_counts,
                             c.pool ? (const uint64_t*)ix->mr_slot_map.p : nullptr, stream);
     if (rc || !c.pool) return rc;
@@ -441,6 +492,21 @@ int rbq_mstg_search_refined_batch_device(const rbq_index* idx, const float* d_qu
                                          uint32_t* d_out_list_counts, void* hip_stream) {
     return ms_search_device(idx, {d_queries, nq, query_dim, top_k, ef_search, pruning_epsilon, d_out_ids, d_out_scores, d_out_counts, d_out_list_ids,
                                   d_out_list_counts, true, refine_pool}, hip_stream);
+}
+
+// ---- MSTG range search (include/ext/rbq_mstg_range.h) ----------------------------------------------------------------
+int rbq_mstg_range_batch(const rbq_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t capacity, uint32_t ef_search,
+                         float pruning_epsilon, float radius, uint32_t distinct, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                         uint32_t* out_list_ids, uint32_t* out_list_counts) {
+    return ms_search_host(idx, {queries, nq, query_dim, capacity, ef_search, pruning_epsilon, out_ids, out_scores, out_counts, out_list_ids, out_list_counts,
+                                false, 0, true, radius, distinct != 0});
+}
+int rbq_mstg_range_batch_device(const rbq_index* idx, const float* d_queries, uint64_t nq, uint32_t query_dim, uint32_t capacity,
+                                uint32_t ef_search, float pruning_epsilon, float radius, uint32_t distinct, uint64_t* d_out_ids,
+                                float* d_out_scores, uint32_t* d_out_counts, uint32_t* d_out_list_ids, uint32_t* d_out_list_counts,
+                                void* hip_stream) {
+    return ms_search_device(idx, {d_queries, nq, query_dim, capacity, ef_search, pruning_epsilon, d_out_ids, d_out_scores, d_out_counts, d_out_list_ids,
+                                  d_out_list_counts, false, 0, true, radius, distinct != 0}, hip_stream);
 }
 
 uint64_t rbq_mstg_debug_search_fallbacks(void) {

@@ -19,6 +19,7 @@
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, canon_score.hpp)
 //   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan_codes.hpp, mstg_pool.hpp)
 //   k_mstg_rerank.hip  exact rerank of the MSTG pool: one entry per id, exact scores from the raw rows (mstg_pool.hpp, rerank_score.hpp)
+//   k_mstg_range.hip  MSTG range search: the estimate against a constant radius in scan order, one entry per id (scan_codes.hpp, mstg_pool.hpp)
 //   k_rerank_pool.hip  pooled rerank: exact scores of a candidate pool from whole lines of the raw rows, order in LDS (rerank_score.hpp)
 //   k_append.hip rbq_index_append: carry of an index into a larger geometry, id bound, nearest list of rotated rows (km_common.hpp)
 //   k_remove.hip rbq_index_remove_ids: keep masks against a sorted id set, slot map, gather of an index into a smaller geometry
@@ -476,6 +477,39 @@ struct MstgRerankParams {
 };
 size_t mstg_rerank_lds_bytes(uint32_t dim, uint32_t pool_np2);
 hipError_t launch_mstg_rerank(const MstgRerankParams& P, int device, hipStream_t s);
+
+// ---- MSTG range search (k_mstg_range.hip): the selected lists' vectors whose binary estimate is below R, in
+// scan order (k_mstg_range), then one entry per id (k_mstg_range_distinct) where the caller asks for distinct ids
+constexpr uint32_t kMstgRangeDistinctMax = 4096; // RBQ_MSTG_RANGE_DISTINCT_MAX: the matches of one query are sorted in LDS
+struct MstgRangeParams {
+    const uint8_t* blocks;      // the index, as ScanParams names it (the ex codes and their factors are never read)
+    const uint64_t* ids;
+    const uint8_t* lut;         // [nq][4Dc], consts [nq]: as k_prep left them with ex_bits 0
+    const QueryConsts* consts;
+    const ProbeInfo* probe;     // [nq][nprobe], wl [nq][wl_stride], nstream [nq]: as k_probes_given wrote them
+    const StreamItem* wl;
+    const uint32_t* nstream;
+    uint64_t wl_stride;
+    uint64_t* out_ids;          // [nq][cap], out_scores [nq][cap]: the first min(total, cap) matches, then UINT64_MAX / NaN
+    float* out_scores;
+    uint32_t* out_counts;       // [nq] the total, which may exceed cap
+    uint32_t nq, D, Dc, nprobe, cap, metric;
+    uint32_t no_block_bound;    // diagnostic option of the handle: stream every block
+    uint32_t no_fill;           // the slots behind the matches are left as they are (the rows k_mstg_range_distinct reads the head of)
+    uint32_t numeric_variant;   // host-side dispatch only
+    float R;                    // a candidate matches iff estimate < R (both metrics: MSTG reports distances)
+};
+hipError_t launch_mstg_range(const MstgRangeParams& P, int device, hipStream_t s);
+struct MstgRangeDistinctParams {
+    const uint64_t* raw_ids;    // [nq][kMstgRangeDistinctMax] the scan's rows (capacity kMstgRangeDistinctMax), raw_scores alike,
+    const float* raw_scores;    // raw_counts [nq] their totals
+    const uint32_t* raw_counts;
+    uint64_t* out_ids;          // [nq][cap], out_scores [nq][cap], out_counts [nq]: distinct ids, or UINT32_MAX where the total
+    float* out_scores;          // exceeds kMstgRangeDistinctMax (the row is then empty)
+    uint32_t* out_counts;
+    uint32_t nq, cap;
+};
+hipError_t launch_mstg_range_distinct(const MstgRangeDistinctParams& P, int device, hipStream_t s);
 
 // ---- RBQ1 writer (k_save.hip): words [w0, w0 + nw) of the cluster section of the stream, into out[0, nw)
 struct SaveParams {

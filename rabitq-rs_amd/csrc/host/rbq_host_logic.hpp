@@ -391,7 +391,7 @@ inline HostCallPlan host_call_plan(uint64_t nq, bool in_pinned, size_t query_byt
     return p;
 }
 
-// The argument errors of rbq_mstg_search_batch* and rbq_mstg_search_refined_batch* (include/rbq_mstg.h), in their order; no
+// The argument errors of rbq_mstg_search_batch*, rbq_mstg_search_refined_batch* (include/rbq_mstg.h) and rbq_mstg_range_batch* (include/ext/rbq_mstg_range.h), in their order; no
 // device is needed to find any of them.  RBQ_OK with *done set: the call is answered as it stands (nq == 0).
 struct MstgSearchArgs {
     bool have_index = false;       // a non-null handle with a replica
@@ -403,6 +403,7 @@ struct MstgSearchArgs {
     uint32_t top_k = 0;
     bool refined = false;          // rbq_mstg_search_refined_batch*: the pool is max(refine_pool, top_k)
     uint32_t refine_pool = 0;
+    bool range = false;            // rbq_mstg_range_batch*: top_k is the capacity of a row, bounded like top_k
 };
 constexpr uint32_t kMstgTopKHardMax = 1u << 20;  // (kTopKHardMax of the device side)
 constexpr uint32_t kMstgRefinePoolMax = 4096;    // RBQ_MSTG_REFINE_POOL_MAX
@@ -419,7 +420,7 @@ inline int mstg_search_check(const MstgSearchArgs& a, std::string* detail, bool*
     // (top_k == 0: out_ids and out_scores hold no element, so they have no address to ask for)
     if (!a.queries || !a.out_counts || (a.top_k && (!a.out_ids || !a.out_scores))) return fail(RBQ_INVALID_CONFIG, "null buffer");
     if (a.top_k > kMstgTopKHardMax || (uint64_t)std::min<uint64_t>(a.nq, 16384) * ((uint64_t)a.top_k + 1) * 8 > (8ull << 30))
-        return fail(RBQ_INVALID_CONFIG, "top_k too large for one call (top_k <= 2^20)");
+        return fail(RBQ_INVALID_CONFIG, a.range ? "capacity too large for one call (capacity <= 2^20)" : "top_k too large for one call (top_k <= 2^20)");
     if (a.refined) {
         const uint32_t p = std::max(a.refine_pool, a.top_k);
         if (p > kMstgRefinePoolMax)

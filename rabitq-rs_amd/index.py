@@ -10,6 +10,7 @@ from ._abi import READ_FN, WRITE_FN  # noqa: F401  (their home is the prototype 
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+_LIB_EXT = None
 LIB_PATH = os.environ.get("RBQ_LIB_PATH") or os.path.join(_HERE, "csrc", "librbq.so")  # override: kernel A/B builds
 RERANK_POOL_MAX = 4096  # largest pool of IvfRabitqIndex.set_rerank_pool (kRerankPoolMax: one workgroup orders a pool in LDS)
 
@@ -40,6 +41,16 @@ def lib():
         _hip_runtime_of_torch_first()
         _LIB = _abi.bind(C.CDLL(LIB_PATH), _abi.LIBRBQ)
     return _LIB
+
+
+def lib_ext():
+    """The entries of librbq.so that include/ext/ declares (_abi.LIBRBQ_EXT), on a function table of their own: the same loaded
+    library as lib(), which is loaded first."""
+    global _LIB_EXT
+    if _LIB_EXT is None:
+        lib()
+        _LIB_EXT = _abi.bind(C.CDLL(LIB_PATH), _abi.LIBRBQ_EXT)
+    return _LIB_EXT
 
 
 def _detail():

@@ -302,6 +302,88 @@ def mstg_search(index, queries, top_k, ef_search=150, pruning_epsilon=0.6, retur
     return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
 
 
+RANGE_DISTINCT_MAX = _abi.MSTG_RANGE_DISTINCT_MAX
+_U32_MAX = 0xFFFFFFFF
+
+
+def mstg_range_rows(index, queries, radius, capacity, ef_search=150, pruning_epsilon=0.6, distinct=True, return_lists=False, dtype=None):
+    """The rows of a range search on an MSTG handle as the C ABI returns them: (ids [nq][capacity] u64, distances [nq][capacity]
+    f32, counts [nq] u32), plus (lists, list_counts) with `return_lists`.  A row holds the first min(count, capacity) matches in
+    scan order, then UINT64_MAX / NaN; counts are the totals (they may exceed `capacity`), or UINT32_MAX for a query whose matches
+    exceed RANGE_DISTINCT_MAX with `distinct`.  NumPy queries take rbq_mstg_range_batch and return arrays; a CUDA tensor takes
+    rbq_mstg_range_batch_device on the current stream, without synchronising, and returns tensors (bit patterns in int64 / int32,
+    as mstg_search): the caller reads the counts once the stream has got there and repeats with a larger capacity where one
+    exceeds it.  `queries` and `dtype` as mstg_search."""
+    from . import _marshal
+    from .index import _check, lib_ext
+    capacity, ef_search = int(capacity), int(ef_search)
+    ef = min(max(ef_search, 0), index.cluster_count())
+    q, code = _marshal.query_arg(queries, dtype)
+    args = (capacity, ef_search, float(pruning_epsilon), float(radius), 1 if distinct else 0)
+    nq, qd = q.shape
+    torch = torch_of(q)
+    if torch is not None and q.is_cuda:
+        with torch.cuda.device(q.device):
+            ids = torch.empty((nq, capacity), dtype=torch.int64, device=q.device)
+            sc = torch.empty((nq, capacity), dtype=torch.float32, device=q.device)
+            cnt = torch.empty(nq, dtype=torch.int32, device=q.device)
+            li = torch.empty((nq, ef), dtype=torch.int32, device=q.device) if return_lists else None
+            lc = torch.empty(nq, dtype=torch.int32, device=q.device) if return_lists else None
+            stream = torch.cuda.current_stream().cuda_stream
+            with index._query_dtype_for_call(code):
+                rc = lib_ext().rbq_mstg_range_batch_device(index._h, q.data_ptr(), nq, qd, *args, ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(),
+                                                       li.data_ptr() if return_lists else None, lc.data_ptr() if return_lists else None,
+                                                       C.c_void_p(stream))
+            _check(rc)
+        return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
+    ids, sc, cnt = np.empty((nq, capacity), np.uint64), np.empty((nq, capacity), np.float32), np.zeros(nq, np.uint32)
+    li = np.empty((nq, ef), np.uint32) if return_lists else None
+    lc = np.empty(nq, np.uint32) if return_lists else None
+    with index._query_dtype_for_call(code):
+        rc = lib_ext().rbq_mstg_range_batch(index._h, _marshal.data_ptr(q), nq, qd, *args, ids.ctypes.data, sc.ctypes.data, cnt.ctypes.data,
+                                        li.ctypes.data if return_lists else None, lc.ctypes.data if return_lists else None)
+    _check(rc)
+    return (ids, sc, cnt, li, lc) if return_lists else (ids, sc, cnt)
+
+
+def mstg_range_search(index, queries, radius, ef_search=150, pruning_epsilon=0.6, max_results=None, distinct=True, return_lists=False,
+                      dtype=None):
+    """Range search on an MSTG handle: (lims [nq + 1] i64, ids u64, distances f32) in the CSR shape of
+    IvfRabitqIndex.range_search — query q's matches are ids[lims[q]:lims[q + 1]], in scan order (the selected lists in selection
+    order, each in its vector order).  A match is a vector of the lists `mstg_search` would scan whose estimate (the distance
+    `mstg_search` reports for it, for both metrics) is < radius.  `distinct` (the default): every id once, with the smallest of
+    its estimates; False: one entry per (list, position), so a vector that closure assignment put into several selected lists
+    comes back once per list.
+    max_results=None: complete rows (a first call with rows of 1024; where a total exceeds that, one more with rows of the largest
+    total: the totals are exact).  max_results=m: at most the first m matches of every query, and the totals [nq] u32 as a fourth
+    value.  With `return_lists`, (lists, list_counts) of the selected posting lists follow.  A query with more than
+    RANGE_DISTINCT_MAX matches cannot be reduced to distinct ids on the device: RabitqError names RBQ_MSTG_RANGE_DISTINCT_MAX
+    (repeat with distinct=False, or a smaller radius).  `queries` are host rows (mstg_range_rows takes CUDA tensors); `dtype` as
+    mstg_search."""
+    from . import RabitqError, _marshal
+    from .index import IvfRabitqIndex
+    q, dtype = _marshal.query_arg(queries, dtype)
+    if _marshal.on_device(q):
+        raise ValueError("mstg_range_search takes host queries (mstg_range_rows takes CUDA tensors)")
+
+    def call(cap):
+        got = mstg_range_rows(index, q, radius, cap, ef_search, pruning_epsilon, distinct, return_lists, dtype)
+        over = np.nonzero(got[2] == _U32_MAX)[0]
+        if distinct and over.size:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "query %d has more than RBQ_MSTG_RANGE_DISTINCT_MAX (%d) matches: repeat with "
+                              "distinct=False or a smaller radius" % (int(over[0]), RANGE_DISTINCT_MAX))
+        return got
+
+    cap = 1024 if max_results is None else int(max_results)
+    got = call(cap)
+    if max_results is None and got[2].size and int(got[2].max()) > cap:
+        got = call(int(got[2].max()))
+    out = IvfRabitqIndex._range_csr(got[0], got[1], got[2], False)
+    if max_results is not None:
+        out += (got[2],)
+    return out + tuple(got[3:])
+
+
 def _config_struct(config):
     cfg = config if isinstance(config, _abi.MstgConfig) else _abi.MstgConfig.from_dict(config)
     return cfg
@@ -512,6 +594,14 @@ class MstgIndex:
         if q.ndim != 1 or q.shape[0] != self.dimension:
             raise ValueError(f"Query dimension {q.shape[-1] if q.ndim else 0} does not match expected {self.dimension}")
         return self.batch_query(q[None, :], k, dtype)[0]
+
+    def range_query(self, queries, radius, distinct=True, dtype=None):
+        """Every vector closer than `radius` by the estimate, among the lists a query with the arguments of set_query_arguments
+        scans (mstg_range_search with this object's ef_search and pruning_epsilon; no crate counterpart): a list with one
+        [count][2] f32 array of (id, distance) per query, in scan order, every id once unless distinct=False."""
+        lims, ids, dist = mstg_range_search(self._built(), queries, radius, self.default_ef_search, self.pruning_epsilon,
+                                            distinct=distinct, dtype=dtype)
+        return [np.stack([ids[a:b].astype(np.float32), dist[a:b]], axis=1) for a, b in zip(lims[:-1], lims[1:])]
 
     def config(self):
         """The crate's MstgConfig of this index (what `save` writes)."""
