@@ -37,7 +37,22 @@ extern "C" {
  * Errors: those of rbq_mstg_search_batch in its order, with `capacity` where it has top_k (capacity <= 2^20, as the IVF range
  * search); all before the first HIP call.  Host queries are cut into chunks inside the 1 GiB workspace (the rows of step 5 are
  * part of it); the result does not depend on the chunking.  "query_dtype" is honoured as by the other MSTG entries; the IVF
- * options "range_search" / "range_exact" are not read. */
+ * options "range_search" / "range_exact" are not read.
+ *
+ * Exact range search: with rbq_debug_set_option(idx, "mstg_range_exact", 1) (every replica, default 0) and the
+ * 32 bits of an f32 x in "mstg_range_exact_bits" (default +inf), both entries read `radius` as the candidate radius r and answer:
+ *  a. the candidates of a query are the rows of this call with the option 0 at radius r, distinct != 0 and unlimited capacity —
+ *     lists, estimates, the distinct rule and the scan order of steps 1 to 5; the list outputs are that call's, bit for bit.  A
+ *     query with more than RBQ_MSTG_RANGE_DISTINCT_MAX matches at r, replicas counted, gets out_counts[q] = UINT32_MAX and no entry;
+ *  b. every candidate id is scored as the exact rerank scores it (rbq_mstg.h): canonical l2_distance_sqr, or minus the canonical
+ *     dot product, of the caller's unrotated query row and raw row `id` of rbq_index_set_rerank_vectors, 16-bit elements widened;
+ *  c. a candidate matches iff that distance is finite and < x, for both metrics: NaN never matches, id >= n_raw never matches, a
+ *     NaN x matches nothing;
+ *  d. the matches keep the candidates' scan order; out_scores holds the exact distance's bits; out_counts[q] is their total and may
+ *     exceed `capacity`, the first min(total, capacity) are written, the other slots are UINT64_MAX / NaN.
+ * RBQ_INVALID_CONFIG (detail set), after the errors above and before the first HIP call: distinct == 0 (an exact answer is per
+ * id), no raw vectors attached, "rerank" 0 — nothing is silently approximated.  capacity == 0, ef_search == 0 and nq == 0 are as in
+ * step 6.  With the option 0 both entries are bit for bit what they are without it. */
 #define RBQ_MSTG_RANGE_DISTINCT_MAX 4096
 int rbq_mstg_range_batch(const rbq_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t capacity,
                          uint32_t ef_search, float pruning_epsilon, float radius, uint32_t distinct, uint64_t* out_ids,

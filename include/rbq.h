@@ -431,6 +431,13 @@ int rbq_debug_copy_workspace(rbq_index* idx, void* hip_stream, const char* name,
  *                        attached raw rows.  Needs raw vectors attached and "rerank" 1, else the refined call is
  *                        RBQ_INVALID_CONFIG; may be set with or without vectors attached.  rbq_debug_copy_index(idx, "mstg_rerank",
  *                        &v, 4) reads it back as one int32
+ *   "mstg_range_exact" 0/1  exact MSTG range search (default 0; ext/rbq_mstg_range.h): rbq_mstg_range_batch*, and only they, read
+ *                        their radius as the candidate radius r, score the distinct ids of the estimate's matches at r exactly
+ *                        against the attached raw rows and keep an id iff exact distance < x, for both metrics.  Needs distinct
+ *                        != 0, raw vectors attached and "rerank" 1, else the range call is RBQ_INVALID_CONFIG; may be set with or
+ *                        without vectors attached.  rbq_debug_copy_index(idx, "mstg_range_exact", &v, 4) reads it back as one int32
+ *   "mstg_range_exact_bits" v  the 32 bits of the f32 x, passed through the int (every pattern is accepted; default +inf);
+ *                        rbq_debug_copy_index(idx, "mstg_range_exact_bits", &v, 4) reads them back as one int32
  *   "range_radius_bits" v  the 32 bits of an f32 radius r, passed through the int (every pattern is accepted; default +inf)
  *   "range_search" 0/1   range search (default 0): rbq_search_batch / rbq_search_batch_device return every vector of the probed
  *                        lists with distance < r (L2) or score > r (inner product), see rbq_search_batch; RBQ_INVALID_CONFIG

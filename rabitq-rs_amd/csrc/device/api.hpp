@@ -371,6 +371,11 @@ struct Options {
                               // exactly against the attached vectors and the best top_k are returned (0 = off; <= kRerankPoolMax)
     bool mstg_rerank = false; // rbq_mstg_search_refined_batch* only: the pool is reduced to one entry per id and
                               // scored exactly against the attached raw vectors instead of the ex codes (needs vectors attached, rerank 1)
+    // rbq_mstg_range_batch* only: the call's radius picks the candidates, which are reduced to one entry per id,
+    // scored exactly against the attached raw vectors and kept iff exact distance < x, the f32 of mstg_range_exact_bits (needs
+    // distinct, vectors attached, rerank 1)
+    bool mstg_range_exact = false;
+    uint32_t mstg_range_exact_bits = 0x7f800000u; // +inf
     // range search: while range_search is on, rbq_search_batch / rbq_search_batch_device return every probed
     // vector whose distance is below the radius (an f32 passed by its bits; distance < r for L2, score > r for inner product), in
     // scan order, with top_k read as the capacity of the output row and out_counts as the total

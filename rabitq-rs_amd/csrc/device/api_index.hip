@@ -215,6 +215,8 @@ int Options::set(const char* name, int v) {
         query_dtype = v;
     }
     else if (is("mstg_rerank")) mstg_rerank = v != 0; // (with or without vectors attached; read by rbq_mstg_search_refined_batch* alone)
+    else if (is("mstg_range_exact")) mstg_range_exact = v != 0; // (read by rbq_mstg_range_batch* alone: DESIGN.md section 38)
+    else if (is("mstg_range_exact_bits")) mstg_range_exact_bits = (uint32_t)v; // the 32 bits of an f32: every pattern is accepted
     else if (is("range_search")) range_search = v != 0;
     else if (is("range_radius_bits")) range_radius_bits = (uint32_t)v; // the 32 bits of an f32 radius: every pattern is a radius
     else if (is("range_exact")) range_exact = v != 0; // (acts while range_search is on: DESIGN.md section 33)
@@ -832,6 +834,13 @@ int rbq_debug_copy_index(rbq_index* h, const char* name, void* dst, uint64_t byt
     if (!std::strcmp(name, "mstg_rerank")) { // (not an array: the option "mstg_rerank" as the handle holds it, one int32)
         if (bytes != 4) return fail(RBQ_INVALID_CONFIG, "mstg_rerank is one int32");
         const int32_t v = h->reps[0]->opt.mstg_rerank ? 1 : 0;
+        std::memcpy(dst, &v, 4);
+        return RBQ_OK;
+    }
+    if (!std::strcmp(name, "mstg_range_exact") || !std::strcmp(name, "mstg_range_exact_bits")) { // (the options as the handle holds them, one int32 each)
+        if (bytes != 4) return fail(RBQ_INVALID_CONFIG, std::string(name) + " is one int32");
+        const Options& o = h->reps[0]->opt;
+        const int32_t v = name[16] ? (int32_t)o.mstg_range_exact_bits : (o.mstg_range_exact ? 1 : 0);
         std::memcpy(dst, &v, 4);
         return RBQ_OK;
     }

@@ -60,10 +60,12 @@ int scan_posting_lists(Replica* ix, Workspace* w, uint64_t n, const uint32_t* d_
 
 // Stages 2 and 3 of the range search (rbq_mstg_range_batch*, k_mstg_range.hip) over those lists: every vector whose estimate is below
 // `radius`, in scan order, into rows of `cap`.  distinct: the scan writes rows of RBQ_MSTG_RANGE_DISTINCT_MAX into the workspace and
-// k_mstg_range_distinct reduces each to one entry per id in the caller's row.
+// k_mstg_range_distinct reduces each to one entry per id in the caller's row.  d_xq (the exact range search, option mstg_range_exact;
+// distinct): the caller's rows in input space, of the handle's query_dtype — k_mstg_range_exact takes k_mstg_range_distinct's place
+// and keeps the ids whose exact distance to their raw row is below x.
 int range_posting_lists(Replica* ix, Workspace* w, uint64_t n, const uint32_t* d_lists, const uint32_t* d_lcnt, uint32_t list_stride,
-                        uint64_t wl_stride, uint32_t cap, float radius, bool distinct, uint64_t* d_ids, float* d_scores, uint32_t* d_counts,
-                        hipStream_t stream) {
+                        uint64_t wl_stride, uint32_t cap, float radius, bool distinct, const float* d_xq, float x, uint64_t* d_ids,
+                        float* d_scores, uint32_t* d_counts, hipStream_t stream) {
     int rc;
     if ((rc = probes_given(ix, w, n, d_lists, d_lcnt, list_stride, wl_stride, stream))) return rc;
     const rbq_host::SearchPlan plan = search_plan(ix, w, n, cap, list_stride, false, false, /*range=*/true, /*mstg=*/true);
@@ -85,6 +87,15 @@ int range_posting_lists(Replica* ix, Workspace* w, uint64_t n, const uint32_t* d
     ProfScope ps(ix, 3, stream); // (the profile stage "scan" times both kernels)
     HIP_TRY(launch_mstg_range(P, ix->device, stream));
     if (!distinct) return RBQ_OK;
+    if (d_xq) {
+        MstgRangeExactParams E{};
+        E.raw_ids = P.out_ids; E.raw_scores = P.out_scores; E.raw_counts = P.out_counts;
+        E.queries = d_xq; E.query_dtype = ix->opt.query_dtype; E.raw = ix->raw.p; E.raw_dtype = ix->raw_dtype; E.n_raw = ix->n_raw;
+        E.out_ids = d_ids; E.out_scores = d_scores; E.out_counts = d_counts;
+        E.nq = (uint32_t)n; E.cap = cap; E.dim = ix->dim; E.metric = ix->metric; E.X = x;
+        HIP_TRY(launch_mstg_range_exact(E, ix->device, stream));
+        return RBQ_OK;
+    }
     MstgRangeDistinctParams X{};
     X.raw_ids = P.out_ids; X.raw_scores = P.out_scores; X.raw_counts = P.out_counts;
     X.out_ids = d_ids; X.out_scores = d_scores; X.out_counts = d_counts; X.nq = (uint32_t)n; X.cap = cap;
@@ -234,6 +245,8 @@ struct MstgCall {
     bool exact = false;       // option mstg_rerank on a refined call: the pool is scored against the raw rows (k_mstg_rerank.hip)
     bool range = false, distinct = false; // rbq_mstg_range_batch*: every estimate below `radius`; one entry per id
     float radius = 0.0f;
+    bool range_exact = false; // option mstg_range_exact on a range call: the distinct candidates are scored against the raw rows
+    float exact_x = 0.0f;     //   (k_mstg_range_exact.hip) and kept below this exact radius, the f32 of mstg_range_exact_bits
     unsigned long long* d_fallbacks = nullptr;
     MstgShape sh{};
 };
@@ -264,6 +277,13 @@ int mstg_begin(rbq_index* h, const MstgArgs& a, bool host, hipStream_t s, MstgCa
         std::string detail;
         if ((rc = rbq_host::mstg_rerank_check(ix->opt.mstg_rerank, ix->raw.p != nullptr && ix->n_raw != 0, ix->rerank, &detail))) return fail(rc, detail);
         c->exact = ix->opt.mstg_rerank;
+    }
+    if (a.range) { // the exact range search reads the raw rows of the replica that serves the call, once per id, or the call is refused
+        std::string detail;
+        if ((rc = rbq_host::mstg_range_exact_check(ix->opt.mstg_range_exact, a.distinct, ix->raw.p != nullptr && ix->n_raw != 0, ix->rerank, &detail)))
+            return fail(rc, detail);
+        c->range_exact = ix->opt.mstg_range_exact;
+        std::memcpy(&c->exact_x, &ix->opt.mstg_range_exact_bits, 4);
     }
     const uint32_t ef = (uint32_t)std::min<uint64_t>(a.ef_search, ix->n_lists);
     const bool empty = a.top_k == 0 || ef == 0;
@@ -298,7 +318,8 @@ int mstg_begin(rbq_index* h, const MstgArgs& a, bool host, hipStream_t s, MstgCa
 }
 
 // n queries at d_q (device; rows of the handle's query_dtype, read by mstg_prep alone), everything enqueued on `stream`; d_lists [n][sh.ef] and d_lcnt [n] receive the selection.
-// Range (c.range, k_mstg_range.hip): the scan is the range scan at the constant c.radius, top_k the capacity of a row.
+// Range (c.range, k_mstg_range.hip): the scan is the range scan at the constant c.radius, top_k the capacity of a row; exact
+// (c.range_exact, k_mstg_range_exact.hip): its distinct matches are scored against the raw rows, for which d_q is read once more.
 // Refined (c.pool, k_mstg_refine.hip): the scan runs with top_k := pool over the slot map into the workspace's pool, which is
 // then refined into the caller's top_k — with the ex codes, or (c.exact, k_mstg_rerank.hip) exactly against the raw rows, for
 // which d_q is read once more, as the caller's rows in input space.
@@ -337,7 +358,8 @@ int run_chunk(const MstgCall& c, Workspace* w, const float* d_q, uint64_t n, uin
         HIP_TRY(launch_mstg_select(p, ix->device, stream));
     }
     if (c.range)
-        return range_posting_lists(ix, w, n, d_lists, d_lcnt, sh.ef, sh.wl_stride, c.top_k, c.radius, c.distinct, d_ids, d_scores, d_counts, stream);
+        return range_posting_lists(ix, w, n, d_lists, d_lcnt, sh.ef, sh.wl_stride, c.top_k, c.radius, c.distinct, c.range_exact ? d_q : nullptr,
+                                   c.exact_x, d_ids, d_scores, d_counts, stream);
     rc = scan_posting_lists(ix, w, n, d_lists, d_lcnt, sh.ef, sh.wl_stride, c.pool ? c.pool : c.top_k, s_ids, s_scores, s_counts,
                             c.pool ? (const uint64_t*)ix->mr_slot_map.p : nullptr, stream);
     if (rc || !c.pool) return rc;

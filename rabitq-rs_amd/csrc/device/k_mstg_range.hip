@@ -143,28 +143,6 @@ __global__ __launch_bounds__(kRangeThreads) void k_mstg_range(MstgRangeParams P)
     if (tid == 0) P.out_counts[q] = total; // every match, also those beyond the capacity
 }
 
-// exclusive prefix sum of one value per thread over the workgroup (kThreads = four waves); *total: the sum, on every thread
-__device__ __forceinline__ uint32_t wg_scan_excl(uint32_t v, uint32_t* s_w, uint32_t tid, uint32_t* total) {
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63u) s_w[wave] = x;
-    __syncthreads();
-    uint32_t base = 0, sum = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < (uint32_t)(kThreads / 64); ++j) {
-        const uint32_t c = s_w[j];
-        base += j < wave ? c : 0u;
-        sum += c;
-    }
-    *total = sum;
-    return base + x - v;
-}
-
 __global__ __launch_bounds__(kThreads) void k_mstg_range_distinct(MstgRangeDistinctParams P) {
     extern __shared__ __align__(16) unsigned char smraw[];
     unsigned long long* k1 = reinterpret_cast<unsigned long long*>(smraw); // the id

@@ -20,6 +20,7 @@
 //   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan_codes.hpp, mstg_pool.hpp)
 //   k_mstg_rerank.hip  exact rerank of the MSTG pool: one entry per id, exact scores from the raw rows (mstg_pool.hpp, rerank_score.hpp)
 //   k_mstg_range.hip  MSTG range search: the estimate against a constant radius in scan order, one entry per id (scan_codes.hpp, mstg_pool.hpp)
+//   k_mstg_range_exact.hip  exact MSTG range search: the distinct candidates scored against the raw rows (mstg_pool.hpp, rerank_score.hpp)
 //   k_rerank_pool.hip  pooled rerank: exact scores of a candidate pool from whole lines of the raw rows, order in LDS (rerank_score.hpp)
 //   k_append.hip rbq_index_append: carry of an index into a larger geometry, id bound, nearest list of rotated rows (km_common.hpp)
 //   k_remove.hip rbq_index_remove_ids: keep masks against a sorted id set, slot map, gather of an index into a smaller geometry
@@ -510,6 +511,28 @@ struct MstgRangeDistinctParams {
     uint32_t nq, cap;
 };
 hipError_t launch_mstg_range_distinct(const MstgRangeDistinctParams& P, int device, hipStream_t s);
+
+// ---- exact MSTG range search (options mstg_range_exact / mstg_range_exact_bits; k_mstg_range_exact.hip): in
+// place of k_mstg_range_distinct — the scan's rows reduced to one entry per id, every distinct id scored exactly against its raw
+// row (canon_l2 or -canon_dot), kept iff that distance is finite and < X, in scan order
+struct MstgRangeExactParams {
+    const uint64_t* raw_ids;    // [nq][kMstgRangeDistinctMax] the scan's rows at the candidate radius, raw_scores alike,
+    const float* raw_scores;    // raw_counts [nq] their totals
+    const uint32_t* raw_counts;
+    const void* queries;        // [nq][dim] elements of query_dtype, input space (the caller's rows)
+    const void* raw;            // [n_raw][dim] elements of raw_dtype, n_raw >= 1
+    uint64_t n_raw;
+    uint64_t* out_ids;          // [nq][cap], out_scores [nq][cap] (the exact distances), out_counts [nq]: the exact matches, or
+    float* out_scores;          // UINT32_MAX where the scan's total exceeds kMstgRangeDistinctMax (the row is then empty)
+    uint32_t* out_counts;
+    uint32_t nq, cap, dim, metric;
+    float X;                     // the exact radius
+    int raw_dtype = kRawF32;     // kRawF32 / kRawF16 / kRawBf16
+    int query_dtype = kRawF32;   // the same values: what `queries` holds
+    uint32_t raw_by_element = 0; // set by the launch: 16-bit rows that do not all start 4-byte aligned (odd dim, or raw at 2 mod 4)
+};
+size_t mstg_range_exact_lds_bytes(uint32_t dim);
+hipError_t launch_mstg_range_exact(const MstgRangeExactParams& P, int device, hipStream_t s);
 
 // ---- RBQ1 writer (k_save.hip): words [w0, w0 + nw) of the cluster section of the stream, into out[0, nw)
 struct SaveParams {

@@ -441,4 +441,17 @@ inline int mstg_rerank_check(bool option, bool have_raw, bool rerank_on, std::st
     return RBQ_INVALID_CONFIG;
 }
 
+// The MSTG range call with the option mstg_range_exact decides its matches by the raw rows attached to the
+// replica that serves it, one answer per id: without distinct, without rows, or with the handle's "rerank" 0, the call is refused,
+// in this order — nothing is silently approximated.  Comes after mstg_search_check's errors and before any HIP call.  option 0:
+// the call is the estimate's range search, which never looks at the rows.
+inline int mstg_range_exact_check(bool option, bool distinct, bool have_raw, bool rerank_on, std::string* detail) {
+    if (!option || (distinct && have_raw && rerank_on)) return RBQ_OK;
+    if (detail)
+        *detail = !distinct   ? "exact MSTG range search answers once per id: call with distinct 1 or set mstg_range_exact 0"
+                  : !have_raw ? "exact MSTG range search needs raw vectors attached (rbq_index_set_rerank_vectors) or mstg_range_exact 0"
+                              : "exact MSTG range search needs the rerank on: set the option rerank 1 or mstg_range_exact 0";
+    return RBQ_INVALID_CONFIG;
+}
+
 } // namespace rbq_host

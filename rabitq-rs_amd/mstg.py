@@ -306,19 +306,58 @@ RANGE_DISTINCT_MAX = _abi.MSTG_RANGE_DISTINCT_MAX
 _U32_MAX = 0xFFFFFFFF
 
 
-def mstg_range_rows(index, queries, radius, capacity, ef_search=150, pruning_epsilon=0.6, distinct=True, return_lists=False, dtype=None):
+def _f32_bits(v):
+    return int(np.array([v], np.float32).view(np.int32)[0])
+
+
+@contextlib.contextmanager
+def _mstg_range_exact_for_call(index, exact, x):
+    """Context of one range call: with `exact` the handle's options "mstg_range_exact_bits" / "mstg_range_exact" are set to the bits
+    of x and 1, and the handle's values (read back from it) put back afterwards, error or not.  exact=False makes no option call: a
+    handle whose options the caller set by hand keeps serving as it was told."""
+    if not exact:
+        yield
+        return
+    from .index import _check, lib
+    was, was_bits = C.c_int32(-1), C.c_int32(-1)
+    _check(lib().rbq_debug_copy_index(index._h, b"mstg_range_exact", C.byref(was), 4))
+    _check(lib().rbq_debug_copy_index(index._h, b"mstg_range_exact_bits", C.byref(was_bits), 4))
+    try:
+        index.set_option("mstg_range_exact_bits", _f32_bits(x))
+        index.set_option("mstg_range_exact", 1)
+        yield
+    finally:
+        index.set_option("mstg_range_exact", was.value)
+        index.set_option("mstg_range_exact_bits", was_bits.value)
+
+
+def mstg_range_rows(index, queries, radius, capacity, ef_search=150, pruning_epsilon=0.6, distinct=True, return_lists=False, dtype=None,
+                    exact=False, candidate_radius=None):
     """The rows of a range search on an MSTG handle as the C ABI returns them: (ids [nq][capacity] u64, distances [nq][capacity]
     f32, counts [nq] u32), plus (lists, list_counts) with `return_lists`.  A row holds the first min(count, capacity) matches in
     scan order, then UINT64_MAX / NaN; counts are the totals (they may exceed `capacity`), or UINT32_MAX for a query whose matches
     exceed RANGE_DISTINCT_MAX with `distinct`.  NumPy queries take rbq_mstg_range_batch and return arrays; a CUDA tensor takes
     rbq_mstg_range_batch_device on the current stream, without synchronising, and returns tensors (bit patterns in int64 / int32,
     as mstg_search): the caller reads the counts once the stream has got there and repeats with a larger capacity where one
-    exceeds it.  `queries` and `dtype` as mstg_search."""
+    exceeds it.  `queries` and `dtype` as mstg_search.
+
+    `exact=True` (needs `distinct` and raw vectors attached with set_rerank_vectors): `radius` is the exact
+    radius x and `candidate_radius` the estimate's radius r that picks the candidates (None: +inf).  The distinct ids of the
+    estimate's matches at r are scored against their raw rows — the canonical l2_distance_sqr, or minus the canonical dot product
+    — and an id is a match iff that distance is < x; the distances returned are the exact ones, the order is still the scan's.  A
+    query with more than RANGE_DISTINCT_MAX candidates at r gets UINT32_MAX.  The options "mstg_range_exact" /
+    "mstg_range_exact_bits" are set for the call and put back afterwards; the library refuses a call it cannot answer exactly."""
     from . import _marshal
     from .index import _check, lib_ext
     capacity, ef_search = int(capacity), int(ef_search)
     ef = min(max(ef_search, 0), index.cluster_count())
     q, code = _marshal.query_arg(queries, dtype)
+    if exact:
+        x, radius = radius, np.inf if candidate_radius is None else candidate_radius
+    elif candidate_radius is not None:
+        raise ValueError("candidate_radius belongs to exact=True: without it `radius` is the estimate's radius")
+    else:
+        x = None
     args = (capacity, ef_search, float(pruning_epsilon), float(radius), 1 if distinct else 0)
     nq, qd = q.shape
     torch = torch_of(q)
@@ -330,7 +369,7 @@ def mstg_range_rows(index, queries, radius, capacity, ef_search=150, pruning_eps
             li = torch.empty((nq, ef), dtype=torch.int32, device=q.device) if return_lists else None
             lc = torch.empty(nq, dtype=torch.int32, device=q.device) if return_lists else None
             stream = torch.cuda.current_stream().cuda_stream
-            with index._query_dtype_for_call(code):
+            with index._query_dtype_for_call(code), _mstg_range_exact_for_call(index, exact, x):
                 rc = lib_ext().rbq_mstg_range_batch_device(index._h, q.data_ptr(), nq, qd, *args, ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(),
                                                        li.data_ptr() if return_lists else None, lc.data_ptr() if return_lists else None,
                                                        C.c_void_p(stream))
@@ -339,7 +378,7 @@ def mstg_range_rows(index, queries, radius, capacity, ef_search=150, pruning_eps
     ids, sc, cnt = np.empty((nq, capacity), np.uint64), np.empty((nq, capacity), np.float32), np.zeros(nq, np.uint32)
     li = np.empty((nq, ef), np.uint32) if return_lists else None
     lc = np.empty(nq, np.uint32) if return_lists else None
-    with index._query_dtype_for_call(code):
+    with index._query_dtype_for_call(code), _mstg_range_exact_for_call(index, exact, x):
         rc = lib_ext().rbq_mstg_range_batch(index._h, _marshal.data_ptr(q), nq, qd, *args, ids.ctypes.data, sc.ctypes.data, cnt.ctypes.data,
                                         li.ctypes.data if return_lists else None, lc.ctypes.data if return_lists else None)
     _check(rc)
@@ -347,7 +386,7 @@ def mstg_range_rows(index, queries, radius, capacity, ef_search=150, pruning_eps
 
 
 def mstg_range_search(index, queries, radius, ef_search=150, pruning_epsilon=0.6, max_results=None, distinct=True, return_lists=False,
-                      dtype=None):
+                      dtype=None, exact=False, candidate_radius=None):
     """Range search on an MSTG handle: (lims [nq + 1] i64, ids u64, distances f32) in the CSR shape of
     IvfRabitqIndex.range_search — query q's matches are ids[lims[q]:lims[q + 1]], in scan order (the selected lists in selection
     order, each in its vector order).  A match is a vector of the lists `mstg_search` would scan whose estimate (the distance
@@ -359,7 +398,10 @@ def mstg_range_search(index, queries, radius, ef_search=150, pruning_epsilon=0.6
     value.  With `return_lists`, (lists, list_counts) of the selected posting lists follow.  A query with more than
     RANGE_DISTINCT_MAX matches cannot be reduced to distinct ids on the device: RabitqError names RBQ_MSTG_RANGE_DISTINCT_MAX
     (repeat with distinct=False, or a smaller radius).  `queries` are host rows (mstg_range_rows takes CUDA tensors); `dtype` as
-    mstg_search."""
+    mstg_search.
+    `exact=True`: a match is an id whose exact distance to its raw row is < radius, among the distinct ids whose estimate is <
+    `candidate_radius` (None: +inf); distances are the exact ones (mstg_range_rows' `exact`).  The limit then counts the
+    candidates: where a query exceeds it, repeat with a smaller candidate_radius."""
     from . import RabitqError, _marshal
     from .index import IvfRabitqIndex
     q, dtype = _marshal.query_arg(queries, dtype)
@@ -367,11 +409,11 @@ def mstg_range_search(index, queries, radius, ef_search=150, pruning_epsilon=0.6
         raise ValueError("mstg_range_search takes host queries (mstg_range_rows takes CUDA tensors)")
 
     def call(cap):
-        got = mstg_range_rows(index, q, radius, cap, ef_search, pruning_epsilon, distinct, return_lists, dtype)
+        got = mstg_range_rows(index, q, radius, cap, ef_search, pruning_epsilon, distinct, return_lists, dtype, exact, candidate_radius)
         over = np.nonzero(got[2] == _U32_MAX)[0]
         if distinct and over.size:
-            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "query %d has more than RBQ_MSTG_RANGE_DISTINCT_MAX (%d) matches: repeat with "
-                              "distinct=False or a smaller radius" % (int(over[0]), RANGE_DISTINCT_MAX))
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "query %d has more than RBQ_MSTG_RANGE_DISTINCT_MAX (%d) matches: repeat with %s"
+                              % (int(over[0]), RANGE_DISTINCT_MAX, "a smaller candidate_radius" if exact else "distinct=False or a smaller radius"))
         return got
 
     cap = 1024 if max_results is None else int(max_results)
@@ -595,12 +637,14 @@ class MstgIndex:
             raise ValueError(f"Query dimension {q.shape[-1] if q.ndim else 0} does not match expected {self.dimension}")
         return self.batch_query(q[None, :], k, dtype)[0]
 
-    def range_query(self, queries, radius, distinct=True, dtype=None):
+    def range_query(self, queries, radius, distinct=True, dtype=None, exact=False, candidate_radius=None):
         """Every vector closer than `radius` by the estimate, among the lists a query with the arguments of set_query_arguments
         scans (mstg_range_search with this object's ef_search and pruning_epsilon; no crate counterpart): a list with one
-        [count][2] f32 array of (id, distance) per query, in scan order, every id once unless distinct=False."""
+        [count][2] f32 array of (id, distance) per query, in scan order, every id once unless distinct=False.
+        `exact=True`: closer than `radius` by the exact distance to the vectors of set_rerank_vectors, among the ids whose
+        estimate is below `candidate_radius` (None: +inf); mstg_range_search's `exact`."""
         lims, ids, dist = mstg_range_search(self._built(), queries, radius, self.default_ef_search, self.pruning_epsilon,
-                                            distinct=distinct, dtype=dtype)
+                                            distinct=distinct, dtype=dtype, exact=exact, candidate_radius=candidate_radius)
         return [np.stack([ids[a:b].astype(np.float32), dist[a:b]], axis=1) for a, b in zip(lims[:-1], lims[1:])]
 
     def config(self):
