@@ -248,6 +248,15 @@ LIBRBQ_EXT_BY_HEADER = {
 }
 LIBRBQ_EXT = {name: proto for group in LIBRBQ_EXT_BY_HEADER.values() for name, proto in group.items()}
 
+# The brute-force entries of librbq.so declared under include/ext/, bound on a function table of their own (bruteforce.lib_ext()).
+LIBRBQ_BF_EXT_BY_HEADER = {
+    "ext/rbq_bf_range.h": {
+        "rbq_bf_range_batch": (_INT, [_VP, _VP, _U64, _U32, _U32, _F32, _VP, _U64, _VP, _VP, _VP]),
+        "rbq_bf_metric": (_U32, [_VP]),
+    },
+}
+LIBRBQ_BF_EXT = {name: proto for group in LIBRBQ_BF_EXT_BY_HEADER.values() for name, proto in group.items()}
+
 # csrc/host/rbq_build.h
 LIBRBQ_BUILD = {
     "rbq_build_train_with_clusters": (_INT, [_VP, _U64, _U32, _VP, _U64, _VP, _U32, _U8, _U8, _U64, _INT, _OUT]),

@@ -10,7 +10,19 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _abi, _marshal
-from .index import _check, _detail, lib  # noqa: F401  (shared error mapping; the rbq_bf_* entry points live in the same librbq.so)
+from .index import LIB_PATH, IvfRabitqIndex, _check, _detail, lib  # noqa: F401  (shared error mapping; the rbq_bf_* entry points live in the same librbq.so)
+
+_LIB_EXT = None
+
+
+def lib_ext():
+    """The brute-force entries of librbq.so that include/ext/ declares (_abi.LIBRBQ_BF_EXT), on a function table of their own:
+    the same loaded library as lib(), which is loaded first."""
+    global _LIB_EXT
+    if _LIB_EXT is None:
+        lib()
+        _LIB_EXT = _abi.bind(C.CDLL(LIB_PATH), _abi.LIBRBQ_BF_EXT)
+    return _LIB_EXT
 
 
 @dataclass(frozen=True)
@@ -170,6 +182,47 @@ class BruteForceRabitqIndex:
         """`search` for every row of `queries`, results in input order."""
         ids, scores, counts = self.batch_search_raw(queries, params)
         return [self._results(ids, scores, counts, q) for q in range(ids.shape[0])]
+
+    # -- range search (include/ext/rbq_bf_range.h, DESIGN.md section 39) ------------------------------------------------
+    def range_rows(self, queries, radius, capacity, filter_words=None, filter_nbits=0):
+        """rbq_bf_range_batch as it is: (ids [nq, capacity] u64, scores [nq, capacity] f32, totals [nq] u32).  `radius` is the
+        C entry's threshold on the DISTANCE (inner product: minus the score); a row holds the first min(total, capacity)
+        matches in id order, the other slots are UINT64_MAX / NaN.  capacity 0 counts only."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq, qd = q.shape
+        cap = int(capacity)
+        ids, scores = np.empty((nq, cap), np.uint64), np.empty((nq, cap), np.float32)
+        totals = np.zeros(nq, np.uint32)
+        fw = np.ascontiguousarray(filter_words, dtype=np.uint32) if filter_words is not None else None
+        _check(lib_ext().rbq_bf_range_batch(self._h, q.ctypes.data, nq, qd, cap, float(radius), fw.ctypes.data if fw is not None else None,
+                                            int(filter_nbits), ids.ctypes.data if cap else None, scores.ctypes.data if cap else None,
+                                            totals.ctypes.data))
+        return ids, scores, totals
+
+    def _distance_radius(self, radius):
+        """The user's radius (L2: distance < radius; inner product: score > radius) as the C entry's distance threshold."""
+        return -float(radius) if lib_ext().rbq_bf_metric(self._h) == _abi.METRIC_IP else float(radius)
+
+    def range_search(self, queries, radius, max_results=None, allowed_ids=None, sort=False):
+        """FAISS-style range_search over every vector of the index: (lims [nq + 1] i64, ids u64, scores f32) — query q's matches
+        are ids[lims[q]:lims[q + 1]], ascending by id, or by (score, id) with sort=True.  A match has distance < radius (L2) or
+        score > radius (inner product).  max_results=None: complete rows (a first call with rows of 1024; where a total exceeds
+        that, one more with rows of the largest total — the totals are exact, so one repeat suffices).  max_results=m: at most the
+        first m matches of every query, and the totals [nq] u32 as a fourth value.  `allowed_ids` as search_filtered."""
+        words, nbits = _filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
+        r, cap = self._distance_radius(radius), max_results or 1024
+        ids, sc, cnt = self.range_rows(queries, r, cap, words, nbits)
+        if max_results is None and cnt.size and int(cnt.max()) > cap:
+            ids, sc, cnt = self.range_rows(queries, r, int(cnt.max()), words, nbits)
+        out = IvfRabitqIndex._range_csr(ids, sc, cnt, sort)
+        return out + (cnt,) if max_results is not None else out
+
+    def count_in_range(self, queries, radius, allowed_ids=None):
+        """The number of matches of range_search for every query ([nq] u32), without their rows (capacity 0)."""
+        words, nbits = _filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
+        return self.range_rows(queries, self._distance_radius(radius), 0, words, nbits)[2]
 
     # -- growth, shrinking and read-back (include/rbq_bf_mutate.h) ----------------------------------------------------
     def add(self, data, rescale=None, t_const=None, max_chunk_rows=0):

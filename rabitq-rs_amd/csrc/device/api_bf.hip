@@ -1,8 +1,10 @@
 // api_bf.hip — brute-force index (rbq_bf_*): BruteForceRabitqIndex, reference src/brute_force.rs.
 // Host side: validation, upload, training on the device (rbq_bf_train_device), RBF1 in / out, and per search call: queries -> k_prep (rotation + QueryPrecomputed constants, shared with
-// the IVF path) -> for each chunk of vectors k_bf_dist + k_bf_select (bf.hpp) -> results.  Each call takes a workspace and a stream
+// the IVF path) -> for each chunk of vectors k_bf_dist + k_bf_select (bf.hpp) -> results; the range search (rbq_bf_range_batch)
+// runs k_bf_range_count + k_bf_range_place (bf_range.hpp) behind k_bf_dist instead.  Each call takes a workspace and a stream
 // of its own from the handle's pool, so calls on one handle may overlap.
 #include "bf_index.hpp"
+#include "ext/rbq_bf_range.h"
 
 using namespace rbq_api;
 
@@ -166,10 +168,57 @@ int bf_train_impl(const rbq_header* hdr, const float* data, uint64_t n, int resc
     return RBQ_OK;
 }
 
+// ---- what the search and the range search do the same way ------------------------------------------------------------------------
+// A workspace of the handle's pool for the length of one call.
+struct BfLease {
+    rbq_bf_index* ix;
+    BfWorkspace* w = nullptr;
+    explicit BfLease(rbq_bf_index* i) : ix(i) {
+        {
+            std::lock_guard<std::mutex> lk(ix->mu);
+            if (!ix->pool.empty()) { w = ix->pool.back(); ix->pool.pop_back(); }
+        }
+        if (!w) w = new BfWorkspace();
+    }
+    ~BfLease() { std::lock_guard<std::mutex> lk(ix->mu); ix->pool.push_back(w); }
+};
+
+// The call's stream, and the buffers of `sub` prepared queries and their distances to a chunk of nv_chunk vectors.
+int bf_call_buffers(rbq_bf_index* ix, BfWorkspace* w, uint64_t sub, uint64_t nv_chunk) {
+    if (!w->stream) HIP_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
+    int rc;
+    if ((rc = w->q.ensure(sub * ix->hdr.dim * 4)) || (rc = w->rot.ensure(sub * ix->hdr.padded_dim * 4)) || (rc = w->lut.ensure(sub * 4 * ix->Dc)) ||
+        (rc = w->consts.ensure(sub * sizeof(QueryConsts))) || (rc = w->dist.ensure(sub * nv_chunk * 4)))
+        return rc;
+    return RBQ_OK;
+}
+
+int bf_upload_filter(BfWorkspace* w, const uint32_t* filter_words, uint64_t filter_nbits, const uint32_t** d_filter) {
+    *d_filter = nullptr;
+    if (!filter_words) return RBQ_OK;
+    const uint64_t words = (filter_nbits + 31) / 32;
+    int rc;
+    if ((rc = w->filter.ensure(std::max<uint64_t>(words, 1) * 4))) return rc;
+    if (words) HIP_TRY(hipMemcpyAsync(w->filter.p, filter_words, words * 4, hipMemcpyHostToDevice, w->stream));
+    *d_filter = (const uint32_t*)w->filter.p;
+    return RBQ_OK;
+}
+
+BfDistParams bf_dist_params(const rbq_bf_index* ix, const BfWorkspace* w, uint32_t m, uint64_t v0, uint64_t nv, const uint32_t* d_filter,
+                            uint64_t filter_nbits) {
+    BfDistParams dp;
+    dp.rot = (const float*)w->rot.p; dp.consts = (const QueryConsts*)w->consts.p; dp.nq = m; dp.D = ix->hdr.padded_dim; dp.ex_bits = ix->hdr.ex_bits;
+    dp.v0 = v0; dp.nv = nv; dp.bin = (const uint8_t*)ix->bin.p; dp.ex = (const uint8_t*)ix->ex.p;
+    dp.f_add = (const float*)ix->f[2].p; dp.f_rescale = (const float*)ix->f[3].p;
+    dp.f_add_ex = (const float*)ix->f[6].p; dp.f_rescale_ex = (const float*)ix->f[7].p;
+    dp.filter = d_filter; dp.filter_nbits = filter_nbits; dp.dist = (float*)w->dist.p;
+    return dp;
+}
+
 int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t top_k, const uint32_t* filter_words, uint64_t filter_nbits,
                    uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
     const uint64_t n = ix->hdr.n_vectors, K = top_k;
-    const uint32_t dim = ix->hdr.dim, D = ix->hdr.padded_dim;
+    const uint32_t dim = ix->hdr.dim;
     // plan: vector chunks of at most kBfDistBudget / 4 vectors, sub-batches of queries within the workspace budgets
     const uint64_t cap = g_bf_chunk_vectors.load(std::memory_order_relaxed); // (test hook: read once per call)
     const uint64_t nv_chunk = std::min<uint64_t>({n, kBfDistBudget / 4, cap ? cap : UINT64_MAX});
@@ -179,29 +228,17 @@ int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t
     uint64_t sub = std::min<uint64_t>({nq, kBfMaxSubBatch, std::max<uint64_t>(1, kBfDistBudget / (nv_chunk * 4)),
                                        std::max<uint64_t>(1, kBfOutBudget / (K * 12))});
     if (heap_ws) sub = std::min<uint64_t>(sub, std::max<uint64_t>(1, kBfHeapBudget / ((K + 1) * 8)));
-    BfWorkspace* w = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(ix->mu);
-        if (!ix->pool.empty()) { w = ix->pool.back(); ix->pool.pop_back(); }
-    }
-    if (!w) w = new BfWorkspace();
-    struct Give { rbq_bf_index* ix; BfWorkspace* w; ~Give() { std::lock_guard<std::mutex> lk(ix->mu); ix->pool.push_back(w); } } give{ix, w};
-    if (!w->stream) HIP_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-    hipStream_t st = w->stream;
+    BfLease lease(ix);
+    BfWorkspace* w = lease.w;
     int rc;
-    if ((rc = w->q.ensure(sub * dim * 4)) || (rc = w->rot.ensure(sub * D * 4)) || (rc = w->lut.ensure(sub * 4 * ix->Dc)) ||
-        (rc = w->consts.ensure(sub * sizeof(QueryConsts))) || (rc = w->dist.ensure(sub * nv_chunk * 4)) ||
-        (rc = w->heap_len.ensure(sub * 4)) || (rc = w->ids.ensure(sub * K * 8)) || (rc = w->scores.ensure(sub * K * 4)) ||
+    if ((rc = bf_call_buffers(ix, w, sub, nv_chunk))) return rc;
+    hipStream_t st = w->stream;
+    if ((rc = w->heap_len.ensure(sub * 4)) || (rc = w->ids.ensure(sub * K * 8)) || (rc = w->scores.ensure(sub * K * 4)) ||
         (rc = w->counts.ensure(sub * 4)) || (rc = w->stats.ensure(16)))
         return rc;
     if (heap_ws && ((rc = w->heap_d.ensure(sub * (K + 1) * 4)) || (rc = w->heap_s.ensure(sub * (K + 1) * 4)))) return rc;
     const uint32_t* d_filter = nullptr;
-    if (filter_words) {
-        const uint64_t words = (filter_nbits + 31) / 32;
-        if ((rc = w->filter.ensure(std::max<uint64_t>(words, 1) * 4))) return rc;
-        if (words) HIP_TRY(hipMemcpyAsync(w->filter.p, filter_words, words * 4, hipMemcpyHostToDevice, st));
-        d_filter = (const uint32_t*)w->filter.p;
-    }
+    if ((rc = bf_upload_filter(w, filter_words, filter_nbits, &d_filter))) return rc;
     HIP_TRY(hipMemsetAsync(w->stats.p, 0, 16, st));
     for (uint64_t q0 = 0; q0 < nq; q0 += sub) {
         const uint32_t m = (uint32_t)std::min<uint64_t>(sub, nq - q0);
@@ -209,13 +246,7 @@ int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t
         HIP_TRY(launch_prep(prep_params(*ix, ix->rot_blob, *w, (const float*)w->q.p, m), ix->device, st));
         for (uint64_t c = 0; c < n_chunks; ++c) {
             const uint64_t v0 = c * nv_chunk, nv = std::min<uint64_t>(nv_chunk, n - v0);
-            BfDistParams dp;
-            dp.rot = (const float*)w->rot.p; dp.consts = (const QueryConsts*)w->consts.p; dp.nq = m; dp.D = D; dp.ex_bits = ix->hdr.ex_bits;
-            dp.v0 = v0; dp.nv = nv; dp.bin = (const uint8_t*)ix->bin.p; dp.ex = (const uint8_t*)ix->ex.p;
-            dp.f_add = (const float*)ix->f[2].p; dp.f_rescale = (const float*)ix->f[3].p;
-            dp.f_add_ex = (const float*)ix->f[6].p; dp.f_rescale_ex = (const float*)ix->f[7].p;
-            dp.filter = d_filter; dp.filter_nbits = filter_nbits; dp.dist = (float*)w->dist.p;
-            HIP_TRY(launch_bf_dist(dp, st));
+            HIP_TRY(launch_bf_dist(bf_dist_params(ix, w, m, v0, nv, d_filter, filter_nbits), st));
             BfSelectParams sp;
             sp.dist = (const float*)w->dist.p; sp.nq = m; sp.top_k = top_k; sp.v0 = v0; sp.nv = nv; sp.metric = ix->hdr.metric;
             sp.first = c == 0; sp.last = c + 1 == n_chunks; sp.lds_heap = lds_heap;
@@ -234,6 +265,64 @@ int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t
     HIP_TRY(hipStreamSynchronize(st));
     ix->pushes += stats[0];
     ix->tie_pushes += stats[1];
+    return RBQ_OK;
+}
+
+// rbq_bf_range_batch (include/ext/rbq_bf_range.h): the search's plan without its heap — k_prep, then per chunk
+// of vectors k_bf_dist -> k_bf_range_count -> k_bf_range_place (bf_range.hpp), the totals carried from chunk to chunk in two arrays
+// that alternate.  The sub-batch comes from the distance budget and, with rows, the output budget.
+int bf_range_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t capacity, float radius, const uint32_t* filter_words,
+                  uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+    const uint64_t n = ix->hdr.n_vectors;
+    const uint32_t dim = ix->hdr.dim;
+    const uint64_t limit = g_bf_chunk_vectors.load(std::memory_order_relaxed); // (test hook: read once per call)
+    const uint64_t nv_chunk = std::min<uint64_t>({n, kBfDistBudget / 4, limit ? limit : UINT64_MAX});
+    const uint64_t n_chunks = (n + nv_chunk - 1) / nv_chunk;
+    const uint64_t spans = (nv_chunk + kBfRangeSpan - 1) / kBfRangeSpan;
+    const uint64_t cap = std::min<uint64_t>(capacity, n); // slots per row on the device: no row holds more than n matches
+    uint64_t sub = std::min<uint64_t>({nq, kBfMaxSubBatch, std::max<uint64_t>(1, kBfDistBudget / (nv_chunk * 4))});
+    if (cap) sub = std::min<uint64_t>(sub, std::max<uint64_t>(1, kBfOutBudget / (cap * 12)));
+    BfLease lease(ix);
+    BfWorkspace* w = lease.w;
+    int rc;
+    if ((rc = bf_call_buffers(ix, w, sub, nv_chunk))) return rc;
+    hipStream_t st = w->stream;
+    if ((rc = w->span_counts.ensure(sub * spans * 4)) || (rc = w->running.ensure(2 * sub * 4)) || (rc = w->counts.ensure(sub * 4))) return rc;
+    if (cap && ((rc = w->ids.ensure(sub * cap * 8)) || (rc = w->scores.ensure(sub * cap * 4)))) return rc;
+    const uint32_t* d_filter = nullptr;
+    if ((rc = bf_upload_filter(w, filter_words, filter_nbits, &d_filter))) return rc;
+    for (uint64_t q0 = 0; q0 < nq; q0 += sub) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(sub, nq - q0);
+        HIP_TRY(hipMemcpyAsync(w->q.p, queries + q0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(launch_prep(prep_params(*ix, ix->rot_blob, *w, (const float*)w->q.p, m), ix->device, st));
+        for (uint64_t c = 0; c < n_chunks; ++c) {
+            const uint64_t v0 = c * nv_chunk, nv = std::min<uint64_t>(nv_chunk, n - v0);
+            HIP_TRY(launch_bf_dist(bf_dist_params(ix, w, m, v0, nv, d_filter, filter_nbits), st));
+            BfRangeParams rp;
+            rp.dist = (const float*)w->dist.p; rp.nq = m; rp.n_spans = (uint32_t)((nv + kBfRangeSpan - 1) / kBfRangeSpan);
+            rp.v0 = v0; rp.nv = nv; rp.radius = radius; rp.metric = ix->hdr.metric; rp.first = c == 0; rp.last = c + 1 == n_chunks;
+            rp.capacity = (uint32_t)cap; rp.span_counts = (uint32_t*)w->span_counts.p;
+            rp.run_in = (const uint32_t*)w->running.p + (c & 1) * sub; rp.run_out = (uint32_t*)w->running.p + ((c + 1) & 1) * sub;
+            rp.out_ids = (uint64_t*)w->ids.p; rp.out_scores = (float*)w->scores.p; rp.out_counts = (uint32_t*)w->counts.p;
+            HIP_TRY(launch_bf_range_count(rp, st));
+            HIP_TRY(launch_bf_range_place(rp, st));
+        }
+        if (cap == capacity && cap) {
+            HIP_TRY(hipMemcpyAsync(out_ids + q0 * cap, w->ids.p, (size_t)m * cap * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_scores + q0 * cap, w->scores.p, (size_t)m * cap * 4, hipMemcpyDeviceToHost, st));
+        } else if (cap) { // capacity > n: the caller's rows are wider than the device's
+            HIP_TRY(hipMemcpy2DAsync(out_ids + q0 * capacity, (size_t)capacity * 8, w->ids.p, cap * 8, cap * 8, m, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpy2DAsync(out_scores + q0 * capacity, (size_t)capacity * 4, w->scores.p, cap * 4, cap * 4, m, hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipMemcpyAsync(out_counts + q0, w->counts.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+    }
+    // capacity > n: slots n .. capacity - 1 of a row can hold no match whatever the device finds; they are written here, beside
+    // the copies above, while the stream works
+    for (uint64_t q = 0; cap < capacity && q < nq; ++q) {
+        std::fill_n(out_ids + q * capacity + cap, capacity - cap, ~0ull);
+        std::fill_n(out_scores + q * capacity + cap, capacity - cap, std::numeric_limits<float>::quiet_NaN());
+    }
+    HIP_TRY(hipStreamSynchronize(st));
     return RBQ_OK;
 }
 } // namespace
@@ -321,6 +410,7 @@ void rbq_bf_destroy(rbq_bf_index* idx) { bf_free(idx); }
 uint64_t rbq_bf_len(const rbq_bf_index* idx) { return idx ? idx->hdr.n_vectors : 0; }
 uint32_t rbq_bf_dim(const rbq_bf_index* idx) { return idx ? idx->hdr.dim : 0; }
 uint32_t rbq_bf_padded_dim(const rbq_bf_index* idx) { return idx ? idx->hdr.padded_dim : 0; }
+uint32_t rbq_bf_metric(const rbq_bf_index* idx) { return idx ? idx->hdr.metric : RBQ_METRIC_L2; }
 
 void rbq_bf_debug_heap_stats(const rbq_bf_index* idx, uint64_t* out2) {
     if (!idx || !out2) return;
@@ -353,6 +443,28 @@ int rbq_bf_search_batch(const rbq_bf_index* ch, const float* queries, uint64_t n
     DeviceGuard g(ix->device);
     if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
     return bf_search_impl(ix, queries, nq, top_k, filter_words, filter_nbits, out_ids, out_scores, out_counts);
+    RBQ_GUARD_END
+}
+
+int rbq_bf_range_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t capacity, float radius,
+                       const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!ch) return fail(RBQ_INVALID_CONFIG, "null index");
+    rbq_bf_index* ix = const_cast<rbq_bf_index*>(ch);
+    if (ix->hdr.n_vectors == 0) return fail(RBQ_EMPTY_INDEX, "index is empty");
+    if (query_dim != ix->hdr.dim) {
+        char b[96];
+        std::snprintf(b, sizeof b, "expected %u, got %u", ix->hdr.dim, query_dim);
+        return fail(RBQ_DIMENSION_MISMATCH, b);
+    }
+    if (nq == 0) return RBQ_OK;
+    if (nq >= (1ull << 31)) return fail(RBQ_INVALID_CONFIG, "nq >= 2^31");
+    if (!queries || !out_counts || (capacity && (!out_ids || !out_scores))) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    if (radius != radius) return fail(RBQ_INVALID_CONFIG, "radius is NaN");
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    return bf_range_impl(ix, queries, nq, capacity, radius, filter_words, filter_nbits, out_ids, out_scores, out_counts);
     RBQ_GUARD_END
 }
 } // extern "C"

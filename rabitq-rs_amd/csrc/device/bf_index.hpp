@@ -9,6 +9,7 @@ namespace rbq_api {
 struct BfWorkspace { // what one search call holds: a stream and its buffers, from the handle's pool
     hipStream_t stream = nullptr;
     DevBuf q, rot, lut, consts, dist, heap_d, heap_s, heap_len, filter, ids, scores, counts, stats;
+    DevBuf span_counts, running; // range search: matches per (query, span) of a chunk; per query over the chunks so far (two arrays)
     BfWorkspace() = default;
     BfWorkspace(const BfWorkspace&) = delete;
     ~BfWorkspace() { if (stream) (void)hipStreamDestroy(stream); } // (deleted under the index's DeviceGuard)

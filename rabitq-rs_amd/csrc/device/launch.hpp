@@ -302,6 +302,26 @@ struct BfSelectParams {
 };
 hipError_t launch_bf_select(const BfSelectParams& p, hipStream_t s);
 constexpr uint32_t kBfLdsHeapMaxTopK = 8191; // (top_k + 1) * 8 bytes of LDS heap <= 64 KiB
+// brute-force range search (bf_range.hpp, k_bf_range.hip): behind launch_bf_dist, the matches of every
+// (span of kBfRangeSpan vectors, query) counted, then placed at their rank in id order
+constexpr uint32_t kBfRangeSpan = 2048; // vectors per workgroup: 8 loads in flight per lane, 489 spans per query at 1 M vectors
+struct BfRangeParams {
+    const float* dist;         // [nq][nv] (launch_bf_dist)
+    uint32_t nq, n_spans;      // n_spans = ceil(nv / kBfRangeSpan)
+    uint64_t v0, nv;
+    float radius;              // a match: finite distance < radius
+    int metric;
+    int first, last;           // first / last vector chunk of the call
+    uint32_t capacity;         // slots per row; 0: count only (the outputs may be null)
+    uint32_t* span_counts;     // [nq][n_spans]: written by the count launch, read by the place launch
+    const uint32_t* run_in;    // [nq] matches of the earlier chunks (not read when first)
+    uint32_t* run_out;         // [nq] ... with this chunk's (not written when last); never the array run_in names
+    uint64_t* out_ids;         // [nq][capacity]
+    float* out_scores;
+    uint32_t* out_counts;      // [nq] the total, written on the last chunk
+};
+hipError_t launch_bf_range_count(const BfRangeParams& p, hipStream_t s);
+hipError_t launch_bf_range_place(const BfRangeParams& p, hipStream_t s); // after launch_bf_range_count on the same stream
 // k_bf_train.hip: BruteForceRabitqIndex::train.  launch_bf_encode: k_encode's flat mode over P.nslots rotated rows (see
 // EncodeParams; P.t_row != null: the per-vector rescale factors of launch_rescale).  launch_bf_pack_ex: raw ex codes [nrows][D]
 // u8 -> the crate's ex_code_packed [nrows][D * ex_bits / 8] (ex_bits 2 or 6)
