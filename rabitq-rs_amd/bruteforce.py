@@ -9,7 +9,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _abi, _marshal
+from . import _abi, _marshal, _range
 from .index import LIB_PATH, IvfRabitqIndex, _check, _detail, lib  # noqa: F401  (shared error mapping; the rbq_bf_* entry points live in the same librbq.so)
 
 _LIB_EXT = None
@@ -36,14 +36,7 @@ class BruteForceSearchResult:
     score: float
 
 
-def _filter_words(allowed_ids):
-    allowed = np.asarray(sorted(set(int(i) for i in allowed_ids)), dtype=np.uint64)
-    nbits = int(allowed.max()) + 1 if allowed.size else 0
-    words = np.zeros((nbits + 31) // 32 or 1, np.uint32)
-    if allowed.size:
-        np.bitwise_or.at(words, (allowed >> np.uint64(5)).astype(np.int64),
-                         (np.uint32(1) << (allowed & np.uint64(31)).astype(np.uint32)))
-    return words, nbits
+_filter_words = _range.filter_words
 
 
 class BruteForceRabitqIndex:
@@ -212,11 +205,9 @@ class BruteForceRabitqIndex:
         that, one more with rows of the largest total — the totals are exact, so one repeat suffices).  max_results=m: at most the
         first m matches of every query, and the totals [nq] u32 as a fourth value.  `allowed_ids` as search_filtered."""
         words, nbits = _filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
-        r, cap = self._distance_radius(radius), max_results or 1024
-        ids, sc, cnt = self.range_rows(queries, r, cap, words, nbits)
-        if max_results is None and cnt.size and int(cnt.max()) > cap:
-            ids, sc, cnt = self.range_rows(queries, r, int(cnt.max()), words, nbits)
-        out = IvfRabitqIndex._range_csr(ids, sc, cnt, sort)
+        r = self._distance_radius(radius)
+        ids, sc, cnt = _range.complete_rows(lambda cap: self.range_rows(queries, r, cap, words, nbits), max_results)
+        out = _range.csr(ids, sc, cnt, sort)
         return out + (cnt,) if max_results is not None else out
 
     def count_in_range(self, queries, radius, allowed_ids=None):

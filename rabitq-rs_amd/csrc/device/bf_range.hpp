@@ -23,6 +23,7 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "range_common.hpp" // rg_pad_row
 
 namespace rbq {
 
@@ -134,10 +135,7 @@ __global__ __launch_bounds__(kBfRangeThreads) void k_bf_range_place(BfRangeParam
         const uint32_t piece = (cap - lo + P.n_spans - 1u) / P.n_spans;
         const uint64_t a = (uint64_t)lo + (uint64_t)span * piece;
         const uint64_t b = a + piece < cap ? a + piece : cap;
-        for (uint64_t i = a + tid; i < b; i += kBfRangeThreads) {
-            oid[i] = ~0ull;
-            osc[i] = __int_as_float(0x7fc00000);
-        }
+        rg_pad_row(oid, osc, a, b, tid, kBfRangeThreads);
     }
 }
 

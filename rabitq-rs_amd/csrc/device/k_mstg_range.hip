@@ -20,12 +20,9 @@
 //     Dynamic LDS: lut[4 Dc] u8 at byte 0 | matches per wave [2][4] u32.
 //
 //   k_mstg_range_distinct   one workgroup per query over the row the scan wrote (total <= RBQ_MSTG_RANGE_DISTINCT_MAX):
-//       A  (id | estimate key << 32 + scan rank) of every match into LDS, padded to a power of two;
-//       B  mr_sort (mstg_pool.hpp, the network k_mstg_refine sorts its pool with) by (id, estimate by value, rank): the head of an id
-//          run is the match the contract keeps — the smallest estimate, on equal values the earlier in scan order;
-//       C  every head sets bit (rank & 15) of word rank >> 4: the flags are back in scan order without a second sort;
-//       D  thread t owns ranks 16 t .. 16 t + 15: popcount, workgroup prefix sum (shuffles inside a wave, four partial sums through
-//          LDS), and the kept matches are copied from the scan's row to the caller's in rank order, up to the capacity.
+//       A - C  rg_distinct_heads (range_common.hpp): keys, mr_sort by (id, estimate by value, rank), one flag in scan order per id —
+//          the match the contract keeps is the smallest estimate, on equal values the earlier in scan order;
+//       D  rg_walk_flags: the kept matches are copied from the scan's row to the caller's in rank order, up to the capacity.
 //     A row whose total exceeds the limit is answered with UINT32_MAX and no entry: nothing is deduplicated on a prefix.
 //     Dynamic LDS: id[np2] u64 | key[np2] u64 | flags[256] u32 | wave sums [4] u32, np2 = RBQ_MSTG_RANGE_DISTINCT_MAX: 65 KiB.
 #include <hip/hip_runtime.h>
@@ -34,13 +31,12 @@
 #include "ext/rbq_mstg_range.h"
 #include "launch.hpp"
 #include "kernels.hpp"
-#include "mstg_pool.hpp"  // mr_sort, kMrDropped: shared with k_mstg_refine.hip / k_mstg_rerank.hip
-#include "scan_codes.hpp" // lds_lut_ptr, load_codes / lookup_codes / accumulate_block_rt, lds_barrier
+#include "range_common.hpp" // the steps shared with k_range and k_mstg_range_exact
+#include "scan_codes.hpp"   // load_codes / lookup_codes / accumulate_block_rt
 
 namespace rbq {
 
 static_assert(RBQ_MSTG_RANGE_DISTINCT_MAX == kMstgRangeDistinctMax, "rbq_mstg_range.h and launch.hpp disagree");
-static_assert(kMstgRangeDistinctMax == 16 * kThreads, "k_mstg_range_distinct: sixteen ranks per thread");
 
 template <int DT, bool UNF>
 __global__ __launch_bounds__(kRangeThreads) void k_mstg_range(MstgRangeParams P) {
@@ -70,15 +66,10 @@ __global__ __launch_bounds__(kRangeThreads) void k_mstg_range(MstgRangeParams P)
     float* out_scores = P.out_scores + (size_t)q * cap;
     __syncthreads();
 
-    // the binary estimate as a function of the accumulator: the epilogue's operation sequence up to the estimate (k_scan's lb_of
-    // without the error term, which g_error = 0 makes vanish), one statement per rounding
+    // the estimate as it is: k_scan's lb_of without the error term, which g_error = 0 makes vanish
     auto est_of = [&](float f_add, float f_rescale, float g_add, float accu_f) -> float {
-        const float ip = epi_ip(qc.delta, accu_f, qc.sum_vl, UNF);
-        const float tt = ip + qc.k1x;
-        const float rs = f_rescale * tt;
-        float est = f_add + g_add;
-        est = est + rs;
-        return est;
+        float ip;
+        return rg_estimate(qc, f_add, f_rescale, g_add, accu_f, UNF, ip);
     };
     const bool bound_ok = qc.amax <= 65535.0f && !P.no_block_bound; // (k_scan's condition: the accumulator cannot wrap)
 
@@ -157,46 +148,11 @@ __global__ __launch_bounds__(kThreads) void k_mstg_range_distinct(MstgRangeDisti
     const uint32_t total = P.raw_counts[q];
     uint32_t kept = 0;
     if (total != 0u && total <= kMstgRangeDistinctMax) { // (uniform)
-        uint32_t np2 = 1;
-        while (np2 < total) np2 <<= 1;
-        // ---- A
-        for (uint32_t i = tid; i < np2; i += kThreads) {
-            unsigned long long id = kMrDropped, key = kMrDropped;
-            if (i < total) {
-                const float e = rest[i];
-                const float v = e == 0.0f ? 0.0f : e; // the key orders by value: -0.0 and +0.0 share one, rank decides between them
-                id = rids[i];
-                key = ((unsigned long long)((uint32_t)total_key(v) ^ 0x80000000u) << 32) | i;
-            }
-            k1[i] = id; k2[i] = key;
-        }
-        s_keep[tid] = 0u;
-        // ---- B
-        mr_sort<true>(k1, k2, np2, tid);
-        // ---- C
-        for (uint32_t i = tid; i < np2; i += kThreads) {
-            const unsigned long long key = k2[i];
-            if (key != kMrDropped && (i == 0u || k1[i] != k1[i - 1u])) {
-                const uint32_t rank = (uint32_t)key;
-                atomicOr(&s_keep[rank >> 4], 1u << (rank & 15u));
-            }
-        }
-        __syncthreads();
-        // ---- D
-        uint32_t m = s_keep[tid];
-        uint32_t at = wg_scan_excl((uint32_t)__popc(m), s_w, tid, &kept);
-        while (m && at < cap) {
-            const uint32_t r = tid * 16u + (uint32_t)__ffs(m) - 1u; // < total: only ranks of real entries were flagged
-            m &= m - 1u;
-            out_ids[at] = rids[r];
-            out_scores[at] = rest[r];
-            ++at;
-        }
+        rg_distinct_heads(k1, k2, s_keep, rids, rest, total, tid); // ---- A to C
+        // ---- D (r < total: only ranks of real entries were flagged)
+        kept = rg_walk_flags(s_keep, s_w, tid, cap, [&](uint32_t at, uint32_t r) { out_ids[at] = rids[r]; out_scores[at] = rest[r]; });
     }
-    for (uint32_t i = (kept < cap ? kept : cap) + tid; i < cap; i += kThreads) {
-        out_ids[i] = ~0ull;
-        out_scores[i] = __int_as_float(0x7fc00000);
-    }
+    rg_pad_row(out_ids, out_scores, kept < cap ? kept : cap, cap, tid, (uint32_t)kThreads);
     if (tid == 0) P.out_counts[q] = total > kMstgRangeDistinctMax ? 0xffffffffu : kept;
 }
 

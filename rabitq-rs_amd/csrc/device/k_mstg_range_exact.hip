@@ -5,17 +5,16 @@
 // RBQ_MSTG_RANGE_DISTINCT_MAX entries it reads.  gfx950 only, wave64.
 //
 //   k_mstg_range_exact<IP, RAW>   one workgroup (4 waves) per query.  RAW: the element type of the raw rows (kRawF32 / kRawF16 / kRawBf16).
-//     A  the query widened into LDS; (id | estimate key << 32 + scan rank) of every match, padded to a power of two;
-//     B  mr_sort (mstg_pool.hpp) by (id, estimate by value, rank): the head of an id run is the candidate the distinct rule keeps;
-//     C  every head sets bit (rank & 15) of word rank >> 4 (LDS atomic OR): the flags are in scan order;
-//     D  thread t owns ranks 16 t .. 16 t + 15: popcount, workgroup prefix sum, and the heads' ranks go into a dense list in scan
-//        order (the key arrays are free after C: the list and the distances live there);
+//     A - C  the query widened into LDS; rg_distinct_heads (range_common.hpp, k_mstg_range_distinct's copy): one flag in scan order
+//        for the candidate the distinct rule keeps of every id;
+//     D  rg_walk_flags: the heads' ranks go into a dense list in scan order (the key arrays are free after C: the list and the
+//        distances live there);
 //     S  eight lanes per distinct id, 32 ids per round, ceil(n / 32) rounds on every wave: rp_score_row (rerank_score.hpp: the bits
 //        of canon_l2 / canon_dot) over the query in LDS; the id is the scan's row at the rank.  A group without an id, or with an id
 //        >= n_raw, reads row 0 and discards it.  Lane 0 of a group stores the distance bits at the dense place (canon_l2 or
 //        -canon_dot; NaN without a raw row) and sets the place's hit bit iff the distance is finite and < x;
-//     E  popcount prefix over the hit bits (thread t owns places 16 t .. 16 t + 15): the hits are written at their prefix while that
-//        is below the capacity, the total goes to out_counts, the rest of the row is padded.
+//     E  rg_walk_flags over the hit bits: the hits are written at their prefix while that is below the capacity, the total goes to
+//        out_counts, the rest of the row is padded.
 //     No atomic decides a position: every place is a function of the scan rank alone, so the same call gives the same rows.
 //     A query without a match, or with more than the limit, takes none of A to E: 0 or UINT32_MAX, and an empty row.
 // Dynamic LDS: query[dim rounded up to 2] f32 | k1[4096] u64 | k2[4096] u64 | keep[256] u32 | hit[256] u32 | wave sums [4] u32.
@@ -24,17 +23,15 @@
 
 #include "rbq.h"
 #include "ext/rbq_mstg_range.h"
-#include "launch.hpp"
+#include "launch_util.hpp"
 #include "kernels.hpp"
-#include "mstg_pool.hpp" // mr_sort, kMrDropped, wg_scan_excl
+#include "range_common.hpp" // rg_distinct_heads, rg_walk_flags, rg_pad_row
 
 #pragma clang fp contract(off)
 
 #include "rerank_score.hpp" // (after the pragma: the scorer's sums are unfused)
 
 namespace rbq {
-
-static_assert(kMstgRangeDistinctMax == 16 * kThreads, "k_mstg_range_exact: sixteen ranks, and sixteen dense places, per thread");
 
 template <bool IP, int RAW>
 __global__ __launch_bounds__(kThreads) void k_mstg_range_exact(MstgRangeExactParams P) {
@@ -55,43 +52,12 @@ __global__ __launch_bounds__(kThreads) void k_mstg_range_exact(MstgRangeExactPar
     const uint32_t total = P.raw_counts[q];
     uint32_t hits = 0;
     if (total != 0u && total <= kMstgRangeDistinctMax) { // (uniform)
-        uint32_t np2 = 1;
-        while (np2 < total) np2 <<= 1;
-        // ---- A
+        // ---- A to C (every read of the keys is done behind them: their arrays become the dense list and the distances)
         copy_query_widened<kThreads>(sq, P.queries, P.query_dtype, (size_t)q * dim, dim, tid);
-        for (uint32_t i = tid; i < np2; i += kThreads) {
-            unsigned long long id = kMrDropped, key = kMrDropped;
-            if (i < total) {
-                const float e = rest[i];
-                const float v = e == 0.0f ? 0.0f : e; // the key orders by value: -0.0 and +0.0 share one, rank decides between them
-                id = rids[i];
-                key = ((unsigned long long)((uint32_t)total_key(v) ^ 0x80000000u) << 32) | i;
-            }
-            k1[i] = id; k2[i] = key;
-        }
-        s_keep[tid] = 0u;
         s_hit[tid] = 0u;
-        // ---- B
-        mr_sort<true>(k1, k2, np2, tid);
-        // ---- C
-        for (uint32_t i = tid; i < np2; i += kThreads) {
-            const unsigned long long key = k2[i];
-            if (key != kMrDropped && (i == 0u || k1[i] != k1[i - 1u])) {
-                const uint32_t rank = (uint32_t)key;
-                atomicOr(&s_keep[rank >> 4], 1u << (rank & 15u));
-            }
-        }
-        __syncthreads(); // (every read of the keys is done: their arrays become the dense list and the distances)
-        // ---- D
-        uint32_t n = 0;
-        {
-            uint32_t m = s_keep[tid];
-            uint32_t at = wg_scan_excl((uint32_t)__popc(m), s_w, tid, &n);
-            while (m) {
-                dense[at++] = tid * 16u + (uint32_t)__ffs(m) - 1u; // < total: only ranks of real entries were flagged
-                m &= m - 1u;
-            }
-        }
+        rg_distinct_heads(k1, k2, s_keep, rids, rest, total, tid);
+        // ---- D (every head has a place: at < n <= the limit)
+        const uint32_t n = rg_walk_flags(s_keep, s_w, tid, kMstgRangeDistinctMax, [&](uint32_t at, uint32_t r) { dense[at] = r; });
         __syncthreads();
         // ---- S: eight lanes per distinct id (a group without one reads row 0 and writes nothing)
         const uint32_t j = lane & 7u, grp = lane >> 3, base = lane & ~7u;
@@ -109,21 +75,13 @@ __global__ __launch_bounds__(kThreads) void k_mstg_range_exact(MstgRangeExactPar
             }
         }
         __syncthreads();
-        // ---- E
-        uint32_t h = s_hit[tid];
-        uint32_t at = wg_scan_excl((uint32_t)__popc(h), s_w, tid, &hits);
-        while (h && at < cap) {
-            const uint32_t p = tid * 16u + (uint32_t)__ffs(h) - 1u; // < n: only scored places were flagged
-            h &= h - 1u;
+        // ---- E (p < n: only scored places were flagged)
+        hits = rg_walk_flags(s_hit, s_w, tid, cap, [&](uint32_t at, uint32_t p) {
             out_ids[at] = rids[dense[p]];
             out_scores[at] = __uint_as_float(dist[p]);
-            ++at;
-        }
+        });
     }
-    for (uint32_t i = (hits < cap ? hits : cap) + tid; i < cap; i += kThreads) {
-        out_ids[i] = ~0ull;
-        out_scores[i] = __int_as_float(0x7fc00000);
-    }
+    rg_pad_row(out_ids, out_scores, hits < cap ? hits : cap, cap, tid, (uint32_t)kThreads);
     if (tid == 0) P.out_counts[q] = total > kMstgRangeDistinctMax ? 0xffffffffu : hits;
 }
 
@@ -153,13 +111,8 @@ hipError_t launch_mstg_range_exact(const MstgRangeExactParams& P0, int device, h
     if (P.nq == 0u || P.cap == 0u || P.dim == 0u || P.n_raw == 0u || !P.raw) return hipErrorInvalidValue;
     const size_t lds = mstg_range_exact_lds_bytes(P.dim);
     if (lds > kLdsPerWorkgroupMax) return hipErrorInvalidValue;
-    // as launch_mstg_rerank: 16-byte loads go to 4-byte aligned addresses only; 16-bit rows all start on one exactly when the base
-    // does and dim is even, otherwise the scorer loads element by element
-    P.raw_by_element = P.raw_dtype != kRawF32 && ((P.dim & 1u) != 0u || (reinterpret_cast<uintptr_t>(P.raw) & 3u) != 0u) ? 1u : 0u;
-    if (P.raw_dtype == kRawF32) return launch_mrx<kRawF32>(P, lds, device, s);
-    if (P.raw_dtype == kRawF16) return launch_mrx<kRawF16>(P, lds, device, s);
-    if (P.raw_dtype == kRawBf16) return launch_mrx<kRawBf16>(P, lds, device, s);
-    return hipErrorInvalidValue;
+    P.raw_by_element = raw_rows_by_element(P.raw, P.raw_dtype, P.dim);
+    return dispatch_raw_dtype(P.raw_dtype, [&](auto raw) { return launch_mrx<decltype(raw)::value>(P, lds, device, s); });
 }
 
 } // namespace rbq

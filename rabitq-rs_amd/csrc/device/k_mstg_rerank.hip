@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rbq_mstg.h"
-#include "launch.hpp"
+#include "launch_util.hpp"
 #include "kernels.hpp"
 #include "mstg_pool.hpp"
 
@@ -160,13 +160,8 @@ hipError_t launch_mstg_rerank(const MstgRerankParams& P0, int device, hipStream_
     if (P.pool_np2 > kMrPoolMax || P.pool > P.pool_np2 || (P.pool_np2 & (P.pool_np2 - 1u)) != 0u) return hipErrorInvalidValue;
     const size_t lds = mstg_rerank_lds_bytes(P.dim, P.pool_np2);
     if (lds > kLdsPerWorkgroupMax) return hipErrorInvalidValue;
-    // as launch_rerank_pool: 16-byte loads go to 4-byte aligned addresses only; 16-bit rows all start on one exactly when the base
-    // does and dim is even, otherwise the scorer loads element by element
-    P.raw_by_element = P.raw_dtype != kRawF32 && ((P.dim & 1u) != 0u || (reinterpret_cast<uintptr_t>(P.raw) & 3u) != 0u) ? 1u : 0u;
-    if (P.raw_dtype == kRawF32) return launch_mrr<kRawF32>(P, lds, device, s);
-    if (P.raw_dtype == kRawF16) return launch_mrr<kRawF16>(P, lds, device, s);
-    if (P.raw_dtype == kRawBf16) return launch_mrr<kRawBf16>(P, lds, device, s);
-    return hipErrorInvalidValue;
+    P.raw_by_element = raw_rows_by_element(P.raw, P.raw_dtype, P.dim);
+    return dispatch_raw_dtype(P.raw_dtype, [&](auto raw) { return launch_mrr<decltype(raw)::value>(P, lds, device, s); });
 }
 
 } // namespace rbq

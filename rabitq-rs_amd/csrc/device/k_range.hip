@@ -1,8 +1,7 @@
 // k_range.hip — translation unit of the range search's scan (range.hpp) and its launcher.  gfx950 only.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
-#include "launch.hpp"
+#include "launch_util.hpp"
 #include "range.hpp"
 
 namespace rbq {
@@ -10,13 +9,7 @@ namespace {
 
 template <int DT, int EX, int V = kVarAvx512>
 hipError_t launch_range_r(const RangeParams& P, uint32_t nq, size_t lds, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    static LdsAttrCache attr;
-    if (probe_stage(3, reinterpret_cast<const void*>(&k_range<DT, EX, V>), dim3(nq), kRangeThreads, lds)) return hipSuccess;
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&k_range<DT, EX, V>), lds, device);
-    if (e != hipSuccess) return e;
-    if (ev0) hipExtLaunchKernelGGL((k_range<DT, EX, V>), dim3(nq), dim3(kRangeThreads), lds, s, ev0, ev1, 0, P);
-    else hipLaunchKernelGGL((k_range<DT, EX, V>), dim3(nq), dim3(kRangeThreads), lds, s, P);
-    return hipGetLastError();
+    return launch_range_kernel<&k_range<DT, EX, V>>(P, nq, lds, device, s, ev0, ev1);
 }
 template <int DT>
 hipError_t launch_range_d(const RangeParams& P, uint32_t nq, size_t lds, int device, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {

@@ -26,7 +26,7 @@
 // Dynamic LDS: query[dim rounded up to 2] f32 | key[np2(pool)] u64.
 #include <hip/hip_runtime.h>
 
-#include "launch.hpp"
+#include "launch_util.hpp"
 #include "kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -124,13 +124,8 @@ hipError_t launch_rerank_pool(const RerankPoolParams& P0, int device, hipStream_
     if (P.nq == 0u || P.dim == 0u || P.n_raw == 0u || P.top_k == 0u || P.pool <= P.top_k || P.pool > kRerankPoolMax) return hipErrorInvalidValue;
     const size_t lds = rerank_pool_lds_bytes(P.dim, P.pool);
     if (lds > kLdsPerWorkgroupMax) return hipErrorInvalidValue;
-    // 16-byte loads go to 4-byte aligned addresses only: 16-bit rows all start on one exactly when the base does and dim is even;
-    // otherwise the kernel loads element by element (the slow path; callers who care pad dim to even)
-    P.raw_by_element = P.raw_dtype != kRawF32 && ((P.dim & 1u) != 0u || (reinterpret_cast<uintptr_t>(P.raw) & 3u) != 0u) ? 1u : 0u;
-    if (P.raw_dtype == kRawF32) return launch_rp<kRawF32>(P, lds, device, s);
-    if (P.raw_dtype == kRawF16) return launch_rp<kRawF16>(P, lds, device, s);
-    if (P.raw_dtype == kRawBf16) return launch_rp<kRawBf16>(P, lds, device, s);
-    return hipErrorInvalidValue;
+    P.raw_by_element = raw_rows_by_element(P.raw, P.raw_dtype, P.dim);
+    return dispatch_raw_dtype(P.raw_dtype, [&](auto raw) { return launch_rp<decltype(raw)::value>(P, lds, device, s); });
 }
 
 } // namespace rbq

@@ -3,8 +3,9 @@
 // rebuild k_scan's instantiations and vice versa.
 //   k_query.hip  k_prep / k_prep_wave, k_rank_* , k_select*, k_probes_given     (kernels.hpp, rank_mfma.hpp, canon_score.hpp, select_*.hpp)
 //   k_scan.hip   k_scan<DT, EX, TR>                                               (scan.hpp, scan_codes.hpp, topk.hpp)
-//   k_range.hip  k_range<DT, EX>: the range search's scan against a constant radius     (range.hpp, scan_codes.hpp)
+//   k_range.hip  k_range<DT, EX>: the range search's scan against a constant radius     (range.hpp, range_common.hpp, scan_codes.hpp)
 //   k_range_exact.hip  k_range<0, 0, V, XR, XIP>: the same scan, its matches decided by the raw rows  (range.hpp, rerank_score.hpp)
+//   k_bf_range.hip  brute-force range search: matches counted per span, then placed in id order  (bf_range.hpp, range_common.hpp)
 //   k_build.hip  encoder, reference-layout -> device-layout converters, sorting   (encode.hpp)
 //   k_gemm_shortlist.hip  the front of the GEMM-shortlist paths (finite check, norms, split images, dots), KmGemmAssign (km_common.hpp)
 //   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver         (km_common.hpp)
@@ -19,11 +20,12 @@
 //   k_mstg_search.hip  MSTG search: exact nearest centroids and dynamic_prune               (km_common.hpp, canon_score.hpp)
 //   k_mstg_refine.hip  refined MSTG search: ex-code distances of a candidate pool, unique ids (kernels.hpp, scan_codes.hpp, mstg_pool.hpp)
 //   k_mstg_rerank.hip  exact rerank of the MSTG pool: one entry per id, exact scores from the raw rows (mstg_pool.hpp, rerank_score.hpp)
-//   k_mstg_range.hip  MSTG range search: the estimate against a constant radius in scan order, one entry per id (scan_codes.hpp, mstg_pool.hpp)
-//   k_mstg_range_exact.hip  exact MSTG range search: the distinct candidates scored against the raw rows (mstg_pool.hpp, rerank_score.hpp)
+//   k_mstg_range.hip  MSTG range search: the estimate against a constant radius in scan order, one entry per id (range_common.hpp, scan_codes.hpp)
+//   k_mstg_range_exact.hip  exact MSTG range search: the distinct candidates scored against the raw rows (range_common.hpp, rerank_score.hpp)
 //   k_rerank_pool.hip  pooled rerank: exact scores of a candidate pool from whole lines of the raw rows, order in LDS (rerank_score.hpp)
 //   k_append.hip rbq_index_append: carry of an index into a larger geometry, id bound, nearest list of rotated rows (km_common.hpp)
 //   k_remove.hip rbq_index_remove_ids: keep masks against a sorted id set, slot map, gather of an index into a smaller geometry
+// launch_util.hpp: what the launchers of the range and rerank units share (launch_range_kernel, raw_rows_by_element, dispatch_raw_dtype)
 #pragma once
 #include <atomic>
 #include <string>
@@ -535,17 +537,11 @@ hipError_t launch_mstg_range_distinct(const MstgRangeDistinctParams& P, int devi
 // ---- exact MSTG range search (options mstg_range_exact / mstg_range_exact_bits; k_mstg_range_exact.hip): in
 // place of k_mstg_range_distinct — the scan's rows reduced to one entry per id, every distinct id scored exactly against its raw
 // row (canon_l2 or -canon_dot), kept iff that distance is finite and < X, in scan order
-struct MstgRangeExactParams {
-    const uint64_t* raw_ids;    // [nq][kMstgRangeDistinctMax] the scan's rows at the candidate radius, raw_scores alike,
-    const float* raw_scores;    // raw_counts [nq] their totals
-    const uint32_t* raw_counts;
+struct MstgRangeExactParams : MstgRangeDistinctParams { // (the scan's rows at the candidate radius; the outputs: the exact matches and distances)
     const void* queries;        // [nq][dim] elements of query_dtype, input space (the caller's rows)
     const void* raw;            // [n_raw][dim] elements of raw_dtype, n_raw >= 1
     uint64_t n_raw;
-    uint64_t* out_ids;          // [nq][cap], out_scores [nq][cap] (the exact distances), out_counts [nq]: the exact matches, or
-    float* out_scores;          // UINT32_MAX where the scan's total exceeds kMstgRangeDistinctMax (the row is then empty)
-    uint32_t* out_counts;
-    uint32_t nq, cap, dim, metric;
+    uint32_t dim, metric;
     float X;                     // the exact radius
     int raw_dtype = kRawF32;     // kRawF32 / kRawF16 / kRawBf16
     int query_dtype = kRawF32;   // the same values: what `queries` holds

@@ -3,8 +3,7 @@
 // the identity slot map: entry r of a query is a global slot index (gblock * 32 + lane), ascending by estimate.  One copy of
 //   mp_find_list  the list of an entry among the query's selected lists: its place j in the scan order and its g_add;
 //   mp_rank       the rank of an entry: the contract's order among EQUAL estimates is (list order, vector order);
-//   mr_sort       the bitonic network over two u64 arrays in LDS;
-//   wg_scan_excl  the workgroup's exclusive prefix sum (k_mstg_range.hip, k_mstg_range_exact.hip: DESIGN.md sections 37, 38).
+//   mr_sort       the bitonic network over two u64 arrays in LDS (also under range_common.hpp's distinct-id reduction).
 #pragma once
 #include "kernels.hpp"
 
@@ -58,29 +57,6 @@ __device__ __forceinline__ void mr_sort(unsigned long long* k1, unsigned long lo
             }
         }
     __syncthreads();
-}
-
-// exclusive prefix sum of one value per thread over the workgroup (kThreads = four waves); *total: the sum, on every thread.
-// s_w [kThreads / 64] in LDS; a second scan over the same s_w needs a barrier between the two.
-__device__ __forceinline__ uint32_t wg_scan_excl(uint32_t v, uint32_t* s_w, uint32_t tid, uint32_t* total) {
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63u) s_w[wave] = x;
-    __syncthreads();
-    uint32_t base = 0, sum = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < (uint32_t)(kThreads / 64); ++j) {
-        const uint32_t c = s_w[j];
-        base += j < wave ? c : 0u;
-        sum += c;
-    }
-    *total = sum;
-    return base + x - v;
 }
 
 } // namespace rbq

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "kernels.hpp"
+#include "range_common.hpp"
 #include "scan_codes.hpp"
 #include "rerank_score.hpp"
 
@@ -87,13 +88,9 @@ __global__ __launch_bounds__(kRangeThreads) void k_range(std::conditional_t<XR =
     __syncthreads();
 
     struct Meta { float f_add, f_rescale, f_error, g_add, g_err, dotqc; };
-    // the epilogue's exact operation sequence (k_scan's lb_of: compute_batch_distances_u16, first op fused or not per variant)
+    // k_scan's lb_of: the estimate less its error term
     auto lb_of = [&](const Meta& m, float accu_f, float& ip, float& est) -> float {
-        ip = epi_ip(qc.delta, accu_f, qc.sum_vl, V == kVarPortable);
-        const float tt = ip + qc.k1x;
-        const float rs = m.f_rescale * tt;
-        est = m.f_add + m.g_add;
-        est = est + rs;
+        est = rg_estimate(qc, m.f_add, m.f_rescale, m.g_add, accu_f, V == kVarPortable, ip);
         const float er = m.f_error * m.g_err;
         return est - er;
     };

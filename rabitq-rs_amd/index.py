@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from . import _abi, _marshal
+from . import _abi, _marshal, _range
 from ._abi import READ_FN, WRITE_FN  # noqa: F401  (their home is the prototype table; callers know them by this module)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -524,7 +524,7 @@ class IvfRabitqIndex:
             self.set_option("range_search", 0)
             self.set_option("range_radius_bits", 0x7F800000)
         else:
-            self.set_option("range_radius_bits", int(np.array([radius], np.float32).view(np.int32)[0]))
+            self.set_option("range_radius_bits", _range.f32_bits(radius))
             self.set_option("range_search", 1)
         self._range = radius
 
@@ -539,7 +539,7 @@ class IvfRabitqIndex:
             self.set_option("range_exact", 0)
             self.set_option("range_exact_radius_bits", 0x7F800000)
         else:
-            self.set_option("range_exact_radius_bits", int(np.array([exact_radius], np.float32).view(np.int32)[0]))
+            self.set_option("range_exact_radius_bits", _range.f32_bits(exact_radius))
             self.set_option("range_exact", 1)
         self._range_exact = exact_radius
 
@@ -571,30 +571,8 @@ class IvfRabitqIndex:
             if touch_x:
                 self.set_range_exact(before_x)
 
-    @staticmethod
-    def _filter_words(allowed_ids):
-        allowed = np.asarray(sorted(set(int(i) for i in allowed_ids)), dtype=np.uint64)
-        nbits = int(allowed.max()) + 1 if allowed.size else 0
-        words = np.zeros((nbits + 31) // 32 or 1, np.uint32)
-        if allowed.size:
-            np.bitwise_or.at(words, (allowed >> np.uint64(5)).astype(np.int64),
-                             (np.uint32(1) << (allowed & np.uint64(31)).astype(np.uint32)))
-        return words, nbits
-
-    @staticmethod
-    def _range_csr(ids, scores, counts, sort):
-        """Rows of capacity cap with their totals -> FAISS's (lims [nq + 1], ids, scores); a row holds min(total, cap)."""
-        kept = np.minimum(counts.astype(np.int64), ids.shape[1])
-        lims = np.zeros(len(kept) + 1, np.int64)
-        np.cumsum(kept, out=lims[1:])
-        take = np.arange(ids.shape[1])[None, :] < kept[:, None]
-        out_ids, out_sc = ids[take], scores[take]  # (row-major: rows in query order, scan order inside a row)
-        if sort:
-            for q in range(len(kept)):
-                o = np.argsort(out_sc[lims[q]:lims[q + 1]], kind="stable")  # (score, scan order)
-                out_ids[lims[q]:lims[q + 1]] = out_ids[lims[q]:lims[q + 1]][o]
-                out_sc[lims[q]:lims[q + 1]] = out_sc[lims[q]:lims[q + 1]][o]
-        return lims, out_ids, out_sc
+    _filter_words = staticmethod(_range.filter_words)
+    _range_csr = staticmethod(_range.csr)
 
     def range_search(self, queries, radius, nprobe, max_results=None, allowed_ids=None, want_diag=False, sort=False, dtype=None,
                      exact=False, candidate_radius=None):
@@ -613,12 +591,10 @@ class IvfRabitqIndex:
         from . import SearchParams
         queries, dtype = _marshal.query_arg(queries, dtype)
         words, nbits = self._filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
-        cap = max_results or 1024
         with self._range_for_call(radius, exact, candidate_radius):
-            ids, sc, cnt, diag = self.batch_search_raw(queries, SearchParams(cap, nprobe), words, nbits, want_diag, dtype)
-            if max_results is None and cnt.size and int(cnt.max()) > cap:
-                ids, sc, cnt, diag = self.batch_search_raw(queries, SearchParams(int(cnt.max()), nprobe), words, nbits, want_diag, dtype)
-        out = self._range_csr(ids, sc, cnt, sort)
+            ids, sc, cnt, diag = _range.complete_rows(
+                lambda cap: self.batch_search_raw(queries, SearchParams(cap, nprobe), words, nbits, want_diag, dtype), max_results)
+        out = _range.csr(ids, sc, cnt, sort)
         if max_results is not None:
             out += (cnt,)
         return out + (diag,) if want_diag else out

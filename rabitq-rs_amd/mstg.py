@@ -19,7 +19,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _abi
+from . import _abi, _range
 from ._marshal import ids_arg, owned_bytes, reader_callback, rows_arg, torch_of, writer_callback
 
 NONE = 0xFFFFFFFF  # unused slot of a closure row
@@ -306,10 +306,6 @@ RANGE_DISTINCT_MAX = _abi.MSTG_RANGE_DISTINCT_MAX
 _U32_MAX = 0xFFFFFFFF
 
 
-def _f32_bits(v):
-    return int(np.array([v], np.float32).view(np.int32)[0])
-
-
 @contextlib.contextmanager
 def _mstg_range_exact_for_call(index, exact, x):
     """Context of one range call: with `exact` the handle's options "mstg_range_exact_bits" / "mstg_range_exact" are set to the bits
@@ -323,7 +319,7 @@ def _mstg_range_exact_for_call(index, exact, x):
     _check(lib().rbq_debug_copy_index(index._h, b"mstg_range_exact", C.byref(was), 4))
     _check(lib().rbq_debug_copy_index(index._h, b"mstg_range_exact_bits", C.byref(was_bits), 4))
     try:
-        index.set_option("mstg_range_exact_bits", _f32_bits(x))
+        index.set_option("mstg_range_exact_bits", _range.f32_bits(x))
         index.set_option("mstg_range_exact", 1)
         yield
     finally:
@@ -403,7 +399,6 @@ def mstg_range_search(index, queries, radius, ef_search=150, pruning_epsilon=0.6
     `candidate_radius` (None: +inf); distances are the exact ones (mstg_range_rows' `exact`).  The limit then counts the
     candidates: where a query exceeds it, repeat with a smaller candidate_radius."""
     from . import RabitqError, _marshal
-    from .index import IvfRabitqIndex
     q, dtype = _marshal.query_arg(queries, dtype)
     if _marshal.on_device(q):
         raise ValueError("mstg_range_search takes host queries (mstg_range_rows takes CUDA tensors)")
@@ -416,11 +411,8 @@ def mstg_range_search(index, queries, radius, ef_search=150, pruning_epsilon=0.6
                               % (int(over[0]), RANGE_DISTINCT_MAX, "a smaller candidate_radius" if exact else "distinct=False or a smaller radius"))
         return got
 
-    cap = 1024 if max_results is None else int(max_results)
-    got = call(cap)
-    if max_results is None and got[2].size and int(got[2].max()) > cap:
-        got = call(int(got[2].max()))
-    out = IvfRabitqIndex._range_csr(got[0], got[1], got[2], False)
+    got = _range.complete_rows(call, None) if max_results is None else call(int(max_results))  # (0 is a capacity here: no rows, the totals)
+    out = _range.csr(got[0], got[1], got[2], False)
     if max_results is not None:
         out += (got[2],)
     return out + tuple(got[3:])

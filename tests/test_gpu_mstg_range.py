@@ -66,6 +66,34 @@ def test_capacity_below_the_total(main, distinct):
     assert not zero[2].any() and not none[2].any() and (none[0] == ref.NONE64).all() and np.isnan(none[1]).all()
 
 
+def radius_for_total(est, total):
+    """the radius under which exactly `total` of the estimates `est` match (strictly below it)"""
+    s = np.sort(est)
+    assert total < len(s) and s[total - 1] < s[total]
+    return s[total]
+
+
+@pytest.mark.parametrize("total", [1, 2, 37, ref.DISTINCT_MAX, ref.DISTINCT_MAX + 1])
+def test_distinct_at_its_size_edges(main, total):
+    """the last query's scan matches exactly `total` entries: one, two (the smallest sort), no power of two, the limit (answered)
+    and one more (UINT32_MAX and an empty row); the row without `distinct` is the scan's own, padded from its total"""
+    case, q, idx, lists, counts, cands = main
+    r = radius_for_total(cands[-1][1], total)
+    for distinct in (1, 0):
+        wi, wb, wc, raw = ref.range_rows(cands, r, distinct, CAP)
+        assert raw[-1] == total
+        if distinct:
+            assert wc[-1] == (ref.U32_MAX if total > ref.DISTINCT_MAX else len(np.unique(cands[-1][0][cands[-1][1] < r])))
+        got = bits_of(rq.mstg_range_rows(idx, q, r, CAP, EF, EPS, bool(distinct)))
+        assert np.array_equal(got[2], wc), (got[2], wc)
+        assert np.array_equal(got[0], wi) and np.array_equal(got[1], wb)
+    if total <= 37:  # a capacity equal to the distinct count: the padding starts at the row's end
+        cap = int(ref.range_rows(cands, r, 1, CAP)[2][-1])
+        wi, wb, wc, _ = ref.range_rows(cands, r, 1, cap)
+        got = bits_of(rq.mstg_range_rows(idx, q[-1:], r, cap, EF, EPS, True))
+        assert np.array_equal(got[2], wc[-1:]) and np.array_equal(got[0], wi[-1:]) and np.array_equal(got[1], wb[-1:])
+
+
 def test_errors_are_the_searchs_in_its_order(main):
     case, q, idx, lists, counts, cands = main
     from rabitq_rs_amd import index as ix

@@ -81,6 +81,19 @@ def test_parity_capacity_overflow_and_nan_radius(main, entry):
     call(idx, tq, r, np.nan, want=want_of(x=np.nan))
 
 
+@pytest.mark.parametrize("total", [1, 2, 37, ref.DISTINCT_MAX, ref.DISTINCT_MAX + 1])
+def test_candidates_at_the_size_edges(main, total):
+    """the last query has exactly `total` candidates at r: one, two, no power of two, the limit (answered) and one more
+    (UINT32_MAX and an empty row); x = +inf keeps every scored id, so the dense list and the hit walk run at the same sizes"""
+    case, q, idx, raw, r, x, want_of = main
+    s = np.sort(base(case.metric)[4][-1][1])
+    assert s[total - 1] < s[total]
+    for xx in (np.inf, x):
+        want = want_of(r=s[total], x=xx)
+        assert (want[2][-1] == ref.U32_MAX) == (total > ref.DISTINCT_MAX) and (want[3][-1] >= 1 or total > ref.DISTINCT_MAX)
+        call(idx, q, s[total], xx, want=want)
+
+
 def test_rows_without_a_match_chunks_repeats_and_f16_queries(main):
     case, q, idx, raw, r, x, want_of = main
     want, bad = want_of(), case.x.copy()

@@ -220,6 +220,27 @@ def test_list_shapes(bits):
         built.close()
 
 
+@pytest.mark.parametrize("bits", [1, 7])
+def test_one_long_list_and_a_capacity_inside_a_wave(bits):
+    """One list of 600 vectors (19 blocks: three tiles, the last one partly filled) under the unbounded radius, so every lane of
+    every ballot matches.  Capacity 37 falls inside the first wave's matches of the first tile: some lanes of one ballot write,
+    the others only count.  Capacity = total: the padding starts at the row's end and writes nothing.  -inf: an empty row."""
+    n = 600
+    data = make_dataset(n, 64, 1, 3311)
+    built = rq.builder.train_with_clusters(data, data.mean(0, keepdims=True).astype(F32), np.zeros(n, np.uint32), bits, 0, 1, 3312, True)
+    q = np.ascontiguousarray(data[[3, 599]] + F32(0.01), dtype=F32)
+    idx = rq.IvfRabitqIndex.from_built(built)
+    try:
+        for cap in (37, n, n + 5):
+            ref = _check(idx, built, q, INF, 1, cap=cap, what=f"cap {cap}")
+            assert all(len(x[0]) == n for x in ref)
+        none = _check(idx, built, q, -INF, 1, cap=37, what="no match")
+        assert all(len(x[0]) == 0 for x in none)
+    finally:
+        idx.close()
+        built.close()
+
+
 # ---- 5. filter --------------------------------------------------------------------------------------------------------------------
 def test_filter():
     """about 30 % of the ids, with diagnostics (every candidate's filter bit is tested: no block skip) and without (block skip);
