@@ -39,6 +39,38 @@ int rbq_bf_range_batch(const rbq_bf_index* idx, const float* queries, uint64_t n
  * needs to turn "score > s" into the distance threshold -s above. */
 uint32_t rbq_bf_metric(const rbq_bf_index* idx);
 
+/* ---- exact range search against attached raw vectors ----------------------------------------------------
+ * Raw rows for rbq_bf_range_exact_batch: `vectors` is [n][dim] elements of raw_dtype (RBQ_RAW_F32, RBQ_RAW_F16 or RBQ_RAW_BF16 of
+ * rbq.h), row i the vector of id i — a brute-force index has no id array, an id is a position.  Host memory is copied to the
+ * handle's device; a device pointer on that device is BORROWED: it stays the caller's and must outlive the attachment (memory is
+ * told apart as rbq_bf_train_device tells it).  The library never rounds: a 16-bit element is widened exactly where a kernel loads
+ * it.  NULL detaches (n and raw_dtype are then ignored).
+ * RBQ_INVALID_CONFIG with the detail set, the handle keeping what it had: a null index; an unknown raw_dtype; n != rbq_bf_len(idx)
+ * (these before the first HIP call); a borrowed pointer to 16-bit rows that is not 2-byte aligned.
+ * The handles rbq_bf_append and rbq_bf_remove_ids return carry no raw rows, and RBF1 neither stores nor loads them.
+ * NOT safe concurrently with any other call on the same handle: the old rows are released here. */
+int rbq_bf_set_rerank_vectors(rbq_bf_index* idx, const void* vectors, uint64_t n, int raw_dtype);
+/* RBQ_RAW_* of the attached rows; -1 with none attached, or for a null handle. */
+int rbq_bf_rerank_dtype(const rbq_bf_index* idx);
+
+/* Range search decided by the raw rows.  Per query:
+ *  1. The candidates are exactly the matches of rbq_bf_range_batch at radius = candidate_radius: the estimate is finite and
+ *     < candidate_radius and the filter lets the vector through.  +inf makes every such vector a candidate: a flat exact range
+ *     search.
+ *  2. Every candidate is scored against raw row [id] by the canonical sums (l2_distance_sqr / dot of src/math.rs, bit for bit):
+ *     d = l2_distance_sqr (L2) or -dot (inner product).  It matches iff d is finite and d < x — one rule on the distance for both
+ *     metrics, as in rbq_bf_range_batch.
+ *  3. Rows and counts as rbq_bf_range_batch writes them: matches in ascending id order, out_scores = d (L2) or -d (inner product),
+ *     out_counts[q] the total (it may exceed `capacity`), unused slots UINT64_MAX / NaN, capacity == 0 counts only (the rows may be
+ *     NULL), a capacity above the index's length is legal.  The same call gives the same bytes every time.
+ * Errors, all before the first HIP call: those of rbq_bf_range_batch up to nq == 0 (RBQ_OK) in its order; then RBQ_INVALID_CONFIG
+ * with the detail set when no raw vectors are attached — nothing is silently approximated; then the remaining checks of
+ * rbq_bf_range_batch, a NaN `x` and a NaN `candidate_radius` refused.  Re-entrant on one handle like rbq_bf_range_batch (but not
+ * with rbq_bf_set_rerank_vectors).  Never aborts: device failures are RBQ_DEVICE. */
+int rbq_bf_range_exact_batch(const rbq_bf_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t capacity, float x,
+                             float candidate_radius, const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids,
+                             float* out_scores, uint32_t* out_counts);
+
 #ifdef __cplusplus
 }
 #endif

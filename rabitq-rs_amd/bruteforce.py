@@ -45,6 +45,7 @@ class BruteForceRabitqIndex:
     def __init__(self, handle, rescale=None):
         self._h = handle
         self._rescale = rescale  # (mode, t_const) the encoder ran with, where this object knows it: add()'s default
+        self._raw_keep = None    # the CUDA tensor the handle borrows its raw vectors from (set_rerank_vectors)
 
     @staticmethod
     def _dev(device):
@@ -177,10 +178,12 @@ class BruteForceRabitqIndex:
         return [self._results(ids, scores, counts, q) for q in range(ids.shape[0])]
 
     # -- range search (include/ext/rbq_bf_range.h) ------------------------------------------------
-    def range_rows(self, queries, radius, capacity, filter_words=None, filter_nbits=0):
+    def range_rows(self, queries, radius, capacity, filter_words=None, filter_nbits=0, exact_x=None):
         """rbq_bf_range_batch as it is: (ids [nq, capacity] u64, scores [nq, capacity] f32, totals [nq] u32).  `radius` is the
         C entry's threshold on the DISTANCE (inner product: minus the score); a row holds the first min(total, capacity)
-        matches in id order, the other slots are UINT64_MAX / NaN.  capacity 0 counts only."""
+        matches in id order, the other slots are UINT64_MAX / NaN.  capacity 0 counts only.
+        exact_x (not None): rbq_bf_range_exact_batch as it is — `radius` is its candidate_radius, exact_x its x, both thresholds on
+        the distance; the scores are exact (raw vectors attached with set_rerank_vectors)."""
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -189,31 +192,89 @@ class BruteForceRabitqIndex:
         ids, scores = np.empty((nq, cap), np.uint64), np.empty((nq, cap), np.float32)
         totals = np.zeros(nq, np.uint32)
         fw = np.ascontiguousarray(filter_words, dtype=np.uint32) if filter_words is not None else None
-        _check(lib_ext().rbq_bf_range_batch(self._h, q.ctypes.data, nq, qd, cap, float(radius), fw.ctypes.data if fw is not None else None,
-                                            int(filter_nbits), ids.ctypes.data if cap else None, scores.ctypes.data if cap else None,
-                                            totals.ctypes.data))
+        tail = (fw.ctypes.data if fw is not None else None, int(filter_nbits), ids.ctypes.data if cap else None,
+                scores.ctypes.data if cap else None, totals.ctypes.data)
+        if exact_x is None:
+            _check(lib_ext().rbq_bf_range_batch(self._h, q.ctypes.data, nq, qd, cap, float(radius), *tail))
+        else:
+            _check(lib_ext().rbq_bf_range_exact_batch(self._h, q.ctypes.data, nq, qd, cap, float(exact_x), float(radius), *tail))
         return ids, scores, totals
 
     def _distance_radius(self, radius):
         """The user's radius (L2: distance < radius; inner product: score > radius) as the C entry's distance threshold."""
         return -float(radius) if lib_ext().rbq_bf_metric(self._h) == _abi.METRIC_IP else float(radius)
 
-    def range_search(self, queries, radius, max_results=None, allowed_ids=None, sort=False):
+    def _radii(self, radius, exact, candidate_radius):
+        """(range_rows' radius, its exact_x) of a search by the user's `radius`.  exact: `radius` is the exact x and
+        `candidate_radius` (the user's convention too; None: every vector) bounds the estimates that are scored."""
+        from . import RabitqError
+        if not exact:
+            if candidate_radius is not None:
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "candidate_radius needs exact=True")
+            return self._distance_radius(radius), None
+        return (float("inf") if candidate_radius is None else self._distance_radius(candidate_radius)), self._distance_radius(radius)
+
+    def range_search(self, queries, radius, max_results=None, allowed_ids=None, sort=False, exact=False, candidate_radius=None):
         """FAISS-style range_search over every vector of the index: (lims [nq + 1] i64, ids u64, scores f32) — query q's matches
         are ids[lims[q]:lims[q + 1]], ascending by id, or by (score, id) with sort=True.  A match has distance < radius (L2) or
         score > radius (inner product).  max_results=None: complete rows (a first call with rows of 1024; where a total exceeds
         that, one more with rows of the largest total — the totals are exact, so one repeat suffices).  max_results=m: at most the
-        first m matches of every query, and the totals [nq] u32 as a fourth value.  `allowed_ids` as search_filtered."""
+        first m matches of every query, and the totals [nq] u32 as a fourth value.  `allowed_ids` as search_filtered.
+        exact=True (raw vectors attached with set_rerank_vectors): `radius` is the EXACT radius — a match has
+        its exact distance < radius (score > radius) among the vectors whose estimate is within `candidate_radius`, given like
+        `radius`; None scores every vector, a flat exact range search.  The scores are the exact ones."""
         words, nbits = _filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
-        r = self._distance_radius(radius)
-        ids, sc, cnt = _range.complete_rows(lambda cap: self.range_rows(queries, r, cap, words, nbits), max_results)
+        r, x = self._radii(radius, exact, candidate_radius)
+        ids, sc, cnt = _range.complete_rows(lambda cap: self.range_rows(queries, r, cap, words, nbits, x), max_results)
         out = _range.csr(ids, sc, cnt, sort)
         return out + (cnt,) if max_results is not None else out
 
-    def count_in_range(self, queries, radius, allowed_ids=None):
+    def count_in_range(self, queries, radius, allowed_ids=None, exact=False, candidate_radius=None):
         """The number of matches of range_search for every query ([nq] u32), without their rows (capacity 0)."""
         words, nbits = _filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
-        return self.range_rows(queries, self._distance_radius(radius), 0, words, nbits)[2]
+        r, x = self._radii(radius, exact, candidate_radius)
+        return self.range_rows(queries, r, 0, words, nbits, x)[2]
+
+    def set_rerank_vectors(self, x, dtype=None):
+        """Attach the raw vectors the exact range search scores against (rbq_bf_set_rerank_vectors): [len(self)][dim], row i the
+        vector of id i.  A float32 or numpy.float16 array is copied to the device as it is; a uint16 array holds bit patterns and
+        needs dtype "f16" or "bf16"; a CUDA tensor (float32, float16, bfloat16) on the index's device is BORROWED and kept alive by
+        this object; None detaches.  The library never rounds: "f16" with float32 host data converts with astype(numpy.float16),
+        the caller's rounding.  add and remove_ids leave the object without vectors."""
+        from . import RabitqError
+        if x is None:
+            _check(lib_ext().rbq_bf_set_rerank_vectors(self._h, None, 0, _abi.RAW_F32))
+            self._raw_keep = None
+            return
+        if dtype is not None and dtype not in _abi.RAW_DTYPES:
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "unknown rerank dtype %r (one of %s)" % (dtype, ", ".join(_abi.RAW_DTYPES)))
+        code = None if dtype is None else _abi.RAW_DTYPES[dtype]
+        torch = _marshal.torch_of(x)
+        if torch is not None:
+            kinds = {torch.float32: _abi.RAW_F32, torch.float16: _abi.RAW_F16, torch.bfloat16: _abi.RAW_BF16}
+            want = {c: t for t, c in kinds.items()}[kinds.get(x.dtype, _abi.RAW_F32) if code is None else code]
+            v = x.to(dtype=want).contiguous()
+            code = kinds[want]
+            if not v.is_cuda:  # (NumPy has no bf16: its rows go as their bit patterns)
+                v = v.view(torch.uint16).numpy() if code == _abi.RAW_BF16 else v.numpy()
+        elif isinstance(x, np.ndarray) and x.dtype == np.uint16:
+            if code not in (_abi.RAW_F16, _abi.RAW_BF16):
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, 'uint16 rows are bit patterns: pass dtype="f16" or dtype="bf16"')
+            v = np.ascontiguousarray(x)
+        else:
+            if code is None:
+                code = _abi.RAW_F16 if isinstance(x, np.ndarray) and x.dtype == np.float16 else _abi.RAW_F32
+            if code == _abi.RAW_BF16:
+                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "bf16 rows on the host are a uint16 array of bit patterns")
+            v = np.ascontiguousarray(x, dtype=np.float16 if code == _abi.RAW_F16 else np.float32)
+        if v.ndim != 2 or v.shape[1] != self.dim:
+            raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "rerank vectors must be [len][%d]" % self.dim)
+        _check(lib_ext().rbq_bf_set_rerank_vectors(self._h, C.c_void_p(_marshal.data_ptr(v)), int(v.shape[0]), code))
+        self._raw_keep = v if _marshal.on_device(v) else None  # (host rows were copied; a device tensor is read in place)
+
+    def rerank_dtype(self):
+        """"f32" / "f16" / "bf16": the element type of the attached raw vectors; None with nothing attached."""
+        return {i: n for n, i in _abi.RAW_DTYPES.items()}.get(lib_ext().rbq_bf_rerank_dtype(self._h))
 
     # -- growth, shrinking and read-back (include/rbq_bf_mutate.h) ----------------------------------------------------
     def add(self, data, rescale=None, t_const=None, max_chunk_rows=0):
@@ -237,9 +298,10 @@ class BruteForceRabitqIndex:
         return first
 
     def _swap(self, h):
-        """The handle a mutation returned takes the place of the old one, which is closed."""
+        """The handle a mutation returned takes the place of the old one, which is closed; the new one carries no raw vectors."""
         old, self._h = self._h, h
         lib().rbq_bf_destroy(old)
+        self._raw_keep = None
 
     def remove_ids(self, ids):
         """FAISS IndexFlat-style remove_ids (rbq_bf_remove_ids): the vectors at the positions `ids` (a host array, a list, or a

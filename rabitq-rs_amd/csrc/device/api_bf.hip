@@ -1,7 +1,8 @@
 // api_bf.hip — brute-force index (rbq_bf_*): BruteForceRabitqIndex, reference src/brute_force.rs.
 // Host side: validation, upload, training on the device (rbq_bf_train_device), RBF1 in / out, and per search call: queries -> k_prep (rotation + QueryPrecomputed constants, shared with
 // the IVF path) -> for each chunk of vectors k_bf_dist + k_bf_select (bf.hpp) -> results; the range search (rbq_bf_range_batch)
-// runs k_bf_range_count + k_bf_range_place (bf_range.hpp) behind k_bf_dist instead.  Each call takes a workspace and a stream
+// runs k_bf_range_count + k_bf_range_place (bf_range.hpp) behind k_bf_dist instead, the exact one (rbq_bf_range_exact_batch, raw rows
+// attached with rbq_bf_set_rerank_vectors) k_bf_range_exact (bf_range_exact.hpp) in k_bf_range_count's place.  Each call takes a workspace and a stream
 // of its own from the handle's pool, so calls on one handle may overlap.
 #include "bf_index.hpp"
 #include "ext/rbq_bf_range.h"
@@ -26,6 +27,7 @@ void bf_free(rbq_bf_index* ix) {
     (void)hipDeviceSynchronize();
     for (Arr* a : {&ix->rot_blob, &ix->bin, &ix->ex}) if (a->p) (void)hipFree(a->p);
     for (Arr& a : ix->f) if (a.p) (void)hipFree(a.p);
+    if (ix->raw.p && !ix->raw_borrowed) (void)hipFree(ix->raw.p);
     for (BfWorkspace* w : ix->pool) delete w;
     delete ix;
 }
@@ -271,8 +273,11 @@ int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t
 // rbq_bf_range_batch (include/ext/rbq_bf_range.h): the search's plan without its heap — k_prep, then per chunk
 // of vectors k_bf_dist -> k_bf_range_count -> k_bf_range_place (bf_range.hpp), the totals carried from chunk to chunk in two arrays
 // that alternate.  The sub-batch comes from the distance budget and, with rows, the output budget.
-int bf_range_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t capacity, float radius, const uint32_t* filter_words,
-                  uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+// exact_x (rbq_bf_range_exact_batch; null: the estimate decides): `radius` is the candidate radius,
+// k_bf_range_exact (bf_range_exact.hpp) stands in k_bf_range_count's place — it scores the candidates against the handle's raw rows
+// and writes the exact distances over the workspace — and k_bf_range_place runs at the radius *exact_x.  Everything else is one copy.
+int bf_range_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t capacity, float radius, const float* exact_x,
+                  const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
     const uint64_t n = ix->hdr.n_vectors;
     const uint32_t dim = ix->hdr.dim;
     const uint64_t limit = g_bf_chunk_vectors.load(std::memory_order_relaxed); // (test hook: read once per call)
@@ -300,11 +305,19 @@ int bf_range_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t 
             HIP_TRY(launch_bf_dist(bf_dist_params(ix, w, m, v0, nv, d_filter, filter_nbits), st));
             BfRangeParams rp;
             rp.dist = (const float*)w->dist.p; rp.nq = m; rp.n_spans = (uint32_t)((nv + kBfRangeSpan - 1) / kBfRangeSpan);
-            rp.v0 = v0; rp.nv = nv; rp.radius = radius; rp.metric = ix->hdr.metric; rp.first = c == 0; rp.last = c + 1 == n_chunks;
+            rp.v0 = v0; rp.nv = nv; rp.radius = exact_x ? *exact_x : radius; rp.metric = ix->hdr.metric; rp.first = c == 0; rp.last = c + 1 == n_chunks;
             rp.capacity = (uint32_t)cap; rp.span_counts = (uint32_t*)w->span_counts.p;
             rp.run_in = (const uint32_t*)w->running.p + (c & 1) * sub; rp.run_out = (uint32_t*)w->running.p + ((c + 1) & 1) * sub;
             rp.out_ids = (uint64_t*)w->ids.p; rp.out_scores = (float*)w->scores.p; rp.out_counts = (uint32_t*)w->counts.p;
-            HIP_TRY(launch_bf_range_count(rp, st));
+            if (exact_x) {
+                BfRangeExactParams xp;
+                xp.dist = (float*)w->dist.p; xp.queries = (const float*)w->q.p; xp.raw = ix->raw.p; xp.nq = m; xp.n_spans = rp.n_spans;
+                xp.dim = dim; xp.v0 = v0; xp.nv = nv; xp.candidate_radius = radius; xp.x = *exact_x; xp.metric = ix->hdr.metric;
+                xp.raw_dtype = ix->raw_dtype; xp.span_counts = rp.span_counts;
+                HIP_TRY(launch_bf_range_exact(xp, st));
+            } else {
+                HIP_TRY(launch_bf_range_count(rp, st));
+            }
             HIP_TRY(launch_bf_range_place(rp, st));
         }
         if (cap == capacity && cap) {
@@ -446,8 +459,11 @@ int rbq_bf_search_batch(const rbq_bf_index* ch, const float* queries, uint64_t n
     RBQ_GUARD_END
 }
 
-int rbq_bf_range_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t capacity, float radius,
-                       const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+// The checks of the two range entries, in their order, then the call.  exact_x null: rbq_bf_range_batch at `radius`; else
+// rbq_bf_range_exact_batch with `radius` its candidate radius.
+static int bf_range_entry(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t capacity, float radius,
+                          const float* exact_x, const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores,
+                          uint32_t* out_counts) {
     g_err.clear();
     RBQ_GUARD_BEGIN
     if (!ch) return fail(RBQ_INVALID_CONFIG, "null index");
@@ -459,12 +475,77 @@ int rbq_bf_range_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq
         return fail(RBQ_DIMENSION_MISMATCH, b);
     }
     if (nq == 0) return RBQ_OK;
+    if (exact_x && !ix->raw.p) return fail(RBQ_INVALID_CONFIG, "exact range search needs raw vectors attached (rbq_bf_set_rerank_vectors)");
     if (nq >= (1ull << 31)) return fail(RBQ_INVALID_CONFIG, "nq >= 2^31");
     if (!queries || !out_counts || (capacity && (!out_ids || !out_scores))) return fail(RBQ_INVALID_CONFIG, "null buffer");
-    if (radius != radius) return fail(RBQ_INVALID_CONFIG, "radius is NaN");
+    if (exact_x && *exact_x != *exact_x) return fail(RBQ_INVALID_CONFIG, "x is NaN");
+    if (radius != radius) return fail(RBQ_INVALID_CONFIG, exact_x ? "candidate_radius is NaN" : "radius is NaN");
     DeviceGuard g(ix->device);
     if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
-    return bf_range_impl(ix, queries, nq, capacity, radius, filter_words, filter_nbits, out_ids, out_scores, out_counts);
+    return bf_range_impl(ix, queries, nq, capacity, radius, exact_x, filter_words, filter_nbits, out_ids, out_scores, out_counts);
     RBQ_GUARD_END
 }
+
+int rbq_bf_range_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t capacity, float radius,
+                       const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+    return bf_range_entry(ch, queries, nq, query_dim, capacity, radius, nullptr, filter_words, filter_nbits, out_ids, out_scores, out_counts);
+}
+
+int rbq_bf_range_exact_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t capacity, float x,
+                             float candidate_radius, const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids,
+                             float* out_scores, uint32_t* out_counts) {
+    return bf_range_entry(ch, queries, nq, query_dim, capacity, candidate_radius, &x, filter_words, filter_nbits, out_ids, out_scores,
+                          out_counts);
+}
+
+// Raw rows for the exact range search.  n and the dtype are checked before the first HIP call; the alignment
+// of a borrowed 16-bit pointer as soon as the memory is known to be the device's.  The new copy exists before the old rows go, so a
+// failure leaves the handle as it was.
+int rbq_bf_set_rerank_vectors(rbq_bf_index* ix, const void* vectors, uint64_t n, int raw_dtype) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    if (!ix) return fail(RBQ_INVALID_CONFIG, "null index");
+    const bool attach = vectors != nullptr;
+    if (attach) {
+        if (raw_dtype != RBQ_RAW_F32 && raw_dtype != RBQ_RAW_F16 && raw_dtype != RBQ_RAW_BF16)
+            return fail(RBQ_INVALID_CONFIG, "rerank vectors: unknown raw dtype " + std::to_string(raw_dtype));
+        if (n != ix->hdr.n_vectors)
+            return fail(RBQ_INVALID_CONFIG, "rerank vectors: " + std::to_string(n) + " rows for an index of " + std::to_string(ix->hdr.n_vectors) +
+                                                " vectors (ids are positions)");
+    }
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    Arr fresh;
+    bool borrowed = false;
+    if (attach && n) {
+        const size_t bytes = (size_t)n * ix->hdr.dim * raw_elem_bytes(raw_dtype);
+        hipPointerAttribute_t a;
+        const bool on_dev = hipPointerGetAttributes(&a, vectors) == hipSuccess && a.type == hipMemoryTypeDevice;
+        if (!on_dev) (void)hipGetLastError();
+        if (on_dev && a.device == ix->device) { // borrowed: stays the caller's, must outlive the attachment
+            if (raw_dtype != RBQ_RAW_F32 && (reinterpret_cast<uintptr_t>(vectors) & 1u))
+                return fail(RBQ_INVALID_CONFIG, "rerank vectors: a device pointer to 16-bit rows must be 2-byte aligned");
+            fresh.p = const_cast<void*>(vectors); fresh.bytes = bytes; borrowed = true;
+        } else {
+            int rc = alloc_arr(fresh, bytes);
+            if (rc) return rc;
+            const hipError_t e = hipMemcpy(fresh.p, vectors, bytes, on_dev ? hipMemcpyDefault : hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                (void)hipFree(fresh.p);
+                return fail(RBQ_DEVICE, std::string("attaching the rerank vectors: ") + hipGetErrorString(e));
+            }
+        }
+    }
+    const hipError_t e = hipDeviceSynchronize(); // (the old rows go: not safe concurrently with calls on the handle)
+    if (e != hipSuccess) {
+        if (fresh.p && !borrowed) (void)hipFree(fresh.p);
+        return fail(RBQ_DEVICE, std::string("hipDeviceSynchronize: ") + hipGetErrorString(e));
+    }
+    if (ix->raw.p && !ix->raw_borrowed) (void)hipFree(ix->raw.p);
+    ix->raw = fresh; ix->n_raw = fresh.p ? n : 0; ix->raw_borrowed = borrowed; ix->raw_dtype = fresh.p ? raw_dtype : RBQ_RAW_F32;
+    return RBQ_OK;
+    RBQ_GUARD_END
+}
+
+int rbq_bf_rerank_dtype(const rbq_bf_index* idx) { return idx && idx->raw.p ? idx->raw_dtype : -1; }
 } // extern "C"

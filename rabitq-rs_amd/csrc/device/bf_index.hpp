@@ -22,6 +22,12 @@ struct rbq_bf_index : rbq_api::Geometry {
     std::vector<uint8_t> blob;         // host copy of the rotator (RBF1 writer)
     uint64_t ex_len = 0;               // bytes of ex code per vector as the index holds them (rbq_bf_view::ex_len)
     rbq_api::Arr rot_blob, bin, ex, f[8]; // f: delta, vl, f_add, f_rescale, f_error, residual_norm, f_add_ex, f_rescale_ex
+    // raw rows for the exact range search (rbq_bf_set_rerank_vectors): [n_raw][dim] elements of raw_dtype,
+    // row i the vector of id i; n_raw == hdr.n_vectors while attached.  Borrowed: the caller's device memory, never freed here.
+    rbq_api::Arr raw;
+    uint64_t n_raw = 0;
+    int raw_dtype = RBQ_RAW_F32;
+    bool raw_borrowed = false;
     std::mutex mu;
     std::vector<rbq_api::BfWorkspace*> pool;
     std::atomic<uint64_t> pushes{0}, tie_pushes{0};

@@ -23,28 +23,10 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
-#include "range_common.hpp" // rg_pad_row
+#include "bf_range_span.hpp" // kBfRangeThreads / Rounds / Waves, bf_range_load, bf_range_hit: shared with k_bf_range_exact
+#include "range_common.hpp"  // rg_pad_row
 
 namespace rbq {
-
-constexpr uint32_t kBfRangeThreads = 256;
-constexpr uint32_t kBfRangeRounds = kBfRangeSpan / kBfRangeThreads; // 256-vector rounds of a span: the loads a lane has in flight
-constexpr uint32_t kBfRangeWaves = kBfRangeThreads / 64;
-static_assert(kBfRangeSpan % kBfRangeThreads == 0, "a span is a whole number of 256-vector rounds");
-
-// the lane's kBfRangeRounds distances of its span (NaN past the chunk's end), all loads issued before any is used
-__device__ __forceinline__ void bf_range_load(const BfRangeParams& P, uint32_t q, uint32_t span, uint32_t tid, float (&dv)[kBfRangeRounds]) {
-    const float* row = P.dist + (size_t)q * P.nv;
-    const uint64_t s0 = (uint64_t)span * kBfRangeSpan;
-#pragma unroll
-    for (uint32_t u = 0; u < kBfRangeRounds; ++u) {
-        const uint64_t i = s0 + kBfRangeThreads * u + tid;
-        dv[u] = i < P.nv ? row[i] : __int_as_float(0x7fc00000);
-    }
-}
-
-// the match rule, for both metrics: finite and below the radius (never true against a NaN distance)
-__device__ __forceinline__ bool bf_range_hit(float d, float r) { return finite_f(d) && d < r; }
 
 // grid: (n_spans, nq); block kBfRangeThreads
 __global__ __launch_bounds__(kBfRangeThreads) void k_bf_range_count(BfRangeParams P) {

@@ -6,6 +6,7 @@
 //   k_range.hip  k_range<DT, EX>: the range search's scan against a constant radius     (range.hpp, range_common.hpp, scan_codes.hpp)
 //   k_range_exact.hip  k_range<0, 0, V, XR, XIP>: the same scan, its matches decided by the raw rows  (range.hpp, rerank_score.hpp)
 //   k_bf_range.hip  brute-force range search: matches counted per span, then placed in id order  (bf_range.hpp, range_common.hpp)
+//   k_bf_range_exact.hip  exact brute-force range search: a span's candidates scored against the raw rows  (bf_range_exact.hpp, rerank_score.hpp)
 //   k_build.hip  encoder, reference-layout -> device-layout converters, sorting   (encode.hpp)
 //   k_gemm_shortlist.hip  the front of the GEMM-shortlist paths (finite check, norms, split images, dots), KmGemmAssign (km_common.hpp)
 //   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver         (km_common.hpp)
@@ -324,6 +325,24 @@ struct BfRangeParams {
 };
 hipError_t launch_bf_range_count(const BfRangeParams& p, hipStream_t s);
 hipError_t launch_bf_range_place(const BfRangeParams& p, hipStream_t s); // after launch_bf_range_count on the same stream
+// exact brute-force range search (bf_range_exact.hpp, k_bf_range_exact.hip): in launch_bf_range_count's
+// place.  The estimates below candidate_radius are candidates; each is scored against its raw row, and the exact distance is
+// written over the estimate (NaN over every other entry), so that launch_bf_range_place at radius = x places the exact matches.
+constexpr uint32_t kBfRangeExactMaxDim = 2048; // the query row staged in LDS: 8 KiB
+struct BfRangeExactParams {
+    float* dist;               // [nq][nv] (launch_bf_dist): estimates in; exact distances of the candidates, NaN elsewhere, out
+    const float* queries;      // [nq][dim] f32, input space
+    const void* raw;           // [v0 + nv ..][dim] elements of raw_dtype: row i belongs to vector id i
+    uint32_t nq, n_spans, dim; // n_spans = ceil(nv / kBfRangeSpan)
+    uint64_t v0, nv;
+    float candidate_radius;    // a candidate: finite estimate < candidate_radius
+    float x;                   // a match: finite exact distance < x
+    int metric;
+    int raw_dtype;             // kRawF32 / kRawF16 / kRawBf16
+    uint32_t raw_by_element = 0; // set by the launch (raw_rows_by_element)
+    uint32_t* span_counts;     // [nq][n_spans]: the exact matches of every span, for the place launch
+};
+hipError_t launch_bf_range_exact(const BfRangeExactParams& p, hipStream_t s);
 // k_bf_train.hip: BruteForceRabitqIndex::train.  launch_bf_encode: k_encode's flat mode over P.nslots rotated rows (see
 // EncodeParams; P.t_row != null: the per-vector rescale factors of launch_rescale).  launch_bf_pack_ex: raw ex codes [nrows][D]
 // u8 -> the crate's ex_code_packed [nrows][D * ex_bits / 8] (ex_bits 2 or 6)

@@ -54,6 +54,27 @@ def kernel_table(a):
     print(json.dumps(rec))
 
 
+def exact_legs(a, idx, rows, q, rec):
+    """--exact: rbq_bf_range_exact_batch over the training rows attached as f32 and as f16 (borrowed device
+    tensors), x at the median over the batch of the --kth smallest exact distance, the candidate radius at x, 1.05 x and +inf (every
+    vector scored: three windows of one call), each next to the estimate-only range_rows at the same radius in the same run."""
+    import torch
+    d2 = torch.cdist(torch.from_numpy(q).cuda(), rows).square_()
+    x = float(d2.kthvalue(a.kth, dim=1).values.median())
+    del d2
+    rec["exact_x"] = x
+    for name, r in (("r_1.00x", x), ("r_1.05x", 1.05 * x), ("r_inf", float("inf"))):
+        n_win, calls = (a.windows, a.calls) if np.isfinite(r) else (min(a.windows, 3), 1)
+        rec["estimate_" + name] = dict(windows(lambda: idx.range_rows(q, r, a.capacity), n_win, calls),
+                                       candidates_median=int(np.median(idx.count_in_range(q, r))))
+        for raw, stored in (("f32", rows), ("f16", rows.half())):
+            idx.set_rerank_vectors(stored)
+            leg = windows(lambda: idx.range_rows(q, r, a.capacity, exact_x=x), n_win, calls)
+            leg["matches_median"] = int(np.median(idx.range_rows(q, r, 0, exact_x=x)[2]))
+            rec["exact_%s_%s" % (raw, name)] = leg
+            idx.set_rerank_vectors(None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=200_000)
@@ -65,6 +86,7 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--calls", type=int, default=3)
     ap.add_argument("--seed", type=int, default=20261019)
+    ap.add_argument("--exact", action="store_true", help="the legs of the exact range search instead (see exact_legs)")
     ap.add_argument("--kernel-table", default=None, metavar="DIR", help="no run: tabulate the kernel trace under DIR (see kernel_table)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
@@ -79,17 +101,21 @@ def main():
     idx = rq.BruteForceRabitqIndex.train_on_device(x, a.bits, 0, 1, a.seed, True)  # (L2, FHT-Kac rotator, faster config)
     rng = np.random.default_rng(a.seed)
     q = (x[torch.from_numpy(rng.integers(0, a.n, a.batch)).cuda()].cpu().numpy() + 0.5 * rng.standard_normal((a.batch, a.dim))).astype(np.float32)
-    del x
+    if not a.exact:
+        del x
     _, d, cnt = idx.batch_search_raw(q, rq.BruteForceSearchParams(a.kth))
     radius = float(np.median(d[cnt >= a.kth, a.kth - 1]))
     totals = idx.count_in_range(q, radius).astype(np.int64)
     rec = {"tool": "bf_range_rate", "n": a.n, "dim": a.dim, "bits": a.bits, "metric": "l2", "batch": a.batch, "kth": a.kth, "radius": radius,
            "capacity": a.capacity, "windows": a.windows, "calls": a.calls, "matches_median": int(np.median(totals)),
            "matches_max": int(totals.max()), "rows_cut": int((totals > a.capacity).sum())}
-    rec["range_rows"] = windows(lambda: idx.range_rows(q, radius, a.capacity), a.windows, a.calls)
-    rec["count_in_range"] = windows(lambda: idx.count_in_range(q, radius), a.windows, a.calls)
-    for k in (100, 1024):
-        rec["search_top_k_%d" % k] = windows(lambda: idx.batch_search_raw(q, rq.BruteForceSearchParams(k)), a.windows, a.calls)
+    if a.exact:
+        exact_legs(a, idx, x, q, rec)
+    else:
+        rec["range_rows"] = windows(lambda: idx.range_rows(q, radius, a.capacity), a.windows, a.calls)
+        rec["count_in_range"] = windows(lambda: idx.count_in_range(q, radius), a.windows, a.calls)
+        for k in (100, 1024):
+            rec["search_top_k_%d" % k] = windows(lambda: idx.batch_search_raw(q, rq.BruteForceSearchParams(k)), a.windows, a.calls)
     idx.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
