@@ -86,6 +86,31 @@ def query_arg(queries, dtype=None):
     return np.ascontiguousarray(queries, dtype=np.float16 if code == _abi.RAW_F16 else np.float32), code
 
 
+RAW_DTYPE_NAMES = {code: name for name, code in _abi.RAW_DTYPES.items()}  # RBQ_RAW_* -> "f32" / "f16" / "bf16" (rerank_dtype)
+
+
+def raw_dtype_code(dtype, codes=True):
+    """RBQ_RAW_* of set_rerank_vectors' `dtype`: a name of _abi.RAW_DTYPES or, with `codes`, an RBQ_RAW_* value as it is (the
+    library checks it)."""
+    if dtype in _abi.RAW_DTYPES:
+        return _abi.RAW_DTYPES[dtype]
+    if isinstance(dtype, str) or not codes:
+        from . import RabitqError
+        raise RabitqError(_abi.RBQ_INVALID_CONFIG, "unknown rerank dtype %r (one of %s)" % (dtype, ", ".join(_abi.RAW_DTYPES)))
+    return int(dtype)
+
+
+def raw_rows_host(x, code):
+    """The contiguous host array to pass for raw rows of RBQ_RAW_* `code`: bf16 takes a uint16 array of bit patterns (NumPy has no
+    bf16), f16 converts with astype(numpy.float16) (the caller's rounding: the library never rounds), anything else becomes f32."""
+    if code == _abi.RAW_BF16:
+        if not (isinstance(x, np.ndarray) and x.dtype == np.uint16):
+            from . import RabitqError
+            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "bf16 rows on the host are a uint16 array of bit patterns")
+        return np.ascontiguousarray(x)
+    return np.ascontiguousarray(x, dtype=np.float16 if code == _abi.RAW_F16 else np.float32)
+
+
 def data_ptr(x):
     """The address of the first element of what query_arg returned."""
     return int(x.data_ptr()) if torch_of(x) is not None else int(x.ctypes.data)

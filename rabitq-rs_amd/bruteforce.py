@@ -246,9 +246,7 @@ class BruteForceRabitqIndex:
             _check(lib_ext().rbq_bf_set_rerank_vectors(self._h, None, 0, _abi.RAW_F32))
             self._raw_keep = None
             return
-        if dtype is not None and dtype not in _abi.RAW_DTYPES:
-            raise RabitqError(_abi.RBQ_INVALID_CONFIG, "unknown rerank dtype %r (one of %s)" % (dtype, ", ".join(_abi.RAW_DTYPES)))
-        code = None if dtype is None else _abi.RAW_DTYPES[dtype]
+        code = None if dtype is None else _marshal.raw_dtype_code(dtype, codes=False)
         torch = _marshal.torch_of(x)
         if torch is not None:
             kinds = {torch.float32: _abi.RAW_F32, torch.float16: _abi.RAW_F16, torch.bfloat16: _abi.RAW_BF16}
@@ -264,9 +262,7 @@ class BruteForceRabitqIndex:
         else:
             if code is None:
                 code = _abi.RAW_F16 if isinstance(x, np.ndarray) and x.dtype == np.float16 else _abi.RAW_F32
-            if code == _abi.RAW_BF16:
-                raise RabitqError(_abi.RBQ_INVALID_CONFIG, "bf16 rows on the host are a uint16 array of bit patterns")
-            v = np.ascontiguousarray(x, dtype=np.float16 if code == _abi.RAW_F16 else np.float32)
+            v = _marshal.raw_rows_host(x, code)
         if v.ndim != 2 or v.shape[1] != self.dim:
             raise RabitqError(_abi.RBQ_DIMENSION_MISMATCH, "rerank vectors must be [len][%d]" % self.dim)
         _check(lib_ext().rbq_bf_set_rerank_vectors(self._h, C.c_void_p(_marshal.data_ptr(v)), int(v.shape[0]), code))
@@ -274,7 +270,7 @@ class BruteForceRabitqIndex:
 
     def rerank_dtype(self):
         """"f32" / "f16" / "bf16": the element type of the attached raw vectors; None with nothing attached."""
-        return {i: n for n, i in _abi.RAW_DTYPES.items()}.get(lib_ext().rbq_bf_rerank_dtype(self._h))
+        return _marshal.RAW_DTYPE_NAMES.get(lib_ext().rbq_bf_rerank_dtype(self._h))
 
     # -- growth, shrinking and read-back (include/rbq_bf_mutate.h) ----------------------------------------------------
     def add(self, data, rescale=None, t_const=None, max_chunk_rows=0):

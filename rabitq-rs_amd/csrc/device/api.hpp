@@ -488,6 +488,28 @@ struct ReplicaOwner { // frees a half-built replica on an early return
     ~ReplicaOwner() { if (ix) free_replica(ix); }
     Replica* release() { Replica* r = ix; ix = nullptr; return r; }
 };
+// Raw rows attached to a handle (rbq_index_set_rerank_vectors, rbq_bf_set_rerank_vectors).  The caller's pointer is classified once
+// per call; raw_rows_on then gives ONE device (the current one) its rows: the caller's memory itself where it is that device's
+// (borrowed: never freed here), else a fresh allocation filled from it, freed again if the copy fails.  raw_rows_drop frees rows
+// that are not borrowed; raw_rows_swap puts `fresh` (empty: detach) in the place of a handle's old rows, which it drops.
+struct RawSource {
+    const void* p = nullptr;
+    bool on_dev = false;
+    int device = -1;
+    explicit RawSource(const void* vectors);
+};
+struct RawRows {
+    Arr rows;
+    bool borrowed = false;
+};
+int raw_rows_on(int dev, const RawSource& src, size_t bytes, RawRows& fresh);
+inline void raw_rows_drop(const RawRows& r) { if (r.rows.p && !r.borrowed) (void)hipFree(r.rows.p); }
+template <class Handle> // Replica, rbq_bf_index
+void raw_rows_swap(Handle* ix, const RawRows& fresh, uint64_t n, int dtype) {
+    raw_rows_drop(RawRows{ix->raw, ix->raw_borrowed});
+    ix->raw = fresh.rows; ix->raw_borrowed = fresh.borrowed;
+    ix->n_raw = fresh.rows.p ? n : 0; ix->raw_dtype = fresh.rows.p ? dtype : RBQ_RAW_F32;
+}
 int validate_header(const rbq_header* h, bool brute_force = false);
 int resolve_devices(int n_devices, const int* devices, std::vector<int>& out);
 Replica* new_replica(const rbq_header* hdr, int dev);

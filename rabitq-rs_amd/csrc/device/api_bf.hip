@@ -2,20 +2,22 @@
 // Host side: validation, upload, training on the device (rbq_bf_train_device), RBF1 in / out, and per search call: queries -> k_prep (rotation + QueryPrecomputed constants, shared with
 // the IVF path) -> for each chunk of vectors k_bf_dist + k_bf_select (bf.hpp) -> results; the range search (rbq_bf_range_batch)
 // runs k_bf_range_count + k_bf_range_place (bf_range.hpp) behind k_bf_dist instead, the exact one (rbq_bf_range_exact_batch, raw rows
-// attached with rbq_bf_set_rerank_vectors) k_bf_range_exact (bf_range_exact.hpp) in k_bf_range_count's place.  Each call takes a workspace and a stream
-// of its own from the handle's pool, so calls on one handle may overlap.
+// attached with rbq_bf_set_rerank_vectors) k_bf_range_exact (bf_range_exact.hpp) in k_bf_range_count's place.  The chunks and
+// sub-batches of a call are decided in csrc/host/rbq_bf_plan.hpp (plan_bf_call, pure host code); bf_run_call is the one loop that
+// walks them, and the three kinds of call hand it only what differs.  Each call takes a workspace and a stream of its own from the
+// handle's pool, so calls on one handle may overlap.
+#include <optional>
+
 #include "bf_index.hpp"
 #include "ext/rbq_bf_range.h"
+#include "../host/rbq_bf_plan.hpp"
 
 using namespace rbq_api;
 
 namespace rbq_api {
 namespace {
+static_assert(rbq_host::kBfPlanLdsHeapMaxTopK == kBfLdsHeapMaxTopK && rbq_host::kBfPlanRangeSpan == kBfRangeSpan, "host plan and kernels disagree");
 constexpr uint32_t kBfTopKMax = 16384;
-constexpr uint64_t kBfDistBudget = 128ull << 20; // distance workspace of one sub-batch (bytes)
-constexpr uint64_t kBfHeapBudget = 48ull << 20;  // heap workspace (between vector chunks, or for top_k above the LDS heap)
-constexpr uint64_t kBfOutBudget = 48ull << 20;   // result buffers of one sub-batch
-constexpr uint64_t kBfMaxSubBatch = 1024;
 constexpr uint64_t kBfTrainRowBudget = 512ull << 20; // rotated rows of one training pass (the IVF encoder's scratch budget)
 std::atomic<uint64_t> g_bf_chunk_vectors{0};   // rbq_bf_debug_set_chunk_vectors (0: the default)
 std::atomic<uint64_t> g_bf_select_launches{0}; // rbq_bf_debug_select_launches
@@ -99,6 +101,24 @@ int bf_encode_rows(rbq_bf_index* ix, const float* data, uint64_t n, uint64_t row
 }
 
 namespace {
+// The device a handle is made on (device < 0: the current one), checked against the device count; on RBQ_OK `g` has switched to it.
+int bf_enter_device(int device, int* dev, std::optional<DeviceGuard>& g) {
+    *dev = device;
+    if (*dev < 0) HIP_TRY(hipGetDevice(dev));
+    int count = 0;
+    HIP_TRY(hipGetDeviceCount(&count));
+    if (*dev >= count) return fail(RBQ_INVALID_CONFIG, "no such device: " + std::to_string(*dev));
+    g.emplace(*dev);
+    if (!g->ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
+    return RBQ_OK;
+}
+
+// The caller's host array into an array bf_new_index has allocated (nothing to copy for an array of no bytes: n == 0, or no ex code).
+int fill_arr(const Arr& a, const void* src) {
+    if (a.bytes) HIP_TRY(hipMemcpy(a.p, src, a.bytes, hipMemcpyHostToDevice));
+    return RBQ_OK;
+}
+
 int bf_create_impl(const rbq_header* hdr, const rbq_bf_view* v, int device, rbq_bf_index** out) {
     if (!out) return fail(RBQ_INVALID_CONFIG, "null output");
     *out = nullptr;
@@ -114,27 +134,15 @@ int bf_create_impl(const rbq_header* hdr, const rbq_bf_view* v, int device, rbq_
         if (!v->bin_codes || (ex && !v->ex_codes)) return fail(RBQ_INVALID_CONFIG, "null code array");
         for (const float* p : fs) if (!p) return fail(RBQ_INVALID_CONFIG, "null factor array");
     }
-    int dev = device;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    int count = 0;
-    HIP_TRY(hipGetDeviceCount(&count));
-    if (dev >= count) return fail(RBQ_INVALID_CONFIG, "no such device: " + std::to_string(dev));
-    std::unique_ptr<rbq_bf_index> ix(new rbq_bf_index());
-    static_cast<Geometry&>(*ix) = geometry_of(*hdr);
-    ix->device = dev;
-    ix->hdr = *hdr;
-    ix->hdr.n_vectors = n; ix->hdr.n_lists = 0;
-    ix->blob.assign(hdr->rotator_blob, hdr->rotator_blob + hdr->rotator_len);
-    ix->hdr.rotator_blob = ix->blob.data();
-    ix->ex_len = v->ex_len;
-    DeviceGuard g(dev);
-    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
-    rc = upload_arr(ix->rot_blob, ix->blob.data(), ix->blob.size());
-    if (!rc) rc = upload_arr(ix->bin, v->bin_codes, n * (D / 8));
-    if (!rc) rc = ex ? upload_arr(ix->ex, v->ex_codes, n * ex_want) : alloc_arr(ix->ex, 0);
-    for (int k = 0; k < 8 && !rc; ++k) rc = upload_arr(ix->f[k], fs[k], n * 4);
-    if (rc) { bf_free(ix.release()); return rc; }
-    *out = ix.release();
+    int dev;
+    std::optional<DeviceGuard> g;
+    if ((rc = bf_enter_device(device, &dev, g))) return rc;
+    BfOwner own{nullptr};
+    if ((rc = bf_new_index(hdr, n, v->ex_len, dev, own))) return rc;
+    rbq_bf_index* ix = own.ix;
+    if ((rc = fill_arr(ix->bin, v->bin_codes)) || (rc = fill_arr(ix->ex, v->ex_codes))) return rc; // (ex: no bytes for a 1-bit index)
+    for (int k = 0; k < 8; ++k) if ((rc = fill_arr(ix->f[k], fs[k]))) return rc;
+    *out = own.release();
     return RBQ_OK;
 }
 
@@ -153,14 +161,9 @@ int bf_train_impl(const rbq_header* hdr, const float* data, uint64_t n, int resc
     const int opt = rescale_mode(rescale, hdr);
     if (opt < 0) return RBQ_INVALID_CONFIG;
     if (!opt && hdr->ex_bits > 0 && !(t_const > 0.0f)) return fail(RBQ_INVALID_CONFIG, "the device encoder needs the constant rescale factor (faster config)");
-    int dev = device;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    int count = 0;
-    HIP_TRY(hipGetDeviceCount(&count));
-    if (dev >= count) return fail(RBQ_INVALID_CONFIG, "no such device: " + std::to_string(dev));
-    DeviceGuard g(dev);
-    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
-
+    int dev;
+    std::optional<DeviceGuard> g;
+    if ((rc = bf_enter_device(device, &dev, g))) return rc;
     BfOwner own{nullptr};
     // a trained 1-bit index carries D/8 zero bytes of ex code per vector (rbq_bf_view::ex_len)
     const uint64_t D = hdr->padded_dim;
@@ -170,7 +173,7 @@ int bf_train_impl(const rbq_header* hdr, const float* data, uint64_t n, int resc
     return RBQ_OK;
 }
 
-// ---- what the search and the range search do the same way ------------------------------------------------------------------------
+// ---- a search call: top-k, range and exact range ---------------------------------------------------------------------------------
 // A workspace of the handle's pool for the length of one call.
 struct BfLease {
     rbq_bf_index* ix;
@@ -185,158 +188,160 @@ struct BfLease {
     ~BfLease() { std::lock_guard<std::mutex> lk(ix->mu); ix->pool.push_back(w); }
 };
 
-// The call's stream, and the buffers of `sub` prepared queries and their distances to a chunk of nv_chunk vectors.
-int bf_call_buffers(rbq_bf_index* ix, BfWorkspace* w, uint64_t sub, uint64_t nv_chunk) {
-    if (!w->stream) HIP_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-    int rc;
-    if ((rc = w->q.ensure(sub * ix->hdr.dim * 4)) || (rc = w->rot.ensure(sub * ix->hdr.padded_dim * 4)) || (rc = w->lut.ensure(sub * 4 * ix->Dc)) ||
-        (rc = w->consts.ensure(sub * sizeof(QueryConsts))) || (rc = w->dist.ensure(sub * nv_chunk * 4)))
-        return rc;
-    return RBQ_OK;
+// The plan of a call on ix (rbq_bf_plan.hpp); `k`: top_k, or the capacity of a range call.  The test hook is read once per call.
+rbq_host::BfCallPlan bf_plan(const rbq_bf_index* ix, uint64_t nq, bool range, uint32_t k) {
+    rbq_host::BfCallShape s;
+    s.n = ix->hdr.n_vectors; s.nq = nq; s.range = range; s.top_k = k; s.chunk_vectors = g_bf_chunk_vectors.load(std::memory_order_relaxed);
+    return rbq_host::plan_bf_call(s);
 }
 
-int bf_upload_filter(BfWorkspace* w, const uint32_t* filter_words, uint64_t filter_nbits, const uint32_t** d_filter) {
-    *d_filter = nullptr;
-    if (!filter_words) return RBQ_OK;
-    const uint64_t words = (filter_nbits + 31) / 32;
-    int rc;
-    if ((rc = w->filter.ensure(std::max<uint64_t>(words, 1) * 4))) return rc;
-    if (words) HIP_TRY(hipMemcpyAsync(w->filter.p, filter_words, words * 4, hipMemcpyHostToDevice, w->stream));
-    *d_filter = (const uint32_t*)w->filter.p;
-    return RBQ_OK;
-}
-
-BfDistParams bf_dist_params(const rbq_bf_index* ix, const BfWorkspace* w, uint32_t m, uint64_t v0, uint64_t nv, const uint32_t* d_filter,
-                            uint64_t filter_nbits) {
-    BfDistParams dp;
-    dp.rot = (const float*)w->rot.p; dp.consts = (const QueryConsts*)w->consts.p; dp.nq = m; dp.D = ix->hdr.padded_dim; dp.ex_bits = ix->hdr.ex_bits;
-    dp.v0 = v0; dp.nv = nv; dp.bin = (const uint8_t*)ix->bin.p; dp.ex = (const uint8_t*)ix->ex.p;
-    dp.f_add = (const float*)ix->f[2].p; dp.f_rescale = (const float*)ix->f[3].p;
-    dp.f_add_ex = (const float*)ix->f[6].p; dp.f_rescale_ex = (const float*)ix->f[7].p;
-    dp.filter = d_filter; dp.filter_nbits = filter_nbits; dp.dist = (float*)w->dist.p;
-    return dp;
-}
-
-int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t top_k, const uint32_t* filter_words, uint64_t filter_nbits,
-                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
-    const uint64_t n = ix->hdr.n_vectors, K = top_k;
+// ONE call, as the plan cuts it: the handle's device, a workspace with its stream, the buffers of a sub-batch's prepared queries and
+// their distances to a chunk, the filter; per sub-batch H2D + k_prep, per chunk k_bf_dist, then the counts back; one wait at the end.
+// What the kinds of call do differently they enqueue themselves:
+//   setup(w, st)                the call's own buffers, and what must be on the stream before the first query
+//   chunk(w, st, m, c, v0, nv)  behind k_bf_dist of chunk c = vectors v0 .. v0 + nv - 1, for the sub-batch's m queries
+//   rows(w, st, q0, m)          the rows of queries q0 .. q0 + m - 1 back to the caller
+//   finish(w, st)               after the last sub-batch, before the synchronise: host work here overlaps the stream's
+template <class Setup, class Chunk, class Rows, class Finish>
+int bf_run_call(rbq_bf_index* ix, const rbq_host::BfCallPlan& pl, const float* queries, uint64_t nq, const uint32_t* filter_words,
+                uint64_t filter_nbits, uint32_t* out_counts, Setup setup, Chunk chunk, Rows rows, Finish finish) {
+    const uint64_t n = ix->hdr.n_vectors, sub = pl.sub;
     const uint32_t dim = ix->hdr.dim;
-    // plan: vector chunks of at most kBfDistBudget / 4 vectors, sub-batches of queries within the workspace budgets
-    const uint64_t cap = g_bf_chunk_vectors.load(std::memory_order_relaxed); // (test hook: read once per call)
-    const uint64_t nv_chunk = std::min<uint64_t>({n, kBfDistBudget / 4, cap ? cap : UINT64_MAX});
-    const uint64_t n_chunks = (n + nv_chunk - 1) / nv_chunk;
-    const bool lds_heap = top_k <= kBfLdsHeapMaxTopK;
-    const bool heap_ws = n_chunks > 1 || !lds_heap;
-    uint64_t sub = std::min<uint64_t>({nq, kBfMaxSubBatch, std::max<uint64_t>(1, kBfDistBudget / (nv_chunk * 4)),
-                                       std::max<uint64_t>(1, kBfOutBudget / (K * 12))});
-    if (heap_ws) sub = std::min<uint64_t>(sub, std::max<uint64_t>(1, kBfHeapBudget / ((K + 1) * 8)));
+    DeviceGuard g(ix->device); // (the last check of every entry)
+    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
     BfLease lease(ix);
     BfWorkspace* w = lease.w;
-    int rc;
-    if ((rc = bf_call_buffers(ix, w, sub, nv_chunk))) return rc;
+    if (!w->stream) HIP_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
     hipStream_t st = w->stream;
-    if ((rc = w->heap_len.ensure(sub * 4)) || (rc = w->ids.ensure(sub * K * 8)) || (rc = w->scores.ensure(sub * K * 4)) ||
-        (rc = w->counts.ensure(sub * 4)) || (rc = w->stats.ensure(16)))
+    int rc;
+    if ((rc = w->q.ensure(sub * dim * 4)) || (rc = w->rot.ensure(sub * ix->hdr.padded_dim * 4)) || (rc = w->lut.ensure(sub * 4 * ix->Dc)) ||
+        (rc = w->consts.ensure(sub * sizeof(QueryConsts))) || (rc = w->dist.ensure(sub * pl.nv_chunk * 4)) || (rc = w->counts.ensure(sub * 4)))
         return rc;
-    if (heap_ws && ((rc = w->heap_d.ensure(sub * (K + 1) * 4)) || (rc = w->heap_s.ensure(sub * (K + 1) * 4)))) return rc;
-    const uint32_t* d_filter = nullptr;
-    if ((rc = bf_upload_filter(w, filter_words, filter_nbits, &d_filter))) return rc;
-    HIP_TRY(hipMemsetAsync(w->stats.p, 0, 16, st));
+    BfDistParams dp;
+    dp.D = ix->hdr.padded_dim; dp.ex_bits = ix->hdr.ex_bits; dp.bin = (const uint8_t*)ix->bin.p; dp.ex = (const uint8_t*)ix->ex.p;
+    dp.f_add = (const float*)ix->f[2].p; dp.f_rescale = (const float*)ix->f[3].p;
+    dp.f_add_ex = (const float*)ix->f[6].p; dp.f_rescale_ex = (const float*)ix->f[7].p;
+    dp.rot = (const float*)w->rot.p; dp.consts = (const QueryConsts*)w->consts.p; dp.dist = (float*)w->dist.p;
+    dp.filter = nullptr; dp.filter_nbits = filter_nbits;
+    if (filter_words) {
+        const uint64_t words = (filter_nbits + 31) / 32;
+        if ((rc = w->filter.ensure(std::max<uint64_t>(words, 1) * 4))) return rc;
+        if (words) HIP_TRY(hipMemcpyAsync(w->filter.p, filter_words, words * 4, hipMemcpyHostToDevice, st));
+        dp.filter = (const uint32_t*)w->filter.p;
+    }
+    if ((rc = setup(w, st))) return rc;
     for (uint64_t q0 = 0; q0 < nq; q0 += sub) {
         const uint32_t m = (uint32_t)std::min<uint64_t>(sub, nq - q0);
         HIP_TRY(hipMemcpyAsync(w->q.p, queries + q0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(launch_prep(prep_params(*ix, ix->rot_blob, *w, (const float*)w->q.p, m), ix->device, st));
-        for (uint64_t c = 0; c < n_chunks; ++c) {
-            const uint64_t v0 = c * nv_chunk, nv = std::min<uint64_t>(nv_chunk, n - v0);
-            HIP_TRY(launch_bf_dist(bf_dist_params(ix, w, m, v0, nv, d_filter, filter_nbits), st));
+        for (uint64_t c = 0; c < pl.n_chunks; ++c) {
+            dp.nq = m; dp.v0 = c * pl.nv_chunk; dp.nv = std::min<uint64_t>(pl.nv_chunk, n - dp.v0);
+            HIP_TRY(launch_bf_dist(dp, st));
+            if ((rc = chunk(w, st, m, c, dp.v0, dp.nv))) return rc;
+        }
+        if ((rc = rows(w, st, q0, m))) return rc;
+        HIP_TRY(hipMemcpyAsync(out_counts + q0, w->counts.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+    }
+    if ((rc = finish(w, st))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return RBQ_OK;
+}
+
+int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t top_k, const uint32_t* filter_words, uint64_t filter_nbits,
+                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+    const rbq_host::BfCallPlan pl = bf_plan(ix, nq, /*range=*/false, top_k);
+    const uint64_t K = top_k, sub = pl.sub;
+    uint64_t stats[2] = {0, 0};
+    const int rc = bf_run_call(
+        ix, pl, queries, nq, filter_words, filter_nbits, out_counts,
+        [&](BfWorkspace* w, hipStream_t st) -> int {
+            int rc;
+            if ((rc = w->heap_len.ensure(sub * 4)) || (rc = w->ids.ensure(sub * K * 8)) || (rc = w->scores.ensure(sub * K * 4)) || (rc = w->stats.ensure(16)))
+                return rc;
+            if (pl.heap_ws && ((rc = w->heap_d.ensure(sub * (K + 1) * 4)) || (rc = w->heap_s.ensure(sub * (K + 1) * 4)))) return rc;
+            HIP_TRY(hipMemsetAsync(w->stats.p, 0, 16, st));
+            return RBQ_OK;
+        },
+        [&](BfWorkspace* w, hipStream_t st, uint32_t m, uint64_t c, uint64_t v0, uint64_t nv) -> int {
             BfSelectParams sp;
             sp.dist = (const float*)w->dist.p; sp.nq = m; sp.top_k = top_k; sp.v0 = v0; sp.nv = nv; sp.metric = ix->hdr.metric;
-            sp.first = c == 0; sp.last = c + 1 == n_chunks; sp.lds_heap = lds_heap;
+            sp.first = c == 0; sp.last = c + 1 == pl.n_chunks; sp.lds_heap = pl.lds_heap;
             sp.heap_d = (float*)w->heap_d.p; sp.heap_s = (uint32_t*)w->heap_s.p; sp.heap_len = (uint32_t*)w->heap_len.p;
             sp.out_ids = (uint64_t*)w->ids.p; sp.out_scores = (float*)w->scores.p; sp.out_counts = (uint32_t*)w->counts.p;
             sp.stats = (unsigned long long*)w->stats.p;
             HIP_TRY(launch_bf_select(sp, st));
             g_bf_select_launches.fetch_add(1, std::memory_order_relaxed);
-        }
-        HIP_TRY(hipMemcpyAsync(out_ids + q0 * K, w->ids.p, (size_t)m * K * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_scores + q0 * K, w->scores.p, (size_t)m * K * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_counts + q0, w->counts.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-    }
-    uint64_t stats[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(stats, w->stats.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    ix->pushes += stats[0];
-    ix->tie_pushes += stats[1];
-    return RBQ_OK;
+            return RBQ_OK;
+        },
+        [&](BfWorkspace* w, hipStream_t st, uint64_t q0, uint32_t m) -> int {
+            HIP_TRY(hipMemcpyAsync(out_ids + q0 * K, w->ids.p, (size_t)m * K * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_scores + q0 * K, w->scores.p, (size_t)m * K * 4, hipMemcpyDeviceToHost, st));
+            return RBQ_OK;
+        },
+        [&](BfWorkspace* w, hipStream_t st) -> int {
+            HIP_TRY(hipMemcpyAsync(stats, w->stats.p, 16, hipMemcpyDeviceToHost, st));
+            return RBQ_OK;
+        });
+    if (rc == RBQ_OK) { ix->pushes += stats[0]; ix->tie_pushes += stats[1]; }
+    return rc;
 }
 
-// rbq_bf_range_batch (include/ext/rbq_bf_range.h): the search's plan without its heap — k_prep, then per chunk
-// of vectors k_bf_dist -> k_bf_range_count -> k_bf_range_place (bf_range.hpp), the totals carried from chunk to chunk in two arrays
-// that alternate.  The sub-batch comes from the distance budget and, with rows, the output budget.
+// rbq_bf_range_batch (include/ext/rbq_bf_range.h): the search's plan without its heap — per chunk of vectors
+// k_bf_range_count -> k_bf_range_place (bf_range.hpp) behind k_bf_dist, the totals carried from chunk to chunk in two arrays that
+// alternate.  The sub-batch comes from the distance budget and, with rows, the output budget.
 // exact_x (rbq_bf_range_exact_batch; null: the estimate decides): `radius` is the candidate radius,
 // k_bf_range_exact (bf_range_exact.hpp) stands in k_bf_range_count's place — it scores the candidates against the handle's raw rows
 // and writes the exact distances over the workspace — and k_bf_range_place runs at the radius *exact_x.  Everything else is one copy.
 int bf_range_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t capacity, float radius, const float* exact_x,
                   const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
-    const uint64_t n = ix->hdr.n_vectors;
-    const uint32_t dim = ix->hdr.dim;
-    const uint64_t limit = g_bf_chunk_vectors.load(std::memory_order_relaxed); // (test hook: read once per call)
-    const uint64_t nv_chunk = std::min<uint64_t>({n, kBfDistBudget / 4, limit ? limit : UINT64_MAX});
-    const uint64_t n_chunks = (n + nv_chunk - 1) / nv_chunk;
-    const uint64_t spans = (nv_chunk + kBfRangeSpan - 1) / kBfRangeSpan;
-    const uint64_t cap = std::min<uint64_t>(capacity, n); // slots per row on the device: no row holds more than n matches
-    uint64_t sub = std::min<uint64_t>({nq, kBfMaxSubBatch, std::max<uint64_t>(1, kBfDistBudget / (nv_chunk * 4))});
-    if (cap) sub = std::min<uint64_t>(sub, std::max<uint64_t>(1, kBfOutBudget / (cap * 12)));
-    BfLease lease(ix);
-    BfWorkspace* w = lease.w;
-    int rc;
-    if ((rc = bf_call_buffers(ix, w, sub, nv_chunk))) return rc;
-    hipStream_t st = w->stream;
-    if ((rc = w->span_counts.ensure(sub * spans * 4)) || (rc = w->running.ensure(2 * sub * 4)) || (rc = w->counts.ensure(sub * 4))) return rc;
-    if (cap && ((rc = w->ids.ensure(sub * cap * 8)) || (rc = w->scores.ensure(sub * cap * 4)))) return rc;
-    const uint32_t* d_filter = nullptr;
-    if ((rc = bf_upload_filter(w, filter_words, filter_nbits, &d_filter))) return rc;
-    for (uint64_t q0 = 0; q0 < nq; q0 += sub) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(sub, nq - q0);
-        HIP_TRY(hipMemcpyAsync(w->q.p, queries + q0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(launch_prep(prep_params(*ix, ix->rot_blob, *w, (const float*)w->q.p, m), ix->device, st));
-        for (uint64_t c = 0; c < n_chunks; ++c) {
-            const uint64_t v0 = c * nv_chunk, nv = std::min<uint64_t>(nv_chunk, n - v0);
-            HIP_TRY(launch_bf_dist(bf_dist_params(ix, w, m, v0, nv, d_filter, filter_nbits), st));
+    const rbq_host::BfCallPlan pl = bf_plan(ix, nq, /*range=*/true, capacity);
+    const uint64_t cap = pl.cap, sub = pl.sub;
+    return bf_run_call(
+        ix, pl, queries, nq, filter_words, filter_nbits, out_counts,
+        [&](BfWorkspace* w, hipStream_t) -> int {
+            int rc;
+            if ((rc = w->span_counts.ensure(sub * pl.spans * 4)) || (rc = w->running.ensure(2 * sub * 4))) return rc;
+            if (cap && ((rc = w->ids.ensure(sub * cap * 8)) || (rc = w->scores.ensure(sub * cap * 4)))) return rc;
+            return RBQ_OK;
+        },
+        [&](BfWorkspace* w, hipStream_t st, uint32_t m, uint64_t c, uint64_t v0, uint64_t nv) -> int {
             BfRangeParams rp;
             rp.dist = (const float*)w->dist.p; rp.nq = m; rp.n_spans = (uint32_t)((nv + kBfRangeSpan - 1) / kBfRangeSpan);
-            rp.v0 = v0; rp.nv = nv; rp.radius = exact_x ? *exact_x : radius; rp.metric = ix->hdr.metric; rp.first = c == 0; rp.last = c + 1 == n_chunks;
+            rp.v0 = v0; rp.nv = nv; rp.radius = exact_x ? *exact_x : radius; rp.metric = ix->hdr.metric; rp.first = c == 0; rp.last = c + 1 == pl.n_chunks;
             rp.capacity = (uint32_t)cap; rp.span_counts = (uint32_t*)w->span_counts.p;
             rp.run_in = (const uint32_t*)w->running.p + (c & 1) * sub; rp.run_out = (uint32_t*)w->running.p + ((c + 1) & 1) * sub;
             rp.out_ids = (uint64_t*)w->ids.p; rp.out_scores = (float*)w->scores.p; rp.out_counts = (uint32_t*)w->counts.p;
             if (exact_x) {
                 BfRangeExactParams xp;
                 xp.dist = (float*)w->dist.p; xp.queries = (const float*)w->q.p; xp.raw = ix->raw.p; xp.nq = m; xp.n_spans = rp.n_spans;
-                xp.dim = dim; xp.v0 = v0; xp.nv = nv; xp.candidate_radius = radius; xp.x = *exact_x; xp.metric = ix->hdr.metric;
+                xp.dim = ix->hdr.dim; xp.v0 = v0; xp.nv = nv; xp.candidate_radius = radius; xp.x = *exact_x; xp.metric = ix->hdr.metric;
                 xp.raw_dtype = ix->raw_dtype; xp.span_counts = rp.span_counts;
                 HIP_TRY(launch_bf_range_exact(xp, st));
             } else {
                 HIP_TRY(launch_bf_range_count(rp, st));
             }
             HIP_TRY(launch_bf_range_place(rp, st));
-        }
-        if (cap == capacity && cap) {
-            HIP_TRY(hipMemcpyAsync(out_ids + q0 * cap, w->ids.p, (size_t)m * cap * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_scores + q0 * cap, w->scores.p, (size_t)m * cap * 4, hipMemcpyDeviceToHost, st));
-        } else if (cap) { // capacity > n: the caller's rows are wider than the device's
-            HIP_TRY(hipMemcpy2DAsync(out_ids + q0 * capacity, (size_t)capacity * 8, w->ids.p, cap * 8, cap * 8, m, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpy2DAsync(out_scores + q0 * capacity, (size_t)capacity * 4, w->scores.p, cap * 4, cap * 4, m, hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(hipMemcpyAsync(out_counts + q0, w->counts.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-    }
-    // capacity > n: slots n .. capacity - 1 of a row can hold no match whatever the device finds; they are written here, beside
-    // the copies above, while the stream works
-    for (uint64_t q = 0; cap < capacity && q < nq; ++q) {
-        std::fill_n(out_ids + q * capacity + cap, capacity - cap, ~0ull);
-        std::fill_n(out_scores + q * capacity + cap, capacity - cap, std::numeric_limits<float>::quiet_NaN());
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return RBQ_OK;
+            return RBQ_OK;
+        },
+        [&](BfWorkspace* w, hipStream_t st, uint64_t q0, uint32_t m) -> int {
+            if (cap == capacity && cap) {
+                HIP_TRY(hipMemcpyAsync(out_ids + q0 * cap, w->ids.p, (size_t)m * cap * 8, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(out_scores + q0 * cap, w->scores.p, (size_t)m * cap * 4, hipMemcpyDeviceToHost, st));
+            } else if (cap) { // capacity > n: the caller's rows are wider than the device's
+                HIP_TRY(hipMemcpy2DAsync(out_ids + q0 * capacity, (size_t)capacity * 8, w->ids.p, cap * 8, cap * 8, m, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpy2DAsync(out_scores + q0 * capacity, (size_t)capacity * 4, w->scores.p, cap * 4, cap * 4, m, hipMemcpyDeviceToHost, st));
+            }
+            return RBQ_OK;
+        },
+        [&](BfWorkspace*, hipStream_t) -> int {
+            // capacity > n: slots n .. capacity - 1 of a row can hold no match whatever the device finds; they are written here, beside
+            // the copies above, while the stream works
+            for (uint64_t q = 0; cap < capacity && q < nq; ++q) {
+                std::fill_n(out_ids + q * capacity + cap, capacity - cap, ~0ull);
+                std::fill_n(out_scores + q * capacity + cap, capacity - cap, std::numeric_limits<float>::quiet_NaN());
+            }
+            return RBQ_OK;
+        });
 }
 } // namespace
 } // namespace rbq_api
@@ -433,19 +438,33 @@ void rbq_bf_debug_heap_stats(const rbq_bf_index* idx, uint64_t* out2) {
 uint64_t rbq_bf_debug_set_chunk_vectors(uint64_t vectors) { return g_bf_chunk_vectors.exchange(vectors, std::memory_order_relaxed); }
 uint64_t rbq_bf_debug_select_launches(void) { return g_bf_select_launches.load(std::memory_order_relaxed); }
 
+// The checks of the search entries, in the order callers see them:
+//   rbq_bf_search_batch:   null index, empty index, dimension, nq == 0 (OK) | top_k == 0 (counts zeroed, OK), top_k > 16384 |
+//                          nq >= 2^31 | null buffer | the device
+//   the two range entries: null index, empty index, dimension, nq == 0 (OK) | raw vectors attached (exact) |
+//                          nq >= 2^31 | null buffer, x is NaN, radius is NaN | the device
+// bf_entry_prefix is the first group of either, and bf_run_call switches to the device before anything else, which is the last;
+// what stands between differs and stays with its entry.  *ix null: the call is answered and the return value is its result.
+static int bf_entry_prefix(const rbq_bf_index* ch, uint32_t query_dim, uint64_t nq, rbq_bf_index** ix) {
+    *ix = nullptr;
+    if (!ch) return fail(RBQ_INVALID_CONFIG, "null index");
+    if (ch->hdr.n_vectors == 0) return fail(RBQ_EMPTY_INDEX, "index is empty");
+    if (query_dim != ch->hdr.dim) {
+        char b[96];
+        std::snprintf(b, sizeof b, "expected %u, got %u", ch->hdr.dim, query_dim);
+        return fail(RBQ_DIMENSION_MISMATCH, b);
+    }
+    if (nq) *ix = const_cast<rbq_bf_index*>(ch);
+    return RBQ_OK;
+}
+
 int rbq_bf_search_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
                         const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
     g_err.clear();
     RBQ_GUARD_BEGIN
-    if (!ch) return fail(RBQ_INVALID_CONFIG, "null index");
-    rbq_bf_index* ix = const_cast<rbq_bf_index*>(ch);
-    if (ix->hdr.n_vectors == 0) return fail(RBQ_EMPTY_INDEX, "index is empty");
-    if (query_dim != ix->hdr.dim) {
-        char b[96];
-        std::snprintf(b, sizeof b, "expected %u, got %u", ix->hdr.dim, query_dim);
-        return fail(RBQ_DIMENSION_MISMATCH, b);
-    }
-    if (nq == 0) return RBQ_OK;
+    rbq_bf_index* ix;
+    const int rc = bf_entry_prefix(ch, query_dim, nq, &ix);
+    if (!ix) return rc;
     if (top_k == 0) {
         if (out_counts) std::memset(out_counts, 0, nq * 4);
         return RBQ_OK;
@@ -453,8 +472,6 @@ int rbq_bf_search_batch(const rbq_bf_index* ch, const float* queries, uint64_t n
     if (top_k > kBfTopKMax) return fail(RBQ_INVALID_CONFIG, "top_k > 16384 is not supported by the brute-force index");
     if (nq >= (1ull << 31)) return fail(RBQ_INVALID_CONFIG, "nq >= 2^31");
     if (!queries || !out_ids || !out_scores || !out_counts) return fail(RBQ_INVALID_CONFIG, "null buffer");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
     return bf_search_impl(ix, queries, nq, top_k, filter_words, filter_nbits, out_ids, out_scores, out_counts);
     RBQ_GUARD_END
 }
@@ -466,22 +483,14 @@ static int bf_range_entry(const rbq_bf_index* ch, const float* queries, uint64_t
                           uint32_t* out_counts) {
     g_err.clear();
     RBQ_GUARD_BEGIN
-    if (!ch) return fail(RBQ_INVALID_CONFIG, "null index");
-    rbq_bf_index* ix = const_cast<rbq_bf_index*>(ch);
-    if (ix->hdr.n_vectors == 0) return fail(RBQ_EMPTY_INDEX, "index is empty");
-    if (query_dim != ix->hdr.dim) {
-        char b[96];
-        std::snprintf(b, sizeof b, "expected %u, got %u", ix->hdr.dim, query_dim);
-        return fail(RBQ_DIMENSION_MISMATCH, b);
-    }
-    if (nq == 0) return RBQ_OK;
+    rbq_bf_index* ix;
+    const int rc = bf_entry_prefix(ch, query_dim, nq, &ix);
+    if (!ix) return rc;
     if (exact_x && !ix->raw.p) return fail(RBQ_INVALID_CONFIG, "exact range search needs raw vectors attached (rbq_bf_set_rerank_vectors)");
     if (nq >= (1ull << 31)) return fail(RBQ_INVALID_CONFIG, "nq >= 2^31");
     if (!queries || !out_counts || (capacity && (!out_ids || !out_scores))) return fail(RBQ_INVALID_CONFIG, "null buffer");
     if (exact_x && *exact_x != *exact_x) return fail(RBQ_INVALID_CONFIG, "x is NaN");
     if (radius != radius) return fail(RBQ_INVALID_CONFIG, exact_x ? "candidate_radius is NaN" : "radius is NaN");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
     return bf_range_impl(ix, queries, nq, capacity, radius, exact_x, filter_words, filter_nbits, out_ids, out_scores, out_counts);
     RBQ_GUARD_END
 }
@@ -515,34 +524,21 @@ int rbq_bf_set_rerank_vectors(rbq_bf_index* ix, const void* vectors, uint64_t n,
     }
     DeviceGuard g(ix->device);
     if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
-    Arr fresh;
-    bool borrowed = false;
+    RawRows fresh;
     if (attach && n) {
-        const size_t bytes = (size_t)n * ix->hdr.dim * raw_elem_bytes(raw_dtype);
-        hipPointerAttribute_t a;
-        const bool on_dev = hipPointerGetAttributes(&a, vectors) == hipSuccess && a.type == hipMemoryTypeDevice;
-        if (!on_dev) (void)hipGetLastError();
-        if (on_dev && a.device == ix->device) { // borrowed: stays the caller's, must outlive the attachment
-            if (raw_dtype != RBQ_RAW_F32 && (reinterpret_cast<uintptr_t>(vectors) & 1u))
-                return fail(RBQ_INVALID_CONFIG, "rerank vectors: a device pointer to 16-bit rows must be 2-byte aligned");
-            fresh.p = const_cast<void*>(vectors); fresh.bytes = bytes; borrowed = true;
-        } else {
-            int rc = alloc_arr(fresh, bytes);
-            if (rc) return rc;
-            const hipError_t e = hipMemcpy(fresh.p, vectors, bytes, on_dev ? hipMemcpyDefault : hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(fresh.p);
-                return fail(RBQ_DEVICE, std::string("attaching the rerank vectors: ") + hipGetErrorString(e));
-            }
-        }
+        const RawSource src(vectors);
+        // (borrowed rows stay the caller's and must outlive the attachment)
+        if (src.on_dev && src.device == ix->device && raw_dtype != RBQ_RAW_F32 && (reinterpret_cast<uintptr_t>(vectors) & 1u))
+            return fail(RBQ_INVALID_CONFIG, "rerank vectors: a device pointer to 16-bit rows must be 2-byte aligned");
+        const int rc = raw_rows_on(ix->device, src, (size_t)n * ix->hdr.dim * raw_elem_bytes(raw_dtype), fresh);
+        if (rc) return rc;
     }
     const hipError_t e = hipDeviceSynchronize(); // (the old rows go: not safe concurrently with calls on the handle)
     if (e != hipSuccess) {
-        if (fresh.p && !borrowed) (void)hipFree(fresh.p);
+        raw_rows_drop(fresh);
         return fail(RBQ_DEVICE, std::string("hipDeviceSynchronize: ") + hipGetErrorString(e));
     }
-    if (ix->raw.p && !ix->raw_borrowed) (void)hipFree(ix->raw.p);
-    ix->raw = fresh; ix->n_raw = fresh.p ? n : 0; ix->raw_borrowed = borrowed; ix->raw_dtype = fresh.p ? raw_dtype : RBQ_RAW_F32;
+    raw_rows_swap(ix, fresh, n, raw_dtype);
     return RBQ_OK;
     RBQ_GUARD_END
 }

@@ -495,6 +495,26 @@ int load_rbq1_impl(const void* bytes, size_t len, int n_devices, const int* devi
     return wrap_and_replicate(first, devs, out);
 }
 } // namespace
+
+RawSource::RawSource(const void* vectors) : p(vectors) {
+    hipPointerAttribute_t a;
+    on_dev = hipPointerGetAttributes(&a, vectors) == hipSuccess && a.type == hipMemoryTypeDevice;
+    if (on_dev) device = a.device;
+    else (void)hipGetLastError();
+}
+
+int raw_rows_on(int dev, const RawSource& src, size_t bytes, RawRows& fresh) {
+    Arr& a = fresh.rows;
+    fresh.borrowed = src.on_dev && src.device == dev;
+    if (fresh.borrowed) { a.p = const_cast<void*>(src.p); a.bytes = bytes; return RBQ_OK; }
+    const int rc = alloc_arr(a, bytes);
+    if (rc) return rc;
+    const hipError_t e = src.on_dev ? copy_cross_device(a.p, dev, src.p, src.device, bytes) : hipMemcpy(a.p, src.p, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) return RBQ_OK;
+    (void)hipFree(a.p);
+    a = Arr();
+    return fail(RBQ_DEVICE, std::string("attaching the rerank vectors: ") + hipGetErrorString(e));
+}
 } // namespace rbq_api
 
 extern "C" {
@@ -570,36 +590,22 @@ int rbq_index_set_rerank_vectors(rbq_index* h, const float* vectors_f32, uint64_
     // all replicas or none: the new copies are made first; only when every one of them exists are the old ones released
     // and the new ones attached (a failure half-way leaves every replica exactly as it was)
     const size_t R = h->reps.size();
-    std::vector<Arr> fresh(R);
-    std::vector<char> borrowed(R, 0);
+    std::vector<RawRows> fresh(R);
     const bool attach = vectors && n;
     if (attach) {
-        hipPointerAttribute_t a;
-        const bool on_dev = hipPointerGetAttributes(&a, vectors) == hipSuccess && a.type == hipMemoryTypeDevice;
-        if (!on_dev) (void)hipGetLastError();
-        if (on_dev && esize == 2 && (reinterpret_cast<uintptr_t>(vectors) & 1u))
+        const RawSource src(vectors);
+        if (src.on_dev && esize == 2 && (reinterpret_cast<uintptr_t>(vectors) & 1u))
             return fail(RBQ_INVALID_CONFIG, "rerank vectors: a device pointer to 16-bit rows must be 2-byte aligned");
         int rc = RBQ_OK;
         for (size_t r = 0; r < R && rc == RBQ_OK; ++r) {
             Replica* ix = h->reps[r];
             DeviceGuard g(ix->device);
             if (!g.ok) { rc = fail(RBQ_DEVICE, "hipSetDevice failed"); break; }
-            const size_t bytes = (size_t)n * ix->dim * esize;
-            if (on_dev && a.device == ix->device) { // borrowed: stays owned by the caller, must outlive the index
-                fresh[r].p = const_cast<void*>(vectors); fresh[r].bytes = bytes; borrowed[r] = 1;
-                continue;
-            }
-            rc = alloc_arr(fresh[r], bytes);
-            if (rc == RBQ_OK) {
-                const hipError_t e = on_dev ? copy_cross_device(fresh[r].p, ix->device, vectors, a.device, bytes)
-                                            : hipMemcpy(fresh[r].p, vectors, bytes, hipMemcpyHostToDevice);
-                if (e != hipSuccess) rc = fail(RBQ_DEVICE, std::string("attaching the rerank vectors: ") + hipGetErrorString(e));
-            }
+            rc = raw_rows_on(ix->device, src, (size_t)n * ix->dim * esize, fresh[r]);
         }
         if (rc != RBQ_OK) {
             const std::string keep = g_err;
-            for (size_t r = 0; r < R; ++r)
-                if (fresh[r].p && !borrowed[r]) { DeviceGuard g(h->reps[r]->device); (void)hipFree(fresh[r].p); }
+            for (size_t r = 0; r < R; ++r) { DeviceGuard g(h->reps[r]->device); raw_rows_drop(fresh[r]); }
             return fail(rc, keep);
         }
     }
@@ -608,11 +614,8 @@ int rbq_index_set_rerank_vectors(rbq_index* h, const float* vectors_f32, uint64_
         DeviceGuard g(ix->device);
         if (!g.ok) return fail(RBQ_DEVICE, "hipSetDevice failed");
         HIP_TRY(hipDeviceSynchronize());
-        if (ix->raw.p && !ix->raw_borrowed) (void)hipFree(ix->raw.p);
-        ix->raw = Arr(); ix->n_raw = 0; ix->rerank = false; ix->raw_borrowed = false; ix->raw_dtype = RBQ_RAW_F32;
-        if (!attach) continue; // detach
-        ix->raw = fresh[r]; ix->raw_borrowed = borrowed[r] != 0; ix->raw_dtype = dtype;
-        ix->n_raw = n; ix->rerank = true;
+        raw_rows_swap(ix, fresh[r], n, dtype); // (fresh[r] empty: detach)
+        ix->rerank = attach;
     }
     return RBQ_OK;
     RBQ_GUARD_END

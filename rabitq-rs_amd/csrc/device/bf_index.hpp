@@ -1,5 +1,6 @@
 // bf_index.hpp — the brute-force handle (rbq_bf_index) and what the units that serve it share: api_bf.hip (create, train, RBF1,
-// search) and api_bf_mutate.hip (append, remove, fetch).  Internal, like api.hpp.
+// raw rows, and the search calls: one loop, bf_run_call, over the plan of csrc/host/rbq_bf_plan.hpp) and api_bf_mutate.hip (append,
+// remove, fetch).  Internal, like api.hpp.
 #pragma once
 #include "api.hpp"
 

@@ -154,6 +154,29 @@ def test_state_of_the_handle():
     idx.close()
 
 
+def test_reattach_and_detach():
+    """f32 host rows, f16 host rows over them, a borrowed bf16 tensor over those, then none: after every step the element type, and
+    every vector scored against the rows as they are then (the rows replaced are gone, borrowed ones are not freed)"""
+    n, dim = 100, 24
+    q, data = case(n, dim, 7, 0)[2::2]
+    idx = rq.BruteForceRabitqIndex.train(data, 7, 0, 1, 7, True)
+    x = np.sort(rows_of(n, dim, 7, 0, "f32")[4][0])[n // 2]
+    for raw in RAWS:
+        stored, dtype = rows_of(n, dim, 7, 0, raw)[:2]
+        if raw == "bf16":
+            stored = torch.from_numpy(stored.view(np.int16)).view(torch.bfloat16).cuda()
+        idx.set_rerank_vectors(stored, dtype=None if raw == "bf16" else dtype)
+        want, ncand = expect((n, dim, 7, 0, raw), INF, x, 64)
+        assert (idx._raw_keep is stored) == (raw == "bf16") and idx.rerank_dtype() == raw
+        assert (ncand == n).all() and visible(want, ncand) and same(rows(idx, q, INF, x, 64), want), raw
+    idx.set_rerank_vectors(None)
+    assert idx.rerank_dtype() is None and idx._raw_keep is None
+    with pytest.raises(rq.RabitqError, match=r"exact range search needs raw vectors attached \(rbq_bf_set_rerank_vectors\)") as e:
+        idx.range_rows(q, INF, 64, exact_x=x)
+    assert e.value.code == _abi.RBQ_INVALID_CONFIG
+    idx.close()
+
+
 @pytest.mark.parametrize("metric", [0, 1])
 def test_python_layer(metric):
     key = (1100, 20, 7, metric, "f32")

@@ -167,6 +167,27 @@ def test_rbf1_save_load(bits, rotator, dim, tmp_path):
     assert [r.id for r in loaded.batch_search(q, rq.BruteForceSearchParams(3))[2]] == [int(i) for i in want[0][2, :3]]
 
 
+@pytest.mark.parametrize("n", [0, 33])
+def test_create_from_a_one_bit_view_with_ex_len(n):
+    """rbq_bf_create with ex_bits 0 and ex_len D / 8 (what a trained 1-bit index carries), with no vector and with 33: the handle
+    holds the view's arrays, keeps the ex_len and saves them as the crate's writer would"""
+    data, built, _, prep = make(33, 64, 1, 0, 1, 77)
+    h, a, src = built.header, built.arrays(), built.view_ptr.contents
+    assert h.ex_bits == 0 and src.n == 33 and src.ex_len == h.padded_dim // 8
+    view = rq._abi.BfView(n=n, ex_len=src.ex_len)  # (n == 0: every array null)
+    for f in (("bin_codes", "ex_codes") + rq._abi.BF_FACTORS) if n else ():
+        setattr(view, f, getattr(src, f))
+    handle = C.c_void_p()
+    bfm._check(bfm.lib().rbq_bf_create(C.cast(built.hdr_ptr, C.c_void_p), C.cast(C.pointer(view), C.c_void_p), -1, C.byref(handle)))
+    idx = rq.BruteForceRabitqIndex(handle)
+    assert len(idx) == n and idx.dim == 64
+    assert a["ex"].shape == (33, 8) and not a["ex"].any()
+    assert idx.save_to_bytes() == write_rbf1(h.dim, h.padded_dim, h.metric, h.rotator, 0, built.rotator_blob(), a["bin"][:n], a["ex"][:n],
+                                             {f: a[f][:n] for f in rq._abi.BF_FACTORS})
+    if n:
+        check(idx, prep, data[:5], 3)
+
+
 def test_train_classmethod_and_search():
     data = np.random.default_rng(6).standard_normal((100, 64)).astype(np.float32)
     idx = rq.BruteForceRabitqIndex.train(data, 7, rq.Metric.L2, rq.RotatorType.FhtKacRotator, 6, True)

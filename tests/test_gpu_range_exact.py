@@ -413,3 +413,32 @@ def test_wrapper():
             idx.range_search(qs, x, NPROBE, candidate_radius=radii[1])  # (candidate_radius goes with exact=True)
     finally:
         idx.close()
+
+
+# ---- 8. rows replaced and detached ---------------------------------------------------------------------------------------------------
+def test_reattach_and_detach():
+    """f32 host rows, f16 host rows over them, borrowed bf16 device rows over those, then none: after every step the element type,
+    and the exact range search over the rows as they are then (the rows replaced are gone, borrowed ones are not freed)"""
+    import torch
+    metric, bits, dim, n = 0, 3, 24, 100
+    idx = rq.IvfRabitqIndex.from_built(_setup(metric, bits, dim, n)[1])
+    try:
+        for kind in ("f32", "f16", "bf16"):
+            data, built, rows, qs, wrows, wq, x, radii = _setup(metric, bits, dim, n, kind)
+            if kind == "bf16":
+                d_rows = torch.from_numpy(np.ascontiguousarray(rows).view(np.int16)).cuda()
+                torch.cuda.synchronize()
+                idx.set_rerank_vectors(device_ptr=d_rows.data_ptr(), n=n, dtype=kind)
+            else:
+                idx.set_rerank_vectors(rows, dtype=kind)
+            assert idx.rerank_dtype() == kind
+            ref = _ref(metric, bits, dim, n, kind, "f32", 2)
+            assert 0 < sum(len(e[0]) for e in ref) < sum(int(d[0]) for d in xref.diag_of(ref))  # matches, and candidates rejected
+            _same(_call(idx, qs, x, radii[2], _cap(ref)), ref, _cap(ref), what=f"{kind} rows")
+        idx.set_rerank_vectors(None)
+        assert idx.rerank_dtype() is None
+        with pytest.raises(rq.RabitqError) as e:
+            _call(idx, qs, x, radii[2], _cap(ref))
+        assert e.value.detail == "exact range search needs raw vectors attached (rbq_index_set_rerank_vectors) or range_exact 0"
+    finally:
+        idx.close()
