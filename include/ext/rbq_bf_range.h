@@ -3,7 +3,7 @@
  * distance to a query is below a radius.  The brute-force index evaluates every vector for every query, so the answer loses
  * nothing to probing.  No counterpart in lqhl/rabitq-rs.  A header of its own under include/ext/, included as
  * "ext/rbq_bf_range.h": rbq_bf.h and the set of headers in include/ itself stay as they are.  The entry is exported by the
- * same library.
+ * same library.  The raw rows attached here also serve the exact top-k search at the end of this header.
  */
 #ifndef RBQ_BF_RANGE_H
 #define RBQ_BF_RANGE_H
@@ -70,6 +70,24 @@ int rbq_bf_rerank_dtype(const rbq_bf_index* idx);
 int rbq_bf_range_exact_batch(const rbq_bf_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t capacity, float x,
                              float candidate_radius, const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids,
                              float* out_scores, uint32_t* out_counts);
+
+/* ---- exact top-k search against the attached raw vectors ------------------------------------------------
+ * The nearest neighbours decided by the raw rows.  Per query, with P = max(pool, top_k) <= 4096:
+ *  1. The candidate pool is exactly what rbq_bf_search_batch returns at top_k := P with the same filter: the best P estimates with
+ *     the crate's heap and its ties, fewer where the filter or the index leaves fewer.
+ *  2. Every pool entry is scored against raw row [id] by the canonical sums (l2_distance_sqr / dot of src/math.rs, bit for bit):
+ *     d = l2_distance_sqr (L2) or -dot (inner product).  An entry whose d is not finite is dropped.
+ *  3. The survivors are ordered by d ascending (-0.0 and +0.0 are one value), then by id ascending; the first top_k are written:
+ *     out_scores holds d (L2) or -d (inner product), unused slots are UINT64_MAX / NaN, out_counts[q] = min(top_k, survivors).
+ *     The same call gives the same bytes every time.
+ *   queries [nq][query_dim] host f32; out_ids [nq][top_k] u64, out_scores [nq][top_k] f32, out_counts [nq] u32, host.
+ * Errors, all before the first HIP call: those of rbq_bf_search_batch up to nq == 0 (RBQ_OK) in its order; top_k == 0 zeroes the
+ * counts and returns RBQ_OK; then RBQ_INVALID_CONFIG with the detail set when no raw vectors are attached — nothing is silently
+ * approximated —, for P > 4096, for nq >= 2^31 and for a null buffer.  Re-entrant on one handle like rbq_bf_search_batch (but not
+ * with rbq_bf_set_rerank_vectors).  Never aborts: device failures are RBQ_DEVICE. */
+int rbq_bf_search_exact_batch(const rbq_bf_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                              uint32_t pool, const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores,
+                              uint32_t* out_counts);
 
 #ifdef __cplusplus
 }

@@ -142,20 +142,23 @@ class BruteForceRabitqIndex:
     def padded_dim(self):
         return lib().rbq_bf_padded_dim(self._h)
 
-    def batch_search_raw(self, queries, params, filter_words=None, filter_nbits=0):
-        """Returns (ids[nq,k] u64, scores[nq,k] f32, counts[nq] u32)."""
+    def _top_k_rows(self, entry, queries, k, filter_words, filter_nbits):
+        """One top-k call: entry(handle, queries, nq, dim, *(top_k ...), filter words, filter bits, ids, scores, counts) over fresh rows."""
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
         nq, qd = q.shape
-        k = int(params.top_k)
-        ids = np.full((nq, k), np.iinfo(np.uint64).max, np.uint64)
-        scores = np.full((nq, k), np.nan, np.float32)
+        ids = np.full((nq, k[0]), np.iinfo(np.uint64).max, np.uint64)
+        scores = np.full((nq, k[0]), np.nan, np.float32)
         counts = np.zeros(nq, np.uint32)
         fw = np.ascontiguousarray(filter_words, dtype=np.uint32) if filter_words is not None else None
-        _check(lib().rbq_bf_search_batch(self._h, q.ctypes.data, nq, qd, k, fw.ctypes.data if fw is not None else None,
-                                         int(filter_nbits), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        _check(entry(self._h, q.ctypes.data, nq, qd, *k, fw.ctypes.data if fw is not None else None,
+                     int(filter_nbits), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
         return ids, scores, counts
+
+    def batch_search_raw(self, queries, params, filter_words=None, filter_nbits=0):
+        """Returns (ids[nq,k] u64, scores[nq,k] f32, counts[nq] u32)."""
+        return self._top_k_rows(lib().rbq_bf_search_batch, queries, (int(params.top_k),), filter_words, filter_nbits)
 
     @staticmethod
     def _results(ids, scores, counts, q):
@@ -175,6 +178,28 @@ class BruteForceRabitqIndex:
     def batch_search(self, queries, params):
         """`search` for every row of `queries`, results in input order."""
         ids, scores, counts = self.batch_search_raw(queries, params)
+        return [self._results(ids, scores, counts, q) for q in range(ids.shape[0])]
+
+    # -- exact top-k (rbq_bf_search_exact_batch of include/ext/rbq_bf_range.h, DESIGN.md section 42) ----------------------
+    def batch_search_exact_raw(self, queries, params, pool=None, filter_words=None, filter_nbits=0):
+        """rbq_bf_search_exact_batch as it is: (ids [nq, k] u64, scores [nq, k] f32, counts [nq] u32).  The pool of every query —
+        the best max(pool, top_k) <= 4096 estimates, what batch_search_raw returns at that top_k with the same filter — is scored
+        against the raw vectors attached with set_rerank_vectors; a row holds the first top_k entries by (exact distance, id) with
+        their exact scores, the other slots are UINT64_MAX / NaN.  pool=None: params.top_k, the estimate's own top-k re-sorted
+        exactly."""
+        k = int(params.top_k)
+        return self._top_k_rows(lib_ext().rbq_bf_search_exact_batch, queries, (k, k if pool is None else int(pool)), filter_words, filter_nbits)
+
+    def search_exact(self, query, params, pool=None, allowed_ids=None):
+        """`search` / `search_filtered` decided by the raw vectors: batch_search_exact_raw for one query; `allowed_ids` as
+        search_filtered."""
+        words, nbits = _filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
+        ids, scores, counts = self.batch_search_exact_raw(np.asarray(query, np.float32)[None, :], params, pool, words, nbits)
+        return self._results(ids, scores, counts, 0)
+
+    def batch_search_exact(self, queries, params, pool=None):
+        """`search_exact` for every row of `queries`, results in input order."""
+        ids, scores, counts = self.batch_search_exact_raw(queries, params, pool)
         return [self._results(ids, scores, counts, q) for q in range(ids.shape[0])]
 
     # -- range search (include/ext/rbq_bf_range.h, DESIGN.md section 39) ------------------------------------------------

@@ -2,9 +2,11 @@
 // Host side: validation, upload, training on the device (rbq_bf_train_device), RBF1 in / out, and per search call: queries -> k_prep (rotation + QueryPrecomputed constants, shared with
 // the IVF path) -> for each chunk of vectors k_bf_dist + k_bf_select (bf.hpp) -> results; the range search (rbq_bf_range_batch)
 // runs k_bf_range_count + k_bf_range_place (bf_range.hpp) behind k_bf_dist instead, the exact one (rbq_bf_range_exact_batch, raw rows
-// attached with rbq_bf_set_rerank_vectors) k_bf_range_exact (bf_range_exact.hpp) in k_bf_range_count's place.  The chunks and
+// attached with rbq_bf_set_rerank_vectors) k_bf_range_exact (bf_range_exact.hpp) in k_bf_range_count's place; the exact top-k
+// (rbq_bf_search_exact_batch) runs the search's chain at top_k := its pool and k_bf_rerank_score + k_bf_rerank_order (bf_rerank.hpp)
+// behind a sub-batch's last k_bf_select.  The chunks and
 // sub-batches of a call are decided in csrc/host/rbq_bf_plan.hpp (plan_bf_call, pure host code); bf_run_call is the one loop that
-// walks them, and the three kinds of call hand it only what differs.  Each call takes a workspace and a stream of its own from the
+// walks them, and the kinds of call hand it only what differs.  Each call takes a workspace and a stream of its own from the
 // handle's pool, so calls on one handle may overlap.
 #include <optional>
 
@@ -247,35 +249,68 @@ int bf_run_call(rbq_bf_index* ix, const rbq_host::BfCallPlan& pl, const float* q
     return RBQ_OK;
 }
 
-int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t top_k, const uint32_t* filter_words, uint64_t filter_nbits,
-                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
-    const rbq_host::BfCallPlan pl = bf_plan(ix, nq, /*range=*/false, top_k);
-    const uint64_t K = top_k, sub = pl.sub;
+// The select of a top-k call at K entries per query, for the two calls that run it (the search, and the exact search at K := its
+// pool): the buffers of a sub-batch's heaps and K-wide rows with the heap statistics cleared, and k_bf_select behind k_bf_dist of
+// chunk c, its counts going to `counts`.
+int bf_select_setup(const rbq_host::BfCallPlan& pl, uint64_t K, BfWorkspace* w, hipStream_t st) {
+    const uint64_t sub = pl.sub;
+    int rc;
+    if ((rc = w->heap_len.ensure(sub * 4)) || (rc = w->ids.ensure(sub * K * 8)) || (rc = w->scores.ensure(sub * K * 4)) || (rc = w->stats.ensure(16)))
+        return rc;
+    if (pl.heap_ws && ((rc = w->heap_d.ensure(sub * (K + 1) * 4)) || (rc = w->heap_s.ensure(sub * (K + 1) * 4)))) return rc;
+    HIP_TRY(hipMemsetAsync(w->stats.p, 0, 16, st));
+    return RBQ_OK;
+}
+int bf_select_chunk(const rbq_bf_index* ix, const rbq_host::BfCallPlan& pl, uint32_t K, BfWorkspace* w, hipStream_t st, uint32_t m, uint64_t c,
+                    uint64_t v0, uint64_t nv, uint32_t* counts) {
+    BfSelectParams sp;
+    sp.dist = (const float*)w->dist.p; sp.nq = m; sp.top_k = K; sp.v0 = v0; sp.nv = nv; sp.metric = ix->hdr.metric;
+    sp.first = c == 0; sp.last = c + 1 == pl.n_chunks; sp.lds_heap = pl.lds_heap;
+    sp.heap_d = (float*)w->heap_d.p; sp.heap_s = (uint32_t*)w->heap_s.p; sp.heap_len = (uint32_t*)w->heap_len.p;
+    sp.out_ids = (uint64_t*)w->ids.p; sp.out_scores = (float*)w->scores.p; sp.out_counts = counts;
+    sp.stats = (unsigned long long*)w->stats.p;
+    HIP_TRY(launch_bf_select(sp, st));
+    g_bf_select_launches.fetch_add(1, std::memory_order_relaxed);
+    return RBQ_OK;
+}
+
+// exact_pool 0: rbq_bf_search_batch.  Else rbq_bf_search_exact_batch (include/ext/rbq_bf_range.h) at the pool
+// P = exact_pool >= top_k: the same plan and the same select at K := P, its counts kept apart; behind the last chunk of a sub-batch
+// k_bf_rerank_score -> k_bf_rerank_order (bf_rerank.hpp) score the pool against the handle's raw rows and write the top_k-wide rows
+// and the counts, which go back in the select's rows' place.
+int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t top_k, uint32_t exact_pool, const uint32_t* filter_words,
+                   uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+    const uint32_t K = exact_pool ? exact_pool : top_k;
+    const rbq_host::BfCallPlan pl = bf_plan(ix, nq, /*range=*/false, K);
+    const uint64_t sub = pl.sub, k = top_k;
+    uint32_t np2 = 1;
+    while (np2 < K) np2 <<= 1;
     uint64_t stats[2] = {0, 0};
     const int rc = bf_run_call(
         ix, pl, queries, nq, filter_words, filter_nbits, out_counts,
         [&](BfWorkspace* w, hipStream_t st) -> int {
             int rc;
-            if ((rc = w->heap_len.ensure(sub * 4)) || (rc = w->ids.ensure(sub * K * 8)) || (rc = w->scores.ensure(sub * K * 4)) || (rc = w->stats.ensure(16)))
+            if (exact_pool && ((rc = w->pool_counts.ensure(sub * 4)) || (rc = w->exact.ensure(sub * K * 4)) || (rc = w->top_ids.ensure(sub * k * 8)) ||
+                               (rc = w->top_scores.ensure(sub * k * 4))))
                 return rc;
-            if (pl.heap_ws && ((rc = w->heap_d.ensure(sub * (K + 1) * 4)) || (rc = w->heap_s.ensure(sub * (K + 1) * 4)))) return rc;
-            HIP_TRY(hipMemsetAsync(w->stats.p, 0, 16, st));
-            return RBQ_OK;
+            return bf_select_setup(pl, K, w, st);
         },
         [&](BfWorkspace* w, hipStream_t st, uint32_t m, uint64_t c, uint64_t v0, uint64_t nv) -> int {
-            BfSelectParams sp;
-            sp.dist = (const float*)w->dist.p; sp.nq = m; sp.top_k = top_k; sp.v0 = v0; sp.nv = nv; sp.metric = ix->hdr.metric;
-            sp.first = c == 0; sp.last = c + 1 == pl.n_chunks; sp.lds_heap = pl.lds_heap;
-            sp.heap_d = (float*)w->heap_d.p; sp.heap_s = (uint32_t*)w->heap_s.p; sp.heap_len = (uint32_t*)w->heap_len.p;
-            sp.out_ids = (uint64_t*)w->ids.p; sp.out_scores = (float*)w->scores.p; sp.out_counts = (uint32_t*)w->counts.p;
-            sp.stats = (unsigned long long*)w->stats.p;
-            HIP_TRY(launch_bf_select(sp, st));
-            g_bf_select_launches.fetch_add(1, std::memory_order_relaxed);
+            int rc;
+            if ((rc = bf_select_chunk(ix, pl, K, w, st, m, c, v0, nv, (uint32_t*)(exact_pool ? w->pool_counts.p : w->counts.p)))) return rc;
+            if (!exact_pool || c + 1 != pl.n_chunks) return RBQ_OK;
+            BfRerankParams rp;
+            rp.queries = (const float*)w->q.p; rp.raw = ix->raw.p; rp.n_raw = ix->n_raw; rp.nq = m; rp.dim = ix->hdr.dim;
+            rp.pool = K; rp.pool_np2 = np2; rp.top_k = top_k; rp.metric = ix->hdr.metric; rp.raw_dtype = ix->raw_dtype;
+            rp.pool_ids = (const uint64_t*)w->ids.p; rp.pool_counts = (const uint32_t*)w->pool_counts.p; rp.exact = (float*)w->exact.p;
+            rp.out_ids = (uint64_t*)w->top_ids.p; rp.out_scores = (float*)w->top_scores.p; rp.out_counts = (uint32_t*)w->counts.p;
+            HIP_TRY(launch_bf_rerank_score(rp, st));
+            HIP_TRY(launch_bf_rerank_order(rp, ix->device, st));
             return RBQ_OK;
         },
         [&](BfWorkspace* w, hipStream_t st, uint64_t q0, uint32_t m) -> int {
-            HIP_TRY(hipMemcpyAsync(out_ids + q0 * K, w->ids.p, (size_t)m * K * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_scores + q0 * K, w->scores.p, (size_t)m * K * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_ids + q0 * k, exact_pool ? w->top_ids.p : w->ids.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_scores + q0 * k, exact_pool ? w->top_scores.p : w->scores.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, st));
             return RBQ_OK;
         },
         [&](BfWorkspace* w, hipStream_t st) -> int {
@@ -441,6 +476,8 @@ uint64_t rbq_bf_debug_select_launches(void) { return g_bf_select_launches.load(s
 // The checks of the search entries, in the order callers see them:
 //   rbq_bf_search_batch:   null index, empty index, dimension, nq == 0 (OK) | top_k == 0 (counts zeroed, OK), top_k > 16384 |
 //                          nq >= 2^31 | null buffer | the device
+//   rbq_bf_search_exact_batch: null index, empty index, dimension, nq == 0 (OK) | top_k == 0 (counts zeroed, OK), raw vectors
+//                          attached, max(pool, top_k) > 4096 | nq >= 2^31 | null buffer | the device
 //   the two range entries: null index, empty index, dimension, nq == 0 (OK) | raw vectors attached (exact) |
 //                          nq >= 2^31 | null buffer, x is NaN, radius is NaN | the device
 // bf_entry_prefix is the first group of either, and bf_run_call switches to the device before anything else, which is the last;
@@ -472,7 +509,28 @@ int rbq_bf_search_batch(const rbq_bf_index* ch, const float* queries, uint64_t n
     if (top_k > kBfTopKMax) return fail(RBQ_INVALID_CONFIG, "top_k > 16384 is not supported by the brute-force index");
     if (nq >= (1ull << 31)) return fail(RBQ_INVALID_CONFIG, "nq >= 2^31");
     if (!queries || !out_ids || !out_scores || !out_counts) return fail(RBQ_INVALID_CONFIG, "null buffer");
-    return bf_search_impl(ix, queries, nq, top_k, filter_words, filter_nbits, out_ids, out_scores, out_counts);
+    return bf_search_impl(ix, queries, nq, top_k, /*exact_pool=*/0, filter_words, filter_nbits, out_ids, out_scores, out_counts);
+    RBQ_GUARD_END
+}
+
+int rbq_bf_search_exact_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t pool,
+                              const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores,
+                              uint32_t* out_counts) {
+    g_err.clear();
+    RBQ_GUARD_BEGIN
+    rbq_bf_index* ix;
+    const int rc = bf_entry_prefix(ch, query_dim, nq, &ix);
+    if (!ix) return rc;
+    if (top_k == 0) {
+        if (out_counts) std::memset(out_counts, 0, nq * 4);
+        return RBQ_OK;
+    }
+    if (!ix->raw.p) return fail(RBQ_INVALID_CONFIG, "exact search needs raw vectors attached (rbq_bf_set_rerank_vectors)");
+    const uint32_t P = std::max(pool, top_k);
+    if (P > kBfRerankPoolMax) return fail(RBQ_INVALID_CONFIG, "max(pool, top_k) > 4096 is not supported by the exact brute-force search");
+    if (nq >= (1ull << 31)) return fail(RBQ_INVALID_CONFIG, "nq >= 2^31");
+    if (!queries || !out_ids || !out_scores || !out_counts) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    return bf_search_impl(ix, queries, nq, top_k, P, filter_words, filter_nbits, out_ids, out_scores, out_counts);
     RBQ_GUARD_END
 }
 

@@ -11,6 +11,8 @@ struct BfWorkspace { // what one search call holds: a stream and its buffers, fr
     hipStream_t stream = nullptr;
     DevBuf q, rot, lut, consts, dist, heap_d, heap_s, heap_len, filter, ids, scores, counts, stats;
     DevBuf span_counts, running; // range search: matches per (query, span) of a chunk; per query over the chunks so far (two arrays)
+    // exact top-k: the select's counts (`counts` holds the result's), the pool's exact distances, the top_k-wide result rows
+    DevBuf pool_counts, exact, top_ids, top_scores;
     BfWorkspace() = default;
     BfWorkspace(const BfWorkspace&) = delete;
     ~BfWorkspace() { if (stream) (void)hipStreamDestroy(stream); } // (deleted under the index's DeviceGuard)

@@ -343,6 +343,31 @@ struct BfRangeExactParams {
     uint32_t* span_counts;     // [nq][n_spans]: the exact matches of every span, for the place launch
 };
 hipError_t launch_bf_range_exact(const BfRangeExactParams& p, hipStream_t s);
+// exact brute-force top-k (bf_rerank.hpp, k_bf_rerank.hip): behind the last launch_bf_select of a sub-batch
+// at top_k := pool.  launch_bf_rerank_score scores every pool entry against its raw row, one workgroup per (slice of
+// kBfRerankSlice entries, query); launch_bf_rerank_order then orders a query's pool by (distance, id) in one workgroup.
+constexpr uint32_t kBfRerankPoolMax = 4096; // the figure of kRerankPoolMax / kMrPoolMax, for their reason
+constexpr uint32_t kBfRerankSlice = 128;    // pool entries per workgroup of the score kernel: four passes of 32 entries
+struct BfRerankParams {
+    const float* queries;        // [nq][dim] f32, input space
+    const void* raw;             // [n_raw][dim] elements of raw_dtype: row i belongs to vector id i
+    uint64_t n_raw;
+    uint32_t nq, dim;
+    uint32_t pool, pool_np2;     // pool_np2: the power of two >= pool (<= kBfRerankPoolMax)
+    uint32_t top_k;              // 1 <= top_k <= pool
+    int metric;
+    int raw_dtype;               // kRawF32 / kRawF16 / kRawBf16
+    uint32_t raw_by_element = 0; // set by the launch (raw_rows_by_element)
+    const uint64_t* pool_ids;    // [nq][pool]: launch_bf_select's out_ids, ascending by estimate
+    const uint32_t* pool_counts; // [nq]: its out_counts
+    float* exact;                // [nq][pool]: the distance of every pool entry (score writes, order reads), NaN for a dropped one
+    uint64_t* out_ids;           // [nq][top_k]
+    float* out_scores;
+    uint32_t* out_counts;        // [nq]
+};
+size_t bf_rerank_order_lds_bytes(uint32_t pool_np2);
+hipError_t launch_bf_rerank_score(const BfRerankParams& p, hipStream_t s);
+hipError_t launch_bf_rerank_order(const BfRerankParams& p, int device, hipStream_t s); // after launch_bf_rerank_score on the same stream
 // k_bf_train.hip: BruteForceRabitqIndex::train.  launch_bf_encode: k_encode's flat mode over P.nslots rotated rows (see
 // EncodeParams; P.t_row != null: the per-vector rescale factors of launch_rescale).  launch_bf_pack_ex: raw ex codes [nrows][D]
 // u8 -> the crate's ex_code_packed [nrows][D * ex_bits / 8] (ex_bits 2 or 6)
