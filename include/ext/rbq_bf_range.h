@@ -89,6 +89,19 @@ int rbq_bf_search_exact_batch(const rbq_bf_index* idx, const float* queries, uin
                               uint32_t pool, const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores,
                               uint32_t* out_counts);
 
+/* ---- the same search with the pool chosen by rank --------------------------------------------------------
+ * rbq_bf_search_exact_batch with another rule for step 1, for callers that want the exact neighbours and not the crate's tie
+ * behaviour inside the pool:
+ *  1. The candidates are the vectors the filter lets through whose estimate d — the distance rbq_bf_search_batch ranks, bit for
+ *     bit — is finite.  The pool is the first min(P, candidates) of them by the key (f32::total_cmp order of d, id ascending):
+ *     the heap's comparison, but among EQUAL estimates at the pool's boundary the smallest ids win.  A radix select over the
+ *     distances finds it, no heap: rbq_bf_debug_select_launches() and the handle's heap statistics do not move.
+ *  2, 3. As above; the same call gives the same bytes every time, whatever the cut into sub-batches and chunks.
+ * Parameters, buffers, errors (their order and texts) and re-entrancy are those of rbq_bf_search_exact_batch. */
+int rbq_bf_search_exact_ranked_batch(const rbq_bf_index* idx, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k,
+                                     uint32_t pool, const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids,
+                                     float* out_scores, uint32_t* out_counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -257,6 +257,7 @@ LIBRBQ_BF_EXT_BY_HEADER = {
         "rbq_bf_rerank_dtype": (_INT, [_VP]),
         "rbq_bf_range_exact_batch": (_INT, [_VP, _VP, _U64, _U32, _U32, _F32, _F32, _VP, _U64, _VP, _VP, _VP]),
         "rbq_bf_search_exact_batch": (_INT, [_VP, _VP, _U64, _U32, _U32, _U32, _VP, _U64, _VP, _VP, _VP]),
+        "rbq_bf_search_exact_ranked_batch": (_INT, [_VP, _VP, _U64, _U32, _U32, _U32, _VP, _U64, _VP, _VP, _VP]),
     },
 }
 LIBRBQ_BF_EXT = {name: proto for group in LIBRBQ_BF_EXT_BY_HEADER.values() for name, proto in group.items()}

@@ -180,26 +180,32 @@ class BruteForceRabitqIndex:
         ids, scores, counts = self.batch_search_raw(queries, params)
         return [self._results(ids, scores, counts, q) for q in range(ids.shape[0])]
 
-    # -- exact top-k (rbq_bf_search_exact_batch of include/ext/rbq_bf_range.h) ----------------------
-    def batch_search_exact_raw(self, queries, params, pool=None, filter_words=None, filter_nbits=0):
+    # -- exact top-k (rbq_bf_search_exact_batch / _ranked_batch of include/ext/rbq_bf_range.h, DESIGN.md sections 42, 43) ----------------------
+    def batch_search_exact_raw(self, queries, params, pool=None, filter_words=None, filter_nbits=0, pool_rule="heap"):
         """rbq_bf_search_exact_batch as it is: (ids [nq, k] u64, scores [nq, k] f32, counts [nq] u32).  The pool of every query —
         the best max(pool, top_k) <= 4096 estimates, what batch_search_raw returns at that top_k with the same filter — is scored
         against the raw vectors attached with set_rerank_vectors; a row holds the first top_k entries by (exact distance, id) with
         their exact scores, the other slots are UINT64_MAX / NaN.  pool=None: params.top_k, the estimate's own top-k re-sorted
-        exactly."""
+        exactly.
+        pool_rule="rank": rbq_bf_search_exact_ranked_batch — the pool is the best estimates by (estimate,
+        id), found by a radix select and no heap replay; it differs from the heap's only among equal estimates at the pool's
+        boundary, where the smallest ids win."""
+        if pool_rule not in ("heap", "rank"):
+            raise ValueError("pool_rule must be 'heap' or 'rank', got %r" % (pool_rule,))
+        entry = lib_ext().rbq_bf_search_exact_batch if pool_rule == "heap" else lib_ext().rbq_bf_search_exact_ranked_batch
         k = int(params.top_k)
-        return self._top_k_rows(lib_ext().rbq_bf_search_exact_batch, queries, (k, k if pool is None else int(pool)), filter_words, filter_nbits)
+        return self._top_k_rows(entry, queries, (k, k if pool is None else int(pool)), filter_words, filter_nbits)
 
-    def search_exact(self, query, params, pool=None, allowed_ids=None):
+    def search_exact(self, query, params, pool=None, allowed_ids=None, pool_rule="heap"):
         """`search` / `search_filtered` decided by the raw vectors: batch_search_exact_raw for one query; `allowed_ids` as
         search_filtered."""
         words, nbits = _filter_words(allowed_ids) if allowed_ids is not None else (None, 0)
-        ids, scores, counts = self.batch_search_exact_raw(np.asarray(query, np.float32)[None, :], params, pool, words, nbits)
+        ids, scores, counts = self.batch_search_exact_raw(np.asarray(query, np.float32)[None, :], params, pool, words, nbits, pool_rule=pool_rule)
         return self._results(ids, scores, counts, 0)
 
-    def batch_search_exact(self, queries, params, pool=None):
+    def batch_search_exact(self, queries, params, pool=None, pool_rule="heap"):
         """`search_exact` for every row of `queries`, results in input order."""
-        ids, scores, counts = self.batch_search_exact_raw(queries, params, pool)
+        ids, scores, counts = self.batch_search_exact_raw(queries, params, pool, pool_rule=pool_rule)
         return [self._results(ids, scores, counts, q) for q in range(ids.shape[0])]
 
     # -- range search (include/ext/rbq_bf_range.h, DESIGN.md section 39) ------------------------------------------------

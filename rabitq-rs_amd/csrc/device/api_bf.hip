@@ -4,7 +4,8 @@
 // runs k_bf_range_count + k_bf_range_place (bf_range.hpp) behind k_bf_dist instead, the exact one (rbq_bf_range_exact_batch, raw rows
 // attached with rbq_bf_set_rerank_vectors) k_bf_range_exact (bf_range_exact.hpp) in k_bf_range_count's place; the exact top-k
 // (rbq_bf_search_exact_batch) runs the search's chain at top_k := its pool and k_bf_rerank_score + k_bf_rerank_order (bf_rerank.hpp)
-// behind a sub-batch's last k_bf_select.  The chunks and
+// behind a sub-batch's last k_bf_select; its ranked variant (rbq_bf_search_exact_ranked_batch) forms the pool with the radix select
+// of bf_pool.hpp in k_bf_select's place.  The chunks and
 // sub-batches of a call are decided in csrc/host/rbq_bf_plan.hpp (plan_bf_call, pure host code); bf_run_call is the one loop that
 // walks them, and the kinds of call hand it only what differs.  Each call takes a workspace and a stream of its own from the
 // handle's pool, so calls on one handle may overlap.
@@ -274,6 +275,34 @@ int bf_select_chunk(const rbq_bf_index* ix, const rbq_host::BfCallPlan& pl, uint
     return RBQ_OK;
 }
 
+// The rerank of a pool of K entries per query down to top_k, for the two exact top-k calls: its buffers; k_bf_rerank_score ->
+// k_bf_rerank_order (bf_rerank.hpp) over the pool in w->ids / w->pool_counts of a sub-batch's m queries, which score it against the
+// handle's raw rows and write the top_k-wide rows and w->counts; and the rows of a sub-batch back to the caller.
+int bf_rerank_setup(uint64_t sub, uint64_t K, uint64_t top_k, BfWorkspace* w) {
+    int rc;
+    if ((rc = w->pool_counts.ensure(sub * 4)) || (rc = w->exact.ensure(sub * K * 4)) || (rc = w->top_ids.ensure(sub * top_k * 8)) ||
+        (rc = w->top_scores.ensure(sub * top_k * 4)))
+        return rc;
+    return RBQ_OK;
+}
+int bf_rerank_pool(const rbq_bf_index* ix, uint32_t K, uint32_t top_k, BfWorkspace* w, hipStream_t st, uint32_t m) {
+    uint32_t np2 = 1;
+    while (np2 < K) np2 <<= 1;
+    BfRerankParams rp;
+    rp.queries = (const float*)w->q.p; rp.raw = ix->raw.p; rp.n_raw = ix->n_raw; rp.nq = m; rp.dim = ix->hdr.dim;
+    rp.pool = K; rp.pool_np2 = np2; rp.top_k = top_k; rp.metric = ix->hdr.metric; rp.raw_dtype = ix->raw_dtype;
+    rp.pool_ids = (const uint64_t*)w->ids.p; rp.pool_counts = (const uint32_t*)w->pool_counts.p; rp.exact = (float*)w->exact.p;
+    rp.out_ids = (uint64_t*)w->top_ids.p; rp.out_scores = (float*)w->top_scores.p; rp.out_counts = (uint32_t*)w->counts.p;
+    HIP_TRY(launch_bf_rerank_score(rp, st));
+    HIP_TRY(launch_bf_rerank_order(rp, ix->device, st));
+    return RBQ_OK;
+}
+int bf_top_k_rows(const DevBuf& ids, const DevBuf& scores, uint64_t k, hipStream_t st, uint64_t q0, uint32_t m, uint64_t* out_ids, float* out_scores) {
+    HIP_TRY(hipMemcpyAsync(out_ids + q0 * k, ids.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_scores + q0 * k, scores.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, st));
+    return RBQ_OK;
+}
+
 // exact_pool 0: rbq_bf_search_batch.  Else rbq_bf_search_exact_batch (include/ext/rbq_bf_range.h) at the pool
 // P = exact_pool >= top_k: the same plan and the same select at K := P, its counts kept apart; behind the last chunk of a sub-batch
 // k_bf_rerank_score -> k_bf_rerank_order (bf_rerank.hpp) score the pool against the handle's raw rows and write the top_k-wide rows
@@ -283,35 +312,22 @@ int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t
     const uint32_t K = exact_pool ? exact_pool : top_k;
     const rbq_host::BfCallPlan pl = bf_plan(ix, nq, /*range=*/false, K);
     const uint64_t sub = pl.sub, k = top_k;
-    uint32_t np2 = 1;
-    while (np2 < K) np2 <<= 1;
     uint64_t stats[2] = {0, 0};
     const int rc = bf_run_call(
         ix, pl, queries, nq, filter_words, filter_nbits, out_counts,
         [&](BfWorkspace* w, hipStream_t st) -> int {
             int rc;
-            if (exact_pool && ((rc = w->pool_counts.ensure(sub * 4)) || (rc = w->exact.ensure(sub * K * 4)) || (rc = w->top_ids.ensure(sub * k * 8)) ||
-                               (rc = w->top_scores.ensure(sub * k * 4))))
-                return rc;
+            if (exact_pool && (rc = bf_rerank_setup(sub, K, k, w))) return rc;
             return bf_select_setup(pl, K, w, st);
         },
         [&](BfWorkspace* w, hipStream_t st, uint32_t m, uint64_t c, uint64_t v0, uint64_t nv) -> int {
             int rc;
             if ((rc = bf_select_chunk(ix, pl, K, w, st, m, c, v0, nv, (uint32_t*)(exact_pool ? w->pool_counts.p : w->counts.p)))) return rc;
             if (!exact_pool || c + 1 != pl.n_chunks) return RBQ_OK;
-            BfRerankParams rp;
-            rp.queries = (const float*)w->q.p; rp.raw = ix->raw.p; rp.n_raw = ix->n_raw; rp.nq = m; rp.dim = ix->hdr.dim;
-            rp.pool = K; rp.pool_np2 = np2; rp.top_k = top_k; rp.metric = ix->hdr.metric; rp.raw_dtype = ix->raw_dtype;
-            rp.pool_ids = (const uint64_t*)w->ids.p; rp.pool_counts = (const uint32_t*)w->pool_counts.p; rp.exact = (float*)w->exact.p;
-            rp.out_ids = (uint64_t*)w->top_ids.p; rp.out_scores = (float*)w->top_scores.p; rp.out_counts = (uint32_t*)w->counts.p;
-            HIP_TRY(launch_bf_rerank_score(rp, st));
-            HIP_TRY(launch_bf_rerank_order(rp, ix->device, st));
-            return RBQ_OK;
+            return bf_rerank_pool(ix, K, top_k, w, st, m);
         },
         [&](BfWorkspace* w, hipStream_t st, uint64_t q0, uint32_t m) -> int {
-            HIP_TRY(hipMemcpyAsync(out_ids + q0 * k, exact_pool ? w->top_ids.p : w->ids.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_scores + q0 * k, exact_pool ? w->top_scores.p : w->scores.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, st));
-            return RBQ_OK;
+            return bf_top_k_rows(exact_pool ? w->top_ids : w->ids, exact_pool ? w->top_scores : w->scores, k, st, q0, m, out_ids, out_scores);
         },
         [&](BfWorkspace* w, hipStream_t st) -> int {
             HIP_TRY(hipMemcpyAsync(stats, w->stats.p, 16, hipMemcpyDeviceToHost, st));
@@ -319,6 +335,43 @@ int bf_search_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t
         });
     if (rc == RBQ_OK) { ix->pushes += stats[0]; ix->tie_pushes += stats[1]; }
     return rc;
+}
+
+// rbq_bf_search_exact_ranked_batch (include/ext/rbq_bf_range.h): the exact search with the pool chosen by rank
+// — the P best estimates by (total_cmp order, id) — and no heap.  The range search's plan at capacity P gives the spans of a chunk
+// and a sub-batch within the output budget; per chunk launch_bf_pool_rank (bf_pool.hpp) behind k_bf_dist, the pool so far carried
+// from chunk to chunk in two lists that alternate (w->carry, their lengths in w->running); behind the last chunk the rerank above.
+int bf_search_ranked_impl(rbq_bf_index* ix, const float* queries, uint64_t nq, uint32_t top_k, uint32_t P, const uint32_t* filter_words,
+                          uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+    const rbq_host::BfCallPlan pl = bf_plan(ix, nq, /*range=*/true, P);
+    const uint64_t sub = pl.sub, k = top_k;
+    const uint32_t carry_blocks = (P + kBfRangeSpan - 1) / kBfRangeSpan;
+    return bf_run_call(
+        ix, pl, queries, nq, filter_words, filter_nbits, out_counts,
+        [&](BfWorkspace* w, hipStream_t) -> int {
+            int rc;
+            if ((rc = bf_rerank_setup(sub, P, k, w)) || (rc = w->ids.ensure(sub * P * 8)) || (rc = w->pool_hist.ensure(sub * kBfPoolPasses * kBfPoolBins * 4)) ||
+                (rc = w->pool_state.ensure(sub * (kBfPoolPasses + 1) * 8)) || (rc = w->span_counts.ensure(2 * sub * (pl.spans + carry_blocks) * 4)))
+                return rc;
+            if (pl.n_chunks > 1 && ((rc = w->carry.ensure(2 * sub * P * 8)) || (rc = w->running.ensure(2 * sub * 4)))) return rc;
+            return RBQ_OK;
+        },
+        [&](BfWorkspace* w, hipStream_t st, uint32_t m, uint64_t c, uint64_t v0, uint64_t nv) -> int {
+            BfPoolParams pp;
+            pp.dist = (const float*)w->dist.p; pp.nq = m; pp.n_spans = (uint32_t)((nv + kBfRangeSpan - 1) / kBfRangeSpan);
+            pp.first = c == 0; pp.last = c + 1 == pl.n_chunks; pp.n_carry = pp.first ? 0u : carry_blocks;
+            pp.v0 = v0; pp.nv = nv; pp.pool = P;
+            pp.hist = (uint32_t*)w->pool_hist.p; pp.state = (uint32_t*)w->pool_state.p; pp.span_counts = (uint32_t*)w->span_counts.p;
+            unsigned long long* lists = (unsigned long long*)w->carry.p; // (null with one chunk: neither side is then used)
+            uint32_t* lens = (uint32_t*)w->running.p;
+            pp.carry_in = pp.first ? nullptr : lists + (c & 1) * sub * P; pp.carry_n_in = pp.first ? nullptr : lens + (c & 1) * sub;
+            pp.carry_out = pp.last ? nullptr : lists + ((c + 1) & 1) * sub * P; pp.carry_n_out = pp.last ? nullptr : lens + ((c + 1) & 1) * sub;
+            pp.out_ids = (uint64_t*)w->ids.p; pp.out_counts = (uint32_t*)w->pool_counts.p;
+            HIP_TRY(launch_bf_pool_rank(pp, st));
+            return pp.last ? bf_rerank_pool(ix, P, top_k, w, st, m) : RBQ_OK;
+        },
+        [&](BfWorkspace* w, hipStream_t st, uint64_t q0, uint32_t m) -> int { return bf_top_k_rows(w->top_ids, w->top_scores, k, st, q0, m, out_ids, out_scores); },
+        [&](BfWorkspace*, hipStream_t) -> int { return RBQ_OK; });
 }
 
 // rbq_bf_range_batch (include/ext/rbq_bf_range.h): the search's plan without its heap — per chunk of vectors
@@ -476,7 +529,7 @@ uint64_t rbq_bf_debug_select_launches(void) { return g_bf_select_launches.load(s
 // The checks of the search entries, in the order callers see them:
 //   rbq_bf_search_batch:   null index, empty index, dimension, nq == 0 (OK) | top_k == 0 (counts zeroed, OK), top_k > 16384 |
 //                          nq >= 2^31 | null buffer | the device
-//   rbq_bf_search_exact_batch: null index, empty index, dimension, nq == 0 (OK) | top_k == 0 (counts zeroed, OK), raw vectors
+//   rbq_bf_search_exact_batch, rbq_bf_search_exact_ranked_batch: null index, empty index, dimension, nq == 0 (OK) | top_k == 0 (counts zeroed, OK), raw vectors
 //                          attached, max(pool, top_k) > 4096 | nq >= 2^31 | null buffer | the device
 //   the two range entries: null index, empty index, dimension, nq == 0 (OK) | raw vectors attached (exact) |
 //                          nq >= 2^31 | null buffer, x is NaN, radius is NaN | the device
@@ -513,9 +566,9 @@ int rbq_bf_search_batch(const rbq_bf_index* ch, const float* queries, uint64_t n
     RBQ_GUARD_END
 }
 
-int rbq_bf_search_exact_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t pool,
-                              const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores,
-                              uint32_t* out_counts) {
+// The checks of the two exact top-k entries, in their order, then the call.  ranked: rbq_bf_search_exact_ranked_batch.
+static int bf_exact_entry(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t pool, bool ranked,
+                          const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
     g_err.clear();
     RBQ_GUARD_BEGIN
     rbq_bf_index* ix;
@@ -530,8 +583,21 @@ int rbq_bf_search_exact_batch(const rbq_bf_index* ch, const float* queries, uint
     if (P > kBfRerankPoolMax) return fail(RBQ_INVALID_CONFIG, "max(pool, top_k) > 4096 is not supported by the exact brute-force search");
     if (nq >= (1ull << 31)) return fail(RBQ_INVALID_CONFIG, "nq >= 2^31");
     if (!queries || !out_ids || !out_scores || !out_counts) return fail(RBQ_INVALID_CONFIG, "null buffer");
+    if (ranked) return bf_search_ranked_impl(ix, queries, nq, top_k, P, filter_words, filter_nbits, out_ids, out_scores, out_counts);
     return bf_search_impl(ix, queries, nq, top_k, P, filter_words, filter_nbits, out_ids, out_scores, out_counts);
     RBQ_GUARD_END
+}
+
+int rbq_bf_search_exact_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t pool,
+                              const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores,
+                              uint32_t* out_counts) {
+    return bf_exact_entry(ch, queries, nq, query_dim, top_k, pool, /*ranked=*/false, filter_words, filter_nbits, out_ids, out_scores, out_counts);
+}
+
+int rbq_bf_search_exact_ranked_batch(const rbq_bf_index* ch, const float* queries, uint64_t nq, uint32_t query_dim, uint32_t top_k, uint32_t pool,
+                                     const uint32_t* filter_words, uint64_t filter_nbits, uint64_t* out_ids, float* out_scores,
+                                     uint32_t* out_counts) {
+    return bf_exact_entry(ch, queries, nq, query_dim, top_k, pool, /*ranked=*/true, filter_words, filter_nbits, out_ids, out_scores, out_counts);
 }
 
 // The checks of the two range entries, in their order, then the call.  exact_x null: rbq_bf_range_batch at `radius`; else

@@ -13,6 +13,9 @@ struct BfWorkspace { // what one search call holds: a stream and its buffers, fr
     DevBuf span_counts, running; // range search: matches per (query, span) of a chunk; per query over the chunks so far (two arrays)
     // exact top-k: the select's counts (`counts` holds the result's), the pool's exact distances, the top_k-wide result rows
     DevBuf pool_counts, exact, top_ids, top_scores;
+    // ranked pool (bf_pool.hpp): the histograms of a chunk's four passes, the select state after every pass, and the two carried
+    // lists of a call with more than one chunk (their lengths in `running`, the blocks' two counts in `span_counts`)
+    DevBuf pool_hist, pool_state, carry;
     BfWorkspace() = default;
     BfWorkspace(const BfWorkspace&) = delete;
     ~BfWorkspace() { if (stream) (void)hipStreamDestroy(stream); } // (deleted under the index's DeviceGuard)

@@ -7,6 +7,7 @@
 //   k_range_exact.hip  k_range<0, 0, V, XR, XIP>: the same scan, its matches decided by the raw rows  (range.hpp, rerank_score.hpp)
 //   k_bf_range.hip  brute-force range search: matches counted per span, then placed in id order  (bf_range.hpp, range_common.hpp)
 //   k_bf_range_exact.hip  exact brute-force range search: a span's candidates scored against the raw rows  (bf_range_exact.hpp, rerank_score.hpp)
+//   k_bf_pool.hip  ranked rerank pool of the exact brute-force top-k: radix select over spans, then count and place  (bf_pool.hpp)
 //   k_build.hip  encoder, reference-layout -> device-layout converters, sorting   (encode.hpp)
 //   k_gemm_shortlist.hip  the front of the GEMM-shortlist paths (finite check, norms, split images, dots), KmGemmAssign (km_common.hpp)
 //   k_kmeans.hip Faiss-style k-means (run_kmeans_with_config) and its host driver         (km_common.hpp)
@@ -368,6 +369,30 @@ struct BfRerankParams {
 size_t bf_rerank_order_lds_bytes(uint32_t pool_np2);
 hipError_t launch_bf_rerank_score(const BfRerankParams& p, hipStream_t s);
 hipError_t launch_bf_rerank_order(const BfRerankParams& p, int device, hipStream_t s); // after launch_bf_rerank_score on the same stream
+// ranked rerank pool of the exact brute-force top-k (bf_pool.hpp, k_bf_pool.hip): behind launch_bf_dist of
+// every chunk, in launch_bf_select's place.  Per query the pool best candidates by (total_cmp order of the distance, id), found by
+// an 8-bit radix select over the blocks of a (sub-batch, chunk): the chunk's spans of kBfRangeSpan vectors and, ahead of them, the
+// query's pool so far as carried from the earlier chunks.  launch_bf_pool_rank enqueues the whole chain of a chunk: the histograms
+// cleared, kBfPoolPasses histogram launches, the count and the place launch.
+constexpr uint32_t kBfPoolDigitBits = 8, kBfPoolBins = 1u << kBfPoolDigitBits, kBfPoolPasses = 4;
+struct BfPoolParams {
+    const float* dist;                   // [nq][nv] (launch_bf_dist)
+    uint32_t nq, n_spans;                // n_spans = ceil(nv / kBfRangeSpan)
+    uint32_t n_carry;                    // blocks of carried entries ahead of span 0: 0 when first, else ceil(pool / kBfRangeSpan)
+    uint64_t v0, nv;
+    uint32_t pool;                       // 1 <= pool <= kBfRerankPoolMax
+    int first, last;                     // first / last vector chunk of the call
+    uint32_t* hist;                      // [kBfPoolPasses][nq][kBfPoolBins]: cleared by the launcher
+    uint32_t* state;                     // [kBfPoolPasses + 1][nq][2]: the select state after every pass (row 0 is not used)
+    uint32_t* span_counts;               // [2][nq][n_carry + n_spans]: a block's keys below / equal to the threshold
+    const unsigned long long* carry_in;  // [nq][pool] key << 32 | id: the pool of the earlier chunks (not read when first)
+    const uint32_t* carry_n_in;          // [nq] its length
+    unsigned long long* carry_out;       // [nq][pool] ... with this chunk (not written when last); never the arrays carry_in names
+    uint32_t* carry_n_out;
+    uint64_t* out_ids;                   // [nq][pool]: the pool's ids, written on the last chunk (launch_bf_rerank_score's pool_ids)
+    uint32_t* out_counts;                // [nq] min(pool, candidates), written on the last chunk
+};
+hipError_t launch_bf_pool_rank(const BfPoolParams& p, hipStream_t s);
 // k_bf_train.hip: BruteForceRabitqIndex::train.  launch_bf_encode: k_encode's flat mode over P.nslots rotated rows (see
 // EncodeParams; P.t_row != null: the per-vector rescale factors of launch_rescale).  launch_bf_pack_ex: raw ex codes [nrows][D]
 // u8 -> the crate's ex_code_packed [nrows][D * ex_bits / 8] (ex_bits 2 or 6)

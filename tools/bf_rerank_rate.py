@@ -9,12 +9,16 @@ device), batches of 1024 page-locked host queries.  One process, under a time li
 Every leg is a host-buffer call, which ends in a stream synchronisation: one warm-up window, then the median of --windows windows
 of --calls calls each.  Legs, per pool of --pools: batch_search_raw at top_k := pool (the same select work, the comparison), then
 batch_search_exact_raw at top_k 10 with the training rows attached as f32 and as f16 (borrowed device tensors).  Recall@10 of the
-estimate-only top 10 and of every exact leg against a flat exact search (torch.cdist over the f32 rows, top 10)."""
+estimate-only top 10 and of every exact leg against a flat exact search (torch.cdist over the f32 rows, top 10).
+--pool-rule rank (profiles/bf_pool_rank/): every exact leg is timed under both pool rules, "heap"
+(rbq_bf_search_exact_batch) and "rank" (rbq_bf_search_exact_ranked_batch), their windows alternating in one loop, with the recall of
+each; the default, heap, is the run above."""
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 
@@ -44,12 +48,25 @@ def kernel_table(a):
     for raw, code in (("f32", 0), ("f16", 1)):
         k = rec["kernels"].get("k_bf_rerank_score<false, %d>" % code)
         if k:
-            k["raw_bytes_requested"] = sum(run["exact_calls_per_leg"] * run["batch"] * p * run["dim"] * (4 if raw == "f32" else 2) for p in run["pools"])
+            k["raw_bytes_requested"] = sum(len(run.get("pool_rules", ["heap"])) * run["exact_calls_per_leg"] * run["batch"] * p * run["dim"] * (4 if raw == "f32" else 2)
+                                           for p in run["pools"])
             k["raw_TB_per_s"] = round(k["raw_bytes_requested"] / (k["sum_us"] * 1e-6) / 1e12, 3)
     with open(a.out, "w") as f:
         json.dump(rec, f, indent=1)
         f.write("\n")
     print(json.dumps(rec))
+
+
+def alternating(fns, n_windows, calls):
+    """tools.bf_range_rate.windows for several legs at once, their windows taking turns: {name: seconds per call}"""
+    out = {name: [] for name in fns}
+    for w in range(n_windows + 1):
+        for name, fn in fns.items():
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                fn()
+            out[name].append((time.perf_counter() - t0) / calls)
+    return {name: {"median_s": statistics.median(t[1:]), "min_s": min(t[1:]), "max_s": max(t[1:])} for name, t in out.items()}
 
 
 def recall(ids, truth):
@@ -66,6 +83,7 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--calls", type=int, default=3)
     ap.add_argument("--seed", type=int, default=20261019)
+    ap.add_argument("--pool-rule", choices=["heap", "rank"], default="heap", help="rank: time every exact leg under both pool rules, alternately")
     ap.add_argument("--kernel-table", default=None, metavar="DIR", help="no run: tabulate the kernel trace under DIR (see kernel_table)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
@@ -88,15 +106,17 @@ def main():
     p10 = rq.BruteForceSearchParams(TOP_K)
     rec = {"tool": "bf_rerank_rate", "n": a.n, "dim": a.dim, "bits": a.bits, "metric": "l2", "batch": a.batch, "top_k": TOP_K, "pools": a.pools,
            "windows": a.windows, "calls": a.calls, "exact_calls_per_leg": (a.windows + 1) * a.calls + 1,
+           "pool_rules": ["heap", "rank"] if a.pool_rule == "rank" else ["heap"],
            "recall_at_10_estimate": recall(idx.batch_search_raw(q, p10)[0], truth)}
     stored = {"f32": x, "f16": x.half()}
     for pool in a.pools:
         rec["estimate_top_k_%d" % pool] = windows(lambda: idx.batch_search_raw(q, rq.BruteForceSearchParams(pool)), a.windows, a.calls)
         for raw, rows in stored.items():
             idx.set_rerank_vectors(rows)
-            leg = windows(lambda: idx.batch_search_exact_raw(q, p10, pool), a.windows, a.calls)
-            leg["recall_at_10"] = recall(idx.batch_search_exact_raw(q, p10, pool)[0], truth)
-            rec["exact_%s_pool_%d" % (raw, pool)] = leg
+            legs = alternating({r: (lambda r=r: idx.batch_search_exact_raw(q, p10, pool, pool_rule=r)) for r in rec["pool_rules"]}, a.windows, a.calls)
+            for r, leg in legs.items():  # (one rule: the windows of tools.bf_range_rate.windows)
+                leg["recall_at_10"] = recall(idx.batch_search_exact_raw(q, p10, pool, pool_rule=r)[0], truth)
+                rec["exact_%s_pool_%d%s" % (raw, pool, "" if r == "heap" else "_rank")] = leg
             idx.set_rerank_vectors(None)
     idx.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
